@@ -4,7 +4,7 @@ forward-backward LK, key-frame detect + stereo LK + triangulation) on MI355X,
 plus local-BA ms/iteration, against the HBM roofline, with the CPU oracle timed
 beside it.
 
-    python bench.py --gpus N --steps K --warmup W [--only leg[,leg...]]
+    python bench.py --gpus N --steps K --warmup W [--full | --only leg[,leg...]] [--dump-outputs DIR]
 
 One process per GPU (a launcher's WORLD_SIZE / RANK are honoured; without one,
 `--gpus N` starts the N rank processes itself).  A step = ONE KEY-FRAME PERIOD
@@ -21,9 +21,15 @@ streams and GPUs = S * KF_EVERY * K / seconds.  N>1 = N independent replicas
 data path.  Rank 0 prints ONE compact JSON line (< 4 KB) as its LAST stdout line;
 the full record goes to bench_detail.json and stderr.
 
-Legs (`--only`, for profiling one population of kernels at a time; default all):
+A plain run measures the headline alone: set-up, warm-up, the K timed steps, the
+line.  `--full` runs every leg below -- the other workloads, precisions and
+configurations, the rooflines (with their own runs of the build), the CPU baseline
+and the oracle checks of the timed run.  `--only` runs the named legs the way
+`--full` does (for profiling one population of kernels at a time):
   single, tolerance, headline, tolbatch, ingest, sweep, host_protocol, configs,
   ba, ba_sharded, pose, cpu
+`--dump-outputs DIR` writes what the headline's last timed step left for its
+caller as DIR/<name>.npy (float64; dump_outputs below).
 """
 import argparse
 import json
@@ -114,12 +120,46 @@ def ba_windows(syn):
     return w
 
 
+PLANE_SAMPLE = 1 << 16          # elements kept per plane and level in --dump-outputs (levels 0 and 1 of a 370 x 1226 frame are larger)
+
+
+def dump_outputs(d, head):
+    """--dump-outputs: what the headline loop's last frame step left for its caller -- every stream's keypoint list (positions,
+    3-D flags, triangulated points, ids) and the S list lengths -- and all six planes of every level of the current left pyramids
+    of the snapshot streams (0 and S - 1), each plane a fixed, seeded sample of PLANE_SAMPLE elements where it is larger (the
+    planes of all S streams are GBs).  Float64 .npy files, at most 64 MB together."""
+    lists = head["lists"]
+    arrays = {"keypoint_counts": np.array([len(k["yx"]) for k in lists], dtype=np.float64),
+              "keypoints_yx": np.concatenate([k["yx"] for k in lists]),
+              "keypoints_is_3d": np.concatenate([k["is_3d"] for k in lists]).astype(np.float64),
+              # a keypoint's point is defined once it is 3-D (fresh detections carry whatever the slot held)
+              "keypoints_xyz": np.concatenate([np.where(k["is_3d"][:, None], k["xyz"], 0.0) for k in lists]),
+              "keypoint_ids": np.concatenate([k["ids"] for k in lists]).astype(np.float64)}
+    for s_, sn in sorted(head["snapshot"].items()):
+        for (nm, l), a in sorted(sn["planes"].items()):
+            a = np.ravel(a)
+            if a.size > PLANE_SAMPLE:
+                a = a[np.sort(np.random.default_rng(l).choice(a.size, PLANE_SAMPLE, replace=False))]
+            arrays[f"left_pyramid_s{s_}_{nm}_l{l}"] = np.asarray(a, dtype=np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= 64e6, total
+    os.makedirs(d, exist_ok=True)
+    if not os.path.exists(os.path.join(d, ".gitignore")):            # a dump inside a checkout stays out of git status, wherever it is
+        with open(os.path.join(d, ".gitignore"), "w") as f:
+            f.write("*\n")
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=60, help="timed steps; one step = one key-frame period (5 frames) of each of the S streams")
     ap.add_argument("--warmup", type=int, default=6)
-    ap.add_argument("--only", type=str, default="", help="comma-separated legs to run (default: all): " + ", ".join(LEGS))
+    ap.add_argument("--full", action="store_true", help="run every leg (default: the headline alone, without its rooflines)")
+    ap.add_argument("--only", type=str, default="", help="comma-separated legs to run as --full runs them: " + ", ".join(LEGS))
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the headline's last step computed "
+                    "as DIR/<name>.npy (float64, <= 64 MB in all; identical inputs for identical arguments)")
     ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg (and the oracle parity checks that live in it)")
     ap.add_argument("--no-ba", action="store_true", help="skip the BA and pose measurements")
     ap.add_argument("--streams", type=int, default=128, help="S: independent stereo streams per GPU advancing in lock-step (one batch of S frames per frame step); "
@@ -128,10 +168,13 @@ def main():
     ap.add_argument("--no-sweep", action="store_true", help="skip the streams-per-GPU sweep legs (S = 32 / 64 / 96 at the default 128)")
     ap.add_argument("--no-configs", action="store_true", help="skip the other BASELINE shapes (kitti00_2000, euroc_mono, fhd_4000)")
     args = ap.parse_args()
-    legs = set(x for x in args.only.split(",") if x) or set(LEGS)
+    full = args.full or bool(args.only)
+    legs = set(x for x in args.only.split(",") if x) or (set(LEGS) if args.full else {"headline"})
     unknown = legs - set(LEGS)
     if unknown:
         raise SystemExit(f"unknown leg(s) {sorted(unknown)}; known: {LEGS}")
+    if args.dump_outputs and "headline" not in legs:
+        raise SystemExit("--dump-outputs writes the headline's outputs: the headline leg must run")
     if args.no_cpu: legs.discard("cpu")
     if args.no_ba: legs -= {"ba", "ba_sharded", "pose"}
     if args.no_tolerance: legs.discard("tolerance")
@@ -424,9 +467,15 @@ def main():
     #      decoder's 8-bit images ----
     head = None
     tol_snapshot = None
+    dump = args.dump_outputs is not None and rank == 0
     if "headline" in legs:
-        head = run_lockstep_kpset(slam, torch, local_rank, wl, args.steps, args.warmup, world, dist, dev, "host_u8", snapshot=[0, S - 1])
+        # the snapshot (lists + planes of two streams, read after the timed loop) feeds the oracle checks of --full and --dump-outputs
+        head = run_lockstep_kpset(slam, torch, local_rank, wl, args.steps, args.warmup, world, dist, dev, "host_u8",
+                                  snapshot=[0, S - 1] if full or dump else None, lists=dump)
         leg_done("headline")
+        if dump:
+            dump_outputs(args.dump_outputs, head)
+            del head["lists"]
         if world > 1:
             # every rank's own frame rate over its own clock (`value` = all frames over the SLOWEST rank's time, as the contract asks)
             per_rank = [None] * world
@@ -443,10 +492,6 @@ def main():
                                    "per_rank_values": per_rank, "config": {"workload": "KITTI-05-shaped stereo 370x1226 @1000 kpts (BASELINE configs[1])", "streams_per_gpu": S}}, f)
                 except OSError:
                     pass
-        rows_us, serial_us, isolated_us = kernel_spans(slam, torch, local_rank, wl, dev)
-        pb = S * pyramid_bytes(H, W, levels)
-        build_ms = head["pyramid_build_ms"]["mean"]
-        rb_bytes = S * iir_rows_bytes(H, W, levels) / (levels + 1)
         out.update({
             "value": head["value"], "ms_per_step": head["ms_per_step"],
             "config": {"workload": "KITTI-05-shaped stereo streams 370x1226, 1000 kpts/frame, key-frame every 5th frame: "
@@ -469,6 +514,14 @@ def main():
                        "tracked_kpts_per_frame": head["tracked_kpts_per_frame"], "host_wait_ms_per_frame": head["host_wait_ms_per_frame"],
                        "window_size": params.window_size, "pyramid_levels": levels,
                        "cull_fraction_per_keyframe": CULL_FRACTION},
+        })
+    if "headline" in legs and full:
+        # the rooflines: the build's per-kernel spans and the graph replay alone are runs of their own, after the timed loop
+        rows_us, serial_us, isolated_us = kernel_spans(slam, torch, local_rank, wl, dev)
+        pb = S * pyramid_bytes(H, W, levels)
+        build_ms = head["pyramid_build_ms"]["mean"]
+        rb_bytes = S * iir_rows_bytes(H, W, levels) / (levels + 1)
+        out.update({
             # the dominant stage (>= 60 % of the device time of a step): the LK pyramid update of the S images of a frame step.  algorithmic
             # bytes = SURVEY 8(d): 7 planes x 8 B x sum_l H_l W_l per image; duration = hipEvents around the build on the stream it runs on, in
             # the timed region (one hipGraph replay of the ~20 kernels of the build), tracking kernels running beside it

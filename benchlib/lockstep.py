@@ -174,7 +174,7 @@ def make_workload(slam, syn, name, seed=0, streams=None):
 
 
 def run_lockstep_kpset(slam, torch, local_rank, wl, periods, warm_periods, world, dist, dev, ingest,
-                       hook=None, seed=1234, pose=False, record=None, snapshot=None, diag=None, ba=None):
+                       hook=None, seed=1234, pose=False, record=None, snapshot=None, diag=None, ba=None, lists=False):
     """The headline loop: S streams in lock-step, keypoints resident in HBM (slam_kpset_*), no host list work
     between the calls of a frame; the host sees the S list lengths once per frame.  Timed: `periods` key-frame periods
     (KF_EVERY frames of every stream each, the first a key-frame) after `warm_periods` untimed ones.
@@ -190,7 +190,8 @@ def run_lockstep_kpset(slam, torch, local_rank, wl, periods, warm_periods, world
     record (dict, optional): replay mode for the parity check -- runs record["frame_steps"] frames from the empty lists, no
       warm-up, and appends per frame {"i", "kf", "shift" (S, 2), "cull" (S, cap) uint8 or None} to record["steps"].
     snapshot (list of stream ids, optional): after the last frame, download those streams' keypoint lists and all planes of
-      their current left pyramids into the result (the cpu_baseline leg compares them with the oracle)."""
+      their current left pyramids into the result (the cpu_baseline leg compares them with the oracle).
+    lists (bool): after the last frame, download every stream's keypoint list into res["lists"] (bench.py --dump-outputs)."""
     import ctypes as C
     S, H, W, params, extractor, camt, disparity = wl["S"], wl["H"], wl["W"], wl["params"], wl["extractor"], wl["camt"], wl["disparity"]
     left, right, flows, stereo = wl["left"], wl["right"], wl["flows"], wl["stereo"]
@@ -501,6 +502,8 @@ def run_lockstep_kpset(slam, torch, local_rank, wl, periods, warm_periods, world
                                    for nm in ("layers", "Iy", "Ix", "Iyy", "Ixx", "Iyx")}}
         res["snapshot"] = snap
         res["seq"] = seq; res["period"] = period; res["cap"] = cap
+    if lists:
+        res["lists"] = [ks.download(s_, ctx=ctx) for s_ in range(S)]
     peek("run_lockstep_kpset: after the loop")
     for c in (ctx, ctx_pyr, ctx_right, ctx_copy):
         c.synchronize()

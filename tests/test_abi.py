@@ -26,7 +26,10 @@ def test_library_exports_every_declared_symbol():
     import ctypes
     import slam_jl_amd
     assert os.path.exists(slam_jl_amd.LIB_PATH), "build first: python -c 'import __graft_entry__ as g; g.build()'"
-    lib = ctypes.CDLL(slam_jl_amd.LIB_PATH)
+    # the package loads the library first, bound to PyTorch's HIP runtime (_lib.load): a bare dlopen before torch binds it to the
+    # system runtime instead, and every later GPU test of the same process would meet two runtimes and no device
+    slam_jl_amd._lib.load()
+    lib = ctypes.CDLL(slam_jl_amd.LIB_PATH)                 # the same handle: every declared name looked up, not only the binding table's
     for name in _declared():
         assert hasattr(lib, name), f"{name} declared in slamhip.h but not exported"
 
