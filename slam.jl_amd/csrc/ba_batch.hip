@@ -103,6 +103,7 @@ struct BARes { size_t off_state, off_theta, off_outl; };
 __global__ __launch_bounds__(256) void k_results_b(const BAWin *tab, const BARes *rtab, char *res)
 {
     const BAWin w = ba_win(tab);
+    if (w.pad == 2) return;                                  // rejected at set-up (slam_local_ba_batch reports SLAM_ERR_ARG): nothing to pack
     const BADev &d = w.d;
     LMState *s = d.st;
     const BARes r = rtab[blockIdx.y];
@@ -265,10 +266,12 @@ int slam_local_ba_batch(slam_ctx *ctx, int S, const double *cams, const int32_t 
         auto emit_window = [&](int zz) {
             if (zz >= NB) return;
             const int k = zz; BAPlan &q = pl[batch[k]];
-            if (ba_emit(q, A + up[k], A + zero_base + ze[k], A + work_base + wk[k], stage + up[k])) return;
-            slam_ba *b = q.ba; b->device = ctx->device; b->owns_arena = false; b->arena = A;
             BAWin &w = tab_h[k];
             memset(&w, 0, sizeof w);
+            BARes &r = rtab_h[k];
+            r.off_state = res_base + rs[k]; r.off_theta = r.off_state + al(sizeof(LMState)); r.off_outl = r.off_theta + al((6 * (size_t)q.P + 3 * (size_t)q.M) * 8 + 8);
+            if (ba_emit(q, A + up[k], A + zero_base + ze[k], A + work_base + wk[k], stage + up[k])) { w.pad = 2; return; }    // rejected (q.err): skipped by every kernel
+            slam_ba *b = q.ba; b->device = ctx->device; b->owns_arena = false; b->arena = A;
             w.d = b->d;
             const int n = w.d.n, Ps = b->pspan > 0 ? b->pspan : q.P, p0 = b->pspan > 0 ? b->p0 : 0, hb = std::min(std::max(b->hb, 1), Ps - 1);
             const double *red = b->reduce;
@@ -286,8 +289,6 @@ int slam_local_ba_batch(slam_ctx *ctx, int S, const double *cams, const int32_t 
                 while (kk < q.M && 2 * (2L * q.start[kk] + 13L * pfs[kk]) < total) kk++;
                 w.ksplit = std::min(std::max(kk, 1), q.M - 1);
             }
-            BARes &r = rtab_h[k];
-            r.off_state = res_base + rs[k]; r.off_theta = r.off_state + al(sizeof(LMState)); r.off_outl = r.off_theta + al((6 * (size_t)q.P + 3 * (size_t)q.M) * 8 + 8);
         };
         bool early_sent = false;
         if (n_early > 0) {
@@ -303,7 +304,8 @@ int slam_local_ba_batch(slam_ctx *ctx, int S, const double *cams, const int32_t 
             BAPlan &q = pl[batch[k]];
             if (q.err) { st_code[batch[k]] = q.err; if (!status) return slam_fail(ctx, q.err, "slam_local_ba_batch: window %d: %s", batch[k], q.msg); }
         }
-        // a window whose set-up failed in ba_emit (a point observed twice by one pose) stays in the table as an inert entry: no groups, no blocks
+        // a window whose set-up failed in ba_emit (a point observed twice by one pose) stays in the table with pad = 2: every batch kernel, k_results_b
+        // included, returns at once for it, it is in no list of k_ba_window's and its (zeroed) table entry is never read for a launch size
         // windows one workgroup can keep to itself (k_ba_window): <= 5 free poses, consecutive; the others take the launch-per-phase kernels
         static const bool no_bw = getenv("SLAMHIP_NO_BA_WINDOW") != nullptr;
         std::vector<int> small_list;
@@ -324,9 +326,8 @@ int slam_local_ba_batch(slam_ctx *ctx, int S, const double *cams, const int32_t 
         for (int k = 0; k < NS_; k++) list_h[k] = small_list[k];
         int gx_obs = 1, gx_grp = 1, gx_red = 1, max_ob = 0, max_hb = 0; size_t lds_sg = 0, lds_band = 0;
         for (int k = 0; k < NB; k++) {
-            BAPlan &q = pl[batch[k]]; BAWin &w = tab_h[k];
-            if (q.err) { w.d.ngrp = 0; w.nb_obs = 0; w.n_red = 0; w.d.O = 0; w.d.M = 0; w.d.n = 0; w.B.nb = 0; continue; }
-            if (w.pad) continue;
+            const BAWin &w = tab_h[k];
+            if (w.pad) continue;                                   // (k_ba_window's, or rejected at set-up)
             gx_obs = std::max(gx_obs, w.nb_obs); gx_grp = std::max(gx_grp, w.d.ngrp); gx_red = std::max(gx_red, w.n_red);
             max_ob = std::max(max_ob, w.d.sg_ob); max_hb = std::max(max_hb, w.d.whb);
             lds_band = std::max(lds_band, (size_t)w.B.lds_bytes);
@@ -446,7 +447,10 @@ int slam_local_ba_batch(slam_ctx *ctx, int S, const double *cams, const int32_t 
         }
         if (e0) (void)hipEventDestroy(e0);
         if (e1) (void)hipEventDestroy(e1);
-        if (e != hipSuccess) return slam_fail(ctx, SLAM_ERR_HIP, "slam_local_ba_batch: %s", hipGetErrorString(e));
+        if (e != hipSuccess) {
+            if (st2) (void)hipStreamSynchronize(st2);              // (work may be in flight on the second stream: it reads the arena the next call reuses)
+            return slam_fail(ctx, SLAM_ERR_HIP, "slam_local_ba_batch: %s", hipGetErrorString(e));
+        }
         const auto tw3 = std::chrono::steady_clock::now();
         // results -> the caller's arrays (its pose order, its observation order); a failed factorisation leaves a window's arrays untouched
         parallel([&](int zz) {

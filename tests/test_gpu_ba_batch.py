@@ -178,6 +178,36 @@ def test_batch_reports_a_bad_window_and_solves_the_others(slam, syn):
     assert np.array_equal(caches[1].theta, bad["theta0"])                                          # untouched
 
 
+@pytest.mark.parametrize("n_good", [4, 150])
+def test_batch_reports_a_window_rejected_at_set_up_and_solves_the_others(slam, syn, n_good):
+    """a map point observed twice by one FREE pose is found while the window is staged (ba_emit), after the batch was laid out: the window
+    comes back as SLAM_ERR_ARG with its arrays untouched and the windows around it equal single calls -- in a small batch (k_ba_window
+    on two workgroups) and in one with more than 128 reference-shaped windows (k_ba_window on one workgroup per window); every tenth good
+    window takes the launch-per-phase kernels"""
+    good = [syn.ba_scene(P=8, M=300, seed=320 + z % 5) if z % 10 == 0 else syn.ba_scene(P=25, M=200, seed=300 + z % 7, n_const=20) for z in range(n_good)]
+    bad = syn.ba_scene(P=25, M=200, seed=330, n_const=20)
+    pose_ids, point_ids = bad["pose_ids"].copy(), bad["point_ids"].copy()
+    i = int(np.where(bad["theta_const"][pose_ids - 1] == 0)[0][5]); j = i + 1 if point_ids[i + 1] == point_ids[i] else i - 1
+    pose_ids[j] = pose_ids[i]                                                      # same point, same free pose twice
+    bad = dict(bad, pose_ids=pose_ids, point_ids=point_ids)
+    sc = good[:n_good // 2] + [bad] + good[n_good // 2:]
+    zb = n_good // 2
+    b = slam.BABatch([_cache(slam, s) for s in sc], [s["cam"] for s in sc])
+    status = b.solve()
+    assert status[zb] == -1 and not np.delete(status, zb).any(), status          # SLAM_ERR_ARG
+    th, ol, _ = b.window(zb)
+    assert np.array_equal(th, bad["theta0"]) and not ol.any()                     # untouched
+    for z, s in enumerate(sc):
+        if z == zb:
+            continue
+        ref = _cache(slam, s); slam.bundle_adjustment_(ref, s["cam"])
+        th, ol, st = b.window(z)
+        assert np.array_equal(ol, ref.outliers), z
+        assert st["iters_pass1"] == ref.stats["iters_pass1"] and st["iters_pass2"] == ref.stats["iters_pass2"], z
+        assert abs(st["ssr_final"] - ref.stats["ssr_final"]) <= 1e-8 * ref.stats["ssr_final"], z
+        assert np.abs(th - ref.theta).max() <= 1e-6 * max(1.0, np.abs(ref.theta).max()), z
+
+
 def test_batch_calls_from_two_threads_at_once(slam, syn):
     """two estimator threads, each with its own context, call slam_local_ba_batch concurrently (the host half shares one worker pool):
     both get what a serial call gives"""
