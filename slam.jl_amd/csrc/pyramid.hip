@@ -1313,6 +1313,251 @@ __global__ __launch_bounds__(CF_MAXW * 64) void k_cum_fused(PlaneSet ps, int H, 
     if (SEG && w == 0 && seg > 0 && lane == 0) __hip_atomic_store(xf_in, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // every block consumed: clear for the next launch
 }
 
+// k_rows_cum: the dim-2 IIR stage of the three product planes AND their integral images in one launch, bit-identical to
+// k_iir_rows_ck followed by k_cum_fused<false> (batches of >= 8 images, planes <= CF_MAXW bands).  One workgroup owns a plane,
+// wave w the 64-row band [64 w, 64 w + 63], lane = row (as k_iir_rows_ck).  Per line:
+//   (A) forward, read only: the causal recurrence; its state is kept every CK_B samples (k_iir_rows_ck's pass A);
+//   (B) backward, read only: per block, right to left, the causal values are recomputed from the checkpoint and the anticausal
+//       recurrence runs over them; its state ENTERING each block (from the right) replaces the causal checkpoint of that block,
+//       which pass B has just consumed.  Nothing is written to the plane;
+//   (C) forward, read + write: per block, left to right, the causal recurrence continues in registers (the running state the
+//       checkpoints were taken from) and the anticausal one runs back across the block from its stored entry state: the finished
+//       block, by the same operations on the same states as k_iir_rows_ck.  It goes through the wave's LDS block in halves of
+//       RC_CW columns: lanes = columns add each column's 64 rows onto the column sums handed down from the band above (LDS,
+//       ready / consumed counters as in k_cum_fused), lanes = rows add the half's column sums onto the row's running sum (a
+//       register), and the integral image is stored once, in place.
+// Per plane 3 R + 1 W (+ 4 checkpoint passes of 3 / CK_B plane) instead of k_iir_rows_ck + k_cum_fused's 3 R + 2 W.  Every sum is
+// formed as k_cum_cols then k_cum_rows form it: the first term of a running sum is added to -0.0, which returns it unchanged.
+// Lanes below the plane (y >= H, last band) run the recurrences of row H - 1 and store nothing; their column sums only reach
+// rows that do not exist.
+#define RC_CW 16                         // columns per LDS round (half a CK_B block): 8.5 KB per band -> two 6..8-band workgroups per CU
+#define RC_LDS_DOUBLES (RC_CW * CF_LS + 2 * RC_CW)      // per wave: the block, then the double-buffered column carries it publishes
+__global__ __launch_bounds__(CF_MAXW * 64) void k_rows_cum(PlaneSet ps, int H, int W, int P, IIRPair cf, double *ck)
+{
+    extern __shared__ __attribute__((aligned(16))) double rc_lds[];
+    __shared__ int s_ready[CF_MAXW], s_done[CF_MAXW];
+    const int pl = blockIdx.y, lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    typedef __attribute__((address_space(3))) double ldsd;
+    typedef __attribute__((address_space(3))) v2d ldsv2;
+    ldsd *Cb = (ldsd *)rc_lds + (size_t)w * RC_LDS_DOUBLES;
+    ldsd *carry_out = Cb + RC_CW * CF_LS;                         // published by this wave
+    const ldsd *carry_in = carry_out - RC_LDS_DOUBLES;            // published by wave w - 1
+    auto flag_ld = [](int *f) { return __hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); };
+    auto flag_st = [](int *f, int v) { __hip_atomic_store(f, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); };
+    if (lane == 0) { flag_st(&s_ready[w], 0); flag_st(&s_done[w], 0); }
+    __syncthreads();
+    const int y = w * 64 + lane;
+    const bool live = y < H;
+    // every global access is (wave-uniform base) + (32-bit lane offset): one address register for all the loads and stores of a block
+    const size_t nlines = (size_t)gridDim.z * gridDim.y * blockDim.x;
+    ck += ((size_t)blockIdx.z * gridDim.y + pl) * blockDim.x;
+    const unsigned lid = threadIdx.x;
+    double *plane = ps_plane(ps, pl);
+    const unsigned yo = (unsigned)(live ? y : H - 1);
+    double *p = plane + yo;
+    const long s = P;
+    const int n = W;
+    const IIRCoef &k = ps_coef(ps, pl) == 0 ? cf.c[0] : cf.c[1];
+    const bool fill0 = ps_fill0(ps, pl);
+    const double a1 = k.a1, a2 = k.a2, a3 = k.a3, scale = k.scale;
+    const double x0 = p[0];
+    const double iminus = fill0 ? 0.0 : x0, iplus = fill0 ? 0.0 : p[(long)(n - 1) * s];
+    const double uminus = iminus / k.inv1masum;
+    const double o0 = ((x0 + a1 * uminus) + a2 * uminus) + a3 * uminus;
+    const double o1 = ((p[s] + a1 * o0) + a2 * uminus) + a3 * uminus;
+    const double o2 = ((p[2 * s] + a1 * o1) + a2 * o0) + a3 * uminus;
+    const int m = n - 6, nb = (m + CK_B - 1) / CK_B;
+    double w3 = o0, w2 = o1, w1 = o2;
+    double cur[CK_B], nxt[CK_B];
+    auto load_x = [&](int j, double *buf) {
+        const int c0 = 3 + j * CK_B, len = n - c0;
+        if (len >= CK_B) {
+#pragma unroll
+            for (int e = 0; e < CK_B; e++) buf[e] = RCK_LD(plane + (size_t)(c0 + e) * P + yo);
+        } else {
+#pragma unroll
+            for (int e = 0; e < CK_B; e++) buf[e] = e < len ? plane[(size_t)(c0 + e) * P + yo] : 0.0;
+        }
+    };
+    // ---- pass A (k_iir_rows_ck's) ----
+    const int nfull = (n - 3) / CK_B, rem = (n - 3) - nfull * CK_B;
+    load_x(0, cur);
+    for (int j = 0; j < nfull; j++) {
+        load_x(j + 1, nxt);
+        if (j > 0 && j < nb) { double *c = ck + ((size_t)j * 3) * nlines + lid; CK_ST(c, w1); CK_ST(c + nlines, w2); CK_ST(c + 2 * nlines, w3); }
+#pragma unroll
+        for (int e = 0; e < CK_B; e++) { const double t = ((cur[e] + a1 * w1) + a2 * w2) + a3 * w3; w3 = w2; w2 = w1; w1 = t; }
+#pragma unroll
+        for (int e = 0; e < CK_B; e++) cur[e] = nxt[e];
+    }
+    {
+        if (nfull > 0 && nfull < nb) { double *c = ck + ((size_t)nfull * 3) * nlines + lid; CK_ST(c, w1); CK_ST(c + nlines, w2); CK_ST(c + 2 * nlines, w3); }
+#pragma unroll
+        for (int e = 0; e < CK_B; e++)
+            if (e < rem) { const double t = ((cur[e] + a1 * w1) + a2 * w2) + a3 * w3; w3 = w2; w2 = w1; w1 = t; }
+    }
+    const bool have_last = nfull == nb - 1;
+    const double uplus = iplus / k.inv1masum, vplus = uplus / k.inv1mbsum;
+    const double d0 = w1 - uplus, d1 = w2 - uplus, d2 = w3 - uplus;
+    const double vr0 = ((k.M[0] * d0 + k.M[1] * d1) + k.M[2] * d2) + vplus;
+    const double vr1 = ((k.M[3] * d0 + k.M[4] * d1) + k.M[5] * d2) + vplus;
+    const double vr2 = ((k.M[6] * d0 + k.M[7] * d1) + k.M[8] * d2) + vplus;
+    const double vA = vr0;
+    const double vB = ((w2 + a1 * vA) + a2 * vr1) + a3 * vr2;
+    const double vC = ((w3 + a1 * vB) + a2 * vA) + a3 * vr1;
+    double v1 = vC, v2 = vB, v3 = vA;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");   // own checkpoints visible
+    // ---- pass B: blocks nb-1 .. 1 as k_iir_rows_ck's pass B without the stores; slot j <- anticausal state entering block j ----
+    double f1n = 0, f2n = 0, f3n = 0, f1 = 0, f2 = 0, f3 = 0;
+    auto load_ck = [&](int j, double &g1, double &g2, double &g3) {
+        if (j > 0) { const double *c = ck + ((size_t)j * 3) * nlines + lid; g1 = CK_LD(c); g2 = CK_LD(c + nlines); g3 = CK_LD(c + 2 * nlines); }
+        else { g1 = o2; g2 = o1; g3 = o0; }
+    };
+    auto store_ack = [&](int j) { double *c = ck + ((size_t)j * 3) * nlines + lid; CK_ST(c, v1); CK_ST(c + nlines, v2); CK_ST(c + 2 * nlines, v3); };
+    if (nb > 1) {
+        const int j = nb - 1, len = m - j * CK_B;
+        if (!have_last) load_x(j, cur);
+        load_ck(j, f1, f2, f3);
+        load_x(j - 1, nxt); load_ck(j - 1, f1n, f2n, f3n);
+#pragma unroll
+        for (int e = 0; e < CK_B; e++)
+            if (e < len) { const double t = ((cur[e] + a1 * f1) + a2 * f2) + a3 * f3; f3 = f2; f2 = f1; f1 = t; cur[e] = t; }
+        store_ack(j);                                             // (after the causal sweep: slot j's causal checkpoint has been read)
+#pragma unroll
+        for (int e = CK_B - 1; e >= 0; e--)
+            if (e < len) { const double t = ((cur[e] + a1 * v1) + a2 * v2) + a3 * v3; v3 = v2; v2 = v1; v1 = t; }
+#pragma unroll
+        for (int e = 0; e < CK_B; e++) cur[e] = nxt[e];
+        f1 = f1n; f2 = f2n; f3 = f3n;
+    }
+    for (int j = nb - 2; j >= 1; j--) {
+        load_x(j - 1, nxt); load_ck(j - 1, f1n, f2n, f3n);
+#pragma unroll
+        for (int e = 0; e < CK_B; e++) { const double t = ((cur[e] + a1 * f1) + a2 * f2) + a3 * f3; f3 = f2; f2 = f1; f1 = t; cur[e] = t; }
+        store_ack(j);
+#pragma unroll
+        for (int e = CK_B - 1; e >= 0; e--) { const double t = ((cur[e] + a1 * v1) + a2 * v2) + a3 * v3; v3 = v2; v2 = v1; v1 = t; }
+#pragma unroll
+        for (int e = 0; e < CK_B; e++) cur[e] = nxt[e];
+        f1 = f1n; f2 = f2n; f3 = f3n;
+    }
+    if (nb > 0) store_ack(0);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    // ---- pass C ----
+    double rcarry = -0.0;                                         // this lane's row: running sum along x
+    int hk = 0;                                                   // halves handed down so far
+    // the LDS block holds this lane's row values in columns [0, wc) of x0 ..: integral image of those columns -> the plane
+    auto cum_half = [&](int x0c, int wc) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier();
+        double acc = -0.0;
+        if (w > 0) {
+            while (flag_ld(&s_ready[w - 1]) <= hk) __builtin_amdgcn_s_sleep(1);
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+            if (lane < RC_CW) acc = carry_in[(hk & 1) * RC_CW + lane];
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+            if (lane == 0) flag_st(&s_done[w], hk + 1);
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier();
+        if (lane < wc) {                                          // lane = column: 64 rows in groups of 16
+            ldsd *c = Cb + lane * CF_LS;
+#pragma unroll
+            for (int g = 0; g < 4; g++) {
+                double v[16];
+#pragma unroll
+                for (int j = 0; j < 8; j++) { const v2d q = *(const ldsv2 *)(c + 16 * g + 2 * j); v[2 * j] = q.x; v[2 * j + 1] = q.y; }
+#pragma unroll
+                for (int e = 0; e < 16; e++) { acc = acc + v[e]; v[e] = acc; }
+#pragma unroll
+                for (int j = 0; j < 8; j++) { const v2d t2 = {v[2 * j], v[2 * j + 1]}; *(ldsv2 *)(c + 16 * g + 2 * j) = t2; }
+            }
+        }
+        if (w + 1 < nw) {                                         // the bottom row's sums to the band below
+            while (flag_ld(&s_done[w + 1]) + 2 <= hk) __builtin_amdgcn_s_sleep(1);
+            if (lane < RC_CW) carry_out[(hk & 1) * RC_CW + lane] = acc;
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+            if (lane == 0) flag_st(&s_ready[w], hk + 1);
+        }
+        hk++;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier();
+        double *q = plane + (size_t)x0c * P;                      // lane = row
+        if (wc == RC_CW) {
+            double r[RC_CW];
+#pragma unroll
+            for (int j = 0; j < RC_CW; j++) r[j] = Cb[j * CF_LS + lane];
+#pragma unroll
+            for (int j = 0; j < RC_CW; j++) { rcarry = rcarry + r[j]; r[j] = rcarry; }
+            if (live) {
+#pragma unroll
+                for (int j = 0; j < RC_CW; j++) RCK_ST(q + (size_t)j * P + yo, r[j]);
+            }
+        } else {
+            for (int j = 0; j < wc; j++) { rcarry = rcarry + Cb[j * CF_LS + lane]; if (live) q[(size_t)j * P + yo] = rcarry; }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier();
+    };
+    auto put = [&](int col, double v) { Cb[col * CF_LS + lane] = v; };
+    double pv0 = 0, pv1 = 0, pv2 = 0;                             // the finished samples of the block's first 3 columns of the next half pair
+    f1 = o2; f2 = o1; f3 = o0;                                    // causal state before block 0 (continued across blocks)
+    if (nb > 0) {
+        load_x(0, cur);
+        { const double *c = ck + lid; v1 = CK_LD(c); v2 = CK_LD(c + nlines); v3 = CK_LD(c + 2 * nlines); }
+    }
+    for (int j = 0; j < nb; j++) {
+        const int len = m - j * CK_B;                             // >= CK_B except in the last block
+        double g1n = 0, g2n = 0, g3n = 0;
+        if (len >= CK_B) {
+#pragma unroll
+            for (int e = 0; e < CK_B; e++) { const double t = ((cur[e] + a1 * f1) + a2 * f2) + a3 * f3; f3 = f2; f2 = f1; f1 = t; cur[e] = t; }
+#pragma unroll
+            for (int e = CK_B - 1; e >= 0; e--) { const double t = ((cur[e] + a1 * v1) + a2 * v2) + a3 * v3; v3 = v2; v2 = v1; v1 = t; cur[e] = t * scale; }
+        } else {
+#pragma unroll
+            for (int e = 0; e < CK_B; e++)
+                if (e < len) { const double t = ((cur[e] + a1 * f1) + a2 * f2) + a3 * f3; f3 = f2; f2 = f1; f1 = t; cur[e] = t; }
+#pragma unroll
+            for (int e = CK_B - 1; e >= 0; e--)
+                if (e < len) { const double t = ((cur[e] + a1 * v1) + a2 * v2) + a3 * v3; v3 = v2; v2 = v1; v1 = t; cur[e] = t * scale; }
+        }
+        if (j == 0) {                                             // i = 2, 1, 0 from the forward values o2, o1, o0
+            double t = ((o2 + a1 * v1) + a2 * v2) + a3 * v3; v3 = v2; v2 = v1; v1 = t; pv2 = t * scale;
+            t = ((o1 + a1 * v1) + a2 * v2) + a3 * v3; v3 = v2; v2 = v1; v1 = t; pv1 = t * scale;
+            t = ((o0 + a1 * v1) + a2 * v2) + a3 * v3; pv0 = t * scale;
+        }
+        if (j + 1 < nb) {                                         // next block's inputs and anticausal entry state, in flight during the sums
+            load_x(j + 1, nxt);
+            const double *c = ck + ((size_t)(j + 1) * 3) * nlines + lid; g1n = CK_LD(c); g2n = CK_LD(c + nlines); g3n = CK_LD(c + 2 * nlines);
+        }
+        const int x0 = j * CK_B;                                  // this block's half pair: columns [x0, x0 + 32) = pv0..2, cur[0..28]
+        if (j + 1 < nb) {
+            put(0, pv0); put(1, pv1); put(2, pv2);
+#pragma unroll
+            for (int e = 0; e < RC_CW - 3; e++) put(3 + e, cur[e]);
+            cum_half(x0, RC_CW);
+#pragma unroll
+            for (int e = RC_CW - 3; e < CK_B - 3; e++) put(e + 3 - RC_CW, cur[e]);
+            cum_half(x0 + RC_CW, RC_CW);
+            pv0 = cur[CK_B - 3]; pv1 = cur[CK_B - 2]; pv2 = cur[CK_B - 1];
+        } else {
+            // the last block (1 .. CK_B samples): pv0..2, cur[0 .. len), then the right-boundary samples n-3 .. n-1 (from slot nb-1's state) = len + 6 columns
+            const double *c = ck + ((size_t)j * 3) * nlines + lid;
+            const double t0 = CK_LD(c) * scale, t1 = CK_LD(c + nlines) * scale, t2 = CK_LD(c + 2 * nlines) * scale;
+            const int tot = len + 6;
+            for (int h = 0; h * RC_CW < tot; h++) {
+                const int lo = h * RC_CW;
+                auto putc = [&](int col, double v) { if (col >= lo && col < lo + RC_CW) put(col - lo, v); };
+                putc(0, pv0); putc(1, pv1); putc(2, pv2);
+#pragma unroll
+                for (int e = 0; e < CK_B; e++) if (e < len) putc(3 + e, cur[e]);
+                putc(len + 3, t0); putc(len + 4, t1); putc(len + 5, t2);
+                cum_half(x0 + lo, min(RC_CW, tot - lo));
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < CK_B; e++) cur[e] = nxt[e];
+        v1 = g1n; v2 = g2n; v3 = g3n;
+    }
+}
+
 // ---- tolerance mode ("fast", mode 3): parallel recurrences -------------------------
 // The exact kernels above are bound by the dependent f64 chain: 68 cycles per IIR
 // step x line length (measured, scripts/ubench/dep_chain.hip), on the few CUs that a
@@ -2240,6 +2485,31 @@ static void launch_level(slam_ctx *ctx, slam_pyr *p, int mode, const IIRPair &cf
         const bool rows_resize = ck_rows && has_next && (H & 1) == 0 && !no_rows_resize;
         RowResize rz = {};
         if (rows_resize) { rz.dst = nextL; rz.Hd = p->H[l + 1]; rz.Wd = p->W[l + 1]; rz.Pd = p->P[l + 1]; }
+        // batches: the product planes take k_rows_cum (dim-2 stage + integral image in one launch) on the aux lane, forked after the
+        // dim-1 stage; the blurred layer alone stays on the main lane (+ imresize!), so the next level waits for nothing else
+        static const bool no_rows_cum = getenv("SLAMHIP_NO_ROWS_CUM") != nullptr;
+        static const bool no_fused_cum = getenv("SLAMHIP_NO_FUSED_CUM") != nullptr;
+        const int cf_bands = (H + 63) / 64;
+        if (!topo && Sall >= 8 && mode != 0 && W >= 64 && cf_bands <= CF_MAXW && p->alloc->rck != nullptr && !no_rows_cum && !no_fused_cum) {
+            B.fork();
+            if (has_next) {
+                PlaneSet pT = {}; pT.p[0] = ps.p[0]; pT.coef[0] = ps.coef[0]; pT.fill0[0] = ps.fill0[0]; pT.n = 1; pT.zs = zs;
+                if (spans) { ProfScope span(ctx, "k_iir_rows");
+                    if (ck_rows) B.launch(k_iir_rows_ck, lines_grid(H, 1, S), dim3(LINE_THREADS), 0, LN_MAIN, pT, H, W, P, cf, p->ck, rz);
+                    else B.launch(k_iir_rows, lines_grid(H, 1, S), dim3(LINE_THREADS), 0, LN_MAIN, pT, H, W, P, cf); }
+                else if (ck_rows) B.launch(k_iir_rows_ck, lines_grid(H, 1, S), dim3(LINE_THREADS), 0, LN_MAIN, pT, H, W, P, cf, p->ck, rz);
+                else B.launch(k_iir_rows, lines_grid(H, 1, S), dim3(LINE_THREADS), 0, LN_MAIN, pT, H, W, P, cf);
+                if (!rows_resize)
+                    B.launch(k_resize, dim3(((size_t)p->H[l + 1] * p->W[l + 1] + 255) / 256, 1, S), dim3(256), 0, LN_MAIN,
+                                       nextL, p->H[l + 1], p->W[l + 1], p->P[l + 1], (const double *)T, H, W, P, zs);
+            }
+            PlaneSet pq = {};
+            for (int q = 0; q < 3; q++) { pq.p[q] = ps.p[np - 3 + q]; pq.coef[q] = ps.coef[np - 3 + q]; pq.fill0[q] = ps.fill0[np - 3 + q]; }
+            pq.n = 3; pq.zs = zs;
+            const size_t lds = (size_t)cf_bands * RC_LDS_DOUBLES * sizeof(double);
+            B.launch(k_rows_cum, dim3(1, 3, S), dim3(cf_bands * 64), lds, LN_AUX, pq, H, W, P, cf, p->alloc->rck);
+            return;
+        }
         if (topo) {
             B.launch(k_iir_rows, lines_grid(H, 1, S), dim3(LINE_THREADS), 0, LN_MAIN, psT, H, W, P, cf);
             B.launch(k_iir_rows, lines_grid(H, 3, S), dim3(LINE_THREADS), 0, side, psQ, H, W, P, cf);
@@ -2253,8 +2523,6 @@ static void launch_level(slam_ctx *ctx, slam_pyr *p, int mode, const IIRPair &cf
         if (has_next && !rows_resize)
             B.launch(k_resize, dim3(((size_t)p->H[l + 1] * p->W[l + 1] + 255) / 256, 1, S), dim3(256), 0, LN_MAIN,
                                nextL, p->H[l + 1], p->W[l + 1], p->P[l + 1], (const double *)T, H, W, P, zs);
-        static const bool no_fused_cum = getenv("SLAMHIP_NO_FUSED_CUM") != nullptr;
-        const int cf_bands = (H + 63) / 64;
         const int cf_seg = cf_bands <= CF_MAXW ? 1 : (cf_bands + CF_SEGW - 1) / CF_SEGW;      // taller planes: row segments of CF_SEGW bands, one workgroup each, chained through p->alloc->xc
         if (Sall >= 8 && !no_fused_cum && (cf_seg == 1 || (p->alloc->xc != nullptr && cf_seg <= p->alloc->xseg))) {      // batches: one-pass integral image
             const int nw = cf_seg == 1 ? cf_bands : CF_SEGW;
@@ -2406,6 +2674,7 @@ static int pyr_create_n(slam_ctx *ctx, int H, int W, int pyramid_levels, int S, 
     {
         hipError_t ea = hipFuncSetAttribute((const void *)k_cum_fused<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
         if (ea == hipSuccess) ea = hipFuncSetAttribute((const void *)k_cum_fused<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+        if (ea == hipSuccess) ea = hipFuncSetAttribute((const void *)k_rows_cum, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
         if (ea != hipSuccess) { (void)hipFree(al->base); delete al; return slam_fail(ctx, SLAM_ERR_HIP, "slam_pyr_create: hipFuncSetAttribute(k_cum_fused): %s", hipGetErrorString(ea)); }
     }
     double *ckbuf = nullptr;
@@ -2417,6 +2686,11 @@ static int pyr_create_n(slam_ctx *ctx, int H, int W, int pyramid_levels, int S, 
         const size_t need = lines * nbk > lines_c * nbk_c ? lines * nbk : lines_c * nbk_c;
         if (hipMalloc((void **)&ckbuf, need * 3 * 8) != hipSuccess) { (void)hipGetLastError(); ckbuf = nullptr; }
         al->ck = ckbuf;
+        // k_rows_cum's checkpoints (causal, then anticausal in the same slots): (blocks x 3) doubles per line of its level-0 launch (3 planes)
+        if ((Hs[0] + 63) / 64 <= CF_MAXW) {
+            const size_t lines_r = (size_t)S * 3 * (((size_t)Hs[0] + 63) / 64) * 64;
+            if (hipMalloc((void **)&al->rck, lines_r * nbk * 3 * 8) != hipSuccess) { (void)hipGetLastError(); al->rck = nullptr; }
+        }
         // column totals of the tolerance build's suffix-sum planes: 3 planes x S images x W_l doubles per level
         size_t wsum = 0; for (int l = 0; l < levels; l++) wsum += (size_t)Ws[l];
         if (hipMalloc((void **)&al->tot, (size_t)3 * S * wsum * 8) != hipSuccess) { (void)hipGetLastError(); al->tot = nullptr; }
@@ -2501,7 +2775,7 @@ int slam_pyr_destroy(slam_pyr *p)
     if (!p) return SLAM_OK;
     (void)hipSetDevice(p->device);
     (void)hipDeviceSynchronize();
-    if (p->alloc && --p->alloc->refs == 0) { (void)hipFree(p->alloc->base); if (p->alloc->ck) (void)hipFree(p->alloc->ck); if (p->alloc->tot) (void)hipFree(p->alloc->tot); if (p->alloc->xc) (void)hipFree(p->alloc->xc); if (p->alloc->xf) (void)hipFree(p->alloc->xf); if (p->alloc->srctab) (void)hipFree(p->alloc->srctab); delete p->alloc; }
+    if (p->alloc && --p->alloc->refs == 0) { (void)hipFree(p->alloc->base); if (p->alloc->ck) (void)hipFree(p->alloc->ck); if (p->alloc->tot) (void)hipFree(p->alloc->tot); if (p->alloc->xc) (void)hipFree(p->alloc->xc); if (p->alloc->xf) (void)hipFree(p->alloc->xf); if (p->alloc->rck) (void)hipFree(p->alloc->rck); if (p->alloc->srctab) (void)hipFree(p->alloc->srctab); delete p->alloc; }
     if (p->norm) (void)hipFree(p->norm);
     for (auto &g : p->graphs) (void)hipGraphExecDestroy(g.exec);
     delete p;
