@@ -380,6 +380,24 @@ __global__ __launch_bounds__(LINE_THREADS) void k_iir_rows(PlaneSet ps, int H, i
     iir_line(io, W, ps_coef(ps, pl) == 0 ? cf.c[0] : cf.c[1], ps_fill0(ps, pl), nrm ? nrm + y : nullptr, P);
 }
 
+// neighbour lanes of the whole wave through DPP (wave_shr:1 / wave_shl:1 of the GFX9 family): lane i receives lane i-1 / i+1,
+// lane 0 / 63 keeps its own value -- __shfl_up / __shfl_down by one lane without the LDS crossbar (ds_bpermute_b32: two per
+// double, ~64 per 8-row Scharr step, queued behind the tile traffic of all eight waves of the CU)
+__device__ __forceinline__ double wave_prev(double v)
+{
+    int lo = __double2loint(v), hi = __double2hiint(v);
+    lo = __builtin_amdgcn_update_dpp(lo, lo, 0x138, 0xF, 0xF, false);
+    hi = __builtin_amdgcn_update_dpp(hi, hi, 0x138, 0xF, 0xF, false);
+    return __hiloint2double(hi, lo);
+}
+__device__ __forceinline__ double wave_next(double v)
+{
+    int lo = __double2loint(v), hi = __double2hiint(v);
+    lo = __builtin_amdgcn_update_dpp(lo, lo, 0x130, 0xF, 0xF, false);
+    hi = __builtin_amdgcn_update_dpp(hi, hi, 0x130, 0xF, 0xF, false);
+    return __hiloint2double(hi, lo);
+}
+
 // dim-2 pass for batched, bandwidth-bound launches.  The backward sweep needs the forward results of the whole
 // line, which do not fit on chip (64 lines x 1226 samples = 628 KB per wave); k_iir_rows writes them to HBM and
 // reads them back (2 reads + 2 writes per sample).  Here the forward sweep only reads: it keeps its state every
@@ -388,12 +406,18 @@ __global__ __launch_bounds__(LINE_THREADS) void k_iir_rows(PlaneSet ps, int H, i
 // operations from the same state: bit-identical), runs the backward recurrence on them and stores once:
 // 2 reads + 1 write per sample for 1.5x the arithmetic, which a bandwidth-bound launch has to spare.
 #define CK_B 32
-// Fused imresize! (even H only): plane 0 of a level with a successor is the blurred layer, whose only reader is k_resize.  With
+// Fused imresize!: plane 0 of a level with a successor is the blurred layer, whose only reader is k_resize.  With
 // `rz.dst` set, the backward sweep of plane 0 does not store its results: every lane interpolates its row horizontally as the
-// samples appear (right to left; the source column and weight of the current output column are wave-uniform), row pairs
-// (2k, 2k+1) -- lanes (2k, 2k+1) of one wave -- are averaged through a shuffle and the even lanes store the next level's
-// layer: the arithmetic of k_resize for an exact 2:1 row ratio, term by term.
+// samples appear (right to left; the source column and weight of the current output column are wave-uniform), then the rows
+// are interpolated vertically between neighbouring lanes and one lane per output row stores the next level's layer: the
+// arithmetic of k_resize, term by term.
+//   * even H (exact 2:1 row ratio): row pairs (2k, 2k+1) -- lanes (2k, 2k+1) of one wave -- fy = 0.5, the even lanes store.
+//   * odd H = 2 Hd - 1 (k_iir_rows_ck_odd): output row k reads the source rows iy, iy + 1 with iy = 2k or 2k - 1 and a weight fy
+//     of its own, both from k_resize's double expressions (a per-lane constant).  The lane that holds row iy stores and takes
+//     row iy + 1 from the next lane.  A pair may start on any lane, so plane 0's bands advance by 63 rows: lane 63 repeats the
+//     next band's first row (the same operations on the same inputs: bit-identical) for lane 62 to read, and never stores.
 struct RowResize { double *dst; int Hd, Wd, Pd; };
+#define RZ_ODD_ROWS (LINE_THREADS - 1)                           // rows a band of the odd-height variant advances by
 __device__ __forceinline__ double dpp_pair_next(double v)        // lanes 2k and 2k+1 both receive lane 2k+1's value (quad_perm [1,1,3,3])
 {
     int lo = __double2loint(v), hi = __double2hiint(v);
@@ -408,15 +432,30 @@ __device__ __forceinline__ double dpp_pair_next(double v)        // lanes 2k and
 // (the checkpoints stay plain accesses: nontemporal ones measured 1-2 % slower per build)
 #define CK_LD(ptr) (*(ptr))
 #define CK_ST(ptr, v) (*(ptr) = (v))
-__global__ __launch_bounds__(LINE_THREADS) void k_iir_rows_ck(PlaneSet ps, int H, int W, int P, IIRPair cf, double *ck, RowResize rz)
+template <bool ODD>
+__device__ __forceinline__ void iir_rows_ck(const PlaneSet &ps, int H, int W, int P, const IIRPair &cf, double *ck, const RowResize &rz)
 {
-    const int y = blockIdx.x * LINE_THREADS + threadIdx.x, pl = blockIdx.y;
+    const int pl = blockIdx.y;
+    const bool resize = ODD || (pl == 0 && rz.dst != nullptr);  // (ODD: a one-plane launch of the blurred layer, rz.dst set)
+    const int slot = blockIdx.x * LINE_THREADS + threadIdx.x;   // line of this launch's checkpoint scratch
+    const int y = ODD ? blockIdx.x * RZ_ODD_ROWS + threadIdx.x : slot;
     if (y >= H) return;
-    const bool resize = pl == 0 && rz.dst != nullptr;
     // resize state: xo = current output column (1-based, descending), c0 = 0-based source column of its left sample, fx = weight
     const double rsx = (double)W / (double)(rz.Wd > 0 ? rz.Wd : 1), rox = 1 - 0.5 - rsx * (1 - 0.5);
     int xo = rz.Wd, c0 = -1; double fx = 0.0, tprev = 0.0;
-    double *rzp = resize ? rz.dst + (size_t)blockIdx.z * ps.zs + (y >> 1) : nullptr;
+    // vertical half: yo = 0-based output row this lane may store, fy = its weight, rz_store = the lane stores
+    int yo = y >> 1; double fy = 0.5; bool rz_store = (y & 1) == 0;
+    if (ODD) {                                                   // k_resize: r = sy * y + oy; iy = floor(r) clamped to [1, Hs - 1]; fy = r - iy
+        yo = (y + 1) >> 1;                                       // the only output row whose first source row (2 yo or 2 yo - 1) can be y
+        const double rsy = (double)H / (double)rz.Hd, roy = 1 - 0.5 - rsy * (1 - 0.5);
+        const double r = rsy * (yo + 1) + roy;
+        int iy = (int)floor(r);
+        if (iy > H - 1) iy = H - 1;
+        if (iy < 1) iy = 1;
+        fy = r - iy;
+        rz_store = yo < rz.Hd && iy - 1 == y && threadIdx.x < RZ_ODD_ROWS;     // (row iy + 1 <= H is the next lane's)
+    }
+    double *rzp = resize ? rz.dst + (size_t)blockIdx.z * ps.zs + yo : nullptr;
     const bool exact2 = 2 * rz.Wd == W;                           // exact 2:1 columns: c = 2 xo - 0.5 -> ixx = 2 xo - 1, fx = 0.5 (what the general path computes, without the floor)
     auto rz_target = [&]() {                                     // k_resize: c = sx * x + ox; ixx = floor(c) clamped to [1, Ws - 1]; fx = c - ixx
         if (xo < 1) { c0 = -1; return; }
@@ -432,16 +471,22 @@ __global__ __launch_bounds__(LINE_THREADS) void k_iir_rows_ck(PlaneSet ps, int H
     auto emit = [&](int x, double val) {                         // called for x = W-1 .. 0 in descending order with the finished sample T[y, x]
         if (x == c0) {
             const double h = (1 - fx) * val + fx * tprev;        // r0 / r1 of k_resize for this lane's row
-            const double hn = dpp_pair_next(h);                   // h of row y + 1 (the odd lane of the pair), no LDS round trip
-            const double fy = 0.5;
-            const double o = (1 - fy) * h + fy * hn;
-            if ((y & 1) == 0) rzp[(size_t)(xo - 1) * rz.Pd] = o;
+            if (ODD) {
+                const double hn = wave_next(h);                  // h of row y + 1
+                const double o = (1 - fy) * h + fy * hn;
+                if (rz_store) rzp[(size_t)(xo - 1) * rz.Pd] = o;
+            } else {
+                const double hn = dpp_pair_next(h);               // h of row y + 1 (the odd lane of the pair), no LDS round trip
+                const double fy2 = 0.5;
+                const double o = (1 - fy2) * h + fy2 * hn;
+                if ((y & 1) == 0) rzp[(size_t)(xo - 1) * rz.Pd] = o;
+            }
             xo--; rz_target();
         }
         tprev = val;
     };
     const size_t nlines = (size_t)gridDim.z * gridDim.y * gridDim.x * LINE_THREADS;
-    const size_t lineid = ((size_t)blockIdx.z * gridDim.y + pl) * gridDim.x * LINE_THREADS + y;
+    const size_t lineid = ((size_t)blockIdx.z * gridDim.y + pl) * gridDim.x * LINE_THREADS + slot;
     double *p = ps_plane(ps, pl) + y;
     const long s = P;
     const int n = W;
@@ -534,7 +579,33 @@ __global__ __launch_bounds__(LINE_THREADS) void k_iir_rows_ck(PlaneSet ps, int H
 #pragma unroll
         for (int e = 0; e < CK_B; e++) { const double t = ((cur[e] + a1 * f1) + a2 * f2) + a3 * f3; f3 = f2; f2 = f1; f1 = t; cur[e] = t; }
 #pragma unroll
-        for (int e = CK_B - 1; e >= 0; e--) { const double t = ((cur[e] + a1 * v1) + a2 * v2) + a3 * v3; v3 = v2; v2 = v1; v1 = t; cur[e] = t * scale; if (resize) emit(3 + j * CK_B + e, cur[e]); }
+        for (int e = CK_B - 1; e >= 0; e--) { const double t = ((cur[e] + a1 * v1) + a2 * v2) + a3 * v3; v3 = v2; v2 = v1; v1 = t; cur[e] = t * scale; if (!ODD && resize) emit(3 + j * CK_B + e, cur[e]); }
+        if (ODD) {
+            // The block's output columns without a branch per sample (the levels that come here run one wave per SIMD: the
+            // interpolation has to fill the recurrences' latency, not queue behind it).  The block starts on an odd column a;
+            // the left source column of output column k is 2k or 2k - 1 (W = 2 Wd or 2 Wd - 1), so the outputs whose left sample
+            // lies in the block are k = (a + 1) / 2 + mm, mm = 0 .. CK_B / 2 - 1, with left sample cur[2 mm + 1] or cur[2 mm]:
+            // k_resize's c, floor and weight per output, the two samples by a select.  tprev = T[a + CK_B].
+            const int kb = (3 + j * CK_B + 1) >> 1;
+#pragma unroll
+            for (int mm = 0; mm < CK_B / 2; mm++) {
+                const int k1 = kb + mm + 1;                      // 1-based output column
+                const double c = rsx * k1 + rox;
+                int ixx = (int)floor(c);
+                if (ixx > W - 1) ixx = W - 1;
+                if (ixx < 1) ixx = 1;
+                const double fxm = c - ixx;
+                const bool low = ixx == 2 * k1 - 2;             // 1-based left sample 2 k1 - 2 (0-based 2k - 1) instead of 2 k1 - 1
+                const double lft = low ? cur[2 * mm] : cur[2 * mm + 1];
+                const double rgt = low ? cur[2 * mm + 1] : (2 * mm + 2 < CK_B ? cur[2 * mm + 2 < CK_B ? 2 * mm + 2 : 0] : tprev);
+                const double h = (1 - fxm) * lft + fxm * rgt;
+                const double hn = wave_next(h);
+                const double o = (1 - fy) * h + fy * hn;
+                if (rz_store) rzp[(size_t)(k1 - 1) * rz.Pd] = o;
+            }
+            tprev = cur[0];
+            if (j == 0) { xo = kb; rz_target(); }                // the per-sample path takes over at x = 2: output columns kb .. 1 are left
+        }
         double *q = p + (long)(3 + j * CK_B) * s;
         if (!resize) {
 #pragma unroll
@@ -549,6 +620,15 @@ __global__ __launch_bounds__(LINE_THREADS) void k_iir_rows_ck(PlaneSet ps, int H
         t = ((o1 + a1 * v1) + a2 * v2) + a3 * v3; v3 = v2; v2 = v1; v1 = t; if (resize) emit(1, t * scale); else p[s] = t * scale;
         t = ((o0 + a1 * v1) + a2 * v2) + a3 * v3; if (resize) emit(0, t * scale); else p[0] = t * scale;
     }
+}
+__global__ __launch_bounds__(LINE_THREADS) void k_iir_rows_ck(PlaneSet ps, int H, int W, int P, IIRPair cf, double *ck, RowResize rz)
+{
+    iir_rows_ck<false>(ps, H, W, P, cf, ck, rz);
+}
+// one plane (the blurred layer), rz.dst set, H == 2 rz.Hd - 1, W == 2 rz.Wd or 2 rz.Wd - 1; gridDim.x = rz_odd_bands(H) bands of RZ_ODD_ROWS rows
+__global__ __launch_bounds__(LINE_THREADS) void k_iir_rows_ck_odd(PlaneSet ps, int H, int W, int P, IIRPair cf, double *ck, RowResize rz)
+{
+    iir_rows_ck<true>(ps, H, W, P, cf, ck, rz);
 }
 
 // dim-1 pass for bandwidth-bound batched launches: the checkpoint scheme of k_iir_rows_ck on column tiles.  Blocks
@@ -691,24 +771,6 @@ struct ColsFusedArgs {
     // P / 2 -- the dim-1 half of imresize! (a blur along x and an average along y commute); the row kernel finishes it
     int dec;
 };
-
-// neighbour lanes of the whole wave through DPP (wave_shr:1 / wave_shl:1 of the GFX9 family): lane i receives lane i-1 / i+1,
-// lane 0 / 63 keeps its own value -- __shfl_up / __shfl_down by one lane without the LDS crossbar (ds_bpermute_b32: two per
-// double, ~64 per 8-row Scharr step, queued behind the tile traffic of all eight waves of the CU)
-__device__ __forceinline__ double wave_prev(double v)
-{
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_update_dpp(lo, lo, 0x138, 0xF, 0xF, false);
-    hi = __builtin_amdgcn_update_dpp(hi, hi, 0x138, 0xF, 0xF, false);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double wave_next(double v)
-{
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_update_dpp(lo, lo, 0x130, 0xF, 0xF, false);
-    hi = __builtin_amdgcn_update_dpp(hi, hi, 0x130, 0xF, 0xF, false);
-    return __hiloint2double(hi, lo);
-}
 
 // x[0..N) holds the lane's layer samples of rows rb .. rb+N-1 on entry, the recurrence inputs of its role on exit
 // (ROLE 1: Iy^2, 2: Ix^2, 3: Iy Ix); g receives Iy (ROLE 1) / Ix (ROLE 2).  top / bot: the layer at rows rb-1 / rb+N.
@@ -2138,6 +2200,19 @@ static inline size_t ck_min_bytes()
     return e ? (size_t)atol(e) << 20 : (size_t)40 << 20;   // (96 MB until round 2: level 2 of 48+ streams and level 1 of 16+ now take the fused kernels too: +1.6 % / +5 % frames/s)
 }
 static inline dim3 lines_grid(int nlines, int nplanes, int S = 1) { return dim3((nlines + LINE_THREADS - 1) / LINE_THREADS, nplanes, S); }
+// Fused imresize! of an odd-height level (k_iir_rows_ck_odd): the rows 0 .. H - 2 can start a row pair, RZ_ODD_ROWS of them per band.
+static inline int rz_odd_bands(int H) { return (H - 1 + RZ_ODD_ROWS - 1) / RZ_ODD_ROWS; }
+// Level l of `p` may take it, in a launch of the blurred plane alone (the batch builds that fork the product planes to k_rows_cum,
+// and target-only builds; a launch over all four planes keeps the plain store + k_resize): H_l = 2 H_(l+1) - 1.  Its lines -- at most
+// one band more than H_l / 64, one plane -- fit the checkpoint scratch, which is sized for four planes of level 0.
+// SLAMHIP_NO_ROWS_RESIZE_ODD=1: plain store + k_resize at odd heights, as before (A/B runs, parity test).
+static inline bool rz_odd_ok(const slam_pyr *p, int l)
+{
+    static const bool off = getenv("SLAMHIP_NO_ROWS_RESIZE_ODD") != nullptr;
+    if (off || l + 1 >= p->levels) return false;
+    const int H = p->H[l], W = p->W[l], Wd = p->W[l + 1];
+    return H >= 3 && 2 * p->H[l + 1] - 1 == H && (W == 2 * Wd || W == 2 * Wd - 1) && rz_odd_bands(H) <= 4 * ((p->H[0] + LINE_THREADS - 1) / LINE_THREADS);
+}
 
 static void make_view(slam_pyr *p)
 {
@@ -2261,6 +2336,13 @@ struct BuildSink {
     bool lanes() const { return graph && forked; }
 };
 
+// the checkpointed row pass over `nplanes` planes; rz.dst: plane 0 leaves as the next level's layer (odd: through k_iir_rows_ck_odd)
+static void launch_rows_ck(BuildSink &B, const PlaneSet &ps, int nplanes, int S, int H, int W, int P, const IIRPair &cf, double *ck, const RowResize &rz, bool odd)
+{
+    if (odd) B.launch(k_iir_rows_ck_odd, dim3(rz_odd_bands(H), 1, S), dim3(LINE_THREADS), 0, LN_MAIN, ps, H, W, P, cf, ck, rz);     // (nplanes == 1)
+    else B.launch(k_iir_rows_ck, lines_grid(H, nplanes, S), dim3(LINE_THREADS), 0, LN_MAIN, ps, H, W, P, cf, ck, rz);
+}
+
 // One level of the build for the images [z0, z0 + S) of a batch of Sall (kernel selection follows Sall: a sub-batch runs the kernels the
 // whole batch would).
 static void launch_level(slam_ctx *ctx, slam_pyr *p, int mode, const IIRPair &cf, BuildSink &B, bool spans, int S, int src_kind, bool target, int l, int z0, int Sall, bool fast)
@@ -2281,10 +2363,11 @@ static void launch_level(slam_ctx *ctx, slam_pyr *p, int mode, const IIRPair &cf
             if (ckr) B.launch(k_iir_cols_ck, lines_grid(W, 1, S), dim3(LINE_THREADS), 0, LN_MAIN, pt, (const double *)v.L, H, W, P, cf, p->ck);
             else B.launch(k_iir_cols<2>, lines_grid(W, 1, S), dim3(LINE_THREADS), 0, LN_MAIN, pt, (const double *)v.L, H, W, P, cf);
             static const bool no_rr = getenv("SLAMHIP_NO_ROWS_RESIZE") != nullptr;
-            const bool rr = ckr && (H & 1) == 0 && !no_rr;
+            const bool rr_odd = ckr && (H & 1) != 0 && !no_rr && rz_odd_ok(p, l);
+            const bool rr = (ckr && (H & 1) == 0 && !no_rr) || rr_odd;
             RowResize rzt = {};
             if (rr) { rzt.dst = nextL; rzt.Hd = p->H[l + 1]; rzt.Wd = p->W[l + 1]; rzt.Pd = p->P[l + 1]; }
-            if (ckr) B.launch(k_iir_rows_ck, lines_grid(H, 1, S), dim3(LINE_THREADS), 0, LN_MAIN, pt, H, W, P, cf, p->ck, rzt);
+            if (ckr) launch_rows_ck(B, pt, 1, S, H, W, P, cf, p->ck, rzt, rr_odd);
             else B.launch(k_iir_rows, lines_grid(H, 1, S), dim3(LINE_THREADS), 0, LN_MAIN, pt, H, W, P, cf);
             if (!rr)
                 B.launch(k_resize, dim3(((size_t)p->H[l + 1] * p->W[l + 1] + 255) / 256, 1, S), dim3(256), 0, LN_MAIN,
@@ -2480,11 +2563,17 @@ static void launch_level(slam_ctx *ctx, slam_pyr *p, int mode, const IIRPair &cf
         else B.launch(k_iir_cols<2>, lines_grid(W, np, S), dim3(LINE_THREADS), 0, LN_MAIN, ps, src0, H, W, P, cf);
         // bandwidth-bound launches (many images x a large level) take the checkpointed row kernel (2R+1W instead of 2R+2W)
         const bool ck_rows = p->ck != nullptr && mode != 0 && W >= 64 && (size_t)Sall * np * H * W * 8 >= ck_min_bytes();
-        // ... with the imresize! into the next level fused into the blurred layer's backward sweep when the row ratio is exactly 2:1
+        // ... with the imresize! into the next level fused into the blurred layer's backward sweep (even H: exact 2:1 row ratio; odd H:
+        // k_iir_rows_ck_odd -- decided below, where the number of planes of the launch is known)
         static const bool no_rows_resize = getenv("SLAMHIP_NO_ROWS_RESIZE") != nullptr;
-        const bool rows_resize = ck_rows && has_next && (H & 1) == 0 && !no_rows_resize;
+        const bool rz_odd_cand = ck_rows && has_next && (H & 1) != 0 && !no_rows_resize;
+        bool rows_resize = ck_rows && has_next && (H & 1) == 0 && !no_rows_resize;
+        bool rows_odd = false;
         RowResize rz = {};
-        if (rows_resize) { rz.dst = nextL; rz.Hd = p->H[l + 1]; rz.Wd = p->W[l + 1]; rz.Pd = p->P[l + 1]; }
+        auto rz_decide = [&](int nplanes) {
+            if (rz_odd_cand && nplanes == 1 && rz_odd_ok(p, l)) rows_resize = rows_odd = true;
+            if (rows_resize) { rz.dst = nextL; rz.Hd = p->H[l + 1]; rz.Wd = p->W[l + 1]; rz.Pd = p->P[l + 1]; }
+        };
         // batches: the product planes take k_rows_cum (dim-2 stage + integral image in one launch) on the aux lane, forked after the
         // dim-1 stage; the blurred layer alone stays on the main lane (+ imresize!), so the next level waits for nothing else
         static const bool no_rows_cum = getenv("SLAMHIP_NO_ROWS_CUM") != nullptr;
@@ -2494,10 +2583,11 @@ static void launch_level(slam_ctx *ctx, slam_pyr *p, int mode, const IIRPair &cf
             B.fork();
             if (has_next) {
                 PlaneSet pT = {}; pT.p[0] = ps.p[0]; pT.coef[0] = ps.coef[0]; pT.fill0[0] = ps.fill0[0]; pT.n = 1; pT.zs = zs;
+                rz_decide(1);
                 if (spans) { ProfScope span(ctx, "k_iir_rows");
-                    if (ck_rows) B.launch(k_iir_rows_ck, lines_grid(H, 1, S), dim3(LINE_THREADS), 0, LN_MAIN, pT, H, W, P, cf, p->ck, rz);
+                    if (ck_rows) launch_rows_ck(B, pT, 1, S, H, W, P, cf, p->ck, rz, rows_odd);
                     else B.launch(k_iir_rows, lines_grid(H, 1, S), dim3(LINE_THREADS), 0, LN_MAIN, pT, H, W, P, cf); }
-                else if (ck_rows) B.launch(k_iir_rows_ck, lines_grid(H, 1, S), dim3(LINE_THREADS), 0, LN_MAIN, pT, H, W, P, cf, p->ck, rz);
+                else if (ck_rows) launch_rows_ck(B, pT, 1, S, H, W, P, cf, p->ck, rz, rows_odd);
                 else B.launch(k_iir_rows, lines_grid(H, 1, S), dim3(LINE_THREADS), 0, LN_MAIN, pT, H, W, P, cf);
                 if (!rows_resize)
                     B.launch(k_resize, dim3(((size_t)p->H[l + 1] * p->W[l + 1] + 255) / 256, 1, S), dim3(256), 0, LN_MAIN,
@@ -2510,14 +2600,15 @@ static void launch_level(slam_ctx *ctx, slam_pyr *p, int mode, const IIRPair &cf
             B.launch(k_rows_cum, dim3(1, 3, S), dim3(cf_bands * 64), lds, LN_AUX, pq, H, W, P, cf, p->alloc->rck);
             return;
         }
+        if (!topo) rz_decide(np);
         if (topo) {
             B.launch(k_iir_rows, lines_grid(H, 1, S), dim3(LINE_THREADS), 0, LN_MAIN, psT, H, W, P, cf);
             B.launch(k_iir_rows, lines_grid(H, 3, S), dim3(LINE_THREADS), 0, side, psQ, H, W, P, cf);
         }
         else if (spans) { ProfScope span(ctx, "k_iir_rows");
-            if (ck_rows) B.launch(k_iir_rows_ck, lines_grid(H, np, S), dim3(LINE_THREADS), 0, LN_MAIN, ps, H, W, P, cf, p->ck, rz);
+            if (ck_rows) launch_rows_ck(B, ps, np, S, H, W, P, cf, p->ck, rz, rows_odd);
             else B.launch(k_iir_rows, lines_grid(H, np, S), dim3(LINE_THREADS), 0, LN_MAIN, ps, H, W, P, cf); }
-        else if (ck_rows) B.launch(k_iir_rows_ck, lines_grid(H, np, S), dim3(LINE_THREADS), 0, LN_MAIN, ps, H, W, P, cf, p->ck, rz);
+        else if (ck_rows) launch_rows_ck(B, ps, np, S, H, W, P, cf, p->ck, rz, rows_odd);
         else B.launch(k_iir_rows, lines_grid(H, np, S), dim3(LINE_THREADS), 0, LN_MAIN, ps, H, W, P, cf);
         if (!topo) B.fork();
         if (has_next && !rows_resize)
