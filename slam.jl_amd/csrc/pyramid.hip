@@ -2188,12 +2188,22 @@ __global__ __launch_bounds__(256) void k_fill(double *p, size_t n, double v)
     if (i < n) p[i] = v;
 }
 
-// smallest batch whose tolerance build (mode 3) takes the batch kernels (k_cols_fused<TOL> + k_rows_tol) instead of the segmented single-image ones
-static inline int tol_batch_min_s()
-{
-    static const int v = [] { const char *e = getenv("SLAMHIP_TOL_BATCH_MIN_S"); return e ? atoi(e) : 4; }();
-    return v;
-}
+// Every SLAMHIP_* switch of the pyramid build (table: scripts/README.md), read once per process: a cached graph never disagrees with them.
+struct PyrKnobs {
+    static bool set(const char *name) { return getenv(name) != nullptr; }
+    static int num(const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; }
+    const int tol_batch_min_s = num("SLAMHIP_TOL_BATCH_MIN_S", 4);    // smallest batch whose tolerance build (mode 3) takes the batch kernels (k_cols_fused<TOL> + k_rows_tol) instead of the segmented single-image ones
+    const int chunk_mb = num("SLAMHIP_PYR_CHUNK_MB", 0);              // intermediate planes of a sub-batch, MB (0: no sub-batches)
+    const int scharr_xc1 = num("SLAMHIP_SCHARR_XC1", 2);              // (measurement knob) columns per thread for a single image: 16 / 8 / 4 / 2 / 1 -> 216 / 200 / 192 / 189 / 189 us per tolerance-mode build
+    const int rt_dbg = num("SLAMHIP_RT_DBG", 0);                      // k_rows_tol debug selector
+    // one fused kernel of the batch build off at a time
+    const bool no_ck_cols = set("SLAMHIP_NO_CK_COLS"), no_sq_fuse = set("SLAMHIP_NO_SQ_FUSE"), no_cols_fused = set("SLAMHIP_NO_COLS_FUSED"), no_fused_cum = set("SLAMHIP_NO_FUSED_CUM");
+    const bool no_fused_ingest = set("SLAMHIP_NO_FUSED_INGEST"), no_rows_resize = set("SLAMHIP_NO_ROWS_RESIZE"), no_rows_resize_odd = set("SLAMHIP_NO_ROWS_RESIZE_ODD"), no_rows_cum = set("SLAMHIP_NO_ROWS_CUM");
+    // tolerance mode
+    const bool no_tol_batch = set("SLAMHIP_NO_TOL_BATCH"), no_tol_dec = set("SLAMHIP_NO_TOL_DEC"), no_rows_tol_single = set("SLAMHIP_NO_ROWS_TOL_SINGLE"), no_seg_cum = set("SLAMHIP_NO_SEG_CUM"), seg_wide = set("SLAMHIP_SEG_WIDE");
+    const bool topology = set("SLAMHIP_TOPOLOGY"), linear_graph = set("SLAMHIP_LINEAR_GRAPH"), no_graph = set("SLAMHIP_NO_GRAPH");
+};
+static const PyrKnobs &knobs() { static const PyrKnobs k; return k; }
 static inline size_t ck_min_bytes()
 {
     const char *e = getenv("SLAMHIP_CK_MIN_MB");          // test / tuning hook; read per build (graphs are keyed on it below)
@@ -2208,8 +2218,7 @@ static inline int rz_odd_bands(int H) { return (H - 1 + RZ_ODD_ROWS - 1) / RZ_OD
 // SLAMHIP_NO_ROWS_RESIZE_ODD=1: plain store + k_resize at odd heights, as before (A/B runs, parity test).
 static inline bool rz_odd_ok(const slam_pyr *p, int l)
 {
-    static const bool off = getenv("SLAMHIP_NO_ROWS_RESIZE_ODD") != nullptr;
-    if (off || l + 1 >= p->levels) return false;
+    if (knobs().no_rows_resize_odd || l + 1 >= p->levels) return false;
     const int H = p->H[l], W = p->W[l], Wd = p->W[l + 1];
     return H >= 3 && 2 * p->H[l + 1] - 1 == H && (W == 2 * Wd || W == 2 * Wd - 1) && rz_odd_bands(H) <= 4 * ((p->H[0] + LINE_THREADS - 1) / LINE_THREADS);
 }
@@ -2244,12 +2253,6 @@ static int build_norm(slam_ctx *ctx, slam_pyr *p, double sigma)
     return SLAM_OK;
 }
 
-// Enqueue the whole pyramid build on ctx->stream; layer 0 must already hold the image.
-// Launch every kernel of one pyramid build.  `st` carries the dependent chain
-// (gradients -> IIR dim 1 -> IIR dim 2 -> resize -> next level); the integral-image
-// passes of level l only feed the LK kernel, so they run on `aux`, concurrently
-// with level l+1 (fork after the row pass, one join at the end).  With
-// aux == st everything is serial on one stream (profiling / fallback path).
 static void mat3_pow(const IIRCoef &k, int e, double P[9])
 {
     double M[9] = {k.a1, k.a2, k.a3, 1, 0, 0, 0, 1, 0}, R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, T[9];
@@ -2291,12 +2294,6 @@ static void rt_seg_pow(const IIRPair &cf, int SL, SegPow &sp)     // M^(SL q), q
         mat3_pow(cf.c[c], SL - 1, sp.Plast[c]);
     }
 }
-// Launch every kernel of one pyramid build.  `st` carries the dependent chain
-// (gradients -> IIR dim 1 -> IIR dim 2 -> resize -> next level); the integral-image
-// passes of level l only feed the LK kernel, so they run on `aux`, concurrently
-// with level l+1 (fork after the row pass, one join at the end).  With
-// aux == st everything is serial on one stream (profiling / fallback path).
-// mode 3 ("fast") swaps the sequential line kernels for the segmented ones.
 // Where the kernels of one build go: straight onto a stream (profiling spans, SLAMHIP_NO_GRAPH), or into an EXPLICITLY constructed
 // hipGraph -- hipGraphAddKernelNode with the dependencies of a two-lane DAG (lane 0: the dependent chain gradients -> dim 1 -> dim 2
 // -> resize -> next level; lane 1: the integral-image passes of level l, which only feed the tracking kernels and run beside level
@@ -2335,310 +2332,326 @@ struct BuildSink {
     void fork(int ln = LN_AUX) { if (graph && forked) fork_dep[ln] = last[LN_MAIN]; }
     bool lanes() const { return graph && forked; }
 };
-
-// the checkpointed row pass over `nplanes` planes; rz.dst: plane 0 leaves as the next level's layer (odd: through k_iir_rows_ck_odd)
-static void launch_rows_ck(BuildSink &B, const PlaneSet &ps, int nplanes, int S, int H, int W, int P, const IIRPair &cf, double *ck, const RowResize &rz, bool odd)
+// ---- The route of one level: every kernel choice of the build is made in level_route() and nowhere else; the emitters below read it.
+enum { FAM_NONE, FAM_TARGET, FAM_SEG, FAM_TOLB, FAM_EXACT };                     // skip the level / layer chain only / single-image tolerance / batch tolerance / exact
+enum { COLS_LINE, COLS_CK, COLS_FUSED, COLS_SEG };                               // dim 1: k_iir_cols<line_c> / k_iir_cols_ck / k_cols_fused / k_iir_seg<true>
+enum { ROWS_LINE, ROWS_CK, ROWS_SEG, ROWS_TOL };                                 // dim 2: k_iir_rows / k_iir_rows_ck[_odd] / k_iir_seg<false> / k_rows_tol
+enum { RZ_NONE, RZ_PLAIN, RZ_EVEN, RZ_ODD };                                     // imresize!: no next level / k_resize / fused into the row pass at even / odd heights
+enum { CUM_NONE, CUM_ROWS_CUM, CUM_FUSED, CUM_FUSED_SEG, CUM_LINES, CUM_SEG };   // integral images: inside the filter kernels / k_rows_cum / k_cum_fused<false> / <true> / k_cum_cols + k_cum_rows / k_cum_seg
+struct LevelRoute {
+    int family;
+    bool has_next; int np;     // a next level exists: the blurred layer is plane 0 of np = 4 planes (else the 3 product planes)
+    bool zero_border;          // mode 0: Fill(0) borders and the NA() normaliser
+    int scharr_xc;             // columns per thread of k_scharr_products; 0: none (k_cols_fused forms the gradients)
+    bool fuse_sq;              // k_iir_cols_ck / k_cols_fused square Iy / Ix themselves: the gradient kernel does not write (and the filter does not re-read) the Iyy / Ixx inputs
+    int cols, rows;            // COLS_*, ROWS_*.  ROWS_CK: bandwidth-bound launches (many images x a large level) take the checkpointed kernels (2R+1W instead of 2R+2W)
+    int line_c;                // template argument of k_iir_cols / k_cum_cols: 3 for one image, 2 for several
+    // LATENCY TOPOLOGY of a single image (round 5): the only thing level l + 1 waits for is level l's blurred, resized layer.  The main
+    // chain carries exactly that -- the dim-1 filter of the layer alone, the dim-2 filter (+ imresize!): 2-3 one-plane kernels per level;
+    // the gradients, the three product planes and their integral images of level l are a side branch of their own (lane LN_SIDE0 + l),
+    // which starts as soon as layer l exists and runs beside the chain and beside the other levels' branches.  Same kernels, same
+    // arithmetic per plane (a launch over 4 planes and two launches over 1 + 3 planes do the same per-line work).
+    // MEASURED (round 5, one 370 x 1226 image, builds back to back): tolerance mode 243 us per build with the topology, 218 without; bit-exact
+    // 450 vs 369 -- the split launches and the extra graph branches cost more than the shorter chain saves (the runtime serialises
+    // branch nodes onto few hardware queues), as the round-1 experiment on the bit-exact kernels had found.  Off unless SLAMHIP_TOPOLOGY=1.
+    // A two-lane variant (layer chain of every level on the main lane, the gradient / product work of levels 0-1 on the aux lane, of the
+    // coarser levels behind the chain) was measured too: one isolated build 181 vs 198 us under the profiler, but 178-220 vs 152 us back to
+    // back -- every cross-queue dependency of the graph costs ~10 us, and consecutive builds no longer overlap.  Not kept.
+    bool topo, cols_split;     // cols_split: the dim-1 stage too runs as layer (main lane) + product planes (side lane)
+    int side, side_cum;        // lanes of the gradients / products and of the integral images (LN_MAIN / LN_AUX unless topo)
+    // RZ_EVEN: exact 2:1 row ratio; RZ_ODD (k_iir_rows_ck_odd) only where the blurred layer launches alone (target-only, CUM_ROWS_CUM).
+    // KEPT AS FOUND: with topo the row pass is k_iir_rows, yet a level big enough for ROWS_CK still counts as RZ_EVEN at an even height: neither a fused
+    // resize nor k_resize runs (a single build on a batch member under SLAMHIP_TOPOLOGY=1 with a SLAMHIP_NO_* dim-1 switch, or under 64 rows with SLAMHIP_CK_MIN_MB=0)
+    int resize;
+    // CUM_ROWS_CUM (batches): the product planes take k_rows_cum (dim-2 stage + integral image in one launch) on the aux lane, forked after
+    // the dim-1 stage; the blurred layer alone stays on the main lane (+ imresize!), so the next level waits for nothing else.
+    // CUM_FUSED_SEG: planes taller than CF_MAXW bands in cum_seg row segments of CF_SEGW bands, one workgroup each, chained through alloc->xc.
+    int cum, cum_seg, cf_bands;
+    // FAM_SEG: columns of up to 512 samples take 32 segments of slc32 <= 16 samples in 256-thread workgroups (see k_iir_seg; 0 = the 128-segment
+    // variant with slc samples: longer columns, SLAMHIP_SEG_WIDE=1, and the split dim-1 launches of topo); cmask: the product planes take
+    // their running sum along y inside the dim-1 kernel (SLAMHIP_NO_SEG_CUM=1: a k_cum_seg launch of their own, CUM_SEG)
+    int slc, slr, slc32, cmask;
+    int rt_sl, rt_ns, rt_dbg;  // k_rows_tol: samples per segment, segments, SLAMHIP_RT_DBG
+    bool dec;                  // FAM_TOLB: the blurred layer leaves k_cols_fused halved along y (SLAMHIP_NO_TOL_DEC=1: off)
+};
+// The route of level l for a (sub-)batch of S images out of a build of Sall, into a sink with (`lanes`) or without parallel lanes.
+// QUIRK under SLAMHIP_PYR_CHUNK_MB, kept as it is: kernel selection follows Sall (a sub-batch runs the kernels the whole batch would), but
+// scharr_xc, line_c and topo follow the sub-batch's own S: a last chunk of one image takes k_scharr_products<2>, k_iir_cols<3>, k_cum_cols<3>.
+static LevelRoute level_route(const slam_pyr *p, int mode, int l, int S, int Sall, bool target, bool lanes)
 {
-    if (odd) B.launch(k_iir_rows_ck_odd, dim3(rz_odd_bands(H), 1, S), dim3(LINE_THREADS), 0, LN_MAIN, ps, H, W, P, cf, ck, rz);     // (nplanes == 1)
-    else B.launch(k_iir_rows_ck, lines_grid(H, nplanes, S), dim3(LINE_THREADS), 0, LN_MAIN, ps, H, W, P, cf, ck, rz);
+    const PyrKnobs &k = knobs();
+    const int H = p->H[l], W = p->W[l], P = p->P[l]; const size_t ckmin = ck_min_bytes();
+    const bool tol_batch = Sall >= k.tol_batch_min_s, ck_ok = p->ck != nullptr && mode != 0;
+    auto bytes = [&](int planes) { return (size_t)Sall * planes * H * W * 8; };
+    LevelRoute r = {};
+    r.has_next = l + 1 < p->levels; r.np = r.has_next ? 4 : 3; r.zero_border = mode == 0; r.line_c = S == 1 ? 3 : 2; r.side = LN_MAIN; r.side_cum = LN_AUX; r.rt_dbg = k.rt_dbg;
+    // the row pass `ck` (checkpointed or not) of the blurred layer, `alone` or with the product planes: how imresize! runs
+    auto resize_of = [&](bool ck, bool alone) -> int {
+        if (!r.has_next) return RZ_NONE;
+        if (!ck || k.no_rows_resize) return RZ_PLAIN;
+        return (H & 1) == 0 ? RZ_EVEN : alone && rz_odd_ok(p, l) ? RZ_ODD : RZ_PLAIN;
+    };
+    if (target && l >= 1) {                                       // the layer chain only: blur (dim 1, dim 2) -> resize
+        if (!r.has_next) return r;
+        const bool ck = (mode != 3 || tol_batch) && ck_ok && W >= 64 && H >= 64 && bytes(4) >= ckmin;
+        r.family = FAM_TARGET; r.line_c = 2;
+        r.cols = ck ? COLS_CK : COLS_LINE; r.rows = ck ? ROWS_CK : ROWS_LINE; r.resize = resize_of(ck, true);
+        return r;
+    }
+    // mode 3 swaps the sequential line kernels for the segmented ones -- unless a line has > 2048 samples, or the build is a batch: the
+    // segmented kernels buy latency for ONE image; with several images per launch the exact kernels are faster (and trivially within the tolerance)
+    const bool fast = mode == 3 && !tol_batch && seg_len(p->H[0], PAR_T / 8) <= PAR_SLMAX && seg_len(p->W[0], PAR_T / 8) <= PAR_SLMAX;
+    const bool ck_cols = !fast && ck_ok && H >= 64 && bytes(r.np) >= ckmin && !k.no_ck_cols;
+    r.fuse_sq = ck_cols && !k.no_sq_fuse;
+    const bool cols_fused = r.fuse_sq && !k.no_cols_fused;       // the fully fused dim-1 stage (Scharr + products + the four dim-1 recurrences straight from the layer)
+    r.topo = S == 1 && Sall == 1 && r.has_next && !cols_fused && lanes && k.topology;
+    if (r.topo) r.side = r.side_cum = LN_SIDE0 + l;
+    const int xc1 = k.scharr_xc1; r.scharr_xc = cols_fused ? 0 : (S == 1 && (xc1 == 1 || xc1 == 2 || xc1 == 4 || xc1 == 8)) ? xc1 : SCH_XC;
+    int rt_ns = RT_NS;
+    const int rt_sl = r.rt_sl = rt_seg_len(W, &rt_ns); r.rt_ns = rt_ns;
+    if (fast) {
+        r.family = FAM_SEG; r.cols = COLS_SEG; r.cols_split = r.topo;
+        r.slc = seg_len(H, PAR_T / 8); r.slr = seg_len(W, PAR_T / 8); r.slc32 = (seg_len(H, 32) <= PAR_SLMAX && !k.seg_wide) ? seg_len(H, 32) : 0;
+        // round 4: the dim-2 stage of a single image through k_rows_tol as well -- the blurred layer (filter along x + imresize!, one launch on
+        // the main chain instead of k_iir_seg + k_resize) and, on the branch, the product planes (running sum along y first: the two
+        // directions commute; then filter + running sum along x in one launch instead of k_iir_seg + k_cum_seg): 5 launches per level, 3 of
+        // them on the chain the next level waits for (6 / 4 before)
+        const bool rt1 = rt_sl > 0 && rt_ns == RT_NS && !k.no_rows_tol_single;
+        r.rows = rt1 ? ROWS_TOL : ROWS_SEG;
+        r.cmask = (rt1 && !r.topo && !k.no_seg_cum) ? (r.has_next ? 0xE : 0x7) : 0;
+        r.cum = r.cmask ? CUM_NONE : CUM_SEG;
+        r.resize = !r.has_next ? RZ_NONE : (rt1 && (H & 1) == 0) ? RZ_EVEN : RZ_PLAIN;
+        return r;
+    }
+    // tolerance build of a batch (mode 3, S >= 4): the dim-1 stage leaves the product planes as suffix sums along y, ONE row kernel
+    // finishes the level (dim-2 filter + running sum along x + imresize!): 1 R + 1 W per plane instead of 11 R + 6.25 W
+    if (mode == 3 && tol_batch && cols_fused && p->alloc->tot != nullptr && rt_sl > 0 && !k.no_tol_batch) {
+        r.family = FAM_TOLB; r.cols = COLS_FUSED; r.rows = ROWS_TOL;
+        r.dec = r.has_next && (H & 1) == 0 && (P & 31) == 0 && !k.no_tol_dec;
+        r.resize = !r.has_next ? RZ_NONE : (H & 1) == 0 ? RZ_EVEN : RZ_PLAIN;
+        return r;
+    }
+    r.family = FAM_EXACT;
+    r.cols = cols_fused ? COLS_FUSED : ck_cols ? COLS_CK : COLS_LINE; r.cols_split = r.topo && r.cols == COLS_LINE;
+    const bool ck_rows = ck_ok && W >= 64 && bytes(r.np) >= ckmin;
+    r.rows = ck_rows && !r.topo ? ROWS_CK : ROWS_LINE; r.cf_bands = (H + 63) / 64;
+    const bool batch_cum = Sall >= 8 && !k.no_fused_cum;
+    const bool rows_cum = batch_cum && !r.topo && mode != 0 && W >= 64 && r.cf_bands <= CF_MAXW && p->alloc->rck != nullptr && !k.no_rows_cum;
+    r.resize = resize_of(ck_rows, rows_cum);
+    r.cum_seg = r.cf_bands <= CF_MAXW ? 1 : (r.cf_bands + CF_SEGW - 1) / CF_SEGW;
+    if (rows_cum) r.cum = CUM_ROWS_CUM;
+    else if (batch_cum && r.cum_seg == 1) r.cum = CUM_FUSED;                  // batches: one-pass integral image
+    else if (batch_cum && p->alloc->xc != nullptr && r.cum_seg <= p->alloc->xseg) r.cum = CUM_FUSED_SEG;
+    else r.cum = CUM_LINES;
+    return r;
 }
-
-// One level of the build for the images [z0, z0 + S) of a batch of Sall (kernel selection follows Sall: a sub-batch runs the kernels the
-// whole batch would).
-static void launch_level(slam_ctx *ctx, slam_pyr *p, int mode, const IIRPair &cf, BuildSink &B, bool spans, int S, int src_kind, bool target, int l, int z0, int Sall, bool fast)
+// ---- What a level's kernels read and write, for the images [z0, z0 + S) of a batch of Sall
+struct LevelIO {
+    int H, W, P; LevelView v; double *T;   // the level's planes, the blur scratch plane
+    RowResize next;                        // the next level's layer (zero at the last level)
+    const double *norm; double *tot;       // NA() normaliser (mode 0); column totals of the batch tolerance build
+    size_t zs; int z0;
+    int src_kind; const void *const *srctab;
+};
+static LevelIO level_io(const slam_pyr *p, int l, int z0, int Sall, int src_kind)
 {
-    const size_t zs = p->zstride, zo = (size_t)z0 * zs;
-    const int border_mode = (mode == 0) ? 1 : 0;
-    {
-        const int H = p->H[l], W = p->W[l], P = p->P[l];
-        LevelView v = p->view.lv[l];
-        v.L += zo; v.Iy += zo; v.Ix += zo; v.Iyy += zo; v.Ixx += zo; v.Iyx += zo;
-        const bool has_next = l + 1 < p->levels;
-        double *T = p->tmp + p->off[l] + zo;
-        double *nextL = has_next ? p->view.lv[l + 1].L + zo : nullptr;
-        if (target && l >= 1) {                                   // the layer chain only: blur (dim 1, dim 2) -> resize
-            if (!has_next) return;
-            PlaneSet pt = {}; pt.p[0] = T; pt.coef[0] = 0; pt.fill0[0] = (mode == 0); pt.nrm[0] = nullptr; pt.n = 1; pt.zs = zs;
-            const bool ckr = (mode != 3 || Sall >= tol_batch_min_s()) && p->ck != nullptr && mode != 0 && W >= 64 && H >= 64 && (size_t)Sall * 4 * H * W * 8 >= ck_min_bytes();
-            if (ckr) B.launch(k_iir_cols_ck, lines_grid(W, 1, S), dim3(LINE_THREADS), 0, LN_MAIN, pt, (const double *)v.L, H, W, P, cf, p->ck);
-            else B.launch(k_iir_cols<2>, lines_grid(W, 1, S), dim3(LINE_THREADS), 0, LN_MAIN, pt, (const double *)v.L, H, W, P, cf);
-            static const bool no_rr = getenv("SLAMHIP_NO_ROWS_RESIZE") != nullptr;
-            const bool rr_odd = ckr && (H & 1) != 0 && !no_rr && rz_odd_ok(p, l);
-            const bool rr = (ckr && (H & 1) == 0 && !no_rr) || rr_odd;
-            RowResize rzt = {};
-            if (rr) { rzt.dst = nextL; rzt.Hd = p->H[l + 1]; rzt.Wd = p->W[l + 1]; rzt.Pd = p->P[l + 1]; }
-            if (ckr) launch_rows_ck(B, pt, 1, S, H, W, P, cf, p->ck, rzt, rr_odd);
-            else B.launch(k_iir_rows, lines_grid(H, 1, S), dim3(LINE_THREADS), 0, LN_MAIN, pt, H, W, P, cf);
-            if (!rr)
-                B.launch(k_resize, dim3(((size_t)p->H[l + 1] * p->W[l + 1] + 255) / 256, 1, S), dim3(256), 0, LN_MAIN,
-                                   nextL, p->H[l + 1], p->W[l + 1], p->P[l + 1], (const double *)T, H, W, P, zs);
-            return;
-        }
-        // bandwidth-bound launches (many images x a large level) take the checkpointed IIR kernels; the column one squares
-        // Iy / Ix itself, so the gradient kernel does not write (and the filter does not re-read) the Iyy / Ixx inputs
-        const int np_ = has_next ? 4 : 3;
-        static const bool no_ck_cols = getenv("SLAMHIP_NO_CK_COLS") != nullptr;     // tuning toggles are read once per process: a cached graph never disagrees with them
-        const bool ck_cols = !fast && p->ck != nullptr && mode != 0 && H >= 64 && (size_t)Sall * np_ * H * W * 8 >= ck_min_bytes() && !no_ck_cols;
-        static const bool no_sq = getenv("SLAMHIP_NO_SQ_FUSE") != nullptr;
-        const bool fuse_sq = ck_cols && !no_sq;
-        // ... and the fully fused dim-1 stage (Scharr + products + the four dim-1 recurrences straight from the layer)
-        static const bool no_cols_fused = getenv("SLAMHIP_NO_COLS_FUSED") != nullptr;
-        const bool cols_fused = fuse_sq && !no_cols_fused;
-        // LATENCY TOPOLOGY of a single image (round 5): the only thing level l + 1 waits for is level l's blurred, resized layer.  The main
-        // chain carries exactly that -- the dim-1 filter of the layer alone, the dim-2 filter (+ imresize!): 2-3 one-plane kernels per level;
-        // the gradients, the three product planes and their integral images of level l are a side branch of their own (lane LN_SIDE0 + l),
-        // which starts as soon as layer l exists and runs beside the chain and beside the other levels' branches.  Same kernels, same
-        // arithmetic per plane (a launch over 4 planes and two launches over 1 + 3 planes do the same per-line work).
-        // MEASURED (round 5, one 370 x 1226 image, builds back to back): tolerance mode 243 us per build with the topology, 218 without; bit-exact
-        // 450 vs 369 -- the split launches and the extra graph branches cost more than the shorter chain saves (the runtime serialises
-        // branch nodes onto few hardware queues), as the round-1 experiment on the bit-exact kernels had found.  Off unless SLAMHIP_TOPOLOGY=1.
-        // A two-lane variant (layer chain of every level on the main lane, the gradient / product work of levels 0-1 on the aux lane, of the
-        // coarser levels behind the chain) was measured too: one isolated build 181 vs 198 us under the profiler, but 178-220 vs 152 us back to
-        // back -- every cross-queue dependency of the graph costs ~10 us, and consecutive builds no longer overlap.  Not kept.
-        static const bool no_topo = getenv("SLAMHIP_TOPOLOGY") == nullptr;
-        const bool topo = S == 1 && Sall == 1 && has_next && !cols_fused && B.lanes() && !no_topo;
-        const int side = topo ? LN_SIDE0 + l : LN_MAIN;            // lane of the gradients / products (non-topology: the main chain)
-        const int side_cum = topo ? LN_SIDE0 + l : LN_AUX;         // lane of the integral images
-        if (topo) B.fork(side);
-        auto emit_scharr = [&](int lane_) {
-            static const int sch1 = [] { const char *e = getenv("SLAMHIP_SCHARR_XC1"); return e ? atoi(e) : 2; }();      // (measurement knob) columns per thread for a single image: 16 / 8 / 4 / 2 / 1 -> 216 / 200 / 192 / 189 / 189 us per tolerance-mode build
-            if (!cols_fused && S == 1 && sch1 == 4) B.launch(k_scharr_products<4>, dim3((H + 63) / 64, (W + 3) / 4, S), dim3(64), 0, lane_, v, border_mode, zs, fuse_sq ? 0 : 1);
-            else if (!cols_fused && S == 1 && sch1 == 2) B.launch(k_scharr_products<2>, dim3((H + 63) / 64, (W + 1) / 2, S), dim3(64), 0, lane_, v, border_mode, zs, fuse_sq ? 0 : 1);
-            else if (!cols_fused && S == 1 && sch1 == 1) B.launch(k_scharr_products<1>, dim3((H + 63) / 64, W, S), dim3(64), 0, lane_, v, border_mode, zs, fuse_sq ? 0 : 1);
-            else if (!cols_fused && S == 1 && sch1 == 8) B.launch(k_scharr_products<8>, dim3((H + 63) / 64, (W + 7) / 8, S), dim3(64), 0, lane_, v, border_mode, zs, fuse_sq ? 0 : 1);
-            else if (!cols_fused) B.launch(k_scharr_products<SCH_XC>, dim3((H + 63) / 64, (W + SCH_XC - 1) / SCH_XC, S), dim3(64), 0, lane_, v, border_mode, zs, fuse_sq ? 0 : 1);
-        };
-        emit_scharr(side);
-        // dim-1 IIR: [blur: L -> T], Iyy, Ixx, Iyx in place
-        PlaneSet ps = {};
-        int np = 0;
-        if (has_next) { ps.p[np] = T; ps.coef[np] = 0; ps.fill0[np] = (mode == 0); ps.nrm[np] = (mode == 0) ? p->norm + p->off[l] : nullptr; np++; }
-        ps.p[np] = v.Iyy; ps.coef[np] = 1; ps.sq[np] = fuse_sq ? v.Iy : nullptr; np++;
-        ps.p[np] = v.Ixx; ps.coef[np] = 1; ps.sq[np] = fuse_sq ? v.Ix : nullptr; np++;
-        ps.p[np] = v.Iyx; ps.coef[np] = 1; np++;
-        ps.n = np; ps.zs = zs;
-        const double *src0 = has_next ? (const double *)v.L : (const double *)nullptr;
-        PlaneSet psT = {}, psQ = {};                                // topology: the blurred layer alone / the three product planes
-        if (topo) {
-            psT.p[0] = ps.p[0]; psT.coef[0] = ps.coef[0]; psT.fill0[0] = ps.fill0[0]; psT.nrm[0] = ps.nrm[0]; psT.n = 1; psT.zs = zs;
-            for (int q = 0; q < 3; q++) { psQ.p[q] = ps.p[q + 1]; psQ.coef[q] = ps.coef[q + 1]; psQ.fill0[q] = ps.fill0[q + 1]; psQ.nrm[q] = ps.nrm[q + 1]; psQ.sq[q] = ps.sq[q + 1]; }
-            psQ.n = 3; psQ.zs = zs;
-        }
-        PlaneSet pc = {};
-        pc.p[0] = v.Iyy; pc.p[1] = v.Ixx; pc.p[2] = v.Iyx; pc.n = 3; pc.zs = zs;
-        if (fast) {
-            const int slc = seg_len(H, PAR_T / 8), slr = seg_len(W, PAR_T / 8);
-            SegPow spc, spr;
-            seg_pow(cf, H, slc, spc); seg_pow(cf, W, slr, spr);
-            const dim3 gc((W + 7) / 8, np, S), gr((H + 7) / 8, np, S), gc3((W + 7) / 8, 3, S), gr3((H + 7) / 8, 3, S);
-            // columns of up to 512 samples: 32 segments of <= 16 samples per column in 256-thread workgroups (see k_iir_seg); SLAMHIP_SEG_WIDE=1: the 128-segment variant
-            static const bool seg_wide = getenv("SLAMHIP_SEG_WIDE") != nullptr;
-            const int slc32 = seg_len(H, 32);
-            const bool c32 = slc32 <= PAR_SLMAX && !seg_wide;
-            SegPow spc32;
-            if (c32) seg_pow(cf, H, slc32, spc32);
-            int rns = RT_NS;
-            const int slt = rt_seg_len(W, &rns);
-            static const bool no_rt1 = getenv("SLAMHIP_NO_ROWS_TOL_SINGLE") != nullptr;
-            const bool rt1 = slt > 0 && rns == RT_NS && !no_rt1;      // the dim-2 stage runs through k_rows_tol (below)
-            // ... then the product planes take their running sum along y inside the dim-1 kernel (SLAMHIP_NO_SEG_CUM=1: a k_cum_seg launch of their own)
-            static const bool no_seg_cum = getenv("SLAMHIP_NO_SEG_CUM") != nullptr;
-            const bool seg_cum = rt1 && !topo && !no_seg_cum;
-            const int cmask = seg_cum ? (has_next ? 0xE : 0x7) : 0;
-            if (topo) {
-                B.launch(k_iir_seg<true>, dim3((W + 7) / 8, 1, S), dim3(PAR_T), 0, LN_MAIN, psT, src0, H, W, P, cf, spc, slc, 0);
-                B.launch(k_iir_seg<true>, gc3, dim3(PAR_T), 0, side, psQ, (const double *)nullptr, H, W, P, cf, spc, slc, 0);
-            }
-            else if (c32) B.launch((k_iir_seg<true, 256, 8>), gc, dim3(256), 0, LN_MAIN, ps, src0, H, W, P, cf, spc32, slc32, cmask);
-            else B.launch(k_iir_seg<true>, gc, dim3(PAR_T), 0, LN_MAIN, ps, src0, H, W, P, cf, spc, slc, cmask);
-            // round 4: the dim-2 stage of a single image through k_rows_tol as well -- the blurred layer (filter along x + imresize!, one launch on
-            // the main chain instead of k_iir_seg + k_resize) and, on the branch, the product planes (running sum along y first: the two
-            // directions commute; then filter + running sum along x in one launch instead of k_iir_seg + k_cum_seg): 5 launches per level, 3 of
-            // them on the chain the next level waits for (6 / 4 before)
-            if (rt1) {
-                SegPow spt; rt_seg_pow(cf, slt, spt);
-                auto rows_tol = [&](RowsTolArgs &ra, int nplanes, int lane_) {
-                    const dim3 g2((H + RT_R - 1) / RT_R, nplanes, S), b2(RT_R * RT_NS);
-#define RT_GO1(SLV) B.launch((k_rows_tol<SLV, RT_NS, RT_R>), g2, b2, 0, lane_, ra, H, W, P, cf, spt)
-                    switch (slt) { case 4: RT_GO1(4); break; case 6: RT_GO1(6); break; case 8: RT_GO1(8); break; case 10: RT_GO1(10); break; case 12: RT_GO1(12); break;
-                                   case 16: RT_GO1(16); break; case 20: RT_GO1(20); break; case 24: RT_GO1(24); break; case 32: RT_GO1(32); break; default: RT_GO1(40); break; }
-#undef RT_GO1
-                };
-                if (!topo) B.fork();
-                if (has_next) {
-                    RowsTolArgs rt = {};
-                    rt.p[0] = T; rt.coef[0] = 0; rt.kind[0] = 0; rt.n = 1; rt.nq0 = 1; rt.zs = zs;
-                    const bool rzf = (H & 1) == 0;
-                    if (rzf) { rt.rz.dst = nextL; rt.rz.Hd = p->H[l + 1]; rt.rz.Wd = p->W[l + 1]; rt.rz.Pd = p->P[l + 1]; }
-                    if (spans) { ProfScope span(ctx, "k_iir_rows"); rows_tol(rt, 1, LN_MAIN); } else rows_tol(rt, 1, LN_MAIN);
-                    if (!rzf)
-                        B.launch(k_resize, dim3(((size_t)p->H[l + 1] * p->W[l + 1] + 255) / 256, 1, S), dim3(256), 0, LN_MAIN,
-                                           nextL, p->H[l + 1], p->W[l + 1], p->P[l + 1], (const double *)T, H, W, P, zs);
-                }
-                if (seg_cum) {}
-                else if (c32) B.launch((k_cum_seg<true, 256, 8>), gc3, dim3(256), 0, side_cum, pc, H, W, P, slc32);
-                else B.launch(k_cum_seg<true>, gc3, dim3(PAR_T), 0, side_cum, pc, H, W, P, slc);
-                RowsTolArgs rq = {};
-                rq.p[0] = v.Iyy; rq.p[1] = v.Ixx; rq.p[2] = v.Iyx;
-                for (int q = 0; q < 3; q++) { rq.coef[q] = 1; rq.kind[q] = 2; }
-                rq.n = 3; rq.nq0 = 0; rq.zs = zs;
-                rows_tol(rq, 3, side_cum);
-                return;
-            }
-            if (topo) {
-                B.launch(k_iir_seg<false>, dim3((H + 7) / 8, 1, S), dim3(PAR_T), 0, LN_MAIN, psT, (const double *)nullptr, H, W, P, cf, spr, slr, 0);
-                B.launch(k_iir_seg<false>, gr3, dim3(PAR_T), 0, side, psQ, (const double *)nullptr, H, W, P, cf, spr, slr, 0);
-            }
-            else if (spans) { ProfScope span(ctx, "k_iir_rows");
-                B.launch(k_iir_seg<false>, gr, dim3(PAR_T), 0, LN_MAIN, ps, (const double *)nullptr, H, W, P, cf, spr, slr, 0); }
-            else B.launch(k_iir_seg<false>, gr, dim3(PAR_T), 0, LN_MAIN, ps, (const double *)nullptr, H, W, P, cf, spr, slr, 0);
-            if (!topo) B.fork();
-            if (has_next)
-                B.launch(k_resize, dim3(((size_t)p->H[l + 1] * p->W[l + 1] + 255) / 256, 1, S), dim3(256), 0, LN_MAIN,
-                                   nextL, p->H[l + 1], p->W[l + 1], p->P[l + 1], (const double *)T, H, W, P, zs);
-            if (c32) B.launch((k_cum_seg<true, 256, 8>), gc3, dim3(256), 0, side_cum, pc, H, W, P, slc32);
-            else B.launch(k_cum_seg<true>, gc3, dim3(PAR_T), 0, side_cum, pc, H, W, P, slc);
-            B.launch(k_cum_seg<false>, gr3, dim3(PAR_T), 0, side_cum, pc, H, W, P, slr);
-            return;
-        }
-        // tolerance build of a batch (mode 3, S >= 4): the dim-1 stage leaves the product planes as suffix sums along y, ONE row kernel
-        // finishes the level (dim-2 filter + running sum along x + imresize!): 1 R + 1 W per plane instead of 11 R + 6.25 W
-        static const bool no_tol_batch = getenv("SLAMHIP_NO_TOL_BATCH") != nullptr;
-        int rt_ns = RT_NS;
-        const int slr_t = rt_seg_len(W, &rt_ns);
-        const bool tolb = mode == 3 && Sall >= tol_batch_min_s() && cols_fused && p->alloc->tot != nullptr && slr_t > 0 && !no_tol_batch;
-        if (cols_fused) {
-            ColsFusedArgs ca;
-            ca.L = v.L; ca.T = has_next ? T : nullptr; ca.Iy = v.Iy; ca.Ix = v.Ix; ca.Qyy = v.Iyy; ca.Qxx = v.Ixx; ca.Qyx = v.Iyx;
-            ca.H = H; ca.W = W; ca.P = P; ca.zs = zs;
-            ca.src_kind = l == 0 ? src_kind : 0; ca.srctab = (const void *const *)p->alloc->srctab + z0;
-            size_t toff = 0;
-            for (int q = 0; q < l; q++) toff += (size_t)3 * Sall * p->W[q];
-            toff += (size_t)3 * z0 * W;
-            ca.tot = tolb ? p->alloc->tot + toff : nullptr; ca.tot_stride = W;
-            static const bool no_dec = getenv("SLAMHIP_NO_TOL_DEC") != nullptr;
-            ca.dec = (tolb && has_next && (H & 1) == 0 && (P & 31) == 0 && !no_dec) ? 1 : 0;
-            if (tolb && ca.dec) B.launch(k_cols_fused<true, true>, dim3((W + CF4_COLS - 1) / CF4_COLS, 1, S), dim3(256), 0, LN_MAIN, ca, cf, p->ck);
-            else if (tolb) B.launch(k_cols_fused<true, false>, dim3((W + CF4_COLS - 1) / CF4_COLS, 1, S), dim3(256), 0, LN_MAIN, ca, cf, p->ck);
-            else B.launch(k_cols_fused<false, false>, dim3((W + CF4_COLS - 1) / CF4_COLS, 1, S), dim3(256), 0, LN_MAIN, ca, cf, p->ck);
-            if (tolb) {
-                RowsTolArgs ra = {};
-                int nr = 0;
-                if (has_next) { ra.p[nr] = T; ra.coef[nr] = 0; ra.kind[nr] = 0; nr++; }
-                ra.nq0 = nr;
-                ra.p[nr] = v.Iyy; ra.coef[nr] = 1; ra.kind[nr] = 1; nr++;
-                ra.p[nr] = v.Ixx; ra.coef[nr] = 1; ra.kind[nr] = 1; nr++;
-                ra.p[nr] = v.Iyx; ra.coef[nr] = 1; ra.kind[nr] = 1; nr++;
-                ra.n = nr; ra.zs = zs; ra.tot = ca.tot; ra.tot_stride = W;
-                const bool rzf = has_next && (H & 1) == 0;
-                ra.dec = ca.dec;
-                if (rzf) { ra.rz.dst = nextL; ra.rz.Hd = p->H[l + 1]; ra.rz.Wd = p->W[l + 1]; ra.rz.Pd = p->P[l + 1]; }
-                SegPow spr; rt_seg_pow(cf, slr_t, spr);
-                static const int rt_dbg = getenv("SLAMHIP_RT_DBG") ? atoi(getenv("SLAMHIP_RT_DBG")) : 0; ra.dbg = rt_dbg;
-                const dim3 gr((H + RT_R - 1) / RT_R, nr, S), bd(RT_R * rt_ns);
-                auto go = [&]() {
-                    if (rt_ns != RT_NS) {                          // wide rows: 64 segments
-                        if (slr_t == 24) B.launch((k_rows_tol<24, 2 * RT_NS, RT_R>), gr, bd, 0, LN_MAIN, ra, H, W, P, cf, spr);
-                        else B.launch((k_rows_tol<32, 2 * RT_NS, RT_R>), gr, bd, 0, LN_MAIN, ra, H, W, P, cf, spr);
-                        return;
-                    }
-#define RT_GO(SLV) B.launch((k_rows_tol<SLV, RT_NS, RT_R>), gr, bd, 0, LN_MAIN, ra, H, W, P, cf, spr)
-                    switch (slr_t) { case 4: RT_GO(4); break; case 6: RT_GO(6); break; case 8: RT_GO(8); break; case 10: RT_GO(10); break; case 12: RT_GO(12); break;
-                                     case 16: RT_GO(16); break; case 20: RT_GO(20); break; case 24: RT_GO(24); break; case 32: RT_GO(32); break; default: RT_GO(40); break; }
+    LevelIO io = {};
+    const size_t zo = (size_t)z0 * p->zstride;
+    io.H = p->H[l]; io.W = p->W[l]; io.P = p->P[l]; io.zs = p->zstride; io.z0 = z0;
+    io.v = p->view.lv[l];
+    io.v.L += zo; io.v.Iy += zo; io.v.Ix += zo; io.v.Iyy += zo; io.v.Ixx += zo; io.v.Iyx += zo;
+    io.T = p->tmp + p->off[l] + zo;
+    if (l + 1 < p->levels) io.next = RowResize{p->view.lv[l + 1].L + zo, p->H[l + 1], p->W[l + 1], p->P[l + 1]};
+    io.norm = p->norm ? p->norm + p->off[l] : nullptr;
+    size_t toff = (size_t)3 * z0 * io.W;
+    for (int q = 0; q < l; q++) toff += (size_t)3 * Sall * p->W[q];
+    io.tot = p->alloc->tot ? p->alloc->tot + toff : nullptr;
+    io.src_kind = l == 0 ? src_kind : 0; io.srctab = (const void *const *)p->alloc->srctab + z0;
+    return io;
+}
+// planes [first, first + n) of a launch's set as a set of their own
+static PlaneSet plane_slice(const PlaneSet &ps, int first, int n, bool with_sq = true)
+{
+    PlaneSet s = {};
+    for (int q = 0, f = first; q < n; q++, f++) { s.p[q] = ps.p[f]; s.nrm[q] = ps.nrm[f]; s.coef[q] = ps.coef[f]; s.fill0[q] = ps.fill0[f]; s.sq[q] = with_sq ? ps.sq[f] : nullptr; }
+    s.n = n; s.zs = ps.zs;
+    return s;
+}
+// the filter passes' planes: [blur: L -> T], Iyy, Ixx, Iyx in place
+static PlaneSet level_planes(const LevelRoute &r, const LevelIO &io)
+{
+    PlaneSet ps = {}; int np = 0;
+    if (r.has_next) { ps.p[np] = io.T; ps.coef[np] = 0; ps.fill0[np] = r.zero_border; ps.nrm[np] = r.zero_border ? io.norm : nullptr; np++; }
+    ps.p[np] = io.v.Iyy; ps.coef[np] = 1; ps.sq[np] = r.fuse_sq ? io.v.Iy : nullptr; np++;
+    ps.p[np] = io.v.Ixx; ps.coef[np] = 1; ps.sq[np] = r.fuse_sq ? io.v.Ix : nullptr; np++;
+    ps.p[np] = io.v.Iyx; ps.coef[np] = 1; np++;
+    ps.n = np; ps.zs = io.zs;
+    return ps;
+}
+static PlaneSet cum_planes(const LevelIO &io) { PlaneSet pc = {}; pc.p[0] = io.v.Iyy; pc.p[1] = io.v.Ixx; pc.p[2] = io.v.Iyx; pc.n = 3; pc.zs = io.zs; return pc; }
+// where the blurred layer's row pass writes the next level's layer, if the route fuses imresize! into it
+static RowResize row_resize(const LevelRoute &r, const LevelIO &io) { return (r.resize == RZ_EVEN || r.resize == RZ_ODD) ? io.next : RowResize{}; }
+// k_rows_tol's planes: [the blurred layer (+ imresize! if the route fuses it)], then [the product planes, of `product_kind` 1 / 2; 0: none]
+static RowsTolArgs rows_tol_args(const LevelRoute &r, const LevelIO &io, bool layer, int product_kind)
+{
+    RowsTolArgs ra = {}; int n = 0;
+    if (layer) { ra.p[n] = io.T; ra.coef[n] = 0; ra.kind[n] = 0; ra.rz = row_resize(r, io); n++; }
+    ra.nq0 = n;
+    if (product_kind) for (double *q : {io.v.Iyy, io.v.Ixx, io.v.Iyx}) { ra.p[n] = q; ra.coef[n] = 1; ra.kind[n] = product_kind; n++; }
+    ra.n = n; ra.zs = io.zs;
+    return ra;
+}
+// ---- Launch helpers: one place per kernel family
+static void launch_resize(BuildSink &B, const LevelIO &io, int S)
+{
+    const RowResize &d = io.next; B.launch(k_resize, dim3(((size_t)d.Hd * d.Wd + 255) / 256, 1, S), dim3(256), 0, LN_MAIN, d.dst, d.Hd, d.Wd, d.Pd, (const double *)io.T, io.H, io.W, io.P, io.zs);
+}
+static void launch_scharr(BuildSink &B, const LevelRoute &r, const LevelIO &io, int S)
+{
+    const int border_mode = r.zero_border ? 1 : 0, write_sq = r.fuse_sq ? 0 : 1;
+#define SCH_GO(XC) B.launch(k_scharr_products<XC>, dim3((io.H + 63) / 64, (io.W + XC - 1) / XC, S), dim3(64), 0, r.side, io.v, border_mode, io.zs, write_sq)
+    if (r.scharr_xc == 1) SCH_GO(1); else if (r.scharr_xc == 2) SCH_GO(2); else if (r.scharr_xc == 4) SCH_GO(4); else if (r.scharr_xc == 8) SCH_GO(8);
+    else if (r.scharr_xc) SCH_GO(SCH_XC);
+#undef SCH_GO
+}
+// dim-1 pass of the line kernels over the planes of `ps` (plane 0 reads src0 if given)
+static void launch_cols(BuildSink &B, const LevelRoute &r, int lane, const PlaneSet &ps, const double *src0, int S, const LevelIO &io, const IIRPair &cf, double *ck)
+{
+    const dim3 g = lines_grid(io.W, ps.n, S);
+    if (r.cols == COLS_CK) B.launch(k_iir_cols_ck, g, dim3(LINE_THREADS), 0, lane, ps, src0, io.H, io.W, io.P, cf, ck);
+    else if (r.line_c == 3) B.launch(k_iir_cols<3>, g, dim3(LINE_THREADS), 0, lane, ps, src0, io.H, io.W, io.P, cf);
+    else B.launch(k_iir_cols<2>, g, dim3(LINE_THREADS), 0, lane, ps, src0, io.H, io.W, io.P, cf);
+}
+static void launch_cols_fused(BuildSink &B, const LevelRoute &r, const LevelIO &io, int S, const IIRPair &cf, double *ck)
+{
+    const bool tol = r.rows == ROWS_TOL;
+    ColsFusedArgs ca;
+    ca.L = io.v.L; ca.T = r.has_next ? io.T : nullptr; ca.Iy = io.v.Iy; ca.Ix = io.v.Ix; ca.Qyy = io.v.Iyy; ca.Qxx = io.v.Ixx; ca.Qyx = io.v.Iyx;
+    ca.H = io.H; ca.W = io.W; ca.P = io.P; ca.zs = io.zs;
+    ca.src_kind = io.src_kind; ca.srctab = io.srctab;
+    ca.tot = tol ? io.tot : nullptr; ca.tot_stride = io.W; ca.dec = r.dec ? 1 : 0;
+    const dim3 g((io.W + CF4_COLS - 1) / CF4_COLS, 1, S);
+    if (tol && r.dec) B.launch(k_cols_fused<true, true>, g, dim3(256), 0, LN_MAIN, ca, cf, ck);
+    else if (tol) B.launch(k_cols_fused<true, false>, g, dim3(256), 0, LN_MAIN, ca, cf, ck);
+    else B.launch(k_cols_fused<false, false>, g, dim3(256), 0, LN_MAIN, ca, cf, ck);
+}
+// dim-2 pass of the line kernels over the planes of `ps`; checkpointed: plane 0 leaves as the next level's layer too if the route
+// fuses imresize! (odd heights: through k_iir_rows_ck_odd, ps.n == 1)
+static void launch_rows(BuildSink &B, const LevelRoute &r, int lane, const PlaneSet &ps, int S, const LevelIO &io, const IIRPair &cf, double *ck)
+{
+    const RowResize rz = row_resize(r, io);
+    if (r.rows == ROWS_CK && r.resize == RZ_ODD) B.launch(k_iir_rows_ck_odd, dim3(rz_odd_bands(io.H), 1, S), dim3(LINE_THREADS), 0, lane, ps, io.H, io.W, io.P, cf, ck, rz);
+    else if (r.rows == ROWS_CK) B.launch(k_iir_rows_ck, lines_grid(io.H, ps.n, S), dim3(LINE_THREADS), 0, lane, ps, io.H, io.W, io.P, cf, ck, rz);
+    else B.launch(k_iir_rows, lines_grid(io.H, ps.n, S), dim3(LINE_THREADS), 0, lane, ps, io.H, io.W, io.P, cf);
+}
+// k_rows_tol over the planes of `ra`: SL samples per segment, NS segments (rt_seg_len's menu: one instantiation each)
+static void launch_rows_tol(BuildSink &B, int lane, int SL, int NS, const RowsTolArgs &ra, int S, const LevelIO &io, const IIRPair &cf)
+{
+    SegPow sp; rt_seg_pow(cf, SL, sp);
+    const dim3 g((io.H + RT_R - 1) / RT_R, ra.n, S), b(RT_R * NS);
+#define RT_GO(SLV, NSV) B.launch((k_rows_tol<SLV, NSV, RT_R>), g, b, 0, lane, ra, io.H, io.W, io.P, cf, sp)
+    if (NS != RT_NS) { if (SL == 24) RT_GO(24, 2 * RT_NS); else RT_GO(32, 2 * RT_NS); }      // wide rows: 64 segments
+    else switch (SL) { case 4: RT_GO(4, RT_NS); break; case 6: RT_GO(6, RT_NS); break; case 8: RT_GO(8, RT_NS); break; case 10: RT_GO(10, RT_NS); break; case 12: RT_GO(12, RT_NS); break;
+                  case 16: RT_GO(16, RT_NS); break; case 20: RT_GO(20, RT_NS); break; case 24: RT_GO(24, RT_NS); break; case 32: RT_GO(32, RT_NS); break; default: RT_GO(40, RT_NS); break; }
 #undef RT_GO
-                };
-                if (spans) { ProfScope span(ctx, "k_iir_rows"); go(); } else go();
-                if (has_next && !rzf)
-                    B.launch(k_resize, dim3(((size_t)p->H[l + 1] * p->W[l + 1] + 255) / 256, 1, S), dim3(256), 0, LN_MAIN,
-                                       nextL, p->H[l + 1], p->W[l + 1], p->P[l + 1], (const double *)T, H, W, P, zs);
-                return;
-            }
+}
+// ---- Emitters: one per family.  They launch what the route says and select nothing themselves.
+// the layer chain of a target-only level
+static void emit_target(BuildSink &B, const LevelRoute &r, const LevelIO &io, int S, const IIRPair &cf, const slam_pyr *p)
+{
+    PlaneSet pt = {}; pt.p[0] = io.T; pt.coef[0] = 0; pt.fill0[0] = r.zero_border; pt.nrm[0] = nullptr; pt.n = 1; pt.zs = io.zs;
+    launch_cols(B, r, LN_MAIN, pt, io.v.L, S, io, cf, p->ck);
+    launch_rows(B, r, LN_MAIN, pt, S, io, cf, p->ck);
+    if (r.resize == RZ_PLAIN) launch_resize(B, io, S);
+}
+// tolerance build of a single image: the segmented kernels
+static void emit_seg(slam_ctx *ctx, BuildSink &B, const LevelRoute &r, const LevelIO &io, int S, const IIRPair &cf)
+{
+    const int H = io.H, W = io.W, P = io.P;
+    if (r.topo) B.fork(r.side);
+    launch_scharr(B, r, io, S);
+    const PlaneSet ps = level_planes(r, io), psT = plane_slice(ps, 0, 1), psQ = plane_slice(ps, r.np - 3, 3), pc = cum_planes(io);
+    const double *src0 = r.has_next ? (const double *)io.v.L : (const double *)nullptr, *none = nullptr;
+    const dim3 gc((W + 7) / 8, r.np, S), gr((H + 7) / 8, r.np, S), gc3((W + 7) / 8, 3, S), gr3((H + 7) / 8, 3, S);
+    SegPow spc, spr, spc32;
+    seg_pow(cf, H, r.slc, spc); seg_pow(cf, W, r.slr, spr); if (r.slc32) seg_pow(cf, H, r.slc32, spc32);
+    if (r.cols_split) {
+        B.launch(k_iir_seg<true>, dim3((W + 7) / 8, 1, S), dim3(PAR_T), 0, LN_MAIN, psT, src0, H, W, P, cf, spc, r.slc, 0);
+        B.launch(k_iir_seg<true>, gc3, dim3(PAR_T), 0, r.side, psQ, none, H, W, P, cf, spc, r.slc, 0);
+    }
+    else if (r.slc32) B.launch((k_iir_seg<true, 256, 8>), gc, dim3(256), 0, LN_MAIN, ps, src0, H, W, P, cf, spc32, r.slc32, r.cmask);
+    else B.launch(k_iir_seg<true>, gc, dim3(PAR_T), 0, LN_MAIN, ps, src0, H, W, P, cf, spc, r.slc, r.cmask);
+    if (r.rows == ROWS_TOL) {                                     // the blurred layer on the main chain (+ imresize! at even heights)
+        if (!r.topo) B.fork();
+        if (r.has_next) { ProfScope span(ctx, "k_iir_rows"); launch_rows_tol(B, LN_MAIN, r.rt_sl, r.rt_ns, rows_tol_args(r, io, true, 0), S, io, cf); }
+    }
+    else {
+        if (r.cols_split) {
+            B.launch(k_iir_seg<false>, dim3((H + 7) / 8, 1, S), dim3(PAR_T), 0, LN_MAIN, psT, none, H, W, P, cf, spr, r.slr, 0);
+            B.launch(k_iir_seg<false>, gr3, dim3(PAR_T), 0, r.side, psQ, none, H, W, P, cf, spr, r.slr, 0);
         }
-        else if (ck_cols) B.launch(k_iir_cols_ck, lines_grid(W, np, S), dim3(LINE_THREADS), 0, LN_MAIN, ps, src0, H, W, P, cf, p->ck);
-        else if (topo) {
-            B.launch(k_iir_cols<3>, lines_grid(W, 1, S), dim3(LINE_THREADS), 0, LN_MAIN, psT, src0, H, W, P, cf);
-            B.launch(k_iir_cols<3>, lines_grid(W, 3, S), dim3(LINE_THREADS), 0, side, psQ, (const double *)nullptr, H, W, P, cf);
+        else { ProfScope span(ctx, "k_iir_rows"); B.launch(k_iir_seg<false>, gr, dim3(PAR_T), 0, LN_MAIN, ps, none, H, W, P, cf, spr, r.slr, 0); }
+        if (!r.topo) B.fork();
+    }
+    if (r.resize == RZ_PLAIN) launch_resize(B, io, S);
+    // the product planes' integral images, on the branch: running sum along y, then along x (ROWS_TOL: with the dim-2 filter, in one launch)
+    if (r.cum == CUM_SEG && r.slc32) B.launch((k_cum_seg<true, 256, 8>), gc3, dim3(256), 0, r.side_cum, pc, H, W, P, r.slc32);
+    else if (r.cum == CUM_SEG) B.launch(k_cum_seg<true>, gc3, dim3(PAR_T), 0, r.side_cum, pc, H, W, P, r.slc);
+    if (r.rows == ROWS_TOL) launch_rows_tol(B, r.side_cum, r.rt_sl, r.rt_ns, rows_tol_args(r, io, false, 2), S, io, cf);
+    else B.launch(k_cum_seg<false>, gr3, dim3(PAR_T), 0, r.side_cum, pc, H, W, P, r.slr);
+}
+// tolerance build of a batch: k_cols_fused<TOL>, then one k_rows_tol over every plane
+static void emit_tol_batch(slam_ctx *ctx, BuildSink &B, const LevelRoute &r, const LevelIO &io, int S, const IIRPair &cf, const slam_pyr *p)
+{
+    launch_cols_fused(B, r, io, S, cf, p->ck);
+    RowsTolArgs ra = rows_tol_args(r, io, r.has_next, 1);
+    ra.tot = io.tot; ra.tot_stride = io.W; ra.dec = r.dec ? 1 : 0; ra.dbg = r.rt_dbg;
+    { ProfScope span(ctx, "k_iir_rows"); launch_rows_tol(B, LN_MAIN, r.rt_sl, r.rt_ns, ra, S, io, cf); }
+    if (r.resize == RZ_PLAIN) launch_resize(B, io, S);
+}
+// the exact (bit-exact) build.  The integral-image passes of a level only feed the tracking kernels, so they run on the aux lane beside
+// the next level: fork after the row pass (CUM_ROWS_CUM: after the dim-1 stage).
+static void emit_exact(slam_ctx *ctx, BuildSink &B, const LevelRoute &r, const LevelIO &io, int S, const IIRPair &cf, const slam_pyr *p)
+{
+    const int H = io.H, W = io.W, P = io.P;
+    if (r.topo) B.fork(r.side);
+    launch_scharr(B, r, io, S);
+    const PlaneSet ps = level_planes(r, io), psT = plane_slice(ps, 0, 1), psQ = plane_slice(ps, r.np - 3, 3), pc = cum_planes(io);
+    const double *src0 = r.has_next ? (const double *)io.v.L : (const double *)nullptr;
+    if (r.cols == COLS_FUSED) launch_cols_fused(B, r, io, S, cf, p->ck);
+    else if (r.cols_split) { launch_cols(B, r, LN_MAIN, psT, src0, S, io, cf, p->ck); launch_cols(B, r, r.side, psQ, nullptr, S, io, cf, p->ck); }
+    else launch_cols(B, r, LN_MAIN, ps, src0, S, io, cf, p->ck);
+    if (r.cum == CUM_ROWS_CUM) {
+        B.fork();
+        if (r.has_next) {
+            { ProfScope span(ctx, "k_iir_rows"); launch_rows(B, r, LN_MAIN, psT, S, io, cf, p->ck); }
+            if (r.resize == RZ_PLAIN) launch_resize(B, io, S);
         }
-        else if (S == 1) B.launch(k_iir_cols<3>, lines_grid(W, np, S), dim3(LINE_THREADS), 0, LN_MAIN, ps, src0, H, W, P, cf);
-        else B.launch(k_iir_cols<2>, lines_grid(W, np, S), dim3(LINE_THREADS), 0, LN_MAIN, ps, src0, H, W, P, cf);
-        // bandwidth-bound launches (many images x a large level) take the checkpointed row kernel (2R+1W instead of 2R+2W)
-        const bool ck_rows = p->ck != nullptr && mode != 0 && W >= 64 && (size_t)Sall * np * H * W * 8 >= ck_min_bytes();
-        // ... with the imresize! into the next level fused into the blurred layer's backward sweep (even H: exact 2:1 row ratio; odd H:
-        // k_iir_rows_ck_odd -- decided below, where the number of planes of the launch is known)
-        static const bool no_rows_resize = getenv("SLAMHIP_NO_ROWS_RESIZE") != nullptr;
-        const bool rz_odd_cand = ck_rows && has_next && (H & 1) != 0 && !no_rows_resize;
-        bool rows_resize = ck_rows && has_next && (H & 1) == 0 && !no_rows_resize;
-        bool rows_odd = false;
-        RowResize rz = {};
-        auto rz_decide = [&](int nplanes) {
-            if (rz_odd_cand && nplanes == 1 && rz_odd_ok(p, l)) rows_resize = rows_odd = true;
-            if (rows_resize) { rz.dst = nextL; rz.Hd = p->H[l + 1]; rz.Wd = p->W[l + 1]; rz.Pd = p->P[l + 1]; }
-        };
-        // batches: the product planes take k_rows_cum (dim-2 stage + integral image in one launch) on the aux lane, forked after the
-        // dim-1 stage; the blurred layer alone stays on the main lane (+ imresize!), so the next level waits for nothing else
-        static const bool no_rows_cum = getenv("SLAMHIP_NO_ROWS_CUM") != nullptr;
-        static const bool no_fused_cum = getenv("SLAMHIP_NO_FUSED_CUM") != nullptr;
-        const int cf_bands = (H + 63) / 64;
-        if (!topo && Sall >= 8 && mode != 0 && W >= 64 && cf_bands <= CF_MAXW && p->alloc->rck != nullptr && !no_rows_cum && !no_fused_cum) {
-            B.fork();
-            if (has_next) {
-                PlaneSet pT = {}; pT.p[0] = ps.p[0]; pT.coef[0] = ps.coef[0]; pT.fill0[0] = ps.fill0[0]; pT.n = 1; pT.zs = zs;
-                rz_decide(1);
-                if (spans) { ProfScope span(ctx, "k_iir_rows");
-                    if (ck_rows) launch_rows_ck(B, pT, 1, S, H, W, P, cf, p->ck, rz, rows_odd);
-                    else B.launch(k_iir_rows, lines_grid(H, 1, S), dim3(LINE_THREADS), 0, LN_MAIN, pT, H, W, P, cf); }
-                else if (ck_rows) launch_rows_ck(B, pT, 1, S, H, W, P, cf, p->ck, rz, rows_odd);
-                else B.launch(k_iir_rows, lines_grid(H, 1, S), dim3(LINE_THREADS), 0, LN_MAIN, pT, H, W, P, cf);
-                if (!rows_resize)
-                    B.launch(k_resize, dim3(((size_t)p->H[l + 1] * p->W[l + 1] + 255) / 256, 1, S), dim3(256), 0, LN_MAIN,
-                                       nextL, p->H[l + 1], p->W[l + 1], p->P[l + 1], (const double *)T, H, W, P, zs);
-            }
-            PlaneSet pq = {};
-            for (int q = 0; q < 3; q++) { pq.p[q] = ps.p[np - 3 + q]; pq.coef[q] = ps.coef[np - 3 + q]; pq.fill0[q] = ps.fill0[np - 3 + q]; }
-            pq.n = 3; pq.zs = zs;
-            const size_t lds = (size_t)cf_bands * RC_LDS_DOUBLES * sizeof(double);
-            B.launch(k_rows_cum, dim3(1, 3, S), dim3(cf_bands * 64), lds, LN_AUX, pq, H, W, P, cf, p->alloc->rck);
-            return;
-        }
-        if (!topo) rz_decide(np);
-        if (topo) {
-            B.launch(k_iir_rows, lines_grid(H, 1, S), dim3(LINE_THREADS), 0, LN_MAIN, psT, H, W, P, cf);
-            B.launch(k_iir_rows, lines_grid(H, 3, S), dim3(LINE_THREADS), 0, side, psQ, H, W, P, cf);
-        }
-        else if (spans) { ProfScope span(ctx, "k_iir_rows");
-            if (ck_rows) launch_rows_ck(B, ps, np, S, H, W, P, cf, p->ck, rz, rows_odd);
-            else B.launch(k_iir_rows, lines_grid(H, np, S), dim3(LINE_THREADS), 0, LN_MAIN, ps, H, W, P, cf); }
-        else if (ck_rows) launch_rows_ck(B, ps, np, S, H, W, P, cf, p->ck, rz, rows_odd);
-        else B.launch(k_iir_rows, lines_grid(H, np, S), dim3(LINE_THREADS), 0, LN_MAIN, ps, H, W, P, cf);
-        if (!topo) B.fork();
-        if (has_next && !rows_resize)
-            B.launch(k_resize, dim3(((size_t)p->H[l + 1] * p->W[l + 1] + 255) / 256, 1, S), dim3(256), 0, LN_MAIN,
-                               nextL, p->H[l + 1], p->W[l + 1], p->P[l + 1], (const double *)T, H, W, P, zs);
-        const int cf_seg = cf_bands <= CF_MAXW ? 1 : (cf_bands + CF_SEGW - 1) / CF_SEGW;      // taller planes: row segments of CF_SEGW bands, one workgroup each, chained through p->alloc->xc
-        if (Sall >= 8 && !no_fused_cum && (cf_seg == 1 || (p->alloc->xc != nullptr && cf_seg <= p->alloc->xseg))) {      // batches: one-pass integral image
-            const int nw = cf_seg == 1 ? cf_bands : CF_SEGW;
-            const size_t lds = ((size_t)nw * CF_W * CF_LS + (size_t)nw * 2 * CF_W) * sizeof(double);
-            const size_t xo = (size_t)z0 * 3 * (size_t)(cf_seg > 1 ? cf_seg - 1 : 1);
-            if (cf_seg == 1) B.launch(k_cum_fused<false>, dim3(1, 3, S), dim3(nw * 64), lds, LN_AUX, pc, H, W, P, (double *)nullptr, (int *)nullptr);
-            else B.launch(k_cum_fused<true>, dim3(cf_seg, 3, S), dim3(nw * 64), lds, LN_AUX, pc, H, W, P, p->alloc->xc + xo * W, p->alloc->xf + xo);
-            return;
-        }
-        if (S == 1) B.launch(k_cum_cols<3>, lines_grid(W, 3, S), dim3(LINE_THREADS), 0, side_cum, pc, H, W, P);
-        else B.launch(k_cum_cols<2>, lines_grid(W, 3, S), dim3(LINE_THREADS), 0, LN_AUX, pc, H, W, P);
-        B.launch(k_cum_rows, lines_grid(H, 3, S), dim3(LINE_THREADS), 0, S == 1 ? side_cum : LN_AUX, pc, H, W, P);
+        const size_t lds = (size_t)r.cf_bands * RC_LDS_DOUBLES * sizeof(double);
+        B.launch(k_rows_cum, dim3(1, 3, S), dim3(r.cf_bands * 64), lds, LN_AUX, plane_slice(ps, r.np - 3, 3, false), H, W, P, cf, p->alloc->rck);
+        return;
+    }
+    if (r.topo) { launch_rows(B, r, LN_MAIN, psT, S, io, cf, p->ck); launch_rows(B, r, r.side, psQ, S, io, cf, p->ck); }
+    else { ProfScope span(ctx, "k_iir_rows"); launch_rows(B, r, LN_MAIN, ps, S, io, cf, p->ck); }
+    if (!r.topo) B.fork();
+    if (r.resize == RZ_PLAIN) launch_resize(B, io, S);
+    const int nw = r.cum == CUM_FUSED ? r.cf_bands : CF_SEGW;
+    const size_t lds = ((size_t)nw * CF_W * CF_LS + (size_t)nw * 2 * CF_W) * sizeof(double);
+    const size_t xo = (size_t)io.z0 * 3 * (size_t)(r.cum_seg - 1);
+    if (r.cum == CUM_FUSED) B.launch(k_cum_fused<false>, dim3(1, 3, S), dim3(nw * 64), lds, LN_AUX, pc, H, W, P, (double *)nullptr, (int *)nullptr);
+    else if (r.cum == CUM_FUSED_SEG) B.launch(k_cum_fused<true>, dim3(r.cum_seg, 3, S), dim3(nw * 64), lds, LN_AUX, pc, H, W, P, p->alloc->xc + xo * W, p->alloc->xf + xo);
+    else {
+        if (r.line_c == 3) B.launch(k_cum_cols<3>, lines_grid(W, 3, S), dim3(LINE_THREADS), 0, r.side_cum, pc, H, W, P);
+        else B.launch(k_cum_cols<2>, lines_grid(W, 3, S), dim3(LINE_THREADS), 0, r.side_cum, pc, H, W, P);
+        B.launch(k_cum_rows, lines_grid(H, 3, S), dim3(LINE_THREADS), 0, r.side_cum, pc, H, W, P);
     }
 }
-
-
 // Launch every kernel of one pyramid build (see BuildSink above for where they go).  A large batch is built in SUB-BATCHES of the big
 // levels: the 3.5 intermediate planes a level's dim-1 stage leaves behind (12.7 MB per 370 x 1226 image) are re-read by its dim-2 stage
 // while they still sit in the 256 MiB Infinity Cache, instead of after the whole batch's 1.6 GB have gone through it.
-static void launch_build(slam_ctx *ctx, slam_pyr *p, int mode, const IIRPair &cf, BuildSink &B, bool spans, int S = 1, int src_kind = 0, bool target = false)
+static void launch_build(slam_ctx *ctx, slam_pyr *p, int mode, const IIRPair &cf, BuildSink &B, int S = 1, int src_kind = 0, bool target = false)
 {
-    bool fast = mode == 3;
-    if (fast && (seg_len(p->H[0], PAR_T / 8) > PAR_SLMAX || seg_len(p->W[0], PAR_T / 8) > PAR_SLMAX)) fast = false;   // lines > 2048 samples: exact kernels
-    if (fast && S >= tol_batch_min_s()) fast = false;   // the segmented kernels buy latency for ONE image; with several images per launch the exact kernels are faster (and trivially within the tolerance)
-    static const int chunk_mb = [] { const char *v = getenv("SLAMHIP_PYR_CHUNK_MB"); return v ? atoi(v) : 0; }();      // intermediate planes of a sub-batch, MB (0: no sub-batches)
+    const int chunk_mb = knobs().chunk_mb;
     for (int l = 0; l < p->levels; l++) {
         int C = S;
         if (chunk_mb > 0 && S >= 8 && mode != 0) {
@@ -2646,29 +2659,31 @@ static void launch_build(slam_ctx *ctx, slam_pyr *p, int mode, const IIRPair &cf
             const size_t want = (size_t)chunk_mb << 20;
             if (per_image * S > 2 * want) { C = (int)std::max<size_t>(4, want / per_image); C = std::min(C, S); }
         }
-        for (int z0 = 0; z0 < S; z0 += C) launch_level(ctx, p, mode, cf, B, spans, std::min(C, S - z0), src_kind, target, l, z0, S, fast);
+        for (int z0 = 0; z0 < S; z0 += C) {
+            const int Sc = std::min(C, S - z0);
+            const LevelRoute r = level_route(p, mode, l, Sc, S, target, B.lanes());
+            const LevelIO io = level_io(p, l, z0, S, src_kind);
+            if (r.family == FAM_TARGET) emit_target(B, r, io, Sc, cf, p);
+            else if (r.family == FAM_SEG) emit_seg(ctx, B, r, io, Sc, cf);
+            else if (r.family == FAM_TOLB) emit_tol_batch(ctx, B, r, io, Sc, cf, p);
+            else if (r.family == FAM_EXACT) emit_exact(ctx, B, r, io, Sc, cf, p);
+        }
     }
 }
 
-// level 0 of an S-image build runs k_cols_fused (which can ingest the source images itself): launch_build's conditions
+// level 0 of an S-image build runs k_cols_fused, which can ingest the source images itself (else k_gather_images* fills layer 0)
 static bool level0_fused(const slam_pyr *p, int mode, int S)
 {
-    static const bool off = getenv("SLAMHIP_NO_COLS_FUSED") != nullptr || getenv("SLAMHIP_NO_SQ_FUSE") != nullptr || getenv("SLAMHIP_NO_CK_COLS") != nullptr ||
-                            getenv("SLAMHIP_NO_FUSED_INGEST") != nullptr;
-    if (off || mode == 0 || p->ck == nullptr || p->alloc->srctab == nullptr || p->H[0] < 64) return false;
-    if (mode == 3 && S < tol_batch_min_s() && !(seg_len(p->H[0], PAR_T / 8) > PAR_SLMAX || seg_len(p->W[0], PAR_T / 8) > PAR_SLMAX)) return false;   // the segmented kernels
-    const int np_ = p->levels > 1 ? 4 : 3;
-    return (size_t)S * np_ * p->H[0] * p->W[0] * 8 >= ck_min_bytes();
+    return level_route(p, mode, 0, S, S, false, false).cols == COLS_FUSED && p->alloc->srctab != nullptr && !knobs().no_fused_ingest;
 }
 __global__ void k_set_ptrs(const void **tab, ImgPtrs src)
 {
     if (threadIdx.x < BATCH_MAX) tab[threadIdx.x] = src.p[threadIdx.x];
 }
 
-// Enqueue the whole pyramid build on ctx->stream; layer 0 must already hold the image.
-// Normal path: one hipGraph replay (captured once per (mode, sigma): two-stream
-// fork/join DAG, ~25 kernel nodes) -> one host launch instead of ~25.  With
-// profiling spans enabled (or SLAMHIP_NO_GRAPH=1) the same kernels are launched
+// Enqueue the whole pyramid build on ctx->stream; layer 0 must already hold the image (or level 0 ingests it: src_kind).
+// Normal path: one hipGraph replay (built once per (mode, sigma, S, SLAMHIP_CK_MIN_MB, src_kind): the lanes of BuildSink, ~25 kernel
+// nodes) -> one host launch instead of ~25.  With profiling spans enabled (or SLAMHIP_NO_GRAPH=1) the same kernels are launched
 // directly, serially, so that per-kernel hipEvent spans are meaningful.
 static int enqueue_build(slam_ctx *ctx, slam_pyr *p, int mode_flags, double sigma, int S = 1, int src_kind = 0)
 {
@@ -2680,8 +2695,7 @@ static int enqueue_build(slam_ctx *ctx, slam_pyr *p, int mode_flags, double sigm
     // SLAM_PYR_CHAIN: the build as ONE chain on the calling context's stream (no forked integral-image branch).  A single build takes
     // ~15 % longer, but it occupies one hardware queue instead of two and its replay costs the host a third (31 vs 84 us): the
     // choice when several builds of consecutive frames are kept in flight on several contexts (3 in flight: 170 us per build, 376 forked)
-    static const bool linear_env = getenv("SLAMHIP_LINEAR_GRAPH") != nullptr;
-    const bool chain = (mode_flags & SLAM_PYR_CHAIN) != 0 || linear_env;
+    const bool chain = (mode_flags & SLAM_PYR_CHAIN) != 0 || knobs().linear_graph;
     const int mode = mode_flags & ~SLAM_PYR_FLAGS;
     p->target_only = target;                                      // (the other members of a batch are marked by the batch entry points)
     p->tol_planes = mode == 3;
@@ -2690,11 +2704,10 @@ static int enqueue_build(slam_ctx *ctx, slam_pyr *p, int mode_flags, double sigm
     IIRPair cf; cf.c[0] = slam_iir_coef(sigma); cf.c[1] = slam_iir_coef(4.0);   // lucas_kanade.jl:112
     if (mode == 0) { int rc = build_norm(ctx, p, sigma); if (rc) return rc; }
     hipStream_t st = ctx->stream;
-    static const bool no_graph = getenv("SLAMHIP_NO_GRAPH") != nullptr;
-    if (ctx->prof_on || no_graph) {
+    if (ctx->prof_on || knobs().no_graph) {
         ProfScope span_all(ctx, "pyr_update");
         BuildSink B; B.st = st;
-        launch_build(ctx, p, mode, cf, B, ctx->prof_on, S, src_kind & 15, target);
+        launch_build(ctx, p, mode, cf, B, S, src_kind & 15, target);
         HIP_TRY(ctx, hipGetLastError());
         return SLAM_OK;
     }
@@ -2708,7 +2721,7 @@ static int enqueue_build(slam_ctx *ctx, slam_pyr *p, int mode_flags, double sigm
             hipError_t e = hipGraphCreate(&graph, 0);
             if (e == hipSuccess) {
                 BuildSink B; B.graph = graph; B.forked = !chain;
-                launch_build(ctx, p, mode, cf, B, false, S, src_kind & 15, target);
+                launch_build(ctx, p, mode, cf, B, S, src_kind & 15, target);
                 e = B.err;
             }
             if (e == hipSuccess) e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
@@ -2719,10 +2732,13 @@ static int enqueue_build(slam_ctx *ctx, slam_pyr *p, int mode_flags, double sigm
         // (launched under the lock: one executable graph is not launched from two threads at the same moment)
         if (exec) HIP_TRY(ctx, hipGraphLaunch(exec, st));
     }
-    if (!exec) { BuildSink B; B.st = st; launch_build(ctx, p, mode, cf, B, false, S, src_kind & 15, target); }
+    if (!exec) { BuildSink B; B.st = st; launch_build(ctx, p, mode, cf, B, S, src_kind & 15, target); }
     HIP_TRY(ctx, hipGetLastError());
     return SLAM_OK;
 }
+
+// the update modes the entry points take: 1 (exact) or 3 (tolerance) with any SLAM_PYR_* flags; one image also the plain mode 0 (Fill(0) borders)
+static inline bool pyr_mode_ok(int mode, bool single) { const int m = mode & ~SLAM_PYR_FLAGS; return m == 1 || m == 3 || (single && mode == 0); }
 
 // dense column-major H x W image (device) -> pitched layer 0
 static void ingest_dense(slam_ctx *ctx, slam_pyr *p, const double *image_dev)
@@ -2819,47 +2835,30 @@ int slam_pyr_create_batch(slam_ctx *ctx, int H, int W, int pyramid_levels, int S
     return pyr_create_n(ctx, H, W, pyramid_levels, S, out);
 }
 
-// pyrs[0..S) must be the members of one slam_pyr_create_batch call, in order
-int slam_pyr_update_batch_dev(slam_ctx *ctx, slam_pyr *const *pyrs, const double *const *images_dev, int S, int mode, double sigma, int sync)
+// pyrs[0..S) must be the members of one slam_pyr_create_batch call, in order; images: S device pointers to Float64 or (u8) 8-bit frames
+static int update_batch(slam_ctx *ctx, slam_pyr *const *pyrs, const void *const *images, bool u8, int S, int mode, double sigma, int sync)
 {
-    ARG_TRY(ctx, ctx != nullptr && pyrs != nullptr && images_dev != nullptr && S >= 1 && S <= BATCH_MAX && ((mode & ~SLAM_PYR_FLAGS) == 1 || (mode & ~SLAM_PYR_FLAGS) == 3) && sigma > 0);
+    ARG_TRY(ctx, ctx != nullptr && pyrs != nullptr && images != nullptr && S >= 1 && S <= BATCH_MAX && pyr_mode_ok(mode, false) && sigma > 0);
     slam_pyr *p0 = pyrs[0];
     ARG_TRY(ctx, p0 != nullptr && p0->batch_index == 0 && p0->batch_size == S);
-    for (int s = 0; s < S; s++) ARG_TRY(ctx, pyrs[s] != nullptr && pyrs[s]->alloc == p0->alloc && pyrs[s]->batch_index == s && images_dev[s] != nullptr);
+    for (int s = 0; s < S; s++) ARG_TRY(ctx, pyrs[s] != nullptr && pyrs[s]->alloc == p0->alloc && pyrs[s]->batch_index == s && images[s] != nullptr);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    ImgPtrs ip;
-    for (int s = 0; s < BATCH_MAX; s++) ip.p[s] = s < S ? images_dev[s] : nullptr;
+    ImgPtrs ip; ImgPtrsU8 ip8;
+    for (int s = 0; s < BATCH_MAX; s++) { ip.p[s] = s < S ? (const double *)images[s] : nullptr; ip8.p[s] = (const unsigned char *)ip.p[s]; }
     const size_t n = (size_t)p0->H[0] * p0->W[0];
     const bool fused_ingest = level0_fused(p0, mode & ~SLAM_PYR_FLAGS, S);          // the level-0 kernel reads the source images itself and writes the layer
     if (fused_ingest) hipLaunchKernelGGL(k_set_ptrs, dim3(1), dim3(BATCH_MAX), 0, ctx->stream, p0->alloc->srctab, ip);
+    else if (u8) hipLaunchKernelGGL(k_gather_images_u8, dim3((n + 255) / 256, 1, S), dim3(256), 0, ctx->stream, ip8, p0->plane(0, 0), p0->H[0], p0->W[0], p0->P[0], p0->zstride);
     else hipLaunchKernelGGL(k_gather_images, dim3((n + 255) / 256, 1, S), dim3(256), 0, ctx->stream, ip, p0->plane(0, 0), p0->H[0], p0->W[0], p0->P[0], p0->zstride);
-    int rc = enqueue_build(ctx, p0, mode, sigma, S, fused_ingest ? 1 : 0);
+    int rc = enqueue_build(ctx, p0, mode, sigma, S, fused_ingest ? (u8 ? 2 : 1) : 0);
     for (int s = 0; s < S; s++) { pyrs[s]->target_only = (mode & SLAM_PYR_TARGET_ONLY) != 0; pyrs[s]->tol_planes = (mode & ~SLAM_PYR_FLAGS) == 3; }
     if (rc) return rc;
     if (sync) HIP_TRY(ctx, slam_stream_wait(ctx->stream));
     return SLAM_OK;
 }
-
+int slam_pyr_update_batch_dev(slam_ctx *ctx, slam_pyr *const *pyrs, const double *const *images_dev, int S, int mode, double sigma, int sync) { return update_batch(ctx, pyrs, (const void *const *)images_dev, false, S, mode, sigma, sync); }
 // 8-bit frames already in HBM (column-major H x W bytes, as the KITTI reader decodes them): converted on the device
-int slam_pyr_update_batch_u8_dev(slam_ctx *ctx, slam_pyr *const *pyrs, const uint8_t *const *images_u8_dev, int S, int mode, double sigma, int sync)
-{
-    ARG_TRY(ctx, ctx != nullptr && pyrs != nullptr && images_u8_dev != nullptr && S >= 1 && S <= BATCH_MAX && ((mode & ~SLAM_PYR_FLAGS) == 1 || (mode & ~SLAM_PYR_FLAGS) == 3) && sigma > 0);
-    slam_pyr *p0 = pyrs[0];
-    ARG_TRY(ctx, p0 != nullptr && p0->batch_index == 0 && p0->batch_size == S);
-    for (int s = 0; s < S; s++) ARG_TRY(ctx, pyrs[s] != nullptr && pyrs[s]->alloc == p0->alloc && pyrs[s]->batch_index == s && images_u8_dev[s] != nullptr);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    ImgPtrsU8 ip;
-    for (int s = 0; s < BATCH_MAX; s++) ip.p[s] = s < S ? images_u8_dev[s] : nullptr;
-    const size_t n = (size_t)p0->H[0] * p0->W[0];
-    const bool fused_ingest = level0_fused(p0, mode & ~SLAM_PYR_FLAGS, S);
-    if (fused_ingest) { ImgPtrs iq; for (int s = 0; s < BATCH_MAX; s++) iq.p[s] = (const double *)ip.p[s]; hipLaunchKernelGGL(k_set_ptrs, dim3(1), dim3(BATCH_MAX), 0, ctx->stream, p0->alloc->srctab, iq); }
-    else hipLaunchKernelGGL(k_gather_images_u8, dim3((n + 255) / 256, 1, S), dim3(256), 0, ctx->stream, ip, p0->plane(0, 0), p0->H[0], p0->W[0], p0->P[0], p0->zstride);
-    int rc = enqueue_build(ctx, p0, mode, sigma, S, fused_ingest ? 2 : 0);
-    for (int s = 0; s < S; s++) { pyrs[s]->target_only = (mode & SLAM_PYR_TARGET_ONLY) != 0; pyrs[s]->tol_planes = (mode & ~SLAM_PYR_FLAGS) == 3; }
-    if (rc) return rc;
-    if (sync) HIP_TRY(ctx, slam_stream_wait(ctx->stream));
-    return SLAM_OK;
-}
+int slam_pyr_update_batch_u8_dev(slam_ctx *ctx, slam_pyr *const *pyrs, const uint8_t *const *images_u8_dev, int S, int mode, double sigma, int sync) { return update_batch(ctx, pyrs, (const void *const *)images_u8_dev, true, S, mode, sigma, sync); }
 
 int slam_pyr_destroy(slam_pyr *p)
 {
@@ -2875,7 +2874,7 @@ int slam_pyr_destroy(slam_pyr *p)
 
 int slam_pyr_update_dev(slam_ctx *ctx, slam_pyr *p, const double *image_dev, int mode, double sigma, int sync)
 {
-    ARG_TRY(ctx, ctx != nullptr && p != nullptr && image_dev != nullptr && (mode == 0 || (mode & ~SLAM_PYR_FLAGS) == 1 || (mode & ~SLAM_PYR_FLAGS) == 3) && sigma > 0);
+    ARG_TRY(ctx, ctx != nullptr && p != nullptr && image_dev != nullptr && pyr_mode_ok(mode, true) && sigma > 0);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     ingest_dense(ctx, p, image_dev);
     int rc = enqueue_build(ctx, p, mode, sigma);
@@ -2886,7 +2885,7 @@ int slam_pyr_update_dev(slam_ctx *ctx, slam_pyr *p, const double *image_dev, int
 
 int slam_pyr_update(slam_ctx *ctx, slam_pyr *p, const double *image, int mode, double sigma)
 {
-    ARG_TRY(ctx, ctx != nullptr && p != nullptr && image != nullptr && (mode == 0 || (mode & ~SLAM_PYR_FLAGS) == 1 || (mode & ~SLAM_PYR_FLAGS) == 3) && sigma > 0);
+    ARG_TRY(ctx, ctx != nullptr && p != nullptr && image != nullptr && pyr_mode_ok(mode, true) && sigma > 0);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     void *stage;
     int rc = slam_scratch2(ctx, (size_t)p->H[0] * p->W[0] * 8, &stage);
@@ -2901,7 +2900,7 @@ int slam_pyr_update(slam_ctx *ctx, slam_pyr *p, const double *image, int mode, d
 
 int slam_pyr_update_u8(slam_ctx *ctx, slam_pyr *p, const uint8_t *image_u8, int mode, double sigma)
 {
-    ARG_TRY(ctx, ctx != nullptr && p != nullptr && image_u8 != nullptr && (mode == 0 || (mode & ~SLAM_PYR_FLAGS) == 1 || (mode & ~SLAM_PYR_FLAGS) == 3) && sigma > 0);
+    ARG_TRY(ctx, ctx != nullptr && p != nullptr && image_u8 != nullptr && pyr_mode_ok(mode, true) && sigma > 0);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t n = (size_t)p->H[0] * p->W[0];
     void *d8;
@@ -2918,7 +2917,7 @@ int slam_pyr_update_u8(slam_ctx *ctx, slam_pyr *p, const uint8_t *image_u8, int 
 // the same from an 8-bit image already in HBM (e.g. copied there by the caller from pinned memory on ctx's stream); sync == 0: enqueue only
 int slam_pyr_update_u8_dev(slam_ctx *ctx, slam_pyr *p, const uint8_t *image_u8_dev, int mode, double sigma, int sync)
 {
-    ARG_TRY(ctx, ctx != nullptr && p != nullptr && image_u8_dev != nullptr && (mode == 0 || (mode & ~SLAM_PYR_FLAGS) == 1 || (mode & ~SLAM_PYR_FLAGS) == 3) && sigma > 0);
+    ARG_TRY(ctx, ctx != nullptr && p != nullptr && image_u8_dev != nullptr && pyr_mode_ok(mode, true) && sigma > 0);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t n = (size_t)p->H[0] * p->W[0];
     hipLaunchKernelGGL(k_u8_to_f64, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, p->plane(0, 0), (const unsigned char *)image_u8_dev, p->H[0], p->W[0], p->P[0]);
