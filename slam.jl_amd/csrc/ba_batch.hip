@@ -179,14 +179,263 @@ struct BAPool {
 std::atomic<long> n_xretry{0};       // calls that were solved again on one workgroup per window (slam_debug_ba_xretries)
 BAPool &ba_pool()
 {
-    static const int env_threads = [] { const char *v = getenv("SLAMHIP_BA_THREADS"); return v ? atoi(v) : 0; }();
-    const int hw = (int)std::thread::hardware_concurrency();
+    const int hw = (int)std::thread::hardware_concurrency(), env_threads = ba_knobs().threads;
     static BAPool pool(std::max(0, (env_threads > 0 ? env_threads : std::min(std::max(hw / 4, 4), 32)) - 1));
     return pool;
 }
 }  // namespace
 void ba_parallel_for(int count, const std::function<void(int)> &fn) { ba_pool().run(count, fn); }
 int ba_pool_threads() { return (int)ba_pool().th.size() + 1; }
+
+// ---- slam_local_ba_batch in steps over one plain state struct: batch_arena -> batch_stage -> batch_route -> batch_enqueue -> batch_scatter
+namespace {
+struct BatchCall {
+    slam_ctx *ctx = nullptr; int S = 0, NB = 0;
+    BatchIn in;                                    // prefix sums over the caller's arrays + the plans of all S windows
+    std::vector<int> st_code, batch, single;      // [S] per-window code; the windows the batch kernels take (batch_takes); those solved one by one afterwards
+    std::vector<SolveRoute> route;                // [S] the batch's solve route of a window
+    // region-major arena: [window table | result table | list of k_ba_window's windows | uploads of every window][zero regions][work regions][results]
+    std::vector<size_t> up, ze, wk, rs;           // [NB + 1] prefix sums of the four regions
+    size_t tab_bytes = 0, rtab_bytes = 0, up_total = 0, zero_base = 0, work_base = 0, res_base = 0, total = 0;
+    char *A = nullptr, *stage = nullptr, *res_host = nullptr; BAWin *tab_h = nullptr; BARes *rtab_h = nullptr;
+    int n_early = 0; bool early_sent = false;     // windows whose staged bytes leave before the launch sequence: all but the last part of a large upload
+    float dev_ms = 0;
+    BAPlan &plan(int k) { return in.pl[batch[k]]; }
+    size_t list_off() const { return tab_bytes + rtab_bytes - al((size_t)NB * 4); }      // (the list travels behind the result table in the same upload)
+    const LMState &state(int k) const { return *(const LMState *)(res_host + (rtab_h[k].off_state - res_base)); }
+};
+// Every launch size of the batch, decided once from the staged table.
+struct BatchRoute {
+    // windows one workgroup can keep to itself (k_ba_window: <= 5 free poses, consecutive; BAWin::pad = 1); the others take the launch-per-phase kernels
+    std::vector<int> small_list; int NS = 0; size_t lds_bw = 0;
+    bool all_small = false;
+    int gx_obs = 1, gx_grp = 1, gx_red = 1;        // grid x extents: the largest launch-per-phase window's
+    // small groups everywhere (the reference's window shape: 16 points x 10 observers): 256-thread workgroups, two to three per compute unit
+    int TT = SG_T; size_t lds_sg = 0, lds_band = 0;
+    void (*build_vec)(const BAWin *, int) = nullptr; void (*update_vec)(const BAWin *, int, int, int, int) = nullptr;      // k_schur_groups_b / k_update_groups_b<., false> at TT threads
+    int ug_n = 6, ug_ob = 8, ug_sb = 8; size_t lds_ug = 0;      // k_update_groups_b's LDS arrays at the batch's own sizes
+    // the Schur products on the matrix cores (k_schur_groups_m, BAWin::pad2 = 1): 256-thread groups whose matrix Y (3 x points columns, 6 x window slots rows) fits
+    // LDS beside two more workgroups.  Per window: one whose Y does not fit (a wide band with few observations per point) does not take the matrix cores from the
+    // others.  The vector kernel's lds_sg and the cost-only linearisation are shared: the vector build stores its own evaluation, the matrix-core build none
+    int n_mfma = 0, n_vec = 0; size_t lds_m = 0;
+    // A batch of >= 32 windows runs its launch-per-phase kernels as TWO halves on two streams: while one half sits in its latency-bound kernels (k_band_solve_b:
+    // one workgroup per window, k_trial_poses_b, k_control_b -- ~75 us of an iteration) the other half's builds fill the chip
+    bool two_streams = false;
+    // two workgroups per window (k_ba_window) only while BOTH halves of EVERY window are resident at once -- they wait for each other: one
+    // workgroup per compute unit (136-148 KB of LDS), so 2 x NS workgroups must fit the device's compute units (hipDeviceProp_t, not a
+    // constant), the stream must not be CU-masked (a mask says nothing about how many of an XCD's units are left, and the halves b / b + 8
+    // need two on the SAME XCD) and the architecture must be the one the memory-side hand-over was validated on (ctx->xwg_ok).  Other
+    // processes' kernels can still hold LDS the count knows nothing about: the kernel's wait is bounded (BAKnobs::xlimit) and a window whose halves
+    // missed each other comes back with chol_fail = 2 -- the call is then solved again with one workgroup per window (batch_enqueue).
+    int two = 0, two_grid = 0;
+};
+
+int batch_arena(BatchCall &c)
+{
+    const int NB = c.NB;
+    c.up.resize(NB + 1); c.ze.resize(NB + 1); c.wk.resize(NB + 1); c.rs.resize(NB + 1);
+    c.tab_bytes = al((size_t)NB * sizeof(BAWin)); c.rtab_bytes = al((size_t)NB * sizeof(BARes)) + al((size_t)NB * 4);   // (+ the list of k_ba_window's windows)
+    c.up[0] = c.tab_bytes + c.rtab_bytes; c.ze[0] = 0; c.wk[0] = 0; c.rs[0] = 0;
+    for (int k = 0; k < NB; k++) {
+        const BAPlan &q = c.plan(k);
+        c.up[k + 1] = c.up[k] + q.up_bytes; c.ze[k + 1] = c.ze[k] + q.zero_bytes; c.wk[k + 1] = c.wk[k] + q.work_bytes;
+        c.rs[k + 1] = c.rs[k] + al(sizeof(LMState)) + al((6 * (size_t)q.P + 3 * (size_t)q.M) * 8 + 8) + al((size_t)q.O + 8);
+    }
+    c.up_total = c.up[NB]; c.zero_base = c.up_total; c.work_base = c.zero_base + c.ze[NB]; c.res_base = c.work_base + c.wk[NB]; c.total = c.res_base + c.rs[NB];
+    if (const int rc = slam_scratch(c.ctx, c.total, (void **)&c.A)) return rc;
+    if (const int rc = slam_pinned(c.ctx, c.up_total + c.rs[NB], (void **)&c.stage)) return rc;
+    c.res_host = c.stage + c.up_total; c.tab_h = (BAWin *)c.stage; c.rtab_h = (BARes *)(c.stage + c.tab_bytes);
+    return SLAM_OK;
+}
+// stage window k of the batch: its uploaded region, its table entries
+void emit_window(BatchCall &c, int k)
+{
+    BAPlan &q = c.plan(k);
+    BAWin &w = c.tab_h[k];
+    memset(&w, 0, sizeof w);
+    BARes &r = c.rtab_h[k];
+    r.off_state = c.res_base + c.rs[k]; r.off_theta = r.off_state + al(sizeof(LMState)); r.off_outl = r.off_theta + al((6 * (size_t)q.P + 3 * (size_t)q.M) * 8 + 8);
+    char *zero = c.A + c.zero_base + c.ze[k];
+    // Kept exactly as found: a window whose set-up fails in ba_emit (q.err: a point observed twice by one pose) stays in the table with pad = 2 -- every batch kernel,
+    // k_results_b included, returns at once for it, it is in no list of k_ba_window's and its (zeroed) table entry is never read for a launch size
+    if (ba_emit(q, c.A + c.up[k], zero, c.A + c.work_base + c.wk[k], c.stage + c.up[k])) { w.pad = 2; return; }
+    slam_ba *b = q.ba; b->device = c.ctx->device; b->owns_arena = false; b->arena = c.A;
+    w.d = b->d;
+    w.B = band_args(b, c.route[c.batch[k]], b->reduce, 0.0); w.B.epoch = 1;
+    w.nb_obs = b->nblocks_obs; w.nb_pts = b->nblocks_pts; w.n_red = (w.d.P * (w.d.whb + 1) * 36 + w.d.P * 12 + 255) / 256;
+    w.ksplit = q.ksplit; w.bwx = q.window ? (double *)(zero + q.o_bwx) : nullptr;
+    if (q.window && q.M > 1) {
+        // the split point of k_ba_window's two workgroups: an observation costs the evaluation phases ~24 cycles, an observation of a FREE
+        // pose ~6.5 times that in the Schur phase (phase clocks, BW_TRACE) -- and those sit at one end of the sorted points: split by cost
+        const int *pfs = (const int *)(c.stage + c.up[k] + q.o_pfs);
+        const long total = 2L * q.O + 13L * pfs[q.M];
+        int kk = 0;
+        while (kk < q.M && 2 * (2L * q.start[kk] + 13L * pfs[kk]) < total) kk++;
+        w.ksplit = std::min(std::max(kk, 1), q.M - 1);
+    }
+}
+// a large upload travels in parts: the staged bytes of the first windows go out while the pool stages the next ones (128 x P20: 203 MB = 4 ms of PCIe
+// beside 2.5 ms of staging); the tables and the last part follow with the launch sequence (batch_enqueue)
+// (a part keeps every thread of the pool busy -- one window per task -- and a small upload is not worth the extra runs of the pool: measured, 128 reference-shaped
+//  windows = 33 MB gained 0.2 ms per call and lost 25 % with two calls in flight; 32 x P100 in four parts of eight windows lost 4 ms)
+int batch_stage(BatchCall &c, BAPool &pool, const int32_t *status)
+{
+    const int NB = c.NB, nthr = (int)pool.th.size() + 1;
+    const int n_parts = c.up_total < ((size_t)64 << 20) ? 1 : std::max(1, std::min(ba_knobs().upload_parts, NB / std::max(nthr, 1)));
+    c.n_early = n_parts > 1 ? NB - (NB + n_parts - 1) / n_parts : 0;
+    const int early_step = n_parts > 1 ? std::max(1, (c.n_early + n_parts - 2) / (n_parts - 1)) : NB;
+    c.early_sent = c.n_early > 0;
+    for (int b0 = 0; c.n_early > 0 && b0 < NB;) {
+        const int b1 = b0 < c.n_early ? std::min(c.n_early, b0 + early_step) : NB;
+        pool.run(b1 - b0, [&](int zz) { emit_window(c, b0 + zz); });
+        if (b1 <= c.n_early && c.early_sent) c.early_sent = hipMemcpyAsync(c.A + c.up[b0], c.stage + c.up[b0], c.up[b1] - c.up[b0], hipMemcpyHostToDevice, c.ctx->stream) == hipSuccess;
+        b0 = b1;
+    }
+    // (kept as found: S pool tasks for NB <= S windows -- the pool wakes its workers by the task count)
+    if (c.n_early == 0) pool.run(c.S, [&](int zz) { if (zz < NB) emit_window(c, zz); });
+    for (int k = 0; k < NB; k++) {
+        const BAPlan &q = c.plan(k);
+        if (q.err) { c.st_code[c.batch[k]] = q.err; if (!status) return slam_fail(c.ctx, q.err, "slam_local_ba_batch: window %d: %s", c.batch[k], q.msg); }
+    }
+    return SLAM_OK;
+}
+// One pass over the staged table marks k_ba_window's windows (pad = 1) and takes the maxima of the others (pad == 0: neither k_ba_window's nor rejected at set-up);
+// TT is a property of the whole batch, so what depends on it -- lds_sg and each window's pad2 -- follows in a second, short loop over the same windows.
+BatchRoute batch_route(BatchCall &c)
+{
+    const BAKnobs &kn = ba_knobs();
+    const int NB = c.NB;
+    BatchRoute r;
+    int max_ob = 0, max_hb = 0;
+    for (int k = 0; k < NB; k++) {
+        BAWin &w = c.tab_h[k];
+        if (!kn.no_bw && !w.pad && c.plan(k).window) { r.small_list.push_back(k); r.lds_bw = std::max(r.lds_bw, bw_lds_bytes(c.plan(k).P)); w.pad = 1; }
+        if (w.pad) continue;
+        const BADev &d = w.d;
+        r.gx_obs = std::max(r.gx_obs, w.nb_obs); r.gx_grp = std::max(r.gx_grp, d.ngrp); r.gx_red = std::max(r.gx_red, w.n_red);
+        max_ob = std::max(max_ob, d.sg_ob); max_hb = std::max(max_hb, d.whb);
+        r.lds_band = std::max(r.lds_band, (size_t)w.B.lds_bytes);
+        r.ug_n = std::max(r.ug_n, d.n); r.ug_ob = std::max(r.ug_ob, d.sg_ob); r.ug_sb = std::max(r.ug_sb, d.sg_sb);
+    }
+    r.NS = (int)r.small_list.size(); r.all_small = r.NS == NB;
+    std::copy(r.small_list.begin(), r.small_list.end(), (int *)(c.stage + c.list_off()));
+    r.TT = (!kn.t512 && max_ob <= 256 && (max_hb + 1) * (max_hb + 2) / 2 <= 256) ? 256 : SG_T;
+    r.build_vec = r.TT == 256 ? k_schur_groups_b<256> : k_schur_groups_b<SG_T>; r.update_vec = r.TT == 256 ? k_update_groups_b<256, false> : k_update_groups_b<SG_T, false>;
+    r.lds_ug = ug_lds_bytes(r.ug_n, r.ug_ob, r.ug_sb);
+    for (int k = 0; k < NB; k++) {
+        BAWin &w = c.tab_h[k];
+        if (w.pad) continue;
+        const BADev &d = w.d;
+        r.lds_sg = std::max(r.lds_sg, sg_lds_bytes(d.whb, d.P, d.sg_ob, d.sg_sb, r.TT, d.sg_hp));
+        const size_t b = sgm_lds_bytes(d.whb, d.P, d.sg_ob, d.sg_sb, d.sg_hp);
+        w.pad2 = !kn.no_mfma && r.TT == 256 && b <= 64 * 1024;
+        if (w.pad2) { r.lds_m = std::max(r.lds_m, b); r.n_mfma++; } else r.n_vec++;
+    }
+    r.two_streams = !r.all_small && NB >= 32 && !kn.one_stream;
+    r.two_grid = 16 * ((r.NS + 7) / 8);
+    r.two = (!kn.window_one && c.ctx->xwg_ok && r.two_grid <= c.ctx->dev_cus) ? 1 : 0;
+    return r;
+}
+
+// the launch-per-phase windows [n0, n0 + nb) on stream q: one pass (the group build and the group update: the matrix-core kernels for the windows with pad2, the
+// route's vector kernels for the others), then both
+void run_pass(const BatchRoute &r, hipStream_t q, const BAWin *tb, int nb, int ignore, int iters)
+{
+    hipLaunchKernelGGL(k_linearize_b, dim3(r.gx_obs, nb), dim3(256), 0, q, tb, ignore, 0);
+    hipLaunchKernelGGL(k_pass_start_b, dim3(1, nb), dim3(256), 0, q, tb, ignore ? 1 : 0);
+    for (int it = 1; it <= iters; it++) {
+        if (r.n_mfma) hipLaunchKernelGGL(k_schur_groups_m<256>, dim3(r.gx_grp, nb), dim3(256), r.lds_m, q, tb, ignore);
+        if (r.n_vec) hipLaunchKernelGGL(r.build_vec, dim3(r.gx_grp, nb), dim3(r.TT), r.lds_sg, q, tb, ignore);
+        hipLaunchKernelGGL(k_schur_reduce_b, dim3(r.gx_red, nb), dim3(256), 0, q, tb);
+        hipLaunchKernelGGL(k_band_solve_b, dim3(1, nb), dim3(BS_T), r.lds_band, q, tb);
+        hipLaunchKernelGGL(k_trial_poses_b, dim3(1, nb), dim3(64), 0, q, tb);
+        if (r.n_mfma) hipLaunchKernelGGL((k_update_groups_b<256, true>), dim3(r.gx_grp, nb), dim3(256), r.lds_ug, q, tb, ignore, r.ug_n, r.ug_ob, r.ug_sb);
+        if (r.n_vec) hipLaunchKernelGGL(r.update_vec, dim3(r.gx_grp, nb), dim3(r.TT), r.lds_ug, q, tb, ignore, r.ug_n, r.ug_ob, r.ug_sb);
+        hipLaunchKernelGGL(k_control_b, dim3(1, nb), dim3(256), 0, q, tb);
+    }
+}
+void both_passes(const BatchRoute &r, hipStream_t q, const BAWin *tb, int nb, int iters_fast, int iterations, double repr_eps)
+{
+    run_pass(r, q, tb, nb, 0, iters_fast);
+    hipLaunchKernelGGL(k_outliers_b, dim3(r.gx_obs, nb), dim3(256), 0, q, tb, repr_eps, 1e-6);
+    hipLaunchKernelGGL(k_outlier_count_b, dim3(1, nb), dim3(256), 0, q, tb);
+    run_pass(r, q, tb, nb, 1, iterations);
+}
+// upload, memset, k_ba_window, the one or two halves, k_results_b, download; a second attempt with one workgroup per window if two halves missed each other
+int batch_enqueue(BatchCall &c, BatchRoute &r, int iters_fast, int iterations, double repr_eps)
+{
+    slam_ctx *ctx = c.ctx;
+    const int NB = c.NB;
+    char *A = c.A;
+    hipStream_t st = ctx->stream;
+    static std::atomic<bool> attr_set[7][64], bw_attr[64];
+    const size_t sg_max = sg_lds_bytes(BS_MAXHB, SOLVE_MAX_N / 6);
+    int rc = LDS_ATTR_ONCE(ctx, attr_set[0], k_schur_groups_b<SG_T>, sg_max);
+    if (!rc) rc = LDS_ATTR_ONCE(ctx, attr_set[1], k_schur_groups_b<256>, sg_max);
+    if (!rc) rc = LDS_ATTR_ONCE(ctx, attr_set[2], k_band_solve_b, 150 * 1024);
+    if (!rc) rc = LDS_ATTR_ONCE(ctx, attr_set[3], k_schur_groups_m<256>, 64 * 1024);
+    if (!rc) rc = LDS_ATTR_ONCE(ctx, attr_set[4], (k_update_groups_b<256, true>), 64 * 1024);
+    if (!rc) rc = LDS_ATTR_ONCE(ctx, attr_set[5], (k_update_groups_b<256, false>), 64 * 1024);
+    if (!rc) rc = LDS_ATTR_ONCE(ctx, attr_set[6], (k_update_groups_b<SG_T, false>), 64 * 1024);
+    if (rc) return rc;
+    const BAWin *tab = (const BAWin *)A; const BARes *rtab = (const BARes *)(A + c.tab_bytes);
+    hipStream_t st2 = r.two_streams ? ctx_aux_stream(ctx) : nullptr;
+    if (r.NS > 0 && (rc = LDS_ATTR_ONCE(ctx, bw_attr, k_ba_window, bw_lds_bytes(BW_PMAX))) != SLAM_OK) return rc;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    hipError_t e = hipEventCreate(&e0);
+    if (e == hipSuccess) e = hipEventCreate(&e1);
+    for (int attempt = 0; e == hipSuccess && attempt < 2; attempt++) {
+        if (attempt == 0 && c.early_sent) {                    // (the first parts of the windows' bytes are on their way already)
+            e = hipMemcpyAsync(A, c.stage, c.up[0], hipMemcpyHostToDevice, st);
+            if (e == hipSuccess) e = hipMemcpyAsync(A + c.up[c.n_early], c.stage + c.up[c.n_early], c.up_total - c.up[c.n_early], hipMemcpyHostToDevice, st);
+        } else e = hipMemcpyAsync(A, c.stage, c.up_total, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemsetAsync(A + c.zero_base, 0, c.ze[NB], st);
+        if (e != hipSuccess) break;
+        (void)hipEventRecord(e0, st);
+        if (r.NS > 0) hipLaunchKernelGGL(k_ba_window, dim3(r.two ? r.two_grid : r.NS), dim3(BW_T), r.lds_bw, st, tab, (const int *)(A + c.list_off()), r.NS, r.two, iters_fast, iterations, repr_eps, 1e-6, ba_knobs().xlimit);
+        if (!r.all_small && st2) {
+            const int nA = NB / 2;
+            (void)hipEventRecord(ctx->fork_ev, st); (void)hipStreamWaitEvent(st2, ctx->fork_ev, 0);
+            both_passes(r, st2, tab + nA, NB - nA, iters_fast, iterations, repr_eps);
+            both_passes(r, st, tab, nA, iters_fast, iterations, repr_eps);
+            (void)hipEventRecord(ctx->join_ev, st2); (void)hipStreamWaitEvent(st, ctx->join_ev, 0);
+        } else if (!r.all_small) both_passes(r, st, tab, NB, iters_fast, iterations, repr_eps);
+        hipLaunchKernelGGL(k_results_b, dim3(8, NB), dim3(256), 0, st, tab, rtab, A);
+        e = hipGetLastError();
+        (void)hipEventRecord(e1, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(c.res_host, A + c.res_base, c.rs[NB], hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = slam_stream_wait(st);
+        if (e == hipSuccess) (void)hipEventElapsedTime(&c.dev_ms, e0, e1);
+        if (e != hipSuccess || !r.two) break;
+        bool missed = false;                                   // did the halves of some window miss each other?
+        for (int k : r.small_list) if (c.state(k).chol_fail == 2) { missed = true; break; }
+        if (!missed) break;
+        r.two = 0; n_xretry.fetch_add(1);
+    }
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    if (e == hipSuccess) return SLAM_OK;
+    if (st2) (void)hipStreamSynchronize(st2);                  // (work may be in flight on the second stream: it reads the arena the next call reuses)
+    return slam_fail(ctx, SLAM_ERR_HIP, "slam_local_ba_batch: %s", hipGetErrorString(e));
+}
+// results -> the caller's arrays (its pose order, its observation order); a failed factorisation leaves a window's arrays untouched
+void batch_scatter(BatchCall &c, BAPool &pool, double *theta, uint8_t *outliers, double *stats)
+{
+    pool.run(c.S, [&](int k) {
+        if (k >= c.NB) return;
+        const int z = c.batch[k]; const BAPlan &q = c.plan(k);
+        if (q.err) return;
+        const BARes &r = c.rtab_h[k];
+        const LMState &h = c.state(k);
+        if (stats) lm_stats(h, c.dev_ms, stats + 8 * (size_t)z);
+        if (h.chol_fail) { c.st_code[z] = SLAM_ERR_NUMERIC; return; }
+        const double *th = (const double *)(c.res_host + (r.off_theta - c.res_base));
+        double *dst = theta + c.in.th_off[z];
+        ba_unpermute(q.ba, th, dst, (const uint8_t *)(c.res_host + (r.off_outl - c.res_base)), outliers + c.in.ob_off[z]);
+        memcpy(dst + 6 * q.P, th + 6 * q.P, (size_t)3 * q.M * 8);
+    });
+}
+}  // namespace
 
 extern "C" {
 
@@ -204,294 +453,49 @@ int slam_local_ba_batch(slam_ctx *ctx, int S, const double *cams, const int32_t 
     ARG_TRY(ctx, ctx != nullptr && S >= 1 && S <= 65535 && cams != nullptr && Pn != nullptr && Mn != nullptr && On != nullptr);
     ARG_TRY(ctx, theta != nullptr && theta_const != nullptr && outliers != nullptr && iters_fast >= 0 && iterations >= 0);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    static const bool host_times = getenv("SLAMHIP_BA_HOSTTIME") != nullptr;
     const auto tw0 = std::chrono::steady_clock::now();
-    std::vector<size_t> th_off(S + 1, 0), pc_off(S + 1, 0), ob_off(S + 1, 0);
-    for (int z = 0; z < S; z++) {
-        ARG_TRY(ctx, Pn[z] > 0 && Mn[z] >= 0 && On[z] >= 0);
-        th_off[z + 1] = th_off[z] + 6 * (size_t)Pn[z] + 3 * (size_t)Mn[z]; pc_off[z + 1] = pc_off[z] + Pn[z]; ob_off[z + 1] = ob_off[z] + On[z];
-    }
+    for (int z = 0; z < S; z++) ARG_TRY(ctx, Pn[z] > 0 && Mn[z] >= 0 && On[z] >= 0);
+    BatchCall c; c.ctx = ctx; c.S = S;
+    batch_in(c.in, S, cams, Pn, Mn, On, theta, theta_const, pixels_yx, pose_ids, point_ids);
+    const std::vector<size_t> &th_off = c.in.th_off, &pc_off = c.in.pc_off, &ob_off = c.in.ob_off;
     ARG_TRY(ctx, ob_off[S] == 0 || (pixels_yx != nullptr && pose_ids != nullptr && point_ids != nullptr));
-    std::vector<BAPlan> pl(S);
-    for (int z = 0; z < S; z++) {
-        BAPlan &q = pl[z];
-        q.fx = cams[4 * z]; q.fy = cams[4 * z + 1]; q.cx = cams[4 * z + 2]; q.cy = cams[4 * z + 3];
-        q.P = Pn[z]; q.M = Mn[z]; q.O = On[z]; q.theta = theta + th_off[z]; q.theta_const_in = theta_const + pc_off[z];
-        q.pixels_yx = pixels_yx ? pixels_yx + 2 * ob_off[z] : nullptr; q.pose_ids = pose_ids ? pose_ids + ob_off[z] : nullptr; q.point_ids = point_ids ? point_ids + ob_off[z] : nullptr;
-        q.may_reorder = true; q.small_groups = true;
-    }
     BAPool &pool = ba_pool();
-    const int nthr = (int)pool.th.size() + 1;
-    auto parallel = [&](const std::function<void(int)> &fn) { pool.run(S, fn); };
-    parallel([&](int z) { ba_plan(pl[z]); });
+    pool.run(S, [&](int z) { ba_plan(c.in.pl[z]); });
     const auto tw1 = std::chrono::steady_clock::now();
-    std::vector<int> st_code(S, SLAM_OK);
-    std::vector<int> batch;                                    // windows the batch kernels take
-    std::vector<int> single;                                   // windows solved one by one afterwards
-    for (int z = 0; z < S; z++) {
-        BAPlan &q = pl[z];
-        if (q.err) { st_code[z] = q.err; if (!status) return slam_fail(ctx, q.err, "slam_local_ba_batch: window %d: %s", z, q.msg); continue; }
-        const slam_ba *b = q.ba;
-        const int Ps = b->pspan > 0 ? b->pspan : q.P, hbq = std::min(std::max(b->hb, 1), Ps - 1);
-        if (b->grouped && hbq >= 1 && hbq <= BS_MAXHB && band_lds_bytes(6 * q.P, Ps, hbq) <= 150 * 1024) batch.push_back(z); else single.push_back(z);
+    c.st_code.assign(S, SLAM_OK); c.route.resize(S);
+    for (int z = 0; z < S; z++) {                              // the windows the batch kernels take; the others are solved one by one afterwards
+        BAPlan &q = c.in.pl[z];
+        if (q.err) { c.st_code[z] = q.err; if (!status) return slam_fail(ctx, q.err, "slam_local_ba_batch: window %d: %s", z, q.msg); continue; }
+        c.route[z] = solve_route(q.ba, q.P, ctx, true);
+        (batch_takes(q.ba, c.route[z]) ? c.batch : c.single).push_back(z);
     }
-    const int NB = (int)batch.size();
-    float dev_ms = 0;
-    if (NB > 0) {
-        // region-major arena: [window table | result table | uploads of every window][zero regions][work regions][results]
-        std::vector<size_t> up(NB + 1), ze(NB + 1), wk(NB + 1), rs(NB + 1);
-        const size_t tab_bytes = al((size_t)NB * sizeof(BAWin)), rtab_bytes = al((size_t)NB * sizeof(BARes)) + al((size_t)NB * 4);   // (+ the list of k_ba_window's windows)
-        up[0] = tab_bytes + rtab_bytes; ze[0] = 0; wk[0] = 0; rs[0] = 0;
-        for (int k = 0; k < NB; k++) {
-            const BAPlan &q = pl[batch[k]];
-            up[k + 1] = up[k] + q.up_bytes; ze[k + 1] = ze[k] + q.zero_bytes; wk[k + 1] = wk[k] + q.work_bytes;
-            rs[k + 1] = rs[k] + al(sizeof(LMState)) + al((6 * (size_t)q.P + 3 * (size_t)q.M) * 8 + 8) + al((size_t)q.O + 8);
-        }
-        const size_t up_total = up[NB], zero_base = up_total, work_base = zero_base + ze[NB], res_base = work_base + wk[NB], total = res_base + rs[NB];
-        char *A = nullptr, *stage = nullptr;
-        int rc = slam_scratch(ctx, total, (void **)&A);
-        if (rc) return rc;
-        rc = slam_pinned(ctx, up_total + rs[NB], (void **)&stage);
-        if (rc) return rc;
-        char *res_host = stage + up_total;
-        BAWin *tab_h = (BAWin *)stage; BARes *rtab_h = (BARes *)(stage + tab_bytes);
-        // a large upload travels in parts: the staged bytes of the first windows go out while the pool stages the next ones (128 x P20: 203 MB = 4 ms of PCIe
-        // beside 2.5 ms of staging); the tables and the last part follow with the launch sequence below
-        // (a part keeps every thread of the pool busy -- one window per task -- and a small upload is not worth the extra runs of the pool: measured, 128 reference-shaped
-        //  windows = 33 MB gained 0.2 ms per call and lost 25 % with two calls in flight; 32 x P100 in four parts of eight windows lost 4 ms)
-        static const int parts_cap = [] { const char *v = getenv("SLAMHIP_BA_UPLOAD_PARTS"); return v ? atoi(v) : 4; }();      // (measurement knob)
-        const int n_parts = up_total < ((size_t)64 << 20) ? 1 : std::max(1, std::min(parts_cap, NB / std::max(nthr, 1)));
-        const int n_early = n_parts > 1 ? NB - (NB + n_parts - 1) / n_parts : 0;            // windows whose bytes leave before the launch sequence: all but the last part
-        const int early_step = n_parts > 1 ? std::max(1, (n_early + n_parts - 2) / (n_parts - 1)) : NB;
-        auto emit_window = [&](int zz) {
-            if (zz >= NB) return;
-            const int k = zz; BAPlan &q = pl[batch[k]];
-            BAWin &w = tab_h[k];
-            memset(&w, 0, sizeof w);
-            BARes &r = rtab_h[k];
-            r.off_state = res_base + rs[k]; r.off_theta = r.off_state + al(sizeof(LMState)); r.off_outl = r.off_theta + al((6 * (size_t)q.P + 3 * (size_t)q.M) * 8 + 8);
-            if (ba_emit(q, A + up[k], A + zero_base + ze[k], A + work_base + wk[k], stage + up[k])) { w.pad = 2; return; }    // rejected (q.err): skipped by every kernel
-            slam_ba *b = q.ba; b->device = ctx->device; b->owns_arena = false; b->arena = A;
-            w.d = b->d;
-            const int n = w.d.n, Ps = b->pspan > 0 ? b->pspan : q.P, p0 = b->pspan > 0 ? b->p0 : 0, hb = std::min(std::max(b->hb, 1), Ps - 1);
-            const double *red = b->reduce;
-            w.B.S = red + (size_t)6 * p0 * (n + 1); w.B.g = red + (size_t)n * n + 6 * p0; w.B.ud = red + (size_t)n * n + n + 6 * p0; w.B.Lg = b->band;
-            w.B.nb = Ps; w.B.hb = hb; w.B.p0 = p0; w.B.inv_delta_host = 0.0; w.B.fail = b->chol_flag; w.B.trace = nullptr;
-            w.B.lds_bytes = (int)band_lds_bytes(n, Ps, hb); w.B.xchg = b->xchg; w.B.epoch = 1; w.B.shift = 0;
-            w.nb_obs = b->nblocks_obs; w.nb_pts = b->nblocks_pts; w.n_red = (w.d.P * (w.d.whb + 1) * 36 + w.d.P * 12 + 255) / 256;
-            w.ksplit = q.ksplit; w.bwx = q.window ? (double *)(A + zero_base + ze[k] + q.o_bwx) : nullptr;
-            if (q.window && q.M > 1) {
-                // the split point of k_ba_window's two workgroups: an observation costs the evaluation phases ~24 cycles, an observation of a FREE
-                // pose ~6.5 times that in the Schur phase (phase clocks, BW_TRACE) -- and those sit at one end of the sorted points: split by cost
-                const int *pfs = (const int *)(stage + up[k] + q.o_pfs);
-                const long total = 2L * q.O + 13L * pfs[q.M];
-                int kk = 0;
-                while (kk < q.M && 2 * (2L * q.start[kk] + 13L * pfs[kk]) < total) kk++;
-                w.ksplit = std::min(std::max(kk, 1), q.M - 1);
-            }
-        };
-        bool early_sent = false;
-        if (n_early > 0) {
-            early_sent = true;
-            for (int b0 = 0; b0 < NB;) {
-                const int b1 = b0 < n_early ? std::min(n_early, b0 + early_step) : NB;
-                pool.run(b1 - b0, [&](int zz) { emit_window(b0 + zz); });
-                if (b1 <= n_early && early_sent) early_sent = hipMemcpyAsync(A + up[b0], stage + up[b0], up[b1] - up[b0], hipMemcpyHostToDevice, ctx->stream) == hipSuccess;
-                b0 = b1;
-            }
-        } else pool.run(S, emit_window);
-        for (int k = 0; k < NB; k++) {
-            BAPlan &q = pl[batch[k]];
-            if (q.err) { st_code[batch[k]] = q.err; if (!status) return slam_fail(ctx, q.err, "slam_local_ba_batch: window %d: %s", batch[k], q.msg); }
-        }
-        // a window whose set-up failed in ba_emit (a point observed twice by one pose) stays in the table with pad = 2: every batch kernel, k_results_b
-        // included, returns at once for it, it is in no list of k_ba_window's and its (zeroed) table entry is never read for a launch size
-        // windows one workgroup can keep to itself (k_ba_window): <= 5 free poses, consecutive; the others take the launch-per-phase kernels
-        static const bool no_bw = getenv("SLAMHIP_NO_BA_WINDOW") != nullptr;
-        std::vector<int> small_list;
-        size_t lds_bw = 0;
-        for (int k = 0; k < NB && !no_bw; k++) {
-            BAPlan &q = pl[batch[k]]; BAWin &w = tab_h[k];
-            if (q.err) continue;
-            if (q.window) {
-                small_list.push_back(k); lds_bw = std::max(lds_bw, bw_lds_bytes(q.P));
-                w.pad = 1;
-            }
-        }
-        // (the list travels behind the result table in the same upload)
-        const int NS_ = (int)small_list.size();
-        bool all_small = NS_ == NB;
-        for (int k = 0; k < NB; k++) if (!pl[batch[k]].err && tab_h[k].pad != 1) all_small = false;
-        int *list_h = (int *)(stage + tab_bytes + rtab_bytes - al((size_t)NB * 4));
-        for (int k = 0; k < NS_; k++) list_h[k] = small_list[k];
-        int gx_obs = 1, gx_grp = 1, gx_red = 1, max_ob = 0, max_hb = 0; size_t lds_sg = 0, lds_band = 0;
-        for (int k = 0; k < NB; k++) {
-            const BAWin &w = tab_h[k];
-            if (w.pad) continue;                                   // (k_ba_window's, or rejected at set-up)
-            gx_obs = std::max(gx_obs, w.nb_obs); gx_grp = std::max(gx_grp, w.d.ngrp); gx_red = std::max(gx_red, w.n_red);
-            max_ob = std::max(max_ob, w.d.sg_ob); max_hb = std::max(max_hb, w.d.whb);
-            lds_band = std::max(lds_band, (size_t)w.B.lds_bytes);
-        }
-        // small groups everywhere (the reference's window shape: 16 points x 10 observers): 256-thread workgroups, two to three per compute unit
-        static const bool no_t256 = getenv("SLAMHIP_BA_BATCH_T512") != nullptr;
-        const int TT = (!no_t256 && max_ob <= 256 && (max_hb + 1) * (max_hb + 2) / 2 <= 256) ? 256 : SG_T;
-        for (int k = 0; k < NB; k++) if (!pl[batch[k]].err && !tab_h[k].pad) lds_sg = std::max(lds_sg, sg_lds_bytes(tab_h[k].d.whb, tab_h[k].d.P, tab_h[k].d.sg_ob, tab_h[k].d.sg_sb, TT, tab_h[k].d.sg_hp));
-        // the Schur products on the matrix cores (k_schur_groups_m): 256-thread groups whose matrix Y (3 x points columns, 6 x window slots rows) fits
-        // LDS beside two more workgroups; SLAMHIP_BA_NO_MFMA=1 keeps the vector kernel (A/B timing, and the parity reference of the tests).  The vector kernel's lds_sg
-        // and the cost-only linearisation are shared: the vector build stores its own evaluation, the matrix-core build none
-        int ug_n = 6, ug_ob = 8, ug_sb = 8;                     // k_update_groups_b's LDS arrays at the batch's own sizes
-        for (int k = 0; k < NB; k++) if (!pl[batch[k]].err && !tab_h[k].pad) { ug_n = std::max(ug_n, tab_h[k].d.n); ug_ob = std::max(ug_ob, tab_h[k].d.sg_ob); ug_sb = std::max(ug_sb, tab_h[k].d.sg_sb); }
-        const size_t lds_ug = ug_lds_bytes(ug_n, ug_ob, ug_sb);
-        static const bool no_mfma = getenv("SLAMHIP_BA_NO_MFMA") != nullptr;
-        // per window (BAWin::pad2): one window whose matrix Y does not fit (a wide band with few observations per point) does not take the matrix cores from the others
-        size_t lds_m = 0; int n_mfma = 0, n_vec = 0;
-        for (int k = 0; k < NB; k++) if (!pl[batch[k]].err && !tab_h[k].pad) {
-            const size_t b = sgm_lds_bytes(tab_h[k].d.whb, tab_h[k].d.P, tab_h[k].d.sg_ob, tab_h[k].d.sg_sb, tab_h[k].d.sg_hp);
-            const bool m = !no_mfma && TT == 256 && b <= 64 * 1024;
-            tab_h[k].pad2 = m ? 1 : 0;
-            if (m) { lds_m = std::max(lds_m, b); n_mfma++; } else n_vec++;
-        }
+    c.NB = (int)c.batch.size();
+    int rc = SLAM_OK;
+    if (c.NB > 0) {
+        if ((rc = batch_arena(c)) != SLAM_OK || (rc = batch_stage(c, pool, status)) != SLAM_OK) return rc;
+        BatchRoute r = batch_route(c);
         const auto tw2 = std::chrono::steady_clock::now();
-        hipStream_t st = ctx->stream;
-        static std::atomic<bool> attr_set[64];
-        const int dv = ctx->device & 63;
-        if (!attr_set[dv].load(std::memory_order_acquire)) {
-            HIP_TRY(ctx, hipFuncSetAttribute((const void *)k_schur_groups_b<SG_T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sg_lds_bytes(BS_MAXHB, SOLVE_MAX_N / 6)));
-            HIP_TRY(ctx, hipFuncSetAttribute((const void *)k_schur_groups_b<256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sg_lds_bytes(BS_MAXHB, SOLVE_MAX_N / 6)));
-            HIP_TRY(ctx, hipFuncSetAttribute((const void *)k_band_solve_b, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-            HIP_TRY(ctx, hipFuncSetAttribute((const void *)k_schur_groups_m<256>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-            HIP_TRY(ctx, hipFuncSetAttribute((const void *)k_update_groups_b<256, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-            HIP_TRY(ctx, hipFuncSetAttribute((const void *)k_update_groups_b<256, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-            HIP_TRY(ctx, hipFuncSetAttribute((const void *)k_update_groups_b<SG_T, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-            attr_set[dv].store(true, std::memory_order_release);
-        }
-        const BAWin *tab = (const BAWin *)A; const BARes *rtab = (const BARes *)(A + tab_bytes);
-        // the launch-per-phase windows [n0, n0 + nb) on stream q: both passes.  A batch of >= 32 such windows runs as TWO halves on two streams: while one half sits
-        // in its latency-bound kernels (k_band_solve_b: one workgroup per window, k_trial_poses_b, k_control_b -- ~75 us of an iteration) the other half's builds fill the chip
-        auto run_pass = [&](hipStream_t q, int n0, int nb, int ignore, int iters) {
-            const BAWin *tb = tab + n0;
-            hipLaunchKernelGGL(k_linearize_b, dim3(gx_obs, nb), dim3(256), 0, q, tb, ignore, 0);
-            hipLaunchKernelGGL(k_pass_start_b, dim3(1, nb), dim3(256), 0, q, tb, ignore ? 1 : 0);
-            for (int it = 1; it <= iters; it++) {
-                if (n_mfma) hipLaunchKernelGGL(k_schur_groups_m<256>, dim3(gx_grp, nb), dim3(256), lds_m, q, tb, ignore);
-                if (n_vec && TT == 256) hipLaunchKernelGGL(k_schur_groups_b<256>, dim3(gx_grp, nb), dim3(256), lds_sg, q, tb, ignore);
-                else if (n_vec) hipLaunchKernelGGL(k_schur_groups_b<SG_T>, dim3(gx_grp, nb), dim3(SG_T), lds_sg, q, tb, ignore);
-                hipLaunchKernelGGL(k_schur_reduce_b, dim3(gx_red, nb), dim3(256), 0, q, tb);
-                hipLaunchKernelGGL(k_band_solve_b, dim3(1, nb), dim3(BS_T), lds_band, q, tb);
-                hipLaunchKernelGGL(k_trial_poses_b, dim3(1, nb), dim3(64), 0, q, tb);
-                if (n_mfma) hipLaunchKernelGGL((k_update_groups_b<256, true>), dim3(gx_grp, nb), dim3(256), lds_ug, q, tb, ignore, ug_n, ug_ob, ug_sb);
-                if (n_vec && TT == 256) hipLaunchKernelGGL((k_update_groups_b<256, false>), dim3(gx_grp, nb), dim3(256), lds_ug, q, tb, ignore, ug_n, ug_ob, ug_sb);
-                else if (n_vec) hipLaunchKernelGGL((k_update_groups_b<SG_T, false>), dim3(gx_grp, nb), dim3(SG_T), lds_ug, q, tb, ignore, ug_n, ug_ob, ug_sb);
-                hipLaunchKernelGGL(k_control_b, dim3(1, nb), dim3(256), 0, q, tb);
-            }
-        };
-        auto both_passes = [&](hipStream_t q, int n0, int nb) {
-            run_pass(q, n0, nb, 0, iters_fast);
-            hipLaunchKernelGGL(k_outliers_b, dim3(gx_obs, nb), dim3(256), 0, q, tab + n0, repr_eps, 1e-6);
-            hipLaunchKernelGGL(k_outlier_count_b, dim3(1, nb), dim3(256), 0, q, tab + n0);
-            run_pass(q, n0, nb, 1, iterations);
-        };
-        static const bool one_stream = getenv("SLAMHIP_BA_ONE_STREAM") != nullptr;      // (measurement knob)
-        hipStream_t st2 = (!all_small && NB >= 32 && !one_stream) ? ctx_aux_stream(ctx) : nullptr;
-        if (NS_ > 0) {                                             // (the flag is set on success only: a failed attribute call is tried again by the next call)
-            static std::atomic<bool> bw_attr[64];
-            if (!bw_attr[dv].load(std::memory_order_acquire)) {
-                HIP_TRY(ctx, hipFuncSetAttribute((const void *)k_ba_window, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bw_lds_bytes(BW_PMAX)));
-                bw_attr[dv].store(true, std::memory_order_release);
-            }
-        }
-        // two workgroups per window (k_ba_window) only while BOTH halves of EVERY window are resident at once -- they wait for each other: one
-        // workgroup per compute unit (136-148 KB of LDS), so 2 x NS workgroups must fit the device's compute units (hipDeviceProp_t, not a
-        // constant), the stream must not be CU-masked (a mask says nothing about how many of an XCD's units are left, and the halves b / b + 8
-        // need two on the SAME XCD) and the architecture must be the one the memory-side hand-over was validated on (ctx->xwg_ok).  Other
-        // processes' kernels can still hold LDS the count knows nothing about: the kernel's wait is bounded (xlimit) and a window whose halves
-        // missed each other comes back with chol_fail = 2 -- the call is then solved again with one workgroup per window.
-        // SLAMHIP_BA_WINDOW_ONE=1: always one; SLAMHIP_BA_XWAIT_US: the bound (default 500 000 us; 0 in the tests = give up at once).
-        static const bool bw_one = getenv("SLAMHIP_BA_WINDOW_ONE") != nullptr;
-        static const long long xlimit = [] { const char *v = getenv("SLAMHIP_BA_XWAIT_US"); return (v ? atoll(v) : 500000LL) * 100; }();
-        const int two_grid = 16 * ((NS_ + 7) / 8);
-        int two = (!bw_one && ctx->xwg_ok && two_grid <= ctx->dev_cus) ? 1 : 0;
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        hipError_t e = hipEventCreate(&e0);
-        if (e == hipSuccess) e = hipEventCreate(&e1);
-        for (int attempt = 0; e == hipSuccess && attempt < 2; attempt++) {
-            if (attempt == 0 && early_sent) {                      // (the first half of the windows' bytes is on its way already)
-                e = hipMemcpyAsync(A, stage, up[0], hipMemcpyHostToDevice, st);
-                if (e == hipSuccess) e = hipMemcpyAsync(A + up[n_early], stage + up[n_early], up_total - up[n_early], hipMemcpyHostToDevice, st);
-            } else e = hipMemcpyAsync(A, stage, up_total, hipMemcpyHostToDevice, st);
-            if (e == hipSuccess) e = hipMemsetAsync(A + zero_base, 0, ze[NB], st);
-            if (e != hipSuccess) break;
-            (void)hipEventRecord(e0, st);
-            if (NS_ > 0) {
-                const int *list_d = (const int *)(A + tab_bytes + rtab_bytes - al((size_t)NB * 4));
-                hipLaunchKernelGGL(k_ba_window, dim3(two ? two_grid : NS_), dim3(BW_T), lds_bw, st, tab, list_d, NS_, two, iters_fast, iterations, repr_eps, 1e-6, xlimit);
-            }
-            if (!all_small && st2) {
-                const int nA = NB / 2;
-                (void)hipEventRecord(ctx->fork_ev, st); (void)hipStreamWaitEvent(st2, ctx->fork_ev, 0);
-                both_passes(st2, nA, NB - nA);
-                both_passes(st, 0, nA);
-                (void)hipEventRecord(ctx->join_ev, st2); (void)hipStreamWaitEvent(st, ctx->join_ev, 0);
-            } else if (!all_small) both_passes(st, 0, NB);
-            hipLaunchKernelGGL(k_results_b, dim3(8, NB), dim3(256), 0, st, tab, rtab, A);
-            e = hipGetLastError();
-            (void)hipEventRecord(e1, st);
-            if (e == hipSuccess) e = hipMemcpyAsync(res_host, A + res_base, rs[NB], hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess) e = slam_stream_wait(st);
-            if (e == hipSuccess) (void)hipEventElapsedTime(&dev_ms, e0, e1);
-            if (e != hipSuccess || !two) break;
-            bool missed = false;                                   // did the halves of some window miss each other?
-            for (int k : small_list) if (((const LMState *)(res_host + (rtab_h[k].off_state - res_base)))->chol_fail == 2) { missed = true; break; }
-            if (!missed) break;
-            two = 0; n_xretry.fetch_add(1);
-        }
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-        if (e != hipSuccess) {
-            if (st2) (void)hipStreamSynchronize(st2);              // (work may be in flight on the second stream: it reads the arena the next call reuses)
-            return slam_fail(ctx, SLAM_ERR_HIP, "slam_local_ba_batch: %s", hipGetErrorString(e));
-        }
+        if ((rc = batch_enqueue(c, r, iters_fast, iterations, repr_eps)) != SLAM_OK) return rc;
         const auto tw3 = std::chrono::steady_clock::now();
-        // results -> the caller's arrays (its pose order, its observation order); a failed factorisation leaves a window's arrays untouched
-        parallel([&](int zz) {
-            if (zz >= NB) return;
-            const int k = zz, z = batch[k]; BAPlan &q = pl[z];
-            if (q.err) return;
-            const BARes &r = rtab_h[k];
-            const LMState &h = *(const LMState *)(res_host + (r.off_state - res_base));
-            if (stats) {
-                double *sv = stats + 8 * (size_t)z;
-                sv[0] = h.ssr_init; sv[1] = h.ssr_pass1; sv[2] = h.ssr_final; sv[3] = h.iters_pass1; sv[4] = h.iters_pass2; sv[5] = h.n_outliers; sv[6] = dev_ms; sv[7] = h.chol_fail;
-            }
-            if (h.chol_fail) { st_code[z] = SLAM_ERR_NUMERIC; return; }
-            const double *th = (const double *)(res_host + (r.off_theta - res_base));
-            double *dst = theta + th_off[z];
-            const int n = 6 * q.P;
-            if (q.ba->pose_order.empty()) memcpy(dst, th, (size_t)n * 8);
-            else for (int p = 0; p < q.P; p++) memcpy(dst + 6 * q.ba->pose_order[p], th + 6 * p, 48);
-            memcpy(dst + n, th + n, (size_t)3 * q.M * 8);
-            const uint8_t *ol = (const uint8_t *)(res_host + (r.off_outl - res_base));
-            uint8_t *od = outliers + ob_off[z];
-            for (int s2 = 0; s2 < q.O; s2++) od[q.ba->perm[s2]] = ol[s2];
-        });
-        if (host_times) {
+        batch_scatter(c, pool, theta, outliers, stats);
+        if (ba_knobs().host_times) {
             const auto us = [](auto a, auto b) { return (long)std::chrono::duration_cast<std::chrono::microseconds>(b - a).count(); };
             fprintf(stderr, "slam_local_ba_batch host: %d windows (%d threads): plan %ld us, emit %ld us, enqueue + wait %ld us (device %.0f us), scatter %ld us; %zu B up, %zu B arena\n",
-                    NB, nthr, us(tw0, tw1), us(tw1, tw2), us(tw2, tw3), dev_ms * 1e3, us(tw3, std::chrono::steady_clock::now()), up_total, total);
+                    c.NB, (int)pool.th.size() + 1, us(tw0, tw1), us(tw1, tw2), us(tw2, tw3), c.dev_ms * 1e3, us(tw3, std::chrono::steady_clock::now()), c.up_total, c.total);
         }
     }
-    for (int z : single) {
-        if (st_code[z]) continue;
-        const BAPlan &q = pl[z];
+    for (int z : c.single) {
+        if (c.st_code[z]) continue;
+        const BAPlan &q = c.in.pl[z];
         double sv[8] = {0};
         const int rc1 = slam_local_ba(ctx, q.fx, q.fy, q.cx, q.cy, q.P, q.M, q.O, theta + th_off[z], theta_const + pc_off[z], q.pixels_yx, q.pose_ids, q.point_ids,
                                       outliers + ob_off[z], iters_fast, iterations, repr_eps, sv);
         if (stats) memcpy(stats + 8 * (size_t)z, sv, sizeof sv);
-        st_code[z] = rc1;
+        c.st_code[z] = rc1;
         if (rc1 && rc1 != SLAM_ERR_NUMERIC && !status) return rc1;
     }
     int first = SLAM_OK;
-    for (int z = 0; z < S; z++) { if (status) status[z] = st_code[z]; if (st_code[z] && !first) first = st_code[z]; }
+    for (int z = 0; z < S; z++) { if (status) status[z] = c.st_code[z]; if (c.st_code[z] && !first) first = c.st_code[z]; }
     if (status) return SLAM_OK;                                // per-window codes are in status[]
     if (first == SLAM_ERR_NUMERIC) return slam_fail(ctx, SLAM_ERR_NUMERIC, "slam_local_ba_batch: a reduced camera system was not positive definite (that window's theta and outliers are left unchanged)");
     return first;
@@ -551,17 +555,10 @@ long slam_debug_ba_xretries(void) { return n_xretry.load(); }
 int slam_debug_ba_host_time(int S, const double *cams, const int32_t *Pn, const int32_t *Mn, const int32_t *On, const double *theta, const uint8_t *theta_const,
                             const double *pixels_yx, const int64_t *pose_ids, const int64_t *point_ids, int threads, double *out_us)
 {
-    std::vector<size_t> th_off(S + 1, 0), pc_off(S + 1, 0), ob_off(S + 1, 0);
-    for (int z = 0; z < S; z++) { th_off[z + 1] = th_off[z] + 6 * (size_t)Pn[z] + 3 * (size_t)Mn[z]; pc_off[z + 1] = pc_off[z] + Pn[z]; ob_off[z + 1] = ob_off[z] + On[z]; }
     const auto t0 = std::chrono::steady_clock::now();
-    std::vector<BAPlan> pl(S);
-    for (int z = 0; z < S; z++) {
-        BAPlan &q = pl[z];
-        q.fx = cams[4 * z]; q.fy = cams[4 * z + 1]; q.cx = cams[4 * z + 2]; q.cy = cams[4 * z + 3];
-        q.P = Pn[z]; q.M = Mn[z]; q.O = On[z]; q.theta = theta + th_off[z]; q.theta_const_in = theta_const + pc_off[z];
-        q.pixels_yx = pixels_yx + 2 * ob_off[z]; q.pose_ids = pose_ids + ob_off[z]; q.point_ids = point_ids + ob_off[z];
-        q.may_reorder = true; q.small_groups = true;
-    }
+    BatchIn in;
+    batch_in(in, S, cams, Pn, Mn, On, theta, theta_const, pixels_yx, pose_ids, point_ids);
+    std::vector<BAPlan> &pl = in.pl;
     auto parallel = [&](auto fn) {
         if (threads == 0) { ba_pool().run(S, fn); return; }      // the parked worker pool of slam_local_ba_batch itself (callers from several threads take turns)
         if (threads <= 1) { for (int z = 0; z < S; z++) fn(z); return; }

@@ -2133,3 +2133,58 @@ static size_t bw_lds_bytes(int P)
 // k_ba_window is defined in ba_window.hip and launched by ba_batch.hip
 __global__ void k_ba_window(const BAWin *tab, const int *list, int ns, int two, int iters_fast, int iterations, double repr_eps, double depth_eps, long long xlimit);
 #include "ba_host.hpp"
+
+// ---- how one window's reduced camera system is solved, decided once: ba_enqueue_solve launches from it, the batch asks it which windows it takes
+enum SolveKind { SOLVE_DENSE, SOLVE_BAND, SOLVE_TILED };      // k_dense_solve / k_band_solve / the k_chol_* chain
+struct SolveRoute {
+    int Ps, p0;            // the poses the solve covers: first .. last free pose
+    int hb;                // clamped half-bandwidth, >= 1: the factor wave reads block row k + 1 while row k + 1 + hb enters the ring
+    size_t band_lds;       // k_band_solve's dynamic LDS for that span
+    SolveKind kind;
+    bool twist; int shift, grid;      // the band: two-sided factorisation, its split point, workgroups launched (1; twisted 9, or 2 under SLAMHIP_TWIST_SPREAD)
+};
+// P: the window's poses (ba->d is not bound before ba_emit); batch: the route of a window inside slam_local_ba_batch (ctx is not read).  Kept exactly as found:
+// the batch never consults SLAMHIP_NO_BAND and has no dense solve (a window is the batch's only if the band takes it, batch_takes), and it always runs
+// k_band_solve_b untwisted with shift = 0; the single-window path honours all of them.
+inline SolveRoute solve_route(const slam_ba *ba, int P, const slam_ctx *ctx, bool batch)
+{
+    const BAKnobs &kn = ba_knobs();
+    SolveRoute r;
+    r.Ps = ba->pspan > 0 ? ba->pspan : P; r.p0 = ba->pspan > 0 ? ba->p0 : 0;
+    r.hb = std::min(std::max(ba->hb, 1), r.Ps - 1);
+    r.band_lds = band_lds_bytes(6 * P, r.Ps, r.hb);
+    const bool band_fits = r.hb <= BS_MAXHB && r.band_lds <= 150 * 1024;
+    if (!batch && ba->grouped && r.hb > BS_MAXHB && r.Ps <= DS_MAXF) r.kind = SOLVE_DENSE;      // not banded, small (ba_plan admitted the groups for exactly this case)
+    else r.kind = (batch || !kn.no_band) && band_fits ? SOLVE_BAND : SOLVE_TILED;
+    // (the two workgroups wait for each other: both must be resident, which a stream confined to one compute unit cannot promise -- xwg_ok)
+    // measured: pays from 19 free poses at hb = 9 (19: 92.1 -> 89.3 us per iteration, 18: equal) since the hand-overs stay in one L2 (24 before)
+    r.twist = !batch && r.kind == SOLVE_BAND && !kn.no_twist && r.hb * 6 <= 58 && r.Ps >= (kn.twist_min > 0 ? std::max(kn.twist_min, r.hb + 8) : std::max(2 * (r.hb + 1) - 1, r.hb + 8)) && ctx->xwg_ok;
+    r.shift = batch ? 0 : kn.twist_shift; r.grid = r.twist ? (kn.twist_spread ? 2 : 9) : 1;
+    return r;
+}
+// "the batch kernels take this window" (r: the batch's route); the others are solved one by one through slam_local_ba
+inline bool batch_takes(const slam_ba *ba, const SolveRoute &r) { return ba->grouped && r.kind == SOLVE_BAND && r.hb >= 1; }
+// The solver's argument block over the reduce buffer `red`.  Kept exactly as found: the dense route leaves Lg = nullptr and lds_bytes, xchg, epoch, shift at 0,
+// the band route sets all of them; epoch (the window's launch counter: ++ba->epoch, 1 in a batch) and trace are the caller's.
+inline BandArgs band_args(const slam_ba *ba, const SolveRoute &r, const double *red, double inv_delta)
+{
+    const int n = ba->d.n;
+    BandArgs B = {};
+    B.S = red + (size_t)6 * r.p0 * (n + 1); B.g = red + (size_t)n * n + 6 * r.p0; B.ud = B.g + n; B.nb = r.Ps; B.hb = r.hb; B.p0 = r.p0;
+    B.inv_delta_host = inv_delta; B.fail = ba->chol_flag;
+    if (r.kind == SOLVE_BAND) { B.Lg = ba->band; B.lds_bytes = (int)r.band_lds; B.xchg = ba->xchg; B.shift = r.shift; }
+    return B;
+}
+// A kernel's dynamic-LDS limit, once per device.  The attribute belongs to the function object of the CURRENT device; the reference's three tasks call the
+// library concurrently (SLAM.jl:166): the flag is atomic, setting the attribute twice is harmless, and the flag is set on success only -- a failed
+// attribute call is tried again by the next call.  The message of a failure names the kernel, as the HIP_TRY at each site used to.
+#define LDS_ATTR_ONCE(ctx, flag, kernel, bytes) lds_attr_once(ctx, flag, (const void *)kernel, (int)(bytes), #kernel)
+inline int lds_attr_once(slam_ctx *ctx, std::atomic<bool> (&flag)[64], const void *kernel, int bytes, const char *name)
+{
+    std::atomic<bool> &f = flag[ctx->device & 63];
+    if (f.load(std::memory_order_acquire)) return SLAM_OK;
+    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e != hipSuccess) return slam_fail(ctx, SLAM_ERR_HIP, "hipFuncSetAttribute((const void *)%s, hipFuncAttributeMaxDynamicSharedMemorySize, %d): %s", name, bytes, hipGetErrorString(e));
+    f.store(true, std::memory_order_release);
+    return SLAM_OK;
+}

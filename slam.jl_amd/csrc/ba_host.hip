@@ -1,9 +1,7 @@
-// ba_host.hip -- definitions of ba_host.hpp: band_lds_bytes, ba_pose_order, ba_plan, ba_emit (host code only; compiled by hipcc for the HIP vector types
-// and the shared structs, launches nothing).  Exercised without a GPU by tests/test_ba_plan_order.py and tests/host_sanitize/.
+// ba_host.hip -- definitions of ba_host.hpp: band_lds_bytes, ba_pose_order, ba_plan_order, ba_plan, ba_emit (host code only; compiled
+// by hipcc for the HIP vector types and the shared structs, launches nothing).  Exercised without a GPU by tests/test_ba_plan_order.py and tests/host_sanitize/.
 #include "ba_device.hpp"
 // ---------------------------------------------------------------------------------
-
-
 // dynamic LDS of k_band_solve for Ps block columns of half-bandwidth hb (n = 6 P: the damping / solution vectors span every pose)
 size_t band_lds_bytes(int n, int Ps, int hb)
 {
@@ -81,13 +79,25 @@ bool ba_pose_order(int P, int M, int O, const uint8_t *theta_const, const int64_
     return true;
 }
 
+// host only: the pose order slam_local_ba solves in, and the block half-bandwidth of the reduced camera system in that order (slam_ba_plan_order): the
+// head of ba_plan itself -- its scan of the free observers' spans and its reorder decision -- with this entry point's own argument checks
+int ba_plan_order(int P, int M, int O, const uint8_t *theta_const, const int64_t *pose_ids, const int64_t *point_ids, int32_t *order_out, int *hb_out)
+{
+    if (P <= 0 || M < 0 || O < 0 || !theta_const || (O > 0 && (!pose_ids || !point_ids))) return SLAM_ERR_ARG;
+    BAPlan pl;
+    pl.P = P; pl.M = M; pl.O = O; pl.theta_const_in = theta_const; pl.pose_ids = pose_ids; pl.point_ids = point_ids; pl.may_reorder = pl.order_only = true;
+    if (ba_plan(pl)) return SLAM_ERR_ARG;                      // (an id out of range)
+    if (order_out) for (int k = 0; k < P; k++) order_out[k] = pl.new_of.empty() ? k : pl.ba->pose_order[k];
+    if (hb_out) *hb_out = pl.hb;
+    return pl.new_of.empty() ? 0 : 1;
+}
 
 int ba_plan(BAPlan &pl)
 {
     const int P = pl.P, M = pl.M, O = pl.O;
     const int64_t *pose_ids = pl.pose_ids, *point_ids = pl.point_ids;
-    if (!(P > 0 && 6 * P <= SOLVE_MAX_N && M >= 0 && O >= 0 && pl.theta != nullptr && pl.theta_const_in != nullptr)) return pl.fail(SLAM_ERR_ARG, "slam_ba: bad arguments (P %lld, M %lld, O %lld)", P, M, O);
-    if (!(O == 0 || (pl.pixels_yx != nullptr && pose_ids != nullptr && point_ids != nullptr))) return pl.fail(SLAM_ERR_ARG, "slam_ba: observations without arrays");
+    if (!pl.order_only && !(P > 0 && 6 * P <= SOLVE_MAX_N && M >= 0 && O >= 0 && pl.theta != nullptr && pl.theta_const_in != nullptr)) return pl.fail(SLAM_ERR_ARG, "slam_ba: bad arguments (P %lld, M %lld, O %lld)", P, M, O);
+    if (!pl.order_only && !(O == 0 || (pl.pixels_yx != nullptr && pose_ids != nullptr && point_ids != nullptr))) return pl.fail(SLAM_ERR_ARG, "slam_ba: observations without arrays");
     pl.theta_const = pl.theta_const_in;
     const uint8_t *&theta_const = pl.theta_const;
     slam_ba *ba = pl.ba = new slam_ba();
@@ -144,8 +154,8 @@ int ba_plan(BAPlan &pl)
     };
     spans();
     if (bad_obs >= 0) return pl.fail(SLAM_ERR_ARG, "slam_ba: observation %lld has pose id %lld / point id %lld out of range", bad_obs, pose_ids[bad_obs], point_ids[bad_obs]);
-    static const bool no_reorder = getenv("SLAMHIP_BA_NO_REORDER") != nullptr;      // (measurement knob)
-    if (pl.may_reorder && !no_reorder && M > 0 && O > 0 && (hb > BS_MAXHB || !sg_fold_fits(hb)) && ba_pose_order(P, M, O, pl.theta_const_in, pose_ids, point_ids, ba->pose_order)) {
+    const BAKnobs &kn = ba_knobs();
+    if (pl.may_reorder && !kn.no_reorder && M > 0 && O > 0 && (hb > BS_MAXHB || !sg_fold_fits(hb)) && ba_pose_order(P, M, O, pl.theta_const_in, pose_ids, point_ids, ba->pose_order)) {
         // not banded in the caller's pose order, banded in another one: the solver works on relabelled poses, ba_download restores the order
         pl.new_of.resize(P); pl.const_perm.resize(P);
         for (int k = 0; k < P; k++) { pl.new_of[ba->pose_order[k]] = k; pl.const_perm[k] = pl.theta_const_in[ba->pose_order[k]]; }
@@ -153,6 +163,7 @@ int ba_plan(BAPlan &pl)
         spans();
     }
     ba->hb = hb; pl.hb = hb;
+    if (pl.order_only) return SLAM_OK;
     {   int f0 = P, f1 = -1;
         for (int p = 0; p < P; p++) if (!theta_const[p]) { f0 = std::min(f0, p); f1 = std::max(f1, p); }
         if (f1 - f0 + 1 >= 2) { ba->p0 = f0; ba->pspan = f1 - f0 + 1; } else { ba->p0 = 0; ba->pspan = P; } }
@@ -165,21 +176,17 @@ int ba_plan(BAPlan &pl)
     for (int k = 0; k < M; k++) start[k + 1] = start[k] + cnt[pt_id[k]];
     ba->perm.assign(O, 0);
     // --- point groups of k_schur_groups: same f, <= SG_SB points, <= SG_OB observations; evenly sized within one f
-    static const bool no_groups = getenv("SLAMHIP_NO_GROUPS") != nullptr;
     // (windows no order makes banded, hb > BS_MAXHB: the point groups still build the system -- their window is the whole block triangle -- when
     //  the free span is small enough for the dense one-workgroup solver, k_dense_solve, and the group's LDS layout fits)
-    static const bool no_dense = getenv("SLAMHIP_NO_DENSE") != nullptr;
-    const bool dense_ok = !no_dense && hb > BS_MAXHB && ba->pspan >= 2 && ba->pspan <= DS_MAXF && P <= DS_MAXF + 8 && sg_lds_bytes(hb, P) <= 150 * 1024;
-    bool grouped = !no_groups && (hb <= BS_MAXHB || dense_ok) && M > 0 && O > 0 && sg_fold_fits(hb);
+    const bool dense_ok = !kn.no_dense && hb > BS_MAXHB && ba->pspan >= 2 && ba->pspan <= DS_MAXF && P <= DS_MAXF + 8 && sg_lds_bytes(hb, P) <= 150 * 1024;
+    bool grouped = !kn.no_groups && (hb <= BS_MAXHB || dense_ok) && M > 0 && O > 0 && sg_fold_fits(hb);
     pl.nfree_obs = nfo;
     {   // a window one workgroup can keep to itself (k_ba_window, batches only): the point groups of the launch-per-phase kernels are not built
-        static const bool no_bw = getenv("SLAMHIP_NO_BA_WINDOW") != nullptr;
         int nfree = 0; for (int p = 0; p < P; p++) nfree += theta_const[p] ? 0 : 1;
         int cmax = 0; for (int j = 0; j < M; j++) cmax = std::max(cmax, cnt[j]);
-        pl.window = pl.small_groups && !no_bw && grouped && nfree >= 1 && nfree <= 5 && nfree == ba->pspan && P <= 128 && O <= 40000 && cmax <= 168;
+        pl.window = pl.small_groups && !kn.no_bw && grouped && nfree >= 1 && nfree <= 5 && nfree == ba->pspan && P <= 128 && O <= 40000 && cmax <= 168;
         if (pl.window) pl.sg_ob = std::max(cmax, 1);               // k_ba_window's tiles are sized from it (no point groups are built for such a window)
-        static const bool no_ends = getenv("SLAMHIP_BA_WINDOW_SORTED") != nullptr;      // (knob: keep the order by first free observer)
-        if (pl.window && M > 1 && !no_ends) {
+        if (pl.window && M > 1 && !kn.window_sorted) {
             // k_ba_window splits a window over two workgroups by map points: the points that see a free pose at all (the Schur phase's records --
             // a fifth of the reference's window, and next to each other in the order by first free observer) go to BOTH ends of the order,
             // alternately, the others between them: each half then holds half of the records and half of the observations (phase clocks per half:
@@ -198,7 +205,6 @@ int ba_plan(BAPlan &pl)
     fgrp.assign(P + 1, 0);
     int max_no = 0, max_np = 0;
     if (grouped && !pl.window) {
-        static const int sg_points = [] { const char *v = getenv("SLAMHIP_SG_POINTS"); return v ? atoi(v) : 0; }();      // (measurement knob)
         // points per group: a small window in full groups occupies a few compute units and each workgroup walks 7 points per subset; with
         // 16-point groups the reference-shaped window (800 points: 18 -> 50 groups) builds in 0.75 instead of 0.83 ms per 15 iterations,
         // while anything that already fills the chip gets slower with more, smaller groups (more partials for k_schur_reduce, more than one
@@ -206,7 +212,7 @@ int ba_plan(BAPlan &pl)
         // a batch of windows (small_groups) fills the chip whatever the group size: groups of <= 256 observations run as 256-thread
         // workgroups, three to a compute unit (128 reference-shaped windows: 7.5 ms with the single-window sizes, 3.7 ms so)
         int ob_cap = pl.small_groups ? 256 : SG_OB;
-        int sb_eff = sg_points > 0 ? std::min(sg_points, SG_SB)
+        int sb_eff = kn.sg_points > 0 ? std::min(kn.sg_points, SG_SB)
                    : pl.small_groups ? std::min(std::max(ob_cap / std::max(1, (O + M - 1) / M), 8), SG_SB)
                    : std::min(std::max((M + 95) / 96, 16), SG_SB);
         if (pl.small_groups) for (int j = 0; j < M; j++) if (cnt[j] > ob_cap) { ob_cap = SG_OB; sb_eff = std::min(sb_eff, SG_SB); break; }

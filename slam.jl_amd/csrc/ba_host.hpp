@@ -1,5 +1,6 @@
 // ba_host.hpp -- the host-only half of the local BA set-up (no HIP call, no device needed): structure analysis of a window (pose order, point groups,
 // pair lists), the layout of its three arena regions and the staging of its uploads.  Included at the end of ba_device.hpp (it uses slam_ba / BADev).
+// Also here: BAKnobs (the planner reads switches too) and the small host helpers slam_local_ba and slam_local_ba_batch share (batch_in, lm_stats, ba_unpermute).
 // Definitions: ba_host.hip.  reference: the arrays are those of src/estimator.jl:143-266 (_get_ba_parameters); the planner has no counterpart there.
 #pragma once
 inline size_t al(size_t b) { return (b + 255) & ~(size_t)255; }
@@ -15,13 +16,42 @@ bool ba_pose_order(int P, int M, int O, const uint8_t *theta_const, const int64_
 // (slam_local_ba, BAPlan::nthreads > 1) splits its own passes over the observations instead.  Never called from inside a task of the pool.
 void ba_parallel_for(int count, const std::function<void(int)> &fn);
 int ba_pool_threads();
+// Every SLAMHIP_* switch of the local BA, read once per process at the first ba_knobs() (names, defaults and meanings: scripts/README.md).  getenv occurs
+// nowhere else in the local BA; a test that sets a switch does so for a child process.
+struct BAKnobs {
+    static long long num(const char *v, long long dflt) { return v ? atoll(v) : dflt; }
+    // the planner (ba_plan, ba_plan_order)
+    bool no_reorder = getenv("SLAMHIP_BA_NO_REORDER") != nullptr;   // (measurement knob) the caller's pose order even where another one is banded
+    bool no_groups = getenv("SLAMHIP_NO_GROUPS") != nullptr;        // pair lists instead of point groups
+    bool no_dense = getenv("SLAMHIP_NO_DENSE") != nullptr;          // no one-workgroup dense solve (pair lists + tiled Cholesky for windows no order makes banded)
+    bool no_bw = getenv("SLAMHIP_NO_BA_WINDOW") != nullptr;         // the launch-per-phase kernels take the small windows of a batch (asked by ba_plan AND by batch_route)
+    bool window_sorted = getenv("SLAMHIP_BA_WINDOW_SORTED") != nullptr; // (knob) k_ba_window's map points stay in the order by first free observer
+    int sg_points = (int)num(getenv("SLAMHIP_SG_POINTS"), 0);   // <n> (measurement knob): points per group, 0 = ba_plan's own choice
+    int threads = (int)num(getenv("SLAMHIP_BA_THREADS"), 0);   // <n>: threads of the worker pool, 0 = hardware threads / 4 between 4 and 32
+    // the solve of one window (solve_route)
+    bool no_band = getenv("SLAMHIP_NO_BAND") != nullptr;            // the tiled Cholesky instead of the banded solve -- consulted by the single-window path only (see solve_route)
+    bool no_twist = getenv("SLAMHIP_NO_TWIST") != nullptr;          // one-sided banded factorisation
+    int twist_min = (int)num(getenv("SLAMHIP_TWIST_MIN"), 0);   // <n> (measurement knob): twisted from n free poses, 0 = the measured threshold
+    int twist_shift = (int)num(getenv("SLAMHIP_TWIST_SHIFT"), 0);   // <n> (measurement knob): side 0 takes 2 x shift columns more than side 1; +1 paid while the hand-over cost 13 k cycles, with 7 k an even split is 1 % ahead
+    bool twist_spread = getenv("SLAMHIP_TWIST_SPREAD") != nullptr;  // (test knob) the two sides on different XCDs
+    bool band_trace = getenv("SLAMHIP_BAND_TRACE") != nullptr;      // print k_band_solve's phase clocks (band_trace, ba_single.hip)
+    // the batch (batch_route)
+    int upload_parts = (int)num(getenv("SLAMHIP_BA_UPLOAD_PARTS"), 4);   // <n> (measurement knob): at most n parts of a large upload, default 4
+    bool t512 = getenv("SLAMHIP_BA_BATCH_T512") != nullptr;         // 512-thread point groups even where 256 fit
+    bool no_mfma = getenv("SLAMHIP_BA_NO_MFMA") != nullptr;         // the vector Schur build for every window (A/B timing, and the parity reference of the tests)
+    bool one_stream = getenv("SLAMHIP_BA_ONE_STREAM") != nullptr;   // (measurement knob) both halves of a batch on one stream
+    bool window_one = getenv("SLAMHIP_BA_WINDOW_ONE") != nullptr;   // k_ba_window always on one workgroup per window
+    long long xlimit = num(getenv("SLAMHIP_BA_XWAIT_US"), 500000LL) * 100;   // <n> x 100: the bound of k_ba_window's wait for its partner workgroup (default 500 000 us; 0 in the tests = give up at once)
+    bool host_times = getenv("SLAMHIP_BA_HOSTTIME") != nullptr;     // print the host-side time split of slam_local_ba / slam_local_ba_batch
+};
+inline const BAKnobs &ba_knobs() { static const BAKnobs kn; return kn; }
 #define BA_PAR_MIN_OBS 32768        // observations per task; windows below 6 such tasks stay on the calling thread (measured: 100 k observations gain nothing from three tasks)
 struct BAPlan {
     // inputs
     double fx = 0, fy = 0, cx = 0, cy = 0; int P = 0, M = 0, O = 0;
     const double *theta = nullptr; const uint8_t *theta_const_in = nullptr; const double *pixels_yx = nullptr;
     const int64_t *pose_ids = nullptr, *point_ids = nullptr;
-    bool may_reorder = false, small_groups = false;
+    bool may_reorder = false, small_groups = false, order_only = false;      // order_only: ba_plan stops behind the pose order and the half-bandwidth (ba_plan_order)
     int nthreads = 1;            // > 1: this one window's passes over the observations run on the worker pool (results identical to the serial passes)
     bool window = false;         // result: the window fits k_ba_window (<= 5 consecutive free poses, ...): no point groups are built for it
     int nfree_obs = 0;           // result: observations of free poses
@@ -122,3 +152,29 @@ struct BAPlan {
 };
 int ba_plan(BAPlan &pl);
 int ba_emit(BAPlan &pl, char *Aup, char *Azero, char *Awork, char *stage);
+int ba_plan_order(int P, int M, int O, const uint8_t *theta_const, const int64_t *pose_ids, const int64_t *point_ids, int32_t *order_out, int *hb_out);
+// S windows of a batch call: the prefix sums over the caller's concatenated arrays and one BAPlan's inputs per window (slam_local_ba_batch, slam_debug_ba_host_time)
+struct BatchIn { std::vector<size_t> th_off, pc_off, ob_off; std::vector<BAPlan> pl; };
+inline void batch_in(BatchIn &in, int S, const double *cams, const int32_t *Pn, const int32_t *Mn, const int32_t *On, const double *theta, const uint8_t *theta_const,
+                     const double *pixels_yx, const int64_t *pose_ids, const int64_t *point_ids)
+{
+    in.th_off.assign(S + 1, 0); in.pc_off.assign(S + 1, 0); in.ob_off.assign(S + 1, 0); in.pl = std::vector<BAPlan>(S);
+    for (int z = 0; z < S; z++) {
+        BAPlan &q = in.pl[z];
+        const size_t th = in.th_off[z], pc = in.pc_off[z], ob = in.ob_off[z];
+        in.th_off[z + 1] = th + 6 * (size_t)Pn[z] + 3 * (size_t)Mn[z]; in.pc_off[z + 1] = pc + Pn[z]; in.ob_off[z + 1] = ob + On[z];
+        q.fx = cams[4 * z]; q.fy = cams[4 * z + 1]; q.cx = cams[4 * z + 2]; q.cy = cams[4 * z + 3];
+        q.P = Pn[z]; q.M = Mn[z]; q.O = On[z]; q.theta = theta + th; q.theta_const_in = theta_const + pc;
+        q.pixels_yx = pixels_yx ? pixels_yx + 2 * ob : nullptr; q.pose_ids = pose_ids ? pose_ids + ob : nullptr; q.point_ids = point_ids ? point_ids + ob : nullptr;
+        q.may_reorder = true; q.small_groups = true;
+    }
+}
+// the eight values of `stats` (slam_local_ba and the batch)
+inline void lm_stats(const LMState &h, float dev_ms, double *sv) { sv[0] = h.ssr_init; sv[1] = h.ssr_pass1; sv[2] = h.ssr_final; sv[3] = h.iters_pass1; sv[4] = h.iters_pass2; sv[5] = h.n_outliers; sv[6] = dev_ms; sv[7] = h.chol_fail; }
+// results in the solver's pose order / sorted observation order -> the caller's arrays (either pair may be absent)
+inline void ba_unpermute(const slam_ba *ba, const double *poses, double *theta, const uint8_t *outl, uint8_t *outliers)
+{
+    if (poses && ba->pose_order.empty()) memcpy(theta, poses, (size_t)ba->d.n * 8);
+    else if (poses) for (int k = 0; k < ba->d.P; k++) memcpy(theta + 6 * ba->pose_order[k], poses + 6 * k, 48);
+    if (outl) for (int s = 0; s < ba->d.O; s++) outliers[ba->perm[s]] = outl[s];
+}

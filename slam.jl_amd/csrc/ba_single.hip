@@ -726,11 +726,8 @@ static int ba_enqueue_build(slam_ctx *ctx, slam_ba *ba, int ignore_outliers, dou
     const bool private_red = red == ba->reduce;
     if (!ba->grouped || !private_red || ba->zeroed != red) { HIP_TRY(ctx, hipMemsetAsync(red, 0, ((size_t)n * n + 2 * n + 8) * 8, st)); ba->zeroed = private_red ? red : nullptr; }
     if (ba->grouped) {
-        // the attribute belongs to the function object of the CURRENT device: once per device, result checked
-        // (the reference's three tasks call the library concurrently, SLAM.jl:166: the flag is atomic; setting the attribute twice is harmless)
-        static std::atomic<bool> attr_set[64];
-        const int dv = ctx->device & 63;
-        if (!attr_set[dv].load(std::memory_order_acquire)) { HIP_TRY(ctx, hipFuncSetAttribute((const void *)k_schur_groups, hipFuncAttributeMaxDynamicSharedMemorySize, (int)std::max(sg_lds_bytes(BS_MAXHB, SOLVE_MAX_N / 6), (size_t)150 * 1024))); attr_set[dv].store(true, std::memory_order_release); }
+        static std::atomic<bool> sg_attr[64];
+        if (const int rc = LDS_ATTR_ONCE(ctx, sg_attr, k_schur_groups, std::max(sg_lds_bytes(BS_MAXHB, SOLVE_MAX_N / 6), (size_t)150 * 1024))) return rc;
         hipLaunchKernelGGL(k_schur_groups, dim3(d.ngrp), dim3(SG_T), sg_lds_bytes(d.whb, d.P, d.sg_ob, d.sg_sb, 512, d.sg_hp), st, d, inv_delta, ignore_outliers, use_state);
         if (!use_state) hipLaunchKernelGGL(k_control, dim3(1), dim3(256), 0, st, d, 0, d.ngrp, ba->nblocks_pts, 0, red + (size_t)n * n + 2 * n);
         const int nthr = d.P * (d.whb + 1) * 36 + d.P * 12;
@@ -745,61 +742,51 @@ static int ba_enqueue_build(slam_ctx *ctx, slam_ba *ba, int ignore_outliers, dou
     return SLAM_OK;
 }
 
-static int ba_enqueue_solve(slam_ctx *ctx, slam_ba *ba, const double *red, int ignore_outliers, double inv_delta, int use_state,
-                            int lm, double *out4)
+// SLAMHIP_BAND_TRACE: the host buffer side 0 of k_band_solve writes its shader clocks to; those of the ninth launch are printed
+static long long *band_trace(hipStream_t st)
+{
+    static long long *trace_dev = nullptr; static int trace_n = 0;
+    if (!trace_dev) (void)hipHostMalloc((void **)&trace_dev, 1024);
+    if (trace_n++ == 8) {      // side 0 of the ninth launch, shader cycles
+        (void)hipStreamSynchronize(st);
+        fprintf(stderr, "band trace (cycles): factor wave: panel %lld factor %lld barrier %lld, then middle + back-substitution %lld | update wave 1: flag %lld update %lld barrier %lld | prefetch wave: flag %lld put/fetch %lld | backsub: chat %lld G %lld recurrence %lld\n",
+                trace_dev[5], trace_dev[4], trace_dev[1], trace_dev[3], trace_dev[2], trace_dev[6], trace_dev[7], trace_dev[8], trace_dev[9], trace_dev[10], trace_dev[11], trace_dev[12]);
+        fprintf(stderr, "  side 0 timeline (cycles): set-up (damping, first window, tables, L2 warm-up) %lld; then, since the end of the set-up: column loop starts %lld, own columns done %lld, middle assembled + factored %lld, forward done %lld\n", trace_dev[26], trace_dev[16], trace_dev[17], trace_dev[18], trace_dev[19]);
+        fprintf(stderr, "  set-up: pair table %lld, window requested %lld, tables %lld, warm-up requested %lld, damping in LDS %lld, window in the ring %lld\n", trace_dev[103], trace_dev[104], trace_dev[105], trace_dev[106], trace_dev[107], trace_dev[26]);
+        fprintf(stderr, "  middle: entries prepared %lld, flag seen %lld, fence done %lld, assembled %lld\n", trace_dev[22], trace_dev[23], trace_dev[24], trace_dev[25]);
+        fprintf(stderr, "  XCC_ID of side 0 / side 1: %lld / %lld; of the idle workgroups 1-7:", trace_dev[20] & 15, trace_dev[21] & 15);
+        for (int w = 1; w < 8; w++) fprintf(stderr, " %lld", trace_dev[80 + w] & 15);
+        fprintf(stderr, "\n");
+        const long long t0 = trace_dev[32];      // step 10 per wave, relative to wave 0's start of the step: start, (wave 0: flag published), arrival at the barrier, release
+        fprintf(stderr, "  factor wave, step 10: row loaded %lld, substituted %lld, flag %lld, D entry %lld, D in every lane %lld\n",
+                trace_dev[96] - t0, trace_dev[97] - t0, trace_dev[40] - t0, trace_dev[98] - t0, trace_dev[99] - t0);
+        fprintf(stderr, "  wave 3: registers copied %lld, blocks in the ring %lld, next row requested %lld\n", trace_dev[72] - t0, trace_dev[73] - t0, trace_dev[74] - t0);
+        for (int w = 0; w < 8; w++) fprintf(stderr, "  wave %d (simd %lld): start %lld%s arrive %lld release %lld\n", w, (trace_dev[64 + w] >> 4) & 3, trace_dev[32 + w] - t0,
+                                            w == 0 ? (" flag " + std::to_string(trace_dev[40] - t0)).c_str() : "", trace_dev[48 + w] - t0, trace_dev[56 + w] - t0);
+    }
+    return trace_dev;
+}
+
+static int ba_enqueue_solve(slam_ctx *ctx, slam_ba *ba, const double *red, int ignore_outliers, double inv_delta, int use_state, int lm, double *out4)
 {
     BADev d = ba->d;
     const int n = d.n;
     hipStream_t st = ctx->stream;
-    static const bool no_band = getenv("SLAMHIP_NO_BAND") != nullptr;
-    const int Ps = ba->pspan > 0 ? ba->pspan : d.P, p0 = ba->pspan > 0 ? ba->p0 : 0;       // the poses the banded solve covers: first .. last free pose
-    const int hb = std::min(std::max(ba->hb, 1), Ps - 1);      // >= 1: the factor wave reads block row k + 1 while row k + 1 + hb enters the ring
-    const size_t band_lds = band_lds_bytes(n, Ps, hb);
-    if (ba->grouped && hb > BS_MAXHB && Ps <= DS_MAXF) {       // not banded, small: dense one-workgroup solve (ba_plan admitted the groups for exactly this case)
-        BandArgs B = {}; B.S = red + (size_t)6 * p0 * (n + 1); B.g = red + (size_t)n * n + 6 * p0; B.ud = red + (size_t)n * n + n + 6 * p0; B.Lg = nullptr; B.nb = Ps; B.hb = hb; B.p0 = p0;
-        B.inv_delta_host = inv_delta; B.fail = ba->chol_flag;
-        static std::atomic<bool> ds_attr[64];
-        const int dv = ctx->device & 63;
-        if (!ds_attr[dv].load(std::memory_order_acquire)) { HIP_TRY(ctx, hipFuncSetAttribute((const void *)k_dense_solve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dense_lds_bytes(DS_MAXF))); ds_attr[dv].store(true, std::memory_order_release); }
-        hipLaunchKernelGGL(k_dense_solve, dim3(1), dim3(DS_T), dense_lds_bytes(Ps), st, d, B, use_state);
-    } else
-    if (!no_band && hb <= BS_MAXHB && band_lds <= 150 * 1024) {
-        BandArgs B; B.S = red + (size_t)6 * p0 * (n + 1); B.g = red + (size_t)n * n + 6 * p0; B.ud = red + (size_t)n * n + n + 6 * p0; B.Lg = ba->band; B.nb = Ps; B.hb = hb; B.p0 = p0;
-        B.inv_delta_host = inv_delta; B.fail = ba->chol_flag; B.lds_bytes = (int)band_lds;
-        B.xchg = ba->xchg; B.epoch = ++ba->epoch;
-        static const int twist_shift = [] { const char *v = getenv("SLAMHIP_TWIST_SHIFT"); return v ? atoi(v) : 0; }();    // (measurement knob: side 0 takes 2 x shift columns more than side 1; +1 paid while the hand-over cost 13 k cycles, with 7 k an even split is 1 % ahead)
-        B.shift = twist_shift;
-        static const bool no_twist = getenv("SLAMHIP_NO_TWIST") != nullptr;
-        // (the two workgroups wait for each other: both must be resident, which a stream confined to one compute unit cannot promise)
-        static const int twist_min = [] { const char *v = getenv("SLAMHIP_TWIST_MIN"); return v ? atoi(v) : 0; }();    // (measurement knob)
-        const bool twist = !no_twist && hb * 6 <= 58 && Ps >= (twist_min > 0 ? std::max(twist_min, hb + 8) : std::max(2 * (hb + 1) - 1, hb + 8))      /* measured: pays from 19 free poses at hb = 9 (19: 92.1 -> 89.3 us per iteration, 18: equal) since the hand-overs stay in one L2 (24 before) */ && ctx->xwg_ok;
-        static long long *trace_dev = nullptr; static int trace_n = 0;
-        static const bool trace_on = getenv("SLAMHIP_BAND_TRACE") != nullptr;
-        if (trace_on && !trace_dev) (void)hipHostMalloc((void **)&trace_dev, 1024);
-        B.trace = trace_dev;
-        if (trace_on && trace_n++ == 8) {      // side 0 of the ninth launch, shader cycles
-            (void)hipStreamSynchronize(st);
-            fprintf(stderr, "band trace (cycles): factor wave: panel %lld factor %lld barrier %lld, then middle + back-substitution %lld | update wave 1: flag %lld update %lld barrier %lld | prefetch wave: flag %lld put/fetch %lld | backsub: chat %lld G %lld recurrence %lld\n",
-                    trace_dev[5], trace_dev[4], trace_dev[1], trace_dev[3], trace_dev[2], trace_dev[6], trace_dev[7], trace_dev[8], trace_dev[9], trace_dev[10], trace_dev[11], trace_dev[12]);
-            fprintf(stderr, "  side 0 timeline (cycles): set-up (damping, first window, tables, L2 warm-up) %lld; then, since the end of the set-up: column loop starts %lld, own columns done %lld, middle assembled + factored %lld, forward done %lld\n", trace_dev[26], trace_dev[16], trace_dev[17], trace_dev[18], trace_dev[19]);
-            fprintf(stderr, "  set-up: pair table %lld, window requested %lld, tables %lld, warm-up requested %lld, damping in LDS %lld, window in the ring %lld\n", trace_dev[103], trace_dev[104], trace_dev[105], trace_dev[106], trace_dev[107], trace_dev[26]);
-            fprintf(stderr, "  middle: entries prepared %lld, flag seen %lld, fence done %lld, assembled %lld\n", trace_dev[22], trace_dev[23], trace_dev[24], trace_dev[25]);
-            fprintf(stderr, "  XCC_ID of side 0 / side 1: %lld / %lld; of the idle workgroups 1-7:", trace_dev[20] & 15, trace_dev[21] & 15);
-            for (int w = 1; w < 8; w++) fprintf(stderr, " %lld", trace_dev[80 + w] & 15);
-            fprintf(stderr, "\n");
-            const long long t0 = trace_dev[32];      // step 10 per wave, relative to wave 0's start of the step: start, (wave 0: flag published), arrival at the barrier, release
-            fprintf(stderr, "  factor wave, step 10: row loaded %lld, substituted %lld, flag %lld, D entry %lld, D in every lane %lld\n",
-                    trace_dev[96] - t0, trace_dev[97] - t0, trace_dev[40] - t0, trace_dev[98] - t0, trace_dev[99] - t0);
-            fprintf(stderr, "  wave 3: registers copied %lld, blocks in the ring %lld, next row requested %lld\n", trace_dev[72] - t0, trace_dev[73] - t0, trace_dev[74] - t0);
-            for (int w = 0; w < 8; w++) fprintf(stderr, "  wave %d (simd %lld): start %lld%s arrive %lld release %lld\n", w, (trace_dev[64 + w] >> 4) & 3, trace_dev[32 + w] - t0,
-                                                w == 0 ? (" flag " + std::to_string(trace_dev[40] - t0)).c_str() : "", trace_dev[48 + w] - t0, trace_dev[56 + w] - t0);
-        }
-        static std::atomic<bool> attr_set[64];
-        const int dv = ctx->device & 63;
-        if (!attr_set[dv].load(std::memory_order_acquire)) { HIP_TRY(ctx, hipFuncSetAttribute((const void *)k_band_solve, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024)); attr_set[dv].store(true, std::memory_order_release); }
-        static const bool twist_spread = getenv("SLAMHIP_TWIST_SPREAD") != nullptr;     // (test knob: the two sides on different XCDs)
-        hipLaunchKernelGGL(k_band_solve, dim3(twist ? (twist_spread ? 2 : 9) : 1), dim3(BS_T), band_lds, st, d, B, use_state);
-    } else {
+    const SolveRoute r = solve_route(ba, d.P, ctx, false);
+    static std::atomic<bool> ds_attr[64], bs_attr[64];
+    switch (r.kind) {
+    case SOLVE_DENSE: {
+        const BandArgs B = band_args(ba, r, red, inv_delta);
+        if (const int rc = LDS_ATTR_ONCE(ctx, ds_attr, k_dense_solve, dense_lds_bytes(DS_MAXF))) return rc;
+        hipLaunchKernelGGL(k_dense_solve, dim3(1), dim3(DS_T), dense_lds_bytes(r.Ps), st, d, B, use_state);
+        break; }
+    case SOLVE_BAND: {
+        BandArgs B = band_args(ba, r, red, inv_delta);
+        B.epoch = ++ba->epoch; B.trace = ba_knobs().band_trace ? band_trace(st) : nullptr;
+        if (const int rc = LDS_ATTR_ONCE(ctx, bs_attr, k_band_solve, 150 * 1024)) return rc;
+        hipLaunchKernelGGL(k_band_solve, dim3(r.grid), dim3(BS_T), r.band_lds, st, d, B, use_state);
+        break; }
+    case SOLVE_TILED: {
         CholArgs C; C.A = d.Swork; C.Lf = ba->lfac; C.n = n; C.ld = n + 1; C.fail = ba->chol_flag;
         const size_t tot = (size_t)(n + 1) * n;
         hipLaunchKernelGGL(k_chol_prepare, dim3((tot + 255) / 256), dim3(256), 0, st, d, red, red + (size_t)n * n, red + (size_t)n * n + n, inv_delta, use_state);
@@ -811,6 +798,7 @@ static int ba_enqueue_solve(slam_ctx *ctx, slam_ba *ba, const double *red, int i
             if (tiles > 1) hipLaunchKernelGGL(k_chol_step, dim3(tiles), dim3(256), 0, st, d, C, ba->linv, k, nbr, use_state);
         }
         hipLaunchKernelGGL(k_chol_backsolve, dim3(1), dim3(256), 0, st, d, C, (const double *)ba->linv, use_state);
+        break; }
     }
     if (ba->grouped) {
         hipLaunchKernelGGL(k_update_groups, dim3(d.ngrp), dim3(SG_T), 0, st, d, ignore_outliers, use_state);
@@ -823,11 +811,19 @@ static int ba_enqueue_solve(slam_ctx *ctx, slam_ba *ba, const double *red, int i
     return SLAM_OK;
 }
 
-static int ba_enqueue_commit(slam_ctx *ctx, slam_ba *ba, int accept, int use_state, int iter_tag)
+static int ba_enqueue_commit(slam_ctx *ctx, slam_ba *ba, int accept, int use_state)
 {
-    (void)iter_tag;
     if (use_state) return SLAM_OK;                           // device-paced: lm_decide has swapped the buffers already
     hipLaunchKernelGGL(k_commit, dim3(1), dim3(1), 0, ctx->stream, ba->d, accept);
+    return SLAM_OK;
+}
+
+// the tail of an entry point that enqueues: the launches' error, then -- the host-paced calls -- the wait for the stream
+static int ba_enqueued(slam_ctx *ctx, int rc, bool wait)
+{
+    if (rc) return rc;
+    HIP_TRY(ctx, hipGetLastError());
+    if (wait) HIP_TRY(ctx, slam_stream_wait(ctx->stream));
     return SLAM_OK;
 }
 
@@ -860,11 +856,7 @@ int slam_ba_build(slam_ctx *ctx, slam_ba *ba, int ignore_outliers, double inv_de
 {
     ARG_TRY(ctx, ctx != nullptr && ba != nullptr && reduce_dev != nullptr);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc = ba_enqueue_build(ctx, ba, ignore_outliers, inv_delta, 0, reduce_dev);
-    if (rc) return rc;
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, slam_stream_wait(ctx->stream));
-    return SLAM_OK;
+    return ba_enqueued(ctx, ba_enqueue_build(ctx, ba, ignore_outliers, inv_delta, 0, reduce_dev), true);
 }
 
 int slam_ba_solve(slam_ctx *ctx, slam_ba *ba, const double *reduce_dev, double inv_delta, double *trial_dev)
@@ -872,21 +864,14 @@ int slam_ba_solve(slam_ctx *ctx, slam_ba *ba, const double *reduce_dev, double i
     ARG_TRY(ctx, ctx != nullptr && ba != nullptr && reduce_dev != nullptr && trial_dev != nullptr);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     // ignore_outliers for the trial residual follows the flags: outliers are only ever set by slam_ba_flag_outliers
-    int rc = ba_enqueue_solve(ctx, ba, reduce_dev, 1, inv_delta, 0, 0, trial_dev);
-    if (rc) return rc;
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, slam_stream_wait(ctx->stream));
-    return SLAM_OK;
+    return ba_enqueued(ctx, ba_enqueue_solve(ctx, ba, reduce_dev, 1, inv_delta, 0, 0, trial_dev), true);
 }
 
 int slam_ba_commit(slam_ctx *ctx, slam_ba *ba, int accept)
 {
     ARG_TRY(ctx, ctx != nullptr && ba != nullptr);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    ba_enqueue_commit(ctx, ba, accept, 0, 0);
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, slam_stream_wait(ctx->stream));
-    return SLAM_OK;
+    return ba_enqueued(ctx, ba_enqueue_commit(ctx, ba, accept, 0), true);
 }
 
 // ---- device-paced LM for the sharded path: every call returns after enqueueing on ctx's stream; the accept / reject decision
@@ -895,10 +880,7 @@ int slam_ba_lm_begin(slam_ctx *ctx, slam_ba *ba, int ignore_outliers, double *re
 {
     ARG_TRY(ctx, ctx != nullptr && ba != nullptr && reduce_dev != nullptr);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc = ba_enqueue_build(ctx, ba, ignore_outliers, 1.0 / LM_DELTA0, 0, reduce_dev);
-    if (rc) return rc;
-    HIP_TRY(ctx, hipGetLastError());
-    return SLAM_OK;
+    return ba_enqueued(ctx, ba_enqueue_build(ctx, ba, ignore_outliers, 1.0 / LM_DELTA0, 0, reduce_dev), false);
 }
 int slam_ba_lm_start(slam_ctx *ctx, slam_ba *ba, const double *reduce_dev, int first_pass)
 {
@@ -906,35 +888,26 @@ int slam_ba_lm_start(slam_ctx *ctx, slam_ba *ba, const double *reduce_dev, int f
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int n = ba->d.n;
     hipLaunchKernelGGL(k_lm_start, dim3(1), dim3(1), 0, ctx->stream, ba->d, reduce_dev + (size_t)n * n + 2 * n, first_pass);
-    HIP_TRY(ctx, hipGetLastError());
-    return SLAM_OK;
+    return ba_enqueued(ctx, SLAM_OK, false);
 }
 int slam_ba_lm_build(slam_ctx *ctx, slam_ba *ba, int ignore_outliers, double *reduce_dev)
 {
     ARG_TRY(ctx, ctx != nullptr && ba != nullptr && reduce_dev != nullptr);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc = ba_enqueue_build(ctx, ba, ignore_outliers, 0.0, 1, reduce_dev);
-    if (rc) return rc;
-    HIP_TRY(ctx, hipGetLastError());
-    return SLAM_OK;
+    return ba_enqueued(ctx, ba_enqueue_build(ctx, ba, ignore_outliers, 0.0, 1, reduce_dev), false);
 }
 int slam_ba_lm_solve(slam_ctx *ctx, slam_ba *ba, const double *reduce_dev, int ignore_outliers, double *trial_dev)
 {
     ARG_TRY(ctx, ctx != nullptr && ba != nullptr && reduce_dev != nullptr && trial_dev != nullptr);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc = ba_enqueue_solve(ctx, ba, reduce_dev, ignore_outliers, 0.0, 1, 0, trial_dev);
-    if (rc) return rc;
-    HIP_TRY(ctx, hipGetLastError());
-    return SLAM_OK;
+    return ba_enqueued(ctx, ba_enqueue_solve(ctx, ba, reduce_dev, ignore_outliers, 0.0, 1, 0, trial_dev), false);
 }
 int slam_ba_lm_step(slam_ctx *ctx, slam_ba *ba, const double *gathered_dev, int nranks, int iter_tag)
 {
     ARG_TRY(ctx, ctx != nullptr && ba != nullptr && gathered_dev != nullptr && nranks >= 1);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipLaunchKernelGGL(k_control_gathered, dim3(1), dim3(1), 0, ctx->stream, ba->d, gathered_dev, nranks);
-    ba_enqueue_commit(ctx, ba, 0, 1, iter_tag);
-    HIP_TRY(ctx, hipGetLastError());
-    return SLAM_OK;
+    return ba_enqueued(ctx, ba_enqueue_commit(ctx, ba, 0, 1), false);
 }
 // synchronises; out8 = {ssr, iters, converged, delta, chol_fail, ssr_init, trial_ssr, max|dx|}
 int slam_ba_lm_state(slam_ctx *ctx, slam_ba *ba, double *out8)
@@ -948,39 +921,11 @@ int slam_ba_lm_state(slam_ctx *ctx, slam_ba *ba, double *out8)
     out8[6] = h.trial_ssr; out8[7] = h.maxdx;
     return SLAM_OK;
 }
+// host only: the pose order slam_local_ba solves in, and the block half-bandwidth of the reduced camera system in that order (ba_plan_order, ba_host.hip)
+int slam_ba_plan_order(int P, int M, int O, const uint8_t *theta_const, const int64_t *pose_ids, const int64_t *point_ids, int32_t *order_out, int *hb_out) { return ba_plan_order(P, M, O, theta_const, pose_ids, point_ids, order_out, hb_out); }
+
 // block half-bandwidth of this shard's reduced system (S_pq = 0 for |p - q| > hb); the all-reduced system has the maximum over
 // the ranks, which the driver sets on every rank before the first solve
-// host only: the pose order slam_local_ba solves in, and the block half-bandwidth of the reduced camera system in that order
-int slam_ba_plan_order(int P, int M, int O, const uint8_t *theta_const, const int64_t *pose_ids, const int64_t *point_ids, int32_t *order_out, int *hb_out)
-{
-    if (P <= 0 || M < 0 || O < 0 || !theta_const || (O > 0 && (!pose_ids || !point_ids))) return SLAM_ERR_ARG;
-    for (int i = 0; i < O; i++) if (pose_ids[i] < 1 || pose_ids[i] > P || point_ids[i] < 1 || point_ids[i] > M) return SLAM_ERR_ARG;
-    std::vector<int> new_of(P), order(P);
-    for (int p = 0; p < P; p++) new_of[p] = order[p] = p;
-    auto halfband = [&]() {
-        std::vector<int> lo(M, P), hi(M, -1);
-        for (int i = 0; i < O; i++) {
-            if (theta_const[pose_ids[i] - 1]) continue;
-            const int j = (int)point_ids[i] - 1, q = new_of[pose_ids[i] - 1];
-            lo[j] = std::min(lo[j], q); hi[j] = std::max(hi[j], q);
-        }
-        int hb = 0;
-        for (int j = 0; j < M; j++) if (hi[j] >= 0) hb = std::max(hb, hi[j] - lo[j]);
-        return hb;
-    };
-    int hb = halfband(), reordered = 0;
-    static const bool no_reorder = getenv("SLAMHIP_BA_NO_REORDER") != nullptr;
-    std::vector<int> cand;
-    if (!no_reorder && M > 0 && O > 0 && (hb > BS_MAXHB || !sg_fold_fits(hb)) && ba_pose_order(P, M, O, theta_const, pose_ids, point_ids, cand)) {
-        order = cand;
-        for (int k = 0; k < P; k++) new_of[order[k]] = k;
-        hb = halfband(); reordered = 1;
-    }
-    if (order_out) for (int k = 0; k < P; k++) order_out[k] = order[k];
-    if (hb_out) *hb_out = hb;
-    return reordered;
-}
-
 int slam_ba_halfband(const slam_ba *ba) { return ba ? ba->hb : SLAM_ERR_ARG; }
 int slam_ba_set_halfband(slam_ba *ba, int hb) { if (!ba || hb < 0) return SLAM_ERR_ARG; ba->hb = hb; return SLAM_OK; }
 
@@ -1015,14 +960,14 @@ static int ba_download(slam_ctx *ctx, slam_ba *ba, double *theta, uint8_t *outli
             std::vector<double> tmp(d.n);
             HIP_TRY(ctx, hipMemcpyAsync(tmp.data(), cur ? d.pose_t : d.pose, (size_t)d.n * 8, hipMemcpyDeviceToHost, ctx->stream));
             HIP_TRY(ctx, slam_stream_wait(ctx->stream));
-            for (int k = 0; k < d.P; k++) memcpy(theta + 6 * ba->pose_order[k], &tmp[6 * k], 48);
+            ba_unpermute(ba, tmp.data(), theta, nullptr, nullptr);
         }
         if (d.M > 0) HIP_TRY(ctx, hipMemcpyAsync(theta + d.n, cur ? d.pts_t : d.pts, (size_t)3 * d.M * 8, hipMemcpyDeviceToHost, ctx->stream));
     }
     std::vector<uint8_t> tmp;
     if (outliers && d.O > 0) { tmp.resize(d.O); HIP_TRY(ctx, hipMemcpyAsync(tmp.data(), d.outl, (size_t)d.O, hipMemcpyDeviceToHost, ctx->stream)); }
     HIP_TRY(ctx, slam_stream_wait(ctx->stream));
-    if (outliers) for (int s = 0; s < d.O; s++) outliers[ba->perm[s]] = tmp[s];
+    if (outliers) ba_unpermute(ba, nullptr, nullptr, tmp.data(), outliers);
     return SLAM_OK;
 }
 int slam_ba_download(slam_ctx *ctx, slam_ba *ba, double *theta, uint8_t *outliers) { return ba_download(ctx, ba, theta, outliers, -1); }
@@ -1035,7 +980,6 @@ int slam_local_ba(slam_ctx *ctx, double fx, double fy, double cx, double cy, int
     ARG_TRY(ctx, ctx != nullptr && outliers != nullptr && iters_fast >= 0 && iterations >= 0);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     slam_ba *ba = nullptr;
-    static const bool host_times = getenv("SLAMHIP_BA_HOSTTIME") != nullptr;
     const auto tw0 = std::chrono::steady_clock::now();
     int rc = ba_setup(ctx, fx, fy, cx, cy, P, M, O, theta, theta_const, pixels_yx, pose_ids, point_ids, &ba, true, true);
     if (rc) return rc;
@@ -1053,7 +997,7 @@ int slam_local_ba(slam_ctx *ctx, double fx, double fy, double cx, double cy, int
         for (int it = 1; it <= iters; it++) {
             ba_enqueue_build(ctx, ba, ignore, 0.0, 1, ba->reduce);
             ba_enqueue_solve(ctx, ba, ba->reduce, ignore, 0.0, 1, 1, nullptr);
-            ba_enqueue_commit(ctx, ba, 0, 1, it);
+            ba_enqueue_commit(ctx, ba, 0, 1);
         }
     };
     run_pass(0, iters_fast);
@@ -1078,16 +1022,13 @@ int slam_local_ba(slam_ctx *ctx, double fx, double fy, double cx, double cy, int
     rc = h.chol_fail ? SLAM_OK : ba_download(ctx, ba, theta, outliers, h.cur);
     const auto tw3 = std::chrono::steady_clock::now();
     slam_ba_destroy(ba);
-    if (host_times) {
+    if (ba_knobs().host_times) {
         const auto us = [](auto a, auto b) { return (long)std::chrono::duration_cast<std::chrono::microseconds>(b - a).count(); };
         fprintf(stderr, "slam_local_ba host: setup %ld us, enqueue + wait %ld us (device %.0f us), download %ld us, destroy %ld us\n",
                 us(tw0, tw1), us(tw1, tw2), ms * 1e3, us(tw2, tw3), us(tw3, std::chrono::steady_clock::now()));
     }
     if (rc) return rc;
-    if (stats) {
-        stats[0] = h.ssr_init; stats[1] = h.ssr_pass1; stats[2] = h.ssr_final; stats[3] = h.iters_pass1; stats[4] = h.iters_pass2;
-        stats[5] = h.n_outliers; stats[6] = ms; stats[7] = h.chol_fail;
-    }
+    if (stats) lm_stats(h, ms, stats);
     if (h.chol_fail) return slam_fail(ctx, SLAM_ERR_NUMERIC, "slam_local_ba: reduced camera system not positive definite (theta and outliers left unchanged)");
     return SLAM_OK;
 }
