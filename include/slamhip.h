@@ -403,6 +403,63 @@ int slam_triangulate(slam_ctx *ctx, const double *P1, const double *P2, const do
                      const double *parallax, double min_parallax,
                      double *out_xyz, uint8_t *status);
 
+/* Array-level body of the mapper's local-map re-matching -- do_local_map_matching + find_best_match + mappoint_min_distance
+ * (src/mapper.jl:318-462, src/map_point.jl:165-174), the consumer of slam_describe's descriptors (map_manager.jl:108-112).  The hash-map work
+ * around it (union! of local-map ids :274-286, merge_mappoints :296-310, the remove_mappoint_obs! clean-ups :412, :429-434) stays with the caller.
+ * All arrays are host arrays; the batch form (S lock-stepped streams, no reference counterpart) concatenates every array over the streams:
+ * stream s owns the keypoints [kp_offsets[s], kp_offsets[s+1]), the key-frame rows [kf_offsets[s], ..) and the local-map points
+ * [mp_offsets[s], ..) (S + 1 entries each, first 0), the CSR offset arrays run over the concatenated keypoints / points, and key-frame rows in
+ * the observer lists are local to their stream.  slam_local_map_match is the batch of one stream with N keypoints, K key-frames, M points.
+ *   Tcw [S x 16]            frame.cw, 4x4 column-major (frame.jl:458-462)
+ *   cam [S x 10]            fx, fy, cx, cy, k1, k2, p1, p2, height, width of the Camera frames and key-frames share (camera.jl:79-125)
+ *   cell_size [S]           frame.cell_size (SLAM.jl:42-45; the grid is ceil(height / cell_size) x ceil(width / cell_size))
+ *   nb_3d_kpts [S]          frame.nb_3d_kpts: below 30 the projection distance is doubled (mapper.jl:332)
+ *   max_projection_distance, max_descriptor_distance [S]   the keyword arguments (mapper.jl:290-291, :320)
+ *   kp_yx [N x 2]           kp.pixel of the frame's keypoints, 1-based (y, x), in the caller's list order (mapper.jl:407); the candidates of a
+ *                           cell are met in this order (the reference iterates a Set there, frame.jl:588), and it decides ties
+ *   kp_desc_off [N + 1], kp_desc [. x 4]   values(keyframes_descriptors) of each keypoint's map point (map_point.jl:168), one row of
+ *                           slam_describe's out_bits (4 x uint64) per descriptor; a keypoint given none is skipped (mapper.jl:406, :411-415)
+ *   kp_obs_off [N + 1], kp_obs_kf [.], kp_obs_yx [. x 2]   get_observers(mp) as rows of the key-frame table and observer_kp.pixel in that
+ *                           key-frame (mapper.jl:419, :427-438)
+ *   kf_Tcw [K x 16]         observer_kf.cw of every key-frame the observer lists name (mapper.jl:436-437)
+ *   mp_xyz [M x 3]          get_position(mp) of the local map in the caller's iteration order of frame.local_map_ids, without the entries
+ *                           mapper.jl:338-341 skips
+ *   mp_desc_off [M + 1], mp_desc [. x 4]   values(target_mp.keyframes_descriptors) (map_point.jl:168)
+ *   mp_obs_off [M + 1], mp_obs_kf [.]      get_observers(target_mp) (mapper.jl:397)
+ * Outputs:
+ *   match [N]       the local-map index prev_new_map maps keypoint j to, or -1 (mapper.jl:370-382)
+ *   best_kp [M]     find_best_match's best_id as a keypoint index of the stream, or -1 (mapper.jl:461)
+ *   best_dist [M]   its best_distance (256 max_descriptor_distance when nothing was taken); -1 where find_best_match was not called
+ *   proj_yx [M x 2] the projection (mapper.jl:351), NaN where a gate of :346-352 dropped the point
+ * Semantics kept: gates in the reference's order (z < 0.1, |z / norm| < cos(atan(max(0.5 H / fy, 0.5 W / fx))), project_undistort, in_image);
+ * cell = round-to-even(p) / cell_size + 1, cells outside the grid skipped one by one (frame.jl:584-586); cells r outer / c inner; both selections
+ * compare with <=, so among equal distances the LAST candidate wins (:445, :375); a keypoint without listed observers has the mean 0/0 = NaN and
+ * passes (:441-442); distance = min popcount(d1 xor d2) over all descriptor pairs as a double, start value 256 max_descriptor_distance (:401).
+ * A stream with N = 0 or M = 0 returns -1 everywhere (NaN in proj_yx) and launches nothing.  Decreasing offsets, an observer row outside its
+ * stream's key-frame table, a keypoint outside the grid or a null array are argument errors: nothing is copied or launched.
+ * Per stream the call moves about M (24 + 32 D + 4 O) + N (16 + 32 D + 20 O) + 4 (cells + N) bytes (D descriptors, O observers per point): under
+ * 2 MB at M = 10 000, N = 1 000 -- bound by latency and issue, not by bandwidth. */
+typedef struct slam_local_map_args {
+    const double *Tcw, *cam;
+    const int32_t *cell_size, *nb_3d_kpts;
+    const double *max_projection_distance, *max_descriptor_distance;
+    const double *kp_yx;
+    const int32_t *kp_desc_off;
+    const uint64_t *kp_desc;
+    const int32_t *kp_obs_off, *kp_obs_kf;
+    const double *kp_obs_yx;
+    const double *kf_Tcw;
+    const double *mp_xyz;
+    const int32_t *mp_desc_off;
+    const uint64_t *mp_desc;
+    const int32_t *mp_obs_off, *mp_obs_kf;
+    int32_t *match, *best_kp;
+    double *best_dist, *proj_yx;
+} slam_local_map_args;
+int slam_local_map_match(slam_ctx *ctx, const slam_local_map_args *args, int N, int K, int M);
+int slam_local_map_match_batch(slam_ctx *ctx, int S, const int32_t *kp_offsets, const int32_t *kf_offsets, const int32_t *mp_offsets,
+                               const slam_local_map_args *args);
+
 /* p3p_ransac(points, pixels, pdn, K; threshold) of compute_pose! (src/front_end.jl:164-167; result consumed at
  * :174-186: n_inliers, (KP, inliers, error)).  pts3d n x 3 map points, px_xy n x 2 undistorted pixels in (x, y)
  * order (front_end.jl:150-151), pdn n x 3 bearing vectors normalize(kp.position) (:149), K 3x3 column-major.

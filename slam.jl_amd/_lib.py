@@ -40,6 +40,8 @@ SIGNATURES = {
     "slam_detect_pyr": (cint, [vp, vp, f64p, cint, cint, cint, cint, cint, cint, dbl, dbl, i64p, cint, C.POINTER(cint)]),
     "slam_detect_batch": (cint, [vp, vp, cint, f64p, i32p, cint, cint, cint, cint, cint, dbl, dbl, i64p, cint, i32p]),
     "slam_triangulate": (cint, [vp, f64p, f64p, f64p, f64p, f64p, f64p, f64p, cint, dbl, dbl, f64p, dbl, f64p, u8p]),
+    "slam_local_map_match": (cint, [vp, vp, cint, cint, cint]),
+    "slam_local_map_match_batch": (cint, [vp, cint, i32p, i32p, i32p, vp]),
     "slam_p3p_ransac": (cint, [vp, f64p, f64p, f64p, cint, f64p, dbl, i32p, cint, f64p, f64p, u8p, C.POINTER(cint), f64p, C.POINTER(cint)]),
     "slam_five_point_ransac": (cint, [vp, f64p, f64p, f64p, f64p, cint, f64p, f64p, dbl, i32p, cint, f64p, f64p, u8p, C.POINTER(cint), f64p, C.POINTER(cint)]),
     "slam_p3p_ransac_batch": (cint, [vp, cint, i32p, f64p, f64p, f64p, f64p, dbl, i32p, cint, f64p, f64p, u8p, i32p, f64p, i32p]),

@@ -261,6 +261,85 @@ function hip_triangulate(cam1::Camera, cam2::Camera, P1::SMatrix{4, 4, Float64},
     [SVector{3, Float64}(out[3i - 2], out[3i - 1], out[3i]) for i in 1:n], Bool[s != 0 for s in st[1:n]]
 end
 
+# Array-level body of do_local_map_matching / find_best_match (mapper.jl:318-462), the consumer of `describe`'s descriptors: gathers the
+# arrays of slam_local_map_match from MapManager / Frame / MapPoint, calls it once and returns the `Dict{Int64, Int64}` (matched keypoint id =>
+# local-map keypoint id) that do_local_map_matching returns.  Not bound by activate!: the reference interleaves remove_mappoint_obs! with the
+# search (mapper.jl:412, :429-434), so a maintainer calls this from match_local_map! in place of do_local_map_matching and does the clean-ups
+# of the vanished map points / observers it skipped before or after.  The keypoints are listed cell by cell in the iteration order of the
+# grid's Sets (frame.jl:588), which is the order that decides ties.
+struct LocalMapArgs                                  # slam_local_map_args (include/slamhip.h), field for field
+    Tcw::Ptr{Float64}; cam::Ptr{Float64}; cell_size::Ptr{Int32}; nb_3d_kpts::Ptr{Int32}
+    max_projection_distance::Ptr{Float64}; max_descriptor_distance::Ptr{Float64}
+    kp_yx::Ptr{Float64}; kp_desc_off::Ptr{Int32}; kp_desc::Ptr{UInt64}; kp_obs_off::Ptr{Int32}; kp_obs_kf::Ptr{Int32}; kp_obs_yx::Ptr{Float64}
+    kf_Tcw::Ptr{Float64}
+    mp_xyz::Ptr{Float64}; mp_desc_off::Ptr{Int32}; mp_desc::Ptr{UInt64}; mp_obs_off::Ptr{Int32}; mp_obs_kf::Ptr{Int32}
+    match::Ptr{Int32}; best_kp::Ptr{Int32}; best_dist::Ptr{Float64}; proj_yx::Ptr{Float64}
+end
+
+function hip_do_local_map_matching(mapper, frame, local_map; max_projection_distance, max_descriptor_distance)
+    mm = mapper.map_manager
+    prev_new_map = Dict{Int64, Int64}()
+    isempty(local_map) && return prev_new_map
+    kf_row = Dict{Int64, Int32}(); kf_tcw = Float64[]
+    row!(kfid) = get!(kf_row, kfid) do
+        kf = SLAM.get_keyframe(mm, kfid)
+        kf === nothing && return Int32(-1)
+        append!(kf_tcw, vec(kf.cw)); Int32(length(kf_tcw) ÷ 16 - 1)
+    end
+    words(d::BitVector) = d.chunks[1:4]              # bit k in word k ÷ 64 at position k % 64, as hip_describe unpacks them
+    # frame keypoints, cell by cell
+    kp_ids = Int64[]; kp_yx = Float64[]; kp_doff = Int32[0]; kp_desc = UInt64[]; kp_ooff = Int32[0]; kp_okf = Int32[]; kp_oyx = Float64[]
+    for r in 1:size(frame.keypoints_grid, 1), c in 1:size(frame.keypoints_grid, 2), id in frame.keypoints_grid[r, c]
+        kp = get(frame.keypoints, id, nothing)
+        kp === nothing && continue
+        push!(kp_ids, id); append!(kp_yx, kp.pixel)
+        mp = kp.id < 0 ? nothing : SLAM.get_mappoint(mm, kp.id)
+        if mp !== nothing && !isempty(mp.descriptor)
+            for d in values(mp.keyframes_descriptors); append!(kp_desc, words(d)); end
+            for kfid in SLAM.get_observers(mp)
+                okf = SLAM.get_keyframe(mm, kfid)
+                okp = okf === nothing ? nothing : SLAM.get_keypoint(okf, kp.id)
+                okp === nothing && continue          # mapper.jl:429-434: left out of the mean; the caller removes the observation
+                push!(kp_okf, row!(kfid)); append!(kp_oyx, okp.pixel)
+            end
+        end
+        push!(kp_doff, Int32(length(kp_desc) ÷ 4)); push!(kp_ooff, Int32(length(kp_okf)))
+    end
+    # the local map, without the entries mapper.jl:338-341 skips
+    mp_ids = Int64[]; mp_xyz = Float64[]; mp_doff = Int32[0]; mp_desc = UInt64[]; mp_ooff = Int32[0]; mp_okf = Int32[]
+    for kpid in local_map
+        SLAM.is_observing_kp(frame, kpid) && continue
+        mp = SLAM.get_mappoint(mm, kpid)
+        (mp === nothing || !mp.is_3d || isempty(mp.descriptor)) && continue
+        push!(mp_ids, kpid); append!(mp_xyz, SLAM.get_position(mp))
+        for d in values(mp.keyframes_descriptors); append!(mp_desc, words(d)); end
+        for kfid in SLAM.get_observers(mp)
+            r = row!(kfid)
+            r ≥ 0 && push!(mp_okf, r)                # a key-frame that is gone observes nothing: it cannot overlap (mapper.jl:420)
+        end
+        push!(mp_doff, Int32(length(mp_desc) ÷ 4)); push!(mp_ooff, Int32(length(mp_okf)))
+    end
+    N, M, K = length(kp_ids), length(mp_ids), length(kf_tcw) ÷ 16
+    (N == 0 || M == 0) && return prev_new_map
+    cam = frame.camera
+    tcw = Vector{Float64}(vec(frame.cw))
+    camv = Float64[cam.fx, cam.fy, cam.cx, cam.cy, cam.k1, cam.k2, cam.p1, cam.p2, cam.height, cam.width]
+    cell = Int32[frame.cell_size]; n3d = Int32[frame.nb_3d_kpts]
+    mpd = Float64[max_projection_distance]; mdd = Float64[max_descriptor_distance]
+    match = Vector{Int32}(undef, N); best_kp = Vector{Int32}(undef, M); best_dist = Vector{Float64}(undef, M); proj = Vector{Float64}(undef, 2M)
+    GC.@preserve tcw camv cell n3d mpd mdd kp_yx kp_doff kp_desc kp_ooff kp_okf kp_oyx kf_tcw mp_xyz mp_doff mp_desc mp_ooff mp_okf match best_kp best_dist proj begin
+        args = Ref(LocalMapArgs(pointer(tcw), pointer(camv), pointer(cell), pointer(n3d), pointer(mpd), pointer(mdd),
+            pointer(kp_yx), pointer(kp_doff), pointer(kp_desc), pointer(kp_ooff), pointer(kp_okf), pointer(kp_oyx), pointer(kf_tcw),
+            pointer(mp_xyz), pointer(mp_doff), pointer(mp_desc), pointer(mp_ooff), pointer(mp_okf),
+            pointer(match), pointer(best_kp), pointer(best_dist), pointer(proj)))
+        check(ccall((:slam_local_map_match, LIB[]), Cint, (Ptr{Cvoid}, Ref{LocalMapArgs}, Cint, Cint, Cint), ctx(), args, N, K, M))
+    end
+    for j in 1:N
+        match[j] ≥ 0 && (prev_new_map[kp_ids[j]] = mp_ids[match[j] + 1];)
+    end
+    prev_new_map
+end
+
 # p3p_ransac of compute_pose! (front_end.jl:164-167): same positional arguments and result shape as
 # RecoverPose.p3p_ransac -- `(n_inliers, (KP, inliers, error))`, or `nothing` when no sample gave a pose.  The
 # sample triples are drawn here (Julia's RNG) and handed to the library 0-based; `iterations` triples are all scored.

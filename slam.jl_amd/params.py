@@ -16,6 +16,8 @@ class Params:
     min_cov_score: int = 25
     do_local_matching: bool = False
     do_local_bundle_adjustment: bool = True
+    max_projection_distance: float = 2.0     # params.jl:75: gate of the local-map match, px
+    max_descriptor_distance: float = 0.35    # params.jl:76: share of the 256 descriptor bits
 
 
 @dataclass

@@ -327,3 +327,130 @@ def five_point_scene(n=400, seed=0, noise_px=0.3, outlier_frac=0.2, iters=128):
     samples = np.stack([rng.permutation(n)[:5] for _ in range(iters)]).astype(np.int32)
     return dict(px1=np.ascontiguousarray(px1), px2=np.ascontiguousarray(px2), pd1=np.ascontiguousarray(pd1), pd2=np.ascontiguousarray(pd2),
                 K=K, Rt_gt=Rt, gross=gross, samples=samples)
+
+
+def _lm_project(cam, Tcw, Xw):
+    """project_world_to_image_distort (frame.jl:478-480) of one world point, (y, x); the k1 / k2 / p1 / p2 model of camera.jl:111-125"""
+    fx, fy, cx, cy, k1, k2, p1, p2 = cam[:8]
+    c = Tcw[:3, :3] @ Xw + Tcw[:3, 3]
+    with np.errstate(all="ignore"):
+        ny, nx = c[1] / c[2], c[0] / c[2]
+    r2 = ny * ny + nx * nx
+    rd = 1.0 + k1 * r2 + k2 * r2 * r2
+    dtx = 2 * p1 * ny * nx + p2 * (r2 + 2 * ny * ny)
+    dty = p1 * (r2 + 2 * nx * nx) + 2 * p2 * ny * nx
+    return np.array([(rd * ny + dty) * fy + cy, (rd * nx + dtx) * fx + cx])
+
+
+def _lm_flip(rng, desc, max_flips=3):
+    """every descriptor of (D, 4) uint64 with 0 .. max_flips random bits flipped"""
+    out = np.array(desc, dtype=np.uint64).reshape(-1, 4).copy()
+    for d in out:
+        for b in rng.choice(256, size=int(rng.integers(0, max_flips + 1)), replace=False):
+            d[b // 64] ^= np.uint64(1) << np.uint64(b % 64)
+    return out
+
+
+def local_map_scene(seed=0, H=120, W=160, cell_size=35, N=150, M=397, K=6, nb_3d=100, distortion=(0.0, 0.0, 0.0, 0.0), crowd=0):
+    """One stream's inputs of the local-map match (slam_jl_amd.local_map_matching; reference: src/mapper.jl:318-462): a key-frame with N
+    triangulated keypoints (the last `crowd` of them inside one 12 x 12-pixel patch), K observer key-frames posed near it and M local-map points.
+    Keypoints: random pixels, depths 3-15 m, 1-5 descriptors and 1-3 observers each (about 5 % with no descriptor, about 5 % with no observer;
+    observer pixels = the keypoint's own 3-D point projected + 0.3 px noise; observers from the lower half of the key-frame rows); one keypoint in
+    25 is a neighbour of the previous one (under a pixel away) with IDENTICAL descriptors.  Local-map points, by share: 35 % the 3-D point of a
+    keypoint moved by up to 1.4 px, descriptors = the keypoint's with 0-3 flipped bits; 15 % a keypoint's pixel at 0.4 x / 2.5 x its depth (the
+    observers' mean reprojection rejects most); 8 % exact duplicates of an earlier point and 7 % an earlier point's descriptors at a fresh
+    offset from the same keypoint (contested keypoints, equal distances); the rest anywhere, behind the camera and outside the image included.
+    Their observers come from the upper half of the key-frame rows; one point in six also lists one of its keypoint's observers (overlap).
+    Returns {"frame", "keypoints", "keyframes", "local_map", "params"} as local_map_matching takes them."""
+    from .params import Params
+    rng = np.random.default_rng(0x10CA1 + seed)
+    f = 0.6 * W
+    cam = np.array([f, f * 1.01, 0.5 * W + 0.3, 0.5 * H - 0.2, *distortion, H, W], dtype=np.float64)
+
+    def pose(ang_scale, t_scale):
+        T = np.eye(4)
+        T[:3, :3] = rotzyx(*(rng.normal(0, ang_scale, 3)))
+        T[:3, 3] = rng.normal(0, t_scale, 3)
+        return T
+    Tcw = pose(0.02, 0.2)
+    Twc = np.linalg.inv(Tcw)
+    keyframes = np.stack([pose(0.03, 0.6) @ Tcw for _ in range(K)]) if K else np.zeros((0, 4, 4))
+    lo = max(K // 2, 1)                                   # keypoints observe rows [0, lo), local-map points rows [lo, K)
+    patch = (rng.uniform(20, H - 32), rng.uniform(20, W - 32))
+
+    def world(pixel, depth):
+        """a world point whose (undistorted-model) projection is near `pixel` at `depth`"""
+        xc = np.array([(pixel[1] - cam[2]) / cam[0] * depth, (pixel[0] - cam[3]) / cam[1] * depth, depth])
+        return Twc[:3, :3] @ xc + Twc[:3, 3]
+
+    def observers(Xw, rows):
+        return [(int(r), tuple(_lm_project(cam, keyframes[r], Xw) + rng.normal(0, 0.3, 2))) for r in rows]
+
+    keypoints, kp_world, kp_depth = [], [], []
+    for j in range(N):
+        for _ in range(100):
+            if keypoints and j % 25 == 24:                # identical descriptors under a pixel away: a tie inside find_best_match
+                target_px = np.array(keypoints[-1]["pixel"]) + rng.uniform(-0.6, 0.6, 2)
+                depth = kp_depth[-1]
+            elif j >= N - crowd:
+                target_px = np.array(patch) + rng.uniform(0, 12, 2)
+                depth = rng.uniform(3, 15)
+            else:
+                target_px = np.array([rng.uniform(4, H - 4), rng.uniform(4, W - 4)])
+                depth = rng.uniform(3, 15)
+            Xw = world(target_px, depth)
+            px = _lm_project(cam, Tcw, Xw)
+            if 1.5 <= px[0] <= H - 0.5 and 1.5 <= px[1] <= W - 0.5:
+                break
+        if keypoints and j % 25 == 24:
+            desc = keypoints[-1]["descriptors"].copy()
+        else:
+            nd = 0 if rng.random() < 0.05 else int(rng.integers(1, 6))
+            base = rng.integers(0, 2 ** 63, size=(1, 4), dtype=np.uint64) * np.uint64(2) + rng.integers(0, 2, size=(1, 4), dtype=np.uint64)
+            desc = _lm_flip(rng, np.repeat(base, nd, axis=0), 6) if nd else np.zeros((0, 4), dtype=np.uint64)
+        no = 0 if (rng.random() < 0.05 or K == 0) else int(rng.integers(1, min(3, lo) + 1))
+        keypoints.append({"pixel": (float(px[0]), float(px[1])), "descriptors": desc,
+                          "observers": observers(Xw, rng.choice(lo, size=no, replace=False))})
+        kp_world.append(Xw); kp_depth.append(depth)
+
+    def mp_observers(j):
+        rows = list(rng.choice(np.arange(lo, K), size=int(rng.integers(1, min(3, K - lo) + 1)), replace=False)) if K > lo else []
+        if j is not None and keypoints[j]["observers"] and rng.random() < 1 / 6:
+            rows.append(keypoints[j]["observers"][0][0])
+        return [int(r) for r in rows]
+
+    def random_desc(n):
+        return rng.integers(0, 2 ** 63, size=(n, 4), dtype=np.uint64) * np.uint64(2) + rng.integers(0, 2, size=(n, 4), dtype=np.uint64)
+
+    def near(j):
+        """keypoint j's 3-D point moved sideways by up to 1.4 px"""
+        d = rng.uniform(0.3, 1.4) * np.array([np.cos(a := rng.uniform(0, 2 * np.pi)), np.sin(a)])
+        return kp_world[j] + Twc[:3, :3] @ np.array([d[1] / cam[0] * kp_depth[j], d[0] / cam[1] * kp_depth[j], 0.0])
+
+    local_map, origin = [], []                            # origin: the keypoint a point was derived from (None: anywhere)
+    for m in range(M):
+        u = rng.random()
+        j = int(rng.integers(0, N)) if N else None
+        if N and u < 0.35:
+            dk = keypoints[j]["descriptors"]
+            mp = {"position": near(j), "descriptors": _lm_flip(rng, dk) if len(dk) else random_desc(2), "observers": mp_observers(j)}
+        elif N and u < 0.50:
+            Xc = Tcw[:3, :3] @ kp_world[j] + Tcw[:3, 3]
+            Xw = Twc[:3, :3] @ (Xc * (0.4 if rng.random() < 0.5 else 2.5)) + Twc[:3, 3]
+            dk = keypoints[j]["descriptors"]
+            mp = {"position": Xw, "descriptors": _lm_flip(rng, dk) if len(dk) else random_desc(1), "observers": mp_observers(j)}
+        elif local_map and u < 0.58:
+            e = int(rng.integers(0, len(local_map)))
+            mp, j = {k: (v.copy() if hasattr(v, "copy") else list(v)) for k, v in local_map[e].items()}, origin[e]
+        elif local_map and u < 0.65:
+            e = int(rng.integers(0, len(local_map)))
+            j = origin[e]
+            mp = {"position": near(j) if j is not None else local_map[e]["position"].copy(), "descriptors": local_map[e]["descriptors"].copy(),
+                  "observers": mp_observers(j)}
+        else:
+            j = None
+            Xc = np.array([rng.uniform(-25, 25), rng.uniform(-20, 20), rng.uniform(-10, 30)])
+            mp = {"position": Twc[:3, :3] @ Xc + Twc[:3, 3], "descriptors": random_desc(int(rng.integers(1, 4))), "observers": mp_observers(None)}
+        local_map.append(mp); origin.append(j)
+    frame = {"Tcw": Tcw, "cam": cam, "cell_size": int(cell_size), "nb_3d_kpts": int(nb_3d)}
+    return {"frame": frame, "keypoints": keypoints, "keyframes": keyframes, "local_map": local_map, "params": Params()}
