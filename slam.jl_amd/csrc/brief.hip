@@ -71,13 +71,14 @@ extern "C" int slam_describe(slam_ctx *ctx, const double *image, int H, int W, c
     Taps t; t.n = window;
     { const int hw = window >> 1; double s = 0; for (int i = 0; i < window; i++) { double x = i - hw; t.w[i] = std::exp(-(x * x) / (2.0 * (sigma * sigma))); s += t.w[i]; } for (int i = 0; i < window; i++) t.w[i] = t.w[i] / s; }
     const size_t N = (size_t)H * W, words = (size_t)n_bits / 64;
-    const size_t img_b = (N * 8 + 255) & ~(size_t)255, rc_b = ((size_t)m * 16 + 255) & ~(size_t)255, pat_b = ((size_t)n_bits * 16 + 255) & ~(size_t)255;
+    Layout D;
+    const size_t o_a = D.take(N * 8), o_b = D.take(N * 8), o_rc = D.take((size_t)m * 16), o_pat = D.take((size_t)n_bits * 16), o_out = D.take((size_t)m * words * 8);
     char *s;
-    int r = slam_scratch(ctx, 2 * img_b + rc_b + pat_b + (size_t)m * words * 8, (void **)&s);
+    int r = slam_scratch(ctx, D.size(), (void **)&s);
     if (r) return r;
-    double *d_a = (double *)s, *d_b = (double *)(s + img_b);
-    int64_t *d_rc = (int64_t *)(s + 2 * img_b); int32_t *d_pat = (int32_t *)(s + 2 * img_b + rc_b);
-    uint64_t *d_out = (uint64_t *)(s + 2 * img_b + rc_b + pat_b);
+    double *d_a = (double *)(s + o_a), *d_b = (double *)(s + o_b);
+    int64_t *d_rc = (int64_t *)(s + o_rc); int32_t *d_pat = (int32_t *)(s + o_pat);
+    uint64_t *d_out = (uint64_t *)(s + o_out);
     HIP_TRY(ctx, hipMemcpyAsync(d_a, image, N * 8, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(d_rc, keep.data(), (size_t)m * 16, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(d_pat, pattern, (size_t)n_bits * 16, hipMemcpyHostToDevice, ctx->stream));

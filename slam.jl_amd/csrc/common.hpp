@@ -126,7 +126,14 @@ int slam_scratch(slam_ctx *ctx, size_t bytes, void **out);
 int slam_scratch2(slam_ctx *ctx, size_t bytes, void **out);
 int slam_pinned(slam_ctx *ctx, size_t bytes, void **out);
 
-#define HIP_TRY(ctx, expr)                                                                  \
+// regions of one scratch / pinned block, each starting on a 256-byte boundary: take(bytes) returns the region's offset, size() the total
+struct Layout {
+    size_t end = 0;
+    size_t take(size_t bytes) { const size_t at = end; end += (bytes + 255) & ~(size_t)255; return at; }
+    size_t size() const { return end; }
+};
+
+#define HIP_TRY(ctx, expr)                                                                 \
     do {                                                                                    \
         hipError_t _e = (expr);                                                             \
         if (_e != hipSuccess)                                                               \

@@ -10,6 +10,7 @@
 // indices are bit-exact with the CPU oracle: every sum runs in the reference's
 // order and the build uses -ffp-contract=off.
 #include "common.hpp"
+#include "geom_device.hpp"
 #include <cmath>
 #include <cstddef>
 
@@ -476,8 +477,7 @@ __global__ __launch_bounds__(DET_THREADS) void detect_cells(DetectArgs A)
 #endif
 }
 
-// Ordered compaction of the per-cell lists (cells row-major: extractor.jl:81):
-// wave-level inclusive scans (shuffle) + one LDS hop across the 16 waves.
+// Ordered compaction of the per-cell lists (cells row-major: extractor.jl:81), cell_scan over chunks of 1024 cells.
 __global__ __launch_bounds__(1024) void detect_compact(const int64_t *cell_out, const int *cell_cnt, int n_cells, int k,
                                                         int64_t *out /* [0] = n_out, then pairs */, int cap,
                                                         const int *k_s /* batched: grid.x = stream, per-stream k, lists strided by kmax = k */)
@@ -489,31 +489,45 @@ __global__ __launch_bounds__(1024) void detect_compact(const int64_t *cell_out, 
     }
     __shared__ int s_w[16];
     __shared__ int s_base;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int tid = threadIdx.x;
     if (tid == 0) s_base = 0;
     __syncthreads();
     for (int c0 = 0; c0 < n_cells; c0 += 1024) {
-        int c = c0 + tid;
-        int cnt = c < n_cells ? cell_cnt[c] : 0;
-        int incl = cnt;
-        for (int off = 1; off < 64; off <<= 1) { int t = __shfl_up(incl, off); if (lane >= off) incl += t; }
-        if (lane == 63) s_w[wv] = incl;
-        __syncthreads();
-        int wbase = 0;
-        for (int i = 0; i < wv; i++) wbase += s_w[i];
-        int total = 0;
-        for (int i = 0; i < 16; i++) total += s_w[i];
-        int start = s_base + wbase + incl - cnt;
+        const int c = c0 + tid, cnt = c < n_cells ? cell_cnt[c] : 0;
+        const int start = cell_scan(cnt, s_w, &s_base);
         for (int i = 0; i < cnt; i++)
             if (start + i < cap) {
                 out[1 + 2 * (start + i)] = cell_out[((size_t)c * k + i) * 2];
                 out[2 + 2 * (start + i)] = cell_out[((size_t)c * k + i) * 2 + 1];
             }
-        __syncthreads();
-        if (tid == 0) s_base += total;
-        __syncthreads();
     }
     if (tid == 0) out[0] = s_base;
+}
+
+// What the three detection entry points share: every field of A but the avoidance list and the cell lists (single image: A.k / A.n_cur
+// are the caller's), the Gaussian taps, and the checks of the LDS carve-up for `kmax`, the largest per-cell quota of the launch.
+static int det_plan(slam_ctx *ctx, DetectArgs &A, const double *img, int H, int W, int pitch, size_t zs, int max_points, int radius,
+                    int grid_rows, int grid_cols, int cell_size, int kmax, double sigma_mask, double min_response, size_t *lds_bytes)
+{
+    A.img = img; A.H = H; A.W = W; A.pitch = pitch; A.zs = zs; A.radius = radius; det_disk_table(A);
+    A.grid_rows = grid_rows; A.grid_cols = grid_cols; A.cs = cell_size; A.k = 0; A.kmax = kmax; A.n_cur = 0; A.min_response = min_response;
+    A.cur = nullptr; A.cur_off = nullptr; A.k_s = nullptr; A.cur_cnt = nullptr; A.cur_stride = 0; A.max_points = max_points;
+    A.ntaps = 0;
+    if (sigma_mask != 0) {
+        ARG_TRY(ctx, 4 * (int)std::ceil(sigma_mask) + 1 <= DET_MAXTAPS);
+        A.ntaps = slam_gaussian_taps(sigma_mask, A.taps);
+    }
+    const int hw = A.ntaps >> 1;
+    const size_t n = (size_t)cell_size * cell_size;
+    // LDS carve-up (4 planes of cell_size^2 doubles): byte mask at the tail of the 4th plane, blur intermediate in planes 2..4 below it
+    const size_t mbytes = ((size_t)(cell_size + 2 * hw) * (cell_size + 2 * hw) + 7) & ~(size_t)7;
+    ARG_TRY(ctx, mbytes <= n * 8 && (size_t)cell_size * (cell_size + 2 * hw) * 8 + mbytes <= 3 * n * 8);
+    ARG_TRY(ctx, (size_t)kmax * sizeof(int) <= n * 8);
+    *lds_bytes = 4 * n * sizeof(double);
+    ARG_TRY(ctx, *lds_bytes <= 150 * 1024);
+    // > 64 KB of dynamic LDS needs the opt-in; per device, so set it on every call (cheap host-side call)
+    HIP_TRY(ctx, hipFuncSetAttribute((const void *)detect_cells, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+    return SLAM_OK;
 }
 
 int slam_detect_device(slam_ctx *ctx, const double *img_dev, int H, int W, int pitch, const double *cur_yx, int n_cur,
@@ -528,40 +542,20 @@ int slam_detect_device(slam_ctx *ctx, const double *img_dev, int H, int W, int p
     const int n_detect = max_points - n_cur;
     const int k = (n_detect + n_cells - 1) / n_cells;             // ceil(Int, n_detect / n_cells)
     DetectArgs A;
-    A.img = img_dev; A.H = H; A.W = W; A.pitch = pitch; A.n_cur = n_cur; A.radius = radius; det_disk_table(A);
-    A.grid_rows = grid_rows; A.grid_cols = grid_cols; A.cs = cell_size; A.k = k; A.min_response = min_response;
-    A.ntaps = 0; A.cur_off = nullptr; A.k_s = nullptr; A.zs = 0; A.kmax = k; A.cur_cnt = nullptr; A.cur_stride = 0; A.max_points = max_points;
-    if (n_cur > 0 && sigma_mask != 0) {
-        int l = 4 * (int)std::ceil(sigma_mask) + 1;
-        ARG_TRY(ctx, l <= DET_MAXTAPS);
-        A.ntaps = slam_gaussian_taps(sigma_mask, A.taps);
-    }
-    const int hw = A.ntaps >> 1;
-    const size_t n = (size_t)cell_size * cell_size;
-    // LDS carve-up checks (4 planes of cell_size^2 doubles)
-    {   // byte mask at the tail of the 4th plane, blur intermediate in planes 2..4 below it
-        const size_t mbytes = ((size_t)(cell_size + 2 * hw) * (cell_size + 2 * hw) + 7) & ~(size_t)7;
-        ARG_TRY(ctx, mbytes <= n * 8 && (size_t)cell_size * (cell_size + 2 * hw) * 8 + mbytes <= 3 * n * 8);
-    }
-    ARG_TRY(ctx, (size_t)k * sizeof(int) <= n * 8);
-    const size_t lds_bytes = 4 * n * sizeof(double);
-    ARG_TRY(ctx, lds_bytes <= 150 * 1024);
-
-    // scratch: [cur (2*n_cur doubles)] [cell_cnt (n_cells int, padded)] [cell_out] [out header+pairs]
-    const size_t cur_b = ((size_t)n_cur * 16 + 255) & ~(size_t)255;
-    const size_t cnt_b = ((size_t)n_cells * 4 + 255) & ~(size_t)255;
-    const size_t cout_b = ((size_t)n_cells * k * 16 + 255) & ~(size_t)255;
-    const size_t out_pairs = (size_t)n_cells * k;
-    const size_t out_b = 8 + out_pairs * 16;
-    char *s;
-    int rc = slam_scratch(ctx, cur_b + cnt_b + cout_b + out_b, (void **)&s);
+    size_t lds_bytes;
+    int rc = det_plan(ctx, A, img_dev, H, W, pitch, 0, max_points, radius, grid_rows, grid_cols, cell_size, k, n_cur > 0 ? sigma_mask : 0.0, min_response, &lds_bytes);
     if (rc) return rc;
-    double *d_cur = (double *)s; int *d_cnt = (int *)(s + cur_b);
-    int64_t *d_cout = (int64_t *)(s + cur_b + cnt_b); int64_t *d_out = (int64_t *)(s + cur_b + cnt_b + cout_b);
+    A.k = k; A.n_cur = n_cur;
+    const size_t out_pairs = (size_t)n_cells * k, out_b = 8 + out_pairs * 16;
+    Layout D;
+    const size_t o_cur = D.take((size_t)n_cur * 16), o_cnt = D.take((size_t)n_cells * 4), o_cout = D.take((size_t)n_cells * k * 16), o_out = D.take(out_b);
+    char *s;
+    rc = slam_scratch(ctx, D.size(), (void **)&s);
+    if (rc) return rc;
+    double *d_cur = (double *)(s + o_cur); int *d_cnt = (int *)(s + o_cnt);
+    int64_t *d_cout = (int64_t *)(s + o_cout); int64_t *d_out = (int64_t *)(s + o_out);
     if (n_cur > 0) HIP_TRY(ctx, hipMemcpyAsync(d_cur, cur_yx, (size_t)n_cur * 16, hipMemcpyHostToDevice, ctx->stream));
     A.cur = d_cur; A.cell_out = d_cout; A.cell_cnt = d_cnt;
-    // > 64 KB of dynamic LDS needs the opt-in; per device, so set it on every call (cheap host-side call)
-    HIP_TRY(ctx, hipFuncSetAttribute((const void *)detect_cells, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
     { ProfScope span(ctx, "detect");
       hipLaunchKernelGGL(detect_cells, dim3(n_cells), dim3(DET_THREADS), lds_bytes, ctx->stream, A);
       hipLaunchKernelGGL(detect_compact, dim3(1), dim3(1024), 0, ctx->stream, d_cout, d_cnt, n_cells, k, d_out, (int)out_pairs, (const int *)nullptr); }
@@ -626,46 +620,33 @@ extern "C" int slam_detect_batch(slam_ctx *ctx, const slam_pyr *pyr0, int S, con
     for (int s = 0; s <= S; s++) out_off[s] = 0;
     if (kmax == 0) return SLAM_OK;
     DetectArgs A;
-    A.img = pyr0->plane(0, 0); A.H = pyr0->H[0]; A.W = pyr0->W[0]; A.pitch = pyr0->P[0]; A.zs = pyr0->zstride;
-    A.n_cur = 0; A.radius = radius; det_disk_table(A); A.grid_rows = grid_rows; A.grid_cols = grid_cols; A.cs = cell_size; A.k = 0; A.kmax = kmax;
-    A.min_response = min_response; A.ntaps = 0; A.cur_cnt = nullptr; A.cur_stride = 0; A.max_points = max_points;
-    if (sigma_mask != 0) {
-        ARG_TRY(ctx, 4 * (int)std::ceil(sigma_mask) + 1 <= DET_MAXTAPS);
-        A.ntaps = slam_gaussian_taps(sigma_mask, A.taps);
-    }
-    const int hw = A.ntaps >> 1;
-    const size_t n = (size_t)cell_size * cell_size;
-    {   // byte mask at the tail of the 4th plane, blur intermediate in planes 2..4 below it
-        const size_t mbytes = ((size_t)(cell_size + 2 * hw) * (cell_size + 2 * hw) + 7) & ~(size_t)7;
-        ARG_TRY(ctx, mbytes <= n * 8 && (size_t)cell_size * (cell_size + 2 * hw) * 8 + mbytes <= 3 * n * 8);
-    }
-    ARG_TRY(ctx, (size_t)kmax * sizeof(int) <= n * 8);
-    const size_t lds_bytes = 4 * n * sizeof(double);
-    ARG_TRY(ctx, lds_bytes <= 150 * 1024);
-
-    // host -> device in one copy: [cur_off (S+1 ints) at 0] [k_s (S ints) at 1024] [cur (2 * n_tot doubles) at 2048]
-    const size_t hdr_b = 2048, cur_b = ((size_t)n_tot * 16 + 255) & ~(size_t)255;
-    const size_t cnt_b = ((size_t)S * n_cells * 4 + 255) & ~(size_t)255;
-    const size_t cout_b = ((size_t)S * n_cells * kmax * 16 + 255) & ~(size_t)255;
+    size_t lds_bytes;
+    int rc = det_plan(ctx, A, pyr0->plane(0, 0), pyr0->H[0], pyr0->W[0], pyr0->P[0], pyr0->zstride, max_points, radius, grid_rows, grid_cols, cell_size, kmax,
+                      sigma_mask, min_response, &lds_bytes);
+    if (rc) return rc;
+    // host -> device in one copy: [cur_off (S+1 ints) at 0] [k_s (S ints) at 1024] [cur (2 * n_tot doubles) at 2048]; the pinned block holds
+    // these inputs and the output behind them
     const size_t pairs = (size_t)n_cells * kmax, out_b = (size_t)S * (8 + pairs * 16);
+    Layout D;
+    const size_t o_hdr = D.take(2048), o_cur = D.take((size_t)n_tot * 16), in_b = D.size();
+    const size_t o_cnt = D.take((size_t)S * n_cells * 4), o_cout = D.take((size_t)S * n_cells * kmax * 16), o_out = D.take(out_b);
     char *d, *h;
-    int rc = slam_scratch(ctx, hdr_b + cur_b + cnt_b + cout_b + out_b, (void **)&d);
+    rc = slam_scratch(ctx, D.size(), (void **)&d);
     if (rc) return rc;
-    rc = slam_pinned(ctx, hdr_b + cur_b + out_b, (void **)&h);
+    rc = slam_pinned(ctx, in_b + out_b, (void **)&h);
     if (rc) return rc;
-    memcpy(h, cur_off, (size_t)(S + 1) * 4); memcpy(h + 1024, ks, (size_t)S * 4);
-    if (n_tot > 0) memcpy(h + hdr_b, cur_yx, (size_t)n_tot * 16);
-    HIP_TRY(ctx, hipMemcpyAsync(d, h, hdr_b + (size_t)n_tot * 16, hipMemcpyHostToDevice, ctx->stream));
-    A.cur_off = (const int *)d; A.k_s = (const int *)(d + 1024); A.cur = (const double *)(d + hdr_b);
-    A.cell_cnt = (int *)(d + hdr_b + cur_b); A.cell_out = (int64_t *)(d + hdr_b + cur_b + cnt_b);
-    int64_t *d_out = (int64_t *)(d + hdr_b + cur_b + cnt_b + cout_b);
-    HIP_TRY(ctx, hipFuncSetAttribute((const void *)detect_cells, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+    memcpy(h + o_hdr, cur_off, (size_t)(S + 1) * 4); memcpy(h + o_hdr + 1024, ks, (size_t)S * 4);
+    if (n_tot > 0) memcpy(h + o_cur, cur_yx, (size_t)n_tot * 16);
+    HIP_TRY(ctx, hipMemcpyAsync(d, h, o_cur + (size_t)n_tot * 16, hipMemcpyHostToDevice, ctx->stream));
+    A.cur_off = (const int *)(d + o_hdr); A.k_s = (const int *)(d + o_hdr + 1024); A.cur = (const double *)(d + o_cur);
+    A.cell_cnt = (int *)(d + o_cnt); A.cell_out = (int64_t *)(d + o_cout);
+    int64_t *d_out = (int64_t *)(d + o_out);
     { ProfScope span(ctx, "detect");
       hipLaunchKernelGGL(detect_cells, dim3(n_cells, S), dim3(DET_THREADS), lds_bytes, ctx->stream, A);
       hipLaunchKernelGGL(detect_compact, dim3(S), dim3(1024), 0, ctx->stream, (const int64_t *)A.cell_out, (const int *)A.cell_cnt, n_cells, kmax,
                          d_out, (int)pairs, A.k_s); }
     HIP_TRY(ctx, hipGetLastError());
-    int64_t *h_out = (int64_t *)(h + hdr_b + cur_b);
+    int64_t *h_out = (int64_t *)(h + in_b);
     HIP_TRY(ctx, hipMemcpyAsync(h_out, d_out, out_b, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, slam_stream_wait(ctx->stream));
     size_t tot = 0;
@@ -684,7 +665,7 @@ extern "C" int slam_detect_batch(slam_ctx *ctx, const slam_pyr *pyr0, int S, con
 // detect() into a device-resident keypoint set: the avoidance list of stream z is its current list in the set, the new
 // keypoints (cells row-major, column-major inside a cell: extractor.jl:81-91) are appended behind it as (row, col) Float64
 // pixels with is_3d = 0 and fresh ids -- extract_keypoints! + add_keypoints_to_frame! (map_manager.jl:98-113) on arrays.
-// One 1024-thread workgroup per stream: wave-level inclusive scans + one LDS hop (as detect_compact).
+// One 1024-thread workgroup per stream, cell_scan over chunks of 1024 cells (as detect_compact).
 __global__ __launch_bounds__(1024) void detect_append(const int64_t *cell_out, const int *cell_cnt, int n_cells, int kmax, int max_points,
                                                        double *yx, double *syx, double *xyz, int64_t *id, uint8_t *is3d, uint8_t *stereo, uint8_t *haskf,
                                                        int *count, int64_t *next_id, int cap)
@@ -696,23 +677,14 @@ __global__ __launch_bounds__(1024) void detect_append(const int64_t *cell_out, c
     const int64_t id0 = next_id[z];
     __shared__ int s_w[16];
     __shared__ int s_base;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int tid = threadIdx.x;
     if (tid == 0) s_base = 0;
     __syncthreads();
     if (n0 >= max_points) return;                                 // extractor.jl:64: nothing detected (cell counts are zero as well)
     const int kz = (max_points - n0 + n_cells - 1) / n_cells;      // this stream's per-cell quota = the stride of its cell lists (detect_cells)
     for (int c0 = 0; c0 < n_cells; c0 += 1024) {
-        const int c = c0 + tid;
-        const int cnt = c < n_cells ? cell_cnt[c] : 0;
-        int incl = cnt;
-        for (int off = 1; off < 64; off <<= 1) { const int t = __shfl_up(incl, off); if (lane >= off) incl += t; }
-        if (lane == 63) s_w[wv] = incl;
-        __syncthreads();
-        int wbase = 0;
-        for (int i = 0; i < wv; i++) wbase += s_w[i];
-        int total = 0;
-        for (int i = 0; i < 16; i++) total += s_w[i];
-        const int start = s_base + wbase + incl - cnt;
+        const int c = c0 + tid, cnt = c < n_cells ? cell_cnt[c] : 0;
+        const int start = cell_scan(cnt, s_w, &s_base);
         for (int i = 0; i < cnt; i++) {
             const int j = n0 + start + i;
             if (j < cap) {
@@ -722,9 +694,6 @@ __global__ __launch_bounds__(1024) void detect_append(const int64_t *cell_out, c
                 id[q] = id0 + start + i; is3d[q] = 0; stereo[q] = 0; haskf[q] = 0;
             }
         }
-        __syncthreads();
-        if (tid == 0) s_base += total;
-        __syncthreads();
     }
     if (tid == 0) { const int n1 = n0 + s_base; count[z] = n1 < cap ? n1 : cap; next_id[z] = id0 + s_base; }
 }
@@ -741,30 +710,17 @@ extern "C" int slam_kpset_detect(slam_ctx *ctx, slam_kpset *ks, const slam_pyr *
     const int kmax = (max_points + n_cells - 1) / n_cells;         // n_cur = 0
     ARG_TRY(ctx, ks->cap >= max_points + n_cells);                  // a stream below max_points may receive up to n_cells * k > max_points - n_cur keypoints
     DetectArgs A;
-    A.img = pyr0->plane(0, 0); A.H = pyr0->H[0]; A.W = pyr0->W[0]; A.pitch = pyr0->P[0]; A.zs = pyr0->zstride;
-    A.n_cur = 0; A.radius = radius; det_disk_table(A); A.grid_rows = grid_rows; A.grid_cols = grid_cols; A.cs = cell_size; A.k = 0; A.kmax = kmax;
-    A.min_response = min_response; A.ntaps = 0; A.cur_off = nullptr; A.k_s = nullptr;
-    A.cur = ks->yx; A.cur_cnt = ks->count; A.cur_stride = ks->cap; A.max_points = max_points;
-    if (sigma_mask != 0) {
-        ARG_TRY(ctx, 4 * (int)std::ceil(sigma_mask) + 1 <= DET_MAXTAPS);
-        A.ntaps = slam_gaussian_taps(sigma_mask, A.taps);
-    }
-    const int hw = A.ntaps >> 1;
-    const size_t n = (size_t)cell_size * cell_size;
-    {
-        const size_t mbytes = ((size_t)(cell_size + 2 * hw) * (cell_size + 2 * hw) + 7) & ~(size_t)7;
-        ARG_TRY(ctx, mbytes <= n * 8 && (size_t)cell_size * (cell_size + 2 * hw) * 8 + mbytes <= 3 * n * 8);
-    }
-    ARG_TRY(ctx, (size_t)kmax * sizeof(int) <= n * 8);
-    const size_t lds_bytes = 4 * n * sizeof(double);
-    ARG_TRY(ctx, lds_bytes <= 150 * 1024);
-    const size_t cnt_b = ((size_t)S * n_cells * 4 + 255) & ~(size_t)255;
-    const size_t cout_b = ((size_t)S * n_cells * kmax * 16 + 255) & ~(size_t)255;
-    char *d;
-    int rc = slam_scratch(ctx, cnt_b + cout_b, (void **)&d);
+    size_t lds_bytes;
+    int rc = det_plan(ctx, A, pyr0->plane(0, 0), pyr0->H[0], pyr0->W[0], pyr0->P[0], pyr0->zstride, max_points, radius, grid_rows, grid_cols, cell_size, kmax,
+                      sigma_mask, min_response, &lds_bytes);
     if (rc) return rc;
-    A.cell_cnt = (int *)d; A.cell_out = (int64_t *)(d + cnt_b);
-    HIP_TRY(ctx, hipFuncSetAttribute((const void *)detect_cells, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+    A.cur = ks->yx; A.cur_cnt = ks->count; A.cur_stride = ks->cap;
+    Layout D;
+    const size_t o_cnt = D.take((size_t)S * n_cells * 4), o_cout = D.take((size_t)S * n_cells * kmax * 16);
+    char *d;
+    rc = slam_scratch(ctx, D.size(), (void **)&d);
+    if (rc) return rc;
+    A.cell_cnt = (int *)(d + o_cnt); A.cell_out = (int64_t *)(d + o_cout);
     { ProfScope span(ctx, "detect");
       hipLaunchKernelGGL(detect_cells, dim3(n_cells, S), dim3(DET_THREADS), lds_bytes, ctx->stream, A);
       hipLaunchKernelGGL(detect_append, dim3(S), dim3(1024), 0, ctx->stream, (const int64_t *)A.cell_out, (const int *)A.cell_cnt, n_cells, kmax, max_points,

@@ -17,7 +17,7 @@
 // The solver is a latency chain (0.2 ms for any tuple count that fits the GPU); scoring is ~iters x 6 x n triangulations
 // of ~0.4 kflop each.
 #include "common.hpp"
-#include "tri_device.hpp"
+#include "geom_device.hpp"
 #include <cmath>
 
 #define FP_TEAM 16                      // lanes per 5-tuple in the solver (one bracketing interval each in the root search)
@@ -519,7 +519,7 @@ __global__ __launch_bounds__(FP_TPB * FP_TEAM) __attribute__((amdgpu_waves_per_e
     extern __shared__ double s_fp[];
     const int team = threadIdx.x / FP_TEAM, l = threadIdx.x % FP_TEAM, z = blockIdx.y;
     const int it = blockIdx.x * FP_TPB + team;
-    const int base = T.cnt ? z * T.stride : T.off[z], n = T.cnt ? T.cnt[z] : T.off[z + 1] - base;
+    const int base = T.cnt ? z * T.stride : T.off[z], n = T.cnt ? T.cnt[z] : T.off[z + 1] - base;   // problem_range spelled out: through the helper the compiler orders this kernel's scalar multiplies differently
     const double *pd1 = T.pd1 + 2 * (size_t)base, *pd2 = T.pd2 + 2 * (size_t)base;
     const Col L{(fp_lds *)s_fp + team};
     bool ok = it < T.iters;
@@ -590,7 +590,8 @@ __global__ __launch_bounds__(FP_SCORE_T) void k_5pt_score(FPArgs T)
     int *bestp = T.counts + (size_t)gridDim.y * T.iters * FP_MAXE + z;
     if (tid < FP_MAXE && tid >= ne) T.counts[slot * FP_MAXE + tid] = 0;
     if (ne <= 0) return;
-    const int base = T.cnt ? z * T.stride : T.off[z], n = T.cnt ? T.cnt[z] : T.off[z + 1] - base;
+    const ProblemRange pr = problem_range(T.off, T.cnt, T.stride, z);
+    const int base = pr.base, n = pr.n;
     const double *px1 = T.px1 + 2 * (size_t)base, *px2 = T.px2 + 2 * (size_t)base;
     double k1[4], k2[4];
     for (int j = 0; j < 4; j++) { k1[j] = T.ks[8 * z + j]; k2[j] = T.ks[8 * z + 4 + j]; }
@@ -620,84 +621,81 @@ __global__ __launch_bounds__(FP_SCORE_T) void k_5pt_score(FPArgs T)
     }
 }
 
-__global__ __launch_bounds__(FP_SEL_T) void k_5pt_select(FPArgs T)
-{
-    __shared__ int s_cnt[FP_SEL_T], s_idx[FP_SEL_T];
-    __shared__ double s_P[12], s_k[8];
-    __shared__ double s_err[FP_ERR_LDS];
-    const int tid = threadIdx.x, z = blockIdx.x, ne = FP_MAXE * T.iters;
-    const int base = T.cnt ? z * T.stride : T.off[z], n = T.cnt ? T.cnt[z] : T.off[z + 1] - base;
-    const double *px1 = T.px1 + 2 * (size_t)base, *px2 = T.px2 + 2 * (size_t)base;
-    const int *counts = T.counts + (size_t)z * ne;
-    const double *poses = T.poses + (size_t)z * ne * 12, *Es = T.Es + (size_t)z * ne * 9;
-    double *errs = T.errs + base, *out = T.out + 32 * (size_t)z;
-    uint8_t *inliers = T.inliers + base;
-    const bool in_lds = n <= FP_ERR_LDS;
-    if (tid < 8) s_k[tid] = T.ks[8 * z + tid];
-    int bc = 0, bi = -1;
-    for (int e = tid; e < ne; e += FP_SEL_T) {
-        const int c = counts[e];
-        if (c > bc) { bc = c; bi = e; }
-    }
-    s_cnt[tid] = bc; s_idx[tid] = bi;
-    __syncthreads();
-    for (int o = FP_SEL_T / 2; o > 0; o >>= 1) {
-        if (tid < o) {
-            const int c2 = s_cnt[tid + o], i2 = s_idx[tid + o];
-            if (c2 > s_cnt[tid] || (c2 == s_cnt[tid] && c2 > 0 && i2 < s_idx[tid])) { s_cnt[tid] = c2; s_idx[tid] = i2; }
-        }
-        __syncthreads();
-    }
-    const int best = s_cnt[0], be = s_idx[0];
-    if (tid < 12) s_P[tid] = best > 0 ? poses[(size_t)be * 12 + tid] : 0.0;
-    __syncthreads();
-    for (int i = tid; i < n; i += FP_SEL_T) {
+// k_5pt_select = ransac_select with this policy: FP_MAXE candidates per tuple, the two reprojection errors of the winning pose
+struct FPSelect {
+    static constexpr int THREADS = FP_SEL_T, PER_ITER = FP_MAXE, ERR_LDS = FP_ERR_LDS;
+    const double *ks, *poses, *Es, *px1, *px2; double thr; double *out, *s_P, *s_k;
+    __device__ void stage(int tid) const { if (tid < 8) s_k[tid] = ks[tid]; }
+    __device__ void winner(int tid, int best, int be) const { if (tid < 12) s_P[tid] = best > 0 ? poses[(size_t)be * 12 + tid] : 0.0; }
+    __device__ bool score(int i, double &e) const
+    {
+        const double a[2] = {px1[2 * i], px1[2 * i + 1]}, b[2] = {px2[2 * i], px2[2 * i + 1]};
         double e1 = 0.0, e2 = 0.0;
-        bool in = false;
-        if (best > 0) {
-            const double a[2] = {px1[2 * i], px1[2 * i + 1]}, b[2] = {px2[2 * i], px2[2 * i + 1]};
-            in = two_view_errors(s_k, s_k + 4, s_P, a, b, &e1, &e2) && e1 < T.thr && e2 < T.thr;
-        }
-        inliers[i] = in ? 1 : 0;
-        if (in_lds) s_err[i] = in ? e1 + e2 : 0.0; else errs[i] = in ? e1 + e2 : 0.0;   // + 0.0 leaves the sum unchanged
+        const bool in = two_view_errors(s_k, s_k + 4, s_P, a, b, &e1, &e2) && e1 < thr && e2 < thr;
+        e = e1 + e2;
+        return in;
     }
-    __threadfence_block();
-    __syncthreads();
-    if (tid == 0) {
-        double esum = 0.0;
-        if (in_lds) {
-#pragma unroll 16
-            for (int i = 0; i < n; i++) esum += s_err[i];             // index order; the reads pipeline, the adds are the chain
-        } else {
-#pragma unroll 16
-            for (int i = 0; i < n; i++) esum += errs[i];
-        }
+    __device__ void write(int best, int be, double esum) const
+    {
         out[21] = esum;
         int *oi = (int *)(out + 22);
-        oi[0] = best; oi[1] = best > 0 ? be / FP_MAXE : -1;
+        oi[0] = best; oi[1] = best > 0 ? be / PER_ITER : -1;
         for (int j = 0; j < 12; j++) out[j] = s_P[j];
         for (int r = 0; r < 3; r++)
             for (int c = 0; c < 3; c++) out[12 + r + 3 * c] = best > 0 ? Es[(size_t)be * 9 + 3 * r + c] : 0.0;
     }
+};
+__global__ __launch_bounds__(FP_SEL_T) void k_5pt_select(FPArgs T)
+{
+    __shared__ double s_P[12], s_k[8];
+    const int z = blockIdx.x, ne = FP_MAXE * T.iters;
+    const ProblemRange pr = problem_range(T.off, T.cnt, T.stride, z);
+    const FPSelect pol{T.ks + 8 * z, T.poses + (size_t)z * ne * 12, T.Es + (size_t)z * ne * 9, T.px1 + 2 * (size_t)pr.base, T.px2 + 2 * (size_t)pr.base,
+                       T.thr, T.out + 32 * (size_t)z, s_P, s_k};
+    ransac_select(pol, T.counts + (size_t)z * ne, ne, pr.n, T.errs + pr.base, T.inliers + pr.base);
 }
 
-// S problems in three launches (grid.y / grid.z / grid.x = problem)
+// the device scratch of FPArgs (ne | Es | poses | counts + the S incumbent counts | errs) as regions of the caller's layout; k_5pt_score
+// finds the incumbents at counts + S * iters * FP_MAXE, fp_enqueue clears them there
+struct FPScratch {
+    size_t ne, Es, poses, counts, errs;
+    FPScratch(Layout &L, int S, int iters, size_t npts)
+        : ne(L.take((size_t)S * iters * 4)), Es(L.take((size_t)S * iters * FP_MAXE * 72)), poses(L.take((size_t)S * iters * FP_MAXE * 96)),
+          counts(L.take((size_t)S * iters * FP_MAXE * 4 + (size_t)S * 4)), errs(L.take(npts * 8)) {}
+    void bind(FPArgs &T, char *scr) const
+    {
+        T.ne = (int *)(scr + ne); T.Es = (double *)(scr + Es); T.poses = (double *)(scr + poses); T.counts = (int *)(scr + counts); T.errs = (double *)(scr + errs);
+    }
+};
+// the only launch site of the three kernels (grid.y / grid.y / grid.x = problem)
+static int fp_enqueue(slam_ctx *ctx, int S, const FPArgs &T)
+{
+    const size_t lds = (size_t)FP_LDS_PER_THREAD * FP_TPB * sizeof(double);
+    HIP_TRY(ctx, hipFuncSetAttribute((const void *)k_5pt_solve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(k_5pt_solve, dim3((T.iters + FP_TPB - 1) / FP_TPB, S), dim3(FP_TPB * FP_TEAM), lds, ctx->stream, T);
+    (void)hipMemsetAsync(T.counts + (size_t)S * T.iters * FP_MAXE, 0, (size_t)S * 4, ctx->stream);      // the incumbent counts
+    hipLaunchKernelGGL(k_5pt_score, dim3(T.iters, S), dim3(FP_SCORE_T), 0, ctx->stream, T);
+    hipLaunchKernelGGL(k_5pt_select, dim3(S), dim3(FP_SEL_T), 0, ctx->stream, T);
+    return SLAM_OK;
+}
+
+// S problems in one round trip through the context's mapped pinned block
 static int fp_run(slam_ctx *ctx, int S, const int32_t *off, const double *px1_xy, const double *px2_xy, const double *pd1_xy,
                   const double *pd2_xy, const double *K1, const double *K2, double max_repr_error, const int32_t *samples, int iters,
                   double *E, double *P, uint8_t *inliers, int *n_inliers, double *error, int *best_iter)
 {
     const int ntot = off[S];
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t pb = up((size_t)ntot * 16);
-    const size_t o_off = 4 * pb, o_k = o_off + up((size_t)(S + 1) * 4), o_smp = o_k + up((size_t)S * 64);
-    const size_t o_out = o_smp + up((size_t)S * iters * 20), o_inl = o_out + (size_t)S * 256, total = o_inl + up((size_t)ntot);
+    Layout H;
+    const size_t o_px1 = H.take((size_t)ntot * 16), o_px2 = H.take((size_t)ntot * 16), o_pd1 = H.take((size_t)ntot * 16), o_pd2 = H.take((size_t)ntot * 16);
+    const size_t o_off = H.take((size_t)(S + 1) * 4), o_k = H.take((size_t)S * 64), o_smp = H.take((size_t)S * iters * 20);
+    const size_t o_out = H.take((size_t)S * 256), o_inl = H.take((size_t)ntot);
     char *h, *d;
-    int rc = slam_pinned(ctx, total, (void **)&h);
+    int rc = slam_pinned(ctx, H.size(), (void **)&h);
     if (rc) return rc;
     HIP_TRY(ctx, hipHostGetDevicePointer((void **)&d, h, 0));
-    memcpy(h, px1_xy, (size_t)ntot * 16); memcpy(h + pb, px2_xy, (size_t)ntot * 16);
-    memcpy(h + 2 * pb, pd1_xy, (size_t)ntot * 16); memcpy(h + 3 * pb, pd2_xy, (size_t)ntot * 16);
+    memcpy(h + o_px1, px1_xy, (size_t)ntot * 16); memcpy(h + o_px2, px2_xy, (size_t)ntot * 16);
+    memcpy(h + o_pd1, pd1_xy, (size_t)ntot * 16); memcpy(h + o_pd2, pd2_xy, (size_t)ntot * 16);
     memcpy(h + o_off, off, (size_t)(S + 1) * 4);
     double *ks = (double *)(h + o_k);
     for (int z = 0; z < S; z++) {
@@ -706,26 +704,20 @@ static int fp_run(slam_ctx *ctx, int S, const int32_t *off, const double *px1_xy
         ks[8 * z + 4] = b[0]; ks[8 * z + 5] = b[4]; ks[8 * z + 6] = b[6]; ks[8 * z + 7] = b[7];
     }
     memcpy(h + o_smp, samples, (size_t)S * iters * 20);
-    const size_t slots = (size_t)S * iters;
-    const size_t s_ne = up(slots * 4), s_es = up(slots * FP_MAXE * 72), s_po = up(slots * FP_MAXE * 96);
-    const size_t s_cn = up(slots * FP_MAXE * 4 + (size_t)S * 4), s_er = up((size_t)ntot * 8);
+    Layout D;
+    const FPScratch ds(D, S, iters, (size_t)ntot);
     char *scr;
-    rc = slam_scratch(ctx, s_ne + s_es + s_po + s_cn + s_er, (void **)&scr);
+    rc = slam_scratch(ctx, D.size(), (void **)&scr);
     if (rc) return rc;
     FPArgs T;
-    T.px1 = (const double *)d; T.px2 = (const double *)(d + pb); T.pd1 = (const double *)(d + 2 * pb); T.pd2 = (const double *)(d + 3 * pb);
+    T.px1 = (const double *)(d + o_px1); T.px2 = (const double *)(d + o_px2); T.pd1 = (const double *)(d + o_pd1); T.pd2 = (const double *)(d + o_pd2);
     T.samples = (const int32_t *)(d + o_smp); T.off = (const int *)(d + o_off); T.ks = (const double *)(d + o_k);
     T.iters = iters; T.thr = max_repr_error; T.cnt = nullptr; T.stride = 0;
-    T.ne = (int *)scr; T.Es = (double *)(scr + s_ne); T.poses = (double *)(scr + s_ne + s_es);
-    T.counts = (int *)(scr + s_ne + s_es + s_po); T.errs = (double *)(scr + s_ne + s_es + s_po + s_cn);
+    ds.bind(T, scr);
     T.out = (double *)(d + o_out); T.inliers = (uint8_t *)(d + o_inl);
-    const size_t lds = (size_t)FP_LDS_PER_THREAD * FP_TPB * sizeof(double);
-    HIP_TRY(ctx, hipFuncSetAttribute((const void *)k_5pt_solve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     { ProfScope span(ctx, "five_point_ransac");
-      hipLaunchKernelGGL(k_5pt_solve, dim3((iters + FP_TPB - 1) / FP_TPB, S), dim3(FP_TPB * FP_TEAM), lds, ctx->stream, T);
-      (void)hipMemsetAsync(T.counts + (size_t)S * iters * FP_MAXE, 0, (size_t)S * 4, ctx->stream);      // the incumbent counts
-      hipLaunchKernelGGL(k_5pt_score, dim3(iters, S), dim3(FP_SCORE_T), 0, ctx->stream, T);
-      hipLaunchKernelGGL(k_5pt_select, dim3(S), dim3(FP_SEL_T), 0, ctx->stream, T); }
+      rc = fp_enqueue(ctx, S, T);
+      if (rc) return rc; }
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, slam_stream_wait(ctx->stream));
     for (int z = 0; z < S; z++) {
@@ -740,6 +732,20 @@ static int fp_run(slam_ctx *ctx, int S, const int32_t *off, const double *px1_xy
     return SLAM_OK;
 }
 
+// nothing to sample from: zero pose and E, zero mask, no inliers, best_iter = -1 for each of the S problems
+static int fp_empty(int S, int ntot, double *E, double *P, uint8_t *inliers, int *n_inliers, double *error, int *best_iter)
+{
+    for (int z = 0; z < S; z++) {
+        n_inliers[z] = 0;
+        for (int j = 0; j < 12; j++) P[12 * z + j] = 0.0;
+        if (E) for (int j = 0; j < 9; j++) E[9 * z + j] = 0.0;
+        if (error) error[z] = 0.0;
+        if (best_iter) best_iter[z] = -1;
+    }
+    for (int i = 0; i < ntot; i++) inliers[i] = 0;
+    return SLAM_OK;
+}
+
 extern "C" int slam_five_point_ransac(slam_ctx *ctx, const double *px1_xy, const double *px2_xy, const double *pd1_xy,
                                       const double *pd2_xy, int n, const double *K1, const double *K2, double max_repr_error,
                                       const int32_t *samples, int iters, double *E, double *P, uint8_t *inliers,
@@ -749,15 +755,7 @@ extern "C" int slam_five_point_ransac(slam_ctx *ctx, const double *px1_xy, const
     ARG_TRY(ctx, K1 && K2 && P && n_inliers);
     ARG_TRY(ctx, n == 0 || (px1_xy && px2_xy && pd1_xy && pd2_xy && inliers));
     ARG_TRY(ctx, iters == 0 || samples);
-    if (n < 5 || iters == 0) {
-        *n_inliers = 0;
-        for (int j = 0; j < 12; j++) P[j] = 0.0;
-        if (E) for (int j = 0; j < 9; j++) E[j] = 0.0;
-        for (int i = 0; i < n; i++) inliers[i] = 0;
-        if (error) *error = 0.0;
-        if (best_iter) *best_iter = -1;
-        return SLAM_OK;
-    }
+    if (n < 5 || iters == 0) return fp_empty(1, n, E, P, inliers, n_inliers, error, best_iter);
     const int32_t off[2] = {0, n};
     return fp_run(ctx, 1, off, px1_xy, px2_xy, pd1_xy, pd2_xy, K1, K2, max_repr_error, samples, iters, E, P, inliers, n_inliers, error, best_iter);
 }
@@ -774,17 +772,7 @@ extern "C" int slam_five_point_ransac_batch(slam_ctx *ctx, int S, const int32_t 
     const int ntot = offsets[S];
     ARG_TRY(ctx, ntot == 0 || (px1_xy && px2_xy && pd1_xy && pd2_xy && inliers));
     ARG_TRY(ctx, iters == 0 || samples);
-    if (ntot == 0 || iters == 0) {
-        for (int z = 0; z < S; z++) {
-            n_inliers[z] = 0;
-            for (int j = 0; j < 12; j++) P[12 * z + j] = 0.0;
-            if (E) for (int j = 0; j < 9; j++) E[9 * z + j] = 0.0;
-            if (error) error[z] = 0.0;
-            if (best_iter) best_iter[z] = -1;
-        }
-        for (int i = 0; i < ntot; i++) inliers[i] = 0;
-        return SLAM_OK;
-    }
+    if (ntot == 0 || iters == 0) return fp_empty(S, ntot, E, P, inliers, n_inliers, error, best_iter);
     return fp_run(ctx, S, offsets, px1_xy, px2_xy, pd1_xy, pd2_xy, K1, K2, max_repr_error, samples, iters, E, P, inliers, n_inliers, error, best_iter);
 }
 
@@ -793,7 +781,7 @@ extern "C" int slam_five_point_ransac_batch(slam_ctx *ctx, int S, const int32_t 
 // compute_pose_5pt! on the device-resident keypoint set (src/front_end.jl:242-332; called every frame at :105): the keypoints the
 // previous key-frame also observes (slam_kpset_keyframe keeps that observation beside every keypoint) -> undistorted pixels and
 // normalised coordinates of both views, the rotation-compensated average parallax (:277-281) -> five-point RANSAC (the kernels
-// above, tuples from the counter-based generator of pose.hip) -> its outliers leave the list (:314-318).  The pose composition
+// above, tuples from the counter-based generator of geom_device.hpp) -> its outliers leave the list (:314-318).  The pose composition
 // with the motion-model scale (:320-330) needs the key-frame's and the frame's poses: that stays with the caller
 // (keypoint_set.pose_5pt_compose), which receives [R | t] of the essential-matrix decomposition.
 // =====================================================================================================================
@@ -806,25 +794,6 @@ struct KFiveArgs {
     uint8_t *flags; double *P; int *status, *ninl; double *parallax;                   // results
 };
 
-__device__ __forceinline__ unsigned long long fp_splitmix64(unsigned long long x)
-{
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-
-__device__ __forceinline__ void fp_undistort(double y, double x, double fx, double fy, double cx, double cy, double k1, double k2, double p1, double p2,
-                                             double &uy, double &ux)
-{   // undistort_point, camera.jl:98-125 (the arithmetic of k_kpose_gather)
-    const double ny = (y - cy) / fy, nx = (x - cx) / fx;
-    const double s0 = ny * ny, s1 = nx * nx, r2 = s0 + s1;
-    const double rd = (1.0 + k1 * r2) + k2 * (r2 * r2);
-    const double pp = ny * nx;
-    const double dtx = 2 * p1 * pp + p2 * (r2 + 2 * s0), dty = p1 * (r2 + 2 * s1) + 2 * p2 * pp;
-    uy = (rd * ny + dty) * fy + cy; ux = (rd * nx + dtx) * fx + cx;
-}
-
 __global__ __launch_bounds__(256) void k_kfive_gather(KFiveArgs A)
 {
     __shared__ int s_w[4], s_base;
@@ -832,7 +801,8 @@ __global__ __launch_bounds__(256) void k_kfive_gather(KFiveArgs A)
     const int z = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, n = A.count[z];
     const size_t b = (size_t)z * A.cap;
     const double *par = A.par + 32 * (size_t)z;
-    const double fx = par[16], fy = par[17], cx = par[18], cy = par[19], k1 = par[20], k2 = par[21], p1 = par[22], p2 = par[23];
+    const double cam[4] = {par[16], par[17], par[18], par[19]}, dist[4] = {par[20], par[21], par[22], par[23]};
+    const double fx = cam[0], fy = cam[1], cx = cam[2], cy = cam[3];
     if (tid == 0) s_base = 0;
     if (tid < 8) A.ks[8 * z + tid] = par[16 + (tid & 3)];        // both views through the same camera
     __syncthreads();
@@ -840,17 +810,12 @@ __global__ __launch_bounds__(256) void k_kfive_gather(KFiveArgs A)
     for (int c0 = 0; c0 < n; c0 += 256) {
         const int j = c0 + tid;
         const bool take = j < n && A.haskf[b + j] != 0;
-        const unsigned long long m = __ballot(take);
-        const int before = __popcll(m & ((1ull << lane) - 1ull));
-        if (lane == 0) s_w[wv] = __popcll(m);
-        __syncthreads();
-        int off = s_base;
-        for (int w = 0; w < wv; w++) off += s_w[w];
+        const int pos = ordered_slot(take, s_w, &s_base);
         if (take) {
-            const size_t q = b + j, o = b + off + before;
+            const size_t q = b + j, o = b + pos;
             double uy, ux, vy, vx;
-            fp_undistort(A.yx[2 * q], A.yx[2 * q + 1], fx, fy, cx, cy, k1, k2, p1, p2, uy, ux);
-            fp_undistort(A.kyx[2 * q], A.kyx[2 * q + 1], fx, fy, cx, cy, k1, k2, p1, p2, vy, vx);
+            undistort_px(cam, dist, A.yx[2 * q], A.yx[2 * q + 1], uy, ux);
+            undistort_px(cam, dist, A.kyx[2 * q], A.kyx[2 * q + 1], vy, vx);
             const double bx = (ux - cx) / fx, by = (uy - cy) / fy, ax = (vx - cx) / fx, ay = (vy - cy) / fy;
             A.px1[2 * o] = vx; A.px1[2 * o + 1] = vy; A.px2[2 * o] = ux; A.px2[2 * o + 1] = uy;      // (x, y), :266-267
             A.pd1[2 * o] = ax; A.pd1[2 * o + 1] = ay; A.pd2[2 * o] = bx; A.pd2[2 * o + 1] = by;      // position[[1, 2]], :268-269
@@ -862,9 +827,6 @@ __global__ __launch_bounds__(256) void k_kfive_gather(KFiveArgs A)
             const double dy = qy - vy, dx = qx - vx;
             psum += sqrt(dy * dy + dx * dx);
         }
-        __syncthreads();
-        if (tid == 0) s_base += s_w[0] + s_w[1] + s_w[2] + s_w[3];
-        __syncthreads();
     }
     // the reference adds the terms in Dict iteration order (unspecified); here: per lane, then a fixed butterfly, then the four waves
     for (int o = 32; o > 0; o >>= 1) psum += __shfl_xor(psum, o, 64);
@@ -882,17 +844,8 @@ __global__ __launch_bounds__(256) void k_kfive_samples(KFiveArgs A)
     // :243 fewer than 8 keypoints in the frame, :283 fewer than 8 in the key-frame, :290 not enough parallax -> no RANSAC
     const bool run = A.count[z] >= 8 && n >= 8 && !(A.psum[z] / (double)n < A.min_parallax);
     if (!run) { for (int k = 0; k < 5; k++) sm[k] = -1; return; }
-    int idx[5]; unsigned att = 0;
-    for (int k = 0; k < 5; k++) {
-        for (;;) {
-            const unsigned long long h = fp_splitmix64(A.seed ^ ((unsigned long long)z << 48) ^ ((unsigned long long)it << 16) ^ (unsigned long long)att);
-            att++;
-            const int c = (int)(h % (unsigned long long)n);
-            bool dup = false;
-            for (int m = 0; m < k; m++) dup = dup || idx[m] == c;
-            if (!dup) { idx[k] = c; break; }
-        }
-    }
+    int idx[5];
+    draw_distinct<5>(A.seed, z, it, n, idx);
     for (int k = 0; k < 5; k++) sm[k] = idx[k];
 }
 
@@ -914,8 +867,6 @@ __global__ __launch_bounds__(256) void k_kfive_finish(KFiveArgs A)
     }
 }
 
-int kpset_compact(slam_ctx *ctx, slam_kpset *ks, int mode, const uint8_t *flags_dev);
-
 extern "C" int slam_kpset_compute_pose_5pt(slam_ctx *ctx, slam_kpset *ks, const double *params, double min_parallax, double max_repr_error,
                                            int iters, uint64_t seed, double *P, int32_t *status, int32_t *n_inliers, double *parallax,
                                            int32_t *counts)
@@ -924,17 +875,17 @@ extern "C" int slam_kpset_compute_pose_5pt(slam_ctx *ctx, slam_kpset *ks, const 
     const bool fetch = P != nullptr;                             // P == status == NULL: enqueue only (the filter's effect is on the lists)
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int S = ks->S, cap = ks->cap;
-    const size_t nc = (size_t)S * cap, slots = (size_t)S * iters;
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t at = o; o += up(bytes); return at; };
-    const size_t o_px1 = take(nc * 16), o_px2 = take(nc * 16), o_pd1 = take(nc * 16), o_pd2 = take(nc * 16), o_slot = take(nc * 4);
-    const size_t o_n5 = take((size_t)S * 4), o_ps = take((size_t)S * 8), o_ks = take((size_t)S * 64), o_smp = take(slots * 20);
-    const size_t o_ne = take(slots * 4), o_es = take(slots * FP_MAXE * 72), o_po = take(slots * FP_MAXE * 96), o_cn = take(slots * FP_MAXE * 4 + (size_t)S * 4);      // (+ the incumbent count per stream: k_5pt_score)
-    const size_t o_er = take(nc * 8), o_out = take((size_t)S * 256), o_inl = take(nc), o_fl = take(nc);
-    const size_t o_P = take((size_t)S * 96), o_st = take((size_t)S * 4), o_ni = take((size_t)S * 4), o_pa = take((size_t)S * 8);
+    const size_t nc = (size_t)S * cap;
+    Layout D;                          // device scratch
+    const size_t o_px1 = D.take(nc * 16), o_px2 = D.take(nc * 16), o_pd1 = D.take(nc * 16), o_pd2 = D.take(nc * 16), o_slot = D.take(nc * 4);
+    const size_t o_n5 = D.take((size_t)S * 4), o_ps = D.take((size_t)S * 8), o_ks = D.take((size_t)S * 64), o_smp = D.take((size_t)S * iters * 20);
+    const FPScratch ds(D, S, iters, nc);
+    const size_t o_out = D.take((size_t)S * 256), o_inl = D.take(nc), o_fl = D.take(nc);
+    const size_t o_P = D.take((size_t)S * 96), o_st = D.take((size_t)S * 4), o_ni = D.take((size_t)S * 4), o_pa = D.take((size_t)S * 8);
+    Layout H;                          // pinned host block of the results (8 bytes per stream each, so that the int regions line up with the parallax)
+    const size_t h_P = H.take((size_t)S * 96), h_st = H.take((size_t)S * 8), h_ni = H.take((size_t)S * 8), h_pa = H.take((size_t)S * 8), h_cn = H.take((size_t)S * 8);
     char *scr;
-    int rc = slam_scratch2(ctx, o, (void **)&scr);
+    int rc = slam_scratch2(ctx, D.size(), (void **)&scr);
     if (rc) return rc;
     const double *par_dev;
     rc = kpset_stage_params(ctx, ks, params, (size_t)S * 32, &par_dev);
@@ -950,35 +901,29 @@ extern "C" int slam_kpset_compute_pose_5pt(slam_ctx *ctx, slam_kpset *ks, const 
     FPArgs T;
     T.px1 = A.px1; T.px2 = A.px2; T.pd1 = A.pd1; T.pd2 = A.pd2; T.samples = A.samples; T.off = nullptr; T.cnt = A.n5; T.stride = cap;
     T.ks = A.ks; T.iters = iters; T.thr = max_repr_error;
-    T.ne = (int *)(scr + o_ne); T.Es = (double *)(scr + o_es); T.poses = (double *)(scr + o_po); T.counts = (int *)(scr + o_cn);
-    T.errs = (double *)(scr + o_er); T.out = (double *)(scr + o_out); T.inliers = (uint8_t *)(scr + o_inl);
-    const size_t lds = (size_t)FP_LDS_PER_THREAD * FP_TPB * sizeof(double);
-    HIP_TRY(ctx, hipFuncSetAttribute((const void *)k_5pt_solve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    ds.bind(T, scr);
+    T.out = (double *)(scr + o_out); T.inliers = (uint8_t *)(scr + o_inl);
     HIP_TRY(ctx, hipMemsetAsync(A.flags, 0, nc, ctx->stream));
     { ProfScope span(ctx, "kpset_compute_pose_5pt");
       hipLaunchKernelGGL(k_kfive_gather, dim3(S), dim3(256), 0, ctx->stream, A);
       hipLaunchKernelGGL(k_kfive_samples, dim3((iters + 255) / 256, S), dim3(256), 0, ctx->stream, A);
-      hipLaunchKernelGGL(k_5pt_solve, dim3((iters + FP_TPB - 1) / FP_TPB, S), dim3(FP_TPB * FP_TEAM), lds, ctx->stream, T);
-      (void)hipMemsetAsync(T.counts + (size_t)S * iters * FP_MAXE, 0, (size_t)S * 4, ctx->stream);      // the incumbent counts
-      hipLaunchKernelGGL(k_5pt_score, dim3(iters, S), dim3(FP_SCORE_T), 0, ctx->stream, T);
-      hipLaunchKernelGGL(k_5pt_select, dim3(S), dim3(FP_SEL_T), 0, ctx->stream, T);
+      rc = fp_enqueue(ctx, S, T);
+      if (rc) return rc;
       hipLaunchKernelGGL(k_kfive_finish, dim3(S), dim3(256), 0, ctx->stream, A); }
     HIP_TRY(ctx, hipGetLastError());
     rc = kpset_compact(ctx, ks, 1, A.flags);
     if (rc) return rc;
     if (!fetch) return SLAM_OK;
-    void *hv;
-    rc = slam_pinned(ctx, up((size_t)S * 96) + 4 * up((size_t)S * 8), &hv);
+    char *h;
+    rc = slam_pinned(ctx, H.size(), (void **)&h);
     if (rc) return rc;
-    char *h = (char *)hv;
-    const size_t h_st = up((size_t)S * 96), h_ni = h_st + up((size_t)S * 8), h_pa = h_ni + up((size_t)S * 8), h_cn = h_pa + up((size_t)S * 8);
-    HIP_TRY(ctx, hipMemcpyAsync(h, A.P, (size_t)S * 96, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(h + h_P, A.P, (size_t)S * 96, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(h + h_st, A.status, (size_t)S * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(h + h_ni, A.ninl, (size_t)S * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(h + h_pa, A.parallax, (size_t)S * 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(h + h_cn, ks->count, (size_t)S * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, slam_stream_wait(ctx->stream));
-    memcpy(P, h, (size_t)S * 96);
+    memcpy(P, h + h_P, (size_t)S * 96);
     memcpy(status, h + h_st, (size_t)S * 4);
     if (n_inliers) memcpy(n_inliers, h + h_ni, (size_t)S * 4);
     if (parallax) memcpy(parallax, h + h_pa, (size_t)S * 8);

@@ -10,10 +10,8 @@
 // keypoints keep their order) and is done with wave ballots + prefix counts, one workgroup per stream.
 #include "common.hpp"
 #include <algorithm>
-#include "tri_device.hpp"
+#include "geom_device.hpp"
 #include <cmath>
-
-static size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // live slots of all streams back to back + their number.  One small workgroup per stream (it sums the counts before its own: S
 // loads): a single 1024-thread workgroup had to wait for sixteen free wave slots on one CU while the pyramid kernels fill the chip
@@ -68,6 +66,7 @@ __global__ __launch_bounds__(256) void k_kpset_compact(KpsetView K, int mode, co
             if (keep) { sy = K.syx[2 * q]; sx = K.syx[2 * q + 1]; X0 = K.xyz[3 * q]; X1 = K.xyz[3 * q + 1]; X2 = K.xyz[3 * q + 2]; id = K.id[q]; f3 = K.is3d[q]; fs = K.stereo[q];
                         ky = K.kyx[2 * q]; kx = K.kyx[2 * q + 1]; fk = K.haskf[q]; fy0 = K.fyx[2 * q]; fx0 = K.fyx[2 * q + 1]; fkid = K.fkf[q]; }
         }
+        // (its own loop, not ordered_slot: the writes follow the one barrier that ends the chunk's reads, and this kernel runs after every match)
         const unsigned long long m = __ballot(keep);
         const int rank = __builtin_popcountll(m & ((1ull << lane) - 1ull));
         if (lane == 0) s_w[wv] = __builtin_popcountll(m);
@@ -121,7 +120,7 @@ int kpset_compact(slam_ctx *ctx, slam_kpset *ks, int mode, const uint8_t *flags_
 // triangulated (the DLT of slam_triangulate, same gates); success -> map point Twc[s] * X, is3d = 1; failure -> the stereo
 // observation is dropped (remove_stereo_keypoint!).
 struct KTriArgs {
-    double P1[16], P2[16], T21[16], cam1[4], cam2[4];
+    TwoViewMats M;
     const double *Twc;                 // [S][16] column-major camera-1 -> world, device
     double max_error, min_depth;
 };
@@ -131,41 +130,12 @@ __device__ __forceinline__ void k_kpset_triangulate_slot(const KpsetView &K, con
     if (!K.stereo[q] || K.is3d[q]) return;
     const int s = (int)(q / K.cap);
     const double x1 = K.yx[2 * q + 1], y1 = K.yx[2 * q], x2 = K.syx[2 * q + 1], y2 = K.syx[2 * q];
-    double A[16], S[16], v[4];
-    for (int j = 0; j < 4; j++) {
-        A[0 + j] = x1 * T.P1[2 + 4 * j] - T.P1[0 + 4 * j];
-        A[4 + j] = y1 * T.P1[2 + 4 * j] - T.P1[1 + 4 * j];
-        A[8 + j] = x2 * T.P2[2 + 4 * j] - T.P2[0 + 4 * j];
-        A[12 + j] = y2 * T.P2[2 + 4 * j] - T.P2[1 + 4 * j];
-    }
-    for (int r = 0; r < 4; r++)
-        for (int c = 0; c < 4; c++) {
-            double acc = 0.0;
-            for (int k = 0; k < 4; k++) acc += A[4 * k + r] * A[4 * k + c];
-            S[4 * r + c] = acc;
-        }
-    sym4_min_eigvec(S, v);
-    const double iw = 1.0 / v[3];
-    const double L0 = v[0] * iw, L1 = v[1] * iw, L2 = v[2] * iw, L3 = v[3] * iw;
-    bool ok = !(L2 < T.min_depth);
-    double R[3];
-    for (int r = 0; r < 3; r++) R[r] = ((T.T21[r] * L0 + T.T21[r + 4] * L1) + T.T21[r + 8] * L2) + T.T21[r + 12] * L3;
-    if (ok && R[2] < T.min_depth) ok = false;
-    if (ok) {
-        const double iz = 1.0 / L2;
-        const double py = T.cam1[1] * L1 * iz + T.cam1[3], px = T.cam1[0] * L0 * iz + T.cam1[2];
-        const double dy = y1 - py, dx = x1 - px;
-        if (sqrt(dy * dy + dx * dx) > T.max_error) ok = false;
-    }
-    if (ok) {
-        const double iz = 1.0 / R[2];
-        const double py = T.cam2[1] * R[1] * iz + T.cam2[3], px = T.cam2[0] * R[0] * iz + T.cam2[2];
-        const double dy = y2 - py, dx = x2 - px;
-        if (sqrt(dy * dy + dx * dx) > T.max_error) ok = false;
-    }
+    double L[4];
+    dlt_two_view(x1, y1, x2, y2, T.M.P1, T.M.P2, L);
+    const bool ok = two_view_gates(L, T.M.T21, T.M.cam1, T.M.cam2, x1, y1, x2, y2, T.max_error, T.min_depth, true);
     if (ok) {
         const double *W = T.Twc + 16 * (size_t)s;                // project_camera_to_world (frame.jl): Twc * X
-        for (int r = 0; r < 3; r++) K.xyz[3 * q + r] = ((W[r] * L0 + W[r + 4] * L1) + W[r + 8] * L2) + W[r + 12] * L3;
+        for (int r = 0; r < 3; r++) K.xyz[3 * q + r] = ((W[r] * L[0] + W[r + 4] * L[1]) + W[r + 8] * L[2]) + W[r + 12] * L[3];
         K.is3d[q] = 1;
     } else K.stereo[q] = 0;
 }
@@ -190,16 +160,6 @@ struct KTempArgs {
     double max_error, min_depth, min_parallax;
     uint8_t *flags;
 };
-__device__ __forceinline__ void kp_undistort(const double *par, double y, double x, double &uy, double &ux)
-{
-    const double fx = par[16], fy = par[17], cx = par[18], cy = par[19], k1 = par[20], k2 = par[21], p1 = par[22], p2 = par[23];
-    const double ny = (y - cy) / fy, nx = (x - cx) / fx;
-    const double s0 = ny * ny, s1 = nx * nx, r2 = s0 + s1;
-    const double rd = (1.0 + k1 * r2) + k2 * (r2 * r2);
-    const double pp = ny * nx;
-    const double dtx = 2 * p1 * pp + p2 * (r2 + 2 * s0), dty = p1 * (r2 + 2 * s1) + 2 * p2 * pp;
-    uy = (rd * ny + dty) * fy + cy; ux = (rd * nx + dtx) * fx + cx;
-}
 __device__ __forceinline__ void k_kpset_tri_temporal_slot(const KpsetView &K, const KTempArgs &T, const int *work, int i)
 {
     const size_t q = (size_t)work[i];
@@ -211,8 +171,8 @@ __device__ __forceinline__ void k_kpset_tri_temporal_slot(const KpsetView &K, co
     const double *P2 = E, *T21 = E + 16, *REL = E + 32, *WOB = E + 48;
     const double fx = par[16], fy = par[17], cx = par[18], cy = par[19];
     double y1, x1, y2, x2;
-    kp_undistort(par, K.fyx[2 * q], K.fyx[2 * q + 1], y1, x1);  // obup
-    kp_undistort(par, K.yx[2 * q], K.yx[2 * q + 1], y2, x2);    // kpup
+    undistort_px(par + 16, par + 20, K.fyx[2 * q], K.fyx[2 * q + 1], y1, x1);  // obup
+    undistort_px(par + 16, par + 20, K.yx[2 * q], K.yx[2 * q + 1], y2, x2);    // kpup
     // parallax = |obup - project(camera, R(rel_pose) * kp.position)|, :236-237
     const double bx = (x2 - cx) / fx, by = (y2 - cy) / fy;
     const double rx = (REL[0] * bx + REL[4] * by) + REL[8] * 1.0, ry = (REL[1] * bx + REL[5] * by) + REL[9] * 1.0, rz = (REL[2] * bx + REL[6] * by) + REL[10] * 1.0;
@@ -220,41 +180,12 @@ __device__ __forceinline__ void k_kpset_tri_temporal_slot(const KpsetView &K, co
     const double pdy = y1 - qy, pdx = x1 - qx;
     const bool gated = sqrt(pdy * pdy + pdx * pdx) > T.min_parallax;
     // P1 = K * I
-    const double P1[16] = {fx, 0, 0, 0, 0, fy, 0, 0, cx, cy, 1, 0, 0, 0, 0, 1};
-    double A[16], S[16], v[4];
-    for (int j = 0; j < 4; j++) {
-        A[0 + j] = x1 * P1[2 + 4 * j] - P1[0 + 4 * j];
-        A[4 + j] = y1 * P1[2 + 4 * j] - P1[1 + 4 * j];
-        A[8 + j] = x2 * P2[2 + 4 * j] - P2[0 + 4 * j];
-        A[12 + j] = y2 * P2[2 + 4 * j] - P2[1 + 4 * j];
-    }
-    for (int r = 0; r < 4; r++)
-        for (int c = 0; c < 4; c++) {
-            double acc = 0.0;
-            for (int k = 0; k < 4; k++) acc += A[4 * k + r] * A[4 * k + c];
-            S[4 * r + c] = acc;
-        }
-    sym4_min_eigvec(S, v);
-    const double iw = 1.0 / v[3];
-    const double L0 = v[0] * iw, L1 = v[1] * iw, L2 = v[2] * iw, L3 = v[3] * iw;
-    bool ok = !(L2 < T.min_depth && gated);
-    double R[3];
-    for (int r = 0; r < 3; r++) R[r] = ((T21[r] * L0 + T21[r + 4] * L1) + T21[r + 8] * L2) + T21[r + 12] * L3;
-    if (ok && R[2] < T.min_depth && gated) ok = false;
+    const double P1[16] = {fx, 0, 0, 0, 0, fy, 0, 0, cx, cy, 1, 0, 0, 0, 0, 1}, cam[4] = {fx, fy, cx, cy};
+    double L[4];
+    dlt_two_view(x1, y1, x2, y2, P1, P2, L);
+    const bool ok = two_view_gates(L, T21, cam, cam, x1, y1, x2, y2, T.max_error, T.min_depth, gated);
     if (ok) {
-        const double iz = 1.0 / L2;
-        const double py = fy * L1 * iz + cy, px = fx * L0 * iz + cx;
-        const double dy = y1 - py, dx = x1 - px;
-        if (sqrt(dy * dy + dx * dx) > T.max_error && gated) ok = false;
-    }
-    if (ok) {
-        const double iz = 1.0 / R[2];
-        const double py = fy * R[1] * iz + cy, px = fx * R[0] * iz + cx;
-        const double dy = y2 - py, dx = x2 - px;
-        if (sqrt(dy * dy + dx * dx) > T.max_error && gated) ok = false;
-    }
-    if (ok) {
-        for (int r = 0; r < 3; r++) K.xyz[3 * q + r] = ((WOB[r] * L0 + WOB[r + 4] * L1) + WOB[r + 8] * L2) + WOB[r + 12] * L3;   // project_camera_to_world(observer_kf, .)
+        for (int r = 0; r < 3; r++) K.xyz[3 * q + r] = ((WOB[r] * L[0] + WOB[r + 4] * L[1]) + WOB[r + 8] * L[2]) + WOB[r + 12] * L[3];   // project_camera_to_world(observer_kf, .)
         K.is3d[q] = 1;
     } else T.flags[q] = 1;                                        // remove_mappoint_obs!(map_manager, id, frame.kfid)
 }
@@ -274,15 +205,14 @@ int slam_kpset_create(slam_ctx *ctx, int S, int cap, slam_kpset **out)
     ARG_TRY(ctx, ctx != nullptr && out != nullptr && S >= 1 && S <= 128 && cap >= 1 && (size_t)S * cap < (1u << 30));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t n = (size_t)S * cap;
-    size_t off = 0;
-    auto take = [&](size_t b) { size_t o = off; off += al256(b); return o; };
-    const size_t o_yx = take(n * 16), o_oyx = take(n * 16), o_syx = take(n * 16), o_xyz = take(n * 24), o_id = take(n * 8);
-    const size_t o_3d = take(n), o_st = take(n), o_ss = take(n), o_cnt = take((size_t)S * 4), o_work = take(n * 4), o_nt = take(64);
-    const size_t o_nid = take((size_t)S * 8), o_par = take((size_t)8 * S * 32 * 8), o_kyx = take(n * 16), o_hk = take(n), o_fyx = take(n * 16), o_fkf = take(n * 4), o_kfc = take((size_t)S * 4);
+    Layout Lo;
+    const size_t o_yx = Lo.take(n * 16), o_oyx = Lo.take(n * 16), o_syx = Lo.take(n * 16), o_xyz = Lo.take(n * 24), o_id = Lo.take(n * 8);
+    const size_t o_3d = Lo.take(n), o_st = Lo.take(n), o_ss = Lo.take(n), o_cnt = Lo.take((size_t)S * 4), o_work = Lo.take(n * 4), o_nt = Lo.take(64);
+    const size_t o_nid = Lo.take((size_t)S * 8), o_par = Lo.take((size_t)8 * S * 32 * 8), o_kyx = Lo.take(n * 16), o_hk = Lo.take(n), o_fyx = Lo.take(n * 16), o_fkf = Lo.take(n * 4), o_kfc = Lo.take((size_t)S * 4);
     slam_kpset *ks = new slam_kpset();
     ks->device = ctx->device; ks->S = S; ks->cap = cap;
-    hipError_t e = hipMalloc((void **)&ks->base, off);
-    if (e == hipSuccess) e = hipMemsetAsync(ks->base, 0, off, ctx->stream);
+    hipError_t e = hipMalloc((void **)&ks->base, Lo.size());
+    if (e == hipSuccess) e = hipMemsetAsync(ks->base, 0, Lo.size(), ctx->stream);
     if (e == hipSuccess) e = slam_stream_wait(ctx->stream);
     if (e != hipSuccess) { if (ks->base) (void)hipFree(ks->base); delete ks; return slam_fail(ctx, SLAM_ERR_HIP, "slam_kpset_create: %s", hipGetErrorString(e)); }
     char *B = ks->base;
@@ -474,8 +404,7 @@ int slam_kpset_triangulate(slam_ctx *ctx, slam_kpset *ks, const double *P1, cons
     ARG_TRY(ctx, ctx != nullptr && ks != nullptr && P1 && P2 && T21 && cam1 && cam2 && Twc);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     KTriArgs T;
-    memcpy(T.P1, P1, sizeof T.P1); memcpy(T.P2, P2, sizeof T.P2); memcpy(T.T21, T21, sizeof T.T21);
-    memcpy(T.cam1, cam1, sizeof T.cam1); memcpy(T.cam2, cam2, sizeof T.cam2);
+    T.M.fill(P1, P2, T21, cam1, cam2);
     T.max_error = max_error; T.min_depth = min_depth;
     int rc = kpset_stage_params(ctx, ks, Twc, (size_t)ks->S * 16, &T.Twc);
     if (rc) return rc;
@@ -494,22 +423,22 @@ int slam_kpset_triangulate_temporal(slam_ctx *ctx, slam_kpset *ks, const double 
     ARG_TRY(ctx, ctx != nullptr && ks != nullptr && params && tab && kf_cur && kf_lo && nkf >= 1);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int S = ks->S;
-    const size_t nc = (size_t)S * ks->cap, tb = al256((size_t)S * nkf * 64 * 8), ib = al256((size_t)S * 4);
-    char *scr;
-    int rc = slam_scratch2(ctx, tb + 2 * ib + al256(nc), (void **)&scr);
+    const size_t nc = (size_t)S * ks->cap;
+    Layout D;                          // the staged inputs (same offsets in the pinned block), then the removal flags
+    const size_t o_tab = D.take((size_t)S * nkf * 64 * 8), o_cur = D.take((size_t)S * 4), o_lo = D.take((size_t)S * 4), in_b = D.size(), o_fl = D.take(nc);
+    char *scr, *h;
+    int rc = slam_scratch2(ctx, D.size(), (void **)&scr);
     if (rc) return rc;
-    void *hv;
-    rc = slam_pinned(ctx, tb + 2 * ib, &hv);
+    rc = slam_pinned(ctx, in_b, (void **)&h);
     if (rc) return rc;
-    char *h = (char *)hv;
-    memcpy(h, tab, (size_t)S * nkf * 64 * 8); memcpy(h + tb, kf_cur, (size_t)S * 4); memcpy(h + tb + ib, kf_lo, (size_t)S * 4);
-    HIP_TRY(ctx, hipMemcpyAsync(scr, h, tb + 2 * ib, hipMemcpyHostToDevice, ctx->stream));
+    memcpy(h + o_tab, tab, (size_t)S * nkf * 64 * 8); memcpy(h + o_cur, kf_cur, (size_t)S * 4); memcpy(h + o_lo, kf_lo, (size_t)S * 4);
+    HIP_TRY(ctx, hipMemcpyAsync(scr, h, in_b, hipMemcpyHostToDevice, ctx->stream));
     KTempArgs T;
     rc = kpset_stage_params(ctx, ks, params, (size_t)S * 32, &T.par);
     if (rc) return rc;
-    T.tab = (const double *)scr; T.kf_cur = (const int *)(scr + tb); T.kf_lo = (const int *)(scr + tb + ib); T.nkf = nkf;
+    T.tab = (const double *)(scr + o_tab); T.kf_cur = (const int *)(scr + o_cur); T.kf_lo = (const int *)(scr + o_lo); T.nkf = nkf;
     T.max_error = max_error; T.min_depth = min_depth; T.min_parallax = min_parallax;
-    T.flags = (uint8_t *)(scr + tb + 2 * ib);
+    T.flags = (uint8_t *)(scr + o_fl);
     HIP_TRY(ctx, hipMemsetAsync(T.flags, 0, nc, ctx->stream));
     rc = kpset_build_worklist(ctx, ks);
     if (rc) return rc;

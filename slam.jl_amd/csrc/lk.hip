@@ -16,6 +16,7 @@
 // CPU oracle (sum_order = 1) and is bit-reproducible; it differs from the
 // reference's single-accumulator order only in rounding (<= 1e-12 px observed).
 #include "common.hpp"
+#include "geom_device.hpp"
 #include <vector>
 #include <cmath>
 #include <cstdlib>
@@ -549,16 +550,6 @@ struct KpMatchArgs {
     const double *par;
     int H, W, stereo_mode; double epipolar;
 };
-// undistort_pdn_point (camera.jl:111-125): normalised (y, x) -> pixel through the lens model
-__device__ __forceinline__ void pdn_to_pixel(const double *cam, const double *dist, double ny, double nx, double &oy, double &ox)
-{
-    const double s0 = ny * ny, s1 = nx * nx, r2 = s0 + s1;
-    const double rd = 1.0 + dist[0] * r2 + dist[1] * (r2 * r2);
-    const double p = ny * nx;
-    const double dtx = 2 * dist[2] * p + dist[3] * (r2 + 2 * s0);
-    const double dty = dist[2] * (r2 + 2 * s1) + 2 * dist[3] * p;
-    oy = (rd * ny + dty) * cam[1] + cam[3]; ox = (rd * nx + dtx) * cam[0] + cam[2];
-}
 template <int LK_MAXE, bool TOL>
 __global__ __launch_bounds__(64) LK_OCC void k_kpset_match(KpMatchArgs M)
 {
@@ -681,7 +672,6 @@ extern "C" int slam_kpset_stereo_match(slam_ctx *ctx, slam_kpset *ks, const slam
     return kpset_match(ctx, ks, left0, right0, params, prior, pyramid_levels, pyramid_levels_3d, window, iterations, eig_thr, eps, max_distance, 1, epipolar_error, n_bound);
 }
 
-static size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
 #define LK_STAGE_MIN_POINTS 4096
 
 // shared host path.  Keypoint lists are tiny (16-33 B per point): instead of staging
@@ -694,22 +684,23 @@ static int run_tracking(slam_ctx *ctx, const slam_pyr *prev, const slam_pyr *cur
                         double eig_thr, double eps, double max_distance, double *out_yx, uint8_t *status, bool flow,
                         const int32_t *img_index = nullptr)
 {
-    const size_t pb = al256((size_t)n * 16), sb = al256((size_t)n), ib = al256((size_t)n * 4);
-    const size_t in_b = 2 * pb + sb + ib, out_b = pb + sb;
+    Layout B;                          // inputs, then outputs
+    const size_t o_pts = B.take((size_t)n * 16), o_aux = B.take((size_t)n * 16), o_3d = B.take((size_t)n), o_img = B.take((size_t)n * 4), in_b = B.size();
+    const size_t o_out = B.take((size_t)n * 16), o_st = B.take((size_t)n), out_b = B.size() - in_b;
     char *h, *d;
-    int rc = slam_pinned(ctx, in_b + out_b, (void **)&h);
+    int rc = slam_pinned(ctx, B.size(), (void **)&h);
     if (rc) return rc;
     HIP_TRY(ctx, hipHostGetDevicePointer((void **)&d, h, 0));
-    memcpy(h, pts_yx, (size_t)n * 16);
-    if (aux_yx) memcpy(h + pb, aux_yx, (size_t)n * 16);
-    if (is3d) memcpy(h + 2 * pb, is3d, (size_t)n);
-    if (img_index) memcpy(h + 2 * pb + sb, img_index, (size_t)n * 4);
+    memcpy(h + o_pts, pts_yx, (size_t)n * 16);
+    if (aux_yx) memcpy(h + o_aux, aux_yx, (size_t)n * 16);
+    if (is3d) memcpy(h + o_3d, is3d, (size_t)n);
+    if (img_index) memcpy(h + o_img, img_index, (size_t)n * 4);
     // Large batches: tens of thousands of 8-byte reads and writes over PCIe (every wave starts with dependent
     // reads of its point and ends with three small stores) are slower than one DMA of the whole block each way.
     const bool staged = n >= LK_STAGE_MIN_POINTS;
     if (staged) {
         void *dbuf;
-        rc = slam_scratch(ctx, in_b + out_b, &dbuf);
+        rc = slam_scratch(ctx, B.size(), &dbuf);
         if (rc) return rc;
         HIP_TRY(ctx, hipMemcpyAsync(dbuf, h, in_b, hipMemcpyHostToDevice, ctx->stream));
         d = (char *)dbuf;
@@ -717,12 +708,12 @@ static int run_tracking(slam_ctx *ctx, const slam_pyr *prev, const slam_pyr *cur
     FlowArgs F;
     LKArgs &A = F.lk;
     A.prev = prev->view; A.cur = cur->view;
-    A.pts = (const double *)d; A.disp0 = aux_yx ? (const double *)(d + pb) : nullptr; A.n = n;
+    A.pts = (const double *)(d + o_pts); A.disp0 = aux_yx ? (const double *)(d + o_aux) : nullptr; A.n = n;
     A.pyramid_levels = pyramid_levels; A.window = window; A.iterations = iterations;
     A.eig_thr = eig_thr; A.eps = eps; A.max_distance = max_distance;
-    A.out = (double *)(d + in_b); A.status = (uint8_t *)(d + in_b + pb);
-    F.is3d = (const uint8_t *)(d + 2 * pb); F.proj = (const double *)(d + pb); F.levels3d = levels3d;
-    F.img = img_index ? (const int *)(d + 2 * pb + sb) : nullptr; F.zs_from = prev->zstride; F.zs_to = cur->zstride;
+    A.out = (double *)(d + o_out); A.status = (uint8_t *)(d + o_st);
+    F.is3d = (const uint8_t *)(d + o_3d); F.proj = (const double *)(d + o_aux); F.levels3d = levels3d;
+    F.img = img_index ? (const int *)(d + o_img) : nullptr; F.zs_from = prev->zstride; F.zs_to = cur->zstride;
     { ProfScope span(ctx, "fb_track");
       const int ne = (2 * window + 1) * (2 * window + 1);
       if (flow) {
@@ -737,8 +728,8 @@ static int run_tracking(slam_ctx *ctx, const slam_pyr *prev, const slam_pyr *cur
     HIP_TRY(ctx, hipGetLastError());
     if (staged) HIP_TRY(ctx, hipMemcpyAsync(h + in_b, d + in_b, out_b, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, slam_stream_wait(ctx->stream));
-    memcpy(out_yx, h + in_b, (size_t)n * 16);
-    memcpy(status, h + in_b + pb, (size_t)n);
+    memcpy(out_yx, h + o_out, (size_t)n * 16);
+    memcpy(status, h + o_st, (size_t)n);
     return SLAM_OK;
 }
 

@@ -8,6 +8,7 @@
 // K [R | t].  Inputs/outputs live in the context's mapped pinned block (a few tens of KB), scores in device scratch.
 // The work is ~iters x 4 x n reprojections (256 x 4 x 1000 = 1 M): launch- and latency-bound, not HBM-bound.
 #include "common.hpp"
+#include "geom_device.hpp"
 #include <cmath>
 
 #define P3P_ERR_LDS 4096                // map points whose errors the select kernel stages in LDS
@@ -210,7 +211,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void k_
     // each point they load.  (Four waves per triple, each repeating the solver for "its" pose, took 190 us per 32-stream call.)
     __shared__ double s_P[48];
     const int it = blockIdx.x, z = blockIdx.y, lane = threadIdx.x;
-    const int base = T.cnt ? z * T.stride : T.off[z], n = T.cnt ? T.cnt[z] : T.off[z + 1] - base;
+    const ProblemRange pr = problem_range(T.off, T.cnt, T.stride, z);
+    const int base = pr.base, n = pr.n;
     const double *pts = T.pts + 3 * (size_t)base, *px = T.px + 2 * (size_t)base, *pdn = T.pdn + 3 * (size_t)base;
     const int32_t *sm = T.samples + 3 * ((size_t)z * T.iters + it);
     const int i0 = sm[0], i1 = sm[1], i2 = sm[2];
@@ -260,68 +262,52 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void k_
     }
 }
 
-__global__ __launch_bounds__(256) void k_p3p_select(P3PArgs T)
-{
-    __shared__ int s_cnt[256], s_idx[256];
-    __shared__ double s_P[12], s_K[9];
-    __shared__ double s_err[P3P_ERR_LDS];
-    const int tid = threadIdx.x, z = blockIdx.x, ne = 4 * T.iters;
-    const int base = T.cnt ? z * T.stride : T.off[z], n = T.cnt ? T.cnt[z] : T.off[z + 1] - base;
-    const double *pts = T.pts + 3 * (size_t)base, *px = T.px + 2 * (size_t)base;
-    const int *counts = T.counts + (size_t)z * ne;
-    const double *poses = T.poses + (size_t)z * ne * 12;
-    double *errs = T.errs + base, *out = T.out + 32 * (size_t)z;
-    uint8_t *inliers = T.inliers + base;
-    const bool in_lds = n <= P3P_ERR_LDS;
-    if (tid < 9) s_K[tid] = T.Ks[9 * z + tid];
-    int bc = 0, bi = -1;
-    for (int e = tid; e < ne; e += 256) {
-        const int c = counts[e];
-        if (c > bc) { bc = c; bi = e; }        // ascending e: the first maximum is kept
+// k_p3p_select = ransac_select with this policy: four candidates per triple, reprojection error of the winning pose
+struct P3PSelect {
+    static constexpr int THREADS = 256, PER_ITER = 4, ERR_LDS = P3P_ERR_LDS;
+    const double *Ks, *poses, *pts, *px; double thr; double *out, *s_P, *s_K;
+    __device__ void stage(int tid) const { if (tid < 9) s_K[tid] = Ks[tid]; }
+    __device__ void winner(int tid, int best, int be) const { if (tid < 12) s_P[tid] = best > 0 ? poses[(size_t)be * 12 + tid] : 0.0; }
+    __device__ bool score(int i, double &e) const
+    {
+        const double X[3] = {pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]};
+        const double q[2] = {px[2 * i], px[2 * i + 1]};
+        e = p3p_reproj(s_P, s_K, X, q);
+        return e >= 0.0 && e < thr;
     }
-    s_cnt[tid] = bc; s_idx[tid] = bi;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (tid < o) {
-            const int c2 = s_cnt[tid + o], i2 = s_idx[tid + o];
-            if (c2 > s_cnt[tid] || (c2 == s_cnt[tid] && c2 > 0 && i2 < s_idx[tid])) { s_cnt[tid] = c2; s_idx[tid] = i2; }
-        }
-        __syncthreads();
-    }
-    const int best = s_cnt[0], be = s_idx[0];
-    if (tid < 12) s_P[tid] = best > 0 ? poses[(size_t)be * 12 + tid] : 0.0;
-    __syncthreads();
-    for (int i = tid; i < n; i += 256) {
-        double e = -1.0;
-        if (best > 0) {
-            const double X[3] = {pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]};
-            const double q[2] = {px[2 * i], px[2 * i + 1]};
-            e = p3p_reproj(s_P, s_K, X, q);
-        }
-        const bool in = best > 0 && e >= 0.0 && e < T.thr;
-        inliers[i] = in ? 1 : 0;
-        if (in_lds) s_err[i] = in ? e : 0.0; else errs[i] = in ? e : 0.0;   // + 0.0 leaves the sum unchanged
-    }
-    __threadfence_block();
-    __syncthreads();
-    if (tid == 0) {
-        double esum = 0.0;
-        if (in_lds) {
-#pragma unroll 16
-            for (int i = 0; i < n; i++) esum += s_err[i];             // index order; the reads pipeline, the adds are the chain
-        } else {
-#pragma unroll 16
-            for (int i = 0; i < n; i++) esum += errs[i];
-        }
+    __device__ void write(int best, int be, double esum) const
+    {
         out[24] = esum;
         int *oi = (int *)(out + 25);
-        oi[0] = best; oi[1] = best > 0 ? be / 4 : -1;
+        oi[0] = best; oi[1] = best > 0 ? be / PER_ITER : -1;
         for (int c = 0; c < 4; c++)
             for (int r = 0; r < 3; r++) {
                 out[r + 3 * c] = (s_K[r] * s_P[3 * c] + s_K[r + 3] * s_P[3 * c + 1]) + s_K[r + 6] * s_P[3 * c + 2];
                 out[12 + r + 3 * c] = s_P[r + 3 * c];
             }
     }
+};
+__global__ __launch_bounds__(P3PSelect::THREADS) void k_p3p_select(P3PArgs T)
+{
+    __shared__ double s_P[12], s_K[9];
+    const int z = blockIdx.x, ne = P3PSelect::PER_ITER * T.iters;
+    const ProblemRange pr = problem_range(T.off, T.cnt, T.stride, z);
+    const P3PSelect pol{T.Ks + 9 * z, T.poses + (size_t)z * ne * 12, T.pts + 3 * (size_t)pr.base, T.px + 2 * (size_t)pr.base, T.thr,
+                        T.out + 32 * (size_t)z, s_P, s_K};
+    ransac_select(pol, T.counts + (size_t)z * ne, ne, pr.n, T.errs + pr.base, T.inliers + pr.base);
+}
+
+// the device scratch of P3PArgs (counts | poses | errs) as regions of the caller's layout, and the only launch site of the two kernels
+struct P3PScratch {
+    size_t counts, poses, errs;
+    P3PScratch(Layout &L, int S, int iters, size_t npts)
+        : counts(L.take((size_t)S * iters * 16)), poses(L.take((size_t)S * iters * 4 * 96)), errs(L.take(npts * 8)) {}
+    void bind(P3PArgs &T, char *scr) const { T.counts = (int *)(scr + counts); T.poses = (double *)(scr + poses); T.errs = (double *)(scr + errs); }
+};
+static void p3p_enqueue(slam_ctx *ctx, int S, const P3PArgs &T)
+{
+    hipLaunchKernelGGL(k_p3p_score, dim3(T.iters, S), dim3(64), 0, ctx->stream, T);
+    hipLaunchKernelGGL(k_p3p_select, dim3(S), dim3(P3PSelect::THREADS), 0, ctx->stream, T);
 }
 
 // S problems in one pair of launches (grid.y / grid.x = problem); offsets, intrinsics, inputs and outputs go through
@@ -332,30 +318,29 @@ static int p3p_run(slam_ctx *ctx, int S, const int32_t *off, const double *pts3d
 {
     const int ntot = off[S];
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t o_off = 0, o_K = o_off + up((size_t)(S + 1) * 4), o_pts = o_K + up((size_t)S * 72);
-    const size_t o_px = o_pts + up((size_t)ntot * 24), o_pdn = o_px + up((size_t)ntot * 16), o_smp = o_pdn + up((size_t)ntot * 24);
-    const size_t o_out = o_smp + up((size_t)S * iters * 12), o_inl = o_out + (size_t)S * 256, total = o_inl + up((size_t)ntot);
+    Layout H;
+    const size_t o_off = H.take((size_t)(S + 1) * 4), o_K = H.take((size_t)S * 72), o_pts = H.take((size_t)ntot * 24), o_px = H.take((size_t)ntot * 16);
+    const size_t o_pdn = H.take((size_t)ntot * 24), o_smp = H.take((size_t)S * iters * 12), o_out = H.take((size_t)S * 256), o_inl = H.take((size_t)ntot);
     char *h, *d;
-    int rc = slam_pinned(ctx, total, (void **)&h);
+    int rc = slam_pinned(ctx, H.size(), (void **)&h);
     if (rc) return rc;
     HIP_TRY(ctx, hipHostGetDevicePointer((void **)&d, h, 0));
     memcpy(h + o_off, off, (size_t)(S + 1) * 4); memcpy(h + o_K, K, (size_t)S * 72);
     memcpy(h + o_pts, pts3d, (size_t)ntot * 24); memcpy(h + o_px, px_xy, (size_t)ntot * 16); memcpy(h + o_pdn, pdn, (size_t)ntot * 24);
     memcpy(h + o_smp, samples, (size_t)S * iters * 12);
-    const size_t s_cnt = up((size_t)S * iters * 16), s_pose = up((size_t)S * iters * 4 * 96), s_err = up((size_t)ntot * 8);
+    Layout D;
+    const P3PScratch ds(D, S, iters, (size_t)ntot);
     char *scr;
-    rc = slam_scratch(ctx, s_cnt + s_pose + s_err, (void **)&scr);
+    rc = slam_scratch(ctx, D.size(), (void **)&scr);
     if (rc) return rc;
     P3PArgs T;
     T.pts = (const double *)(d + o_pts); T.px = (const double *)(d + o_px); T.pdn = (const double *)(d + o_pdn);
     T.samples = (const int32_t *)(d + o_smp); T.off = (const int *)(d + o_off); T.Ks = (const double *)(d + o_K);
     T.iters = iters; T.thr = threshold; T.cnt = nullptr; T.stride = 0;
-    T.counts = (int *)scr; T.poses = (double *)(scr + s_cnt); T.errs = (double *)(scr + s_cnt + s_pose);
+    ds.bind(T, scr);
     T.out = (double *)(d + o_out); T.inliers = (uint8_t *)(d + o_inl);
     { ProfScope span(ctx, "p3p_ransac");
-      hipLaunchKernelGGL(k_p3p_score, dim3(iters, S), dim3(64), 0, ctx->stream, T);
-      hipLaunchKernelGGL(k_p3p_select, dim3(S), dim3(256), 0, ctx->stream, T); }
+      p3p_enqueue(ctx, S, T); }
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, slam_stream_wait(ctx->stream));
     for (int z = 0; z < S; z++) {
@@ -370,6 +355,19 @@ static int p3p_run(slam_ctx *ctx, int S, const int32_t *off, const double *pts3d
     return SLAM_OK;
 }
 
+// "p3p_ransac returned nothing": zero pose, zero mask, no inliers, best_iter = -1 for each of the S problems
+static int p3p_empty(int S, int ntot, double *KP, double *Rt, uint8_t *inliers, int *n_inliers, double *error, int *best_iter)
+{
+    for (int z = 0; z < S; z++) {
+        n_inliers[z] = 0;
+        for (int j = 0; j < 12; j++) { KP[12 * z + j] = 0.0; if (Rt) Rt[12 * z + j] = 0.0; }
+        if (error) error[z] = 0.0;
+        if (best_iter) best_iter[z] = -1;
+    }
+    for (int i = 0; i < ntot; i++) inliers[i] = 0;
+    return SLAM_OK;
+}
+
 extern "C" int slam_p3p_ransac(slam_ctx *ctx, const double *pts3d, const double *px_xy, const double *pdn, int n,
                                const double *K, double threshold, const int32_t *samples, int iters,
                                double *KP, double *Rt, uint8_t *inliers, int *n_inliers, double *error, int *best_iter)
@@ -378,14 +376,7 @@ extern "C" int slam_p3p_ransac(slam_ctx *ctx, const double *pts3d, const double 
     ARG_TRY(ctx, K && KP && n_inliers);
     ARG_TRY(ctx, n == 0 || (pts3d && px_xy && pdn && inliers));
     ARG_TRY(ctx, iters == 0 || samples);
-    if (n < 3 || iters == 0) {                 // nothing to sample from: "p3p_ransac returned nothing"
-        *n_inliers = 0;
-        for (int j = 0; j < 12; j++) { KP[j] = 0.0; if (Rt) Rt[j] = 0.0; }
-        for (int i = 0; i < n; i++) inliers[i] = 0;
-        if (error) *error = 0.0;
-        if (best_iter) *best_iter = -1;
-        return SLAM_OK;
-    }
+    if (n < 3 || iters == 0) return p3p_empty(1, n, KP, Rt, inliers, n_inliers, error, best_iter);      // nothing to sample from
     const int32_t off[2] = {0, n};
     return p3p_run(ctx, 1, off, pts3d, px_xy, pdn, K, threshold, samples, iters, KP, Rt, inliers, n_inliers, error, best_iter);
 }
@@ -401,16 +392,7 @@ extern "C" int slam_p3p_ransac_batch(slam_ctx *ctx, int S, const int32_t *offset
     const int ntot = offsets[S];
     ARG_TRY(ctx, ntot == 0 || (pts3d && px_xy && pdn && inliers));
     ARG_TRY(ctx, iters == 0 || samples);
-    if (ntot == 0 || iters == 0) {
-        for (int z = 0; z < S; z++) {
-            n_inliers[z] = 0;
-            for (int j = 0; j < 12; j++) { KP[12 * z + j] = 0.0; if (Rt) Rt[12 * z + j] = 0.0; }
-            if (error) error[z] = 0.0;
-            if (best_iter) best_iter[z] = -1;
-        }
-        for (int i = 0; i < ntot; i++) inliers[i] = 0;
-        return SLAM_OK;
-    }
+    if (ntot == 0 || iters == 0) return p3p_empty(S, ntot, KP, Rt, inliers, n_inliers, error, best_iter);
     return p3p_run(ctx, S, offsets, pts3d, px_xy, pdn, K, threshold, samples, iters, KP, Rt, inliers, n_inliers, error, best_iter);
 }
 
@@ -436,38 +418,13 @@ struct KPoseArgs {
     double *poses; int *status, *ninl; // S x 16 (column-major Tcw), S, S
 };
 
-__device__ __forceinline__ unsigned long long splitmix64(unsigned long long x)
-{
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-
-// ordered compaction of a stream's flagged elements: returns this thread's output position (or -1), advances *base
-__device__ __forceinline__ int ordered_slot(bool take, int *s_w, int *s_base)
-{
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const unsigned long long m = __ballot(take);
-    const int before = __popcll(m & ((1ull << lane) - 1ull));
-    if (lane == 0) s_w[wv] = __popcll(m);
-    __syncthreads();
-    int off = *s_base;
-    for (int w = 0; w < wv; w++) off += s_w[w];
-    const int pos = take ? off + before : -1;
-    __syncthreads();
-    if (tid == 0) *s_base += s_w[0] + s_w[1] + s_w[2] + s_w[3];
-    __syncthreads();
-    return pos;
-}
-
 __global__ __launch_bounds__(256) void k_kpose_gather(KPoseArgs A)
 {
     __shared__ int s_w[4], s_base;
     const int z = blockIdx.x, tid = threadIdx.x, n = A.count[z];
     const size_t b = (size_t)z * A.cap;
-    const double fx = A.par[32 * z + 16], fy = A.par[32 * z + 17], cx = A.par[32 * z + 18], cy = A.par[32 * z + 19];
-    const double k1 = A.par[32 * z + 20], k2 = A.par[32 * z + 21], p1 = A.par[32 * z + 22], p2 = A.par[32 * z + 23];
+    const double *par = A.par + 32 * (size_t)z;
+    const double cam[4] = {par[16], par[17], par[18], par[19]}, dist[4] = {par[20], par[21], par[22], par[23]};
     if (tid == 0) s_base = 0;
     __syncthreads();
     for (int c0 = 0; c0 < n; c0 += 256) {
@@ -477,13 +434,9 @@ __global__ __launch_bounds__(256) void k_kpose_gather(KPoseArgs A)
         if (take) {
             const size_t q = b + j, o = b + pos;
             // undistort_point (camera.jl:98-125) -> undistorted_pixel (y, x); backproject (:138-140) -> position; normalize
-            const double ny = (A.yx[2 * q] - cy) / fy, nx = (A.yx[2 * q + 1] - cx) / fx;
-            const double s0 = ny * ny, s1 = nx * nx, r2 = s0 + s1;
-            const double rd = (1.0 + k1 * r2) + k2 * (r2 * r2);
-            const double pp = ny * nx;
-            const double dtx = 2 * p1 * pp + p2 * (r2 + 2 * s0), dty = p1 * (r2 + 2 * s1) + 2 * p2 * pp;
-            const double uy = (rd * ny + dty) * fy + cy, ux = (rd * nx + dtx) * fx + cx;
-            const double bx = (ux - cx) / fx, by = (uy - cy) / fy;
+            double uy, ux;
+            undistort_px(cam, dist, A.yx[2 * q], A.yx[2 * q + 1], uy, ux);
+            const double bx = (ux - cam[2]) / cam[0], by = (uy - cam[3]) / cam[1];
             const double inv = 1.0 / sqrt((bx * bx + by * by) + 1.0);
             A.px[2 * o] = ux; A.px[2 * o + 1] = uy;                                   // (x, y), front_end.jl:151
             A.pdn[3 * o] = inv * bx; A.pdn[3 * o + 1] = inv * by; A.pdn[3 * o + 2] = inv * 1.0;
@@ -501,17 +454,8 @@ __global__ __launch_bounds__(256) void k_kpose_samples(KPoseArgs A)
     const int n = A.n3[z];
     int32_t *sm = A.samples + 3 * ((size_t)z * A.iters + it);
     if (n < 5) { sm[0] = sm[1] = sm[2] = -1; return; }              // front_end.jl:133-136: fewer than 5 3-D keypoints -> no P3P
-    int idx[3]; unsigned att = 0;
-    for (int k = 0; k < 3; k++) {
-        for (;;) {
-            const unsigned long long h = splitmix64(A.seed ^ ((unsigned long long)z << 48) ^ ((unsigned long long)it << 16) ^ (unsigned long long)att);
-            att++;
-            const int c = (int)(h % (unsigned long long)n);
-            bool dup = false;
-            for (int m = 0; m < k; m++) dup = dup || idx[m] == c;
-            if (!dup) { idx[k] = c; break; }
-        }
-    }
+    int idx[3];
+    draw_distinct<3>(A.seed, z, it, n, idx);
     sm[0] = idx[0]; sm[1] = idx[1]; sm[2] = idx[2];
 }
 
@@ -596,17 +540,17 @@ extern "C" int slam_kpset_compute_pose(slam_ctx *ctx, slam_kpset *ks, const doub
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int S = ks->S, cap = ks->cap;
     const size_t nc = (size_t)S * cap;
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    // scratch layout
-    size_t o = 0;
-    auto take = [&](size_t bytes) { const size_t at = o; o += up(bytes); return at; };
-    const size_t o_pts = take(nc * 24), o_px = take(nc * 16), o_pdn = take(nc * 24), o_slot = take(nc * 4), o_n3 = take((size_t)S * 4);
-    const size_t o_smp = take((size_t)S * iters * 12), o_cnt = take((size_t)S * iters * 16), o_pose = take((size_t)S * iters * 4 * 96);
-    const size_t o_err = take(nc * 8), o_out = take((size_t)S * 256), o_inl = take(nc);
-    const size_t o_bpx = take(nc * 16), o_bpts = take(nc * 24), o_bslot = take(nc * 4), o_outl = take(nc), o_pnp = take((size_t)S * sizeof(PnPArgs));
-    const size_t o_res = take((size_t)S * 128), o_flags = take(nc), o_T = take((size_t)S * 128), o_st = take((size_t)S * 4), o_ni = take((size_t)S * 4);
+    Layout D;                          // device scratch
+    const size_t o_pts = D.take(nc * 24), o_px = D.take(nc * 16), o_pdn = D.take(nc * 24), o_slot = D.take(nc * 4), o_n3 = D.take((size_t)S * 4);
+    const size_t o_smp = D.take((size_t)S * iters * 12);
+    const P3PScratch ds(D, S, iters, nc);
+    const size_t o_out = D.take((size_t)S * 256), o_inl = D.take(nc);
+    const size_t o_bpx = D.take(nc * 16), o_bpts = D.take(nc * 24), o_bslot = D.take(nc * 4), o_outl = D.take(nc), o_pnp = D.take((size_t)S * sizeof(PnPArgs));
+    const size_t o_res = D.take((size_t)S * 128), o_flags = D.take(nc), o_T = D.take((size_t)S * 128), o_st = D.take((size_t)S * 4), o_ni = D.take((size_t)S * 4);
+    Layout H;                          // pinned host block: K per stream (read by the kernels), then the results
+    const size_t h_K = H.take((size_t)S * 72), h_T = H.take((size_t)S * 128), h_st = H.take((size_t)S * 4), h_ni = H.take((size_t)S * 4), h_cn = H.take((size_t)S * 4);
     char *scr;
-    int rc = slam_scratch2(ctx, o, (void **)&scr);
+    int rc = slam_scratch2(ctx, D.size(), (void **)&scr);
     if (rc) return rc;
     const double *par_dev;
     rc = kpset_stage_params(ctx, ks, params, (size_t)S * 32, &par_dev);
@@ -622,30 +566,24 @@ extern "C" int slam_kpset_compute_pose(slam_ctx *ctx, slam_kpset *ks, const doub
     A.flags = (uint8_t *)(scr + o_flags); A.poses = (double *)(scr + o_T); A.status = (int *)(scr + o_st); A.ninl = (int *)(scr + o_ni);
     P3PArgs T;
     T.pts = A.pts; T.px = A.px; T.pdn = A.pdn; T.samples = A.samples; T.off = nullptr; T.cnt = A.n3; T.stride = cap;
-    T.Ks = nullptr; T.iters = iters; T.thr = threshold;
-    T.counts = (int *)(scr + o_cnt); T.poses = (double *)(scr + o_pose); T.errs = (double *)(scr + o_err);
+    T.iters = iters; T.thr = threshold;
+    ds.bind(T, scr);
     T.out = A.p3p_out; T.inliers = A.inl;
-    // K per stream (column-major 3 x 3) goes with the parameters: built on the host, staged like them
-    {
-        double *Kh; void *hv;
-        rc = slam_pinned(ctx, up((size_t)S * 72) + up((size_t)S * 128) + 3 * up((size_t)S * 4), &hv);
-        if (rc) return rc;
-        Kh = (double *)hv;
-        for (int z = 0; z < S; z++) {
-            double *K = Kh + 9 * z;
-            for (int j = 0; j < 9; j++) K[j] = 0.0;
-            K[0] = params[32 * z + 16]; K[4] = params[32 * z + 17]; K[6] = params[32 * z + 18]; K[7] = params[32 * z + 19]; K[8] = 1.0;
-        }
-        double *Kd;
-        HIP_TRY(ctx, hipHostGetDevicePointer((void **)&Kd, Kh, 0));
-        T.Ks = Kd;
+    // K per stream (column-major 3 x 3) goes with the parameters: built on the host, read through the mapped block
+    char *h;
+    rc = slam_pinned(ctx, H.size(), (void **)&h);
+    if (rc) return rc;
+    for (int z = 0; z < S; z++) {
+        double *K = (double *)(h + h_K) + 9 * z;
+        for (int j = 0; j < 9; j++) K[j] = 0.0;
+        K[0] = params[32 * z + 16]; K[4] = params[32 * z + 17]; K[6] = params[32 * z + 18]; K[7] = params[32 * z + 19]; K[8] = 1.0;
     }
+    HIP_TRY(ctx, hipHostGetDevicePointer((void **)&T.Ks, h + h_K, 0));
     HIP_TRY(ctx, hipMemsetAsync(A.flags, 0, nc, ctx->stream));
     { ProfScope span(ctx, "kpset_compute_pose");
       hipLaunchKernelGGL(k_kpose_gather, dim3(S), dim3(256), 0, ctx->stream, A);
       hipLaunchKernelGGL(k_kpose_samples, dim3((iters + 255) / 256, S), dim3(256), 0, ctx->stream, A);
-      hipLaunchKernelGGL(k_p3p_score, dim3(iters, S), dim3(64), 0, ctx->stream, T);
-      hipLaunchKernelGGL(k_p3p_select, dim3(S), dim3(256), 0, ctx->stream, T);
+      p3p_enqueue(ctx, S, T);
       hipLaunchKernelGGL(k_kpose_prep, dim3(S), dim3(256), 0, ctx->stream, A);
       rc = pnp_launch_device(ctx, S, A.pnp);
       if (rc) return rc;
@@ -654,18 +592,14 @@ extern "C" int slam_kpset_compute_pose(slam_ctx *ctx, slam_kpset *ks, const doub
     rc = kpset_compact(ctx, ks, 1, A.flags);
     if (rc) return rc;
     // results: poses, status, inlier counts, list lengths -- one wait
-    void *hv;
-    rc = slam_pinned(ctx, up((size_t)S * 72) + up((size_t)S * 128) + 3 * up((size_t)S * 4), &hv);     // same block as above (K first)
-    if (rc) return rc;
-    char *h = (char *)hv + up((size_t)S * 72);
-    HIP_TRY(ctx, hipMemcpyAsync(h, A.poses, (size_t)S * 128, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(h + up((size_t)S * 128), A.status, (size_t)S * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(h + up((size_t)S * 128) + up((size_t)S * 4), A.ninl, (size_t)S * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(h + up((size_t)S * 128) + 2 * up((size_t)S * 4), ks->count, (size_t)S * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(h + h_T, A.poses, (size_t)S * 128, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(h + h_st, A.status, (size_t)S * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(h + h_ni, A.ninl, (size_t)S * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(h + h_cn, ks->count, (size_t)S * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, slam_stream_wait(ctx->stream));
-    memcpy(poses_cw, h, (size_t)S * 128);
-    memcpy(status, h + up((size_t)S * 128), (size_t)S * 4);
-    if (n_inliers) memcpy(n_inliers, h + up((size_t)S * 128) + up((size_t)S * 4), (size_t)S * 4);
-    if (counts) memcpy(counts, h + up((size_t)S * 128) + 2 * up((size_t)S * 4), (size_t)S * 4);
+    memcpy(poses_cw, h + h_T, (size_t)S * 128);
+    memcpy(status, h + h_st, (size_t)S * 4);
+    if (n_inliers) memcpy(n_inliers, h + h_ni, (size_t)S * 4);
+    if (counts) memcpy(counts, h + h_cn, (size_t)S * 4);
     return SLAM_OK;
 }
