@@ -101,7 +101,8 @@ struct slam_kpset {
     int64_t *id = nullptr;       // [S cap] keypoint id (per stream, ascending in creation order)
     uint8_t *is3d = nullptr, *stereo = nullptr, *st = nullptr;   // flags; st: status of the last match (0 lost, 1 tracked, 2 skipped)
     int *count = nullptr;        // [S]
-    int *work = nullptr;         // [S cap] live slots, streams back to back
+    int *work = nullptr;         // [S cap] live slots, streams back to back (each stream's segment in the order of work_order.hpp)
+    int sort_pad = 0;            // power of two >= cap the work list's sort pads a segment to; 0: slot order (decided at creation)
     int *ntot = nullptr;         // [4]: number of live slots, ...
     int64_t *next_id = nullptr;  // [S]
     // per-stream parameters of a call (prior shift / pose): ring of 8 slots of S x 32 doubles, staged through pinned host
@@ -166,7 +167,7 @@ struct PnPArgs {
 int pnp_launch_device(slam_ctx *ctx, int S, const PnPArgs *args_dev);     // S problems, argument blocks already in device memory
 
 // kpset plumbing shared by kpset.hip / lk.hip / detect.hip
-int kpset_build_worklist(slam_ctx *ctx, slam_kpset *ks);
+int kpset_build_worklist(slam_ctx *ctx, slam_kpset *ks, int H, int W);   // H <= 0: slot order (no image, or an order would not pay)
 int kpset_compact(slam_ctx *ctx, slam_kpset *ks, int mode, const uint8_t *flags_dev);
 // per-module entry points used across files
 int slam_detect_device(slam_ctx *ctx, const double *img_dev, int H, int W, int pitch, const double *cur_yx, int n_cur,

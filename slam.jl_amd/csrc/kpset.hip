@@ -11,30 +11,63 @@
 #include "common.hpp"
 #include <algorithm>
 #include "geom_device.hpp"
+#include "work_order.hpp"
 #include <cmath>
 
 // live slots of all streams back to back + their number.  One small workgroup per stream (it sums the counts before its own: S
 // loads): a single 1024-thread workgroup had to wait for sixteen free wave slots on one CU while the pyramid kernels fill the chip
 // (58 us on average in the pipeline for 12 us of work).
-__global__ __launch_bounds__(256) void k_kpset_worklist(const int *count, int S, int cap, int *work, int *ntot)
+// Stream s's segment [off_s, off_s + count_s) holds its live slots; O.band > 0 sorts them by work_key (x-band, row, slot:
+// work_order.hpp) with a bitonic network in LDS over the segment padded to a power of two with maximal words -- lists are queues
+// of many detect generations (stable compaction, new keypoints appended behind), so slot order is not a spatial order.  Every wave
+// sums the counts itself (S loads, no barrier); the sort's words are (key << 32 | slot), all different.
+// SLAMHIP_WORK_BAND, read once per process: the band width in pixels, 0 = slot order (the lists as they are); default WORK_BAND_PX.
+// KPSET_SORT_LDS_BYTES is the sort's LDS budget (what a workgroup gets without asking for more): a set whose capacity, padded to a
+// power of two, does not fit keeps slot order -- slam_kpset_create decides that once (sort_pad).
+#define WORK_BAND_PX 16
+#define KPSET_SORT_LDS_BYTES 65536
+static int work_band() { static const int band = [] { const char *v = getenv("SLAMHIP_WORK_BAND"); const int b = v ? atoi(v) : WORK_BAND_PX; return b < 0 ? 0 : b; }(); return band; }
+struct WorkOrder { int H, W, band, pad; };       // band 0: slot order; pad: power of two >= cap whose words fit KPSET_SORT_LDS_BYTES
+__global__ __launch_bounds__(256) void k_kpset_worklist(const int *count, int S, int cap, int *work, int *ntot, const double *yx, WorkOrder O)
 {
-    __shared__ int s_off;
-    const int s = blockIdx.x, tid = threadIdx.x;
-    if (tid < 64) {
-        int c = 0, t = 0;
-        for (int i = tid; i < S; i += 64) { const int v = count[i]; t += v; c += i < s ? v : 0; }
+    extern __shared__ unsigned long long s_word[];
+    const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    int off = 0, t = 0;
+    for (int i = lane; i < S; i += 64) { const int v = count[i]; t += v; off += i < s ? v : 0; }
 #pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) { c += __shfl_xor(c, m); t += __shfl_xor(t, m); }
-        if (tid == 0) { s_off = c; if (s == 0) ntot[0] = t; }
+    for (int m = 32; m >= 1; m >>= 1) { off += __shfl_xor(off, m); t += __shfl_xor(t, m); }
+    if (s == 0 && tid == 0) ntot[0] = t;
+    const int n = count[s];
+    if (O.band <= 0 || n > O.pad) {                              // (n > pad cannot happen: n <= cap <= pad; it guards the LDS array)
+        for (int j = tid; j < n; j += 256) work[off + j] = s * cap + j;
+        return;
     }
+    int P = 1;
+    while (P < n) P <<= 1;
+    const double *p = yx + 2 * (size_t)s * cap;
+    for (int j = tid; j < P; j += 256)
+        s_word[j] = j < n ? ((unsigned long long)work_key(p[2 * j], p[2 * j + 1], O.H, O.W, O.band) << 32) | (unsigned)j : ~0ull;
     __syncthreads();
-    const int off = s_off, n = count[s];
-    for (int j = tid; j < n; j += 256) work[off + j] = s * cap + j;
+    for (int k = 2; k <= P; k <<= 1)
+        for (int d = k >> 1; d > 0; d >>= 1) {
+            for (int u = tid; u < (P >> 1); u += 256) {
+                const int i = ((u & ~(d - 1)) << 1) | (u & (d - 1));             // the lower index of the u-th pair at distance d
+                const unsigned long long a = s_word[i], c = s_word[i + d];
+                if ((a > c) == ((i & k) == 0)) { s_word[i] = c; s_word[i + d] = a; }
+            }
+            __syncthreads();
+        }
+    for (int j = tid; j < n; j += 256) work[off + j] = s * cap + (int)(unsigned)s_word[j];
 }
 
-int kpset_build_worklist(slam_ctx *ctx, slam_kpset *ks)
+// H x W: the image the positions live in (the match that follows reads its planes); H <= 0: slot order -- the triangulation
+// kernels read a few bytes per keypoint and gain nothing from an order
+int kpset_build_worklist(slam_ctx *ctx, slam_kpset *ks, int H, int W)
 {
-    hipLaunchKernelGGL(k_kpset_worklist, dim3(ks->S), dim3(256), 0, ctx->stream, (const int *)ks->count, ks->S, ks->cap, ks->work, ks->ntot);
+    WorkOrder O;
+    O.H = H; O.W = W; O.pad = ks->sort_pad; O.band = H > 0 && W > 0 && ks->sort_pad > 0 ? work_band() : 0;
+    const size_t lds = O.band > 0 ? (size_t)ks->sort_pad * 8 : 0;
+    hipLaunchKernelGGL(k_kpset_worklist, dim3(ks->S), dim3(256), lds, ctx->stream, (const int *)ks->count, ks->S, ks->cap, ks->work, ks->ntot, (const double *)ks->yx, O);
     HIP_TRY(ctx, hipGetLastError());
     return SLAM_OK;
 }
@@ -140,6 +173,8 @@ __device__ __forceinline__ void k_kpset_triangulate_slot(const KpsetView &K, con
     } else K.stereo[q] = 0;
 }
 // (the grid is sized from the host's bound of the list lengths, which is only a hint: the loop covers every live slot whatever it was)
+// One work-list entry per thread and iteration; k_kpset_triangulate_slot reads and writes slot q = work[i] alone (xyz, is3d, stereo
+// of q), so any permutation of a stream's segment gives the same lists.
 __global__ __launch_bounds__(64) void k_kpset_triangulate(KpsetView K, KTriArgs T, const int *work, const int *ntot)
 {
     const int n = ntot[0];
@@ -190,6 +225,8 @@ __device__ __forceinline__ void k_kpset_tri_temporal_slot(const KpsetView &K, co
     } else T.flags[q] = 1;                                        // remove_mappoint_obs!(map_manager, id, frame.kfid)
 }
 // (the grid is sized from the host's bound of the list lengths, which is only a hint: the loop covers every live slot whatever it was)
+// One work-list entry per thread and iteration; k_kpset_tri_temporal_slot writes xyz, is3d and flags of slot q = work[i] alone: the
+// order of the work list does not matter here either.
 __global__ __launch_bounds__(64) void k_kpset_tri_temporal(KpsetView K, KTempArgs T, const int *work, const int *ntot)
 {
     const int n = ntot[0];
@@ -211,6 +248,7 @@ int slam_kpset_create(slam_ctx *ctx, int S, int cap, slam_kpset **out)
     const size_t o_nid = Lo.take((size_t)S * 8), o_par = Lo.take((size_t)8 * S * 32 * 8), o_kyx = Lo.take(n * 16), o_hk = Lo.take(n), o_fyx = Lo.take(n * 16), o_fkf = Lo.take(n * 4), o_kfc = Lo.take((size_t)S * 4);
     slam_kpset *ks = new slam_kpset();
     ks->device = ctx->device; ks->S = S; ks->cap = cap;
+    { size_t pad = 1; while (pad < (size_t)cap) pad <<= 1; ks->sort_pad = work_band() > 0 && pad * 8 <= KPSET_SORT_LDS_BYTES ? (int)pad : 0; }
     hipError_t e = hipMalloc((void **)&ks->base, Lo.size());
     if (e == hipSuccess) e = hipMemsetAsync(ks->base, 0, Lo.size(), ctx->stream);
     if (e == hipSuccess) e = slam_stream_wait(ctx->stream);
@@ -237,6 +275,21 @@ int slam_kpset_destroy(slam_kpset *ks)
     if (ks->par_host) (void)hipHostFree(ks->par_host);
     for (int i = 0; i < 8; i++) if (ks->par_ev[i]) (void)hipEventDestroy(ks->par_ev[i]);
     delete ks;
+    return SLAM_OK;
+}
+
+// Test-only (not part of include/slamhip.h): build the work list for an H x W image (H <= 0: slot order) and copy it out --
+// work_out S x cap ints (the first *ntot_out are the list), band_out the band width in use (0: slot order for this set).
+int slamhip_test_kpset_worklist(slam_ctx *ctx, slam_kpset *ks, int H, int W, int *work_out, int *ntot_out, int *band_out)
+{
+    ARG_TRY(ctx, ctx != nullptr && ks != nullptr && work_out != nullptr && ntot_out != nullptr && band_out != nullptr);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc = kpset_build_worklist(ctx, ks, H, W);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(work_out, ks->work, (size_t)ks->S * ks->cap * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ntot_out, ks->ntot, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, slam_stream_wait(ctx->stream));
+    *band_out = H > 0 && W > 0 && ks->sort_pad > 0 ? work_band() : 0;
     return SLAM_OK;
 }
 
@@ -408,7 +461,7 @@ int slam_kpset_triangulate(slam_ctx *ctx, slam_kpset *ks, const double *P1, cons
     T.max_error = max_error; T.min_depth = min_depth;
     int rc = kpset_stage_params(ctx, ks, Twc, (size_t)ks->S * 16, &T.Twc);
     if (rc) return rc;
-    rc = kpset_build_worklist(ctx, ks);
+    rc = kpset_build_worklist(ctx, ks, 0, 0);
     if (rc) return rc;
     const int nb = n_bound > 0 && n_bound < ks->S * ks->cap ? n_bound : ks->S * ks->cap;
     hipLaunchKernelGGL(k_kpset_triangulate, dim3((nb + 63) / 64), dim3(64), 0, ctx->stream, view_of(ks), T, (const int *)ks->work, (const int *)ks->ntot);
@@ -440,7 +493,7 @@ int slam_kpset_triangulate_temporal(slam_ctx *ctx, slam_kpset *ks, const double 
     T.max_error = max_error; T.min_depth = min_depth; T.min_parallax = min_parallax;
     T.flags = (uint8_t *)(scr + o_fl);
     HIP_TRY(ctx, hipMemsetAsync(T.flags, 0, nc, ctx->stream));
-    rc = kpset_build_worklist(ctx, ks);
+    rc = kpset_build_worklist(ctx, ks, 0, 0);
     if (rc) return rc;
     const int nb = n_bound > 0 && n_bound < S * ks->cap ? n_bound : S * ks->cap;
     hipLaunchKernelGGL(k_kpset_tri_temporal, dim3((nb + 63) / 64), dim3(64), 0, ctx->stream, view_of(ks), T, (const int *)ks->work, (const int *)ks->ntot);

@@ -464,8 +464,13 @@ __device__ __forceinline__ bool fb_point(const PyrView &prev, const PyrView &cur
 }
 
 // Workgroups are dealt round-robin to the 8 XCDs (workgroup b runs on XCD b % 8) and every XCD has its own L2.
-// Keypoint lists are spatially ordered (grid cells, row-major), and neighbouring points share cache lines of
-// their windows: give each XCD one contiguous eighth of the list instead of every eighth point.
+// Neighbouring points share cache lines of their windows when they run close together in time on one XCD: give each XCD
+// one contiguous eighth of the list instead of every eighth point.  What "contiguous" buys depends on the list's order:
+//  * a slam_kpset work list (k_kpset_worklist, kpset.hip) holds every stream's live slots sorted by (x-band, row, slot) --
+//    work_order.hpp -- so consecutive entries are neighbours along y, the direction in which a 128-byte line runs; the
+//    lists themselves are NOT spatially ordered (stable compaction + appended detections: a queue of detect generations,
+//    each a sparse cell-row-major sample of the image), which is the order SLAMHIP_WORK_BAND=0 walks;
+//  * the host lists of slam_fb_track / slam_flow_match* come in the caller's order (a fresh detect: grid cells, row-major).
 #define LK_XCDS 8
 __device__ __forceinline__ int xcd_point(int n)
 {
@@ -554,7 +559,7 @@ template <int LK_MAXE, bool TOL>
 __global__ __launch_bounds__(64) LK_OCC void k_kpset_match(KpMatchArgs M)
 {
     const int ntot = M.ntot[0], per = (ntot + LK_XCDS - 1) / LK_XCDS;
-    // each XCD a contiguous eighth of the (spatially ordered) list.  The grid is sized from the host's bound of the list lengths,
+    // each XCD a contiguous eighth of the work list (streams back to back, each sorted by x-band and row).  The grid is sized from the host's bound of the list lengths,
     // which is only a hint: a launch smaller than the lists walks them in several rounds (a keypoint that no wave visited would keep
     // the previous call's status and be compacted away or kept from stale data)
     for (int slotx = (int)(blockIdx.x / LK_XCDS); slotx < per; slotx += (int)(gridDim.x / LK_XCDS)) {
@@ -631,7 +636,7 @@ static int kpset_match(slam_ctx *ctx, slam_kpset *ks, const slam_pyr *from0, con
     if (!params) { zero.assign((size_t)ks->S * 32, 0.0); for (int s = 0; s < ks->S; s++) { zero[32 * s + 16] = zero[32 * s + 17] = 1.0; } params = zero.data(); }
     int rc = kpset_stage_params(ctx, ks, params, (size_t)ks->S * 32, &M.par);
     if (rc) return rc;
-    rc = kpset_build_worklist(ctx, ks);
+    rc = kpset_build_worklist(ctx, ks, M.H, M.W);
     if (rc) return rc;
     const int nmax = ks->S * ks->cap;
     int nb = n_bound > 0 && n_bound < nmax ? n_bound : nmax;

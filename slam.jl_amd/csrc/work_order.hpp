@@ -1,0 +1,37 @@
+// work_order.hpp -- the order in which the tracking kernel visits a stream's keypoints (k_kpset_worklist, kpset.hip).
+//
+// Planes are column-major (a 128-byte line holds 16 rows of one column), and every keypoint's window is one wave's work in
+// k_kpset_match: two keypoints share lines of their windows when they are close in x AND their rows overlap, and they share
+// them in L2 only when they run close together in time.  The work list is therefore sorted by
+//     (x-band, row, slot)        x-band = floor(x) / band  (band in pixels),  row = floor(y)
+// so that a stream's segment walks the image band by band, top to bottom.  Ties end on the slot index: the order is a pure
+// function of the list.  Shared by the kernel, the host (the stand-alone check tests/c_host/work_key_check.cpp) and nothing else.
+#pragma once
+#include <cstdint>
+
+// (both branches are built: the library by hipcc, the stand-alone check by the host compiler alone)
+#if defined(__HIPCC__)
+#define WORK_HD __host__ __device__ __forceinline__
+#else
+#define WORK_HD static inline
+#endif
+
+// largest pixel coordinate a key distinguishes: both fields of the key are 16 bits wide
+#define WORK_KEY_MAX_PX 65535
+
+// floor(v) clamped to [0, hi] without ever converting a value an int cannot hold (that conversion is undefined behaviour):
+// NaN -> hi (such keypoints sort last in their field), -inf and everything below 1 -> 0, +inf and everything from hi on -> hi.
+WORK_HD uint32_t work_clamp_px(double v, int hi)
+{
+    const uint32_t top = (uint32_t)(hi < 0 ? 0 : hi > WORK_KEY_MAX_PX ? WORK_KEY_MAX_PX : hi);
+    if (v != v) return top;
+    if (!(v >= 1.0)) return 0;
+    if (v >= (double)top) return top;
+    return (uint32_t)v;                                          // 1 <= v < top <= 65535
+}
+
+// the sort key of a keypoint at (y, x) in an H x W image; band >= 1
+WORK_HD uint32_t work_key(double y, double x, int H, int W, int band)
+{
+    return ((work_clamp_px(x, W) / (uint32_t)(band < 1 ? 1 : band)) << 16) | work_clamp_px(y, H);
+}
