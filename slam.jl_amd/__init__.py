@@ -12,7 +12,7 @@ from .params import Camera, Params  # noqa: F401
 from .extractor import Extractor, detect, detect_batch, describe, brief_pattern  # noqa: F401
 from .optical_flow import (LKPyramid, LucasKanade, update_, copy_, deepcopy, has_gradients, fb_tracking_,  # noqa: F401
                            optical_flow_matching, optical_flow_matching_frame, PyramidBatch, optical_flow_matching_batch,
-                           optical_flow_matching_batch_kept)
+                           optical_flow_matching_batch_kept, pyr_route)
 from .bundle_adjustment import LocalBACache, bundle_adjustment_, bundle_adjustment_batch_, BABatch, ba_plan_order, pnp_bundle_adjustment, pnp_bundle_adjustment_batch  # noqa: F401
 from .triangulation import triangulate, projection_matrices  # noqa: F401
 from .local_map import local_map_matching, local_map_matching_batch, local_map_matching_packed, pack_local_map, concat_packs, LocalMapArgs  # noqa: F401

@@ -2445,6 +2445,16 @@ static LevelRoute level_route(const slam_pyr *p, int mode, int l, int S, int Sal
     else r.cum = CUM_LINES;
     return r;
 }
+// Test hook (not in include/slamhip.h): the route a build of S images in `mode` (0 / 1 / 3; target_only: SLAM_PYR_TARGET_ONLY) takes at
+// `level`, into a graph sink with lanes -- family, cols, rows, resize, cum, rt_sl, rt_ns, dec, slc32, slc, slr, fuse_sq.  Launches and allocates nothing.
+extern "C" int slam_debug_pyr_route(const slam_pyr *p, int mode, int S, int target_only, int level, int out[12])
+{
+    if (!p || !out || (mode != 0 && mode != 1 && mode != 3) || S < 1 || S > BATCH_MAX || level < 0 || level >= p->levels) return SLAM_ERR_ARG;
+    const LevelRoute r = level_route(p, mode, level, S, S, target_only != 0, true);
+    const int v[12] = {r.family, r.cols, r.rows, r.resize, r.cum, r.rt_sl, r.rt_ns, r.dec ? 1 : 0, r.slc32, r.slc, r.slr, r.fuse_sq ? 1 : 0};
+    memcpy(out, v, sizeof v);
+    return SLAM_OK;
+}
 // ---- What a level's kernels read and write, for the images [z0, z0 + S) of a batch of Sall
 struct LevelIO {
     int H, W, P; LevelView v; double *T;   // the level's planes, the blur scratch plane

@@ -252,6 +252,26 @@ class PyramidBatch:
         return self
 
 
+ROUTE_FIELDS = ("family", "cols", "rows", "resize", "cum", "rt_sl", "rt_ns", "dec", "slc32", "slc", "slr", "fuse_sq")
+ROUTE_ENUMS = {"family": ("FAM_NONE", "FAM_TARGET", "FAM_SEG", "FAM_TOLB", "FAM_EXACT"),
+               "cols": ("COLS_LINE", "COLS_CK", "COLS_FUSED", "COLS_SEG"),
+               "rows": ("ROWS_LINE", "ROWS_CK", "ROWS_SEG", "ROWS_TOL"),
+               "resize": ("RZ_NONE", "RZ_PLAIN", "RZ_EVEN", "RZ_ODD"),
+               "cum": ("CUM_NONE", "CUM_ROWS_CUM", "CUM_FUSED", "CUM_FUSED_SEG", "CUM_LINES", "CUM_SEG")}
+
+
+def pyr_route(pyr_or_batch, mode, S, level, target_only=False):
+    """The kernel route a build of S images in `mode` (0, 1, or 3 = fast) takes at `level` (csrc/pyramid.hip: level_route through the
+    test hook slam_debug_pyr_route, which launches nothing): a dict of ROUTE_FIELDS, the enums by name.  It depends on the shape, on S,
+    on the SLAMHIP_* switches of the process and on SLAMHIP_CK_MIN_MB as it is set now -- tests assert it before they look at planes."""
+    p = pyr_or_batch.pyramids[0] if isinstance(pyr_or_batch, PyramidBatch) else pyr_or_batch
+    fn = p.ctx.lib.slam_debug_pyr_route
+    fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
+    out = (C.c_int * len(ROUTE_FIELDS))()
+    p.ctx.check(fn(p.h, int(mode), int(S), 1 if target_only else 0, int(level), out))
+    return {k: ROUTE_ENUMS[k][v] if k in ROUTE_ENUMS else v for k, v in zip(ROUTE_FIELDS, out)}
+
+
 def optical_flow_matching_batch(from_batch, to_batch, stream_index, pixels, is_3d, projections, params,
                                 pyramid_levels_3d=1, iterations=30, ctx=None, status_only=False):
     """optical_flow_matching! for S lock-stepped streams in one launch (slam_flow_match_batch): point i belongs to
