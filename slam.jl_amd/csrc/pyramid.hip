@@ -18,7 +18,10 @@
 // whole aligned lines through an LDS transpose.  Batched launches take the image index
 // from blockIdx.z; bandwidth-bound ones switch to the checkpointed IIR kernels
 // (k_iir_*_ck) and the one-pass integral image (k_cum_fused), all bit-identical.
+// The filters' arithmetic itself -- the recurrence step, the two borders, imresize!'s source coordinate, pass A of the
+// checkpointed row filter, the segments' running sum and mv3 -- is in pyr_iir.hpp, one copy each; the kernels here move the samples.
 #include "common.hpp"
+#include "pyr_iir.hpp"
 #include <cmath>
 #include <cstdlib>
 #include <mutex>
@@ -314,7 +317,10 @@ __device__ __forceinline__ void iir_line(const IO &io, int n, const IIRCoef &k, 
     const double x0 = io.ld_src(0);
     const double iminus = fill0 ? 0.0 : x0;
     const double iplus = fill0 ? 0.0 : io.ld_src(n - 1);
-    const double uminus = iminus / k.inv1masum;
+    // (iir_head, iir_tail and every iir3<false> step spelled out in this function: the single-image kernels are bound by this dependent chain;
+    //  through the helpers -- even a lone iir3<false> inside the sweeps' closures -- k_iir_cols<*> and k_iir_rows compile differently and the
+    //  device span of a single-image build moved by 0.2 %.  As written here the three kernels are the parent's, instruction for instruction.)
+    const double uminus = iir_uminus(k, iminus);
     double o0 = ((x0 + a1 * uminus) + a2 * uminus) + a3 * uminus;
     double o1 = ((io.ld_src(1) + a1 * o0) + a2 * uminus) + a3 * uminus;
     double o2 = ((io.ld_src(2) + a1 * o1) + a2 * o0) + a3 * uminus;
@@ -325,15 +331,10 @@ __device__ __forceinline__ void iir_line(const IO &io, int n, const IIRCoef &k, 
         w3 = w2; w2 = w1; w1 = t;
         return t;
     });
-    const double uplus = iplus / k.inv1masum;
-    const double vplus = uplus / k.inv1mbsum;
-    const double d0 = w1 - uplus, d1 = w2 - uplus, d2 = w3 - uplus;
-    const double vr0 = ((k.M[0] * d0 + k.M[1] * d1) + k.M[2] * d2) + vplus;
-    const double vr1 = ((k.M[3] * d0 + k.M[4] * d1) + k.M[5] * d2) + vplus;
-    const double vr2 = ((k.M[6] * d0 + k.M[7] * d1) + k.M[8] * d2) + vplus;
-    double vA = vr0;                                              // v[n-1]
-    double vB = ((w2 + a1 * vA) + a2 * vr1) + a3 * vr2;           // v[n-2]
-    double vC = ((w3 + a1 * vB) + a2 * vA) + a3 * vr1;            // v[n-3]
+    const IirBoundary bd = iir_boundary(k, w1, w2, w3, iplus);
+    double vA = bd.vr0;                                           // v[n-1]
+    double vB = ((w2 + a1 * vA) + a2 * bd.vr1) + a3 * bd.vr2;  // v[n-2]
+    double vC = ((w3 + a1 * vB) + a2 * vA) + a3 * bd.vr1;      // v[n-3]
     double v1 = vC, v2 = vB, v3 = vA;
     const double scale = k.scale;
     io.fence();                                                   // forward results visible to every lane of the wave
@@ -405,7 +406,7 @@ __device__ __forceinline__ double wave_next(double v)
 // left, re-reads a block's input, recomputes its forward values in registers from the checkpoint (the same
 // operations from the same state: bit-identical), runs the backward recurrence on them and stores once:
 // 2 reads + 1 write per sample for 1.5x the arithmetic, which a bandwidth-bound launch has to spare.
-#define CK_B 32
+// (CK_B, the block plan, pass A and the checkpoint accesses: RowCk in pyr_iir.hpp, shared with k_rows_cum)
 // Fused imresize!: plane 0 of a level with a successor is the blurred layer, whose only reader is k_resize.  With
 // `rz.dst` set, the backward sweep of plane 0 does not store its results: every lane interpolates its row horizontally as the
 // samples appear (right to left; the source column and weight of the current output column are wave-uniform), then the rows
@@ -431,7 +432,6 @@ __device__ __forceinline__ double dpp_pair_next(double v)        // lanes 2k and
 #define RCK_ST(ptr, v) __builtin_nontemporal_store(v, ptr)
 // (the checkpoints stay plain accesses: nontemporal ones measured 1-2 % slower per build)
 #define CK_LD(ptr) (*(ptr))
-#define CK_ST(ptr, v) (*(ptr) = (v))
 template <bool ODD>
 __device__ __forceinline__ void iir_rows_ck(const PlaneSet &ps, int H, int W, int P, const IIRPair &cf, double *ck, const RowResize &rz)
 {
@@ -441,31 +441,24 @@ __device__ __forceinline__ void iir_rows_ck(const PlaneSet &ps, int H, int W, in
     const int y = ODD ? blockIdx.x * RZ_ODD_ROWS + threadIdx.x : slot;
     if (y >= H) return;
     // resize state: xo = current output column (1-based, descending), c0 = 0-based source column of its left sample, fx = weight
-    const double rsx = (double)W / (double)(rz.Wd > 0 ? rz.Wd : 1), rox = 1 - 0.5 - rsx * (1 - 0.5);
+    const ResizeAxis rax = resize_axis(W, rz.Wd > 0 ? rz.Wd : 1, false);
     int xo = rz.Wd, c0 = -1; double fx = 0.0, tprev = 0.0;
     // vertical half: yo = 0-based output row this lane may store, fy = its weight, rz_store = the lane stores
     int yo = y >> 1; double fy = 0.5; bool rz_store = (y & 1) == 0;
-    if (ODD) {                                                   // k_resize: r = sy * y + oy; iy = floor(r) clamped to [1, Hs - 1]; fy = r - iy
+    if (ODD) {                                                   // k_resize's row coordinate (resize_coord)
         yo = (y + 1) >> 1;                                       // the only output row whose first source row (2 yo or 2 yo - 1) can be y
-        const double rsy = (double)H / (double)rz.Hd, roy = 1 - 0.5 - rsy * (1 - 0.5);
-        const double r = rsy * (yo + 1) + roy;
-        int iy = (int)floor(r);
-        if (iy > H - 1) iy = H - 1;
-        if (iy < 1) iy = 1;
-        fy = r - iy;
-        rz_store = yo < rz.Hd && iy - 1 == y && threadIdx.x < RZ_ODD_ROWS;     // (row iy + 1 <= H is the next lane's)
+        const ResizeCoord ry = resize_coord(resize_axis(H, rz.Hd, false), yo + 1);
+        fy = ry.f;
+        rz_store = yo < rz.Hd && ry.i - 1 == y && threadIdx.x < RZ_ODD_ROWS;     // (row iy + 1 <= H is the next lane's)
     }
     double *rzp = resize ? rz.dst + (size_t)blockIdx.z * ps.zs + yo : nullptr;
     const bool exact2 = 2 * rz.Wd == W;                           // exact 2:1 columns: c = 2 xo - 0.5 -> ixx = 2 xo - 1, fx = 0.5 (what the general path computes, without the floor)
-    auto rz_target = [&]() {                                     // k_resize: c = sx * x + ox; ixx = floor(c) clamped to [1, Ws - 1]; fx = c - ixx
+    auto rz_target = [&]() {                                     // k_resize's column coordinate (resize_coord)
         if (xo < 1) { c0 = -1; return; }
         if (exact2) { c0 = 2 * xo - 2; fx = 0.5; return; }
-        const double c = rsx * xo + rox;
-        int ixx = (int)floor(c);
-        if (ixx > W - 1) ixx = W - 1;
-        if (ixx < 1) ixx = 1;
-        fx = c - ixx;
-        c0 = __builtin_amdgcn_readfirstlane(ixx - 1);
+        const ResizeCoord rx = resize_coord(rax, xo);
+        fx = rx.f;
+        c0 = __builtin_amdgcn_readfirstlane(rx.i - 1);
     };
     if (resize) rz_target();
     auto emit = [&](int x, double val) {                         // called for x = W-1 .. 0 in descending order with the finished sample T[y, x]
@@ -495,64 +488,34 @@ __device__ __forceinline__ void iir_rows_ck(const PlaneSet &ps, int H, int W, in
     const double a1 = k.a1, a2 = k.a2, a3 = k.a3, scale = k.scale;
     const double x0 = p[0];
     const double iminus = fill0 ? 0.0 : x0, iplus = fill0 ? 0.0 : p[(long)(n - 1) * s];
-    const double uminus = iminus / k.inv1masum;
-    const double o0 = ((x0 + a1 * uminus) + a2 * uminus) + a3 * uminus;
-    const double o1 = ((p[s] + a1 * o0) + a2 * uminus) + a3 * uminus;
-    const double o2 = ((p[2 * s] + a1 * o1) + a2 * o0) + a3 * uminus;
-    // ---- pass A: forward over i = 3 .. n-1, read only, block by block (next block prefetched while the current
-    //      one runs); the state before block j >= 1 is its checkpoint.  The last block absorbs the 3 trailing
-    //      samples (n-3 .. n-1), which only the boundary computation needs. ----
-    const int m = n - 6, nb = (m + CK_B - 1) / CK_B;            // the backward sweep needs forward values on [3, n-4]
-    double w3 = o0, w2 = o1, w1 = o2;
-    double cur[CK_B], nxt[CK_B];
-    auto load_x = [&](int j, double *buf) {                     // block j = samples [3 + j CK_B, ...), CK_B of them (clamped reads)
-        const double *q = p + (long)(3 + j * CK_B) * s;
-        const int len = n - (3 + j * CK_B);                     // samples left in the line
-        if (len >= CK_B) {
-#pragma unroll
-            for (int e = 0; e < CK_B; e++) buf[e] = RCK_LD(q + (long)e * s);
-        } else {
-#pragma unroll
-            for (int e = 0; e < CK_B; e++) buf[e] = e < len ? q[(long)e * s] : 0.0;
-        }
+    const IirHead hd = iir_head<false>(k, x0, p[s], p[2 * s], iminus);
+    // ---- pass A (RowCk): forward over i = 3 .. n-1, read only; the state before block j >= 1 is its checkpoint ----
+    struct Line {                                               // RowCk's accessor: the lane's line is strided, checkpoints [block][3][line]
+        const double *p; long s; double *ck; size_t nlines, lineid;
+        __device__ __forceinline__ double x(int c0, int e) const { return (p + (long)c0 * s)[(long)e * s]; }
+        __device__ __forceinline__ double x_nt(int c0, int e) const { return RCK_LD(p + (long)c0 * s + (long)e * s); }
+        __device__ __forceinline__ double *ckp(int j) const { return ck + ((size_t)j * 3) * nlines + lineid; }
     };
-    const int nfull = (n - 3) / CK_B;                           // blocks of pass A that are complete
-    const int rem = (n - 3) - nfull * CK_B;                     // samples of the trailing partial block (block nfull), prefetched like the others
-    load_x(0, cur);
-    for (int j = 0; j < nfull; j++) {
-        load_x(j + 1, nxt);                                     // (block nfull: clamped reads, the missing samples are zeros)
-        if (j > 0 && j < nb) { double *c = ck + ((size_t)j * 3) * nlines + lineid; CK_ST(c, w1); CK_ST(c + nlines, w2); CK_ST(c + 2 * nlines, w3); }
+    const Line io = {p, s, ck, nlines, lineid};
+    const RowCk rc = rowck_plan(n);
+    const int m = rc.m, nb = rc.nb;                             // the backward sweep needs forward values on [3, n-4]
+    double w3 = hd.o0, w2 = hd.o1, w1 = hd.o2;
+    double cur[CK_B], nxt[CK_B];
+    auto load_x = [&](int j, double *buf) { rowck_load_x(io, rc, j, buf); };     // (a closure, like load_ck below: with the calls written out this kernel's code changes)
+    rowck_pass_a(io, rc, a1, a2, a3, cur, nxt, w1, w2, w3);
 #pragma unroll
-        for (int e = 0; e < CK_B; e++) { const double t = ((cur[e] + a1 * w1) + a2 * w2) + a3 * w3; w3 = w2; w2 = w1; w1 = t; }
-#pragma unroll
-        for (int e = 0; e < CK_B; e++) cur[e] = nxt[e];
-    }
-    {   // remainder (< CK_B samples, in `cur`): its start may still be a checkpoint
-        if (nfull > 0 && nfull < nb) { double *c = ck + ((size_t)nfull * 3) * nlines + lineid; CK_ST(c, w1); CK_ST(c + nlines, w2); CK_ST(c + 2 * nlines, w3); }
-#pragma unroll
-        for (int e = 0; e < CK_B; e++)
-            if (e < rem) { const double t = ((cur[e] + a1 * w1) + a2 * w2) + a3 * w3; w3 = w2; w2 = w1; w1 = t; }
-    }
-    const bool have_last = nfull == nb - 1;                     // `cur` already holds the inputs of pass B's first block
-    // ---- Triggs-Sdika right boundary (as iir_line) ----
-    const double uplus = iplus / k.inv1masum, vplus = uplus / k.inv1mbsum;
-    const double d0 = w1 - uplus, d1 = w2 - uplus, d2 = w3 - uplus;
-    const double vr0 = ((k.M[0] * d0 + k.M[1] * d1) + k.M[2] * d2) + vplus;
-    const double vr1 = ((k.M[3] * d0 + k.M[4] * d1) + k.M[5] * d2) + vplus;
-    const double vr2 = ((k.M[6] * d0 + k.M[7] * d1) + k.M[8] * d2) + vplus;
-    const double vA = vr0;
-    const double vB = ((w2 + a1 * vA) + a2 * vr1) + a3 * vr2;
-    const double vC = ((w3 + a1 * vB) + a2 * vA) + a3 * vr1;
-    double v1 = vC, v2 = vB, v3 = vA;
+    for (int e = 0; e < CK_B; e++)                              // the remainder (< CK_B samples, in `cur`): iir_block_fwd, predicated, the state only
+        if (e < rc.rem) { const double t = iir3<false>(cur[e], a1, w1, a2, w2, a3, w3); w3 = w2; w2 = w1; w1 = t; }
+    const bool have_last = rc.have_last;                        // `cur` already holds the inputs of pass B's first block
+    // ---- Triggs-Sdika right boundary ----
+    const IirTail tl = iir_tail<false>(k, w1, w2, w3, iplus);
+    double v1 = tl.vC, v2 = tl.vB, v3 = tl.vA;
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");   // own checkpoints visible
-    if (resize) { emit(n - 1, vA * scale); emit(n - 2, vB * scale); emit(n - 3, vC * scale); }
-    else { p[(long)(n - 1) * s] = vA * scale; p[(long)(n - 2) * s] = vB * scale; p[(long)(n - 3) * s] = vC * scale; }
+    if (resize) { emit(n - 1, tl.vA * scale); emit(n - 2, tl.vB * scale); emit(n - 3, tl.vC * scale); }
+    else { p[(long)(n - 1) * s] = tl.vA * scale; p[(long)(n - 2) * s] = tl.vB * scale; p[(long)(n - 3) * s] = tl.vC * scale; }
     // ---- pass B: blocks right to left; block j covers i in [3 + j CK_B, 3 + min((j+1) CK_B, m)) ----
     double f1n = 0, f2n = 0, f3n = 0, f1 = 0, f2 = 0, f3 = 0;
-    auto load_ck = [&](int j, double &g1, double &g2, double &g3) {
-        if (j > 0) { const double *c = ck + ((size_t)j * 3) * nlines + lineid; g1 = CK_LD(c); g2 = CK_LD(c + nlines); g3 = CK_LD(c + 2 * nlines); }
-        else { g1 = o2; g2 = o1; g3 = o0; }
-    };
+    auto load_ck = [&](int j, double &g1, double &g2, double &g3) { rowck_load(io, j, hd, g1, g2, g3); };
     if (nb > 0) {
         // rightmost block: possibly partial (1 .. CK_B samples), predicated
         const int j = nb - 1, a = 3 + j * CK_B, len = m - j * CK_B;
@@ -560,11 +523,11 @@ __device__ __forceinline__ void iir_rows_ck(const PlaneSet &ps, int H, int W, in
         load_ck(j, f1, f2, f3);
         if (j > 0) { load_x(j - 1, nxt); load_ck(j - 1, f1n, f2n, f3n); }
 #pragma unroll
-        for (int e = 0; e < CK_B; e++)
-            if (e < len) { const double t = ((cur[e] + a1 * f1) + a2 * f2) + a3 * f3; f3 = f2; f2 = f1; f1 = t; cur[e] = t; }
+        for (int e = 0; e < CK_B; e++)                              // (iir_block_fwd, predicated)
+            if (e < len) { const double t = iir3<false>(cur[e], a1, f1, a2, f2, a3, f3); f3 = f2; f2 = f1; f1 = t; cur[e] = t; }
 #pragma unroll
-        for (int e = CK_B - 1; e >= 0; e--)
-            if (e < len) { const double t = ((cur[e] + a1 * v1) + a2 * v2) + a3 * v3; v3 = v2; v2 = v1; v1 = t; cur[e] = t * scale; if (resize) emit(a + e, cur[e]); }
+        for (int e = CK_B - 1; e >= 0; e--)                      // (iir_block_bwd, predicated, with the fused imresize! in the loop)
+            if (e < len) { const double t = iir3<false>(cur[e], a1, v1, a2, v2, a3, v3); v3 = v2; v2 = v1; v1 = t; cur[e] = t * scale; if (resize) emit(a + e, cur[e]); }
         double *q = p + (long)a * s;
         if (!resize) {
 #pragma unroll
@@ -576,10 +539,12 @@ __device__ __forceinline__ void iir_rows_ck(const PlaneSet &ps, int H, int W, in
     }
     for (int j = nb - 2; j >= 0; j--) {                          // full blocks: straight-line code
         if (j > 0) { load_x(j - 1, nxt); load_ck(j - 1, f1n, f2n, f3n); }
+        iir_block_fwd<CK_B, true>(cur, a1, a2, a3, f1, f2, f3);
 #pragma unroll
-        for (int e = 0; e < CK_B; e++) { const double t = ((cur[e] + a1 * f1) + a2 * f2) + a3 * f3; f3 = f2; f2 = f1; f1 = t; cur[e] = t; }
-#pragma unroll
-        for (int e = CK_B - 1; e >= 0; e--) { const double t = ((cur[e] + a1 * v1) + a2 * v2) + a3 * v3; v3 = v2; v2 = v1; v1 = t; cur[e] = t * scale; if (!ODD && resize) emit(3 + j * CK_B + e, cur[e]); }
+        for (int e = CK_B - 1; e >= 0; e--) {                    // (iir_block_bwd with the fused imresize! in the loop)
+            const double t = iir3<false>(cur[e], a1, v1, a2, v2, a3, v3); v3 = v2; v2 = v1; v1 = t; cur[e] = t * scale;
+            if (!ODD && resize) emit(3 + j * CK_B + e, cur[e]);
+        }
         if (ODD) {
             // The block's output columns without a branch per sample (the levels that come here run one wave per SIMD: the
             // interpolation has to fill the recurrences' latency, not queue behind it).  The block starts on an odd column a;
@@ -590,11 +555,8 @@ __device__ __forceinline__ void iir_rows_ck(const PlaneSet &ps, int H, int W, in
 #pragma unroll
             for (int mm = 0; mm < CK_B / 2; mm++) {
                 const int k1 = kb + mm + 1;                      // 1-based output column
-                const double c = rsx * k1 + rox;
-                int ixx = (int)floor(c);
-                if (ixx > W - 1) ixx = W - 1;
-                if (ixx < 1) ixx = 1;
-                const double fxm = c - ixx;
+                const ResizeCoord rx = resize_coord(rax, k1);
+                const int ixx = rx.i; const double fxm = rx.f;
                 const bool low = ixx == 2 * k1 - 2;             // 1-based left sample 2 k1 - 2 (0-based 2k - 1) instead of 2 k1 - 1
                 const double lft = low ? cur[2 * mm] : cur[2 * mm + 1];
                 const double rgt = low ? cur[2 * mm + 1] : (2 * mm + 2 < CK_B ? cur[2 * mm + 2 < CK_B ? 2 * mm + 2 : 0] : tprev);
@@ -615,10 +577,10 @@ __device__ __forceinline__ void iir_rows_ck(const PlaneSet &ps, int H, int W, in
         for (int e = 0; e < CK_B; e++) cur[e] = nxt[e];
         f1 = f1n; f2 = f2n; f3 = f3n;
     }
-    {   // i = 2, 1, 0: forward values o2, o1, o0
-        double t = ((o2 + a1 * v1) + a2 * v2) + a3 * v3; v3 = v2; v2 = v1; v1 = t; if (resize) emit(2, t * scale); else p[2 * s] = t * scale;
-        t = ((o1 + a1 * v1) + a2 * v2) + a3 * v3; v3 = v2; v2 = v1; v1 = t; if (resize) emit(1, t * scale); else p[s] = t * scale;
-        t = ((o0 + a1 * v1) + a2 * v2) + a3 * v3; if (resize) emit(0, t * scale); else p[0] = t * scale;
+    {   // i = 2, 1, 0: forward values hd.o2, hd.o1, hd.o0
+        double t = iir3<false>(hd.o2, a1, v1, a2, v2, a3, v3); v3 = v2; v2 = v1; v1 = t; if (resize) emit(2, t * scale); else p[2 * s] = t * scale;
+        t = iir3<false>(hd.o1, a1, v1, a2, v2, a3, v3); v3 = v2; v2 = v1; v1 = t; if (resize) emit(1, t * scale); else p[s] = t * scale;
+        t = iir3<false>(hd.o0, a1, v1, a2, v2, a3, v3); if (resize) emit(0, t * scale); else p[0] = t * scale;
     }
 }
 __global__ __launch_bounds__(LINE_THREADS) void k_iir_rows_ck(PlaneSet ps, int H, int W, int P, IIRPair cf, double *ck, RowResize rz)
@@ -655,11 +617,8 @@ __global__ __launch_bounds__(LINE_THREADS) void k_iir_cols_ck(PlaneSet ps, const
     auto in = [&](double v) { return sq ? v * v : v; };
     const double x0 = in(io.ld_src(0));
     const double iminus = fill0 ? 0.0 : x0, iplus = fill0 ? 0.0 : in(io.ld_src(n - 1));
-    const double uminus = iminus / k.inv1masum;
-    const double o0 = ((x0 + a1 * uminus) + a2 * uminus) + a3 * uminus;
-    const double o1 = ((in(io.ld_src(1)) + a1 * o0) + a2 * uminus) + a3 * uminus;
-    const double o2 = ((in(io.ld_src(2)) + a1 * o1) + a2 * o0) + a3 * uminus;
-    double w3 = o0, w2 = o1, w1 = o2;
+    const IirHead hd = iir_head<false>(k, x0, in(io.ld_src(1)), in(io.ld_src(2)), iminus);
+    double w3 = hd.o0, w2 = hd.o1, w1 = hd.o2;
     double raw[32], x[32];
     // ---- pass A: forward over rows 3 .. n-1, read only; checkpoint before rows 32 b (b >= 1) ----
     {
@@ -674,25 +633,16 @@ __global__ __launch_bounds__(LINE_THREADS) void k_iir_cols_ck(PlaneSet ps, const
             }
             if (t + 1 < NT) io.tile_load(io.src, rb + 16, raw);
             if ((t & 1) == 0 && t >= 2) { double *c = ck + ((size_t)(t >> 1) * 3) * nlines + lineid; c[0] = w1; c[nlines] = w2; c[2 * nlines] = w3; }
-            if (rb >= 3 && rb + 15 <= n - 1) {
+            if (rb >= 3 && rb + 15 <= n - 1) iir_block_fwd<16, false>(x, a1, a2, a3, w1, w2, w3);
+            else {                                              // (iir_block_fwd, predicated)
 #pragma unroll
-                for (int e = 0; e < 16; e++) { const double tt = ((x[e] + a1 * w1) + a2 * w2) + a3 * w3; w3 = w2; w2 = w1; w1 = tt; }
-            } else {
-#pragma unroll
-                for (int e = 0; e < 16; e++) { const int row = rb + e; if (row >= 3 && row <= n - 1) { const double tt = ((x[e] + a1 * w1) + a2 * w2) + a3 * w3; w3 = w2; w2 = w1; w1 = tt; } }
+                for (int e = 0; e < 16; e++) { const int row = rb + e; if (row >= 3 && row <= n - 1) { const double tt = iir3<false>(x[e], a1, w1, a2, w2, a3, w3); w3 = w2; w2 = w1; w1 = tt; } }
             }
         }
     }
-    // ---- Triggs-Sdika right boundary (as iir_line) ----
-    const double uplus = iplus / k.inv1masum, vplus = uplus / k.inv1mbsum;
-    const double d0 = w1 - uplus, d1 = w2 - uplus, d2 = w3 - uplus;
-    const double vr0 = ((k.M[0] * d0 + k.M[1] * d1) + k.M[2] * d2) + vplus;
-    const double vr1 = ((k.M[3] * d0 + k.M[4] * d1) + k.M[5] * d2) + vplus;
-    const double vr2 = ((k.M[6] * d0 + k.M[7] * d1) + k.M[8] * d2) + vplus;
-    const double vA = vr0;
-    const double vB = ((w2 + a1 * vA) + a2 * vr1) + a3 * vr2;
-    const double vC = ((w3 + a1 * vB) + a2 * vA) + a3 * vr1;
-    double v1 = vC, v2 = vB, v3 = vA;
+    // ---- Triggs-Sdika right boundary ----
+    const IirTail tl = iir_tail<false>(k, w1, w2, w3, iplus);
+    double v1 = tl.vC, v2 = tl.vB, v3 = tl.vA;
     io.fence();
     // ---- pass B: blocks of 32 rows, bottom to top; rows [3, n-4] carry the recurrence, n-3 .. n-1 and 2 .. 0 are direct ----
     const int NBk = ((n - 4) >> 5) + 1;
@@ -702,7 +652,7 @@ __global__ __launch_bounds__(LINE_THREADS) void k_iir_cols_ck(PlaneSet ps, const
         if (2 * b + 1 < ntile) io.tile_load(io.src, (b << 5) + 16, raw + 16);
     };
     if (n - 4 >= 3) load_block(NBk - 1);
-    io.st(n - 1, vA * scale); io.st(n - 2, vB * scale); io.st(n - 3, vC * scale);
+    io.st(n - 1, tl.vA * scale); io.st(n - 2, tl.vB * scale); io.st(n - 3, tl.vC * scale);
     for (int b = NBk - 1; b >= 0 && n - 4 >= 3; b--) {
         const int rb = b << 5, lo = rb > 3 ? rb : 3, hi = rb + 31 < n - 4 ? rb + 31 : n - 4;
         const bool two = 2 * b + 1 < ntile;
@@ -715,17 +665,15 @@ __global__ __launch_bounds__(LINE_THREADS) void k_iir_cols_ck(PlaneSet ps, const
         if (b > 0) load_block(b - 1);
         double f1, f2, f3;
         if (b > 0) { const double *c = ck + ((size_t)b * 3) * nlines + lineid; f1 = c[0]; f2 = c[nlines]; f3 = c[2 * nlines]; }
-        else { f1 = o2; f2 = o1; f3 = o0; }
+        else { f1 = hd.o2; f2 = hd.o1; f3 = hd.o0; }
         if (lo == rb && hi == rb + 31) {
+            iir_block_fwd<32, true>(x, a1, a2, a3, f1, f2, f3);
+            iir_block_bwd<32>(x, a1, a2, a3, scale, v1, v2, v3);
+        } else {                                                // (iir_block_fwd / iir_block_bwd, predicated)
 #pragma unroll
-            for (int e = 0; e < 32; e++) { const double tt = ((x[e] + a1 * f1) + a2 * f2) + a3 * f3; f3 = f2; f2 = f1; f1 = tt; x[e] = tt; }
+            for (int e = 0; e < 32; e++) { const int row = rb + e; if (row >= lo && row <= hi) { const double tt = iir3<false>(x[e], a1, f1, a2, f2, a3, f3); f3 = f2; f2 = f1; f1 = tt; x[e] = tt; } }
 #pragma unroll
-            for (int e = 31; e >= 0; e--) { const double tt = ((x[e] + a1 * v1) + a2 * v2) + a3 * v3; v3 = v2; v2 = v1; v1 = tt; x[e] = tt * scale; }
-        } else {
-#pragma unroll
-            for (int e = 0; e < 32; e++) { const int row = rb + e; if (row >= lo && row <= hi) { const double tt = ((x[e] + a1 * f1) + a2 * f2) + a3 * f3; f3 = f2; f2 = f1; f1 = tt; x[e] = tt; } }
-#pragma unroll
-            for (int e = 31; e >= 0; e--) { const int row = rb + e; if (row >= lo && row <= hi) { const double tt = ((x[e] + a1 * v1) + a2 * v2) + a3 * v3; v3 = v2; v2 = v1; v1 = tt; x[e] = tt * scale; } }
+            for (int e = 31; e >= 0; e--) { const int row = rb + e; if (row >= lo && row <= hi) { const double tt = iir3<false>(x[e], a1, v1, a2, v2, a3, v3); v3 = v2; v2 = v1; v1 = tt; x[e] = tt * scale; } }
         }
         double u[16];
         io.template lds_put_col<+1>(x); io.lds_get_tile(u);
@@ -735,10 +683,10 @@ __global__ __launch_bounds__(LINE_THREADS) void k_iir_cols_ck(PlaneSet ps, const
             io.tile_store(rb + 16, u, lo, hi, !(lo <= rb + 16 && hi >= rb + 31));
         }
     }
-    {   // rows 2, 1, 0: forward values o2, o1, o0
-        double tt = ((o2 + a1 * v1) + a2 * v2) + a3 * v3; v3 = v2; v2 = v1; v1 = tt; io.st(2, tt * scale);
-        tt = ((o1 + a1 * v1) + a2 * v2) + a3 * v3; v3 = v2; v2 = v1; v1 = tt; io.st(1, tt * scale);
-        tt = ((o0 + a1 * v1) + a2 * v2) + a3 * v3; io.st(0, tt * scale);
+    {   // rows 2, 1, 0: forward values hd.o2, hd.o1, hd.o0
+        double tt = iir3<false>(hd.o2, a1, v1, a2, v2, a3, v3); v3 = v2; v2 = v1; v1 = tt; io.st(2, tt * scale);
+        tt = iir3<false>(hd.o1, a1, v1, a2, v2, a3, v3); v3 = v2; v2 = v1; v1 = tt; io.st(1, tt * scale);
+        tt = iir3<false>(hd.o0, a1, v1, a2, v2, a3, v3); io.st(0, tt * scale);
     }
 }
 
@@ -774,14 +722,6 @@ struct ColsFusedArgs {
 
 // x[0..N) holds the lane's layer samples of rows rb .. rb+N-1 on entry, the recurrence inputs of its role on exit
 // (ROLE 1: Iy^2, 2: Ix^2, 3: Iy Ix); g receives Iy (ROLE 1) / Ix (ROLE 2).  top / bot: the layer at rows rb-1 / rb+N.
-// one step of the third-order recurrence: the reference's operation order, or (tolerance build, mode 3) three fused multiply-adds whose
-// dependent chain is the single operation that takes the newest state
-template <bool TOL>
-__device__ __forceinline__ double iir3(double x, double a1, double w1, double a2, double w2, double a3, double w3)
-{
-    if (TOL) return __builtin_fma(a1, w1, __builtin_fma(a2, w2, __builtin_fma(a3, w3, x)));
-    return ((x + a1 * w1) + a2 * w2) + a3 * w3;
-}
 // the two factors of the separable Scharr pair along one line: derivative (-1, 0, 1) / 2 and smoothing (3, 10, 3) / 16 of (a, b, c).
 // Bit-exact build: imfilter's accumulation from 0.0, term by term; tolerance build: the same sums in 2 + 3 operations
 template <bool TOL>
@@ -972,11 +912,8 @@ __device__ __forceinline__ void cols_fused_wave(const ColsFusedArgs &A, const II
     };
     const double x0 = in_row(0);
     const double iminus = x0, iplus = in_row(n - 1);
-    const double uminus = iminus / k.inv1masum;
-    const double o0 = iir3<TOL>(x0, a1, uminus, a2, uminus, a3, uminus);
-    const double o1 = iir3<TOL>(in_row(1), a1, o0, a2, uminus, a3, uminus);
-    const double o2 = iir3<TOL>(in_row(2), a1, o1, a2, o0, a3, uminus);
-    double w3 = o0, w2 = o1, w1 = o2;
+    const IirHead hd = iir_head<TOL>(k, x0, in_row(1), in_row(2), iminus);
+    double w3 = hd.o0, w2 = hd.o1, w1 = hd.o2;
     const int NBk = ((n - 1) >> 5) + 1;                           // 32-row blocks of the plane
     const int ntile = P >> 4;
     double pre[16], x[32], u[16];
@@ -1051,36 +988,29 @@ __device__ __forceinline__ void cols_fused_wave(const ColsFusedArgs &A, const II
             for (int e = 0; e < 32; e++) { const int row = rb + e; if (row >= 3 && row <= n - 1) { const double tt = iir3<TOL>(x[e], a1, w1, a2, w2, a3, w3); w3 = w2; w2 = w1; w1 = tt; } }
         }
     }
-    // ---- Triggs-Sdika right boundary (as iir_line) ----
-    const double uplus = iplus / k.inv1masum, vplus = uplus / k.inv1mbsum;
-    const double d0 = w1 - uplus, d1 = w2 - uplus, d2 = w3 - uplus;
-    const double vr0 = ((k.M[0] * d0 + k.M[1] * d1) + k.M[2] * d2) + vplus;
-    const double vr1 = ((k.M[3] * d0 + k.M[4] * d1) + k.M[5] * d2) + vplus;
-    const double vr2 = ((k.M[6] * d0 + k.M[7] * d1) + k.M[8] * d2) + vplus;
-    const double vA = vr0;
-    const double vB = iir3<TOL>(w2, a1, vA, a2, vr1, a3, vr2);
-    const double vC = iir3<TOL>(w3, a1, vB, a2, vA, a3, vr1);
-    double v1 = vC, v2 = vB, v3 = vA;
+    // ---- Triggs-Sdika right boundary ----
+    const IirTail tl = iir_tail<TOL>(k, w1, w2, w3, iplus);
+    double v1 = tl.vC, v2 = tl.vB, v3 = tl.vA;
     io.fence();
     // ---- pass B: blocks bottom to top.  Every block is visited (the gradient planes need all rows); rows [3, n-4] carry the
     //      recurrence, n-3 .. n-1 and 2 .. 0 are direct ----
     // the forward state at the top of a block (its checkpoint) is requested a block ahead, like the layer operands: loaded where
     // it is used, its s_waitcnt would also wait for every store issued before it (vmcnt counts in order) -- the block's gradient
     // lines and the previous block's results -- and the stores would never overlap the recurrences
-    double f1n = o2, f2n = o1, f3n = o0;
+    double f1n = hd.o2, f2n = hd.o1, f3n = hd.o0;
     auto load_ck = [&](int b) {
         if (b > 0) { const double *c = ck + ((size_t)b * 3) * nlines + lineid; f1n = c[0]; f2n = c[nlines]; f3n = c[2 * nlines]; }
-        else { f1n = o2; f2n = o1; f3n = o0; }
+        else { f1n = hd.o2; f2n = hd.o1; f3n = hd.o0; }
     };
     prefetch(NBk - 1);
     if (active) load_ck(NBk - 1);
     constexpr bool SFX = TOL && ROLE != 0;                        // this wave's outputs leave as exclusive suffix sums (see ColsFusedArgs::tot)
     constexpr bool dec = TOL && DEC && ROLE == 0;                 // the blurred layer leaves halved along y (ColsFusedArgs::dec; a compile-time variant: the plain store path is not in this instantiation)
     double sfx = 0.0;
-    if (active && !SFX && !dec) { io.st(n - 1, vA * scale); io.st(n - 2, vB * scale); io.st(n - 3, vC * scale); }
+    if (active && !SFX && !dec) { io.st(n - 1, tl.vA * scale); io.st(n - 2, tl.vB * scale); io.st(n - 3, tl.vC * scale); }
     double *tailv = QB + 64 * CF4_GS + 3 * lane;                  // (dec) rows n-1, n-2, n-3 wait here for their block: not in registers across the loop
-    if (active && dec) { tailv[0] = vA * scale; tailv[1] = vB * scale; tailv[2] = vC * scale; }
-    if (active && SFX) { io.st(n - 1, sfx); sfx = __builtin_fma(vA, scale, sfx); io.st(n - 2, sfx); sfx = __builtin_fma(vB, scale, sfx); io.st(n - 3, sfx); sfx = __builtin_fma(vC, scale, sfx); }
+    if (active && dec) { tailv[0] = tl.vA * scale; tailv[1] = tl.vB * scale; tailv[2] = tl.vC * scale; }
+    if (active && SFX) { io.st(n - 1, sfx); sfx = __builtin_fma(tl.vA, scale, sfx); io.st(n - 2, sfx); sfx = __builtin_fma(tl.vB, scale, sfx); io.st(n - 3, sfx); sfx = __builtin_fma(tl.vC, scale, sfx); }
     for (int b = NBk - 1; b >= 0; b--) {
         const int rb = b << 5, lo = rb > 3 ? rb : 3, hi = rb + 31 < n - 4 ? rb + 31 : n - 4;     // recurrence rows of the block (may be empty: lo > hi)
         const bool two = 2 * b + 1 < ntile;
@@ -1139,9 +1069,9 @@ __device__ __forceinline__ void cols_fused_wave(const ColsFusedArgs &A, const II
                 if (n - 3 >= rb) q[n - 3 - rb] = tailv[2];
             }
             if (b == 0) {
-                double tt = iir3<TOL>(o2, a1, v1, a2, v2, a3, v3); v3 = v2; v2 = v1; v1 = tt; q[2] = tt * scale;
-                tt = iir3<TOL>(o1, a1, v1, a2, v2, a3, v3); v3 = v2; v2 = v1; v1 = tt; q[1] = tt * scale;
-                tt = iir3<TOL>(o0, a1, v1, a2, v2, a3, v3); q[0] = tt * scale;
+                double tt = iir3<TOL>(hd.o2, a1, v1, a2, v2, a3, v3); v3 = v2; v2 = v1; v1 = tt; q[2] = tt * scale;
+                tt = iir3<TOL>(hd.o1, a1, v1, a2, v2, a3, v3); v3 = v2; v2 = v1; v1 = tt; q[1] = tt * scale;
+                tt = iir3<TOL>(hd.o0, a1, v1, a2, v2, a3, v3); q[0] = tt * scale;
             }
 #pragma unroll
             for (int j = 0; j < 8; j++) {                         // in place: pair j writes q[2j], q[2j+1] < the next pair's reads q[4j+4 ..]
@@ -1167,15 +1097,15 @@ __device__ __forceinline__ void cols_fused_wave(const ColsFusedArgs &A, const II
             __builtin_amdgcn_wave_barrier();
         }
     }
-    if (active && !SFX && !dec) {   // rows 2, 1, 0: forward values o2, o1, o0
-        double tt = iir3<TOL>(o2, a1, v1, a2, v2, a3, v3); v3 = v2; v2 = v1; v1 = tt; io.st(2, tt * scale);
-        tt = iir3<TOL>(o1, a1, v1, a2, v2, a3, v3); v3 = v2; v2 = v1; v1 = tt; io.st(1, tt * scale);
-        tt = iir3<TOL>(o0, a1, v1, a2, v2, a3, v3); io.st(0, tt * scale);
+    if (active && !SFX && !dec) {   // rows 2, 1, 0: forward values hd.o2, hd.o1, hd.o0
+        double tt = iir3<TOL>(hd.o2, a1, v1, a2, v2, a3, v3); v3 = v2; v2 = v1; v1 = tt; io.st(2, tt * scale);
+        tt = iir3<TOL>(hd.o1, a1, v1, a2, v2, a3, v3); v3 = v2; v2 = v1; v1 = tt; io.st(1, tt * scale);
+        tt = iir3<TOL>(hd.o0, a1, v1, a2, v2, a3, v3); io.st(0, tt * scale);
     }
     if (active && SFX) {
-        double tt = iir3<TOL>(o2, a1, v1, a2, v2, a3, v3); v3 = v2; v2 = v1; v1 = tt; io.st(2, sfx); sfx = __builtin_fma(tt, scale, sfx);
-        tt = iir3<TOL>(o1, a1, v1, a2, v2, a3, v3); v3 = v2; v2 = v1; v1 = tt; io.st(1, sfx); sfx = __builtin_fma(tt, scale, sfx);
-        tt = iir3<TOL>(o0, a1, v1, a2, v2, a3, v3); io.st(0, sfx); sfx = __builtin_fma(tt, scale, sfx);
+        double tt = iir3<TOL>(hd.o2, a1, v1, a2, v2, a3, v3); v3 = v2; v2 = v1; v1 = tt; io.st(2, sfx); sfx = __builtin_fma(tt, scale, sfx);
+        tt = iir3<TOL>(hd.o1, a1, v1, a2, v2, a3, v3); v3 = v2; v2 = v1; v1 = tt; io.st(1, sfx); sfx = __builtin_fma(tt, scale, sfx);
+        tt = iir3<TOL>(hd.o0, a1, v1, a2, v2, a3, v3); io.st(0, sfx); sfx = __builtin_fma(tt, scale, sfx);
         if (io.valid()) A.tot[((size_t)blockIdx.z * 3 + (ROLE - 1)) * A.tot_stride + io.xown()] = sfx;
     }
 }
@@ -1424,86 +1354,56 @@ __global__ __launch_bounds__(CF_MAXW * 64) void k_rows_cum(PlaneSet ps, int H, i
     const double a1 = k.a1, a2 = k.a2, a3 = k.a3, scale = k.scale;
     const double x0 = p[0];
     const double iminus = fill0 ? 0.0 : x0, iplus = fill0 ? 0.0 : p[(long)(n - 1) * s];
-    const double uminus = iminus / k.inv1masum;
-    const double o0 = ((x0 + a1 * uminus) + a2 * uminus) + a3 * uminus;
-    const double o1 = ((p[s] + a1 * o0) + a2 * uminus) + a3 * uminus;
-    const double o2 = ((p[2 * s] + a1 * o1) + a2 * o0) + a3 * uminus;
-    const int m = n - 6, nb = (m + CK_B - 1) / CK_B;
-    double w3 = o0, w2 = o1, w1 = o2;
-    double cur[CK_B], nxt[CK_B];
-    auto load_x = [&](int j, double *buf) {
-        const int c0 = 3 + j * CK_B, len = n - c0;
-        if (len >= CK_B) {
-#pragma unroll
-            for (int e = 0; e < CK_B; e++) buf[e] = RCK_LD(plane + (size_t)(c0 + e) * P + yo);
-        } else {
-#pragma unroll
-            for (int e = 0; e < CK_B; e++) buf[e] = e < len ? plane[(size_t)(c0 + e) * P + yo] : 0.0;
-        }
+    const IirHead hd = iir_head<false>(k, x0, p[s], p[2 * s], iminus);
+    struct Line {                                               // RowCk's accessor: uniform plane / checkpoint base + 32-bit lane offset
+        const double *plane; int P; unsigned yo; double *ck; size_t nlines; unsigned lid;
+        __device__ __forceinline__ double x(int c0, int e) const { return plane[(size_t)(c0 + e) * P + yo]; }
+        __device__ __forceinline__ double x_nt(int c0, int e) const { return RCK_LD(plane + (size_t)(c0 + e) * P + yo); }
+        __device__ __forceinline__ double *ckp(int j) const { return ck + ((size_t)j * 3) * nlines + lid; }
     };
-    // ---- pass A (k_iir_rows_ck's) ----
-    const int nfull = (n - 3) / CK_B, rem = (n - 3) - nfull * CK_B;
-    load_x(0, cur);
-    for (int j = 0; j < nfull; j++) {
-        load_x(j + 1, nxt);
-        if (j > 0 && j < nb) { double *c = ck + ((size_t)j * 3) * nlines + lid; CK_ST(c, w1); CK_ST(c + nlines, w2); CK_ST(c + 2 * nlines, w3); }
+    const Line io = {plane, P, yo, ck, nlines, lid};
+    const RowCk rc = rowck_plan(n);
+    const int m = rc.m, nb = rc.nb;
+    double w3 = hd.o0, w2 = hd.o1, w1 = hd.o2;
+    double cur[CK_B], nxt[CK_B];
+    // ---- pass A (RowCk, as k_iir_rows_ck) ----
+    rowck_pass_a(io, rc, a1, a2, a3, cur, nxt, w1, w2, w3);
 #pragma unroll
-        for (int e = 0; e < CK_B; e++) { const double t = ((cur[e] + a1 * w1) + a2 * w2) + a3 * w3; w3 = w2; w2 = w1; w1 = t; }
-#pragma unroll
-        for (int e = 0; e < CK_B; e++) cur[e] = nxt[e];
-    }
-    {
-        if (nfull > 0 && nfull < nb) { double *c = ck + ((size_t)nfull * 3) * nlines + lid; CK_ST(c, w1); CK_ST(c + nlines, w2); CK_ST(c + 2 * nlines, w3); }
-#pragma unroll
-        for (int e = 0; e < CK_B; e++)
-            if (e < rem) { const double t = ((cur[e] + a1 * w1) + a2 * w2) + a3 * w3; w3 = w2; w2 = w1; w1 = t; }
-    }
-    const bool have_last = nfull == nb - 1;
-    const double uplus = iplus / k.inv1masum, vplus = uplus / k.inv1mbsum;
-    const double d0 = w1 - uplus, d1 = w2 - uplus, d2 = w3 - uplus;
-    const double vr0 = ((k.M[0] * d0 + k.M[1] * d1) + k.M[2] * d2) + vplus;
-    const double vr1 = ((k.M[3] * d0 + k.M[4] * d1) + k.M[5] * d2) + vplus;
-    const double vr2 = ((k.M[6] * d0 + k.M[7] * d1) + k.M[8] * d2) + vplus;
-    const double vA = vr0;
-    const double vB = ((w2 + a1 * vA) + a2 * vr1) + a3 * vr2;
-    const double vC = ((w3 + a1 * vB) + a2 * vA) + a3 * vr1;
-    double v1 = vC, v2 = vB, v3 = vA;
+    for (int e = 0; e < CK_B; e++)                              // the remainder (< CK_B samples, in `cur`): iir_block_fwd, predicated, the state only
+        if (e < rc.rem) { const double t = iir3<false>(cur[e], a1, w1, a2, w2, a3, w3); w3 = w2; w2 = w1; w1 = t; }
+    const bool have_last = rc.have_last;
+    const IirTail tl = iir_tail<false>(k, w1, w2, w3, iplus);
+    double v1 = tl.vC, v2 = tl.vB, v3 = tl.vA;
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");   // own checkpoints visible
     // ---- pass B: blocks nb-1 .. 1 as k_iir_rows_ck's pass B without the stores; slot j <- anticausal state entering block j ----
     double f1n = 0, f2n = 0, f3n = 0, f1 = 0, f2 = 0, f3 = 0;
-    auto load_ck = [&](int j, double &g1, double &g2, double &g3) {
-        if (j > 0) { const double *c = ck + ((size_t)j * 3) * nlines + lid; g1 = CK_LD(c); g2 = CK_LD(c + nlines); g3 = CK_LD(c + 2 * nlines); }
-        else { g1 = o2; g2 = o1; g3 = o0; }
-    };
-    auto store_ack = [&](int j) { double *c = ck + ((size_t)j * 3) * nlines + lid; CK_ST(c, v1); CK_ST(c + nlines, v2); CK_ST(c + 2 * nlines, v3); };
-    if (nb > 1) {
+    if (nb > 1) {                                                 // rightmost block: possibly partial (1 .. CK_B samples), predicated
         const int j = nb - 1, len = m - j * CK_B;
-        if (!have_last) load_x(j, cur);
-        load_ck(j, f1, f2, f3);
-        load_x(j - 1, nxt); load_ck(j - 1, f1n, f2n, f3n);
+        if (!have_last) rowck_load_x(io, rc, j, cur);
+        rowck_load(io, j, hd, f1, f2, f3);
+        rowck_load_x(io, rc, j - 1, nxt); rowck_load(io, j - 1, hd, f1n, f2n, f3n);
 #pragma unroll
-        for (int e = 0; e < CK_B; e++)
-            if (e < len) { const double t = ((cur[e] + a1 * f1) + a2 * f2) + a3 * f3; f3 = f2; f2 = f1; f1 = t; cur[e] = t; }
-        store_ack(j);                                             // (after the causal sweep: slot j's causal checkpoint has been read)
+        for (int e = 0; e < CK_B; e++)                            // (iir_block_fwd, predicated)
+            if (e < len) { const double t = iir3<false>(cur[e], a1, f1, a2, f2, a3, f3); f3 = f2; f2 = f1; f1 = t; cur[e] = t; }
+        rowck_store(io, j, v1, v2, v3);                                             // (after the causal sweep: slot j's causal checkpoint has been read)
 #pragma unroll
-        for (int e = CK_B - 1; e >= 0; e--)
-            if (e < len) { const double t = ((cur[e] + a1 * v1) + a2 * v2) + a3 * v3; v3 = v2; v2 = v1; v1 = t; }
+        for (int e = CK_B - 1; e >= 0; e--)                       // (iir_block_bwd, predicated, the state only)
+            if (e < len) { const double t = iir3<false>(cur[e], a1, v1, a2, v2, a3, v3); v3 = v2; v2 = v1; v1 = t; }
 #pragma unroll
         for (int e = 0; e < CK_B; e++) cur[e] = nxt[e];
         f1 = f1n; f2 = f2n; f3 = f3n;
     }
     for (int j = nb - 2; j >= 1; j--) {
-        load_x(j - 1, nxt); load_ck(j - 1, f1n, f2n, f3n);
+        rowck_load_x(io, rc, j - 1, nxt); rowck_load(io, j - 1, hd, f1n, f2n, f3n);
+        iir_block_fwd<CK_B, true>(cur, a1, a2, a3, f1, f2, f3);
+        rowck_store(io, j, v1, v2, v3);
 #pragma unroll
-        for (int e = 0; e < CK_B; e++) { const double t = ((cur[e] + a1 * f1) + a2 * f2) + a3 * f3; f3 = f2; f2 = f1; f1 = t; cur[e] = t; }
-        store_ack(j);
-#pragma unroll
-        for (int e = CK_B - 1; e >= 0; e--) { const double t = ((cur[e] + a1 * v1) + a2 * v2) + a3 * v3; v3 = v2; v2 = v1; v1 = t; }
+        for (int e = CK_B - 1; e >= 0; e--) { const double t = iir3<false>(cur[e], a1, v1, a2, v2, a3, v3); v3 = v2; v2 = v1; v1 = t; }   // (iir_block_bwd, the state only)
 #pragma unroll
         for (int e = 0; e < CK_B; e++) cur[e] = nxt[e];
         f1 = f1n; f2 = f2n; f3 = f3n;
     }
-    if (nb > 0) store_ack(0);
+    if (nb > 0) rowck_store(io, 0, v1, v2, v3);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     // ---- pass C ----
     double rcarry = -0.0;                                         // this lane's row: running sum along x
@@ -1559,34 +1459,32 @@ __global__ __launch_bounds__(CF_MAXW * 64) void k_rows_cum(PlaneSet ps, int H, i
     };
     auto put = [&](int col, double v) { Cb[col * CF_LS + lane] = v; };
     double pv0 = 0, pv1 = 0, pv2 = 0;                             // the finished samples of the block's first 3 columns of the next half pair
-    f1 = o2; f2 = o1; f3 = o0;                                    // causal state before block 0 (continued across blocks)
+    f1 = hd.o2; f2 = hd.o1; f3 = hd.o0;                                    // causal state before block 0 (continued across blocks)
     if (nb > 0) {
-        load_x(0, cur);
+        rowck_load_x(io, rc, 0, cur);
         { const double *c = ck + lid; v1 = CK_LD(c); v2 = CK_LD(c + nlines); v3 = CK_LD(c + 2 * nlines); }
     }
     for (int j = 0; j < nb; j++) {
         const int len = m - j * CK_B;                             // >= CK_B except in the last block
         double g1n = 0, g2n = 0, g3n = 0;
         if (len >= CK_B) {
-#pragma unroll
-            for (int e = 0; e < CK_B; e++) { const double t = ((cur[e] + a1 * f1) + a2 * f2) + a3 * f3; f3 = f2; f2 = f1; f1 = t; cur[e] = t; }
-#pragma unroll
-            for (int e = CK_B - 1; e >= 0; e--) { const double t = ((cur[e] + a1 * v1) + a2 * v2) + a3 * v3; v3 = v2; v2 = v1; v1 = t; cur[e] = t * scale; }
+            iir_block_fwd<CK_B, true>(cur, a1, a2, a3, f1, f2, f3);
+            iir_block_bwd<CK_B>(cur, a1, a2, a3, scale, v1, v2, v3);
         } else {
 #pragma unroll
-            for (int e = 0; e < CK_B; e++)
-                if (e < len) { const double t = ((cur[e] + a1 * f1) + a2 * f2) + a3 * f3; f3 = f2; f2 = f1; f1 = t; cur[e] = t; }
+            for (int e = 0; e < CK_B; e++)                              // (iir_block_fwd, predicated)
+                if (e < len) { const double t = iir3<false>(cur[e], a1, f1, a2, f2, a3, f3); f3 = f2; f2 = f1; f1 = t; cur[e] = t; }
 #pragma unroll
-            for (int e = CK_B - 1; e >= 0; e--)
-                if (e < len) { const double t = ((cur[e] + a1 * v1) + a2 * v2) + a3 * v3; v3 = v2; v2 = v1; v1 = t; cur[e] = t * scale; }
+            for (int e = CK_B - 1; e >= 0; e--)                   // (iir_block_bwd, predicated)
+                if (e < len) { const double t = iir3<false>(cur[e], a1, v1, a2, v2, a3, v3); v3 = v2; v2 = v1; v1 = t; cur[e] = t * scale; }
         }
-        if (j == 0) {                                             // i = 2, 1, 0 from the forward values o2, o1, o0
-            double t = ((o2 + a1 * v1) + a2 * v2) + a3 * v3; v3 = v2; v2 = v1; v1 = t; pv2 = t * scale;
-            t = ((o1 + a1 * v1) + a2 * v2) + a3 * v3; v3 = v2; v2 = v1; v1 = t; pv1 = t * scale;
-            t = ((o0 + a1 * v1) + a2 * v2) + a3 * v3; pv0 = t * scale;
+        if (j == 0) {                                             // i = 2, 1, 0 from the forward values hd.o2, hd.o1, hd.o0
+            double t = iir3<false>(hd.o2, a1, v1, a2, v2, a3, v3); v3 = v2; v2 = v1; v1 = t; pv2 = t * scale;
+            t = iir3<false>(hd.o1, a1, v1, a2, v2, a3, v3); v3 = v2; v2 = v1; v1 = t; pv1 = t * scale;
+            t = iir3<false>(hd.o0, a1, v1, a2, v2, a3, v3); pv0 = t * scale;
         }
         if (j + 1 < nb) {                                         // next block's inputs and anticausal entry state, in flight during the sums
-            load_x(j + 1, nxt);
+            rowck_load_x(io, rc, j + 1, nxt);
             const double *c = ck + ((size_t)(j + 1) * 3) * nlines + lid; g1n = CK_LD(c); g2n = CK_LD(c + nlines); g3n = CK_LD(c + 2 * nlines);
         }
         const int x0 = j * CK_B;                                  // this block's half pair: columns [x0, x0 + 32) = pv0..2, cur[0..28]
@@ -1637,16 +1535,7 @@ __global__ __launch_bounds__(CF_MAXW * 64) void k_rows_cum(PlaneSet ps, int H, i
 // rounded differently (tested: planes <= 1e-11 relative to the exact mode).
 #define PAR_T 1024
 #define PAR_SLMAX 16
-#define PAR_G 8
 struct SegPow { double P[2][PAR_G][9]; double Plast[2][9]; };   // M^(SL*q), q = 1..8; M^(len_last - 1)
-
-__device__ __forceinline__ void mv3(const double *P, double &a, double &b, double &c, double za, double zb, double zc)
-{
-    const double n1 = __builtin_fma(P[0], a, __builtin_fma(P[1], b, __builtin_fma(P[2], c, za)));      // (mode-3 kernels only: contracted)
-    const double n2 = __builtin_fma(P[3], a, __builtin_fma(P[4], b, __builtin_fma(P[5], c, zb)));
-    const double n3 = __builtin_fma(P[6], a, __builtin_fma(P[7], b, __builtin_fma(P[8], c, zc)));
-    a = n1; b = n2; c = n3;
-}
 
 // entry state of segment index `k` (0-based in fold order) of line l: two-level fold.
 // Z: zero-state end states [3][nslots][LPW] indexed by fold order through `slot(k)`.
@@ -1708,7 +1597,7 @@ __global__ __launch_bounds__(T) void k_iir_seg(PlaneSet ps, const double *src0, 
 #pragma unroll
     for (int j = 0; j < PAR_SLMAX; j++) x[j] = (j < len) ? srcp[(long)(b + j) * stride] : 0.0;
     const double x0 = srcp[0], xlast = srcp[(long)(n - 1) * stride];
-    const double uminus = x0 / k.inv1masum;
+    const double uminus = iir_uminus(k, x0);
     // ---------------- forward: A ----------------
     {
         double w1 = 0.0, w2 = 0.0, w3 = 0.0;
@@ -1728,12 +1617,8 @@ __global__ __launch_bounds__(T) void k_iir_seg(PlaneSet ps, const double *src0, 
     __syncthreads();
     // ---------------- Triggs-Sdika right boundary ----------------
     const double f1 = Fin[0][l], f2 = Fin[1][l], f3 = Fin[2][l];
-    const double uplus = xlast / k.inv1masum, vplus = uplus / k.inv1mbsum;
-    const double d0 = f1 - uplus, d1 = f2 - uplus, d2 = f3 - uplus;
-    const double vr0 = ((k.M[0] * d0 + k.M[1] * d1) + k.M[2] * d2) + vplus;
-    const double vr1 = ((k.M[3] * d0 + k.M[4] * d1) + k.M[5] * d2) + vplus;
-    const double vr2 = ((k.M[6] * d0 + k.M[7] * d1) + k.M[8] * d2) + vplus;
-    // ---------------- backward: A' (sample n-1 is not part of the recurrence: v[n-1] = vr0) ----------------
+    const IirBoundary bd = iir_boundary(k, f1, f2, f3, xlast);
+    // ---------------- backward: A' (sample n-1 is not part of the recurrence: v[n-1] = bd.vr0) ----------------
     const int blen = lastseg ? len - 1 : len;              // samples of this segment that the backward recurrence visits
     {
         double v1 = 0.0, v2 = 0.0, v3 = 0.0;
@@ -1745,17 +1630,17 @@ __global__ __launch_bounds__(T) void k_iir_seg(PlaneSet ps, const double *src0, 
     // ---------------- backward: B', C' ----------------
     {
         // state after the (short) last segment, then fold the full segments right-to-left
-        double s0a = vr0, s0b = vr1, s0c = vr2;
+        double s0a = bd.vr0, s0b = bd.vr1, s0c = bd.vr2;
         mv3(sp.Plast[cs], s0a, s0b, s0c, Z[0][(nseg - 1) * ZG + l * ZL], Z[1][(nseg - 1) * ZG + l * ZL], Z[2][(nseg - 1) * ZG + l * ZL]);
         double v1, v2, v3;
         const int kq = nseg - 2 - g;                        // fold order of the full segments
         const bool hasq = has && !lastseg;
         fold_entry<ZG, ZL, GG, GL, ZN, GN>(sp, cs, Z, GT, l, hasq ? kq : 0, hasq, [nseg](int kk) { return nseg - 2 - kk; }, s0a, s0b, s0c, v1, v2, v3);
-        if (lastseg) { v1 = vr0; v2 = vr1; v3 = vr2; }
+        if (lastseg) { v1 = bd.vr0; v2 = bd.vr1; v3 = bd.vr2; }
 #pragma unroll
         for (int j = PAR_SLMAX - 1; j >= 0; j--) if (j < blen) { const double tt = iir3<true>(x[j], a1, v1, a2, v2, a3, v3); v3 = v2; v2 = v1; v1 = tt; x[j] = tt * scale; }
 #pragma unroll
-        for (int j = 0; j < PAR_SLMAX; j++) if (lastseg && j == len - 1) x[j] = vr0 * scale;
+        for (int j = 0; j < PAR_SLMAX; j++) if (lastseg && j == len - 1) x[j] = bd.vr0 * scale;
     }
     // planes of cum_mask: the running sum along the line follows in registers (k_cum_seg's arithmetic on the same values: segment totals
     // folded in two levels through LDS) -- the product planes of a single image leave with their dim-1 integral, one kernel and one
@@ -1765,16 +1650,7 @@ __global__ __launch_bounds__(T) void k_iir_seg(PlaneSet ps, const double *src0, 
 #pragma unroll
         for (int j = 0; j < PAR_SLMAX; j++) if (j < len) acc = acc + x[j];
         __syncthreads();                                          // the backward fold's LDS arrays are free
-        if (has) Z[0][g * ZG + l * ZL] = acc;
-        __syncthreads();
-        const int q = g % PAR_G, grp = g / PAR_G;
-        double pre = 0.0;
-        if (has) for (int i = 0; i < q; i++) pre = pre + Z[0][(grp * PAR_G + i) * ZG + l * ZL];
-        if (has && q == PAR_G - 1) GT[0][grp * GG + l * GL] = pre + Z[0][g * ZG + l * ZL];
-        __syncthreads();
-        double base = 0.0;
-        if (has) for (int h = 0; h < grp; h++) base = base + GT[0][h * GG + l * GL];
-        acc = base + pre;
+        acc = seg_running_sum(g, has, acc, [&](int sl) -> double & { return Z[0][sl * ZG + l * ZL]; }, [&](int h) -> double & { return GT[0][h * GG + l * GL]; });
 #pragma unroll
         for (int j = 0; j < PAR_SLMAX; j++) if (j < len) { acc = acc + x[j]; x[j] = acc; }
     }
@@ -1807,16 +1683,7 @@ __global__ __launch_bounds__(T) void k_cum_seg(PlaneSet ps, int H, int W, int P,
     double acc = 0.0;
 #pragma unroll
     for (int j = 0; j < PAR_SLMAX; j++) if (j < len) acc = acc + x[j];
-    if (has) Zs[g * ZG + l * ZL] = acc;
-    __syncthreads();
-    const int q = g % PAR_G, grp = g / PAR_G;
-    double pre = 0.0;
-    if (has) for (int i = 0; i < q; i++) pre = pre + Zs[(grp * PAR_G + i) * ZG + l * ZL];
-    if (has && q == PAR_G - 1) Gs[grp * GG + l * GL] = pre + Zs[g * ZG + l * ZL];
-    __syncthreads();
-    double base = 0.0;
-    if (has) for (int h = 0; h < grp; h++) base = base + Gs[h * GG + l * GL];
-    acc = base + pre;
+    acc = seg_running_sum(g, has, acc, [&](int sl) -> double & { return Zs[sl * ZG + l * ZL]; }, [&](int h) -> double & { return Gs[h * GG + l * GL]; });
     if (valid) {
 #pragma unroll
         for (int j = 0; j < PAR_SLMAX; j++) if (j < len) { acc = acc + x[j]; p[(long)(b + j) * stride] = acc; }
@@ -1854,19 +1721,11 @@ struct RowsTolArgs {
     int dec;                // kind 0: the plane is the half-height Th of k_cols_fused<TOL> (H / 2 rows, pitch P / 2): no row pairing left to do
     int dbg;                // SLAMHIP_RT_DBG (timing experiments only): 1 = loads + stores without the arithmetic (invalid planes)
 };
-// (this kernel is tolerance mode by definition: its multiply-adds are fused -- half the f64 instructions of the -ffp-contract=off form)
-__device__ __forceinline__ double rt_step(double x, double a1, double a2, double a3, double w1, double w2, double w3)
-{
-    return __builtin_fma(a3, w3, __builtin_fma(a2, w2, __builtin_fma(a1, w1, x)));
-}
-__device__ __forceinline__ void mv3f(const double *P, double &a, double &b, double &c, double za, double zb, double zc)
-{
-    const double n1 = __builtin_fma(P[0], a, __builtin_fma(P[1], b, __builtin_fma(P[2], c, za)));
-    const double n2 = __builtin_fma(P[3], a, __builtin_fma(P[4], b, __builtin_fma(P[5], c, zb)));
-    const double n3 = __builtin_fma(P[6], a, __builtin_fma(P[7], b, __builtin_fma(P[8], c, zc)));
-    a = n1; b = n2; c = n3;
-}
-// entry state of segment `k` (0-based in fold order) of row l: two-level fold over groups of PAR_G segments (fold_entry's scheme).
+// (this kernel is tolerance mode by definition: its multiply-adds are fused -- half the f64 instructions of the -ffp-contract=off form;
+//  its recurrence step is rt_step, pyr_iir.hpp)
+// entry state of segment `k` (0-based in fold order) of row l: two-level fold over groups of PAR_G segments.  (fold_entry's scheme with this
+// kernel's LDS layout, power source and rolled loops, kept as a body of its own: behind one shared fold either this kernel or k_iir_seg<false>
+// gains registers and loses a wave of occupancy, see HISTORY round 15.)
 // Z: zero-state end states [3][NS][RT_R] indexed through slot(fold index); GT: group totals [3][NS / PAR_G + 1][RT_R]
 template <int NS, int R, class Slot>
 __device__ __forceinline__ void rt_fold(const SegPow &sp, int cs, const double *PW, double (*Z)[NS][R], double (*GT)[NS / PAR_G + 1][R], int l, int k, bool has, Slot slot,
@@ -1879,19 +1738,19 @@ __device__ __forceinline__ void rt_fold(const SegPow &sp, int cs, const double *
     double a = 0.0, b = 0.0, c = 0.0;
     if (has) {
 #pragma unroll 1
-        for (int i = 0; i < q; i++) { const int s = slot(grp * PAR_G + i); mv3f(P1, a, b, c, Z[0][s][l], Z[1][s][l], Z[2][s][l]); }
+        for (int i = 0; i < q; i++) { const int s = slot(grp * PAR_G + i); mv3(P1, a, b, c, Z[0][s][l], Z[1][s][l], Z[2][s][l]); }
     }
     if (has && q == PAR_G - 1) {
         double ta = a, tb = b, tc = c; const int s = slot(k);
-        mv3f(P1, ta, tb, tc, Z[0][s][l], Z[1][s][l], Z[2][s][l]);
+        mv3(P1, ta, tb, tc, Z[0][s][l], Z[1][s][l], Z[2][s][l]);
         GT[0][grp][l] = ta; GT[1][grp][l] = tb; GT[2][grp][l] = tc;
     }
     __syncthreads();
     double Sa = s0a, Sb = s0b, Sc = s0c;
     if (has) {
 #pragma unroll 1
-        for (int h = 0; h < grp; h++) mv3f(P8, Sa, Sb, Sc, GT[0][h][l], GT[1][h][l], GT[2][h][l]);
-        if (q > 0) mv3f(PW + 9 * (q - 1), Sa, Sb, Sc, 0.0, 0.0, 0.0);
+        for (int h = 0; h < grp; h++) mv3(P8, Sa, Sb, Sc, GT[0][h][l], GT[1][h][l], GT[2][h][l]);
+        if (q > 0) mv3(PW + 9 * (q - 1), Sa, Sb, Sc, 0.0, 0.0, 0.0);
     }
     ea = Sa + a; eb = Sb + b; ec = Sc + c;
 }
@@ -1963,7 +1822,7 @@ __global__ __launch_bounds__(R * NS, (R * NS >= 1024 ? 4 : 4)) void k_rows_tol(R
         }
         return;
     }
-    const double uminus = x0 / k.inv1masum;
+    const double uminus = iir_uminus(k, x0);
     // ---------------- forward: zero-state pass, fold, true pass ----------------
     {
         double w1 = 0.0, w2 = 0.0, w3 = 0.0;
@@ -1982,12 +1841,8 @@ __global__ __launch_bounds__(R * NS, (R * NS >= 1024 ? 4 : 4)) void k_rows_tol(R
     __syncthreads();
     // ---------------- Triggs-Sdika right boundary ----------------
     const double f1 = Fin[0][l], f2 = Fin[1][l], f3 = Fin[2][l];
-    const double uplus = xlast / k.inv1masum, vplus = uplus / k.inv1mbsum;
-    const double d0 = f1 - uplus, d1 = f2 - uplus, d2 = f3 - uplus;
-    const double vr0 = ((k.M[0] * d0 + k.M[1] * d1) + k.M[2] * d2) + vplus;
-    const double vr1 = ((k.M[3] * d0 + k.M[4] * d1) + k.M[5] * d2) + vplus;
-    const double vr2 = ((k.M[6] * d0 + k.M[7] * d1) + k.M[8] * d2) + vplus;
-    // ---------------- backward (sample n-1, the last segment's last, is not part of the recurrence: v[n-1] = vr0) ----------------
+    const IirBoundary bd = iir_boundary(k, f1, f2, f3, xlast);
+    // ---------------- backward (sample n-1, the last segment's last, is not part of the recurrence: v[n-1] = bd.vr0) ----------------
     {
         double v1 = 0.0, v2 = 0.0, v3 = 0.0;
         if (!lastseg) { const double tt = rt_step(x[SL - 1], a1, a2, a3, v1, v2, v3); v3 = v2; v2 = v1; v1 = tt; }
@@ -1997,13 +1852,13 @@ __global__ __launch_bounds__(R * NS, (R * NS >= 1024 ? 4 : 4)) void k_rows_tol(R
     }
     __syncthreads();
     {
-        double s0a = vr0, s0b = vr1, s0c = vr2;
-        mv3f(sp.Plast[cs], s0a, s0b, s0c, Z[0][nseg - 1][l], Z[1][nseg - 1][l], Z[2][nseg - 1][l]);
+        double s0a = bd.vr0, s0b = bd.vr1, s0c = bd.vr2;
+        mv3(sp.Plast[cs], s0a, s0b, s0c, Z[0][nseg - 1][l], Z[1][nseg - 1][l], Z[2][nseg - 1][l]);
         double v1, v2, v3;
         const int kq = nseg - 2 - g;
         const bool hasq = has && !lastseg;
         rt_fold<NS, R>(sp, cs, PW, Z, GT, l, hasq ? kq : 0, hasq, [nseg](int kk) { return nseg - 2 - kk; }, s0a, s0b, s0c, v1, v2, v3);
-        if (lastseg) { v1 = vr0; v2 = vr1; v3 = vr2; x[SL - 1] = vr0 * scale; }
+        if (lastseg) { v1 = bd.vr0; v2 = bd.vr1; v3 = bd.vr2; x[SL - 1] = bd.vr0 * scale; }
         else { const double tt = rt_step(x[SL - 1], a1, a2, a3, v1, v2, v3); v3 = v2; v2 = v1; v1 = tt; x[SL - 1] = tt * scale; }
 #pragma unroll
         for (int j = SL - 2; j >= 0; j--) { const double tt = rt_step(x[j], a1, a2, a3, v1, v2, v3); v3 = v2; v2 = v1; v1 = tt; x[j] = tt * scale; }
@@ -2020,7 +1875,7 @@ __global__ __launch_bounds__(R * NS, (R * NS >= 1024 ? 4 : 4)) void k_rows_tol(R
         double acc = 0.0;
 #pragma unroll
         for (int j = 0; j < SL; j++) acc = acc + x[j];
-        if (has) Zs[g][l] = acc;
+        if (has) Zs[g][l] = acc;                            // (seg_running_sum, spelled out: through the helper this kernel's code changes, see HISTORY round 15)
         __syncthreads();
         const int q = g % PAR_G, grp = g / PAR_G;
         double pre = 0.0;
@@ -2054,23 +1909,21 @@ __global__ __launch_bounds__(R * NS, (R * NS >= 1024 ? 4 : 4)) void k_rows_tol(R
     if (!has) return;
     const double nxt = g + 1 < nseg ? Zs[g + 1][l] : 0.0;
     const int Wd = A.rz.Wd, Hd = A.rz.Hd;
-    const double sx = (double)W / (double)Wd, ox = 1 - 0.5 - sx * (1 - 0.5);
-    // first output column (1-based) whose left source sample (1-based: floor(c)) is >= max(b, 0) + 1
+    const ResizeAxis rax = resize_axis(W, Wd, false);
+    // first output column (1-based) whose left source sample (1-based: floor(c)) is >= max(b, 0) + 1 -- a search over the unclamped
+    // coordinate, started from its inverse (not resize_coord's clamped index: mirrors its c = s k1 + o)
     const int b0 = b > 0 ? b : 0;
-    int xo = (int)ceil(((double)(b0 + 1) - ox) / sx);
+    int xo = (int)ceil(((double)(b0 + 1) - rax.o) / rax.s);
     if (xo < 1) xo = 1;
-    while (xo > 1 && (int)floor(sx * (xo - 1) + ox) >= b0 + 1) xo--;
-    while (xo <= Wd && (int)floor(sx * xo + ox) < b0 + 1) xo++;
+    while (xo > 1 && (int)floor(rax.s * (xo - 1) + rax.o) >= b0 + 1) xo--;
+    while (xo <= Wd && (int)floor(rax.s * xo + rax.o) < b0 + 1) xo++;
     double *dbase = A.rz.dst + (size_t)blockIdx.z * A.zs + (size_t)(hd ? y : y >> 1);
     const bool writer = hd ? (valid && y < Hd) : (valid && (l & 1) == 0 && (y >> 1) < Hd);
 #pragma unroll
     for (int j = 0; j < SL; j++) {                         // (the conditions are uniform over the 16 rows of a segment: the DPP pairs stay together)
-        const double c = sx * xo + ox;
-        int ixx = (int)floor(c);
-        if (ixx > W - 1) ixx = W - 1;
-        if (ixx < 1) ixx = 1;
-        if (xo <= Wd && ixx == b + j + 1) {
-            const double fx = c - ixx;
+        const ResizeCoord rx = resize_coord(rax, xo);
+        if (xo <= Wd && rx.i == b + j + 1) {
+            const double fx = rx.f;
             const double bb = j + 1 < SL ? x[j + 1 < SL ? j + 1 : j] : nxt;
             const double h = (1 - fx) * x[j] + fx * bb;
             const double hn = dpp_pair_next(h);            // lanes 2k, 2k+1 <- lane 2k+1
@@ -2134,17 +1987,9 @@ __global__ __launch_bounds__(256) void k_resize(double *dst, int Hd, int Wd, int
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= (size_t)Hd * Wd) return;
     const int y = (int)(i % Hd) + 1, x = (int)(i / Hd) + 1;
-    const double sy = (double)Hs / (double)Hd, sx = (double)Ws / (double)Wd;
-    const double oy = 1 - 0.5 - sy * (1 - 0.5), ox = 1 - 0.5 - sx * (1 - 0.5);
-    double r = sy * y + oy, c = sx * x + ox;
-    if (sy < 1) r = r < 1 ? 1 : (r > Hs ? Hs : r);
-    if (sx < 1) c = c < 1 ? 1 : (c > Ws ? Ws : c);
-    int iy = (int)floor(r), ixx = (int)floor(c);
-    if (iy > Hs - 1) iy = Hs - 1;
-    if (ixx > Ws - 1) ixx = Ws - 1;
-    if (iy < 1) iy = 1;
-    if (ixx < 1) ixx = 1;
-    const double fy = r - iy, fx = c - ixx;
+    const ResizeCoord ry = resize_coord(resize_axis(Hs, Hd), y), rx = resize_coord(resize_axis(Ws, Wd), x);
+    const int iy = ry.i, ixx = rx.i;
+    const double fy = ry.f, fx = rx.f;
     const double *p = src + (size_t)(iy - 1) + (size_t)(ixx - 1) * Ps;
     const int dy = Hs > 1 ? 1 : 0; const size_t dx = Ws > 1 ? (size_t)Ps : 0;
     const double r0 = (1 - fx) * p[0] + fx * p[dx];
@@ -2266,6 +2111,7 @@ static void mat3_pow(const IIRCoef &k, int e, double P[9])
     memcpy(P, R, sizeof R);
 }
 static inline int seg_len(int n, int nseg_max) { int sl = (n + nseg_max - 1) / nseg_max; return sl < 4 ? 4 : sl; }
+// M^(SL q), q = 1 .. PAR_G, and M^(len_last - 1) for a line of n samples in segments of SL (k_rows_tol: n = SL, every segment is full -- left padding)
 static void seg_pow(const IIRPair &cf, int n, int SL, SegPow &sp)
 {
     const int nseg = (n + SL - 1) / SL, len_last = n - (nseg - 1) * SL;
@@ -2286,13 +2132,6 @@ static int rt_seg_len(int n, int *ns)
     *ns = 2 * RT_NS;
     for (int m : {24, 32}) if ((n + m - 1) / m <= 2 * RT_NS && n >= 2 * m) return m;
     return 0;
-}
-static void rt_seg_pow(const IIRPair &cf, int SL, SegPow &sp)     // M^(SL q), q = 1 .. PAR_G; M^(SL - 1): all segments are full (left padding)
-{
-    for (int c = 0; c < 2; c++) {
-        for (int q = 1; q <= PAR_G; q++) mat3_pow(cf.c[c], SL * q, sp.P[c][q - 1]);
-        mat3_pow(cf.c[c], SL - 1, sp.Plast[c]);
-    }
 }
 // Where the kernels of one build go: straight onto a stream (profiling spans, SLAMHIP_NO_GRAPH), or into an EXPLICITLY constructed
 // hipGraph -- hipGraphAddKernelNode with the dependencies of a two-lane DAG (lane 0: the dependent chain gradients -> dim 1 -> dim 2
@@ -2557,7 +2396,7 @@ static void launch_rows(BuildSink &B, const LevelRoute &r, int lane, const Plane
 // k_rows_tol over the planes of `ra`: SL samples per segment, NS segments (rt_seg_len's menu: one instantiation each)
 static void launch_rows_tol(BuildSink &B, int lane, int SL, int NS, const RowsTolArgs &ra, int S, const LevelIO &io, const IIRPair &cf)
 {
-    SegPow sp; rt_seg_pow(cf, SL, sp);
+    SegPow sp; seg_pow(cf, SL, SL, sp);
     const dim3 g((io.H + RT_R - 1) / RT_R, ra.n, S), b(RT_R * NS);
 #define RT_GO(SLV, NSV) B.launch((k_rows_tol<SLV, NSV, RT_R>), g, b, 0, lane, ra, io.H, io.W, io.P, cf, sp)
     if (NS != RT_NS) { if (SL == 24) RT_GO(24, 2 * RT_NS); else RT_GO(32, 2 * RT_NS); }      // wide rows: 64 segments
