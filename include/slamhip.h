@@ -137,6 +137,18 @@ int slam_describe(slam_ctx *ctx, const double *image, int H, int W,
                   const int64_t *rc, int n, const int32_t *pattern, int n_bits,
                   double sigma, int window,
                   uint64_t *out_bits, int64_t *out_rc, int *n_out);
+/* describe() (src/extractor.jl:103-105, called at map_manager.jl:106) on the image resident as layer 0 of a device pyramid; no image
+ * upload.  Results identical to slam_describe on the image the pyramid was built from.  Odd window <= 15 (the neighbourhood of a
+ * keypoint is smoothed in LDS: csrc/brief.hip, k_brief_patch); a larger window is SLAM_ERR_ARG. */
+int slam_describe_pyr(slam_ctx *ctx, const slam_pyr *pyr, const int64_t *rc, int n,
+                      const int32_t *pattern, int n_bits, double sigma, int window,
+                      uint64_t *out_bits, int64_t *out_rc, int *n_out);
+/* describe() for the first S members of a pyramid batch in one launch (map_manager.jl:106 called for S streams): stream s owns
+ * rc[off[s] .. off[s+1]) and out_bits / out_rc[out_off[s] .. out_off[s+1]) (as slam_detect_batch; off and out_off hold S + 1 entries).
+ * The caller's out_bits / out_rc hold off[S] keypoints. */
+int slam_describe_batch(slam_ctx *ctx, const slam_pyr *pyr0, int S, const int64_t *rc, const int32_t *off,
+                        const int32_t *pattern, int n_bits, double sigma, int window,
+                        uint64_t *out_bits, int64_t *out_rc, int32_t *out_off);
 
 /* ---- LKPyramid -------------------------------------------------------------- */
 /* LKPyramid(image, levels; sigma, reusable=true) / update!(lk, img) / copy! /
@@ -293,6 +305,17 @@ int slam_kpset_remove(slam_ctx *ctx, slam_kpset *ks, const uint8_t *flags_dev);
  * new keypoints are appended (is_3d = 0, fresh ids).  Needs cap >= max_points + grid_rows x grid_cols. */
 int slam_kpset_detect(slam_ctx *ctx, slam_kpset *ks, const slam_pyr *pyr0, int max_points, int radius, int grid_rows, int grid_cols,
                       int cell_size, double sigma_mask, double min_response);
+/* extract_keypoints! WITH describe (map_manager.jl:98-113: keypoints = detect(...); descriptors, keypoints = describe(...);
+ * add_keypoints_to_frame!) on the lists: detect, drop the candidates whose +-lim box (lim = (window + 1) / 2) leaves the image,
+ * append the survivors (is_3d = 0, fresh consecutive ids), describe them.  desc_dev: S x dcap x (n_bits / 64) words in HBM; the j-th
+ * keypoint appended to stream s by THIS call has id info_dev[2 s] + j and its descriptor at desc_dev[(s dcap + j) words ..];
+ * info_dev[2 s + 1] = number appended (info_dev: S x 2 int64 in HBM).  Descriptors belong to the map point of that id
+ * (map_manager.jl:116-131) and are not carried through compactions.  Enqueue-only, like slam_kpset_detect.
+ * dcap >= grid_rows grid_cols ceil(max_points / (grid_rows grid_cols)); window as slam_describe_pyr. */
+int slam_kpset_detect_describe(slam_ctx *ctx, slam_kpset *ks, const slam_pyr *pyr0, int max_points, int radius,
+                               int grid_rows, int grid_cols, int cell_size, double sigma_mask, double min_response,
+                               const int32_t *pattern, int n_bits, double sigma, int window,
+                               uint64_t *desc_dev, int64_t *info_dev, int dcap);
 /* triangulate_stereo! (mapper.jl:142-183) for every 2-D keypoint with a stereo match: success -> map point Twc[s] X and
  * is_3d = 1, failure -> the stereo observation is dropped.  P1, P2, T21, cam1, cam2 as slam_triangulate; Twc: S x 16.
  * The left and right pixels are used as stored: the set's stereo path is for RECTIFIED, zero-distortion pairs (KITTI, the reference's

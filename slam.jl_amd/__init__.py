@@ -9,7 +9,7 @@ There is no CPU fallback: every function here runs hand-written HIP kernels
 and raises if the library / a HIP device is unavailable."""
 from ._lib import Context, Event, SlamHipError, default_context, load, LIB_PATH  # noqa: F401
 from .params import Camera, Params  # noqa: F401
-from .extractor import Extractor, detect, detect_batch, describe, brief_pattern  # noqa: F401
+from .extractor import Extractor, detect, detect_batch, describe, describe_batch, brief_pattern  # noqa: F401
 from .optical_flow import (LKPyramid, LucasKanade, update_, copy_, deepcopy, has_gradients, fb_tracking_,  # noqa: F401
                            optical_flow_matching, optical_flow_matching_frame, PyramidBatch, optical_flow_matching_batch,
                            optical_flow_matching_batch_kept, pyr_route)

@@ -48,6 +48,8 @@ SIGNATURES = {
     "slam_five_point_ransac_batch": (cint, [vp, cint, i32p, f64p, f64p, f64p, f64p, f64p, f64p, dbl, i32p, cint, f64p, f64p, u8p, i32p, f64p, i32p]),
     "slam_pnp_ba_batch": (cint, [vp, cint, i32p, f64p, f64p, f64p, f64p, cint, cint, dbl, dbl, f64p, f64p, f64p, u8p, i32p]),
     "slam_describe": (cint, [vp, f64p, cint, cint, i64p, cint, i32p, cint, dbl, cint, u64p, i64p, C.POINTER(cint)]),
+    "slam_describe_pyr": (cint, [vp, vp, i64p, cint, i32p, cint, dbl, cint, u64p, i64p, C.POINTER(cint)]),
+    "slam_describe_batch": (cint, [vp, vp, cint, i64p, i32p, i32p, cint, dbl, cint, u64p, i64p, i32p]),
     "slam_pyr_create": (cint, [vp, cint, cint, cint, C.POINTER(vp)]),
     "slam_pyr_destroy": (cint, [vp]),
     "slam_pyr_update": (cint, [vp, vp, f64p, cint, dbl]),
@@ -84,6 +86,7 @@ SIGNATURES = {
     "slam_kpset_stereo_match": (cint, [vp, vp, vp, vp, f64p, cint, cint, cint, cint, cint, dbl, dbl, dbl, dbl, cint]),
     "slam_kpset_remove": (cint, [vp, vp, vp]),
     "slam_kpset_detect": (cint, [vp, vp, vp, cint, cint, cint, cint, cint, dbl, dbl]),
+    "slam_kpset_detect_describe": (cint, [vp, vp, vp, cint, cint, cint, cint, cint, dbl, dbl, i32p, cint, dbl, cint, vp, vp, cint]),
     "slam_kpset_triangulate": (cint, [vp, vp, f64p, f64p, f64p, f64p, f64p, f64p, dbl, dbl, cint]),
     "slam_kpset_keyframe": (cint, [vp, vp]),
     "slam_kpset_triangulate_temporal": (cint, [vp, vp, f64p, f64p, cint, i32p, i32p, dbl, dbl, dbl, cint]),

@@ -28,6 +28,11 @@ struct slam_ctx {
     hipEvent_t wait_event = nullptr;      // slam_ctx_wait_for
     hipStream_t stream2 = nullptr;        // a second stream of the same scheduling class (ctx_aux_stream: the second half of a batch of BA windows), with its fork / join events
     hipEvent_t fork_ev = nullptr, join_ev = nullptr;
+    // the BRIEF sampling table of the device-pyramid describe forms (brief.hip): the copy in HBM, the host's copy of what it holds, and
+    // the pinned block + event an upload goes through (a table that did not change is not uploaded again)
+    int32_t *brief_pat_dev = nullptr, *brief_pat_pin = nullptr; size_t brief_pat_cap = 0;
+    std::vector<int32_t> brief_pat_host;
+    hipEvent_t brief_pat_ev = nullptr;
     // optional device-side timing (hipEvents on ctx->stream), see slam_prof_*
     bool prof_on = false;
     struct ProfSpan { int id; hipEvent_t a, b; };
@@ -165,6 +170,23 @@ struct PnPArgs {
     uint8_t *outl; double *result;   // [X(6), err_init, err_final, n_outliers, identity, iters1, iters2]
 };
 int pnp_launch_device(slam_ctx *ctx, int S, const PnPArgs *args_dev);     // S problems, argument blocks already in device memory
+
+// describe() on device-resident pyramids (brief.hip): one launch of k_brief_patch, by value.  List form (rc != nullptr): n keypoints that passed
+// the box test, keypoint k in batch member `member[k]` (nullptr: member 0), descriptor k at out + k words.  Set form (rc == nullptr, grid.y =
+// stream): the slots [cnt0[z], count[z]) of stream z's list, the j-th of them at out + (z dcap + j) words; info[2 z + 1] = their number.
+#define BRIEF_PATCH_MAXWIN 15
+struct BriefJob {
+    const double *img; int H, W, P; size_t zs;                    // level-0 `layers` plane of member 0, column pitch P, member z at img + z zs
+    const int32_t *pattern; int n_bits, window;
+    const int64_t *rc; const int32_t *member; int n;
+    const double *yx; const int *cnt0, *count; int cap, dcap; int64_t *info;
+    uint64_t *out;
+    double w[BRIEF_PATCH_MAXWIN];
+};
+// argument checks, the Gaussian taps and the sampling table in HBM (uploaded only when it differs from the copy held); J.img .. J.window filled
+int brief_prepare(slam_ctx *ctx, const char *who, const double *img, int H, int W, int P, size_t zs, const int32_t *pattern, int n_bits,
+                  double sigma, int window, BriefJob *J);
+int brief_launch(slam_ctx *ctx, const BriefJob &J, int per_stream, int S);      // list form: per_stream = n, S = 1
 
 // kpset plumbing shared by kpset.hip / lk.hip / detect.hip
 int kpset_build_worklist(slam_ctx *ctx, slam_kpset *ks, int H, int W);   // H <= 0: slot order (no image, or an order would not pay)

@@ -232,6 +232,9 @@ int slam_ctx_destroy(slam_ctx *ctx)
     if (ctx->scratch) (void)hipFree(ctx->scratch);
     if (ctx->scratch2) (void)hipFree(ctx->scratch2);
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
+    if (ctx->brief_pat_dev) (void)hipFree(ctx->brief_pat_dev);
+    if (ctx->brief_pat_pin) (void)hipHostFree(ctx->brief_pat_pin);
+    if (ctx->brief_pat_ev) (void)hipEventDestroy(ctx->brief_pat_ev);
     if (ctx->wait_event) (void)hipEventDestroy(ctx->wait_event);
     if (ctx->stream2) { (void)hipStreamSynchronize(ctx->stream2); (void)hipStreamDestroy(ctx->stream2); }
     if (ctx->fork_ev) (void)hipEventDestroy(ctx->fork_ev);

@@ -728,3 +728,72 @@ extern "C" int slam_kpset_detect(slam_ctx *ctx, slam_kpset *ks, const slam_pyr *
     HIP_TRY(ctx, hipGetLastError());
     return SLAM_OK;
 }
+
+// describe()'s border drop on the cell lists (map_manager.jl:105-106: detect, then describe returns the keypoints it kept): every cell's
+// candidates whose +-lim box leaves the image go, order kept, before detect_append merges the lists -- the dropped ones are not replaced, as in
+// the reference.  One thread per cell (a list holds the cell's quota, a handful of entries); kz as in detect_append.  The thread of cell 0 notes
+// the stream's list length and id counter before the append (cnt0, info[2 z]).
+__global__ __launch_bounds__(256) void detect_box_filter(int64_t *cell_out, int *cell_cnt, int n_cells, int kmax, int max_points, const int *count,
+                                                          const int64_t *next_id, int H, int W, int lim, int *cnt0, int64_t *info)
+{
+    const int z = blockIdx.y, c = blockIdx.x * 256 + threadIdx.x;
+    const int n0 = count[z];
+    if (c == 0) { cnt0[z] = n0; info[2 * z] = next_id[z]; }
+    if (c >= n_cells || n0 >= max_points) return;
+    const int kz = (max_points - n0 + n_cells - 1) / n_cells;
+    int64_t *o = cell_out + ((size_t)z * n_cells * kmax + (size_t)c * kz) * 2;
+    int *pc = cell_cnt + (size_t)z * n_cells + c;
+    const int cnt = *pc;
+    int m = 0;
+    for (int i = 0; i < cnt; i++) {
+        const int64_t y = o[2 * i], x = o[2 * i + 1];
+        if (y - lim < 1 || y + lim > H || x - lim < 1 || x + lim > W) continue;
+        o[2 * m] = y; o[2 * m + 1] = x; m++;
+    }
+    *pc = m;
+}
+
+// extract_keypoints! with describe (map_manager.jl:98-113) on the lists: detect_cells, the border drop, detect_append, k_brief_patch over
+// the appended slots.  Enqueue-only.
+extern "C" int slam_kpset_detect_describe(slam_ctx *ctx, slam_kpset *ks, const slam_pyr *pyr0, int max_points, int radius, int grid_rows, int grid_cols,
+                                          int cell_size, double sigma_mask, double min_response, const int32_t *pattern, int n_bits, double sigma,
+                                          int window, uint64_t *desc_dev, int64_t *info_dev, int dcap)
+{
+    ARG_TRY(ctx, ctx != nullptr && ks != nullptr && pyr0 != nullptr && desc_dev != nullptr && info_dev != nullptr);
+    const int S = ks->S;
+    ARG_TRY(ctx, pyr0->batch_index == 0 && pyr0->batch_size >= S);
+    ARG_TRY(ctx, grid_rows > 0 && grid_cols > 0 && cell_size >= 8 && radius > 0 && radius <= DET_MAXR && max_points > 0);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int n_cells = grid_rows * grid_cols;
+    const int kmax = (max_points + n_cells - 1) / n_cells;         // n_cur = 0
+    ARG_TRY(ctx, ks->cap >= max_points + n_cells);
+    if (dcap < n_cells * kmax)
+        return slam_fail(ctx, SLAM_ERR_ARG, "slam_kpset_detect_describe: dcap = %d, a key-frame may append %d keypoints per stream", dcap, n_cells * kmax);
+    BriefJob J;
+    int rc = brief_prepare(ctx, "slam_kpset_detect_describe", pyr0->plane(0, 0), pyr0->H[0], pyr0->W[0], pyr0->P[0], pyr0->zstride, pattern, n_bits,
+                           sigma, window, &J);
+    if (rc) return rc;
+    DetectArgs A;
+    size_t lds_bytes;
+    rc = det_plan(ctx, A, pyr0->plane(0, 0), pyr0->H[0], pyr0->W[0], pyr0->P[0], pyr0->zstride, max_points, radius, grid_rows, grid_cols, cell_size, kmax,
+                  sigma_mask, min_response, &lds_bytes);
+    if (rc) return rc;
+    A.cur = ks->yx; A.cur_cnt = ks->count; A.cur_stride = ks->cap;
+    Layout D;
+    const size_t o_cnt = D.take((size_t)S * n_cells * 4), o_cout = D.take((size_t)S * n_cells * kmax * 16), o_c0 = D.take((size_t)S * 4);
+    char *d;
+    rc = slam_scratch(ctx, D.size(), (void **)&d);
+    if (rc) return rc;
+    A.cell_cnt = (int *)(d + o_cnt); A.cell_out = (int64_t *)(d + o_cout);
+    int *cnt0 = (int *)(d + o_c0);
+    { ProfScope span(ctx, "detect");
+      { ProfScope cells(ctx, "detect_cells");                       // (the yardstick scripts/probes/prof_describe.py quotes the describe stage against)
+        hipLaunchKernelGGL(detect_cells, dim3(n_cells, S), dim3(DET_THREADS), lds_bytes, ctx->stream, A); }
+      hipLaunchKernelGGL(detect_box_filter, dim3((n_cells + 255) / 256, S), dim3(256), 0, ctx->stream, A.cell_out, A.cell_cnt, n_cells, kmax, max_points,
+                         (const int *)ks->count, (const int64_t *)ks->next_id, pyr0->H[0], pyr0->W[0], (window + 1) / 2, cnt0, info_dev);
+      hipLaunchKernelGGL(detect_append, dim3(S), dim3(1024), 0, ctx->stream, (const int64_t *)A.cell_out, (const int *)A.cell_cnt, n_cells, kmax, max_points,
+                         ks->yx, ks->syx, ks->xyz, ks->id, ks->is3d, ks->stereo, ks->haskf, ks->count, ks->next_id, ks->cap); }
+    HIP_TRY(ctx, hipGetLastError());
+    J.yx = ks->yx; J.cnt0 = cnt0; J.count = ks->count; J.cap = ks->cap; J.dcap = dcap; J.info = info_dev; J.out = desc_dev;
+    return brief_launch(ctx, J, n_cells * kmax, S);
+}

@@ -89,16 +89,52 @@ def brief_pattern(size=256, window=9, seed=123):
 
 
 def describe(e, image, keypoints, pattern=None, sigma=np.sqrt(2.0), window=9, ctx=None):
-    """describe(e, image, keypoints) -> (descriptors (n', 4) uint64, keypoints (n', 2) int64)."""
+    """describe(e, image, keypoints) -> (descriptors (n', n_bits / 64) uint64, keypoints (n', 2) int64).
+
+    `image` is an H x W float64 array or an LKPyramid, in which case its device-resident base layer is described
+    (slam_describe_pyr: nothing is uploaded but the keypoints; odd window <= 15)."""
+    from .optical_flow import LKPyramid
     ctx = ctx or L.default_context()
-    img = np.asfortranarray(image, dtype=np.float64)
-    H, W = img.shape
     rc_in = np.ascontiguousarray(keypoints, dtype=np.int64).reshape(-1, 2)
     pat = np.ascontiguousarray(brief_pattern() if pattern is None else pattern, dtype=np.int32).reshape(-1, 4)
     nb = len(pat)
     bits = np.zeros((len(rc_in), nb // 64), dtype=np.uint64)
     out_rc = np.zeros((len(rc_in), 2), dtype=np.int64)
     n = C.c_int(0)
-    ctx.check(ctx.lib.slam_describe(ctx.h, L.ptr(img), H, W, L.ptr(rc_in, L.i64p), len(rc_in), L.ptr(pat, L.i32p), nb,
-                                    float(sigma), int(window), L.ptr(bits, L.u64p), L.ptr(out_rc, L.i64p), C.byref(n)))
+    if isinstance(image, LKPyramid):
+        ctx.check(ctx.lib.slam_describe_pyr(ctx.h, image.h, L.ptr(rc_in, L.i64p), len(rc_in), L.ptr(pat, L.i32p), nb,
+                                            float(sigma), int(window), L.ptr(bits, L.u64p), L.ptr(out_rc, L.i64p), C.byref(n)))
+    else:
+        img = np.asfortranarray(image, dtype=np.float64)
+        H, W = img.shape
+        ctx.check(ctx.lib.slam_describe(ctx.h, L.ptr(img), H, W, L.ptr(rc_in, L.i64p), len(rc_in), L.ptr(pat, L.i32p), nb,
+                                        float(sigma), int(window), L.ptr(bits, L.u64p), L.ptr(out_rc, L.i64p), C.byref(n)))
     return bits[:n.value].copy(), out_rc[:n.value].copy()
+
+
+def describe_batch(e, batch, keypoints, stream_index, pattern=None, sigma=np.sqrt(2.0), window=9, ctx=None):
+    """describe() for every stream of a PyramidBatch in one launch (slam_describe_batch).
+
+    keypoints (n, 2) with stream_index (n,) sorted ascending (keypoints of stream s contiguous).
+    Returns (descriptors (m, n_bits / 64) uint64, keypoints (m, 2) int64, stream_index (m,) int32), grouped by stream."""
+    ctx = ctx or batch.ctx
+    S = batch.S
+    rc_in = np.ascontiguousarray(keypoints, dtype=np.int64).reshape(-1, 2)
+    sid = np.asarray(stream_index, dtype=np.int64).reshape(-1)
+    if len(sid) != len(rc_in):
+        raise ValueError("describe_batch: one stream index per keypoint")
+    if len(sid) and (sid.min() < 0 or sid.max() >= S):
+        raise ValueError("describe_batch: stream_index outside the batch")
+    if len(sid) > 1 and np.any(np.diff(sid) < 0):
+        raise ValueError("describe_batch: keypoints must be grouped by ascending stream_index")
+    off = np.zeros(S + 1, dtype=np.int32)
+    off[1:] = np.cumsum(np.bincount(sid, minlength=S)[:S])
+    pat = np.ascontiguousarray(brief_pattern() if pattern is None else pattern, dtype=np.int32).reshape(-1, 4)
+    nb = len(pat)
+    bits = np.zeros((len(rc_in), nb // 64), dtype=np.uint64)
+    out_rc = np.zeros((len(rc_in), 2), dtype=np.int64)
+    out_off = np.zeros(S + 1, dtype=np.int32)
+    ctx.check(ctx.lib.slam_describe_batch(ctx.h, batch.pyramids[0].h, S, L.ptr(rc_in, L.i64p), L.ptr(off, L.i32p), L.ptr(pat, L.i32p), nb,
+                                          float(sigma), int(window), L.ptr(bits, L.u64p), L.ptr(out_rc, L.i64p), L.ptr(out_off, L.i32p)))
+    m = int(out_off[S])
+    return bits[:m].copy(), out_rc[:m].copy(), np.repeat(np.arange(S, dtype=np.int32), np.diff(out_off))

@@ -80,6 +80,16 @@ function brief_table(e::Extractor)
     t
 end
 
+function unpack_descriptors(d, bits::Matrix{UInt64}, orc::Matrix{Int64}, m::Integer)
+    descriptors = BitVector[]
+    for i in 1:m
+        b = falses(d.size)
+        for k in 0:(d.size - 1); b[k + 1] = (bits[k ÷ 64 + 1, i] >> (k % 64)) & 1 == 1; end
+        push!(descriptors, b)
+    end
+    descriptors, [CartesianIndex{2}(orc[1, i], orc[2, i]) for i in 1:m]
+end
+
 function hip_describe(e::Extractor, image, keypoints)
     H, W = size(image)
     n = length(keypoints)
@@ -92,13 +102,23 @@ function hip_describe(e::Extractor, image, keypoints)
     GC.@preserve image rc table bits orc check(ccall((:slam_describe, LIB[]), Cint,
         (Ptr{Cvoid}, Ptr{Float64}, Cint, Cint, Ptr{Int64}, Cint, Ptr{Int32}, Cint, Cdouble, Cint, Ptr{UInt64}, Ptr{Int64}, Ref{Cint}),
         ctx(), rawptr(image), H, W, rc, n, table, d.size, Float64(d.sigma), d.window, bits, orc, m))
-    descriptors = BitVector[]
-    for i in 1:m[]
-        b = falses(d.size)
-        for k in 0:(d.size - 1); b[k + 1] = (bits[k ÷ 64 + 1, i] >> (k % 64)) & 1 == 1; end
-        push!(descriptors, b)
-    end
-    descriptors, [CartesianIndex{2}(orc[1, i], orc[2, i]) for i in 1:m[]]
+    unpack_descriptors(d, bits, orc, m[])
+end
+
+# describe(e, pyr::LKPyramid, keypoints): the image is layer 1 of the pyramid's device twin (the frame the key-frame's pyramid was built from,
+# map_manager.jl:105-106) -- nothing but the keypoints is uploaded.  Odd windows up to 15 (ImageFeatures' BRIEF default is 9).
+function hip_describe(e::Extractor, pyr::LKPyramid, keypoints)
+    n = length(keypoints)
+    d = e.descriptor
+    rc = Matrix{Int64}(undef, 2, n)
+    for (i, k) in enumerate(keypoints); rc[1, i] = k[1]; rc[2, i] = k[2]; end
+    table = brief_table(e)
+    words = d.size ÷ 64
+    bits = Matrix{UInt64}(undef, words, n); orc = Matrix{Int64}(undef, 2, n); m = Ref{Cint}(0)
+    GC.@preserve rc table bits orc check(ccall((:slam_describe_pyr, LIB[]), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int64}, Cint, Ptr{Int32}, Cint, Cdouble, Cint, Ptr{UInt64}, Ptr{Int64}, Ref{Cint}),
+        ctx(), handle(pyr), rc, n, table, d.size, Float64(d.sigma), d.window, bits, orc, m))
+    unpack_descriptors(d, bits, orc, m[])
 end
 
 # ---- LKPyramid (src/optical_flow/pyramid.jl) ------------------------------------

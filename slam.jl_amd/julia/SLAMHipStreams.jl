@@ -25,7 +25,7 @@ module SLAMHipStreams
 
 import ..SLAMHip: LIB, ctx, check
 
-export PyramidBatch, FrameRing, KeypointSet, upload!, update!, flow_match!, stereo_match!, remove!, detect!, keyframe!,
+export PyramidBatch, FrameRing, KeypointSet, upload!, update!, flow_match!, stereo_match!, remove!, detect!, detect_describe!, describe_batch, keyframe!,
        triangulate!, triangulate_temporal!, compute_pose_5pt!, compute_pose!, counts, download, stream_params
 
 const HIP = "libamdhip64"
@@ -164,6 +164,31 @@ function detect!(k::KeypointSet, cur::PyramidBatch, e; σ_mask = 3.0, min_respon
     check(ccall((:slam_kpset_detect, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cint, Cint, Cint, Cint, Cdouble, Cdouble),
         ctx(), k.h, cur.handles[1], e.max_points, e.radius, e.grid_resolution[1], e.grid_resolution[2], e.cell_size, Float64(σ_mask), min_response))
     k
+end
+
+# extract_keypoints! with describe (map_manager.jl:98-113): as detect!, but the candidates describe() drops at the border are not appended and
+# the appended ones are described.  table: 4 x n_bits Int32 (SLAMHip.brief_table(e)); desc_dev: S x dcap x (n_bits ÷ 64) UInt64 and info_dev:
+# S x 2 Int64 in HBM (hipMalloc) -- the j-th keypoint (0-based) this call appends to stream s (0-based) has id info[2 s] + j and its descriptor at
+# desc[(s dcap + j) words ..]; info[2 s + 1] keypoints were appended.  dcap ≥ cells * cld(e.max_points, cells).  Enqueue-only.
+function detect_describe!(k::KeypointSet, cur::PyramidBatch, e, table::Matrix{Int32}, desc_dev::Ptr{UInt64}, info_dev::Ptr{Int64}, dcap::Integer;
+                          σ_mask = 3.0, min_response = 1e-4, σ = sqrt(2.0), window = 9)
+    GC.@preserve table check(ccall((:slam_kpset_detect_describe, LIB[]), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cint, Cint, Cint, Cint, Cdouble, Cdouble, Ptr{Int32}, Cint, Cdouble, Cint, Ptr{UInt64}, Ptr{Int64}, Cint),
+        ctx(), k.h, cur.handles[1], e.max_points, e.radius, e.grid_resolution[1], e.grid_resolution[2], e.cell_size, Float64(σ_mask), min_response,
+        table, size(table, 2), Float64(σ), window, desc_dev, info_dev, dcap))
+    k
+end
+
+# describe() for every stream of a batch in one launch: rc 2 x n Int64 (row, col) grouped by stream, off S + 1 Int32 (0-based offsets, off[1] = 0).
+# Returns (bits words x m, rc 2 x m, out_off S + 1): stream s (1-based) owns the columns out_off[s] + 1 : out_off[s + 1].
+function describe_batch(cur::PyramidBatch, rc::Matrix{Int64}, off::Vector{Int32}, table::Matrix{Int32}; σ = sqrt(2.0), window = 9)
+    S = length(cur); n = size(rc, 2); words = size(table, 2) ÷ 64
+    bits = Matrix{UInt64}(undef, words, n); orc = Matrix{Int64}(undef, 2, n); out_off = zeros(Int32, S + 1)
+    GC.@preserve rc off table bits orc out_off check(ccall((:slam_describe_batch, LIB[]), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Int64}, Ptr{Int32}, Ptr{Int32}, Cint, Cdouble, Cint, Ptr{UInt64}, Ptr{Int64}, Ptr{Int32}),
+        ctx(), cur.handles[1], S, rc, off, table, size(table, 2), Float64(σ), window, bits, orc, out_off))
+    m = Int(out_off[S + 1])
+    bits[:, 1:m], orc[:, 1:m], out_off
 end
 
 # create_keyframe! as far as the lists go (map_manager.jl:60-96); call after detect!

@@ -105,6 +105,19 @@ class KeypointSet:
         c.check(c.lib.slam_kpset_detect(c.h, self.h, batch.pyramids[0].h, e.max_points, e.radius, e.grid_resolution[0], e.grid_resolution[1],
                                         e.cell_size, float(sigma_mask), float(min_response)))
 
+    def detect_describe(self, e, batch, desc_ptr, info_ptr, dcap, pattern=None, sigma=np.sqrt(2.0), window=9, sigma_mask=3.0, min_response=1e-4,
+                        ctx=None):
+        """extract_keypoints! with describe (map_manager.jl:98-113) on the lists (slam_kpset_detect_describe): the candidates describe() would
+        drop at the border are not appended, the appended ones are described.  desc_ptr: device pointer to S x dcap x (n_bits / 64) uint64,
+        info_ptr: device pointer to S x 2 int64 (first id, number appended), e.g. torch_tensor.data_ptr(); the j-th keypoint this call
+        appends to stream s has its descriptor at [s, j].  dcap >= cells * ceil(max_points / cells).  Enqueue-only."""
+        from .extractor import brief_pattern
+        c = ctx or self.ctx
+        pat = np.ascontiguousarray(brief_pattern() if pattern is None else pattern, dtype=np.int32).reshape(-1, 4)
+        c.check(c.lib.slam_kpset_detect_describe(c.h, self.h, batch.pyramids[0].h, e.max_points, e.radius, e.grid_resolution[0], e.grid_resolution[1],
+                                                 e.cell_size, float(sigma_mask), float(min_response), L.ptr(pat, L.i32p), len(pat), float(sigma),
+                                                 int(window), C.c_void_p(desc_ptr), C.c_void_p(info_ptr), int(dcap)))
+
     def triangulate(self, cam1, cam2, T21, Twc, max_error, min_depth=0.1, n_bound=0, ctx=None):
         from .triangulation import projection_matrices
         c = ctx or self.ctx
