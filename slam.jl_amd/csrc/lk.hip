@@ -17,15 +17,23 @@
 // reference's single-accumulator order only in rounding (<= 1e-12 px observed).
 #include "common.hpp"
 #include "geom_device.hpp"
+#include "work_order.hpp"
 #include <vector>
 #include <cmath>
 #include <cstdlib>
+#include <type_traits>
 
+// the tuning values of a match, as every seam takes them (levels3d: the levels of the 3-D prior attempt; 0 for slam_fb_track)
+struct LKTune {
+    int pyramid_levels, levels3d, window, iterations;
+    double eig_thr, eps, max_distance;
+    bool nonneg() const { return pyramid_levels >= 0 && levels3d >= 0 && window >= 0 && iterations >= 0; }
+};
 struct LKArgs {
     PyrView prev, cur;
     const double *pts, *disp0;
-    int n, pyramid_levels, window, iterations;
-    double eig_thr, eps, max_distance;
+    int n;
+    LKTune tune;
     double *out;
     uint8_t *status;
 };
@@ -301,7 +309,7 @@ __device__ __forceinline__ bool lk_level(const LevelView &first, const LevelView
     const int p0 = (int)floor(pty * iscale), p1 = (int)floor(ptx * iscale);
     const double pf0 = (double)p0, pf1 = (double)p1;
     LKT_BEGIN;
-    const bool cached = (2 * window + 1) * (2 * window + 1) <= 64 * LK_MAXE;
+    const bool cached = lk_window_elems(window) <= 64 * LK_MAXE;          // the instantiation lk_launch chose holds the window (work_order.hpp)
     Tmpl<LK_MAXE> T;
     constexpr int PS = PatchGeom<LK_MAXE>::PS;
     __shared__ __attribute__((aligned(16))) double lds_patch[PS * PS];
@@ -435,13 +443,13 @@ __device__ __forceinline__ LevelView shifted(const LevelView &v, size_t off)
     return r;
 }
 
-// offP / offC: plane offset (doubles) of this point's image inside a pyramid batch (0 for single pyramids).
+// offP / offC: plane offset (doubles) of this point's image inside a pyramid batch (0 for single pyramids); pyramid_levels: this attempt's level
+// count.  The tune travels BY VALUE: through a reference every tracking kernel comes out with other register names and another schedule.
 // The forward levels and the backward pass run through ONE inlined copy of lk_level (a loop over passes with the
 // roles of the two pyramids swapped for the last one): the tracking kernels are a few KB instead of ~100 KB.
 template <int LK_MAXE, bool TOL = false>
 __device__ __forceinline__ bool fb_point(const PyrView &prev, const PyrView &cur, double py, double px, double dy, double dx,
-                                         int pyramid_levels, int window, int iterations, double eig_thr, double eps,
-                                         double max_distance, double &ny, double &nx, size_t offP = 0, size_t offC = 0)
+                                         LKTune t, int pyramid_levels, double &ny, double &nx, size_t offP = 0, size_t offC = 0)
 {
     double qy = py, qx = px, cy = dy, cx = dx;
     for (int k = 0; k <= pyramid_levels + 1; k++) {
@@ -455,12 +463,12 @@ __device__ __forceinline__ bool fb_point(const PyrView &prev, const PyrView &cur
         // backward: pyramid_levels = 0, default eps 1e-2 (tracker.jl:34,51-57)
         const PyrView *pf = back ? &cur : &prev, *ps = back ? &prev : &cur;
         const bool ok = lk_level<LK_MAXE, TOL>(shifted(pf->lv[level - 1], back ? offC : offP), shifted(ps->lv[level - 1], back ? offP : offC),
-                                          level, qy, qx, cy, cx, window, iterations, eig_thr, back ? 1e-2 : eps);
+                                          level, qy, qx, cy, cx, t.window, t.iterations, t.eig_thr, back ? 1e-2 : t.eps);
         if (!ok) return false;
     }
     const double b0 = ny + cy, b1 = nx + cx;
     const double d0 = py - b0, d1 = px - b1;
-    return !(sqrt(d0 * d0 + d1 * d1) >= max_distance);
+    return !(sqrt(d0 * d0 + d1 * d1) >= t.max_distance);
 }
 
 // Workgroups are dealt round-robin to the 8 XCDs (workgroup b runs on XCD b % 8) and every XCD has its own L2.
@@ -487,8 +495,7 @@ __global__ __launch_bounds__(64) LK_OCC void k_fb_track(LKArgs A)
     const double py = A.pts[2 * i], px = A.pts[2 * i + 1];
     const double dy = A.disp0 ? A.disp0[2 * i] : 0.0, dx = A.disp0 ? A.disp0[2 * i + 1] : 0.0;
     double ny = nan(""), nx = nan("");
-    const bool ok = fb_point<LK_MAXE>(A.prev, A.cur, py, px, dy, dx, A.pyramid_levels, A.window, A.iterations, A.eig_thr, A.eps,
-                             A.max_distance, ny, nx);
+    const bool ok = fb_point<LK_MAXE>(A.prev, A.cur, py, px, dy, dx, A.tune, A.tune.pyramid_levels, ny, nx);
     if ((threadIdx.x & 63) == 0) {
         A.out[2 * i] = ny; A.out[2 * i + 1] = nx;
         A.status[i] = ok ? 1 : 0;
@@ -503,7 +510,7 @@ __global__ __launch_bounds__(64) LK_OCC void k_fb_track(LKArgs A)
 // per-point control flow.
 struct FlowArgs {
     LKArgs lk;
-    const uint8_t *is3d; const double *proj; int levels3d;
+    const uint8_t *is3d; const double *proj;
     const int *img;            // batched call: image index of each point inside the pyramid batches (nullptr: single pyramids)
     size_t zs_from, zs_to;     // batch strides (doubles) of the from / to pyramids
 };
@@ -519,15 +526,14 @@ __global__ __launch_bounds__(64) LK_OCC void k_flow_match(FlowArgs F)
     bool ok = false;
     const size_t zi = F.img ? (size_t)F.img[i] : 0;
     const size_t offP = zi * F.zs_from, offC = zi * F.zs_to;
-    // attempt 0: 3-D point with its projected prior; attempt 1: no prior, all levels (one inlined fb_point)
+    // attempt 0: 3-D point with its projected prior; attempt 1: no prior, all levels (one inlined fb_point; k_kpset_match mirrors this loop)
     for (int att = F.is3d[i] ? 0 : 1; att < 2 && !ok; att++) {
         double dy = 0.0, dx = 0.0;
         if (att == 0) {
-            const double scale = 1.0 / (double)(1 << F.levels3d);
+            const double scale = 1.0 / (double)(1 << A.tune.levels3d);
             dy = scale * (F.proj[2 * i] - py); dx = scale * (F.proj[2 * i + 1] - px);                // map_manager.jl:494,504
         }
-        ok = fb_point<LK_MAXE>(A.prev, A.cur, py, px, dy, dx, att == 0 ? F.levels3d : A.pyramid_levels, A.window, A.iterations, A.eig_thr, A.eps,
-                               A.max_distance, ny, nx, offP, offC);
+        ok = fb_point<LK_MAXE>(A.prev, A.cur, py, px, dy, dx, A.tune, att == 0 ? A.tune.levels3d : A.tune.pyramid_levels, ny, nx, offP, offC);
     }
     LKT(0);
     if ((threadIdx.x & 63) == 0) {
@@ -548,7 +554,7 @@ __global__ __launch_bounds__(64) LK_OCC void k_flow_match(FlowArgs F)
 // [16..19] fx fy cx cy, [20..23] k1 k2 p1 p2 of the target camera, [24..25] prior shift (y, x).
 struct KpMatchArgs {
     PyrView from, to; size_t zs_from, zs_to;
-    int pyramid_levels, levels3d, window, iterations; double eig_thr, eps, max_distance;
+    LKTune tune;
     double *yx, *oyx, *syx; const double *xyz; const uint8_t *is3d; uint8_t *st, *stereo; int cap;
     const int *work, *ntot;
     int prior;                 // 0: prior = the pixel itself, 1: projection of the map point (pose-based), 2: pixel + per-stream shift
@@ -589,14 +595,13 @@ __global__ __launch_bounds__(64) LK_OCC void k_kpset_match(KpMatchArgs M)
     const size_t offF = (size_t)s * M.zs_from, offT = (size_t)s * M.zs_to;
     double ny = nan(""), nx = nan("");
     bool ok = false;
-    for (int att = is3 ? 0 : 1; att < 2 && !ok; att++) {
+    for (int att = is3 ? 0 : 1; att < 2 && !ok; att++) {                                             // mirrors k_flow_match's two attempts
         double dy = 0.0, dx = 0.0;
         if (att == 0) {
-            const double scale = 1.0 / (double)(1 << M.levels3d);
+            const double scale = 1.0 / (double)(1 << M.tune.levels3d);
             dy = scale * (pry - py); dx = scale * (prx - px);                                        // map_manager.jl:494,504
         }
-        ok = fb_point<LK_MAXE, TOL>(M.from, M.to, py, px, dy, dx, att == 0 ? M.levels3d : M.pyramid_levels, M.window, M.iterations, M.eig_thr, M.eps,
-                               M.max_distance, ny, nx, offF, offT);
+        ok = fb_point<LK_MAXE, TOL>(M.from, M.to, py, px, dy, dx, M.tune, att == 0 ? M.tune.levels3d : M.tune.pyramid_levels, ny, nx, offF, offT);
     }
     if (lane0 && !M.stereo_mode) {
         M.oyx[2 * q] = ok ? ny : nan(""); M.oyx[2 * q + 1] = ok ? nx : nan("");
@@ -614,27 +619,44 @@ __global__ __launch_bounds__(64) LK_OCC void k_kpset_match(KpMatchArgs M)
     }
 }
 
+// ---- host ----------------------------------------------------------------------------------------------------------------------
+// f(std::integral_constant<int, N>) for the instantiation a window_size runs on (lk_slots, work_order.hpp; lk_level's `cached` is its device side)
+template <class F> static void lk_launch(int window, F f)
+{
+    switch (lk_slots(window)) {
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    case 6: f(std::integral_constant<int, 6>{}); break;
+    default: f(std::integral_constant<int, 9>{});
+    }
+}
+
+// what every match requires of its two pyramids (the seam's own argument checks, t.nonneg() among them, come before the array seams' n == 0 exit)
+static int match_check(slam_ctx *ctx, const slam_pyr *from, const slam_pyr *to, const LKTune &t)
+{
+    const int need = t.pyramid_levels > t.levels3d ? t.pyramid_levels : t.levels3d;
+    if (!(from->levels > need && to->levels > need)) return slam_fail(ctx, SLAM_ERR_LAYERS, "Not enough layers in pyramids.");   // lucas_kanade.jl:12-15
+    ARG_TRY(ctx, from->H[0] == to->H[0] && from->W[0] == to->W[0]);
+    if (from->target_only) return slam_fail(ctx, SLAM_ERR_ARG, "the source pyramid of a match was updated with SLAM_PYR_TARGET_ONLY: its gradient planes exist at level 0 only");
+    return SLAM_OK;
+}
+
 static int kpset_match(slam_ctx *ctx, slam_kpset *ks, const slam_pyr *from0, const slam_pyr *to0, const double *params,
-                       int prior, int pyramid_levels, int levels3d, int window, int iterations, double eig_thr, double eps,
-                       double max_distance, int stereo_mode, double epipolar, int n_bound)
+                       int prior, const LKTune &t, int stereo_mode, double epipolar, int n_bound)
 {
     ARG_TRY(ctx, ctx != nullptr && ks != nullptr && from0 != nullptr && to0 != nullptr);
     ARG_TRY(ctx, from0->batch_index == 0 && to0->batch_index == 0 && from0->batch_size >= ks->S && to0->batch_size >= ks->S);
-    ARG_TRY(ctx, pyramid_levels >= 0 && levels3d >= 0 && window >= 0 && iterations >= 0 && prior >= 0 && prior <= 2 && (prior == 0 || params != nullptr));
-    const int need = pyramid_levels > levels3d ? pyramid_levels : levels3d;
-    if (!(from0->levels > need && to0->levels > need)) return slam_fail(ctx, SLAM_ERR_LAYERS, "Not enough layers in pyramids.");
-    ARG_TRY(ctx, from0->H[0] == to0->H[0] && from0->W[0] == to0->W[0]);
-    if (from0->target_only) return slam_fail(ctx, SLAM_ERR_ARG, "the source pyramid of a match was updated with SLAM_PYR_TARGET_ONLY: its gradient planes exist at level 0 only");
+    ARG_TRY(ctx, t.nonneg() && prior >= 0 && prior <= 2 && (prior == 0 || params != nullptr));
+    int rc = match_check(ctx, from0, to0, t);
+    if (rc) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     KpMatchArgs M;
     M.from = from0->view; M.to = to0->view; M.zs_from = from0->zstride; M.zs_to = to0->zstride;
-    M.pyramid_levels = pyramid_levels; M.levels3d = levels3d; M.window = window; M.iterations = iterations;
-    M.eig_thr = eig_thr; M.eps = eps; M.max_distance = max_distance;
+    M.tune = t;
     M.yx = ks->yx; M.oyx = ks->oyx; M.syx = ks->syx; M.xyz = ks->xyz; M.is3d = ks->is3d; M.st = ks->st; M.stereo = ks->stereo; M.cap = ks->cap;
     M.work = ks->work; M.ntot = ks->ntot; M.prior = prior; M.H = from0->H[0]; M.W = from0->W[0]; M.stereo_mode = stereo_mode; M.epipolar = epipolar;
     std::vector<double> zero;
     if (!params) { zero.assign((size_t)ks->S * 32, 0.0); for (int s = 0; s < ks->S; s++) { zero[32 * s + 16] = zero[32 * s + 17] = 1.0; } params = zero.data(); }
-    int rc = kpset_stage_params(ctx, ks, params, (size_t)ks->S * 32, &M.par);
+    rc = kpset_stage_params(ctx, ks, params, (size_t)ks->S * 32, &M.par);
     if (rc) return rc;
     rc = kpset_build_worklist(ctx, ks, M.H, M.W);
     if (rc) return rc;
@@ -644,18 +666,12 @@ static int kpset_match(slam_ctx *ctx, slam_kpset *ks, const slam_pyr *from0, con
     static const int grid_cap = [] { const char *v = getenv("SLAMHIP_LK_GRID"); return v ? atoi(v) : 0; }();
     if (grid_cap > 0 && nb > grid_cap) nb = grid_cap;
     { ProfScope span(ctx, "fb_track");
-      const int ne = (2 * window + 1) * (2 * window + 1);
       // both pyramids built in tolerance mode (slam_pyr_update* mode 3): the contracted-arithmetic instantiation (positions <= 1e-6 px)
       static const bool no_tol_lk = getenv("SLAMHIP_NO_TOL_LK") != nullptr;
       const bool tol = from0->tol_planes && to0->tol_planes && !no_tol_lk;
-      if (tol) {
-          if (ne <= 192) hipLaunchKernelGGL((k_kpset_match<3, true>), dim3(lk_grid(nb)), dim3(64), 0, ctx->stream, M);
-          else if (ne <= 384) hipLaunchKernelGGL((k_kpset_match<6, true>), dim3(lk_grid(nb)), dim3(64), 0, ctx->stream, M);
-          else hipLaunchKernelGGL((k_kpset_match<9, true>), dim3(lk_grid(nb)), dim3(64), 0, ctx->stream, M);
-      }
-      else if (ne <= 192) hipLaunchKernelGGL((k_kpset_match<3, false>), dim3(lk_grid(nb)), dim3(64), 0, ctx->stream, M);
-      else if (ne <= 384) hipLaunchKernelGGL((k_kpset_match<6, false>), dim3(lk_grid(nb)), dim3(64), 0, ctx->stream, M);
-      else hipLaunchKernelGGL((k_kpset_match<9, false>), dim3(lk_grid(nb)), dim3(64), 0, ctx->stream, M); }
+      // (one lambda per mode: the instantiations then keep the parent's order -- and addresses -- in the code object)
+      if (tol) lk_launch(t.window, [&](auto N) { hipLaunchKernelGGL((k_kpset_match<N.value, true>), dim3(lk_grid(nb)), dim3(64), 0, ctx->stream, M); });
+      else lk_launch(t.window, [&](auto N) { hipLaunchKernelGGL((k_kpset_match<N.value, false>), dim3(lk_grid(nb)), dim3(64), 0, ctx->stream, M); }); }
     HIP_TRY(ctx, hipGetLastError());
     return kpset_compact(ctx, ks, 0, nullptr);                   // lost keypoints (st = 0) leave the lists; stable
 }
@@ -667,28 +683,32 @@ extern "C" int slam_kpset_flow_match(slam_ctx *ctx, slam_kpset *ks, const slam_p
                                      int pyramid_levels, int pyramid_levels_3d, int window, int iterations, double eig_thr, double eps,
                                      double max_distance, int n_bound)
 {
-    return kpset_match(ctx, ks, from0, to0, params, prior, pyramid_levels, pyramid_levels_3d, window, iterations, eig_thr, eps, max_distance, 0, 0.0, n_bound);
+    return kpset_match(ctx, ks, from0, to0, params, prior, {pyramid_levels, pyramid_levels_3d, window, iterations, eig_thr, eps, max_distance}, 0, 0.0, n_bound);
 }
 // optical_flow_matching!(..., stereo = true): left0 -> right0; params describe the RIGHT camera
 extern "C" int slam_kpset_stereo_match(slam_ctx *ctx, slam_kpset *ks, const slam_pyr *left0, const slam_pyr *right0, const double *params, int prior,
                                        int pyramid_levels, int pyramid_levels_3d, int window, int iterations, double eig_thr, double eps,
                                        double max_distance, double epipolar_error, int n_bound)
 {
-    return kpset_match(ctx, ks, left0, right0, params, prior, pyramid_levels, pyramid_levels_3d, window, iterations, eig_thr, eps, max_distance, 1, epipolar_error, n_bound);
+    return kpset_match(ctx, ks, left0, right0, params, prior, {pyramid_levels, pyramid_levels_3d, window, iterations, eig_thr, eps, max_distance}, 1, epipolar_error, n_bound);
 }
 
 #define LK_STAGE_MIN_POINTS 4096
+
+// the host lists of an array seam: `aux` = initial displacements (slam_fb_track, nullable) or projections (flow: k_flow_match, with is3d and, batched, img)
+struct TrackLists {
+    const double *pts, *aux; const uint8_t *is3d; const int32_t *img; int n;
+    double *out; uint8_t *status; bool flow;
+};
 
 // shared host path.  Keypoint lists are tiny (16-33 B per point): instead of staging
 // them through HBM (H2D copy -> kernel -> D2H copy: two extra dependent DMA hops per
 // call) the kernel reads its inputs from, and writes its results to, the context's
 // pinned, device-mapped, coherent host block directly over PCIe.  One launch + one
 // stream sync per call.
-static int run_tracking(slam_ctx *ctx, const slam_pyr *prev, const slam_pyr *cur, const double *pts_yx, const double *aux_yx,
-                        const uint8_t *is3d, int n, int pyramid_levels, int levels3d, int window, int iterations,
-                        double eig_thr, double eps, double max_distance, double *out_yx, uint8_t *status, bool flow,
-                        const int32_t *img_index = nullptr)
+static int run_tracking(slam_ctx *ctx, const slam_pyr *prev, const slam_pyr *cur, const LKTune &t, const TrackLists &l)
 {
+    const int n = l.n;
     Layout B;                          // inputs, then outputs
     const size_t o_pts = B.take((size_t)n * 16), o_aux = B.take((size_t)n * 16), o_3d = B.take((size_t)n), o_img = B.take((size_t)n * 4), in_b = B.size();
     const size_t o_out = B.take((size_t)n * 16), o_st = B.take((size_t)n), out_b = B.size() - in_b;
@@ -696,10 +716,10 @@ static int run_tracking(slam_ctx *ctx, const slam_pyr *prev, const slam_pyr *cur
     int rc = slam_pinned(ctx, B.size(), (void **)&h);
     if (rc) return rc;
     HIP_TRY(ctx, hipHostGetDevicePointer((void **)&d, h, 0));
-    memcpy(h + o_pts, pts_yx, (size_t)n * 16);
-    if (aux_yx) memcpy(h + o_aux, aux_yx, (size_t)n * 16);
-    if (is3d) memcpy(h + o_3d, is3d, (size_t)n);
-    if (img_index) memcpy(h + o_img, img_index, (size_t)n * 4);
+    memcpy(h + o_pts, l.pts, (size_t)n * 16);
+    if (l.aux) memcpy(h + o_aux, l.aux, (size_t)n * 16);
+    if (l.is3d) memcpy(h + o_3d, l.is3d, (size_t)n);
+    if (l.img) memcpy(h + o_img, l.img, (size_t)n * 4);
     // Large batches: tens of thousands of 8-byte reads and writes over PCIe (every wave starts with dependent
     // reads of its point and ends with three small stores) are slower than one DMA of the whole block each way.
     const bool staged = n >= LK_STAGE_MIN_POINTS;
@@ -713,28 +733,19 @@ static int run_tracking(slam_ctx *ctx, const slam_pyr *prev, const slam_pyr *cur
     FlowArgs F;
     LKArgs &A = F.lk;
     A.prev = prev->view; A.cur = cur->view;
-    A.pts = (const double *)(d + o_pts); A.disp0 = aux_yx ? (const double *)(d + o_aux) : nullptr; A.n = n;
-    A.pyramid_levels = pyramid_levels; A.window = window; A.iterations = iterations;
-    A.eig_thr = eig_thr; A.eps = eps; A.max_distance = max_distance;
+    A.pts = (const double *)(d + o_pts); A.disp0 = l.aux ? (const double *)(d + o_aux) : nullptr; A.n = n;
+    A.tune = t;
     A.out = (double *)(d + o_out); A.status = (uint8_t *)(d + o_st);
-    F.is3d = (const uint8_t *)(d + o_3d); F.proj = (const double *)(d + o_aux); F.levels3d = levels3d;
-    F.img = img_index ? (const int *)(d + o_img) : nullptr; F.zs_from = prev->zstride; F.zs_to = cur->zstride;
+    F.is3d = (const uint8_t *)(d + o_3d); F.proj = (const double *)(d + o_aux);
+    F.img = l.img ? (const int *)(d + o_img) : nullptr; F.zs_from = prev->zstride; F.zs_to = cur->zstride;
     { ProfScope span(ctx, "fb_track");
-      const int ne = (2 * window + 1) * (2 * window + 1);
-      if (flow) {
-          if (ne <= 192) hipLaunchKernelGGL(k_flow_match<3>, dim3(lk_grid(n)), dim3(64), 0, ctx->stream, F);
-          else if (ne <= 384) hipLaunchKernelGGL(k_flow_match<6>, dim3(lk_grid(n)), dim3(64), 0, ctx->stream, F);
-          else hipLaunchKernelGGL(k_flow_match<9>, dim3(lk_grid(n)), dim3(64), 0, ctx->stream, F);
-      } else {
-          if (ne <= 192) hipLaunchKernelGGL(k_fb_track<3>, dim3(lk_grid(n)), dim3(64), 0, ctx->stream, A);
-          else if (ne <= 384) hipLaunchKernelGGL(k_fb_track<6>, dim3(lk_grid(n)), dim3(64), 0, ctx->stream, A);
-          else hipLaunchKernelGGL(k_fb_track<9>, dim3(lk_grid(n)), dim3(64), 0, ctx->stream, A);
-      } }
+      if (l.flow) lk_launch(t.window, [&](auto N) { hipLaunchKernelGGL(k_flow_match<N.value>, dim3(lk_grid(n)), dim3(64), 0, ctx->stream, F); });
+      else lk_launch(t.window, [&](auto N) { hipLaunchKernelGGL(k_fb_track<N.value>, dim3(lk_grid(n)), dim3(64), 0, ctx->stream, A); }); }
     HIP_TRY(ctx, hipGetLastError());
     if (staged) HIP_TRY(ctx, hipMemcpyAsync(h + in_b, d + in_b, out_b, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, slam_stream_wait(ctx->stream));
-    memcpy(out_yx, h + o_out, (size_t)n * 16);
-    memcpy(status, h + o_st, (size_t)n);
+    memcpy(l.out, h + o_out, (size_t)n * 16);
+    memcpy(l.status, h + o_st, (size_t)n);
     return SLAM_OK;
 }
 
@@ -744,17 +755,14 @@ extern "C" int slam_fb_track(slam_ctx *ctx, const slam_pyr *prev, const slam_pyr
                              double eig_thr, double eps, double max_distance,
                              double *out_yx, uint8_t *status)
 {
+    const LKTune t = {pyramid_levels, 0, window, iterations, eig_thr, eps, max_distance};
     ARG_TRY(ctx, ctx != nullptr && prev != nullptr && cur != nullptr);
-    ARG_TRY(ctx, n >= 0 && pyramid_levels >= 0 && window >= 0 && iterations >= 0);
+    ARG_TRY(ctx, n >= 0 && t.nonneg());
     if (n == 0) return SLAM_OK;                                       // tracker.jl:24
     ARG_TRY(ctx, pts_yx != nullptr && out_yx != nullptr && status != nullptr);
-    if (!(prev->levels > pyramid_levels && cur->levels > pyramid_levels))
-        return slam_fail(ctx, SLAM_ERR_LAYERS, "Not enough layers in pyramids.");   // lucas_kanade.jl:12-15
-    ARG_TRY(ctx, prev->H[0] == cur->H[0] && prev->W[0] == cur->W[0]);
-    if (prev->target_only) return slam_fail(ctx, SLAM_ERR_ARG, "the source pyramid of a match was updated with SLAM_PYR_TARGET_ONLY: its gradient planes exist at level 0 only");
+    if (const int rc = match_check(ctx, prev, cur, t)) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return run_tracking(ctx, prev, cur, pts_yx, disp0_yx, nullptr, n, pyramid_levels, 0, window, iterations, eig_thr, eps,
-                        max_distance, out_yx, status, false);
+    return run_tracking(ctx, prev, cur, t, {pts_yx, disp0_yx, nullptr, nullptr, n, out_yx, status, false});
 }
 
 extern "C" int slam_flow_match(slam_ctx *ctx, const slam_pyr *from, const slam_pyr *to,
@@ -763,18 +771,14 @@ extern "C" int slam_flow_match(slam_ctx *ctx, const slam_pyr *from, const slam_p
                                double eig_thr, double eps, double max_distance,
                                double *out_yx, uint8_t *status)
 {
+    const LKTune t = {pyramid_levels, pyramid_levels_3d, window, iterations, eig_thr, eps, max_distance};
     ARG_TRY(ctx, ctx != nullptr && from != nullptr && to != nullptr);
-    ARG_TRY(ctx, n >= 0 && pyramid_levels >= 0 && pyramid_levels_3d >= 0 && window >= 0 && iterations >= 0);
+    ARG_TRY(ctx, n >= 0 && t.nonneg());
     if (n == 0) return SLAM_OK;
     ARG_TRY(ctx, pts_yx != nullptr && is_3d != nullptr && proj_yx != nullptr && out_yx != nullptr && status != nullptr);
-    const int need = pyramid_levels > pyramid_levels_3d ? pyramid_levels : pyramid_levels_3d;
-    if (!(from->levels > need && to->levels > need))
-        return slam_fail(ctx, SLAM_ERR_LAYERS, "Not enough layers in pyramids.");
-    ARG_TRY(ctx, from->H[0] == to->H[0] && from->W[0] == to->W[0]);
-    if (from->target_only) return slam_fail(ctx, SLAM_ERR_ARG, "the source pyramid of a match was updated with SLAM_PYR_TARGET_ONLY: its gradient planes exist at level 0 only");
+    if (const int rc = match_check(ctx, from, to, t)) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return run_tracking(ctx, from, to, pts_yx, proj_yx, is_3d, n, pyramid_levels, pyramid_levels_3d, window, iterations, eig_thr, eps,
-                        max_distance, out_yx, status, true);
+    return run_tracking(ctx, from, to, t, {pts_yx, proj_yx, is_3d, nullptr, n, out_yx, status, true});
 }
 
 // optical_flow_matching! for S lock-stepped streams in one launch: point i belongs to stream img_index[i]; from0 / to0 are
@@ -785,20 +789,16 @@ extern "C" int slam_flow_match_batch(slam_ctx *ctx, const slam_pyr *from0, const
                                      int pyramid_levels, int pyramid_levels_3d, int window, int iterations,
                                      double eig_thr, double eps, double max_distance, double *out_yx, uint8_t *status)
 {
+    const LKTune t = {pyramid_levels, pyramid_levels_3d, window, iterations, eig_thr, eps, max_distance};
     ARG_TRY(ctx, ctx != nullptr && from0 != nullptr && to0 != nullptr && S >= 1);
     ARG_TRY(ctx, from0->batch_index == 0 && to0->batch_index == 0 && from0->batch_size >= S && to0->batch_size >= S);
-    ARG_TRY(ctx, n >= 0 && pyramid_levels >= 0 && pyramid_levels_3d >= 0 && window >= 0 && iterations >= 0);
+    ARG_TRY(ctx, n >= 0 && t.nonneg());
     if (n == 0) return SLAM_OK;
     ARG_TRY(ctx, img_index != nullptr && pts_yx != nullptr && is_3d != nullptr && proj_yx != nullptr && out_yx != nullptr && status != nullptr);
     for (int i = 0; i < n; i++) if (img_index[i] < 0 || img_index[i] >= S) return slam_fail(ctx, SLAM_ERR_ARG, "slam_flow_match_batch: img_index[%d] = %d outside [0,%d)", i, img_index[i], S);
-    const int need = pyramid_levels > pyramid_levels_3d ? pyramid_levels : pyramid_levels_3d;
-    if (!(from0->levels > need && to0->levels > need))
-        return slam_fail(ctx, SLAM_ERR_LAYERS, "Not enough layers in pyramids.");
-    ARG_TRY(ctx, from0->H[0] == to0->H[0] && from0->W[0] == to0->W[0]);
-    if (from0->target_only) return slam_fail(ctx, SLAM_ERR_ARG, "the source pyramid of a match was updated with SLAM_PYR_TARGET_ONLY: its gradient planes exist at level 0 only");
+    if (const int rc = match_check(ctx, from0, to0, t)) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return run_tracking(ctx, from0, to0, pts_yx, proj_yx, is_3d, n, pyramid_levels, pyramid_levels_3d, window, iterations, eig_thr, eps,
-                        max_distance, out_yx, status, true, img_index);
+    return run_tracking(ctx, from0, to0, t, {pts_yx, proj_yx, is_3d, img_index, n, out_yx, status, true});
 }
 
 // slam_flow_match_batch followed by the list surgery of optical_flow_matching! (map_manager.jl:523-560: keypoints whose

@@ -35,3 +35,9 @@ WORK_HD uint32_t work_key(double y, double x, int H, int W, int band)
 {
     return ((work_clamp_px(x, W) / (uint32_t)(band < 1 ? 1 : band)) << 16) | work_clamp_px(y, H);
 }
+
+// Which instantiation of the tracking kernels (lk.hip: 3, 6 or 9 template slots per lane) a window_size runs on: the smallest
+// whose 64 lanes hold the (2 w + 1)^2 window elements, the 9-slot one (uncached path) beyond.  The host launches by lk_slots,
+// lk_level decides `cached` from the same element count.
+WORK_HD int lk_window_elems(int window) { return (2 * window + 1) * (2 * window + 1); }
+WORK_HD int lk_slots(int window) { const int ne = lk_window_elems(window); return ne <= 192 ? 3 : ne <= 384 ? 6 : 9; }

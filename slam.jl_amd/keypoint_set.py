@@ -7,6 +7,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
+from .optical_flow import _check_match, _tune
 
 
 def stream_params(S, Tcw=None, cam=None, dist=None, shift_yx=None):
@@ -78,22 +79,16 @@ class KeypointSet:
         c = ctx or self.ctx
         sp = None if stream_params_ is None else np.ascontiguousarray(stream_params_, dtype=np.float64)
         rc = c.lib.slam_kpset_flow_match(c.h, self.h, from_batch.pyramids[0].h, to_batch.pyramids[0].h, L.ptr(sp) if sp is not None else None,
-                                         prior, params.pyramid_levels, pyramid_levels_3d, params.window_size, iterations, 1e-4, 1e-2,
-                                         float(params.max_ktl_distance), int(n_bound))
-        if rc == -3:
-            raise RuntimeError("Not enough layers in pyramids.")
-        c.check(rc)
+                                         prior, *_tune(params, pyramid_levels_3d, iterations), int(n_bound))
+        _check_match(c, rc)
 
     def stereo_match(self, left_batch, right_batch, params, stream_params_=None, prior=0, pyramid_levels_3d=1, iterations=30,
                      epipolar_error=2.0, n_bound=0, ctx=None):
         c = ctx or self.ctx
         sp = None if stream_params_ is None else np.ascontiguousarray(stream_params_, dtype=np.float64)
         rc = c.lib.slam_kpset_stereo_match(c.h, self.h, left_batch.pyramids[0].h, right_batch.pyramids[0].h, L.ptr(sp) if sp is not None else None,
-                                           prior, params.pyramid_levels, pyramid_levels_3d, params.window_size, iterations, 1e-4, 1e-2,
-                                           float(params.max_ktl_distance), float(epipolar_error), int(n_bound))
-        if rc == -3:
-            raise RuntimeError("Not enough layers in pyramids.")
-        c.check(rc)
+                                           prior, *_tune(params, pyramid_levels_3d, iterations), float(epipolar_error), int(n_bound))
+        _check_match(c, rc)
 
     def remove(self, flags_dev_ptr, ctx=None):
         """flags_dev_ptr: device pointer to S x cap bytes (1 = remove), e.g. torch_tensor.data_ptr()"""

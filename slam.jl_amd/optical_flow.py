@@ -105,6 +105,22 @@ def deepcopy(lk):
     return LKPyramid(ctx=lk.ctx, _handle=h)
 
 
+def _check_match(ctx, rc):
+    if rc == -3:                                                     # SLAM_ERR_LAYERS: the reference's error (lucas_kanade.jl:15)
+        raise RuntimeError("Not enough layers in pyramids.")
+    ctx.check(rc)
+
+
+def _tune(params, pyramid_levels_3d, iterations):
+    """the tuning arguments of a flow-match seam in the C ABI's order (eigenvalue threshold and eps: LucasKanade's defaults)"""
+    return (params.pyramid_levels, pyramid_levels_3d, params.window_size, iterations, 1e-4, 1e-2, float(params.max_ktl_distance))
+
+
+def _lists(pixels, is_3d, projections):                              # the contiguous arrays the seams read
+    return (np.ascontiguousarray(pixels, dtype=np.float64).reshape(-1, 2), np.ascontiguousarray(is_3d, dtype=np.uint8),
+            np.ascontiguousarray(projections, dtype=np.float64).reshape(-1, 2))
+
+
 def fb_tracking_(previous_pyramid, current_pyramid, keypoints, displacement=None,
                  iterations=30, window_size=11, pyramid_levels=3, max_distance=0.5,
                  eigenvalue_threshold=1e-4, eps=1e-2, ctx=None):
@@ -122,9 +138,7 @@ def fb_tracking_(previous_pyramid, current_pyramid, keypoints, displacement=None
     rc = ctx.lib.slam_fb_track(ctx.h, previous_pyramid.h, current_pyramid.h, L.ptr(pts), L.ptr(d0), n,
                                pyramid_levels, window_size, iterations, float(eigenvalue_threshold), float(eps),
                                float(max_distance), L.ptr(out), L.ptr(status, L.u8p))
-    if rc == -3:
-        raise RuntimeError("Not enough layers in pyramids.")      # lucas_kanade.jl:15
-    ctx.check(rc)
+    _check_match(ctx, rc)
     return out, status.astype(bool)
 
 
@@ -138,21 +152,16 @@ def optical_flow_matching(from_pyramid, to_pyramid, pixels, is_3d, projections, 
 
     fused=True issues ONE slam_flow_match launch; fused=False issues the
     reference's two fb_tracking! calls (kept for the parity test: identical results)."""
-    pixels = np.ascontiguousarray(pixels, dtype=np.float64).reshape(-1, 2)
+    pixels, is_3d, proj = _lists(pixels, is_3d, projections)
     n = len(pixels)
-    is_3d = np.ascontiguousarray(is_3d, dtype=np.uint8)
-    proj = np.ascontiguousarray(projections, dtype=np.float64).reshape(-1, 2)
     if fused:
         ctx = ctx or from_pyramid.ctx
         if n == 0:
             return pixels.copy(), np.zeros(0, dtype=bool)
         out = np.empty((n, 2)); status = np.zeros(n, dtype=np.uint8)
         rc = ctx.lib.slam_flow_match(ctx.h, from_pyramid.h, to_pyramid.h, L.ptr(pixels), L.ptr(is_3d, L.u8p), L.ptr(proj), n,
-                                     params.pyramid_levels, pyramid_levels_3d, params.window_size, iterations, 1e-4, 1e-2,
-                                     float(params.max_ktl_distance), L.ptr(out), L.ptr(status, L.u8p))
-        if rc == -3:
-            raise RuntimeError("Not enough layers in pyramids.")
-        ctx.check(rc)
+                                     *_tune(params, pyramid_levels_3d, iterations), L.ptr(out), L.ptr(status, L.u8p))
+        _check_match(ctx, rc)
         st = status.view(np.bool_)
         return np.where(st[:, None], out, pixels), st
     is3 = is_3d.astype(bool)
@@ -277,21 +286,16 @@ def optical_flow_matching_batch(from_batch, to_batch, stream_index, pixels, is_3
     """optical_flow_matching! for S lock-stepped streams in one launch (slam_flow_match_batch): point i belongs to
     stream stream_index[i]; pyramids from_batch.pyramids[s] -> to_batch.pyramids[s].  Returns (new_pixels, status)."""
     ctx = ctx or from_batch.ctx
-    pixels = np.ascontiguousarray(pixels, dtype=np.float64).reshape(-1, 2)
+    pixels, is3, proj = _lists(pixels, is_3d, projections)
     n = len(pixels)
     if n == 0:
         return pixels.copy(), np.zeros(0, dtype=bool)
     idx = np.ascontiguousarray(stream_index, dtype=np.int32)
-    is3 = np.ascontiguousarray(is_3d, dtype=np.uint8)
-    proj = np.ascontiguousarray(projections, dtype=np.float64).reshape(-1, 2)
     out = np.empty((n, 2)); status = np.zeros(n, dtype=np.uint8)
     rc = ctx.lib.slam_flow_match_batch(ctx.h, from_batch.pyramids[0].h, to_batch.pyramids[0].h, from_batch.S, L.ptr(idx, L.i32p),
-                                       L.ptr(pixels), L.ptr(is3, L.u8p), L.ptr(proj), n, params.pyramid_levels, pyramid_levels_3d,
-                                       params.window_size, iterations, 1e-4, 1e-2, float(params.max_ktl_distance),
+                                       L.ptr(pixels), L.ptr(is3, L.u8p), L.ptr(proj), n, *_tune(params, pyramid_levels_3d, iterations),
                                        L.ptr(out), L.ptr(status, L.u8p))
-    if rc == -3:
-        raise RuntimeError("Not enough layers in pyramids.")
-    ctx.check(rc)
+    _check_match(ctx, rc)
     st = status.view(np.bool_)
     if status_only:                                   # e.g. stereo matching: only the flags are used (mapper.jl:58-66)
         return None, st
@@ -303,21 +307,16 @@ def optical_flow_matching_batch_kept(from_batch, to_batch, stream_index, pixels,
     """optical_flow_matching_batch + removal of the keypoints whose tracking failed (slam_flow_match_batch_kept): returns
     (new_pixels (k, 2), is_3d (k,) bool, stream_index (k,) int32, source_index (k,) int32) of the survivors, in input order."""
     ctx = ctx or from_batch.ctx
-    pixels = np.ascontiguousarray(pixels, dtype=np.float64).reshape(-1, 2)
+    pixels, is3, proj = _lists(pixels, is_3d, projections)
     n = len(pixels)
     if n == 0:
         return pixels.copy(), np.zeros(0, dtype=bool), np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int32)
     idx = np.ascontiguousarray(stream_index, dtype=np.int32)
-    is3 = np.ascontiguousarray(is_3d, dtype=np.uint8) if np.asarray(is_3d).dtype != np.bool_ else np.ascontiguousarray(is_3d).view(np.uint8)
-    proj = np.ascontiguousarray(projections, dtype=np.float64).reshape(-1, 2)
     out = np.empty((n, 2)); k3 = np.empty(n, dtype=np.uint8); kimg = np.empty(n, dtype=np.int32); ksrc = np.empty(n, dtype=np.int32)
     nk = C.c_int(0)
     rc = ctx.lib.slam_flow_match_batch_kept(ctx.h, from_batch.pyramids[0].h, to_batch.pyramids[0].h, from_batch.S, L.ptr(idx, L.i32p),
-                                            L.ptr(pixels), L.ptr(is3, L.u8p), L.ptr(proj), n, params.pyramid_levels, pyramid_levels_3d,
-                                            params.window_size, iterations, 1e-4, 1e-2, float(params.max_ktl_distance),
+                                            L.ptr(pixels), L.ptr(is3, L.u8p), L.ptr(proj), n, *_tune(params, pyramid_levels_3d, iterations),
                                             L.ptr(out), L.ptr(k3, L.u8p), L.ptr(kimg, L.i32p), L.ptr(ksrc, L.i32p), C.byref(nk), None)
-    if rc == -3:
-        raise RuntimeError("Not enough layers in pyramids.")
-    ctx.check(rc)
+    _check_match(ctx, rc)
     k = nk.value
     return out[:k], k3[:k].view(np.bool_), kimg[:k], ksrc[:k]

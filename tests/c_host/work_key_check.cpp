@@ -1,18 +1,24 @@
 // Stand-alone host check of the work list's sort key (slam.jl_amd/csrc/work_order.hpp): monotone in band and row, clamped to the
-// image, defined for NaN / inf / huge positions.  Built and run by tests/test_work_key_host.py (plain, and with
-// -fsanitize=undefined,float-cast-overflow: no conversion of a value an int cannot hold).
+// image, defined for NaN / inf / huge positions; and of the rule that picks the tracking kernels' instantiation (lk_slots, lk_window_elems:
+// `work_key_check slots` prints "window slots elems" for windows 0..16).  Built and run by tests/test_work_key_host.py (plain, and with
+// -fsanitize=address,undefined,float-cast-overflow: no conversion of a value an int cannot hold).
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <initializer_list>
+#include <cstring>
 #include <limits>
 #include "work_order.hpp"
 
 static int fails = 0;
 #define CHECK(c) do { if (!(c)) { std::printf("FAILED line %d: %s\n", __LINE__, #c); fails++; } } while (0)
 
-int main()
+int main(int argc, char **argv)
 {
+    if (argc > 1 && !std::strcmp(argv[1], "slots")) {
+        for (int w = 0; w <= 16; w++) std::printf("%d %d %d\n", w, lk_slots(w), lk_window_elems(w));
+        return 0;
+    }
     const int H = 370, W = 1226;
     const double inf = std::numeric_limits<double>::infinity(), nan = std::numeric_limits<double>::quiet_NaN();
     const double odd[] = {nan, -nan, inf, -inf, 1e300, -1e300, 4294967296.0, -4294967296.0, 2147483648.0, -2147483649.0, 1e19, -0.0, 0.0,
@@ -49,6 +55,15 @@ int main()
     CHECK(work_key(50.2, 33.0, H, W, 32) == work_key(50.9, 63.9, H, W, 32) && work_key(50.2, 31.9, H, W, 32) != work_key(50.2, 32.0, H, W, 32));
     // a band wider than the image is a pure row order, a 1-px band a pure column order
     CHECK(work_key(10.0, 1200.0, H, W, 5000) < work_key(11.0, 3.0, H, W, 5000) && work_key(300.0, 7.0, H, W, 1) < work_key(2.0, 8.0, H, W, 1));
+    // the instantiation rule: the smallest of 3 / 6 / 9 slots per lane whose 64 lanes hold the window; the kernel's `cached`
+    // (lk_window_elems(w) <= 64 * LK_MAXE, LK_MAXE = lk_slots(w)) holds exactly up to window 11
+    for (int w = 0; w <= 16; w++) {
+        const int ne = lk_window_elems(w), n = lk_slots(w);
+        CHECK(ne == (2 * w + 1) * (2 * w + 1) && (n == 3 || n == 6 || n == 9));
+        CHECK(n == 9 || ne <= 64 * n);                               // a 3- / 6-slot kernel always holds its window
+        CHECK(n == 3 || ne > 64 * (n - 3));                          // and no smaller one would
+        CHECK((ne <= 64 * n) == (w <= 11));
+    }
     if (fails) { std::printf("%d checks failed\n", fails); return 1; }
     std::printf("work_key OK\n");
     return 0;
