@@ -2,6 +2,7 @@
 //   hipcc -O3 --offload-arch=gfx950 -ffp-contract=off -I slam.jl_amd/csrc scripts/ubench/potrf.hip -o scripts/ubench/potrf && scripts/ubench/potrf
 #include "../../slam.jl_amd/csrc/ctx.hip"
 #include "../../slam.jl_amd/csrc/ba_device.hpp"
+extern "C" void ba_forget_jobs(slam_ctx *) {}      // ctx.hip calls it at slam_ctx_destroy; it lives in ba_batch.hip, which this one-file program does not link (no batch job exists here)
 #include <vector>
 #include <cstdio>
 

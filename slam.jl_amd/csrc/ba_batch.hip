@@ -1,5 +1,5 @@
 // ba_batch.hip -- bundle_adjustment! for S windows in one set of launches (slam_local_ba_batch, _begin / _end): the window-indexed wrappers of the
-// kernels of ba_device.hpp (table of BAWin read through the constant address space), the matrix-core Schur build, the host half of the call
+// bodies of ba_device.hpp (table of BAWin read through the constant address space: ba_win), among them the matrix-core Schur build, and the host half of the call
 // (worker pool, arena layout, retry of k_ba_window on one workgroup).  reference: src/estimator.jl:78-99, :317-347; src/bundle_adjustment.jl:1-111.
 #include "ba_device.hpp"
 
@@ -21,8 +21,8 @@ __global__ __launch_bounds__(256) void k_pass_start_b(const BAWin *tab, int pass
     __syncthreads();
     if (threadIdx.x != 0) return;
     LMState *s = w.d.st;
-    if (pass == 0) { s->ssr_init = s->ssr; s->chol_fail = 0; s->n_outliers = 0; }
-    s->delta = LM_DELTA0; s->decrease_factor = 2.0; s->converged = 0; s->accept = 0; s->iters = 0;
+    if (pass == 0) lm_first_pass(s);
+    lm_trust_reset(s);
 }
 template <int TT> __global__ __launch_bounds__(TT) __attribute__((amdgpu_waves_per_eu(4))) void k_schur_groups_b(const BAWin *tab, int ignore_outliers)
 {
@@ -94,7 +94,7 @@ __global__ __launch_bounds__(256) void k_outlier_count_b(const BAWin *tab)
     const BAWin w = ba_win(tab);
     if (w.pad) return;                                       // the window is k_ba_window's
     LMState *s = w.d.st;
-    if (threadIdx.x == 0) { s->ssr_pass1 = s->ssr; s->iters_pass1 = s->iters; }
+    if (threadIdx.x == 0) lm_record_pass(s, 1);
     outlier_count_body(w.d, w.nb_obs);
 }
 // end of pass 2: record it and pack every window's result -- committed parameters (solver's pose order), LM state, outlier flags (sorted
@@ -117,7 +117,7 @@ __global__ __launch_bounds__(256) void k_results_b(const BAWin *tab, const BARes
     for (int i = tid; i < d.O; i += nth) ol[i] = d.outl[i];
     if (tid == 0) {
         LMState h = *s;
-        h.ssr_final = h.ssr; h.iters_pass2 = h.iters;
+        lm_record_pass(&h, 2);
         *(LMState *)(res + r.off_state) = h;
     }
 }

@@ -1,9 +1,12 @@
-// ba_device.hpp -- what the four translation units of the local bundle adjustment share: the device-side state (LMState, BADev, BAWin), the
-// residual / Jacobian evaluation, the bodies of the grouped build, the banded and dense solves, the update and the LM control (every kernel of
-// ba_single.hip and ba_batch.hip is a thin wrapper around one of them), their LDS-size helpers, and the constants of k_ba_window that the host
-// planner needs.  (Round 6: ba.hip, 4 900 lines, split into ba_single.hip / ba_batch.hip / ba_window.hip / ba_host.hip + this header.)
+// ba_device.hpp -- what the four translation units of the local bundle adjustment share: the device-side structures (BADev, BAWin, BandArgs), the
+// residual / Jacobian evaluation, the workgroup reductions and record moves, the bodies that the single-window kernels of ba_single.hip and the
+// window-indexed kernels of ba_batch.hip both wrap (linearisation, the grouped builds, the reduce, the banded solve, the update, the LM control, the
+// outlier flags), the tile factorisation of the k_chol_* chain, their LDS-size helpers, the constants of k_ba_window that the host planner needs, and
+// the host's solve route.  The shared formulas and the LM state are ba_math.hpp's; the fall-back kernels (k_points ... k_trial, k_chol_*), k_dense_solve,
+// the one-thread LM kernels and k_pnp are written out in ba_single.hip, k_ba_window in ba_window.hip.
 #pragma once
 #include "common.hpp"
+#include "ba_math.hpp"
 #include <atomic>
 #include <algorithm>
 #include <type_traits>
@@ -15,23 +18,7 @@
 #include <mutex>
 #include <cmath>
 
-#define LM_MAX_DELTA 1e16
-#define LM_MIN_DELTA 1e-16
-#define LM_MIN_STEP_QUALITY 1e-3
-#define LM_MIN_DIAGONAL 1e-6
-#define LM_MAX_DIAGONAL 1e32
-#define LM_DELTA0 10.0
-#define LM_XTOL 1e-8
-#define LM_FTOL 1e-8
 #define SOLVE_MAX_N 1536   /* 6 * 256 key-frames */
-
-struct LMState {
-    double delta, decrease_factor, ssr, trial_ssr, pred_ssr, maxdx;
-    double ssr_init, ssr_pass1, ssr_final;
-    int converged, accept, iters, n_outliers, chol_fail, iters_pass1, iters_pass2;
-    int cur;                     // which of the two parameter buffers is the committed one: an accepted step SWAPS them (lm_decide) -- no copy
-                                 // kernel per iteration (k_commit cost the iteration a launch: ~5 us of its 127)
-};
 
 
 // BADevT<PlainP> = BADev: what the host fills and every kernel receives.  BADevT<GlobP> = BADevG: the same bytes with every pointer typed as GLOBAL memory -- a
@@ -180,7 +167,6 @@ __device__ __forceinline__ void obs_eval(const double *pose, const double *X, do
     obs_eval_sc(sc, pose + 3, X, py, px, c, r, Jp, Jl, depth);
 }
 
-// deterministic block reduction (256 threads): wave butterfly, then wave order
 // workgroup barrier that orders LDS traffic only.  __syncthreads() also drains the outstanding global loads / stores: after a store
 // that is a full memory round trip (k_schur_groups: its "barrier" phases were mostly the Jacobian / partial stores being acknowledged).
 // For barriers that only hand LDS data (or nothing) between the threads of a workgroup.
@@ -190,83 +176,51 @@ __device__ __forceinline__ void lds_sync()
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
-__device__ __forceinline__ double block_sum_lds(double v, double *sh)       // block_sum with LDS-only barriers
+// ONE deterministic block reduction: wave butterfly, then the waves' values in wave order (from 0.0: the maxima are of magnitudes).  LDS_ONLY: lds_sync
+// instead of __syncthreads between the steps; NW: the workgroup's waves when the caller knows them at compile time, 0 = blockDim.x >> 6.
+struct RedSum { static __device__ __forceinline__ double op(double a, double b) { return a + b; } };
+struct RedMax { static __device__ __forceinline__ double op(double a, double b) { return fmax(a, b); } };
+template <class Op, bool LDS_ONLY, int NW = 0> __device__ __forceinline__ double block_reduce(double v, double *sh)
 {
 #pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-    lds_sync();
+    for (int m = 32; m >= 1; m >>= 1) v = Op::op(v, __shfl_xor(v, m));
+    if (LDS_ONLY) lds_sync(); else __syncthreads();
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    lds_sync();
+    if (LDS_ONLY) lds_sync(); else __syncthreads();
     double t = 0.0;
-    for (int w = 0; w < (int)(blockDim.x >> 6); w++) t += sh[w];
+    for (int w = 0; w < (NW ? NW : (int)(blockDim.x >> 6)); w++) t = Op::op(t, sh[w]);
     return t;
 }
-__device__ __forceinline__ double block_max_lds(double v, double *sh)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = fmax(v, __shfl_xor(v, m));
-    lds_sync();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    lds_sync();
-    double t = 0.0;
-    for (int w = 0; w < (int)(blockDim.x >> 6); w++) t = fmax(t, sh[w]);
-    return t;
-}
-__device__ __forceinline__ double block_sum(double v, double *sh)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double t = 0.0;
-    for (int w = 0; w < (int)(blockDim.x >> 6); w++) t += sh[w];
-    return t;
-}
-__device__ __forceinline__ double block_max(double v, double *sh)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = fmax(v, __shfl_xor(v, m));
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double t = 0.0;
-    for (int w = 0; w < (int)(blockDim.x >> 6); w++) t = fmax(t, sh[w]);
-    return t;
-}
+__device__ __forceinline__ double block_sum_lds(double v, double *sh) { return block_reduce<RedSum, true>(v, sh); }      // block_sum with LDS-only barriers
+__device__ __forceinline__ double block_max_lds(double v, double *sh) { return block_reduce<RedMax, true>(v, sh); }
+__device__ __forceinline__ double block_sum(double v, double *sh) { return block_reduce<RedSum, false>(v, sh); }
+__device__ __forceinline__ double block_max(double v, double *sh) { return block_reduce<RedMax, false>(v, sh); }
 
 // ---------------------------------------------------------------------------------
 // An observation's records (Jp 12, Jl 6, T 18, W 18 doubles) are 16-byte aligned AoS blocks: move them as 16-byte vectors
 // (half the memory instructions of scalar loads).
-template <int N> __device__ __forceinline__ void ld_rec(const double *p, double *v)
-{
-    static_assert(N % 2 == 0, "even record length");
-    const double2 *q = (const double2 *)p;
-#pragma unroll
-    for (int k = 0; k < N / 2; k++) { const double2 t = q[k]; v[2 * k] = t.x; v[2 * k + 1] = t.y; }
-}
-template <int N> __device__ __forceinline__ void st_rec(double *p, const double *v)
-{
-    static_assert(N % 2 == 0, "even record length");
-    double2 *q = (double2 *)p;
-#pragma unroll
-    for (int k = 0; k < N / 2; k++) q[k] = make_double2(v[2 * k], v[2 * k + 1]);
-}
-// (the same through pointers typed as global memory: BADevG)
+// P: a pointer to double, plain or typed as global memory (BADevG) -- the 16-byte pair pointer stays in P's address space.  The two pair types are DELIBERATE:
+// generic pointers keep HIP's double2, global-typed ones need the bare ext vector (double2's copy constructor wants a generic reference).  With the ext vector
+// for both, k_schur_groups needs 246 instead of 176 VGPRs and k_schur_groups_b 160 instead of 88 bytes of scratch (profiles/r18a_ba_kernel_table.txt).
 typedef double sg_d2 __attribute__((ext_vector_type(2)));
-template <int N> __device__ __forceinline__ void ld_rec(__attribute__((address_space(1))) const double *p, double *v)
+template <class P> struct RecPair;
+template <> struct RecPair<double *> { typedef double2 vec; typedef double2 *type; };
+template <> struct RecPair<const double *> { typedef double2 vec; typedef const double2 *type; };
+template <> struct RecPair<GlobP<double>::type> { typedef sg_d2 vec; typedef GlobP<sg_d2>::type type; };
+template <> struct RecPair<GlobP<const double>::type> { typedef sg_d2 vec; typedef GlobP<const sg_d2>::type type; };
+template <int N, class P> __device__ __forceinline__ void ld_rec(P p, double *v)
 {
     static_assert(N % 2 == 0, "even record length");
-    __attribute__((address_space(1))) const sg_d2 *q = (__attribute__((address_space(1))) const sg_d2 *)p;
+    const typename RecPair<P>::type q = (typename RecPair<P>::type)p;
 #pragma unroll
-    for (int k = 0; k < N / 2; k++) { const sg_d2 t = q[k]; v[2 * k] = t.x; v[2 * k + 1] = t.y; }
+    for (int k = 0; k < N / 2; k++) { const typename RecPair<P>::vec t = q[k]; v[2 * k] = t.x; v[2 * k + 1] = t.y; }
 }
-template <int N> __device__ __forceinline__ void st_rec(__attribute__((address_space(1))) double *p, const double *v)
+template <int N, class P> __device__ __forceinline__ void st_rec(P p, const double *v)
 {
     static_assert(N % 2 == 0, "even record length");
-    __attribute__((address_space(1))) sg_d2 *q = (__attribute__((address_space(1))) sg_d2 *)p;
+    const typename RecPair<P>::type q = (typename RecPair<P>::type)p;
 #pragma unroll
-    for (int k = 0; k < N / 2; k++) { sg_d2 t; t.x = v[2 * k]; t.y = v[2 * k + 1]; q[k] = t; }
+    for (int k = 0; k < N / 2; k++) { typename RecPair<P>::vec t; t.x = v[2 * k]; t.y = v[2 * k + 1]; q[k] = t; }
 }
 
 template <bool STORE = true>          // STORE = false (batches): the cost only -- the grouped build evaluates every observation again and keeps what it needs
@@ -310,20 +264,6 @@ __device__ __forceinline__ void linearize_body(const BADev &d0, int ignore_outli
     const double t = block_sum(ss, sh);
     if (threadIdx.x == 0) d.part[blockIdx.x] = t;
 }
-
-__device__ __forceinline__ void inv3_sym(const double V[6], double I[6])
-{
-    const double a = V[0], b = V[1], c = V[2], dd = V[3], e = V[4], f = V[5];
-    const double A = dd * f - e * e, B = c * e - b * f, C = b * e - c * dd;
-    const double det = a * A + b * B + c * C, id = 1.0 / det;
-    I[0] = A * id; I[1] = B * id; I[2] = C * id;
-    I[3] = (a * f - c * c) * id; I[4] = (b * c - a * e) * id; I[5] = (a * dd - b * b) * id;
-}
-
-
-// per observation: W = Jp'Jl (6x3), T = W V^-1 of its point
-
-// One wave per non-zero upper block (p <= q) of the reduced camera system.
 
 // ---- the reduced camera system of a windowed problem, built point group by point group ---------------------------------
 // A map point seen by free poses f .. f + hb only touches the (hb + 1) x (hb + 1) window of 6 x 6 blocks that starts at its first
@@ -462,11 +402,7 @@ __device__ __forceinline__ void schur_groups_body(const BADev &d0, double inv_de
         if (hp) st_rec<12>(d.Jp + (size_t)i * 12, Jp);     // (k_update_groups takes zeros where hasp is clear: the reference's window is 80 % observations of constant poses)
         st_rec<6>(d.Jl + (size_t)i * 6, Jl);
         if (hp) s_slot[pl * hbw + (p - f)] = (short)hpi; else hpi = -1;
-        double *v = s_W + tid * 9;
-        v[0] = Jl[0] * Jl[0] + Jl[3] * Jl[3]; v[1] = Jl[0] * Jl[1] + Jl[3] * Jl[4]; v[2] = Jl[0] * Jl[2] + Jl[3] * Jl[5];
-        v[3] = Jl[1] * Jl[1] + Jl[4] * Jl[4]; v[4] = Jl[1] * Jl[2] + Jl[4] * Jl[5]; v[5] = Jl[2] * Jl[2] + Jl[5] * Jl[5];
-#pragma unroll
-        for (int k = 0; k < 3; k++) v[6 + k] = Jl[k] * r2[0] + Jl[3 + k] * r2[1];
+        jl_products(Jl, r2, s_W + tid * 9);
     }
     SG_CLK(1);
     lds_sync();
@@ -481,11 +417,8 @@ __device__ __forceinline__ void schur_groups_body(const BADev &d0, double inv_de
 #pragma unroll
             for (int c = 0; c < 9; c++) V[c] += s_W[t * 9 + c];
         }
-        V[0] += fmin(fmax(V[0], LM_MIN_DIAGONAL), LM_MAX_DIAGONAL) * inv_delta;
-        V[3] += fmin(fmax(V[3], LM_MIN_DIAGONAL), LM_MAX_DIAGONAL) * inv_delta;
-        V[5] += fmin(fmax(V[5], LM_MIN_DIAGONAL), LM_MAX_DIAGONAL) * inv_delta;
         double Vi[6];
-        inv3_sym(V, Vi);
+        point_solve(V, inv_delta, Vi);
 #pragma unroll
         for (int c = 0; c < 6; c++) { d.Vinv[(size_t)c * M + j] = Vi[c]; s_pt[tid * 10 + c] = Vi[c]; }
 #pragma unroll
@@ -500,16 +433,14 @@ __device__ __forceinline__ void schur_groups_body(const BADev &d0, double inv_de
         for (int c = 0; c < 6; c++) Vi[c] = s_pt[pl * 10 + c];
 #pragma unroll
         for (int c = 0; c < 3; c++) bl[c] = s_pt[pl * 10 + 6 + c];
-        const double vb0 = Vi[0] * bl[0] + Vi[1] * bl[1] + Vi[2] * bl[2];
-        const double vb1 = Vi[1] * bl[0] + Vi[3] * bl[1] + Vi[4] * bl[2];
-        const double vb2 = Vi[2] * bl[0] + Vi[4] * bl[1] + Vi[5] * bl[2];
+        double vb0, vb1, vb2;
+        sym3_mul(Vi, bl, vb0, vb1, vb2);
 #pragma unroll
         for (int a = 0; a < 6; a++) {
-            const double w0 = Jp[a] * Jl[0] + Jp[6 + a] * Jl[3];
-            const double w1 = Jp[a] * Jl[1] + Jp[6 + a] * Jl[4];
-            const double w2 = Jp[a] * Jl[2] + Jp[6 + a] * Jl[5];
-            s_W[hpi * 18 + 3 * a] = w0; s_W[hpi * 18 + 3 * a + 1] = w1; s_W[hpi * 18 + 3 * a + 2] = w2;
-            s_g[hpi * 6 + a] = (Jp[a] * r2[0] + Jp[6 + a] * r2[1]) - (w0 * vb0 + w1 * vb1 + w2 * vb2);
+            double w[3];
+            w_row(Jp, Jl, a, w);
+            s_W[hpi * 18 + 3 * a] = w[0]; s_W[hpi * 18 + 3 * a + 1] = w[1]; s_W[hpi * 18 + 3 * a + 2] = w[2];
+            s_g[hpi * 6 + a] = (Jp[a] * r2[0] + Jp[6 + a] * r2[1]) - (w[0] * vb0 + w[1] * vb1 + w[2] * vb2);
         }
 #pragma unroll
         for (int k = 0; k < 12; k++) s_Jp[hpi * 12 + k] = Jp[k];
@@ -707,11 +638,7 @@ __device__ __forceinline__ void schur_groups_mfma_body(const BADev &d0, int igno
         }
         // (nothing of the evaluation is stored: k_update_groups_b<.., RECOMP> forms it again -- 160 bytes per observation not written here, not read there)
         if (hp) s_slot[pl * hbw + (p - f)] = (short)hpi; else hpi = -1;
-        double *v = s_R + tid * 9;
-        v[0] = Jl[0] * Jl[0] + Jl[3] * Jl[3]; v[1] = Jl[0] * Jl[1] + Jl[3] * Jl[4]; v[2] = Jl[0] * Jl[2] + Jl[3] * Jl[5];
-        v[3] = Jl[1] * Jl[1] + Jl[4] * Jl[4]; v[4] = Jl[1] * Jl[2] + Jl[4] * Jl[5]; v[5] = Jl[2] * Jl[2] + Jl[5] * Jl[5];
-#pragma unroll
-        for (int k = 0; k < 3; k++) v[6 + k] = Jl[k] * r2[0] + Jl[3 + k] * r2[1];
+        jl_products(Jl, r2, s_R + tid * 9);
     }
     SG_CLK(1);
     lds_sync();
@@ -724,11 +651,8 @@ __device__ __forceinline__ void schur_groups_mfma_body(const BADev &d0, int igno
 #pragma unroll
             for (int c = 0; c < 9; c++) V[c] += s_R[t * 9 + c];
         }
-        V[0] += fmin(fmax(V[0], LM_MIN_DIAGONAL), LM_MAX_DIAGONAL) * inv_delta;
-        V[3] += fmin(fmax(V[3], LM_MIN_DIAGONAL), LM_MAX_DIAGONAL) * inv_delta;
-        V[5] += fmin(fmax(V[5], LM_MIN_DIAGONAL), LM_MAX_DIAGONAL) * inv_delta;
         double Vi[6];
-        inv3_sym(V, Vi);
+        point_solve(V, inv_delta, Vi);
 #pragma unroll
         for (int c = 0; c < 6; c++) { g_Vinv[(size_t)c * M + jj] = Vi[c]; s_pt[tid * 16 + c] = Vi[c]; }
 #pragma unroll
@@ -754,17 +678,15 @@ __device__ __forceinline__ void schur_groups_mfma_body(const BADev &d0, int igno
         for (int c = 0; c < 3; c++) bl[c] = s_pt[pl * 16 + 6 + c];
 #pragma unroll
         for (int c = 0; c < 6; c++) L[c] = s_pt[pl * 16 + 9 + c];
-        const double vb0 = Vi[0] * bl[0] + Vi[1] * bl[1] + Vi[2] * bl[2];
-        const double vb1 = Vi[1] * bl[0] + Vi[3] * bl[1] + Vi[4] * bl[2];
-        const double vb2 = Vi[2] * bl[0] + Vi[4] * bl[1] + Vi[5] * bl[2];
+        double vb0, vb1, vb2;
+        sym3_mul(Vi, bl, vb0, vb1, vb2);
         double *E = s_R + hpi * 18;
 #pragma unroll
         for (int a = 0; a < 6; a++) {
-            const double w0 = Jp[a] * Jl[0] + Jp[6 + a] * Jl[3];
-            const double w1 = Jp[a] * Jl[1] + Jp[6 + a] * Jl[4];
-            const double w2 = Jp[a] * Jl[2] + Jp[6 + a] * Jl[5];
-            Y[3 * a] = w0 * L[0] + w1 * L[1] + w2 * L[2]; Y[3 * a + 1] = w1 * L[3] + w2 * L[4]; Y[3 * a + 2] = w2 * L[5];
-            E[12 + a] = (Jp[a] * r2[0] + Jp[6 + a] * r2[1]) - (w0 * vb0 + w1 * vb1 + w2 * vb2);
+            double w[3];
+            w_row(Jp, Jl, a, w);
+            Y[3 * a] = w[0] * L[0] + w[1] * L[1] + w[2] * L[2]; Y[3 * a + 1] = w[1] * L[3] + w[2] * L[4]; Y[3 * a + 2] = w[2] * L[5];
+            E[12 + a] = (Jp[a] * r2[0] + Jp[6 + a] * r2[1]) - (w[0] * vb0 + w[1] * vb1 + w[2] * vb2);
         }
 #pragma unroll
         for (int k = 0; k < 12; k++) E[k] = Jp[k];
@@ -967,8 +889,6 @@ __device__ __forceinline__ void schur_reduce_body(const BADev &d0, int use_state
 #define CT 32
 struct CholArgs { double *A; double *Lf; int n, ld; int *fail; };   // A: working matrix (updated in place); Lf: finished factor tiles
 
-// copy S -> work (lower triangle + rhs row), add the LM damping to the diagonal
-
 // Factor a diagonal tile and invert its triangle, by ONE wave, rows in registers.
 // t (LDS, 32x33): in = tile (lower part, h rows x w valid columns, rows >= w are
 // panel rows riding along), out = L.  inv (LDS): out = L^-1 (w x w lower).
@@ -1048,10 +968,6 @@ __device__ __forceinline__ void tile_mask_lower(double (*t)[CT + 1], int h, int 
     }
 }
 
-
-
-// L' dp = y (y = row n of the factor), blocked from the last tile column upwards;
-// the diagonal solves are mat-vecs with the stored tile inverses.
 
 // ---- banded solve of the reduced camera system in ONE launch --------------------------------------------------------
 // A windowed problem couples pose p only with poses p - hb .. p + hb (a map point is seen by a run of consecutive
@@ -1257,8 +1173,8 @@ __device__ __forceinline__ void band_solve_body(const BADev &d0, const BandArgs 
     }
     if (B.trace && side == 0 && tid == 0) B.trace[106] = clock64() - tr_in;
     // ---- the first window goes into the ring ----
-        if (tid < 6 * nb) damp[tid] = fmin(fmax(udv, LM_MIN_DIAGONAL), LM_MAX_DIAGONAL) * inv_delta;
-        for (int a = tid + BS_T; a < 6 * nb; a += BS_T) damp[a] = fmin(fmax(B.ud[6 * gi(a / 6) + a % 6], LM_MIN_DIAGONAL), LM_MAX_DIAGONAL) * inv_delta;
+        if (tid < 6 * nb) damp[tid] = lm_damp(udv, inv_delta);
+        for (int a = tid + BS_T; a < 6 * nb; a += BS_T) damp[a] = lm_damp(B.ud[6 * gi(a / 6) + a % 6], inv_delta);
         __syncthreads();
         if (B.trace && side == 0 && tid == 0) B.trace[107] = clock64() - tr_in;
 #pragma unroll
@@ -1857,7 +1773,6 @@ static size_t dense_lds_bytes(int F) { return ((size_t)F * (F + 1) / 2 * 36 + (s
 __device__ __forceinline__ void ds_barrier() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local"); __builtin_amdgcn_s_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local"); }
 
 
-
 // k_backsub + k_trial on the point groups of k_schur_groups (one workgroup per group, dp in LDS): thread = observation forms
 // Jl' (Jp dp), thread = point sums them in observation order, dl = V^-1 (bl - sum), trial point; thread = observation again: trial
 // and predicted residual.  Partials: part[g] = max |dx|, part[ngrp + 2 g] = trial cost, part[ngrp + 2 g + 1] = predicted cost.
@@ -1937,7 +1852,7 @@ __device__ __forceinline__ void update_groups_body(const BADev &d0, int ignore_o
         ld_rec<6>(d.Jl + (size_t)i * 6, jl); ld_rec<2>(d.f + 2 * (size_t)i, ff);
         }
 #pragma unroll
-        for (int k = 0; k < 6; k++) { a += jp[k] * s_dp[6 * p + k]; b += jp[6 + k] * s_dp[6 * p + k]; }
+        for (int k = 0; k < 6; k++) { a += jp[k] * s_dp[6 * p + k]; b += jp[6 + k] * s_dp[6 * p + k]; }      // jp_dot (ba_math.hpp), spelled out: the call renames the kernel's registers
 #pragma unroll
         for (int k = 0; k < 3; k++) s_u[tid * 3 + k] = jl[k] * a + jl[3 + k] * b;
     }
@@ -1951,9 +1866,8 @@ __device__ __forceinline__ void update_groups_body(const BADev &d0, int ignore_o
             for (int k = 0; k < 3; k++) bl[k] -= s_u[t * 3 + k];
         }
         const double *Vi = p2_Vi;
-        const double l0 = Vi[0] * bl[0] + Vi[1] * bl[1] + Vi[2] * bl[2];
-        const double l1 = Vi[1] * bl[0] + Vi[3] * bl[1] + Vi[4] * bl[2];
-        const double l2 = Vi[2] * bl[0] + Vi[4] * bl[1] + Vi[5] * bl[2];
+        double l0, l1, l2;
+        sym3_mul(Vi, bl, l0, l1, l2);
         const double X0 = p2_X[0] - l0, X1 = p2_X[1] - l1, X2 = p2_X[2] - l2;
         d.dl[3 * j] = l0; d.dl[3 * j + 1] = l1; d.dl[3 * j + 2] = l2;
         pb.pts_t[3 * j] = X0; pb.pts_t[3 * j + 1] = X1; pb.pts_t[3 * j + 2] = X2;
@@ -2003,32 +1917,6 @@ __device__ __forceinline__ double ctl_max(__attribute__((address_space(1))) cons
     for (int i = threadIdx.x; i < n; i += 256) t = fmax(t, p[i]);
     return block_max(t, sh);
 }
-// LeastSquaresOptim's accept / reject of a trial step (trust-region radius update, step-quality test): t = trial cost,
-// p = predicted cost, mx = max |dx|
-template <class SP>      // LMState * (k_ba_window's copy in LDS) or a pointer typed as global memory
-__device__ __forceinline__ void lm_decide(SP s, double t, double p, double mx)
-{
-    s->iters++;
-    if (s->chol_fail) { s->converged = 1; s->accept = 0; return; }
-    const double ssr = s->ssr;
-    const double rho = (t - ssr) / (p - ssr);
-    if (rho > LM_MIN_STEP_QUALITY) {
-        const int x_conv = mx <= LM_XTOL;
-        const int f_conv = fabs(ssr - t) / (fabs(ssr) + LM_FTOL) <= LM_FTOL;
-        s->ssr = t;
-        const double u = 2.0 * rho - 1.0;
-        s->delta = fmin(s->delta / fmax(1.0 / 3.0, 1.0 - u * u * u), LM_MAX_DELTA);
-        s->decrease_factor = 2.0;
-        s->accept = 1;
-        s->cur ^= 1;                                         // the trial parameters become the committed ones
-        s->converged = x_conv || f_conv;
-    } else {
-        s->delta = fmax(s->delta / s->decrease_factor, LM_MIN_DELTA);
-        s->decrease_factor *= 2.0;
-        s->accept = 0;
-        s->converged = mx <= LM_XTOL;
-    }
-}
 __device__ __forceinline__ void control_body(const BADev &d0, int mode, int nb_obs, int nb_pts, int lm, double *out4)
 {
     const BADevG d = ba_global(d0);                          // (global_load / global_store, not flat accesses, where the caller read the window out of the batch's table)
@@ -2052,14 +1940,6 @@ __device__ __forceinline__ void control_body(const BADev &d0, int mode, int nb_o
     lm_decide(s, t, p, mx);
 }
 
-// The sharded path: every rank's [trial_ssr, pred_ssr, max|dx|, chol_fail] gathered into g (nranks x 4).  Sums / maxima in
-// rank order, then the same decision as the single-GPU path -- identical on every rank, taken on the device.
-// start of an LM pass in the sharded path: the all-reduced cost of the current parameters comes from the reduce buffer
-
-// host-paced protocol (slam_ba_commit): the host has decided -- an accepted step swaps the two parameter buffers.  (The device-paced
-// paths swap inside lm_decide: no launch at all.)
-
-
 // _ba_detect_outliers!, bundle_adjustment.jl:90-111
 __device__ __forceinline__ void outliers_body(const BADev &d0, double repr_eps, double depth_eps)
 {
@@ -2075,7 +1955,7 @@ __device__ __forceinline__ void outliers_body(const BADev &d0, double repr_eps, 
 #pragma unroll
         for (int k = 0; k < 6; k++) pose[k] = pb.pose[6 * p + k];
         obs_eval(pose, X, d.pix[i], d.pix[O + i], d.cam, r, nullptr, nullptr, &z);
-        const bool out = z < depth_eps || (r[0] * r[0] + r[1] * r[1]) > repr_eps;
+        const bool out = obs_is_outlier(z, r, depth_eps, repr_eps);
         d.outl[i] = out ? 1 : 0;
         c = out ? 1.0 : 0.0;
     }
@@ -2098,10 +1978,11 @@ __device__ __forceinline__ void outlier_count_body(const BADev &d0, int nb_obs)
 
 struct BAWin { BADev d; BandArgs B; int nb_obs, nb_pts, n_red, pad; int ksplit, pad2; double *bwx; };   // ksplit / bwx: k_ba_window on TWO workgroups -- the first map point (sorted order) of the second one, their exchange area      // pad = 1: the window runs in k_ba_window (one workgroup, all iterations)
 static_assert(sizeof(BAWin) % 8 == 0, "BAWin is copied as 64-bit words");
-__device__ __forceinline__ BAWin ba_win(const BAWin *tab)
+template <class I>       // (the index keeps its type: unsigned for blockIdx.y, int for an entry of k_ba_window's list -- the address arithmetic follows it)
+__device__ __forceinline__ BAWin ba_win_at(const BAWin *tab, I index)
 {
     typedef const __attribute__((address_space(4))) unsigned long long *cq_t;
-    cq_t q = (cq_t)(const void *)(tab + blockIdx.y);
+    cq_t q = (cq_t)(const void *)(tab + index);
     unsigned long long raw[sizeof(BAWin) / 8];
 #pragma unroll
     for (int k = 0; k < (int)(sizeof(BAWin) / 8); k++) raw[k] = q[k];
@@ -2109,6 +1990,7 @@ __device__ __forceinline__ BAWin ba_win(const BAWin *tab)
     __builtin_memcpy(&w, raw, sizeof w);
     return w;
 }
+__device__ __forceinline__ BAWin ba_win(const BAWin *tab) { return ba_win_at(tab, blockIdx.y); }      // the batch kernels: blockIdx.y = window
 
 #ifdef BW_TRACE
 #define BW_CLK(k) do { if (tid == 0) bw_clk[k] = clock64(); } while (0)

@@ -24,7 +24,8 @@
 //   k_linearize, k_points, k_obs_factors, k_blocks (pair lists sorted by pose block), k_backsub, k_trial.
 // Observations are re-ordered by map point at upload (map points by first free observer) so a point's observations
 // and a group's points are contiguous.
-// (this file: the single-window kernels, slam_local_ba, the sharded slam_ba_* protocol and pnp_bundle_adjustment)
+// (this file: the single-window kernels -- thin wrappers of ba_device.hpp's bodies, and the fall-back chain, the k_chol_* chain, k_dense_solve, the one-thread
+//  LM kernels and k_pnp written out here --, slam_local_ba, the sharded slam_ba_* protocol and pnp_bundle_adjustment; the shared formulas: ba_math.hpp)
 #include "ba_device.hpp"
 
 __global__ __launch_bounds__(256) void k_linearize(BADev d, int ignore_outliers, int respect_done) { linearize_body(d, ignore_outliers, respect_done); }
@@ -40,23 +41,22 @@ __global__ __launch_bounds__(256) void k_points(BADev d, double inv_delta_host, 
     for (int i = t0; i < t1; i++) {
         double jl[6], ff[2];
         ld_rec<6>(d.Jl + (size_t)i * 6, jl); ld_rec<2>(d.f + 2 * (size_t)i, ff);
-        const double f0 = ff[0], f1 = ff[1];
-        V[0] += jl[0] * jl[0] + jl[3] * jl[3]; V[1] += jl[0] * jl[1] + jl[3] * jl[4]; V[2] += jl[0] * jl[2] + jl[3] * jl[5];
-        V[3] += jl[1] * jl[1] + jl[4] * jl[4]; V[4] += jl[1] * jl[2] + jl[4] * jl[5]; V[5] += jl[2] * jl[2] + jl[5] * jl[5];
+        double v9[9];
+        jl_products(jl, ff, v9);
 #pragma unroll
-        for (int k = 0; k < 3; k++) bl[k] += jl[k] * f0 + jl[3 + k] * f1;
+        for (int k = 0; k < 6; k++) V[k] += v9[k];
+#pragma unroll
+        for (int k = 0; k < 3; k++) bl[k] += v9[6 + k];
     }
-    V[0] += fmin(fmax(V[0], LM_MIN_DIAGONAL), LM_MAX_DIAGONAL) * inv_delta;
-    V[3] += fmin(fmax(V[3], LM_MIN_DIAGONAL), LM_MAX_DIAGONAL) * inv_delta;
-    V[5] += fmin(fmax(V[5], LM_MIN_DIAGONAL), LM_MAX_DIAGONAL) * inv_delta;
     double Vi[6];
-    inv3_sym(V, Vi);
+    point_solve(V, inv_delta, Vi);
 #pragma unroll
     for (int k = 0; k < 6; k++) d.Vinv[(size_t)k * M + j] = Vi[k];
 #pragma unroll
     for (int k = 0; k < 3; k++) d.bl[(size_t)k * M + j] = bl[k];
 }
 
+// per observation: W = Jp'Jl (6x3), T = W V^-1 of its point
 __global__ __launch_bounds__(256) void k_obs_factors(BADev d, int use_state)
 {
     if (use_state && d.st->converged) return;
@@ -76,17 +76,13 @@ __global__ __launch_bounds__(256) void k_obs_factors(BADev d, int use_state)
     for (int k = 0; k < 6; k++) Vi[k] = d.Vinv[(size_t)k * M + j];
 #pragma unroll
     for (int a = 0; a < 6; a++) {
-        const double w0 = jp[a] * jl[0] + jp[6 + a] * jl[3];
-        const double w1 = jp[a] * jl[1] + jp[6 + a] * jl[4];
-        const double w2 = jp[a] * jl[2] + jp[6 + a] * jl[5];
-        wv[3 * a] = w0; wv[3 * a + 1] = w1; wv[3 * a + 2] = w2;
-        tv[3 * a] = w0 * Vi[0] + w1 * Vi[1] + w2 * Vi[2];
-        tv[3 * a + 1] = w0 * Vi[1] + w1 * Vi[3] + w2 * Vi[4];
-        tv[3 * a + 2] = w0 * Vi[2] + w1 * Vi[4] + w2 * Vi[5];
+        w_row(jp, jl, a, wv + 3 * a);
+        sym3_mul(Vi, wv + 3 * a, tv[3 * a], tv[3 * a + 1], tv[3 * a + 2]);      // row a of T = W V^-1 (V^-1 is symmetric)
     }
     st_rec<18>(Wo, wv); st_rec<18>(To, tv);
 }
 
+// One wave per non-zero upper block (p <= q) of the reduced camera system.
 __global__ __launch_bounds__(256) void k_blocks(BADev d, int use_state)
 {
     __shared__ double s_red[4][48];
@@ -162,6 +158,7 @@ __global__ __launch_bounds__(256) void k_blocks(BADev d, int use_state)
 
 __global__ __launch_bounds__(SG_T) void k_schur_groups(BADev d, double inv_delta_host, int ignore_outliers, int use_state) { schur_groups_body<SG_T>(d, inv_delta_host, ignore_outliers, use_state); }
 __global__ __launch_bounds__(256) void k_schur_reduce(BADev d, int use_state) { schur_reduce_body(d, use_state); }
+// copy S -> work (lower triangle + rhs row), add the LM damping to the diagonal
 __global__ __launch_bounds__(256) void k_chol_prepare(BADev d, const double *Sin, const double *gin, const double *udin,
                                                       double inv_delta_host, int use_state)
 {
@@ -175,7 +172,7 @@ __global__ __launch_bounds__(256) void k_chol_prepare(BADev d, const double *Sin
     if (i == n) v = gin[j];
     else {
         v = Sin[(size_t)i + (size_t)j * n];
-        if (i == j) v += fmin(fmax(udin[j], LM_MIN_DIAGONAL), LM_MAX_DIAGONAL) * inv_delta;
+        if (i == j) v += lm_damp(udin[j], inv_delta);
     }
     d.Swork[idx] = v;
 }
@@ -284,6 +281,8 @@ __global__ __launch_bounds__(256) void k_chol_first(BADev d, CholArgs C, double 
     }
 }
 
+// L' dp = y (y = row n of the factor), blocked from the last tile column upwards;
+// the diagonal solves are mat-vecs with the stored tile inverses.
 __global__ __launch_bounds__(256) void k_chol_backsolve(BADev d, CholArgs C, const double *Linv, int use_state)
 {
     if (use_state && d.st->converged) return;
@@ -389,7 +388,7 @@ __global__ __launch_bounds__(DS_T) void k_dense_solve(BADev d, BandArgs B, int u
         for (int u = 0; u < NL; u++) { const int e = tid + u * DS_T; if (e < nblk * 36) A[e] = v[u]; }
         if (tid < ns) y[tid] = gv;
         ds_barrier();
-        if (tid < ns) { const int k = tid / 6, r = tid - 6 * k; A[(size_t)(k * (k + 1) / 2 + k) * 36 + 7 * r] += fmin(fmax(udv, LM_MIN_DIAGONAL), LM_MAX_DIAGONAL) * inv_delta; }
+        if (tid < ns) { const int k = tid / 6, r = tid - 6 * k; A[(size_t)(k * (k + 1) / 2 + k) * 36 + 7 * r] += lm_damp(udv, inv_delta); }
     }
     ds_barrier();
     // Cholesky of the diagonal block (k, k) by wave 0.  upd: the block first loses L_{k,k-1} L_{k,k-1}^T (the previous column's trailing update
@@ -574,19 +573,16 @@ __global__ __launch_bounds__(256) void k_backsub(BADev d, int use_state)
         double bl[3] = {d.bl[j], d.bl[(size_t)M + j], d.bl[(size_t)2 * M + j]};
         for (int i = d.pt_start[kk]; i < d.pt_start[kk + 1]; i++) {
             if (!d.hasp[i]) continue;
-            const double *dp = d.dp + 6 * d.opose[i];
             double a = 0.0, b = 0.0;
-#pragma unroll
-            for (int k = 0; k < 6; k++) { a += d.Jp[(size_t)i * 12 + k] * dp[k]; b += d.Jp[(size_t)i * 12 + 6 + k] * dp[k]; }
+            jp_dot(d.Jp + (size_t)i * 12, d.dp + 6 * d.opose[i], a, b);
 #pragma unroll
             for (int k = 0; k < 3; k++) bl[k] -= d.Jl[(size_t)i * 6 + k] * a + d.Jl[(size_t)i * 6 + 3 + k] * b;
         }
         double Vi[6];
 #pragma unroll
         for (int k = 0; k < 6; k++) Vi[k] = d.Vinv[(size_t)k * M + j];
-        const double l0 = Vi[0] * bl[0] + Vi[1] * bl[1] + Vi[2] * bl[2];
-        const double l1 = Vi[1] * bl[0] + Vi[3] * bl[1] + Vi[4] * bl[2];
-        const double l2 = Vi[2] * bl[0] + Vi[4] * bl[1] + Vi[5] * bl[2];
+        double l0, l1, l2;
+        sym3_mul(Vi, bl, l0, l1, l2);
         d.dl[3 * j] = l0; d.dl[3 * j + 1] = l1; d.dl[3 * j + 2] = l2;
         pb.pts_t[3 * j] = pb.pts[3 * j] - l0; pb.pts_t[3 * j + 1] = pb.pts[3 * j + 1] - l1; pb.pts_t[3 * j + 2] = pb.pts[3 * j + 2] - l2;
         mx = fmax(fabs(l0), fmax(fabs(l1), fabs(l2)));
@@ -614,9 +610,8 @@ __global__ __launch_bounds__(256) void k_trial(BADev d, int ignore_outliers, int
             obs_eval(pose, X, d.pix[i], d.pix[O + i], d.cam, r, nullptr, nullptr, nullptr);
         }
         double a = 0.0, b = 0.0;
-        const double *dp = d.dp + 6 * p, *dl = d.dl + 3 * j;
-#pragma unroll
-        for (int k = 0; k < 6; k++) { a += d.Jp[(size_t)i * 12 + k] * dp[k]; b += d.Jp[(size_t)i * 12 + 6 + k] * dp[k]; }
+        const double *dl = d.dl + 3 * j;
+        jp_dot(d.Jp + (size_t)i * 12, d.dp + 6 * p, a, b);
 #pragma unroll
         for (int k = 0; k < 3; k++) { a += d.Jl[(size_t)i * 6 + k] * dl[k]; b += d.Jl[(size_t)i * 6 + 3 + k] * dl[k]; }
         a -= d.f[2 * (size_t)i]; b -= d.f[2 * (size_t)i + 1];
@@ -635,6 +630,8 @@ __global__ __launch_bounds__(SG_T) void k_update_groups(BADev d, int ignore_outl
 }
 
 __global__ __launch_bounds__(256) void k_control(BADev d, int mode, int nb_obs, int nb_pts, int lm, double *out4) { control_body(d, mode, nb_obs, nb_pts, lm, out4); }
+// The sharded path: every rank's [trial_ssr, pred_ssr, max|dx|, chol_fail] gathered into g (nranks x 4).  Sums / maxima in
+// rank order, then the same decision as the single-GPU path -- identical on every rank, taken on the device.
 __global__ void k_control_gathered(BADev d, const double *g, int nranks)
 {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
@@ -647,15 +644,18 @@ __global__ void k_control_gathered(BADev d, const double *g, int nranks)
     lm_decide(s, t, p, mx);
 }
 
+// start of an LM pass in the sharded path: the all-reduced cost of the current parameters comes from the reduce buffer
 __global__ void k_lm_start(BADev d, const double *ssr_slot, int first_pass)
 {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     LMState *s = d.st;
     s->ssr = *ssr_slot;
-    if (first_pass) { s->ssr_init = s->ssr; s->chol_fail = 0; }
-    s->delta = LM_DELTA0; s->decrease_factor = 2.0; s->converged = 0; s->accept = 0; s->iters = 0;
+    if (first_pass) lm_first_pass(s, false);                 // (this protocol never cleared n_outliers here: kept)
+    lm_trust_reset(s);
 }
 
+// host-paced protocol (slam_ba_commit): the host has decided -- an accepted step swaps the two parameter buffers.  (The device-paced
+// paths swap inside lm_decide: no launch at all.)
 __global__ void k_commit(BADev d, int accept_host)
 {
     if (threadIdx.x == 0 && blockIdx.x == 0 && accept_host) d.st->cur ^= 1;
@@ -665,10 +665,10 @@ __global__ void k_lm_reset(BADev d, int pass)
 {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     LMState *s = d.st;
-    if (pass == 0) { s->ssr_init = s->ssr; s->chol_fail = 0; s->n_outliers = 0; }
-    if (pass == 3) { s->ssr_pass1 = s->ssr; s->iters_pass1 = s->iters; return; }   // record the end of pass 1
-    if (pass == 2) { s->ssr_final = s->ssr; s->iters_pass2 = s->iters; return; }   // record the end of pass 2
-    s->delta = LM_DELTA0; s->decrease_factor = 2.0; s->converged = 0; s->accept = 0; s->iters = 0;
+    if (pass == 0) lm_first_pass(s);
+    if (pass == 3) { lm_record_pass(s, 1); return; }         // record the end of pass 1
+    if (pass == 2) { lm_record_pass(s, 2); return; }         // record the end of pass 2
+    lm_trust_reset(s);
 }
 
 __global__ __launch_bounds__(256) void k_outliers(BADev d, double repr_eps, double depth_eps) { outliers_body(d, repr_eps, depth_eps); }
@@ -1122,7 +1122,7 @@ __device__ __forceinline__ int pnp_lm(const PnPArgs &A, pnp_gcd gpx, pnp_gcd gpt
 #pragma unroll
             for (int k = 0; k < 36; k++) H[k] = Hs[k];
 #pragma unroll
-            for (int a = 0; a < 6; a++) { H[a + 6 * a] += fmin(fmax(Hs[a + 6 * a], LM_MIN_DIAGONAL), LM_MAX_DIAGONAL) * (1 / delta); x[a] = gs[a]; }
+            for (int a = 0; a < 6; a++) { H[a + 6 * a] += lm_damp(Hs[a + 6 * a], 1 / delta); x[a] = gs[a]; }
             int fail = 0;
 #pragma unroll
             for (int j = 0; j < 6; j++) {
@@ -1169,7 +1169,7 @@ __device__ __forceinline__ int pnp_lm(const PnPArgs &A, pnp_gcd gpx, pnp_gcd gpt
             obs_eval(X, (const double *)(gpts + 3 * i), gpx[2 * i], gpx[2 * i + 1], A.cam, r, Jp, Jl, nullptr);
             double a = 0.0, b = 0.0;
 #pragma unroll
-            for (int k = 0; k < 6; k++) { a += Jp[k] * dxs[k]; b += Jp[6 + k] * dxs[k]; }
+            for (int k = 0; k < 6; k++) { a += Jp[k] * dxs[k]; b += Jp[6 + k] * dxs[k]; }      // jp_dot (ba_math.hpp), spelled out: the call changes k_pnp's instructions
             a -= r[0]; b -= r[1];
             v[0] += rt[0] * rt[0] + rt[1] * rt[1];
             v[1] += a * a + b * b;
@@ -1178,6 +1178,7 @@ __device__ __forceinline__ int pnp_lm(const PnPArgs &A, pnp_gcd gpx, pnp_gcd gpt
         const double trial = red[0], pred = red[1];
         double mx = 0.0;
         for (int a = 0; a < 6; a++) mx = fmax(mx, fabs(dxs[a]));
+        // (lm_decide's rule, ba_math.hpp, on local variables: a change there is a change here)
         const double rho = (trial - ssr) / (pred - ssr);
         if (rho > LM_MIN_STEP_QUALITY) {
             const int x_conv = mx <= LM_XTOL;
@@ -1223,7 +1224,7 @@ __device__ __forceinline__ void pnp_body(const PnPArgs &A)
     for (int i = tid; i < n; i += PNP_T) {
         double r[2], z;
         obs_eval(X, (const double *)(gpts + 3 * i), gpx[2 * i], gpx[2 * i + 1], A.cam, r, nullptr, nullptr, &z);
-        const bool o = z < A.depth_eps || (r[0] * r[0] + r[1] * r[1]) > A.repr_eps;
+        const bool o = obs_is_outlier(z, r, A.depth_eps, A.repr_eps);
         goutl[i] = o ? 1 : 0;
         v[0] += o ? 1.0 : 0.0;
     }

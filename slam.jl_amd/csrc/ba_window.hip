@@ -1,5 +1,5 @@
 // ba_window.hip -- k_ba_window: the whole two-pass Levenberg-Marquardt of one small window in one (or two) workgroups (src/bundle_adjustment.jl:1-111,
-// windows of <= 5 free key-frames: src/estimator.jl:327-331).  Launched by ba_batch.hip.
+// windows of <= 5 free key-frames: src/estimator.jl:327-331).  Launched by ba_batch.hip; the formulas it shares with the other routes are ba_math.hpp's.
 #include "ba_device.hpp"
 
 // ---- small windows: the WHOLE two-pass Levenberg-Marquardt of one window in ONE workgroup, one launch for the batch -------------------
@@ -19,28 +19,8 @@
 // poses that are not consecutive, > 128 poses or > BW_OMAX observations take the batch kernels above.
 // (First version, thread = map point with a serial loop over its observations at 512 threads: 235 us per iteration -- two waves per
 //  SIMD cannot hide the dependent loads and the Float64 latency of ten evaluations in a row; slower than the kernels it replaces.)
-__device__ __forceinline__ double bw_sum(double v, double *sh)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double t = 0.0;
-    for (int w = 0; w < BW_T / 64; w++) t += sh[w];
-    return t;
-}
-__device__ __forceinline__ double bw_max(double v, double *sh)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = fmax(v, __shfl_xor(v, m));
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double t = 0.0;
-    for (int w = 0; w < BW_T / 64; w++) t = fmax(t, sh[w]);
-    return t;
-}
+__device__ __forceinline__ double bw_sum(double v, double *sh) { return block_reduce<RedSum, false, BW_T / 64>(v, sh); }
+__device__ __forceinline__ double bw_max(double v, double *sh) { return block_reduce<RedMax, false, BW_T / 64>(v, sh); }
 __device__ __forceinline__ void bw_wave_sync() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); }
 // TWO WORKGROUPS PER WINDOW (two != 0; 128 windows then use all 256 compute units): workgroups b and b + 8 (same XCD) share window
 // (b & 7) + 8 (b >> 4); half h takes the map points [0, ksplit) / [ksplit, M) and their observations through every phase, and the two
@@ -53,16 +33,8 @@ __global__ __launch_bounds__(BW_T) void k_ba_window(const BAWin *tab, const int 
     const int half = two ? (int)((blockIdx.x >> 3) & 1) : 0;
     const int widx = two ? (int)((blockIdx.x & 7) + 8 * (blockIdx.x >> 4)) : (int)blockIdx.x;
     if (widx >= ns) return;
-    BAWin w;
-    {   typedef const __attribute__((address_space(4))) unsigned long long *cq_t;
-        cq_t q = (cq_t)(const void *)(tab + list[widx]);
-        unsigned long long raw[sizeof(BAWin) / 8];
-#pragma unroll
-        for (int k = 0; k < (int)(sizeof(BAWin) / 8); k++) raw[k] = q[k];
-        __builtin_memcpy(&w, raw, sizeof w); }
-    BADevG dg;                                                 // the window's arrays as GLOBAL-memory pointers (global_load / global_store, not flat accesses: ba_device.hpp)
-    __builtin_memcpy(&dg, &w.d, sizeof dg);
-    const BADevG &d = dg;
+    const BAWin w = ba_win_at(tab, list[widx]);
+    const BADevG d = ba_global(w.d);                           // the window's arrays as GLOBAL-memory pointers (global_load / global_store, not flat accesses: ba_device.hpp)
     extern __shared__ __attribute__((aligned(16))) double bw_sm[];
     const int tid = threadIdx.x;
     const int P = d.P, M = d.M, O = d.O, p0 = w.B.p0, F = w.B.nb, n = 6 * F, nwin = F * (F + 1) / 2;
@@ -180,8 +152,8 @@ __global__ __launch_bounds__(BW_T) void k_ba_window(const BAWin *tab, const int 
             xscal(t, tz1, tz2);
             if (tid == 0) {
                 s->ssr = t;
-                if (pass == 0) { s->ssr_init = t; s->chol_fail = 0; s->n_outliers = 0; }
-                s->delta = LM_DELTA0; s->decrease_factor = 2.0; s->converged = 0; s->accept = 0; s->iters = 0;
+                if (pass == 0) lm_first_pass(s);
+                lm_trust_reset(s);
             }
             __syncthreads();
         }
@@ -217,11 +189,7 @@ __global__ __launch_bounds__(BW_T) void k_ba_window(const BAWin *tab, const int 
                         st_rec<2>(d.f + 2 * (size_t)i, r);
                         st_rec<6>(d.Jl + (size_t)i * 6, Jl);
                         if (hp) st_rec<12>(d.Jp + (size_t)i * 12, Jp);
-                        double *v = s_w9 + t * 9;
-                        v[0] = Jl[0] * Jl[0] + Jl[3] * Jl[3]; v[1] = Jl[0] * Jl[1] + Jl[3] * Jl[4]; v[2] = Jl[0] * Jl[2] + Jl[3] * Jl[5];
-                        v[3] = Jl[1] * Jl[1] + Jl[4] * Jl[4]; v[4] = Jl[1] * Jl[2] + Jl[4] * Jl[5]; v[5] = Jl[2] * Jl[2] + Jl[5] * Jl[5];
-#pragma unroll
-                        for (int c = 0; c < 3; c++) v[6 + c] = Jl[c] * r[0] + Jl[3 + c] * r[1];
+                        jl_products(Jl, r, s_w9 + t * 9);
                     }
                     bw_wave_sync();
                     if (ln < k1 - k0) {
@@ -232,11 +200,8 @@ __global__ __launch_bounds__(BW_T) void k_ba_window(const BAWin *tab, const int 
 #pragma unroll
                             for (int c = 0; c < 9; c++) V[c] += s_w9[t * 9 + c];
                         }
-                        V[0] += fmin(fmax(V[0], LM_MIN_DIAGONAL), LM_MAX_DIAGONAL) * inv_delta;
-                        V[3] += fmin(fmax(V[3], LM_MIN_DIAGONAL), LM_MAX_DIAGONAL) * inv_delta;
-                        V[5] += fmin(fmax(V[5], LM_MIN_DIAGONAL), LM_MAX_DIAGONAL) * inv_delta;
                         double Vi[6];
-                        inv3_sym(V, Vi);
+                        point_solve(V, inv_delta, Vi);
 #pragma unroll
                         for (int c = 0; c < 6; c++) d.Vinv[(size_t)c * M + k] = Vi[c];
 #pragma unroll
@@ -280,16 +245,14 @@ __global__ __launch_bounds__(BW_T) void k_ba_window(const BAWin *tab, const int 
                     for (int c = 0; c < 6; c++) Vi[c] = s_pt[x * 10 + c];
 #pragma unroll
                     for (int c = 0; c < 3; c++) bl[c] = s_pt[x * 10 + 6 + c];
-                    const double vb0 = Vi[0] * bl[0] + Vi[1] * bl[1] + Vi[2] * bl[2];
-                    const double vb1 = Vi[1] * bl[0] + Vi[3] * bl[1] + Vi[4] * bl[2];
-                    const double vb2 = Vi[2] * bl[0] + Vi[4] * bl[1] + Vi[5] * bl[2];
+                    double vb0, vb1, vb2;
+                    sym3_mul(Vi, bl, vb0, vb1, vb2);
 #pragma unroll
                     for (int a = 0; a < 6; a++) {
-                        const double w0 = jp[a] * jl[0] + jp[6 + a] * jl[3];
-                        const double w1 = jp[a] * jl[1] + jp[6 + a] * jl[4];
-                        const double w2 = jp[a] * jl[2] + jp[6 + a] * jl[5];
-                        s_W[rec * 18 + 3 * a] = w0; s_W[rec * 18 + 3 * a + 1] = w1; s_W[rec * 18 + 3 * a + 2] = w2;
-                        s_gr[rec * 6 + a] = (jp[a] * ff[0] + jp[6 + a] * ff[1]) - (w0 * vb0 + w1 * vb1 + w2 * vb2);
+                        double w[3];
+                        w_row(jp, jl, a, w);
+                        s_W[rec * 18 + 3 * a] = w[0]; s_W[rec * 18 + 3 * a + 1] = w[1]; s_W[rec * 18 + 3 * a + 2] = w[2];
+                        s_gr[rec * 6 + a] = (jp[a] * ff[0] + jp[6 + a] * ff[1]) - (w[0] * vb0 + w[1] * vb1 + w[2] * vb2);
                     }
 #pragma unroll
                     for (int c = 0; c < 12; c++) s_Jp[rec * 12 + c] = jp[c];
@@ -406,7 +369,7 @@ __global__ __launch_bounds__(BW_T) void k_ba_window(const BAWin *tab, const int 
                 // damped Cholesky A = L L': lane i keeps row i of the lower triangle in REGISTERS (lane n: the right-hand side row -- the forward
                 // substitution comes for free); the entries of row jc a step needs are lane broadcasts (v_readlane), not LDS round trips
                 // (a first version walked the rows in LDS: 79 k cycles per solve, every multiply-add behind an exposed LDS latency)
-                if (tid < n) s_A[tid * n + tid] += fmin(fmax(s_ud[tid], LM_MIN_DIAGONAL), LM_MAX_DIAGONAL) * inv_delta;
+                if (tid < n) s_A[tid * n + tid] += lm_damp(s_ud[tid], inv_delta);
                 bw_wave_sync();
                 double a[6 * BW_FMAX];
 #pragma unroll
@@ -482,16 +445,15 @@ __global__ __launch_bounds__(BW_T) void k_ba_window(const BAWin *tab, const int 
                     ld_rec<12>(d.Jp + (size_t)i * 12, jp); ld_rec<6>(d.Jl + (size_t)i * 6, jl);
                     double ua = 0.0, ub = 0.0;
 #pragma unroll
-                    for (int c = 0; c < 6; c++) { ua += jp[c] * s_dp[6 * a + c]; ub += jp[6 + c] * s_dp[6 * a + c]; }
+                    for (int c = 0; c < 6; c++) { ua += jp[c] * s_dp[6 * a + c]; ub += jp[6 + c] * s_dp[6 * a + c]; }      // jp_dot (ba_math.hpp), spelled out: the call swaps operands in this kernel
 #pragma unroll
                     for (int c = 0; c < 3; c++) bl[c] -= jl[c] * ua + jl[3 + c] * ub;
                 }
                 double Vi[6];
 #pragma unroll
                 for (int c = 0; c < 6; c++) Vi[c] = d.Vinv[(size_t)c * M + k];
-                const double l0 = Vi[0] * bl[0] + Vi[1] * bl[1] + Vi[2] * bl[2];
-                const double l1 = Vi[1] * bl[0] + Vi[3] * bl[1] + Vi[4] * bl[2];
-                const double l2 = Vi[2] * bl[0] + Vi[4] * bl[1] + Vi[5] * bl[2];
+                double l0, l1, l2;
+                sym3_mul(Vi, bl, l0, l1, l2);
                 d.dl[3 * k] = l0; d.dl[3 * k + 1] = l1; d.dl[3 * k + 2] = l2;
                 pb.pts_t[3 * j] = pb.pts[3 * j] - l0; pb.pts_t[3 * j + 1] = pb.pts[3 * j + 1] - l1; pb.pts_t[3 * j + 2] = pb.pts[3 * j + 2] - l2;
                 mx = fmax(mx, fmax(fabs(l0), fmax(fabs(l1), fabs(l2))));
@@ -512,7 +474,7 @@ __global__ __launch_bounds__(BW_T) void k_ba_window(const BAWin *tab, const int 
                     double jp[12];
                     ld_rec<12>(d.Jp + (size_t)i * 12, jp);
 #pragma unroll
-                    for (int c = 0; c < 6; c++) { pa += jp[c] * s_dp[6 * a + c]; pbv += jp[6 + c] * s_dp[6 * a + c]; }
+                    for (int c = 0; c < 6; c++) { pa += jp[c] * s_dp[6 * a + c]; pbv += jp[6 + c] * s_dp[6 * a + c]; }      // jp_dot (ba_math.hpp), spelled out: the call reorders the kernel's instructions
                 }
                 if (active) {
                     const double Xt[3] = {pb.pts_t[3 * j], pb.pts_t[3 * j + 1], pb.pts_t[3 * j + 2]};
@@ -536,7 +498,7 @@ __global__ __launch_bounds__(BW_T) void k_ba_window(const BAWin *tab, const int 
                        bw_clk[1] - bw_clk[0], bw_clk[2] - bw_clk[1], bw_clk[3] - bw_clk[2], bw_clk[4] - bw_clk[3], bw_clk[5] - bw_clk[4], bw_clk[6] - bw_clk[5], bw_clk[7] - bw_clk[6]); }
 #endif
         }
-        if (tid == 0) { if (pass == 0) { s->ssr_pass1 = s->ssr; s->iters_pass1 = s->iters; } else { s->ssr_final = s->ssr; s->iters_pass2 = s->iters; } }
+        if (tid == 0) lm_record_pass(s, pass + 1);
         if (pass == 0) {
             // ---- _ba_detect_outliers! at theta_1 (bundle_adjustment.jl:90-111)
             __syncthreads();
@@ -549,7 +511,7 @@ __global__ __launch_bounds__(BW_T) void k_ba_window(const BAWin *tab, const int 
                 const double X[3] = {pb.pts[3 * j], pb.pts[3 * j + 1], pb.pts[3 * j + 2]};
                 double r[2], z;
                 obs_eval_sc(s_sc + 6 * p, s_tr + 3 * p, X, d.pix[i], d.pix[O + i], d.cam, r, nullptr, nullptr, &z);
-                const bool out = z < depth_eps || (r[0] * r[0] + r[1] * r[1]) > repr_eps;
+                const bool out = obs_is_outlier(z, r, depth_eps, repr_eps);
                 d.outl[i] = out ? 1 : 0;
                 cnt += out ? 1.0 : 0.0;
             }
