@@ -7,12 +7,18 @@ lock-stepped stereo streams with every keypoint list resident in HBM -- the call
     KeypointSet.compute_pose_5pt   epipolar outlier filter against the previous key-frame       (compute_pose_5pt!)
     KeypointSet.compute_pose       P3P RANSAC + PnP refinement -> the frame's pose              (compute_pose!)
     key-frames: detect -> keyframe -> right frames -> stereo_match -> triangulate -> triangulate_temporal   (create_keyframe!, mapper)
+    --adaptive-keyframes: KeypointSet.frame_stats + keyframe_required after the pose                 (check_new_kf_required)
 
 No host keypoint arrays anywhere; per frame the host receives S poses, S status words and S list lengths.  It is an
 array-level driver, not SLAM (no map maintenance, no bundle adjustment, no relocalisation): what it shows is that the seams
 compose -- on a rigid synthetic scene the poses it returns are the camera motion.
 
-    python examples/device_frontend.py --frames 12 --streams 4
+Key-frames are taken every `kf_every`-th frame, or, with --adaptive-keyframes, where the reference's rule asks for one
+(front_end.jl:361-393 on the statistics of the lists, one S x 8 read-back per frame).  The streams are lock-stepped -- every launch is
+shared -- so the policy is: a key-frame FOR ALL streams when ANY stream requires one.  Per-stream masks on detect / stereo match /
+triangulate would let each stream follow its own rule; the seams have none yet.
+
+    python examples/device_frontend.py --frames 12 --streams 4 [--adaptive-keyframes]
 """
 import argparse
 import os
@@ -26,9 +32,13 @@ import slam_jl_amd as slam  # noqa: E402
 from slam_jl_amd import synthetic as syn  # noqa: E402
 
 
-def run(lefts, rights, cam, baseline, kf_every=4, max_keypoints=300, seed=0, ctx=None, verbose=False):
+def run(lefts, rights, cam, baseline, kf_every=4, max_keypoints=300, seed=0, ctx=None, verbose=False, adaptive=False, probe=None):
     """lefts / rights: per stream a list of float images in [0, 1] (H, W).  Returns per frame a dict with the S poses
-    (world -> camera, world = the first frame's camera), status words, list lengths and the wall time."""
+    (world -> camera, world = the first frame's camera), status words, list lengths and the wall time.
+    adaptive: frame 0 is a key-frame; after the pose of every later frame the lists' statistics (KeypointSet.frame_stats, flags = 1) go
+    through keyframe_required, and a key-frame is taken for all streams when any stream requires one (kf_every is not used).  Those rows
+    also carry kf_stats (S, 8), kf_required, kf_rule, frames_delta and prev_kf_nb_3d (the key-frame's nb_3d_kpts, from the statistics
+    taken when it was created).  probe(frame, keypoint set, R_compensation (S, 3, 3)) is called right after the statistics are taken."""
     import torch
     ctx = ctx or slam.default_context(0)
     S = len(lefts); n_frames = len(lefts[0])
@@ -47,6 +57,7 @@ def run(lefts, rights, cam, baseline, kf_every=4, max_keypoints=300, seed=0, ctx
     Tcw = np.tile(np.eye(4), (S, 1, 1)); Tkf = Tcw.copy()
     NKF = 8; kf_cw = np.tile(np.eye(4), (S, NKF, 1, 1)); n_kf = 0          # poses of the last key-frames (triangulate_temporal!'s observers)
     sp_right = slam.stream_params(S, cam=cam, shift_yx=np.zeros((S, 2)))
+    last_kf, prev_kf_nb_3d = 0, np.zeros(S, np.int32)                  # adaptive: frame id and nb_3d_kpts of the previous key-frame
     out = []
     for i in range(n_frames):
         t0 = time.perf_counter()
@@ -69,7 +80,21 @@ def run(lefts, rights, cam, baseline, kf_every=4, max_keypoints=300, seed=0, ctx
             for s in range(S):
                 if status[s]:
                     Tcw[s] = poses[s]
-        if i % kf_every == 0:
+        is_kf, decision = i % kf_every == 0, {}
+        if adaptive:
+            is_kf = i == 0
+            if i > 0:                                                       # check_new_kf_required, front_end.jl:117
+                Rc = np.tile(np.eye(4), (S, 1, 1))
+                for s in range(S):
+                    Rc[s, :3, :3] = Tkf[s, :3, :3] @ Tcw[s, :3, :3].T      # against the pose just computed
+                stats = ks.frame_stats(slam.stream_params(S, Tcw=Rc, cam=cam), 1, ex.cell_size, (H, W), ctx=ctx)
+                if probe is not None:
+                    probe(i, ks, Rc[:, :3, :3].copy())
+                fd = np.full(S, i - last_kf, np.int32)
+                req, rule = slam.keyframe_required(stats, fd, prev_kf_nb_3d, np.ones(S, np.uint8), params, local_ba_on=False)
+                is_kf = bool(req.any())                                     # lock-step: one stream's need is every stream's key-frame
+                decision = dict(kf_stats=stats, kf_required=req, kf_rule=rule, frames_delta=fd, prev_kf_nb_3d=prev_kf_nb_3d.copy())
+        if is_kf:
             ks.detect(ex, cur, ctx=ctx)
             ks.keyframe(ctx=ctx)
             Tkf = Tcw.copy()
@@ -82,9 +107,13 @@ def run(lefts, rights, cam, baseline, kf_every=4, max_keypoints=300, seed=0, ctx
             ks.triangulate(cam, cam, T21, Twc, max_error=params.max_reprojection_error, ctx=ctx)
             if kfid > 0:                                                    # mapper.jl:86: 2-D keypoints left over, against their first observers
                 ks.triangulate_temporal(slam.stream_params(S, cam=cam), kf_cw, Twc, kfid, max_error=params.max_reprojection_error, ctx=ctx)
+            if adaptive:                                                    # the key-frame's own nb_3d_kpts, after the mapper's triangulations
+                last_kf = i
+                prev_kf_nb_3d = ks.frame_stats(slam.stream_params(S, cam=cam), 0, ex.cell_size, (H, W), ctx=ctx)[:, 1].astype(np.int32)
         cnt = ks.counts(ctx=ctx)
-        row = dict(frame=i, keyframe=i % kf_every == 0, poses=Tcw.copy(), status=status.copy(), status_5pt=np.asarray(st5).copy(),
+        row = dict(frame=i, keyframe=is_kf, poses=Tcw.copy(), status=status.copy(), status_5pt=np.asarray(st5).copy(),
                    counts=cnt.copy(), ms=(time.perf_counter() - t0) * 1e3)
+        row.update(decision)
         out.append(row)
         if verbose:
             print(f"frame {i:3d} kf={row['keyframe']!s:5} keypoints {cnt.tolist()} pose ok {status.tolist()} 5pt ok {np.asarray(st5).tolist()} "
@@ -109,11 +138,12 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=12)
     ap.add_argument("--streams", type=int, default=2)
+    ap.add_argument("--adaptive-keyframes", action="store_true", help="take key-frames where check_new_kf_required asks for one (any stream), not every 4th frame")
     ap.add_argument("--replay-dir", default=None, help="write stream s's camera positions to DIR/stream_s as a ReplaySaver dump (src/io/saver.jl)")
     args = ap.parse_args()
     cam, baseline, disparity = syn.KITTI_CAM, 0.54, 8.0
     lefts, rights, offs = synthetic_scene(args.streams, args.frames, disparity=disparity)
-    out, n3 = run(lefts, rights, cam, baseline, verbose=True)
+    out, n3 = run(lefts, rights, cam, baseline, verbose=True, adaptive=args.adaptive_keyframes)
     Z = cam[0] * baseline / disparity
     for s in range(args.streams):
         o = offs[s][-1] - offs[s][0]

@@ -370,6 +370,39 @@ int slam_kpset_compute_pose_5pt(slam_ctx *ctx, slam_kpset *ks, const double *par
                                 int iters, uint64_t seed, double *P, int32_t *status, int32_t *n_inliers, double *parallax,
                                 int32_t *counts);
 
+/* What the front-end's key-frame tests read of a frame -- check_new_kf_required (front_end.jl:361-393, run at the end of every
+ * track_mono!, :117) and check_ready_for_init! (:343-354) -- reduced from the lists, one workgroup per stream, SLAM_KF_STATS doubles
+ * per stream (counts are held as doubles: one array, one copy):
+ *   [0] list length   [1] nb_3d_kpts   [2] nb_stereo_kpts   [3] keypoints the previous key-frame observes
+ *   [4] nb_occupied_cells (frame.jl:321-337): distinct cells (round(y) / cell_size + 1, round(x) / cell_size + 1) -- round to nearest even,
+ *       truncating division (SLAM.jl:30,42-45) -- in the grid of ceil(height / cell_size) x ceil(width / cell_size) cells (frame.jl:130-132).
+ *       A keypoint whose cell lies outside that grid (NaN and +-inf included) is NOT counted; the reference would throw at grid[kpi].
+ *   [5] n_parallax   [6] mean parallax   [7] median parallax -- compute_parallax (front_end.jl:412-452) over the keypoints the previous
+ *       key-frame observes (flags bit 1 = only_2d: the 2-D ones among them): |upx - undistort(key-frame pixel)| with upx = undistort(pixel),
+ *       or, flags bit 0 = compensate_rotation, upx = project(camera, R_compensation * backproject(undistort(pixel))) -- then the mean is
+ *       the average parallax of slam_kpset_compute_pose_5pt.  The median is Julia's: the middle order statistic, lo / 2 + hi / 2 of the
+ *       two middle ones for an even number, NaN if any term is NaN -- exact for any list length (a radix select, no sort).  Both are
+ *       0.0 when n_parallax == 0 (:444).
+ * params: S x 32 as for slam_kpset_compute_pose_5pt ([0..8] R_compensation = Rcw(key-frame) Rwc(frame), dense column-major 3 x 3;
+ * [16..23] fx fy cx cy k1 k2 p1 p2).  check_new_kf_required calls with flags = 1, check_ready_for_init! with flags = 2.
+ * cell_size, height, width > 0; at most 131072 cells.  The lists are only read.
+ * stats == NULL: the call only enqueues; the results go to stats_dev (caller-owned HBM, S x SLAM_KF_STATS doubles) or, stats_dev == NULL,
+ * to a buffer of the set.  stats != NULL: the call ends with the one device -> host copy of S x SLAM_KF_STATS doubles and a wait for ctx's
+ * stream; [0] is the list length, so a loop that calls this need not call slam_kpset_counts as well. */
+#define SLAM_KF_STATS 8
+int slam_kpset_frame_stats(slam_ctx *ctx, slam_kpset *ks, const double *params, int flags, int cell_size, int height, int width,
+                           double *stats_dev, double *stats);
+/* check_new_kf_required (front_end.jl:361-393) line for line, per stream, on host arrays (no context, no device): stats = the S x
+ * SLAM_KF_STATS array of slam_kpset_frame_stats with flags = 1; frames_delta[s] = frame id - key-frame id; prev_kf_nb_3d[s] = the
+ * key-frame's own nb_3d_kpts (the mapper and the estimator change it after creation: the host owns it); has_prev_kf[s] = 0: the key-frame
+ * is not in the map (:363).  Comparisons are the reference's, in doubles, against its own products (nb < 0.33 * max_nb_keypoints ...).  required[s] = 1: insert a
+ * key-frame.  rule (nullable) names the exit: 0 no previous key-frame -> 0 (:363); 1 few occupied cells -> 1 (:367-370); 2 fewer than
+ * 20 3-D keypoints and frames_delta >= 2 -> 1 (:371-373); 3 enough 3-D keypoints -> 0 (:374-377); 4 the parallax rule cx && (c0 || c1 ||
+ * c2) (:385-392; a NaN median makes cx false). */
+int slam_keyframe_required(int S, const double *stats, const int32_t *frames_delta, const int32_t *prev_kf_nb_3d,
+                           const uint8_t *has_prev_kf, int max_nb_keypoints, double initial_parallax, int local_ba_on,
+                           uint8_t *required, uint8_t *rule);
+
 /* ---- one live stream, one call per frame (round 6) -----------------------------------------------------------------------------------
  * What run!() does per frame (src/front_end.jl:58-113: preprocess! :454-470 = copy!(previous_pyramid, current_pyramid) + update!,
  * klt_tracking! -> optical_flow_matching! map_manager.jl:451-564; at a key-frame create_keyframe! -> extract_keypoints!

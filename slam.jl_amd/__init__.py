@@ -21,4 +21,4 @@ from .kitti import KittyDataset  # noqa: F401
 from .frontend import FrontEnd, FrontEndConfig  # noqa: F401
 from .saver import ReplaySaver  # noqa: F401
 from .keypoint_set import (KeypointSet, stream_params, pose_samples, pose_inputs, pose_samples5, pose_5pt_inputs,  # noqa: F401
-                           pose_5pt_compose)
+                           pose_5pt_compose, keyframe_required)

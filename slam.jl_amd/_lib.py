@@ -95,6 +95,8 @@ SIGNATURES = {
     "slam_kpset_upload_keyframe": (cint, [vp, vp, cint, f64p, u8p, cint]),
     "slam_kpset_download_keyframe": (cint, [vp, vp, cint, f64p, u8p, cint, C.POINTER(cint)]),
     "slam_kpset_compute_pose_5pt": (cint, [vp, vp, f64p, dbl, dbl, cint, C.c_uint64, f64p, i32p, i32p, f64p, i32p]),
+    "slam_kpset_frame_stats": (cint, [vp, vp, f64p, cint, cint, cint, cint, vp, f64p]),
+    "slam_keyframe_required": (cint, [cint, f64p, i32p, i32p, u8p, cint, dbl, cint, u8p, u8p]),
     "slam_kpset_compute_pose": (cint, [vp, vp, f64p, dbl, cint, C.c_uint64, cint, cint, dbl, dbl, f64p, i32p, i32p, i32p]),
     "slam_local_ba": (cint, [vp, dbl, dbl, dbl, dbl, cint, cint, cint, f64p, u8p, f64p, i64p, i64p, u8p, cint, cint, dbl, f64p]),
     "slam_local_ba_batch": (cint, [vp, cint, f64p, i32p, i32p, i32p, f64p, u8p, f64p, i64p, i64p, u8p, cint, cint, dbl, f64p, i32p]),

@@ -115,6 +115,10 @@ struct slam_kpset {
     double *par = nullptr, *par_host = nullptr;
     hipEvent_t par_ev[8] = {};
     int par_slot = 0;
+    // slam_kpset_frame_stats (allocations of their own, made by its first call): the S x 8 results when the caller passes no buffer, and
+    // S x cap parallax terms for the streams whose terms do not fit the kernel's LDS array (only for cap > that array)
+    double *kf_stats = nullptr;
+    unsigned long long *kf_terms = nullptr;
 };
 // stage `n` doubles (<= S x 32) of per-stream parameters into the next ring slot; returns the device pointer
 int kpset_stage_params(slam_ctx *ctx, slam_kpset *ks, const double *host, size_t n, const double **dev_out);

@@ -821,6 +821,7 @@ __global__ __launch_bounds__(256) void k_kfive_gather(KFiveArgs A)
             A.pd1[2 * o] = ax; A.pd1[2 * o + 1] = ay; A.pd2[2 * o] = bx; A.pd2[2 * o + 1] = by;      // position[[1, 2]], :268-269
             A.slot[o] = j;
             // rotation-compensated parallax, :277-279: project(camera, R_compensation * position) - previous undistorted pixel
+            // (k_kpset_frame_stats, kpset.hip, forms the same term for compute_parallax's mean and median: the two sites are kept equal by hand)
             const double rx = (par[0] * bx + par[3] * by) + par[6] * 1.0, ry = (par[1] * bx + par[4] * by) + par[7] * 1.0,
                          rz = (par[2] * bx + par[5] * by) + par[8] * 1.0;
             const double qy = fy * ry / rz + cy, qx = fx * rx / rz + cx;

@@ -12,6 +12,7 @@
 #include <algorithm>
 #include "geom_device.hpp"
 #include "work_order.hpp"
+#include "kf_host.hpp"
 #include <cmath>
 
 // live slots of all streams back to back + their number.  One small workgroup per stream (it sums the counts before its own: S
@@ -233,6 +234,180 @@ __global__ __launch_bounds__(64) void k_kpset_tri_temporal(KpsetView K, KTempArg
     for (int i = blockIdx.x * 64 + threadIdx.x; i < n; i += gridDim.x * 64) k_kpset_tri_temporal_slot(K, T, work, i);
 }
 
+// What check_new_kf_required / check_ready_for_init! (src/front_end.jl:343-393) read of a frame, reduced from the lists: the counts
+// (nb_3d_kpts, nb_stereo_kpts, keypoints the previous key-frame observes), nb_occupied_cells (frame.jl:321-337) and compute_parallax
+// (front_end.jl:412-452) as mean AND median.  One 256-thread workgroup per stream (stream = blockIdx.x); the lists are only read.
+//   cells     a bitmap in LDS over the gr x gc grid (dynamic LDS, one bit per cell), cell = rint(p) / cell_size with the truncating
+//             division of SLAM.jl:42-45 (so rint(p) in (-cell_size, 0) is cell 0, as there); a keypoint off the grid -- NaN and
+//             +-inf included -- sets no bit (the reference's grid[kpi] would throw)
+//   terms     the parallax of every keypoint with haskf (and !is3d under only_2d), compacted in list order (ordered_slot) into LDS
+//             while there are at most KF_TERMS_LDS of them, else into the stream's row of A.terms; compensated, the term is the one
+//             k_kfive_gather (fivepoint.hip) sums -- same expressions, same order -- so the mean here is the parallax that call returns
+//   mean      per lane, butterfly, four waves: k_kfive_gather's order
+//   median    Julia's: NaN if any term is NaN, else the middle order statistic(s) by a radix select over the terms' bit patterns
+//             (non-negative doubles order as unsigned integers): 8 passes of a 256-bin histogram, most significant byte first
+#define KF_TERMS_LDS 4096
+static_assert(KF_STATS == SLAM_KF_STATS, "kf_host.hpp and slamhip.h disagree on the record length");
+#define KF_BITMAP_LDS_BYTES 16384     /* with the 32 KiB of terms and the histogram: inside the 64 KiB a workgroup gets without asking */
+struct KfStatsArgs {
+    const double *yx, *kyx; const uint8_t *is3d, *stereo, *haskf; const int *count; int cap;
+    const double *par;                 // S x 32: [0..8] R_compensation (column-major 3 x 3), [16..19] fx fy cx cy, [20..23] k1 k2 p1 p2
+    int flags, cell, gr, gc, words;    // flags: bit 0 compensate_rotation, bit 1 only_2d; words: 32-bit words of the cell bitmap
+    unsigned long long *terms;         // S x cap, or nullptr when cap <= KF_TERMS_LDS
+    double *out;                       // S x SLAM_KF_STATS
+};
+// sum of four ints over the 256 threads (s_c: 16 ints); every thread gets the totals
+__device__ __forceinline__ void kf_block_sum4(int *v, int *s_c)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    for (int o = 32; o > 0; o >>= 1)
+        for (int k = 0; k < 4; k++) v[k] += __shfl_xor(v[k], o, 64);
+    __syncthreads();                                             // the previous use of s_c is over
+    if (lane == 0) for (int k = 0; k < 4; k++) s_c[4 * wv + k] = v[k];
+    __syncthreads();
+    for (int k = 0; k < 4; k++) v[k] = (s_c[k] + s_c[4 + k]) + (s_c[8 + k] + s_c[12 + k]);
+}
+// the element of rank `rank` (0-based, ascending) among T[0 .. m), 0 <= rank < m; k_eq: its rank among the elements equal to it,
+// mult: how many of those there are.  s_hist: 256 words, s_w: 4, s_sel: 3.
+__device__ __forceinline__ unsigned long long kf_radix_select(const unsigned long long *T, int m, int rank, unsigned *s_hist, int *s_w, int *s_sel,
+                                                              int &k_eq, int &mult)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    unsigned long long prefix = 0;
+    int k = rank;
+    for (int shift = 56; shift >= 0; shift -= 8) {
+        const unsigned long long himask = shift == 56 ? 0ull : ~0ull << (shift + 8);      // the bytes already decided
+        s_hist[tid] = 0;
+        __syncthreads();
+        for (int i = tid; i < m; i += 256) {
+            const unsigned long long v = T[i];
+            if ((v & himask) == prefix) atomicAdd(&s_hist[(unsigned)(v >> shift) & 255u], 1u);
+        }
+        __syncthreads();
+        const int h = (int)s_hist[tid];
+        int incl = h;                                            // inclusive scan of the 256 bins: shuffles inside a wave, one LDS hop across
+        for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(incl, o, 64); if (lane >= o) incl += t; }
+        if (lane == 63) s_w[wv] = incl;
+        __syncthreads();
+        for (int w = 0; w < wv; w++) incl += s_w[w];
+        if (incl - h <= k && k < incl) { s_sel[0] = tid; s_sel[1] = k - (incl - h); s_sel[2] = h; }    // one bin holds rank k (k < the bins' total)
+        __syncthreads();
+        prefix |= (unsigned long long)(unsigned)s_sel[0] << shift; k = s_sel[1]; mult = s_sel[2];
+    }
+    k_eq = k;
+    return prefix;
+}
+// Julia's median of T[0 .. m), m >= 1, no NaN among the terms: the lower middle by kf_radix_select; for even m the upper middle is the
+// same value when its multiplicity reaches past the lower's rank, else the smallest term above it.  Every thread returns the result.
+__device__ __forceinline__ double kf_median(const unsigned long long *T, int m, unsigned *s_hist, int *s_w, int *s_sel, unsigned long long *s_min)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    int k_eq = 0, mult = 0;
+    const unsigned long long lo = kf_radix_select(T, m, (m - 1) >> 1, s_hist, s_w, s_sel, k_eq, mult);
+    if (m & 1) return __longlong_as_double((long long)lo);
+    unsigned long long hi = lo;
+    if (k_eq + 1 >= mult) {                                      // (uniform: k_eq and mult come from LDS)
+        unsigned long long mn = ~0ull;
+        for (int i = tid; i < m; i += 256) { const unsigned long long v = T[i]; if (v > lo && v < mn) mn = v; }
+        for (int o = 32; o > 0; o >>= 1) {
+            const unsigned ol = __shfl_xor((unsigned)mn, o, 64), oh = __shfl_xor((unsigned)(mn >> 32), o, 64);
+            const unsigned long long other = ((unsigned long long)oh << 32) | ol;
+            mn = other < mn ? other : mn;
+        }
+        if (lane == 0) s_min[wv] = mn;
+        __syncthreads();
+        const unsigned long long a = s_min[0] < s_min[1] ? s_min[0] : s_min[1], c = s_min[2] < s_min[3] ? s_min[2] : s_min[3];
+        hi = a < c ? a : c;
+    }
+    return __longlong_as_double((long long)lo) / 2.0 + __longlong_as_double((long long)hi) / 2.0;      // middle(lo, hi)
+}
+__global__ __launch_bounds__(256) void k_kpset_frame_stats(KfStatsArgs A)
+{
+    extern __shared__ unsigned s_bits[];
+    __shared__ unsigned long long s_term[KF_TERMS_LDS], s_min[4];
+    __shared__ unsigned s_hist[256];
+    __shared__ int s_w[4], s_base, s_sel[3], s_c[16];
+    __shared__ double s_par[4];
+    const int z = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int n = min(max(A.count[z], 0), A.cap);
+    const size_t b = (size_t)z * A.cap;
+    const double *par = A.par + 32 * (size_t)z;
+    const double cam[4] = {par[16], par[17], par[18], par[19]}, dist[4] = {par[20], par[21], par[22], par[23]};
+    const double fx = cam[0], fy = cam[1], cx = cam[2], cy = cam[3];
+    const bool comp = (A.flags & 1) != 0, only2d = (A.flags & 2) != 0;
+    for (int w = tid; w < A.words; w += 256) s_bits[w] = 0;
+    if (tid == 0) s_base = 0;
+    // pass 1, the flags alone: the counts, and with them where the terms go
+    int c[4] = {0, 0, 0, 0};                                     // is3d, stereo, haskf, terms
+    for (int j = tid; j < n; j += 256) {
+        const bool f3 = A.is3d[b + j] != 0, fk = A.haskf[b + j] != 0;
+        c[0] += f3; c[1] += A.stereo[b + j] != 0; c[2] += fk; c[3] += fk && !(only2d && f3);
+    }
+    kf_block_sum4(c, s_c);                                       // (its barriers also publish the cleared bitmap and s_base)
+    const int m = c[3];
+    const bool in_lds = m <= KF_TERMS_LDS;
+    unsigned long long *gterm = A.terms ? A.terms + b : nullptr; // (dereferenced only when !in_lds: then cap > KF_TERMS_LDS and A.terms is allocated)
+    // pass 2: cells and parallax terms
+    const double ylim = (double)A.gr * (double)A.cell, xlim = (double)A.gc * (double)A.cell, low = -(double)A.cell;
+    double psum = 0.0;
+    int isnan_any = 0;
+    for (int c0 = 0; c0 < n; c0 += 256) {
+        const int j = c0 + tid;
+        bool take = false;
+        double y = 0.0, x = 0.0;
+        if (j < n) {
+            y = A.yx[2 * (b + j)]; x = A.yx[2 * (b + j) + 1];
+            const double ry = rint(y), rx = rint(x);
+            if (ry > low && ry < ylim && rx > low && rx < xlim) {            // (false for NaN)
+                const int cell = ((int)ry / A.cell) * A.gc + (int)rx / A.cell;
+                atomicOr(&s_bits[cell >> 5], 1u << (cell & 31));
+            }
+            take = A.haskf[b + j] != 0 && !(only2d && A.is3d[b + j] != 0);
+        }
+        const int pos = ordered_slot(take, s_w, &s_base);
+        if (take) {
+            const size_t q = b + j;
+            double uy, ux, vy, vx, t;
+            undistort_px(cam, dist, y, x, uy, ux);
+            undistort_px(cam, dist, A.kyx[2 * q], A.kyx[2 * q + 1], vy, vx);
+            if (comp) {
+                // project(camera, R_compensation * position) - previous undistorted pixel: the term of k_kfive_gather (fivepoint.hip)
+                const double bx = (ux - cx) / fx, by = (uy - cy) / fy;
+                const double rx = (par[0] * bx + par[3] * by) + par[6] * 1.0, ry = (par[1] * bx + par[4] * by) + par[7] * 1.0,
+                             rz = (par[2] * bx + par[5] * by) + par[8] * 1.0;
+                const double qy = fy * ry / rz + cy, qx = fx * rx / rz + cx;
+                const double dy = qy - vy, dx = qx - vx;
+                t = sqrt(dy * dy + dx * dx);
+            } else {
+                const double dy = uy - vy, dx = ux - vx;
+                t = sqrt(dy * dy + dx * dx);
+            }
+            psum += t;
+            isnan_any |= t != t;
+            const unsigned long long bits = (unsigned long long)__double_as_longlong(t);
+            if (in_lds) s_term[pos] = bits; else gterm[pos] = bits;          // pos < m: <= KF_TERMS_LDS in LDS, <= n <= cap in the stream's row
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) psum += __shfl_xor(psum, o, 64);
+    if (lane == 0) s_par[wv] = psum;
+    __threadfence_block();
+    const int has_nan = __syncthreads_or(isnan_any);             // terms, bitmap and s_par complete
+    int occ[4] = {0, 0, 0, 0};
+    for (int w = tid; w < A.words; w += 256) occ[0] += __popc(s_bits[w]);
+    kf_block_sum4(occ, s_c);
+    double median = 0.0;                                         // :444 without a term
+    if (m > 0) {
+        if (has_nan) median = __longlong_as_double(0x7FF8000000000000ll);
+        else median = in_lds ? kf_median(s_term, m, s_hist, s_w, s_sel, s_min) : kf_median(gterm, m, s_hist, s_w, s_sel, s_min);
+    }
+    if (tid == 0) {
+        double *o = A.out + SLAM_KF_STATS * (size_t)z;
+        o[KF_N] = (double)n; o[KF_N3D] = (double)c[0]; o[KF_NSTEREO] = (double)c[1]; o[KF_NHASKF] = (double)c[2]; o[KF_CELLS] = (double)occ[0]; o[KF_NPAR] = (double)m;
+        o[KF_MEAN] = m > 0 ? ((s_par[0] + s_par[1]) + (s_par[2] + s_par[3])) / (double)m : 0.0;
+        o[KF_MEDIAN] = median;
+    }
+}
+
 extern "C" {
 
 int slam_kpset_destroy(slam_kpset *ks);
@@ -273,6 +448,8 @@ int slam_kpset_destroy(slam_kpset *ks)
     (void)hipDeviceSynchronize();
     if (ks->base) (void)hipFree(ks->base);
     if (ks->par_host) (void)hipHostFree(ks->par_host);
+    if (ks->kf_stats) (void)hipFree(ks->kf_stats);
+    if (ks->kf_terms) (void)hipFree(ks->kf_terms);
     for (int i = 0; i < 8; i++) if (ks->par_ev[i]) (void)hipEventDestroy(ks->par_ev[i]);
     delete ks;
     return SLAM_OK;
@@ -502,6 +679,47 @@ int slam_kpset_triangulate_temporal(slam_ctx *ctx, slam_kpset *ks, const double 
     if (rc) return rc;
     // the pinned table is read by the copy above: it must be gone from the host block before the next call reuses it
     HIP_TRY(ctx, slam_stream_wait(ctx->stream));
+    return SLAM_OK;
+}
+
+// the per-frame statistics of every stream's list (k_kpset_frame_stats); stats == NULL: enqueue only
+int slam_kpset_frame_stats(slam_ctx *ctx, slam_kpset *ks, const double *params, int flags, int cell_size, int height, int width,
+                           double *stats_dev, double *stats)
+{
+    ARG_TRY(ctx, ctx != nullptr && ks != nullptr && params != nullptr && cell_size > 0 && height > 0 && width > 0 && (flags & ~3) == 0);
+    const int S = ks->S;
+    KfStatsArgs A;
+    A.gr = (int)(((long long)height + cell_size - 1) / cell_size); A.gc = (int)(((long long)width + cell_size - 1) / cell_size);
+    const long long cells = (long long)A.gr * A.gc;
+    if (cells > 8ll * KF_BITMAP_LDS_BYTES)
+        return slam_fail(ctx, SLAM_ERR_ARG, "slam_kpset_frame_stats: %d x %d cells, the kernel's bitmap holds %d", A.gr, A.gc, 8 * KF_BITMAP_LDS_BYTES);
+    A.words = (int)((cells + 31) / 32);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (!ks->kf_stats) HIP_TRY(ctx, hipMalloc((void **)&ks->kf_stats, (size_t)S * SLAM_KF_STATS * 8));
+    if (ks->cap > KF_TERMS_LDS && !ks->kf_terms) HIP_TRY(ctx, hipMalloc((void **)&ks->kf_terms, (size_t)S * ks->cap * 8));
+    int rc = kpset_stage_params(ctx, ks, params, (size_t)S * 32, &A.par);
+    if (rc) return rc;
+    A.yx = ks->yx; A.kyx = ks->kyx; A.is3d = ks->is3d; A.stereo = ks->stereo; A.haskf = ks->haskf; A.count = ks->count; A.cap = ks->cap;
+    A.flags = flags; A.cell = cell_size; A.terms = ks->kf_terms; A.out = stats_dev ? stats_dev : ks->kf_stats;
+    { ProfScope span(ctx, "kpset_frame_stats");
+      hipLaunchKernelGGL(k_kpset_frame_stats, dim3(S), dim3(256), (size_t)A.words * 4, ctx->stream, A); }
+    HIP_TRY(ctx, hipGetLastError());
+    if (!stats) return SLAM_OK;
+    void *h;
+    rc = slam_pinned(ctx, std::max<size_t>(256, (size_t)S * SLAM_KF_STATS * 8), &h);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(h, A.out, (size_t)S * SLAM_KF_STATS * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, slam_stream_wait(ctx->stream));
+    memcpy(stats, h, (size_t)S * SLAM_KF_STATS * 8);
+    return SLAM_OK;
+}
+
+// check_new_kf_required for S streams on those statistics (kf_host.hpp): host arithmetic only, no context
+int slam_keyframe_required(int S, const double *stats, const int32_t *frames_delta, const int32_t *prev_kf_nb_3d, const uint8_t *has_prev_kf,
+                           int max_nb_keypoints, double initial_parallax, int local_ba_on, uint8_t *required, uint8_t *rule)
+{
+    if (!kf_required(S, stats, frames_delta, prev_kf_nb_3d, has_prev_kf, max_nb_keypoints, initial_parallax, local_ba_on, required, rule))
+        return slam_fail(nullptr, SLAM_ERR_ARG, "slam_keyframe_required: S < 1 or a null array");
     return SLAM_OK;
 }
 

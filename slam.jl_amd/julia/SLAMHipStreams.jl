@@ -26,7 +26,7 @@ module SLAMHipStreams
 import ..SLAMHip: LIB, ctx, check
 
 export PyramidBatch, FrameRing, KeypointSet, upload!, update!, flow_match!, stereo_match!, remove!, detect!, detect_describe!, describe_batch, keyframe!,
-       triangulate!, triangulate_temporal!, compute_pose_5pt!, compute_pose!, counts, download, stream_params
+       triangulate!, triangulate_temporal!, compute_pose_5pt!, compute_pose!, frame_stats, keyframe_required, counts, download, stream_params
 
 const HIP = "libamdhip64"
 hipcheck(e::Cint, what) = e == 0 || error("$what: HIP error $e")
@@ -236,6 +236,36 @@ function compute_pose_5pt!(k::KeypointSet, params::Matrix{Float64}; min_parallax
         (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Cdouble, Cdouble, Cint, UInt64, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{Int32}),
         ctx(), k.h, params, min_parallax, max_repr_error, iters, seed, P, status, ninl, par, cnt))
     (Rt = [reshape(P[:, s], 3, 4) for s in 1:k.S], status = status, n_inliers = ninl, parallax = par, counts = cnt)
+end
+
+# What check_new_kf_required (flags = 1) / check_ready_for_init! (flags = 2) read of the frame (slam_kpset_frame_stats): an 8 x S matrix, per
+# stream [list length, nb_3d_kpts, nb_stereo_kpts, keypoints the key-frame observes, nb_occupied_cells, n_parallax, mean, median parallax].
+# params as for compute_pose_5pt!.  fetch = false: enqueue only; the results stay in HBM (stats_dev, or a buffer of the set).
+function frame_stats(k::KeypointSet, params::Matrix{Float64}, flags::Integer, cell_size::Integer, height::Integer, width::Integer;
+                     fetch = true, stats_dev::Ptr{Cvoid} = C_NULL)
+    if !fetch
+        GC.@preserve params check(ccall((:slam_kpset_frame_stats, LIB[]), Cint,
+            (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Cint, Cint, Cint, Cint, Ptr{Cvoid}, Ptr{Float64}),
+            ctx(), k.h, params, flags, cell_size, height, width, stats_dev, C_NULL))
+        return nothing
+    end
+    stats = zeros(Float64, 8, k.S)
+    GC.@preserve params check(ccall((:slam_kpset_frame_stats, LIB[]), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Cint, Cint, Cint, Cint, Ptr{Cvoid}, Ptr{Float64}),
+        ctx(), k.h, params, flags, cell_size, height, width, stats_dev, stats))
+    stats
+end
+
+# check_new_kf_required (front_end.jl:361-393) per stream on those statistics (slam_keyframe_required: host arithmetic, no device).
+# prev_kf_nb_3d: the key-frames' own nb_3d_kpts (the mapper and the estimator change it: the caller owns it).  rule: which exit decided.
+function keyframe_required(stats::Matrix{Float64}, frames_delta::Vector{Int32}, prev_kf_nb_3d::Vector{Int32}, has_prev_kf::Vector{UInt8};
+                           max_nb_keypoints::Integer, initial_parallax::Real = 20.0, local_ba_on::Bool = false)
+    S = size(stats, 2)
+    required = zeros(UInt8, S); rule = zeros(UInt8, S)
+    check(ccall((:slam_keyframe_required, LIB[]), Cint,
+        (Cint, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Ptr{UInt8}, Cint, Cdouble, Cint, Ptr{UInt8}, Ptr{UInt8}),
+        S, stats, frames_delta, prev_kf_nb_3d, has_prev_kf, max_nb_keypoints, Float64(initial_parallax), local_ba_on ? 1 : 0, required, rule))
+    (required = required .!= 0, rule = rule)
 end
 
 # compute_pose! (front_end.jl:132-219): P3P RANSAC + pnp_bundle_adjustment on the lists; the step's device -> host copy

@@ -1,7 +1,8 @@
 """Device-resident keypoint lists of S lock-stepped streams (slam_kpset, include/slamhip.h): the arrays behind
 Frame.keypoints (src/frame.jl) for the calls of the front-end / mapper hot path -- optical_flow_matching!
 (src/map_manager.jl:451-564), extract_keypoints! (:98-113), triangulate_stereo! (src/mapper.jl:142-183) -- kept in HBM
-between calls.  Only `counts()`, `upload()` and `download()` touch the host."""
+between calls.  Only `counts()`, `frame_stats()` (the statistics the key-frame decision reads), the pose calls, `upload()` and `download()`
+touch the host."""
 import ctypes as C
 
 import numpy as np
@@ -200,6 +201,22 @@ class KeypointSet:
                                                   L.ptr(par), L.ptr(counts, L.i32p)))
         return P.reshape(self.S, 4, 3).transpose(0, 2, 1).copy(), status, ninl, par, counts
 
+    def frame_stats(self, sp, flags, cell_size, shape, fetch=True, stats_dev_ptr=None, ctx=None):
+        """What check_new_kf_required (flags = 1) / check_ready_for_init! (flags = 2) read of the frame, for every stream
+        (slam_kpset_frame_stats): (S, 8) array of [list length, nb_3d_kpts, nb_stereo_kpts, keypoints the previous key-frame observes,
+        nb_occupied_cells, n_parallax, mean parallax, median parallax] (front_end.jl:412-452, frame.jl:321-337).  flags: bit 0
+        compensate_rotation, bit 1 only_2d.  sp: stream_params(...) as for compute_pose_5pt (R_compensation in the rotation part of the
+        Tcw slot, camera / distortion filled); shape = (height, width) of the image.  The call is the step's one device -> host copy;
+        fetch=False only enqueues (results in stats_dev_ptr, a device pointer to S x 8 doubles, or in a buffer of the set) and returns None."""
+        c = ctx or self.ctx
+        sp = np.ascontiguousarray(sp, dtype=np.float64).reshape(self.S, 32).copy()
+        T = sp[:, :16].reshape(self.S, 4, 4)                                       # [col][row], repacked as compute_pose_5pt does
+        sp[:, :9] = T[:, :3, :3].reshape(self.S, 9)
+        out = np.zeros((self.S, 8)) if fetch else None
+        c.check(c.lib.slam_kpset_frame_stats(c.h, self.h, L.ptr(sp), int(flags), int(cell_size), int(shape[0]), int(shape[1]),
+                                             C.c_void_p(stats_dev_ptr) if stats_dev_ptr else None, L.ptr(out) if fetch else None))
+        return out
+
     def compute_pose(self, sp, threshold=3.0, iters=256, seed=0, pnp_iters_fast=5, pnp_iterations=10, depth_eps=1e-6, repr_eps=None, ctx=None):
         """compute_pose! (front_end.jl:132-219) for every stream on the device-resident lists (slam_kpset_compute_pose): returns
         (poses (S, 4, 4) world -> camera, status (S,), P3P inlier counts (S,), list lengths after the outlier removals (S,)).
@@ -214,6 +231,24 @@ class KeypointSet:
                                               float(threshold if repr_eps is None else repr_eps),
                                               L.ptr(poses), L.ptr(status, L.i32p), L.ptr(ninl, L.i32p), L.ptr(counts, L.i32p)))
         return poses.reshape(self.S, 4, 4).transpose(0, 2, 1).copy(), status, ninl, counts
+
+
+def keyframe_required(stats, frames_delta, prev_kf_nb_3d, has_prev_kf, params, local_ba_on=False):
+    """check_new_kf_required (front_end.jl:361-393) per stream (slam_keyframe_required; host arithmetic, no device): stats = the (S, 8)
+    array of KeypointSet.frame_stats(flags=1), frames_delta = frame id - key-frame id, prev_kf_nb_3d = the key-frame's own nb_3d_kpts,
+    has_prev_kf = the key-frame is in the map; params: Params (max_nb_keypoints, initial_parallax).  Returns (required (S,) bool,
+    rule (S,) uint8: 0 no key-frame, 1 sparse cells, 2 few 3-D keypoints, 3 enough 3-D keypoints, 4 the parallax rule)."""
+    st = np.ascontiguousarray(stats, dtype=np.float64).reshape(-1, 8)
+    S = len(st)
+    b = lambda a, t: np.ascontiguousarray(np.broadcast_to(np.asarray(a).astype(t), (S,)))
+    fd, pk, hp = b(frames_delta, np.int32), b(prev_kf_nb_3d, np.int32), b(has_prev_kf, np.uint8)
+    req = np.zeros(S, dtype=np.uint8); rule = np.zeros(S, dtype=np.uint8)
+    lib = L.load()
+    rc = lib.slam_keyframe_required(S, L.ptr(st), L.ptr(fd, L.i32p), L.ptr(pk, L.i32p), L.ptr(hp, L.u8p), int(params.max_nb_keypoints),
+                                    float(params.initial_parallax), 1 if local_ba_on else 0, L.ptr(req, L.u8p), L.ptr(rule, L.u8p))
+    if rc != 0:
+        raise L.SlamHipError(f"libslamhip error {rc}: {lib.slam_last_error(None).decode()}")
+    return req.astype(bool), rule
 
 
 def _splitmix64(x):

@@ -18,6 +18,7 @@ class Params:
     do_local_bundle_adjustment: bool = True
     max_projection_distance: float = 2.0     # params.jl:75: gate of the local-map match, px
     max_descriptor_distance: float = 0.35    # params.jl:76: share of the 256 descriptor bits
+    initial_parallax: float = 20.0           # params.jl:66: px; check_ready_for_init! and the parallax rule of check_new_kf_required
 
 
 @dataclass
