@@ -89,40 +89,6 @@ struct slam_pyr {
     double *plane(int p, int l) const { return planes + (int64_t)p * off[levels] + off[l]; }
 };
 
-// Device-resident keypoint lists of S lock-stepped streams: stream s owns the slots
-// [s * cap, s * cap + count[s]) of every per-keypoint array; all of it lives in one allocation.
-struct slam_kpset {
-    int device = 0, S = 0, cap = 0;
-    char *base = nullptr;
-    double *yx = nullptr;        // [S cap][2] pixel (y, x) in the current left image
-    double *oyx = nullptr;       // [S cap][2] positions returned by the last temporal match (scratch)
-    double *syx = nullptr;       // [S cap][2] stereo pixel (right image), valid where stereo != 0
-    double *xyz = nullptr;       // [S cap][3] map point, valid where is3d != 0
-    double *kyx = nullptr;       // [S cap][2] pixel (y, x) in the previous key-frame, valid where haskf != 0 (slam_kpset_keyframe)
-    uint8_t *haskf = nullptr;    // [S cap] the keypoint is observed by the previous key-frame
-    double *fyx = nullptr;       // [S cap][2] pixel (y, x) in the FIRST key-frame that observed the keypoint (the one that detected it)
-    int *fkf = nullptr;          // [S cap] that key-frame's id (per-stream counter), valid where haskf != 0
-    int *kfcount = nullptr;      // [S] number of key-frames created so far = id of the next one
-    int64_t *id = nullptr;       // [S cap] keypoint id (per stream, ascending in creation order)
-    uint8_t *is3d = nullptr, *stereo = nullptr, *st = nullptr;   // flags; st: status of the last match (0 lost, 1 tracked, 2 skipped)
-    int *count = nullptr;        // [S]
-    int *work = nullptr;         // [S cap] live slots, streams back to back (each stream's segment in the order of work_order.hpp)
-    int sort_pad = 0;            // power of two >= cap the work list's sort pads a segment to; 0: slot order (decided at creation)
-    int *ntot = nullptr;         // [4]: number of live slots, ...
-    int64_t *next_id = nullptr;  // [S]
-    // per-stream parameters of a call (prior shift / pose): ring of 8 slots of S x 32 doubles, staged through pinned host
-    // memory with an event per slot, so that the enqueue-only calls never wait for an earlier call's copy
-    double *par = nullptr, *par_host = nullptr;
-    hipEvent_t par_ev[8] = {};
-    int par_slot = 0;
-    // slam_kpset_frame_stats (allocations of their own, made by its first call): the S x 8 results when the caller passes no buffer, and
-    // S x cap parallax terms for the streams whose terms do not fit the kernel's LDS array (only for cap > that array)
-    double *kf_stats = nullptr;
-    unsigned long long *kf_terms = nullptr;
-};
-// stage `n` doubles (<= S x 32) of per-stream parameters into the next ring slot; returns the device pointer
-int kpset_stage_params(slam_ctx *ctx, slam_kpset *ks, const double *host, size_t n, const double **dev_out);
-
 extern thread_local std::string g_slam_err;
 
 // The synchronous seams end with a wait for the context's stream.  The interrupt-driven hipStreamSynchronize costs tens of
@@ -192,9 +158,6 @@ int brief_prepare(slam_ctx *ctx, const char *who, const double *img, int H, int 
                   double sigma, int window, BriefJob *J);
 int brief_launch(slam_ctx *ctx, const BriefJob &J, int per_stream, int S);      // list form: per_stream = n, S = 1
 
-// kpset plumbing shared by kpset.hip / lk.hip / detect.hip
-int kpset_build_worklist(slam_ctx *ctx, slam_kpset *ks, int H, int W);   // H <= 0: slot order (no image, or an order would not pay)
-int kpset_compact(slam_ctx *ctx, slam_kpset *ks, int mode, const uint8_t *flags_dev);
 // per-module entry points used across files
 int slam_detect_device(slam_ctx *ctx, const double *img_dev, int H, int W, int pitch, const double *cur_yx, int n_cur,
                        int max_points, int radius, int grid_rows, int grid_cols, int cell_size,

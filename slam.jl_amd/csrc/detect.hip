@@ -9,7 +9,7 @@
 // algorithmic minimum (8*H*W + 16*(K + n_out) bytes).  Keypoint order and
 // indices are bit-exact with the CPU oracle: every sum runs in the reference's
 // order and the build uses -ffp-contract=off.
-#include "common.hpp"
+#include "kpset.hpp"
 #include "geom_device.hpp"
 #include <cmath>
 #include <cstddef>
@@ -666,14 +666,13 @@ extern "C" int slam_detect_batch(slam_ctx *ctx, const slam_pyr *pyr0, int S, con
 // keypoints (cells row-major, column-major inside a cell: extractor.jl:81-91) are appended behind it as (row, col) Float64
 // pixels with is_3d = 0 and fresh ids -- extract_keypoints! + add_keypoints_to_frame! (map_manager.jl:98-113) on arrays.
 // One 1024-thread workgroup per stream, cell_scan over chunks of 1024 cells (as detect_compact).
-__global__ __launch_bounds__(1024) void detect_append(const int64_t *cell_out, const int *cell_cnt, int n_cells, int kmax, int max_points,
-                                                       double *yx, double *syx, double *xyz, int64_t *id, uint8_t *is3d, uint8_t *stereo, uint8_t *haskf,
-                                                       int *count, int64_t *next_id, int cap)
+__global__ __launch_bounds__(1024) void detect_append(const int64_t *cell_out, const int *cell_cnt, int n_cells, int kmax, int max_points, KpsetView K,
+                                                       int64_t *next_id)
 {
-    const int z = blockIdx.x;
+    const int z = blockIdx.x, cap = K.cap;
     cell_out += (size_t)z * n_cells * kmax * 2; cell_cnt += (size_t)z * n_cells;
     const size_t b = (size_t)z * cap;
-    const int n0 = count[z];
+    const int n0 = K.count[z];
     const int64_t id0 = next_id[z];
     __shared__ int s_w[16];
     __shared__ int s_base;
@@ -689,44 +688,13 @@ __global__ __launch_bounds__(1024) void detect_append(const int64_t *cell_out, c
             const int j = n0 + start + i;
             if (j < cap) {
                 const size_t q = b + j;
-                yx[2 * q] = (double)cell_out[((size_t)c * kz + i) * 2]; yx[2 * q + 1] = (double)cell_out[((size_t)c * kz + i) * 2 + 1];
-                syx[2 * q] = 0.0; syx[2 * q + 1] = 0.0; xyz[3 * q] = 0.0; xyz[3 * q + 1] = 0.0; xyz[3 * q + 2] = 0.0;
-                id[q] = id0 + start + i; is3d[q] = 0; stereo[q] = 0; haskf[q] = 0;
+                K.yx[2 * q] = (double)cell_out[((size_t)c * kz + i) * 2]; K.yx[2 * q + 1] = (double)cell_out[((size_t)c * kz + i) * 2 + 1];
+                K.syx[2 * q] = 0.0; K.syx[2 * q + 1] = 0.0; K.xyz[3 * q] = 0.0; K.xyz[3 * q + 1] = 0.0; K.xyz[3 * q + 2] = 0.0;
+                K.id[q] = id0 + start + i; K.is3d[q] = 0; K.stereo[q] = 0; K.haskf[q] = 0;
             }
         }
     }
-    if (tid == 0) { const int n1 = n0 + s_base; count[z] = n1 < cap ? n1 : cap; next_id[z] = id0 + s_base; }
-}
-
-extern "C" int slam_kpset_detect(slam_ctx *ctx, slam_kpset *ks, const slam_pyr *pyr0, int max_points, int radius, int grid_rows, int grid_cols,
-                                 int cell_size, double sigma_mask, double min_response)
-{
-    ARG_TRY(ctx, ctx != nullptr && ks != nullptr && pyr0 != nullptr);
-    const int S = ks->S;
-    ARG_TRY(ctx, pyr0->batch_index == 0 && pyr0->batch_size >= S);
-    ARG_TRY(ctx, grid_rows > 0 && grid_cols > 0 && cell_size >= 8 && radius > 0 && radius <= DET_MAXR && max_points > 0);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const int n_cells = grid_rows * grid_cols;
-    const int kmax = (max_points + n_cells - 1) / n_cells;         // n_cur = 0
-    ARG_TRY(ctx, ks->cap >= max_points + n_cells);                  // a stream below max_points may receive up to n_cells * k > max_points - n_cur keypoints
-    DetectArgs A;
-    size_t lds_bytes;
-    int rc = det_plan(ctx, A, pyr0->plane(0, 0), pyr0->H[0], pyr0->W[0], pyr0->P[0], pyr0->zstride, max_points, radius, grid_rows, grid_cols, cell_size, kmax,
-                      sigma_mask, min_response, &lds_bytes);
-    if (rc) return rc;
-    A.cur = ks->yx; A.cur_cnt = ks->count; A.cur_stride = ks->cap;
-    Layout D;
-    const size_t o_cnt = D.take((size_t)S * n_cells * 4), o_cout = D.take((size_t)S * n_cells * kmax * 16);
-    char *d;
-    rc = slam_scratch(ctx, D.size(), (void **)&d);
-    if (rc) return rc;
-    A.cell_cnt = (int *)(d + o_cnt); A.cell_out = (int64_t *)(d + o_cout);
-    { ProfScope span(ctx, "detect");
-      hipLaunchKernelGGL(detect_cells, dim3(n_cells, S), dim3(DET_THREADS), lds_bytes, ctx->stream, A);
-      hipLaunchKernelGGL(detect_append, dim3(S), dim3(1024), 0, ctx->stream, (const int64_t *)A.cell_out, (const int *)A.cell_cnt, n_cells, kmax, max_points,
-                         ks->yx, ks->syx, ks->xyz, ks->id, ks->is3d, ks->stereo, ks->haskf, ks->count, ks->next_id, ks->cap); }
-    HIP_TRY(ctx, hipGetLastError());
-    return SLAM_OK;
+    if (tid == 0) { const int n1 = n0 + s_base; K.count[z] = n1 < cap ? n1 : cap; next_id[z] = id0 + s_base; }
 }
 
 // describe()'s border drop on the cell lists (map_manager.jl:105-106: detect, then describe returns the keypoints it kept): every cell's
@@ -753,6 +721,55 @@ __global__ __launch_bounds__(256) void detect_box_filter(int64_t *cell_out, int 
     *pc = m;
 }
 
+// What slam_kpset_detect and slam_kpset_detect_describe share.  kpset_detect_check: the checks both make after their null checks, in their order; kpset_detect_plan:
+// det_plan on the set's current lists and the scratch of the cell lists, `extra` bytes behind them at D.extra; kpset_detect_append: the merge of the cell lists into the set.
+struct KpDetect { int max_points, radius, grid_rows, grid_cols, cell_size, n_cells, kmax; DetectArgs A; size_t lds_bytes; char *extra; };
+static int kpset_detect_check(slam_ctx *ctx, const slam_kpset *ks, const slam_pyr *pyr0, int max_points, int radius, int grid_rows, int grid_cols, int cell_size, KpDetect &D)
+{
+    ARG_TRY(ctx, pyr0->batch_index == 0 && pyr0->batch_size >= ks->S);
+    ARG_TRY(ctx, grid_rows > 0 && grid_cols > 0 && cell_size >= 8 && radius > 0 && radius <= DET_MAXR && max_points > 0);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int n_cells = grid_rows * grid_cols;
+    ARG_TRY(ctx, ks->v.cap >= max_points + n_cells);                // a stream below max_points may receive up to n_cells * k > max_points - n_cur keypoints
+    D.max_points = max_points; D.radius = radius; D.grid_rows = grid_rows; D.grid_cols = grid_cols; D.cell_size = cell_size;
+    D.n_cells = n_cells; D.kmax = (max_points + n_cells - 1) / n_cells;      // n_cur = 0
+    return SLAM_OK;
+}
+static int kpset_detect_plan(slam_ctx *ctx, const slam_kpset *ks, const slam_pyr *pyr0, double sigma_mask, double min_response, size_t extra, KpDetect &D)
+{
+    int rc = det_plan(ctx, D.A, pyr0->plane(0, 0), pyr0->H[0], pyr0->W[0], pyr0->P[0], pyr0->zstride, D.max_points, D.radius, D.grid_rows, D.grid_cols, D.cell_size,
+                      D.kmax, sigma_mask, min_response, &D.lds_bytes);
+    if (rc) return rc;
+    D.A.cur = ks->v.yx; D.A.cur_cnt = ks->v.count; D.A.cur_stride = ks->v.cap;
+    Layout L;
+    const size_t o_cnt = L.take((size_t)ks->S * D.n_cells * 4), o_cout = L.take((size_t)ks->S * D.n_cells * D.kmax * 16), o_extra = L.take(extra);
+    char *d;
+    rc = slam_scratch(ctx, L.size(), (void **)&d);
+    if (rc) return rc;
+    D.A.cell_cnt = (int *)(d + o_cnt); D.A.cell_out = (int64_t *)(d + o_cout); D.extra = d + o_extra;
+    return SLAM_OK;
+}
+static void kpset_detect_append(slam_ctx *ctx, slam_kpset *ks, const KpDetect &D)
+{
+    hipLaunchKernelGGL(detect_append, dim3(ks->S), dim3(1024), 0, ctx->stream, (const int64_t *)D.A.cell_out, (const int *)D.A.cell_cnt, D.n_cells, D.kmax,
+                       D.max_points, ks->v, ks->next_id);
+}
+
+extern "C" int slam_kpset_detect(slam_ctx *ctx, slam_kpset *ks, const slam_pyr *pyr0, int max_points, int radius, int grid_rows, int grid_cols,
+                                 int cell_size, double sigma_mask, double min_response)
+{
+    ARG_TRY(ctx, ctx != nullptr && ks != nullptr && pyr0 != nullptr);
+    KpDetect D;
+    int rc = kpset_detect_check(ctx, ks, pyr0, max_points, radius, grid_rows, grid_cols, cell_size, D);
+    if (!rc) rc = kpset_detect_plan(ctx, ks, pyr0, sigma_mask, min_response, 0, D);
+    if (rc) return rc;
+    { ProfScope span(ctx, "detect");
+      hipLaunchKernelGGL(detect_cells, dim3(D.n_cells, ks->S), dim3(DET_THREADS), D.lds_bytes, ctx->stream, D.A);
+      kpset_detect_append(ctx, ks, D); }
+    HIP_TRY(ctx, hipGetLastError());
+    return SLAM_OK;
+}
+
 // extract_keypoints! with describe (map_manager.jl:98-113) on the lists: detect_cells, the border drop, detect_append, k_brief_patch over
 // the appended slots.  Enqueue-only.
 extern "C" int slam_kpset_detect_describe(slam_ctx *ctx, slam_kpset *ks, const slam_pyr *pyr0, int max_points, int radius, int grid_rows, int grid_cols,
@@ -761,39 +778,24 @@ extern "C" int slam_kpset_detect_describe(slam_ctx *ctx, slam_kpset *ks, const s
 {
     ARG_TRY(ctx, ctx != nullptr && ks != nullptr && pyr0 != nullptr && desc_dev != nullptr && info_dev != nullptr);
     const int S = ks->S;
-    ARG_TRY(ctx, pyr0->batch_index == 0 && pyr0->batch_size >= S);
-    ARG_TRY(ctx, grid_rows > 0 && grid_cols > 0 && cell_size >= 8 && radius > 0 && radius <= DET_MAXR && max_points > 0);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const int n_cells = grid_rows * grid_cols;
-    const int kmax = (max_points + n_cells - 1) / n_cells;         // n_cur = 0
-    ARG_TRY(ctx, ks->cap >= max_points + n_cells);
-    if (dcap < n_cells * kmax)
-        return slam_fail(ctx, SLAM_ERR_ARG, "slam_kpset_detect_describe: dcap = %d, a key-frame may append %d keypoints per stream", dcap, n_cells * kmax);
+    KpDetect D;
+    int rc = kpset_detect_check(ctx, ks, pyr0, max_points, radius, grid_rows, grid_cols, cell_size, D);
+    if (rc) return rc;
+    if (dcap < D.n_cells * D.kmax)
+        return slam_fail(ctx, SLAM_ERR_ARG, "slam_kpset_detect_describe: dcap = %d, a key-frame may append %d keypoints per stream", dcap, D.n_cells * D.kmax);
     BriefJob J;
-    int rc = brief_prepare(ctx, "slam_kpset_detect_describe", pyr0->plane(0, 0), pyr0->H[0], pyr0->W[0], pyr0->P[0], pyr0->zstride, pattern, n_bits,
-                           sigma, window, &J);
+    rc = brief_prepare(ctx, "slam_kpset_detect_describe", pyr0->plane(0, 0), pyr0->H[0], pyr0->W[0], pyr0->P[0], pyr0->zstride, pattern, n_bits,
+                       sigma, window, &J);
+    if (!rc) rc = kpset_detect_plan(ctx, ks, pyr0, sigma_mask, min_response, (size_t)S * 4, D);
     if (rc) return rc;
-    DetectArgs A;
-    size_t lds_bytes;
-    rc = det_plan(ctx, A, pyr0->plane(0, 0), pyr0->H[0], pyr0->W[0], pyr0->P[0], pyr0->zstride, max_points, radius, grid_rows, grid_cols, cell_size, kmax,
-                  sigma_mask, min_response, &lds_bytes);
-    if (rc) return rc;
-    A.cur = ks->yx; A.cur_cnt = ks->count; A.cur_stride = ks->cap;
-    Layout D;
-    const size_t o_cnt = D.take((size_t)S * n_cells * 4), o_cout = D.take((size_t)S * n_cells * kmax * 16), o_c0 = D.take((size_t)S * 4);
-    char *d;
-    rc = slam_scratch(ctx, D.size(), (void **)&d);
-    if (rc) return rc;
-    A.cell_cnt = (int *)(d + o_cnt); A.cell_out = (int64_t *)(d + o_cout);
-    int *cnt0 = (int *)(d + o_c0);
+    int *cnt0 = (int *)D.extra;
     { ProfScope span(ctx, "detect");
       { ProfScope cells(ctx, "detect_cells");                       // (the yardstick scripts/probes/prof_describe.py quotes the describe stage against)
-        hipLaunchKernelGGL(detect_cells, dim3(n_cells, S), dim3(DET_THREADS), lds_bytes, ctx->stream, A); }
-      hipLaunchKernelGGL(detect_box_filter, dim3((n_cells + 255) / 256, S), dim3(256), 0, ctx->stream, A.cell_out, A.cell_cnt, n_cells, kmax, max_points,
-                         (const int *)ks->count, (const int64_t *)ks->next_id, pyr0->H[0], pyr0->W[0], (window + 1) / 2, cnt0, info_dev);
-      hipLaunchKernelGGL(detect_append, dim3(S), dim3(1024), 0, ctx->stream, (const int64_t *)A.cell_out, (const int *)A.cell_cnt, n_cells, kmax, max_points,
-                         ks->yx, ks->syx, ks->xyz, ks->id, ks->is3d, ks->stereo, ks->haskf, ks->count, ks->next_id, ks->cap); }
+        hipLaunchKernelGGL(detect_cells, dim3(D.n_cells, S), dim3(DET_THREADS), D.lds_bytes, ctx->stream, D.A); }
+      hipLaunchKernelGGL(detect_box_filter, dim3((D.n_cells + 255) / 256, S), dim3(256), 0, ctx->stream, D.A.cell_out, D.A.cell_cnt, D.n_cells, D.kmax, max_points,
+                         (const int *)ks->v.count, (const int64_t *)ks->next_id, pyr0->H[0], pyr0->W[0], (window + 1) / 2, cnt0, info_dev);
+      kpset_detect_append(ctx, ks, D); }
     HIP_TRY(ctx, hipGetLastError());
-    J.yx = ks->yx; J.cnt0 = cnt0; J.count = ks->count; J.cap = ks->cap; J.dcap = dcap; J.info = info_dev; J.out = desc_dev;
-    return brief_launch(ctx, J, n_cells * kmax, S);
+    J.yx = ks->v.yx; J.cnt0 = cnt0; J.count = ks->v.count; J.cap = ks->v.cap; J.dcap = dcap; J.info = info_dev; J.out = desc_dev;
+    return brief_launch(ctx, J, D.n_cells * D.kmax, S);
 }

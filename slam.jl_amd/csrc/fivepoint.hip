@@ -16,7 +16,7 @@
 //                 error, E and [R | t].
 // The solver is a latency chain (0.2 ms for any tuple count that fits the GPU); scoring is ~iters x 6 x n triangulations
 // of ~0.4 kflop each.
-#include "common.hpp"
+#include "kpset.hpp"
 #include "geom_device.hpp"
 #include <cmath>
 
@@ -787,7 +787,7 @@ extern "C" int slam_five_point_ransac_batch(slam_ctx *ctx, int S, const int32_t 
 // =====================================================================================================================
 struct KFiveArgs {
     const double *yx, *kyx; const uint8_t *haskf; const int *count; int cap;
-    const double *par;                 // S x 32: [0..8] R_compensation (column-major 3 x 3), [16..19] fx fy cx cy, [20..23] k1 k2 p1 p2
+    const double *par;                 // S x KP_PAR (kpset.hpp), R_compensation in [0..8]
     double *px1, *px2, *pd1, *pd2; int *slot; int *n5; double *psum; double *ks;      // gathered pairs, stride cap; S x 8 intrinsics
     int32_t *samples; int iters; unsigned long long seed; double min_parallax;
     const double *fp_out; const uint8_t *inl;                                          // k_5pt_select's outputs
@@ -800,11 +800,12 @@ __global__ __launch_bounds__(256) void k_kfive_gather(KFiveArgs A)
     __shared__ double s_par[4];
     const int z = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, n = A.count[z];
     const size_t b = (size_t)z * A.cap;
-    const double *par = A.par + 32 * (size_t)z;
-    const double cam[4] = {par[16], par[17], par[18], par[19]}, dist[4] = {par[20], par[21], par[22], par[23]};
+    const double *par = A.par + KP_PAR * (size_t)z;
+    double cam[4], dist[4];
+    load_cam(par, cam, dist);
     const double fx = cam[0], fy = cam[1], cx = cam[2], cy = cam[3];
     if (tid == 0) s_base = 0;
-    if (tid < 8) A.ks[8 * z + tid] = par[16 + (tid & 3)];        // both views through the same camera
+    if (tid < 8) A.ks[8 * z + tid] = par[KP_PAR_CAM + (tid & 3)];        // both views through the same camera
     __syncthreads();
     double psum = 0.0;
     for (int c0 = 0; c0 < n; c0 += 256) {
@@ -821,7 +822,7 @@ __global__ __launch_bounds__(256) void k_kfive_gather(KFiveArgs A)
             A.pd1[2 * o] = ax; A.pd1[2 * o + 1] = ay; A.pd2[2 * o] = bx; A.pd2[2 * o + 1] = by;      // position[[1, 2]], :268-269
             A.slot[o] = j;
             // rotation-compensated parallax, :277-279: project(camera, R_compensation * position) - previous undistorted pixel
-            // (k_kpset_frame_stats, kpset.hip, forms the same term for compute_parallax's mean and median: the two sites are kept equal by hand)
+            // rotate_project<3> (geom_device.hpp) spelled out: inlined, it swaps the operands of one multiplication of this kernel
             const double rx = (par[0] * bx + par[3] * by) + par[6] * 1.0, ry = (par[1] * bx + par[4] * by) + par[7] * 1.0,
                          rz = (par[2] * bx + par[5] * by) + par[8] * 1.0;
             const double qy = fy * ry / rz + cy, qx = fx * rx / rz + cx;
@@ -875,7 +876,7 @@ extern "C" int slam_kpset_compute_pose_5pt(slam_ctx *ctx, slam_kpset *ks, const 
     ARG_TRY(ctx, ctx != nullptr && ks != nullptr && params != nullptr && iters > 0 && ((P != nullptr) == (status != nullptr)));
     const bool fetch = P != nullptr;                             // P == status == NULL: enqueue only (the filter's effect is on the lists)
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const int S = ks->S, cap = ks->cap;
+    const int S = ks->S, cap = ks->v.cap;
     const size_t nc = (size_t)S * cap;
     Layout D;                          // device scratch
     const size_t o_px1 = D.take(nc * 16), o_px2 = D.take(nc * 16), o_pd1 = D.take(nc * 16), o_pd2 = D.take(nc * 16), o_slot = D.take(nc * 4);
@@ -889,10 +890,10 @@ extern "C" int slam_kpset_compute_pose_5pt(slam_ctx *ctx, slam_kpset *ks, const 
     int rc = slam_scratch2(ctx, D.size(), (void **)&scr);
     if (rc) return rc;
     const double *par_dev;
-    rc = kpset_stage_params(ctx, ks, params, (size_t)S * 32, &par_dev);
+    rc = kpset_stage_params(ctx, ks, params, (size_t)S * KP_PAR, &par_dev);
     if (rc) return rc;
     KFiveArgs A;
-    A.yx = ks->yx; A.kyx = ks->kyx; A.haskf = ks->haskf; A.count = ks->count; A.cap = cap; A.par = par_dev;
+    A.yx = ks->v.yx; A.kyx = ks->v.kyx; A.haskf = ks->v.haskf; A.count = ks->v.count; A.cap = cap; A.par = par_dev;
     A.px1 = (double *)(scr + o_px1); A.px2 = (double *)(scr + o_px2); A.pd1 = (double *)(scr + o_pd1); A.pd2 = (double *)(scr + o_pd2);
     A.slot = (int *)(scr + o_slot); A.n5 = (int *)(scr + o_n5); A.psum = (double *)(scr + o_ps); A.ks = (double *)(scr + o_ks);
     A.samples = (int32_t *)(scr + o_smp); A.iters = iters; A.seed = seed; A.min_parallax = min_parallax;
@@ -918,16 +919,6 @@ extern "C" int slam_kpset_compute_pose_5pt(slam_ctx *ctx, slam_kpset *ks, const 
     char *h;
     rc = slam_pinned(ctx, H.size(), (void **)&h);
     if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(h + h_P, A.P, (size_t)S * 96, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(h + h_st, A.status, (size_t)S * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(h + h_ni, A.ninl, (size_t)S * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(h + h_pa, A.parallax, (size_t)S * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(h + h_cn, ks->count, (size_t)S * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, slam_stream_wait(ctx->stream));
-    memcpy(P, h + h_P, (size_t)S * 96);
-    memcpy(status, h + h_st, (size_t)S * 4);
-    if (n_inliers) memcpy(n_inliers, h + h_ni, (size_t)S * 4);
-    if (parallax) memcpy(parallax, h + h_pa, (size_t)S * 8);
-    if (counts) memcpy(counts, h + h_cn, (size_t)S * 4);
-    return SLAM_OK;
+    return kpset_read_back(ctx, h, {{h_P, A.P, (size_t)S * 96, P}, {h_st, A.status, (size_t)S * 4, status}, {h_ni, A.ninl, (size_t)S * 4, n_inliers},
+                                    {h_pa, A.parallax, (size_t)S * 8, parallax}, {h_cn, ks->v.count, (size_t)S * 4, counts}});
 }

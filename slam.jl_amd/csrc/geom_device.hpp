@@ -48,6 +48,15 @@ __device__ __forceinline__ void undistort_px(const double *cam, const double *di
 {
     pdn_to_pixel(cam, dist, (y - cam[3]) / cam[1], (x - cam[2]) / cam[0], uy, ux);
 }
+// project(camera, R * (bx, by, 1)) -> pixel (qy, qx): the rotation-compensated position of the parallax terms (front_end.jl:277-279,
+// :436-438; mapper.jl:236-237).  R column-major with column stride LD: 3 for R_compensation, 4 for the rotation of a 4 x 4 pose
+template <int LD>
+__device__ __forceinline__ void rotate_project(const double *R, const double *cam, double bx, double by, double &qy, double &qx)
+{
+    const double rx = (R[0] * bx + R[LD] * by) + R[2 * LD] * 1.0, ry = (R[1] * bx + R[LD + 1] * by) + R[2 * LD + 1] * 1.0,
+                 rz = (R[2] * bx + R[LD + 2] * by) + R[2 * LD + 2] * 1.0;
+    qy = cam[1] * ry / rz + cam[3]; qx = cam[0] * rx / rz + cam[2];
+}
 
 // ---- two-view DLT and the mapper's gates ---------------------------------------------------------------------------------------------
 // the five matrices of a triangulation call, as the host hands them over: column-major 4 x 4 (Julia SMatrix) and fx, fy, cx, cy

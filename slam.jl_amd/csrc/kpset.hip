@@ -8,12 +8,13 @@
 // (slam_kpset_stereo_match) and triangulation (slam_kpset_triangulate) all read and write the same device arrays; the
 // host sees one small copy of the per-stream counts per step (slam_kpset_counts).  Compaction is stable (a stream's
 // keypoints keep their order) and is done with wave ballots + prefix counts, one workgroup per stream.
-#include "common.hpp"
+#include "kpset.hpp"
 #include <algorithm>
 #include "geom_device.hpp"
 #include "work_order.hpp"
 #include "kf_host.hpp"
 #include <cmath>
+#include <type_traits>
 
 // live slots of all streams back to back + their number.  One small workgroup per stream (it sums the counts before its own: S
 // loads): a single 1024-thread workgroup had to wait for sixteen free wave slots on one CU while the pyramid kernels fill the chip
@@ -68,7 +69,7 @@ int kpset_build_worklist(slam_ctx *ctx, slam_kpset *ks, int H, int W)
     WorkOrder O;
     O.H = H; O.W = W; O.pad = ks->sort_pad; O.band = H > 0 && W > 0 && ks->sort_pad > 0 ? work_band() : 0;
     const size_t lds = O.band > 0 ? (size_t)ks->sort_pad * 8 : 0;
-    hipLaunchKernelGGL(k_kpset_worklist, dim3(ks->S), dim3(256), lds, ctx->stream, (const int *)ks->count, ks->S, ks->cap, ks->work, ks->ntot, (const double *)ks->yx, O);
+    hipLaunchKernelGGL(k_kpset_worklist, dim3(ks->S), dim3(256), lds, ctx->stream, (const int *)ks->v.count, ks->S, ks->v.cap, ks->work, ks->ntot, (const double *)ks->v.yx, O);
     HIP_TRY(ctx, hipGetLastError());
     return SLAM_OK;
 }
@@ -78,9 +79,7 @@ int kpset_build_worklist(slam_ctx *ctx, slam_kpset *ks, int H, int W)
 // mode 1 (removal by flags): keep flags[slot] == 0.
 // Chunks of 256 slots are read (all fields into registers), ranked with a wave ballot + the popcount of the lower lanes,
 // and written back after a barrier: destinations never lie to the right of their sources, so in place is safe.
-struct KpsetView {
-    double *yx, *oyx, *syx, *xyz, *kyx, *fyx; int64_t *id; uint8_t *is3d, *stereo, *st, *haskf; int *fkf, *kfcount; int *count; int cap;
-};
+// (The load and the store block stay spelled out: a record struct with load / store members changes the kernel's register assignment -- HISTORY.md, round 20.)
 __global__ __launch_bounds__(256) void k_kpset_compact(KpsetView K, int mode, const uint8_t *flags)
 {
     __shared__ int s_w[4], s_base;
@@ -121,17 +120,9 @@ __global__ __launch_bounds__(256) void k_kpset_compact(KpsetView K, int mode, co
     if (tid == 0) K.count[s] = s_base;
 }
 
-static KpsetView view_of(slam_kpset *ks)
-{
-    KpsetView K; K.yx = ks->yx; K.oyx = ks->oyx; K.syx = ks->syx; K.xyz = ks->xyz; K.kyx = ks->kyx; K.id = ks->id; K.is3d = ks->is3d; K.stereo = ks->stereo;
-    K.haskf = ks->haskf; K.fyx = ks->fyx; K.fkf = ks->fkf; K.kfcount = ks->kfcount;
-    K.st = ks->st; K.count = ks->count; K.cap = ks->cap;
-    return K;
-}
-
 int kpset_stage_params(slam_ctx *ctx, slam_kpset *ks, const double *host, size_t n, const double **dev_out)
 {
-    const size_t slot_d = (size_t)ks->S * 32;
+    const size_t slot_d = (size_t)ks->S * KP_PAR;
     ARG_TRY(ctx, n <= slot_d);
     const int sl = ks->par_slot; ks->par_slot = (sl + 1) & 7;
     HIP_TRY(ctx, hipEventSynchronize(ks->par_ev[sl]));           // the copy that last used this slot (8 calls ago) has long completed
@@ -145,7 +136,7 @@ int kpset_stage_params(slam_ctx *ctx, slam_kpset *ks, const double *host, size_t
 
 int kpset_compact(slam_ctx *ctx, slam_kpset *ks, int mode, const uint8_t *flags_dev)
 {
-    hipLaunchKernelGGL(k_kpset_compact, dim3(ks->S), dim3(256), 0, ctx->stream, view_of(ks), mode, flags_dev);
+    hipLaunchKernelGGL(k_kpset_compact, dim3(ks->S), dim3(256), 0, ctx->stream, ks->v, mode, flags_dev);
     HIP_TRY(ctx, hipGetLastError());
     return SLAM_OK;
 }
@@ -190,7 +181,7 @@ __global__ __launch_bounds__(64) void k_kpset_triangulate(KpsetView K, KTriArgs 
 // a failed gate removes the observation only when the rotation-compensated parallax exceeds min_parallax (20 px), otherwise the
 // point is accepted as it is (:244-258).
 struct KTempArgs {
-    const double *par;        // S x 32: [16..19] fx fy cx cy, [20..23] k1 k2 p1 p2
+    const double *par;        // S x KP_PAR (kpset.hpp)
     const double *tab;        // S x nkf x 64
     const int *kf_cur, *kf_lo; int nkf;
     double max_error, min_depth, min_parallax;
@@ -202,21 +193,19 @@ __device__ __forceinline__ void k_kpset_tri_temporal_slot(const KpsetView &K, co
     if (K.is3d[q] || !K.haskf[q]) return;                        // get_2d_keypoints; keypoints no key-frame has observed yet
     const int s = (int)(q / K.cap), kf = K.fkf[q];
     if (kf == T.kf_cur[s] || kf < T.kf_lo[s]) return;            // :216 the frame itself is the first observer; observer no longer in the table
-    const double *par = T.par + 32 * (size_t)s;
+    const double *par = T.par + KP_PAR * (size_t)s, *cam = par + KP_PAR_CAM, *dist = par + KP_PAR_DIST;
     const double *E = T.tab + ((size_t)s * T.nkf + (kf % T.nkf)) * 64;
     const double *P2 = E, *T21 = E + 16, *REL = E + 32, *WOB = E + 48;
-    const double fx = par[16], fy = par[17], cx = par[18], cy = par[19];
-    double y1, x1, y2, x2;
-    undistort_px(par + 16, par + 20, K.fyx[2 * q], K.fyx[2 * q + 1], y1, x1);  // obup
-    undistort_px(par + 16, par + 20, K.yx[2 * q], K.yx[2 * q + 1], y2, x2);    // kpup
+    const double fx = cam[0], fy = cam[1], cx = cam[2], cy = cam[3];
+    double y1, x1, y2, x2, qy, qx;
+    undistort_px(cam, dist, K.fyx[2 * q], K.fyx[2 * q + 1], y1, x1);  // obup
+    undistort_px(cam, dist, K.yx[2 * q], K.yx[2 * q + 1], y2, x2);    // kpup
     // parallax = |obup - project(camera, R(rel_pose) * kp.position)|, :236-237
-    const double bx = (x2 - cx) / fx, by = (y2 - cy) / fy;
-    const double rx = (REL[0] * bx + REL[4] * by) + REL[8] * 1.0, ry = (REL[1] * bx + REL[5] * by) + REL[9] * 1.0, rz = (REL[2] * bx + REL[6] * by) + REL[10] * 1.0;
-    const double qy = fy * ry / rz + cy, qx = fx * rx / rz + cx;
+    rotate_project<4>(REL, cam, (x2 - cx) / fx, (y2 - cy) / fy, qy, qx);
     const double pdy = y1 - qy, pdx = x1 - qx;
     const bool gated = sqrt(pdy * pdy + pdx * pdx) > T.min_parallax;
     // P1 = K * I
-    const double P1[16] = {fx, 0, 0, 0, 0, fy, 0, 0, cx, cy, 1, 0, 0, 0, 0, 1}, cam[4] = {fx, fy, cx, cy};
+    const double P1[16] = {fx, 0, 0, 0, 0, fy, 0, 0, cx, cy, 1, 0, 0, 0, 0, 1};
     double L[4];
     dlt_two_view(x1, y1, x2, y2, P1, P2, L);
     const bool ok = two_view_gates(L, T21, cam, cam, x1, y1, x2, y2, T.max_error, T.min_depth, gated);
@@ -251,7 +240,7 @@ static_assert(KF_STATS == SLAM_KF_STATS, "kf_host.hpp and slamhip.h disagree on 
 #define KF_BITMAP_LDS_BYTES 16384     /* with the 32 KiB of terms and the histogram: inside the 64 KiB a workgroup gets without asking */
 struct KfStatsArgs {
     const double *yx, *kyx; const uint8_t *is3d, *stereo, *haskf; const int *count; int cap;
-    const double *par;                 // S x 32: [0..8] R_compensation (column-major 3 x 3), [16..19] fx fy cx cy, [20..23] k1 k2 p1 p2
+    const double *par;                 // S x KP_PAR (kpset.hpp), R_compensation in [0..8]
     int flags, cell, gr, gc, words;    // flags: bit 0 compensate_rotation, bit 1 only_2d; words: 32-bit words of the cell bitmap
     unsigned long long *terms;         // S x cap, or nullptr when cap <= KF_TERMS_LDS
     double *out;                       // S x SLAM_KF_STATS
@@ -331,8 +320,9 @@ __global__ __launch_bounds__(256) void k_kpset_frame_stats(KfStatsArgs A)
     const int z = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int n = min(max(A.count[z], 0), A.cap);
     const size_t b = (size_t)z * A.cap;
-    const double *par = A.par + 32 * (size_t)z;
-    const double cam[4] = {par[16], par[17], par[18], par[19]}, dist[4] = {par[20], par[21], par[22], par[23]};
+    const double *par = A.par + KP_PAR * (size_t)z;
+    double cam[4], dist[4];
+    load_cam(par, cam, dist);
     const double fx = cam[0], fy = cam[1], cx = cam[2], cy = cam[3];
     const bool comp = (A.flags & 1) != 0, only2d = (A.flags & 2) != 0;
     for (int w = tid; w < A.words; w += 256) s_bits[w] = 0;
@@ -367,15 +357,12 @@ __global__ __launch_bounds__(256) void k_kpset_frame_stats(KfStatsArgs A)
         const int pos = ordered_slot(take, s_w, &s_base);
         if (take) {
             const size_t q = b + j;
-            double uy, ux, vy, vx, t;
+            double uy, ux, vy, vx, qy, qx, t;
             undistort_px(cam, dist, y, x, uy, ux);
             undistort_px(cam, dist, A.kyx[2 * q], A.kyx[2 * q + 1], vy, vx);
             if (comp) {
-                // project(camera, R_compensation * position) - previous undistorted pixel: the term of k_kfive_gather (fivepoint.hip)
-                const double bx = (ux - cx) / fx, by = (uy - cy) / fy;
-                const double rx = (par[0] * bx + par[3] * by) + par[6] * 1.0, ry = (par[1] * bx + par[4] * by) + par[7] * 1.0,
-                             rz = (par[2] * bx + par[5] * by) + par[8] * 1.0;
-                const double qy = fy * ry / rz + cy, qx = fx * rx / rz + cx;
+                // project(camera, R_compensation * position) - previous undistorted pixel: the term k_kfive_gather (fivepoint.hip) sums
+                rotate_project<3>(par, cam, (ux - cx) / fx, (uy - cy) / fy, qy, qx);
                 const double dy = qy - vy, dx = qx - vx;
                 t = sqrt(dy * dy + dx * dx);
             } else {
@@ -408,6 +395,56 @@ __global__ __launch_bounds__(256) void k_kpset_frame_stats(KfStatsArgs A)
     }
 }
 
+// Every region of the set's one allocation, each named once with its size: called without a block for the total, then with the block
+// to bind the pointers.  The order is the allocation's.
+static size_t kpset_regions(slam_kpset *ks, char *base)
+{
+    Layout Lo;
+    auto region = [&](auto *&p, size_t bytes) { const size_t at = Lo.take(bytes); if (base) p = (std::remove_reference_t<decltype(p)>)(base + at); };
+    KpsetView &v = ks->v;
+    const size_t S = (size_t)ks->S, n = S * v.cap;
+    region(v.yx, n * 16); region(v.oyx, n * 16); region(v.syx, n * 16); region(v.xyz, n * 24); region(v.id, n * 8);
+    region(v.is3d, n); region(v.stereo, n); region(v.st, n); region(v.count, S * 4); region(ks->work, n * 4); region(ks->ntot, 64);
+    region(ks->next_id, S * 8); region(ks->par, 8 * S * KP_PAR * 8); region(v.kyx, n * 16); region(v.haskf, n); region(v.fyx, n * 16);
+    region(v.fkf, n * 4); region(v.kfcount, S * 4);
+    return Lo.size();
+}
+
+// One body of the three uploads and the three downloads: n keypoints of stream s between each listed array (bytes per keypoint) and
+// its host array, skipped where that is null; n == 0 enqueues nothing; `wait`: the seam's wait after the copies.
+struct KpField { void *dev; size_t bytes; const void *host; };
+static int kpset_copy(slam_ctx *ctx, const slam_kpset *ks, int s, int n, hipMemcpyKind kind, bool wait, std::initializer_list<KpField> fields)
+{
+    if (n <= 0) return SLAM_OK;
+    for (const KpField &f : fields) {
+        if (!f.host) continue;
+        void *d = (char *)f.dev + (size_t)s * ks->v.cap * f.bytes, *h = const_cast<void *>(f.host);
+        HIP_TRY(ctx, hipMemcpyAsync(kind == hipMemcpyHostToDevice ? d : h, kind == hipMemcpyHostToDevice ? h : d, (size_t)n * f.bytes, kind, ctx->stream));
+    }
+    if (wait) HIP_TRY(ctx, slam_stream_wait(ctx->stream));
+    return SLAM_OK;
+}
+// What every download does first: read count[s] (and kfcount[s] `with_kf`), one wait, *n_out (and *kf_count, where given), the capacity refusal in `who`'s name
+static int kpset_download_begin(slam_ctx *ctx, slam_kpset *ks, int s, const char *who, int cap_out, int *n_out, bool with_kf, int *kf_count)
+{
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int n = 0, kc = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(&n, ks->v.count + s, 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (with_kf) HIP_TRY(ctx, hipMemcpyAsync(&kc, ks->v.kfcount + s, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, slam_stream_wait(ctx->stream));
+    *n_out = n; if (kf_count) *kf_count = kc;
+    if (n > cap_out) return slam_fail(ctx, SLAM_ERR_CAPACITY, "%s: %d keypoints but cap = %d", who, n, cap_out);
+    return SLAM_OK;
+}
+
+int kpset_read_back(slam_ctx *ctx, char *h, std::initializer_list<KpReadBack> parts)
+{
+    for (const KpReadBack &p : parts) HIP_TRY(ctx, hipMemcpyAsync(h + p.at, p.dev, p.bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, slam_stream_wait(ctx->stream));
+    for (const KpReadBack &p : parts) if (p.out) memcpy(p.out, h + p.at, p.bytes);
+    return SLAM_OK;
+}
+
 extern "C" {
 
 int slam_kpset_destroy(slam_kpset *ks);
@@ -416,25 +453,16 @@ int slam_kpset_create(slam_ctx *ctx, int S, int cap, slam_kpset **out)
 {
     ARG_TRY(ctx, ctx != nullptr && out != nullptr && S >= 1 && S <= 128 && cap >= 1 && (size_t)S * cap < (1u << 30));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t n = (size_t)S * cap;
-    Layout Lo;
-    const size_t o_yx = Lo.take(n * 16), o_oyx = Lo.take(n * 16), o_syx = Lo.take(n * 16), o_xyz = Lo.take(n * 24), o_id = Lo.take(n * 8);
-    const size_t o_3d = Lo.take(n), o_st = Lo.take(n), o_ss = Lo.take(n), o_cnt = Lo.take((size_t)S * 4), o_work = Lo.take(n * 4), o_nt = Lo.take(64);
-    const size_t o_nid = Lo.take((size_t)S * 8), o_par = Lo.take((size_t)8 * S * 32 * 8), o_kyx = Lo.take(n * 16), o_hk = Lo.take(n), o_fyx = Lo.take(n * 16), o_fkf = Lo.take(n * 4), o_kfc = Lo.take((size_t)S * 4);
     slam_kpset *ks = new slam_kpset();
-    ks->device = ctx->device; ks->S = S; ks->cap = cap;
+    ks->device = ctx->device; ks->S = S; ks->v.cap = cap;
+    const size_t bytes = kpset_regions(ks, nullptr);
     { size_t pad = 1; while (pad < (size_t)cap) pad <<= 1; ks->sort_pad = work_band() > 0 && pad * 8 <= KPSET_SORT_LDS_BYTES ? (int)pad : 0; }
-    hipError_t e = hipMalloc((void **)&ks->base, Lo.size());
-    if (e == hipSuccess) e = hipMemsetAsync(ks->base, 0, Lo.size(), ctx->stream);
+    hipError_t e = hipMalloc((void **)&ks->base, bytes);
+    if (e == hipSuccess) e = hipMemsetAsync(ks->base, 0, bytes, ctx->stream);
     if (e == hipSuccess) e = slam_stream_wait(ctx->stream);
     if (e != hipSuccess) { if (ks->base) (void)hipFree(ks->base); delete ks; return slam_fail(ctx, SLAM_ERR_HIP, "slam_kpset_create: %s", hipGetErrorString(e)); }
-    char *B = ks->base;
-    ks->yx = (double *)(B + o_yx); ks->oyx = (double *)(B + o_oyx); ks->syx = (double *)(B + o_syx); ks->xyz = (double *)(B + o_xyz);
-    ks->id = (int64_t *)(B + o_id); ks->is3d = (uint8_t *)(B + o_3d); ks->stereo = (uint8_t *)(B + o_st); ks->st = (uint8_t *)(B + o_ss);
-    ks->count = (int *)(B + o_cnt); ks->work = (int *)(B + o_work); ks->ntot = (int *)(B + o_nt); ks->next_id = (int64_t *)(B + o_nid);
-    ks->par = (double *)(B + o_par); ks->kyx = (double *)(B + o_kyx); ks->haskf = (uint8_t *)(B + o_hk);
-    ks->fyx = (double *)(B + o_fyx); ks->fkf = (int *)(B + o_fkf); ks->kfcount = (int *)(B + o_kfc);
-    e = hipHostMalloc((void **)&ks->par_host, (size_t)8 * S * 32 * 8);
+    kpset_regions(ks, ks->base);
+    e = hipHostMalloc((void **)&ks->par_host, (size_t)8 * S * KP_PAR * 8);
     for (int i = 0; i < 8 && e == hipSuccess; i++) { e = hipEventCreateWithFlags(&ks->par_ev[i], hipEventDisableTiming); if (e == hipSuccess) e = hipEventRecord(ks->par_ev[i], ctx->stream); }
     if (e != hipSuccess) { slam_kpset_destroy(ks); return slam_fail(ctx, SLAM_ERR_HIP, "slam_kpset_create: %s", hipGetErrorString(e)); }
     *out = ks;
@@ -463,7 +491,7 @@ int slamhip_test_kpset_worklist(slam_ctx *ctx, slam_kpset *ks, int H, int W, int
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     int rc = kpset_build_worklist(ctx, ks, H, W);
     if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(work_out, ks->work, (size_t)ks->S * ks->cap * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(work_out, ks->work, (size_t)ks->S * ks->v.cap * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(ntot_out, ks->ntot, 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, slam_stream_wait(ctx->stream));
     *band_out = H > 0 && W > 0 && ks->sort_pad > 0 ? work_band() : 0;
@@ -471,28 +499,29 @@ int slamhip_test_kpset_worklist(slam_ctx *ctx, slam_kpset *ks, int H, int W, int
 }
 
 int slam_kpset_streams(const slam_kpset *ks) { return ks ? ks->S : SLAM_ERR_ARG; }
-int slam_kpset_capacity(const slam_kpset *ks) { return ks ? ks->cap : SLAM_ERR_ARG; }
+int slam_kpset_capacity(const slam_kpset *ks) { return ks ? ks->v.cap : SLAM_ERR_ARG; }
 
 // replace stream s's list (initialisation, tests); ids == NULL: 0 .. n-1, the stream's id counter moves past them
 int slam_kpset_upload(slam_ctx *ctx, slam_kpset *ks, int s, const double *yx, const uint8_t *is3d, const double *xyz, const int64_t *ids, int n)
 {
-    ARG_TRY(ctx, ctx != nullptr && ks != nullptr && s >= 0 && s < ks->S && n >= 0 && n <= ks->cap && (n == 0 || (yx != nullptr && is3d != nullptr)));
+    ARG_TRY(ctx, ctx != nullptr && ks != nullptr && s >= 0 && s < ks->S && n >= 0 && n <= ks->v.cap && (n == 0 || (yx != nullptr && is3d != nullptr)));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t b = (size_t)s * ks->cap;
+    const KpsetView &v = ks->v;
+    const size_t b = (size_t)s * v.cap;
     std::vector<int64_t> idv((size_t)n);
     int64_t mx = -1;
     for (int i = 0; i < n; i++) { idv[i] = ids ? ids[i] : i; mx = idv[i] > mx ? idv[i] : mx; }
     const int64_t next = mx + 1;
+    int rc = kpset_copy(ctx, ks, s, n, hipMemcpyHostToDevice, false, {{v.yx, 16, yx}, {v.is3d, 1, is3d}, {v.xyz, 24, xyz}});
+    if (rc) return rc;
+    if (n > 0 && !xyz) HIP_TRY(ctx, hipMemsetAsync(v.xyz + 3 * b, 0, (size_t)n * 24, ctx->stream));
+    rc = kpset_copy(ctx, ks, s, n, hipMemcpyHostToDevice, false, {{v.id, 8, idv.data()}});
+    if (rc) return rc;
     if (n > 0) {
-        HIP_TRY(ctx, hipMemcpyAsync(ks->yx + 2 * b, yx, (size_t)n * 16, hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(ks->is3d + b, is3d, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-        if (xyz) HIP_TRY(ctx, hipMemcpyAsync(ks->xyz + 3 * b, xyz, (size_t)n * 24, hipMemcpyHostToDevice, ctx->stream));
-        else HIP_TRY(ctx, hipMemsetAsync(ks->xyz + 3 * b, 0, (size_t)n * 24, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(ks->id + b, idv.data(), (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipMemsetAsync(ks->stereo + b, 0, (size_t)n, ctx->stream));
-        HIP_TRY(ctx, hipMemsetAsync(ks->haskf + b, 0, (size_t)n, ctx->stream));
+        HIP_TRY(ctx, hipMemsetAsync(v.stereo + b, 0, (size_t)n, ctx->stream));
+        HIP_TRY(ctx, hipMemsetAsync(v.haskf + b, 0, (size_t)n, ctx->stream));
     }
-    HIP_TRY(ctx, hipMemcpyAsync(ks->count + s, &n, 4, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(v.count + s, &n, 4, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(ks->next_id + s, &next, 8, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, slam_stream_wait(ctx->stream));
     return SLAM_OK;
@@ -503,23 +532,11 @@ int slam_kpset_download(slam_ctx *ctx, slam_kpset *ks, int s, double *yx, uint8_
                         double *stereo_yx, uint8_t *has_stereo, int cap_out, int *n_out)
 {
     ARG_TRY(ctx, ctx != nullptr && ks != nullptr && s >= 0 && s < ks->S && n_out != nullptr);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int n = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(&n, ks->count + s, 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, slam_stream_wait(ctx->stream));
-    *n_out = n;
-    if (n > cap_out) return slam_fail(ctx, SLAM_ERR_CAPACITY, "slam_kpset_download: %d keypoints but cap = %d", n, cap_out);
-    const size_t b = (size_t)s * ks->cap;
-    if (n > 0) {
-        if (yx) HIP_TRY(ctx, hipMemcpyAsync(yx, ks->yx + 2 * b, (size_t)n * 16, hipMemcpyDeviceToHost, ctx->stream));
-        if (is3d) HIP_TRY(ctx, hipMemcpyAsync(is3d, ks->is3d + b, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-        if (xyz) HIP_TRY(ctx, hipMemcpyAsync(xyz, ks->xyz + 3 * b, (size_t)n * 24, hipMemcpyDeviceToHost, ctx->stream));
-        if (ids) HIP_TRY(ctx, hipMemcpyAsync(ids, ks->id + b, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
-        if (stereo_yx) HIP_TRY(ctx, hipMemcpyAsync(stereo_yx, ks->syx + 2 * b, (size_t)n * 16, hipMemcpyDeviceToHost, ctx->stream));
-        if (has_stereo) HIP_TRY(ctx, hipMemcpyAsync(has_stereo, ks->stereo + b, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, slam_stream_wait(ctx->stream));
-    }
-    return SLAM_OK;
+    const int rc = kpset_download_begin(ctx, ks, s, "slam_kpset_download", cap_out, n_out, false, nullptr);
+    if (rc) return rc;
+    const KpsetView &v = ks->v;
+    return kpset_copy(ctx, ks, s, *n_out, hipMemcpyDeviceToHost, true,
+                      {{v.yx, 16, yx}, {v.is3d, 1, is3d}, {v.xyz, 24, xyz}, {v.id, 8, ids}, {v.syx, 16, stereo_yx}, {v.stereo, 1, has_stereo}});
 }
 
 // create_keyframe! (map_manager.jl:60-96) as far as the lists are concerned: the current frame becomes the previous key-frame
@@ -538,71 +555,41 @@ int slam_kpset_keyframe(slam_ctx *ctx, slam_kpset *ks)
 {
     ARG_TRY(ctx, ctx != nullptr && ks != nullptr);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipLaunchKernelGGL(k_kpset_keyframe, dim3((ks->cap + 255) / 256, ks->S), dim3(256), 0, ctx->stream, view_of(ks));
-    hipLaunchKernelGGL(k_kpset_kf_advance, dim3((ks->S + 63) / 64), dim3(64), 0, ctx->stream, ks->kfcount, ks->S);
+    hipLaunchKernelGGL(k_kpset_keyframe, dim3((ks->v.cap + 255) / 256, ks->S), dim3(256), 0, ctx->stream, ks->v);
+    hipLaunchKernelGGL(k_kpset_kf_advance, dim3((ks->S + 63) / 64), dim3(64), 0, ctx->stream, ks->v.kfcount, ks->S);
     HIP_TRY(ctx, hipGetLastError());
     return SLAM_OK;
 }
 // the key-frame observations of stream s's list, host <-> device (restoring state, tests): kyx n x 2 (y, x), has_kf n flags
 int slam_kpset_upload_first(slam_ctx *ctx, slam_kpset *ks, int s, const double *first_yx, const int32_t *first_kf, int n, int kf_count)
 {
-    ARG_TRY(ctx, ctx != nullptr && ks != nullptr && s >= 0 && s < ks->S && n >= 0 && n <= ks->cap && (n == 0 || (first_yx != nullptr && first_kf != nullptr)));
+    ARG_TRY(ctx, ctx != nullptr && ks != nullptr && s >= 0 && s < ks->S && n >= 0 && n <= ks->v.cap && (n == 0 || (first_yx != nullptr && first_kf != nullptr)));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t b = (size_t)s * ks->cap;
-    if (n > 0) {
-        HIP_TRY(ctx, hipMemcpyAsync(ks->fyx + 2 * b, first_yx, (size_t)n * 16, hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(ks->fkf + b, first_kf, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-    }
-    HIP_TRY(ctx, hipMemcpyAsync(ks->kfcount + s, &kf_count, 4, hipMemcpyHostToDevice, ctx->stream));
+    const int rc = kpset_copy(ctx, ks, s, n, hipMemcpyHostToDevice, false, {{ks->v.fyx, 16, first_yx}, {ks->v.fkf, 4, first_kf}});
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(ks->v.kfcount + s, &kf_count, 4, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, slam_stream_wait(ctx->stream));
     return SLAM_OK;
 }
 int slam_kpset_download_first(slam_ctx *ctx, slam_kpset *ks, int s, double *first_yx, int32_t *first_kf, int cap_out, int *n_out, int *kf_count)
 {
     ARG_TRY(ctx, ctx != nullptr && ks != nullptr && s >= 0 && s < ks->S && n_out != nullptr);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int n = 0, kc = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(&n, ks->count + s, 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(&kc, ks->kfcount + s, 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, slam_stream_wait(ctx->stream));
-    *n_out = n; if (kf_count) *kf_count = kc;
-    if (n > cap_out) return slam_fail(ctx, SLAM_ERR_CAPACITY, "slam_kpset_download_first: %d keypoints but cap = %d", n, cap_out);
-    const size_t b = (size_t)s * ks->cap;
-    if (n > 0) {
-        if (first_yx) HIP_TRY(ctx, hipMemcpyAsync(first_yx, ks->fyx + 2 * b, (size_t)n * 16, hipMemcpyDeviceToHost, ctx->stream));
-        if (first_kf) HIP_TRY(ctx, hipMemcpyAsync(first_kf, ks->fkf + b, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, slam_stream_wait(ctx->stream));
-    }
-    return SLAM_OK;
+    const int rc = kpset_download_begin(ctx, ks, s, "slam_kpset_download_first", cap_out, n_out, true, kf_count);
+    if (rc) return rc;
+    return kpset_copy(ctx, ks, s, *n_out, hipMemcpyDeviceToHost, true, {{ks->v.fyx, 16, first_yx}, {ks->v.fkf, 4, first_kf}});
 }
 int slam_kpset_upload_keyframe(slam_ctx *ctx, slam_kpset *ks, int s, const double *kyx, const uint8_t *has_kf, int n)
 {
-    ARG_TRY(ctx, ctx != nullptr && ks != nullptr && s >= 0 && s < ks->S && n >= 0 && n <= ks->cap && (n == 0 || (kyx != nullptr && has_kf != nullptr)));
+    ARG_TRY(ctx, ctx != nullptr && ks != nullptr && s >= 0 && s < ks->S && n >= 0 && n <= ks->v.cap && (n == 0 || (kyx != nullptr && has_kf != nullptr)));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t b = (size_t)s * ks->cap;
-    if (n > 0) {
-        HIP_TRY(ctx, hipMemcpyAsync(ks->kyx + 2 * b, kyx, (size_t)n * 16, hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(ks->haskf + b, has_kf, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, slam_stream_wait(ctx->stream));
-    }
-    return SLAM_OK;
+    return kpset_copy(ctx, ks, s, n, hipMemcpyHostToDevice, true, {{ks->v.kyx, 16, kyx}, {ks->v.haskf, 1, has_kf}});
 }
 int slam_kpset_download_keyframe(slam_ctx *ctx, slam_kpset *ks, int s, double *kyx, uint8_t *has_kf, int cap_out, int *n_out)
 {
     ARG_TRY(ctx, ctx != nullptr && ks != nullptr && s >= 0 && s < ks->S && n_out != nullptr);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int n = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(&n, ks->count + s, 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, slam_stream_wait(ctx->stream));
-    *n_out = n;
-    if (n > cap_out) return slam_fail(ctx, SLAM_ERR_CAPACITY, "slam_kpset_download_keyframe: %d keypoints but cap = %d", n, cap_out);
-    const size_t b = (size_t)s * ks->cap;
-    if (n > 0) {
-        if (kyx) HIP_TRY(ctx, hipMemcpyAsync(kyx, ks->kyx + 2 * b, (size_t)n * 16, hipMemcpyDeviceToHost, ctx->stream));
-        if (has_kf) HIP_TRY(ctx, hipMemcpyAsync(has_kf, ks->haskf + b, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, slam_stream_wait(ctx->stream));
-    }
-    return SLAM_OK;
+    const int rc = kpset_download_begin(ctx, ks, s, "slam_kpset_download_keyframe", cap_out, n_out, false, nullptr);
+    if (rc) return rc;
+    return kpset_copy(ctx, ks, s, *n_out, hipMemcpyDeviceToHost, true, {{ks->v.kyx, 16, kyx}, {ks->v.haskf, 1, has_kf}});
 }
 
 // the one small device -> host copy of a step: the S list lengths (synchronises ctx's stream)
@@ -610,13 +597,10 @@ int slam_kpset_counts(slam_ctx *ctx, slam_kpset *ks, int32_t *counts)
 {
     ARG_TRY(ctx, ctx != nullptr && ks != nullptr && counts != nullptr);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    void *h;
-    int rc = slam_pinned(ctx, std::max<size_t>(256, (size_t)ks->S * 4), &h);
+    char *h;
+    int rc = slam_pinned(ctx, std::max<size_t>(256, (size_t)ks->S * 4), (void **)&h);
     if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(h, ks->count, (size_t)ks->S * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, slam_stream_wait(ctx->stream));
-    memcpy(counts, h, (size_t)ks->S * 4);
-    return SLAM_OK;
+    return kpset_read_back(ctx, h, {{0, ks->v.count, (size_t)ks->S * 4, counts}});
 }
 
 // remove the keypoints whose flag is set (flags_dev: S x cap bytes in HBM, slot order): map culling, outliers of the pose
@@ -640,8 +624,8 @@ int slam_kpset_triangulate(slam_ctx *ctx, slam_kpset *ks, const double *P1, cons
     if (rc) return rc;
     rc = kpset_build_worklist(ctx, ks, 0, 0);
     if (rc) return rc;
-    const int nb = n_bound > 0 && n_bound < ks->S * ks->cap ? n_bound : ks->S * ks->cap;
-    hipLaunchKernelGGL(k_kpset_triangulate, dim3((nb + 63) / 64), dim3(64), 0, ctx->stream, view_of(ks), T, (const int *)ks->work, (const int *)ks->ntot);
+    const int nb = kpset_grid_bound(ks, n_bound);
+    hipLaunchKernelGGL(k_kpset_triangulate, dim3((nb + 63) / 64), dim3(64), 0, ctx->stream, ks->v, T, (const int *)ks->work, (const int *)ks->ntot);
     HIP_TRY(ctx, hipGetLastError());
     return SLAM_OK;
 }
@@ -653,7 +637,7 @@ int slam_kpset_triangulate_temporal(slam_ctx *ctx, slam_kpset *ks, const double 
     ARG_TRY(ctx, ctx != nullptr && ks != nullptr && params && tab && kf_cur && kf_lo && nkf >= 1);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int S = ks->S;
-    const size_t nc = (size_t)S * ks->cap;
+    const size_t nc = (size_t)S * ks->v.cap;
     Layout D;                          // the staged inputs (same offsets in the pinned block), then the removal flags
     const size_t o_tab = D.take((size_t)S * nkf * 64 * 8), o_cur = D.take((size_t)S * 4), o_lo = D.take((size_t)S * 4), in_b = D.size(), o_fl = D.take(nc);
     char *scr, *h;
@@ -664,7 +648,7 @@ int slam_kpset_triangulate_temporal(slam_ctx *ctx, slam_kpset *ks, const double 
     memcpy(h + o_tab, tab, (size_t)S * nkf * 64 * 8); memcpy(h + o_cur, kf_cur, (size_t)S * 4); memcpy(h + o_lo, kf_lo, (size_t)S * 4);
     HIP_TRY(ctx, hipMemcpyAsync(scr, h, in_b, hipMemcpyHostToDevice, ctx->stream));
     KTempArgs T;
-    rc = kpset_stage_params(ctx, ks, params, (size_t)S * 32, &T.par);
+    rc = kpset_stage_params(ctx, ks, params, (size_t)S * KP_PAR, &T.par);
     if (rc) return rc;
     T.tab = (const double *)(scr + o_tab); T.kf_cur = (const int *)(scr + o_cur); T.kf_lo = (const int *)(scr + o_lo); T.nkf = nkf;
     T.max_error = max_error; T.min_depth = min_depth; T.min_parallax = min_parallax;
@@ -672,8 +656,8 @@ int slam_kpset_triangulate_temporal(slam_ctx *ctx, slam_kpset *ks, const double 
     HIP_TRY(ctx, hipMemsetAsync(T.flags, 0, nc, ctx->stream));
     rc = kpset_build_worklist(ctx, ks, 0, 0);
     if (rc) return rc;
-    const int nb = n_bound > 0 && n_bound < S * ks->cap ? n_bound : S * ks->cap;
-    hipLaunchKernelGGL(k_kpset_tri_temporal, dim3((nb + 63) / 64), dim3(64), 0, ctx->stream, view_of(ks), T, (const int *)ks->work, (const int *)ks->ntot);
+    const int nb = kpset_grid_bound(ks, n_bound);
+    hipLaunchKernelGGL(k_kpset_tri_temporal, dim3((nb + 63) / 64), dim3(64), 0, ctx->stream, ks->v, T, (const int *)ks->work, (const int *)ks->ntot);
     HIP_TRY(ctx, hipGetLastError());
     rc = kpset_compact(ctx, ks, 1, T.flags);
     if (rc) return rc;
@@ -696,22 +680,19 @@ int slam_kpset_frame_stats(slam_ctx *ctx, slam_kpset *ks, const double *params, 
     A.words = (int)((cells + 31) / 32);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (!ks->kf_stats) HIP_TRY(ctx, hipMalloc((void **)&ks->kf_stats, (size_t)S * SLAM_KF_STATS * 8));
-    if (ks->cap > KF_TERMS_LDS && !ks->kf_terms) HIP_TRY(ctx, hipMalloc((void **)&ks->kf_terms, (size_t)S * ks->cap * 8));
-    int rc = kpset_stage_params(ctx, ks, params, (size_t)S * 32, &A.par);
+    if (ks->v.cap > KF_TERMS_LDS && !ks->kf_terms) HIP_TRY(ctx, hipMalloc((void **)&ks->kf_terms, (size_t)S * ks->v.cap * 8));
+    int rc = kpset_stage_params(ctx, ks, params, (size_t)S * KP_PAR, &A.par);
     if (rc) return rc;
-    A.yx = ks->yx; A.kyx = ks->kyx; A.is3d = ks->is3d; A.stereo = ks->stereo; A.haskf = ks->haskf; A.count = ks->count; A.cap = ks->cap;
+    A.yx = ks->v.yx; A.kyx = ks->v.kyx; A.is3d = ks->v.is3d; A.stereo = ks->v.stereo; A.haskf = ks->v.haskf; A.count = ks->v.count; A.cap = ks->v.cap;
     A.flags = flags; A.cell = cell_size; A.terms = ks->kf_terms; A.out = stats_dev ? stats_dev : ks->kf_stats;
     { ProfScope span(ctx, "kpset_frame_stats");
       hipLaunchKernelGGL(k_kpset_frame_stats, dim3(S), dim3(256), (size_t)A.words * 4, ctx->stream, A); }
     HIP_TRY(ctx, hipGetLastError());
     if (!stats) return SLAM_OK;
-    void *h;
-    rc = slam_pinned(ctx, std::max<size_t>(256, (size_t)S * SLAM_KF_STATS * 8), &h);
+    char *h;
+    rc = slam_pinned(ctx, std::max<size_t>(256, (size_t)S * SLAM_KF_STATS * 8), (void **)&h);
     if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(h, A.out, (size_t)S * SLAM_KF_STATS * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, slam_stream_wait(ctx->stream));
-    memcpy(stats, h, (size_t)S * SLAM_KF_STATS * 8);
-    return SLAM_OK;
+    return kpset_read_back(ctx, h, {{0, A.out, (size_t)S * SLAM_KF_STATS * 8, stats}});
 }
 
 // check_new_kf_required for S streams on those statistics (kf_host.hpp): host arithmetic only, no context

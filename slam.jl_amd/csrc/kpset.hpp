@@ -1,0 +1,64 @@
+// kpset.hpp -- the device-resident keypoint lists (slam_kpset, kpset.hip): the one definition of a keypoint's record, of the set, of the
+// per-stream parameter slot, and the plumbing the files that touch a set share (kpset.hip, lk.hip, detect.hip, pose.hip, fivepoint.hip).
+#pragma once
+#include "common.hpp"
+#include <initializer_list>
+
+// The per-keypoint arrays of S lock-stepped streams: stream s owns the slots [s * cap, s * cap + count[s]) of every
+// array.  Passed by value to k_kpset_compact, k_kpset_keyframe, detect_append and both triangulation kernels: the order of the
+// members is their kernel-argument layout.  A new field goes here, into kpset_regions and into the load and the store block of
+// k_kpset_compact (both kpset.hip; tests/test_gpu_kpset_record.py carries every field through both compaction modes).
+struct KpsetView {
+    double *yx;                  // [S cap][2] pixel (y, x) in the current left image
+    double *oyx;                 // [S cap][2] positions returned by the last temporal match (scratch)
+    double *syx;                 // [S cap][2] stereo pixel (right image), valid where stereo != 0
+    double *xyz;                 // [S cap][3] map point, valid where is3d != 0
+    double *kyx;                 // [S cap][2] pixel (y, x) in the previous key-frame, valid where haskf != 0 (slam_kpset_keyframe)
+    double *fyx;                 // [S cap][2] pixel (y, x) in the FIRST key-frame that observed the keypoint (the one that detected it)
+    int64_t *id;                 // [S cap] keypoint id (per stream, ascending in creation order)
+    uint8_t *is3d, *stereo, *st, *haskf;   // [S cap] flags; st: status of the last match (0 lost, 1 tracked, 2 skipped); haskf: the previous key-frame observes the keypoint
+    int *fkf;                    // [S cap] id of the first key-frame (per-stream counter), valid where haskf != 0
+    int *kfcount;                // [S] number of key-frames created so far = id of the next one
+    int *count;                  // [S] list lengths
+    int cap;
+};
+
+// The per-stream parameters of a call: KP_PAR doubles per stream, staged by kpset_stage_params (keypoint_set.py restates the numbers).
+//   [0 .. 15]                     Tcw of the target camera, column-major 4 x 4: the pose prior of a match (k_kpset_match, prior 1)
+//   [0 .. 8]                      or R_compensation, dense column-major 3 x 3: k_kfive_gather, k_kpset_frame_stats
+//   [KP_PAR_CAM .. + 3]           fx fy cx cy: k_kpset_match, k_kpose_gather, k_kpose_prep and the host's K of slam_kpset_compute_pose, k_kfive_gather, k_kpset_tri_temporal, k_kpset_frame_stats
+//   [KP_PAR_DIST .. + 3]          k1 k2 p1 p2: the same kernels but k_kpose_prep
+//   [KP_PAR_SHIFT, + 1]           prior shift (y, x): k_kpset_match, prior 2
+constexpr int KP_PAR = 32, KP_PAR_CAM = 16, KP_PAR_DIST = 20, KP_PAR_SHIFT = 24;
+__device__ __forceinline__ void load_cam(const double *par, double *cam, double *dist) { for (int k = 0; k < 4; k++) { cam[k] = par[KP_PAR_CAM + k]; dist[k] = par[KP_PAR_DIST + k]; } }
+
+// The set: the lists (v) and what is not per-keypoint state of them; all arrays but the kf_* ones live in one allocation.
+struct slam_kpset {
+    int device = 0, S = 0;
+    char *base = nullptr;
+    KpsetView v = {};
+    int *work = nullptr;         // [S cap] live slots, streams back to back (each stream's segment in the order of work_order.hpp)
+    int sort_pad = 0;            // power of two >= cap the work list's sort pads a segment to; 0: slot order (decided at creation)
+    int *ntot = nullptr;         // [4]: number of live slots, ...
+    int64_t *next_id = nullptr;  // [S]
+    // per-stream parameters of a call (prior shift / pose): ring of 8 slots of S x KP_PAR doubles, staged through pinned host
+    // memory with an event per slot, so that the enqueue-only calls never wait for an earlier call's copy
+    double *par = nullptr, *par_host = nullptr;
+    hipEvent_t par_ev[8] = {};
+    int par_slot = 0;
+    // slam_kpset_frame_stats (allocations of their own, made by its first call): the S x 8 results when the caller passes no buffer, and
+    // S x cap parallax terms for the streams whose terms do not fit the kernel's LDS array (only for cap > that array)
+    double *kf_stats = nullptr;
+    unsigned long long *kf_terms = nullptr;
+};
+
+// ---- plumbing (kpset.hip) --------------------------------------------------------------------------------------------------------------
+// stage `n` doubles (<= S x KP_PAR) of per-stream parameters into the next ring slot; returns the device pointer
+int kpset_stage_params(slam_ctx *ctx, slam_kpset *ks, const double *host, size_t n, const double **dev_out);
+int kpset_build_worklist(slam_ctx *ctx, slam_kpset *ks, int H, int W);   // H <= 0: slot order (no image, or an order would not pay)
+int kpset_compact(slam_ctx *ctx, slam_kpset *ks, int mode, const uint8_t *flags_dev);
+// the number of keypoints a launch over the work list is sized for: the host's bound of the live slots where it has one, else S x cap
+inline int kpset_grid_bound(const slam_kpset *ks, int n_bound) { const int nmax = ks->S * ks->v.cap; return n_bound > 0 && n_bound < nmax ? n_bound : nmax; }
+// the tail of a seam that returns results: `bytes` from `dev` to h + at (a region of the caller's Layout in its pinned block), one wait, then on into `out` (skipped where null)
+struct KpReadBack { size_t at; const void *dev; size_t bytes; void *out; };
+int kpset_read_back(slam_ctx *ctx, char *h, std::initializer_list<KpReadBack> parts);

@@ -15,7 +15,7 @@
 // folded with a 6-step xor butterfly (wave_sum2: m = 32, 16, 1, 2, 4, 8).  That summation order is restated in the
 // CPU oracle (sum_order = 1) and is bit-reproducible; it differs from the
 // reference's single-accumulator order only in rounding (<= 1e-12 px observed).
-#include "common.hpp"
+#include "kpset.hpp"
 #include "geom_device.hpp"
 #include "work_order.hpp"
 #include <vector>
@@ -550,8 +550,8 @@ __global__ __launch_bounds__(64) LK_OCC void k_flow_match(FlowArgs F)
 //   stereo (stereo = true): a 3-D keypoint projected outside the right image loses its observation (st = 0); a match must
 //     pass maybe_stereo_update! (:579-590: |row - undistorted right row| <= epipolar_error) and is stored as
 //     (left row, right column) in syx with stereo = 1; the keypoint itself always stays (st = 2).
-// Per-stream parameters (32 doubles per stream, staged by the host): [0..15] Tcw of the TARGET camera (column-major),
-// [16..19] fx fy cx cy, [20..23] k1 k2 p1 p2 of the target camera, [24..25] prior shift (y, x).
+// Per-stream parameters (KP_PAR doubles per stream, staged by the host; layout in kpset.hpp): Tcw, intrinsics and distortion are the
+// TARGET camera's.
 struct KpMatchArgs {
     PyrView from, to; size_t zs_from, zs_to;
     LKTune tune;
@@ -573,7 +573,7 @@ __global__ __launch_bounds__(64) LK_OCC void k_kpset_match(KpMatchArgs M)
     if (idx >= ntot) break;
     const size_t q = (size_t)M.work[idx];
     const int s = (int)(q / M.cap);
-    const double *P = M.par + 32 * (size_t)s;
+    const double *P = M.par + KP_PAR * (size_t)s, *cam = P + KP_PAR_CAM, *dist = P + KP_PAR_DIST;
     const double py = M.yx[2 * q], px = M.yx[2 * q + 1];
     const bool is3 = M.is3d[q] != 0;
     double pry = py, prx = px;
@@ -583,8 +583,8 @@ __global__ __launch_bounds__(64) LK_OCC void k_kpset_match(KpMatchArgs M)
             const double cx = ((P[0] * X0 + P[4] * X1) + P[8] * X2) + P[12];
             const double cy = ((P[1] * X0 + P[5] * X1) + P[9] * X2) + P[13];
             const double cz = ((P[2] * X0 + P[6] * X1) + P[10] * X2) + P[14];
-            pdn_to_pixel(P + 16, P + 20, cy / cz, cx / cz, pry, prx);                  // project_undistort (camera.jl:79-82)
-        } else if (M.prior == 2) { pry = py + P[24]; prx = px + P[25]; }
+            pdn_to_pixel(cam, dist, cy / cz, cx / cz, pry, prx);                  // project_undistort (camera.jl:79-82)
+        } else if (M.prior == 2) { pry = py + P[KP_PAR_SHIFT]; prx = px + P[KP_PAR_SHIFT + 1]; }
     }
     const bool inside = 1 <= pry && pry <= (double)M.H && 1 <= prx && prx <= (double)M.W;   // in_image (camera.jl:90-92)
     const bool lane0 = (threadIdx.x & 63) == 0;
@@ -609,7 +609,7 @@ __global__ __launch_bounds__(64) LK_OCC void k_kpset_match(KpMatchArgs M)
     } else if (lane0) {
         if (ok) {                                                                                    // maybe_stereo_update!
             double uy, ux;
-            pdn_to_pixel(P + 16, P + 20, (ny - P[19]) / P[17], (nx - P[18]) / P[16], uy, ux);      // undistort_point (camera.jl:98-103)
+            undistort_px(cam, dist, ny, nx, uy, ux);                                                 // undistort_point (camera.jl:98-103)
             if (fabs(py - uy) > M.epipolar) ok = false;
         }
         if (ok) { M.syx[2 * q] = py; M.syx[2 * q + 1] = nx; }
@@ -652,16 +652,16 @@ static int kpset_match(slam_ctx *ctx, slam_kpset *ks, const slam_pyr *from0, con
     KpMatchArgs M;
     M.from = from0->view; M.to = to0->view; M.zs_from = from0->zstride; M.zs_to = to0->zstride;
     M.tune = t;
-    M.yx = ks->yx; M.oyx = ks->oyx; M.syx = ks->syx; M.xyz = ks->xyz; M.is3d = ks->is3d; M.st = ks->st; M.stereo = ks->stereo; M.cap = ks->cap;
+    const KpsetView &v = ks->v;
+    M.yx = v.yx; M.oyx = v.oyx; M.syx = v.syx; M.xyz = v.xyz; M.is3d = v.is3d; M.st = v.st; M.stereo = v.stereo; M.cap = v.cap;
     M.work = ks->work; M.ntot = ks->ntot; M.prior = prior; M.H = from0->H[0]; M.W = from0->W[0]; M.stereo_mode = stereo_mode; M.epipolar = epipolar;
     std::vector<double> zero;
-    if (!params) { zero.assign((size_t)ks->S * 32, 0.0); for (int s = 0; s < ks->S; s++) { zero[32 * s + 16] = zero[32 * s + 17] = 1.0; } params = zero.data(); }
-    rc = kpset_stage_params(ctx, ks, params, (size_t)ks->S * 32, &M.par);
+    if (!params) { zero.assign((size_t)ks->S * KP_PAR, 0.0); for (int s = 0; s < ks->S; s++) { zero[KP_PAR * s + KP_PAR_CAM] = zero[KP_PAR * s + KP_PAR_CAM + 1] = 1.0; } params = zero.data(); }
+    rc = kpset_stage_params(ctx, ks, params, (size_t)ks->S * KP_PAR, &M.par);
     if (rc) return rc;
     rc = kpset_build_worklist(ctx, ks, M.H, M.W);
     if (rc) return rc;
-    const int nmax = ks->S * ks->cap;
-    int nb = n_bound > 0 && n_bound < nmax ? n_bound : nmax;
+    int nb = kpset_grid_bound(ks, n_bound);
     // (measurement knob) cap the launch: every wave then walks several keypoints (the kernel loops) instead of one wave being dispatched per keypoint
     static const int grid_cap = [] { const char *v = getenv("SLAMHIP_LK_GRID"); return v ? atoi(v) : 0; }();
     if (grid_cap > 0 && nb > grid_cap) nb = grid_cap;
@@ -677,7 +677,7 @@ static int kpset_match(slam_ctx *ctx, slam_kpset *ks, const slam_pyr *from0, con
 }
 
 // optical_flow_matching!(map_manager, frame, from, to, false) for the S streams of the set (enqueue only).
-// params: S x 32 doubles (layout above) or NULL (prior 0); n_bound: an upper bound of the number of live keypoints known to the
+// params: S x KP_PAR doubles (kpset.hpp) or NULL (prior 0); n_bound: an upper bound of the number of live keypoints known to the
 // host (sizes the launch; <= 0: S x cap)
 extern "C" int slam_kpset_flow_match(slam_ctx *ctx, slam_kpset *ks, const slam_pyr *from0, const slam_pyr *to0, const double *params, int prior,
                                      int pyramid_levels, int pyramid_levels_3d, int window, int iterations, double eig_thr, double eps,

@@ -7,7 +7,7 @@
 // ties to the lower iteration then solution), writes its inlier mask, the summed inlier error (index order) and
 // K [R | t].  Inputs/outputs live in the context's mapped pinned block (a few tens of KB), scores in device scratch.
 // The work is ~iters x 4 x n reprojections (256 x 4 x 1000 = 1 M): launch- and latency-bound, not HBM-bound.
-#include "common.hpp"
+#include "kpset.hpp"
 #include "geom_device.hpp"
 #include <cmath>
 
@@ -408,7 +408,7 @@ extern "C" int slam_p3p_ransac_batch(slam_ctx *ctx, int S, const int32_t *offset
 // =====================================================================================================================
 struct KPoseArgs {
     const double *yx, *xyz; const uint8_t *is3d; const int *count; int cap;   // the set
-    const double *par;                 // S x 32: [16..19] fx fy cx cy, [20..23] k1 k2 p1 p2
+    const double *par;                 // S x KP_PAR (kpset.hpp)
     double *pts, *px, *pdn; int *slot; int *n3;                                // gathered 3-D keypoints, stride cap per stream
     int32_t *samples; int iters; unsigned long long seed;
     double *p3p_out; uint8_t *inl;     // k_p3p_select's outputs (S x 32 doubles; stride cap)
@@ -423,8 +423,8 @@ __global__ __launch_bounds__(256) void k_kpose_gather(KPoseArgs A)
     __shared__ int s_w[4], s_base;
     const int z = blockIdx.x, tid = threadIdx.x, n = A.count[z];
     const size_t b = (size_t)z * A.cap;
-    const double *par = A.par + 32 * (size_t)z;
-    const double cam[4] = {par[16], par[17], par[18], par[19]}, dist[4] = {par[20], par[21], par[22], par[23]};
+    double cam[4], dist[4];
+    load_cam(A.par + KP_PAR * (size_t)z, cam, dist);
     if (tid == 0) s_base = 0;
     __syncthreads();
     for (int c0 = 0; c0 < n; c0 += 256) {
@@ -495,7 +495,7 @@ __global__ __launch_bounds__(256) void k_kpose_prep(KPoseArgs A)
     __syncthreads();
     if (tid == 0) {
         PnPArgs P;
-        P.cam = {A.par[32 * z + 16], A.par[32 * z + 17], A.par[32 * z + 18], A.par[32 * z + 19]};
+        const double *cam = A.par + KP_PAR * z + KP_PAR_CAM; P.cam = {cam[0], cam[1], cam[2], cam[3]};
         P.px = A.bpx + 2 * b; P.pts = A.bpts + 3 * b; P.n = ok ? s_base : 0;
         P.iters_fast = A.iters_fast; P.iterations = A.iterations; P.depth_eps = A.depth_eps; P.repr_eps = A.repr_eps;
         P.outl = A.outl + b; P.result = A.res + 16 * (size_t)z;
@@ -538,7 +538,7 @@ extern "C" int slam_kpset_compute_pose(slam_ctx *ctx, slam_kpset *ks, const doub
 {
     ARG_TRY(ctx, ctx != nullptr && ks != nullptr && params != nullptr && iters > 0 && poses_cw && status);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const int S = ks->S, cap = ks->cap;
+    const int S = ks->S, cap = ks->v.cap;
     const size_t nc = (size_t)S * cap;
     Layout D;                          // device scratch
     const size_t o_pts = D.take(nc * 24), o_px = D.take(nc * 16), o_pdn = D.take(nc * 24), o_slot = D.take(nc * 4), o_n3 = D.take((size_t)S * 4);
@@ -553,10 +553,10 @@ extern "C" int slam_kpset_compute_pose(slam_ctx *ctx, slam_kpset *ks, const doub
     int rc = slam_scratch2(ctx, D.size(), (void **)&scr);
     if (rc) return rc;
     const double *par_dev;
-    rc = kpset_stage_params(ctx, ks, params, (size_t)S * 32, &par_dev);
+    rc = kpset_stage_params(ctx, ks, params, (size_t)S * KP_PAR, &par_dev);
     if (rc) return rc;
     KPoseArgs A;
-    A.yx = ks->yx; A.xyz = ks->xyz; A.is3d = ks->is3d; A.count = ks->count; A.cap = cap; A.par = par_dev;
+    A.yx = ks->v.yx; A.xyz = ks->v.xyz; A.is3d = ks->v.is3d; A.count = ks->v.count; A.cap = cap; A.par = par_dev;
     A.pts = (double *)(scr + o_pts); A.px = (double *)(scr + o_px); A.pdn = (double *)(scr + o_pdn); A.slot = (int *)(scr + o_slot); A.n3 = (int *)(scr + o_n3);
     A.samples = (int32_t *)(scr + o_smp); A.iters = iters; A.seed = seed;
     A.p3p_out = (double *)(scr + o_out); A.inl = (uint8_t *)(scr + o_inl);
@@ -576,7 +576,7 @@ extern "C" int slam_kpset_compute_pose(slam_ctx *ctx, slam_kpset *ks, const doub
     for (int z = 0; z < S; z++) {
         double *K = (double *)(h + h_K) + 9 * z;
         for (int j = 0; j < 9; j++) K[j] = 0.0;
-        K[0] = params[32 * z + 16]; K[4] = params[32 * z + 17]; K[6] = params[32 * z + 18]; K[7] = params[32 * z + 19]; K[8] = 1.0;
+        const double *cam = params + KP_PAR * z + KP_PAR_CAM; K[0] = cam[0]; K[4] = cam[1]; K[6] = cam[2]; K[7] = cam[3]; K[8] = 1.0;
     }
     HIP_TRY(ctx, hipHostGetDevicePointer((void **)&T.Ks, h + h_K, 0));
     HIP_TRY(ctx, hipMemsetAsync(A.flags, 0, nc, ctx->stream));
@@ -592,14 +592,6 @@ extern "C" int slam_kpset_compute_pose(slam_ctx *ctx, slam_kpset *ks, const doub
     rc = kpset_compact(ctx, ks, 1, A.flags);
     if (rc) return rc;
     // results: poses, status, inlier counts, list lengths -- one wait
-    HIP_TRY(ctx, hipMemcpyAsync(h + h_T, A.poses, (size_t)S * 128, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(h + h_st, A.status, (size_t)S * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(h + h_ni, A.ninl, (size_t)S * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(h + h_cn, ks->count, (size_t)S * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, slam_stream_wait(ctx->stream));
-    memcpy(poses_cw, h + h_T, (size_t)S * 128);
-    memcpy(status, h + h_st, (size_t)S * 4);
-    if (n_inliers) memcpy(n_inliers, h + h_ni, (size_t)S * 4);
-    if (counts) memcpy(counts, h + h_cn, (size_t)S * 4);
-    return SLAM_OK;
+    return kpset_read_back(ctx, h, {{h_T, A.poses, (size_t)S * 128, poses_cw}, {h_st, A.status, (size_t)S * 4, status}, {h_ni, A.ninl, (size_t)S * 4, n_inliers},
+                                    {h_cn, ks->v.count, (size_t)S * 4, counts}});
 }

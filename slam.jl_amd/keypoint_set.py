@@ -11,20 +11,37 @@ from . import _lib as L
 from .optical_flow import _check_match, _tune
 
 
+# the per-stream parameter slot of csrc/kpset.hpp (tests/test_keypoint_set_host.py keeps the two in step)
+KP_PAR, KP_PAR_CAM, KP_PAR_DIST, KP_PAR_SHIFT = 32, 16, 20, 24
+
+
 def stream_params(S, Tcw=None, cam=None, dist=None, shift_yx=None):
-    """S x 32 per-stream call parameters: [0..15] Tcw (column-major), [16..19] fx fy cx cy, [20..23] k1 k2 p1 p2, [24..25] shift."""
-    p = np.zeros((S, 32))
-    p[:, 16:18] = 1.0
+    """S x KP_PAR per-stream call parameters: [0..15] Tcw (column-major), fx fy cx cy at KP_PAR_CAM, k1 k2 p1 p2 at KP_PAR_DIST, the prior shift (y, x) at KP_PAR_SHIFT."""
+    p = np.zeros((S, KP_PAR))
+    p[:, KP_PAR_CAM:KP_PAR_CAM + 2] = 1.0
     if Tcw is not None:
         T = np.asarray(Tcw, dtype=np.float64).reshape(-1, 4, 4)
         p[:, :16] = np.broadcast_to(T, (S, 4, 4)).transpose(0, 2, 1).reshape(S, 16)       # column-major
     if cam is not None:
-        p[:, 16:20] = np.asarray(cam, dtype=np.float64)
+        p[:, KP_PAR_CAM:KP_PAR_CAM + 4] = np.asarray(cam, dtype=np.float64)
     if dist is not None:
-        p[:, 20:24] = np.asarray(dist, dtype=np.float64)
+        p[:, KP_PAR_DIST:KP_PAR_DIST + 4] = np.asarray(dist, dtype=np.float64)
     if shift_yx is not None:
-        p[:, 24:26] = np.asarray(shift_yx, dtype=np.float64).reshape(-1, 2)
+        p[:, KP_PAR_SHIFT:KP_PAR_SHIFT + 2] = np.asarray(shift_yx, dtype=np.float64).reshape(-1, 2)
     return np.ascontiguousarray(p)
+
+
+def _with_rcomp(sp, S):
+    """a copy of sp with R_compensation as the seams read it, a dense column-major 3 x 3 at [0..8]: repacked from the 4 x 4 Tcw slot (column-major, stride 4)"""
+    sp = np.ascontiguousarray(sp, dtype=np.float64).reshape(S, KP_PAR).copy()
+    sp[:, :9] = sp[:, :16].reshape(S, 4, 4)[:, :3, :3].reshape(S, 9)            # [col][row]
+    return sp
+
+
+def _sp_ptr(stream_params_):
+    """(array kept alive, pointer or None) of a match's optional stream parameters"""
+    sp = None if stream_params_ is None else np.ascontiguousarray(stream_params_, dtype=np.float64)
+    return sp, (L.ptr(sp) if sp is not None else None)
 
 
 class KeypointSet:
@@ -47,6 +64,13 @@ class KeypointSet:
             pass
 
     # ---- host <-> device (initialisation, tests, host consumers) ----
+    def _fetch(self, call, *spec):
+        """one download seam: cap-long outputs of the (trailing shape, pointer type) in `spec`, call(pointers..., cap, byref(n)), trimmed to n"""
+        out = [np.zeros((self.cap,) + shape, dtype=np.dtype(t._type_)) for shape, t in spec]
+        n = C.c_int(0)
+        call(*[L.ptr(a, t) for a, (_, t) in zip(out, spec)], self.cap, C.byref(n))
+        return [a[:n.value].copy() for a in out]
+
     def upload(self, s, yx, is_3d, xyz=None, ids=None, ctx=None):
         c = ctx or self.ctx
         yx = np.ascontiguousarray(yx, dtype=np.float64).reshape(-1, 2)
@@ -59,14 +83,9 @@ class KeypointSet:
     def download(self, s, ctx=None):
         """dict(yx, is_3d, xyz, ids, stereo_yx, has_stereo) of stream s"""
         c = ctx or self.ctx
-        cap = self.cap
-        yx = np.empty((cap, 2)); f = np.empty(cap, np.uint8); xyz = np.empty((cap, 3)); ids = np.empty(cap, np.int64)
-        syx = np.empty((cap, 2)); hs = np.empty(cap, np.uint8); n = C.c_int(0)
-        c.check(c.lib.slam_kpset_download(c.h, self.h, s, L.ptr(yx), L.ptr(f, L.u8p), L.ptr(xyz), L.ptr(ids, L.i64p), L.ptr(syx),
-                                          L.ptr(hs, L.u8p), cap, C.byref(n)))
-        k = n.value
-        return dict(yx=yx[:k].copy(), is_3d=f[:k].astype(bool), xyz=xyz[:k].copy(), ids=ids[:k].copy(), stereo_yx=syx[:k].copy(),
-                    has_stereo=hs[:k].astype(bool))
+        yx, f, xyz, ids, syx, hs = self._fetch(lambda *a: c.check(c.lib.slam_kpset_download(c.h, self.h, s, *a)),
+                                               ((2,), L.f64p), ((), L.u8p), ((3,), L.f64p), ((), L.i64p), ((2,), L.f64p), ((), L.u8p))
+        return dict(yx=yx, is_3d=f.astype(bool), xyz=xyz, ids=ids, stereo_yx=syx, has_stereo=hs.astype(bool))
 
     def counts(self, ctx=None):
         """the S list lengths: the one small device -> host copy of a step (synchronises the context's stream)"""
@@ -78,16 +97,16 @@ class KeypointSet:
     # ---- enqueue-only calls ----
     def flow_match(self, from_batch, to_batch, params, stream_params_=None, prior=0, pyramid_levels_3d=1, iterations=30, n_bound=0, ctx=None):
         c = ctx or self.ctx
-        sp = None if stream_params_ is None else np.ascontiguousarray(stream_params_, dtype=np.float64)
-        rc = c.lib.slam_kpset_flow_match(c.h, self.h, from_batch.pyramids[0].h, to_batch.pyramids[0].h, L.ptr(sp) if sp is not None else None,
+        sp, sp_ptr = _sp_ptr(stream_params_)
+        rc = c.lib.slam_kpset_flow_match(c.h, self.h, from_batch.pyramids[0].h, to_batch.pyramids[0].h, sp_ptr,
                                          prior, *_tune(params, pyramid_levels_3d, iterations), int(n_bound))
         _check_match(c, rc)
 
     def stereo_match(self, left_batch, right_batch, params, stream_params_=None, prior=0, pyramid_levels_3d=1, iterations=30,
                      epipolar_error=2.0, n_bound=0, ctx=None):
         c = ctx or self.ctx
-        sp = None if stream_params_ is None else np.ascontiguousarray(stream_params_, dtype=np.float64)
-        rc = c.lib.slam_kpset_stereo_match(c.h, self.h, left_batch.pyramids[0].h, right_batch.pyramids[0].h, L.ptr(sp) if sp is not None else None,
+        sp, sp_ptr = _sp_ptr(stream_params_)
+        rc = c.lib.slam_kpset_stereo_match(c.h, self.h, left_batch.pyramids[0].h, right_batch.pyramids[0].h, sp_ptr,
                                            prior, *_tune(params, pyramid_levels_3d, iterations), float(epipolar_error), int(n_bound))
         _check_match(c, rc)
 
@@ -138,9 +157,8 @@ class KeypointSet:
 
     def download_keyframe(self, s, ctx=None):
         c = ctx or self.ctx
-        k = np.zeros((self.cap, 2)); f = np.zeros(self.cap, dtype=np.uint8); n = C.c_int(0)
-        c.check(c.lib.slam_kpset_download_keyframe(c.h, self.h, s, L.ptr(k), L.ptr(f, L.u8p), self.cap, C.byref(n)))
-        return k[:n.value].copy(), f[:n.value].astype(bool)
+        k, f = self._fetch(lambda *a: c.check(c.lib.slam_kpset_download_keyframe(c.h, self.h, s, *a)), ((2,), L.f64p), ((), L.u8p))
+        return k, f.astype(bool)
 
     def upload_first(self, s, first_yx, first_kf, kf_count, ctx=None):
         c = ctx or self.ctx
@@ -151,9 +169,9 @@ class KeypointSet:
     def download_first(self, s, ctx=None):
         """(first_yx, first_kf, key-frame counter) of stream s: where and by which key-frame each keypoint was first observed"""
         c = ctx or self.ctx
-        f = np.zeros((self.cap, 2)); k = np.zeros(self.cap, dtype=np.int32); n = C.c_int(0); kc = C.c_int(0)
-        c.check(c.lib.slam_kpset_download_first(c.h, self.h, s, L.ptr(f), L.ptr(k, L.i32p), self.cap, C.byref(n), C.byref(kc)))
-        return f[:n.value].copy(), k[:n.value].copy(), kc.value
+        kc = C.c_int(0)
+        f, k = self._fetch(lambda *a: c.check(c.lib.slam_kpset_download_first(c.h, self.h, s, *a, C.byref(kc))), ((2,), L.f64p), ((), L.i32p))
+        return f, k, kc.value
 
     def triangulate_temporal(self, sp, kf_cw, Twc, kf_cur, kf_lo=None, max_error=3.0, min_depth=0.1, min_parallax=20.0, n_bound=0, ctx=None):
         """triangulate_temporal! (mapper.jl:185-262) on the lists (slam_kpset_triangulate_temporal).  kf_cw: (S, nkf, 4, 4) world ->
@@ -161,7 +179,7 @@ class KeypointSet:
         kf_cur: (S,) the frame's key-frame id; kf_lo: (S,) oldest id still in the table (default kf_cur - nkf + 1).  The per-observer
         matrices of mapper.jl:226-231 are formed here (numpy), as the Julia caller would form them."""
         c = ctx or self.ctx
-        sp = np.ascontiguousarray(sp, dtype=np.float64).reshape(self.S, 32)
+        sp = np.ascontiguousarray(sp, dtype=np.float64).reshape(self.S, KP_PAR)
         kf_cw = np.asarray(kf_cw, dtype=np.float64).reshape(self.S, -1, 4, 4)
         nkf = kf_cw.shape[1]
         Twc = np.broadcast_to(np.asarray(Twc, dtype=np.float64).reshape(-1, 4, 4), (self.S, 4, 4))
@@ -169,7 +187,7 @@ class KeypointSet:
         kf_lo = np.ascontiguousarray(np.maximum(kf_cur - nkf + 1, 0) if kf_lo is None else np.broadcast_to(np.asarray(kf_lo, dtype=np.int32), (self.S,)), dtype=np.int32)
         tab = np.zeros((self.S, nkf, 4, 16))
         for s in range(self.S):
-            fx, fy, cx, cy = sp[s, 16:20]
+            fx, fy, cx, cy = sp[s, KP_PAR_CAM:KP_PAR_CAM + 4]
             K4 = np.array([[fx, 0, cx, 0], [0, fy, cy, 0], [0, 0, 1, 0], [0, 0, 0, 1.0]])
             for k in range(nkf):
                 rel = kf_cw[s, k] @ Twc[s]                                # observer_kf.cw * frame.wc
@@ -186,10 +204,7 @@ class KeypointSet:
         after the removals (S,)).  sp: stream_params(...) with R_compensation in the rotation part of the Tcw slot (rows / columns
         0..2) and the camera / distortion entries filled."""
         c = ctx or self.ctx
-        sp = np.ascontiguousarray(sp, dtype=np.float64).reshape(self.S, 32).copy()
-        # the seam reads R_compensation as a dense column-major 3 x 3 at [0..8]: repack from the 4 x 4 slot (column-major, stride 4)
-        T = sp[:, :16].reshape(self.S, 4, 4)                                       # [col][row]
-        sp[:, :9] = T[:, :3, :3].reshape(self.S, 9)
+        sp = _with_rcomp(sp, self.S)
         if not fetch:                                            # enqueue only: the filter acts on the lists, nothing comes back
             c.check(c.lib.slam_kpset_compute_pose_5pt(c.h, self.h, L.ptr(sp), float(min_parallax), float(max_repr_error), int(iters),
                                                       int(seed) & 0xFFFFFFFFFFFFFFFF, None, None, None, None, None))
@@ -209,9 +224,7 @@ class KeypointSet:
         Tcw slot, camera / distortion filled); shape = (height, width) of the image.  The call is the step's one device -> host copy;
         fetch=False only enqueues (results in stats_dev_ptr, a device pointer to S x 8 doubles, or in a buffer of the set) and returns None."""
         c = ctx or self.ctx
-        sp = np.ascontiguousarray(sp, dtype=np.float64).reshape(self.S, 32).copy()
-        T = sp[:, :16].reshape(self.S, 4, 4)                                       # [col][row], repacked as compute_pose_5pt does
-        sp[:, :9] = T[:, :3, :3].reshape(self.S, 9)
+        sp = _with_rcomp(sp, self.S)
         out = np.zeros((self.S, 8)) if fetch else None
         c.check(c.lib.slam_kpset_frame_stats(c.h, self.h, L.ptr(sp), int(flags), int(cell_size), int(shape[0]), int(shape[1]),
                                              C.c_void_p(stats_dev_ptr) if stats_dev_ptr else None, L.ptr(out) if fetch else None))
@@ -223,7 +236,7 @@ class KeypointSet:
         sp: stream_params(...) with the camera / distortion entries filled; repr_eps defaults to `threshold`
         (max_reprojection_error on both, front_end.jl:166,206)."""
         c = ctx or self.ctx
-        sp = np.ascontiguousarray(sp, dtype=np.float64).reshape(self.S, 32)
+        sp = np.ascontiguousarray(sp, dtype=np.float64).reshape(self.S, KP_PAR)
         poses = np.zeros((self.S, 16)); status = np.zeros(self.S, dtype=np.int32); ninl = np.zeros(self.S, dtype=np.int32)
         counts = np.zeros(self.S, dtype=np.int32)
         c.check(c.lib.slam_kpset_compute_pose(c.h, self.h, L.ptr(sp), float(threshold), int(iters), int(seed) & 0xFFFFFFFFFFFFFFFF,
@@ -258,16 +271,13 @@ def _splitmix64(x):
     return x ^ (x >> 31)
 
 
-def pose_samples(seed, stream, n, iters):
-    """The triples slam_kpset_compute_pose draws for stream `stream` with `n` 3-D keypoints (csrc/pose.hip, k_kpose_samples):
-    three distinct indices per iteration, splitmix64(seed ^ stream << 48 ^ iteration << 16 ^ attempt) mod n; -1 when n < 5."""
-    out = np.full((iters, 3), -1, dtype=np.int32)
-    if n < 5:
-        return out
+def _samples(seed, stream, n, iters, k):
+    """iters x k: k distinct indices below n per iteration, splitmix64(seed ^ stream << 48 ^ iteration << 16 ^ attempt) mod n (draw_distinct, csrc/geom_device.hpp)"""
+    out = np.full((iters, k), -1, dtype=np.int32)
     for it in range(iters):
         att = 0
         idx = []
-        while len(idx) < 3:
+        while len(idx) < k:
             h = _splitmix64((int(seed) ^ (int(stream) << 48) ^ (it << 16) ^ att) & 0xFFFFFFFFFFFFFFFF)
             att += 1
             c = int(h % n)
@@ -275,22 +285,16 @@ def pose_samples(seed, stream, n, iters):
                 idx.append(c)
         out[it] = idx
     return out
+
+
+def pose_samples(seed, stream, n, iters):
+    """The triples slam_kpset_compute_pose draws for stream `stream` with `n` 3-D keypoints (csrc/pose.hip, k_kpose_samples); -1 when n < 5."""
+    return np.full((iters, 3), -1, dtype=np.int32) if n < 5 else _samples(seed, stream, n, iters, 3)
 
 
 def pose_samples5(seed, stream, n, iters):
     """The 5-tuples slam_kpset_compute_pose_5pt draws (csrc/fivepoint.hip, k_kfive_samples): as pose_samples, five distinct indices."""
-    out = np.full((iters, 5), -1, dtype=np.int32)
-    for it in range(iters):
-        att = 0
-        idx = []
-        while len(idx) < 5:
-            h = _splitmix64((int(seed) ^ (int(stream) << 48) ^ (it << 16) ^ att) & 0xFFFFFFFFFFFFFFFF)
-            att += 1
-            c = int(h % n)
-            if c not in idx:
-                idx.append(c)
-        out[it] = idx
-    return out
+    return _samples(seed, stream, n, iters, 5)
 
 
 def pose_5pt_inputs(cam, dist, yx, kyx):

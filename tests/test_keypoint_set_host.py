@@ -45,3 +45,43 @@ def test_pose_5pt_compose_scales_and_chains(slam_host):
     T = slam_host.pose_5pt_compose(Rt, prev_cw, cur_wc)
     rel = T @ np.linalg.inv(prev_cw)
     assert np.allclose(rel[:3, :3], R) and np.allclose(rel[:3, 3], 2.5 * np.array([0.6, 0.0, 0.8]))
+
+
+def test_parameter_slot_constants_match_the_header(slam_host):
+    """KP_PAR* of csrc/kpset.hpp (read from the header text) are keypoint_set.py's module constants, and stream_params puts camera,
+    distortion and shift at exactly those columns."""
+    import os
+    import re
+    from slam_jl_amd import keypoint_set as K
+    text = open(os.path.join(os.path.dirname(K.__file__), "csrc", "kpset.hpp")).read()
+    line = re.search(r"^constexpr int (KP_PAR\b.*);$", text, re.M).group(1)
+    hdr = {m.group(1): int(m.group(2)) for m in re.finditer(r"(KP_PAR\w*) = (\d+)", line)}
+    assert hdr == {"KP_PAR": K.KP_PAR, "KP_PAR_CAM": K.KP_PAR_CAM, "KP_PAR_DIST": K.KP_PAR_DIST, "KP_PAR_SHIFT": K.KP_PAR_SHIFT}
+    T = np.arange(16.0).reshape(4, 4) + 100
+    p = K.stream_params(3, Tcw=T, cam=(1.5, 2.5, 3.5, 4.5), dist=(5.5, 6.5, 7.5, 8.5), shift_yx=[[9.5, 10.5], [11.5, 12.5], [13.5, 14.5]])
+    assert p.shape == (3, hdr["KP_PAR"]) and p.flags["C_CONTIGUOUS"]
+    want = np.zeros((3, hdr["KP_PAR"]))
+    want[:, :16] = T.T.reshape(16)                                             # column-major
+    want[:, hdr["KP_PAR_CAM"]:hdr["KP_PAR_CAM"] + 4] = (1.5, 2.5, 3.5, 4.5)
+    want[:, hdr["KP_PAR_DIST"]:hdr["KP_PAR_DIST"] + 4] = (5.5, 6.5, 7.5, 8.5)
+    want[:, hdr["KP_PAR_SHIFT"]:hdr["KP_PAR_SHIFT"] + 2] = [[9.5, 10.5], [11.5, 12.5], [13.5, 14.5]]
+    assert np.array_equal(p, want)
+    d = K.stream_params(2)                                                     # the defaults: fx = fy = 1, everything else 0
+    want = np.zeros((2, hdr["KP_PAR"])); want[:, hdr["KP_PAR_CAM"]:hdr["KP_PAR_CAM"] + 2] = 1.0
+    assert np.array_equal(d, want)
+
+
+def test_pose_samples_equal_the_recorded_arrays(slam_host):
+    """tests/golden/pose_samples_v1.npz: pose_samples / pose_samples5 over a small grid of (seed, stream, n, iters), recorded from the two
+    spelled-out loops before they became one (_samples); the n = 4 entry is pose_samples' all -1 exit."""
+    import os
+    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "pose_samples_v1.npz"))
+    assert len(g["grid"]) == 5
+    for i, (seed, stream, n, iters) in enumerate(g["grid"].tolist()):
+        a = slam_host.pose_samples(seed, stream, n, iters)
+        assert a.dtype == np.int32 and np.array_equal(a, g[f"s3_{i}"]), i
+        if n >= 5:
+            b = slam_host.pose_samples5(seed, stream, n, iters)
+            assert b.dtype == np.int32 and np.array_equal(b, g[f"s5_{i}"]), i
+        else:
+            assert (a == -1).all() and a.shape == (iters, 3)
