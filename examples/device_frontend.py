@@ -15,12 +15,14 @@ compose -- on a rigid synthetic scene the poses it returns are the camera motion
 
 Key-frames are taken every `kf_every`-th frame, or, with --adaptive-keyframes, where the reference's rule asks for one
 (front_end.jl:361-393 on the statistics of the lists, one S x 8 read-back per frame).  The streams are lock-stepped -- every launch is
-shared -- so the policy is: a key-frame FOR ALL streams when ANY stream requires one.  Per-stream masks on detect / stereo match /
-triangulate would let each stream follow its own rule; the seams have none yet.
+shared -- so --adaptive-keyframes alone takes a key-frame FOR ALL streams when ANY stream requires one.  --per-stream-keyframes lets every
+stream follow its own rule: the key-frame seams run under KeypointSet.selected(required), which restricts them to the streams that asked
+(slam_kpset_select), and the key-frame bookkeeping (last key-frame, its nb_3d_kpts, its pose, the observer ring, the key-frame id) is per stream.
 
-    python examples/device_frontend.py --frames 12 --streams 4 [--adaptive-keyframes]
+    python examples/device_frontend.py --frames 12 --streams 4 [--adaptive-keyframes | --per-stream-keyframes]
 """
 import argparse
+import contextlib
 import os
 import sys
 import time
@@ -32,13 +34,17 @@ import slam_jl_amd as slam  # noqa: E402
 from slam_jl_amd import synthetic as syn  # noqa: E402
 
 
-def run(lefts, rights, cam, baseline, kf_every=4, max_keypoints=300, seed=0, ctx=None, verbose=False, adaptive=False, probe=None):
+def run(lefts, rights, cam, baseline, kf_every=4, max_keypoints=300, seed=0, ctx=None, verbose=False, adaptive=False, probe=None, per_stream=False):
     """lefts / rights: per stream a list of float images in [0, 1] (H, W).  Returns per frame a dict with the S poses
     (world -> camera, world = the first frame's camera), status words, list lengths and the wall time.
     adaptive: frame 0 is a key-frame; after the pose of every later frame the lists' statistics (KeypointSet.frame_stats, flags = 1) go
     through keyframe_required, and a key-frame is taken for all streams when any stream requires one (kf_every is not used).  Those rows
     also carry kf_stats (S, 8), kf_required, kf_rule, frames_delta and prev_kf_nb_3d (the key-frame's nb_3d_kpts, from the statistics
-    taken when it was created).  probe(frame, keypoint set, R_compensation (S, 3, 3)) is called right after the statistics are taken."""
+    taken when it was created).  probe(frame, keypoint set, R_compensation (S, 3, 3)) is called right after the statistics are taken.
+    per_stream (implies adaptive): frame 0 is a key-frame for all streams; afterwards stream s takes a key-frame exactly where keyframe_required
+    says so for s -- the key-frame seams run on the selected streams only -- and `keyframe` of a row is an (S,) bool array.  (The right-pyramid
+    batch is still built for all S streams at such a frame: a batch build takes the whole batch.)"""
+    adaptive = adaptive or per_stream
     import torch
     ctx = ctx or slam.default_context(0)
     S = len(lefts); n_frames = len(lefts[0])
@@ -55,9 +61,9 @@ def run(lefts, rights, cam, baseline, kf_every=4, max_keypoints=300, seed=0, ctx
     dev = lambda im: torch.from_numpy(np.ascontiguousarray(im.T)).cuda()          # Julia layout: column-major H x W
     T21 = np.eye(4); T21[0, 3] = -baseline                                          # left camera -> right camera
     Tcw = np.tile(np.eye(4), (S, 1, 1)); Tkf = Tcw.copy()
-    NKF = 8; kf_cw = np.tile(np.eye(4), (S, NKF, 1, 1)); n_kf = 0          # poses of the last key-frames (triangulate_temporal!'s observers)
+    NKF = 8; kf_cw = np.tile(np.eye(4), (S, NKF, 1, 1)); n_kf = np.zeros(S, np.int32)     # poses of the last key-frames (triangulate_temporal!'s observers), per stream
     sp_right = slam.stream_params(S, cam=cam, shift_yx=np.zeros((S, 2)))
-    last_kf, prev_kf_nb_3d = 0, np.zeros(S, np.int32)                  # adaptive: frame id and nb_3d_kpts of the previous key-frame
+    last_kf, prev_kf_nb_3d = np.zeros(S, np.int32), np.zeros(S, np.int32)      # adaptive: frame id and nb_3d_kpts of each stream's previous key-frame
     out = []
     for i in range(n_frames):
         t0 = time.perf_counter()
@@ -80,9 +86,9 @@ def run(lefts, rights, cam, baseline, kf_every=4, max_keypoints=300, seed=0, ctx
             for s in range(S):
                 if status[s]:
                     Tcw[s] = poses[s]
-        is_kf, decision = i % kf_every == 0, {}
+        kf_mask, decision = np.full(S, i % kf_every == 0), {}         # the streams that take a key-frame at this frame
         if adaptive:
-            is_kf = i == 0
+            kf_mask = np.full(S, i == 0)
             if i > 0:                                                       # check_new_kf_required, front_end.jl:117
                 Rc = np.tile(np.eye(4), (S, 1, 1))
                 for s in range(S):
@@ -90,28 +96,34 @@ def run(lefts, rights, cam, baseline, kf_every=4, max_keypoints=300, seed=0, ctx
                 stats = ks.frame_stats(slam.stream_params(S, Tcw=Rc, cam=cam), 1, ex.cell_size, (H, W), ctx=ctx)
                 if probe is not None:
                     probe(i, ks, Rc[:, :3, :3].copy())
-                fd = np.full(S, i - last_kf, np.int32)
+                fd = (i - last_kf).astype(np.int32)
                 req, rule = slam.keyframe_required(stats, fd, prev_kf_nb_3d, np.ones(S, np.uint8), params, local_ba_on=False)
-                is_kf = bool(req.any())                                     # lock-step: one stream's need is every stream's key-frame
+                kf_mask = req.copy() if per_stream else np.full(S, bool(req.any()))    # lock-step without per_stream: one stream's need is every stream's key-frame
                 decision = dict(kf_stats=stats, kf_required=req, kf_rule=rule, frames_delta=fd, prev_kf_nb_3d=prev_kf_nb_3d.copy())
-        if is_kf:
-            ks.detect(ex, cur, ctx=ctx)
-            ks.keyframe(ctx=ctx)
-            Tkf = Tcw.copy()
-            kfid = n_kf; kf_cw[:, kfid % NKF] = Tcw; n_kf += 1
-            rframes = [dev(rights[s][i]) for s in range(S)]
-            torch.cuda.synchronize()
-            rpyr.update_([f.data_ptr() for f in rframes], sigma=params.pyramid_sigma, ctx=ctx, target_only=True)   # only matched INTO
-            ks.stereo_match(cur, rpyr, params, sp_right, prior=2, ctx=ctx)
-            Twc = np.stack([np.linalg.inv(Tcw[s]) for s in range(S)])
-            ks.triangulate(cam, cam, T21, Twc, max_error=params.max_reprojection_error, ctx=ctx)
-            if kfid > 0:                                                    # mapper.jl:86: 2-D keypoints left over, against their first observers
-                ks.triangulate_temporal(slam.stream_params(S, cam=cam), kf_cw, Twc, kfid, max_error=params.max_reprojection_error, ctx=ctx)
+        if kf_mask.any():
+            # the six key-frame seams act on the streams of kf_mask (all of them without per_stream: no selection is ever set then)
+            with (ks.selected(kf_mask, ctx=ctx) if per_stream else contextlib.nullcontext()):
+                ks.detect(ex, cur, ctx=ctx)
+                ks.keyframe(ctx=ctx)
+                Tkf[kf_mask] = Tcw[kf_mask]
+                kfid = n_kf.copy()                                          # per stream: the id of the key-frame being created
+                for s in np.flatnonzero(kf_mask):
+                    kf_cw[s, kfid[s] % NKF] = Tcw[s]
+                n_kf[kf_mask] += 1
+                rframes = [dev(rights[s][i]) for s in range(S)]
+                torch.cuda.synchronize()
+                rpyr.update_([f.data_ptr() for f in rframes], sigma=params.pyramid_sigma, ctx=ctx, target_only=True)   # only matched INTO
+                ks.stereo_match(cur, rpyr, params, sp_right, prior=2, ctx=ctx)
+                Twc = np.stack([np.linalg.inv(Tcw[s]) for s in range(S)])
+                ks.triangulate(cam, cam, T21, Twc, max_error=params.max_reprojection_error, ctx=ctx)
+                if (kfid[kf_mask] > 0).any():                               # mapper.jl:86: 2-D keypoints left over, against their first observers
+                    ks.triangulate_temporal(slam.stream_params(S, cam=cam), kf_cw, Twc, kfid, max_error=params.max_reprojection_error, ctx=ctx)
             if adaptive:                                                    # the key-frame's own nb_3d_kpts, after the mapper's triangulations
-                last_kf = i
-                prev_kf_nb_3d = ks.frame_stats(slam.stream_params(S, cam=cam), 0, ex.cell_size, (H, W), ctx=ctx)[:, 1].astype(np.int32)
+                last_kf[kf_mask] = i
+                nb_3d = ks.frame_stats(slam.stream_params(S, cam=cam), 0, ex.cell_size, (H, W), ctx=ctx)[:, 1].astype(np.int32)
+                prev_kf_nb_3d[kf_mask] = nb_3d[kf_mask]                     # refreshed only for the streams that took the key-frame
         cnt = ks.counts(ctx=ctx)
-        row = dict(frame=i, keyframe=is_kf, poses=Tcw.copy(), status=status.copy(), status_5pt=np.asarray(st5).copy(),
+        row = dict(frame=i, keyframe=kf_mask.copy() if per_stream else bool(kf_mask.any()), poses=Tcw.copy(), status=status.copy(), status_5pt=np.asarray(st5).copy(),
                    counts=cnt.copy(), ms=(time.perf_counter() - t0) * 1e3)
         row.update(decision)
         out.append(row)
@@ -139,11 +151,12 @@ def main():
     ap.add_argument("--frames", type=int, default=12)
     ap.add_argument("--streams", type=int, default=2)
     ap.add_argument("--adaptive-keyframes", action="store_true", help="take key-frames where check_new_kf_required asks for one (any stream), not every 4th frame")
+    ap.add_argument("--per-stream-keyframes", action="store_true", help="every stream takes its key-frames where check_new_kf_required asks for one for THAT stream (implies --adaptive-keyframes)")
     ap.add_argument("--replay-dir", default=None, help="write stream s's camera positions to DIR/stream_s as a ReplaySaver dump (src/io/saver.jl)")
     args = ap.parse_args()
     cam, baseline, disparity = syn.KITTI_CAM, 0.54, 8.0
     lefts, rights, offs = synthetic_scene(args.streams, args.frames, disparity=disparity)
-    out, n3 = run(lefts, rights, cam, baseline, verbose=True, adaptive=args.adaptive_keyframes)
+    out, n3 = run(lefts, rights, cam, baseline, verbose=True, adaptive=args.adaptive_keyframes, per_stream=args.per_stream_keyframes)
     Z = cam[0] * baseline / disparity
     for s in range(args.streams):
         o = offs[s][-1] - offs[s][0]

@@ -272,12 +272,29 @@ int slam_flow_match_batch_kept(slam_ctx *ctx, const slam_pyr *from0, const slam_
  * needs.  n_bound: an upper bound of the number of live keypoints known to the host (sizes launches; <= 0: S x cap).
  * Per-stream call parameters `params`: S x 32 doubles, [0..15] Tcw of the target camera (column-major 4x4), [16..19] fx fy cx
  * cy and [20..23] k1 k2 p1 p2 of the target camera, [24..25] prior shift (y, x); prior = 0: none, 1: projection of the map
- * point through Tcw and the lens model (project_world_to_image_distort, frame.jl:478-484), 2: pixel + shift. */
+ * point through Tcw and the lens model (project_world_to_image_distort, frame.jl:478-484), 2: pixel + shift.
+ * THE SELECTION (slam_kpset_select): a key-frame is a per-stream event (check_new_kf_required, slam_keyframe_required below), so the SIX
+ * KEY-FRAME SEAMS -- slam_kpset_detect, _detect_describe, _keyframe, _stereo_match, _triangulate, _triangulate_temporal -- act on the
+ * selected streams only.  EVERY OTHER SEAM IGNORES THE SELECTION and acts on all S streams: slam_kpset_flow_match, _remove,
+ * _compute_pose, _compute_pose_5pt, _frame_stats, _counts and the uploads / downloads (slam_frontend_step owns a set of one stream and
+ * never selects).  An unselected stream comes out of the six seams as it went in -- every per-keypoint array, its list length, its
+ * key-frame counter and its id counter byte for byte -- and none of the per-stream inputs a seam takes for it (params row, Twc, tab,
+ * kf_cur, kf_lo) has any effect; a selected stream's result does not depend on which other streams are selected.  Launches are sized
+ * by the number of selected streams; with none selected the six seams check their arguments and enqueue nothing. */
 typedef struct slam_kpset slam_kpset;
 int slam_kpset_create(slam_ctx *ctx, int S, int cap, slam_kpset **out);
 int slam_kpset_destroy(slam_kpset *ks);
 int slam_kpset_streams(const slam_kpset *ks);
 int slam_kpset_capacity(const slam_kpset *ks);
+/* Set the streams the six key-frame seams act on: selected = S bytes on the host, non-zero = selected (required[] of
+ * slam_keyframe_required can be passed as it is), or NULL = every stream (the state of a new set; a mask that selects every stream is the
+ * same thing).  The selection is a property of the set and holds until the next call.  Enqueue-only on ctx's stream: the bytes are staged,
+ * the caller's array is free on return.  The table the kernels read is written in ctx's stream order, so a host that drives one set from
+ * several contexts orders slam_kpset_select against the seams exactly as it orders the seams against each other today (events /
+ * slam_ctx_synchronize between contexts): a key-frame seam enqueued on another context must not run before the select it relies on has,
+ * nor may the next select run while it still does.  slam_kpset_selection: the current selection as S bytes of 0 / 1 (all 1 when none is set). */
+int slam_kpset_select(slam_ctx *ctx, slam_kpset *ks, const uint8_t *selected /* S bytes, host; NULL = every stream */);
+int slam_kpset_selection(const slam_kpset *ks, uint8_t *selected_out /* S bytes */);
 /* replace / read stream s's list (initialisation, tests, host consumers); NULL arrays are skipped; ids == NULL: 0 .. n-1 */
 int slam_kpset_upload(slam_ctx *ctx, slam_kpset *ks, int s, const double *yx, const uint8_t *is_3d, const double *xyz,
                       const int64_t *ids, int n);
@@ -311,7 +328,8 @@ int slam_kpset_detect(slam_ctx *ctx, slam_kpset *ks, const slam_pyr *pyr0, int m
  * keypoint appended to stream s by THIS call has id info_dev[2 s] + j and its descriptor at desc_dev[(s dcap + j) words ..];
  * info_dev[2 s + 1] = number appended (info_dev: S x 2 int64 in HBM).  Descriptors belong to the map point of that id
  * (map_manager.jl:116-131) and are not carried through compactions.  Enqueue-only, like slam_kpset_detect.
- * dcap >= grid_rows grid_cols ceil(max_points / (grid_rows grid_cols)); window as slam_describe_pyr. */
+ * dcap >= grid_rows grid_cols ceil(max_points / (grid_rows grid_cols)); window as slam_describe_pyr.
+ * An unselected stream s (slam_kpset_select): info_dev[2 s] = its id counter, info_dev[2 s + 1] = 0, its desc_dev rows are not written. */
 int slam_kpset_detect_describe(slam_ctx *ctx, slam_kpset *ks, const slam_pyr *pyr0, int max_points, int radius,
                                int grid_rows, int grid_cols, int cell_size, double sigma_mask, double min_response,
                                const int32_t *pattern, int n_bits, double sigma, int window,

@@ -79,6 +79,8 @@ SIGNATURES = {
     "slam_kpset_destroy": (cint, [vp]),
     "slam_kpset_streams": (cint, [vp]),
     "slam_kpset_capacity": (cint, [vp]),
+    "slam_kpset_select": (cint, [vp, vp, u8p]),
+    "slam_kpset_selection": (cint, [vp, u8p]),
     "slam_kpset_upload": (cint, [vp, vp, cint, f64p, u8p, f64p, i64p, cint]),
     "slam_kpset_download": (cint, [vp, vp, cint, f64p, u8p, f64p, i64p, f64p, u8p, cint, C.POINTER(cint)]),
     "slam_kpset_counts": (cint, [vp, vp, i32p]),

@@ -16,13 +16,7 @@
 #include <cmath>
 #include <type_traits>
 
-// live slots of all streams back to back + their number.  One small workgroup per stream (it sums the counts before its own: S
-// loads): a single 1024-thread workgroup had to wait for sixteen free wave slots on one CU while the pyramid kernels fill the chip
-// (58 us on average in the pipeline for 12 us of work).
-// Stream s's segment [off_s, off_s + count_s) holds its live slots; O.band > 0 sorts them by work_key (x-band, row, slot:
-// work_order.hpp) with a bitonic network in LDS over the segment padded to a power of two with maximal words -- lists are queues
-// of many detect generations (stable compaction, new keypoints appended behind), so slot order is not a spatial order.  Every wave
-// sums the counts itself (S loads, no barrier); the sort's words are (key << 32 | slot), all different.
+// The work list (k_kpset_worklist, kpset_kernels.inc): live slots of the streams back to back, each segment in the order of work_order.hpp.
 // SLAMHIP_WORK_BAND, read once per process: the band width in pixels, 0 = slot order (the lists as they are); default WORK_BAND_PX.
 // KPSET_SORT_LDS_BYTES is the sort's LDS budget (what a workgroup gets without asking for more): a set whose capacity, padded to a
 // power of two, does not fit keeps slot order -- slam_kpset_create decides that once (sort_pad).
@@ -30,94 +24,45 @@
 #define KPSET_SORT_LDS_BYTES 65536
 static int work_band() { static const int band = [] { const char *v = getenv("SLAMHIP_WORK_BAND"); const int b = v ? atoi(v) : WORK_BAND_PX; return b < 0 ? 0 : b; }(); return band; }
 struct WorkOrder { int H, W, band, pad; };       // band 0: slot order; pad: power of two >= cap whose words fit KPSET_SORT_LDS_BYTES
-__global__ __launch_bounds__(256) void k_kpset_worklist(const int *count, int S, int cap, int *work, int *ntot, const double *yx, WorkOrder O)
-{
-    extern __shared__ unsigned long long s_word[];
-    const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
-    int off = 0, t = 0;
-    for (int i = lane; i < S; i += 64) { const int v = count[i]; t += v; off += i < s ? v : 0; }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) { off += __shfl_xor(off, m); t += __shfl_xor(t, m); }
-    if (s == 0 && tid == 0) ntot[0] = t;
-    const int n = count[s];
-    if (O.band <= 0 || n > O.pad) {                              // (n > pad cannot happen: n <= cap <= pad; it guards the LDS array)
-        for (int j = tid; j < n; j += 256) work[off + j] = s * cap + j;
-        return;
-    }
-    int P = 1;
-    while (P < n) P <<= 1;
-    const double *p = yx + 2 * (size_t)s * cap;
-    for (int j = tid; j < P; j += 256)
-        s_word[j] = j < n ? ((unsigned long long)work_key(p[2 * j], p[2 * j + 1], O.H, O.W, O.band) << 32) | (unsigned)j : ~0ull;
-    __syncthreads();
-    for (int k = 2; k <= P; k <<= 1)
-        for (int d = k >> 1; d > 0; d >>= 1) {
-            for (int u = tid; u < (P >> 1); u += 256) {
-                const int i = ((u & ~(d - 1)) << 1) | (u & (d - 1));             // the lower index of the u-th pair at distance d
-                const unsigned long long a = s_word[i], c = s_word[i + d];
-                if ((a > c) == ((i & k) == 0)) { s_word[i] = c; s_word[i + d] = a; }
-            }
-            __syncthreads();
-        }
-    for (int j = tid; j < n; j += 256) work[off + j] = s * cap + (int)(unsigned)s_word[j];
-}
+// k_kpset_worklist, k_kpset_compact and k_kpset_keyframe, plain and selected (slam_kpset_select): kpset_kernels.inc, included once per form
+#define SEL_NAME(k) k
+#define SEL_ARG
+#define SEL_STREAM(b) b
+#define SEL_STREAMS(S) S
+#define SEL_SELF(s) s
+#include "kpset_kernels.inc"
+#undef SEL_NAME
+#undef SEL_ARG
+#undef SEL_STREAM
+#undef SEL_STREAMS
+#undef SEL_SELF
+#define SEL_NAME(k) k##_sel
+#define SEL_ARG , const int *sel
+#define SEL_STREAM(b) sel[b]
+#define SEL_STREAMS(S) (int)gridDim.x
+#define SEL_SELF(s) (int)blockIdx.x
+#include "kpset_kernels.inc"
+#undef SEL_NAME
+#undef SEL_ARG
+#undef SEL_STREAM
+#undef SEL_STREAMS
+#undef SEL_SELF
 
 // H x W: the image the positions live in (the match that follows reads its planes); H <= 0: slot order -- the triangulation
 // kernels read a few bytes per keypoint and gain nothing from an order
-int kpset_build_worklist(slam_ctx *ctx, slam_kpset *ks, int H, int W)
+// selected: the caller is one of the six key-frame seams, which honour the set's selection (it has returned already when no stream is selected)
+int kpset_build_worklist(slam_ctx *ctx, slam_kpset *ks, int H, int W, bool selected)
 {
     WorkOrder O;
     O.H = H; O.W = W; O.pad = ks->sort_pad; O.band = H > 0 && W > 0 && ks->sort_pad > 0 ? work_band() : 0;
     const size_t lds = O.band > 0 ? (size_t)ks->sort_pad * 8 : 0;
-    hipLaunchKernelGGL(k_kpset_worklist, dim3(ks->S), dim3(256), lds, ctx->stream, (const int *)ks->v.count, ks->S, ks->v.cap, ks->work, ks->ntot, (const double *)ks->v.yx, O);
+    if (selected && ks->n_sel != KPSEL_ALL)
+        hipLaunchKernelGGL(k_kpset_worklist_sel, dim3(ks->n_sel), dim3(256), lds, ctx->stream, (const int *)ks->v.count, ks->S, ks->v.cap, ks->work, ks->ntot, (const double *)ks->v.yx, O,
+                           (const int *)ks->sel_idx);
+    else
+        hipLaunchKernelGGL(k_kpset_worklist, dim3(ks->S), dim3(256), lds, ctx->stream, (const int *)ks->v.count, ks->S, ks->v.cap, ks->work, ks->ntot, (const double *)ks->v.yx, O);
     HIP_TRY(ctx, hipGetLastError());
     return SLAM_OK;
-}
-
-// Stable in-place compaction of every stream's list, one 256-thread workgroup per stream.
-// mode 0 (after a temporal match): keep st != 0; a tracked keypoint (st == 1) takes its new position from oyx.
-// mode 1 (removal by flags): keep flags[slot] == 0.
-// Chunks of 256 slots are read (all fields into registers), ranked with a wave ballot + the popcount of the lower lanes,
-// and written back after a barrier: destinations never lie to the right of their sources, so in place is safe.
-// (The load and the store block stay spelled out: a record struct with load / store members changes the kernel's register assignment -- HISTORY.md, round 20.)
-__global__ __launch_bounds__(256) void k_kpset_compact(KpsetView K, int mode, const uint8_t *flags)
-{
-    __shared__ int s_w[4], s_base;
-    const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const size_t b = (size_t)s * K.cap;
-    const int n = K.count[s];
-    if (tid == 0) s_base = 0;
-    __syncthreads();
-    for (int c0 = 0; c0 < n; c0 += 256) {
-        const int j = c0 + tid;
-        bool keep = false;
-        double y = 0, x = 0, sy = 0, sx = 0, X0 = 0, X1 = 0, X2 = 0, ky = 0, kx = 0, fy0 = 0, fx0 = 0; int64_t id = 0; uint8_t f3 = 0, fs = 0, fk = 0; int fkid = 0;
-        if (j < n) {
-            const size_t q = b + j;
-            if (mode == 0) { const uint8_t t = K.st[q]; keep = t != 0; if (t == 1) { y = K.oyx[2 * q]; x = K.oyx[2 * q + 1]; } else { y = K.yx[2 * q]; x = K.yx[2 * q + 1]; } }
-            else { keep = flags[q] == 0; y = K.yx[2 * q]; x = K.yx[2 * q + 1]; }
-            if (keep) { sy = K.syx[2 * q]; sx = K.syx[2 * q + 1]; X0 = K.xyz[3 * q]; X1 = K.xyz[3 * q + 1]; X2 = K.xyz[3 * q + 2]; id = K.id[q]; f3 = K.is3d[q]; fs = K.stereo[q];
-                        ky = K.kyx[2 * q]; kx = K.kyx[2 * q + 1]; fk = K.haskf[q]; fy0 = K.fyx[2 * q]; fx0 = K.fyx[2 * q + 1]; fkid = K.fkf[q]; }
-        }
-        // (its own loop, not ordered_slot: the writes follow the one barrier that ends the chunk's reads, and this kernel runs after every match)
-        const unsigned long long m = __ballot(keep);
-        const int rank = __builtin_popcountll(m & ((1ull << lane) - 1ull));
-        if (lane == 0) s_w[wv] = __builtin_popcountll(m);
-        __syncthreads();                                        // all reads of the chunk done; wave totals visible
-        int wbase = 0;
-        for (int i = 0; i < wv; i++) wbase += s_w[i];
-        const int total = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-        if (keep) {
-            const size_t q = b + s_base + wbase + rank;
-            K.yx[2 * q] = y; K.yx[2 * q + 1] = x; K.syx[2 * q] = sy; K.syx[2 * q + 1] = sx;
-            K.xyz[3 * q] = X0; K.xyz[3 * q + 1] = X1; K.xyz[3 * q + 2] = X2; K.id[q] = id; K.is3d[q] = f3; K.stereo[q] = fs;
-            K.kyx[2 * q] = ky; K.kyx[2 * q + 1] = kx; K.haskf[q] = fk; K.fyx[2 * q] = fy0; K.fyx[2 * q + 1] = fx0; K.fkf[q] = fkid;
-        }
-        __syncthreads();
-        if (tid == 0) s_base += total;
-        __syncthreads();
-    }
-    if (tid == 0) K.count[s] = s_base;
 }
 
 int kpset_stage_params(slam_ctx *ctx, slam_kpset *ks, const double *host, size_t n, const double **dev_out)
@@ -134,9 +79,12 @@ int kpset_stage_params(slam_ctx *ctx, slam_kpset *ks, const double *host, size_t
     return SLAM_OK;
 }
 
-int kpset_compact(slam_ctx *ctx, slam_kpset *ks, int mode, const uint8_t *flags_dev)
+int kpset_compact(slam_ctx *ctx, slam_kpset *ks, int mode, const uint8_t *flags_dev, bool selected)
 {
-    hipLaunchKernelGGL(k_kpset_compact, dim3(ks->S), dim3(256), 0, ctx->stream, ks->v, mode, flags_dev);
+    if (selected && ks->n_sel != KPSEL_ALL)
+        hipLaunchKernelGGL(k_kpset_compact_sel, dim3(ks->n_sel), dim3(256), 0, ctx->stream, ks->v, mode, flags_dev, (const int *)ks->sel_idx);
+    else
+        hipLaunchKernelGGL(k_kpset_compact, dim3(ks->S), dim3(256), 0, ctx->stream, ks->v, mode, flags_dev);
     HIP_TRY(ctx, hipGetLastError());
     return SLAM_OK;
 }
@@ -407,6 +355,8 @@ static size_t kpset_regions(slam_kpset *ks, char *base)
     region(v.is3d, n); region(v.stereo, n); region(v.st, n); region(v.count, S * 4); region(ks->work, n * 4); region(ks->ntot, 64);
     region(ks->next_id, S * 8); region(ks->par, 8 * S * KP_PAR * 8); region(v.kyx, n * 16); region(v.haskf, n); region(v.fyx, n * 16);
     region(v.fkf, n * 4); region(v.kfcount, S * 4);
+    region(ks->sel_idx, S * 4 + S);                               // the selection as one block (one staged copy): S indices, then the S mask bytes
+    if (base) ks->sel_mask = (uint8_t *)(ks->sel_idx + S);
     return Lo.size();
 }
 
@@ -479,6 +429,8 @@ int slam_kpset_destroy(slam_kpset *ks)
     if (ks->kf_stats) (void)hipFree(ks->kf_stats);
     if (ks->kf_terms) (void)hipFree(ks->kf_terms);
     for (int i = 0; i < 8; i++) if (ks->par_ev[i]) (void)hipEventDestroy(ks->par_ev[i]);
+    if (ks->sel_pin) (void)hipHostFree(ks->sel_pin);
+    for (int i = 0; i < 8; i++) if (ks->sel_ev[i]) (void)hipEventDestroy(ks->sel_ev[i]);
     delete ks;
     return SLAM_OK;
 }
@@ -500,6 +452,40 @@ int slamhip_test_kpset_worklist(slam_ctx *ctx, slam_kpset *ks, int H, int W, int
 
 int slam_kpset_streams(const slam_kpset *ks) { return ks ? ks->S : SLAM_ERR_ARG; }
 int slam_kpset_capacity(const slam_kpset *ks) { return ks ? ks->v.cap : SLAM_ERR_ARG; }
+
+// The streams the six key-frame seams act on (kpset_select.hpp makes the table; kpset.hpp says who reads it).  Enqueue-only: the table and
+// the normalised mask go through the next slot of a pinned ring (the caller's array is free on return; the wait is for the copy that used
+// the slot 8 calls ago) into the set's one device block, in ctx's stream order -- behind every seam enqueued before, ahead of every one after.
+int slam_kpset_select(slam_ctx *ctx, slam_kpset *ks, const uint8_t *selected)
+{
+    ARG_TRY(ctx, ctx != nullptr && ks != nullptr);
+    const int S = ks->S;
+    int32_t idx[128]; uint8_t norm[128];
+    const int n_sel = kpset_select_plan(S, selected, idx, norm);
+    if (n_sel != KPSEL_ALL) {                                    // (no selection needs no table: the unselected kernel forms read none)
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        const size_t bytes = (size_t)S * 5;
+        if (!ks->sel_pin) {
+            HIP_TRY(ctx, hipHostMalloc((void **)&ks->sel_pin, 8 * bytes));
+            for (int i = 0; i < 8; i++) if (!ks->sel_ev[i]) HIP_TRY(ctx, hipEventCreateWithFlags(&ks->sel_ev[i], hipEventDisableTiming));
+        }
+        const int sl = ks->sel_slot; ks->sel_slot = (sl + 1) & 7;
+        HIP_TRY(ctx, hipEventSynchronize(ks->sel_ev[sl]));       // (an event never recorded is complete)
+        char *h = ks->sel_pin + (size_t)sl * bytes;
+        memcpy(h, idx, (size_t)S * 4); memcpy(h + (size_t)S * 4, norm, (size_t)S);
+        HIP_TRY(ctx, hipMemcpyAsync(ks->sel_idx, h, bytes, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipEventRecord(ks->sel_ev[sl], ctx->stream));
+    }
+    memcpy(ks->sel_host, norm, (size_t)S);
+    ks->n_sel = n_sel;
+    return SLAM_OK;
+}
+int slam_kpset_selection(const slam_kpset *ks, uint8_t *selected_out)
+{
+    if (!ks || !selected_out) return SLAM_ERR_ARG;
+    for (int s = 0; s < ks->S; s++) selected_out[s] = ks->n_sel == KPSEL_ALL ? 1 : ks->sel_host[s];
+    return SLAM_OK;
+}
 
 // replace stream s's list (initialisation, tests); ids == NULL: 0 .. n-1, the stream's id counter moves past them
 int slam_kpset_upload(slam_ctx *ctx, slam_kpset *ks, int s, const double *yx, const uint8_t *is3d, const double *xyz, const int64_t *ids, int n)
@@ -539,24 +525,22 @@ int slam_kpset_download(slam_ctx *ctx, slam_kpset *ks, int s, double *yx, uint8_
                       {{v.yx, 16, yx}, {v.is3d, 1, is3d}, {v.xyz, 24, xyz}, {v.id, 8, ids}, {v.syx, 16, stereo_yx}, {v.stereo, 1, has_stereo}});
 }
 
-// create_keyframe! (map_manager.jl:60-96) as far as the lists are concerned: the current frame becomes the previous key-frame
-// of every keypoint it holds (frames_map[kfid] is a copy of the frame, new keypoints included: call it after slam_kpset_detect)
-__global__ __launch_bounds__(256) void k_kpset_keyframe(KpsetView K)
-{
-    const int s = blockIdx.y, j = blockIdx.x * 256 + threadIdx.x;
-    if (j >= K.count[s]) return;
-    const size_t q = (size_t)s * K.cap + j;
-    const double y = K.yx[2 * q], x = K.yx[2 * q + 1];
-    if (!K.haskf[q]) { K.fyx[2 * q] = y; K.fyx[2 * q + 1] = x; K.fkf[q] = K.kfcount[s]; }     // detected by this key-frame: its first observer
-    K.kyx[2 * q] = y; K.kyx[2 * q + 1] = x; K.haskf[q] = 1;
-}
+// create_keyframe! for the lists: k_kpset_keyframe (kpset_kernels.inc), then the streams' key-frame counters
 __global__ void k_kpset_kf_advance(int *kfcount, int S) { const int s = blockIdx.x * 64 + threadIdx.x; if (s < S) kfcount[s] += 1; }   // (one 64-thread block until round 5: streams 64.. never advanced)
+// only the selected streams' key-frame counters advance: an unselected stream's next key-frame keeps the id it would have had
+__global__ void k_kpset_kf_advance_sel(int *kfcount, const int *sel, int n_sel) { const int i = blockIdx.x * 64 + threadIdx.x; if (i < n_sel) kfcount[sel[i]] += 1; }
 int slam_kpset_keyframe(slam_ctx *ctx, slam_kpset *ks)
 {
     ARG_TRY(ctx, ctx != nullptr && ks != nullptr);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipLaunchKernelGGL(k_kpset_keyframe, dim3((ks->v.cap + 255) / 256, ks->S), dim3(256), 0, ctx->stream, ks->v);
-    hipLaunchKernelGGL(k_kpset_kf_advance, dim3((ks->S + 63) / 64), dim3(64), 0, ctx->stream, ks->v.kfcount, ks->S);
+    if (kpset_none_selected(ks)) return SLAM_OK;
+    if (const int *sel = kpset_sel_table(ks)) {
+        hipLaunchKernelGGL(k_kpset_keyframe_sel, dim3((ks->v.cap + 255) / 256, ks->n_sel), dim3(256), 0, ctx->stream, ks->v, sel);
+        hipLaunchKernelGGL(k_kpset_kf_advance_sel, dim3((ks->n_sel + 63) / 64), dim3(64), 0, ctx->stream, ks->v.kfcount, sel, ks->n_sel);
+    } else {
+        hipLaunchKernelGGL(k_kpset_keyframe, dim3((ks->v.cap + 255) / 256, ks->S), dim3(256), 0, ctx->stream, ks->v);
+        hipLaunchKernelGGL(k_kpset_kf_advance, dim3((ks->S + 63) / 64), dim3(64), 0, ctx->stream, ks->v.kfcount, ks->S);
+    }
     HIP_TRY(ctx, hipGetLastError());
     return SLAM_OK;
 }
@@ -620,11 +604,12 @@ int slam_kpset_triangulate(slam_ctx *ctx, slam_kpset *ks, const double *P1, cons
     KTriArgs T;
     T.M.fill(P1, P2, T21, cam1, cam2);
     T.max_error = max_error; T.min_depth = min_depth;
-    int rc = kpset_stage_params(ctx, ks, Twc, (size_t)ks->S * 16, &T.Twc);
+    if (kpset_none_selected(ks)) return SLAM_OK;
+    int rc = kpset_stage_params(ctx, ks, Twc, (size_t)ks->S * 16, &T.Twc);      // (an unselected stream's row is staged and never read: no slot of it is in the work list)
     if (rc) return rc;
-    rc = kpset_build_worklist(ctx, ks, 0, 0);
+    rc = kpset_build_worklist(ctx, ks, 0, 0, true);
     if (rc) return rc;
-    const int nb = kpset_grid_bound(ks, n_bound);
+    const int nb = kpset_sel_grid_bound(ks, n_bound);
     hipLaunchKernelGGL(k_kpset_triangulate, dim3((nb + 63) / 64), dim3(64), 0, ctx->stream, ks->v, T, (const int *)ks->work, (const int *)ks->ntot);
     HIP_TRY(ctx, hipGetLastError());
     return SLAM_OK;
@@ -636,6 +621,7 @@ int slam_kpset_triangulate_temporal(slam_ctx *ctx, slam_kpset *ks, const double 
 {
     ARG_TRY(ctx, ctx != nullptr && ks != nullptr && params && tab && kf_cur && kf_lo && nkf >= 1);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (kpset_none_selected(ks)) return SLAM_OK;
     const int S = ks->S;
     const size_t nc = (size_t)S * ks->v.cap;
     Layout D;                          // the staged inputs (same offsets in the pinned block), then the removal flags
@@ -654,12 +640,12 @@ int slam_kpset_triangulate_temporal(slam_ctx *ctx, slam_kpset *ks, const double 
     T.max_error = max_error; T.min_depth = min_depth; T.min_parallax = min_parallax;
     T.flags = (uint8_t *)(scr + o_fl);
     HIP_TRY(ctx, hipMemsetAsync(T.flags, 0, nc, ctx->stream));
-    rc = kpset_build_worklist(ctx, ks, 0, 0);
+    rc = kpset_build_worklist(ctx, ks, 0, 0, true);
     if (rc) return rc;
-    const int nb = kpset_grid_bound(ks, n_bound);
+    const int nb = kpset_sel_grid_bound(ks, n_bound);
     hipLaunchKernelGGL(k_kpset_tri_temporal, dim3((nb + 63) / 64), dim3(64), 0, ctx->stream, ks->v, T, (const int *)ks->work, (const int *)ks->ntot);
     HIP_TRY(ctx, hipGetLastError());
-    rc = kpset_compact(ctx, ks, 1, T.flags);
+    rc = kpset_compact(ctx, ks, 1, T.flags, true);
     if (rc) return rc;
     // the pinned table is read by the copy above: it must be gone from the host block before the next call reuses it
     HIP_TRY(ctx, slam_stream_wait(ctx->stream));

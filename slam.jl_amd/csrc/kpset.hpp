@@ -2,6 +2,7 @@
 // per-stream parameter slot, and the plumbing the files that touch a set share (kpset.hip, lk.hip, detect.hip, pose.hip, fivepoint.hip).
 #pragma once
 #include "common.hpp"
+#include "kpset_select.hpp"
 #include <initializer_list>
 
 // The per-keypoint arrays of S lock-stepped streams: stream s owns the slots [s * cap, s * cap + count[s]) of every
@@ -50,15 +51,34 @@ struct slam_kpset {
     // S x cap parallax terms for the streams whose terms do not fit the kernel's LDS array (only for cap > that array)
     double *kf_stats = nullptr;
     unsigned long long *kf_terms = nullptr;
+    // slam_kpset_select: the streams the six key-frame seams act on (detect, detect_describe, keyframe, stereo_match, triangulate,
+    // triangulate_temporal; every other seam acts on all streams).  n_sel == KPSEL_ALL: no selection, the seams launch what they launch
+    // without one.  Otherwise sel_idx[0 .. n_sel) are the selected streams ascending and sel_mask[s] is 0 / 1 (both device, one block of
+    // the set's allocation; sel_host is the host's copy of the mask), staged through a pinned ring of 8 slots with an event each (made by
+    // the first call that sets a selection), like `par`.  Not members of KpsetView: that struct is a kernel-argument block.
+    int n_sel = KPSEL_ALL;
+    int *sel_idx = nullptr; uint8_t *sel_mask = nullptr;
+    uint8_t sel_host[128] = {};
+    char *sel_pin = nullptr;
+    hipEvent_t sel_ev[8] = {};
+    int sel_slot = 0;
 };
 
 // ---- plumbing (kpset.hip) --------------------------------------------------------------------------------------------------------------
 // stage `n` doubles (<= S x KP_PAR) of per-stream parameters into the next ring slot; returns the device pointer
 int kpset_stage_params(slam_ctx *ctx, slam_kpset *ks, const double *host, size_t n, const double **dev_out);
-int kpset_build_worklist(slam_ctx *ctx, slam_kpset *ks, int H, int W);   // H <= 0: slot order (no image, or an order would not pay)
-int kpset_compact(slam_ctx *ctx, slam_kpset *ks, int mode, const uint8_t *flags_dev);
+// `selected` (both): the caller is a key-frame seam and honours the set's selection -- only the selected streams' segments / lists; the caller has returned
+// before when no stream is selected (kpset_none_selected)
+int kpset_build_worklist(slam_ctx *ctx, slam_kpset *ks, int H, int W, bool selected = false);   // H <= 0: slot order (no image, or an order would not pay)
+int kpset_compact(slam_ctx *ctx, slam_kpset *ks, int mode, const uint8_t *flags_dev, bool selected = false);
+inline bool kpset_none_selected(const slam_kpset *ks) { return ks->n_sel == 0; }
+// the stream dimension of a key-frame seam's launch, and the table its selected kernel form reads (nullptr: the unselected form)
+inline int kpset_sel_streams(const slam_kpset *ks) { return kpset_select_streams(ks->S, ks->n_sel); }
+inline const int *kpset_sel_table(const slam_kpset *ks) { return ks->n_sel == KPSEL_ALL ? nullptr : ks->sel_idx; }
 // the number of keypoints a launch over the work list is sized for: the host's bound of the live slots where it has one, else S x cap
 inline int kpset_grid_bound(const slam_kpset *ks, int n_bound) { const int nmax = ks->S * ks->v.cap; return n_bound > 0 && n_bound < nmax ? n_bound : nmax; }
+// the same for a key-frame seam: the selected streams' share of the capacity (no selection: kpset_grid_bound's value)
+inline int kpset_sel_grid_bound(const slam_kpset *ks, int n_bound) { return kpset_select_bound(ks->S, ks->v.cap, ks->n_sel, n_bound); }
 // the tail of a seam that returns results: `bytes` from `dev` to h + at (a region of the caller's Layout in its pinned block), one wait, then on into `out` (skipped where null)
 struct KpReadBack { size_t at; const void *dev; size_t bytes; void *out; };
 int kpset_read_back(slam_ctx *ctx, char *h, std::initializer_list<KpReadBack> parts);

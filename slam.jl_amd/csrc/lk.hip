@@ -649,6 +649,9 @@ static int kpset_match(slam_ctx *ctx, slam_kpset *ks, const slam_pyr *from0, con
     int rc = match_check(ctx, from0, to0, t);
     if (rc) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // the stereo match is a key-frame seam and honours the set's selection (slam_kpset_select); the temporal match acts on every stream
+    const bool selected = stereo_mode != 0;
+    if (selected && kpset_none_selected(ks)) return SLAM_OK;
     KpMatchArgs M;
     M.from = from0->view; M.to = to0->view; M.zs_from = from0->zstride; M.zs_to = to0->zstride;
     M.tune = t;
@@ -659,9 +662,9 @@ static int kpset_match(slam_ctx *ctx, slam_kpset *ks, const slam_pyr *from0, con
     if (!params) { zero.assign((size_t)ks->S * KP_PAR, 0.0); for (int s = 0; s < ks->S; s++) { zero[KP_PAR * s + KP_PAR_CAM] = zero[KP_PAR * s + KP_PAR_CAM + 1] = 1.0; } params = zero.data(); }
     rc = kpset_stage_params(ctx, ks, params, (size_t)ks->S * KP_PAR, &M.par);
     if (rc) return rc;
-    rc = kpset_build_worklist(ctx, ks, M.H, M.W);
+    rc = kpset_build_worklist(ctx, ks, M.H, M.W, selected);
     if (rc) return rc;
-    int nb = kpset_grid_bound(ks, n_bound);
+    int nb = selected ? kpset_sel_grid_bound(ks, n_bound) : kpset_grid_bound(ks, n_bound);
     // (measurement knob) cap the launch: every wave then walks several keypoints (the kernel loops) instead of one wave being dispatched per keypoint
     static const int grid_cap = [] { const char *v = getenv("SLAMHIP_LK_GRID"); return v ? atoi(v) : 0; }();
     if (grid_cap > 0 && nb > grid_cap) nb = grid_cap;
@@ -673,7 +676,7 @@ static int kpset_match(slam_ctx *ctx, slam_kpset *ks, const slam_pyr *from0, con
       if (tol) lk_launch(t.window, [&](auto N) { hipLaunchKernelGGL((k_kpset_match<N.value, true>), dim3(lk_grid(nb)), dim3(64), 0, ctx->stream, M); });
       else lk_launch(t.window, [&](auto N) { hipLaunchKernelGGL((k_kpset_match<N.value, false>), dim3(lk_grid(nb)), dim3(64), 0, ctx->stream, M); }); }
     HIP_TRY(ctx, hipGetLastError());
-    return kpset_compact(ctx, ks, 0, nullptr);                   // lost keypoints (st = 0) leave the lists; stable
+    return kpset_compact(ctx, ks, 0, nullptr, selected);         // lost keypoints (st = 0) leave the lists; stable
 }
 
 // optical_flow_matching!(map_manager, frame, from, to, false) for the S streams of the set (enqueue only).

@@ -25,7 +25,7 @@ module SLAMHipStreams
 
 import ..SLAMHip: LIB, ctx, check
 
-export PyramidBatch, FrameRing, KeypointSet, upload!, update!, flow_match!, stereo_match!, remove!, detect!, detect_describe!, describe_batch, keyframe!,
+export PyramidBatch, FrameRing, KeypointSet, upload!, update!, flow_match!, stereo_match!, remove!, detect!, detect_describe!, describe_batch, keyframe!, select!, selection,
        triangulate!, triangulate_temporal!, compute_pose_5pt!, compute_pose!, frame_stats, keyframe_required, counts, download, stream_params
 
 const HIP = "libamdhip64"
@@ -193,6 +193,26 @@ end
 
 # create_keyframe! as far as the lists go (map_manager.jl:60-96); call after detect!
 keyframe!(k::KeypointSet) = (check(ccall((:slam_kpset_keyframe, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), ctx(), k.h)); k)
+
+# The streams the six key-frame seams act on (detect!, detect_describe!, keyframe!, stereo_match!, triangulate!, triangulate_temporal!): mask = S
+# entries, non-zero / true = selected (the `required` of keyframe_required as it is), or nothing = every stream.  Every other call acts on all
+# streams.  The selection holds until the next select!; the bytes are staged, `mask` is free on return.
+function select!(k::KeypointSet, mask::Union{Nothing,AbstractVector})
+    if mask === nothing
+        check(ccall((:slam_kpset_select, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{UInt8}), ctx(), k.h, C_NULL))
+    else
+        length(mask) == k.S || throw(ArgumentError("select!: $(length(mask)) entries for $(k.S) streams"))
+        m = UInt8[x != 0 ? 0x01 : 0x00 for x in mask]
+        GC.@preserve m check(ccall((:slam_kpset_select, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{UInt8}), ctx(), k.h, m))
+    end
+    k
+end
+"the current selection as S Bools (all true when none is set)"
+function selection(k::KeypointSet)
+    m = zeros(UInt8, k.S)
+    check(ccall((:slam_kpset_selection, LIB[]), Cint, (Ptr{Cvoid}, Ptr{UInt8}), k.h, m))
+    m .!= 0
+end
 
 # triangulate_stereo! (mapper.jl:142-183): P1, P2 4 x 4 projection matrices, T21 right <- left, cam1 / cam2 = (fx, fy, cx, cy), Twc 16 x S
 function triangulate!(k::KeypointSet, P1::Matrix{Float64}, P2::Matrix{Float64}, T21::Matrix{Float64}, cam1, cam2, Twc::Matrix{Float64};

@@ -3,6 +3,7 @@ Frame.keypoints (src/frame.jl) for the calls of the front-end / mapper hot path 
 (src/map_manager.jl:451-564), extract_keypoints! (:98-113), triangulate_stereo! (src/mapper.jl:142-183) -- kept in HBM
 between calls.  Only `counts()`, `frame_stats()` (the statistics the key-frame decision reads), the pose calls, `upload()` and `download()`
 touch the host."""
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -93,6 +94,37 @@ class KeypointSet:
         out = np.zeros(self.S, dtype=np.int32)
         c.check(c.lib.slam_kpset_counts(c.h, self.h, L.ptr(out, L.i32p)))
         return out
+
+    # ---- the streams the six key-frame seams act on (slam_kpset_select) ----
+    def select(self, mask, ctx=None):
+        """The streams detect / detect_describe / keyframe / stereo_match / triangulate / triangulate_temporal act on: mask = S entries, non-zero
+        (or True) = selected -- the `required` of keyframe_required as it is -- or None = every stream.  Every other call acts on all streams.  The
+        selection is a property of the set and holds until the next select(); an unselected stream comes out of the six seams byte for byte as it
+        went in.  Enqueue-only; the mask is staged, the caller's array is free on return."""
+        c = ctx or self.ctx
+        if mask is None:
+            c.check(c.lib.slam_kpset_select(c.h, self.h, None))
+            return
+        m = np.ascontiguousarray(np.asarray(mask).reshape(-1) != 0, dtype=np.uint8)
+        if m.shape != (self.S,):
+            raise ValueError(f"select: {m.size} entries for {self.S} streams")
+        c.check(c.lib.slam_kpset_select(c.h, self.h, L.ptr(m, L.u8p)))
+
+    def selection(self):
+        """the current selection as (S,) bool (all True when none is set)"""
+        m = np.zeros(self.S, dtype=np.uint8)
+        self.ctx.check(self.ctx.lib.slam_kpset_selection(self.h, L.ptr(m, L.u8p)))
+        return m.astype(bool)
+
+    @contextlib.contextmanager
+    def selected(self, mask, ctx=None):
+        """with ks.selected(mask): ...  -- the key-frame seams inside act on `mask`; the previous selection is restored on the way out"""
+        before = self.selection()
+        self.select(mask, ctx=ctx)
+        try:
+            yield self
+        finally:
+            self.select(before, ctx=ctx)
 
     # ---- enqueue-only calls ----
     def flow_match(self, from_batch, to_batch, params, stream_params_=None, prior=0, pyramid_levels_3d=1, iterations=30, n_bound=0, ctx=None):
