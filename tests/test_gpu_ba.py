@@ -90,6 +90,8 @@ def test_local_ba_edge_cases(slam, orc, syn):
 
 
 def test_pnp_ba_matches_oracle(slam, orc, syn):
+    """the END of a converged run on an easy scene (every LM step accepted) against the oracle: a parity smoke test.  Its 1e-8 / 1e-9 bars are
+    ~ 1e7 times the f64 error; the accuracy test of the refinement, stage by stage and at rounding level, is test_gpu_pnp_model.py."""
     for seed in range(3):
         s = syn.pnp_scene(n=300, seed=seed)
         pose, e0, e1, ol, no = slam.pnp_bundle_adjustment(s["cam"], s["pose0"], s["pixels_yx"], s["points"], repr_eps=3.0)
@@ -106,8 +108,15 @@ def test_pnp_ba_identity_sentinel(slam, orc, syn):
     pose, e0, e1, ol, no = slam.pnp_bundle_adjustment(s["cam"], s["pose0"], px, s["points"], repr_eps=3.0)
     rp, r0, r1, rol, rno = orc.pnp_ba(s["cam"], s["pose0"], px, s["points"], repr_eps=3.0)
     assert no == rno and np.array_equal(ol, rol)
-    if len(px) - rno < 5:
-        assert np.array_equal(pose, np.eye(4)) and np.array_equal(rp, np.eye(4))   # bundle_adjustment.jl:157-161
+    assert len(px) - rno < 5                                                    # the identity exit IS taken
+    assert np.array_equal(pose, np.eye(4)) and np.array_equal(rp, np.eye(4))   # bundle_adjustment.jl:157-161
+    # the mirror: one inlier above the exit (7 points, 2 displaced: exactly five remain) is refined
+    s = syn.pnp_scene(n=7, seed=1, outlier_frac=0.0)
+    px = s["pixels_yx"].copy(); px[:2] += 300.0
+    pose, e0, e1, ol, no = slam.pnp_bundle_adjustment(s["cam"], s["pose_gt"], px, s["points"], repr_eps=9.0, iters_fast=0)
+    rp, r0, r1, rol, rno = orc.pnp_ba(s["cam"], s["pose_gt"], px, s["points"], repr_eps=9.0, iters_fast=0)
+    assert no == rno == 2 and np.array_equal(ol, rol) and len(px) - rno == 5
+    assert not np.array_equal(pose, np.eye(4)) and np.abs(pose - rp).max() <= 1e-8
 
 
 @pytest.mark.parametrize("P,M", [(50, 10000), (100, 40000)])
