@@ -24,6 +24,24 @@
 #define KPSET_SORT_LDS_BYTES 65536
 static int work_band() { static const int band = [] { const char *v = getenv("SLAMHIP_WORK_BAND"); const int b = v ? atoi(v) : WORK_BAND_PX; return b < 0 ? 0 : b; }(); return band; }
 struct WorkOrder { int H, W, band, pad; };       // band 0: slot order; pad: power of two >= cap whose words fit KPSET_SORT_LDS_BYTES
+// SLAMHIP_NO_MATCH_REC=1, read once per process: the matches build no work records and run their record-less prologue (the A/B of round 22)
+bool kpset_match_records() { static const bool on = [] { const char *v = getenv("SLAMHIP_NO_MATCH_REC"); return !(v && atoi(v) != 0); }(); return on; }
+// the work record of entry idx (work_order.hpp: work_rec_slot) of a list of ceil(ntot / 8) = per entries per XCD: slot q of stream s
+__device__ __forceinline__ void kp_write_rec(const KpWorkRecs &R, const double *yx, int H, int W, int idx, int per, int q, int s)
+{
+    const int at = work_rec_slot(idx, per, R.stride);
+    if (at >= WORK_XCDS * R.stride) return;                      // (cannot happen while count <= cap: ntot <= S cap, so per <= stride; it guards the region)
+    KpWorkRec r;
+    r.py = yx[2 * (size_t)q]; r.px = yx[2 * (size_t)q + 1];
+    const bool is3 = R.is3d[q] != 0;
+    // the prior is formed for every keypoint and kept for the 3-D ones: under `if (is3)` the loads of the map point and of the parameter slot would wait
+    // for the flag -- one more dependent round trip per entry (a 2-D keypoint's xyz holds whatever the slot held: read, computed with, dropped)
+    double pry, prx;
+    kp_match_prior(R.prior, R.xyz + 3 * (size_t)q, R.par + KP_PAR * (size_t)s, r.py, r.px, pry, prx);
+    r.pry = is3 ? pry : r.py; r.prx = is3 ? prx : r.px;
+    r.q = q; r.s = s; r.flags = (is3 ? KPREC_3D : 0) | (kp_in_image(r.pry, r.prx, H, W) ? KPREC_INSIDE : 0); r.pad = 0;
+    R.rec[at] = r;
+}
 // k_kpset_worklist, k_kpset_compact and k_kpset_keyframe, plain and selected (slam_kpset_select): kpset_kernels.inc, included once per form
 #define SEL_NAME(k) k
 #define SEL_ARG
@@ -51,16 +69,19 @@ struct WorkOrder { int H, W, band, pad; };       // band 0: slot order; pad: pow
 // H x W: the image the positions live in (the match that follows reads its planes); H <= 0: slot order -- the triangulation
 // kernels read a few bytes per keypoint and gain nothing from an order
 // selected: the caller is one of the six key-frame seams, which honour the set's selection (it has returned already when no stream is selected)
-int kpset_build_worklist(slam_ctx *ctx, slam_kpset *ks, int H, int W, bool selected)
+// match: the caller is a match with this prior and these staged parameters -- the entries' work records are written too (unless SLAMHIP_NO_MATCH_REC)
+int kpset_build_worklist(slam_ctx *ctx, slam_kpset *ks, int H, int W, bool selected, const KpMatchPrior *match)
 {
     WorkOrder O;
     O.H = H; O.W = W; O.pad = ks->sort_pad; O.band = H > 0 && W > 0 && ks->sort_pad > 0 ? work_band() : 0;
     const size_t lds = O.band > 0 ? (size_t)ks->sort_pad * 8 : 0;
+    KpWorkRecs R = {nullptr, 0, 0, nullptr, nullptr, nullptr};
+    if (match && kpset_match_records()) R = {ks->rec, ks->rec_stride, match->prior, match->par, ks->v.xyz, ks->v.is3d};
     if (selected && ks->n_sel != KPSEL_ALL)
-        hipLaunchKernelGGL(k_kpset_worklist_sel, dim3(ks->n_sel), dim3(256), lds, ctx->stream, (const int *)ks->v.count, ks->S, ks->v.cap, ks->work, ks->ntot, (const double *)ks->v.yx, O,
+        hipLaunchKernelGGL(k_kpset_worklist_sel, dim3(ks->n_sel), dim3(256), lds, ctx->stream, (const int *)ks->v.count, ks->S, ks->v.cap, ks->work, ks->ntot, (const double *)ks->v.yx, O, R,
                            (const int *)ks->sel_idx);
     else
-        hipLaunchKernelGGL(k_kpset_worklist, dim3(ks->S), dim3(256), lds, ctx->stream, (const int *)ks->v.count, ks->S, ks->v.cap, ks->work, ks->ntot, (const double *)ks->v.yx, O);
+        hipLaunchKernelGGL(k_kpset_worklist, dim3(ks->S), dim3(256), lds, ctx->stream, (const int *)ks->v.count, ks->S, ks->v.cap, ks->work, ks->ntot, (const double *)ks->v.yx, O, R);
     HIP_TRY(ctx, hipGetLastError());
     return SLAM_OK;
 }
@@ -357,6 +378,8 @@ static size_t kpset_regions(slam_kpset *ks, char *base)
     region(v.fkf, n * 4); region(v.kfcount, S * 4);
     region(ks->sel_idx, S * 4 + S);                               // the selection as one block (one staged copy): S indices, then the S mask bytes
     if (base) ks->sel_mask = (uint8_t *)(ks->sel_idx + S);
+    ks->rec_stride = work_rec_stride((long long)n);
+    region(ks->rec, (size_t)WORK_XCDS * ks->rec_stride * sizeof(KpWorkRec));      // the work records of a match (regions start 256-byte aligned)
     return Lo.size();
 }
 

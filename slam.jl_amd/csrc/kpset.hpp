@@ -3,6 +3,7 @@
 #pragma once
 #include "common.hpp"
 #include "kpset_select.hpp"
+#include "geom_device.hpp"
 #include <initializer_list>
 
 // The per-keypoint arrays of S lock-stepped streams: stream s owns the slots [s * cap, s * cap + count[s]) of every
@@ -33,6 +34,41 @@ struct KpsetView {
 constexpr int KP_PAR = 32, KP_PAR_CAM = 16, KP_PAR_DIST = 20, KP_PAR_SHIFT = 24;
 __device__ __forceinline__ void load_cam(const double *par, double *cam, double *dist) { for (int k = 0; k < 4; k++) { cam[k] = par[KP_PAR_CAM + k]; dist[k] = par[KP_PAR_DIST + k]; } }
 
+// Where a match starts looking for a 3-D keypoint at (py, px) (map_manager.jl:484-504): prior 0 the pixel itself, 1 the projection of its map
+// point X through the stream's slot P (Tcw, intrinsics, distortion), 2 the pixel + the slot's shift.  The ONE copy: k_kpset_worklist computes it
+// into the keypoint's work record, the record-less prologue of k_kpset_match (SLAMHIP_NO_MATCH_REC) computes it itself -- same operations in the
+// same order, no contraction (-ffp-contract=off): the same bits at both sites (tests/test_gpu_match_records.py).
+__device__ __forceinline__ void kp_match_prior(int prior, const double *X, const double *P, double py, double px, double &pry, double &prx)
+{
+    pry = py; prx = px;
+    if (prior == 1) {
+        const double X0 = X[0], X1 = X[1], X2 = X[2];
+        const double cx = ((P[0] * X0 + P[4] * X1) + P[8] * X2) + P[12];
+        const double cy = ((P[1] * X0 + P[5] * X1) + P[9] * X2) + P[13];
+        const double cz = ((P[2] * X0 + P[6] * X1) + P[10] * X2) + P[14];
+        pdn_to_pixel(P + KP_PAR_CAM, P + KP_PAR_DIST, cy / cz, cx / cz, pry, prx);     // project_undistort (camera.jl:79-82)
+    } else if (prior == 2) { pry = py + P[KP_PAR_SHIFT]; prx = px + P[KP_PAR_SHIFT + 1]; }
+}
+__device__ __forceinline__ bool kp_in_image(double y, double x, int H, int W) { return 1 <= y && y <= (double)H && 1 <= x && x <= (double)W; }   // in_image (camera.jl:90-92)
+
+// What k_kpset_match needs of a keypoint before its first level visit, written by k_kpset_worklist for every entry of the work list when
+// the caller is a match (KpWorkRecs::rec != nullptr): the match's prologue is then ONE wave-uniform fetch whose address depends on kernel
+// arguments alone, instead of the chain ntot -> work[idx] -> yx / is3d / par -> xyz.  Placement: work_order.hpp (work_rec_slot).
+struct alignas(16) KpWorkRec {
+    double py, px;               // the keypoint's pixel (yx[q])
+    double pry, prx;             // its prior (kp_match_prior; the pixel itself for a 2-D keypoint)
+    int q, s;                    // slot in the set's arrays, stream
+    int flags;                   // KPREC_3D: is3d[q] != 0, KPREC_INSIDE: the prior lies in the image
+    int pad;
+};
+constexpr int KPREC_3D = 1, KPREC_INSIDE = 2;
+static_assert(sizeof(KpWorkRec) == 48 && alignof(KpWorkRec) == 16, "the fetch of k_kpset_match (lk.hip) restates the layout");
+// the record side of a work-list launch (rec == nullptr: none are written -- the triangulation seams, the pose seams, SLAMHIP_NO_MATCH_REC)
+struct KpWorkRecs {
+    KpWorkRec *rec; int stride;  // 8 x stride records (work_rec_stride)
+    int prior; const double *par, *xyz; const uint8_t *is3d;
+};
+
 // The set: the lists (v) and what is not per-keypoint state of them; all arrays but the kf_* ones live in one allocation.
 struct slam_kpset {
     int device = 0, S = 0;
@@ -41,6 +77,8 @@ struct slam_kpset {
     int *work = nullptr;         // [S cap] live slots, streams back to back (each stream's segment in the order of work_order.hpp)
     int sort_pad = 0;            // power of two >= cap the work list's sort pads a segment to; 0: slot order (decided at creation)
     int *ntot = nullptr;         // [4]: number of live slots, ...
+    KpWorkRec *rec = nullptr;    // [8 rec_stride] the work list's records for k_kpset_match (written by the work list of a match; placement: work_order.hpp)
+    int rec_stride = 0;          // ceil(S cap / 8)
     int64_t *next_id = nullptr;  // [S]
     // per-stream parameters of a call (prior shift / pose): ring of 8 slots of S x KP_PAR doubles, staged through pinned host
     // memory with an event per slot, so that the enqueue-only calls never wait for an earlier call's copy
@@ -69,7 +107,9 @@ struct slam_kpset {
 int kpset_stage_params(slam_ctx *ctx, slam_kpset *ks, const double *host, size_t n, const double **dev_out);
 // `selected` (both): the caller is a key-frame seam and honours the set's selection -- only the selected streams' segments / lists; the caller has returned
 // before when no stream is selected (kpset_none_selected)
-int kpset_build_worklist(slam_ctx *ctx, slam_kpset *ks, int H, int W, bool selected = false);   // H <= 0: slot order (no image, or an order would not pay)
+struct KpMatchPrior { int prior; const double *par; };           // what a match hands the work list for the records: its prior mode and its staged parameters (device)
+bool kpset_match_records();                                      // false under SLAMHIP_NO_MATCH_REC=1 (read once per process)
+int kpset_build_worklist(slam_ctx *ctx, slam_kpset *ks, int H, int W, bool selected = false, const KpMatchPrior *match = nullptr);   // H <= 0: slot order (no image, or an order would not pay)
 int kpset_compact(slam_ctx *ctx, slam_kpset *ks, int mode, const uint8_t *flags_dev, bool selected = false);
 inline bool kpset_none_selected(const slam_kpset *ks) { return ks->n_sel == 0; }
 // the stream dimension of a key-frame seam's launch, and the table its selected kernel form reads (nullptr: the unselected form)

@@ -7,6 +7,7 @@
 // An include, not a template over a shared __device__ body: the plain kernels then compile from the token sequence they had before there was a
 // selection, and their code objects stay instruction for instruction what they were (profiles/r21a_select_kernel_table.txt; with an inlined body
 // k_kpset_worklist came out with two operands of one instruction swapped, the detection kernels with other registers).
+// (Round 22 gave k_kpset_worklist the work records of a match -- both forms, here, once: profiles/r22a_lk_kernel_table.txt has its new figures.)
 
 // live slots of all streams back to back + their number.  One small workgroup per stream (it sums the counts before its own: S
 // loads): a single 1024-thread workgroup had to wait for sixteen free wave slots on one CU while the pyramid kernels fill the chip
@@ -17,7 +18,8 @@
 // sums the counts itself (S loads, no barrier); the sort's words are (key << 32 | slot), all different.
 // Selected form: only the selected streams' segments are laid back to back and ntot is their sum, so whatever walks the list (k_kpset_match,
 // both triangulation kernels) never sees a slot of an unselected stream.
-__global__ __launch_bounds__(256) void SEL_NAME(k_kpset_worklist)(const int *count, int S, int cap, int *work, int *ntot, const double *yx, WorkOrder O SEL_ARG)
+// R.rec != nullptr (the caller is a match): entry off + j also gets its work record (KpWorkRec, kpset.hpp; placed by work_rec_slot, work_order.hpp).
+__global__ __launch_bounds__(256) void SEL_NAME(k_kpset_worklist)(const int *count, int S, int cap, int *work, int *ntot, const double *yx, WorkOrder O, KpWorkRecs R SEL_ARG)
 {
     extern __shared__ unsigned long long s_word[];
     const int s = SEL_STREAM(blockIdx.x), tid = threadIdx.x, lane = tid & 63;
@@ -26,9 +28,9 @@ __global__ __launch_bounds__(256) void SEL_NAME(k_kpset_worklist)(const int *cou
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) { off += __shfl_xor(off, m); t += __shfl_xor(t, m); }
     if (SEL_SELF(s) == 0 && tid == 0) ntot[0] = t;
-    const int n = count[s];
+    const int n = count[s], per = work_rec_per(t);
     if (O.band <= 0 || n > O.pad) {                              // (n > pad cannot happen: n <= cap <= pad; it guards the LDS array)
-        for (int j = tid; j < n; j += 256) work[off + j] = s * cap + j;
+        for (int j = tid; j < n; j += 256) { work[off + j] = s * cap + j; if (R.rec) kp_write_rec(R, yx, O.H, O.W, off + j, per, s * cap + j, s); }
         return;
     }
     int P = 1;
@@ -46,7 +48,11 @@ __global__ __launch_bounds__(256) void SEL_NAME(k_kpset_worklist)(const int *cou
             }
             __syncthreads();
         }
-    for (int j = tid; j < n; j += 256) work[off + j] = s * cap + (int)(unsigned)s_word[j];
+    for (int j = tid; j < n; j += 256) {
+        const int q = s * cap + (int)(unsigned)s_word[j];
+        work[off + j] = q;
+        if (R.rec) kp_write_rec(R, yx, O.H, O.W, off + j, per, q, s);        // a match follows: everything its prologue looks up, where its wave will read it
+    }
 }
 
 // Stable in-place compaction of every stream's list, one 256-thread workgroup per stream.

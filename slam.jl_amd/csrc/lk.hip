@@ -560,46 +560,87 @@ struct KpMatchArgs {
     int prior;                 // 0: prior = the pixel itself, 1: projection of the map point (pose-based), 2: pixel + per-stream shift
     const double *par;
     int H, W, stereo_mode; double epipolar;
+    const KpWorkRec *rec; int rec_stride, use_rec;      // the work list's records (the set's region, always); use_rec 0 under SLAMHIP_NO_MATCH_REC: none were written, the record-less prologue
 };
+// a wave-uniform record through the scalar data cache (constant address space: the records are written by the kernel before this one, never by
+// it): three 16-byte scalar loads into SGPRs, no VGPR and no vector-memory slot spent on values every lane shares
+__device__ __forceinline__ KpWorkRec load_rec_uniform(const KpWorkRec *p)
+{
+    typedef int rec_v4i __attribute__((ext_vector_type(4)));
+    const __attribute__((address_space(4))) rec_v4i *c = (const __attribute__((address_space(4))) rec_v4i *)p;
+    const rec_v4i a = c[0], b = c[1], d = c[2];
+    KpWorkRec r;
+    r.py = __hiloint2double(a.y, a.x); r.px = __hiloint2double(a.w, a.z);
+    r.pry = __hiloint2double(b.y, b.x); r.prx = __hiloint2double(b.w, b.z);
+    r.q = d.x; r.s = d.y; r.flags = d.z; r.pad = 0;
+    return r;
+}
+// The first record of a wave AND ntot in one round trip: the three scalar loads are issued back to back and waited for once.  Spelled as one
+// asm block because the compiler, given the same loads in C++, requests ntot first, waits, and sinks the record's loads into the loop behind
+// that wait (they are invariant to it): two dependent round trips again.
+__device__ __forceinline__ KpWorkRec load_rec_and_ntot(const KpWorkRec *p, const int *ntot_p, int &ntot)
+{
+    typedef int rec_v4i __attribute__((ext_vector_type(4)));
+    typedef int rec_v8i __attribute__((ext_vector_type(8)));
+    rec_v8i a; rec_v4i d;
+    asm volatile("s_load_dwordx8 %0, %3, 0x0\n\ts_load_dwordx4 %1, %3, 0x20\n\ts_load_dword %2, %4, 0x0\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&s"(a), "=&s"(d), "=&s"(ntot) : "s"(p), "s"(ntot_p) : "memory");
+    KpWorkRec r;
+    r.py = __hiloint2double(a[1], a[0]); r.px = __hiloint2double(a[3], a[2]);
+    r.pry = __hiloint2double(a[5], a[4]); r.prx = __hiloint2double(a[7], a[6]);
+    r.q = d[0]; r.s = d[1]; r.flags = d[2]; r.pad = 0;
+    return r;
+}
 template <int LK_MAXE, bool TOL>
 __global__ __launch_bounds__(64) LK_OCC void k_kpset_match(KpMatchArgs M)
 {
-    const int ntot = M.ntot[0], per = (ntot + LK_XCDS - 1) / LK_XCDS;
+    LKT_BEGIN;
+    // The first round's work record (KpWorkRec, kpset.hpp; written by k_kpset_worklist): its place depends on the workgroup index and on kernel
+    // arguments alone (work_order.hpp), so its fetch is issued together with the load of ntot -- one memory round trip before the first level visit
+    const int xcd = (int)(blockIdx.x % LK_XCDS), slot0 = (int)(blockIdx.x / LK_XCDS);
+    // (fetched without a branch, also where the records are not in use: the region exists and holds stale bytes then)
+    int ntot;
+    KpWorkRec rc = load_rec_and_ntot(M.rec + ((size_t)xcd * M.rec_stride + slot0), M.ntot, ntot);   // in the region whatever ntot is: slot0 < gridDim.x / 8 <= rec_stride
+    const int per = (ntot + LK_XCDS - 1) / LK_XCDS;
     // each XCD a contiguous eighth of the work list (streams back to back, each sorted by x-band and row).  The grid is sized from the host's bound of the list lengths,
     // which is only a hint: a launch smaller than the lists walks them in several rounds (a keypoint that no wave visited would keep
     // the previous call's status and be compacted away or kept from stale data)
-    for (int slotx = (int)(blockIdx.x / LK_XCDS); slotx < per; slotx += (int)(gridDim.x / LK_XCDS)) {
-    const int idx = (int)(blockIdx.x % LK_XCDS) * per + slotx;
+    for (int slotx = slot0; slotx < per; slotx += (int)(gridDim.x / LK_XCDS)) {
+    const int idx = xcd * per + slotx;
     if (idx >= ntot) break;
-    const size_t q = (size_t)M.work[idx];
-    const int s = (int)(q / M.cap);
-    const double *P = M.par + KP_PAR * (size_t)s, *cam = P + KP_PAR_CAM, *dist = P + KP_PAR_DIST;
-    const double py = M.yx[2 * q], px = M.yx[2 * q + 1];
-    const bool is3 = M.is3d[q] != 0;
-    double pry = py, prx = px;
-    if (is3) {
-        if (M.prior == 1) {
-            const double X0 = M.xyz[3 * q], X1 = M.xyz[3 * q + 1], X2 = M.xyz[3 * q + 2];
-            const double cx = ((P[0] * X0 + P[4] * X1) + P[8] * X2) + P[12];
-            const double cy = ((P[1] * X0 + P[5] * X1) + P[9] * X2) + P[13];
-            const double cz = ((P[2] * X0 + P[6] * X1) + P[10] * X2) + P[14];
-            pdn_to_pixel(cam, dist, cy / cz, cx / cz, pry, prx);                  // project_undistort (camera.jl:79-82)
-        } else if (M.prior == 2) { pry = py + P[KP_PAR_SHIFT]; prx = px + P[KP_PAR_SHIFT + 1]; }
+    size_t q; int s; double py, px, pry, prx; bool is3, inside;
+    // 2^-levels3d from its exponent (as lk_level's iscale): 1.0 / (1 << levels3d) bit for bit, which k_flow_match still spells as the quotient.
+    // (For both prologues: the compiler hoists a quotient in the record-less branch in front of the loop, where every wave would pay for it.)
+    const double scale3 = __hiloint2double((1023 - M.tune.levels3d) << 20, 0);
+    if (M.use_rec) {
+        // everything from the record: no work[], yx, is3d, xyz or par load, no division
+        if (slotx != slot0) rc = load_rec_uniform(M.rec + ((size_t)xcd * M.rec_stride + slotx));   // later rounds (slotx < per <= rec_stride)
+        q = (size_t)rc.q; s = rc.s; py = rc.py; px = rc.px; pry = rc.pry; prx = rc.prx;
+        is3 = (rc.flags & KPREC_3D) != 0; inside = (rc.flags & KPREC_INSIDE) != 0;
+    } else {
+        // the record-less prologue (SLAMHIP_NO_MATCH_REC=1): ntot -> work[idx] -> yx, is3d, par -> xyz
+        q = (size_t)M.work[idx];
+        s = (int)(q / M.cap);
+        py = M.yx[2 * q]; px = M.yx[2 * q + 1];
+        is3 = M.is3d[q] != 0;
+        pry = py; prx = px;
+        if (is3) kp_match_prior(M.prior, M.xyz + 3 * q, M.par + KP_PAR * (size_t)s, py, px, pry, prx);
+        inside = kp_in_image(pry, prx, M.H, M.W);
     }
-    const bool inside = 1 <= pry && pry <= (double)M.H && 1 <= prx && prx <= (double)M.W;   // in_image (camera.jl:90-92)
+    const double *P = M.par + KP_PAR * (size_t)s, *cam = P + KP_PAR_CAM, *dist = P + KP_PAR_DIST;   // (the stereo check's lens model)
     const bool lane0 = (threadIdx.x & 63) == 0;
     if (is3 && !inside) {
         if (lane0) { M.st[q] = M.stereo_mode ? 0 : 2; if (M.stereo_mode) M.stereo[q] = 0; }
         continue;
     }
+    LKT(6);                                                      // the prologue: wave start (or the previous keypoint's end) to the keypoint's position, prior and decision in registers
     const size_t offF = (size_t)s * M.zs_from, offT = (size_t)s * M.zs_to;
     double ny = nan(""), nx = nan("");
     bool ok = false;
     for (int att = is3 ? 0 : 1; att < 2 && !ok; att++) {                                             // mirrors k_flow_match's two attempts
         double dy = 0.0, dx = 0.0;
         if (att == 0) {
-            const double scale = 1.0 / (double)(1 << M.tune.levels3d);
-            dy = scale * (pry - py); dx = scale * (prx - px);                                        // map_manager.jl:494,504
+            dy = scale3 * (pry - py); dx = scale3 * (prx - px);                                      // map_manager.jl:494,504
         }
         ok = fb_point<LK_MAXE, TOL>(M.from, M.to, py, px, dy, dx, M.tune, att == 0 ? M.tune.levels3d : M.tune.pyramid_levels, ny, nx, offF, offT);
     }
@@ -616,6 +657,7 @@ __global__ __launch_bounds__(64) LK_OCC void k_kpset_match(KpMatchArgs M)
         M.stereo[q] = ok ? 1 : 0;
         M.st[q] = 2;
     }
+    LKT(7);                                                      // the keypoint's level visits and its stores
     }
 }
 
@@ -662,8 +704,10 @@ static int kpset_match(slam_ctx *ctx, slam_kpset *ks, const slam_pyr *from0, con
     if (!params) { zero.assign((size_t)ks->S * KP_PAR, 0.0); for (int s = 0; s < ks->S; s++) { zero[KP_PAR * s + KP_PAR_CAM] = zero[KP_PAR * s + KP_PAR_CAM + 1] = 1.0; } params = zero.data(); }
     rc = kpset_stage_params(ctx, ks, params, (size_t)ks->S * KP_PAR, &M.par);
     if (rc) return rc;
-    rc = kpset_build_worklist(ctx, ks, M.H, M.W, selected);
+    const KpMatchPrior mp = {prior, M.par};
+    rc = kpset_build_worklist(ctx, ks, M.H, M.W, selected, &mp);  // with every entry's work record, the match's whole prologue
     if (rc) return rc;
+    M.rec = ks->rec; M.rec_stride = ks->rec_stride; M.use_rec = kpset_match_records() ? 1 : 0;
     int nb = selected ? kpset_sel_grid_bound(ks, n_bound) : kpset_grid_bound(ks, n_bound);
     // (measurement knob) cap the launch: every wave then walks several keypoints (the kernel loops) instead of one wave being dispatched per keypoint
     static const int grid_cap = [] { const char *v = getenv("SLAMHIP_LK_GRID"); return v ? atoi(v) : 0; }();

@@ -36,6 +36,21 @@ WORK_HD uint32_t work_key(double y, double x, int H, int W, int band)
     return ((work_clamp_px(x, W) / (uint32_t)(band < 1 ? 1 : band)) << 16) | work_clamp_px(y, H);
 }
 
+// ---- where the work records live (KpWorkRec, kpset.hpp) ---------------------------------------------------------------------------------
+// k_kpset_match deals its workgroups round-robin to the WORK_XCDS chips of the package (workgroup b runs on XCD b % 8) and gives each one
+// contiguous eighth of the list: with per = ceil(ntot / 8), XCD x walks the entries [x per, min((x + 1) per, ntot)).  The records are laid out
+// for that walk: 8 rows of `stride` = ceil(S cap / 8) records (>= per for every list the set can hold), entry idx in row idx / per at column
+// idx % per.  Workgroup b's first record is then at (b % 8) stride + b / 8 -- kernel arguments and the workgroup index alone, so its fetch does
+// not wait for ntot -- and the entry is valid iff its column r < per and (b % 8) per + r < ntot.  Slots no entry maps to hold stale bytes: they
+// lie inside the 8 x stride records and are never interpreted.
+#define WORK_XCDS 8
+WORK_HD int work_rec_stride(long long slots) { return (int)((slots + WORK_XCDS - 1) / WORK_XCDS); }             // slots = S x cap
+WORK_HD int work_rec_per(int ntot) { return (ntot + WORK_XCDS - 1) / WORK_XCDS; }
+// entry idx (0 <= idx < ntot, per = work_rec_per(ntot) >= 1) -> record slot, < 8 stride
+WORK_HD int work_rec_slot(int idx, int per, int stride) { return (idx / per) * stride + idx % per; }
+// the inverse as the match kernel applies it: row x (0 .. 7), column r -> entry, or -1 where the slot holds none
+WORK_HD int work_rec_entry(int x, int r, int per, int ntot) { return r < per && x * per + r < ntot ? x * per + r : -1; }
+
 // Which instantiation of the tracking kernels (lk.hip: 3, 6 or 9 template slots per lane) a window_size runs on: the smallest
 // whose 64 lanes hold the (2 w + 1)^2 window elements, the 9-slot one (uncached path) beyond.  The host launches by lk_slots,
 // lk_level decides `cached` from the same element count.
