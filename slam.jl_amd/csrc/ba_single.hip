@@ -1236,8 +1236,9 @@ __device__ __forceinline__ void pnp_body(const PnPArgs &A)
     else it2 = pnp_lm(A, gpx, gpts, goutl, X, 1, A.iterations, sh, red, Xt, dxs, flags, &ssr2);
     __syncthreads();
     if (tid == 0) {
-        for (int a = 0; a < 6; a++) A.result[a] = X[a];
-        A.result[6] = err_init; A.result[7] = ssr2; A.result[8] = no; A.result[9] = identity; A.result[10] = it1; A.result[11] = it2;
+        PnPResult &R = *A.result;
+        for (int a = 0; a < 6; a++) R.X[a] = X[a];
+        R.err_init = err_init; R.err_final = ssr2; R.n_outliers = no; R.identity = identity; R.iters1 = it1; R.iters2 = it2;
     }
 }
 
@@ -1256,23 +1257,30 @@ int pnp_launch_device(slam_ctx *ctx, int S, const PnPArgs *args_dev)
     return SLAM_OK;
 }
 
-// RotZYX(pose[1:3,1:3]) -> angles (Rotations.jl), pose column-major: R[i][j] = pose[i + 4j]
-static void pnp_pose_to_x(const double *pose_cw, double *X0)
+// The device side of S refinements over ntot points as regions of the context's scratch: pixels | points | outlier flags | S result records (the
+// inputs keep the 8 bytes of padding they always had), with the pixels and points staged into it
+struct PnPStage { double *px, *pts; uint8_t *outl; PnPResult *res; };
+static int pnp_stage(slam_ctx *ctx, int S, int ntot, const double *pixels_yx, const double *points_xyz, PnPStage *st)
 {
-    const double R11 = pose_cw[0], R21 = pose_cw[1], R31 = pose_cw[2], R12 = pose_cw[4], R22 = pose_cw[5], R13 = pose_cw[8], R23 = pose_cw[9];
-    const double t1 = std::atan2(R21, R11), s1 = std::sin(t1), c1 = std::cos(t1);
-    X0[0] = t1; X0[1] = std::atan2(-R31, std::sqrt(R11 * R11 + R21 * R21)); X0[2] = std::atan2(R13 * s1 - R23 * c1, R22 * c1 - R12 * s1);
-    X0[3] = pose_cw[12]; X0[4] = pose_cw[13]; X0[5] = pose_cw[14];
-}
-static void pnp_x_to_pose(const double *res, double *out_pose)
-{
-    for (int k = 0; k < 16; k++) out_pose[k] = (k % 5 == 0) ? 1.0 : 0.0;
-    if (res[9] == 0.0) {
-        const double s1 = std::sin(res[0]), c1 = std::cos(res[0]), s2 = std::sin(res[1]), c2 = std::cos(res[1]), s3 = std::sin(res[2]), c3 = std::cos(res[2]);
-        const double R[9] = {c1 * c2, c1 * s2 * s3 - s1 * c3, c1 * s2 * c3 + s1 * s3, s1 * c2, s1 * s2 * s3 + c1 * c3, s1 * s2 * c3 - c1 * s3, -s2, c2 * s3, c2 * c3};
-        for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) out_pose[i + 4 * j] = R[3 * i + j];
-        out_pose[12] = res[3]; out_pose[13] = res[4]; out_pose[14] = res[5];
+    Layout D;
+    const auto o_px = D.take<double>((size_t)ntot * 2 + 1), o_pts = D.take<double>((size_t)ntot * 3 + 1); const auto o_outl = D.take<uint8_t>((size_t)ntot + 8); const auto o_res = D.take<PnPResult>(S);
+    char *s;
+    const int rc = slam_scratch(ctx, D.size(), (void **)&s);
+    if (rc) return rc;
+    *st = {o_px.at(s), o_pts.at(s), o_outl.at(s), o_res.at(s)};
+    if (ntot > 0) {
+        HIP_TRY(ctx, hipMemcpyAsync(st->px, pixels_yx, (size_t)ntot * 16, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(st->pts, points_xyz, (size_t)ntot * 24, hipMemcpyHostToDevice, ctx->stream));
     }
+    return SLAM_OK;
+}
+// problem z's record into the caller's outputs (the error and count arrays may be null); the identity pose where the refinement gave up
+static void pnp_decode(const PnPResult &r, int z, double *out_poses, double *err_init, double *err_final, int *n_outliers)
+{
+    if (err_init) err_init[z] = r.err_init; if (err_final) err_final[z] = r.err_final; if (n_outliers) n_outliers[z] = (int)r.n_outliers;
+    double *T = out_poses + 16 * z;
+    for (int k = 0; k < 16; k++) T[k] = (k % 5 == 0) ? 1.0 : 0.0;
+    if (r.identity == 0.0) angles_to_pose(r.X, T);
 }
 
 // S single-pose refinements in one launch: problem z owns points [offsets[z], offsets[z+1]); cams S x 4 (fx, fy,
@@ -1289,42 +1297,30 @@ extern "C" int slam_pnp_ba_batch(slam_ctx *ctx, int S, const int32_t *offsets, c
     const int ntot = offsets[S];
     ARG_TRY(ctx, ntot == 0 || (pixels_yx && points_xyz && outliers));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t pxb = al((size_t)ntot * 16 + 8), ptb = al((size_t)ntot * 24 + 8), ob = al((size_t)ntot + 8), rb = al((size_t)S * 128);
-    char *s;
-    int rc = slam_scratch(ctx, pxb + ptb + ob + rb, (void **)&s);
-    if (rc) return rc;
-    double *d_px = (double *)s, *d_pts = (double *)(s + pxb); uint8_t *d_o = (uint8_t *)(s + pxb + ptb); double *d_res = (double *)(s + pxb + ptb + ob);
+    Layout H;                          // mapped pinned block: the argument blocks (read in place by the kernel), then the host's copy of the records
+    const auto h_args = H.take<PnPArgs>(S); const auto h_res = H.take<PnPResult>(S);
     char *h, *d;
-    rc = slam_pinned(ctx, (size_t)S * sizeof(PnPArgs) + (size_t)S * 128, (void **)&h);
+    int rc = slam_pinned(ctx, H.size(), (void **)&h);
     if (rc) return rc;
     HIP_TRY(ctx, hipHostGetDevicePointer((void **)&d, h, 0));
-    PnPArgs *args = (PnPArgs *)h;
+    PnPStage st;
+    rc = pnp_stage(ctx, S, ntot, pixels_yx, points_xyz, &st);
+    if (rc) return rc;
     for (int z = 0; z < S; z++) {
-        PnPArgs &A = args[z];
+        PnPArgs &A = h_args.at(h)[z];
         A.cam = {cams[4 * z], cams[4 * z + 1], cams[4 * z + 2], cams[4 * z + 3]};
         A.n = offsets[z + 1] - offsets[z]; A.iters_fast = iters_fast; A.iterations = iterations;
         A.depth_eps = depth_eps; A.repr_eps = repr_eps;
-        pnp_pose_to_x(poses_cw + 16 * z, A.X0);
-        A.px = d_px + 2 * (size_t)offsets[z]; A.pts = d_pts + 3 * (size_t)offsets[z]; A.outl = d_o + offsets[z]; A.result = d_res + 16 * z;
-    }
-    if (ntot > 0) {
-        HIP_TRY(ctx, hipMemcpyAsync(d_px, pixels_yx, (size_t)ntot * 16, hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(d_pts, points_xyz, (size_t)ntot * 24, hipMemcpyHostToDevice, ctx->stream));
+        pose_to_angles<4>(poses_cw + 16 * z, poses_cw + 16 * z + 12, A.X0);
+        A.px = st.px + 2 * (size_t)offsets[z]; A.pts = st.pts + 3 * (size_t)offsets[z]; A.outl = st.outl + offsets[z]; A.result = st.res + z;
     }
     { ProfScope span(ctx, "pnp_ba");
-      hipLaunchKernelGGL(k_pnp_batch, dim3(S), dim3(PNP_T), 0, ctx->stream, (const PnPArgs *)d); }
+      hipLaunchKernelGGL(k_pnp_batch, dim3(S), dim3(PNP_T), 0, ctx->stream, (const PnPArgs *)h_args.at(d)); }
     HIP_TRY(ctx, hipGetLastError());
-    double *res = (double *)(h + (size_t)S * sizeof(PnPArgs));
-    HIP_TRY(ctx, hipMemcpyAsync(res, d_res, (size_t)S * 128, hipMemcpyDeviceToHost, ctx->stream));
-    if (ntot > 0) HIP_TRY(ctx, hipMemcpyAsync(outliers, d_o, (size_t)ntot, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(h_res.at(h), st.res, h_res.bytes(), hipMemcpyDeviceToHost, ctx->stream));
+    if (ntot > 0) HIP_TRY(ctx, hipMemcpyAsync(outliers, st.outl, (size_t)ntot, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, slam_stream_wait(ctx->stream));
-    for (int z = 0; z < S; z++) {
-        const double *r = res + 16 * z;
-        if (err_init) err_init[z] = r[6];
-        if (err_final) err_final[z] = r[7];
-        if (n_outliers) n_outliers[z] = (int)r[8];
-        pnp_x_to_pose(r, out_poses + 16 * z);
-    }
+    for (int z = 0; z < S; z++) pnp_decode(h_res.at(h)[z], z, out_poses, err_init, err_final, n_outliers);
     return SLAM_OK;
 }
 
@@ -1339,26 +1335,17 @@ extern "C" int slam_pnp_ba(slam_ctx *ctx, double fx, double fy, double cx, doubl
     PnPArgs A;
     A.cam = {fx, fy, cx, cy}; A.n = n; A.iters_fast = iters_fast; A.iterations = iterations;
     A.depth_eps = depth_eps; A.repr_eps = repr_eps;
-    pnp_pose_to_x(pose_cw, A.X0);
-    const size_t pxb = al((size_t)n * 16 + 8), ptb = al((size_t)n * 24 + 8), ob = al((size_t)n + 8);
-    char *s;
-    int rc = slam_scratch(ctx, pxb + ptb + ob + 256, (void **)&s);
+    pose_to_angles<4>(pose_cw, pose_cw + 12, A.X0);
+    PnPStage st;
+    const int rc = pnp_stage(ctx, 1, n, pixels_yx, points_xyz, &st);
     if (rc) return rc;
-    double *d_px = (double *)s, *d_pts = (double *)(s + pxb); uint8_t *d_o = (uint8_t *)(s + pxb + ptb); double *d_res = (double *)(s + pxb + ptb + ob);
-    if (n > 0) {
-        HIP_TRY(ctx, hipMemcpyAsync(d_px, pixels_yx, (size_t)n * 16, hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(d_pts, points_xyz, (size_t)n * 24, hipMemcpyHostToDevice, ctx->stream));
-    }
-    A.px = d_px; A.pts = d_pts; A.outl = d_o; A.result = d_res;
+    A.px = st.px; A.pts = st.pts; A.outl = st.outl; A.result = st.res;
     hipLaunchKernelGGL(k_pnp, dim3(1), dim3(PNP_T), 0, ctx->stream, A);
     HIP_TRY(ctx, hipGetLastError());
-    double res[12];
-    HIP_TRY(ctx, hipMemcpyAsync(res, d_res, sizeof res, hipMemcpyDeviceToHost, ctx->stream));
-    if (n > 0) HIP_TRY(ctx, hipMemcpyAsync(outliers, d_o, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    PnPResult res;
+    HIP_TRY(ctx, hipMemcpyAsync(&res, st.res, sizeof res, hipMemcpyDeviceToHost, ctx->stream));
+    if (n > 0) HIP_TRY(ctx, hipMemcpyAsync(outliers, st.outl, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, slam_stream_wait(ctx->stream));
-    if (err_init) *err_init = res[6];
-    if (err_final) *err_final = res[7];
-    if (n_outliers) *n_outliers = (int)res[8];
-    pnp_x_to_pose(res, out_pose);
+    pnp_decode(res, 0, out_pose, err_init, err_final, n_outliers);
     return SLAM_OK;
 }

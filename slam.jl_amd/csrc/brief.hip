@@ -204,16 +204,16 @@ static int describe_lists(slam_ctx *ctx, const char *who, const slam_pyr *pyr0, 
     if (m == 0) return SLAM_OK;
     const size_t words = (size_t)n_bits / 64;
     Layout D;
-    const size_t o_rc = D.take((size_t)m * 16), o_mem = D.take((size_t)m * 4), o_out = D.take((size_t)m * words * 8);
+    const auto o_rc = D.take<int64_t>((size_t)m * 2); const auto o_mem = D.take<int32_t>(m); const auto o_out = D.take<uint64_t>((size_t)m * words);
     char *s;
     r = slam_scratch(ctx, D.size(), (void **)&s);
     if (r) return r;
-    HIP_TRY(ctx, hipMemcpyAsync(s + o_rc, keep.data(), (size_t)m * 16, hipMemcpyHostToDevice, ctx->stream));
-    if (batch) HIP_TRY(ctx, hipMemcpyAsync(s + o_mem, member.data(), (size_t)m * 4, hipMemcpyHostToDevice, ctx->stream));
-    J.rc = (const int64_t *)(s + o_rc); J.member = batch ? (const int32_t *)(s + o_mem) : nullptr; J.n = m; J.out = (uint64_t *)(s + o_out);
+    HIP_TRY(ctx, hipMemcpyAsync(o_rc.at(s), keep.data(), o_rc.bytes(), hipMemcpyHostToDevice, ctx->stream));
+    if (batch) HIP_TRY(ctx, hipMemcpyAsync(o_mem.at(s), member.data(), o_mem.bytes(), hipMemcpyHostToDevice, ctx->stream));
+    J.rc = o_rc.at(s); J.member = batch ? o_mem.at(s) : nullptr; J.n = m; J.out = o_out.at(s);
     r = brief_launch(ctx, J, m, 1);
     if (r) return r;
-    HIP_TRY(ctx, hipMemcpyAsync(out_bits, J.out, (size_t)m * words * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(out_bits, J.out, o_out.bytes(), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, slam_stream_wait(ctx->stream));                  // (the pageable sources above are read by now as well)
     memcpy(out_rc, keep.data(), (size_t)m * 16);
     return SLAM_OK;
@@ -274,21 +274,21 @@ extern "C" int slam_describe(slam_ctx *ctx, const double *image, int H, int W, c
     brief_taps(sigma, window, t.w);
     const size_t N = (size_t)H * W, words = (size_t)n_bits / 64;
     Layout D;
-    const size_t o_a = D.take(N * 8), o_b = D.take(N * 8), o_rc = D.take((size_t)m * 16), o_pat = D.take((size_t)n_bits * 16), o_out = D.take((size_t)m * words * 8);
+    const auto o_a = D.take<double>(N), o_b = D.take<double>(N); const auto o_rc = D.take<int64_t>((size_t)m * 2); const auto o_pat = D.take<int32_t>((size_t)n_bits * 4); const auto o_out = D.take<uint64_t>((size_t)m * words);
     char *s;
     int r = slam_scratch(ctx, D.size(), (void **)&s);
     if (r) return r;
-    double *d_a = (double *)(s + o_a), *d_b = (double *)(s + o_b);
-    int64_t *d_rc = (int64_t *)(s + o_rc); int32_t *d_pat = (int32_t *)(s + o_pat);
-    uint64_t *d_out = (uint64_t *)(s + o_out);
-    HIP_TRY(ctx, hipMemcpyAsync(d_a, image, N * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(d_rc, keep.data(), (size_t)m * 16, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(d_pat, pattern, (size_t)n_bits * 16, hipMemcpyHostToDevice, ctx->stream));
+    double *d_a = o_a.at(s), *d_b = o_b.at(s);
+    int64_t *d_rc = o_rc.at(s); int32_t *d_pat = o_pat.at(s);
+    uint64_t *d_out = o_out.at(s);
+    HIP_TRY(ctx, hipMemcpyAsync(d_a, image, o_a.bytes(), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(d_rc, keep.data(), o_rc.bytes(), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(d_pat, pattern, o_pat.bytes(), hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL(k_fir_y, dim3((N + 255) / 256), dim3(256), 0, ctx->stream, d_b, (const double *)d_a, H, W, t);
     hipLaunchKernelGGL(k_fir_x, dim3((N + 255) / 256), dim3(256), 0, ctx->stream, d_a, (const double *)d_b, H, W, t);
     hipLaunchKernelGGL(k_brief, dim3(m), dim3(64), 0, ctx->stream, (const double *)d_a, H, (const int64_t *)d_rc, (const int32_t *)d_pat, n_bits, d_out);
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(out_bits, d_out, (size_t)m * words * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(out_bits, d_out, o_out.bytes(), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, slam_stream_wait(ctx->stream));
     memcpy(out_rc, keep.data(), (size_t)m * 16);
     *n_out = m;

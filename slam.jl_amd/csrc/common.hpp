@@ -8,6 +8,8 @@
 #include <vector>
 #include <mutex>
 #include "../../include/slamhip.h"
+#include "layout.hpp"
+#include "pose_records.hpp"
 
 #define SLAM_MAX_LEVELS 8
 
@@ -102,13 +104,6 @@ int slam_scratch(slam_ctx *ctx, size_t bytes, void **out);
 int slam_scratch2(slam_ctx *ctx, size_t bytes, void **out);
 int slam_pinned(slam_ctx *ctx, size_t bytes, void **out);
 
-// regions of one scratch / pinned block, each starting on a 256-byte boundary: take(bytes) returns the region's offset, size() the total
-struct Layout {
-    size_t end = 0;
-    size_t take(size_t bytes) { const size_t at = end; end += (bytes + 255) & ~(size_t)255; return at; }
-    size_t size() const { return end; }
-};
-
 #define HIP_TRY(ctx, expr)                                                                 \
     do {                                                                                    \
         hipError_t _e = (expr);                                                             \
@@ -137,7 +132,7 @@ struct Cam { double fx, fy, cx, cy; };
 struct PnPArgs {
     Cam cam; const double *px; const double *pts; int n;
     double X0[6]; int iters_fast, iterations; double depth_eps, repr_eps;
-    uint8_t *outl; double *result;   // [X(6), err_init, err_final, n_outliers, identity, iters1, iters2]
+    uint8_t *outl; PnPResult *result;
 };
 int pnp_launch_device(slam_ctx *ctx, int S, const PnPArgs *args_dev);     // S problems, argument blocks already in device memory
 

@@ -78,6 +78,24 @@ hipError_t slam_stream_wait(hipStream_t s)
     return hipStreamSynchronize(s);
 }
 
+// What the three context constructors share: the device count and range checks, the context on its device, the stream `make_stream` gives it
+// (a hipError_t(slam_ctx *)), the failure path; `who` names the seam in the messages.
+template <class MakeStream> static int ctx_create_on(const char *who, int device, slam_ctx **out, MakeStream make_stream)
+{
+    int n = 0;
+    hipError_t e = hipGetDeviceCount(&n);
+    if (e != hipSuccess || n <= 0) return slam_fail(nullptr, SLAM_ERR_HIP, "%s: no HIP device (%s)", who, hipGetErrorString(e));
+    if (device < 0 || device >= n) return slam_fail(nullptr, SLAM_ERR_ARG, "%s: device %d out of range [0,%d)", who, device, n);
+    slam_ctx *c = new slam_ctx();
+    c->device = device;
+    e = hipSetDevice(device);
+    if (e == hipSuccess) e = make_stream(c);
+    if (e != hipSuccess) { delete c; return slam_fail(nullptr, SLAM_ERR_HIP, "%s: %s", who, hipGetErrorString(e)); }
+    ctx_probe_device(c);
+    *out = c;
+    return SLAM_OK;
+}
+
 extern "C" {
 
 int slam_prof_enable(slam_ctx *ctx, int on)
@@ -159,20 +177,10 @@ void ctx_probe_device(slam_ctx *c)
 int slam_ctx_create(int device, slam_ctx **out)
 {
     if (!out) return slam_fail(nullptr, SLAM_ERR_ARG, "slam_ctx_create: out is NULL");
-    int n = 0;
-    hipError_t e = hipGetDeviceCount(&n);
-    if (e != hipSuccess || n <= 0)
-        return slam_fail(nullptr, SLAM_ERR_HIP, "slam_ctx_create: no HIP device (%s)", hipGetErrorString(e));
-    if (device < 0 || device >= n) return slam_fail(nullptr, SLAM_ERR_ARG, "slam_ctx_create: device %d out of range [0,%d)", device, n);
-    slam_ctx *c = new slam_ctx();
-    c->device = device;
-    e = hipSetDevice(device);
-    c->pool_class = 0;
-    if (e == hipSuccess && (c->stream = take_parked(device, 0)) == nullptr) e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-    if (e != hipSuccess) { delete c; return slam_fail(nullptr, SLAM_ERR_HIP, "slam_ctx_create: %s", hipGetErrorString(e)); }
-    ctx_probe_device(c);
-    *out = c;
-    return SLAM_OK;
+    return ctx_create_on("slam_ctx_create", device, out, [&](slam_ctx *c) {
+        c->pool_class = 0;
+        return (c->stream = take_parked(device, 0)) != nullptr ? hipSuccess : hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
+    });
 }
 
 // A context whose stream may only use the compute units set in `cu_mask` (bit i of word i / 32: CU i of the device's
@@ -181,19 +189,10 @@ int slam_ctx_create(int device, slam_ctx **out)
 int slam_ctx_create_cumask(int device, const uint32_t *cu_mask, int n_words, slam_ctx **out)
 {
     if (!out || !cu_mask || n_words <= 0) return slam_fail(nullptr, SLAM_ERR_ARG, "slam_ctx_create_cumask: bad argument");
-    int n = 0;
-    hipError_t e = hipGetDeviceCount(&n);
-    if (e != hipSuccess || n <= 0) return slam_fail(nullptr, SLAM_ERR_HIP, "slam_ctx_create_cumask: no HIP device (%s)", hipGetErrorString(e));
-    if (device < 0 || device >= n) return slam_fail(nullptr, SLAM_ERR_ARG, "slam_ctx_create_cumask: device %d out of range [0,%d)", device, n);
-    slam_ctx *c = new slam_ctx();
-    c->device = device;
-    e = hipSetDevice(device);
-    if (e == hipSuccess) e = hipExtStreamCreateWithCUMask(&c->stream, (uint32_t)n_words, cu_mask);
-    for (int w = 0; w < n_words; w++) c->cus += __builtin_popcount(cu_mask[w]);
-    if (e != hipSuccess) { delete c; return slam_fail(nullptr, SLAM_ERR_HIP, "slam_ctx_create_cumask: %s", hipGetErrorString(e)); }
-    ctx_probe_device(c);
-    *out = c;
-    return SLAM_OK;
+    return ctx_create_on("slam_ctx_create_cumask", device, out, [&](slam_ctx *c) {
+        for (int w = 0; w < n_words; w++) c->cus += __builtin_popcount(cu_mask[w]);
+        return hipExtStreamCreateWithCUMask(&c->stream, (uint32_t)n_words, cu_mask);
+    });
 }
 
 // A context on a stream of its own scheduling class: priority > 0 high, < 0 low, 0 the default class.  The runtime maps
@@ -204,22 +203,14 @@ int slam_ctx_create_cumask(int device, const uint32_t *cu_mask, int n_words, sla
 int slam_ctx_create_priority(int device, int priority, slam_ctx **out)
 {
     if (!out) return slam_fail(nullptr, SLAM_ERR_ARG, "slam_ctx_create_priority: out is NULL");
-    int n = 0;
-    hipError_t e = hipGetDeviceCount(&n);
-    if (e != hipSuccess || n <= 0) return slam_fail(nullptr, SLAM_ERR_HIP, "slam_ctx_create_priority: no HIP device (%s)", hipGetErrorString(e));
-    if (device < 0 || device >= n) return slam_fail(nullptr, SLAM_ERR_ARG, "slam_ctx_create_priority: device %d out of range [0,%d)", device, n);
-    slam_ctx *c = new slam_ctx();
-    c->device = device;
-    e = hipSetDevice(device);
-    int least = 0, greatest = 0;                      // numerically: greatest priority <= 0 <= least priority
-    if (e == hipSuccess) e = hipDeviceGetStreamPriorityRange(&least, &greatest);
-    int p = priority > 0 ? greatest : priority < 0 ? least : 0;
-    c->pool_class = priority > 0 ? 1 : priority < 0 ? -1 : 0;
-    if (e == hipSuccess && (c->stream = take_parked(device, c->pool_class)) == nullptr) e = hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, p);
-    if (e != hipSuccess) { delete c; return slam_fail(nullptr, SLAM_ERR_HIP, "slam_ctx_create_priority: %s", hipGetErrorString(e)); }
-    ctx_probe_device(c);
-    *out = c;
-    return SLAM_OK;
+    return ctx_create_on("slam_ctx_create_priority", device, out, [&](slam_ctx *c) {
+        int least = 0, greatest = 0;                      // numerically: greatest priority <= 0 <= least priority
+        const hipError_t e = hipDeviceGetStreamPriorityRange(&least, &greatest);
+        if (e != hipSuccess) return e;
+        const int p = priority > 0 ? greatest : priority < 0 ? least : 0;
+        c->pool_class = priority > 0 ? 1 : priority < 0 ? -1 : 0;
+        return (c->stream = take_parked(device, c->pool_class)) != nullptr ? hipSuccess : hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, p);
+    });
 }
 
 extern "C" void ba_forget_jobs(slam_ctx *ctx);          // ba_batch.hip: a batch job still in flight on the context is waited for
@@ -269,29 +260,20 @@ int slam_ctx_wait_for(slam_ctx *ctx, slam_ctx *other)
 // Markers: "what `ctx` has enqueued up to here" as a handle another context can wait on later, after more work has been
 // enqueued on `ctx` (slam_ctx_wait_for can only name the current tail of the other stream).
 struct slam_event { hipEvent_t ev; int device; };
-int slam_event_create(slam_ctx *ctx, slam_event **out)
+static int event_create(slam_ctx *ctx, slam_event **out, unsigned flags)
 {
     ARG_TRY(ctx, ctx != nullptr && out != nullptr);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     slam_event *e = new slam_event();
     e->device = ctx->device;
-    hipError_t rc = hipEventCreateWithFlags(&e->ev, hipEventDisableTiming);
+    hipError_t rc = hipEventCreateWithFlags(&e->ev, flags);
     if (rc != hipSuccess) { delete e; return slam_fail(ctx, SLAM_ERR_HIP, "hipEventCreate: %s", hipGetErrorString(rc)); }
     *out = e;
     return SLAM_OK;
 }
+int slam_event_create(slam_ctx *ctx, slam_event **out) { return event_create(ctx, out, hipEventDisableTiming); }
 // event with timing enabled: a pair of them brackets a stage on a context's stream (slam_event_elapsed_ms)
-int slam_event_create_timed(slam_ctx *ctx, slam_event **out)
-{
-    ARG_TRY(ctx, ctx != nullptr && out != nullptr);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    slam_event *e = new slam_event();
-    e->device = ctx->device;
-    hipError_t rc = hipEventCreate(&e->ev);
-    if (rc != hipSuccess) { delete e; return slam_fail(ctx, SLAM_ERR_HIP, "hipEventCreate: %s", hipGetErrorString(rc)); }
-    *out = e;
-    return SLAM_OK;
-}
+int slam_event_create_timed(slam_ctx *ctx, slam_event **out) { return event_create(ctx, out, hipEventDefault); }
 // milliseconds between two recorded timed events (waits for `b`)
 int slam_event_elapsed_ms(slam_event *a, slam_event *b, double *ms)
 {

@@ -273,13 +273,13 @@ int slam_detect_device(slam_ctx *ctx, const double *img_dev, int H, int W, int p
     A.k = k; A.n_cur = n_cur;
     const size_t out_pairs = (size_t)n_cells * k, out_b = 8 + out_pairs * 16;
     Layout D;
-    const size_t o_cur = D.take((size_t)n_cur * 16), o_cnt = D.take((size_t)n_cells * 4), o_cout = D.take((size_t)n_cells * k * 16), o_out = D.take(out_b);
+    const auto o_cur = D.take<double>((size_t)n_cur * 2); const auto o_cnt = D.take<int>(n_cells); const auto o_cout = D.take<int64_t>(out_pairs * 2), o_out = D.take<int64_t>(out_b / 8);
     char *s;
     rc = slam_scratch(ctx, D.size(), (void **)&s);
     if (rc) return rc;
-    double *d_cur = (double *)(s + o_cur); int *d_cnt = (int *)(s + o_cnt);
-    int64_t *d_cout = (int64_t *)(s + o_cout); int64_t *d_out = (int64_t *)(s + o_out);
-    if (n_cur > 0) HIP_TRY(ctx, hipMemcpyAsync(d_cur, cur_yx, (size_t)n_cur * 16, hipMemcpyHostToDevice, ctx->stream));
+    double *d_cur = o_cur.at(s); int *d_cnt = o_cnt.at(s);
+    int64_t *d_cout = o_cout.at(s), *d_out = o_out.at(s);
+    if (n_cur > 0) HIP_TRY(ctx, hipMemcpyAsync(d_cur, cur_yx, o_cur.bytes(), hipMemcpyHostToDevice, ctx->stream));
     A.cur = d_cur; A.cell_out = d_cout; A.cell_cnt = d_cnt;
     { ProfScope span(ctx, "detect");
       hipLaunchKernelGGL(detect_cells, dim3(n_cells), dim3(DET_THREADS), lds_bytes, ctx->stream, A);
@@ -353,19 +353,19 @@ extern "C" int slam_detect_batch(slam_ctx *ctx, const slam_pyr *pyr0, int S, con
     // these inputs and the output behind them
     const size_t pairs = (size_t)n_cells * kmax, out_b = (size_t)S * (8 + pairs * 16);
     Layout D;
-    const size_t o_hdr = D.take(2048), o_cur = D.take((size_t)n_tot * 16), in_b = D.size();
-    const size_t o_cnt = D.take((size_t)S * n_cells * 4), o_cout = D.take((size_t)S * n_cells * kmax * 16), o_out = D.take(out_b);
+    const auto o_hdr = D.take<int>(512); const auto o_cur = D.take<double>((size_t)n_tot * 2); const size_t in_b = D.size();
+    const auto o_cnt = D.take<int>((size_t)S * n_cells); const auto o_cout = D.take<int64_t>((size_t)S * pairs * 2), o_out = D.take<int64_t>(out_b / 8);
     char *d, *h;
     rc = slam_scratch(ctx, D.size(), (void **)&d);
     if (rc) return rc;
     rc = slam_pinned(ctx, in_b + out_b, (void **)&h);
     if (rc) return rc;
-    memcpy(h + o_hdr, cur_off, (size_t)(S + 1) * 4); memcpy(h + o_hdr + 1024, ks, (size_t)S * 4);
-    if (n_tot > 0) memcpy(h + o_cur, cur_yx, (size_t)n_tot * 16);
-    HIP_TRY(ctx, hipMemcpyAsync(d, h, o_cur + (size_t)n_tot * 16, hipMemcpyHostToDevice, ctx->stream));
-    A.cur_off = (const int *)(d + o_hdr); A.k_s = (const int *)(d + o_hdr + 1024); A.cur = (const double *)(d + o_cur);
-    A.cell_cnt = (int *)(d + o_cnt); A.cell_out = (int64_t *)(d + o_cout);
-    int64_t *d_out = (int64_t *)(d + o_out);
+    memcpy(o_hdr.at(h), cur_off, (size_t)(S + 1) * 4); memcpy(o_hdr.at(h) + 256, ks, (size_t)S * 4);
+    if (n_tot > 0) memcpy(o_cur.at(h), cur_yx, o_cur.bytes());
+    HIP_TRY(ctx, hipMemcpyAsync(d, h, o_cur.off + o_cur.bytes(), hipMemcpyHostToDevice, ctx->stream));
+    A.cur_off = o_hdr.at(d); A.k_s = o_hdr.at(d) + 256; A.cur = o_cur.at(d);
+    A.cell_cnt = o_cnt.at(d); A.cell_out = o_cout.at(d);
+    int64_t *d_out = o_out.at(d);
     { ProfScope span(ctx, "detect");
       hipLaunchKernelGGL(detect_cells, dim3(n_cells, S), dim3(DET_THREADS), lds_bytes, ctx->stream, A);
       hipLaunchKernelGGL(detect_compact, dim3(S), dim3(1024), 0, ctx->stream, (const int64_t *)A.cell_out, (const int *)A.cell_cnt, n_cells, kmax,
@@ -417,11 +417,11 @@ static int kpset_detect_plan(slam_ctx *ctx, const slam_kpset *ks, const slam_pyr
     if (rc) return rc;
     D.A.cur = ks->v.yx; D.A.cur_cnt = ks->v.count; D.A.cur_stride = ks->v.cap;
     Layout L;
-    const size_t o_cnt = L.take((size_t)ks->S * D.n_cells * 4), o_cout = L.take((size_t)ks->S * D.n_cells * D.kmax * 16), o_extra = L.take(extra);
+    const auto o_cnt = L.take<int>((size_t)ks->S * D.n_cells); const auto o_cout = L.take<int64_t>((size_t)ks->S * D.n_cells * D.kmax * 2); const auto o_extra = L.take<char>(extra);
     char *d;
     rc = slam_scratch(ctx, L.size(), (void **)&d);
     if (rc) return rc;
-    D.A.cell_cnt = (int *)(d + o_cnt); D.A.cell_out = (int64_t *)(d + o_cout); D.extra = d + o_extra;
+    D.A.cell_cnt = o_cnt.at(d); D.A.cell_out = o_cout.at(d); D.extra = o_extra.at(d);
     return SLAM_OK;
 }
 static void kpset_detect_append(slam_ctx *ctx, slam_kpset *ks, const KpDetect &D)

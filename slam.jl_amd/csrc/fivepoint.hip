@@ -40,7 +40,7 @@ struct FPArgs {                            // S independent problems (S = 1: sla
     double *poses;                         // S x iters x 10 x 12
     int *counts;                           // S x iters x 10
     double *errs;                          // off[S]
-    double *out;                           // S x 32 (mapped host): P 12 | E 9 | error | {n_inliers, best_iter} as two ints
+    FPOut *out;                            // S (mapped host)
     uint8_t *inliers;                      // off[S] (mapped host)
 };
 
@@ -624,7 +624,7 @@ __global__ __launch_bounds__(FP_SCORE_T) void k_5pt_score(FPArgs T)
 // k_5pt_select = ransac_select with this policy: FP_MAXE candidates per tuple, the two reprojection errors of the winning pose
 struct FPSelect {
     static constexpr int THREADS = FP_SEL_T, PER_ITER = FP_MAXE, ERR_LDS = FP_ERR_LDS;
-    const double *ks, *poses, *Es, *px1, *px2; double thr; double *out, *s_P, *s_k;
+    const double *ks, *poses, *Es, *px1, *px2; double thr; FPOut *out; double *s_P, *s_k;
     __device__ void stage(int tid) const { if (tid < 8) s_k[tid] = ks[tid]; }
     __device__ void winner(int tid, int best, int be) const { if (tid < 12) s_P[tid] = best > 0 ? poses[(size_t)be * 12 + tid] : 0.0; }
     __device__ bool score(int i, double &e) const
@@ -637,12 +637,11 @@ struct FPSelect {
     }
     __device__ void write(int best, int be, double esum) const
     {
-        out[21] = esum;
-        int *oi = (int *)(out + 22);
-        oi[0] = best; oi[1] = best > 0 ? be / PER_ITER : -1;
-        for (int j = 0; j < 12; j++) out[j] = s_P[j];
+        out->err = esum;
+        out->n_inliers = best; out->best_iter = best > 0 ? be / PER_ITER : -1;
+        for (int j = 0; j < 12; j++) out->P[j] = s_P[j];
         for (int r = 0; r < 3; r++)
-            for (int c = 0; c < 3; c++) out[12 + r + 3 * c] = best > 0 ? Es[(size_t)be * 9 + 3 * r + c] : 0.0;
+            for (int c = 0; c < 3; c++) out->E[r + 3 * c] = best > 0 ? Es[(size_t)be * 9 + 3 * r + c] : 0.0;
     }
 };
 __global__ __launch_bounds__(FP_SEL_T) void k_5pt_select(FPArgs T)
@@ -651,21 +650,18 @@ __global__ __launch_bounds__(FP_SEL_T) void k_5pt_select(FPArgs T)
     const int z = blockIdx.x, ne = FP_MAXE * T.iters;
     const ProblemRange pr = problem_range(T.off, T.cnt, T.stride, z);
     const FPSelect pol{T.ks + 8 * z, T.poses + (size_t)z * ne * 12, T.Es + (size_t)z * ne * 9, T.px1 + 2 * (size_t)pr.base, T.px2 + 2 * (size_t)pr.base,
-                       T.thr, T.out + 32 * (size_t)z, s_P, s_k};
+                       T.thr, T.out + z, s_P, s_k};
     ransac_select(pol, T.counts + (size_t)z * ne, ne, pr.n, T.errs + pr.base, T.inliers + pr.base);
 }
 
 // the device scratch of FPArgs (ne | Es | poses | counts + the S incumbent counts | errs) as regions of the caller's layout; k_5pt_score
 // finds the incumbents at counts + S * iters * FP_MAXE, fp_enqueue clears them there
 struct FPScratch {
-    size_t ne, Es, poses, counts, errs;
+    Region<int> ne; Region<double> Es, poses; Region<int> counts; Region<double> errs;
     FPScratch(Layout &L, int S, int iters, size_t npts)
-        : ne(L.take((size_t)S * iters * 4)), Es(L.take((size_t)S * iters * FP_MAXE * 72)), poses(L.take((size_t)S * iters * FP_MAXE * 96)),
-          counts(L.take((size_t)S * iters * FP_MAXE * 4 + (size_t)S * 4)), errs(L.take(npts * 8)) {}
-    void bind(FPArgs &T, char *scr) const
-    {
-        T.ne = (int *)(scr + ne); T.Es = (double *)(scr + Es); T.poses = (double *)(scr + poses); T.counts = (int *)(scr + counts); T.errs = (double *)(scr + errs);
-    }
+        : ne(L.take<int>((size_t)S * iters)), Es(L.take<double>((size_t)S * iters * FP_MAXE * 9)), poses(L.take<double>((size_t)S * iters * FP_MAXE * 12)),
+          counts(L.take<int>((size_t)S * iters * FP_MAXE + (size_t)S)), errs(L.take<double>(npts)) {}
+    void bind(FPArgs &T, char *scr) const { T.ne = ne.at(scr); T.Es = Es.at(scr); T.poses = poses.at(scr); T.counts = counts.at(scr); T.errs = errs.at(scr); }
 };
 // the only launch site of the three kernels (grid.y / grid.y / grid.x = problem)
 static int fp_enqueue(slam_ctx *ctx, int S, const FPArgs &T)
@@ -679,6 +675,13 @@ static int fp_enqueue(slam_ctx *ctx, int S, const FPArgs &T)
     return SLAM_OK;
 }
 
+// problem z's record into the caller's arrays (E, error, best_iter may be null)
+static void fp_copy_out(const FPOut &o, int z, double *E, double *P, int *n_inliers, double *error, int *best_iter)
+{
+    memcpy(P + 12 * z, o.P, sizeof o.P); if (E) memcpy(E + 9 * z, o.E, sizeof o.E);
+    n_inliers[z] = o.n_inliers; if (error) error[z] = o.err; if (best_iter) best_iter[z] = o.best_iter;
+}
+
 // S problems in one round trip through the context's mapped pinned block
 static int fp_run(slam_ctx *ctx, int S, const int32_t *off, const double *px1_xy, const double *px2_xy, const double *pd1_xy,
                   const double *pd2_xy, const double *K1, const double *K2, double max_repr_error, const int32_t *samples, int iters,
@@ -687,61 +690,47 @@ static int fp_run(slam_ctx *ctx, int S, const int32_t *off, const double *px1_xy
     const int ntot = off[S];
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     Layout H;
-    const size_t o_px1 = H.take((size_t)ntot * 16), o_px2 = H.take((size_t)ntot * 16), o_pd1 = H.take((size_t)ntot * 16), o_pd2 = H.take((size_t)ntot * 16);
-    const size_t o_off = H.take((size_t)(S + 1) * 4), o_k = H.take((size_t)S * 64), o_smp = H.take((size_t)S * iters * 20);
-    const size_t o_out = H.take((size_t)S * 256), o_inl = H.take((size_t)ntot);
+    const auto o_px1 = H.take<double>((size_t)ntot * 2), o_px2 = H.take<double>((size_t)ntot * 2), o_pd1 = H.take<double>((size_t)ntot * 2), o_pd2 = H.take<double>((size_t)ntot * 2);
+    const auto o_off = H.take<int>((size_t)S + 1); const auto o_k = H.take<double>((size_t)S * 8); const auto o_smp = H.take<int32_t>((size_t)S * iters * 5);
+    const auto o_out = H.take<FPOut>(S); const auto o_inl = H.take<uint8_t>(ntot);
     char *h, *d;
     int rc = slam_pinned(ctx, H.size(), (void **)&h);
     if (rc) return rc;
     HIP_TRY(ctx, hipHostGetDevicePointer((void **)&d, h, 0));
-    memcpy(h + o_px1, px1_xy, (size_t)ntot * 16); memcpy(h + o_px2, px2_xy, (size_t)ntot * 16);
-    memcpy(h + o_pd1, pd1_xy, (size_t)ntot * 16); memcpy(h + o_pd2, pd2_xy, (size_t)ntot * 16);
-    memcpy(h + o_off, off, (size_t)(S + 1) * 4);
-    double *ks = (double *)(h + o_k);
+    memcpy(o_px1.at(h), px1_xy, o_px1.bytes()); memcpy(o_px2.at(h), px2_xy, o_px2.bytes());
+    memcpy(o_pd1.at(h), pd1_xy, o_pd1.bytes()); memcpy(o_pd2.at(h), pd2_xy, o_pd2.bytes());
+    memcpy(o_off.at(h), off, o_off.bytes());
+    double *ks = o_k.at(h);
     for (int z = 0; z < S; z++) {
         const double *a = K1 + 9 * z, *b = K2 + 9 * z;
         ks[8 * z] = a[0]; ks[8 * z + 1] = a[4]; ks[8 * z + 2] = a[6]; ks[8 * z + 3] = a[7];
         ks[8 * z + 4] = b[0]; ks[8 * z + 5] = b[4]; ks[8 * z + 6] = b[6]; ks[8 * z + 7] = b[7];
     }
-    memcpy(h + o_smp, samples, (size_t)S * iters * 20);
+    memcpy(o_smp.at(h), samples, o_smp.bytes());
     Layout D;
     const FPScratch ds(D, S, iters, (size_t)ntot);
     char *scr;
     rc = slam_scratch(ctx, D.size(), (void **)&scr);
     if (rc) return rc;
     FPArgs T;
-    T.px1 = (const double *)(d + o_px1); T.px2 = (const double *)(d + o_px2); T.pd1 = (const double *)(d + o_pd1); T.pd2 = (const double *)(d + o_pd2);
-    T.samples = (const int32_t *)(d + o_smp); T.off = (const int *)(d + o_off); T.ks = (const double *)(d + o_k);
+    T.px1 = o_px1.at(d); T.px2 = o_px2.at(d); T.pd1 = o_pd1.at(d); T.pd2 = o_pd2.at(d); T.samples = o_smp.at(d); T.off = o_off.at(d); T.ks = o_k.at(d);
     T.iters = iters; T.thr = max_repr_error; T.cnt = nullptr; T.stride = 0;
-    ds.bind(T, scr);
-    T.out = (double *)(d + o_out); T.inliers = (uint8_t *)(d + o_inl);
+    ds.bind(T, scr); T.out = o_out.at(d); T.inliers = o_inl.at(d);
     { ProfScope span(ctx, "five_point_ransac");
       rc = fp_enqueue(ctx, S, T);
       if (rc) return rc; }
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, slam_stream_wait(ctx->stream));
-    for (int z = 0; z < S; z++) {
-        const char *o = h + o_out + (size_t)z * 256;      // P [0,96) E [96,168) error [168,176) n_inliers [176,180) best_iter [180,184)
-        memcpy(P + 12 * z, o, 96);
-        if (E) memcpy(E + 9 * z, o + 96, 72);
-        if (error) memcpy(error + z, o + 168, 8);
-        memcpy(n_inliers + z, o + 176, 4);
-        if (best_iter) memcpy(best_iter + z, o + 180, 4);
-    }
-    memcpy(inliers, h + o_inl, (size_t)ntot);
+    for (int z = 0; z < S; z++) fp_copy_out(o_out.at(h)[z], z, E, P, n_inliers, error, best_iter);
+    memcpy(inliers, o_inl.at(h), o_inl.bytes());
     return SLAM_OK;
 }
 
 // nothing to sample from: zero pose and E, zero mask, no inliers, best_iter = -1 for each of the S problems
 static int fp_empty(int S, int ntot, double *E, double *P, uint8_t *inliers, int *n_inliers, double *error, int *best_iter)
 {
-    for (int z = 0; z < S; z++) {
-        n_inliers[z] = 0;
-        for (int j = 0; j < 12; j++) P[12 * z + j] = 0.0;
-        if (E) for (int j = 0; j < 9; j++) E[9 * z + j] = 0.0;
-        if (error) error[z] = 0.0;
-        if (best_iter) best_iter[z] = -1;
-    }
+    FPOut o = {}; o.best_iter = -1;
+    for (int z = 0; z < S; z++) fp_copy_out(o, z, E, P, n_inliers, error, best_iter);
     for (int i = 0; i < ntot; i++) inliers[i] = 0;
     return SLAM_OK;
 }
@@ -790,7 +779,7 @@ struct KFiveArgs {
     const double *par;                 // S x KP_PAR (kpset.hpp), R_compensation in [0..8]
     double *px1, *px2, *pd1, *pd2; int *slot; int *n5; double *psum; double *ks;      // gathered pairs, stride cap; S x 8 intrinsics
     int32_t *samples; int iters; unsigned long long seed; double min_parallax;
-    const double *fp_out; const uint8_t *inl;                                          // k_5pt_select's outputs
+    const FPOut *fp_out; const uint8_t *inl;                                         // k_5pt_select's outputs
     uint8_t *flags; double *P; int *status, *ninl; double *parallax;                   // results
 };
 
@@ -855,15 +844,15 @@ __global__ __launch_bounds__(256) void k_kfive_finish(KFiveArgs A)
 {
     const int z = blockIdx.x, tid = threadIdx.x, n = A.n5[z];
     const size_t b = (size_t)z * A.cap;
-    const double *out = A.fp_out + 32 * (size_t)z;
-    const int best = ((const int *)(out + 22))[0];
+    const FPOut &out = A.fp_out[z];
+    const int best = out.n_inliers;
     const bool ran = A.count[z] >= 8 && n >= 8 && !(A.psum[z] / (double)n < A.min_parallax);
     const bool ok = ran && best >= 5;                                        // :305
     if (ok && best != n)                                                     // :310-318
         for (int i = tid; i < n; i += 256)
             if (!A.inl[b + i]) A.flags[b + A.slot[b + i]] = 1;
     if (tid == 0) {
-        for (int j = 0; j < 12; j++) A.P[12 * z + j] = ok ? out[j] : 0.0;
+        for (int j = 0; j < 12; j++) A.P[12 * z + j] = ok ? out.P[j] : 0.0;
         A.status[z] = ok ? 1 : 0; A.ninl[z] = ran ? best : 0;
         A.parallax[z] = n > 0 ? A.psum[z] / (double)n : 0.0;
     }
@@ -879,11 +868,11 @@ extern "C" int slam_kpset_compute_pose_5pt(slam_ctx *ctx, slam_kpset *ks, const 
     const int S = ks->S, cap = ks->v.cap;
     const size_t nc = (size_t)S * cap;
     Layout D;                          // device scratch
-    const size_t o_px1 = D.take(nc * 16), o_px2 = D.take(nc * 16), o_pd1 = D.take(nc * 16), o_pd2 = D.take(nc * 16), o_slot = D.take(nc * 4);
-    const size_t o_n5 = D.take((size_t)S * 4), o_ps = D.take((size_t)S * 8), o_ks = D.take((size_t)S * 64), o_smp = D.take((size_t)S * iters * 20);
+    const auto o_px1 = D.take<double>(nc * 2), o_px2 = D.take<double>(nc * 2), o_pd1 = D.take<double>(nc * 2), o_pd2 = D.take<double>(nc * 2); const auto o_slot = D.take<int>(nc);
+    const auto o_n5 = D.take<int>(S); const auto o_ps = D.take<double>(S), o_ks = D.take<double>((size_t)S * 8); const auto o_smp = D.take<int32_t>((size_t)S * iters * 5);
     const FPScratch ds(D, S, iters, nc);
-    const size_t o_out = D.take((size_t)S * 256), o_inl = D.take(nc), o_fl = D.take(nc);
-    const size_t o_P = D.take((size_t)S * 96), o_st = D.take((size_t)S * 4), o_ni = D.take((size_t)S * 4), o_pa = D.take((size_t)S * 8);
+    const auto o_out = D.take<FPOut>(S); const auto o_inl = D.take<uint8_t>(nc), o_fl = D.take<uint8_t>(nc);
+    const auto o_P = D.take<double>((size_t)S * 12); const auto o_st = D.take<int>(S), o_ni = D.take<int>(S); const auto o_pa = D.take<double>(S);
     Layout H;                          // pinned host block of the results (8 bytes per stream each, so that the int regions line up with the parallax)
     const size_t h_P = H.take((size_t)S * 96), h_st = H.take((size_t)S * 8), h_ni = H.take((size_t)S * 8), h_pa = H.take((size_t)S * 8), h_cn = H.take((size_t)S * 8);
     char *scr;
@@ -894,17 +883,16 @@ extern "C" int slam_kpset_compute_pose_5pt(slam_ctx *ctx, slam_kpset *ks, const 
     if (rc) return rc;
     KFiveArgs A;
     A.yx = ks->v.yx; A.kyx = ks->v.kyx; A.haskf = ks->v.haskf; A.count = ks->v.count; A.cap = cap; A.par = par_dev;
-    A.px1 = (double *)(scr + o_px1); A.px2 = (double *)(scr + o_px2); A.pd1 = (double *)(scr + o_pd1); A.pd2 = (double *)(scr + o_pd2);
-    A.slot = (int *)(scr + o_slot); A.n5 = (int *)(scr + o_n5); A.psum = (double *)(scr + o_ps); A.ks = (double *)(scr + o_ks);
-    A.samples = (int32_t *)(scr + o_smp); A.iters = iters; A.seed = seed; A.min_parallax = min_parallax;
-    A.fp_out = (const double *)(scr + o_out); A.inl = (const uint8_t *)(scr + o_inl);
-    A.flags = (uint8_t *)(scr + o_fl); A.P = (double *)(scr + o_P); A.status = (int *)(scr + o_st); A.ninl = (int *)(scr + o_ni);
-    A.parallax = (double *)(scr + o_pa);
+    A.px1 = o_px1.at(scr); A.px2 = o_px2.at(scr); A.pd1 = o_pd1.at(scr); A.pd2 = o_pd2.at(scr);
+    A.slot = o_slot.at(scr); A.n5 = o_n5.at(scr); A.psum = o_ps.at(scr); A.ks = o_ks.at(scr);
+    A.samples = o_smp.at(scr); A.iters = iters; A.seed = seed; A.min_parallax = min_parallax;
+    A.fp_out = o_out.at(scr); A.inl = o_inl.at(scr);
+    A.flags = o_fl.at(scr); A.P = o_P.at(scr); A.status = o_st.at(scr); A.ninl = o_ni.at(scr); A.parallax = o_pa.at(scr);
     FPArgs T;
     T.px1 = A.px1; T.px2 = A.px2; T.pd1 = A.pd1; T.pd2 = A.pd2; T.samples = A.samples; T.off = nullptr; T.cnt = A.n5; T.stride = cap;
     T.ks = A.ks; T.iters = iters; T.thr = max_repr_error;
     ds.bind(T, scr);
-    T.out = (double *)(scr + o_out); T.inliers = (uint8_t *)(scr + o_inl);
+    T.out = o_out.at(scr); T.inliers = o_inl.at(scr);
     HIP_TRY(ctx, hipMemsetAsync(A.flags, 0, nc, ctx->stream));
     { ProfScope span(ctx, "kpset_compute_pose_5pt");
       hipLaunchKernelGGL(k_kfive_gather, dim3(S), dim3(256), 0, ctx->stream, A);

@@ -648,20 +648,20 @@ int slam_kpset_triangulate_temporal(slam_ctx *ctx, slam_kpset *ks, const double 
     const int S = ks->S;
     const size_t nc = (size_t)S * ks->v.cap;
     Layout D;                          // the staged inputs (same offsets in the pinned block), then the removal flags
-    const size_t o_tab = D.take((size_t)S * nkf * 64 * 8), o_cur = D.take((size_t)S * 4), o_lo = D.take((size_t)S * 4), in_b = D.size(), o_fl = D.take(nc);
+    const auto o_tab = D.take<double>((size_t)S * nkf * 64); const auto o_cur = D.take<int>(S), o_lo = D.take<int>(S); const size_t in_b = D.size(); const auto o_fl = D.take<uint8_t>(nc);
     char *scr, *h;
     int rc = slam_scratch2(ctx, D.size(), (void **)&scr);
     if (rc) return rc;
     rc = slam_pinned(ctx, in_b, (void **)&h);
     if (rc) return rc;
-    memcpy(h + o_tab, tab, (size_t)S * nkf * 64 * 8); memcpy(h + o_cur, kf_cur, (size_t)S * 4); memcpy(h + o_lo, kf_lo, (size_t)S * 4);
+    memcpy(o_tab.at(h), tab, o_tab.bytes()); memcpy(o_cur.at(h), kf_cur, o_cur.bytes()); memcpy(o_lo.at(h), kf_lo, o_lo.bytes());
     HIP_TRY(ctx, hipMemcpyAsync(scr, h, in_b, hipMemcpyHostToDevice, ctx->stream));
     KTempArgs T;
     rc = kpset_stage_params(ctx, ks, params, (size_t)S * KP_PAR, &T.par);
     if (rc) return rc;
-    T.tab = (const double *)(scr + o_tab); T.kf_cur = (const int *)(scr + o_cur); T.kf_lo = (const int *)(scr + o_lo); T.nkf = nkf;
+    T.tab = o_tab.at(scr); T.kf_cur = o_cur.at(scr); T.kf_lo = o_lo.at(scr); T.nkf = nkf;
     T.max_error = max_error; T.min_depth = min_depth; T.min_parallax = min_parallax;
-    T.flags = (uint8_t *)(scr + o_fl);
+    T.flags = o_fl.at(scr);
     HIP_TRY(ctx, hipMemsetAsync(T.flags, 0, nc, ctx->stream));
     rc = kpset_build_worklist(ctx, ks, 0, 0, true);
     if (rc) return rc;

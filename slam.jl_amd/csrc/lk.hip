@@ -757,16 +757,16 @@ static int run_tracking(slam_ctx *ctx, const slam_pyr *prev, const slam_pyr *cur
 {
     const int n = l.n;
     Layout B;                          // inputs, then outputs
-    const size_t o_pts = B.take((size_t)n * 16), o_aux = B.take((size_t)n * 16), o_3d = B.take((size_t)n), o_img = B.take((size_t)n * 4), in_b = B.size();
-    const size_t o_out = B.take((size_t)n * 16), o_st = B.take((size_t)n), out_b = B.size() - in_b;
+    const auto o_pts = B.take<double>((size_t)n * 2), o_aux = B.take<double>((size_t)n * 2); const auto o_3d = B.take<uint8_t>(n); const auto o_img = B.take<int>(n); const size_t in_b = B.size();
+    const auto o_out = B.take<double>((size_t)n * 2); const auto o_st = B.take<uint8_t>(n); const size_t out_b = B.size() - in_b;
     char *h, *d;
     int rc = slam_pinned(ctx, B.size(), (void **)&h);
     if (rc) return rc;
     HIP_TRY(ctx, hipHostGetDevicePointer((void **)&d, h, 0));
-    memcpy(h + o_pts, l.pts, (size_t)n * 16);
-    if (l.aux) memcpy(h + o_aux, l.aux, (size_t)n * 16);
-    if (l.is3d) memcpy(h + o_3d, l.is3d, (size_t)n);
-    if (l.img) memcpy(h + o_img, l.img, (size_t)n * 4);
+    memcpy(o_pts.at(h), l.pts, o_pts.bytes());
+    if (l.aux) memcpy(o_aux.at(h), l.aux, o_aux.bytes());
+    if (l.is3d) memcpy(o_3d.at(h), l.is3d, o_3d.bytes());
+    if (l.img) memcpy(o_img.at(h), l.img, o_img.bytes());
     // Large batches: tens of thousands of 8-byte reads and writes over PCIe (every wave starts with dependent
     // reads of its point and ends with three small stores) are slower than one DMA of the whole block each way.
     const bool staged = n >= LK_STAGE_MIN_POINTS;
@@ -780,19 +780,19 @@ static int run_tracking(slam_ctx *ctx, const slam_pyr *prev, const slam_pyr *cur
     FlowArgs F;
     LKArgs &A = F.lk;
     A.prev = prev->view; A.cur = cur->view;
-    A.pts = (const double *)(d + o_pts); A.disp0 = l.aux ? (const double *)(d + o_aux) : nullptr; A.n = n;
+    A.pts = o_pts.at(d); A.disp0 = l.aux ? o_aux.at(d) : nullptr; A.n = n;
     A.tune = t;
-    A.out = (double *)(d + o_out); A.status = (uint8_t *)(d + o_st);
-    F.is3d = (const uint8_t *)(d + o_3d); F.proj = (const double *)(d + o_aux);
-    F.img = l.img ? (const int *)(d + o_img) : nullptr; F.zs_from = prev->zstride; F.zs_to = cur->zstride;
+    A.out = o_out.at(d); A.status = o_st.at(d);
+    F.is3d = o_3d.at(d); F.proj = o_aux.at(d);
+    F.img = l.img ? o_img.at(d) : nullptr; F.zs_from = prev->zstride; F.zs_to = cur->zstride;
     { ProfScope span(ctx, "fb_track");
       if (l.flow) lk_launch(t.window, [&](auto N) { hipLaunchKernelGGL(k_flow_match<N.value>, dim3(lk_grid(n)), dim3(64), 0, ctx->stream, F); });
       else lk_launch(t.window, [&](auto N) { hipLaunchKernelGGL(k_fb_track<N.value>, dim3(lk_grid(n)), dim3(64), 0, ctx->stream, A); }); }
     HIP_TRY(ctx, hipGetLastError());
     if (staged) HIP_TRY(ctx, hipMemcpyAsync(h + in_b, d + in_b, out_b, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, slam_stream_wait(ctx->stream));
-    memcpy(l.out, h + o_out, (size_t)n * 16);
-    memcpy(l.status, h + o_st, (size_t)n);
+    memcpy(l.out, o_out.at(h), o_out.bytes());
+    memcpy(l.status, o_st.at(h), o_st.bytes());
     return SLAM_OK;
 }
 

@@ -24,7 +24,7 @@ struct P3PArgs {                    // S independent problems (S = 1: slam_p3p_r
     int *counts;                    // S x iters x 4
     double *poses;                  // S x iters x 4 x 12
     double *errs;                   // off[S] (only read back when a problem has more than P3P_ERR_LDS points)
-    double *out;                    // S x 32 (mapped host): KP 12 | Rt 12 | error | {n_inliers, best_iter} as two ints
+    P3POut *out;                    // S (mapped host)
     uint8_t *inliers;               // off[S] (mapped host)
 };
 
@@ -265,7 +265,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void k_
 // k_p3p_select = ransac_select with this policy: four candidates per triple, reprojection error of the winning pose
 struct P3PSelect {
     static constexpr int THREADS = 256, PER_ITER = 4, ERR_LDS = P3P_ERR_LDS;
-    const double *Ks, *poses, *pts, *px; double thr; double *out, *s_P, *s_K;
+    const double *Ks, *poses, *pts, *px; double thr; P3POut *out; double *s_P, *s_K;
     __device__ void stage(int tid) const { if (tid < 9) s_K[tid] = Ks[tid]; }
     __device__ void winner(int tid, int best, int be) const { if (tid < 12) s_P[tid] = best > 0 ? poses[(size_t)be * 12 + tid] : 0.0; }
     __device__ bool score(int i, double &e) const
@@ -277,13 +277,12 @@ struct P3PSelect {
     }
     __device__ void write(int best, int be, double esum) const
     {
-        out[24] = esum;
-        int *oi = (int *)(out + 25);
-        oi[0] = best; oi[1] = best > 0 ? be / PER_ITER : -1;
+        out->err = esum;
+        out->n_inliers = best; out->best_iter = best > 0 ? be / PER_ITER : -1;
         for (int c = 0; c < 4; c++)
             for (int r = 0; r < 3; r++) {
-                out[r + 3 * c] = (s_K[r] * s_P[3 * c] + s_K[r + 3] * s_P[3 * c + 1]) + s_K[r + 6] * s_P[3 * c + 2];
-                out[12 + r + 3 * c] = s_P[r + 3 * c];
+                out->KP[r + 3 * c] = (s_K[r] * s_P[3 * c] + s_K[r + 3] * s_P[3 * c + 1]) + s_K[r + 6] * s_P[3 * c + 2];
+                out->Rt[r + 3 * c] = s_P[r + 3 * c];
             }
     }
 };
@@ -293,21 +292,28 @@ __global__ __launch_bounds__(P3PSelect::THREADS) void k_p3p_select(P3PArgs T)
     const int z = blockIdx.x, ne = P3PSelect::PER_ITER * T.iters;
     const ProblemRange pr = problem_range(T.off, T.cnt, T.stride, z);
     const P3PSelect pol{T.Ks + 9 * z, T.poses + (size_t)z * ne * 12, T.pts + 3 * (size_t)pr.base, T.px + 2 * (size_t)pr.base, T.thr,
-                        T.out + 32 * (size_t)z, s_P, s_K};
+                        T.out + z, s_P, s_K};
     ransac_select(pol, T.counts + (size_t)z * ne, ne, pr.n, T.errs + pr.base, T.inliers + pr.base);
 }
 
 // the device scratch of P3PArgs (counts | poses | errs) as regions of the caller's layout, and the only launch site of the two kernels
 struct P3PScratch {
-    size_t counts, poses, errs;
+    Region<int> counts; Region<double> poses, errs;
     P3PScratch(Layout &L, int S, int iters, size_t npts)
-        : counts(L.take((size_t)S * iters * 16)), poses(L.take((size_t)S * iters * 4 * 96)), errs(L.take(npts * 8)) {}
-    void bind(P3PArgs &T, char *scr) const { T.counts = (int *)(scr + counts); T.poses = (double *)(scr + poses); T.errs = (double *)(scr + errs); }
+        : counts(L.take<int>((size_t)S * iters * 4)), poses(L.take<double>((size_t)S * iters * 4 * 12)), errs(L.take<double>(npts)) {}
+    void bind(P3PArgs &T, char *scr) const { T.counts = counts.at(scr); T.poses = poses.at(scr); T.errs = errs.at(scr); }
 };
 static void p3p_enqueue(slam_ctx *ctx, int S, const P3PArgs &T)
 {
     hipLaunchKernelGGL(k_p3p_score, dim3(T.iters, S), dim3(64), 0, ctx->stream, T);
     hipLaunchKernelGGL(k_p3p_select, dim3(S), dim3(P3PSelect::THREADS), 0, ctx->stream, T);
+}
+
+// problem z's record into the caller's arrays (Rt, error, best_iter may be null)
+static void p3p_copy_out(const P3POut &o, int z, double *KP, double *Rt, int *n_inliers, double *error, int *best_iter)
+{
+    memcpy(KP + 12 * z, o.KP, sizeof o.KP); if (Rt) memcpy(Rt + 12 * z, o.Rt, sizeof o.Rt);
+    n_inliers[z] = o.n_inliers; if (error) error[z] = o.err; if (best_iter) best_iter[z] = o.best_iter;
 }
 
 // S problems in one pair of launches (grid.y / grid.x = problem); offsets, intrinsics, inputs and outputs go through
@@ -319,51 +325,38 @@ static int p3p_run(slam_ctx *ctx, int S, const int32_t *off, const double *pts3d
     const int ntot = off[S];
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     Layout H;
-    const size_t o_off = H.take((size_t)(S + 1) * 4), o_K = H.take((size_t)S * 72), o_pts = H.take((size_t)ntot * 24), o_px = H.take((size_t)ntot * 16);
-    const size_t o_pdn = H.take((size_t)ntot * 24), o_smp = H.take((size_t)S * iters * 12), o_out = H.take((size_t)S * 256), o_inl = H.take((size_t)ntot);
+    const auto o_off = H.take<int>((size_t)S + 1); const auto o_K = H.take<double>((size_t)S * 9), o_pts = H.take<double>((size_t)ntot * 3), o_px = H.take<double>((size_t)ntot * 2);
+    const auto o_pdn = H.take<double>((size_t)ntot * 3); const auto o_smp = H.take<int32_t>((size_t)S * iters * 3); const auto o_out = H.take<P3POut>(S); const auto o_inl = H.take<uint8_t>(ntot);
     char *h, *d;
     int rc = slam_pinned(ctx, H.size(), (void **)&h);
     if (rc) return rc;
     HIP_TRY(ctx, hipHostGetDevicePointer((void **)&d, h, 0));
-    memcpy(h + o_off, off, (size_t)(S + 1) * 4); memcpy(h + o_K, K, (size_t)S * 72);
-    memcpy(h + o_pts, pts3d, (size_t)ntot * 24); memcpy(h + o_px, px_xy, (size_t)ntot * 16); memcpy(h + o_pdn, pdn, (size_t)ntot * 24);
-    memcpy(h + o_smp, samples, (size_t)S * iters * 12);
+    memcpy(o_off.at(h), off, o_off.bytes()); memcpy(o_K.at(h), K, o_K.bytes());
+    memcpy(o_pts.at(h), pts3d, o_pts.bytes()); memcpy(o_px.at(h), px_xy, o_px.bytes()); memcpy(o_pdn.at(h), pdn, o_pdn.bytes());
+    memcpy(o_smp.at(h), samples, o_smp.bytes());
     Layout D;
     const P3PScratch ds(D, S, iters, (size_t)ntot);
     char *scr;
     rc = slam_scratch(ctx, D.size(), (void **)&scr);
     if (rc) return rc;
     P3PArgs T;
-    T.pts = (const double *)(d + o_pts); T.px = (const double *)(d + o_px); T.pdn = (const double *)(d + o_pdn);
-    T.samples = (const int32_t *)(d + o_smp); T.off = (const int *)(d + o_off); T.Ks = (const double *)(d + o_K);
+    T.pts = o_pts.at(d); T.px = o_px.at(d); T.pdn = o_pdn.at(d); T.samples = o_smp.at(d); T.off = o_off.at(d); T.Ks = o_K.at(d);
     T.iters = iters; T.thr = threshold; T.cnt = nullptr; T.stride = 0;
-    ds.bind(T, scr);
-    T.out = (double *)(d + o_out); T.inliers = (uint8_t *)(d + o_inl);
+    ds.bind(T, scr); T.out = o_out.at(d); T.inliers = o_inl.at(d);
     { ProfScope span(ctx, "p3p_ransac");
       p3p_enqueue(ctx, S, T); }
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, slam_stream_wait(ctx->stream));
-    for (int z = 0; z < S; z++) {
-        const char *o = h + o_out + (size_t)z * 256;
-        memcpy(KP + 12 * z, o, 96);
-        if (Rt) memcpy(Rt + 12 * z, o + 96, 96);
-        if (error) memcpy(error + z, o + 192, 8);
-        memcpy(n_inliers + z, o + 200, 4);
-        if (best_iter) memcpy(best_iter + z, o + 204, 4);
-    }
-    memcpy(inliers, h + o_inl, (size_t)ntot);
+    for (int z = 0; z < S; z++) p3p_copy_out(o_out.at(h)[z], z, KP, Rt, n_inliers, error, best_iter);
+    memcpy(inliers, o_inl.at(h), o_inl.bytes());
     return SLAM_OK;
 }
 
 // "p3p_ransac returned nothing": zero pose, zero mask, no inliers, best_iter = -1 for each of the S problems
 static int p3p_empty(int S, int ntot, double *KP, double *Rt, uint8_t *inliers, int *n_inliers, double *error, int *best_iter)
 {
-    for (int z = 0; z < S; z++) {
-        n_inliers[z] = 0;
-        for (int j = 0; j < 12; j++) { KP[12 * z + j] = 0.0; if (Rt) Rt[12 * z + j] = 0.0; }
-        if (error) error[z] = 0.0;
-        if (best_iter) best_iter[z] = -1;
-    }
+    P3POut o = {}; o.best_iter = -1;
+    for (int z = 0; z < S; z++) p3p_copy_out(o, z, KP, Rt, n_inliers, error, best_iter);
     for (int i = 0; i < ntot; i++) inliers[i] = 0;
     return SLAM_OK;
 }
@@ -411,8 +404,8 @@ struct KPoseArgs {
     const double *par;                 // S x KP_PAR (kpset.hpp)
     double *pts, *px, *pdn; int *slot; int *n3;                                // gathered 3-D keypoints, stride cap per stream
     int32_t *samples; int iters; unsigned long long seed;
-    double *p3p_out; uint8_t *inl;     // k_p3p_select's outputs (S x 32 doubles; stride cap)
-    double *bpx, *bpts; int *bslot; uint8_t *outl; PnPArgs *pnp; double *res;   // refinement inputs / outputs
+    P3POut *p3p_out; uint8_t *inl;     // k_p3p_select's outputs (S records; stride cap)
+    double *bpx, *bpts; int *bslot; uint8_t *outl; PnPArgs *pnp; PnPResult *res;   // refinement inputs / outputs
     int iters_fast, iterations; double depth_eps, repr_eps;
     uint8_t *flags;                    // S x cap: observations to remove
     double *poses; int *status, *ninl; // S x 16 (column-major Tcw), S, S
@@ -459,22 +452,13 @@ __global__ __launch_bounds__(256) void k_kpose_samples(KPoseArgs A)
     sm[0] = idx[0]; sm[1] = idx[1]; sm[2] = idx[2];
 }
 
-// RotZYX(R).theta1..3 (Rotations.jl; get_cw_ba, frame.jl:432-437) of a column-major 3 x 4 [R | t]
-__device__ __forceinline__ void rt_to_x(const double *Rt, double *X)
-{
-    const double R11 = Rt[0], R21 = Rt[1], R31 = Rt[2], R12 = Rt[3], R22 = Rt[4], R13 = Rt[6], R23 = Rt[7];
-    const double t1 = atan2(R21, R11), s1 = sin(t1), c1 = cos(t1);
-    X[0] = t1; X[1] = atan2(-R31, sqrt(R11 * R11 + R21 * R21)); X[2] = atan2(R13 * s1 - R23 * c1, R22 * c1 - R12 * s1);
-    X[3] = Rt[9]; X[4] = Rt[10]; X[5] = Rt[11];
-}
-
 __global__ __launch_bounds__(256) void k_kpose_prep(KPoseArgs A)
 {
     __shared__ int s_w[4], s_base;
     const int z = blockIdx.x, tid = threadIdx.x, n = A.n3[z];
     const size_t b = (size_t)z * A.cap;
-    const double *out = A.p3p_out + 32 * (size_t)z;
-    const int best = ((const int *)(out + 25))[0];
+    const P3POut &out = A.p3p_out[z];
+    const int best = out.n_inliers;
     const bool ok = n >= 5 && best >= 5;                                     // :133, :179
     if (tid == 0) s_base = 0;
     __syncthreads();
@@ -498,8 +482,8 @@ __global__ __launch_bounds__(256) void k_kpose_prep(KPoseArgs A)
         const double *cam = A.par + KP_PAR * z + KP_PAR_CAM; P.cam = {cam[0], cam[1], cam[2], cam[3]};
         P.px = A.bpx + 2 * b; P.pts = A.bpts + 3 * b; P.n = ok ? s_base : 0;
         P.iters_fast = A.iters_fast; P.iterations = A.iterations; P.depth_eps = A.depth_eps; P.repr_eps = A.repr_eps;
-        P.outl = A.outl + b; P.result = A.res + 16 * (size_t)z;
-        if (ok) rt_to_x(out + 12, P.X0);                                     // set_cw!(frame, iK * KP) = [R | t] (:184)
+        P.outl = A.outl + b; P.result = A.res + z;
+        if (ok) pose_to_angles<3>(out.Rt, out.Rt + 9, P.X0);                                   // set_cw!(frame, iK * KP) = [R | t] (:184)
         else for (int a = 0; a < 6; a++) P.X0[a] = 0.0;
         A.pnp[z] = P;
         A.status[z] = ok ? 1 : 0; A.ninl[z] = ok ? best : 0;
@@ -510,24 +494,19 @@ __global__ __launch_bounds__(256) void k_kpose_finish(KPoseArgs A)
 {
     const int z = blockIdx.x, tid = threadIdx.x;
     const size_t b = (size_t)z * A.cap;
-    const double *r = A.res + 16 * (size_t)z;
-    const int n = A.pnp[z].n, no = (int)r[8];
+    const PnPResult &r = A.res[z];
+    const int n = A.pnp[z].n, no = (int)r.n_outliers;
     const bool p3p_ok = A.status[z] != 0;
     // :207-211: too few inliers after the refinement, or the refinement made the error worse -> reset (pose not applied, its
-    // outliers not removed); r[9] = pnp_bundle_adjustment's own < 5 inliers exit
-    const bool accept = p3p_ok && !(n - no < 5 || r[7] > r[6]) && r[9] == 0.0;
+    // outliers not removed); identity = pnp_bundle_adjustment's own < 5 inliers exit
+    const bool accept = p3p_ok && !(n - no < 5 || r.err_final > r.err_init) && r.identity == 0.0;
     if (accept)
         for (int i = tid; i < n; i += 256)
             if (A.outl[b + i]) A.flags[b + A.bslot[b + i]] = 1;              // :213-215
     if (tid == 0) {
         double *T = A.poses + 16 * (size_t)z;
         for (int k = 0; k < 16; k++) T[k] = (k % 5 == 0) ? 1.0 : 0.0;
-        if (accept) {
-            const double s1 = sin(r[0]), c1 = cos(r[0]), s2 = sin(r[1]), c2 = cos(r[1]), s3 = sin(r[2]), c3 = cos(r[2]);
-            const double R[9] = {c1 * c2, c1 * s2 * s3 - s1 * c3, c1 * s2 * c3 + s1 * s3, s1 * c2, s1 * s2 * s3 + c1 * c3, s1 * s2 * c3 - c1 * s3, -s2, c2 * s3, c2 * c3};
-            for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) T[i + 4 * j] = R[3 * i + j];
-            T[12] = r[3]; T[13] = r[4]; T[14] = r[5];
-        }
+        if (accept) angles_to_pose(r.X, T);
         A.status[z] = accept ? 1 : 0;
     }
 }
@@ -541,14 +520,14 @@ extern "C" int slam_kpset_compute_pose(slam_ctx *ctx, slam_kpset *ks, const doub
     const int S = ks->S, cap = ks->v.cap;
     const size_t nc = (size_t)S * cap;
     Layout D;                          // device scratch
-    const size_t o_pts = D.take(nc * 24), o_px = D.take(nc * 16), o_pdn = D.take(nc * 24), o_slot = D.take(nc * 4), o_n3 = D.take((size_t)S * 4);
-    const size_t o_smp = D.take((size_t)S * iters * 12);
+    const auto o_pts = D.take<double>(nc * 3), o_px = D.take<double>(nc * 2), o_pdn = D.take<double>(nc * 3); const auto o_slot = D.take<int>(nc), o_n3 = D.take<int>(S);
+    const auto o_smp = D.take<int32_t>((size_t)S * iters * 3);
     const P3PScratch ds(D, S, iters, nc);
-    const size_t o_out = D.take((size_t)S * 256), o_inl = D.take(nc);
-    const size_t o_bpx = D.take(nc * 16), o_bpts = D.take(nc * 24), o_bslot = D.take(nc * 4), o_outl = D.take(nc), o_pnp = D.take((size_t)S * sizeof(PnPArgs));
-    const size_t o_res = D.take((size_t)S * 128), o_flags = D.take(nc), o_T = D.take((size_t)S * 128), o_st = D.take((size_t)S * 4), o_ni = D.take((size_t)S * 4);
+    const auto o_out = D.take<P3POut>(S); const auto o_inl = D.take<uint8_t>(nc);
+    const auto o_bpx = D.take<double>(nc * 2), o_bpts = D.take<double>(nc * 3); const auto o_bslot = D.take<int>(nc); const auto o_outl = D.take<uint8_t>(nc); const auto o_pnp = D.take<PnPArgs>(S);
+    const auto o_res = D.take<PnPResult>(S); const auto o_flags = D.take<uint8_t>(nc); const auto o_T = D.take<double>((size_t)S * 16); const auto o_st = D.take<int>(S), o_ni = D.take<int>(S);
     Layout H;                          // pinned host block: K per stream (read by the kernels), then the results
-    const size_t h_K = H.take((size_t)S * 72), h_T = H.take((size_t)S * 128), h_st = H.take((size_t)S * 4), h_ni = H.take((size_t)S * 4), h_cn = H.take((size_t)S * 4);
+    const auto h_K = H.take<double>((size_t)S * 9); const size_t h_T = H.take((size_t)S * 128), h_st = H.take((size_t)S * 4), h_ni = H.take((size_t)S * 4), h_cn = H.take((size_t)S * 4);
     char *scr;
     int rc = slam_scratch2(ctx, D.size(), (void **)&scr);
     if (rc) return rc;
@@ -557,13 +536,13 @@ extern "C" int slam_kpset_compute_pose(slam_ctx *ctx, slam_kpset *ks, const doub
     if (rc) return rc;
     KPoseArgs A;
     A.yx = ks->v.yx; A.xyz = ks->v.xyz; A.is3d = ks->v.is3d; A.count = ks->v.count; A.cap = cap; A.par = par_dev;
-    A.pts = (double *)(scr + o_pts); A.px = (double *)(scr + o_px); A.pdn = (double *)(scr + o_pdn); A.slot = (int *)(scr + o_slot); A.n3 = (int *)(scr + o_n3);
-    A.samples = (int32_t *)(scr + o_smp); A.iters = iters; A.seed = seed;
-    A.p3p_out = (double *)(scr + o_out); A.inl = (uint8_t *)(scr + o_inl);
-    A.bpx = (double *)(scr + o_bpx); A.bpts = (double *)(scr + o_bpts); A.bslot = (int *)(scr + o_bslot); A.outl = (uint8_t *)(scr + o_outl);
-    A.pnp = (PnPArgs *)(scr + o_pnp); A.res = (double *)(scr + o_res);
+    A.pts = o_pts.at(scr); A.px = o_px.at(scr); A.pdn = o_pdn.at(scr); A.slot = o_slot.at(scr); A.n3 = o_n3.at(scr);
+    A.samples = o_smp.at(scr); A.iters = iters; A.seed = seed;
+    A.p3p_out = o_out.at(scr); A.inl = o_inl.at(scr);
+    A.bpx = o_bpx.at(scr); A.bpts = o_bpts.at(scr); A.bslot = o_bslot.at(scr); A.outl = o_outl.at(scr);
+    A.pnp = o_pnp.at(scr); A.res = o_res.at(scr);
     A.iters_fast = pnp_iters_fast; A.iterations = pnp_iterations; A.depth_eps = depth_eps; A.repr_eps = repr_eps;
-    A.flags = (uint8_t *)(scr + o_flags); A.poses = (double *)(scr + o_T); A.status = (int *)(scr + o_st); A.ninl = (int *)(scr + o_ni);
+    A.flags = o_flags.at(scr); A.poses = o_T.at(scr); A.status = o_st.at(scr); A.ninl = o_ni.at(scr);
     P3PArgs T;
     T.pts = A.pts; T.px = A.px; T.pdn = A.pdn; T.samples = A.samples; T.off = nullptr; T.cnt = A.n3; T.stride = cap;
     T.iters = iters; T.thr = threshold;
@@ -574,11 +553,11 @@ extern "C" int slam_kpset_compute_pose(slam_ctx *ctx, slam_kpset *ks, const doub
     rc = slam_pinned(ctx, H.size(), (void **)&h);
     if (rc) return rc;
     for (int z = 0; z < S; z++) {
-        double *K = (double *)(h + h_K) + 9 * z;
+        double *K = h_K.at(h) + 9 * z;
         for (int j = 0; j < 9; j++) K[j] = 0.0;
         const double *cam = params + KP_PAR * z + KP_PAR_CAM; K[0] = cam[0]; K[4] = cam[1]; K[6] = cam[2]; K[7] = cam[3]; K[8] = 1.0;
     }
-    HIP_TRY(ctx, hipHostGetDevicePointer((void **)&T.Ks, h + h_K, 0));
+    HIP_TRY(ctx, hipHostGetDevicePointer((void **)&T.Ks, h_K.at(h), 0));
     HIP_TRY(ctx, hipMemsetAsync(A.flags, 0, nc, ctx->stream));
     { ProfScope span(ctx, "kpset_compute_pose");
       hipLaunchKernelGGL(k_kpose_gather, dim3(S), dim3(256), 0, ctx->stream, A);

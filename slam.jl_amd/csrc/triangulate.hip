@@ -42,23 +42,23 @@ extern "C" int slam_triangulate(slam_ctx *ctx, const double *P1, const double *P
     ARG_TRY(ctx, P1 && P2 && T21 && cam1 && cam2 && px1_yx && px2_yx && out_xyz && status);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     Layout H;
-    const size_t o_px1 = H.take((size_t)n * 16), o_px2 = H.take((size_t)n * 16), o_par = H.take((size_t)n * 8), o_out = H.take((size_t)n * 24), o_st = H.take((size_t)n);
+    const auto o_px1 = H.take<double>((size_t)n * 2), o_px2 = H.take<double>((size_t)n * 2), o_par = H.take<double>(n), o_out = H.take<double>((size_t)n * 3); const auto o_st = H.take<uint8_t>(n);
     char *h, *d;
     int rc = slam_pinned(ctx, H.size(), (void **)&h);
     if (rc) return rc;
     HIP_TRY(ctx, hipHostGetDevicePointer((void **)&d, h, 0));
-    memcpy(h + o_px1, px1_yx, (size_t)n * 16); memcpy(h + o_px2, px2_yx, (size_t)n * 16);
-    if (parallax) memcpy(h + o_par, parallax, (size_t)n * 8);
+    memcpy(o_px1.at(h), px1_yx, o_px1.bytes()); memcpy(o_px2.at(h), px2_yx, o_px2.bytes());
+    if (parallax) memcpy(o_par.at(h), parallax, o_par.bytes());
     TriArgs T;
     T.M.fill(P1, P2, T21, cam1, cam2);
-    T.px1 = (const double *)(d + o_px1); T.px2 = (const double *)(d + o_px2); T.parallax = parallax ? (const double *)(d + o_par) : nullptr;
+    T.px1 = o_px1.at(d); T.px2 = o_px2.at(d); T.parallax = parallax ? o_par.at(d) : nullptr;
     T.max_error = max_error; T.min_depth = min_depth; T.min_parallax = min_parallax; T.n = n;
-    T.out = (double *)(d + o_out); T.status = (uint8_t *)(d + o_st);
+    T.out = o_out.at(d); T.status = o_st.at(d);
     { ProfScope span(ctx, "triangulate");
       hipLaunchKernelGGL(k_triangulate, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, T); }
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, slam_stream_wait(ctx->stream));
-    memcpy(out_xyz, h + o_out, (size_t)n * 24);
-    memcpy(status, h + o_st, (size_t)n);
+    memcpy(out_xyz, o_out.at(h), o_out.bytes());
+    memcpy(status, o_st.at(h), o_st.bytes());
     return SLAM_OK;
 }

@@ -292,7 +292,7 @@ def cases(syn):
         return _CASES
     c = []
     sc = lambda n, seed=None, **kw: syn.pnp_scene(n=n, seed=n if seed is None else seed, **kw)
-    # ---- (0, 0): the pose round trip pnp_pose_to_x -> pnp_x_to_pose, initial_error and the inlier cost at X0 (nothing flagged) ----
+    # ---- (0, 0): the pose round trip pose_to_angles<4> -> angles_to_pose, initial_error and the inlier cost at X0 (nothing flagged) ----
     for n in (5, 64, 257):
         c.append(_case(f"trip_n{n}", sc(n), 0, 0, **OFF))
     for tag, t2 in (("1.2", 1.2), ("below_half_pi", np.pi / 2 - 1e-9), ("plus_half_pi", np.pi / 2), ("minus_half_pi", -np.pi / 2)):

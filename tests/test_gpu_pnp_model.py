@@ -204,7 +204,7 @@ def _compute_pose_against_model(slam, orc, syn, label, scenes, n2, iters_fast, i
 def test_compute_pose_refinement_against_the_model(slam, orc, syn):
     """k_kpose_prep -> k_pnp_batch -> k_kpose_finish.  Streams: the reference's counts on 400 / 250 keypoints with gross outliers and on fewer
     than five 3-D keypoints (status 0); depth_eps = 25 m with exactly FIVE keypoints beyond it (accepted) and exactly FOUR (reset:
-    identity, nothing of the refinement removed); pnp_iters_fast = pnp_iterations = 0 (the pose is the P3P pose through rt_to_x and
+    identity, nothing of the refinement removed); pnp_iters_fast = pnp_iterations = 0 (the pose is the P3P pose through pose_to_angles<3> and
     k_kpose_finish's rotation).  A stream where the refinement RAISES the cost does not exist (see the assertion in the helper): the
     `e1 > e0` test of k_kpose_finish can only see e1 == e0, which the (0, 0) stream without flagged points produces -- and accepts.
     A P3P pose at theta2 = +-pi/2 cannot be prescribed (P3P returns its own solution of a triple); slam_pnp_ba's round-trip cases
