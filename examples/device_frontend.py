@@ -8,10 +8,16 @@ lock-stepped stereo streams with every keypoint list resident in HBM -- the call
     KeypointSet.compute_pose       P3P RANSAC + PnP refinement -> the frame's pose              (compute_pose!)
     key-frames: detect -> keyframe -> right frames -> stereo_match -> triangulate -> triangulate_temporal   (create_keyframe!, mapper)
     --adaptive-keyframes: KeypointSet.frame_stats + keyframe_required after the pose                 (check_new_kf_required)
+    --local-ba: after every key-frame step KeyframeMap.add_keyframe -> gather -> bundle_adjustment_batch_ -> update(ks)   (local_bundle_adjustment!)
 
 No host keypoint arrays anywhere; per frame the host receives S poses, S status words and S list lengths.  It is an
-array-level driver, not SLAM (no map maintenance, no bundle adjustment, no relocalisation): what it shows is that the seams
-compose -- on a rigid synthetic scene the poses it returns are the camera motion.
+array-level driver, not SLAM (no map filtering, no relocalisation): what it shows is that the seams compose -- on a rigid synthetic
+scene the poses it returns are the camera motion.
+
+With --local-ba the estimator's step runs too, on a key-frame map that lives in HBM beside the lists (slam_kfmap): every key-frame is recorded
+from the lists, the windows of the streams' newest key-frames are gathered in slam_local_ba_batch's layout, solved in one batch, and the
+solution goes back into the map AND the live lists -- the front end tracks refined landmarks from the next frame on.  Under
+--adaptive-keyframes / --per-stream-keyframes the map calls run under the same selection as the key-frame seams.
 
 Key-frames are taken every `kf_every`-th frame, or, with --adaptive-keyframes, where the reference's rule asks for one
 (front_end.jl:361-393 on the statistics of the lists, one S x 8 read-back per frame).  The streams are lock-stepped -- every launch is
@@ -19,7 +25,7 @@ shared -- so --adaptive-keyframes alone takes a key-frame FOR ALL streams when A
 stream follow its own rule: the key-frame seams run under KeypointSet.selected(required), which restricts them to the streams that asked
 (slam_kpset_select), and the key-frame bookkeeping (last key-frame, its nb_3d_kpts, its pose, the observer ring, the key-frame id) is per stream.
 
-    python examples/device_frontend.py --frames 12 --streams 4 [--adaptive-keyframes | --per-stream-keyframes]
+    python examples/device_frontend.py --frames 12 --streams 4 [--adaptive-keyframes | --per-stream-keyframes] [--local-ba]
 """
 import argparse
 import contextlib
@@ -34,7 +40,7 @@ import slam_jl_amd as slam  # noqa: E402
 from slam_jl_amd import synthetic as syn  # noqa: E402
 
 
-def run(lefts, rights, cam, baseline, kf_every=4, max_keypoints=300, seed=0, ctx=None, verbose=False, adaptive=False, probe=None, per_stream=False):
+def run(lefts, rights, cam, baseline, kf_every=4, max_keypoints=300, seed=0, ctx=None, verbose=False, adaptive=False, probe=None, per_stream=False, local_ba=False):
     """lefts / rights: per stream a list of float images in [0, 1] (H, W).  Returns per frame a dict with the S poses
     (world -> camera, world = the first frame's camera), status words, list lengths and the wall time.
     adaptive: frame 0 is a key-frame; after the pose of every later frame the lists' statistics (KeypointSet.frame_stats, flags = 1) go
@@ -43,7 +49,10 @@ def run(lefts, rights, cam, baseline, kf_every=4, max_keypoints=300, seed=0, ctx
     taken when it was created).  probe(frame, keypoint set, R_compensation (S, 3, 3)) is called right after the statistics are taken.
     per_stream (implies adaptive): frame 0 is a key-frame for all streams; afterwards stream s takes a key-frame exactly where keyframe_required
     says so for s -- the key-frame seams run on the selected streams only -- and `keyframe` of a row is an (S,) bool array.  (The right-pyramid
-    batch is still built for all S streams at such a frame: a batch build takes the whole batch.)"""
+    batch is still built for all S streams at such a frame: a batch build takes the whole batch.)
+    local_ba: a KeyframeMap follows the key-frames; after the key-frame seams (same selection) the key-frame is added, the windows are gathered,
+    solved by bundle_adjustment_batch_ and written back into the map and the lists.  Rows of key-frame steps carry `ba`: per solved window
+    (stream, P, M, O, outliers, ssr before, ssr after)."""
     adaptive = adaptive or per_stream
     import torch
     ctx = ctx or slam.default_context(0)
@@ -55,6 +64,7 @@ def run(lefts, rights, cam, baseline, kf_every=4, max_keypoints=300, seed=0, ctx
     ex = slam.Extractor.from_params(params, camera)
     ncell = ex.grid_resolution[0] * ex.grid_resolution[1]
     ks = slam.KeypointSet(S, max_keypoints + ncell + 8, ctx=ctx)
+    km = slam.KeyframeMap(S, ks.cap, R=16, mcap=8192, ctx=ctx) if local_ba else None
     prev = slam.PyramidBatch((H, W), levels=params.pyramid_levels, S=S, ctx=ctx)
     cur = slam.PyramidBatch((H, W), levels=params.pyramid_levels, S=S, ctx=ctx)
     rpyr = slam.PyramidBatch((H, W), levels=params.pyramid_levels, S=S, ctx=ctx)
@@ -118,6 +128,14 @@ def run(lefts, rights, cam, baseline, kf_every=4, max_keypoints=300, seed=0, ctx
                 ks.triangulate(cam, cam, T21, Twc, max_error=params.max_reprojection_error, ctx=ctx)
                 if (kfid[kf_mask] > 0).any():                               # mapper.jl:86: 2-D keypoints left over, against their first observers
                     ks.triangulate_temporal(slam.stream_params(S, cam=cam), kf_cw, Twc, kfid, max_error=params.max_reprojection_error, ctx=ctx)
+                if km is not None:                                          # local_bundle_adjustment! (estimator.jl:317-347) of the streams that took the key-frame
+                    km.add_keyframe(ks, slam.stream_params(S, Tcw=Tcw, cam=cam), ctx=ctx)
+                    wins, _ = km.gather(params.min_cov_score, ctx=ctx)
+                    if wins:
+                        slam.bundle_adjustment_batch_([w.cache for w in wins], cam, ctx=ctx)
+                        km.update(wins, ks=ks, ctx=ctx)
+                    decision["ba"] = [(w.stream, w.cache.n_poses, w.cache.n_points, len(w.cache.poses_ids), int(w.cache.outliers.sum()),
+                                       w.cache.stats["ssr_init"], w.cache.stats["ssr_final"]) for w in wins]
             if adaptive:                                                    # the key-frame's own nb_3d_kpts, after the mapper's triangulations
                 last_kf[kf_mask] = i
                 nb_3d = ks.frame_stats(slam.stream_params(S, cam=cam), 0, ex.cell_size, (H, W), ctx=ctx)[:, 1].astype(np.int32)
@@ -130,7 +148,11 @@ def run(lefts, rights, cam, baseline, kf_every=4, max_keypoints=300, seed=0, ctx
         if verbose:
             print(f"frame {i:3d} kf={row['keyframe']!s:5} keypoints {cnt.tolist()} pose ok {status.tolist()} 5pt ok {np.asarray(st5).tolist()} "
                   f"t = {np.round(Tcw[0][:3, 3], 3).tolist()} {row['ms']:.2f} ms")
+            for s_, P_, M_, O_, no_, e0_, e1_ in row.get("ba", []):
+                print(f"          local BA stream {s_}: window of {P_} poses, {M_} points, {O_} observations; {no_} outliers, ssr {e0_:.3f} -> {e1_:.3f}")
     n3 = [int(ks.download(s)["is_3d"].sum()) for s in range(S)]
+    if km is not None:
+        km.close()
     ks.close()
     return out, n3
 
@@ -152,17 +174,21 @@ def main():
     ap.add_argument("--streams", type=int, default=2)
     ap.add_argument("--adaptive-keyframes", action="store_true", help="take key-frames where check_new_kf_required asks for one (any stream), not every 4th frame")
     ap.add_argument("--per-stream-keyframes", action="store_true", help="every stream takes its key-frames where check_new_kf_required asks for one for THAT stream (implies --adaptive-keyframes)")
+    ap.add_argument("--local-ba", action="store_true", help="run the estimator's local BA after every key-frame step, on a key-frame map in HBM; the lists take the refined landmarks")
     ap.add_argument("--replay-dir", default=None, help="write stream s's camera positions to DIR/stream_s as a ReplaySaver dump (src/io/saver.jl)")
     args = ap.parse_args()
     cam, baseline, disparity = syn.KITTI_CAM, 0.54, 8.0
     lefts, rights, offs = synthetic_scene(args.streams, args.frames, disparity=disparity)
-    out, n3 = run(lefts, rights, cam, baseline, verbose=True, adaptive=args.adaptive_keyframes, per_stream=args.per_stream_keyframes)
+    out, n3 = run(lefts, rights, cam, baseline, verbose=True, adaptive=args.adaptive_keyframes, per_stream=args.per_stream_keyframes, local_ba=args.local_ba)
     Z = cam[0] * baseline / disparity
     for s in range(args.streams):
         o = offs[s][-1] - offs[s][0]
         want = np.array([o[1] * Z / cam[0], o[0] * Z / cam[1], 0.0])
         got = out[-1]["poses"][s][:3, 3]
         print(f"stream {s}: translation {np.round(got, 3).tolist()} m, expected {np.round(want, 3).tolist()} m (plane at {Z:.1f} m), {n3[s]} map points")
+        if args.local_ba:
+            n_win = sum(1 for r in out for w in r.get("ba", []) if w[0] == s)
+            print(f"stream {s}: {n_win} local-BA windows solved, motion error {np.abs(got - want).max():.4f} m")
     if args.replay_dir:
         import os
         for s in range(args.streams):

@@ -280,7 +280,9 @@ int slam_flow_match_batch_kept(slam_ctx *ctx, const slam_pyr *from0, const slam_
  * never selects).  An unselected stream comes out of the six seams as it went in -- every per-keypoint array, its list length, its
  * key-frame counter and its id counter byte for byte -- and none of the per-stream inputs a seam takes for it (params row, Twc, tab,
  * kf_cur, kf_lo) has any effect; a selected stream's result does not depend on which other streams are selected.  Launches are sized
- * by the number of selected streams; with none selected the six seams check their arguments and enqueue nothing. */
+ * by the number of selected streams; with none selected the six seams check their arguments and enqueue nothing.
+ * slam_kfmap_add_keyframe (the key-frame map, below) reads the lists of a key-frame and honours the selection like the six: an unselected
+ * stream's map comes out byte for byte as it went in. */
 typedef struct slam_kpset slam_kpset;
 int slam_kpset_create(slam_ctx *ctx, int S, int cap, slam_kpset **out);
 int slam_kpset_destroy(slam_kpset *ks);
@@ -420,6 +422,70 @@ int slam_kpset_frame_stats(slam_ctx *ctx, slam_kpset *ks, const double *params, 
 int slam_keyframe_required(int S, const double *stats, const int32_t *frames_delta, const int32_t *prev_kf_nb_3d,
                            const uint8_t *has_prev_kf, int max_nb_keypoints, double initial_parallax, int local_ba_on,
                            uint8_t *required, uint8_t *rule);
+
+/* ---- the key-frame map of the lists: gather and apply local-BA windows --------------------------------------------------------------------
+ * What local_bundle_adjustment! reads and writes of the map manager (_get_ba_parameters src/estimator.jl:143-266, _update_ba_parameters!
+ * :268-306; update_frame_covisibility! map_manager.jl:302-340, remove_mappoint_obs! :224-, remove_mappoint! :139-168, is_bad!
+ * map_point.jl:155-161) for S lock-stepped streams whose keypoints live in a slam_kpset: a per-stream map in HBM, filled from the lists,
+ * that emits LocalBACache arrays (estimator.jl:16-40) in slam_local_ba_batch's layout and takes the solution back.  One allocation:
+ *   ring    R key-frames per stream, 2 <= R <= 64: key-frame k in slot k % R with get_cw_ba (frame.jl:432-437; 6 doubles), the list's ids
+ *           (ascending), the undistorted pixels (y, x) and a live flag per observation (a removed observation is a tombstone).  Reusing a
+ *           slot first forgets the old key-frame as remove_keyframe! does (map_manager.jl:184-209): its points lose that observer.
+ *   table   mcap points per stream: point `id` in entry id % mcap with xyz, a 64-bit observer mask (bit k % R) and the flags is_3d,
+ *           observed, ba, gone.  A newer id that lands on an occupied entry replaces it; the old point is gone, its observations are
+ *           skipped like a missing map point.
+ * `observed` is what the last slam_kfmap_add_keyframe saw (cleared by slam_kfmap_ba_update for what it removes from the frame); it is NOT
+ * refreshed every frame as the reference's is_observed is.  Orders the reference takes from Dicts and Sets (a key-frame's 3-D keypoints, a
+ * point's observers) are ascending by id; the covisibility walk is newest first over the <= 5 newest covisible key-frames and the dense
+ * 1-based ids are numbered in first-encounter order, as in _get_ba_parameters.
+ * Ordering across contexts: as for slam_kpset_select -- the map calls run in their ctx's stream order; a host that drives one map (or the
+ * map and its set) from several contexts orders the calls against each other and against the list seams with events. */
+typedef struct slam_kfmap slam_kfmap;
+int slam_kfmap_create(slam_ctx *ctx, int S, int cap, int R, int mcap, slam_kfmap **out);   /* cap >= the set's cap */
+int slam_kfmap_destroy(slam_kfmap *km);
+/* Record the key-frame slam_kpset_keyframe has just made (call it right after): stream s records key-frame kfcount[s] - 1 from its list
+ * (id, pixel, is_3d, map point; a 3-D keypoint's position replaces the point's unless a bundle adjustment has set it).  params: S x 32 as
+ * for the seams above -- [0..15] Tcw, whose RotZYX angles and translation become the key-frame's theta; [16..23] fx fy cx cy k1 k2 p1 p2:
+ * the stored pixel is undistort_point (camera.jl:98-125) of the list's, or the pixel itself when k1 = k2 = p1 = p2 = 0.  An id the frame
+ * has lost (gone) is not recorded.  A KEY-FRAME SEAM: acts on the set's selected streams; the selection is remembered as the map's own (it
+ * names the streams slam_kfmap_ba_gather acts on).  Enqueue-only. */
+int slam_kfmap_add_keyframe(slam_ctx *ctx, slam_kfmap *km, slam_kpset *ks, const double *params /* S x 32 */);
+/* The windows of the newest key-frames of the streams the last slam_kfmap_add_keyframe acted on, back to back in window order, as
+ * slam_local_ba_batch takes them.  The caller owns every array; cap_* are their total capacities (windows; poses: theta_const,
+ * poses_remap; points: points_remap; observations: pixels_yx x 2, pose_ids, point_ids, obs_*; theta holds 6 cap_poses + 3 cap_points
+ * doubles).  status[s] (S entries): 0 window produced; 1 none (fewer than min_cov_score[s] 3-D keypoints, estimator.jl:321, or no
+ * observation: the first key-frame); 2 the window does not fit what is left of the capacities -- nothing of it is written, later windows
+ * are unaffected, the stream has no pending window (the is_bad! demotions its gather made stay: any later gather makes them again); 3 not selected.  The bookkeeping arrays (poses_remap, points_remap: key-frame / keypoint id of a dense id; obs_kf,
+ * obs_kp, obs_in_covmap per observation) may be NULL.  The map keeps every produced window's bookkeeping, its `bad` set included, as the
+ * stream's pending window.  Synchronous: the estimator step's one copy of results (after one small copy of the window sizes). */
+typedef struct slam_kfmap_windows {
+    int32_t cap_windows, cap_poses, cap_points, cap_obs;
+    int32_t *status, *win_stream, *Pn, *Mn, *On;
+    double *theta;
+    uint8_t *theta_const;
+    double *pixels_yx;
+    int64_t *pose_ids, *point_ids;
+    int64_t *poses_remap, *points_remap, *obs_kf, *obs_kp;
+    uint8_t *obs_in_covmap;
+} slam_kfmap_windows;
+int slam_kfmap_ba_gather(slam_ctx *ctx, slam_kfmap *km, const int32_t *min_cov_score /* S */, const slam_kfmap_windows *out, int32_t *n_windows);
+/* _update_ba_parameters! for the pending windows of the listed streams: theta and outliers as slam_local_ba_batch left them (windows back
+ * to back, in win_stream's order).  Refined poses and positions go into the map, an outlier observation inside the covisibility map is
+ * removed, is_bad! is evaluated after all removals and removes the points it condemns.  Everything goes by key-frame and keypoint id: key-frames
+ * added since the gather do not matter, one the ring has forgotten meanwhile is skipped.  ks != NULL: the live lists follow -- a 3-D keypoint
+ * whose point was kept takes the refined position; an outlier observation of the window's own key-frame (remove_obs_from_current_frame!) and
+ * an observed point that was removed leave the list (slam_kpset_remove's compaction); nothing else in the lists changes.  A stream without a
+ * pending window is an argument error and nothing is enqueued for any stream; a window is consumed by its update.  Enqueue-only. */
+int slam_kfmap_ba_update(slam_ctx *ctx, slam_kfmap *km, slam_kpset *ks /* nullable */, int n_windows, const int32_t *win_stream,
+                         const double *theta, const uint8_t *outliers);
+/* read-backs (tests, checkpoints).  download_keyframe: *n_out = -1 when key-frame kfid is not in the ring.  download_points: the valid
+ * entries in id order; flags bit 0 is_3d, 1 observed, 2 ba, 3 gone; point k's observer key-frame ids, ascending, are
+ * obs_kf[obs_off[k] .. obs_off[k + 1]) (obs_off: cap_out + 1 entries).  slam_kfmap_reset empties stream s's map (enqueue-only). */
+int slam_kfmap_download_keyframe(slam_ctx *ctx, slam_kfmap *km, int s, int kfid, double *theta, int64_t *ids, double *upx_yx, uint8_t *live,
+                                 int cap_out, int *n_out);
+int slam_kfmap_download_points(slam_ctx *ctx, slam_kfmap *km, int s, int64_t *ids, double *xyz, uint8_t *flags, int32_t *obs_off,
+                               int32_t *obs_kf, int cap_out, int cap_obs, int *n_out);
+int slam_kfmap_reset(slam_ctx *ctx, slam_kfmap *km, int s);
 
 /* ---- one live stream, one call per frame (round 6) -----------------------------------------------------------------------------------
  * What run!() does per frame (src/front_end.jl:58-113: preprocess! :454-470 = copy!(previous_pyramid, current_pyramid) + update!,

@@ -22,3 +22,4 @@ from .frontend import FrontEnd, FrontEndConfig  # noqa: F401
 from .saver import ReplaySaver  # noqa: F401
 from .keypoint_set import (KeypointSet, stream_params, pose_samples, pose_inputs, pose_samples5, pose_5pt_inputs,  # noqa: F401
                            pose_5pt_compose, keyframe_required)
+from .keyframe_map import KeyframeMap  # noqa: F401

@@ -99,6 +99,14 @@ SIGNATURES = {
     "slam_kpset_compute_pose_5pt": (cint, [vp, vp, f64p, dbl, dbl, cint, C.c_uint64, f64p, i32p, i32p, f64p, i32p]),
     "slam_kpset_frame_stats": (cint, [vp, vp, f64p, cint, cint, cint, cint, vp, f64p]),
     "slam_keyframe_required": (cint, [cint, f64p, i32p, i32p, u8p, cint, dbl, cint, u8p, u8p]),
+    "slam_kfmap_create": (cint, [vp, cint, cint, cint, cint, C.POINTER(vp)]),
+    "slam_kfmap_destroy": (cint, [vp]),
+    "slam_kfmap_add_keyframe": (cint, [vp, vp, vp, f64p]),
+    "slam_kfmap_ba_gather": (cint, [vp, vp, i32p, vp, i32p]),
+    "slam_kfmap_ba_update": (cint, [vp, vp, vp, cint, i32p, f64p, u8p]),
+    "slam_kfmap_download_keyframe": (cint, [vp, vp, cint, cint, f64p, i64p, f64p, u8p, cint, C.POINTER(cint)]),
+    "slam_kfmap_download_points": (cint, [vp, vp, cint, i64p, f64p, u8p, i32p, i32p, cint, cint, C.POINTER(cint)]),
+    "slam_kfmap_reset": (cint, [vp, vp, cint]),
     "slam_kpset_compute_pose": (cint, [vp, vp, f64p, dbl, cint, C.c_uint64, cint, cint, dbl, dbl, f64p, i32p, i32p, i32p]),
     "slam_local_ba": (cint, [vp, dbl, dbl, dbl, dbl, cint, cint, cint, f64p, u8p, f64p, i64p, i64p, u8p, cint, cint, dbl, f64p]),
     "slam_local_ba_batch": (cint, [vp, cint, f64p, i32p, i32p, i32p, f64p, u8p, f64p, i64p, i64p, u8p, cint, cint, dbl, f64p, i32p]),

@@ -1,0 +1,661 @@
+// kfmap.hip -- the key-frame map of S lock-stepped streams in HBM (kfmap.hpp has the layout): filled from the keypoint lists (slam_kfmap_add_keyframe),
+// it emits the local-BA windows of the streams' newest key-frames in slam_local_ba_batch's layout (slam_kfmap_ba_gather) and takes the solution back, into
+// the map and optionally into the live lists (slam_kfmap_ba_update).  The semantics are _get_ba_parameters / _update_ba_parameters!
+// (src/estimator.jl:143-306) as tests/tracked_ba.py restates them, bounded by the ring and the table (tests/np_kfmap.py is the bounded model).
+//
+// Every kernel takes `sel`: nullptr = workgroup (or grid row) b works on stream b, else on stream sel[b] -- launches are sized by the number of streams
+// acted on, so nothing of any other stream is read or written.
+#include "kfmap.hpp"
+#include <algorithm>
+#include <climits>
+
+#define KFM_STREAM(b) (sel ? sel[b] : (int)(b))
+// the table entry of point `id` (ids are non-negative; taken as unsigned, any 64 bits land inside the table)
+__device__ __forceinline__ size_t kfm_entry(int64_t id, int mcap) { return (size_t)((unsigned long long)id % (unsigned long long)mcap); }
+__device__ __forceinline__ bool kfm_valid(const KfmapView &V, size_t pe, int64_t id) { return V.ptag[pe] == (unsigned long long)id + 1ull && !(V.pflags[pe] & KFM_DEAD); }
+// index of `id` among the ascending ids[0 .. n), or -1
+__device__ __forceinline__ int kfm_find(const int64_t *ids, int n, int64_t id)
+{
+    int lo = 0, hi = n;
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (ids[mid] < id) lo = mid + 1; else hi = mid; }
+    return lo < n && ids[lo] == id ? lo : -1;
+}
+// the live observation of `id` in slot b's slab of stream s, or -1
+__device__ __forceinline__ int kfm_find_live(const KfmapView &V, int s, int b, int64_t id)
+{
+    const size_t sl = ((size_t)s * V.R + b) * V.cap;
+    const int i = kfm_find(V.kid + sl, min(V.kn[s * V.R + b], V.cap), id);
+    return i >= 0 && V.klive[sl + i] ? i : -1;
+}
+
+// ---- recording: slot-parallel, one thread per list slot (grid.y = stream) -------------------------------------------------------------------------------
+// remove_keyframe! (map_manager.jl:184-209) as far as the map goes: the key-frame whose slot the new one takes is forgotten, every point it observed
+// loses that observer.  Several slots of the slab may not name the same point (ids are unique), but the atomic keeps the read-modify-write whole anyway.
+__global__ __launch_bounds__(256) void k_kfm_forget(KfmapView V, const int *kfcount, const int *sel)
+{
+    const int s = KFM_STREAM(blockIdx.y), i = blockIdx.x * 256 + threadIdx.x, kfid = kfcount[s] - 1;
+    if (kfid < 0) return;
+    const int r = kfid % V.R, t = V.tag[s * V.R + r];
+    if (t == 0 || t == kfid + 1 || i >= min(V.kn[s * V.R + r], V.cap)) return;
+    const size_t q = ((size_t)s * V.R + r) * V.cap + i;
+    if (!V.klive[q]) return;
+    const int64_t id = V.kid[q];
+    const size_t pe = (size_t)s * V.mcap + kfm_entry(id, V.mcap);
+    if (V.ptag[pe] == (unsigned long long)id + 1ull) atomicAnd(&V.pmask[pe], ~(1ull << r));
+}
+// "for mp in rec.mps.values(): mp.observed = False"
+__global__ __launch_bounds__(256) void k_kfm_clear_observed(KfmapView V, const int *kfcount, const int *sel)
+{
+    const int s = KFM_STREAM(blockIdx.y), e = blockIdx.x * 256 + threadIdx.x;
+    if (kfcount[s] < 1 || e >= V.mcap) return;
+    V.pflags[(size_t)s * V.mcap + e] &= (uint8_t)~KFM_OBS;
+}
+// who owns a table entry after this key-frame: the largest id that maps to it (a newer id replaces an older one); kfresh: whether the point is new
+__global__ __launch_bounds__(256) void k_kfm_claim(KfmapView V, KpsetView K, const int *sel)
+{
+    const int s = KFM_STREAM(blockIdx.y), i = blockIdx.x * 256 + threadIdx.x;
+    if (K.kfcount[s] < 1 || i >= min(K.count[s], V.cap)) return;
+    const int64_t id = K.id[(size_t)s * K.cap + i];
+    const size_t pe = (size_t)s * V.mcap + kfm_entry(id, V.mcap);
+    const unsigned long long mine = (unsigned long long)id + 1ull;
+    const uint8_t fl = V.pflags[pe];                             // (flags are written by the record pass only: a kernel boundary away)
+    uint8_t fresh;
+    if (V.ptag[pe] == mine && (fl & KFM_GONE)) fresh = 2;
+    else { const unsigned long long old = atomicMax(&V.ptag[pe], mine); fresh = old != mine || (fl & KFM_DEAD) ? 1 : 0; }
+    V.kfresh[(size_t)s * V.cap + i] = fresh;
+}
+// tracked_ba.add_keyframe: the slab of the new key-frame, and every listed point's entry (one thread per entry: its owner's)
+__global__ __launch_bounds__(256) void k_kfm_record(KfmapView V, KpsetView K, const double *par, const int *sel)
+{
+    const int s = KFM_STREAM(blockIdx.y), i = blockIdx.x * 256 + threadIdx.x, kfid = K.kfcount[s] - 1;
+    if (kfid < 0) return;
+    const int r = kfid % V.R, n = min(K.count[s], V.cap);
+    const double *P = par + KP_PAR * (size_t)s;
+    if (i == 0) {
+        double X[6];
+        pose_to_angles<4>(P, P + 12, X);
+        for (int k = 0; k < 6; k++) V.ktheta[6 * ((size_t)s * V.R + r) + k] = X[k];
+        V.tag[s * V.R + r] = kfid + 1; V.kn[s * V.R + r] = n; V.cur[s] = kfid + 1;
+    }
+    if (i >= n) return;
+    const size_t ql = (size_t)s * K.cap + i, q = ((size_t)s * V.R + r) * V.cap + i;
+    const int64_t id = K.id[ql];
+    double cam[4], dist[4], y = K.yx[2 * ql], x = K.yx[2 * ql + 1];
+    load_cam(P, cam, dist);
+    if (dist[0] != 0.0 || dist[1] != 0.0 || dist[2] != 0.0 || dist[3] != 0.0) undistort_px(cam, dist, y, x, y, x);     // (all zero: the pixel as it is, a copy)
+    const uint8_t fresh = V.kfresh[(size_t)s * V.cap + i];
+    V.kid[q] = id; V.kupx[2 * q] = y; V.kupx[2 * q + 1] = x; V.klive[q] = fresh != 2;
+    const size_t pe = (size_t)s * V.mcap + kfm_entry(id, V.mcap);
+    if (fresh == 2 || V.ptag[pe] != (unsigned long long)id + 1ull) return;      // not recorded; or an older id whose entry a newer point holds: an orphan
+    const bool t3 = K.is3d[ql] != 0;
+    if (fresh) {
+        for (int k = 0; k < 3; k++) V.pxyz[3 * pe + k] = K.xyz[3 * ql + k];
+        V.pmask[pe] = 1ull << r; V.pflags[pe] = KFM_OBS | (t3 ? KFM_3D : 0);
+    } else {
+        const uint8_t fl = V.pflags[pe];
+        V.pmask[pe] |= 1ull << r;
+        if (t3 && !(fl & KFM_BA)) for (int k = 0; k < 3; k++) V.pxyz[3 * pe + k] = K.xyz[3 * ql + k];
+        V.pflags[pe] = fl | KFM_OBS | (t3 ? KFM_3D : 0);
+    }
+}
+
+// ---- gather ---------------------------------------------------------------------------------------------------------------------------------------------
+// exclusive scan of one count per thread over the 256 threads (wave shuffles + one LDS hop); *s_base carries the running total across calls
+__device__ __forceinline__ int kfm_scan(int cnt, int *s_w, int *s_base)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    int incl = cnt;
+    for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(incl, o, 64); if (lane >= o) incl += t; }
+    if (lane == 63) s_w[wv] = incl;
+    __syncthreads();
+    int off = *s_base + incl - cnt;
+    for (int w = 0; w < wv; w++) off += s_w[w];
+    __syncthreads();
+    if (tid == 0) *s_base += s_w[0] + s_w[1] + s_w[2] + s_w[3];
+    __syncthreads();
+    return off;
+}
+// The plan of one stream's window (tracked_ba.gather up to its arrays), one 256-thread workgroup per stream, no workgroup waits for another:
+//   covisibility   one pass over the newest key-frame's slab: nb_3d and, per other observer slot, the shared points (LDS atomics)
+//   covmap         the at most 5 newest covisible key-frames (one thread; R <= 64), walked newest first
+//   phase          per co-key-frame a pass over its slab in chunks of 256: a thread takes its slot's point if it is 3-D and not yet processed, demotes it
+//                  (is_bad) or accepts it and validates its observers (binary search per observer slab); the point's rank is a ballot prefix
+//                  (ordered_slot), its first observation index a scan of the observer counts; a pose's first observation index is an LDS atomicMin
+//   poses          after each phase the key-frames first met in it take the next pose ids in the order of those indices (one thread): membership in
+//                  `poses` decides whether a later low-score co-key-frame is walked, hence the phases are dependent
+// Everything the emit pass and the update need goes into the stream's pending-window regions; hdr = status (0 window, 1 none), kfid, P, M, O.
+__global__ __launch_bounds__(256) void k_kfm_plan(KfmapView V, const int *minc_all, const int *sel)
+{
+    __shared__ int s_cov[64], s_first[64], s_order[64], s_asc[64], s_rank[64], s_tag[64], s_w[4], s_base, s_obase, s_cl[N_COVISIBLE], s_ncl, s_P, s_nb3, s_nv, s_nbad;
+    __shared__ unsigned long long s_covmask;
+    const int s = KFM_STREAM(blockIdx.x), tid = threadIdx.x, R = V.R, cap = V.cap, mcap = V.mcap;
+    int *hdr = V.whdr + KFM_HDR * (size_t)s;
+    const int minc = minc_all[s], kfid = V.cur[s] - 1;
+    const size_t pb = (size_t)s * mcap;
+    if (tid < 64) { s_cov[tid] = 0; s_first[tid] = INT_MAX; s_order[tid] = 0; s_rank[tid] = 0; s_tag[tid] = tid < R ? V.tag[s * R + tid] : 0; }
+    if (tid == 0) { s_nb3 = 0; s_P = 0; s_base = 0; s_obase = 0; s_nbad = 0; s_ncl = 0; s_nv = 0; }
+    for (int e = tid; e < mcap; e += 256) V.went[pb + e] = 0;
+    __syncthreads();
+    if (kfid < 0) { if (tid == 0) { hdr[0] = 1; hdr[1] = -1; hdr[2] = hdr[3] = hdr[4] = 0; hdr[5] = minc; hdr[6] = 0; } return; }
+    const int r0 = kfid % R;
+    {   // nb_3d of the key-frame and update_frame_covisibility!'s counts (map_manager.jl:302-340)
+        const size_t sl = ((size_t)s * R + r0) * cap;
+        const int n0 = min(V.kn[s * R + r0], cap);
+        int nb3 = 0;
+        for (int i = tid; i < n0; i += 256) {
+            if (!V.klive[sl + i]) continue;
+            const int64_t id = V.kid[sl + i];
+            const size_t pe = pb + kfm_entry(id, mcap);
+            if (!kfm_valid(V, pe, id)) continue;
+            nb3 += (V.pflags[pe] & KFM_3D) != 0;
+            unsigned long long m = V.pmask[pe] & ~(1ull << r0);
+            while (m) { const int b = __ffsll((long long)m) - 1; m &= m - 1; if (b < R && s_tag[b]) atomicAdd(&s_cov[b], 1); }
+        }
+        if (nb3) atomicAdd(&s_nb3, nb3);
+    }
+    __syncthreads();
+    const int nb3 = s_nb3;
+    if (nb3 < minc) { if (tid == 0) { hdr[0] = 1; hdr[1] = kfid; hdr[2] = hdr[3] = hdr[4] = 0; hdr[5] = minc; hdr[6] = 0; } return; }
+    if (tid == 0) {
+        s_cov[r0] = nb3;
+        unsigned long long used = 0;
+        int ncl = 0;
+        for (int k = 0; k < N_COVISIBLE; k++) {                  // sorted(cov, reverse=True)[:5]
+            int best = -1;
+            for (int b = 0; b < R; b++) if (s_tag[b] && !(used >> b & 1) && (b == r0 || s_cov[b] > 0) && (best < 0 || s_tag[b] > s_tag[best])) best = b;
+            if (best < 0) break;
+            used |= 1ull << best; s_cl[ncl++] = best;
+        }
+        s_ncl = ncl; s_covmask = used;
+        int nv = 0;                                              // observers are walked in ascending key-frame id
+        for (int b = 0; b < R; b++) if (s_tag[b]) {
+            int rank = 0;
+            for (int c = 0; c < R; c++) rank += s_tag[c] && s_tag[c] < s_tag[b];
+            s_rank[b] = rank; s_asc[rank] = b; nv++;
+        }
+        s_nv = nv;
+    }
+    __syncthreads();
+    const int ncl = s_ncl, nv = s_nv;
+    for (int c = 0; c < ncl; c++) {
+        const int rc = s_cl[c], score = s_cov[rc];
+        if (score == 0) continue;                                                        // (every branch here is uniform over the workgroup)
+        if (s_order[rc] == 0 && (score < minc || s_tag[rc] == 1)) continue;              // low score or key-frame 0, and not yet a pose of the window: constant, not walked
+        const size_t sl = ((size_t)s * R + rc) * cap;
+        const int n = min(V.kn[s * R + rc], cap);
+        for (int c0 = 0; c0 < n; c0 += 256) {
+            const int i = c0 + tid;
+            bool acc = false;
+            int cnt = 0;
+            unsigned long long wm = 0;
+            int64_t id = 0;
+            size_t pe = 0;
+            if (i < n && V.klive[sl + i]) {
+                id = V.kid[sl + i]; pe = pb + kfm_entry(id, mcap);
+                const uint8_t fl = kfm_valid(V, pe, id) ? V.pflags[pe] : 0;
+                if ((fl & KFM_3D) && V.went[pe] == 0) {                                  // ids_3d, not yet processed (one thread per entry: ids are unique in a slab)
+                    const unsigned long long m = V.pmask[pe];
+                    if (__popcll(m) < 2 && !(fl & KFM_OBS)) {                            // is_bad! (map_point.jl:155-161) demotes the point
+                        V.pflags[pe] = fl & (uint8_t)~KFM_3D; V.went[pe] = -1;
+                        V.wpid[pb + mcap - 1 - atomicAdd(&s_nbad, 1)] = id;
+                    } else {
+                        acc = true;
+                        unsigned long long mm = m;
+                        while (mm) {                                                     // an observer whose key-frame or pixel is gone loses the point (remove_obs)
+                            const int b = __ffsll((long long)mm) - 1; mm &= mm - 1;
+                            if (b < R && s_tag[b] && kfm_find_live(V, s, b, id) >= 0) { wm |= 1ull << b; cnt++; }
+                        }
+                        if (wm != m) V.pmask[pe] = wm;
+                    }
+                }
+            }
+            const int pos = ordered_slot(acc, s_w, &s_base);
+            const int off = kfm_scan(cnt, s_w, &s_obase);
+            if (acc) {
+                V.went[pe] = pos + 1; V.wpid[pb + pos] = id; V.wpmask[pb + pos] = wm; V.wpoff[pb + pos] = off;
+                int j = 0;
+                for (int k = 0; k < nv; k++) { const int b = s_asc[k]; if (wm >> b & 1) { if (s_order[b] == 0) atomicMin(&s_first[b], off + j); j++; } }
+            }
+        }
+        __syncthreads();
+        if (tid == 0)                                            // dense 1-based pose ids in first-encounter order
+            for (;;) {
+                int best = -1;
+                for (int b = 0; b < R; b++) if (s_order[b] == 0 && s_first[b] != INT_MAX && (best < 0 || s_first[b] < s_first[best])) best = b;
+                if (best < 0) break;
+                s_order[best] = ++s_P; s_first[best] = INT_MAX;
+            }
+        __syncthreads();
+    }
+    if (tid < R) {
+        const int b = tid;
+        V.wtag[s * R + b] = s_tag[b]; V.worder[s * R + b] = s_order[b]; V.wrank[s * R + b] = s_rank[b];
+        V.wconst[s * R + b] = s_tag[b] == 1 || !(s_covmask >> b & 1) || s_cov[b] < minc;
+    }
+    if (tid == 0) {
+        V.wcov[s] = s_covmask;
+        hdr[0] = s_obase > 0 ? 0 : 1; hdr[1] = kfid; hdr[2] = s_P; hdr[3] = s_base; hdr[4] = s_obase; hdr[5] = minc; hdr[6] = s_nbad;
+    }
+}
+
+// the caller's arrays on the device, windows back to back (slam_local_ba_batch's layout + the bookkeeping)
+struct KfmOut { double *theta; uint8_t *tconst; double *px; int64_t *pose_ids, *point_ids, *poses_remap, *points_remap, *obs_kf, *obs_kp; uint8_t *incov; };
+struct KfmWin { int s, pose0, point0, obs0; long long theta0; };          // a window's stream and where its arrays start
+// the ascending walk of a stream's slots as the gather saw them: s_asc[rank] = slot; returns their number
+__device__ __forceinline__ int kfm_window_slots(const KfmapView &V, int s, int *s_asc)
+{
+    __shared__ int s_n;
+    if (threadIdx.x == 0) s_n = 0;
+    __syncthreads();
+    if ((int)threadIdx.x < V.R && V.wtag[s * V.R + threadIdx.x]) { s_asc[V.wrank[s * V.R + threadIdx.x]] = threadIdx.x; atomicAdd(&s_n, 1); }
+    __syncthreads();
+    return s_n;
+}
+// Emit: point-parallel (grid.x chunks of 256 points, grid.y = window); the poses are written by the first chunk
+__global__ __launch_bounds__(256) void k_kfm_emit(KfmapView V, const KfmWin *wins, KfmOut Q)
+{
+    __shared__ int s_asc[64];
+    const KfmWin W = wins[blockIdx.y];
+    const int s = W.s, R = V.R, j = blockIdx.x * 256 + threadIdx.x;
+    const int *hdr = V.whdr + KFM_HDR * (size_t)s;
+    const int P = hdr[2], M = hdr[3];
+    const int nv = kfm_window_slots(V, s, s_asc);
+    if (blockIdx.x == 0 && (int)threadIdx.x < R) {
+        const int b = threadIdx.x, o = V.worder[s * R + b];
+        if (o > 0) {
+            for (int k = 0; k < 6; k++) Q.theta[W.theta0 + 6 * (o - 1) + k] = V.ktheta[6 * ((size_t)s * R + b) + k];
+            Q.tconst[W.pose0 + o - 1] = (uint8_t)V.wconst[s * R + b]; Q.poses_remap[W.pose0 + o - 1] = V.wtag[s * R + b] - 1;
+        }
+    }
+    if (j >= M) return;
+    const size_t pb = (size_t)s * V.mcap;
+    const int64_t id = V.wpid[pb + j];
+    const size_t pe = pb + kfm_entry(id, V.mcap);
+    for (int k = 0; k < 3; k++) Q.theta[W.theta0 + 6 * P + 3 * (size_t)j + k] = V.pxyz[3 * pe + k];
+    Q.points_remap[W.point0 + j] = id;
+    const unsigned long long wm = V.wpmask[pb + j], cov = V.wcov[s];
+    size_t o = (size_t)W.obs0 + V.wpoff[pb + j];
+    for (int k = 0; k < nv; k++) {
+        const int b = s_asc[k];
+        if (!(wm >> b & 1)) continue;
+        const int i = max(kfm_find_live(V, s, b, id), 0);        // (found: the plan validated it in this stream order)
+        const size_t q = ((size_t)s * R + b) * V.cap + i;
+        Q.px[2 * o] = V.kupx[2 * q]; Q.px[2 * o + 1] = V.kupx[2 * q + 1];
+        Q.pose_ids[o] = V.worder[s * R + b]; Q.point_ids[o] = j + 1;
+        Q.obs_kf[o] = V.wtag[s * R + b] - 1; Q.obs_kp[o] = id; Q.incov[o] = cov >> b & 1;
+        o++;
+    }
+}
+
+// ---- update (tracked_ba.update): two kernels, because is_bad is evaluated after ALL of a window's removals ------------------------------------------------
+struct KfmUpd { int s; long long theta0, obs0; };
+// poses, and the removals of the outlier observations: one thread per point of the window walks the point's observations.  A thread touches its own
+// point's entry alone; the tombstone it writes is its own observation's: any thread order gives the same map.  Everything goes by key-frame and keypoint
+// id: a slot whose tag is no longer the gather's holds another key-frame now and is skipped, a point whose entry another id holds is skipped.
+__global__ __launch_bounds__(256) void k_kfm_upd_obs(KfmapView V, const KfmUpd *wins, const double *theta, const uint8_t *outl)
+{
+    __shared__ int s_asc[64];
+    const KfmUpd W = wins[blockIdx.y];
+    const int s = W.s, R = V.R, j = blockIdx.x * 256 + threadIdx.x;
+    const int *hdr = V.whdr + KFM_HDR * (size_t)s;
+    const int kfid = hdr[1], M = hdr[3];
+    const int nv = kfm_window_slots(V, s, s_asc);
+    if (blockIdx.x == 0 && (int)threadIdx.x < R) {
+        const int b = threadIdx.x, o = V.worder[s * R + b];
+        if (o > 0 && V.tag[s * R + b] == V.wtag[s * R + b])
+            for (int k = 0; k < 6; k++) V.ktheta[6 * ((size_t)s * R + b) + k] = theta[W.theta0 + 6 * (o - 1) + k];
+    }
+    if (j >= M) return;
+    const size_t pb = (size_t)s * V.mcap;
+    const int64_t id = V.wpid[pb + j];
+    const size_t pe = pb + kfm_entry(id, V.mcap);
+    const bool have = kfm_valid(V, pe, id);
+    const unsigned long long wm = V.wpmask[pb + j], cov = V.wcov[s];
+    unsigned long long mask = have ? V.pmask[pe] : 0;
+    uint8_t fl = have ? V.pflags[pe] : 0;
+    size_t o = (size_t)W.obs0 + V.wpoff[pb + j];
+    for (int k = 0; k < nv; k++) {
+        const int b = s_asc[k];
+        if (!(wm >> b & 1)) continue;
+        if (outl[o++]) {
+            if ((cov >> b & 1) && V.tag[s * R + b] == V.wtag[s * R + b]) {               // remove_mappoint_obs! (map_manager.jl:224-)
+                const int i = kfm_find_live(V, s, b, id);
+                if (i >= 0) V.klive[((size_t)s * R + b) * V.cap + i] = 0;
+                mask &= ~(1ull << b);
+            }
+            if (V.wtag[s * R + b] - 1 == kfid) fl = (fl & (uint8_t)~KFM_OBS) | KFM_GONE;     // remove_obs_from_current_frame!
+        }
+    }
+    if (have) { V.pmask[pe] = mask; V.pflags[pe] = fl; }
+}
+// remove_mappoint! (map_manager.jl:139-168): the point's observations become tombstones, the entry dies; an observed point's id has left the frame
+__device__ __forceinline__ void kfm_remove_point(const KfmapView &V, int s, size_t pe, int64_t id, uint8_t fl)
+{
+    unsigned long long m = V.pmask[pe];
+    while (m) {
+        const int b = __ffsll((long long)m) - 1; m &= m - 1;
+        if (b >= V.R || !V.tag[s * V.R + b]) continue;
+        const int i = kfm_find_live(V, s, b, id);
+        if (i >= 0) V.klive[((size_t)s * V.R + b) * V.cap + i] = 0;
+    }
+    V.pmask[pe] = 0; V.pflags[pe] = KFM_DEAD | ((fl & KFM_OBS) ? KFM_GONE : 0) | (fl & KFM_GONE);
+}
+// is_bad on every point of the window and on the gather's bad set: removed, or (window points) the refined position.  Thread t < M owns point t of the
+// window, thread t < M + nbad the bad point t - M: all different entries.
+__global__ __launch_bounds__(256) void k_kfm_upd_points(KfmapView V, const KfmUpd *wins, const double *theta)
+{
+    const KfmUpd W = wins[blockIdx.y];
+    const int s = W.s, t = blockIdx.x * 256 + threadIdx.x;
+    const int *hdr = V.whdr + KFM_HDR * (size_t)s;
+    const int P = hdr[2], M = hdr[3], nbad = hdr[6];
+    if (t >= M + nbad) return;
+    const size_t pb = (size_t)s * V.mcap;
+    const int64_t id = t < M ? V.wpid[pb + t] : V.wpid[pb + V.mcap - 1 - (t - M)];
+    const size_t pe = pb + kfm_entry(id, V.mcap);
+    if (!kfm_valid(V, pe, id)) return;
+    const uint8_t fl = V.pflags[pe];
+    const int nobs = __popcll(V.pmask[pe]);
+    if (nobs < 2 && !(fl & KFM_OBS) && ((fl & KFM_3D) || nobs == 0)) { kfm_remove_point(V, s, pe, id, fl); return; }
+    if (t < M) {
+        for (int k = 0; k < 3; k++) V.pxyz[3 * pe + k] = theta[W.theta0 + 6 * P + 3 * (size_t)t + k];
+        V.pflags[pe] = fl | KFM_BA;
+    }
+}
+// the live lists follow: an id that has left the frame is flagged for the compaction, a 3-D keypoint whose point the window kept takes its position
+__global__ __launch_bounds__(256) void k_kfm_upd_list(KfmapView V, KpsetView K, const KfmUpd *wins, uint8_t *flags)
+{
+    const int s = wins[blockIdx.y].s, i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= K.count[s]) return;
+    const size_t q = (size_t)s * K.cap + i, pb = (size_t)s * V.mcap;
+    const int64_t id = K.id[q];
+    const size_t pe = pb + kfm_entry(id, V.mcap);
+    if (V.ptag[pe] != (unsigned long long)id + 1ull) return;
+    const uint8_t fl = V.pflags[pe];
+    if (fl & KFM_GONE) { flags[q] = 1; return; }
+    const int w = V.went[pe];
+    if (!(fl & KFM_DEAD) && K.is3d[q] && w > 0 && V.wpid[pb + w - 1] == id) for (int k = 0; k < 3; k++) K.xyz[3 * q + k] = V.pxyz[3 * pe + k];
+}
+
+// Every region of the map's one allocation, each named once (kfmap.hpp has the formula): without a block for the total, with it to bind the pointers
+static size_t kfmap_regions(slam_kfmap *km, char *base)
+{
+    Layout Lo;
+    auto region = [&](auto *&p, size_t bytes) { const size_t at = Lo.take(bytes); if (base) p = (std::remove_reference_t<decltype(p)>)(base + at); };
+    KfmapView &v = km->v;
+    const size_t S = v.S, sr = S * v.R, n = sr * v.cap, m = S * v.mcap;
+    region(v.tag, sr * 4); region(v.kn, sr * 4); region(v.ktheta, sr * 48); region(v.kid, n * 8); region(v.kupx, n * 16); region(v.klive, n); region(v.kfresh, S * v.cap);
+    region(v.ptag, m * 8); region(v.pxyz, m * 24); region(v.pmask, m * 8); region(v.pflags, m);
+    region(v.cur, S * 4);
+    region(v.whdr, S * KFM_HDR * 4); region(v.wtag, sr * 4); region(v.worder, sr * 4); region(v.wrank, sr * 4); region(v.wconst, sr * 4); region(v.wcov, S * 8);
+    region(v.wpid, m * 8); region(v.wpmask, m * 8); region(v.wpoff, m * 4); region(v.went, m * 4);
+    return Lo.size();
+}
+// the streams the gather acts on (those of the last add_keyframe), ascending; returns their number
+static int kfmap_streams(const slam_kfmap *km, int *list)
+{
+    int n = 0;
+    for (int s = 0; s < km->v.S; s++) if (km->n_sel == KPSEL_ALL || km->sel_host[s]) list[n++] = s;
+    return n;
+}
+
+extern "C" {
+
+int slam_kfmap_destroy(slam_kfmap *km);
+
+int slam_kfmap_create(slam_ctx *ctx, int S, int cap, int R, int mcap, slam_kfmap **out)
+{
+    ARG_TRY(ctx, ctx != nullptr && out != nullptr && S >= 1 && S <= 128 && cap >= 1 && R >= 2 && R <= KFM_MAX_R && mcap >= 1 && mcap <= (1 << 22) &&
+                     (size_t)S * R * cap < (1u << 30) && (size_t)S * mcap < (1u << 30));
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    slam_kfmap *km = new slam_kfmap();
+    km->device = ctx->device; km->v.S = S; km->v.cap = cap; km->v.R = R; km->v.mcap = mcap;
+    km->bytes = kfmap_regions(km, nullptr);
+    hipError_t e = hipMalloc((void **)&km->base, km->bytes);
+    if (e == hipSuccess) e = hipMemsetAsync(km->base, 0, km->bytes, ctx->stream);
+    if (e == hipSuccess) e = slam_stream_wait(ctx->stream);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&km->pin_ev, hipEventDisableTiming);
+    if (e != hipSuccess) { slam_kfmap_destroy(km); return slam_fail(ctx, SLAM_ERR_HIP, "slam_kfmap_create: %s", hipGetErrorString(e)); }
+    kfmap_regions(km, km->base);
+    *out = km;
+    return SLAM_OK;
+}
+
+int slam_kfmap_destroy(slam_kfmap *km)
+{
+    if (!km) return SLAM_OK;
+    (void)hipSetDevice(km->device);
+    (void)hipDeviceSynchronize();
+    if (km->base) (void)hipFree(km->base);
+    if (km->pin) (void)hipHostFree(km->pin);
+    if (km->pin_ev) (void)hipEventDestroy(km->pin_ev);
+    delete km;
+    return SLAM_OK;
+}
+
+int slam_kfmap_add_keyframe(slam_ctx *ctx, slam_kfmap *km, slam_kpset *ks, const double *params)
+{
+    ARG_TRY(ctx, ctx != nullptr && km != nullptr && ks != nullptr && params != nullptr && ks->S == km->v.S && ks->v.cap <= km->v.cap);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    km->n_sel = ks->n_sel; memcpy(km->sel_host, ks->sel_host, sizeof km->sel_host);
+    if (kpset_none_selected(ks)) return SLAM_OK;
+    const double *par;
+    const int rc = kpset_stage_params(ctx, ks, params, (size_t)ks->S * KP_PAR, &par);
+    if (rc) return rc;
+    const int *sel = kpset_sel_table(ks), ns = kpset_sel_streams(ks);
+    const KfmapView &V = km->v;
+    const dim3 gl((ks->v.cap + 255) / 256, ns), gs((V.cap + 255) / 256, ns), gm((V.mcap + 255) / 256, ns);
+    { ProfScope span(ctx, "kfmap_add");
+      hipLaunchKernelGGL(k_kfm_forget, gs, dim3(256), 0, ctx->stream, V, (const int *)ks->v.kfcount, sel);
+      hipLaunchKernelGGL(k_kfm_clear_observed, gm, dim3(256), 0, ctx->stream, V, (const int *)ks->v.kfcount, sel);
+      hipLaunchKernelGGL(k_kfm_claim, gl, dim3(256), 0, ctx->stream, V, ks->v, sel);
+      hipLaunchKernelGGL(k_kfm_record, gl, dim3(256), 0, ctx->stream, V, ks->v, par, sel); }
+    HIP_TRY(ctx, hipGetLastError());
+    return SLAM_OK;
+}
+
+int slam_kfmap_ba_gather(slam_ctx *ctx, slam_kfmap *km, const int32_t *min_cov_score, const slam_kfmap_windows *out, int32_t *n_windows)
+{
+    ARG_TRY(ctx, ctx != nullptr && km != nullptr && min_cov_score != nullptr && out != nullptr && n_windows != nullptr && out->status && out->win_stream &&
+                     out->Pn && out->Mn && out->On && out->theta && out->theta_const && out->pixels_yx && out->pose_ids && out->point_ids &&
+                     out->cap_windows >= 0 && out->cap_poses >= 0 && out->cap_points >= 0 && out->cap_obs >= 0);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const KfmapView &V = km->v;
+    const int S = V.S;
+    int list[128];
+    const int ns = kfmap_streams(km, list);
+    *n_windows = 0;
+    for (int s = 0; s < S; s++) { out->status[s] = 3; }
+    for (int k = 0; k < ns; k++) km->pend[list[k]].valid = 0;
+    if (ns == 0) return SLAM_OK;
+    // count pass: table + thresholds up, the plan, the headers back (the first of the call's two waits)
+    Layout D;
+    const auto o_sel = D.take<int>(S), o_minc = D.take<int>(S); const size_t in_b = D.size();
+    char *scr, *h;
+    int rc = slam_scratch(ctx, D.size(), (void **)&scr);
+    if (rc) return rc;
+    rc = slam_pinned(ctx, std::max<size_t>(D.size(), (size_t)S * KFM_HDR * 4), (void **)&h);
+    if (rc) return rc;
+    memcpy(o_sel.at(h), list, (size_t)ns * 4); memcpy(o_minc.at(h), min_cov_score, (size_t)S * 4);
+    HIP_TRY(ctx, hipMemcpyAsync(scr, h, in_b, hipMemcpyHostToDevice, ctx->stream));
+    { ProfScope span(ctx, "kfmap_gather_plan");
+      hipLaunchKernelGGL(k_kfm_plan, dim3(ns), dim3(256), 0, ctx->stream, V, (const int *)o_minc.at(scr), (const int *)o_sel.at(scr)); }
+    HIP_TRY(ctx, hipGetLastError());
+    rc = kpset_read_back(ctx, h, {{0, V.whdr, (size_t)S * KFM_HDR * 4, nullptr}});
+    if (rc) return rc;
+    // scan over the streams: where each window goes, which ones fit
+    std::vector<int> hdr((size_t)S * KFM_HDR);
+    memcpy(hdr.data(), h, hdr.size() * 4);
+    std::vector<KfmWin> wins;
+    long long nP = 0, nM = 0, nO = 0, nT = 0;
+    for (int k = 0; k < ns; k++) {
+        const int s = list[k], *hd = hdr.data() + (size_t)KFM_HDR * s, P = hd[2], M = hd[3], O = hd[4];
+        if (hd[0] != 0) { out->status[s] = 1; continue; }
+        if ((int)wins.size() + 1 > out->cap_windows || nP + P > out->cap_poses || nM + M > out->cap_points || nO + O > out->cap_obs) { out->status[s] = 2; continue; }
+        out->status[s] = 0;
+        const int w = (int)wins.size();
+        out->win_stream[w] = s; out->Pn[w] = P; out->Mn[w] = M; out->On[w] = O;
+        wins.push_back({s, (int)nP, (int)nM, (int)nO, nT});
+        km->pend[s] = {1, hd[1], P, M, O};
+        nP += P; nM += M; nO += O; nT += 6ll * P + 3ll * M;
+    }
+    const int nw = (int)wins.size();
+    *n_windows = nw;
+    if (nw == 0) return SLAM_OK;
+    // emit pass into one block laid out as the caller's arrays, then the call's one copy of results
+    Layout E;
+    const auto e_win = E.take<KfmWin>(nw);
+    const auto e_th = E.take<double>((size_t)nT), e_px = E.take<double>(2 * (size_t)nO);
+    const auto e_pi = E.take<int64_t>((size_t)nO), e_li = E.take<int64_t>((size_t)nO), e_ok = E.take<int64_t>((size_t)nO), e_op = E.take<int64_t>((size_t)nO);
+    const auto e_pr = E.take<int64_t>((size_t)nP), e_lr = E.take<int64_t>((size_t)nM);
+    const auto e_tc = E.take<uint8_t>((size_t)nP), e_ic = E.take<uint8_t>((size_t)nO);
+    rc = slam_scratch(ctx, E.size(), (void **)&scr);
+    if (rc) return rc;
+    rc = slam_pinned(ctx, E.size(), (void **)&h);
+    if (rc) return rc;
+    memcpy(e_win.at(h), wins.data(), e_win.bytes());
+    HIP_TRY(ctx, hipMemcpyAsync(e_win.at(scr), e_win.at(h), e_win.bytes(), hipMemcpyHostToDevice, ctx->stream));
+    int maxM = 1;
+    for (int w = 0; w < nw; w++) maxM = std::max(maxM, (int)out->Mn[w]);
+    const KfmOut Q = {e_th.at(scr), e_tc.at(scr), e_px.at(scr), e_pi.at(scr), e_li.at(scr), e_pr.at(scr), e_lr.at(scr), e_ok.at(scr), e_op.at(scr), e_ic.at(scr)};
+    { ProfScope span(ctx, "kfmap_gather_emit");
+      hipLaunchKernelGGL(k_kfm_emit, dim3((maxM + 255) / 256, nw), dim3(256), 0, ctx->stream, V, (const KfmWin *)e_win.at(scr), Q); }
+    HIP_TRY(ctx, hipGetLastError());
+    const size_t lo = e_th.off, len = E.size() - lo;
+    HIP_TRY(ctx, hipMemcpyAsync(h + lo, scr + lo, len, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, slam_stream_wait(ctx->stream));
+    auto give = [&](void *dst, const auto &r) { if (dst && r.count) memcpy(dst, r.at(h), r.bytes()); };
+    give(out->theta, e_th); give(out->theta_const, e_tc); give(out->pixels_yx, e_px); give(out->pose_ids, e_pi); give(out->point_ids, e_li);
+    give(out->poses_remap, e_pr); give(out->points_remap, e_lr); give(out->obs_kf, e_ok); give(out->obs_kp, e_op); give(out->obs_in_covmap, e_ic);
+    return SLAM_OK;
+}
+
+int slam_kfmap_ba_update(slam_ctx *ctx, slam_kfmap *km, slam_kpset *ks, int n_windows, const int32_t *win_stream, const double *theta, const uint8_t *outliers)
+{
+    ARG_TRY(ctx, ctx != nullptr && km != nullptr && n_windows >= 0 && n_windows <= km->v.S && (n_windows == 0 || (win_stream && theta && outliers)) &&
+                     (ks == nullptr || (ks->S == km->v.S && ks->v.cap <= km->v.cap)));
+    const KfmapView &V = km->v;
+    std::vector<KfmUpd> wins((size_t)n_windows);
+    long long nT = 0, nO = 0;
+    int maxM = 1;
+    uint8_t seen[128] = {};
+    for (int w = 0; w < n_windows; w++) {                        // every check before anything is enqueued
+        const int s = win_stream[w];
+        if (s < 0 || s >= V.S || seen[s] || !km->pend[s].valid)
+            return slam_fail(ctx, SLAM_ERR_ARG, "slam_kfmap_ba_update: window %d names stream %d, which has no pending window", w, s);
+        seen[s] = 1;
+        wins[w] = {s, nT, nO};
+        nT += 6ll * km->pend[s].P + 3ll * km->pend[s].M; nO += km->pend[s].O; maxM = std::max(maxM, km->pend[s].M);
+    }
+    if (n_windows == 0) return SLAM_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    Layout D;
+    const auto o_win = D.take<KfmUpd>(n_windows); const auto o_th = D.take<double>((size_t)nT); const auto o_ol = D.take<uint8_t>((size_t)nO);
+    HIP_TRY(ctx, hipEventSynchronize(km->pin_ev));               // the copy that last read the pinned block (an event never recorded is complete)
+    if (km->pin_bytes < D.size()) {
+        if (km->pin) (void)hipHostFree(km->pin);
+        km->pin = nullptr; km->pin_bytes = 0;
+        HIP_TRY(ctx, hipHostMalloc((void **)&km->pin, D.size() + D.size() / 4));
+        km->pin_bytes = D.size() + D.size() / 4;
+    }
+    char *scr, *h = km->pin;
+    int rc = slam_scratch(ctx, D.size(), (void **)&scr);
+    if (rc) return rc;
+    memcpy(o_win.at(h), wins.data(), o_win.bytes()); memcpy(o_th.at(h), theta, o_th.bytes()); memcpy(o_ol.at(h), outliers, o_ol.bytes());
+    HIP_TRY(ctx, hipMemcpyAsync(scr, h, D.size(), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(km->pin_ev, ctx->stream));
+    const KfmUpd *wd = o_win.at(scr);
+    uint8_t *flags = nullptr;
+    if (ks) {
+        rc = slam_scratch2(ctx, (size_t)ks->S * ks->v.cap, (void **)&flags);
+        if (rc) return rc;
+        HIP_TRY(ctx, hipMemsetAsync(flags, 0, (size_t)ks->S * ks->v.cap, ctx->stream));
+    }
+    { ProfScope span(ctx, "kfmap_update");
+      hipLaunchKernelGGL(k_kfm_upd_obs, dim3((maxM + 255) / 256, n_windows), dim3(256), 0, ctx->stream, V, wd, (const double *)o_th.at(scr), (const uint8_t *)o_ol.at(scr));
+      hipLaunchKernelGGL(k_kfm_upd_points, dim3((V.mcap + 255) / 256, n_windows), dim3(256), 0, ctx->stream, V, wd, (const double *)o_th.at(scr));
+      if (ks) hipLaunchKernelGGL(k_kfm_upd_list, dim3((ks->v.cap + 255) / 256, n_windows), dim3(256), 0, ctx->stream, V, ks->v, wd, flags); }
+    HIP_TRY(ctx, hipGetLastError());
+    for (int w = 0; w < n_windows; w++) km->pend[win_stream[w]].valid = 0;
+    if (ks) return kpset_compact(ctx, ks, 1, flags);             // (a stream without a flag keeps every slot where it is)
+    return SLAM_OK;
+}
+
+int slam_kfmap_download_keyframe(slam_ctx *ctx, slam_kfmap *km, int s, int kfid, double *theta, int64_t *ids, double *upx_yx, uint8_t *live, int cap_out, int *n_out)
+{
+    ARG_TRY(ctx, ctx != nullptr && km != nullptr && s >= 0 && s < km->v.S && kfid >= 0 && n_out != nullptr);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const KfmapView &V = km->v;
+    const size_t sr = (size_t)s * V.R + kfid % V.R;
+    int tn[2] = {0, 0};
+    HIP_TRY(ctx, hipMemcpyAsync(&tn[0], V.tag + sr, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(&tn[1], V.kn + sr, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, slam_stream_wait(ctx->stream));
+    if (tn[0] != kfid + 1) { *n_out = -1; return SLAM_OK; }      // not in the ring (never added, or forgotten)
+    const int n = tn[1];
+    *n_out = n;
+    if (n > cap_out) return slam_fail(ctx, SLAM_ERR_CAPACITY, "slam_kfmap_download_keyframe: %d observations but cap = %d", n, cap_out);
+    if (theta) HIP_TRY(ctx, hipMemcpyAsync(theta, V.ktheta + 6 * sr, 48, hipMemcpyDeviceToHost, ctx->stream));
+    if (n > 0 && ids) HIP_TRY(ctx, hipMemcpyAsync(ids, V.kid + sr * V.cap, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (n > 0 && upx_yx) HIP_TRY(ctx, hipMemcpyAsync(upx_yx, V.kupx + 2 * sr * V.cap, (size_t)n * 16, hipMemcpyDeviceToHost, ctx->stream));
+    if (n > 0 && live) HIP_TRY(ctx, hipMemcpyAsync(live, V.klive + sr * V.cap, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, slam_stream_wait(ctx->stream));
+    return SLAM_OK;
+}
+
+int slam_kfmap_download_points(slam_ctx *ctx, slam_kfmap *km, int s, int64_t *ids, double *xyz, uint8_t *flags, int32_t *obs_off, int32_t *obs_kf,
+                               int cap_out, int cap_obs, int *n_out)
+{
+    ARG_TRY(ctx, ctx != nullptr && km != nullptr && s >= 0 && s < km->v.S && n_out != nullptr);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const KfmapView &V = km->v;
+    const size_t m = V.mcap, pb = (size_t)s * m;
+    std::vector<unsigned long long> tag(m), mask(m);
+    std::vector<double> pos(3 * m);
+    std::vector<uint8_t> fl(m);
+    std::vector<int> ring(V.R);
+    HIP_TRY(ctx, hipMemcpyAsync(tag.data(), V.ptag + pb, m * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(mask.data(), V.pmask + pb, m * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(pos.data(), V.pxyz + 3 * pb, m * 24, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(fl.data(), V.pflags + pb, m, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ring.data(), V.tag + (size_t)s * V.R, (size_t)V.R * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, slam_stream_wait(ctx->stream));
+    std::vector<std::pair<int64_t, size_t>> live;
+    size_t nobs = 0;
+    for (size_t e = 0; e < m; e++) if (tag[e] && !(fl[e] & KFM_DEAD)) { live.push_back({(int64_t)(tag[e] - 1), e}); nobs += __builtin_popcountll(mask[e]); }
+    std::sort(live.begin(), live.end());
+    *n_out = (int)live.size();
+    if ((int)live.size() > cap_out || (obs_kf && nobs > (size_t)cap_obs))
+        return slam_fail(ctx, SLAM_ERR_CAPACITY, "slam_kfmap_download_points: %zu points with %zu observers, caps %d and %d", live.size(), nobs, cap_out, cap_obs);
+    int at = 0;
+    for (size_t k = 0; k < live.size(); k++) {
+        const size_t e = live[k].second;
+        if (ids) ids[k] = live[k].first;
+        if (xyz) for (int c = 0; c < 3; c++) xyz[3 * k + c] = pos[3 * e + c];
+        if (flags) flags[k] = fl[e];
+        if (obs_off) obs_off[k] = at;
+        std::vector<int> kf;
+        for (int b = 0; b < V.R; b++) if ((mask[e] >> b & 1) && ring[b]) kf.push_back(ring[b] - 1);
+        std::sort(kf.begin(), kf.end());
+        for (int o : kf) { if (obs_kf) obs_kf[at] = o; at++; }
+    }
+    if (obs_off) obs_off[live.size()] = at;
+    return SLAM_OK;
+}
+
+int slam_kfmap_reset(slam_ctx *ctx, slam_kfmap *km, int s)
+{
+    ARG_TRY(ctx, ctx != nullptr && km != nullptr && s >= 0 && s < km->v.S);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const KfmapView &V = km->v;
+    // an empty ring, an empty table, no key-frame yet, no window: the tags alone decide what the rest means
+    HIP_TRY(ctx, hipMemsetAsync(V.tag + (size_t)s * V.R, 0, (size_t)V.R * 4, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(V.ptag + (size_t)s * V.mcap, 0, (size_t)V.mcap * 8, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(V.pflags + (size_t)s * V.mcap, 0, (size_t)V.mcap, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(V.pmask + (size_t)s * V.mcap, 0, (size_t)V.mcap * 8, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(V.cur + s, 0, 4, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(V.whdr + (size_t)s * KFM_HDR, 0, KFM_HDR * 4, ctx->stream));
+    km->pend[s].valid = 0;
+    return SLAM_OK;
+}
+
+}  // extern "C"

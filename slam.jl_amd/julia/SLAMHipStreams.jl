@@ -26,7 +26,8 @@ module SLAMHipStreams
 import ..SLAMHip: LIB, ctx, check
 
 export PyramidBatch, FrameRing, KeypointSet, upload!, update!, flow_match!, stereo_match!, remove!, detect!, detect_describe!, describe_batch, keyframe!, select!, selection,
-       triangulate!, triangulate_temporal!, compute_pose_5pt!, compute_pose!, frame_stats, keyframe_required, counts, download, stream_params
+       triangulate!, triangulate_temporal!, compute_pose_5pt!, compute_pose!, frame_stats, keyframe_required, counts, download, stream_params,
+       KeyframeMap, add_keyframe!, gather, download_keyframe, download_points, reset!
 
 const HIP = "libamdhip64"
 hipcheck(e::Cint, what) = e == 0 || error("$what: HIP error $e")
@@ -356,6 +357,68 @@ function finish!(job::BABatchJob)
     end
     job.status
 end
+
+# ---- the key-frame map of the lists (slam_kfmap_*, include/slamhip.h): _get_ba_parameters / _update_ba_parameters! (estimator.jl:143-306) for S
+# lock-stepped streams whose keypoints live in a KeypointSet.  add_keyframe! right after keyframe!; gather returns the windows of the newest key-frames
+# in slam_local_ba_batch's layout (pass the arrays straight on); update! takes θ and the outlier flags back, into the map and (k given) the live lists.
+# KfmapWindows mirrors slam_kfmap_windows field for field; the arrays it points to belong to the GatheredWindows that owns it.
+mutable struct KfmapWindows
+    cap_windows::Int32; cap_poses::Int32; cap_points::Int32; cap_obs::Int32
+    status::Ptr{Int32}; win_stream::Ptr{Int32}; Pn::Ptr{Int32}; Mn::Ptr{Int32}; On::Ptr{Int32}
+    theta::Ptr{Float64}; theta_const::Ptr{UInt8}; pixels_yx::Ptr{Float64}; pose_ids::Ptr{Int64}; point_ids::Ptr{Int64}
+    poses_remap::Ptr{Int64}; points_remap::Ptr{Int64}; obs_kf::Ptr{Int64}; obs_kp::Ptr{Int64}; obs_in_covmap::Ptr{UInt8}
+end
+mutable struct KeyframeMap
+    h::Ptr{Cvoid}; S::Int; cap::Int; R::Int; mcap::Int
+    function KeyframeMap(S, cap; R = 32, mcap = 16384)
+        r = Ref{Ptr{Cvoid}}(C_NULL)
+        check(ccall((:slam_kfmap_create, LIB[]), Cint, (Ptr{Cvoid}, Cint, Cint, Cint, Cint, Ref{Ptr{Cvoid}}), ctx(), S, cap, R, mcap, r))
+        m = new(r[], S, cap, R, mcap)
+        finalizer(x -> ccall((:slam_kfmap_destroy, LIB[]), Cint, (Ptr{Cvoid},), x.h), m)
+    end
+end
+# sp: S x 32 stream parameters (Tcw, camera, distortion); acts on the streams k has selected
+add_keyframe!(m::KeyframeMap, k::KeypointSet, sp::Matrix{Float64}) =
+    (check(ccall((:slam_kfmap_add_keyframe, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}), ctx(), m.h, k.h, sp)); m)
+struct GatheredWindows
+    n::Int; status::Vector{Int32}; win_stream::Vector{Int32}; Pn::Vector{Int32}; Mn::Vector{Int32}; On::Vector{Int32}
+    θ::Vector{Float64}; θconst::Vector{UInt8}; pixels::Vector{Float64}; poses_ids::Vector{Int64}; points_ids::Vector{Int64}
+    poses_remap::Vector{Int64}; points_remap::Vector{Int64}; obs_kf::Vector{Int64}; obs_kp::Vector{Int64}; obs_in_covmap::Vector{UInt8}
+end
+function gather(m::KeyframeMap, min_cov_score::Vector{Int32}; max_poses::Int = m.S * m.R, max_points::Int = m.S * min(m.mcap, 5 * m.cap), max_obs::Int = 8 * max_points)
+    S = m.S
+    g = GatheredWindows(0, zeros(Int32, S), zeros(Int32, S), zeros(Int32, S), zeros(Int32, S), zeros(Int32, S),
+                        zeros(6 * max_poses + 3 * max_points), zeros(UInt8, max_poses), zeros(2 * max_obs), zeros(Int64, max_obs), zeros(Int64, max_obs),
+                        zeros(Int64, max_poses), zeros(Int64, max_points), zeros(Int64, max_obs), zeros(Int64, max_obs), zeros(UInt8, max_obs))
+    n = Ref{Int32}(0)
+    GC.@preserve g min_cov_score begin
+        w = KfmapWindows(S, max_poses, max_points, max_obs, pointer(g.status), pointer(g.win_stream), pointer(g.Pn), pointer(g.Mn), pointer(g.On),
+                         pointer(g.θ), pointer(g.θconst), pointer(g.pixels), pointer(g.poses_ids), pointer(g.points_ids),
+                         pointer(g.poses_remap), pointer(g.points_remap), pointer(g.obs_kf), pointer(g.obs_kp), pointer(g.obs_in_covmap))
+        check(ccall((:slam_kfmap_ba_gather, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int32}, Ref{KfmapWindows}, Ref{Int32}), ctx(), m.h, min_cov_score, w, n))
+    end
+    GatheredWindows(Int(n[]), g.status, g.win_stream, g.Pn, g.Mn, g.On, g.θ, g.θconst, g.pixels, g.poses_ids, g.points_ids,
+                    g.poses_remap, g.points_remap, g.obs_kf, g.obs_kp, g.obs_in_covmap)
+end
+# θ / outliers: the arrays slam_local_ba_batch has written (windows back to back, in g.win_stream's order)
+function update!(m::KeyframeMap, g::GatheredWindows, θ::Vector{Float64}, outliers::Vector{UInt8}; k::Union{Nothing, KeypointSet} = nothing)
+    GC.@preserve g θ outliers check(ccall((:slam_kfmap_ba_update, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Int32}, Ptr{Float64}, Ptr{UInt8}),
+        ctx(), m.h, k === nothing ? C_NULL : k.h, g.n, g.win_stream, θ, outliers))
+    m
+end
+function download_keyframe(m::KeyframeMap, s::Integer, kfid::Integer)
+    θ = zeros(6); ids = zeros(Int64, m.cap); upx = zeros(2, m.cap); live = zeros(UInt8, m.cap); n = Ref{Cint}(0)
+    check(ccall((:slam_kfmap_download_keyframe, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cint, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{UInt8}, Cint, Ref{Cint}),
+                ctx(), m.h, s, kfid, θ, ids, upx, live, m.cap, n))
+    n[] < 0 ? nothing : (θ = θ, ids = ids[1:n[]], upx = upx[:, 1:n[]], live = live[1:n[]] .!= 0)
+end
+function download_points(m::KeyframeMap, s::Integer)
+    ids = zeros(Int64, m.mcap); xyz = zeros(3, m.mcap); flags = zeros(UInt8, m.mcap); off = zeros(Int32, m.mcap + 1); okf = zeros(Int32, m.mcap * m.R); n = Ref{Cint}(0)
+    check(ccall((:slam_kfmap_download_points, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Int64}, Ptr{Float64}, Ptr{UInt8}, Ptr{Int32}, Ptr{Int32}, Cint, Cint, Ref{Cint}),
+                ctx(), m.h, s, ids, xyz, flags, off, okf, m.mcap, m.mcap * m.R, n))
+    (ids = ids[1:n[]], xyz = xyz[:, 1:n[]], flags = flags[1:n[]], observers = [okf[off[j] + 1:off[j + 1]] for j in 1:n[]])
+end
+reset!(m::KeyframeMap, s::Integer) = (check(ccall((:slam_kfmap_reset, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint), ctx(), m.h, s)); m)
 
 # ---- one live stream, one call per frame (slam_frontend_*, include/slamhip.h): what run!()'s front-end task does per frame
 # (front_end.jl:58-113, :454-470) and, at a key-frame, create_keyframe! + the mapper's stereo step (map_manager.jl:98-113, mapper.jl:51-66, :142-183),

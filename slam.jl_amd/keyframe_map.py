@@ -1,0 +1,141 @@
+"""The key-frame map of S lock-stepped streams in HBM (slam_kfmap, include/slamhip.h): what local_bundle_adjustment!
+(src/estimator.jl:317-347) reads and writes of the map manager -- _get_ba_parameters (:143-266), _update_ba_parameters! (:268-306) -- for
+streams whose keypoints live in a KeypointSet.  add_keyframe() fills it from the lists, gather() returns the windows of the newest
+key-frames as LocalBACaches for bundle_adjustment_batch_, update() takes the solution back into the map and the live lists."""
+import ctypes as C
+import time
+from dataclasses import dataclass
+
+import numpy as np
+
+from . import _lib as L
+from .bundle_adjustment import LocalBACache
+from .keypoint_set import KP_PAR
+
+N_COVISIBLE = 5                         # local_bundle_adjustment!: up to 5 latest covisible key-frames
+
+
+class _Windows(C.Structure):
+    """slam_kfmap_windows"""
+    _fields_ = [("cap_windows", C.c_int32), ("cap_poses", C.c_int32), ("cap_points", C.c_int32), ("cap_obs", C.c_int32),
+                ("status", L.i32p), ("win_stream", L.i32p), ("Pn", L.i32p), ("Mn", L.i32p), ("On", L.i32p),
+                ("theta", L.f64p), ("theta_const", L.u8p), ("pixels_yx", L.f64p), ("pose_ids", L.i64p), ("point_ids", L.i64p),
+                ("poses_remap", L.i64p), ("points_remap", L.i64p), ("obs_kf", L.i64p), ("obs_kp", L.i64p), ("obs_in_covmap", L.u8p)]
+
+
+@dataclass
+class Window:
+    """One gathered window: the solver's arrays (cache) and the bookkeeping that names them -- poses_remap / points_remap: the key-frame /
+    keypoint id of a dense id; per observation its key-frame, keypoint and whether the key-frame is in the covisibility map."""
+    stream: int
+    cache: LocalBACache
+    poses_remap: np.ndarray
+    points_remap: np.ndarray
+    obs_kf: np.ndarray
+    obs_kp: np.ndarray
+    obs_in_covmap: np.ndarray
+
+
+class KeyframeMap:
+    def __init__(self, S, cap, R=32, mcap=16384, ctx=None):
+        self.ctx = ctx or L.default_context()
+        self.S, self.cap, self.R, self.mcap = S, cap, R, mcap
+        h = C.c_void_p()
+        self.ctx.check(self.ctx.lib.slam_kfmap_create(self.ctx.h, S, cap, R, mcap, C.byref(h)))
+        self.h = h
+        self.last_gather_ms = 0.0
+        self._bufs = None
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.ctx.lib.slam_kfmap_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add_keyframe(self, ks, sp, ctx=None):
+        """Record the key-frame ks.keyframe() has just made, for the streams ks has selected.  sp: stream_params(...) with Tcw and the camera /
+        distortion entries filled.  Enqueue-only."""
+        c = ctx or self.ctx
+        sp = np.ascontiguousarray(sp, dtype=np.float64).reshape(self.S, KP_PAR)
+        c.check(c.lib.slam_kfmap_add_keyframe(c.h, self.h, ks.h, L.ptr(sp)))
+
+    def gather(self, min_cov_score, max_poses=None, max_points=None, max_obs=None, max_windows=None, ctx=None):
+        """-> (windows, status): the Window of every stream of the last add_keyframe that has one, ascending by stream, and the (S,) status
+        codes (0 window, 1 none, 2 does not fit the capacities, 3 not selected).  min_cov_score: one threshold or S of them; max_*: the total
+        capacities of the arrays the windows are gathered into (default: what S windows can at most need).  Synchronous."""
+        c = ctx or self.ctx
+        S = self.S
+        minc = np.ascontiguousarray(np.broadcast_to(np.asarray(min_cov_score, dtype=np.int32), (S,)))
+        nW = S if max_windows is None else int(max_windows)
+        nP = S * self.R if max_poses is None else int(max_poses)
+        nM = S * min(self.mcap, N_COVISIBLE * self.cap) if max_points is None else int(max_points)
+        nO = min(nM * self.R, 4_000_000) if max_obs is None else int(max_obs)
+        if self._bufs is None or self._bufs[0] != (nW, nP, nM, nO):     # the arrays the library fills: made once per capacity, reused by every gather
+            i32, i64 = (lambda n: np.zeros(max(n, 1), dtype=np.int32)), (lambda n: np.zeros(max(n, 1), dtype=np.int64))
+            self._bufs = ((nW, nP, nM, nO), (i32(S), i32(nW), i32(nW), i32(nW), i32(nW), np.zeros(max(6 * nP + 3 * nM, 1)), np.zeros(max(nP, 1), dtype=np.uint8),
+                                            np.zeros(max(2 * nO, 1)), i64(nO), i64(nO), i64(nP), i64(nM), i64(nO), i64(nO), np.zeros(max(nO, 1), dtype=np.uint8)))
+        status, ws, Pn, Mn, On, theta, tc, px, pi, li, pr, lr, okf, okp, oc = self._bufs[1]
+        out = _Windows(nW, nP, nM, nO, L.ptr(status, L.i32p), L.ptr(ws, L.i32p), L.ptr(Pn, L.i32p), L.ptr(Mn, L.i32p), L.ptr(On, L.i32p),
+                       L.ptr(theta), L.ptr(tc, L.u8p), L.ptr(px), L.ptr(pi, L.i64p), L.ptr(li, L.i64p), L.ptr(pr, L.i64p), L.ptr(lr, L.i64p),
+                       L.ptr(okf, L.i64p), L.ptr(okp, L.i64p), L.ptr(oc, L.u8p))
+        n = C.c_int32(0)
+        t0 = time.perf_counter()
+        c.check(c.lib.slam_kfmap_ba_gather(c.h, self.h, L.ptr(minc, L.i32p), C.byref(out), C.byref(n)))
+        self.last_gather_ms = (time.perf_counter() - t0) * 1e3   # wall time of the synchronous call itself (scripts/probes/prof_kfmap.py)
+        wins, t0, p0, m0, o0 = [], 0, 0, 0, 0
+        for w in range(n.value):
+            P, M, O = int(Pn[w]), int(Mn[w]), int(On[w])
+            cache = LocalBACache(theta[t0:t0 + 6 * P + 3 * M].copy(), tc[p0:p0 + P].copy(), px[2 * o0:2 * (o0 + O)].reshape(O, 2).copy(),
+                                 pi[o0:o0 + O].copy(), li[o0:o0 + O].copy())
+            wins.append(Window(int(ws[w]), cache, pr[p0:p0 + P].copy(), lr[m0:m0 + M].copy(), okf[o0:o0 + O].copy(), okp[o0:o0 + O].copy(),
+                               oc[o0:o0 + O].astype(bool)))
+            t0 += 6 * P + 3 * M; p0 += P; m0 += M; o0 += O
+        return wins, status.copy()
+
+    def update(self, windows, thetas=None, outliers=None, ks=None, ctx=None):
+        """_update_ba_parameters! for the pending windows of the listed streams.  windows: Windows (or stream indices); thetas / outliers: one
+        array per window, default the windows' caches as bundle_adjustment_batch_ left them.  ks: the KeypointSet whose live lists follow
+        (refined positions in, removed ids out).  Enqueue-only."""
+        c = ctx or self.ctx
+        streams = np.ascontiguousarray([w.stream if isinstance(w, Window) else int(w) for w in windows], dtype=np.int32)
+        if thetas is None:
+            thetas = [w.cache.theta for w in windows]
+        if outliers is None:
+            outliers = [w.cache.outliers for w in windows]
+        th = np.ascontiguousarray(np.concatenate([np.asarray(t, dtype=np.float64).reshape(-1) for t in thetas] + [np.zeros(1)]))
+        ol = np.ascontiguousarray(np.concatenate([np.asarray(o).astype(np.uint8).reshape(-1) for o in outliers] + [np.zeros(1, dtype=np.uint8)]))
+        c.check(c.lib.slam_kfmap_ba_update(c.h, self.h, ks.h if ks is not None else None, len(streams), L.ptr(streams, L.i32p), L.ptr(th), L.ptr(ol, L.u8p)))
+
+    def download_keyframe(self, s, kfid, ctx=None):
+        """dict(theta, ids, upx, live) of key-frame kfid of stream s, or None when the ring does not hold it"""
+        c = ctx or self.ctx
+        theta = np.zeros(6); ids = np.zeros(self.cap, dtype=np.int64); upx = np.zeros((self.cap, 2)); live = np.zeros(self.cap, dtype=np.uint8)
+        n = C.c_int(0)
+        c.check(c.lib.slam_kfmap_download_keyframe(c.h, self.h, int(s), int(kfid), L.ptr(theta), L.ptr(ids, L.i64p), L.ptr(upx), L.ptr(live, L.u8p), self.cap, C.byref(n)))
+        if n.value < 0:
+            return None
+        return dict(theta=theta, ids=ids[:n.value].copy(), upx=upx[:n.value].copy(), live=live[:n.value].astype(bool))
+
+    def download_points(self, s, ctx=None):
+        """dict(ids, xyz, is_3d, observed, ba, gone, observers) of stream s's map points in id order; observers: a tuple of key-frame ids per point"""
+        c = ctx or self.ctx
+        m = self.mcap
+        ids = np.zeros(m, dtype=np.int64); xyz = np.zeros((m, 3)); fl = np.zeros(m, dtype=np.uint8)
+        off = np.zeros(m + 1, dtype=np.int32); okf = np.zeros(m * self.R, dtype=np.int32)
+        n = C.c_int(0)
+        c.check(c.lib.slam_kfmap_download_points(c.h, self.h, int(s), L.ptr(ids, L.i64p), L.ptr(xyz), L.ptr(fl, L.u8p), L.ptr(off, L.i32p),
+                                                 L.ptr(okf, L.i32p), m, m * self.R, C.byref(n)))
+        k = n.value
+        f = fl[:k]
+        return dict(ids=ids[:k].copy(), xyz=xyz[:k].copy(), is_3d=(f & 1) != 0, observed=(f & 2) != 0, ba=(f & 4) != 0, gone=(f & 8) != 0,
+                    observers=[tuple(int(v) for v in okf[off[j]:off[j + 1]]) for j in range(k)])
+
+    def reset(self, s, ctx=None):
+        c = ctx or self.ctx
+        c.check(c.lib.slam_kfmap_reset(c.h, self.h, int(s)))
+
