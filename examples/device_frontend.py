@@ -9,9 +9,10 @@ lock-stepped stereo streams with every keypoint list resident in HBM -- the call
     key-frames: detect -> keyframe -> right frames -> stereo_match -> triangulate -> triangulate_temporal   (create_keyframe!, mapper)
     --adaptive-keyframes: KeypointSet.frame_stats + keyframe_required after the pose                 (check_new_kf_required)
     --local-ba: after every key-frame step KeyframeMap.add_keyframe -> gather -> bundle_adjustment_batch_ -> update(ks)   (local_bundle_adjustment!)
+    --map-filtering: after update(ks) KeyframeMap.filter drops the redundant key-frames of the ring                          (map_filtering!)
 
 No host keypoint arrays anywhere; per frame the host receives S poses, S status words and S list lengths.  It is an
-array-level driver, not SLAM (no map filtering, no relocalisation): what it shows is that the seams compose -- on a rigid synthetic
+array-level driver, not SLAM (no local-map matching, no relocalisation): what it shows is that the seams compose -- on a rigid synthetic
 scene the poses it returns are the camera motion.
 
 With --local-ba the estimator's step runs too, on a key-frame map that lives in HBM beside the lists (slam_kfmap): every key-frame is recorded
@@ -19,13 +20,17 @@ from the lists, the windows of the streams' newest key-frames are gathered in sl
 solution goes back into the map AND the live lists -- the front end tracks refined landmarks from the next frame on.  Under
 --adaptive-keyframes / --per-stream-keyframes the map calls run under the same selection as the key-frame seams.
 
+With --map-filtering (requires --local-ba) the other half of the estimator's loop runs as well: after the update, map_filtering!
+(estimator.jl:358-406) removes from each stream's ring the covisible key-frames most of whose 3-D points more than four key-frames observe
+(Params.filtering_ratio), from key-frame --filter-from on (the reference's literal is 20).  A removed key-frame no longer enters later windows.
+
 Key-frames are taken every `kf_every`-th frame, or, with --adaptive-keyframes, where the reference's rule asks for one
 (front_end.jl:361-393 on the statistics of the lists, one S x 8 read-back per frame).  The streams are lock-stepped -- every launch is
 shared -- so --adaptive-keyframes alone takes a key-frame FOR ALL streams when ANY stream requires one.  --per-stream-keyframes lets every
 stream follow its own rule: the key-frame seams run under KeypointSet.selected(required), which restricts them to the streams that asked
 (slam_kpset_select), and the key-frame bookkeeping (last key-frame, its nb_3d_kpts, its pose, the observer ring, the key-frame id) is per stream.
 
-    python examples/device_frontend.py --frames 12 --streams 4 [--adaptive-keyframes | --per-stream-keyframes] [--local-ba]
+    python examples/device_frontend.py --frames 12 --streams 4 [--adaptive-keyframes | --per-stream-keyframes] [--local-ba [--map-filtering [--filter-from K]]]
 """
 import argparse
 import contextlib
@@ -40,7 +45,8 @@ import slam_jl_amd as slam  # noqa: E402
 from slam_jl_amd import synthetic as syn  # noqa: E402
 
 
-def run(lefts, rights, cam, baseline, kf_every=4, max_keypoints=300, seed=0, ctx=None, verbose=False, adaptive=False, probe=None, per_stream=False, local_ba=False):
+def run(lefts, rights, cam, baseline, kf_every=4, max_keypoints=300, seed=0, ctx=None, verbose=False, adaptive=False, probe=None, per_stream=False, local_ba=False,
+        map_filtering=False, filter_from=20, map_probe=None):
     """lefts / rights: per stream a list of float images in [0, 1] (H, W).  Returns per frame a dict with the S poses
     (world -> camera, world = the first frame's camera), status words, list lengths and the wall time.
     adaptive: frame 0 is a key-frame; after the pose of every later frame the lists' statistics (KeypointSet.frame_stats, flags = 1) go
@@ -52,14 +58,20 @@ def run(lefts, rights, cam, baseline, kf_every=4, max_keypoints=300, seed=0, ctx
     batch is still built for all S streams at such a frame: a batch build takes the whole batch.)
     local_ba: a KeyframeMap follows the key-frames; after the key-frame seams (same selection) the key-frame is added, the windows are gathered,
     solved by bundle_adjustment_batch_ and written back into the map and the lists.  Rows of key-frame steps carry `ba`: per solved window
-    (stream, P, M, O, outliers, ssr before, ssr after)."""
+    (stream, P, M, O, outliers, ssr before, ssr after).
+    map_filtering (needs local_ba): after the update KeyframeMap.filter(params.filtering_ratio, params.min_cov_score, first_kfid=filter_from) runs
+    for the same streams; those rows carry `removed`: per stream the key-frame ids it dropped.  map_probe(frame, stage, ...) is called around the
+    map calls of a key-frame step: ("lists", ks, kf_mask, Tcw) before add_keyframe, ("added", km) after it, ("solved", wins) after the solve and
+    before the update, ("filtered", km, removed) after the filter."""
+    if map_filtering and not local_ba:
+        raise ValueError("map_filtering needs local_ba: the filter works on the local BA's key-frame map")
     adaptive = adaptive or per_stream
     import torch
     ctx = ctx or slam.default_context(0)
     S = len(lefts); n_frames = len(lefts[0])
     H, W = lefts[0][0].shape
     fx, fy, cx, cy = cam
-    params = slam.Params(stereo=True, max_nb_keypoints=max_keypoints)
+    params = slam.Params(stereo=True, max_nb_keypoints=max_keypoints, map_filtering=map_filtering)
     camera = slam.Camera(fx, fy, cx, cy, height=H, width=W)
     ex = slam.Extractor.from_params(params, camera)
     ncell = ex.grid_resolution[0] * ex.grid_resolution[1]
@@ -129,11 +141,18 @@ def run(lefts, rights, cam, baseline, kf_every=4, max_keypoints=300, seed=0, ctx
                 if (kfid[kf_mask] > 0).any():                               # mapper.jl:86: 2-D keypoints left over, against their first observers
                     ks.triangulate_temporal(slam.stream_params(S, cam=cam), kf_cw, Twc, kfid, max_error=params.max_reprojection_error, ctx=ctx)
                 if km is not None:                                          # local_bundle_adjustment! (estimator.jl:317-347) of the streams that took the key-frame
+                    notify = map_probe or (lambda *a: None)
+                    notify(i, "lists", ks, kf_mask.copy(), Tcw.copy())
                     km.add_keyframe(ks, slam.stream_params(S, Tcw=Tcw, cam=cam), ctx=ctx)
+                    notify(i, "added", km)
                     wins, _ = km.gather(params.min_cov_score, ctx=ctx)
                     if wins:
                         slam.bundle_adjustment_batch_([w.cache for w in wins], cam, ctx=ctx)
+                        notify(i, "solved", wins)
                         km.update(wins, ks=ks, ctx=ctx)
+                    if params.map_filtering:                                # map_filtering! (estimator.jl:358-406), the estimator's next step
+                        decision["removed"] = km.filter(params.filtering_ratio, params.min_cov_score, first_kfid=filter_from, ctx=ctx)
+                        notify(i, "filtered", km, decision["removed"])
                     decision["ba"] = [(w.stream, w.cache.n_poses, w.cache.n_points, len(w.cache.poses_ids), int(w.cache.outliers.sum()),
                                        w.cache.stats["ssr_init"], w.cache.stats["ssr_final"]) for w in wins]
             if adaptive:                                                    # the key-frame's own nb_3d_kpts, after the mapper's triangulations
@@ -150,6 +169,8 @@ def run(lefts, rights, cam, baseline, kf_every=4, max_keypoints=300, seed=0, ctx
                   f"t = {np.round(Tcw[0][:3, 3], 3).tolist()} {row['ms']:.2f} ms")
             for s_, P_, M_, O_, no_, e0_, e1_ in row.get("ba", []):
                 print(f"          local BA stream {s_}: window of {P_} poses, {M_} points, {O_} observations; {no_} outliers, ssr {e0_:.3f} -> {e1_:.3f}")
+            if "removed" in row:
+                print(f"          map filtering: removed key-frames {row['removed']}")
     n3 = [int(ks.download(s)["is_3d"].sum()) for s in range(S)]
     if km is not None:
         km.close()
@@ -175,11 +196,16 @@ def main():
     ap.add_argument("--adaptive-keyframes", action="store_true", help="take key-frames where check_new_kf_required asks for one (any stream), not every 4th frame")
     ap.add_argument("--per-stream-keyframes", action="store_true", help="every stream takes its key-frames where check_new_kf_required asks for one for THAT stream (implies --adaptive-keyframes)")
     ap.add_argument("--local-ba", action="store_true", help="run the estimator's local BA after every key-frame step, on a key-frame map in HBM; the lists take the refined landmarks")
+    ap.add_argument("--map-filtering", action="store_true", help="after every local BA drop the redundant key-frames of the map (map_filtering!); requires --local-ba")
+    ap.add_argument("--filter-from", type=int, default=20, help="first key-frame id at which the filter acts (the reference's literal 20)")
     ap.add_argument("--replay-dir", default=None, help="write stream s's camera positions to DIR/stream_s as a ReplaySaver dump (src/io/saver.jl)")
     args = ap.parse_args()
+    if args.map_filtering and not args.local_ba:
+        ap.error("--map-filtering requires --local-ba")
     cam, baseline, disparity = syn.KITTI_CAM, 0.54, 8.0
     lefts, rights, offs = synthetic_scene(args.streams, args.frames, disparity=disparity)
-    out, n3 = run(lefts, rights, cam, baseline, verbose=True, adaptive=args.adaptive_keyframes, per_stream=args.per_stream_keyframes, local_ba=args.local_ba)
+    out, n3 = run(lefts, rights, cam, baseline, verbose=True, adaptive=args.adaptive_keyframes, per_stream=args.per_stream_keyframes, local_ba=args.local_ba,
+                  map_filtering=args.map_filtering, filter_from=args.filter_from)
     Z = cam[0] * baseline / disparity
     for s in range(args.streams):
         o = offs[s][-1] - offs[s][0]
@@ -189,6 +215,8 @@ def main():
         if args.local_ba:
             n_win = sum(1 for r in out for w in r.get("ba", []) if w[0] == s)
             print(f"stream {s}: {n_win} local-BA windows solved, motion error {np.abs(got - want).max():.4f} m")
+        if args.map_filtering:
+            print(f"stream {s}: map filtering removed key-frames {sorted(k for r in out for k in r.get('removed', [[]] * args.streams)[s])}")
     if args.replay_dir:
         import os
         for s in range(args.streams):

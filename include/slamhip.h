@@ -472,12 +472,39 @@ int slam_kfmap_ba_gather(slam_ctx *ctx, slam_kfmap *km, const int32_t *min_cov_s
 /* _update_ba_parameters! for the pending windows of the listed streams: theta and outliers as slam_local_ba_batch left them (windows back
  * to back, in win_stream's order).  Refined poses and positions go into the map, an outlier observation inside the covisibility map is
  * removed, is_bad! is evaluated after all removals and removes the points it condemns.  Everything goes by key-frame and keypoint id: key-frames
- * added since the gather do not matter, one the ring has forgotten meanwhile is skipped.  ks != NULL: the live lists follow -- a 3-D keypoint
+ * added since the gather do not matter, one the ring has forgotten or slam_kfmap_filter has removed meanwhile is skipped.  ks != NULL: the live lists follow -- a 3-D keypoint
  * whose point was kept takes the refined position; an outlier observation of the window's own key-frame (remove_obs_from_current_frame!) and
  * an observed point that was removed leave the list (slam_kpset_remove's compaction); nothing else in the lists changes.  A stream without a
  * pending window is an argument error and nothing is enqueued for any stream; a window is consumed by its update.  Enqueue-only. */
 int slam_kfmap_ba_update(slam_ctx *ctx, slam_kfmap *km, slam_kpset *ks /* nullable */, int n_windows, const int32_t *win_stream,
                          const double *theta, const uint8_t *outliers);
+/* map_filtering! (estimator.jl:358-406) for the streams the last slam_kfmap_add_keyframe acted on: key-frames that share too many well-observed
+ * points with the rest of the ring are removed.  Per stream s, with cur = its newest key-frame:
+ *   gates        nothing happens when filtering_ratio[s] >= 1 or cur < first_kfid (the reference's literal is 20; a parameter here);
+ *   candidates   the covisibility map of cur as the gather forms it -- every other key-frame of the ring that shares at least one live point with
+ *                cur (2-D points count) -- walked ASCENDING by key-frame id (the reference walks a Dict).  `kfid == 0 && break` is kept literally:
+ *                while key-frame 0 is covisible with cur nothing is filtered.  An id >= cur is passed over.
+ *   per candidate   n_total = its live observations whose point is 3-D (an observation without a point is skipped and left as it is); n_good = those
+ *                with more than four observers, counted after the removals this call has already made.  n_total < min_cov_score[s] / 2 (integer
+ *                division) removes the key-frame; else n_good / n_total > filtering_ratio[s], one division in doubles, removes it (0 / 0 is
+ *                NaN: kept).
+ * Deviations: n_total stands for kf.nb_3d_kpts as well (the map keeps is_3d per point, no counter per frame); `new_kf_available && break` has no
+ * counterpart (lock-stepped streams never race); has_keyframe / remove_covisible_kf! have none (covisibility is derived from the observer masks).
+ * A removal is remove_keyframe! (below).  Legal between a gather and its update: the update skips the removed key-frame (pose not copied, its
+ * outlier observations not applied).  filtering_ratio[s] must be finite or >= 1, min_cov_score[s] >= 0, first_kfid >= 0, for EVERY stream: on an
+ * error nothing is enqueued for any stream.  removed (nullable, S words): bit k % R set for every key-frame this call removed (its id is the one
+ * in (cur - R, cur) with that residue; 0 for a stream the call did not act on); non-NULL makes the call synchronous (one 8 S byte copy), NULL
+ * leaves it enqueue-only. */
+int slam_kfmap_filter(slam_ctx *ctx, slam_kfmap *km, const double *filtering_ratio /* S */, const int32_t *min_cov_score /* S */,
+                      int first_kfid, uint64_t *removed);
+/* remove_keyframe! (map_manager.jl:184-209) of one key-frame of stream s: every point it observes loses that observer, the slot becomes empty
+ * (later downloads answer "not in the ring", the next key-frame with that residue is recorded into an empty slot).  Nothing else changes: no
+ * is_bad! evaluation (the reference makes none here; the next gather demotes what became bad), the live lists are untouched, and
+ * remove_covisible_kf! has no counterpart.  Not in the ring: no-op; the newest key-frame: argument error.  The check reads the stream's newest id
+ * (one 4-byte copy, one wait); the removal itself is enqueued. */
+int slam_kfmap_remove_keyframe(slam_ctx *ctx, slam_kfmap *km, int s, int kfid);
+/* newest[s] = the id of stream s's newest key-frame, -1 where there is none yet (what turns a bit of `removed` into an id).  Synchronous. */
+int slam_kfmap_newest(slam_ctx *ctx, slam_kfmap *km, int32_t *newest /* S */);
 /* read-backs (tests, checkpoints).  download_keyframe: *n_out = -1 when key-frame kfid is not in the ring.  download_points: the valid
  * entries in id order; flags bit 0 is_3d, 1 observed, 2 ba, 3 gone; point k's observer key-frame ids, ascending, are
  * obs_kf[obs_off[k] .. obs_off[k + 1]) (obs_off: cap_out + 1 entries).  slam_kfmap_reset empties stream s's map (enqueue-only). */

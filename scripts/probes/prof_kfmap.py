@@ -10,8 +10,13 @@ camera that moves 0.3 m sideways per key-frame, 0.3 px of pixel noise, 2 cm of t
   (b) device time (plan + emit kernels) and synchronous wall time of slam_kfmap_ba_gather;
   (c) device time of slam_local_ba_batch on the gathered windows (its own figure, stats[6]);
   (d) device time of slam_kfmap_ba_update with the live lists following.
+With --filter the sequence runs a second time with map_filtering! behind every update (KeyframeMap.filter at the reference's defaults:
+filtering_ratio 0.9, min_cov_score 25, first key-frame 20), and the record is the filter's instead:
+  (e) device time of slam_kfmap_filter (span kfmap_filter), with the per-step figures and the key-frames each step removed, and the mean window
+      P / M / O of the same steps' gathers with and without the filter -- what the filter is for.
 
     python scripts/probes/prof_kfmap.py [--streams 128] [--repeats 25] [--out profiles/kfmap_s128.json]
+    python scripts/probes/prof_kfmap.py --filter [--out profiles/kfmap_filter_s128.json]
 """
 import argparse
 import json
@@ -27,6 +32,8 @@ H, W, CAP, NKP, RING, MCAP, WARM = 370, 1226, 1400, 1000, 32, 16384, 8
 
 def stat(v):
     v = [float(x) for x in v]
+    if not v:
+        return None
     return {"median": round(float(np.median(v)), 5), "min": round(min(v), 5), "max": round(max(v), 5)}
 
 
@@ -58,21 +65,12 @@ class Stream:
         return T, self.project(k) + rng.normal(0, 0.3, (n, 2)), self.f3.copy(), self.X + rng.normal(0, 0.02, (n, 3)), self.ids.copy()
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--streams", type=int, default=128)
-    ap.add_argument("--repeats", type=int, default=25)
-    ap.add_argument("--out", default=None)
-    args = ap.parse_args()
-    import slam_jl_amd as slam
-    from slam_jl_amd import synthetic as syn
-    S, R = args.streams, args.repeats
-    ctx = slam.default_context(0)                                # no device: raises here, nothing is measured
-    cam = syn.KITTI_CAM
+def sequence(slam, ctx, cam, S, R, do_filter):
+    """WARM + R key-frames of all S streams through the map's calls -> the per-step measurements of the last R"""
     streams = [Stream(np.random.default_rng(100 + s), cam) for s in range(S)]
     ks = slam.KeypointSet(S, CAP)
     km = slam.KeyframeMap(S, CAP, R=RING, mcap=MCAP)
-    t_add, t_gather, t_plan, t_emit, w_gather, t_solve, t_update, sizes = [], [], [], [], [], [], [], []
+    m = {k: [] for k in ("add", "gather", "plan", "emit", "wall", "solve", "update", "sizes", "filter", "removed", "kfid")}
     ctx.prof_enable(True)
     for k in range(WARM + R):
         Tcw = np.tile(np.eye(4), (S, 1, 1))
@@ -91,23 +89,59 @@ def main():
         if wins:
             slam.bundle_adjustment_batch_([w.cache for w in wins], cam)
             km.update(wins, ks=ks)
+        removed = km.filter(0.9, 25) if do_filter else [[]] * S
         ctx.synchronize()
         if k >= WARM:
-            t_add.append(ctx.prof_get("kfmap_add")[0]); t_plan.append(ctx.prof_get("kfmap_gather_plan")[0]); t_emit.append(ctx.prof_get("kfmap_gather_emit")[0]); t_gather.append(t_plan[-1] + t_emit[-1]); t_update.append(ctx.prof_get("kfmap_update")[0])
-            w_gather.append(wall); t_solve.append(wins[0].cache.stats["device_ms"])
-            sizes.append([np.mean([w.cache.n_poses for w in wins]), np.mean([w.cache.n_points for w in wins]), np.mean([len(w.cache.poses_ids) for w in wins]), len(wins)])
+            m["add"].append(ctx.prof_get("kfmap_add")[0]); m["plan"].append(ctx.prof_get("kfmap_gather_plan")[0]); m["emit"].append(ctx.prof_get("kfmap_gather_emit")[0])
+            m["gather"].append(m["plan"][-1] + m["emit"][-1]); m["update"].append(ctx.prof_get("kfmap_update")[0])
+            m["wall"].append(wall); m["solve"].append(wins[0].cache.stats["device_ms"])
+            m["sizes"].append([np.mean([w.cache.n_poses for w in wins]), np.mean([w.cache.n_points for w in wins]), np.mean([len(w.cache.poses_ids) for w in wins]), len(wins)])
+            if do_filter:
+                m["filter"].append(ctx.prof_get("kfmap_filter")[0]); m["removed"].append(sum(len(r) for r in removed)); m["kfid"].append(k)
     ctx.prof_enable(False)
-    sz = np.mean(np.array(sizes), axis=0)
-    rec = {"lib": os.path.basename(slam.LIB_PATH), "S": S, "cap": CAP, "keypoints_per_stream": NKP, "shape": [H, W], "ring": RING, "table": MCAP, "repeats": R,
-           "warmup_keyframes": WARM, "windows_per_step": float(sz[3]), "window_mean": {"poses": float(sz[0]), "points": float(sz[1]), "observations": float(sz[2])},
-           "a_add_keyframe_device_ms": stat(t_add), "b_gather_device_ms": stat(t_gather), "b_gather_plan_kernel_ms": stat(t_plan), "b_gather_emit_kernel_ms": stat(t_emit), "b_gather_sync_wall_ms": stat(w_gather),
-           "c_local_ba_batch_device_ms": stat(t_solve), "d_update_device_ms": stat(t_update),
-           "map_calls_device_ms_median_sum": round(float(np.median(t_add) + np.median(t_gather) + np.median(t_update)), 5)}
+    km.close(); ks.close()
+    return m
+
+
+def window_mean(m):
+    sz = np.mean(np.array(m["sizes"]), axis=0)
+    return float(sz[3]), {"poses": float(sz[0]), "points": float(sz[1]), "observations": float(sz[2])}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--streams", type=int, default=128)
+    ap.add_argument("--repeats", type=int, default=25)
+    ap.add_argument("--filter", action="store_true", help="measure slam_kfmap_filter: the sequence once without and once with the filter behind every update")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    import slam_jl_amd as slam
+    from slam_jl_amd import synthetic as syn
+    S, R = args.streams, args.repeats
+    ctx = slam.default_context(0)                                # no device: raises here, nothing is measured
+    cam = syn.KITTI_CAM
+    m = sequence(slam, ctx, cam, S, R, False)
+    n_win, wmean = window_mean(m)
+    base = {"lib": os.path.basename(slam.LIB_PATH), "S": S, "cap": CAP, "keypoints_per_stream": NKP, "shape": [H, W], "ring": RING, "table": MCAP, "repeats": R,
+            "warmup_keyframes": WARM}
+    if args.filter:
+        f = sequence(slam, ctx, cam, S, R, True)
+        rec = dict(base, filtering_ratio=0.9, min_cov_score=25, first_kfid=20, e_filter_device_ms=stat(f["filter"]),
+                   e_filter_device_ms_steps_before_first_kfid=stat([t for t, k in zip(f["filter"], f["kfid"]) if k < 20]),
+                   e_filter_device_ms_steps_from_first_kfid=stat([t for t, k in zip(f["filter"], f["kfid"]) if k >= 20]),
+                   per_step=[{"keyframe": k, "filter_ms": round(float(t), 5), "removed_all_streams": int(n)} for k, t, n in zip(f["kfid"], f["filter"], f["removed"])],
+                   keyframes_removed=int(sum(f["removed"])), window_mean_without_filter=wmean, window_mean_with_filter=window_mean(f)[1],
+                   b_gather_plan_kernel_ms_without_filter=stat(m["plan"]), b_gather_plan_kernel_ms_with_filter=stat(f["plan"]),
+                   c_local_ba_batch_device_ms_without_filter=stat(m["solve"]), c_local_ba_batch_device_ms_with_filter=stat(f["solve"]))
+    else:
+        rec = dict(base, windows_per_step=n_win, window_mean=wmean,
+                   a_add_keyframe_device_ms=stat(m["add"]), b_gather_device_ms=stat(m["gather"]), b_gather_plan_kernel_ms=stat(m["plan"]), b_gather_emit_kernel_ms=stat(m["emit"]),
+                   b_gather_sync_wall_ms=stat(m["wall"]), c_local_ba_batch_device_ms=stat(m["solve"]), d_update_device_ms=stat(m["update"]),
+                   map_calls_device_ms_median_sum=round(float(np.median(m["add"]) + np.median(m["gather"]) + np.median(m["update"])), 5))
     print(json.dumps(rec))
     if args.out:
-        with open(args.out, "w") as f:
-            f.write(json.dumps(rec, indent=1) + "\n")
-    km.close(); ks.close()
+        with open(args.out, "w") as f_:
+            f_.write(json.dumps(rec, indent=1) + "\n")
 
 
 if __name__ == "__main__":

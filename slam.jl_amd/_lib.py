@@ -104,6 +104,9 @@ SIGNATURES = {
     "slam_kfmap_add_keyframe": (cint, [vp, vp, vp, f64p]),
     "slam_kfmap_ba_gather": (cint, [vp, vp, i32p, vp, i32p]),
     "slam_kfmap_ba_update": (cint, [vp, vp, vp, cint, i32p, f64p, u8p]),
+    "slam_kfmap_filter": (cint, [vp, vp, f64p, i32p, cint, u64p]),
+    "slam_kfmap_remove_keyframe": (cint, [vp, vp, cint, cint]),
+    "slam_kfmap_newest": (cint, [vp, vp, i32p]),
     "slam_kfmap_download_keyframe": (cint, [vp, vp, cint, cint, f64p, i64p, f64p, u8p, cint, C.POINTER(cint)]),
     "slam_kfmap_download_points": (cint, [vp, vp, cint, i64p, f64p, u8p, i32p, i32p, cint, cint, C.POINTER(cint)]),
     "slam_kfmap_reset": (cint, [vp, vp, cint]),

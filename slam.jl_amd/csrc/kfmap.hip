@@ -2,12 +2,15 @@
 // it emits the local-BA windows of the streams' newest key-frames in slam_local_ba_batch's layout (slam_kfmap_ba_gather) and takes the solution back, into
 // the map and optionally into the live lists (slam_kfmap_ba_update).  The semantics are _get_ba_parameters / _update_ba_parameters!
 // (src/estimator.jl:143-306) as tests/tracked_ba.py restates them, bounded by the ring and the table (tests/np_kfmap.py is the bounded model).
+// slam_kfmap_filter is map_filtering! (src/estimator.jl:358-406) on the same map, slam_kfmap_remove_keyframe the remove_keyframe! it calls
+// (src/map_manager.jl:184-209); tests/np_kfmap_filter.py is their model.
 //
 // Every kernel takes `sel`: nullptr = workgroup (or grid row) b works on stream b, else on stream sel[b] -- launches are sized by the number of streams
 // acted on, so nothing of any other stream is read or written.
 #include "kfmap.hpp"
 #include <algorithm>
 #include <climits>
+#include <cmath>
 
 #define KFM_STREAM(b) (sel ? sel[b] : (int)(b))
 // the table entry of point `id` (ids are non-negative; taken as unsigned, any 64 bits land inside the table)
@@ -28,20 +31,28 @@ __device__ __forceinline__ int kfm_find_live(const KfmapView &V, int s, int b, i
     return i >= 0 && V.klive[sl + i] ? i : -1;
 }
 
+// remove_kf_observation! for observation i of slot r's slab (i < the slab's length): a live observation's point, where its entry still carries that id,
+// loses observer bit r.  THE rule of remove_keyframe! (map_manager.jl:184-209) as far as the map goes -- the forgetting of a re-used slot, the filter's
+// removals and slam_kfmap_remove_keyframe all come here.  Ids are unique within a slab, but several slabs may lose the same point in one launch (the
+// filter's closing pass): the atomic keeps every read-modify-write whole.
+__device__ __forceinline__ void kfm_forget_slab(const KfmapView &V, int s, int r, int i)
+{
+    const size_t q = ((size_t)s * V.R + r) * V.cap + i;
+    if (!V.klive[q]) return;
+    const int64_t id = V.kid[q];
+    const size_t pe = (size_t)s * V.mcap + kfm_entry(id, V.mcap);
+    if (V.ptag[pe] == (unsigned long long)id + 1ull) atomicAnd(&V.pmask[pe], ~(1ull << r));
+}
+
 // ---- recording: slot-parallel, one thread per list slot (grid.y = stream) -------------------------------------------------------------------------------
-// remove_keyframe! (map_manager.jl:184-209) as far as the map goes: the key-frame whose slot the new one takes is forgotten, every point it observed
-// loses that observer.  Several slots of the slab may not name the same point (ids are unique), but the atomic keeps the read-modify-write whole anyway.
+// the key-frame whose slot the new one takes is forgotten: every point it observed loses that observer
 __global__ __launch_bounds__(256) void k_kfm_forget(KfmapView V, const int *kfcount, const int *sel)
 {
     const int s = KFM_STREAM(blockIdx.y), i = blockIdx.x * 256 + threadIdx.x, kfid = kfcount[s] - 1;
     if (kfid < 0) return;
     const int r = kfid % V.R, t = V.tag[s * V.R + r];
     if (t == 0 || t == kfid + 1 || i >= min(V.kn[s * V.R + r], V.cap)) return;
-    const size_t q = ((size_t)s * V.R + r) * V.cap + i;
-    if (!V.klive[q]) return;
-    const int64_t id = V.kid[q];
-    const size_t pe = (size_t)s * V.mcap + kfm_entry(id, V.mcap);
-    if (V.ptag[pe] == (unsigned long long)id + 1ull) atomicAnd(&V.pmask[pe], ~(1ull << r));
+    kfm_forget_slab(V, s, r, i);
 }
 // "for mp in rec.mps.values(): mp.observed = False"
 __global__ __launch_bounds__(256) void k_kfm_clear_observed(KfmapView V, const int *kfcount, const int *sel)
@@ -115,6 +126,25 @@ __device__ __forceinline__ int kfm_scan(int cnt, int *s_w, int *s_base)
     __syncthreads();
     return off;
 }
+// update_frame_covisibility!'s counts (map_manager.jl:302-340) over the slab of the newest key-frame (slot r0), by the whole workgroup: s_cov[b] += 1 for
+// every live, owned point the slab shares with another slot b whose tag is valid (LDS atomics; s_tag: the ring's tags, 64 entries, 0 beyond R).  Returns the
+// thread's share of the key-frame's 3-D points.  The gather's plan and the filter both take their covisibility map from here.
+__device__ __forceinline__ int kfm_covisibility(const KfmapView &V, int s, int r0, const int *s_tag, int *s_cov)
+{
+    const size_t sl = ((size_t)s * V.R + r0) * V.cap, pb = (size_t)s * V.mcap;
+    const int n0 = min(V.kn[s * V.R + r0], V.cap);
+    int nb3 = 0;
+    for (int i = threadIdx.x; i < n0; i += 256) {
+        if (!V.klive[sl + i]) continue;
+        const int64_t id = V.kid[sl + i];
+        const size_t pe = pb + kfm_entry(id, V.mcap);
+        if (!kfm_valid(V, pe, id)) continue;
+        nb3 += (V.pflags[pe] & KFM_3D) != 0;
+        unsigned long long m = V.pmask[pe] & ~(1ull << r0);
+        while (m) { const int b = __ffsll((long long)m) - 1; m &= m - 1; if (b < V.R && s_tag[b]) atomicAdd(&s_cov[b], 1); }
+    }
+    return nb3;
+}
 // The plan of one stream's window (tracked_ba.gather up to its arrays), one 256-thread workgroup per stream, no workgroup waits for another:
 //   covisibility   one pass over the newest key-frame's slab: nb_3d and, per other observer slot, the shared points (LDS atomics)
 //   covmap         the at most 5 newest covisible key-frames (one thread; R <= 64), walked newest first
@@ -138,19 +168,8 @@ __global__ __launch_bounds__(256) void k_kfm_plan(KfmapView V, const int *minc_a
     __syncthreads();
     if (kfid < 0) { if (tid == 0) { hdr[0] = 1; hdr[1] = -1; hdr[2] = hdr[3] = hdr[4] = 0; hdr[5] = minc; hdr[6] = 0; } return; }
     const int r0 = kfid % R;
-    {   // nb_3d of the key-frame and update_frame_covisibility!'s counts (map_manager.jl:302-340)
-        const size_t sl = ((size_t)s * R + r0) * cap;
-        const int n0 = min(V.kn[s * R + r0], cap);
-        int nb3 = 0;
-        for (int i = tid; i < n0; i += 256) {
-            if (!V.klive[sl + i]) continue;
-            const int64_t id = V.kid[sl + i];
-            const size_t pe = pb + kfm_entry(id, mcap);
-            if (!kfm_valid(V, pe, id)) continue;
-            nb3 += (V.pflags[pe] & KFM_3D) != 0;
-            unsigned long long m = V.pmask[pe] & ~(1ull << r0);
-            while (m) { const int b = __ffsll((long long)m) - 1; m &= m - 1; if (b < R && s_tag[b]) atomicAdd(&s_cov[b], 1); }
-        }
+    {   // nb_3d of the key-frame and the covisibility counts
+        const int nb3 = kfm_covisibility(V, s, r0, s_tag, s_cov);
         if (nb3) atomicAdd(&s_nb3, nb3);
     }
     __syncthreads();
@@ -376,6 +395,89 @@ __global__ __launch_bounds__(256) void k_kfm_upd_list(KfmapView V, KpsetView K, 
     if (!(fl & KFM_DEAD) && K.is3d[q] && w > 0 && V.wpid[pb + w - 1] == id) for (int k = 0; k < 3; k++) K.xyz[3 * q + k] = V.pxyz[3 * pe + k];
 }
 
+// ---- filtering (map_filtering!, estimator.jl:358-406; tests/np_kfmap_filter.py is the model) -------------------------------------------------------------
+// One 256-thread workgroup per stream, no workgroup waits for another:
+//   candidates     the covisibility map of the newest key-frame (kfm_covisibility); one thread ranks it ascending by key-frame id and applies the walk's
+//                  gates: key-frame 0 ends the walk (`kfid == 0 && break`), an id >= the newest is passed over
+//   phase          per candidate a pass over its slab in chunks of 256: a thread looks its observation's point up and, if it is 3-D, counts it (n_total) and
+//                  whether more than four key-frames observe it (n_good); a wave reduction and one LDS hop give every thread both sums, so the decision --
+//                  n_total < min_cov_score / 2, else n_good / n_total > filtering_ratio in doubles (0 / 0 is NaN: kept) -- is uniform
+//   removal        the set X of key-frames removed so far is a register of every thread (uniform); observers are counted as popcount(mask & valid & ~X), so
+//                  no phase reads anything an earlier phase wrote and the map is written once, in a closing pass over the removed slabs (kfm_forget_slab),
+//                  after the last phase's barrier; then their tags and lengths are reset
+// frem[s] = X: bit k % R per removed key-frame.  new_kf_available has no counterpart: lock-stepped streams never race.
+__global__ __launch_bounds__(256) void k_kfm_filter(KfmapView V, const double *ratio_all, const int *minc_all, int first_kfid, const int *sel)
+{
+    __shared__ int s_cov[64], s_tag[64], s_cand[64], s_ncand, s_tot[2][4], s_good[2][4];
+    __shared__ unsigned long long s_valid;
+    const int s = KFM_STREAM(blockIdx.x), tid = threadIdx.x, R = V.R, cap = V.cap, mcap = V.mcap;
+    const double ratio = ratio_all[s];
+    const int kfid = V.cur[s] - 1, few = minc_all[s] / 2;
+    if (ratio >= 1.0 || kfid < first_kfid) { if (tid == 0) V.frem[s] = 0; return; }      // (uniform; first_kfid >= 0: a stream without a key-frame leaves here)
+    if (tid < 64) { s_cov[tid] = 0; s_tag[tid] = tid < R ? V.tag[s * R + tid] : 0; }
+    __syncthreads();
+    const int r0 = kfid % R;
+    (void)kfm_covisibility(V, s, r0, s_tag, s_cov);
+    __syncthreads();
+    if (tid == 0) {
+        unsigned long long used = 0, valid = 0;
+        int n = 0;
+        for (int b = 0; b < R; b++) if (s_tag[b]) valid |= 1ull << b;
+        for (;;) {                                               // ascending by key-frame id
+            int best = -1;
+            for (int b = 0; b < R; b++) if (b != r0 && s_tag[b] && s_cov[b] > 0 && !(used >> b & 1) && (best < 0 || s_tag[b] < s_tag[best])) best = b;
+            if (best < 0 || s_tag[best] == 1) break;
+            used |= 1ull << best;
+            if (s_tag[best] - 1 < kfid) s_cand[n++] = best;
+        }
+        s_ncand = n; s_valid = valid;
+    }
+    __syncthreads();
+    const int ncand = s_ncand, lane = tid & 63, wv = tid >> 6;
+    const unsigned long long valid = s_valid;
+    const size_t pb = (size_t)s * mcap;
+    unsigned long long X = 0;
+    for (int c = 0; c < ncand; c++) {
+        const int rc = s_cand[c];
+        const size_t sl = ((size_t)s * R + rc) * cap;
+        const int n = min(V.kn[s * R + rc], cap);
+        const unsigned long long seen = valid & ~X;
+        int tot = 0, good = 0;
+        for (int i = tid; i < n; i += 256) {
+            if (!V.klive[sl + i]) continue;
+            const int64_t id = V.kid[sl + i];
+            const size_t pe = pb + kfm_entry(id, mcap);
+            if (!kfm_valid(V, pe, id) || !(V.pflags[pe] & KFM_3D)) continue;             // an orphan is skipped and left as it is
+            tot++; good += __popcll(V.pmask[pe] & seen) > 4;
+        }
+        for (int o = 32; o; o >>= 1) { tot += __shfl_down(tot, o, 64); good += __shfl_down(good, o, 64); }
+        if (lane == 0) { s_tot[c & 1][wv] = tot; s_good[c & 1][wv] = good; }
+        __syncthreads();                                         // (two buffers: a wave that writes phase c + 2's sums has passed phase c + 1's barrier, behind every read of phase c's)
+        const int n_total = s_tot[c & 1][0] + s_tot[c & 1][1] + s_tot[c & 1][2] + s_tot[c & 1][3];
+        const int n_good = s_good[c & 1][0] + s_good[c & 1][1] + s_good[c & 1][2] + s_good[c & 1][3];
+        if (n_total < few || (double)n_good / (double)n_total > ratio) X |= 1ull << rc;
+    }
+    for (unsigned long long m = X; m; m &= m - 1) {              // every phase's reads lie behind its barrier: now the removals, all at once
+        const int b = __ffsll((long long)m) - 1, n = min(V.kn[s * R + b], cap);
+        for (int i = tid; i < n; i += 256) kfm_forget_slab(V, s, b, i);
+    }
+    __syncthreads();                                             // the lengths are read above, reset below
+    if (tid < R && (X >> tid & 1)) { V.tag[s * R + tid] = 0; V.kn[s * R + tid] = 0; }
+    if (tid == 0) V.frem[s] = X;
+}
+// slam_kfmap_remove_keyframe: slab-parallel, then (a launch later: every block has read the tag) the slot is emptied
+__global__ __launch_bounds__(256) void k_kfm_remove(KfmapView V, int s, int kfid)
+{
+    const int r = kfid % V.R, i = blockIdx.x * 256 + threadIdx.x;
+    if (V.tag[s * V.R + r] != kfid + 1 || V.cur[s] == kfid + 1 || i >= min(V.kn[s * V.R + r], V.cap)) return;
+    kfm_forget_slab(V, s, r, i);
+}
+__global__ void k_kfm_drop_slot(KfmapView V, int s, int kfid)
+{
+    const int q = s * V.R + kfid % V.R;
+    if (V.tag[q] == kfid + 1 && V.cur[s] != kfid + 1) { V.tag[q] = 0; V.kn[q] = 0; }
+}
+
 // Every region of the map's one allocation, each named once (kfmap.hpp has the formula): without a block for the total, with it to bind the pointers
 static size_t kfmap_regions(slam_kfmap *km, char *base)
 {
@@ -385,7 +487,7 @@ static size_t kfmap_regions(slam_kfmap *km, char *base)
     const size_t S = v.S, sr = S * v.R, n = sr * v.cap, m = S * v.mcap;
     region(v.tag, sr * 4); region(v.kn, sr * 4); region(v.ktheta, sr * 48); region(v.kid, n * 8); region(v.kupx, n * 16); region(v.klive, n); region(v.kfresh, S * v.cap);
     region(v.ptag, m * 8); region(v.pxyz, m * 24); region(v.pmask, m * 8); region(v.pflags, m);
-    region(v.cur, S * 4);
+    region(v.cur, S * 4); region(v.frem, S * 8);
     region(v.whdr, S * KFM_HDR * 4); region(v.wtag, sr * 4); region(v.worder, sr * 4); region(v.wrank, sr * 4); region(v.wconst, sr * 4); region(v.wcov, S * 8);
     region(v.wpid, m * 8); region(v.wpmask, m * 8); region(v.wpoff, m * 4); region(v.went, m * 4);
     return Lo.size();
@@ -396,6 +498,21 @@ static int kfmap_streams(const slam_kfmap *km, int *list)
     int n = 0;
     for (int s = 0; s < km->v.S; s++) if (km->n_sel == KPSEL_ALL || km->sel_host[s]) list[n++] = s;
     return n;
+}
+
+// the map's pinned staging block for an enqueue-only call's inputs, at least `bytes` long, once the copy that last read it has completed (an event never
+// recorded is complete); the caller records pin_ev behind its own copy
+static int kfmap_pin(slam_ctx *ctx, slam_kfmap *km, size_t bytes, char **out)
+{
+    HIP_TRY(ctx, hipEventSynchronize(km->pin_ev));
+    if (km->pin_bytes < bytes) {
+        if (km->pin) (void)hipHostFree(km->pin);
+        km->pin = nullptr; km->pin_bytes = 0;
+        HIP_TRY(ctx, hipHostMalloc((void **)&km->pin, bytes + bytes / 4));
+        km->pin_bytes = bytes + bytes / 4;
+    }
+    *out = km->pin;
+    return SLAM_OK;
 }
 
 extern "C" {
@@ -550,15 +667,10 @@ int slam_kfmap_ba_update(slam_ctx *ctx, slam_kfmap *km, slam_kpset *ks, int n_wi
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     Layout D;
     const auto o_win = D.take<KfmUpd>(n_windows); const auto o_th = D.take<double>((size_t)nT); const auto o_ol = D.take<uint8_t>((size_t)nO);
-    HIP_TRY(ctx, hipEventSynchronize(km->pin_ev));               // the copy that last read the pinned block (an event never recorded is complete)
-    if (km->pin_bytes < D.size()) {
-        if (km->pin) (void)hipHostFree(km->pin);
-        km->pin = nullptr; km->pin_bytes = 0;
-        HIP_TRY(ctx, hipHostMalloc((void **)&km->pin, D.size() + D.size() / 4));
-        km->pin_bytes = D.size() + D.size() / 4;
-    }
-    char *scr, *h = km->pin;
-    int rc = slam_scratch(ctx, D.size(), (void **)&scr);
+    char *scr, *h;
+    int rc = kfmap_pin(ctx, km, D.size(), &h);
+    if (rc) return rc;
+    rc = slam_scratch(ctx, D.size(), (void **)&scr);
     if (rc) return rc;
     memcpy(o_win.at(h), wins.data(), o_win.bytes()); memcpy(o_th.at(h), theta, o_th.bytes()); memcpy(o_ol.at(h), outliers, o_ol.bytes());
     HIP_TRY(ctx, hipMemcpyAsync(scr, h, D.size(), hipMemcpyHostToDevice, ctx->stream));
@@ -577,6 +689,68 @@ int slam_kfmap_ba_update(slam_ctx *ctx, slam_kfmap *km, slam_kpset *ks, int n_wi
     HIP_TRY(ctx, hipGetLastError());
     for (int w = 0; w < n_windows; w++) km->pend[win_stream[w]].valid = 0;
     if (ks) return kpset_compact(ctx, ks, 1, flags);             // (a stream without a flag keeps every slot where it is)
+    return SLAM_OK;
+}
+
+int slam_kfmap_filter(slam_ctx *ctx, slam_kfmap *km, const double *filtering_ratio, const int32_t *min_cov_score, int first_kfid, uint64_t *removed)
+{
+    ARG_TRY(ctx, ctx != nullptr && km != nullptr && filtering_ratio != nullptr && min_cov_score != nullptr && first_kfid >= 0);
+    const KfmapView &V = km->v;
+    const int S = V.S;
+    for (int s = 0; s < S; s++)                                  // every check before anything is enqueued
+        if (!(std::isfinite(filtering_ratio[s]) || filtering_ratio[s] >= 1.0) || min_cov_score[s] < 0)
+            return slam_fail(ctx, SLAM_ERR_ARG, "slam_kfmap_filter: stream %d: filtering_ratio %g (finite or >= 1), min_cov_score %d (>= 0)", s, filtering_ratio[s], (int)min_cov_score[s]);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int list[128];
+    const int ns = kfmap_streams(km, list);
+    if (removed) memset(removed, 0, (size_t)S * 8);
+    if (ns == 0) return SLAM_OK;
+    Layout D;
+    const auto o_sel = D.take<int>(S), o_minc = D.take<int>(S); const auto o_ratio = D.take<double>(S);
+    char *scr, *h;
+    int rc = kfmap_pin(ctx, km, D.size(), &h);
+    if (rc) return rc;
+    rc = slam_scratch(ctx, D.size(), (void **)&scr);
+    if (rc) return rc;
+    memcpy(o_sel.at(h), list, (size_t)ns * 4); memcpy(o_minc.at(h), min_cov_score, (size_t)S * 4); memcpy(o_ratio.at(h), filtering_ratio, (size_t)S * 8);
+    HIP_TRY(ctx, hipMemcpyAsync(scr, h, D.size(), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(km->pin_ev, ctx->stream));
+    { ProfScope span(ctx, "kfmap_filter");
+      hipLaunchKernelGGL(k_kfm_filter, dim3(ns), dim3(256), 0, ctx->stream, V, (const double *)o_ratio.at(scr), (const int *)o_minc.at(scr), first_kfid, (const int *)o_sel.at(scr)); }
+    HIP_TRY(ctx, hipGetLastError());
+    if (!removed) return SLAM_OK;
+    rc = slam_pinned(ctx, (size_t)S * 8, (void **)&h);
+    if (rc) return rc;
+    rc = kpset_read_back(ctx, h, {{0, V.frem, (size_t)S * 8, nullptr}});
+    if (rc) return rc;
+    for (int k = 0; k < ns; k++) memcpy(&removed[list[k]], h + (size_t)list[k] * 8, 8);       // (a stream the call did not act on keeps its 0)
+    return SLAM_OK;
+}
+
+int slam_kfmap_remove_keyframe(slam_ctx *ctx, slam_kfmap *km, int s, int kfid)
+{
+    ARG_TRY(ctx, ctx != nullptr && km != nullptr && s >= 0 && s < km->v.S && kfid >= 0);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const KfmapView &V = km->v;
+    int cur = 0;                                                 // the argument check needs the stream's newest id, which the device alone knows: one 4-byte read
+    HIP_TRY(ctx, hipMemcpyAsync(&cur, V.cur + s, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, slam_stream_wait(ctx->stream));
+    if (cur >= 1 && kfid == cur - 1) return slam_fail(ctx, SLAM_ERR_ARG, "slam_kfmap_remove_keyframe: key-frame %d is the newest of stream %d", kfid, s);
+    if (kfid >= cur || kfid + V.R < cur) return SLAM_OK;         // never added, or long forgotten: not in the ring
+    { ProfScope span(ctx, "kfmap_remove");
+      hipLaunchKernelGGL(k_kfm_remove, dim3((V.cap + 255) / 256), dim3(256), 0, ctx->stream, V, s, kfid);
+      hipLaunchKernelGGL(k_kfm_drop_slot, dim3(1), dim3(1), 0, ctx->stream, V, s, kfid); }
+    HIP_TRY(ctx, hipGetLastError());
+    return SLAM_OK;
+}
+
+int slam_kfmap_newest(slam_ctx *ctx, slam_kfmap *km, int32_t *newest)
+{
+    ARG_TRY(ctx, ctx != nullptr && km != nullptr && newest != nullptr);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipMemcpyAsync(newest, km->v.cur, (size_t)km->v.S * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, slam_stream_wait(ctx->stream));
+    for (int s = 0; s < km->v.S; s++) newest[s] -= 1;
     return SLAM_OK;
 }
 

@@ -4,14 +4,14 @@
 // ONE allocation, every region starting on a 256-byte boundary (Layout); with n = S R cap, m = S mcap its size is the sum, each term rounded up to 256, of
 //   ring    tag 4 S R | n_kf 4 S R | theta 48 S R | ids 8 n | upx 16 n | live n | fresh S cap
 //   table   tag 8 m | xyz 24 m | observers 8 m | flags m
-//   state   cur 4 S
+//   state   cur 4 S | removed mask 8 S
 //   window  header 32 S | tags, pose order, rank, constant 4 S R each | covmap mask 8 S | point ids 8 m | point observers 8 m | obs offsets 4 m | entry -> window 4 m
 // i.e. about 25 R cap + 65 mcap bytes per stream (cap 1 400, R 32, mcap 16 384: 2.2 MB).
 //
 // Ring: key-frame k of stream s lives in slot k % R while tag == k + 1 (0: empty).  Its slab holds the list as it was (ids ascending: ids are per-stream
 // and ascending, compaction is stable), the undistorted pixel (y, x) and a live byte per observation -- a removed observation is a tombstone, the slab stays
 // sorted and a lookup is a binary search.  Reusing a slot forgets the old key-frame: every point it observed loses that observer bit (remove_keyframe!,
-// map_manager.jl:184-209).
+// map_manager.jl:184-209); slam_kfmap_filter and slam_kfmap_remove_keyframe empty a slot the same way (tag 0, length 0) before its turn comes.
 // Table: point `id` lives in entry id % mcap while tag == id + 1.  A newer id replaces an older one; the old point is then gone and its observations in the
 // slabs are orphans (looked up, not found, skipped like a missing dictionary entry).  observers: bit k % R, meaningful only while that slot's tag matches -- the
 // forgetting rule keeps the two in step.  flags: KFM_3D is_3d, KFM_OBS `observed` = seen by the LAST key-frame added (set by add_keyframe, cleared by update;
@@ -40,6 +40,7 @@ struct KfmapView {
     unsigned long long *pmask;            // [S mcap] observer bits
     uint8_t *pflags;                      // [S mcap] KFM_*
     int *cur;                             // [S] newest key-frame id + 1
+    unsigned long long *frem;             // [S] the last slam_kfmap_filter's removals: bit k % R per removed key-frame
     // the pending window of a stream: what slam_kfmap_ba_update needs of the last gather
     int *whdr;                            // [S][KFM_HDR]
     int *wtag, *worder, *wrank, *wconst;  // [S R] the ring's tags at the gather; a slot's 1-based pose id in the window (0: none); its rank by key-frame id; theta_const

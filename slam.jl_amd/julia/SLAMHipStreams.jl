@@ -27,7 +27,7 @@ import ..SLAMHip: LIB, ctx, check
 
 export PyramidBatch, FrameRing, KeypointSet, upload!, update!, flow_match!, stereo_match!, remove!, detect!, detect_describe!, describe_batch, keyframe!, select!, selection,
        triangulate!, triangulate_temporal!, compute_pose_5pt!, compute_pose!, frame_stats, keyframe_required, counts, download, stream_params,
-       KeyframeMap, add_keyframe!, gather, download_keyframe, download_points, reset!
+       KeyframeMap, add_keyframe!, gather, download_keyframe, download_points, reset!, filter_map!, remove_keyframe!, newest
 
 const HIP = "libamdhip64"
 hipcheck(e::Cint, what) = e == 0 || error("$what: HIP error $e")
@@ -419,6 +419,21 @@ function download_points(m::KeyframeMap, s::Integer)
     (ids = ids[1:n[]], xyz = xyz[:, 1:n[]], flags = flags[1:n[]], observers = [okf[off[j] + 1:off[j + 1]] for j in 1:n[]])
 end
 reset!(m::KeyframeMap, s::Integer) = (check(ccall((:slam_kfmap_reset, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint), ctx(), m.h, s)); m)
+# map_filtering! (estimator.jl:358-406) for the streams of the last add_keyframe!: per-stream filtering_ratio and min_cov_score (S each); returns the S
+# removed-masks (bit k % R per removed key-frame), or nothing with want_removed = false (enqueue-only).  newest(m): the streams' newest key-frame ids.
+function filter_map!(m::KeyframeMap, filtering_ratio::Vector{Float64}, min_cov_score::Vector{Int32}; first_kfid::Integer = 20, want_removed::Bool = true)
+    removed = zeros(UInt64, m.S)
+    check(ccall((:slam_kfmap_filter, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Int32}, Cint, Ptr{UInt64}),
+                ctx(), m.h, filtering_ratio, min_cov_score, first_kfid, want_removed ? removed : C_NULL))
+    want_removed ? removed : nothing
+end
+remove_keyframe!(m::KeyframeMap, s::Integer, kfid::Integer) =
+    (check(ccall((:slam_kfmap_remove_keyframe, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cint), ctx(), m.h, s, kfid)); m)
+function newest(m::KeyframeMap)
+    cur = zeros(Int32, m.S)
+    check(ccall((:slam_kfmap_newest, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int32}), ctx(), m.h, cur))
+    cur
+end
 
 # ---- one live stream, one call per frame (slam_frontend_*, include/slamhip.h): what run!()'s front-end task does per frame
 # (front_end.jl:58-113, :454-470) and, at a key-frame, create_keyframe! + the mapper's stereo step (map_manager.jl:98-113, mapper.jl:51-66, :142-183),

@@ -111,6 +111,38 @@ class KeyframeMap:
         ol = np.ascontiguousarray(np.concatenate([np.asarray(o).astype(np.uint8).reshape(-1) for o in outliers] + [np.zeros(1, dtype=np.uint8)]))
         c.check(c.lib.slam_kfmap_ba_update(c.h, self.h, ks.h if ks is not None else None, len(streams), L.ptr(streams, L.i32p), L.ptr(th), L.ptr(ol, L.u8p)))
 
+    def filter(self, filtering_ratio, min_cov_score, first_kfid=20, want_removed=True, ctx=None):
+        """map_filtering! (src/estimator.jl:358-406) for the streams of the last add_keyframe: a covisible key-frame with fewer than
+        min_cov_score // 2 3-D points, or with more than filtering_ratio of them seen by more than four key-frames, is removed.
+        filtering_ratio / min_cov_score: one value or S of them; first_kfid: no filtering before that key-frame (the reference's 20).
+        -> per stream the ascending list of removed key-frame ids (synchronous), or None with want_removed=False (enqueue-only)."""
+        c = ctx or self.ctx
+        S = self.S
+        ratio = np.ascontiguousarray(np.broadcast_to(np.asarray(filtering_ratio, dtype=np.float64), (S,)))
+        minc = np.ascontiguousarray(np.broadcast_to(np.asarray(min_cov_score, dtype=np.int32), (S,)))
+        if not want_removed:
+            c.check(c.lib.slam_kfmap_filter(c.h, self.h, L.ptr(ratio), L.ptr(minc, L.i32p), int(first_kfid), None))
+            return None
+        words = np.zeros(S, dtype=np.uint64)
+        c.check(c.lib.slam_kfmap_filter(c.h, self.h, L.ptr(ratio), L.ptr(minc, L.i32p), int(first_kfid), L.ptr(words, L.u64p)))
+        self.last_removed_masks = words
+        if not words.any():
+            return [[] for _ in range(S)]
+        cur = self.newest(ctx=c)                                 # a bit names a residue: the id is the one in (cur - R, cur) with it
+        return [sorted(int(cur[s]) - ((int(cur[s]) - b) % self.R) for b in range(self.R) if int(words[s]) >> b & 1) for s in range(S)]
+
+    def newest(self, ctx=None):
+        """(S,) the id of every stream's newest key-frame, -1 where there is none yet"""
+        c = ctx or self.ctx
+        cur = np.zeros(self.S, dtype=np.int32)
+        c.check(c.lib.slam_kfmap_newest(c.h, self.h, L.ptr(cur, L.i32p)))
+        return cur
+
+    def remove_keyframe(self, s, kfid, ctx=None):
+        """remove_keyframe! (src/map_manager.jl:184-209) of key-frame kfid of stream s; not in the ring: nothing; the newest: SlamHipError"""
+        c = ctx or self.ctx
+        c.check(c.lib.slam_kfmap_remove_keyframe(c.h, self.h, int(s), int(kfid)))
+
     def download_keyframe(self, s, kfid, ctx=None):
         """dict(theta, ids, upx, live) of key-frame kfid of stream s, or None when the ring does not hold it"""
         c = ctx or self.ctx

@@ -15,6 +15,8 @@ class Params:
     max_reprojection_error: float = 3.0
     min_cov_score: int = 25
     do_local_matching: bool = False
+    filtering_ratio: float = 0.9             # params.jl:71: map_filtering! removes a key-frame when more than this share of its 3-D points has > 4 observers
+    map_filtering: bool = False              # params.jl:72
     do_local_bundle_adjustment: bool = True
     max_projection_distance: float = 2.0     # params.jl:75: gate of the local-map match, px
     max_descriptor_distance: float = 0.35    # params.jl:76: share of the 256 descriptor bits
