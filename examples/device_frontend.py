@@ -10,9 +10,10 @@ lock-stepped stereo streams with every keypoint list resident in HBM -- the call
     --adaptive-keyframes: KeypointSet.frame_stats + keyframe_required after the pose                 (check_new_kf_required)
     --local-ba: after every key-frame step KeyframeMap.add_keyframe -> gather -> bundle_adjustment_batch_ -> update(ks)   (local_bundle_adjustment!)
     --map-filtering: after update(ks) KeyframeMap.filter drops the redundant key-frames of the ring                          (map_filtering!)
+    --local-map-match: key-frames detect WITH describe; after add_keyframe KeyframeMap.add_descriptors -> local_map_match     (update_frame_covisibility! + match_local_map!)
 
 No host keypoint arrays anywhere; per frame the host receives S poses, S status words and S list lengths.  It is an
-array-level driver, not SLAM (no local-map matching, no relocalisation): what it shows is that the seams compose -- on a rigid synthetic
+array-level driver, not SLAM (no relocalisation, and the local-map match of --local-map-match is not followed by its merges): what it shows is that the seams compose -- on a rigid synthetic
 scene the poses it returns are the camera motion.
 
 With --local-ba the estimator's step runs too, on a key-frame map that lives in HBM beside the lists (slam_kfmap): every key-frame is recorded
@@ -24,13 +25,18 @@ With --map-filtering (requires --local-ba) the other half of the estimator's loo
 (estimator.jl:358-406) removes from each stream's ring the covisible key-frames most of whose 3-D points more than four key-frames observe
 (Params.filtering_ratio), from key-frame --filter-from on (the reference's literal is 20).  A removed key-frame no longer enters later windows.
 
+With --local-map-match (requires --local-ba) the mapper's last step before the estimator runs on the map too: the key-frame's new keypoints are
+described on the device (KeypointSet.detect_describe), their descriptors go into the map (add_descriptors), and the local map of every stream's newest
+key-frame -- the 3-D points of its covisible key-frames that it does not observe itself -- is staged and matched in HBM (local_map_match).  The pairs
+(keypoint id, local-map point id) are reported per stream; merging them (merge_mappoints) is not done: the map is left as it is.
+
 Key-frames are taken every `kf_every`-th frame, or, with --adaptive-keyframes, where the reference's rule asks for one
 (front_end.jl:361-393 on the statistics of the lists, one S x 8 read-back per frame).  The streams are lock-stepped -- every launch is
 shared -- so --adaptive-keyframes alone takes a key-frame FOR ALL streams when ANY stream requires one.  --per-stream-keyframes lets every
 stream follow its own rule: the key-frame seams run under KeypointSet.selected(required), which restricts them to the streams that asked
 (slam_kpset_select), and the key-frame bookkeeping (last key-frame, its nb_3d_kpts, its pose, the observer ring, the key-frame id) is per stream.
 
-    python examples/device_frontend.py --frames 12 --streams 4 [--adaptive-keyframes | --per-stream-keyframes] [--local-ba [--map-filtering [--filter-from K]]]
+    python examples/device_frontend.py --frames 12 --streams 4 [--adaptive-keyframes | --per-stream-keyframes] [--local-ba [--map-filtering [--filter-from K]] [--local-map-match]]
 """
 import argparse
 import contextlib
@@ -46,7 +52,7 @@ from slam_jl_amd import synthetic as syn  # noqa: E402
 
 
 def run(lefts, rights, cam, baseline, kf_every=4, max_keypoints=300, seed=0, ctx=None, verbose=False, adaptive=False, probe=None, per_stream=False, local_ba=False,
-        map_filtering=False, filter_from=20, map_probe=None):
+        map_filtering=False, filter_from=20, map_probe=None, local_map_match=False):
     """lefts / rights: per stream a list of float images in [0, 1] (H, W).  Returns per frame a dict with the S poses
     (world -> camera, world = the first frame's camera), status words, list lengths and the wall time.
     adaptive: frame 0 is a key-frame; after the pose of every later frame the lists' statistics (KeypointSet.frame_stats, flags = 1) go
@@ -62,9 +68,14 @@ def run(lefts, rights, cam, baseline, kf_every=4, max_keypoints=300, seed=0, ctx
     map_filtering (needs local_ba): after the update KeyframeMap.filter(params.filtering_ratio, params.min_cov_score, first_kfid=filter_from) runs
     for the same streams; those rows carry `removed`: per stream the key-frame ids it dropped.  map_probe(frame, stage, ...) is called around the
     map calls of a key-frame step: ("lists", ks, kf_mask, Tcw) before add_keyframe, ("added", km) after it, ("solved", wins) after the solve and
-    before the update, ("filtered", km, removed) after the filter."""
+    before the update, ("filtered", km, removed) after the filter.
+    local_map_match (needs local_ba): key-frames detect with describe, the descriptors follow the key-frame into the map, and before the gather
+    KeyframeMap.local_map_match runs for the same streams; those rows carry `lmm`: (status (S,), pairs per stream, distances per stream).  map_probe
+    is also called with ("described", desc, info, dcap) -- the device tensors detect_describe filled -- and ("matched", km, status, pairs, dist)."""
     if map_filtering and not local_ba:
         raise ValueError("map_filtering needs local_ba: the filter works on the local BA's key-frame map")
+    if local_map_match and not local_ba:
+        raise ValueError("local_map_match needs local_ba: the match works on the local BA's key-frame map")
     adaptive = adaptive or per_stream
     import torch
     ctx = ctx or slam.default_context(0)
@@ -77,6 +88,12 @@ def run(lefts, rights, cam, baseline, kf_every=4, max_keypoints=300, seed=0, ctx
     ncell = ex.grid_resolution[0] * ex.grid_resolution[1]
     ks = slam.KeypointSet(S, max_keypoints + ncell + 8, ctx=ctx)
     km = slam.KeyframeMap(S, ks.cap, R=16, mcap=8192, ctx=ctx) if local_ba else None
+    if local_map_match:
+        km.enable_descriptors(ctx=ctx)
+        dcap = ncell * -(-ex.max_points // ncell)
+        desc = torch.zeros((S, dcap, 4), dtype=torch.int64, device="cuda"); info = torch.zeros((S, 2), dtype=torch.int64, device="cuda")
+        cam10 = (fx, fy, cx, cy, 0.0, 0.0, 0.0, 0.0, float(H), float(W))
+        torch.cuda.synchronize()
     prev = slam.PyramidBatch((H, W), levels=params.pyramid_levels, S=S, ctx=ctx)
     cur = slam.PyramidBatch((H, W), levels=params.pyramid_levels, S=S, ctx=ctx)
     rpyr = slam.PyramidBatch((H, W), levels=params.pyramid_levels, S=S, ctx=ctx)
@@ -125,7 +142,10 @@ def run(lefts, rights, cam, baseline, kf_every=4, max_keypoints=300, seed=0, ctx
         if kf_mask.any():
             # the six key-frame seams act on the streams of kf_mask (all of them without per_stream: no selection is ever set then)
             with (ks.selected(kf_mask, ctx=ctx) if per_stream else contextlib.nullcontext()):
-                ks.detect(ex, cur, ctx=ctx)
+                if local_map_match:                                         # extract_keypoints! with describe (map_manager.jl:98-113)
+                    ks.detect_describe(ex, cur, desc.data_ptr(), info.data_ptr(), dcap, ctx=ctx)
+                else:
+                    ks.detect(ex, cur, ctx=ctx)
                 ks.keyframe(ctx=ctx)
                 Tkf[kf_mask] = Tcw[kf_mask]
                 kfid = n_kf.copy()                                          # per stream: the id of the key-frame being created
@@ -145,6 +165,12 @@ def run(lefts, rights, cam, baseline, kf_every=4, max_keypoints=300, seed=0, ctx
                     notify(i, "lists", ks, kf_mask.copy(), Tcw.copy())
                     km.add_keyframe(ks, slam.stream_params(S, Tcw=Tcw, cam=cam), ctx=ctx)
                     notify(i, "added", km)
+                    if local_map_match:                                     # update_frame_covisibility! + match_local_map! (mapper.jl:118-133), before add_new_kf!
+                        km.add_descriptors(desc.data_ptr(), info.data_ptr(), dcap, ctx=ctx)
+                        notify(i, "described", desc, info, dcap)
+                        decision["lmm"] = km.local_map_match(cam10, ex.cell_size, params.max_projection_distance, params.max_descriptor_distance,
+                                                             max_local=10 * max_keypoints, ctx=ctx)
+                        notify(i, "matched", km, *decision["lmm"])
                     wins, _ = km.gather(params.min_cov_score, ctx=ctx)
                     if wins:
                         slam.bundle_adjustment_batch_([w.cache for w in wins], cam, ctx=ctx)
@@ -169,6 +195,8 @@ def run(lefts, rights, cam, baseline, kf_every=4, max_keypoints=300, seed=0, ctx
                   f"t = {np.round(Tcw[0][:3, 3], 3).tolist()} {row['ms']:.2f} ms")
             for s_, P_, M_, O_, no_, e0_, e1_ in row.get("ba", []):
                 print(f"          local BA stream {s_}: window of {P_} poses, {M_} points, {O_} observations; {no_} outliers, ssr {e0_:.3f} -> {e1_:.3f}")
+            if "lmm" in row:
+                print(f"          local-map match: status {row['lmm'][0].tolist()}, pairs per stream {[len(p) for p in row['lmm'][1]]}")
             if "removed" in row:
                 print(f"          map filtering: removed key-frames {row['removed']}")
     n3 = [int(ks.download(s)["is_3d"].sum()) for s in range(S)]
@@ -197,15 +225,18 @@ def main():
     ap.add_argument("--per-stream-keyframes", action="store_true", help="every stream takes its key-frames where check_new_kf_required asks for one for THAT stream (implies --adaptive-keyframes)")
     ap.add_argument("--local-ba", action="store_true", help="run the estimator's local BA after every key-frame step, on a key-frame map in HBM; the lists take the refined landmarks")
     ap.add_argument("--map-filtering", action="store_true", help="after every local BA drop the redundant key-frames of the map (map_filtering!); requires --local-ba")
+    ap.add_argument("--local-map-match", action="store_true", help="describe the key-frames' new keypoints and match each stream's local map against them on the key-frame map (match_local_map!); requires --local-ba")
     ap.add_argument("--filter-from", type=int, default=20, help="first key-frame id at which the filter acts (the reference's literal 20)")
     ap.add_argument("--replay-dir", default=None, help="write stream s's camera positions to DIR/stream_s as a ReplaySaver dump (src/io/saver.jl)")
     args = ap.parse_args()
     if args.map_filtering and not args.local_ba:
         ap.error("--map-filtering requires --local-ba")
+    if args.local_map_match and not args.local_ba:
+        ap.error("--local-map-match requires --local-ba")
     cam, baseline, disparity = syn.KITTI_CAM, 0.54, 8.0
     lefts, rights, offs = synthetic_scene(args.streams, args.frames, disparity=disparity)
     out, n3 = run(lefts, rights, cam, baseline, verbose=True, adaptive=args.adaptive_keyframes, per_stream=args.per_stream_keyframes, local_ba=args.local_ba,
-                  map_filtering=args.map_filtering, filter_from=args.filter_from)
+                  map_filtering=args.map_filtering, filter_from=args.filter_from, local_map_match=args.local_map_match)
     Z = cam[0] * baseline / disparity
     for s in range(args.streams):
         o = offs[s][-1] - offs[s][0]
@@ -215,6 +246,8 @@ def main():
         if args.local_ba:
             n_win = sum(1 for r in out for w in r.get("ba", []) if w[0] == s)
             print(f"stream {s}: {n_win} local-BA windows solved, motion error {np.abs(got - want).max():.4f} m")
+        if args.local_map_match:
+            print(f"stream {s}: local-map match found {sum(len(r['lmm'][1][s]) for r in out if 'lmm' in r)} pairs over {sum(1 for r in out if 'lmm' in r)} key-frames")
         if args.map_filtering:
             print(f"stream {s}: map filtering removed key-frames {sorted(k for r in out for k in r.get('removed', [[]] * args.streams)[s])}")
     if args.replay_dir:

@@ -513,6 +513,40 @@ int slam_kfmap_download_keyframe(slam_ctx *ctx, slam_kfmap *km, int s, int kfid,
 int slam_kfmap_download_points(slam_ctx *ctx, slam_kfmap *km, int s, int64_t *ids, double *xyz, uint8_t *flags, int32_t *obs_off,
                                int32_t *obs_kf, int cap_out, int cap_obs, int *n_out);
 int slam_kfmap_reset(slam_ctx *ctx, slam_kfmap *km, int s);
+/* Descriptors in the map, opt-in (nothing changes for a map that never enables them): one n_bits = 256 row (4 words, the only width the
+ * local-map match handles) and a "has descriptor" byte per table entry, 33 mcap bytes per stream in an allocation of their own.  The row of
+ * point `id` lives at entry id % mcap under the table's ownership rule; a point replaced by a larger id loses its descriptor with its entry.
+ * ONE descriptor per point is the whole of keyframes_descriptors here: map_manager.jl:116-131 describes only the keypoints a key-frame has just
+ * extracted; further rows would come from merges, which the map does not apply.  Enabling twice is a no-op. */
+int slam_kfmap_enable_descriptors(slam_ctx *ctx, slam_kfmap *km, int n_bits);
+/* Right after slam_kfmap_add_keyframe, with the arrays slam_kpset_detect_describe has just filled (desc_dev: S x dcap x 4 words, info_dev:
+ * S x 2 int64, both in HBM): row j of stream s goes to the entry of id info_dev[2 s] + j where that entry carries the id.  Acts on the streams
+ * the last slam_kfmap_add_keyframe acted on.  Enqueue-only. */
+int slam_kfmap_add_descriptors(slam_ctx *ctx, slam_kfmap *km, const uint64_t *desc_dev, const int64_t *info_dev, int dcap);
+/* update_frame_covisibility! + match_local_map! (map_manager.jl:302-355, mapper.jl:265-383) on the map, for the streams the last
+ * slam_kfmap_add_keyframe acted on: the local map of each stream's newest key-frame `cur` is staged in HBM in slam_local_map_match_batch's packed
+ * layout and matched by the same kernel; nothing returns to the host between staging and match, the call ends in one copy of the results.
+ *   covisible key-frames   every other key-frame of the ring that shares a live point with cur (the gather's and the filter's covisibility);
+ *   local map      the points that are 3-D, not removed, have a descriptor, have a live observation in a covisible key-frame and are NOT observed by
+ *                  cur, each once, ASCENDING by id (the reference iterates a Set); among equal distances the larger local-map index wins;
+ *   keypoints      cur's live observations whose point has a descriptor, in list order (ascending id); a keypoint's observers are its point's
+ *                  observer key-frames with the pixel found there, a missing or removed observation skipped (mapper.jl:429-434);
+ *   frame          Tcw from cur's theta; nb_3d_kpts = cur's live 3-D points (below 30 the projection distance doubles, mapper.jl:332).
+ * cam [S x 10] = fx fy cx cy k1 k2 p1 p2 height width, cell_size, max_projection_distance, max_descriptor_distance [S] as for
+ * slam_local_map_match_batch.  max_local bounds a stream's local map (the reference's 10 max_nb_keypoints).  status[s]: 0 matched; 1 nothing to
+ * match (not acted on, no covisible key-frame, an empty local map or keypoint list); 2 the local map exceeds max_local -- nothing is matched for
+ * that stream, the others are unaffected.  Result: the reference's prev_new_map (mapper.jl:370-382) as pairs (keypoint id, local-map point id),
+ * ascending by keypoint id, the streams back to back in stream order (n_pairs[s] each), with the winning descriptor distance; more than
+ * cap_pairs pairs in all is a capacity error.  The call changes NOTHING in the map: merge_mappoints is the caller's.
+ * Deviations: the slabs hold undistorted pixels while find_best_match uses kp.pixel, so non-zero k1, k2, p1, p2 of any stream is an argument
+ * error (as is a map without descriptors), nothing is launched; frame.local_map_ids is not kept between key-frames (no replace-or-union rule
+ * map_manager.jl:350-354, no union with the oldest covisible key-frame's local map mapper.jl:274-286); no remove_mappoint_obs! clean-ups; a
+ * keypoint outside the cell grid is in no cell.  Memory: a staging allocation with fixed per-stream strides, about cap (100 + 20 R) +
+ * max_local (100 + 4 R) + 4 mcap bytes per stream, made by the first call.  Synchronous. */
+int slam_kfmap_local_map_match(slam_ctx *ctx, slam_kfmap *km, const double *cam /* S x 10 */, const int32_t *cell_size,
+                               const double *max_projection_distance, const double *max_descriptor_distance, int max_local,
+                               int32_t *status /* S */, int32_t *n_pairs /* S */, int64_t *pairs /* cap_pairs x 2: keypoint id, local-map id */,
+                               double *dist, int cap_pairs);
 
 /* ---- one live stream, one call per frame (round 6) -----------------------------------------------------------------------------------
  * What run!() does per frame (src/front_end.jl:58-113: preprocess! :454-470 = copy!(previous_pyramid, current_pyramid) + update!,

@@ -1,0 +1,162 @@
+"""slam_kfmap_local_map_match at the throughput shape against the only route there was before it -- download every stream's slabs and table, assemble
+the local map, the observer lists and the descriptor sets in Python, slam_local_map_match_batch -- on the SAME map, in one session.
+
+Shape: prof_kfmap.py's (S = 128 streams, 370 x 1226, lists of about 1 000 keypoints, cap 1 400, ring R = 32, table of 16 384 points, a rigid scene, a
+fifth of a list replaced per key-frame), cell 35, max_local = 10 000, every new point with a random 256-bit descriptor (so hardly any pair: the cost of
+staging and of the gates, not of merges).  Warm-up runs 8 key-frames; then per repeat one key-frame of all S streams:
+  (a) device time of slam_kfmap_add_descriptors (span kfmap_add_descriptors);
+  (b) slam_kfmap_local_map_match: device time of the whole call (span kfmap_local_map_match: upload, memset, staging, match, pairs, copy of results), of
+      the staging kernel (kfmap_lm_stage) and of the match kernel (local_map_match_kernel), and the wall time of the synchronous call;
+  (c) the host route on the same map, on the first --host-repeats of the steps (it takes seconds per step at S = 128): wall time of the downloads, of the
+      Python assembly + packing, and of the slam_local_map_match_batch call; its pairs are compared with (b)'s.
+Medians with the spread (min - max) over the repeats.
+
+    python scripts/probes/prof_kfmap_local_map.py [--streams 128] [--repeats 25] [--host-repeats 25] [--out profiles/kfmap_local_map_s128.json]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from prof_kfmap import CAP, H, MCAP, RING, W, WARM, NKP, Stream, stat  # noqa: E402
+
+CELL, MAX_LOCAL, DCAP = 35, 10000, CAP
+
+
+def tcw_of(theta):
+    s1, c1, s2, c2, s3, c3 = np.sin(theta[0]), np.cos(theta[0]), np.sin(theta[1]), np.cos(theta[1]), np.sin(theta[2]), np.cos(theta[2])
+    T = np.eye(4)
+    T[:3, :3] = [[c1 * c2, c1 * s2 * s3 - s1 * c3, c1 * s2 * c3 + s1 * s3], [s1 * c2, s1 * s2 * s3 + c1 * c3, s1 * s2 * c3 - c1 * s3], [-s2, c2 * s3, c2 * c3]]
+    T[:3, 3] = theta[3:6]
+    return T
+
+
+def download(km, s, cur):
+    kfs = {k: d for k in range(max(cur - RING + 1, 0), cur + 1) for d in [km.download_keyframe(s, k)] if d is not None}
+    return kfs, km.download_points(s)
+
+
+def assemble(kfs, pts, cur, rows, cam10, params):
+    """the host-array problem of one stream from its downloads (update_frame_covisibility! + the lists of do_local_map_matching) -> (problem, lm ids, keypoint ids)"""
+    point = {int(i): j for j, i in enumerate(pts["ids"])}
+    live = {k: {int(i): (float(p[0]), float(p[1])) for i, p, lv in zip(d["ids"], d["upx"], d["live"]) if lv} for k, d in kfs.items()}
+    obs, is3 = pts["observers"], pts["is_3d"]
+    cov = set()
+    for i in live[cur]:
+        if i in point:
+            cov.update(o for o in obs[point[i]] if o != cur and o in kfs)
+    lm = sorted({i for o in cov for i in live[o] if i in point and is3[point[i]] and i in rows and cur not in obs[point[i]]})
+    order = sorted(kfs)
+    row = {k: j for j, k in enumerate(order)}
+    kp_ids = [i for i in live[cur] if i in point and i in rows]
+    if not lm or not kp_ids:
+        return None, lm, kp_ids
+    keypoints = [{"pixel": live[cur][i], "descriptors": rows[i].reshape(1, 4), "observers": [(row[o], live[o][i]) for o in obs[point[i]] if o in kfs and i in live[o]]}
+                 for i in kp_ids]
+    local_map = [{"position": pts["xyz"][point[i]], "descriptors": rows[i].reshape(1, 4), "observers": [row[o] for o in obs[point[i]] if o in kfs]} for i in lm]
+    frame = {"Tcw": tcw_of(kfs[cur]["theta"]), "cam": cam10, "cell_size": CELL, "nb_3d_kpts": sum(1 for i in live[cur] if i in point and is3[point[i]])}
+    return (frame, keypoints, np.array([tcw_of(kfs[k]["theta"]) for k in order]), local_map, params), lm, kp_ids
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--streams", type=int, default=128)
+    ap.add_argument("--repeats", type=int, default=25)
+    ap.add_argument("--host-repeats", type=int, default=25)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    import torch
+    import slam_jl_amd as slam
+    from slam_jl_amd import synthetic as syn
+    S, R = args.streams, args.repeats
+    ctx = slam.default_context(0)                                # no device: raises here, nothing is measured
+    cam = syn.KITTI_CAM
+    cam10 = tuple(cam) + (0.0, 0.0, 0.0, 0.0, float(H), float(W))
+    params = slam.Params()
+    rng = np.random.default_rng(7)
+    streams = [Stream(np.random.default_rng(100 + s), cam) for s in range(S)]
+    ks = slam.KeypointSet(S, CAP)
+    km = slam.KeyframeMap(S, CAP, R=RING, mcap=MCAP)
+    km.enable_descriptors()
+    rows = [dict() for _ in range(S)]
+    m = {k: [] for k in ("desc", "call", "stage", "kernel", "wall", "h_down", "h_asm", "h_call", "h_total", "M", "N", "pairs")}
+    agree = []
+    ctx.prof_enable(True)
+    for k in range(WARM + R):
+        Tcw = np.tile(np.eye(4), (S, 1, 1))
+        desc = np.zeros((S, DCAP, 4), dtype=np.uint64); info = np.zeros((S, 2), dtype=np.int64)
+        for s, st in enumerate(streams):
+            first = st.next
+            Tcw[s], yx, f3, xyz, ids = st.keyframe(k)
+            ks.upload(s, yx, f3, xyz, ids)
+            n_new = st.next - first
+            assert n_new <= DCAP
+            new = rng.integers(0, 2 ** 64, (n_new, 4), dtype=np.uint64)
+            desc[s, :n_new] = new; info[s] = (first, n_new)
+            rows[s].update({first + j: new[j] for j in range(n_new)})
+        desc_dev = torch.from_numpy(desc.view(np.int64)).cuda(); info_dev = torch.from_numpy(info).cuda()
+        torch.cuda.synchronize()
+        ks.keyframe()
+        km.add_keyframe(ks, slam.stream_params(S, Tcw=Tcw, cam=cam))
+        ctx.synchronize()
+        ctx.prof_reset()
+        km.add_descriptors(desc_dev.data_ptr(), info_dev.data_ptr(), DCAP)
+        ctx.synchronize()
+        t0 = time.perf_counter()
+        status, pairs, dist = km.local_map_match(cam10, CELL, params.max_projection_distance, params.max_descriptor_distance, max_local=MAX_LOCAL)
+        wall = (time.perf_counter() - t0) * 1e3
+        assert not (status == 2).any(), "a local map did not fit the probe's max_local"
+        if k >= WARM:
+            m["desc"].append(ctx.prof_get("kfmap_add_descriptors")[0]); m["call"].append(ctx.prof_get("kfmap_local_map_match")[0])
+            m["stage"].append(ctx.prof_get("kfmap_lm_stage")[0]); m["kernel"].append(ctx.prof_get("local_map_match_kernel")[0]); m["wall"].append(wall)
+            dbg = [km.debug_local_map(s) for s in range(0, S, max(S // 8, 1))]
+            m["M"].append(float(np.mean([len(d["lm_ids"]) for d in dbg]))); m["N"].append(float(np.mean([len(d["kp_ids"]) for d in dbg])))
+            m["pairs"].append(int(sum(len(p) for p in pairs)))
+        if k >= WARM and k - WARM < args.host_repeats:
+            cur = km.newest()
+            t0 = time.perf_counter()
+            down = [download(km, s, int(cur[s])) for s in range(S)]
+            t1 = time.perf_counter()
+            made = [assemble(down[s][0], down[s][1], int(cur[s]), rows[s], cam10, params) for s in range(S)]
+            live = [s for s in range(S) if made[s][0] is not None]
+            from slam_jl_amd import _lib as L, local_map as lmod
+            import ctypes as C
+            packs = [lmod.pack_local_map(*made[s][0]) for s in live]
+            p, kp_off, kf_off, mp_off = lmod.concat_packs(packs)
+            a, out = lmod._args(p)
+            t2 = time.perf_counter()
+            ctx.check(ctx.lib.slam_local_map_match_batch(ctx.h, len(live), L.ptr(kp_off, L.i32p), L.ptr(kf_off, L.i32p), L.ptr(mp_off, L.i32p), C.byref(a)))
+            t3 = time.perf_counter()
+            m["h_down"].append((t1 - t0) * 1e3); m["h_asm"].append((t2 - t1) * 1e3); m["h_call"].append((t3 - t2) * 1e3); m["h_total"].append((t3 - t0) * 1e3)
+            same = [status[s] == 0 for s in live] == [True] * len(live)
+            for z, s in enumerate(live):
+                mt = out["match"][kp_off[z]:kp_off[z + 1]]
+                took = np.flatnonzero(mt >= 0)
+                want = np.array([(made[s][2][j], made[s][1][mt[j]]) for j in took], dtype=np.int64).reshape(-1, 2)
+                same = same and np.array_equal(want, pairs[s])
+            agree.append(bool(same))
+        del desc_dev, info_dev
+    ctx.prof_enable(False)
+    km.close(); ks.close()
+    rec = {"lib": os.path.basename(slam.LIB_PATH), "S": S, "cap": CAP, "keypoints_per_stream": NKP, "shape": [H, W], "cell": CELL, "ring": RING, "table": MCAP,
+           "max_local": MAX_LOCAL, "repeats": R, "host_repeats": len(m["h_total"]), "warmup_keyframes": WARM,
+           "local_map_points_per_stream": stat(m["M"]), "keypoints_with_descriptor_per_stream": stat(m["N"]), "pairs_all_streams": stat(m["pairs"]),
+           "a_add_descriptors_device_ms": stat(m["desc"]),
+           "b_local_map_match_device_ms": stat(m["call"]), "b_stage_kernel_ms": stat(m["stage"]), "b_match_kernel_ms": stat(m["kernel"]),
+           "b_local_map_match_sync_wall_ms": stat(m["wall"]),
+           "c_host_route_wall_ms": stat(m["h_total"]), "c_host_downloads_wall_ms": stat(m["h_down"]), "c_host_assembly_and_packing_wall_ms": stat(m["h_asm"]),
+           "c_host_batch_call_wall_ms": stat(m["h_call"]), "c_host_route_pairs_equal_device": agree}
+    print(json.dumps(rec))
+    if args.out:
+        with open(args.out, "w") as f_:
+            f_.write(json.dumps(rec, indent=1) + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -3,7 +3,8 @@
 // the map and optionally into the live lists (slam_kfmap_ba_update).  The semantics are _get_ba_parameters / _update_ba_parameters!
 // (src/estimator.jl:143-306) as tests/tracked_ba.py restates them, bounded by the ring and the table (tests/np_kfmap.py is the bounded model).
 // slam_kfmap_filter is map_filtering! (src/estimator.jl:358-406) on the same map, slam_kfmap_remove_keyframe the remove_keyframe! it calls
-// (src/map_manager.jl:184-209); tests/np_kfmap_filter.py is their model.
+// (src/map_manager.jl:184-209); tests/np_kfmap_filter.py is their model.  The descriptor store and slam_kfmap_local_map_match (update_frame_covisibility! +
+// match_local_map!, staged on the device for localmap.hip's match kernel) are in kfmap_lmm.inc, included at the end: they use the routines below.
 //
 // Every kernel takes `sel`: nullptr = workgroup (or grid row) b works on stream b, else on stream sel[b] -- launches are sized by the number of streams
 // acted on, so nothing of any other stream is read or written.
@@ -102,6 +103,7 @@ __global__ __launch_bounds__(256) void k_kfm_record(KfmapView V, KpsetView K, co
     if (fresh) {
         for (int k = 0; k < 3; k++) V.pxyz[3 * pe + k] = K.xyz[3 * ql + k];
         V.pmask[pe] = 1ull << r; V.pflags[pe] = KFM_OBS | (t3 ? KFM_3D : 0);
+        if (V.dhas) V.dhas[pe] = 0;                                              // a new owner: the old point's descriptor goes with it
     } else {
         const uint8_t fl = V.pflags[pe];
         V.pmask[pe] |= 1ull << r;
@@ -544,6 +546,8 @@ int slam_kfmap_destroy(slam_kfmap *km)
     (void)hipDeviceSynchronize();
     if (km->base) (void)hipFree(km->base);
     if (km->pin) (void)hipHostFree(km->pin);
+    if (km->dbase) (void)hipFree(km->dbase);
+    if (km->lm_base) (void)hipFree(km->lm_base);
     if (km->pin_ev) (void)hipEventDestroy(km->pin_ev);
     delete km;
     return SLAM_OK;
@@ -827,9 +831,12 @@ int slam_kfmap_reset(slam_ctx *ctx, slam_kfmap *km, int s)
     HIP_TRY(ctx, hipMemsetAsync(V.pflags + (size_t)s * V.mcap, 0, (size_t)V.mcap, ctx->stream));
     HIP_TRY(ctx, hipMemsetAsync(V.pmask + (size_t)s * V.mcap, 0, (size_t)V.mcap * 8, ctx->stream));
     HIP_TRY(ctx, hipMemsetAsync(V.cur + s, 0, 4, ctx->stream));
+    if (V.dhas) HIP_TRY(ctx, hipMemsetAsync(V.dhas + (size_t)s * V.mcap, 0, (size_t)V.mcap, ctx->stream));
     HIP_TRY(ctx, hipMemsetAsync(V.whdr + (size_t)s * KFM_HDR, 0, KFM_HDR * 4, ctx->stream));
     km->pend[s].valid = 0;
     return SLAM_OK;
 }
 
 }  // extern "C"
+
+#include "kfmap_lmm.inc"

@@ -18,8 +18,37 @@
 // NOT refreshed every frame as the reference's is_observed is), KFM_BA position set by a bundle adjustment, KFM_GONE the id has left the current frame (an
 // outlier observation of the window's own key-frame, an observed point that was removed): later lists that still carry it are not recorded, KFM_DEAD the
 // point was removed (the entry keeps its tag so that KFM_GONE outlives it).
+//
+// Descriptors (slam_kfmap_enable_descriptors; a second allocation, made by that call): one 256-bit row and a "has descriptor" byte per table entry,
+// 33 mcap bytes per stream.  The row of point `id` lives at entry id % mcap under the table's ownership rule: slam_kfmap_add_descriptors writes it only
+// where the entry carries that id, and an entry that changes owner (a larger id claims it, or a removed id is recorded anew) loses the byte with the point.
+// ONE descriptor per point is the whole of the reference's keyframes_descriptors here: map_manager.jl:116-131 describes only the keypoints a key-frame
+// has just extracted, and further rows would come from merges (merge_mappoints), which this map does not apply.
+//
+// Local-map staging (slam_kfmap_local_map_match, kfmap_lmm.inc; a third allocation, made by the first call and re-made when max_local or the grid grows):
+// the packed buffer of k_lmm_match (lmm_host.hpp) with FIXED per-stream strides -- no count pass, no scan over the streams, hence no host round trip between
+// staging and match.  With N1 = cap + 1, M1 = max_local + 1, C1 = the call's largest cell count + 1, per stream, each region rounded up to 256 over S:
+//   keypoints   N1 (16 yx + 4 + 4 offsets + 32 descriptor + 8 id + 4 cell list + 8 key) + 20 N1 R observers (row, pixel)
+//   key-frames  128 R
+//   local map   M1 (24 xyz + 4 + 4 offsets + 32 descriptor + 8 id + 4 + 8 + 16 best_kp, best_dist, proj_yx) + 4 M1 R observers
+//   cells       8 C1 (offsets, cursors) | mark 4 mcap | LmmStream 280 | counts 8
+//   results     status 4 | pairs 4 | cap (16 ids + 8 distance)
+// i.e. about cap (100 + 20 R) + max_local (100 + 4 R) + 4 mcap bytes per stream (cap 1 400, R 32, max_local 14 000, mcap 16 384: 4.3 MB; S = 128:
+// 550 MB).  The observer regions are sized for the worst case (every point seen by every key-frame of the ring); they are what a count -> scan -> emit
+// staging would save, at the price of a second pass over the table and a scan launch.
+//
+// Deviations of slam_kfmap_local_map_match from update_frame_covisibility! + match_local_map! (map_manager.jl:302-355, mapper.jl:265-462):
+//   distortion    the slabs hold UNDISTORTED pixels, find_best_match uses kp.pixel and project_world_to_image_distort; the two coincide only without
+//                 lens distortion, so a stream with non-zero k1, k2, p1, p2 is an argument error (the restriction of the set's stereo seams)
+//   persistence   frame.local_map_ids is not kept between key-frames: neither the replace-or-union rule (map_manager.jl:350-354) nor the union with the
+//                 oldest covisible key-frame's local map (mapper.jl:274-286) is modelled; the local map is what this key-frame's covisibility pass yields
+//   clean-ups     no remove_mappoint_obs! clean-ups (mapper.jl:412, :429-434), as in the array form: a missing or dead observation is skipped
+//   merges        merge_mappoints is not applied: the call reports pairs and changes nothing in the map
+//   order         the local map is walked ascending by id (the reference iterates a Set); among equal distances the larger local-map index wins
+//   grid          a keypoint whose pixel lies in no cell of the grid is in no cell list (the array form rejects such a call)
 #pragma once
 #include "kpset.hpp"
+#include "lmm_host.hpp"
 
 constexpr int KFM_MAX_R = 64;
 constexpr uint8_t KFM_3D = 1, KFM_OBS = 2, KFM_BA = 4, KFM_GONE = 8, KFM_DEAD = 16;
@@ -49,6 +78,27 @@ struct KfmapView {
     unsigned long long *wpmask;           // [S mcap] the point's observers in the window
     int *wpoff;                           // [S mcap] index of its first observation
     int *went;                            // [S mcap] by table entry: 0 untouched, -1 bad, j + 1 = point j of the window
+    // the descriptor store (nullptr until slam_kfmap_enable_descriptors)
+    uint64_t *ddesc;                      // [S mcap][4] the 256-bit row of the entry's point
+    uint8_t *dhas;                        // [S mcap] 1: the row belongs to the entry's current owner
+};
+
+// what the host works out per stream for a staged local-map call (everything of LmmStream that does not depend on the map)
+struct KfmLmArg { double cam[10], max_proj, start, view_thr; int32_t cell, gr, gc, pad; };
+// the staged call's regions (kfmap.hpp's size formula), by value to the staging kernels; stream s owns [s N1, ..) of the keypoint regions, [s M1, ..) of
+// the local-map regions, [s R, ..) of the key-frame rows, [s C1, ..) of the cell regions, [s N1 R, ..) / [s M1 R, ..) of the observer regions
+struct KfmLm {
+    int N1, M1, C1, max_local;
+    LmmStream *st;                        // [S] by LAUNCH index: row z is the z-th stream acted on
+    double *kp_yx; int32_t *kp_doff; uint64_t *kp_desc; int32_t *kp_ooff, *kp_okf; double *kp_oyx; int64_t *kp_id;
+    double *kf_Tcw;
+    double *mp_xyz; int32_t *mp_doff; uint64_t *mp_desc; int32_t *mp_ooff, *mp_okf; int64_t *mp_id;
+    int32_t *cell_off, *cell_kp, *cell_cur;
+    int32_t *best_kp; double *best_dist, *proj;
+    unsigned long long *keys;
+    int32_t *mark;                        // [S mcap] 1: the entry's point is in the local map
+    int32_t *cnt;                         // [S][2] N, M of the last staging (0, 0 unless status 0)
+    int32_t *status, *rn; int64_t *rpairs; double *rdist;        // results, one block: [S] | [S] | [S cap][2] | [S cap]
 };
 
 struct slam_kfmap {
@@ -60,4 +110,6 @@ struct slam_kfmap {
     struct Pending { int valid = 0, kfid = -1, P = 0, M = 0, O = 0; } pend[128];      // host copy of the pending windows' sizes
     // update's staging (theta, outlier flags, window table): a pinned block of the map's own with the event of the copy that last read it
     char *pin = nullptr; size_t pin_bytes = 0; hipEvent_t pin_ev = nullptr;
+    char *dbase = nullptr;                // the descriptor store
+    char *lm_base = nullptr; size_t lm_bytes = 0, lm_res_off = 0, lm_res_bytes = 0; KfmLm lm = {};        // the local-map staging (lm.max_local, lm.C1: what it was laid out for)
 };

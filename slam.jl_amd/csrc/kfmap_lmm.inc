@@ -1,0 +1,423 @@
+// kfmap_lmm.inc -- part of kfmap.hip: the descriptor store of the key-frame map and the device staging of the mapper's local-map match
+// (update_frame_covisibility! map_manager.jl:302-355 + match_local_map! / do_local_map_matching mapper.jl:265-383) from the map itself.  The stager
+// writes the packed buffer of k_lmm_match (lmm_host.hpp's regions, fixed per-stream strides: kfmap.hpp has the layout, its cost and the deviations),
+// the match kernel of localmap.hip runs on it unchanged (lmm_launch), a closing pass turns the keypoints' keys into id pairs.  Between the upload of the
+// call's arguments and the one copy of results nothing returns to the host.  tests/np_kfmap_local_map.py is the model.
+
+// ---- descriptors: slot-parallel, one thread per appended keypoint (grid.y = stream) ---------------------------------------------------------------------
+// row j of stream s belongs to id info[2 s] + j (slam_kpset_detect_describe); it is stored where the table entry carries that id
+__global__ __launch_bounds__(256) void k_kfm_desc_record(KfmapView V, const uint64_t *desc, const int64_t *info, int dcap, const int *sel)
+{
+    const int s = KFM_STREAM(blockIdx.y), j = blockIdx.x * 256 + threadIdx.x;
+    const int64_t n = info[2 * s + 1];
+    if (j >= dcap || (int64_t)j >= n) return;
+    const int64_t id = info[2 * s] + j;
+    const size_t pe = (size_t)s * V.mcap + kfm_entry(id, V.mcap);
+    if (V.ptag[pe] != (unsigned long long)id + 1ull) return;                    // a larger id holds the entry (or the id was never recorded): no point, no descriptor
+    const uint64_t *src = desc + 4 * ((size_t)s * dcap + j);
+    for (int k = 0; k < 4; k++) V.ddesc[4 * pe + k] = src[k];
+    V.dhas[pe] = 1;
+}
+
+// ---- staging: one 256-thread workgroup per stream, no workgroup waits for another ------------------------------------------------------------------------
+//   covisibility   kfm_covisibility over the newest key-frame's slab (the gather's and the filter's): nb_3d and the score of every other valid slot; the
+//                  covisible key-frames are the slots with a score
+//   mark           per covisible slab a pass over its live observations: the entry of an owned, 3-D point with a descriptor that the newest key-frame does
+//                  not observe is marked (every writer writes 1: the per-entry mark is the deduplication)
+//   local map      ascending by id: ids of one quotient id / mcap ascend with the entry, so the marked entries are emitted quotient by quotient, each an
+//                  ordered compaction over the table (ordered_slot); the quotients present are found by a minimum search (one LDS atomicMin per pass).  Few
+//                  quotients are alive at a time (ids are consecutive, the ring bounds a point's life)
+//   points         per local-map point its position, descriptor and observers (mask bits whose tag matches, ascending by key-frame id); the observer
+//                  offsets are a scan of the counts (kfm_scan)
+//   keypoints      ordered compaction of the newest slab's live observations whose point has a descriptor; per observer the pixel by binary search in that
+//                  slab (kfm_find_live), a missing or dead observation skipped (mapper.jl:429-434 without the clean-up)
+//   key-frames     row = rank of the slot by key-frame id; Tcw from theta by angles_to_pose
+//   cells          lmm_emit's stable counting sort: counts by global atomics of this workgroup alone, offsets by kfm_scan, then the keypoints in chunks of
+//                  256 in list order -- a keypoint's place is its cell's cursor plus the chunk's earlier keypoints of the same cell
+// status: 0 staged, 1 nothing to match (no key-frame, no covisible key-frame, an empty local map or keypoint list), 2 the local map exceeds max_local
+// (nothing of it is used).  A stream that is not staged gets M = 0 in its LmmStream row: every group of the match kernel leaves at once.
+__global__ __launch_bounds__(256) void k_kfm_lm_stage(KfmapView V, KfmLm Q, const KfmLmArg *args, const int *sel)
+{
+    __shared__ int s_cov[64], s_tag[64], s_rank[64], s_asc[64], s_w[4], s_cell[256], s_base, s_obase, s_nb3, s_nv;
+    __shared__ unsigned long long s_covmask, s_q;
+    const int z = blockIdx.x, s = sel[z], tid = threadIdx.x, R = V.R, cap = V.cap, mcap = V.mcap;
+    LmmStream &T = Q.st[z];
+    const KfmLmArg &A = args[s];
+    const size_t pb = (size_t)s * mcap;
+    const int kp0 = s * Q.N1, mp0 = s * Q.M1, kf0 = s * R, cell0 = s * Q.C1, kobs0 = s * Q.N1 * R, mobs0 = s * Q.M1 * R;
+#define KFM_LM_LEAVE(code) { if (tid == 0) { T.N = 0; T.M = 0; T.K = 0; Q.status[s] = (code); Q.rn[s] = 0; Q.cnt[2 * s] = 0; Q.cnt[2 * s + 1] = 0; } return; }
+    if (tid < 64) { s_cov[tid] = 0; s_rank[tid] = 0; s_asc[tid] = 0; s_tag[tid] = tid < R ? V.tag[s * R + tid] : 0; }
+    if (tid == 0) { s_base = 0; s_obase = 0; s_nb3 = 0; s_nv = 0; s_covmask = 0; }
+    __syncthreads();
+    const int kfid = V.cur[s] - 1;
+    if (kfid < 0) KFM_LM_LEAVE(1)                                               // (every branch that leaves is uniform over the workgroup)
+    const int r0 = kfid % R;
+    {
+        const int nb3 = kfm_covisibility(V, s, r0, s_tag, s_cov);
+        if (nb3) atomicAdd(&s_nb3, nb3);
+    }
+    __syncthreads();
+    if (tid == 0) {
+        unsigned long long cov = 0;
+        int nv = 0;
+        for (int b = 0; b < R; b++) {
+            if (!s_tag[b]) continue;
+            if (b != r0 && s_cov[b] > 0) cov |= 1ull << b;
+            int rank = 0;
+            for (int c = 0; c < R; c++) rank += s_tag[c] && s_tag[c] < s_tag[b];
+            s_rank[b] = rank; s_asc[rank] = b; nv++;
+        }
+        s_covmask = cov; s_nv = nv;
+    }
+    for (int e = tid; e < mcap; e += 256) Q.mark[pb + e] = 0;
+    __syncthreads();
+    const unsigned long long covmask = s_covmask;
+    const int nv = s_nv, nb3 = s_nb3;
+    if (covmask == 0) KFM_LM_LEAVE(1)
+    for (unsigned long long cm = covmask; cm; cm &= cm - 1) {
+        const int b = __ffsll((long long)cm) - 1, n = min(V.kn[s * R + b], cap);
+        const size_t sl = ((size_t)s * R + b) * cap;
+        for (int i = tid; i < n; i += 256) {
+            if (!V.klive[sl + i]) continue;
+            const int64_t id = V.kid[sl + i];
+            const size_t pe = pb + kfm_entry(id, mcap);
+            if (!kfm_valid(V, pe, id) || !(V.pflags[pe] & KFM_3D) || !V.dhas[pe] || (V.pmask[pe] >> r0 & 1)) continue;
+            Q.mark[pe] = 1;
+        }
+    }
+    __syncthreads();
+    // the local map, ascending by id
+    for (unsigned long long qlo = 0;;) {
+        if (tid == 0) s_q = ~0ull;
+        __syncthreads();
+        unsigned long long lmin = ~0ull;
+        for (int e = tid; e < mcap; e += 256)
+            if (Q.mark[pb + e]) { const unsigned long long q = (V.ptag[pb + e] - 1ull) / (unsigned long long)mcap; if (q >= qlo && q < lmin) lmin = q; }
+        if (lmin != ~0ull) atomicMin(&s_q, lmin);
+        __syncthreads();
+        const unsigned long long q = s_q;
+        if (q == ~0ull) break;
+        for (int e0 = 0; e0 < mcap; e0 += 256) {
+            const int e = e0 + tid;
+            const bool acc = e < mcap && Q.mark[pb + e] && (V.ptag[pb + e] - 1ull) / (unsigned long long)mcap == q;
+            const int pos = ordered_slot(acc, s_w, &s_base);                     // (its barriers also fence s_q: read above, reset below)
+            if (acc && pos < Q.max_local) Q.mp_id[mp0 + pos] = (int64_t)(V.ptag[pb + e] - 1ull);
+        }
+        qlo = q + 1ull;
+    }
+    const int M = s_base;
+    __syncthreads();
+    if (M > Q.max_local) KFM_LM_LEAVE(2)
+    if (M == 0) KFM_LM_LEAVE(1)
+    for (int m0 = 0; m0 < M; m0 += 256) {
+        const int m = m0 + tid;
+        unsigned long long wm = 0;
+        size_t pe = 0;
+        if (m < M) {
+            pe = pb + kfm_entry(Q.mp_id[mp0 + m], mcap);
+            for (unsigned long long mm = V.pmask[pe]; mm; mm &= mm - 1) { const int b = __ffsll((long long)mm) - 1; if (b < R && s_tag[b]) wm |= 1ull << b; }
+        }
+        const int off = kfm_scan(__popcll(wm), s_w, &s_obase);
+        if (m < M) {
+            const size_t g = (size_t)mp0 + m;
+            for (int k = 0; k < 3; k++) Q.mp_xyz[3 * g + k] = V.pxyz[3 * pe + k];
+            for (int k = 0; k < 4; k++) Q.mp_desc[4 * g + k] = V.ddesc[4 * pe + k];
+            Q.mp_doff[g] = (int32_t)g; Q.mp_ooff[g] = mobs0 + off;
+            int j = 0;
+            for (int k = 0; k < nv; k++) if (wm >> s_asc[k] & 1) Q.mp_okf[(size_t)mobs0 + off + j++] = k;
+        }
+    }
+    if (tid == 0) { Q.mp_doff[mp0 + M] = mp0 + M; Q.mp_ooff[mp0 + M] = mobs0 + s_obase; s_base = 0; s_obase = 0; }
+    __syncthreads();
+    // the keypoints: the newest slab, in slab order
+    {
+        const size_t sl = ((size_t)s * R + r0) * cap;
+        const int n0 = min(V.kn[s * R + r0], cap);
+        for (int c0 = 0; c0 < n0; c0 += 256) {
+            const int i = c0 + tid;
+            bool acc = false;
+            int64_t id = 0;
+            size_t pe = 0;
+            unsigned long long wm = 0;
+            if (i < n0 && V.klive[sl + i]) {
+                id = V.kid[sl + i]; pe = pb + kfm_entry(id, mcap);
+                acc = kfm_valid(V, pe, id) && V.dhas[pe];
+            }
+            if (acc)
+                for (unsigned long long mm = V.pmask[pe]; mm; mm &= mm - 1) {
+                    const int b = __ffsll((long long)mm) - 1;
+                    if (b < R && s_tag[b] && kfm_find_live(V, s, b, id) >= 0) wm |= 1ull << b;
+                }
+            const int pos = ordered_slot(acc, s_w, &s_base);
+            const int off = kfm_scan(__popcll(wm), s_w, &s_obase);
+            if (acc) {
+                const size_t g = (size_t)kp0 + pos;
+                Q.kp_id[g] = id; Q.kp_yx[2 * g] = V.kupx[2 * (sl + i)]; Q.kp_yx[2 * g + 1] = V.kupx[2 * (sl + i) + 1];
+                for (int k = 0; k < 4; k++) Q.kp_desc[4 * g + k] = V.ddesc[4 * pe + k];
+                Q.kp_doff[g] = (int32_t)g; Q.kp_ooff[g] = kobs0 + off;
+                size_t o = (size_t)kobs0 + off;
+                for (int k = 0; k < nv; k++) {
+                    const int b = s_asc[k];
+                    if (!(wm >> b & 1)) continue;
+                    const size_t qo = ((size_t)s * R + b) * cap + max(kfm_find_live(V, s, b, id), 0);      // (found: validated above)
+                    Q.kp_okf[o] = k; Q.kp_oyx[2 * o] = V.kupx[2 * qo]; Q.kp_oyx[2 * o + 1] = V.kupx[2 * qo + 1];
+                    o++;
+                }
+            }
+        }
+    }
+    const int N = s_base;
+    if (tid == 0) { Q.kp_doff[kp0 + N] = kp0 + N; Q.kp_ooff[kp0 + N] = kobs0 + s_obase; }
+    __syncthreads();
+    if (N == 0) KFM_LM_LEAVE(1)
+    if (tid < R && s_tag[tid]) {
+        double *K = Q.kf_Tcw + 16 * (size_t)(kf0 + s_rank[tid]);
+        angles_to_pose(V.ktheta + 6 * ((size_t)s * R + tid), K);
+        K[3] = 0.0; K[7] = 0.0; K[11] = 0.0; K[15] = 1.0;
+    }
+    // the cell lists (lmm_emit's counting sort)
+    const int cells = A.gr * A.gc;
+    int32_t *co = Q.cell_off + cell0, *cc = Q.cell_cur + cell0, *ck = Q.cell_kp + kp0;
+    auto cell_of = [&](int j) -> int {
+        const long long r = lmm_cell(Q.kp_yx[2 * ((size_t)kp0 + j)], A.cell), c = lmm_cell(Q.kp_yx[2 * ((size_t)kp0 + j) + 1], A.cell);
+        return r >= 1 && r <= A.gr && c >= 1 && c <= A.gc ? (int)((r - 1) * A.gc + (c - 1)) : -1;
+    };
+    for (int c = tid; c <= cells; c += 256) co[c] = 0;
+    if (tid == 0) s_obase = 0;
+    __syncthreads();
+    for (int j = tid; j < N; j += 256) { const int c = cell_of(j); if (c >= 0) atomicAdd(&co[c + 1], 1); }
+    __syncthreads();
+    for (int c0 = 0; c0 < cells; c0 += 256) {
+        const int c = c0 + tid, cnt = c < cells ? co[c + 1] : 0;
+        const int off = kfm_scan(cnt, s_w, &s_obase);
+        if (c < cells) { co[c + 1] = off + cnt; cc[c] = off; }
+    }
+    __syncthreads();
+    for (int c0 = 0; c0 < N; c0 += 256) {
+        const int j = c0 + tid, c = j < N ? cell_of(j) : -1;
+        s_cell[tid] = c;
+        __syncthreads();
+        if (c >= 0) {
+            int before = 0;
+            for (int k = 0; k < tid; k++) before += s_cell[k] == c;
+            ck[cc[c] + before] = j;
+        }
+        __syncthreads();
+        if (c >= 0) atomicAdd(&cc[c], 1);
+        __syncthreads();
+    }
+    if (tid == 0) {
+        angles_to_pose(V.ktheta + 6 * ((size_t)s * R + r0), T.Tcw);
+        T.Tcw[3] = 0.0; T.Tcw[7] = 0.0; T.Tcw[11] = 0.0; T.Tcw[15] = 1.0;
+        T.fx = A.cam[0]; T.fy = A.cam[1]; T.cx = A.cam[2]; T.cy = A.cam[3]; T.k1 = A.cam[4]; T.k2 = A.cam[5]; T.p1 = A.cam[6]; T.p2 = A.cam[7];
+        T.H = A.cam[8]; T.W = A.cam[9];
+        T.max_proj = nb3 < 30 ? A.max_proj * 2.0 : A.max_proj;                   // mapper.jl:332, nb_3d from the slab
+        T.start = A.start; T.view_thr = A.view_thr;
+        T.cell = A.cell; T.gr = A.gr; T.gc = A.gc;
+        T.N = N; T.M = M; T.K = nv; T.kp0 = kp0; T.kf0 = kf0; T.mp0 = mp0; T.cell0 = cell0;
+        Q.status[s] = 0; Q.cnt[2 * s] = N; Q.cnt[2 * s + 1] = M;
+    }
+#undef KFM_LM_LEAVE
+}
+
+// prev_new_map (mapper.jl:370-382) as id pairs: ordered compaction of the keypoints somebody chose, in list order = ascending keypoint id
+__global__ __launch_bounds__(256) void k_kfm_lm_pairs(KfmapView V, KfmLm Q, const int *sel)
+{
+    __shared__ int s_w[4], s_base;
+    const int s = sel[blockIdx.x], tid = threadIdx.x;
+    if (Q.status[s] != 0) return;                                               // (uniform; the stager has written rn = 0)
+    const int N = Q.cnt[2 * s], kp0 = s * Q.N1, mp0 = s * Q.M1;
+    if (tid == 0) s_base = 0;
+    __syncthreads();
+    for (int c0 = 0; c0 < N; c0 += 256) {
+        const int j = c0 + tid;
+        const unsigned long long key = j < N ? Q.keys[kp0 + j] : ~0ull;
+        const int m = lmm_decode(key);
+        const int pos = ordered_slot(m >= 0, s_w, &s_base);
+        if (m >= 0) {
+            const size_t o = (size_t)s * V.cap + pos;
+            Q.rpairs[2 * o] = Q.kp_id[kp0 + j]; Q.rpairs[2 * o + 1] = Q.mp_id[mp0 + m]; Q.rdist[o] = (double)(key >> 32);
+        }
+    }
+    if (tid == 0) Q.rn[s] = s_base;
+}
+
+// every region of the staging allocation, each named once (kfmap.hpp has the formula); the results last, one block
+static size_t kfmap_lm_regions(slam_kfmap *km, int max_local, int C1, char *base)
+{
+    Layout Lo;
+    auto region = [&](auto *&p, size_t bytes) { const size_t at = Lo.take(bytes); if (base) p = (std::remove_reference_t<decltype(p)>)(base + at); };
+    const KfmapView &v = km->v;
+    KfmLm &q = km->lm;
+    const size_t S = v.S, N1 = (size_t)v.cap + 1, M1 = (size_t)max_local + 1, n = S * N1, m = S * M1, R = v.R;
+    q.N1 = (int)N1; q.M1 = (int)M1; q.C1 = C1; q.max_local = max_local;
+    region(q.st, S * sizeof(LmmStream));
+    region(q.kp_yx, n * 16); region(q.kp_doff, n * 4); region(q.kp_desc, n * 32); region(q.kp_ooff, n * 4); region(q.kp_okf, n * R * 4); region(q.kp_oyx, n * R * 16);
+    region(q.kp_id, n * 8); region(q.kf_Tcw, S * R * 128);
+    region(q.mp_xyz, m * 24); region(q.mp_doff, m * 4); region(q.mp_desc, m * 32); region(q.mp_ooff, m * 4); region(q.mp_okf, m * R * 4); region(q.mp_id, m * 8);
+    region(q.cell_off, S * (size_t)C1 * 4); region(q.cell_kp, n * 4); region(q.cell_cur, S * (size_t)C1 * 4);
+    region(q.best_kp, m * 4); region(q.best_dist, m * 8); region(q.proj, m * 16); region(q.keys, n * 8);
+    region(q.mark, S * (size_t)v.mcap * 4); region(q.cnt, S * 8);
+    km->lm_res_off = Lo.size();
+    region(q.status, S * 4); region(q.rn, S * 4); region(q.rpairs, S * (size_t)v.cap * 16); region(q.rdist, S * (size_t)v.cap * 8);
+    km->lm_res_bytes = Lo.size() - km->lm_res_off;
+    return Lo.size();
+}
+
+extern "C" {
+
+int slam_kfmap_enable_descriptors(slam_ctx *ctx, slam_kfmap *km, int n_bits)
+{
+    ARG_TRY(ctx, ctx != nullptr && km != nullptr);
+    if (n_bits != 256) return slam_fail(ctx, SLAM_ERR_ARG, "slam_kfmap_enable_descriptors: n_bits = %d, the local-map match handles 256-bit descriptors only", n_bits);
+    if (km->dbase) return SLAM_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t m = (size_t)km->v.S * km->v.mcap;
+    Layout Lo;
+    const size_t o_desc = Lo.take(m * 32), o_has = Lo.take(m);
+    char *base = nullptr;
+    HIP_TRY(ctx, hipMalloc((void **)&base, Lo.size()));
+    hipError_t e = hipMemsetAsync(base, 0, Lo.size(), ctx->stream);
+    if (e == hipSuccess) e = slam_stream_wait(ctx->stream);
+    if (e != hipSuccess) { (void)hipFree(base); return slam_fail(ctx, SLAM_ERR_HIP, "slam_kfmap_enable_descriptors: %s", hipGetErrorString(e)); }
+    km->dbase = base; km->v.ddesc = (uint64_t *)(base + o_desc); km->v.dhas = (uint8_t *)(base + o_has);
+    return SLAM_OK;
+}
+
+int slam_kfmap_add_descriptors(slam_ctx *ctx, slam_kfmap *km, const uint64_t *desc_dev, const int64_t *info_dev, int dcap)
+{
+    ARG_TRY(ctx, ctx != nullptr && km != nullptr && desc_dev != nullptr && info_dev != nullptr && dcap >= 1);
+    if (!km->dbase) return slam_fail(ctx, SLAM_ERR_ARG, "slam_kfmap_add_descriptors: descriptors are not enabled (slam_kfmap_enable_descriptors)");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int list[128];
+    const int ns = kfmap_streams(km, list);
+    if (ns == 0) return SLAM_OK;
+    const int *sel = nullptr;
+    if (km->n_sel != KPSEL_ALL) {                                // the streams of the last add_keyframe, staged like the filter's table
+        char *scr, *h;
+        int rc = kfmap_pin(ctx, km, (size_t)ns * 4, &h);
+        if (rc) return rc;
+        rc = slam_scratch(ctx, (size_t)ns * 4, (void **)&scr);
+        if (rc) return rc;
+        memcpy(h, list, (size_t)ns * 4);
+        HIP_TRY(ctx, hipMemcpyAsync(scr, h, (size_t)ns * 4, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipEventRecord(km->pin_ev, ctx->stream));
+        sel = (const int *)scr;
+    }
+    { ProfScope span(ctx, "kfmap_add_descriptors");
+      hipLaunchKernelGGL(k_kfm_desc_record, dim3((dcap + 255) / 256, ns), dim3(256), 0, ctx->stream, km->v, desc_dev, info_dev, dcap, sel); }
+    HIP_TRY(ctx, hipGetLastError());
+    return SLAM_OK;
+}
+
+int slam_kfmap_local_map_match(slam_ctx *ctx, slam_kfmap *km, const double *cam, const int32_t *cell_size, const double *max_projection_distance,
+                               const double *max_descriptor_distance, int max_local, int32_t *status, int32_t *n_pairs, int64_t *pairs, double *dist,
+                               int cap_pairs)
+{
+    ARG_TRY(ctx, ctx != nullptr && km != nullptr && cam != nullptr && cell_size != nullptr && max_projection_distance != nullptr &&
+                     max_descriptor_distance != nullptr && status != nullptr && n_pairs != nullptr && max_local >= 1 && max_local <= (1 << 22) &&
+                     cap_pairs >= 0 && (cap_pairs == 0 || (pairs != nullptr && dist != nullptr)));
+    if (!km->dbase) return slam_fail(ctx, SLAM_ERR_ARG, "slam_kfmap_local_map_match: descriptors are not enabled (slam_kfmap_enable_descriptors)");
+    const KfmapView &V = km->v;
+    const int S = V.S;
+    std::vector<KfmLmArg> args((size_t)S);
+    int C1 = 2;
+    for (int s = 0; s < S; s++) {                                // every check, for every stream, before anything is enqueued
+        const double *c = cam + 10 * (size_t)s;
+        KfmLmArg &A = args[s];
+        if (c[4] != 0.0 || c[5] != 0.0 || c[6] != 0.0 || c[7] != 0.0)
+            return slam_fail(ctx, SLAM_ERR_ARG, "slam_kfmap_local_map_match: stream %d has lens distortion (%g %g %g %g); the map's pixels are undistorted", s, c[4], c[5], c[6], c[7]);
+        const double H = c[8], W = c[9];
+        const int cell = cell_size[s];
+        if (cell < 1 || !(H >= 1.0) || !(W >= 1.0) || H > 65536.0 || W > 65536.0 || !(c[0] > 0.0) || !(c[1] > 0.0))
+            return slam_fail(ctx, SLAM_ERR_ARG, "slam_kfmap_local_map_match: stream %d: cell_size %d / image %g x %g / focal lengths %g %g out of range", s, cell, H, W, c[0], c[1]);
+        memcpy(A.cam, c, sizeof A.cam);
+        A.max_proj = max_projection_distance[s];
+        A.start = 256.0 * max_descriptor_distance[s];                              // mapper.jl:401
+        const double vfov = 0.5 * H / c[1], hfov = 0.5 * W / c[0];                 // mapper.jl:326-329, as lmm_emit
+        A.view_thr = std::cos(vfov > hfov ? std::atan(vfov) : std::atan(hfov));
+        A.cell = cell; A.gr = (int)std::ceil(H / cell); A.gc = (int)std::ceil(W / cell); A.pad = 0;
+        if ((long long)A.gr * A.gc > (1 << 22)) return slam_fail(ctx, SLAM_ERR_ARG, "slam_kfmap_local_map_match: stream %d: a grid of %d x %d cells", s, A.gr, A.gc);
+        C1 = std::max(C1, A.gr * A.gc + 1);
+    }
+    if ((size_t)S * ((size_t)max_local + 1) * V.R >= ((size_t)1 << 31) || (size_t)S * ((size_t)V.cap + 1) * V.R >= ((size_t)1 << 31))
+        return slam_fail(ctx, SLAM_ERR_ARG, "slam_kfmap_local_map_match: S (max_local + 1) R or S (cap + 1) R exceeds 2^31");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int list[128];
+    const int ns = kfmap_streams(km, list);
+    for (int s = 0; s < S; s++) { status[s] = 1; n_pairs[s] = 0; }
+    if (ns == 0) return SLAM_OK;
+    if (!km->lm_base || km->lm.max_local < max_local || km->lm.C1 < C1) {          // (re)made for the larger of what it had and what is asked
+        const int ml = std::max(max_local, km->lm_base ? km->lm.max_local : 0), c1 = std::max(C1, km->lm_base ? km->lm.C1 : 0);
+        if (km->lm_base) { HIP_TRY(ctx, hipDeviceSynchronize()); (void)hipFree(km->lm_base); km->lm_base = nullptr; }
+        km->lm_bytes = kfmap_lm_regions(km, ml, c1, nullptr);
+        HIP_TRY(ctx, hipMalloc((void **)&km->lm_base, km->lm_bytes));
+        kfmap_lm_regions(km, ml, c1, km->lm_base);
+    }
+    KfmLm Q = km->lm;
+    Q.max_local = max_local;                                                       // the call's bound; the strides stay the allocation's
+    Layout D;
+    const auto o_sel = D.take<int>(S); const auto o_arg = D.take<KfmLmArg>(S); const size_t in_b = D.size();
+    const size_t o_res = D.take(km->lm_res_bytes);
+    char *scr, *h;
+    int rc = slam_scratch(ctx, in_b, (void **)&scr);
+    if (rc) return rc;
+    rc = slam_pinned(ctx, D.size(), (void **)&h);
+    if (rc) return rc;
+    memcpy(o_sel.at(h), list, (size_t)ns * 4); memcpy(o_arg.at(h), args.data(), o_arg.bytes());
+    LmmDev L;
+    L.st = Q.st; L.kp_yx = Q.kp_yx; L.kp_desc_off = Q.kp_doff; L.kp_desc = Q.kp_desc; L.kp_obs_off = Q.kp_ooff; L.kp_obs_kf = Q.kp_okf; L.kp_obs_yx = Q.kp_oyx;
+    L.kf_Tcw = Q.kf_Tcw; L.mp_xyz = Q.mp_xyz; L.mp_desc_off = Q.mp_doff; L.mp_desc = Q.mp_desc; L.mp_obs_off = Q.mp_ooff; L.mp_obs_kf = Q.mp_okf;
+    L.cell_off = Q.cell_off; L.cell_kp = Q.cell_kp; L.best_kp = Q.best_kp; L.best_dist = Q.best_dist; L.proj = Q.proj; L.keys = Q.keys;
+    const int *sel = o_sel.at(scr);
+    { ProfScope span(ctx, "kfmap_local_map_match");
+      HIP_TRY(ctx, hipMemcpyAsync(scr, h, in_b, hipMemcpyHostToDevice, ctx->stream));
+      HIP_TRY(ctx, hipMemsetAsync(Q.keys, 0xFF, (size_t)S * Q.N1 * 8, ctx->stream));
+      { ProfScope stage(ctx, "kfmap_lm_stage");
+        hipLaunchKernelGGL(k_kfm_lm_stage, dim3(ns), dim3(256), 0, ctx->stream, V, Q, (const KfmLmArg *)o_arg.at(scr), sel); }
+      lmm_launch(ctx, L, max_local, ns);
+      hipLaunchKernelGGL(k_kfm_lm_pairs, dim3(ns), dim3(256), 0, ctx->stream, V, Q, sel);
+      HIP_TRY(ctx, hipGetLastError());
+      HIP_TRY(ctx, hipMemcpyAsync(h + o_res, km->lm_base + km->lm_res_off, km->lm_res_bytes, hipMemcpyDeviceToHost, ctx->stream)); }
+    HIP_TRY(ctx, slam_stream_wait(ctx->stream));
+    const char *res = h + o_res;
+    const int32_t *st = (const int32_t *)(res + ((char *)Q.status - (km->lm_base + km->lm_res_off)));
+    const int32_t *rn = (const int32_t *)(res + ((char *)Q.rn - (km->lm_base + km->lm_res_off)));
+    const int64_t *rp = (const int64_t *)(res + ((char *)Q.rpairs - (km->lm_base + km->lm_res_off)));
+    const double *rd = (const double *)(res + ((char *)Q.rdist - (km->lm_base + km->lm_res_off)));
+    long long total = 0;
+    for (int k = 0; k < ns; k++) { const int s = list[k]; status[s] = st[s]; n_pairs[s] = st[s] == 0 ? rn[s] : 0; total += n_pairs[s]; }
+    if (total > cap_pairs) return slam_fail(ctx, SLAM_ERR_CAPACITY, "slam_kfmap_local_map_match: %lld pairs but cap_pairs = %d", total, cap_pairs);
+    size_t at = 0;
+    for (int k = 0; k < ns; k++) {
+        const int s = list[k], n = n_pairs[s];
+        if (n == 0) continue;
+        memcpy(pairs + 2 * at, rp + 2 * (size_t)s * V.cap, (size_t)n * 16); memcpy(dist + at, rd + (size_t)s * V.cap, (size_t)n * 8);
+        at += n;
+    }
+    return SLAM_OK;
+}
+
+// Test hook (not declared in slamhip.h): what the last slam_kfmap_local_map_match staged for stream s -- the local-map ids in order with the match
+// kernel's proj_yx, best_kp and best_dist, and the keypoint ids in order.  counts[0] = N, counts[1] = M (0, 0 unless the stream's status was 0).
+int slam_debug_kfmap_local_map(slam_ctx *ctx, slam_kfmap *km, int s, int64_t *lm_ids, double *proj_yx, int32_t *best_kp, double *best_dist, int64_t *kp_ids,
+                               int cap_lm, int cap_kp, int32_t *counts)
+{
+    ARG_TRY(ctx, ctx != nullptr && km != nullptr && s >= 0 && s < km->v.S && counts != nullptr && km->lm_base != nullptr);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const KfmLm &Q = km->lm;
+    HIP_TRY(ctx, hipMemcpyAsync(counts, Q.cnt + 2 * s, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, slam_stream_wait(ctx->stream));
+    const int N = counts[0], M = counts[1];
+    if (N > cap_kp || M > cap_lm) return slam_fail(ctx, SLAM_ERR_CAPACITY, "slam_debug_kfmap_local_map: %d keypoints, %d points, caps %d and %d", N, M, cap_kp, cap_lm);
+    const size_t kp0 = (size_t)s * Q.N1, mp0 = (size_t)s * Q.M1;
+    if (N > 0 && kp_ids) HIP_TRY(ctx, hipMemcpyAsync(kp_ids, Q.kp_id + kp0, (size_t)N * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (M > 0 && lm_ids) HIP_TRY(ctx, hipMemcpyAsync(lm_ids, Q.mp_id + mp0, (size_t)M * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (M > 0 && proj_yx) HIP_TRY(ctx, hipMemcpyAsync(proj_yx, Q.proj + 2 * mp0, (size_t)M * 16, hipMemcpyDeviceToHost, ctx->stream));
+    if (M > 0 && best_kp) HIP_TRY(ctx, hipMemcpyAsync(best_kp, Q.best_kp + mp0, (size_t)M * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (M > 0 && best_dist) HIP_TRY(ctx, hipMemcpyAsync(best_dist, Q.best_dist + mp0, (size_t)M * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, slam_stream_wait(ctx->stream));
+    return SLAM_OK;
+}
+
+}  // extern "C"

@@ -10,6 +10,13 @@
 #include <vector>
 #include "../../include/slamhip.h"
 
+// the two routines the device stager of the key-frame map (kfmap_lmm.inc) shares with this file compile for both sides under hipcc
+#if defined(__HIPCC__)
+#define LMM_HD __host__ __device__
+#else
+#define LMM_HD
+#endif
+
 // what the kernel reads per stream (one entry per stream that has both keypoints and local-map points)
 struct LmmStream {
     double Tcw[16];                               // frame.cw, column-major
@@ -21,6 +28,21 @@ struct LmmStream {
     int32_t N, M, K;
     int32_t kp0, kf0, mp0, cell0;                 // first keypoint / key-frame row / local-map point / cell_off entry of the stream
 };
+
+// the argument block of k_lmm_match (localmap.hip), by value: the regions of one packed buffer, wherever they were filled -- by lmm_emit on the host
+// (slam_local_map_match*) or on the device from the key-frame map (slam_kfmap_local_map_match, fixed per-stream strides)
+struct LmmDev {
+    const LmmStream *st;
+    const double *kp_yx; const int32_t *kp_desc_off; const uint64_t *kp_desc; const int32_t *kp_obs_off, *kp_obs_kf; const double *kp_obs_yx;
+    const double *kf_Tcw;
+    const double *mp_xyz; const int32_t *mp_desc_off; const uint64_t *mp_desc; const int32_t *mp_obs_off, *mp_obs_kf;
+    const int32_t *cell_off, *cell_kp;
+    int32_t *best_kp; double *best_dist, *proj;
+    unsigned long long *keys;
+};
+// the one launch of k_lmm_match<LMM_G> (localmap.hip): n_streams rows of D.st, every row's M <= max_M; enqueue-only, the caller checks hipGetLastError
+struct slam_ctx;
+void lmm_launch(slam_ctx *ctx, const LmmDev &D, int max_M, int n_streams);
 
 enum { LMM_ST, LMM_KP_YX, LMM_KP_DOFF, LMM_KP_DESC, LMM_KP_OOFF, LMM_KP_OKF, LMM_KP_OYX, LMM_KF, LMM_MP_XYZ, LMM_MP_DOFF, LMM_MP_DESC, LMM_MP_OOFF,
        LMM_MP_OKF, LMM_CELL_OFF, LMM_CELL_KP, LMM_IN_REGIONS,
@@ -46,7 +68,7 @@ static inline bool lmm_monotone(const int32_t *o, int n, std::string &err, const
 }
 
 // the cell of a pixel coordinate: round(p) ÷ cell_size + 1, round to nearest even, ÷ truncating (SLAM.jl:30,42-45)
-static inline long long lmm_cell(double p, int cell) { return (long long)std::rint(p) / cell + 1; }
+LMM_HD static inline long long lmm_cell(double p, int cell) { return (long long)rint(p) / cell + 1; }
 
 // Checks every argument the device would trust and lays the buffer out.  false: `err` says what is wrong, nothing may be launched.
 static inline bool lmm_plan(int S, const int32_t *kp_offsets, const int32_t *kf_offsets, const int32_t *mp_offsets, const slam_local_map_args *a,
@@ -147,4 +169,4 @@ static inline void lmm_emit(const LmmPlan &P, const int32_t *kp_offsets, const i
 }
 
 // key of the reverse selection -> local-map index (mapper.jl:370-381); all ones: nobody chose the keypoint
-static inline int32_t lmm_decode(uint64_t key) { return key == ~(uint64_t)0 ? -1 : (int32_t)(0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFu)); }
+LMM_HD static inline int32_t lmm_decode(uint64_t key) { return key == ~(uint64_t)0 ? -1 : (int32_t)(0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFu)); }

@@ -19,16 +19,6 @@
 #include "lmm_host.hpp"
 #include <cmath>
 
-struct LmmDev {
-    const LmmStream *st;
-    const double *kp_yx; const int32_t *kp_desc_off; const uint64_t *kp_desc; const int32_t *kp_obs_off, *kp_obs_kf; const double *kp_obs_yx;
-    const double *kf_Tcw;
-    const double *mp_xyz; const int32_t *mp_desc_off; const uint64_t *mp_desc; const int32_t *mp_obs_off, *mp_obs_kf;
-    const int32_t *cell_off, *cell_kp;
-    int32_t *best_kp; double *best_dist, *proj;
-    unsigned long long *keys;
-};
-
 // f.cw * to_homogeneous(point) (frame.jl:458-462): the first three rows, each summed left to right
 __device__ __forceinline__ void lmm_to_camera(const double *T, double X, double Y, double Z, double c[3])
 {
@@ -145,6 +135,13 @@ __global__ __launch_bounds__(256) void k_lmm_match(LmmDev D)
     }
 }
 
+void lmm_launch(slam_ctx *ctx, const LmmDev &D, int max_M, int n_streams)
+{
+    constexpr int per_block = 256 / LMM_G;
+    ProfScope kernel(ctx, "local_map_match_kernel");
+    hipLaunchKernelGGL(k_lmm_match<LMM_G>, dim3((max_M + per_block - 1) / per_block, (unsigned)n_streams), dim3(256), 0, ctx->stream, D);
+}
+
 static int lmm_run(slam_ctx *ctx, int S, const int32_t *kp_offsets, const int32_t *kf_offsets, const int32_t *mp_offsets, const slam_local_map_args *a)
 {
     ARG_TRY(ctx, ctx != nullptr);
@@ -171,12 +168,10 @@ static int lmm_run(slam_ctx *ctx, int S, const int32_t *kp_offsets, const int32_
     D.cell_off = (const int32_t *)(d + P.off[LMM_CELL_OFF]); D.cell_kp = (const int32_t *)(d + P.off[LMM_CELL_KP]);
     D.best_kp = (int32_t *)(d + P.off[LMM_BEST_KP]); D.best_dist = (double *)(d + P.off[LMM_BEST_DIST]); D.proj = (double *)(d + P.off[LMM_PROJ]);
     D.keys = (unsigned long long *)(d + P.off[LMM_KEYS]);
-    constexpr int per_block = 256 / LMM_G;
     { ProfScope span(ctx, "local_map_match");
       HIP_TRY(ctx, hipMemcpyAsync(d, h, P.in_bytes(), hipMemcpyHostToDevice, ctx->stream));
       HIP_TRY(ctx, hipMemsetAsync(d + P.off[LMM_KEYS], 0xFF, P.off[LMM_REGIONS] - P.off[LMM_KEYS], ctx->stream));
-      { ProfScope kernel(ctx, "local_map_match_kernel");
-        hipLaunchKernelGGL(k_lmm_match<LMM_G>, dim3((P.max_M + per_block - 1) / per_block, (unsigned)P.active.size()), dim3(256), 0, ctx->stream, D); }
+      lmm_launch(ctx, D, P.max_M, (int)P.active.size());
       HIP_TRY(ctx, hipGetLastError());
       HIP_TRY(ctx, hipMemcpyAsync(h + P.in_bytes(), d + P.in_bytes(), P.out_bytes(), hipMemcpyDeviceToHost, ctx->stream)); }
     HIP_TRY(ctx, slam_stream_wait(ctx->stream));

@@ -434,6 +434,23 @@ function newest(m::KeyframeMap)
     check(ccall((:slam_kfmap_newest, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int32}), ctx(), m.h, cur))
     cur
 end
+# update_frame_covisibility! + match_local_map! (map_manager.jl:302-355, mapper.jl:265-383) on the map: enable_descriptors! once; per key-frame, after
+# add_keyframe!, add_descriptors! with the device arrays slam_kpset_detect_describe filled (desc_dev: S x dcap x 4 UInt64, info_dev: S x 2 Int64), then
+# local_map_match -> (status, n_pairs, pairs 2 x n (keypoint id, local-map id), dist), the streams back to back.  cam: 10 x S, no lens distortion.
+enable_descriptors!(m::KeyframeMap, n_bits::Integer = 256) =
+    (check(ccall((:slam_kfmap_enable_descriptors, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint), ctx(), m.h, n_bits)); m)
+add_descriptors!(m::KeyframeMap, desc_dev::Ptr{UInt64}, info_dev::Ptr{Int64}, dcap::Integer) =
+    (check(ccall((:slam_kfmap_add_descriptors, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{UInt64}, Ptr{Int64}, Cint), ctx(), m.h, desc_dev, info_dev, dcap)); m)
+function local_map_match(m::KeyframeMap, cam::Matrix{Float64}, cell_size::Vector{Int32}, max_projection_distance::Vector{Float64},
+                         max_descriptor_distance::Vector{Float64}; max_local::Integer = 10 * m.cap, cap_pairs::Integer = m.S * m.cap)
+    status = zeros(Int32, m.S); n_pairs = zeros(Int32, m.S)
+    pairs = zeros(Int64, 2, max(cap_pairs, 1)); dist = zeros(Float64, max(cap_pairs, 1))
+    check(ccall((:slam_kfmap_local_map_match, LIB[]), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Cint, Ptr{Int32}, Ptr{Int32}, Ptr{Int64}, Ptr{Float64}, Cint),
+                ctx(), m.h, cam, cell_size, max_projection_distance, max_descriptor_distance, max_local, status, n_pairs, pairs, dist, cap_pairs))
+    n = sum(n_pairs)
+    (status = status, n_pairs = n_pairs, pairs = pairs[:, 1:n], dist = dist[1:n])
+end
 
 # ---- one live stream, one call per frame (slam_frontend_*, include/slamhip.h): what run!()'s front-end task does per frame
 # (front_end.jl:58-113, :454-470) and, at a key-frame, create_keyframe! + the mapper's stereo step (map_manager.jl:98-113, mapper.jl:51-66, :142-183),

@@ -167,6 +167,52 @@ class KeyframeMap:
         return dict(ids=ids[:k].copy(), xyz=xyz[:k].copy(), is_3d=(f & 1) != 0, observed=(f & 2) != 0, ba=(f & 4) != 0, gone=(f & 8) != 0,
                     observers=[tuple(int(v) for v in okf[off[j]:off[j + 1]]) for j in range(k)])
 
+    # ---- descriptors and the local-map match (slam_kfmap_enable_descriptors / _add_descriptors / _local_map_match) ----
+    def enable_descriptors(self, n_bits=256, ctx=None):
+        """Give every table entry a descriptor row (n_bits = 256, the only width the match handles).  Opt-in; a second call is a no-op."""
+        c = ctx or self.ctx
+        c.check(c.lib.slam_kfmap_enable_descriptors(c.h, self.h, int(n_bits)))
+
+    def add_descriptors(self, desc_ptr, info_ptr, dcap, ctx=None):
+        """Right after add_keyframe: the rows ks.detect_describe has just written (desc_ptr: device pointer to S x dcap x 4 uint64, info_ptr: device
+        pointer to S x 2 int64, e.g. torch_tensor.data_ptr()) go to the points of their ids, for the streams of that add_keyframe.  Enqueue-only."""
+        c = ctx or self.ctx
+        c.check(c.lib.slam_kfmap_add_descriptors(c.h, self.h, C.c_void_p(int(desc_ptr)), C.c_void_p(int(info_ptr)), int(dcap)))
+
+    def local_map_match(self, cam, cell_size, max_projection_distance, max_descriptor_distance, max_local=None, cap_pairs=None, ctx=None):
+        """update_frame_covisibility! + match_local_map! for the newest key-frames of the streams of the last add_keyframe, staged and matched in
+        HBM.  cam: (10,) or (S, 10) = fx fy cx cy k1 k2 p1 p2 height width (no lens distortion); cell_size and the two distances: one value or S.
+        max_local: the bound of a stream's local map (default 10 cap, the reference's 10 max_nb_keypoints).
+        -> (status (S,), pairs: per stream an (n, 2) int64 array of (keypoint id, local-map point id) ascending by keypoint id, dist: per stream
+        the (n,) winning descriptor distances).  status 0 matched, 1 nothing to match, 2 local map larger than max_local.  Synchronous."""
+        c = ctx or self.ctx
+        S = self.S
+        cam = np.ascontiguousarray(np.broadcast_to(np.asarray(cam, dtype=np.float64), (S, 10)))
+        cell = np.ascontiguousarray(np.broadcast_to(np.asarray(cell_size, dtype=np.int32), (S,)))
+        mpd = np.ascontiguousarray(np.broadcast_to(np.asarray(max_projection_distance, dtype=np.float64), (S,)))
+        mdd = np.ascontiguousarray(np.broadcast_to(np.asarray(max_descriptor_distance, dtype=np.float64), (S,)))
+        max_local = 10 * self.cap if max_local is None else int(max_local)
+        cap_pairs = S * self.cap if cap_pairs is None else int(cap_pairs)
+        status = np.zeros(S, dtype=np.int32); n = np.zeros(S, dtype=np.int32)
+        pairs = np.zeros((max(cap_pairs, 1), 2), dtype=np.int64); dist = np.zeros(max(cap_pairs, 1))
+        c.check(c.lib.slam_kfmap_local_map_match(c.h, self.h, L.ptr(cam), L.ptr(cell, L.i32p), L.ptr(mpd), L.ptr(mdd), max_local, L.ptr(status, L.i32p),
+                                                 L.ptr(n, L.i32p), L.ptr(pairs, L.i64p), L.ptr(dist), cap_pairs))
+        at = np.concatenate([[0], np.cumsum(n)])
+        return status, [pairs[at[s]:at[s + 1]].copy() for s in range(S)], [dist[at[s]:at[s + 1]].copy() for s in range(S)]
+
+    def debug_local_map(self, s, ctx=None):
+        """Test hook (slam_debug_kfmap_local_map, not part of the C header): what the last local_map_match staged for stream s ->
+        dict(lm_ids (M,), proj_yx (M, 2), best_kp (M,), best_dist (M,), kp_ids (N,)); empty arrays unless the stream's status was 0."""
+        c = ctx or self.ctx
+        fn = c.lib.slam_debug_kfmap_local_map
+        fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.c_void_p, C.c_int, L.i64p, L.f64p, L.i32p, L.f64p, L.i64p, C.c_int, C.c_int, L.i32p]
+        cap_lm = self.mcap                                       # a local map has at most one point per table entry
+        lm = np.zeros(cap_lm, dtype=np.int64); proj = np.zeros((cap_lm, 2)); bk = np.zeros(cap_lm, dtype=np.int32); bd = np.zeros(cap_lm)
+        kp = np.zeros(self.cap, dtype=np.int64); cnt = np.zeros(2, dtype=np.int32)
+        c.check(fn(c.h, self.h, int(s), L.ptr(lm, L.i64p), L.ptr(proj), L.ptr(bk, L.i32p), L.ptr(bd), L.ptr(kp, L.i64p), cap_lm, self.cap, L.ptr(cnt, L.i32p)))
+        N, M = int(cnt[0]), int(cnt[1])
+        return dict(lm_ids=lm[:M].copy(), proj_yx=proj[:M].copy(), best_kp=bk[:M].copy(), best_dist=bd[:M].copy(), kp_ids=kp[:N].copy())
+
     def reset(self, s, ctx=None):
         c = ctx or self.ctx
         c.check(c.lib.slam_kfmap_reset(c.h, self.h, int(s)))
