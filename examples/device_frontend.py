@@ -11,9 +11,10 @@ lock-stepped stereo streams with every keypoint list resident in HBM -- the call
     --local-ba: after every key-frame step KeyframeMap.add_keyframe -> gather -> bundle_adjustment_batch_ -> update(ks)   (local_bundle_adjustment!)
     --map-filtering: after update(ks) KeyframeMap.filter drops the redundant key-frames of the ring                          (map_filtering!)
     --local-map-match: key-frames detect WITH describe; after add_keyframe KeyframeMap.add_descriptors -> local_map_match     (update_frame_covisibility! + match_local_map!)
+    --merge: after local_map_match KeyframeMap.merge(ks) applies the match's pairs to the map and the lists, before the gather  (merge_matches)
 
 No host keypoint arrays anywhere; per frame the host receives S poses, S status words and S list lengths.  It is an
-array-level driver, not SLAM (no relocalisation, and the local-map match of --local-map-match is not followed by its merges): what it shows is that the seams compose -- on a rigid synthetic
+array-level driver, not SLAM (no relocalisation; the local-map match of --local-map-match is followed by its merges only with --merge): what it shows is that the seams compose -- on a rigid synthetic
 scene the poses it returns are the camera motion.
 
 With --local-ba the estimator's step runs too, on a key-frame map that lives in HBM beside the lists (slam_kfmap): every key-frame is recorded
@@ -28,7 +29,9 @@ With --map-filtering (requires --local-ba) the other half of the estimator's loo
 With --local-map-match (requires --local-ba) the mapper's last step before the estimator runs on the map too: the key-frame's new keypoints are
 described on the device (KeypointSet.detect_describe), their descriptors go into the map (add_descriptors), and the local map of every stream's newest
 key-frame -- the 3-D points of its covisible key-frames that it does not observe itself -- is staged and matched in HBM (local_map_match).  The pairs
-(keypoint id, local-map point id) are reported per stream; merging them (merge_mappoints) is not done: the map is left as it is.
+(keypoint id, local-map point id) are reported per stream.  With --merge (requires --local-map-match) the pairs are applied where they lie in HBM
+(KeyframeMap.merge: merge_matches -> merge_mappoints -> update_keypoint!) before the windows are gathered, and the per-stream counts are printed; on
+the rigid scene the match finds no pair, so the flag shows the wiring and that a call without pairs changes nothing.
 
 Key-frames are taken every `kf_every`-th frame, or, with --adaptive-keyframes, where the reference's rule asks for one
 (front_end.jl:361-393 on the statistics of the lists, one S x 8 read-back per frame).  The streams are lock-stepped -- every launch is
@@ -36,7 +39,7 @@ shared -- so --adaptive-keyframes alone takes a key-frame FOR ALL streams when A
 stream follow its own rule: the key-frame seams run under KeypointSet.selected(required), which restricts them to the streams that asked
 (slam_kpset_select), and the key-frame bookkeeping (last key-frame, its nb_3d_kpts, its pose, the observer ring, the key-frame id) is per stream.
 
-    python examples/device_frontend.py --frames 12 --streams 4 [--adaptive-keyframes | --per-stream-keyframes] [--local-ba [--map-filtering [--filter-from K]] [--local-map-match]]
+    python examples/device_frontend.py --frames 12 --streams 4 [--adaptive-keyframes | --per-stream-keyframes] [--local-ba [--map-filtering [--filter-from K]] [--local-map-match [--merge]]]
 """
 import argparse
 import contextlib
@@ -52,7 +55,7 @@ from slam_jl_amd import synthetic as syn  # noqa: E402
 
 
 def run(lefts, rights, cam, baseline, kf_every=4, max_keypoints=300, seed=0, ctx=None, verbose=False, adaptive=False, probe=None, per_stream=False, local_ba=False,
-        map_filtering=False, filter_from=20, map_probe=None, local_map_match=False):
+        map_filtering=False, filter_from=20, map_probe=None, local_map_match=False, merge=False):
     """lefts / rights: per stream a list of float images in [0, 1] (H, W).  Returns per frame a dict with the S poses
     (world -> camera, world = the first frame's camera), status words, list lengths and the wall time.
     adaptive: frame 0 is a key-frame; after the pose of every later frame the lists' statistics (KeypointSet.frame_stats, flags = 1) go
@@ -71,11 +74,15 @@ def run(lefts, rights, cam, baseline, kf_every=4, max_keypoints=300, seed=0, ctx
     before the update, ("filtered", km, removed) after the filter.
     local_map_match (needs local_ba): key-frames detect with describe, the descriptors follow the key-frame into the map, and before the gather
     KeyframeMap.local_map_match runs for the same streams; those rows carry `lmm`: (status (S,), pairs per stream, distances per stream).  map_probe
-    is also called with ("described", desc, info, dcap) -- the device tensors detect_describe filled -- and ("matched", km, status, pairs, dist)."""
+    is also called with ("described", desc, info, dcap) -- the device tensors detect_describe filled -- and ("matched", km, status, pairs, dist).
+    merge (needs local_map_match): behind the match KeyframeMap.merge(ks) applies its pairs, taken where the match left them on the device; those rows
+    carry `merged`: the (S, 4) counts (pairs applied, pairs skipped, observations renamed, status); map_probe is called with ("merged", km, counts)."""
     if map_filtering and not local_ba:
         raise ValueError("map_filtering needs local_ba: the filter works on the local BA's key-frame map")
     if local_map_match and not local_ba:
         raise ValueError("local_map_match needs local_ba: the match works on the local BA's key-frame map")
+    if merge and not local_map_match:
+        raise ValueError("merge needs local_map_match: it applies the match's pairs")
     adaptive = adaptive or per_stream
     import torch
     ctx = ctx or slam.default_context(0)
@@ -171,6 +178,9 @@ def run(lefts, rights, cam, baseline, kf_every=4, max_keypoints=300, seed=0, ctx
                         decision["lmm"] = km.local_map_match(cam10, ex.cell_size, params.max_projection_distance, params.max_descriptor_distance,
                                                              max_local=10 * max_keypoints, ctx=ctx)
                         notify(i, "matched", km, *decision["lmm"])
+                        if merge:                                           # merge_matches (mapper.jl:296-310): before the estimator reads the map
+                            decision["merged"] = km.merge(ks, ctx=ctx)
+                            notify(i, "merged", km, decision["merged"])
                     wins, _ = km.gather(params.min_cov_score, ctx=ctx)
                     if wins:
                         slam.bundle_adjustment_batch_([w.cache for w in wins], cam, ctx=ctx)
@@ -197,6 +207,8 @@ def run(lefts, rights, cam, baseline, kf_every=4, max_keypoints=300, seed=0, ctx
                 print(f"          local BA stream {s_}: window of {P_} poses, {M_} points, {O_} observations; {no_} outliers, ssr {e0_:.3f} -> {e1_:.3f}")
             if "lmm" in row:
                 print(f"          local-map match: status {row['lmm'][0].tolist()}, pairs per stream {[len(p) for p in row['lmm'][1]]}")
+            if "merged" in row:
+                print(f"          merge: pairs applied {row['merged'][:, 0].tolist()}, skipped {row['merged'][:, 1].tolist()}, observations renamed {row['merged'][:, 2].tolist()}")
             if "removed" in row:
                 print(f"          map filtering: removed key-frames {row['removed']}")
     n3 = [int(ks.download(s)["is_3d"].sum()) for s in range(S)]
@@ -226,6 +238,7 @@ def main():
     ap.add_argument("--local-ba", action="store_true", help="run the estimator's local BA after every key-frame step, on a key-frame map in HBM; the lists take the refined landmarks")
     ap.add_argument("--map-filtering", action="store_true", help="after every local BA drop the redundant key-frames of the map (map_filtering!); requires --local-ba")
     ap.add_argument("--local-map-match", action="store_true", help="describe the key-frames' new keypoints and match each stream's local map against them on the key-frame map (match_local_map!); requires --local-ba")
+    ap.add_argument("--merge", action="store_true", help="apply the local-map match's pairs to the map and the lists (merge_matches); requires --local-map-match")
     ap.add_argument("--filter-from", type=int, default=20, help="first key-frame id at which the filter acts (the reference's literal 20)")
     ap.add_argument("--replay-dir", default=None, help="write stream s's camera positions to DIR/stream_s as a ReplaySaver dump (src/io/saver.jl)")
     args = ap.parse_args()
@@ -233,10 +246,12 @@ def main():
         ap.error("--map-filtering requires --local-ba")
     if args.local_map_match and not args.local_ba:
         ap.error("--local-map-match requires --local-ba")
+    if args.merge and not args.local_map_match:
+        ap.error("--merge requires --local-map-match")
     cam, baseline, disparity = syn.KITTI_CAM, 0.54, 8.0
     lefts, rights, offs = synthetic_scene(args.streams, args.frames, disparity=disparity)
     out, n3 = run(lefts, rights, cam, baseline, verbose=True, adaptive=args.adaptive_keyframes, per_stream=args.per_stream_keyframes, local_ba=args.local_ba,
-                  map_filtering=args.map_filtering, filter_from=args.filter_from, local_map_match=args.local_map_match)
+                  map_filtering=args.map_filtering, filter_from=args.filter_from, local_map_match=args.local_map_match, merge=args.merge)
     Z = cam[0] * baseline / disparity
     for s in range(args.streams):
         o = offs[s][-1] - offs[s][0]
@@ -248,6 +263,8 @@ def main():
             print(f"stream {s}: {n_win} local-BA windows solved, motion error {np.abs(got - want).max():.4f} m")
         if args.local_map_match:
             print(f"stream {s}: local-map match found {sum(len(r['lmm'][1][s]) for r in out if 'lmm' in r)} pairs over {sum(1 for r in out if 'lmm' in r)} key-frames")
+        if args.merge:
+            print(f"stream {s}: merge applied {sum(int(r['merged'][s, 0]) for r in out if 'merged' in r)} pairs, renamed {sum(int(r['merged'][s, 2]) for r in out if 'merged' in r)} observations")
         if args.map_filtering:
             print(f"stream {s}: map filtering removed key-frames {sorted(k for r in out for k in r.get('removed', [[]] * args.streams)[s])}")
     if args.replay_dir:

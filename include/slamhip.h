@@ -517,7 +517,7 @@ int slam_kfmap_reset(slam_ctx *ctx, slam_kfmap *km, int s);
  * local-map match handles) and a "has descriptor" byte per table entry, 33 mcap bytes per stream in an allocation of their own.  The row of
  * point `id` lives at entry id % mcap under the table's ownership rule; a point replaced by a larger id loses its descriptor with its entry.
  * ONE descriptor per point is the whole of keyframes_descriptors here: map_manager.jl:116-131 describes only the keypoints a key-frame has just
- * extracted; further rows would come from merges, which the map does not apply.  Enabling twice is a no-op. */
+ * extracted; further rows would come from merges, and slam_kfmap_merge keeps one row per point.  Enabling twice is a no-op. */
 int slam_kfmap_enable_descriptors(slam_ctx *ctx, slam_kfmap *km, int n_bits);
 /* Right after slam_kfmap_add_keyframe, with the arrays slam_kpset_detect_describe has just filled (desc_dev: S x dcap x 4 words, info_dev:
  * S x 2 int64, both in HBM): row j of stream s goes to the entry of id info_dev[2 s] + j where that entry carries the id.  Acts on the streams
@@ -537,7 +537,7 @@ int slam_kfmap_add_descriptors(slam_ctx *ctx, slam_kfmap *km, const uint64_t *de
  * match (not acted on, no covisible key-frame, an empty local map or keypoint list); 2 the local map exceeds max_local -- nothing is matched for
  * that stream, the others are unaffected.  Result: the reference's prev_new_map (mapper.jl:370-382) as pairs (keypoint id, local-map point id),
  * ascending by keypoint id, the streams back to back in stream order (n_pairs[s] each), with the winning descriptor distance; more than
- * cap_pairs pairs in all is a capacity error.  The call changes NOTHING in the map: merge_mappoints is the caller's.
+ * cap_pairs pairs in all is a capacity error.  The call changes NOTHING in the map: slam_kfmap_merge applies the pairs.
  * Deviations: the slabs hold undistorted pixels while find_best_match uses kp.pixel, so non-zero k1, k2, p1, p2 of any stream is an argument
  * error (as is a map without descriptors), nothing is launched; frame.local_map_ids is not kept between key-frames (no replace-or-union rule
  * map_manager.jl:350-354, no union with the oldest covisible key-frame's local map mapper.jl:274-286); no remove_mappoint_obs! clean-ups; a
@@ -547,6 +547,35 @@ int slam_kfmap_local_map_match(slam_ctx *ctx, slam_kfmap *km, const double *cam 
                                const double *max_projection_distance, const double *max_descriptor_distance, int max_local,
                                int32_t *status /* S */, int32_t *n_pairs /* S */, int64_t *pairs /* cap_pairs x 2: keypoint id, local-map id */,
                                double *dist, int cap_pairs);
+/* merge_matches -> merge_mappoints -> update_keypoint! (mapper.jl:296-310, map_manager.jl:378-427, frame.jl:290-307) on the map: the pairs
+ * (prev_id, new_id) = (keypoint of the newest key-frame, local-map point) of a local-map match are applied in HBM, with no host round trip between
+ * match and merge.  n_pairs == NULL takes the result block of the last slam_kfmap_local_map_match where it lies in HBM (a stream whose status
+ * was not 0 has no pairs; a block is consumed once); otherwise n_pairs[s] pairs per stream, the streams back to back in `pairs`, are uploaded
+ * through the map's pinned block.  The call acts only on the streams that have pairs.  Per stream and pair:
+ *   validity    skipped, nothing changed, unless both ids own their table entries (not removed), prev_id != new_id and the new point is 3-D;
+ *   observers   in every key-frame of prev's observers whose slab holds a live observation of prev_id and none of new_id, that observation's
+ *               id becomes new_id (pixel and live byte kept) and the new point gains the observer; a slab that holds both is left as it is
+ *               (has_new: the prev observation stays, an orphan);
+ *   order       every touched slab holds unique ascending ids again: the renamed record moves to its place, a tombstone whose id equals an
+ *               arriving new_id is dropped, other tombstones stay; a slab never grows;
+ *   points      prev's entry is removed as by pop!(map_points, prev_id) -- NOT remove_mappoint!: observations that were not renamed stay in their
+ *               slabs; the new point is `observed` if the newest key-frame's slab was renamed to it; its position and `ba` are untouched;
+ *   live list   (ks != NULL) a list that carries prev_id and not new_id: the slot takes new_id, is_3d = 1 and the new point's position in the map,
+ *               every other field of the record travels with it, the list is re-ordered so that ids ascend, its count is unchanged;
+ *   ks == NULL  prev's entry is also marked `gone`: later lists that still carry prev_id are not recorded as a fresh point.
+ * The pairs of a stream must be one-to-one (no prev id twice, no new id twice, no id on both sides of two pairs): the merges then commute.  A
+ * stream that has pairs and a pending local-BA window (the reference merges under optimization_lock), host pairs that are not one-to-one,
+ * more than cap pairs for a stream, and n_pairs == NULL on a map without descriptors or without a match are argument errors: nothing is
+ * enqueued for any stream.  Device pairs that are not one-to-one are reported in the status word, that stream unchanged.
+ * merged (nullable) [S x 4]: pairs applied, pairs skipped, observations renamed in key-frames, status (0; 1 not one-to-one); zeros for a
+ * stream without pairs.  merged == NULL: enqueue-only; else one copy and one wait more.
+ * Deviations: add_covisibility! has no counterpart (covisibility is derived from the observer masks); the map keeps ONE descriptor row per
+ * point, so the new point keeps its own and prev's row goes with prev (the reference appends prev's rows to keyframes_descriptors and
+ * mappoint_min_distance takes the minimum over all of them); the `gone` mark of ks == NULL.  Memory: a scratch allocation made by the first
+ * call that has pairs -- per slab and per list the rename list and the rebuild's plan (28 bytes a record), a scratch slab per (stream, slot)
+ * (25 bytes a record), a scratch record array per list (103 bytes a record): about (53 R + 132) cap bytes per stream. */
+int slam_kfmap_merge(slam_ctx *ctx, slam_kfmap *km, slam_kpset *ks /* nullable */, const int32_t *n_pairs /* S, or NULL */,
+                     const int64_t *pairs /* x 2, streams back to back, or NULL */, int32_t *merged /* nullable, S x 4 */);
 
 /* ---- one live stream, one call per frame (round 6) -----------------------------------------------------------------------------------
  * What run!() does per frame (src/front_end.jl:58-113: preprocess! :454-470 = copy!(previous_pyramid, current_pyramid) + update!,

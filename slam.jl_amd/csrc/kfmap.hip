@@ -5,6 +5,8 @@
 // slam_kfmap_filter is map_filtering! (src/estimator.jl:358-406) on the same map, slam_kfmap_remove_keyframe the remove_keyframe! it calls
 // (src/map_manager.jl:184-209); tests/np_kfmap_filter.py is their model.  The descriptor store and slam_kfmap_local_map_match (update_frame_covisibility! +
 // match_local_map!, staged on the device for localmap.hip's match kernel) are in kfmap_lmm.inc, included at the end: they use the routines below.
+// slam_kfmap_merge (merge_matches -> merge_mappoints -> update_keypoint!: the match's pairs applied in HBM, the touched slabs and lists rebuilt in id
+// order) is in kfmap_merge.inc, included behind it.
 //
 // Every kernel takes `sel`: nullptr = workgroup (or grid row) b works on stream b, else on stream sel[b] -- launches are sized by the number of streams
 // acted on, so nothing of any other stream is read or written.
@@ -548,6 +550,7 @@ int slam_kfmap_destroy(slam_kfmap *km)
     if (km->pin) (void)hipHostFree(km->pin);
     if (km->dbase) (void)hipFree(km->dbase);
     if (km->lm_base) (void)hipFree(km->lm_base);
+    if (km->mg_base) (void)hipFree(km->mg_base);
     if (km->pin_ev) (void)hipEventDestroy(km->pin_ev);
     delete km;
     return SLAM_OK;
@@ -833,10 +836,11 @@ int slam_kfmap_reset(slam_ctx *ctx, slam_kfmap *km, int s)
     HIP_TRY(ctx, hipMemsetAsync(V.cur + s, 0, 4, ctx->stream));
     if (V.dhas) HIP_TRY(ctx, hipMemsetAsync(V.dhas + (size_t)s * V.mcap, 0, (size_t)V.mcap, ctx->stream));
     HIP_TRY(ctx, hipMemsetAsync(V.whdr + (size_t)s * KFM_HDR, 0, KFM_HDR * 4, ctx->stream));
-    km->pend[s].valid = 0;
+    km->pend[s].valid = 0; km->lm_np[s] = 0;
     return SLAM_OK;
 }
 
 }  // extern "C"
 
 #include "kfmap_lmm.inc"
+#include "kfmap_merge.inc"

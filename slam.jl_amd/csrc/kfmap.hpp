@@ -23,7 +23,8 @@
 // 33 mcap bytes per stream.  The row of point `id` lives at entry id % mcap under the table's ownership rule: slam_kfmap_add_descriptors writes it only
 // where the entry carries that id, and an entry that changes owner (a larger id claims it, or a removed id is recorded anew) loses the byte with the point.
 // ONE descriptor per point is the whole of the reference's keyframes_descriptors here: map_manager.jl:116-131 describes only the keypoints a key-frame
-// has just extracted, and further rows would come from merges (merge_mappoints), which this map does not apply.
+// has just extracted, and further rows would come from merges: slam_kfmap_merge keeps the new point's own row and lets prev's row go with prev (the
+// reference appends prev's rows to keyframes_descriptors, and mappoint_min_distance takes the minimum over all of them).
 //
 // Local-map staging (slam_kfmap_local_map_match, kfmap_lmm.inc; a third allocation, made by the first call and re-made when max_local or the grid grows):
 // the packed buffer of k_lmm_match (lmm_host.hpp) with FIXED per-stream strides -- no count pass, no scan over the streams, hence no host round trip between
@@ -43,9 +44,26 @@
 //   persistence   frame.local_map_ids is not kept between key-frames: neither the replace-or-union rule (map_manager.jl:350-354) nor the union with the
 //                 oldest covisible key-frame's local map (mapper.jl:274-286) is modelled; the local map is what this key-frame's covisibility pass yields
 //   clean-ups     no remove_mappoint_obs! clean-ups (mapper.jl:412, :429-434), as in the array form: a missing or dead observation is skipped
-//   merges        merge_mappoints is not applied: the call reports pairs and changes nothing in the map
+//   merges        the call reports pairs and changes nothing in the map: slam_kfmap_merge (below) applies them
 //   order         the local map is walked ascending by id (the reference iterates a Set); among equal distances the larger local-map index wins
 //   grid          a keypoint whose pixel lies in no cell of the grid is in no cell list (the array form rejects such a call)
+//
+// Merge scratch (slam_kfmap_merge, kfmap_merge.inc; a fourth allocation, made by the first merge call that has pairs): merge_matches -> merge_mappoints ->
+// update_keypoint! (mapper.jl:296-310, map_manager.jl:378-427, frame.jl:290-307) renames a keypoint in every key-frame that observes it, and every slab
+// and live list is sorted by id, so the touched slabs and lists are rebuilt in order through scratch.  With Z = S (R + 1) (a stream's R slabs, then its
+// list), n = S R cap, l = S cap, each region rounded up to 256:
+//   renames   count 4 Z | position 4 Z cap | new id 8 Z cap | new ids ascending 8 Z cap | rank by position 4 Z cap | kept before 4 Z (cap + 1)
+//   slabs     ids 8 n | upx 16 n | live n
+//   pairs     applied l | counts 16 S
+//   lists     yx, stereo yx, key-frame yx, first yx 16 l each | xyz 24 l | id 8 l | is3d, stereo, haskf l each | first key-frame 4 l
+// i.e. about (53 R + 132) cap bytes per stream (cap 1 400, R 32: 2.6 MB; S = 128: 330 MB).  The main allocation's layout is untouched.
+// slam_kfmap_merge against the reference (the first three are deviations, the last two the reference's own rules as they show in slabs):
+//   covisibility  add_covisibility! has no counterpart: covisibility is derived from the observer masks (as for the filter's remove_covisible_kf!)
+//   descriptors   one row per point: new keeps its own, prev's goes with prev (above)
+//   gone          without a keypoint set (ks == NULL) prev's entry is also marked KFM_GONE, so that later lists that still carry prev_id are not
+//                 recorded as a fresh point (the reference always has the current frame at hand)
+//   orphans       pop!(map_points, prev_id) is not remove_mappoint!: where a slab holds both ids (has_new) prev's observation stays, alive, without a point
+//   tombstones    a tombstone whose id equals an arriving new_id is dropped from the slab (a lower bound must not land on it); the slab shrinks by one
 #pragma once
 #include "kpset.hpp"
 #include "lmm_host.hpp"
@@ -101,6 +119,17 @@ struct KfmLm {
     int32_t *status, *rn; int64_t *rpairs; double *rdist;        // results, one block: [S] | [S] | [S cap][2] | [S cap]
 };
 
+// slam_kfmap_merge's scratch allocation (kfmap_merge.inc), by value to its kernels; Z = S (R + 1): a stream's R slabs, then its list
+struct KfmMerge {
+    int *cnt;                             // [Z] renames of the slab / list
+    int *rn_pos; int64_t *rn_id, *rs_id; int *rank_at, *kept;   // [Z cap] ([Z (cap + 1)]: kept) KfmRename's regions
+    int64_t *t_id; double *t_upx; uint8_t *t_live;              // [S R cap] the scratch slabs
+    uint8_t *applied;                     // [S cap] per pair: 1 applied
+    int32_t *stat;                        // [S][4] pairs applied, pairs skipped, observations renamed, status (1: the pairs are not one-to-one)
+    // the scratch record array of the lists [S cap]: every field k_kpset_compact carries
+    double *q_yx, *q_syx, *q_xyz, *q_kyx, *q_fyx; int64_t *q_id; uint8_t *q_is3d, *q_stereo, *q_haskf; int *q_fkf;
+};
+
 struct slam_kfmap {
     int device = 0;
     char *base = nullptr; size_t bytes = 0;
@@ -112,4 +141,6 @@ struct slam_kfmap {
     char *pin = nullptr; size_t pin_bytes = 0; hipEvent_t pin_ev = nullptr;
     char *dbase = nullptr;                // the descriptor store
     char *lm_base = nullptr; size_t lm_bytes = 0, lm_res_off = 0, lm_res_bytes = 0; KfmLm lm = {};        // the local-map staging (lm.max_local, lm.C1: what it was laid out for)
+    int lm_np[128] = {};                  // pairs per stream in the result block of the last local-map match, until a merge has consumed them
+    char *mg_base = nullptr; size_t mg_bytes = 0; KfmMerge mg = {};       // the merge's scratch
 };

@@ -345,7 +345,7 @@ int slam_kfmap_local_map_match(slam_ctx *ctx, slam_kfmap *km, const double *cam,
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     int list[128];
     const int ns = kfmap_streams(km, list);
-    for (int s = 0; s < S; s++) { status[s] = 1; n_pairs[s] = 0; }
+    for (int s = 0; s < S; s++) { status[s] = 1; n_pairs[s] = 0; km->lm_np[s] = 0; }
     if (ns == 0) return SLAM_OK;
     if (!km->lm_base || km->lm.max_local < max_local || km->lm.C1 < C1) {          // (re)made for the larger of what it had and what is asked
         const int ml = std::max(max_local, km->lm_base ? km->lm.max_local : 0), c1 = std::max(C1, km->lm_base ? km->lm.C1 : 0);
@@ -386,7 +386,7 @@ int slam_kfmap_local_map_match(slam_ctx *ctx, slam_kfmap *km, const double *cam,
     const int64_t *rp = (const int64_t *)(res + ((char *)Q.rpairs - (km->lm_base + km->lm_res_off)));
     const double *rd = (const double *)(res + ((char *)Q.rdist - (km->lm_base + km->lm_res_off)));
     long long total = 0;
-    for (int k = 0; k < ns; k++) { const int s = list[k]; status[s] = st[s]; n_pairs[s] = st[s] == 0 ? rn[s] : 0; total += n_pairs[s]; }
+    for (int k = 0; k < ns; k++) { const int s = list[k]; status[s] = st[s]; n_pairs[s] = st[s] == 0 ? rn[s] : 0; total += n_pairs[s]; km->lm_np[s] = n_pairs[s]; }
     if (total > cap_pairs) return slam_fail(ctx, SLAM_ERR_CAPACITY, "slam_kfmap_local_map_match: %lld pairs but cap_pairs = %d", total, cap_pairs);
     size_t at = 0;
     for (int k = 0; k < ns; k++) {

@@ -451,6 +451,17 @@ function local_map_match(m::KeyframeMap, cam::Matrix{Float64}, cell_size::Vector
     n = sum(n_pairs)
     (status = status, n_pairs = n_pairs, pairs = pairs[:, 1:n], dist = dist[1:n])
 end
+# merge_matches (mapper.jl:296-310) on the map: the pairs of the last local_map_match where they lie in HBM (n_pairs === nothing), or the caller's
+# (n_pairs: S counts, pairs: 2 x n (prev id, new id), the streams back to back).  k: the KeypointSet whose live lists follow.  Returns the 4 x S counts
+# (pairs applied, pairs skipped, observations renamed, status), or nothing with want_counts = false (enqueue-only).
+function merge!(m::KeyframeMap, k::Union{Nothing, KeypointSet} = nothing; n_pairs::Union{Nothing, Vector{Int32}} = nothing,
+                pairs::Union{Nothing, Matrix{Int64}} = nothing, want_counts::Bool = true)
+    merged = zeros(Int32, 4, m.S)
+    GC.@preserve n_pairs pairs merged check(ccall((:slam_kfmap_merge, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int32}, Ptr{Int64}, Ptr{Int32}),
+        ctx(), m.h, k === nothing ? C_NULL : k.h, n_pairs === nothing ? Ptr{Int32}(C_NULL) : pointer(n_pairs),
+        pairs === nothing ? Ptr{Int64}(C_NULL) : pointer(pairs), want_counts ? pointer(merged) : Ptr{Int32}(C_NULL)))
+    want_counts ? merged : nothing
+end
 
 # ---- one live stream, one call per frame (slam_frontend_*, include/slamhip.h): what run!()'s front-end task does per frame
 # (front_end.jl:58-113, :454-470) and, at a key-frame, create_keyframe! + the mapper's stereo step (map_manager.jl:98-113, mapper.jl:51-66, :142-183),

@@ -200,6 +200,27 @@ class KeyframeMap:
         at = np.concatenate([[0], np.cumsum(n)])
         return status, [pairs[at[s]:at[s + 1]].copy() for s in range(S)], [dist[at[s]:at[s + 1]].copy() for s in range(S)]
 
+    def merge(self, ks=None, pairs=None, want_counts=True, ctx=None):
+        """merge_matches -> merge_mappoints -> update_keypoint! (src/mapper.jl:296-310, src/map_manager.jl:378-427, src/frame.jl:290-307): the pairs
+        (keypoint id, local-map point id) are applied in HBM -- the keypoint is renamed in every key-frame that observes it, the touched slabs are put
+        back in id order, the old point leaves the table.  pairs=None: the result of the last local_map_match where it lies on the device; else a list
+        of S (n, 2) int64 arrays (one-to-one per stream).  ks: the KeypointSet whose live lists follow the renames (without one the old ids are marked
+        gone).  -> (S, 4) int32: pairs applied, pairs skipped, observations renamed, status per stream (synchronous), or None with
+        want_counts=False (enqueue-only)."""
+        c = ctx or self.ctx
+        S = self.S
+        n_ptr = p_ptr = None
+        if pairs is not None:
+            if len(pairs) != S:
+                raise ValueError(f"merge: {len(pairs)} pair arrays for {S} streams")
+            per = [np.asarray(p, dtype=np.int64).reshape(-1, 2) for p in pairs]
+            n = np.ascontiguousarray([len(p) for p in per], dtype=np.int32)
+            flat = np.ascontiguousarray(np.concatenate(per + [np.zeros((1, 2), dtype=np.int64)]))
+            n_ptr, p_ptr = L.ptr(n, L.i32p), L.ptr(flat, L.i64p)
+        merged = np.zeros((S, 4), dtype=np.int32) if want_counts else None
+        c.check(c.lib.slam_kfmap_merge(c.h, self.h, ks.h if ks is not None else None, n_ptr, p_ptr, L.ptr(merged, L.i32p) if want_counts else None))
+        return merged
+
     def debug_local_map(self, s, ctx=None):
         """Test hook (slam_debug_kfmap_local_map, not part of the C header): what the last local_map_match staged for stream s ->
         dict(lm_ids (M,), proj_yx (M, 2), best_kp (M,), best_dist (M,), kp_ids (N,)); empty arrays unless the stream's status was 0."""
