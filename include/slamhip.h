@@ -539,14 +539,29 @@ int slam_kfmap_add_descriptors(slam_ctx *ctx, slam_kfmap *km, const uint64_t *de
  * ascending by keypoint id, the streams back to back in stream order (n_pairs[s] each), with the winning descriptor distance; more than
  * cap_pairs pairs in all is a capacity error.  The call changes NOTHING in the map: slam_kfmap_merge applies the pairs.
  * Deviations: the slabs hold undistorted pixels while find_best_match uses kp.pixel, so non-zero k1, k2, p1, p2 of any stream is an argument
- * error (as is a map without descriptors), nothing is launched; frame.local_map_ids is not kept between key-frames (no replace-or-union rule
- * map_manager.jl:350-354, no union with the oldest covisible key-frame's local map mapper.jl:274-286); no remove_mappoint_obs! clean-ups; a
+ * error (as is a map without descriptors), nothing is launched; frame.local_map_ids is kept between key-frames only after
+ * slam_kfmap_enable_local_map_history (below); no remove_mappoint_obs! clean-ups; a
  * keypoint outside the cell grid is in no cell.  Memory: a staging allocation with fixed per-stream strides, about cap (100 + 20 R) +
  * max_local (100 + 4 R) + 4 mcap bytes per stream, made by the first call.  Synchronous. */
 int slam_kfmap_local_map_match(slam_ctx *ctx, slam_kfmap *km, const double *cam /* S x 10 */, const int32_t *cell_size,
                                const double *max_projection_distance, const double *max_descriptor_distance, int max_local,
                                int32_t *status /* S */, int32_t *n_pairs /* S */, int64_t *pairs /* cap_pairs x 2: keypoint id, local-map id */,
                                double *dist, int cap_pairs);
+/* The local-map history: frame.local_map_ids of every key-frame of the ring, kept in HBM between key-frames.  Opt-in, ONE allocation of about
+ * R mcap / 8 + 8 mcap bytes per stream (a bitset over the table's entries per ring slot, the key-frame each set belongs to, a copy of the table's
+ * tags as of the stream's last match); a second call is a no-op.  From then on slam_kfmap_local_map_match, for the newest key-frame K of every
+ * stream it acts on: (0) drops from the stream's stored sets every id whose table entry another id has taken; (1) forms C, the local map of K's
+ * covisibility pass (what the call yields without history; empty without a covisible key-frame); (2) map_manager.jl:350-354: with P the set stored
+ * for K (empty unless the match already ran for K), L = C if |C| > 0.5 |P|, else P + C; (3) mapper.jl:274-286: if a key-frame is covisible and
+ * |L| < max_local, L takes in the set stored for the covisible key-frame of the smallest id, if one was stored for it; (4) stores L as K's set,
+ * whatever the status; (5) stages the ids of L that pass the match's gates now (alive, 3-D, described, not observed by K), ascending: more than
+ * max_local is status 2, none status 1.  A stored set holds ids that passed the gates when they were stored (the reference stores raw ids and gates
+ * at match time).  Sets grow along the chain: max_local >= mcap rules status 2 out.  slam_kfmap_merge leaves the sets alone; slam_kfmap_reset clears
+ * the stream's.  A map that never makes this call behaves exactly as before. */
+int slam_kfmap_enable_local_map_history(slam_ctx *ctx, slam_kfmap *km);
+/* The set stored for key-frame kfid of stream s, ascending (n_ids of them).  kfid not in the ring, or no set stored for it (its match was
+ * skipped): an argument error; more than cap_ids: a capacity error (n_ids is set).  Synchronous. */
+int slam_kfmap_download_local_map_ids(slam_ctx *ctx, slam_kfmap *km, int s, int kfid, int64_t *ids, int cap_ids, int32_t *n_ids);
 /* merge_matches -> merge_mappoints -> update_keypoint! (mapper.jl:296-310, map_manager.jl:378-427, frame.jl:290-307) on the map: the pairs
  * (prev_id, new_id) = (keypoint of the newest key-frame, local-map point) of a local-map match are applied in HBM, with no host round trip between
  * match and merge.  n_pairs == NULL takes the result block of the last slam_kfmap_local_map_match where it lies in HBM (a stream whose status

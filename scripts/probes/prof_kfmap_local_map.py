@@ -11,7 +11,12 @@ staging and of the gates, not of merges).  Warm-up runs 8 key-frames; then per r
       Python assembly + packing, and of the slam_local_map_match_batch call; its pairs are compared with (b)'s.
 Medians with the spread (min - max) over the repeats.
 
+--history: a SECOND map with slam_kfmap_enable_local_map_history takes the same key-frames and descriptors, and per repeat both maps' match calls are
+timed back to back (without history first): (b) for each, plus the local-map sizes each reaches and how many streams had status 2.  The host route (c)
+is not run (it models the match without history).  --max-local sets the bound of both calls (16 384 = the table's size rules status 2 out).
+
     python scripts/probes/prof_kfmap_local_map.py [--streams 128] [--repeats 25] [--host-repeats 25] [--out profiles/kfmap_local_map_s128.json]
+    python scripts/probes/prof_kfmap_local_map.py --history [--max-local 16384] [--out profiles/kfmap_local_map_history_s128.json]
 """
 import argparse
 import json
@@ -70,7 +75,11 @@ def main():
     ap.add_argument("--repeats", type=int, default=25)
     ap.add_argument("--host-repeats", type=int, default=25)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--history", action="store_true", help="time a second map with the local-map history beside the first, on the same steps (no host route)")
+    ap.add_argument("--max-local", type=int, default=MAX_LOCAL)
     args = ap.parse_args()
+    if args.history:
+        args.host_repeats = 0
     import torch
     import slam_jl_amd as slam
     from slam_jl_amd import synthetic as syn
@@ -84,8 +93,13 @@ def main():
     ks = slam.KeypointSet(S, CAP)
     km = slam.KeyframeMap(S, CAP, R=RING, mcap=MCAP)
     km.enable_descriptors()
+    kmh = None
+    if args.history:
+        kmh = slam.KeyframeMap(S, CAP, R=RING, mcap=MCAP)
+        kmh.enable_descriptors(); kmh.enable_local_map_history()
     rows = [dict() for _ in range(S)]
-    m = {k: [] for k in ("desc", "call", "stage", "kernel", "wall", "h_down", "h_asm", "h_call", "h_total", "M", "N", "pairs")}
+    m = {k: [] for k in ("desc", "call", "stage", "kernel", "wall", "h_down", "h_asm", "h_call", "h_total", "M", "N", "pairs",
+                         "hist_call", "hist_stage", "hist_kernel", "hist_wall", "hist_M", "hist_pairs", "hist_status2", "status2")}
     agree = []
     ctx.prof_enable(True)
     for k in range(WARM + R):
@@ -104,20 +118,35 @@ def main():
         torch.cuda.synchronize()
         ks.keyframe()
         km.add_keyframe(ks, slam.stream_params(S, Tcw=Tcw, cam=cam))
+        if kmh is not None:
+            kmh.add_keyframe(ks, slam.stream_params(S, Tcw=Tcw, cam=cam))
+            kmh.add_descriptors(desc_dev.data_ptr(), info_dev.data_ptr(), DCAP)
         ctx.synchronize()
         ctx.prof_reset()
         km.add_descriptors(desc_dev.data_ptr(), info_dev.data_ptr(), DCAP)
         ctx.synchronize()
         t0 = time.perf_counter()
-        status, pairs, dist = km.local_map_match(cam10, CELL, params.max_projection_distance, params.max_descriptor_distance, max_local=MAX_LOCAL)
+        status, pairs, dist = km.local_map_match(cam10, CELL, params.max_projection_distance, params.max_descriptor_distance, max_local=args.max_local)
         wall = (time.perf_counter() - t0) * 1e3
-        assert not (status == 2).any(), "a local map did not fit the probe's max_local"
+        assert args.history or not (status == 2).any(), "a local map did not fit the probe's max_local"
         if k >= WARM:
+            m["status2"].append(int((status == 2).sum()))
             m["desc"].append(ctx.prof_get("kfmap_add_descriptors")[0]); m["call"].append(ctx.prof_get("kfmap_local_map_match")[0])
             m["stage"].append(ctx.prof_get("kfmap_lm_stage")[0]); m["kernel"].append(ctx.prof_get("local_map_match_kernel")[0]); m["wall"].append(wall)
             dbg = [km.debug_local_map(s) for s in range(0, S, max(S // 8, 1))]
             m["M"].append(float(np.mean([len(d["lm_ids"]) for d in dbg]))); m["N"].append(float(np.mean([len(d["kp_ids"]) for d in dbg])))
             m["pairs"].append(int(sum(len(p) for p in pairs)))
+        if kmh is not None:                                      # the same step on the map with history, right behind
+            ctx.prof_reset()
+            t0 = time.perf_counter()
+            hstatus, hpairs, _ = kmh.local_map_match(cam10, CELL, params.max_projection_distance, params.max_descriptor_distance, max_local=args.max_local)
+            hwall = (time.perf_counter() - t0) * 1e3
+            if k >= WARM:
+                m["hist_call"].append(ctx.prof_get("kfmap_local_map_match")[0]); m["hist_stage"].append(ctx.prof_get("kfmap_lm_stage")[0])
+                m["hist_kernel"].append(ctx.prof_get("local_map_match_kernel")[0]); m["hist_wall"].append(hwall)
+                dbg = [kmh.debug_local_map(s) for s in range(0, S, max(S // 8, 1))]
+                m["hist_M"].append(float(np.mean([len(d["lm_ids"]) for d in dbg])))
+                m["hist_pairs"].append(int(sum(len(p) for p in hpairs))); m["hist_status2"].append(int((hstatus == 2).sum()))
         if k >= WARM and k - WARM < args.host_repeats:
             cur = km.newest()
             t0 = time.perf_counter()
@@ -143,15 +172,26 @@ def main():
             agree.append(bool(same))
         del desc_dev, info_dev
     ctx.prof_enable(False)
+    if kmh is not None:
+        newest = int(kmh.newest()[0])
+        stored = [len(kmh.local_map_ids(s, newest)) for s in range(0, S, max(S // 8, 1))]
+        kmh.close()
     km.close(); ks.close()
     rec = {"lib": os.path.basename(slam.LIB_PATH), "S": S, "cap": CAP, "keypoints_per_stream": NKP, "shape": [H, W], "cell": CELL, "ring": RING, "table": MCAP,
-           "max_local": MAX_LOCAL, "repeats": R, "host_repeats": len(m["h_total"]), "warmup_keyframes": WARM,
+           "max_local": args.max_local, "repeats": R, "host_repeats": len(m["h_total"]), "warmup_keyframes": WARM,
            "local_map_points_per_stream": stat(m["M"]), "keypoints_with_descriptor_per_stream": stat(m["N"]), "pairs_all_streams": stat(m["pairs"]),
            "a_add_descriptors_device_ms": stat(m["desc"]),
            "b_local_map_match_device_ms": stat(m["call"]), "b_stage_kernel_ms": stat(m["stage"]), "b_match_kernel_ms": stat(m["kernel"]),
            "b_local_map_match_sync_wall_ms": stat(m["wall"]),
            "c_host_route_wall_ms": stat(m["h_total"]), "c_host_downloads_wall_ms": stat(m["h_down"]), "c_host_assembly_and_packing_wall_ms": stat(m["h_asm"]),
            "c_host_batch_call_wall_ms": stat(m["h_call"]), "c_host_route_pairs_equal_device": agree}
+    if args.history:
+        rec = {k: v for k, v in rec.items() if not k.startswith("c_")}
+        rec.update({"streams_with_status_2": stat(m["status2"]),
+                    "history_local_map_points_per_stream": stat(m["hist_M"]), "history_stored_set_of_newest_keyframe": stat(stored),
+                    "history_pairs_all_streams": stat(m["hist_pairs"]), "history_streams_with_status_2": stat(m["hist_status2"]),
+                    "history_local_map_match_device_ms": stat(m["hist_call"]), "history_stage_kernel_ms": stat(m["hist_stage"]),
+                    "history_match_kernel_ms": stat(m["hist_kernel"]), "history_local_map_match_sync_wall_ms": stat(m["hist_wall"])})
     print(json.dumps(rec))
     if args.out:
         with open(args.out, "w") as f_:

@@ -551,6 +551,7 @@ int slam_kfmap_destroy(slam_kfmap *km)
     if (km->dbase) (void)hipFree(km->dbase);
     if (km->lm_base) (void)hipFree(km->lm_base);
     if (km->mg_base) (void)hipFree(km->mg_base);
+    if (km->hs_base) (void)hipFree(km->hs_base);
     if (km->pin_ev) (void)hipEventDestroy(km->pin_ev);
     delete km;
     return SLAM_OK;
@@ -836,6 +837,12 @@ int slam_kfmap_reset(slam_ctx *ctx, slam_kfmap *km, int s)
     HIP_TRY(ctx, hipMemsetAsync(V.cur + s, 0, 4, ctx->stream));
     if (V.dhas) HIP_TRY(ctx, hipMemsetAsync(V.dhas + (size_t)s * V.mcap, 0, (size_t)V.mcap, ctx->stream));
     HIP_TRY(ctx, hipMemsetAsync(V.whdr + (size_t)s * KFM_HDR, 0, KFM_HDR * 4, ctx->stream));
+    if (km->hs_base) {                                           // the stream's stored sets, their owners and the shadow tags (= the emptied table's)
+        const KfmHist &H = km->hs;
+        HIP_TRY(ctx, hipMemsetAsync(H.bits + (size_t)s * H.W * V.R, 0, (size_t)H.W * V.R * 8, ctx->stream));
+        HIP_TRY(ctx, hipMemsetAsync(H.htag + (size_t)s * V.R, 0, (size_t)V.R * 4, ctx->stream));
+        HIP_TRY(ctx, hipMemsetAsync(H.shadow + (size_t)s * V.mcap, 0, (size_t)V.mcap * 8, ctx->stream));
+    }
     km->pend[s].valid = 0; km->lm_np[s] = 0;
     return SLAM_OK;
 }

@@ -41,12 +41,29 @@
 // Deviations of slam_kfmap_local_map_match from update_frame_covisibility! + match_local_map! (map_manager.jl:302-355, mapper.jl:265-462):
 //   distortion    the slabs hold UNDISTORTED pixels, find_best_match uses kp.pixel and project_world_to_image_distort; the two coincide only without
 //                 lens distortion, so a stream with non-zero k1, k2, p1, p2 is an argument error (the restriction of the set's stereo seams)
-//   persistence   frame.local_map_ids is not kept between key-frames: neither the replace-or-union rule (map_manager.jl:350-354) nor the union with the
-//                 oldest covisible key-frame's local map (mapper.jl:274-286) is modelled; the local map is what this key-frame's covisibility pass yields
+//   persistence   without slam_kfmap_enable_local_map_history frame.local_map_ids is not kept between key-frames (the local map is what this key-frame's
+//                 covisibility pass yields).  With it (below) the replace-or-union rule (map_manager.jl:350-354) and the union with the oldest covisible
+//                 key-frame's local map (mapper.jl:274-286) hold, with three differences: a stored set holds the ids that passed the match's gates
+//                 when it was stored (the reference stores raw ids and gates at match time; an id that fails a gate never passes one later, so only the
+//                 sizes the two rules compare can differ), an id whose table entry another id has taken leaves every stored set (the purge), and
+//                 "oldest" is the covisible key-frame of the smallest id (the reference takes the first key of a Dict)
 //   clean-ups     no remove_mappoint_obs! clean-ups (mapper.jl:412, :429-434), as in the array form: a missing or dead observation is skipped
 //   merges        the call reports pairs and changes nothing in the map: slam_kfmap_merge (below) applies them
 //   order         the local map is walked ascending by id (the reference iterates a Set); among equal distances the larger local-map index wins
 //   grid          a keypoint whose pixel lies in no cell of the grid is in no cell list (the array form rejects such a call)
+//
+// Local-map history (slam_kfmap_enable_local_map_history, kfmap_lmm.inc; an allocation of its own, made by that call): frame.local_map_ids of every
+// key-frame of the ring as a bitset over the table's entries -- a point is named by its entry, the id is the entry's tag.  With W = ceil(mcap / 64), each
+// region rounded up to 256 over S:
+//   sets     8 S W R   word w of slot b's set at [s][w][b]: the R words of one group of 64 entries are adjacent
+//   owners   4 S R     the key-frame id + 1 a slot's set belongs to (0: none; a key-frame whose match was skipped leaves its slot's set to the old one)
+//   shadow   8 S mcap  the table's tags as of the stream's last match: an entry whose tag differs has changed owner, its bit goes from all R sets
+// i.e. about R mcap / 8 + 8 mcap bytes per stream (R 32, mcap 16 384: 192 KB; S = 128: 25 MB).  Storing ids instead would cost 8 R max_local per stream
+// (S = 128: 460 MB).  A match with history sweeps a stream's sets and shadow twice (k_kfm_lm_stage_hist); without the call nothing of this exists and the
+// match launches the kernels it always did.  Sets grow along the chain, so max_local >= mcap (status 2 cannot occur) is the setting to use with it.
+// P of the replace-or-union rule is non-empty only when the match runs twice for one key-frame: in the reference the key-frame is a deepcopy of a current
+// frame whose set is never written (map_manager.jl:174).  slam_kfmap_merge does not touch the sets (prev_id goes at the next purge once a larger id takes
+// its entry, and is gated out meanwhile: it is dead); slam_kfmap_reset clears the stream's.
 //
 // Merge scratch (slam_kfmap_merge, kfmap_merge.inc; a fourth allocation, made by the first merge call that has pairs): merge_matches -> merge_mappoints ->
 // update_keypoint! (mapper.jl:296-310, map_manager.jl:378-427, frame.jl:290-307) renames a keypoint in every key-frame that observes it, and every slab
@@ -119,6 +136,14 @@ struct KfmLm {
     int32_t *status, *rn; int64_t *rpairs; double *rdist;        // results, one block: [S] | [S] | [S cap][2] | [S cap]
 };
 
+// the local-map history's regions (above), by value to k_kfm_lm_stage_hist
+struct KfmHist {
+    unsigned long long *bits;             // [S W R] the stored sets
+    int *htag;                            // [S R] key-frame id + 1 of the slot's set
+    unsigned long long *shadow;           // [S mcap] ptag as of the stream's last match with history
+    int W;                                // words per set: ceil(mcap / 64)
+};
+
 // slam_kfmap_merge's scratch allocation (kfmap_merge.inc), by value to its kernels; Z = S (R + 1): a stream's R slabs, then its list
 struct KfmMerge {
     int *cnt;                             // [Z] renames of the slab / list
@@ -143,4 +168,5 @@ struct slam_kfmap {
     char *lm_base = nullptr; size_t lm_bytes = 0, lm_res_off = 0, lm_res_bytes = 0; KfmLm lm = {};        // the local-map staging (lm.max_local, lm.C1: what it was laid out for)
     int lm_np[128] = {};                  // pairs per stream in the result block of the last local-map match, until a merge has consumed them
     char *mg_base = nullptr; size_t mg_bytes = 0; KfmMerge mg = {};       // the merge's scratch
+    char *hs_base = nullptr; size_t hs_bytes = 0; KfmHist hs = {};        // the local-map history (nullptr: off)
 };

@@ -2,7 +2,8 @@
 // (update_frame_covisibility! map_manager.jl:302-355 + match_local_map! / do_local_map_matching mapper.jl:265-383) from the map itself.  The stager
 // writes the packed buffer of k_lmm_match (lmm_host.hpp's regions, fixed per-stream strides: kfmap.hpp has the layout, its cost and the deviations),
 // the match kernel of localmap.hip runs on it unchanged (lmm_launch), a closing pass turns the keypoints' keys into id pairs.  Between the upload of the
-// call's arguments and the one copy of results nothing returns to the host.  tests/np_kfmap_local_map.py is the model.
+// call's arguments and the one copy of results nothing returns to the host.  tests/np_kfmap_local_map.py is the model.  With the local-map history
+// (slam_kfmap_enable_local_map_history) the stager also keeps frame.local_map_ids per key-frame: kfm_lm_history below, tests/np_kfmap_local_map_history.py.
 
 // ---- descriptors: slot-parallel, one thread per appended keypoint (grid.y = stream) ---------------------------------------------------------------------
 // row j of stream s belongs to id info[2 s] + j (slam_kpset_detect_describe); it is stored where the table entry carries that id
@@ -17,6 +18,76 @@ __global__ __launch_bounds__(256) void k_kfm_desc_record(KfmapView V, const uint
     const uint64_t *src = desc + 4 * ((size_t)s * dcap + j);
     for (int k = 0; k < 4; k++) V.ddesc[4 * pe + k] = src[k];
     V.dhas[pe] = 1;
+}
+
+// ---- the local-map history (slam_kfmap_enable_local_map_history): frame.local_map_ids kept between key-frames -------------------------------------------
+// Called by the whole workgroup of stream s once `mark` holds C, the local map of this key-frame's covisibility pass.  A wave takes 64 consecutive table
+// entries at a time -- one word of every bitset: a ballot turns per-entry facts into that word, lane b holds the word of slot b's set (the R words of one
+// entry group are adjacent: one coalesced access).  Two sweeps over the table, a barrier between them (tests/np_kfmap_local_map_history.py is the model):
+//   sweep 1   purge: an entry whose tag differs from the shadow (its owner changed since the stream's last call) loses its bit in all R sets and the
+//             shadow follows; the sizes of C, of P (the set stored for this key-frame, if the slot's set is its own) and of P | C
+//   rule      map_manager.jl:350-354: L = C if 2 |C| > |P| else P | C; the chain (mapper.jl:274-286) runs if a key-frame is covisible and |L| < max_local,
+//             with the set of the covisible key-frame of the smallest id if that slot's set is that key-frame's
+//   sweep 2   L, word by word, is stored as this key-frame's set; `mark` becomes L's entries that pass the gates now (alive, 3-D, described, not
+//             observed by this key-frame) -- what the ascending emission below reads
+__device__ __forceinline__ unsigned long long kfm_shfl64(unsigned long long v, int lane)
+{
+    const unsigned lo = (unsigned)__shfl((int)(unsigned)v, lane, 64), hi = (unsigned)__shfl((int)(unsigned)(v >> 32), lane, 64);
+    return (unsigned long long)hi << 32 | lo;
+}
+__device__ __forceinline__ void kfm_lm_history(const KfmapView &V, const KfmLm &Q, const KfmHist &Hs, int s, int kfid, int r0, unsigned long long covmask,
+                                               const int *s_tag)
+{
+    __shared__ int s_len[3];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, R = V.R, mcap = V.mcap;
+    const size_t pb = (size_t)s * mcap;
+    unsigned long long *H = Hs.bits + (size_t)s * Hs.W * R;
+    int *htag = Hs.htag + s * R;
+    const bool own = htag[r0] == kfid + 1;                                      // the slot's set is this key-frame's: the match runs again for it
+    int oldest = -1;                                                            // the covisible key-frame with the smallest id
+    for (unsigned long long cm = covmask; cm; cm &= cm - 1) { const int b = __ffsll((long long)cm) - 1; if (oldest < 0 || s_tag[b] < s_tag[oldest]) oldest = b; }
+    const bool linked = oldest >= 0 && htag[oldest] == s_tag[oldest];
+    if (tid < 3) s_len[tid] = 0;
+    __syncthreads();                                                            // (also: every thread has read htag[r0] before it is written below)
+    int nC = 0, nP = 0, nU = 0;
+    for (int e0 = wv * 64; e0 < mcap; e0 += 256) {
+        const int e = e0 + lane, w = e0 >> 6;
+        bool changed = false, inC = false;
+        if (e < mcap) {
+            const unsigned long long t = V.ptag[pb + e];
+            changed = t != Hs.shadow[pb + e];
+            if (changed) Hs.shadow[pb + e] = t;
+            inC = Q.mark[pb + e] != 0;
+        }
+        const unsigned long long chg = __ballot(changed), cw = __ballot(inC);
+        unsigned long long h = 0;
+        if (lane < R) {
+            h = H[(size_t)w * R + lane];
+            if (h & chg) { h &= ~chg; H[(size_t)w * R + lane] = h; }
+        }
+        const unsigned long long pw = own ? kfm_shfl64(h, r0) : 0ull;
+        nC += __popcll(cw); nP += __popcll(pw); nU += __popcll(pw | cw);
+    }
+    if (lane == 0) { atomicAdd(&s_len[0], nC); atomicAdd(&s_len[1], nP); atomicAdd(&s_len[2], nU); }
+    __syncthreads();
+    const bool replace = 2 * s_len[0] > s_len[1];                               // len(C) > 0.5 len(P), exact in integers
+    const int size = replace ? s_len[0] : s_len[2];
+    const bool chain = covmask != 0 && size < Q.max_local && linked;
+    for (int e0 = wv * 64; e0 < mcap; e0 += 256) {
+        const int e = e0 + lane, w = e0 >> 6;
+        const unsigned long long cw = __ballot(e < mcap && Q.mark[pb + e] != 0);
+        unsigned long long lw = cw;                                             // (every lane computes the word: uniform loads)
+        if (own && !replace) lw |= H[(size_t)w * R + r0];
+        if (chain) lw |= H[(size_t)w * R + oldest];
+        if (lane == 0) H[(size_t)w * R + r0] = lw;
+        if (e < mcap) {
+            const size_t pe = pb + e;
+            const bool in = (lw >> lane & 1) && V.ptag[pe] != 0 && !(V.pflags[pe] & KFM_DEAD) && (V.pflags[pe] & KFM_3D) && V.dhas[pe] && !(V.pmask[pe] >> r0 & 1);
+            Q.mark[pe] = in ? 1 : 0;
+        }
+    }
+    if (tid == 0) htag[r0] = kfid + 1;
+    __syncthreads();
 }
 
 // ---- staging: one 256-thread workgroup per stream, no workgroup waits for another ------------------------------------------------------------------------
@@ -36,7 +107,8 @@ __global__ __launch_bounds__(256) void k_kfm_desc_record(KfmapView V, const uint
 //                  256 in list order -- a keypoint's place is its cell's cursor plus the chunk's earlier keypoints of the same cell
 // status: 0 staged, 1 nothing to match (no key-frame, no covisible key-frame, an empty local map or keypoint list), 2 the local map exceeds max_local
 // (nothing of it is used).  A stream that is not staged gets M = 0 in its LmmStream row: every group of the match kernel leaves at once.
-__global__ __launch_bounds__(256) void k_kfm_lm_stage(KfmapView V, KfmLm Q, const KfmLmArg *args, const int *sel)
+template <bool HIST>
+__device__ __forceinline__ void kfm_lm_stage_body(const KfmapView &V, const KfmLm &Q, const KfmHist &Hs, const KfmLmArg *args, const int *sel)
 {
     __shared__ int s_cov[64], s_tag[64], s_rank[64], s_asc[64], s_w[4], s_cell[256], s_base, s_obase, s_nb3, s_nv;
     __shared__ unsigned long long s_covmask, s_q;
@@ -73,7 +145,7 @@ __global__ __launch_bounds__(256) void k_kfm_lm_stage(KfmapView V, KfmLm Q, cons
     __syncthreads();
     const unsigned long long covmask = s_covmask;
     const int nv = s_nv, nb3 = s_nb3;
-    if (covmask == 0) KFM_LM_LEAVE(1)
+    if (!HIST && covmask == 0) KFM_LM_LEAVE(1)
     for (unsigned long long cm = covmask; cm; cm &= cm - 1) {
         const int b = __ffsll((long long)cm) - 1, n = min(V.kn[s * R + b], cap);
         const size_t sl = ((size_t)s * R + b) * cap;
@@ -86,6 +158,7 @@ __global__ __launch_bounds__(256) void k_kfm_lm_stage(KfmapView V, KfmLm Q, cons
         }
     }
     __syncthreads();
+    if constexpr (HIST) kfm_lm_history(V, Q, Hs, s, kfid, r0, covmask, s_tag);
     // the local map, ascending by id
     for (unsigned long long qlo = 0;;) {
         if (tid == 0) s_q = ~0ull;
@@ -219,6 +292,16 @@ __global__ __launch_bounds__(256) void k_kfm_lm_stage(KfmapView V, KfmLm Q, cons
     }
 #undef KFM_LM_LEAVE
 }
+__global__ __launch_bounds__(256) void k_kfm_lm_stage(KfmapView V, KfmLm Q, const KfmLmArg *args, const int *sel)
+{
+    kfm_lm_stage_body<false>(V, Q, KfmHist{}, args, sel);
+}
+// the same stager for a map with the local-map history: `mark` comes out of kfm_lm_history, and a stream without a covisible key-frame is still staged
+// (its stored set may hold points)
+__global__ __launch_bounds__(256) void k_kfm_lm_stage_hist(KfmapView V, KfmLm Q, KfmHist Hs, const KfmLmArg *args, const int *sel)
+{
+    kfm_lm_stage_body<true>(V, Q, Hs, args, sel);
+}
 
 // prev_new_map (mapper.jl:370-382) as id pairs: ordered compaction of the keypoints somebody chose, in list order = ascending keypoint id
 __global__ __launch_bounds__(256) void k_kfm_lm_pairs(KfmapView V, KfmLm Q, const int *sel)
@@ -281,6 +364,55 @@ int slam_kfmap_enable_descriptors(slam_ctx *ctx, slam_kfmap *km, int n_bits)
     if (e == hipSuccess) e = slam_stream_wait(ctx->stream);
     if (e != hipSuccess) { (void)hipFree(base); return slam_fail(ctx, SLAM_ERR_HIP, "slam_kfmap_enable_descriptors: %s", hipGetErrorString(e)); }
     km->dbase = base; km->v.ddesc = (uint64_t *)(base + o_desc); km->v.dhas = (uint8_t *)(base + o_has);
+    return SLAM_OK;
+}
+
+int slam_kfmap_enable_local_map_history(slam_ctx *ctx, slam_kfmap *km)
+{
+    ARG_TRY(ctx, ctx != nullptr && km != nullptr);
+    if (km->hs_base) return SLAM_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const KfmapView &V = km->v;
+    const size_t W = ((size_t)V.mcap + 63) / 64;
+    Layout Lo;
+    const size_t o_bits = Lo.take((size_t)V.S * W * V.R * 8), o_tag = Lo.take((size_t)V.S * V.R * 4), o_shadow = Lo.take((size_t)V.S * V.mcap * 8);
+    char *base = nullptr;
+    HIP_TRY(ctx, hipMalloc((void **)&base, Lo.size()));
+    hipError_t e = hipMemsetAsync(base, 0, Lo.size(), ctx->stream);           // empty sets without owners; the first match brings the shadow up to the table
+    if (e == hipSuccess) e = slam_stream_wait(ctx->stream);
+    if (e != hipSuccess) { (void)hipFree(base); return slam_fail(ctx, SLAM_ERR_HIP, "slam_kfmap_enable_local_map_history: %s", hipGetErrorString(e)); }
+    km->hs.bits = (unsigned long long *)(base + o_bits); km->hs.htag = (int *)(base + o_tag); km->hs.shadow = (unsigned long long *)(base + o_shadow);
+    km->hs.W = (int)W; km->hs_bytes = Lo.size(); km->hs_base = base;
+    return SLAM_OK;
+}
+
+int slam_kfmap_download_local_map_ids(slam_ctx *ctx, slam_kfmap *km, int s, int kfid, int64_t *ids, int cap_ids, int32_t *n_ids)
+{
+    ARG_TRY(ctx, ctx != nullptr && km != nullptr && s >= 0 && s < km->v.S && kfid >= 0 && n_ids != nullptr && cap_ids >= 0 && (cap_ids == 0 || ids != nullptr));
+    if (!km->hs_base) return slam_fail(ctx, SLAM_ERR_ARG, "slam_kfmap_download_local_map_ids: the local-map history is not enabled (slam_kfmap_enable_local_map_history)");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const KfmapView &V = km->v;
+    const KfmHist &H = km->hs;
+    const int b = kfid % V.R;
+    const size_t sr = (size_t)s * V.R + b, W = (size_t)H.W;
+    int tg[2] = {0, 0};
+    HIP_TRY(ctx, hipMemcpyAsync(&tg[0], V.tag + sr, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(&tg[1], H.htag + sr, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, slam_stream_wait(ctx->stream));
+    *n_ids = 0;
+    if (tg[0] != kfid + 1) return slam_fail(ctx, SLAM_ERR_ARG, "slam_kfmap_download_local_map_ids: key-frame %d of stream %d is not in the ring", kfid, s);
+    if (tg[1] != kfid + 1) return slam_fail(ctx, SLAM_ERR_ARG, "slam_kfmap_download_local_map_ids: no local map was stored for key-frame %d of stream %d", kfid, s);
+    std::vector<unsigned long long> bits(W * V.R), shadow((size_t)V.mcap);
+    HIP_TRY(ctx, hipMemcpyAsync(bits.data(), H.bits + (size_t)s * W * V.R, W * V.R * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(shadow.data(), H.shadow + (size_t)s * V.mcap, (size_t)V.mcap * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, slam_stream_wait(ctx->stream));
+    std::vector<int64_t> got;                                    // a set bit's id is the entry's tag at the store, which the shadow still holds
+    for (int e = 0; e < V.mcap; e++)
+        if ((bits[(size_t)(e >> 6) * V.R + b] >> (e & 63) & 1) && shadow[e]) got.push_back((int64_t)(shadow[e] - 1ull));
+    std::sort(got.begin(), got.end());
+    *n_ids = (int32_t)got.size();
+    if (got.size() > (size_t)cap_ids) return slam_fail(ctx, SLAM_ERR_CAPACITY, "slam_kfmap_download_local_map_ids: %zu ids but cap_ids = %d", got.size(), cap_ids);
+    if (!got.empty()) memcpy(ids, got.data(), got.size() * 8);
     return SLAM_OK;
 }
 
@@ -374,7 +506,8 @@ int slam_kfmap_local_map_match(slam_ctx *ctx, slam_kfmap *km, const double *cam,
       HIP_TRY(ctx, hipMemcpyAsync(scr, h, in_b, hipMemcpyHostToDevice, ctx->stream));
       HIP_TRY(ctx, hipMemsetAsync(Q.keys, 0xFF, (size_t)S * Q.N1 * 8, ctx->stream));
       { ProfScope stage(ctx, "kfmap_lm_stage");
-        hipLaunchKernelGGL(k_kfm_lm_stage, dim3(ns), dim3(256), 0, ctx->stream, V, Q, (const KfmLmArg *)o_arg.at(scr), sel); }
+        if (km->hs_base) hipLaunchKernelGGL(k_kfm_lm_stage_hist, dim3(ns), dim3(256), 0, ctx->stream, V, Q, km->hs, (const KfmLmArg *)o_arg.at(scr), sel);
+        else hipLaunchKernelGGL(k_kfm_lm_stage, dim3(ns), dim3(256), 0, ctx->stream, V, Q, (const KfmLmArg *)o_arg.at(scr), sel); }
       lmm_launch(ctx, L, max_local, ns);
       hipLaunchKernelGGL(k_kfm_lm_pairs, dim3(ns), dim3(256), 0, ctx->stream, V, Q, sel);
       HIP_TRY(ctx, hipGetLastError());

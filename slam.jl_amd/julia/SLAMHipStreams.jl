@@ -451,6 +451,17 @@ function local_map_match(m::KeyframeMap, cam::Matrix{Float64}, cell_size::Vector
     n = sum(n_pairs)
     (status = status, n_pairs = n_pairs, pairs = pairs[:, 1:n], dist = dist[1:n])
 end
+# The local-map history (slam_kfmap_enable_local_map_history): frame.local_map_ids kept between key-frames -- from then on local_map_match follows the
+# replace-or-union rule (map_manager.jl:350-354) and takes in the oldest covisible key-frame's set (mapper.jl:274-286).  local_map_ids: the set stored
+# for key-frame kfid of stream s, ascending (an error where the ring does not hold the key-frame or no set was stored for it).
+enable_local_map_history!(m::KeyframeMap) =
+    (check(ccall((:slam_kfmap_enable_local_map_history, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), ctx(), m.h)); m)
+function local_map_ids(m::KeyframeMap, s::Integer, kfid::Integer)
+    ids = zeros(Int64, m.mcap); n = Ref{Int32}(0)
+    check(ccall((:slam_kfmap_download_local_map_ids, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cint, Ptr{Int64}, Cint, Ref{Int32}),
+                ctx(), m.h, s, kfid, ids, m.mcap, n))
+    ids[1:n[]]
+end
 # merge_matches (mapper.jl:296-310) on the map: the pairs of the last local_map_match where they lie in HBM (n_pairs === nothing), or the caller's
 # (n_pairs: S counts, pairs: 2 x n (prev id, new id), the streams back to back).  k: the KeypointSet whose live lists follow.  Returns the 4 x S counts
 # (pairs applied, pairs skipped, observations renamed, status), or nothing with want_counts = false (enqueue-only).

@@ -200,6 +200,22 @@ class KeyframeMap:
         at = np.concatenate([[0], np.cumsum(n)])
         return status, [pairs[at[s]:at[s + 1]].copy() for s in range(S)], [dist[at[s]:at[s + 1]].copy() for s in range(S)]
 
+    def enable_local_map_history(self, ctx=None):
+        """Keep frame.local_map_ids of every key-frame of the ring in HBM (slam_kfmap_enable_local_map_history): from then on local_map_match applies
+        the replace-or-union rule (src/map_manager.jl:350-354) and takes in the set of the oldest covisible key-frame (src/mapper.jl:274-286), so a
+        point can reach the match after every key-frame that observes it has stopped being covisible.  Sets grow along that chain: use
+        max_local >= mcap with it.  Opt-in; a second call is a no-op."""
+        c = ctx or self.ctx
+        c.check(c.lib.slam_kfmap_enable_local_map_history(c.h, self.h))
+
+    def local_map_ids(self, s, kfid, ctx=None):
+        """(n,) int64, ascending: the set local_map_match stored for key-frame kfid of stream s.  SlamHipError where the ring does not hold the
+        key-frame or no set was stored for it (its match was skipped).  Synchronous."""
+        c = ctx or self.ctx
+        ids = np.zeros(self.mcap, dtype=np.int64); n = C.c_int32(0)
+        c.check(c.lib.slam_kfmap_download_local_map_ids(c.h, self.h, int(s), int(kfid), L.ptr(ids, L.i64p), self.mcap, C.byref(n)))
+        return ids[:n.value].copy()
+
     def merge(self, ks=None, pairs=None, want_counts=True, ctx=None):
         """merge_matches -> merge_mappoints -> update_keypoint! (src/mapper.jl:296-310, src/map_manager.jl:378-427, src/frame.jl:290-307): the pairs
         (keypoint id, local-map point id) are applied in HBM -- the keypoint is renamed in every key-frame that observes it, the touched slabs are put
