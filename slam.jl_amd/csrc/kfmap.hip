@@ -6,7 +6,9 @@
 // (src/map_manager.jl:184-209); tests/np_kfmap_filter.py is their model.  The descriptor store and slam_kfmap_local_map_match (update_frame_covisibility! +
 // match_local_map!, staged on the device for localmap.hip's match kernel) are in kfmap_lmm.inc, included at the end: they use the routines below.
 // slam_kfmap_merge (merge_matches -> merge_mappoints -> update_keypoint!: the match's pairs applied in HBM, the touched slabs and lists rebuilt in id
-// order) is in kfmap_merge.inc, included behind it.
+// order) is in kfmap_merge.inc, included behind it.  The integer logic -- where an id lives, the search in a slab, every serial decision over a ring's slots --
+// is kfmap_ring.hpp's, host and device (tested on the CPU); the routines every kernel shares (kfm_owned, kfm_slab_point, kfm_each_observer, kfm_live_observers,
+// kfm_tcw) and every host seam shares (kfmap_upload, kfmap_alloc_zeroed, kfmap_put_streams) are below, one copy each.
 //
 // Every kernel takes `sel`: nullptr = workgroup (or grid row) b works on stream b, else on stream sel[b] -- launches are sized by the number of streams
 // acted on, so nothing of any other stream is read or written.
@@ -16,15 +18,17 @@
 #include <cmath>
 
 #define KFM_STREAM(b) (sel ? sel[b] : (int)(b))
-// the table entry of point `id` (ids are non-negative; taken as unsigned, any 64 bits land inside the table)
-__device__ __forceinline__ size_t kfm_entry(int64_t id, int mcap) { return (size_t)((unsigned long long)id % (unsigned long long)mcap); }
-__device__ __forceinline__ bool kfm_valid(const KfmapView &V, size_t pe, int64_t id) { return V.ptag[pe] == (unsigned long long)id + 1ull && !(V.pflags[pe] & KFM_DEAD); }
-// index of `id` among the ascending ids[0 .. n), or -1
-__device__ __forceinline__ int kfm_find(const int64_t *ids, int n, int64_t id)
+// THE ownership test: entry pe carries point `id` (dead or alive); kfm_valid: and the point has not been removed
+__device__ __forceinline__ bool kfm_owned(const KfmapView &V, size_t pe, int64_t id) { return V.ptag[pe] == (unsigned long long)id + 1ull; }
+__device__ __forceinline__ bool kfm_valid(const KfmapView &V, size_t pe, int64_t id) { return kfm_owned(V, pe, id) && !(V.pflags[pe] & KFM_DEAD); }
+// observation i of slot b's slab of stream s (i < the slab's length): false for a tombstone, else its id and its point's table entry -- the caller's own
+// gate (kfm_owned, kfm_valid, 3-D, descriptor) follows
+__device__ __forceinline__ bool kfm_slab_point(const KfmapView &V, int s, int b, int i, int64_t &id, size_t &pe)
 {
-    int lo = 0, hi = n;
-    while (lo < hi) { const int mid = (lo + hi) >> 1; if (ids[mid] < id) lo = mid + 1; else hi = mid; }
-    return lo < n && ids[lo] == id ? lo : -1;
+    const size_t q = ((size_t)s * V.R + b) * V.cap + i;
+    if (!V.klive[q]) return false;
+    id = V.kid[q]; pe = (size_t)s * V.mcap + kfm_entry(id, V.mcap);
+    return true;
 }
 // the live observation of `id` in slot b's slab of stream s, or -1
 __device__ __forceinline__ int kfm_find_live(const KfmapView &V, int s, int b, int64_t id)
@@ -33,6 +37,21 @@ __device__ __forceinline__ int kfm_find_live(const KfmapView &V, int s, int b, i
     const int i = kfm_find(V.kid + sl, min(V.kn[s * V.R + b], V.cap), id);
     return i >= 0 && V.klive[sl + i] ? i : -1;
 }
+// THE observer-mask walk: f(b) for the bits of `mask` that mean something -- below R, their slot with a tag (tag: the stream's R tags, the map's or a copy in
+// LDS) -- in ascending slot order
+template <class F> __device__ __forceinline__ void kfm_each_observer(unsigned long long mask, const int *tag, int R, F f)
+{
+    for (unsigned long long mm = mask; mm; mm &= mm - 1) { const int b = __ffsll((long long)mm) - 1; if (b < R && tag[b]) f(b); }
+}
+// of those, the slots whose slab still holds `id` alive (an observer whose key-frame or pixel is gone does not count)
+__device__ __forceinline__ unsigned long long kfm_live_observers(const KfmapView &V, int s, unsigned long long mask, const int *tag, int64_t id)
+{
+    unsigned long long wm = 0;
+    kfm_each_observer(mask, tag, V.R, [&](int b) { if (kfm_find_live(V, s, b, id) >= 0) wm |= 1ull << b; });
+    return wm;
+}
+// Tcw of a key-frame from its six parameters: angles_to_pose and the bottom row 0 0 0 1 (column-major 4 x 4)
+__device__ __forceinline__ void kfm_tcw(const double *theta, double *T) { angles_to_pose(theta, T); T[3] = 0.0; T[7] = 0.0; T[11] = 0.0; T[15] = 1.0; }
 
 // remove_kf_observation! for observation i of slot r's slab (i < the slab's length): a live observation's point, where its entry still carries that id,
 // loses observer bit r.  THE rule of remove_keyframe! (map_manager.jl:184-209) as far as the map goes -- the forgetting of a re-used slot, the filter's
@@ -40,11 +59,9 @@ __device__ __forceinline__ int kfm_find_live(const KfmapView &V, int s, int b, i
 // filter's closing pass): the atomic keeps every read-modify-write whole.
 __device__ __forceinline__ void kfm_forget_slab(const KfmapView &V, int s, int r, int i)
 {
-    const size_t q = ((size_t)s * V.R + r) * V.cap + i;
-    if (!V.klive[q]) return;
-    const int64_t id = V.kid[q];
-    const size_t pe = (size_t)s * V.mcap + kfm_entry(id, V.mcap);
-    if (V.ptag[pe] == (unsigned long long)id + 1ull) atomicAnd(&V.pmask[pe], ~(1ull << r));
+    int64_t id;
+    size_t pe;
+    if (kfm_slab_point(V, s, r, i, id, pe) && kfm_owned(V, pe, id)) atomicAnd(&V.pmask[pe], ~(1ull << r));
 }
 
 // ---- recording: slot-parallel, one thread per list slot (grid.y = stream) -------------------------------------------------------------------------------
@@ -100,7 +117,7 @@ __global__ __launch_bounds__(256) void k_kfm_record(KfmapView V, KpsetView K, co
     const uint8_t fresh = V.kfresh[(size_t)s * V.cap + i];
     V.kid[q] = id; V.kupx[2 * q] = y; V.kupx[2 * q + 1] = x; V.klive[q] = fresh != 2;
     const size_t pe = (size_t)s * V.mcap + kfm_entry(id, V.mcap);
-    if (fresh == 2 || V.ptag[pe] != (unsigned long long)id + 1ull) return;      // not recorded; or an older id whose entry a newer point holds: an orphan
+    if (fresh == 2 || !kfm_owned(V, pe, id)) return;                            // not recorded; or an older id whose entry a newer point holds: an orphan
     const bool t3 = K.is3d[ql] != 0;
     if (fresh) {
         for (int k = 0; k < 3; k++) V.pxyz[3 * pe + k] = K.xyz[3 * ql + k];
@@ -135,17 +152,14 @@ __device__ __forceinline__ int kfm_scan(int cnt, int *s_w, int *s_base)
 // thread's share of the key-frame's 3-D points.  The gather's plan and the filter both take their covisibility map from here.
 __device__ __forceinline__ int kfm_covisibility(const KfmapView &V, int s, int r0, const int *s_tag, int *s_cov)
 {
-    const size_t sl = ((size_t)s * V.R + r0) * V.cap, pb = (size_t)s * V.mcap;
     const int n0 = min(V.kn[s * V.R + r0], V.cap);
     int nb3 = 0;
     for (int i = threadIdx.x; i < n0; i += 256) {
-        if (!V.klive[sl + i]) continue;
-        const int64_t id = V.kid[sl + i];
-        const size_t pe = pb + kfm_entry(id, V.mcap);
-        if (!kfm_valid(V, pe, id)) continue;
+        int64_t id;
+        size_t pe;
+        if (!kfm_slab_point(V, s, r0, i, id, pe) || !kfm_valid(V, pe, id)) continue;
         nb3 += (V.pflags[pe] & KFM_3D) != 0;
-        unsigned long long m = V.pmask[pe] & ~(1ull << r0);
-        while (m) { const int b = __ffsll((long long)m) - 1; m &= m - 1; if (b < V.R && s_tag[b]) atomicAdd(&s_cov[b], 1); }
+        kfm_each_observer(V.pmask[pe] & ~(1ull << r0), s_tag, V.R, [&](int b) { atomicAdd(&s_cov[b], 1); });
     }
     return nb3;
 }
@@ -181,22 +195,10 @@ __global__ __launch_bounds__(256) void k_kfm_plan(KfmapView V, const int *minc_a
     if (nb3 < minc) { if (tid == 0) { hdr[0] = 1; hdr[1] = kfid; hdr[2] = hdr[3] = hdr[4] = 0; hdr[5] = minc; hdr[6] = 0; } return; }
     if (tid == 0) {
         s_cov[r0] = nb3;
-        unsigned long long used = 0;
-        int ncl = 0;
-        for (int k = 0; k < N_COVISIBLE; k++) {                  // sorted(cov, reverse=True)[:5]
-            int best = -1;
-            for (int b = 0; b < R; b++) if (s_tag[b] && !(used >> b & 1) && (b == r0 || s_cov[b] > 0) && (best < 0 || s_tag[b] > s_tag[best])) best = b;
-            if (best < 0) break;
-            used |= 1ull << best; s_cl[ncl++] = best;
-        }
-        s_ncl = ncl; s_covmask = used;
-        int nv = 0;                                              // observers are walked in ascending key-frame id
-        for (int b = 0; b < R; b++) if (s_tag[b]) {
-            int rank = 0;
-            for (int c = 0; c < R; c++) rank += s_tag[c] && s_tag[c] < s_tag[b];
-            s_rank[b] = rank; s_asc[rank] = b; nv++;
-        }
-        s_nv = nv;
+        unsigned long long used;
+        s_ncl = kfm_covmap_pick(s_tag, s_cov, R, r0, s_cl, used);        // sorted(cov, reverse=True)[:5]
+        s_covmask = used;
+        s_nv = kfm_rank_slots(s_tag, R, s_rank, s_asc);                  // observers are walked in ascending key-frame id
     }
     __syncthreads();
     const int ncl = s_ncl, nv = s_nv;
@@ -204,7 +206,6 @@ __global__ __launch_bounds__(256) void k_kfm_plan(KfmapView V, const int *minc_a
         const int rc = s_cl[c], score = s_cov[rc];
         if (score == 0) continue;                                                        // (every branch here is uniform over the workgroup)
         if (s_order[rc] == 0 && (score < minc || s_tag[rc] == 1)) continue;              // low score or key-frame 0, and not yet a pose of the window: constant, not walked
-        const size_t sl = ((size_t)s * R + rc) * cap;
         const int n = min(V.kn[s * R + rc], cap);
         for (int c0 = 0; c0 < n; c0 += 256) {
             const int i = c0 + tid;
@@ -213,8 +214,7 @@ __global__ __launch_bounds__(256) void k_kfm_plan(KfmapView V, const int *minc_a
             unsigned long long wm = 0;
             int64_t id = 0;
             size_t pe = 0;
-            if (i < n && V.klive[sl + i]) {
-                id = V.kid[sl + i]; pe = pb + kfm_entry(id, mcap);
+            if (i < n && kfm_slab_point(V, s, rc, i, id, pe)) {
                 const uint8_t fl = kfm_valid(V, pe, id) ? V.pflags[pe] : 0;
                 if ((fl & KFM_3D) && V.went[pe] == 0) {                                  // ids_3d, not yet processed (one thread per entry: ids are unique in a slab)
                     const unsigned long long m = V.pmask[pe];
@@ -223,11 +223,8 @@ __global__ __launch_bounds__(256) void k_kfm_plan(KfmapView V, const int *minc_a
                         V.wpid[pb + mcap - 1 - atomicAdd(&s_nbad, 1)] = id;
                     } else {
                         acc = true;
-                        unsigned long long mm = m;
-                        while (mm) {                                                     // an observer whose key-frame or pixel is gone loses the point (remove_obs)
-                            const int b = __ffsll((long long)mm) - 1; mm &= mm - 1;
-                            if (b < R && s_tag[b] && kfm_find_live(V, s, b, id) >= 0) { wm |= 1ull << b; cnt++; }
-                        }
+                        wm = kfm_live_observers(V, s, m, s_tag, id);                     // an observer whose key-frame or pixel is gone loses the point (remove_obs)
+                        cnt = __popcll(wm);
                         if (wm != m) V.pmask[pe] = wm;
                     }
                 }
@@ -241,19 +238,13 @@ __global__ __launch_bounds__(256) void k_kfm_plan(KfmapView V, const int *minc_a
             }
         }
         __syncthreads();
-        if (tid == 0)                                            // dense 1-based pose ids in first-encounter order
-            for (;;) {
-                int best = -1;
-                for (int b = 0; b < R; b++) if (s_order[b] == 0 && s_first[b] != INT_MAX && (best < 0 || s_first[b] < s_first[best])) best = b;
-                if (best < 0) break;
-                s_order[best] = ++s_P; s_first[best] = INT_MAX;
-            }
+        if (tid == 0) { int P = s_P; kfm_assign_poses(s_order, s_first, R, P); s_P = P; }      // dense 1-based pose ids in first-encounter order
         __syncthreads();
     }
     if (tid < R) {
         const int b = tid;
         V.wtag[s * R + b] = s_tag[b]; V.worder[s * R + b] = s_order[b]; V.wrank[s * R + b] = s_rank[b];
-        V.wconst[s * R + b] = s_tag[b] == 1 || !(s_covmask >> b & 1) || s_cov[b] < minc;
+        V.wconst[s * R + b] = kfm_window_const(s_tag[b], s_covmask >> b & 1, s_cov[b], minc);
     }
     if (tid == 0) {
         V.wcov[s] = s_covmask;
@@ -354,13 +345,10 @@ __global__ __launch_bounds__(256) void k_kfm_upd_obs(KfmapView V, const KfmUpd *
 // remove_mappoint! (map_manager.jl:139-168): the point's observations become tombstones, the entry dies; an observed point's id has left the frame
 __device__ __forceinline__ void kfm_remove_point(const KfmapView &V, int s, size_t pe, int64_t id, uint8_t fl)
 {
-    unsigned long long m = V.pmask[pe];
-    while (m) {
-        const int b = __ffsll((long long)m) - 1; m &= m - 1;
-        if (b >= V.R || !V.tag[s * V.R + b]) continue;
+    kfm_each_observer(V.pmask[pe], V.tag + s * V.R, V.R, [&](int b) {
         const int i = kfm_find_live(V, s, b, id);
         if (i >= 0) V.klive[((size_t)s * V.R + b) * V.cap + i] = 0;
-    }
+    });
     V.pmask[pe] = 0; V.pflags[pe] = KFM_DEAD | ((fl & KFM_OBS) ? KFM_GONE : 0) | (fl & KFM_GONE);
 }
 // is_bad on every point of the window and on the gather's bad set: removed, or (window points) the refined position.  Thread t < M owns point t of the
@@ -392,7 +380,7 @@ __global__ __launch_bounds__(256) void k_kfm_upd_list(KfmapView V, KpsetView K, 
     const size_t q = (size_t)s * K.cap + i, pb = (size_t)s * V.mcap;
     const int64_t id = K.id[q];
     const size_t pe = pb + kfm_entry(id, V.mcap);
-    if (V.ptag[pe] != (unsigned long long)id + 1ull) return;
+    if (!kfm_owned(V, pe, id)) return;
     const uint8_t fl = V.pflags[pe];
     if (fl & KFM_GONE) { flags[q] = 1; return; }
     const int w = V.went[pe];
@@ -414,7 +402,7 @@ __global__ __launch_bounds__(256) void k_kfm_filter(KfmapView V, const double *r
 {
     __shared__ int s_cov[64], s_tag[64], s_cand[64], s_ncand, s_tot[2][4], s_good[2][4];
     __shared__ unsigned long long s_valid;
-    const int s = KFM_STREAM(blockIdx.x), tid = threadIdx.x, R = V.R, cap = V.cap, mcap = V.mcap;
+    const int s = KFM_STREAM(blockIdx.x), tid = threadIdx.x, R = V.R, cap = V.cap;
     const double ratio = ratio_all[s];
     const int kfid = V.cur[s] - 1, few = minc_all[s] / 2;
     if (ratio >= 1.0 || kfid < first_kfid) { if (tid == 0) V.frem[s] = 0; return; }      // (uniform; first_kfid >= 0: a stream without a key-frame leaves here)
@@ -424,34 +412,23 @@ __global__ __launch_bounds__(256) void k_kfm_filter(KfmapView V, const double *r
     (void)kfm_covisibility(V, s, r0, s_tag, s_cov);
     __syncthreads();
     if (tid == 0) {
-        unsigned long long used = 0, valid = 0;
-        int n = 0;
-        for (int b = 0; b < R; b++) if (s_tag[b]) valid |= 1ull << b;
-        for (;;) {                                               // ascending by key-frame id
-            int best = -1;
-            for (int b = 0; b < R; b++) if (b != r0 && s_tag[b] && s_cov[b] > 0 && !(used >> b & 1) && (best < 0 || s_tag[b] < s_tag[best])) best = b;
-            if (best < 0 || s_tag[best] == 1) break;
-            used |= 1ull << best;
-            if (s_tag[best] - 1 < kfid) s_cand[n++] = best;
-        }
-        s_ncand = n; s_valid = valid;
+        unsigned long long valid;
+        s_ncand = kfm_filter_candidates(s_tag, s_cov, R, r0, kfid, s_cand, valid);       // ascending by key-frame id
+        s_valid = valid;
     }
     __syncthreads();
     const int ncand = s_ncand, lane = tid & 63, wv = tid >> 6;
     const unsigned long long valid = s_valid;
-    const size_t pb = (size_t)s * mcap;
     unsigned long long X = 0;
     for (int c = 0; c < ncand; c++) {
         const int rc = s_cand[c];
-        const size_t sl = ((size_t)s * R + rc) * cap;
         const int n = min(V.kn[s * R + rc], cap);
         const unsigned long long seen = valid & ~X;
         int tot = 0, good = 0;
         for (int i = tid; i < n; i += 256) {
-            if (!V.klive[sl + i]) continue;
-            const int64_t id = V.kid[sl + i];
-            const size_t pe = pb + kfm_entry(id, mcap);
-            if (!kfm_valid(V, pe, id) || !(V.pflags[pe] & KFM_3D)) continue;             // an orphan is skipped and left as it is
+            int64_t id;
+            size_t pe;
+            if (!kfm_slab_point(V, s, rc, i, id, pe) || !kfm_valid(V, pe, id) || !(V.pflags[pe] & KFM_3D)) continue;      // an orphan is skipped and left as it is
             tot++; good += __popcll(V.pmask[pe] & seen) > 4;
         }
         for (int o = 32; o; o >>= 1) { tot += __shfl_down(tot, o, 64); good += __shfl_down(good, o, 64); }
@@ -459,7 +436,7 @@ __global__ __launch_bounds__(256) void k_kfm_filter(KfmapView V, const double *r
         __syncthreads();                                         // (two buffers: a wave that writes phase c + 2's sums has passed phase c + 1's barrier, behind every read of phase c's)
         const int n_total = s_tot[c & 1][0] + s_tot[c & 1][1] + s_tot[c & 1][2] + s_tot[c & 1][3];
         const int n_good = s_good[c & 1][0] + s_good[c & 1][1] + s_good[c & 1][2] + s_good[c & 1][3];
-        if (n_total < few || (double)n_good / (double)n_total > ratio) X |= 1ull << rc;
+        if (kfm_filter_removes(n_total, n_good, few, ratio)) X |= 1ull << rc;
     }
     for (unsigned long long m = X; m; m &= m - 1) {              // every phase's reads lie behind its barrier: now the removals, all at once
         const int b = __ffsll((long long)m) - 1, n = min(V.kn[s * R + b], cap);
@@ -486,14 +463,13 @@ __global__ void k_kfm_drop_slot(KfmapView V, int s, int kfid)
 static size_t kfmap_regions(slam_kfmap *km, char *base)
 {
     Layout Lo;
-    auto region = [&](auto *&p, size_t bytes) { const size_t at = Lo.take(bytes); if (base) p = (std::remove_reference_t<decltype(p)>)(base + at); };
     KfmapView &v = km->v;
     const size_t S = v.S, sr = S * v.R, n = sr * v.cap, m = S * v.mcap;
-    region(v.tag, sr * 4); region(v.kn, sr * 4); region(v.ktheta, sr * 48); region(v.kid, n * 8); region(v.kupx, n * 16); region(v.klive, n); region(v.kfresh, S * v.cap);
-    region(v.ptag, m * 8); region(v.pxyz, m * 24); region(v.pmask, m * 8); region(v.pflags, m);
-    region(v.cur, S * 4); region(v.frem, S * 8);
-    region(v.whdr, S * KFM_HDR * 4); region(v.wtag, sr * 4); region(v.worder, sr * 4); region(v.wrank, sr * 4); region(v.wconst, sr * 4); region(v.wcov, S * 8);
-    region(v.wpid, m * 8); region(v.wpmask, m * 8); region(v.wpoff, m * 4); region(v.went, m * 4);
+    Lo.bind(v.tag, sr * 4, base); Lo.bind(v.kn, sr * 4, base); Lo.bind(v.ktheta, sr * 48, base); Lo.bind(v.kid, n * 8, base); Lo.bind(v.kupx, n * 16, base); Lo.bind(v.klive, n, base); Lo.bind(v.kfresh, S * v.cap, base);
+    Lo.bind(v.ptag, m * 8, base); Lo.bind(v.pxyz, m * 24, base); Lo.bind(v.pmask, m * 8, base); Lo.bind(v.pflags, m, base);
+    Lo.bind(v.cur, S * 4, base); Lo.bind(v.frem, S * 8, base);
+    Lo.bind(v.whdr, S * KFM_HDR * 4, base); Lo.bind(v.wtag, sr * 4, base); Lo.bind(v.worder, sr * 4, base); Lo.bind(v.wrank, sr * 4, base); Lo.bind(v.wconst, sr * 4, base); Lo.bind(v.wcov, S * 8, base);
+    Lo.bind(v.wpid, m * 8, base); Lo.bind(v.wpmask, m * 8, base); Lo.bind(v.wpoff, m * 4, base); Lo.bind(v.went, m * 4, base);
     return Lo.size();
 }
 // the streams the gather acts on (those of the last add_keyframe), ascending; returns their number
@@ -504,6 +480,8 @@ static int kfmap_streams(const slam_kfmap *km, int *list)
     return n;
 }
 
+// a call's table of the streams it acts on, into its region of a staging block
+static void kfmap_put_streams(const Region<int> &o_sel, char *h, const int *list, int ns) { memcpy(o_sel.at(h), list, (size_t)ns * 4); }
 // the map's pinned staging block for an enqueue-only call's inputs, at least `bytes` long, once the copy that last read it has completed (an event never
 // recorded is complete); the caller records pin_ev behind its own copy
 static int kfmap_pin(slam_ctx *ctx, slam_kfmap *km, size_t bytes, char **out)
@@ -516,6 +494,31 @@ static int kfmap_pin(slam_ctx *ctx, slam_kfmap *km, size_t bytes, char **out)
         km->pin_bytes = bytes + bytes / 4;
     }
     *out = km->pin;
+    return SLAM_OK;
+}
+// An enqueue-only call's inputs: `bytes` of the map's pinned block, filled by fill(h), copied to scratch (*scr) on the stream, pin_ev recorded behind the
+// copy.  Nothing waits.
+template <class Fill> static int kfmap_upload(slam_ctx *ctx, slam_kfmap *km, size_t bytes, char **scr, Fill fill)
+{
+    char *h;
+    int rc = kfmap_pin(ctx, km, bytes, &h);
+    if (rc) return rc;
+    rc = slam_scratch(ctx, bytes, (void **)scr);
+    if (rc) return rc;
+    fill(h);
+    HIP_TRY(ctx, hipMemcpyAsync(*scr, h, bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(km->pin_ev, ctx->stream));
+    return SLAM_OK;
+}
+// One of the map's long-lived allocations: `bytes` of HBM, zeroed on the stream, waited for.  An error frees the block and fails under the entry point's name.
+static int kfmap_alloc_zeroed(slam_ctx *ctx, const char *who, size_t bytes, char **out)
+{
+    char *base = nullptr;
+    hipError_t e = hipMalloc((void **)&base, bytes);
+    if (e == hipSuccess) e = hipMemsetAsync(base, 0, bytes, ctx->stream);
+    if (e == hipSuccess) e = slam_stream_wait(ctx->stream);
+    if (e != hipSuccess) { if (base) (void)hipFree(base); return slam_fail(ctx, SLAM_ERR_HIP, "%s: %s", who, hipGetErrorString(e)); }
+    *out = base;
     return SLAM_OK;
 }
 
@@ -531,10 +534,9 @@ int slam_kfmap_create(slam_ctx *ctx, int S, int cap, int R, int mcap, slam_kfmap
     slam_kfmap *km = new slam_kfmap();
     km->device = ctx->device; km->v.S = S; km->v.cap = cap; km->v.R = R; km->v.mcap = mcap;
     km->bytes = kfmap_regions(km, nullptr);
-    hipError_t e = hipMalloc((void **)&km->base, km->bytes);
-    if (e == hipSuccess) e = hipMemsetAsync(km->base, 0, km->bytes, ctx->stream);
-    if (e == hipSuccess) e = slam_stream_wait(ctx->stream);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&km->pin_ev, hipEventDisableTiming);
+    const int rc = kfmap_alloc_zeroed(ctx, "slam_kfmap_create", km->bytes, &km->base);
+    if (rc) { slam_kfmap_destroy(km); return rc; }
+    const hipError_t e = hipEventCreateWithFlags(&km->pin_ev, hipEventDisableTiming);
     if (e != hipSuccess) { slam_kfmap_destroy(km); return slam_fail(ctx, SLAM_ERR_HIP, "slam_kfmap_create: %s", hipGetErrorString(e)); }
     kfmap_regions(km, km->base);
     *out = km;
@@ -600,7 +602,7 @@ int slam_kfmap_ba_gather(slam_ctx *ctx, slam_kfmap *km, const int32_t *min_cov_s
     if (rc) return rc;
     rc = slam_pinned(ctx, std::max<size_t>(D.size(), (size_t)S * KFM_HDR * 4), (void **)&h);
     if (rc) return rc;
-    memcpy(o_sel.at(h), list, (size_t)ns * 4); memcpy(o_minc.at(h), min_cov_score, (size_t)S * 4);
+    kfmap_put_streams(o_sel, h, list, ns); memcpy(o_minc.at(h), min_cov_score, (size_t)S * 4);
     HIP_TRY(ctx, hipMemcpyAsync(scr, h, in_b, hipMemcpyHostToDevice, ctx->stream));
     { ProfScope span(ctx, "kfmap_gather_plan");
       hipLaunchKernelGGL(k_kfm_plan, dim3(ns), dim3(256), 0, ctx->stream, V, (const int *)o_minc.at(scr), (const int *)o_sel.at(scr)); }
@@ -675,14 +677,11 @@ int slam_kfmap_ba_update(slam_ctx *ctx, slam_kfmap *km, slam_kpset *ks, int n_wi
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     Layout D;
     const auto o_win = D.take<KfmUpd>(n_windows); const auto o_th = D.take<double>((size_t)nT); const auto o_ol = D.take<uint8_t>((size_t)nO);
-    char *scr, *h;
-    int rc = kfmap_pin(ctx, km, D.size(), &h);
+    char *scr;
+    int rc = kfmap_upload(ctx, km, D.size(), &scr, [&](char *h) {
+        memcpy(o_win.at(h), wins.data(), o_win.bytes()); memcpy(o_th.at(h), theta, o_th.bytes()); memcpy(o_ol.at(h), outliers, o_ol.bytes());
+    });
     if (rc) return rc;
-    rc = slam_scratch(ctx, D.size(), (void **)&scr);
-    if (rc) return rc;
-    memcpy(o_win.at(h), wins.data(), o_win.bytes()); memcpy(o_th.at(h), theta, o_th.bytes()); memcpy(o_ol.at(h), outliers, o_ol.bytes());
-    HIP_TRY(ctx, hipMemcpyAsync(scr, h, D.size(), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipEventRecord(km->pin_ev, ctx->stream));
     const KfmUpd *wd = o_win.at(scr);
     uint8_t *flags = nullptr;
     if (ks) {
@@ -716,13 +715,10 @@ int slam_kfmap_filter(slam_ctx *ctx, slam_kfmap *km, const double *filtering_rat
     Layout D;
     const auto o_sel = D.take<int>(S), o_minc = D.take<int>(S); const auto o_ratio = D.take<double>(S);
     char *scr, *h;
-    int rc = kfmap_pin(ctx, km, D.size(), &h);
+    int rc = kfmap_upload(ctx, km, D.size(), &scr, [&](char *h) {
+        kfmap_put_streams(o_sel, h, list, ns); memcpy(o_minc.at(h), min_cov_score, (size_t)S * 4); memcpy(o_ratio.at(h), filtering_ratio, (size_t)S * 8);
+    });
     if (rc) return rc;
-    rc = slam_scratch(ctx, D.size(), (void **)&scr);
-    if (rc) return rc;
-    memcpy(o_sel.at(h), list, (size_t)ns * 4); memcpy(o_minc.at(h), min_cov_score, (size_t)S * 4); memcpy(o_ratio.at(h), filtering_ratio, (size_t)S * 8);
-    HIP_TRY(ctx, hipMemcpyAsync(scr, h, D.size(), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipEventRecord(km->pin_ev, ctx->stream));
     { ProfScope span(ctx, "kfmap_filter");
       hipLaunchKernelGGL(k_kfm_filter, dim3(ns), dim3(256), 0, ctx->stream, V, (const double *)o_ratio.at(scr), (const int *)o_minc.at(scr), first_kfid, (const int *)o_sel.at(scr)); }
     HIP_TRY(ctx, hipGetLastError());

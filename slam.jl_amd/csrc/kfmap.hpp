@@ -1,6 +1,9 @@
 // kfmap.hpp -- the per-stream key-frame map of S lock-stepped streams (slam_kfmap, kfmap.hip): what the estimator's _get_ba_parameters /
 // _update_ba_parameters! (src/estimator.jl:143-306) read and write of the map manager's dictionaries, held in HBM beside the keypoint lists.
 //
+// The integer logic of the map (entry of an id, search in a slab, the serial decisions over a ring's slots) is kfmap_ring.hpp, included below: plain C++
+// for host and device.  Every allocation's regions are named once, in a *_regions(km, base) function built on Layout::bind (layout.hpp).
+//
 // ONE allocation, every region starting on a 256-byte boundary (Layout); with n = S R cap, m = S mcap its size is the sum, each term rounded up to 256, of
 //   ring    tag 4 S R | n_kf 4 S R | theta 48 S R | ids 8 n | upx 16 n | live n | fresh S cap
 //   table   tag 8 m | xyz 24 m | observers 8 m | flags m
@@ -83,12 +86,12 @@
 //   tombstones    a tombstone whose id equals an arriving new_id is dropped from the slab (a lower bound must not land on it); the slab shrinks by one
 #pragma once
 #include "kpset.hpp"
+#include "kfmap_ring.hpp"
 #include "lmm_host.hpp"
 
 constexpr int KFM_MAX_R = 64;
 constexpr uint8_t KFM_3D = 1, KFM_OBS = 2, KFM_BA = 4, KFM_GONE = 8, KFM_DEAD = 16;
 constexpr int KFM_HDR = 8;            // ints per pending-window header: status, kfid, P, M, O, min_cov_score, number of bad points, 0
-constexpr int N_COVISIBLE = 5;        // local_bundle_adjustment!: up to 5 latest covisible key-frames (estimator.jl:317-335)
 
 // passed by value to every kernel of kfmap.hip: the order of the members is their kernel-argument layout
 struct KfmapView {
@@ -135,6 +138,16 @@ struct KfmLm {
     int32_t *cnt;                         // [S][2] N, M of the last staging (0, 0 unless status 0)
     int32_t *status, *rn; int64_t *rpairs; double *rdist;        // results, one block: [S] | [S] | [S cap][2] | [S cap]
 };
+
+// the match kernel's argument block over the staged regions
+inline LmmDev kfm_lmm_dev(const KfmLm &Q)
+{
+    LmmDev L;
+    L.st = Q.st; L.kp_yx = Q.kp_yx; L.kp_desc_off = Q.kp_doff; L.kp_desc = Q.kp_desc; L.kp_obs_off = Q.kp_ooff; L.kp_obs_kf = Q.kp_okf; L.kp_obs_yx = Q.kp_oyx;
+    L.kf_Tcw = Q.kf_Tcw; L.mp_xyz = Q.mp_xyz; L.mp_desc_off = Q.mp_doff; L.mp_desc = Q.mp_desc; L.mp_obs_off = Q.mp_ooff; L.mp_obs_kf = Q.mp_okf;
+    L.cell_off = Q.cell_off; L.cell_kp = Q.cell_kp; L.best_kp = Q.best_kp; L.best_dist = Q.best_dist; L.proj = Q.proj; L.keys = Q.keys;
+    return L;
+}
 
 // the local-map history's regions (above), by value to k_kfm_lm_stage_hist
 struct KfmHist {

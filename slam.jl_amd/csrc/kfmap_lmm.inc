@@ -4,6 +4,7 @@
 // the match kernel of localmap.hip runs on it unchanged (lmm_launch), a closing pass turns the keypoints' keys into id pairs.  Between the upload of the
 // call's arguments and the one copy of results nothing returns to the host.  tests/np_kfmap_local_map.py is the model.  With the local-map history
 // (slam_kfmap_enable_local_map_history) the stager also keeps frame.local_map_ids per key-frame: kfm_lm_history below, tests/np_kfmap_local_map_history.py.
+// The stager's serial decisions (kfm_rank_slots, kfm_oldest_covisible, kfm_history_rule) are kfmap_ring.hpp's, the frame constants lmm_host.hpp's lmm_frame.
 
 // ---- descriptors: slot-parallel, one thread per appended keypoint (grid.y = stream) ---------------------------------------------------------------------
 // row j of stream s belongs to id info[2 s] + j (slam_kpset_detect_describe); it is stored where the table entry carries that id
@@ -14,7 +15,7 @@ __global__ __launch_bounds__(256) void k_kfm_desc_record(KfmapView V, const uint
     if (j >= dcap || (int64_t)j >= n) return;
     const int64_t id = info[2 * s] + j;
     const size_t pe = (size_t)s * V.mcap + kfm_entry(id, V.mcap);
-    if (V.ptag[pe] != (unsigned long long)id + 1ull) return;                    // a larger id holds the entry (or the id was never recorded): no point, no descriptor
+    if (!kfm_owned(V, pe, id)) return;                                          // a larger id holds the entry (or the id was never recorded): no point, no descriptor
     const uint64_t *src = desc + 4 * ((size_t)s * dcap + j);
     for (int k = 0; k < 4; k++) V.ddesc[4 * pe + k] = src[k];
     V.dhas[pe] = 1;
@@ -44,8 +45,7 @@ __device__ __forceinline__ void kfm_lm_history(const KfmapView &V, const KfmLm &
     unsigned long long *H = Hs.bits + (size_t)s * Hs.W * R;
     int *htag = Hs.htag + s * R;
     const bool own = htag[r0] == kfid + 1;                                      // the slot's set is this key-frame's: the match runs again for it
-    int oldest = -1;                                                            // the covisible key-frame with the smallest id
-    for (unsigned long long cm = covmask; cm; cm &= cm - 1) { const int b = __ffsll((long long)cm) - 1; if (oldest < 0 || s_tag[b] < s_tag[oldest]) oldest = b; }
+    const int oldest = kfm_oldest_covisible(covmask, s_tag);                    // the covisible key-frame with the smallest id
     const bool linked = oldest >= 0 && htag[oldest] == s_tag[oldest];
     if (tid < 3) s_len[tid] = 0;
     __syncthreads();                                                            // (also: every thread has read htag[r0] before it is written below)
@@ -70,9 +70,8 @@ __device__ __forceinline__ void kfm_lm_history(const KfmapView &V, const KfmLm &
     }
     if (lane == 0) { atomicAdd(&s_len[0], nC); atomicAdd(&s_len[1], nP); atomicAdd(&s_len[2], nU); }
     __syncthreads();
-    const bool replace = 2 * s_len[0] > s_len[1];                               // len(C) > 0.5 len(P), exact in integers
-    const int size = replace ? s_len[0] : s_len[2];
-    const bool chain = covmask != 0 && size < Q.max_local && linked;
+    bool replace, chain;
+    (void)kfm_history_rule(s_len[0], s_len[1], s_len[2], covmask, linked, Q.max_local, replace, chain);
     for (int e0 = wv * 64; e0 < mcap; e0 += 256) {
         const int e = e0 + lane, w = e0 >> 6;
         const unsigned long long cw = __ballot(e < mcap && Q.mark[pb + e] != 0);
@@ -131,15 +130,8 @@ __device__ __forceinline__ void kfm_lm_stage_body(const KfmapView &V, const KfmL
     __syncthreads();
     if (tid == 0) {
         unsigned long long cov = 0;
-        int nv = 0;
-        for (int b = 0; b < R; b++) {
-            if (!s_tag[b]) continue;
-            if (b != r0 && s_cov[b] > 0) cov |= 1ull << b;
-            int rank = 0;
-            for (int c = 0; c < R; c++) rank += s_tag[c] && s_tag[c] < s_tag[b];
-            s_rank[b] = rank; s_asc[rank] = b; nv++;
-        }
-        s_covmask = cov; s_nv = nv;
+        for (int b = 0; b < R; b++) if (s_tag[b] && b != r0 && s_cov[b] > 0) cov |= 1ull << b;
+        s_covmask = cov; s_nv = kfm_rank_slots(s_tag, R, s_rank, s_asc);
     }
     for (int e = tid; e < mcap; e += 256) Q.mark[pb + e] = 0;
     __syncthreads();
@@ -148,12 +140,10 @@ __device__ __forceinline__ void kfm_lm_stage_body(const KfmapView &V, const KfmL
     if (!HIST && covmask == 0) KFM_LM_LEAVE(1)
     for (unsigned long long cm = covmask; cm; cm &= cm - 1) {
         const int b = __ffsll((long long)cm) - 1, n = min(V.kn[s * R + b], cap);
-        const size_t sl = ((size_t)s * R + b) * cap;
         for (int i = tid; i < n; i += 256) {
-            if (!V.klive[sl + i]) continue;
-            const int64_t id = V.kid[sl + i];
-            const size_t pe = pb + kfm_entry(id, mcap);
-            if (!kfm_valid(V, pe, id) || !(V.pflags[pe] & KFM_3D) || !V.dhas[pe] || (V.pmask[pe] >> r0 & 1)) continue;
+            int64_t id;
+            size_t pe;
+            if (!kfm_slab_point(V, s, b, i, id, pe) || !kfm_valid(V, pe, id) || !(V.pflags[pe] & KFM_3D) || !V.dhas[pe] || (V.pmask[pe] >> r0 & 1)) continue;
             Q.mark[pe] = 1;
         }
     }
@@ -188,7 +178,7 @@ __device__ __forceinline__ void kfm_lm_stage_body(const KfmapView &V, const KfmL
         size_t pe = 0;
         if (m < M) {
             pe = pb + kfm_entry(Q.mp_id[mp0 + m], mcap);
-            for (unsigned long long mm = V.pmask[pe]; mm; mm &= mm - 1) { const int b = __ffsll((long long)mm) - 1; if (b < R && s_tag[b]) wm |= 1ull << b; }
+            kfm_each_observer(V.pmask[pe], s_tag, R, [&](int b) { wm |= 1ull << b; });
         }
         const int off = kfm_scan(__popcll(wm), s_w, &s_obase);
         if (m < M) {
@@ -212,15 +202,8 @@ __device__ __forceinline__ void kfm_lm_stage_body(const KfmapView &V, const KfmL
             int64_t id = 0;
             size_t pe = 0;
             unsigned long long wm = 0;
-            if (i < n0 && V.klive[sl + i]) {
-                id = V.kid[sl + i]; pe = pb + kfm_entry(id, mcap);
-                acc = kfm_valid(V, pe, id) && V.dhas[pe];
-            }
-            if (acc)
-                for (unsigned long long mm = V.pmask[pe]; mm; mm &= mm - 1) {
-                    const int b = __ffsll((long long)mm) - 1;
-                    if (b < R && s_tag[b] && kfm_find_live(V, s, b, id) >= 0) wm |= 1ull << b;
-                }
+            if (i < n0 && kfm_slab_point(V, s, r0, i, id, pe)) acc = kfm_valid(V, pe, id) && V.dhas[pe];
+            if (acc) wm = kfm_live_observers(V, s, V.pmask[pe], s_tag, id);
             const int pos = ordered_slot(acc, s_w, &s_base);
             const int off = kfm_scan(__popcll(wm), s_w, &s_obase);
             if (acc) {
@@ -243,11 +226,7 @@ __device__ __forceinline__ void kfm_lm_stage_body(const KfmapView &V, const KfmL
     if (tid == 0) { Q.kp_doff[kp0 + N] = kp0 + N; Q.kp_ooff[kp0 + N] = kobs0 + s_obase; }
     __syncthreads();
     if (N == 0) KFM_LM_LEAVE(1)
-    if (tid < R && s_tag[tid]) {
-        double *K = Q.kf_Tcw + 16 * (size_t)(kf0 + s_rank[tid]);
-        angles_to_pose(V.ktheta + 6 * ((size_t)s * R + tid), K);
-        K[3] = 0.0; K[7] = 0.0; K[11] = 0.0; K[15] = 1.0;
-    }
+    if (tid < R && s_tag[tid]) kfm_tcw(V.ktheta + 6 * ((size_t)s * R + tid), Q.kf_Tcw + 16 * (size_t)(kf0 + s_rank[tid]));
     // the cell lists (lmm_emit's counting sort)
     const int cells = A.gr * A.gc;
     int32_t *co = Q.cell_off + cell0, *cc = Q.cell_cur + cell0, *ck = Q.cell_kp + kp0;
@@ -280,8 +259,7 @@ __device__ __forceinline__ void kfm_lm_stage_body(const KfmapView &V, const KfmL
         __syncthreads();
     }
     if (tid == 0) {
-        angles_to_pose(V.ktheta + 6 * ((size_t)s * R + r0), T.Tcw);
-        T.Tcw[3] = 0.0; T.Tcw[7] = 0.0; T.Tcw[11] = 0.0; T.Tcw[15] = 1.0;
+        kfm_tcw(V.ktheta + 6 * ((size_t)s * R + r0), T.Tcw);
         T.fx = A.cam[0]; T.fy = A.cam[1]; T.cx = A.cam[2]; T.cy = A.cam[3]; T.k1 = A.cam[4]; T.k2 = A.cam[5]; T.p1 = A.cam[6]; T.p2 = A.cam[7];
         T.H = A.cam[8]; T.W = A.cam[9];
         T.max_proj = nb3 < 30 ? A.max_proj * 2.0 : A.max_proj;                   // mapper.jl:332, nb_3d from the slab
@@ -325,24 +303,41 @@ __global__ __launch_bounds__(256) void k_kfm_lm_pairs(KfmapView V, KfmLm Q, cons
     if (tid == 0) Q.rn[s] = s_base;
 }
 
+// the descriptor store's and the history's regions, each named once (kfmap.hpp has the formulas)
+static size_t kfmap_desc_regions(slam_kfmap *km, char *base)
+{
+    Layout Lo;
+    const size_t m = (size_t)km->v.S * km->v.mcap;
+    Lo.bind(km->v.ddesc, m * 32, base); Lo.bind(km->v.dhas, m, base);
+    return Lo.size();
+}
+static size_t kfmap_hist_regions(slam_kfmap *km, char *base)
+{
+    Layout Lo;
+    const KfmapView &v = km->v;
+    KfmHist &hs = km->hs;
+    const size_t W = ((size_t)v.mcap + 63) / 64;
+    Lo.bind(hs.bits, (size_t)v.S * W * v.R * 8, base); Lo.bind(hs.htag, (size_t)v.S * v.R * 4, base); Lo.bind(hs.shadow, (size_t)v.S * v.mcap * 8, base);
+    if (base) hs.W = (int)W;
+    return Lo.size();
+}
 // every region of the staging allocation, each named once (kfmap.hpp has the formula); the results last, one block
 static size_t kfmap_lm_regions(slam_kfmap *km, int max_local, int C1, char *base)
 {
     Layout Lo;
-    auto region = [&](auto *&p, size_t bytes) { const size_t at = Lo.take(bytes); if (base) p = (std::remove_reference_t<decltype(p)>)(base + at); };
     const KfmapView &v = km->v;
     KfmLm &q = km->lm;
     const size_t S = v.S, N1 = (size_t)v.cap + 1, M1 = (size_t)max_local + 1, n = S * N1, m = S * M1, R = v.R;
     q.N1 = (int)N1; q.M1 = (int)M1; q.C1 = C1; q.max_local = max_local;
-    region(q.st, S * sizeof(LmmStream));
-    region(q.kp_yx, n * 16); region(q.kp_doff, n * 4); region(q.kp_desc, n * 32); region(q.kp_ooff, n * 4); region(q.kp_okf, n * R * 4); region(q.kp_oyx, n * R * 16);
-    region(q.kp_id, n * 8); region(q.kf_Tcw, S * R * 128);
-    region(q.mp_xyz, m * 24); region(q.mp_doff, m * 4); region(q.mp_desc, m * 32); region(q.mp_ooff, m * 4); region(q.mp_okf, m * R * 4); region(q.mp_id, m * 8);
-    region(q.cell_off, S * (size_t)C1 * 4); region(q.cell_kp, n * 4); region(q.cell_cur, S * (size_t)C1 * 4);
-    region(q.best_kp, m * 4); region(q.best_dist, m * 8); region(q.proj, m * 16); region(q.keys, n * 8);
-    region(q.mark, S * (size_t)v.mcap * 4); region(q.cnt, S * 8);
+    Lo.bind(q.st, S * sizeof(LmmStream), base);
+    Lo.bind(q.kp_yx, n * 16, base); Lo.bind(q.kp_doff, n * 4, base); Lo.bind(q.kp_desc, n * 32, base); Lo.bind(q.kp_ooff, n * 4, base); Lo.bind(q.kp_okf, n * R * 4, base); Lo.bind(q.kp_oyx, n * R * 16, base);
+    Lo.bind(q.kp_id, n * 8, base); Lo.bind(q.kf_Tcw, S * R * 128, base);
+    Lo.bind(q.mp_xyz, m * 24, base); Lo.bind(q.mp_doff, m * 4, base); Lo.bind(q.mp_desc, m * 32, base); Lo.bind(q.mp_ooff, m * 4, base); Lo.bind(q.mp_okf, m * R * 4, base); Lo.bind(q.mp_id, m * 8, base);
+    Lo.bind(q.cell_off, S * (size_t)C1 * 4, base); Lo.bind(q.cell_kp, n * 4, base); Lo.bind(q.cell_cur, S * (size_t)C1 * 4, base);
+    Lo.bind(q.best_kp, m * 4, base); Lo.bind(q.best_dist, m * 8, base); Lo.bind(q.proj, m * 16, base); Lo.bind(q.keys, n * 8, base);
+    Lo.bind(q.mark, S * (size_t)v.mcap * 4, base); Lo.bind(q.cnt, S * 8, base);
     km->lm_res_off = Lo.size();
-    region(q.status, S * 4); region(q.rn, S * 4); region(q.rpairs, S * (size_t)v.cap * 16); region(q.rdist, S * (size_t)v.cap * 8);
+    Lo.bind(q.status, S * 4, base); Lo.bind(q.rn, S * 4, base); Lo.bind(q.rpairs, S * (size_t)v.cap * 16, base); Lo.bind(q.rdist, S * (size_t)v.cap * 8, base);
     km->lm_res_bytes = Lo.size() - km->lm_res_off;
     return Lo.size();
 }
@@ -355,15 +350,9 @@ int slam_kfmap_enable_descriptors(slam_ctx *ctx, slam_kfmap *km, int n_bits)
     if (n_bits != 256) return slam_fail(ctx, SLAM_ERR_ARG, "slam_kfmap_enable_descriptors: n_bits = %d, the local-map match handles 256-bit descriptors only", n_bits);
     if (km->dbase) return SLAM_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t m = (size_t)km->v.S * km->v.mcap;
-    Layout Lo;
-    const size_t o_desc = Lo.take(m * 32), o_has = Lo.take(m);
-    char *base = nullptr;
-    HIP_TRY(ctx, hipMalloc((void **)&base, Lo.size()));
-    hipError_t e = hipMemsetAsync(base, 0, Lo.size(), ctx->stream);
-    if (e == hipSuccess) e = slam_stream_wait(ctx->stream);
-    if (e != hipSuccess) { (void)hipFree(base); return slam_fail(ctx, SLAM_ERR_HIP, "slam_kfmap_enable_descriptors: %s", hipGetErrorString(e)); }
-    km->dbase = base; km->v.ddesc = (uint64_t *)(base + o_desc); km->v.dhas = (uint8_t *)(base + o_has);
+    const int rc = kfmap_alloc_zeroed(ctx, "slam_kfmap_enable_descriptors", kfmap_desc_regions(km, nullptr), &km->dbase);
+    if (rc) return rc;
+    kfmap_desc_regions(km, km->dbase);
     return SLAM_OK;
 }
 
@@ -372,17 +361,10 @@ int slam_kfmap_enable_local_map_history(slam_ctx *ctx, slam_kfmap *km)
     ARG_TRY(ctx, ctx != nullptr && km != nullptr);
     if (km->hs_base) return SLAM_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const KfmapView &V = km->v;
-    const size_t W = ((size_t)V.mcap + 63) / 64;
-    Layout Lo;
-    const size_t o_bits = Lo.take((size_t)V.S * W * V.R * 8), o_tag = Lo.take((size_t)V.S * V.R * 4), o_shadow = Lo.take((size_t)V.S * V.mcap * 8);
-    char *base = nullptr;
-    HIP_TRY(ctx, hipMalloc((void **)&base, Lo.size()));
-    hipError_t e = hipMemsetAsync(base, 0, Lo.size(), ctx->stream);           // empty sets without owners; the first match brings the shadow up to the table
-    if (e == hipSuccess) e = slam_stream_wait(ctx->stream);
-    if (e != hipSuccess) { (void)hipFree(base); return slam_fail(ctx, SLAM_ERR_HIP, "slam_kfmap_enable_local_map_history: %s", hipGetErrorString(e)); }
-    km->hs.bits = (unsigned long long *)(base + o_bits); km->hs.htag = (int *)(base + o_tag); km->hs.shadow = (unsigned long long *)(base + o_shadow);
-    km->hs.W = (int)W; km->hs_bytes = Lo.size(); km->hs_base = base;
+    km->hs_bytes = kfmap_hist_regions(km, nullptr);                             // zeroed: empty sets without owners; the first match brings the shadow up to the table
+    const int rc = kfmap_alloc_zeroed(ctx, "slam_kfmap_enable_local_map_history", km->hs_bytes, &km->hs_base);
+    if (rc) return rc;
+    kfmap_hist_regions(km, km->hs_base);
     return SLAM_OK;
 }
 
@@ -426,14 +408,9 @@ int slam_kfmap_add_descriptors(slam_ctx *ctx, slam_kfmap *km, const uint64_t *de
     if (ns == 0) return SLAM_OK;
     const int *sel = nullptr;
     if (km->n_sel != KPSEL_ALL) {                                // the streams of the last add_keyframe, staged like the filter's table
-        char *scr, *h;
-        int rc = kfmap_pin(ctx, km, (size_t)ns * 4, &h);
+        char *scr;
+        const int rc = kfmap_upload(ctx, km, (size_t)ns * 4, &scr, [&](char *h) { kfmap_put_streams(Region<int>{0, (size_t)ns}, h, list, ns); });
         if (rc) return rc;
-        rc = slam_scratch(ctx, (size_t)ns * 4, (void **)&scr);
-        if (rc) return rc;
-        memcpy(h, list, (size_t)ns * 4);
-        HIP_TRY(ctx, hipMemcpyAsync(scr, h, (size_t)ns * 4, hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipEventRecord(km->pin_ev, ctx->stream));
         sel = (const int *)scr;
     }
     { ProfScope span(ctx, "kfmap_add_descriptors");
@@ -461,14 +438,13 @@ int slam_kfmap_local_map_match(slam_ctx *ctx, slam_kfmap *km, const double *cam,
             return slam_fail(ctx, SLAM_ERR_ARG, "slam_kfmap_local_map_match: stream %d has lens distortion (%g %g %g %g); the map's pixels are undistorted", s, c[4], c[5], c[6], c[7]);
         const double H = c[8], W = c[9];
         const int cell = cell_size[s];
-        if (cell < 1 || !(H >= 1.0) || !(W >= 1.0) || H > 65536.0 || W > 65536.0 || !(c[0] > 0.0) || !(c[1] > 0.0))
+        LmmFrame F;
+        if (!lmm_frame(c, cell, max_descriptor_distance[s], F) || !(c[0] > 0.0) || !(c[1] > 0.0))
             return slam_fail(ctx, SLAM_ERR_ARG, "slam_kfmap_local_map_match: stream %d: cell_size %d / image %g x %g / focal lengths %g %g out of range", s, cell, H, W, c[0], c[1]);
         memcpy(A.cam, c, sizeof A.cam);
         A.max_proj = max_projection_distance[s];
-        A.start = 256.0 * max_descriptor_distance[s];                              // mapper.jl:401
-        const double vfov = 0.5 * H / c[1], hfov = 0.5 * W / c[0];                 // mapper.jl:326-329, as lmm_emit
-        A.view_thr = std::cos(vfov > hfov ? std::atan(vfov) : std::atan(hfov));
-        A.cell = cell; A.gr = (int)std::ceil(H / cell); A.gc = (int)std::ceil(W / cell); A.pad = 0;
+        A.start = F.start; A.view_thr = F.view_thr;
+        A.cell = cell; A.gr = F.gr; A.gc = F.gc; A.pad = 0;
         if ((long long)A.gr * A.gc > (1 << 22)) return slam_fail(ctx, SLAM_ERR_ARG, "slam_kfmap_local_map_match: stream %d: a grid of %d x %d cells", s, A.gr, A.gc);
         C1 = std::max(C1, A.gr * A.gc + 1);
     }
@@ -496,11 +472,8 @@ int slam_kfmap_local_map_match(slam_ctx *ctx, slam_kfmap *km, const double *cam,
     if (rc) return rc;
     rc = slam_pinned(ctx, D.size(), (void **)&h);
     if (rc) return rc;
-    memcpy(o_sel.at(h), list, (size_t)ns * 4); memcpy(o_arg.at(h), args.data(), o_arg.bytes());
-    LmmDev L;
-    L.st = Q.st; L.kp_yx = Q.kp_yx; L.kp_desc_off = Q.kp_doff; L.kp_desc = Q.kp_desc; L.kp_obs_off = Q.kp_ooff; L.kp_obs_kf = Q.kp_okf; L.kp_obs_yx = Q.kp_oyx;
-    L.kf_Tcw = Q.kf_Tcw; L.mp_xyz = Q.mp_xyz; L.mp_desc_off = Q.mp_doff; L.mp_desc = Q.mp_desc; L.mp_obs_off = Q.mp_ooff; L.mp_obs_kf = Q.mp_okf;
-    L.cell_off = Q.cell_off; L.cell_kp = Q.cell_kp; L.best_kp = Q.best_kp; L.best_dist = Q.best_dist; L.proj = Q.proj; L.keys = Q.keys;
+    kfmap_put_streams(o_sel, h, list, ns); memcpy(o_arg.at(h), args.data(), o_arg.bytes());
+    const LmmDev L = kfm_lmm_dev(Q);
     const int *sel = o_sel.at(scr);
     { ProfScope span(ctx, "kfmap_local_map_match");
       HIP_TRY(ctx, hipMemcpyAsync(scr, h, in_b, hipMemcpyHostToDevice, ctx->stream));
@@ -513,11 +486,10 @@ int slam_kfmap_local_map_match(slam_ctx *ctx, slam_kfmap *km, const double *cam,
       HIP_TRY(ctx, hipGetLastError());
       HIP_TRY(ctx, hipMemcpyAsync(h + o_res, km->lm_base + km->lm_res_off, km->lm_res_bytes, hipMemcpyDeviceToHost, ctx->stream)); }
     HIP_TRY(ctx, slam_stream_wait(ctx->stream));
-    const char *res = h + o_res;
-    const int32_t *st = (const int32_t *)(res + ((char *)Q.status - (km->lm_base + km->lm_res_off)));
-    const int32_t *rn = (const int32_t *)(res + ((char *)Q.rn - (km->lm_base + km->lm_res_off)));
-    const int64_t *rp = (const int64_t *)(res + ((char *)Q.rpairs - (km->lm_base + km->lm_res_off)));
-    const double *rd = (const double *)(res + ((char *)Q.rdist - (km->lm_base + km->lm_res_off)));
+    auto result = [&](const auto *p) { return (decltype(p))(h + o_res + ((const char *)p - (km->lm_base + km->lm_res_off))); };        // a result region in the host's copy of the block
+    const int32_t *st = result(Q.status), *rn = result(Q.rn);
+    const int64_t *rp = result(Q.rpairs);
+    const double *rd = result(Q.rdist);
     long long total = 0;
     for (int k = 0; k < ns; k++) { const int s = list[k]; status[s] = st[s]; n_pairs[s] = st[s] == 0 ? rn[s] : 0; total += n_pairs[s]; km->lm_np[s] = n_pairs[s]; }
     if (total > cap_pairs) return slam_fail(ctx, SLAM_ERR_CAPACITY, "slam_kfmap_local_map_match: %lld pairs but cap_pairs = %d", total, cap_pairs);

@@ -2,7 +2,7 @@
 // map_manager.jl:378-427, frame.jl:290-307) on the key-frame map.  The pairs (prev_id, new_id) of a local-map match -- where they lie in HBM, or a
 // caller's -- are applied in HBM: a keypoint is renamed in every key-frame that observes it, and because every slab and every live list is sorted by id
 // (kfm_find is a binary search) the touched slabs and lists are rebuilt in order.  tests/np_kfmap_merge.py is the model; kfmap.hpp has the scratch
-// allocation's formula and the deviations.
+// allocation's formula and the deviations; kfm_find, kfm_lower and the one-to-one rule of the pairs (device and host form) are kfmap_ring.hpp's.
 //
 // Three kernels, no workgroup waits for another, nothing returns to the host between them:
 //   k_kfm_merge_resolve   one workgroup per stream: the pairs are checked (one-to-one), each pair by one thread: validity, then for every observer slab of
@@ -37,13 +37,6 @@ __device__ __forceinline__ int kfm_pairs_of(const KfmPairs &P, int s, const int6
 __device__ __forceinline__ KfmRename kfm_rename_of(const KfmMerge &G, size_t z, int cap)
 {
     return {G.rn_pos + z * cap, G.rn_id + z * cap, G.rs_id + z * cap, G.rank_at + z * cap, G.kept + z * ((size_t)cap + 1)};
-}
-// first index of ids[0 .. n) (ascending) whose id is not below `id`
-__device__ __forceinline__ int kfm_lower(const int64_t *ids, int n, int64_t id)
-{
-    int lo = 0, hi = n;
-    while (lo < hi) { const int mid = (lo + hi) >> 1; if (ids[mid] < id) lo = mid + 1; else hi = mid; }
-    return lo;
 }
 // The plan of a rebuild, by the whole workgroup: ids[0 .. n) ascending, k <= n renames in Z.pos / Z.id; live == nullptr: no tombstones (a list).
 // Returns the new length.  Ends behind a barrier: Z.sid, Z.rank and Z.kept are the workgroup's to read.
@@ -95,12 +88,7 @@ __global__ __launch_bounds__(256) void k_kfm_merge_resolve(KfmapView V, KfmMerge
     if (tid <= R) s_cnt[tid] = 0;
     if (tid == 0) { s_bad = 0; s_stat[0] = 0; s_stat[1] = 0; s_stat[2] = 0; }
     __syncthreads();
-    for (int t = tid; t < n; t += 256) {
-        const int64_t a = pr[2 * t], b = pr[2 * t + 1];
-        bool bad = false;
-        for (int u = 0; u < n; u++) if (u != t) { const int64_t a2 = pr[2 * u], b2 = pr[2 * u + 1]; bad |= a2 == a || b2 == b || a2 == b; }
-        if (bad) s_bad = 1;
-    }
+    for (int t = tid; t < n; t += 256) if (kfm_pair_clashes(pr, n, t)) s_bad = 1;
     __syncthreads();
     if (s_bad) {                                                 // (uniform) an argument error of the device form: the stream is left as it is
         for (int t = tid; t < n; t += 256) G.applied[(size_t)s * cap + t] = 0;
@@ -118,7 +106,7 @@ __global__ __launch_bounds__(256) void k_kfm_merge_resolve(KfmapView V, KfmMerge
         unsigned long long add = 0;
         bool obs = false;
         int nr = 0;
-        for (unsigned long long mm = V.pmask[pe]; mm; mm &= mm - 1) {
+        for (unsigned long long mm = V.pmask[pe]; mm; mm &= mm - 1) {          // (kfm_each_observer's walk, spelled out: through it this kernel loses a wave per SIMD to SGPRs)
             const int b = __ffsll((long long)mm) - 1;
             if (b >= R || !V.tag[s * R + b]) continue;
             const int i = kfm_find_live(V, s, b, prev);
@@ -212,15 +200,14 @@ __global__ __launch_bounds__(256) void k_kfm_merge_list(KfmapView V, KpsetView K
 static size_t kfmap_merge_regions(slam_kfmap *km, char *base)
 {
     Layout Lo;
-    auto region = [&](auto *&p, size_t bytes) { const size_t at = Lo.take(bytes); if (base) p = (std::remove_reference_t<decltype(p)>)(base + at); };
     const KfmapView &v = km->v;
     KfmMerge &g = km->mg;
     const size_t S = v.S, cap = v.cap, Z = S * ((size_t)v.R + 1), n = S * v.R * cap, l = S * cap;
-    region(g.cnt, Z * 4); region(g.rn_pos, Z * cap * 4); region(g.rn_id, Z * cap * 8); region(g.rs_id, Z * cap * 8); region(g.rank_at, Z * cap * 4); region(g.kept, Z * (cap + 1) * 4);
-    region(g.t_id, n * 8); region(g.t_upx, n * 16); region(g.t_live, n);
-    region(g.applied, l); region(g.stat, S * 16);
-    region(g.q_yx, l * 16); region(g.q_syx, l * 16); region(g.q_xyz, l * 24); region(g.q_kyx, l * 16); region(g.q_fyx, l * 16); region(g.q_id, l * 8);
-    region(g.q_is3d, l); region(g.q_stereo, l); region(g.q_haskf, l); region(g.q_fkf, l * 4);
+    Lo.bind(g.cnt, Z * 4, base); Lo.bind(g.rn_pos, Z * cap * 4, base); Lo.bind(g.rn_id, Z * cap * 8, base); Lo.bind(g.rs_id, Z * cap * 8, base); Lo.bind(g.rank_at, Z * cap * 4, base); Lo.bind(g.kept, Z * (cap + 1) * 4, base);
+    Lo.bind(g.t_id, n * 8, base); Lo.bind(g.t_upx, n * 16, base); Lo.bind(g.t_live, n, base);
+    Lo.bind(g.applied, l, base); Lo.bind(g.stat, S * 16, base);
+    Lo.bind(g.q_yx, l * 16, base); Lo.bind(g.q_syx, l * 16, base); Lo.bind(g.q_xyz, l * 24, base); Lo.bind(g.q_kyx, l * 16, base); Lo.bind(g.q_fyx, l * 16, base); Lo.bind(g.q_id, l * 8, base);
+    Lo.bind(g.q_is3d, l, base); Lo.bind(g.q_stereo, l, base); Lo.bind(g.q_haskf, l, base); Lo.bind(g.q_fkf, l * 4, base);
     return Lo.size();
 }
 
@@ -241,15 +228,15 @@ int slam_kfmap_merge(slam_ctx *ctx, slam_kfmap *km, slam_kpset *ks, const int32_
         }
         if (total > 0 && pairs == nullptr) return slam_fail(ctx, SLAM_ERR_ARG, "slam_kfmap_merge: %lld pairs announced, none given", total);
         std::vector<int64_t> a, b, both;
-        for (int s = 0; s < S; s++) {                            // one-to-one: no prev id twice, no new id twice, no id on both sides of two pairs
+        for (int s = 0; s < S; s++) {                            // one-to-one (kfm_sorted_one_to_one: the rule k_kfm_merge_resolve checks pair by pair)
             a.clear(); b.clear(); both.clear();
             for (int t = 0; t < np[s]; t++) {
                 const int64_t p = pairs[2 * ((size_t)off[s] + t)], q = pairs[2 * ((size_t)off[s] + t) + 1];
                 a.push_back(p); b.push_back(q);
-                if (p != q) { both.push_back(p); both.push_back(q); }             // (a pair of one id is skipped by the validity rule, not refused)
+                if (p != q) { both.push_back(p); both.push_back(q); }
             }
             std::sort(a.begin(), a.end()); std::sort(b.begin(), b.end()); std::sort(both.begin(), both.end());
-            if (std::adjacent_find(a.begin(), a.end()) != a.end() || std::adjacent_find(b.begin(), b.end()) != b.end() || std::adjacent_find(both.begin(), both.end()) != both.end())
+            if (!kfm_sorted_one_to_one(a.data(), b.data(), np[s], both.data(), (int)both.size()))
                 return slam_fail(ctx, SLAM_ERR_ARG, "slam_kfmap_merge: the pairs of stream %d are not one-to-one (a repeated prev id, a repeated new id, or an id on both sides)", s);
         }
     } else {
@@ -274,14 +261,11 @@ int slam_kfmap_merge(slam_ctx *ctx, slam_kfmap *km, slam_kpset *ks, const int32_
     Layout D;
     const auto o_sel = D.take<int>(S), o_n = D.take<int>(S), o_off = D.take<int>(S); const auto o_pairs = D.take<int64_t>(n_pairs ? 2 * (size_t)total : 0);
     char *scr, *h;
-    int rc = kfmap_pin(ctx, km, D.size(), &h);
+    int rc = kfmap_upload(ctx, km, D.size(), &scr, [&](char *h) {
+        kfmap_put_streams(o_sel, h, list, ns); memcpy(o_n.at(h), np, (size_t)S * 4); memcpy(o_off.at(h), off, (size_t)S * 4);
+        if (n_pairs && total > 0) memcpy(o_pairs.at(h), pairs, o_pairs.bytes());
+    });
     if (rc) return rc;
-    rc = slam_scratch(ctx, D.size(), (void **)&scr);
-    if (rc) return rc;
-    memcpy(o_sel.at(h), list, (size_t)ns * 4); memcpy(o_n.at(h), np, (size_t)S * 4); memcpy(o_off.at(h), off, (size_t)S * 4);
-    if (n_pairs && total > 0) memcpy(o_pairs.at(h), pairs, o_pairs.bytes());
-    HIP_TRY(ctx, hipMemcpyAsync(scr, h, D.size(), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipEventRecord(km->pin_ev, ctx->stream));
     KfmPairs P = {km->lm.status, km->lm.rn, km->lm.rpairs, V.cap, nullptr, nullptr, nullptr};
     if (n_pairs) P = {nullptr, nullptr, nullptr, V.cap, (const int32_t *)o_n.at(scr), (const int32_t *)o_off.at(scr), (const int64_t *)o_pairs.at(scr)};
     const int *sel = o_sel.at(scr);

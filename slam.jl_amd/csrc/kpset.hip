@@ -369,17 +369,16 @@ __global__ __launch_bounds__(256) void k_kpset_frame_stats(KfStatsArgs A)
 static size_t kpset_regions(slam_kpset *ks, char *base)
 {
     Layout Lo;
-    auto region = [&](auto *&p, size_t bytes) { const size_t at = Lo.take(bytes); if (base) p = (std::remove_reference_t<decltype(p)>)(base + at); };
     KpsetView &v = ks->v;
     const size_t S = (size_t)ks->S, n = S * v.cap;
-    region(v.yx, n * 16); region(v.oyx, n * 16); region(v.syx, n * 16); region(v.xyz, n * 24); region(v.id, n * 8);
-    region(v.is3d, n); region(v.stereo, n); region(v.st, n); region(v.count, S * 4); region(ks->work, n * 4); region(ks->ntot, 64);
-    region(ks->next_id, S * 8); region(ks->par, 8 * S * KP_PAR * 8); region(v.kyx, n * 16); region(v.haskf, n); region(v.fyx, n * 16);
-    region(v.fkf, n * 4); region(v.kfcount, S * 4);
-    region(ks->sel_idx, S * 4 + S);                               // the selection as one block (one staged copy): S indices, then the S mask bytes
+    Lo.bind(v.yx, n * 16, base); Lo.bind(v.oyx, n * 16, base); Lo.bind(v.syx, n * 16, base); Lo.bind(v.xyz, n * 24, base); Lo.bind(v.id, n * 8, base);
+    Lo.bind(v.is3d, n, base); Lo.bind(v.stereo, n, base); Lo.bind(v.st, n, base); Lo.bind(v.count, S * 4, base); Lo.bind(ks->work, n * 4, base); Lo.bind(ks->ntot, 64, base);
+    Lo.bind(ks->next_id, S * 8, base); Lo.bind(ks->par, 8 * S * KP_PAR * 8, base); Lo.bind(v.kyx, n * 16, base); Lo.bind(v.haskf, n, base); Lo.bind(v.fyx, n * 16, base);
+    Lo.bind(v.fkf, n * 4, base); Lo.bind(v.kfcount, S * 4, base);
+    Lo.bind(ks->sel_idx, S * 4 + S, base);                               // the selection as one block (one staged copy): S indices, then the S mask bytes
     if (base) ks->sel_mask = (uint8_t *)(ks->sel_idx + S);
     ks->rec_stride = work_rec_stride((long long)n);
-    region(ks->rec, (size_t)WORK_XCDS * ks->rec_stride * sizeof(KpWorkRec));      // the work records of a match (regions start 256-byte aligned)
+    Lo.bind(ks->rec, (size_t)WORK_XCDS * ks->rec_stride * sizeof(KpWorkRec), base);      // the work records of a match (regions start 256-byte aligned)
     return Lo.size();
 }
 

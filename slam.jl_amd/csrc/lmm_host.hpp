@@ -70,6 +70,21 @@ static inline bool lmm_monotone(const int32_t *o, int n, std::string &err, const
 // the cell of a pixel coordinate: round(p) ÷ cell_size + 1, round to nearest even, ÷ truncating (SLAM.jl:30,42-45)
 LMM_HD static inline long long lmm_cell(double p, int cell) { return (long long)rint(p) / cell + 1; }
 
+// The frame constants of a local-map call that follow from a stream's camera row (fx fy cx cy k1 k2 p1 p2 H W), its cell size and its
+// max_descriptor_distance -- one copy for lmm_plan / lmm_emit and the key-frame map's stager (kfmap_lmm.inc).  false: cell_size, H or W out of range
+// (each seam reports it in its own words).
+struct LmmFrame { double start, view_thr; int32_t gr, gc; };
+static inline bool lmm_frame(const double *cam, int cell, double max_descriptor_distance, LmmFrame &F)
+{
+    const double H = cam[8], W = cam[9];
+    if (cell < 1 || !(H >= 1.0) || !(W >= 1.0) || H > 65536.0 || W > 65536.0) return false;
+    F.start = 256.0 * max_descriptor_distance;                                         // mapper.jl:401
+    const double vfov = 0.5 * H / cam[1], hfov = 0.5 * W / cam[0];                     // mapper.jl:326-329
+    F.view_thr = std::cos(vfov > hfov ? std::atan(vfov) : std::atan(hfov));
+    F.gr = (int)std::ceil(H / cell); F.gc = (int)std::ceil(W / cell);
+    return true;
+}
+
 // Checks every argument the device would trust and lays the buffer out.  false: `err` says what is wrong, nothing may be launched.
 static inline bool lmm_plan(int S, const int32_t *kp_offsets, const int32_t *kf_offsets, const int32_t *mp_offsets, const slam_local_map_args *a,
                             LmmPlan &P, std::string &err)
@@ -100,8 +115,9 @@ static inline bool lmm_plan(int S, const int32_t *kp_offsets, const int32_t *kf_
         const double H = a->cam[10 * s + 8], W = a->cam[10 * s + 9];
         const int cell = a->cell_size[s];
         char b[200];
-        if (cell < 1 || !(H >= 1.0) || !(W >= 1.0) || H > 65536.0 || W > 65536.0) { snprintf(b, sizeof b, "stream %d: cell_size %d / image %g x %g out of range", s, cell, H, W); err = b; return false; }
-        const int gr = (int)std::ceil(H / cell), gc = (int)std::ceil(W / cell);
+        LmmFrame F;
+        if (!lmm_frame(a->cam + 10 * s, cell, a->max_descriptor_distance[s], F)) { snprintf(b, sizeof b, "stream %d: cell_size %d / image %g x %g out of range", s, cell, H, W); err = b; return false; }
+        const int gr = F.gr, gc = F.gc;
         // observer rows are checked for every stream, launched or not: a caller's bad table is reported where it is
         for (int o = P.Ntot ? a->kp_obs_off[kp_offsets[s]] : 0, e = P.Ntot ? a->kp_obs_off[kp_offsets[s + 1]] : 0; o < e; o++)
             if (a->kp_obs_kf[o] < 0 || a->kp_obs_kf[o] >= K) { snprintf(b, sizeof b, "stream %d: kp_obs_kf[%d] = %d is no row of its %d key-frames", s, o, a->kp_obs_kf[o], K); err = b; return false; }
@@ -149,10 +165,10 @@ static inline void lmm_emit(const LmmPlan &P, const int32_t *kp_offsets, const i
         memcpy(&T.fx, a->cam + 10 * (size_t)s, 10 * sizeof(double));
         T.max_proj = a->max_projection_distance[s];
         if (a->nb_3d_kpts[s] < 30) T.max_proj *= 2.0;                                   // mapper.jl:332
-        T.start = 256.0 * a->max_descriptor_distance[s];                               // mapper.jl:401
-        const double vfov = 0.5 * T.H / T.fy, hfov = 0.5 * T.W / T.fx;                 // mapper.jl:326-329
-        T.view_thr = std::cos(vfov > hfov ? std::atan(vfov) : std::atan(hfov));
-        T.cell = a->cell_size[s]; T.gr = (int)std::ceil(T.H / T.cell); T.gc = (int)std::ceil(T.W / T.cell);
+        LmmFrame F;
+        (void)lmm_frame(&T.fx, a->cell_size[s], a->max_descriptor_distance[s], F);      // (in range: lmm_plan has checked)
+        T.start = F.start; T.view_thr = F.view_thr;
+        T.cell = a->cell_size[s]; T.gr = F.gr; T.gc = F.gc;
         T.kp0 = kp_offsets[s]; T.kf0 = kf_offsets[s]; T.mp0 = mp_offsets[s]; T.cell0 = P.cell0[z];
         T.N = kp_offsets[s + 1] - T.kp0; T.K = kf_offsets[s + 1] - T.kf0; T.M = mp_offsets[s + 1] - T.mp0;
         // stable counting sort of the keypoints over their cell (row-major r, c): inside a cell the list order is kept

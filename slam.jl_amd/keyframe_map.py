@@ -15,6 +15,11 @@ from .keypoint_set import KP_PAR
 N_COVISIBLE = 5                         # local_bundle_adjustment!: up to 5 latest covisible key-frames
 
 
+def _per_stream(x, dtype, S, width=None):
+    """a per-stream argument as the C seam takes it: a contiguous (S,) or (S, width) array; a scalar (or one row) stands for every stream"""
+    return np.ascontiguousarray(np.broadcast_to(np.asarray(x, dtype=dtype), (S,) if width is None else (S, width)))
+
+
 class _Windows(C.Structure):
     """slam_kfmap_windows"""
     _fields_ = [("cap_windows", C.c_int32), ("cap_poses", C.c_int32), ("cap_points", C.c_int32), ("cap_obs", C.c_int32),
@@ -70,7 +75,7 @@ class KeyframeMap:
         capacities of the arrays the windows are gathered into (default: what S windows can at most need).  Synchronous."""
         c = ctx or self.ctx
         S = self.S
-        minc = np.ascontiguousarray(np.broadcast_to(np.asarray(min_cov_score, dtype=np.int32), (S,)))
+        minc = _per_stream(min_cov_score, np.int32, S)
         nW = S if max_windows is None else int(max_windows)
         nP = S * self.R if max_poses is None else int(max_poses)
         nM = S * min(self.mcap, N_COVISIBLE * self.cap) if max_points is None else int(max_points)
@@ -118,8 +123,8 @@ class KeyframeMap:
         -> per stream the ascending list of removed key-frame ids (synchronous), or None with want_removed=False (enqueue-only)."""
         c = ctx or self.ctx
         S = self.S
-        ratio = np.ascontiguousarray(np.broadcast_to(np.asarray(filtering_ratio, dtype=np.float64), (S,)))
-        minc = np.ascontiguousarray(np.broadcast_to(np.asarray(min_cov_score, dtype=np.int32), (S,)))
+        ratio = _per_stream(filtering_ratio, np.float64, S)
+        minc = _per_stream(min_cov_score, np.int32, S)
         if not want_removed:
             c.check(c.lib.slam_kfmap_filter(c.h, self.h, L.ptr(ratio), L.ptr(minc, L.i32p), int(first_kfid), None))
             return None
@@ -187,10 +192,10 @@ class KeyframeMap:
         the (n,) winning descriptor distances).  status 0 matched, 1 nothing to match, 2 local map larger than max_local.  Synchronous."""
         c = ctx or self.ctx
         S = self.S
-        cam = np.ascontiguousarray(np.broadcast_to(np.asarray(cam, dtype=np.float64), (S, 10)))
-        cell = np.ascontiguousarray(np.broadcast_to(np.asarray(cell_size, dtype=np.int32), (S,)))
-        mpd = np.ascontiguousarray(np.broadcast_to(np.asarray(max_projection_distance, dtype=np.float64), (S,)))
-        mdd = np.ascontiguousarray(np.broadcast_to(np.asarray(max_descriptor_distance, dtype=np.float64), (S,)))
+        cam = _per_stream(cam, np.float64, S, 10)
+        cell = _per_stream(cell_size, np.int32, S)
+        mpd = _per_stream(max_projection_distance, np.float64, S)
+        mdd = _per_stream(max_descriptor_distance, np.float64, S)
         max_local = 10 * self.cap if max_local is None else int(max_local)
         cap_pairs = S * self.cap if cap_pairs is None else int(cap_pairs)
         status = np.zeros(S, dtype=np.int32); n = np.zeros(S, dtype=np.int32)

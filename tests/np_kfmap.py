@@ -145,6 +145,27 @@ def remove_mappoint(m, e):
     m.flags[e] = F_DEAD | (F_GONE if m.flags[e] & (F_OBS | F_GONE) else 0)
 
 
+def covmap(tag, cov):
+    """sorted(cov, reverse=True)[:5]: the at most N_COVISIBLE newest slots of `cov` (slot -> score; tag[b] = the slot's key-frame id), newest first"""
+    return sorted(cov, key=lambda b: -tag[b])[:N_COVISIBLE]
+
+
+def ascending(tag):
+    """the slots that hold a key-frame, ascending by key-frame id"""
+    return sorted((b for b in range(len(tag)) if tag[b] >= 0), key=lambda b: tag[b])
+
+
+def meet(order, b):
+    """slot b's 1-based pose id: dense, in first-encounter order"""
+    if b not in order:
+        order[b] = len(order) + 1
+    return order[b]
+
+
+def window_const(tag_b, in_covmap, score, minc):
+    return bool(tag_b == 0 or not in_covmap or score < minc)
+
+
 def gather(m):
     """The window of the newest key-frame -> dict as tracked_ba.gather's (plus what update() needs of the ring), or None"""
     kfid, R, minc = m.cur, m.R, m.min_cov_score
@@ -165,8 +186,8 @@ def gather(m):
     if nb3 < minc:
         return None
     cov[r0] = nb3
-    co = sorted(cov, key=lambda b: -m.tag[b])[:N_COVISIBLE]
-    asc = sorted((b for b in range(R) if m.tag[b] >= 0), key=lambda b: m.tag[b])
+    co = covmap(m.tag, cov)
+    asc = ascending(m.tag)
     order = {}                                                   # slot -> 1-based pose id
     went, bad = {}, []
     pts, obs = [], []                                            # (kpid, entry), (pixel, slot, point id, kpid)
@@ -193,8 +214,7 @@ def gather(m):
                 if j is None:
                     m.mask[e] &= ~(1 << b)                       # remove_obs of an observation whose pixel is gone
                     continue
-                if b not in order:
-                    order[b] = len(order) + 1
+                meet(order, b)
                 obs.append((m.upx[b, j].copy(), b, len(pts), kpid))
     if not obs:
         return None
@@ -204,7 +224,7 @@ def gather(m):
     poses_remap = np.zeros(P, dtype=np.int64)
     for b, o in order.items():
         theta[6 * (o - 1):6 * o] = m.theta[b]
-        tconst[o - 1] = m.tag[b] == 0 or b not in co or cov[b] < minc
+        tconst[o - 1] = window_const(m.tag[b], b in co, cov.get(b, 0), minc)
         poses_remap[o - 1] = m.tag[b]
     for j, (kpid, e) in enumerate(pts):
         theta[6 * P + 3 * j:6 * P + 3 * j + 3] = m.xyz[e]

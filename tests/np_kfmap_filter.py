@@ -49,8 +49,24 @@ def remove_keyframe(m, kfid):
     m.tag[b] = -1; m.n[b] = 0
 
 
-def candidates(m):
-    """the covisible key-frames of the newest one, ascending by id"""
+def ascending_ids(tag, slots):
+    """the key-frame ids of `slots`, ascending"""
+    return sorted(int(tag[b]) for b in slots)
+
+
+def walked(cands, cur):
+    """the candidates the walk evaluates -> (their ids, whether key-frame 0 ended the walk): an id >= the newest is passed over"""
+    out = []
+    for kfid in cands:
+        if kfid == 0:
+            return out, True
+        if kfid < cur:
+            out.append(kfid)
+    return out, False
+
+
+def covisible(m):
+    """the slots of the key-frames covisible with the newest one"""
     r0 = m.cur % m.R
     cov = set()
     for i in range(int(m.n[r0])):
@@ -60,7 +76,12 @@ def candidates(m):
         if e is None:
             continue
         cov |= {b for b in range(m.R) if b != r0 and m.mask[e] >> b & 1 and m.tag[b] >= 0}
-    return sorted(int(m.tag[b]) for b in cov)
+    return cov
+
+
+def candidates(m):
+    """the covisible key-frames of the newest one, ascending by id"""
+    return ascending_ids(m.tag, covisible(m))
 
 
 def _decide(n_total, n_good, filtering_ratio, min_cov_score):
@@ -76,12 +97,10 @@ def filter_map(m, filtering_ratio, min_cov_score, first_kfid=FIRST_KFID):
     log = []
     if filtering_ratio >= 1 or m.cur < first_kfid:
         return log
-    for kfid in candidates(m):
-        if kfid == 0:
-            log.append((0, "break", 0, 0))
-            break
-        if kfid >= m.cur:
-            continue
+    kfids, broke = walked(candidates(m), m.cur)
+    if broke:                                                    # (key-frame 0 is the smallest id: nothing was walked before it)
+        log.append((0, "break", 0, 0))
+    for kfid in kfids:
         b = m.slot(kfid)
         n_total = n_good = 0
         for i in range(int(m.n[b])):

@@ -121,6 +121,22 @@ def staged_match(m, D, lm, cam, cell_size, params):
                 best_kp=out["best_kp"], best_dist=out["best_dist"], margin=out["margin"], count=out["count"])
 
 
+def oldest(cov, tag):
+    """the covisible slot of the smallest key-frame id (the "newest" mutant takes the largest)"""
+    return min(cov, key=lambda b: tag[b])
+
+
+def rule(C, P, has_cov, linked, max_local=None, mutant=None):
+    """steps 2 and 3's decisions on the sets -> (replace, L before the chain, whether the chain runs)"""
+    replace = float(len(C)) > 0.5 * float(len(P))
+    if mutant == "rule":
+        replace = not replace
+    L = set(C) if replace else P | C
+    bound = math.inf if max_local is None else max_local
+    chain = bool(has_cov) and (len(L) <= bound if mutant == "le" else len(L) < bound) and mutant != "nochain" and bool(linked)
+    return replace, L, chain
+
+
 def local_map_match(m, D, H, cam, cell_size, params, max_local=None, mutant=None):
     """-> np_kfmap_local_map.local_map_match's dict plus C (step 1's ids), size (len(L) at step 3's test), chain (the ids step 3 added), branch
     ("replace" / "union" when P was non-empty, else None)"""
@@ -131,22 +147,17 @@ def local_map_match(m, D, H, cam, cell_size, params, max_local=None, mutant=None
     cov = nl.covisible_slots(m)
     C = set(nl.local_map_ids(m, D, cov)) if cov else set()
     P = set(H.sets[r0]) if H.kf[r0] == K else set()
-    replace = float(len(C)) > 0.5 * float(len(P))
-    if mutant == "rule":
-        replace = not replace
+    b = (max(cov, key=lambda b: m.tag[b]) if mutant == "newest" else oldest(cov, m.tag)) if cov else None
+    replace, L, runs = rule(C, P, cov, b is not None and H.kf[b] == m.tag[b], max_local, mutant)
     branch = None
     if P:
         branch = "replace" if replace else "union"
         H.count[branch] += 1
-    L = set(C) if replace else P | C
     size, chain = len(L), set()
-    bound = math.inf if max_local is None else max_local
-    if cov and (size <= bound if mutant == "le" else size < bound) and mutant != "nochain":
-        b = (max if mutant == "newest" else min)(cov, key=lambda b: m.tag[b])
-        if H.kf[b] == m.tag[b]:
-            chain = H.sets[b] - L
-            L |= H.sets[b]
-            H.count["chained"] += bool(chain)
+    if runs:
+        chain = H.sets[b] - L
+        L |= H.sets[b]
+        H.count["chained"] += bool(chain)
     H.kf[r0], H.sets[r0] = K, set(L)
     lm = gated(m, D, L)
     extra = dict(C=sorted(C), size=size, chain=sorted(chain), branch=branch)
