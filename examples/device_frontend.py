@@ -12,6 +12,7 @@ lock-stepped stereo streams with every keypoint list resident in HBM -- the call
     --map-filtering: after update(ks) KeyframeMap.filter drops the redundant key-frames of the ring                          (map_filtering!)
     --local-map-match: key-frames detect WITH describe; after add_keyframe KeyframeMap.add_descriptors -> local_map_match     (update_frame_covisibility! + match_local_map!)
     --merge: after local_map_match KeyframeMap.merge(ks) applies the match's pairs to the map and the lists, before the gather  (merge_matches)
+    --descriptor-rows D: KeyframeMap.enable_descriptor_rows(D); a point keeps one row per key-frame, the match takes the minimum over all pairs of rows  (keyframes_descriptors)
     --local-map-history: KeyframeMap.enable_local_map_history; the match keeps every key-frame's local map and takes in the oldest covisible one's  (frame.local_map_ids)
 
 No host keypoint arrays anywhere; per frame the host receives S poses, S status words and S list lengths.  It is an
@@ -44,7 +45,7 @@ shared -- so --adaptive-keyframes alone takes a key-frame FOR ALL streams when A
 stream follow its own rule: the key-frame seams run under KeypointSet.selected(required), which restricts them to the streams that asked
 (slam_kpset_select), and the key-frame bookkeeping (last key-frame, its nb_3d_kpts, its pose, the observer ring, the key-frame id) is per stream.
 
-    python examples/device_frontend.py --frames 12 --streams 4 [--adaptive-keyframes | --per-stream-keyframes] [--local-ba [--map-filtering [--filter-from K]] [--local-map-match [--merge] [--local-map-history]]]
+    python examples/device_frontend.py --frames 12 --streams 4 [--adaptive-keyframes | --per-stream-keyframes] [--local-ba [--map-filtering [--filter-from K]] [--local-map-match [--merge] [--local-map-history] [--descriptor-rows D]]]
 """
 import argparse
 import contextlib
@@ -60,7 +61,7 @@ from slam_jl_amd import synthetic as syn  # noqa: E402
 
 
 def run(lefts, rights, cam, baseline, kf_every=4, max_keypoints=300, seed=0, ctx=None, verbose=False, adaptive=False, probe=None, per_stream=False, local_ba=False,
-        map_filtering=False, filter_from=20, map_probe=None, local_map_match=False, merge=False, local_map_history=False):
+        map_filtering=False, filter_from=20, map_probe=None, local_map_match=False, merge=False, local_map_history=False, descriptor_rows=0):
     """lefts / rights: per stream a list of float images in [0, 1] (H, W).  Returns per frame a dict with the S poses
     (world -> camera, world = the first frame's camera), status words, list lengths and the wall time.
     adaptive: frame 0 is a key-frame; after the pose of every later frame the lists' statistics (KeypointSet.frame_stats, flags = 1) go
@@ -82,6 +83,7 @@ def run(lefts, rights, cam, baseline, kf_every=4, max_keypoints=300, seed=0, ctx
     is also called with ("described", desc, info, dcap) -- the device tensors detect_describe filled -- and ("matched", km, status, pairs, dist).
     merge (needs local_map_match): behind the match KeyframeMap.merge(ks) applies its pairs, taken where the match left them on the device; those rows
     carry `merged`: the (S, 4) counts (pairs applied, pairs skipped, observations renamed, status); map_probe is called with ("merged", km, counts).
+    descriptor_rows (needs local_map_match): D > 0: KeyframeMap.enable_descriptor_rows(D) -- a point keeps one descriptor row per key-frame (at most D).
     local_map_history (needs local_map_match): KeyframeMap.enable_local_map_history() -- the map keeps every key-frame's local map, the match applies the
     replace-or-union rule and takes in the oldest covisible key-frame's stored set (mapper.jl:274-286); max_local is then the table's size (sets grow along
     that chain; status 2 cannot occur).  KeyframeMap.local_map_ids(s, kfid) reads a stored set back."""
@@ -93,6 +95,8 @@ def run(lefts, rights, cam, baseline, kf_every=4, max_keypoints=300, seed=0, ctx
         raise ValueError("merge needs local_map_match: it applies the match's pairs")
     if local_map_history and not local_map_match:
         raise ValueError("local_map_history needs local_map_match: it is the match that keeps and reads the stored local maps")
+    if descriptor_rows and not local_map_match:
+        raise ValueError("descriptor_rows needs local_map_match: the rows are what the match is decided on")
     adaptive = adaptive or per_stream
     import torch
     ctx = ctx or slam.default_context(0)
@@ -107,6 +111,8 @@ def run(lefts, rights, cam, baseline, kf_every=4, max_keypoints=300, seed=0, ctx
     km = slam.KeyframeMap(S, ks.cap, R=16, mcap=8192, ctx=ctx) if local_ba else None
     if local_map_match:
         km.enable_descriptors(ctx=ctx)
+        if descriptor_rows:
+            km.enable_descriptor_rows(descriptor_rows, ctx=ctx)
         if local_map_history:
             km.enable_local_map_history(ctx=ctx)
         dcap = ncell * -(-ex.max_points // ncell)
@@ -251,6 +257,7 @@ def main():
     ap.add_argument("--map-filtering", action="store_true", help="after every local BA drop the redundant key-frames of the map (map_filtering!); requires --local-ba")
     ap.add_argument("--local-map-match", action="store_true", help="describe the key-frames' new keypoints and match each stream's local map against them on the key-frame map (match_local_map!); requires --local-ba")
     ap.add_argument("--merge", action="store_true", help="apply the local-map match's pairs to the map and the lists (merge_matches); requires --local-map-match")
+    ap.add_argument("--descriptor-rows", type=int, default=0, metavar="D", help="keep one descriptor row per key-frame and point, at most D = 2 .. 8 (keyframes_descriptors): merges hand rows over, removed observations drop theirs, the match reads all of them; requires --local-map-match")
     ap.add_argument("--local-map-history", action="store_true", help="keep every key-frame's local map on the device and let the match take in the oldest covisible key-frame's (frame.local_map_ids, match_local_map!); requires --local-map-match")
     ap.add_argument("--filter-from", type=int, default=20, help="first key-frame id at which the filter acts (the reference's literal 20)")
     ap.add_argument("--replay-dir", default=None, help="write stream s's camera positions to DIR/stream_s as a ReplaySaver dump (src/io/saver.jl)")
@@ -263,11 +270,13 @@ def main():
         ap.error("--merge requires --local-map-match")
     if args.local_map_history and not args.local_map_match:
         ap.error("--local-map-history requires --local-map-match")
+    if args.descriptor_rows and not args.local_map_match:
+        ap.error("--descriptor-rows requires --local-map-match")
     cam, baseline, disparity = syn.KITTI_CAM, 0.54, 8.0
     lefts, rights, offs = synthetic_scene(args.streams, args.frames, disparity=disparity)
     out, n3 = run(lefts, rights, cam, baseline, verbose=True, adaptive=args.adaptive_keyframes, per_stream=args.per_stream_keyframes, local_ba=args.local_ba,
                   map_filtering=args.map_filtering, filter_from=args.filter_from, local_map_match=args.local_map_match, merge=args.merge,
-                  local_map_history=args.local_map_history)
+                  local_map_history=args.local_map_history, descriptor_rows=args.descriptor_rows)
     Z = cam[0] * baseline / disparity
     for s in range(args.streams):
         o = offs[s][-1] - offs[s][0]

@@ -591,6 +591,33 @@ int slam_kfmap_download_local_map_ids(slam_ctx *ctx, slam_kfmap *km, int s, int 
  * (25 bytes a record), a scratch record array per list (103 bytes a record): about (53 R + 132) cap bytes per stream. */
 int slam_kfmap_merge(slam_ctx *ctx, slam_kfmap *km, slam_kpset *ks /* nullable */, const int32_t *n_pairs /* S, or NULL */,
                      const int64_t *pairs /* x 2, streams back to back, or NULL */, int32_t *merged /* nullable, S x 4 */);
+/* Descriptor rows: a point keeps one row per key-frame, the reference's keyframes_descriptors (map_point.jl:15).  Opt-in, after
+ * slam_kfmap_enable_descriptors, ONE allocation of about 36 max_rows mcap bytes per stream: per table entry D = max_rows (2 .. 8) keys (key-frame id
+ * + 1, 0 = empty slot) and D rows of 4 words, and a dropped-rows counter per stream.  A second call with the same D is a no-op, another D an argument
+ * error.  A map that never makes this call behaves, allocates and launches exactly as before.  From then on:
+ *   add_descriptors   the row also goes into the point's rows under the key of the stream's newest key-frame (add_mappoint!'s current_keyframe_id);
+ *   observations      wherever a live point loses an observer -- a ring slot reused, slam_kfmap_filter, slam_kfmap_remove_keyframe, an outlier
+ *                     observation of slam_kfmap_ba_update, an observer whose pixel is gone at slam_kfmap_ba_gather -- the row keyed by that
+ *                     key-frame goes (remove_kf_observation!, map_point.jl:88-122); with the last valid observer every row goes and the point is no
+ *                     longer described ("mp.descriptor is empty": the local map and the keypoint list pass it over);
+ *   owners            an entry that takes a new owner loses its rows; slam_kfmap_reset clears the stream's rows and its counter;
+ *   merge             the new point takes prev's rows by key; on an equal key its own row stays (add_descriptor!, map_point.jl:124-131,
+ *                     map_manager.jl:410-412); prev's rows go with prev;
+ *   match             every row of a local-map point and of a keypoint is staged, ascending by key: the distance of a pair is the minimum over ALL
+ *                     pairs of rows (mappoint_min_distance, map_point.jl:165-174).  A described point without a row is staged with an empty row
+ *                     range and is never chosen.  The staging allocation's descriptor regions hold D rows per record.
+ * Deviations: a point keeps at most D rows -- where a row arrives at a full point the D rows with the LARGEST keys stay, whatever the order of
+ * arrival, and the stream's counter counts the rows that went; the reference's most representative `descriptor` is read by nothing but its
+ * emptiness test and is not modelled (the single row of slam_kfmap_enable_descriptors stays what add_descriptors wrote and is not staged); a
+ * reused ring slot counts as remove_keyframe!. */
+int slam_kfmap_enable_descriptor_rows(slam_ctx *ctx, slam_kfmap *km, int max_rows);
+/* The rows of stream s's points: the owned points that have not been removed, ascending by id (the set slam_kfmap_download_points lists;
+ * n_points of them).  Point k: ids[k], described[k] (the "has descriptor" byte), its rows rows[4 j .. 4 j + 4) with keys[j] = the key-frame id,
+ * j in row_off[k] .. row_off[k + 1), ascending by key (row_off: cap_points + 1 entries).  dropped: the rows the bound D has dropped on this
+ * stream since its creation or reset.  Every array is nullable.  More than cap_points points, or (keys or rows given) more than cap_rows rows: a
+ * capacity error (n_points is set); a map without rows: an argument error.  Synchronous. */
+int slam_kfmap_download_descriptor_rows(slam_ctx *ctx, slam_kfmap *km, int s, int64_t *ids, uint8_t *described, int32_t *row_off, int32_t *keys,
+                                        uint64_t *rows, int cap_points, int cap_rows, int32_t *n_points, int32_t *dropped);
 
 /* ---- one live stream, one call per frame (round 6) -----------------------------------------------------------------------------------
  * What run!() does per frame (src/front_end.jl:58-113: preprocess! :454-470 = copy!(previous_pyramid, current_pyramid) + update!,

@@ -15,8 +15,12 @@ Medians with the spread (min - max) over the repeats.
 timed back to back (without history first): (b) for each, plus the local-map sizes each reaches and how many streams had status 2.  The host route (c)
 is not run (it models the match without history).  --max-local sets the bound of both calls (16 384 = the table's size rules status 2 out).
 
+--rows D: a SECOND map with slam_kfmap_enable_descriptor_rows(D) takes the same key-frames and descriptors; per repeat add_keyframe, add_descriptors and
+the match of both maps are timed (rows off first).  With random descriptors no pair occurs: the figures are upkeep and staging, not merges.
+
     python scripts/probes/prof_kfmap_local_map.py [--streams 128] [--repeats 25] [--host-repeats 25] [--out profiles/kfmap_local_map_s128.json]
     python scripts/probes/prof_kfmap_local_map.py --history [--max-local 16384] [--out profiles/kfmap_local_map_history_s128.json]
+    python scripts/probes/prof_kfmap_local_map.py --rows 4 [--out profiles/kfmap_rows_s128.json]
 """
 import argparse
 import json
@@ -76,9 +80,12 @@ def main():
     ap.add_argument("--host-repeats", type=int, default=25)
     ap.add_argument("--out", default=None)
     ap.add_argument("--history", action="store_true", help="time a second map with the local-map history beside the first, on the same steps (no host route)")
+    ap.add_argument("--rows", type=int, default=0, metavar="D", help="time a second map with D descriptor rows per point beside the first, on the same steps (no host route)")
     ap.add_argument("--max-local", type=int, default=MAX_LOCAL)
     args = ap.parse_args()
-    if args.history:
+    if args.history and args.rows:
+        ap.error("--history and --rows each time ONE second map")
+    if args.history or args.rows:
         args.host_repeats = 0
     import torch
     import slam_jl_amd as slam
@@ -97,9 +104,12 @@ def main():
     if args.history:
         kmh = slam.KeyframeMap(S, CAP, R=RING, mcap=MCAP)
         kmh.enable_descriptors(); kmh.enable_local_map_history()
+    if args.rows:
+        kmh = slam.KeyframeMap(S, CAP, R=RING, mcap=MCAP)
+        kmh.enable_descriptors(); kmh.enable_descriptor_rows(args.rows)
     rows = [dict() for _ in range(S)]
     m = {k: [] for k in ("desc", "call", "stage", "kernel", "wall", "h_down", "h_asm", "h_call", "h_total", "M", "N", "pairs",
-                         "hist_call", "hist_stage", "hist_kernel", "hist_wall", "hist_M", "hist_pairs", "hist_status2", "status2")}
+                         "hist_call", "hist_stage", "hist_kernel", "hist_wall", "hist_M", "hist_pairs", "hist_status2", "status2", "add", "hist_add", "hist_desc")}
     agree = []
     ctx.prof_enable(True)
     for k in range(WARM + R):
@@ -117,10 +127,19 @@ def main():
         desc_dev = torch.from_numpy(desc.view(np.int64)).cuda(); info_dev = torch.from_numpy(info).cuda()
         torch.cuda.synchronize()
         ks.keyframe()
+        ctx.synchronize()
+        ctx.prof_reset()
         km.add_keyframe(ks, slam.stream_params(S, Tcw=Tcw, cam=cam))
+        ctx.synchronize()
+        if k >= WARM:
+            m["add"].append(ctx.prof_get("kfmap_add")[0])
         if kmh is not None:
+            ctx.prof_reset()
             kmh.add_keyframe(ks, slam.stream_params(S, Tcw=Tcw, cam=cam))
             kmh.add_descriptors(desc_dev.data_ptr(), info_dev.data_ptr(), DCAP)
+            ctx.synchronize()
+            if k >= WARM:
+                m["hist_add"].append(ctx.prof_get("kfmap_add")[0]); m["hist_desc"].append(ctx.prof_get("kfmap_add_descriptors")[0])
         ctx.synchronize()
         ctx.prof_reset()
         km.add_descriptors(desc_dev.data_ptr(), info_dev.data_ptr(), DCAP)
@@ -128,7 +147,7 @@ def main():
         t0 = time.perf_counter()
         status, pairs, dist = km.local_map_match(cam10, CELL, params.max_projection_distance, params.max_descriptor_distance, max_local=args.max_local)
         wall = (time.perf_counter() - t0) * 1e3
-        assert args.history or not (status == 2).any(), "a local map did not fit the probe's max_local"
+        assert args.history or args.rows or not (status == 2).any(), "a local map did not fit the probe's max_local"
         if k >= WARM:
             m["status2"].append(int((status == 2).sum()))
             m["desc"].append(ctx.prof_get("kfmap_add_descriptors")[0]); m["call"].append(ctx.prof_get("kfmap_local_map_match")[0])
@@ -173,14 +192,19 @@ def main():
         del desc_dev, info_dev
     ctx.prof_enable(False)
     if kmh is not None:
-        newest = int(kmh.newest()[0])
-        stored = [len(kmh.local_map_ids(s, newest)) for s in range(0, S, max(S // 8, 1))]
+        if args.history:
+            newest = int(kmh.newest()[0])
+            stored = [len(kmh.local_map_ids(s, newest)) for s in range(0, S, max(S // 8, 1))]
+        else:                                                    # the rows the second map holds: per sampled stream the rows per live point, and what the bound dropped
+            got = [kmh.descriptor_rows(s) for s in range(0, S, max(S // 8, 1))]
+            rows_per_point = [float(np.mean([len(k_) for k_ in g["keys"]])) if len(g["keys"]) else 0.0 for g in got]
+            rows_dropped = [g["dropped"] for g in got]
         kmh.close()
     km.close(); ks.close()
     rec = {"lib": os.path.basename(slam.LIB_PATH), "S": S, "cap": CAP, "keypoints_per_stream": NKP, "shape": [H, W], "cell": CELL, "ring": RING, "table": MCAP,
            "max_local": args.max_local, "repeats": R, "host_repeats": len(m["h_total"]), "warmup_keyframes": WARM,
            "local_map_points_per_stream": stat(m["M"]), "keypoints_with_descriptor_per_stream": stat(m["N"]), "pairs_all_streams": stat(m["pairs"]),
-           "a_add_descriptors_device_ms": stat(m["desc"]),
+           "a_add_keyframe_device_ms": stat(m["add"]), "a_add_descriptors_device_ms": stat(m["desc"]),
            "b_local_map_match_device_ms": stat(m["call"]), "b_stage_kernel_ms": stat(m["stage"]), "b_match_kernel_ms": stat(m["kernel"]),
            "b_local_map_match_sync_wall_ms": stat(m["wall"]),
            "c_host_route_wall_ms": stat(m["h_total"]), "c_host_downloads_wall_ms": stat(m["h_down"]), "c_host_assembly_and_packing_wall_ms": stat(m["h_asm"]),
@@ -192,6 +216,15 @@ def main():
                     "history_pairs_all_streams": stat(m["hist_pairs"]), "history_streams_with_status_2": stat(m["hist_status2"]),
                     "history_local_map_match_device_ms": stat(m["hist_call"]), "history_stage_kernel_ms": stat(m["hist_stage"]),
                     "history_match_kernel_ms": stat(m["hist_kernel"]), "history_local_map_match_sync_wall_ms": stat(m["hist_wall"])})
+    if args.rows:                                                # with random descriptors no pair occurs: upkeep and staging, not merges
+        rec = {k: v for k, v in rec.items() if not k.startswith("c_")}
+        rec.update({"rows_per_point_D": args.rows, "rows_per_live_point": stat(rows_per_point), "rows_dropped_by_the_bound": stat(rows_dropped),
+                    "rows_pairs_all_streams": stat(m["hist_pairs"]), "rows_streams_with_status_2": stat(m["hist_status2"]),
+                    "rows_add_keyframe_device_ms": stat(m["hist_add"]), "rows_add_descriptors_device_ms": stat(m["hist_desc"]),
+                    "rows_local_map_match_device_ms": stat(m["hist_call"]), "rows_stage_kernel_ms": stat(m["hist_stage"]),
+                    "rows_match_kernel_ms": stat(m["hist_kernel"]), "rows_local_map_match_sync_wall_ms": stat(m["hist_wall"]),
+                    "note": "both maps take the same key-frames in one session; random descriptors pair nothing, so the figures are upkeep (add_keyframe's forgetting and "
+                            "recording, add_descriptors) and staging, not merges; slam_kfmap_merge and slam_kfmap_filter are not timed here"})
     print(json.dumps(rec))
     if args.out:
         with open(args.out, "w") as f_:

@@ -53,26 +53,41 @@ __device__ __forceinline__ unsigned long long kfm_live_observers(const KfmapView
 // Tcw of a key-frame from its six parameters: angles_to_pose and the bottom row 0 0 0 1 (column-major 4 x 4)
 __device__ __forceinline__ void kfm_tcw(const double *theta, double *T) { angles_to_pose(theta, T); T[3] = 0.0; T[7] = 0.0; T[11] = 0.0; T[15] = 1.0; }
 
+// Kernels that clear an observer bit come as <bool ROWS>; <true>: the row store is on and they take the whole view (KfmapRows), <false>: the kernel as it
+// always was, on the KfmapView.
+// The row store's share of remove_kf_observation! (map_point.jl:88-122) for entry pe, which has just lost the observer of key-frame `key` - 1 and keeps the
+// observers `left`: the row under that key goes; with no valid observer left every row goes and the point is no longer described.  A thread zeroes its
+// own key's slot alone; the clear-all belongs to the one thread whose update left no observer (several slabs may lose one point in the filter's closing pass).
+__device__ __forceinline__ void kfm_rows_lost(const KfmapRows &V, int s, size_t pe, int32_t key, unsigned long long left)
+{
+    int32_t *rk = V.rkey + pe * V.D;
+    bool any = false;
+    kfm_each_observer(left, V.tag + s * V.R, V.R, [&](int) { any = true; });
+    if (any) (void)kfm_rows_drop(rk, V.D, key);
+    else { kfm_rows_clear(rk, V.D); V.dhas[pe] = 0; }
+}
 // remove_kf_observation! for observation i of slot r's slab (i < the slab's length): a live observation's point, where its entry still carries that id,
 // loses observer bit r.  THE rule of remove_keyframe! (map_manager.jl:184-209) as far as the map goes -- the forgetting of a re-used slot, the filter's
 // removals and slam_kfmap_remove_keyframe all come here.  Ids are unique within a slab, but several slabs may lose the same point in one launch (the
-// filter's closing pass): the atomic keeps every read-modify-write whole.
-__device__ __forceinline__ void kfm_forget_slab(const KfmapView &V, int s, int r, int i)
+// filter's closing pass): the atomic keeps every read-modify-write whole, and its return value tells the rows (ROWS) whether the bit was set and what is left.
+template <bool ROWS> __device__ __forceinline__ void kfm_forget_slab(const KfmView<ROWS> &V, int s, int r, int i)
 {
     int64_t id;
     size_t pe;
-    if (kfm_slab_point(V, s, r, i, id, pe) && kfm_owned(V, pe, id)) atomicAnd(&V.pmask[pe], ~(1ull << r));
+    if (!kfm_slab_point(V, s, r, i, id, pe) || !kfm_owned(V, pe, id)) return;
+    const unsigned long long old = atomicAnd(&V.pmask[pe], ~(1ull << r));
+    if constexpr (ROWS) { if ((old >> r & 1) && !(V.pflags[pe] & KFM_DEAD)) kfm_rows_lost(V, s, pe, V.tag[s * V.R + r], old & ~(1ull << r)); }
 }
 
 // ---- recording: slot-parallel, one thread per list slot (grid.y = stream) -------------------------------------------------------------------------------
 // the key-frame whose slot the new one takes is forgotten: every point it observed loses that observer
-__global__ __launch_bounds__(256) void k_kfm_forget(KfmapView V, const int *kfcount, const int *sel)
+template <bool ROWS> __global__ __launch_bounds__(256) void k_kfm_forget(KfmView<ROWS> V, const int *kfcount, const int *sel)
 {
     const int s = KFM_STREAM(blockIdx.y), i = blockIdx.x * 256 + threadIdx.x, kfid = kfcount[s] - 1;
     if (kfid < 0) return;
     const int r = kfid % V.R, t = V.tag[s * V.R + r];
     if (t == 0 || t == kfid + 1 || i >= min(V.kn[s * V.R + r], V.cap)) return;
-    kfm_forget_slab(V, s, r, i);
+    kfm_forget_slab<ROWS>(V, s, r, i);
 }
 // "for mp in rec.mps.values(): mp.observed = False"
 __global__ __launch_bounds__(256) void k_kfm_clear_observed(KfmapView V, const int *kfcount, const int *sel)
@@ -96,7 +111,7 @@ __global__ __launch_bounds__(256) void k_kfm_claim(KfmapView V, KpsetView K, con
     V.kfresh[(size_t)s * V.cap + i] = fresh;
 }
 // tracked_ba.add_keyframe: the slab of the new key-frame, and every listed point's entry (one thread per entry: its owner's)
-__global__ __launch_bounds__(256) void k_kfm_record(KfmapView V, KpsetView K, const double *par, const int *sel)
+template <bool ROWS> __global__ __launch_bounds__(256) void k_kfm_record(KfmView<ROWS> V, KpsetView K, const double *par, const int *sel)
 {
     const int s = KFM_STREAM(blockIdx.y), i = blockIdx.x * 256 + threadIdx.x, kfid = K.kfcount[s] - 1;
     if (kfid < 0) return;
@@ -123,6 +138,7 @@ __global__ __launch_bounds__(256) void k_kfm_record(KfmapView V, KpsetView K, co
         for (int k = 0; k < 3; k++) V.pxyz[3 * pe + k] = K.xyz[3 * ql + k];
         V.pmask[pe] = 1ull << r; V.pflags[pe] = KFM_OBS | (t3 ? KFM_3D : 0);
         if (V.dhas) V.dhas[pe] = 0;                                              // a new owner: the old point's descriptor goes with it
+        if constexpr (ROWS) kfm_rows_clear(V.rkey + pe * V.D, V.D);              // and its rows
     } else {
         const uint8_t fl = V.pflags[pe];
         V.pmask[pe] |= 1ull << r;
@@ -172,7 +188,7 @@ __device__ __forceinline__ int kfm_covisibility(const KfmapView &V, int s, int r
 //   poses          after each phase the key-frames first met in it take the next pose ids in the order of those indices (one thread): membership in
 //                  `poses` decides whether a later low-score co-key-frame is walked, hence the phases are dependent
 // Everything the emit pass and the update need goes into the stream's pending-window regions; hdr = status (0 window, 1 none), kfid, P, M, O.
-__global__ __launch_bounds__(256) void k_kfm_plan(KfmapView V, const int *minc_all, const int *sel)
+template <bool ROWS> __global__ __launch_bounds__(256) void k_kfm_plan(KfmView<ROWS> V, const int *minc_all, const int *sel)
 {
     __shared__ int s_cov[64], s_first[64], s_order[64], s_asc[64], s_rank[64], s_tag[64], s_w[4], s_base, s_obase, s_cl[N_COVISIBLE], s_ncl, s_P, s_nb3, s_nv, s_nbad;
     __shared__ unsigned long long s_covmask;
@@ -225,7 +241,14 @@ __global__ __launch_bounds__(256) void k_kfm_plan(KfmapView V, const int *minc_a
                         acc = true;
                         wm = kfm_live_observers(V, s, m, s_tag, id);                     // an observer whose key-frame or pixel is gone loses the point (remove_obs)
                         cnt = __popcll(wm);
-                        if (wm != m) V.pmask[pe] = wm;
+                        if (wm != m) {
+                            V.pmask[pe] = wm;
+                            if constexpr (ROWS) {                                        // the lost observers' rows go; no observer left: all of them
+                                int32_t *rk = V.rkey + pe * V.D;
+                                kfm_each_observer(m & ~wm, s_tag, R, [&](int b) { (void)kfm_rows_drop(rk, V.D, s_tag[b]); });
+                                if (wm == 0) { kfm_rows_clear(rk, V.D); V.dhas[pe] = 0; }
+                            }
+                        }
                     }
                 }
             }
@@ -306,7 +329,7 @@ struct KfmUpd { int s; long long theta0, obs0; };
 // poses, and the removals of the outlier observations: one thread per point of the window walks the point's observations.  A thread touches its own
 // point's entry alone; the tombstone it writes is its own observation's: any thread order gives the same map.  Everything goes by key-frame and keypoint
 // id: a slot whose tag is no longer the gather's holds another key-frame now and is skipped, a point whose entry another id holds is skipped.
-__global__ __launch_bounds__(256) void k_kfm_upd_obs(KfmapView V, const KfmUpd *wins, const double *theta, const uint8_t *outl)
+template <bool ROWS> __global__ __launch_bounds__(256) void k_kfm_upd_obs(KfmView<ROWS> V, const KfmUpd *wins, const double *theta, const uint8_t *outl)
 {
     __shared__ int s_asc[64];
     const KfmUpd W = wins[blockIdx.y];
@@ -335,11 +358,13 @@ __global__ __launch_bounds__(256) void k_kfm_upd_obs(KfmapView V, const KfmUpd *
             if ((cov >> b & 1) && V.tag[s * R + b] == V.wtag[s * R + b]) {               // remove_mappoint_obs! (map_manager.jl:224-)
                 const int i = kfm_find_live(V, s, b, id);
                 if (i >= 0) V.klive[((size_t)s * R + b) * V.cap + i] = 0;
+                if constexpr (ROWS) { if (have && (mask >> b & 1)) (void)kfm_rows_drop(V.rkey + pe * V.D, V.D, V.wtag[s * R + b]); }
                 mask &= ~(1ull << b);
             }
             if (V.wtag[s * R + b] - 1 == kfid) fl = (fl & (uint8_t)~KFM_OBS) | KFM_GONE;     // remove_obs_from_current_frame!
         }
     }
+    if constexpr (ROWS) { if (have && mask != V.pmask[pe]) kfm_rows_lost(V, s, pe, 0, mask); }       // (the rows went above; no valid observer left: all go)
     if (have) { V.pmask[pe] = mask; V.pflags[pe] = fl; }
 }
 // remove_mappoint! (map_manager.jl:139-168): the point's observations become tombstones, the entry dies; an observed point's id has left the frame
@@ -398,7 +423,7 @@ __global__ __launch_bounds__(256) void k_kfm_upd_list(KfmapView V, KpsetView K, 
 //                  no phase reads anything an earlier phase wrote and the map is written once, in a closing pass over the removed slabs (kfm_forget_slab),
 //                  after the last phase's barrier; then their tags and lengths are reset
 // frem[s] = X: bit k % R per removed key-frame.  new_kf_available has no counterpart: lock-stepped streams never race.
-__global__ __launch_bounds__(256) void k_kfm_filter(KfmapView V, const double *ratio_all, const int *minc_all, int first_kfid, const int *sel)
+template <bool ROWS> __global__ __launch_bounds__(256) void k_kfm_filter(KfmView<ROWS> V, const double *ratio_all, const int *minc_all, int first_kfid, const int *sel)
 {
     __shared__ int s_cov[64], s_tag[64], s_cand[64], s_ncand, s_tot[2][4], s_good[2][4];
     __shared__ unsigned long long s_valid;
@@ -440,18 +465,18 @@ __global__ __launch_bounds__(256) void k_kfm_filter(KfmapView V, const double *r
     }
     for (unsigned long long m = X; m; m &= m - 1) {              // every phase's reads lie behind its barrier: now the removals, all at once
         const int b = __ffsll((long long)m) - 1, n = min(V.kn[s * R + b], cap);
-        for (int i = tid; i < n; i += 256) kfm_forget_slab(V, s, b, i);
+        for (int i = tid; i < n; i += 256) kfm_forget_slab<ROWS>(V, s, b, i);
     }
     __syncthreads();                                             // the lengths are read above, reset below
     if (tid < R && (X >> tid & 1)) { V.tag[s * R + tid] = 0; V.kn[s * R + tid] = 0; }
     if (tid == 0) V.frem[s] = X;
 }
 // slam_kfmap_remove_keyframe: slab-parallel, then (a launch later: every block has read the tag) the slot is emptied
-__global__ __launch_bounds__(256) void k_kfm_remove(KfmapView V, int s, int kfid)
+template <bool ROWS> __global__ __launch_bounds__(256) void k_kfm_remove(KfmView<ROWS> V, int s, int kfid)
 {
     const int r = kfid % V.R, i = blockIdx.x * 256 + threadIdx.x;
     if (V.tag[s * V.R + r] != kfid + 1 || V.cur[s] == kfid + 1 || i >= min(V.kn[s * V.R + r], V.cap)) return;
-    kfm_forget_slab(V, s, r, i);
+    kfm_forget_slab<ROWS>(V, s, r, i);
 }
 __global__ void k_kfm_drop_slot(KfmapView V, int s, int kfid)
 {
@@ -459,6 +484,11 @@ __global__ void k_kfm_drop_slot(KfmapView V, int s, int kfid)
     if (V.tag[q] == kfid + 1 && V.cur[s] != kfid + 1) { V.tag[q] = 0; V.kn[q] = 0; }
 }
 
+// A <bool ROWS> kernel's launch, 256 threads a workgroup, the view first among its arguments: <true> with the whole view where the row store is on, else
+// <false> with the view as it always was
+#define KFM_LAUNCH_ROWS(km, kernel, grid, ...) \
+    do { if ((km)->v.rkey) hipLaunchKernelGGL(kernel<true>, grid, dim3(256), 0, ctx->stream, (km)->v, __VA_ARGS__); \
+         else hipLaunchKernelGGL(kernel<false>, grid, dim3(256), 0, ctx->stream, static_cast<const KfmapView &>((km)->v), __VA_ARGS__); } while (0)
 // Every region of the map's one allocation, each named once (kfmap.hpp has the formula): without a block for the total, with it to bind the pointers
 static size_t kfmap_regions(slam_kfmap *km, char *base)
 {
@@ -551,6 +581,7 @@ int slam_kfmap_destroy(slam_kfmap *km)
     if (km->base) (void)hipFree(km->base);
     if (km->pin) (void)hipHostFree(km->pin);
     if (km->dbase) (void)hipFree(km->dbase);
+    if (km->rbase) (void)hipFree(km->rbase);
     if (km->lm_base) (void)hipFree(km->lm_base);
     if (km->mg_base) (void)hipFree(km->mg_base);
     if (km->hs_base) (void)hipFree(km->hs_base);
@@ -572,10 +603,10 @@ int slam_kfmap_add_keyframe(slam_ctx *ctx, slam_kfmap *km, slam_kpset *ks, const
     const KfmapView &V = km->v;
     const dim3 gl((ks->v.cap + 255) / 256, ns), gs((V.cap + 255) / 256, ns), gm((V.mcap + 255) / 256, ns);
     { ProfScope span(ctx, "kfmap_add");
-      hipLaunchKernelGGL(k_kfm_forget, gs, dim3(256), 0, ctx->stream, V, (const int *)ks->v.kfcount, sel);
+      KFM_LAUNCH_ROWS(km, k_kfm_forget, gs, (const int *)ks->v.kfcount, sel);
       hipLaunchKernelGGL(k_kfm_clear_observed, gm, dim3(256), 0, ctx->stream, V, (const int *)ks->v.kfcount, sel);
       hipLaunchKernelGGL(k_kfm_claim, gl, dim3(256), 0, ctx->stream, V, ks->v, sel);
-      hipLaunchKernelGGL(k_kfm_record, gl, dim3(256), 0, ctx->stream, V, ks->v, par, sel); }
+      KFM_LAUNCH_ROWS(km, k_kfm_record, gl, ks->v, par, sel); }
     HIP_TRY(ctx, hipGetLastError());
     return SLAM_OK;
 }
@@ -605,7 +636,7 @@ int slam_kfmap_ba_gather(slam_ctx *ctx, slam_kfmap *km, const int32_t *min_cov_s
     kfmap_put_streams(o_sel, h, list, ns); memcpy(o_minc.at(h), min_cov_score, (size_t)S * 4);
     HIP_TRY(ctx, hipMemcpyAsync(scr, h, in_b, hipMemcpyHostToDevice, ctx->stream));
     { ProfScope span(ctx, "kfmap_gather_plan");
-      hipLaunchKernelGGL(k_kfm_plan, dim3(ns), dim3(256), 0, ctx->stream, V, (const int *)o_minc.at(scr), (const int *)o_sel.at(scr)); }
+      KFM_LAUNCH_ROWS(km, k_kfm_plan, dim3(ns), (const int *)o_minc.at(scr), (const int *)o_sel.at(scr)); }
     HIP_TRY(ctx, hipGetLastError());
     rc = kpset_read_back(ctx, h, {{0, V.whdr, (size_t)S * KFM_HDR * 4, nullptr}});
     if (rc) return rc;
@@ -690,7 +721,7 @@ int slam_kfmap_ba_update(slam_ctx *ctx, slam_kfmap *km, slam_kpset *ks, int n_wi
         HIP_TRY(ctx, hipMemsetAsync(flags, 0, (size_t)ks->S * ks->v.cap, ctx->stream));
     }
     { ProfScope span(ctx, "kfmap_update");
-      hipLaunchKernelGGL(k_kfm_upd_obs, dim3((maxM + 255) / 256, n_windows), dim3(256), 0, ctx->stream, V, wd, (const double *)o_th.at(scr), (const uint8_t *)o_ol.at(scr));
+      KFM_LAUNCH_ROWS(km, k_kfm_upd_obs, dim3((maxM + 255) / 256, n_windows), wd, (const double *)o_th.at(scr), (const uint8_t *)o_ol.at(scr));
       hipLaunchKernelGGL(k_kfm_upd_points, dim3((V.mcap + 255) / 256, n_windows), dim3(256), 0, ctx->stream, V, wd, (const double *)o_th.at(scr));
       if (ks) hipLaunchKernelGGL(k_kfm_upd_list, dim3((ks->v.cap + 255) / 256, n_windows), dim3(256), 0, ctx->stream, V, ks->v, wd, flags); }
     HIP_TRY(ctx, hipGetLastError());
@@ -720,7 +751,7 @@ int slam_kfmap_filter(slam_ctx *ctx, slam_kfmap *km, const double *filtering_rat
     });
     if (rc) return rc;
     { ProfScope span(ctx, "kfmap_filter");
-      hipLaunchKernelGGL(k_kfm_filter, dim3(ns), dim3(256), 0, ctx->stream, V, (const double *)o_ratio.at(scr), (const int *)o_minc.at(scr), first_kfid, (const int *)o_sel.at(scr)); }
+      KFM_LAUNCH_ROWS(km, k_kfm_filter, dim3(ns), (const double *)o_ratio.at(scr), (const int *)o_minc.at(scr), first_kfid, (const int *)o_sel.at(scr)); }
     HIP_TRY(ctx, hipGetLastError());
     if (!removed) return SLAM_OK;
     rc = slam_pinned(ctx, (size_t)S * 8, (void **)&h);
@@ -742,7 +773,7 @@ int slam_kfmap_remove_keyframe(slam_ctx *ctx, slam_kfmap *km, int s, int kfid)
     if (cur >= 1 && kfid == cur - 1) return slam_fail(ctx, SLAM_ERR_ARG, "slam_kfmap_remove_keyframe: key-frame %d is the newest of stream %d", kfid, s);
     if (kfid >= cur || kfid + V.R < cur) return SLAM_OK;         // never added, or long forgotten: not in the ring
     { ProfScope span(ctx, "kfmap_remove");
-      hipLaunchKernelGGL(k_kfm_remove, dim3((V.cap + 255) / 256), dim3(256), 0, ctx->stream, V, s, kfid);
+      KFM_LAUNCH_ROWS(km, k_kfm_remove, dim3((V.cap + 255) / 256), s, kfid);
       hipLaunchKernelGGL(k_kfm_drop_slot, dim3(1), dim3(1), 0, ctx->stream, V, s, kfid); }
     HIP_TRY(ctx, hipGetLastError());
     return SLAM_OK;
@@ -832,6 +863,10 @@ int slam_kfmap_reset(slam_ctx *ctx, slam_kfmap *km, int s)
     HIP_TRY(ctx, hipMemsetAsync(V.pmask + (size_t)s * V.mcap, 0, (size_t)V.mcap * 8, ctx->stream));
     HIP_TRY(ctx, hipMemsetAsync(V.cur + s, 0, 4, ctx->stream));
     if (V.dhas) HIP_TRY(ctx, hipMemsetAsync(V.dhas + (size_t)s * V.mcap, 0, (size_t)V.mcap, ctx->stream));
+    if (km->v.rkey) {                                            // no rows, nothing dropped (the rows' bits mean nothing without their keys)
+        HIP_TRY(ctx, hipMemsetAsync(km->v.rkey + (size_t)s * V.mcap * km->v.D, 0, (size_t)V.mcap * km->v.D * 4, ctx->stream));
+        HIP_TRY(ctx, hipMemsetAsync(km->v.rdrop + s, 0, 4, ctx->stream));
+    }
     HIP_TRY(ctx, hipMemsetAsync(V.whdr + (size_t)s * KFM_HDR, 0, KFM_HDR * 4, ctx->stream));
     if (km->hs_base) {                                           // the stream's stored sets, their owners and the shadow tags (= the emptied table's)
         const KfmHist &H = km->hs;

@@ -25,20 +25,45 @@
 // Descriptors (slam_kfmap_enable_descriptors; a second allocation, made by that call): one 256-bit row and a "has descriptor" byte per table entry,
 // 33 mcap bytes per stream.  The row of point `id` lives at entry id % mcap under the table's ownership rule: slam_kfmap_add_descriptors writes it only
 // where the entry carries that id, and an entry that changes owner (a larger id claims it, or a removed id is recorded anew) loses the byte with the point.
-// ONE descriptor per point is the whole of the reference's keyframes_descriptors here: map_manager.jl:116-131 describes only the keypoints a key-frame
-// has just extracted, and further rows would come from merges: slam_kfmap_merge keeps the new point's own row and lets prev's row go with prev (the
-// reference appends prev's rows to keyframes_descriptors, and mappoint_min_distance takes the minimum over all of them).
+// Without the row store (below) ONE descriptor per point is the whole of the reference's keyframes_descriptors: map_manager.jl:116-131 describes only the
+// keypoints a key-frame has just extracted, and further rows would come from merges: slam_kfmap_merge then keeps the new point's own row and lets prev's
+// row go with prev (the reference appends prev's rows to keyframes_descriptors, and mappoint_min_distance takes the minimum over all of them).
+//
+// Descriptor rows (slam_kfmap_enable_descriptor_rows, kfmap_lmm.inc; an allocation of its own, made by that call; needs the descriptors): keyframes_descriptors
+// (map_point.jl:15), one row per key-frame id, D = 2 .. 8 slots per table entry.  With m = S mcap, each region rounded up to 256:
+//   keys     4 m D    key-frame id + 1 of the slot's row (0: an empty slot)
+//   rows     32 m D   the slot's 256-bit row
+//   dropped  4 S      rows the bound D has dropped on the stream
+// i.e. about 36 D mcap bytes per stream (D 4, mcap 16 384: 2.4 MB; S = 128: 300 MB).  Slots may have holes; readers take the non-empty slots ascending by key.
+// The row-set logic is kfmap_ring.hpp's kfm_rows_*.  dhas becomes the reference's "mp.descriptor is not empty": set by add_descriptors (and by a merge
+// that hands a point its first row), cleared when the entry changes owner and when the point's last valid observer goes; a described point without a row is
+// legal, staged with an empty row range and never chosen.  ddesc stays what add_descriptors wrote and is not staged.  Upkeep, every kernel a <bool ROWS>
+// instantiation (a map without the store launches the <false> kernels, which are the kernels as they were):
+//   add_descriptors   the row also goes under the key of the stream's newest key-frame (add_mappoint!'s current_keyframe_id; add_descriptor!: a key the
+//                     point already has is skipped)
+//   observers         wherever an observer bit of a live, owned point is cleared -- kfm_forget_slab (ring reuse in k_kfm_forget, the filter's closing pass,
+//                     k_kfm_remove), the outlier tombstone of k_kfm_upd_obs, the vanished pixel of k_kfm_plan -- the row keyed by that slot's key-frame goes;
+//                     no valid observer left: all keys and dhas are cleared (remove_kf_observation!, map_point.jl:88-122).  Several slabs may lose one point
+//                     concurrently (the filter): a thread zeroes its own key's slot, the clear-all is the thread's whose atomicAnd left no observer
+//   owners            k_kfm_record clears the keys of an entry that takes a new owner; slam_kfmap_reset clears the stream's rows and counter
+//   merge             the pair's thread of k_kfm_merge_resolve forms the union of new's and prev's rows by key (the pair owns both entries); on an equal key
+//                     new's row stays; prev's keys are cleared with the point (map_manager.jl:410-412)
+//   match             the stager writes every row of a local-map point and of a keypoint ascending by key, mp_doff / kp_doff are a scan of the row counts,
+//                     the staging's descriptor regions hold D rows per record (DR in the formula below); k_lmm_match is untouched
+// Deviations: the bound -- a union of more than D rows keeps the D rows with the LARGEST keys, whatever the order of slots, arrivals or pairs, and the excess
+// is added to the stream's counter; the reference's most representative `descriptor` (map_point.jl:98-120, :132-144) is read by nothing but the emptiness test
+// and is not modelled; a reused ring slot counts as remove_keyframe!.
 //
 // Local-map staging (slam_kfmap_local_map_match, kfmap_lmm.inc; a third allocation, made by the first call and re-made when max_local or the grid grows):
 // the packed buffer of k_lmm_match (lmm_host.hpp) with FIXED per-stream strides -- no count pass, no scan over the streams, hence no host round trip between
 // staging and match.  With N1 = cap + 1, M1 = max_local + 1, C1 = the call's largest cell count + 1, per stream, each region rounded up to 256 over S:
-//   keypoints   N1 (16 yx + 4 + 4 offsets + 32 descriptor + 8 id + 4 cell list + 8 key) + 20 N1 R observers (row, pixel)
+//   keypoints   N1 (16 yx + 4 + 4 offsets + 32 DR descriptors + 8 id + 4 cell list + 8 key) + 20 N1 R observers (row, pixel)
 //   key-frames  128 R
-//   local map   M1 (24 xyz + 4 + 4 offsets + 32 descriptor + 8 id + 4 + 8 + 16 best_kp, best_dist, proj_yx) + 4 M1 R observers
+//   local map   M1 (24 xyz + 4 + 4 offsets + 32 DR descriptors + 8 id + 4 + 8 + 16 best_kp, best_dist, proj_yx) + 4 M1 R observers
 //   cells       8 C1 (offsets, cursors) | mark 4 mcap | LmmStream 280 | counts 8
 //   results     status 4 | pairs 4 | cap (16 ids + 8 distance)
-// i.e. about cap (100 + 20 R) + max_local (100 + 4 R) + 4 mcap bytes per stream (cap 1 400, R 32, max_local 14 000, mcap 16 384: 4.3 MB; S = 128:
-// 550 MB).  The observer regions are sized for the worst case (every point seen by every key-frame of the ring); they are what a count -> scan -> emit
+// (DR = 1 descriptor row per record, or D with the row store) i.e. about cap (68 + 32 DR + 20 R) + max_local (68 + 32 DR + 4 R) + 4 mcap bytes per
+// stream (cap 1 400, R 32, max_local 14 000, mcap 16 384, DR 1: 4.3 MB; S = 128: 550 MB; DR 4: 5.8 MB; 740 MB).  The observer regions are sized for the worst case (every point seen by every key-frame of the ring); they are what a count -> scan -> emit
 // staging would save, at the price of a second pass over the table and a scan launch.
 //
 // Deviations of slam_kfmap_local_map_match from update_frame_covisibility! + match_local_map! (map_manager.jl:302-355, mapper.jl:265-462):
@@ -79,7 +104,7 @@
 // i.e. about (53 R + 132) cap bytes per stream (cap 1 400, R 32: 2.6 MB; S = 128: 330 MB).  The main allocation's layout is untouched.
 // slam_kfmap_merge against the reference (the first three are deviations, the last two the reference's own rules as they show in slabs):
 //   covisibility  add_covisibility! has no counterpart: covisibility is derived from the observer masks (as for the filter's remove_covisible_kf!)
-//   descriptors   one row per point: new keeps its own, prev's goes with prev (above)
+//   descriptors   without the row store one row per point: new keeps its own, prev's goes with prev; with it new takes prev's rows by key (above)
 //   gone          without a keypoint set (ks == NULL) prev's entry is also marked KFM_GONE, so that later lists that still carry prev_id are not
 //                 recorded as a fresh point (the reference always has the current frame at hand)
 //   orphans       pop!(map_points, prev_id) is not remove_mappoint!: where a slab holds both ids (has_new) prev's observation stays, alive, without a point
@@ -118,8 +143,20 @@ struct KfmapView {
     int *went;                            // [S mcap] by table entry: 0 untouched, -1 bad, j + 1 = point j of the window
     // the descriptor store (nullptr until slam_kfmap_enable_descriptors)
     uint64_t *ddesc;                      // [S mcap][4] the 256-bit row of the entry's point
-    uint8_t *dhas;                        // [S mcap] 1: the row belongs to the entry's current owner
+    uint8_t *dhas;                        // [S mcap] 1: the row belongs to the entry's current owner (with rows: the point's `descriptor` is not empty)
 };
+// the view with the row store (slam_kfmap_enable_descriptor_rows): keyframes_descriptors, D slots per entry (kfmap_ring.hpp's kfm_rows_*).  Only the
+// <true> instantiations of the <bool ROWS> kernels take it; every other kernel takes the KfmapView in it, so a map without rows launches the kernels it
+// always did with the argument block they always had.
+struct KfmapRows : KfmapView {
+    int32_t *rkey;                        // [S mcap][D] key-frame id + 1 of the slot's row (0: empty; nullptr: the store is off)
+    uint64_t *rrow;                       // [S mcap][D][4]
+    int32_t *rdrop;                       // [S] rows dropped by the bound D so far
+    int D;                                // rows per point (0: the store is off)
+};
+template <bool ROWS> struct KfmViewOf { using type = KfmapView; };
+template <> struct KfmViewOf<true> { using type = KfmapRows; };
+template <bool ROWS> using KfmView = typename KfmViewOf<ROWS>::type;
 
 // what the host works out per stream for a staged local-map call (everything of LmmStream that does not depend on the map)
 struct KfmLmArg { double cam[10], max_proj, start, view_thr; int32_t cell, gr, gc, pad; };
@@ -127,6 +164,7 @@ struct KfmLmArg { double cam[10], max_proj, start, view_thr; int32_t cell, gr, g
 // the local-map regions, [s R, ..) of the key-frame rows, [s C1, ..) of the cell regions, [s N1 R, ..) / [s M1 R, ..) of the observer regions
 struct KfmLm {
     int N1, M1, C1, max_local;
+    int DR;                               // descriptor rows a record's share of kp_desc / mp_desc holds: 1, or D with the row store
     LmmStream *st;                        // [S] by LAUNCH index: row z is the z-th stream acted on
     double *kp_yx; int32_t *kp_doff; uint64_t *kp_desc; int32_t *kp_ooff, *kp_okf; double *kp_oyx; int64_t *kp_id;
     double *kf_Tcw;
@@ -171,13 +209,14 @@ struct KfmMerge {
 struct slam_kfmap {
     int device = 0;
     char *base = nullptr; size_t bytes = 0;
-    KfmapView v = {};
+    KfmapRows v = {};
     // the streams the last add_keyframe acted on (the set's selection at that call): gather's streams
     int n_sel = KPSEL_ALL; uint8_t sel_host[128] = {};
     struct Pending { int valid = 0, kfid = -1, P = 0, M = 0, O = 0; } pend[128];      // host copy of the pending windows' sizes
     // update's staging (theta, outlier flags, window table): a pinned block of the map's own with the event of the copy that last read it
     char *pin = nullptr; size_t pin_bytes = 0; hipEvent_t pin_ev = nullptr;
     char *dbase = nullptr;                // the descriptor store
+    char *rbase = nullptr;                // the row store (nullptr: off)
     char *lm_base = nullptr; size_t lm_bytes = 0, lm_res_off = 0, lm_res_bytes = 0; KfmLm lm = {};        // the local-map staging (lm.max_local, lm.C1: what it was laid out for)
     int lm_np[128] = {};                  // pairs per stream in the result block of the last local-map match, until a merge has consumed them
     char *mg_base = nullptr; size_t mg_bytes = 0; KfmMerge mg = {};       // the merge's scratch

@@ -8,7 +8,8 @@
 
 // ---- descriptors: slot-parallel, one thread per appended keypoint (grid.y = stream) ---------------------------------------------------------------------
 // row j of stream s belongs to id info[2 s] + j (slam_kpset_detect_describe); it is stored where the table entry carries that id
-__global__ __launch_bounds__(256) void k_kfm_desc_record(KfmapView V, const uint64_t *desc, const int64_t *info, int dcap, const int *sel)
+// ROWS: the row also goes into the row store under the key of the stream's newest key-frame (add_mappoint!'s current_keyframe_id)
+template <bool ROWS> __global__ __launch_bounds__(256) void k_kfm_desc_record(KfmView<ROWS> V, const uint64_t *desc, const int64_t *info, int dcap, const int *sel)
 {
     const int s = KFM_STREAM(blockIdx.y), j = blockIdx.x * 256 + threadIdx.x;
     const int64_t n = info[2 * s + 1];
@@ -19,6 +20,10 @@ __global__ __launch_bounds__(256) void k_kfm_desc_record(KfmapView V, const uint
     const uint64_t *src = desc + 4 * ((size_t)s * dcap + j);
     for (int k = 0; k < 4; k++) V.ddesc[4 * pe + k] = src[k];
     V.dhas[pe] = 1;
+    if constexpr (ROWS) {
+        const int dropped = kfm_rows_put(V.rkey + pe * V.D, V.rrow + 4 * pe * V.D, V.D, V.cur[s], src);
+        if (dropped) atomicAdd(&V.rdrop[s], dropped);
+    }
 }
 
 // ---- the local-map history (slam_kfmap_enable_local_map_history): frame.local_map_ids kept between key-frames -------------------------------------------
@@ -106,11 +111,14 @@ __device__ __forceinline__ void kfm_lm_history(const KfmapView &V, const KfmLm &
 //                  256 in list order -- a keypoint's place is its cell's cursor plus the chunk's earlier keypoints of the same cell
 // status: 0 staged, 1 nothing to match (no key-frame, no covisible key-frame, an empty local map or keypoint list), 2 the local map exceeds max_local
 // (nothing of it is used).  A stream that is not staged gets M = 0 in its LmmStream row: every group of the match kernel leaves at once.
-template <bool HIST>
-__device__ __forceinline__ void kfm_lm_stage_body(const KfmapView &V, const KfmLm &Q, const KfmHist &Hs, const KfmLmArg *args, const int *sel)
+// ROWS (the row store is on): a record's descriptors are its point's rows ascending by key, kp_doff / mp_doff a scan of the row counts (kfm_scan, beside
+// the observers'), a stream's rows packed from row s N1 DR / s M1 DR of kp_desc / mp_desc on; a described point without a row has an empty range.
+template <bool HIST, bool ROWS>
+__device__ __forceinline__ void kfm_lm_stage_body(const KfmView<ROWS> &V, const KfmLm &Q, const KfmHist &Hs, const KfmLmArg *args, const int *sel)
 {
     __shared__ int s_cov[64], s_tag[64], s_rank[64], s_asc[64], s_w[4], s_cell[256], s_base, s_obase, s_nb3, s_nv;
     __shared__ unsigned long long s_covmask, s_q;
+    __shared__ int s_dbase;
     const int z = blockIdx.x, s = sel[z], tid = threadIdx.x, R = V.R, cap = V.cap, mcap = V.mcap;
     LmmStream &T = Q.st[z];
     const KfmLmArg &A = args[s];
@@ -119,7 +127,18 @@ __device__ __forceinline__ void kfm_lm_stage_body(const KfmapView &V, const KfmL
 #define KFM_LM_LEAVE(code) { if (tid == 0) { T.N = 0; T.M = 0; T.K = 0; Q.status[s] = (code); Q.rn[s] = 0; Q.cnt[2 * s] = 0; Q.cnt[2 * s + 1] = 0; } return; }
     if (tid < 64) { s_cov[tid] = 0; s_rank[tid] = 0; s_asc[tid] = 0; s_tag[tid] = tid < R ? V.tag[s * R + tid] : 0; }
     if (tid == 0) { s_base = 0; s_obase = 0; s_nb3 = 0; s_nv = 0; s_covmask = 0; }
+    if constexpr (ROWS) { if (tid == 0) s_dbase = 0; }
     __syncthreads();
+    // (ROWS) the rows of entry pe, ascending by key, to dst; returns their number
+    [[maybe_unused]] auto rows_out = [&](size_t pe, uint64_t *dst) {
+        int n = 0;
+        if constexpr (ROWS) {
+            const int32_t *rk = V.rkey + pe * V.D;
+            for (int j = kfm_rows_next(rk, V.D, 0); j >= 0; j = kfm_rows_next(rk, V.D, rk[j]), n++)
+                for (int k = 0; k < 4; k++) dst[4 * (size_t)n + k] = V.rrow[4 * (pe * V.D + j) + k];
+        }
+        return n;
+    };
     const int kfid = V.cur[s] - 1;
     if (kfid < 0) KFM_LM_LEAVE(1)                                               // (every branch that leaves is uniform over the workgroup)
     const int r0 = kfid % R;
@@ -181,16 +200,22 @@ __device__ __forceinline__ void kfm_lm_stage_body(const KfmapView &V, const KfmL
             kfm_each_observer(V.pmask[pe], s_tag, R, [&](int b) { wm |= 1ull << b; });
         }
         const int off = kfm_scan(__popcll(wm), s_w, &s_obase);
+        int doff = 0;
+        if constexpr (ROWS) doff = kfm_scan(m < M ? kfm_rows_count(V.rkey + pe * V.D, V.D) : 0, s_w, &s_dbase);
         if (m < M) {
             const size_t g = (size_t)mp0 + m;
             for (int k = 0; k < 3; k++) Q.mp_xyz[3 * g + k] = V.pxyz[3 * pe + k];
-            for (int k = 0; k < 4; k++) Q.mp_desc[4 * g + k] = V.ddesc[4 * pe + k];
-            Q.mp_doff[g] = (int32_t)g; Q.mp_ooff[g] = mobs0 + off;
+            if constexpr (ROWS) { Q.mp_doff[g] = mp0 * Q.DR + doff; (void)rows_out(pe, Q.mp_desc + 4 * ((size_t)mp0 * Q.DR + doff)); }
+            else { for (int k = 0; k < 4; k++) Q.mp_desc[4 * g + k] = V.ddesc[4 * pe + k]; Q.mp_doff[g] = (int32_t)g; }
+            Q.mp_ooff[g] = mobs0 + off;
             int j = 0;
             for (int k = 0; k < nv; k++) if (wm >> s_asc[k] & 1) Q.mp_okf[(size_t)mobs0 + off + j++] = k;
         }
     }
-    if (tid == 0) { Q.mp_doff[mp0 + M] = mp0 + M; Q.mp_ooff[mp0 + M] = mobs0 + s_obase; s_base = 0; s_obase = 0; }
+    if (tid == 0) {
+        if constexpr (ROWS) { Q.mp_doff[mp0 + M] = mp0 * Q.DR + s_dbase; s_dbase = 0; } else Q.mp_doff[mp0 + M] = mp0 + M;
+        Q.mp_ooff[mp0 + M] = mobs0 + s_obase; s_base = 0; s_obase = 0;
+    }
     __syncthreads();
     // the keypoints: the newest slab, in slab order
     {
@@ -206,11 +231,14 @@ __device__ __forceinline__ void kfm_lm_stage_body(const KfmapView &V, const KfmL
             if (acc) wm = kfm_live_observers(V, s, V.pmask[pe], s_tag, id);
             const int pos = ordered_slot(acc, s_w, &s_base);
             const int off = kfm_scan(__popcll(wm), s_w, &s_obase);
+            int doff = 0;
+            if constexpr (ROWS) doff = kfm_scan(acc ? kfm_rows_count(V.rkey + pe * V.D, V.D) : 0, s_w, &s_dbase);
             if (acc) {
                 const size_t g = (size_t)kp0 + pos;
                 Q.kp_id[g] = id; Q.kp_yx[2 * g] = V.kupx[2 * (sl + i)]; Q.kp_yx[2 * g + 1] = V.kupx[2 * (sl + i) + 1];
-                for (int k = 0; k < 4; k++) Q.kp_desc[4 * g + k] = V.ddesc[4 * pe + k];
-                Q.kp_doff[g] = (int32_t)g; Q.kp_ooff[g] = kobs0 + off;
+                if constexpr (ROWS) { Q.kp_doff[g] = kp0 * Q.DR + doff; (void)rows_out(pe, Q.kp_desc + 4 * ((size_t)kp0 * Q.DR + doff)); }
+                else { for (int k = 0; k < 4; k++) Q.kp_desc[4 * g + k] = V.ddesc[4 * pe + k]; Q.kp_doff[g] = (int32_t)g; }
+                Q.kp_ooff[g] = kobs0 + off;
                 size_t o = (size_t)kobs0 + off;
                 for (int k = 0; k < nv; k++) {
                     const int b = s_asc[k];
@@ -223,7 +251,10 @@ __device__ __forceinline__ void kfm_lm_stage_body(const KfmapView &V, const KfmL
         }
     }
     const int N = s_base;
-    if (tid == 0) { Q.kp_doff[kp0 + N] = kp0 + N; Q.kp_ooff[kp0 + N] = kobs0 + s_obase; }
+    if (tid == 0) {
+        if constexpr (ROWS) Q.kp_doff[kp0 + N] = kp0 * Q.DR + s_dbase; else Q.kp_doff[kp0 + N] = kp0 + N;
+        Q.kp_ooff[kp0 + N] = kobs0 + s_obase;
+    }
     __syncthreads();
     if (N == 0) KFM_LM_LEAVE(1)
     if (tid < R && s_tag[tid]) kfm_tcw(V.ktheta + 6 * ((size_t)s * R + tid), Q.kf_Tcw + 16 * (size_t)(kf0 + s_rank[tid]));
@@ -270,15 +301,15 @@ __device__ __forceinline__ void kfm_lm_stage_body(const KfmapView &V, const KfmL
     }
 #undef KFM_LM_LEAVE
 }
-__global__ __launch_bounds__(256) void k_kfm_lm_stage(KfmapView V, KfmLm Q, const KfmLmArg *args, const int *sel)
+template <bool ROWS> __global__ __launch_bounds__(256) void k_kfm_lm_stage(KfmView<ROWS> V, KfmLm Q, const KfmLmArg *args, const int *sel)
 {
-    kfm_lm_stage_body<false>(V, Q, KfmHist{}, args, sel);
+    kfm_lm_stage_body<false, ROWS>(V, Q, KfmHist{}, args, sel);
 }
 // the same stager for a map with the local-map history: `mark` comes out of kfm_lm_history, and a stream without a covisible key-frame is still staged
 // (its stored set may hold points)
-__global__ __launch_bounds__(256) void k_kfm_lm_stage_hist(KfmapView V, KfmLm Q, KfmHist Hs, const KfmLmArg *args, const int *sel)
+template <bool ROWS> __global__ __launch_bounds__(256) void k_kfm_lm_stage_hist(KfmView<ROWS> V, KfmLm Q, KfmHist Hs, const KfmLmArg *args, const int *sel)
 {
-    kfm_lm_stage_body<true>(V, Q, Hs, args, sel);
+    kfm_lm_stage_body<true, ROWS>(V, Q, Hs, args, sel);
 }
 
 // prev_new_map (mapper.jl:370-382) as id pairs: ordered compaction of the keypoints somebody chose, in list order = ascending keypoint id
@@ -321,18 +352,26 @@ static size_t kfmap_hist_regions(slam_kfmap *km, char *base)
     if (base) hs.W = (int)W;
     return Lo.size();
 }
+// the row store's regions, each named once (kfmap.hpp has the formula)
+static size_t kfmap_rows_regions(slam_kfmap *km, int D, char *base)
+{
+    Layout Lo;
+    const size_t m = (size_t)km->v.S * km->v.mcap;
+    Lo.bind(km->v.rkey, m * D * 4, base); Lo.bind(km->v.rrow, m * D * 32, base); Lo.bind(km->v.rdrop, (size_t)km->v.S * 4, base);
+    return Lo.size();
+}
 // every region of the staging allocation, each named once (kfmap.hpp has the formula); the results last, one block
 static size_t kfmap_lm_regions(slam_kfmap *km, int max_local, int C1, char *base)
 {
     Layout Lo;
     const KfmapView &v = km->v;
     KfmLm &q = km->lm;
-    const size_t S = v.S, N1 = (size_t)v.cap + 1, M1 = (size_t)max_local + 1, n = S * N1, m = S * M1, R = v.R;
-    q.N1 = (int)N1; q.M1 = (int)M1; q.C1 = C1; q.max_local = max_local;
+    const size_t S = v.S, N1 = (size_t)v.cap + 1, M1 = (size_t)max_local + 1, n = S * N1, m = S * M1, R = v.R, DR = km->v.D ? km->v.D : 1;
+    q.N1 = (int)N1; q.M1 = (int)M1; q.C1 = C1; q.max_local = max_local; q.DR = (int)DR;
     Lo.bind(q.st, S * sizeof(LmmStream), base);
-    Lo.bind(q.kp_yx, n * 16, base); Lo.bind(q.kp_doff, n * 4, base); Lo.bind(q.kp_desc, n * 32, base); Lo.bind(q.kp_ooff, n * 4, base); Lo.bind(q.kp_okf, n * R * 4, base); Lo.bind(q.kp_oyx, n * R * 16, base);
+    Lo.bind(q.kp_yx, n * 16, base); Lo.bind(q.kp_doff, n * 4, base); Lo.bind(q.kp_desc, n * DR * 32, base); Lo.bind(q.kp_ooff, n * 4, base); Lo.bind(q.kp_okf, n * R * 4, base); Lo.bind(q.kp_oyx, n * R * 16, base);
     Lo.bind(q.kp_id, n * 8, base); Lo.bind(q.kf_Tcw, S * R * 128, base);
-    Lo.bind(q.mp_xyz, m * 24, base); Lo.bind(q.mp_doff, m * 4, base); Lo.bind(q.mp_desc, m * 32, base); Lo.bind(q.mp_ooff, m * 4, base); Lo.bind(q.mp_okf, m * R * 4, base); Lo.bind(q.mp_id, m * 8, base);
+    Lo.bind(q.mp_xyz, m * 24, base); Lo.bind(q.mp_doff, m * 4, base); Lo.bind(q.mp_desc, m * DR * 32, base); Lo.bind(q.mp_ooff, m * 4, base); Lo.bind(q.mp_okf, m * R * 4, base); Lo.bind(q.mp_id, m * 8, base);
     Lo.bind(q.cell_off, S * (size_t)C1 * 4, base); Lo.bind(q.cell_kp, n * 4, base); Lo.bind(q.cell_cur, S * (size_t)C1 * 4, base);
     Lo.bind(q.best_kp, m * 4, base); Lo.bind(q.best_dist, m * 8, base); Lo.bind(q.proj, m * 16, base); Lo.bind(q.keys, n * 8, base);
     Lo.bind(q.mark, S * (size_t)v.mcap * 4, base); Lo.bind(q.cnt, S * 8, base);
@@ -353,6 +392,72 @@ int slam_kfmap_enable_descriptors(slam_ctx *ctx, slam_kfmap *km, int n_bits)
     const int rc = kfmap_alloc_zeroed(ctx, "slam_kfmap_enable_descriptors", kfmap_desc_regions(km, nullptr), &km->dbase);
     if (rc) return rc;
     kfmap_desc_regions(km, km->dbase);
+    return SLAM_OK;
+}
+
+int slam_kfmap_enable_descriptor_rows(slam_ctx *ctx, slam_kfmap *km, int max_rows)
+{
+    ARG_TRY(ctx, ctx != nullptr && km != nullptr);
+    if (!km->dbase) return slam_fail(ctx, SLAM_ERR_ARG, "slam_kfmap_enable_descriptor_rows: descriptors are not enabled (slam_kfmap_enable_descriptors)");
+    if (max_rows < 2 || max_rows > KFM_MAX_ROWS) return slam_fail(ctx, SLAM_ERR_ARG, "slam_kfmap_enable_descriptor_rows: max_rows = %d (2 .. %d)", max_rows, KFM_MAX_ROWS);
+    if (km->rbase) {
+        if (km->v.D == max_rows) return SLAM_OK;
+        return slam_fail(ctx, SLAM_ERR_ARG, "slam_kfmap_enable_descriptor_rows: max_rows = %d, but the map keeps %d rows per point", max_rows, km->v.D);
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int rc = kfmap_alloc_zeroed(ctx, "slam_kfmap_enable_descriptor_rows", kfmap_rows_regions(km, max_rows, nullptr), &km->rbase);      // zeroed: no rows
+    if (rc) return rc;
+    kfmap_rows_regions(km, max_rows, km->rbase);
+    km->v.D = max_rows;
+    if (km->lm_base) {                                           // the staging was laid out for one row per record: the next match makes it anew
+        HIP_TRY(ctx, hipDeviceSynchronize());
+        (void)hipFree(km->lm_base); km->lm_base = nullptr; km->lm = KfmLm{};
+        memset(km->lm_np, 0, sizeof km->lm_np);
+    }
+    return SLAM_OK;
+}
+
+int slam_kfmap_download_descriptor_rows(slam_ctx *ctx, slam_kfmap *km, int s, int64_t *ids, uint8_t *described, int32_t *row_off, int32_t *keys, uint64_t *rows,
+                                        int cap_points, int cap_rows, int32_t *n_points, int32_t *dropped)
+{
+    ARG_TRY(ctx, ctx != nullptr && km != nullptr && s >= 0 && s < km->v.S && n_points != nullptr && cap_points >= 0 && cap_rows >= 0);
+    if (!km->rbase) return slam_fail(ctx, SLAM_ERR_ARG, "slam_kfmap_download_descriptor_rows: descriptor rows are not enabled (slam_kfmap_enable_descriptor_rows)");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const KfmapRows &V = km->v;
+    const size_t m = V.mcap, pb = (size_t)s * m, D = V.D;
+    std::vector<unsigned long long> tag(m);
+    std::vector<uint8_t> fl(m), has(m);
+    std::vector<int32_t> key(m * D);
+    std::vector<uint64_t> row(m * D * 4);
+    int32_t drop = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(tag.data(), V.ptag + pb, m * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(fl.data(), V.pflags + pb, m, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(has.data(), V.dhas + pb, m, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(key.data(), V.rkey + pb * D, m * D * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(row.data(), V.rrow + pb * D * 4, m * D * 32, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(&drop, V.rdrop + s, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, slam_stream_wait(ctx->stream));
+    std::vector<std::pair<int64_t, size_t>> live;                // the set slam_kfmap_download_points lists
+    size_t nrows = 0;
+    for (size_t e = 0; e < m; e++) if (tag[e] && !(fl[e] & KFM_DEAD)) { live.push_back({(int64_t)(tag[e] - 1), e}); nrows += kfm_rows_count(key.data() + e * D, (int)D); }
+    std::sort(live.begin(), live.end());
+    *n_points = (int32_t)live.size();
+    if (dropped) *dropped = drop;
+    if (live.size() > (size_t)cap_points || ((keys || rows) && nrows > (size_t)cap_rows))
+        return slam_fail(ctx, SLAM_ERR_CAPACITY, "slam_kfmap_download_descriptor_rows: %zu points with %zu rows, caps %d and %d", live.size(), nrows, cap_points, cap_rows);
+    int32_t at = 0;
+    for (size_t k = 0; k < live.size(); k++) {
+        const size_t e = live[k].second;
+        const int32_t *rk = key.data() + e * D;
+        if (ids) ids[k] = live[k].first;
+        if (described) described[k] = has[e];
+        if (row_off) row_off[k] = at;
+        for (int j = kfm_rows_next(rk, (int)D, 0); j >= 0; j = kfm_rows_next(rk, (int)D, rk[j]), at++) {
+            if (keys) keys[at] = rk[j] - 1;
+            if (rows) memcpy(rows + 4 * (size_t)at, row.data() + 4 * (e * D + j), 32);
+        }
+    }
+    if (row_off) row_off[live.size()] = at;
     return SLAM_OK;
 }
 
@@ -414,7 +519,7 @@ int slam_kfmap_add_descriptors(slam_ctx *ctx, slam_kfmap *km, const uint64_t *de
         sel = (const int *)scr;
     }
     { ProfScope span(ctx, "kfmap_add_descriptors");
-      hipLaunchKernelGGL(k_kfm_desc_record, dim3((dcap + 255) / 256, ns), dim3(256), 0, ctx->stream, km->v, desc_dev, info_dev, dcap, sel); }
+      KFM_LAUNCH_ROWS(km, k_kfm_desc_record, dim3((dcap + 255) / 256, ns), desc_dev, info_dev, dcap, sel); }
     HIP_TRY(ctx, hipGetLastError());
     return SLAM_OK;
 }
@@ -450,6 +555,8 @@ int slam_kfmap_local_map_match(slam_ctx *ctx, slam_kfmap *km, const double *cam,
     }
     if ((size_t)S * ((size_t)max_local + 1) * V.R >= ((size_t)1 << 31) || (size_t)S * ((size_t)V.cap + 1) * V.R >= ((size_t)1 << 31))
         return slam_fail(ctx, SLAM_ERR_ARG, "slam_kfmap_local_map_match: S (max_local + 1) R or S (cap + 1) R exceeds 2^31");
+    if (km->v.D && ((size_t)S * ((size_t)max_local + 1) * km->v.D >= ((size_t)1 << 31) || (size_t)S * ((size_t)V.cap + 1) * km->v.D >= ((size_t)1 << 31)))
+        return slam_fail(ctx, SLAM_ERR_ARG, "slam_kfmap_local_map_match: S (max_local + 1) D or S (cap + 1) D exceeds 2^31 descriptor rows");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     int list[128];
     const int ns = kfmap_streams(km, list);
@@ -479,8 +586,8 @@ int slam_kfmap_local_map_match(slam_ctx *ctx, slam_kfmap *km, const double *cam,
       HIP_TRY(ctx, hipMemcpyAsync(scr, h, in_b, hipMemcpyHostToDevice, ctx->stream));
       HIP_TRY(ctx, hipMemsetAsync(Q.keys, 0xFF, (size_t)S * Q.N1 * 8, ctx->stream));
       { ProfScope stage(ctx, "kfmap_lm_stage");
-        if (km->hs_base) hipLaunchKernelGGL(k_kfm_lm_stage_hist, dim3(ns), dim3(256), 0, ctx->stream, V, Q, km->hs, (const KfmLmArg *)o_arg.at(scr), sel);
-        else hipLaunchKernelGGL(k_kfm_lm_stage, dim3(ns), dim3(256), 0, ctx->stream, V, Q, (const KfmLmArg *)o_arg.at(scr), sel); }
+        if (km->hs_base) KFM_LAUNCH_ROWS(km, k_kfm_lm_stage_hist, dim3(ns), Q, km->hs, (const KfmLmArg *)o_arg.at(scr), sel);
+        else KFM_LAUNCH_ROWS(km, k_kfm_lm_stage, dim3(ns), Q, (const KfmLmArg *)o_arg.at(scr), sel); }
       lmm_launch(ctx, L, max_local, ns);
       hipLaunchKernelGGL(k_kfm_lm_pairs, dim3(ns), dim3(256), 0, ctx->stream, V, Q, sel);
       HIP_TRY(ctx, hipGetLastError());

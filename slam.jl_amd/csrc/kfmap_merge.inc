@@ -78,7 +78,9 @@ __device__ __forceinline__ int kfm_rename_dest(const int64_t *ids, int n, int k,
 // One 256-thread workgroup per stream with pairs.  The pairs of a call are one-to-one -- no prev id twice, no new id twice, no id on both sides of two
 // pairs -- so every pair reads and writes table entries of its own and no atomics are needed there; only the per-slab append counters are shared (LDS).
 // The slabs are read, not written: every look-up sees the map as the call found it.  gone: no live list follows (ks == NULL): prev is marked KFM_GONE.
-__global__ __launch_bounds__(256) void k_kfm_merge_resolve(KfmapView V, KfmMerge G, KfmPairs P, int gone, const int *sel)
+// ROWS (the row store is on): the pair's thread also forms the union of new's and prev's rows by key (kfm_rows_union: on an equal key new's row stays,
+// beyond D rows the largest keys stay and the excess is counted) -- the pair owns both entries -- and prev's keys go with the point.
+template <bool ROWS> __global__ __launch_bounds__(256) void k_kfm_merge_resolve(KfmView<ROWS> V, KfmMerge G, KfmPairs P, int gone, const int *sel)
 {
     __shared__ int s_cnt[KFM_MAX_R + 1], s_bad, s_stat[3];
     const int s = sel[blockIdx.x], tid = threadIdx.x, R = V.R, cap = V.cap, mcap = V.mcap;
@@ -120,6 +122,13 @@ __global__ __launch_bounds__(256) void k_kfm_merge_resolve(KfmapView V, KfmMerge
         if (obs) V.pflags[ne] |= KFM_OBS;
         const uint8_t fl = V.pflags[pe];
         V.pmask[pe] = 0; V.pflags[pe] = KFM_DEAD | (fl & KFM_GONE) | (gone ? KFM_GONE : 0);      // pop!(m.map_points, prev_id)
+        if constexpr (ROWS) {                                    // map_manager.jl:410-412; a point that takes its first row is described from then on
+            int32_t *pk = V.rkey + pe * V.D;
+            if (kfm_rows_count(pk, V.D)) V.dhas[ne] = 1;
+            const int dropped = kfm_rows_union(V.rkey + ne * V.D, V.rrow + 4 * ne * V.D, pk, V.rrow + 4 * pe * V.D, V.D);
+            if (dropped) atomicAdd(&V.rdrop[s], dropped);
+            kfm_rows_clear(pk, V.D);
+        }
         atomicAdd(&s_stat[0], 1); atomicAdd(&s_stat[2], nr);
     }
     __syncthreads();
@@ -271,7 +280,7 @@ int slam_kfmap_merge(slam_ctx *ctx, slam_kfmap *km, slam_kpset *ks, const int32_
     const int *sel = o_sel.at(scr);
     { ProfScope span(ctx, "kfmap_merge");
       { ProfScope part(ctx, "kfmap_merge_resolve");
-        hipLaunchKernelGGL(k_kfm_merge_resolve, dim3(ns), dim3(256), 0, ctx->stream, V, G, P, ks ? 0 : 1, sel); }
+        KFM_LAUNCH_ROWS(km, k_kfm_merge_resolve, dim3(ns), G, P, ks ? 0 : 1, sel); }
       { ProfScope part(ctx, "kfmap_merge_slabs");
         hipLaunchKernelGGL(k_kfm_merge_slabs, dim3(V.R, ns), dim3(256), 0, ctx->stream, V, G, sel); }
       if (ks) { ProfScope part(ctx, "kfmap_merge_list");

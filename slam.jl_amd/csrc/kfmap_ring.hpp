@@ -133,3 +133,63 @@ KFM_HD static inline bool kfm_sorted_one_to_one(const int64_t *prev, const int64
     for (int i = 1; i < nb; i++) if (both[i] == both[i - 1]) return false;
     return true;
 }
+
+// ---- the descriptor rows of a map point (slam_kfmap_enable_descriptor_rows): keyframes_descriptors (map_point.jl:15), one 256-bit row per key-frame id,
+// bounded: D slots per point, key[j] = key-frame id + 1 (0: an empty slot), row[4 j .. 4 j + 4) its row.  Slots may have holes; readers take the
+// non-empty slots ascending by key (kfm_rows_next).  tests/c_host/kfmap_rows_check.cpp holds these to tests/np_kfmap_rows.py.
+constexpr int KFM_MAX_ROWS = 8;
+// the slot that holds `key`, or -1
+KFM_HD static inline int kfm_rows_find(const int32_t *key, int D, int32_t k)
+{
+    for (int j = 0; j < D; j++) if (key[j] == k) return j;
+    return -1;
+}
+// remove_kf_observation!'s pop!(keyframes_descriptors, kfid): the slot of `k` is emptied; false where no slot holds it
+KFM_HD static inline bool kfm_rows_drop(int32_t *key, int D, int32_t k)
+{
+    const int j = k > 0 ? kfm_rows_find(key, D, k) : -1;
+    if (j >= 0) key[j] = 0;
+    return j >= 0;
+}
+// empty!(keyframes_descriptors)
+KFM_HD static inline void kfm_rows_clear(int32_t *key, int D) { for (int j = 0; j < D; j++) key[j] = 0; }
+// the number of rows
+KFM_HD static inline int kfm_rows_count(const int32_t *key, int D)
+{
+    int n = 0;
+    for (int j = 0; j < D; j++) n += key[j] != 0;
+    return n;
+}
+// the walk ascending by key: the slot of the smallest key above `after` (0 to start), or -1 (keys are unique within a point)
+KFM_HD static inline int kfm_rows_next(const int32_t *key, int D, int32_t after)
+{
+    int best = -1;
+    for (int j = 0; j < D; j++) if (key[j] > after && (best < 0 || key[j] < key[best])) best = j;
+    return best;
+}
+// add_descriptor! (map_point.jl:124-131) under the bound: a key the point already has is skipped; else the row takes an empty slot; with no slot left
+// the row of the SMALLEST key among the D + 1 goes (the arriving one, if that is it).  Returns the rows dropped by the bound: 0 or 1.
+KFM_HD static inline int kfm_rows_put(int32_t *key, uint64_t *row, int D, int32_t k, const uint64_t *r)
+{
+    int freej = -1, minj = 0;
+    for (int j = 0; j < D; j++) {
+        if (key[j] == k) return 0;
+        if (key[j] == 0) { if (freej < 0) freej = j; }
+        else if (key[minj] == 0 || key[j] < key[minj]) minj = j;
+    }
+    int j = freej;
+    if (j < 0) { if (k < key[minj]) return 1; j = minj; }
+    key[j] = k;
+    for (int w = 0; w < 4; w++) row[4 * j + w] = r[w];
+    return freej < 0;
+}
+// merge_mappoints' copy (map_manager.jl:410-412): every row of prev into the survivor, an equal key keeps the survivor's row; more than D keys: the D
+// LARGEST stay, whatever the order of the slots (evicting the smallest key one arrival at a time leaves the largest D).  Returns the rows dropped: the
+// size of the union of the keys less D -- counted on the keys, not on the evictions, whose number depends on the slots' order where a key is equal.
+KFM_HD static inline int kfm_rows_union(int32_t *key, uint64_t *row, const int32_t *pkey, const uint64_t *prow, int D)
+{
+    int n = kfm_rows_count(key, D);
+    for (int j = 0; j < D; j++) n += pkey[j] && kfm_rows_find(key, D, pkey[j]) < 0;
+    for (int j = 0; j < D; j++) if (pkey[j]) (void)kfm_rows_put(key, row, D, pkey[j], prow + 4 * j);
+    return n > D ? n - D : 0;
+}

@@ -462,6 +462,21 @@ function local_map_ids(m::KeyframeMap, s::Integer, kfid::Integer)
                 ctx(), m.h, s, kfid, ids, m.mcap, n))
     ids[1:n[]]
 end
+# Descriptor rows (slam_kfmap_enable_descriptor_rows): a point keeps one row per key-frame, at most max_rows (2 .. 8) of them -- keyframes_descriptors
+# (map_point.jl:15): a merge hands prev's rows to the surviving point, a removed observation takes its key-frame's row along, the match takes the minimum
+# over all pairs of rows.  After enable_descriptors!; another max_rows on a second call is an error.  descriptor_rows: the rows of stream s's points in id
+# order -- (ids, described, row_off (n + 1, 0-based), keys (key-frame ids, ascending per point), rows (4 x total), dropped).
+enable_descriptor_rows!(m::KeyframeMap, max_rows::Integer = 4) =
+    (check(ccall((:slam_kfmap_enable_descriptor_rows, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint), ctx(), m.h, max_rows)); m)
+function descriptor_rows(m::KeyframeMap, s::Integer; max_rows::Integer = 8)
+    cap = m.mcap; ids = zeros(Int64, cap); described = zeros(UInt8, cap); off = zeros(Int32, cap + 1)
+    keys = zeros(Int32, cap * max_rows); rows = zeros(UInt64, 4, cap * max_rows); n = Ref{Int32}(0); dropped = Ref{Int32}(0)
+    check(ccall((:slam_kfmap_download_descriptor_rows, LIB[]), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Int64}, Ptr{UInt8}, Ptr{Int32}, Ptr{Int32}, Ptr{UInt64}, Cint, Cint, Ref{Int32}, Ref{Int32}),
+                ctx(), m.h, s, ids, described, off, keys, rows, cap, cap * max_rows, n, dropped))
+    k = Int(n[]); r = Int(off[k + 1])
+    (ids = ids[1:k], described = described[1:k] .!= 0, row_off = off[1:k + 1], keys = keys[1:r], rows = rows[:, 1:r], dropped = Int(dropped[]))
+end
 # merge_matches (mapper.jl:296-310) on the map: the pairs of the last local_map_match where they lie in HBM (n_pairs === nothing), or the caller's
 # (n_pairs: S counts, pairs: 2 x n (prev id, new id), the streams back to back).  k: the KeypointSet whose live lists follow.  Returns the 4 x S counts
 # (pairs applied, pairs skipped, observations renamed, status), or nothing with want_counts = false (enqueue-only).

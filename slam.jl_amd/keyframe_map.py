@@ -242,6 +242,30 @@ class KeyframeMap:
         c.check(c.lib.slam_kfmap_merge(c.h, self.h, ks.h if ks is not None else None, n_ptr, p_ptr, L.ptr(merged, L.i32p) if want_counts else None))
         return merged
 
+    # ---- descriptor rows (slam_kfmap_enable_descriptor_rows / _download_descriptor_rows) ----
+    def enable_descriptor_rows(self, max_rows=4, ctx=None):
+        """A point keeps one descriptor row per key-frame, at most max_rows (2 .. 8) of them, the reference's keyframes_descriptors: a merge hands
+        prev's rows to the surviving point, a removed observation takes its key-frame's row along, and local_map_match takes the minimum distance
+        over all pairs of rows.  Beyond max_rows the rows of the largest key-frame ids stay.  After enable_descriptors(); opt-in; a second call with
+        the same max_rows is a no-op, another value a SlamHipError."""
+        c = ctx or self.ctx
+        c.check(c.lib.slam_kfmap_enable_descriptor_rows(c.h, self.h, int(max_rows)))
+        self.max_rows = int(max_rows)
+
+    def descriptor_rows(self, s, ctx=None):
+        """dict(ids (n,), described (n,) bool, keys: per point the (k,) int32 key-frame ids of its rows, ascending, rows: per point the (k, 4) uint64
+        rows in that order, dropped: the rows the bound has dropped on stream s) for the points download_points lists, in id order.  Synchronous."""
+        c = ctx or self.ctx
+        m, D = self.mcap, getattr(self, "max_rows", 1)
+        ids = np.zeros(m, dtype=np.int64); has = np.zeros(m, dtype=np.uint8); off = np.zeros(m + 1, dtype=np.int32)
+        keys = np.zeros(m * D, dtype=np.int32); rows = np.zeros((m * D, 4), dtype=np.uint64)
+        n = C.c_int32(0); dropped = C.c_int32(0)
+        c.check(c.lib.slam_kfmap_download_descriptor_rows(c.h, self.h, int(s), L.ptr(ids, L.i64p), L.ptr(has, L.u8p), L.ptr(off, L.i32p), L.ptr(keys, L.i32p),
+                                                          L.ptr(rows, L.u64p), m, m * D, C.byref(n), C.byref(dropped)))
+        k = n.value
+        return dict(ids=ids[:k].copy(), described=has[:k] != 0, keys=[keys[off[j]:off[j + 1]].copy() for j in range(k)],
+                    rows=[rows[off[j]:off[j + 1]].copy() for j in range(k)], dropped=int(dropped.value))
+
     def debug_local_map(self, s, ctx=None):
         """Test hook (slam_debug_kfmap_local_map, not part of the C header): what the last local_map_match staged for stream s ->
         dict(lm_ids (M,), proj_yx (M, 2), best_kp (M,), best_dist (M,), kp_ids (N,)); empty arrays unless the stream's status was 0."""
