@@ -11,6 +11,7 @@ lock-stepped stereo streams with every keypoint list resident in HBM -- the call
     --local-ba: after every key-frame step KeyframeMap.add_keyframe -> gather -> bundle_adjustment_batch_ -> update(ks)   (local_bundle_adjustment!)
     --map-filtering: after update(ks) KeyframeMap.filter drops the redundant key-frames of the ring                          (map_filtering!)
     --local-map-match: key-frames detect WITH describe; after add_keyframe KeyframeMap.add_descriptors -> local_map_match     (update_frame_covisibility! + match_local_map!)
+    --device-ba: with --local-ba the step is KeyframeMap.add_keyframe -> local_ba(ks): emit, solve and update on the windows where they lie in HBM
     --merge: after local_map_match KeyframeMap.merge(ks) applies the match's pairs to the map and the lists, before the gather  (merge_matches)
     --descriptor-rows D: KeyframeMap.enable_descriptor_rows(D); a point keeps one row per key-frame, the match takes the minimum over all pairs of rows  (keyframes_descriptors)
     --local-map-history: KeyframeMap.enable_local_map_history; the match keeps every key-frame's local map and takes in the oldest covisible one's  (frame.local_map_ids)
@@ -45,7 +46,7 @@ shared -- so --adaptive-keyframes alone takes a key-frame FOR ALL streams when A
 stream follow its own rule: the key-frame seams run under KeypointSet.selected(required), which restricts them to the streams that asked
 (slam_kpset_select), and the key-frame bookkeeping (last key-frame, its nb_3d_kpts, its pose, the observer ring, the key-frame id) is per stream.
 
-    python examples/device_frontend.py --frames 12 --streams 4 [--adaptive-keyframes | --per-stream-keyframes] [--local-ba [--map-filtering [--filter-from K]] [--local-map-match [--merge] [--local-map-history] [--descriptor-rows D]]]
+    python examples/device_frontend.py --frames 12 --streams 4 [--adaptive-keyframes | --per-stream-keyframes] [--local-ba [--device-ba] [--map-filtering [--filter-from K]] [--local-map-match [--merge] [--local-map-history] [--descriptor-rows D]]]
 """
 import argparse
 import contextlib
@@ -61,7 +62,7 @@ from slam_jl_amd import synthetic as syn  # noqa: E402
 
 
 def run(lefts, rights, cam, baseline, kf_every=4, max_keypoints=300, seed=0, ctx=None, verbose=False, adaptive=False, probe=None, per_stream=False, local_ba=False,
-        map_filtering=False, filter_from=20, map_probe=None, local_map_match=False, merge=False, local_map_history=False, descriptor_rows=0):
+        map_filtering=False, filter_from=20, map_probe=None, local_map_match=False, merge=False, local_map_history=False, descriptor_rows=0, device_ba=False):
     """lefts / rights: per stream a list of float images in [0, 1] (H, W).  Returns per frame a dict with the S poses
     (world -> camera, world = the first frame's camera), status words, list lengths and the wall time.
     adaptive: frame 0 is a key-frame; after the pose of every later frame the lists' statistics (KeypointSet.frame_stats, flags = 1) go
@@ -86,7 +87,11 @@ def run(lefts, rights, cam, baseline, kf_every=4, max_keypoints=300, seed=0, ctx
     descriptor_rows (needs local_map_match): D > 0: KeyframeMap.enable_descriptor_rows(D) -- a point keeps one descriptor row per key-frame (at most D).
     local_map_history (needs local_map_match): KeyframeMap.enable_local_map_history() -- the map keeps every key-frame's local map, the match applies the
     replace-or-union rule and takes in the oldest covisible key-frame's stored set (mapper.jl:274-286); max_local is then the table's size (sets grow along
-    that chain; status 2 cannot occur).  KeyframeMap.local_map_ids(s, kfid) reads a stored set back."""
+    that chain; status 2 cannot occur).  KeyframeMap.local_map_ids(s, kfid) reads a stored set back.
+    device_ba (needs local_ba): the estimator step is add_keyframe -> KeyframeMap.local_ba(ks): the windows are emitted, solved (slam_local_ba_batch_dev) and
+    applied where they lie in HBM; `ba` is built from the call's stats and KeyframeMap.last_windows(); map_probe's "solved" stage is not called."""
+    if device_ba and not local_ba:
+        raise ValueError("device_ba needs local_ba: it is the local BA's estimator step with the windows kept in HBM")
     if map_filtering and not local_ba:
         raise ValueError("map_filtering needs local_ba: the filter works on the local BA's key-frame map")
     if local_map_match and not local_ba:
@@ -199,16 +204,24 @@ def run(lefts, rights, cam, baseline, kf_every=4, max_keypoints=300, seed=0, ctx
                         if merge:                                           # merge_matches (mapper.jl:296-310): before the estimator reads the map
                             decision["merged"] = km.merge(ks, ctx=ctx)
                             notify(i, "merged", km, decision["merged"])
-                    wins, _ = km.gather(params.min_cov_score, ctx=ctx)
-                    if wins:
-                        slam.bundle_adjustment_batch_([w.cache for w in wins], cam, ctx=ctx)
-                        notify(i, "solved", wins)
-                        km.update(wins, ks=ks, ctx=ctx)
+                    if device_ba:                                           # the same step without the windows' trip through the host
+                        ba_status, ba_stats = km.local_ba(params.min_cov_score, cam, ks=ks, ctx=ctx)
+                        pmo = km.last_windows()
+                        wins = []
+                        decision["ba"] = [(s_, int(pmo[s_, 0]), int(pmo[s_, 1]), int(pmo[s_, 2]), int(ba_stats[s_, 5]), float(ba_stats[s_, 0]), float(ba_stats[s_, 2]))
+                                          for s_ in range(S) if ba_status[s_] == 0]
+                    else:
+                        wins, _ = km.gather(params.min_cov_score, ctx=ctx)
+                        if wins:
+                            slam.bundle_adjustment_batch_([w.cache for w in wins], cam, ctx=ctx)
+                            notify(i, "solved", wins)
+                            km.update(wins, ks=ks, ctx=ctx)
                     if params.map_filtering:                                # map_filtering! (estimator.jl:358-406), the estimator's next step
                         decision["removed"] = km.filter(params.filtering_ratio, params.min_cov_score, first_kfid=filter_from, ctx=ctx)
                         notify(i, "filtered", km, decision["removed"])
-                    decision["ba"] = [(w.stream, w.cache.n_poses, w.cache.n_points, len(w.cache.poses_ids), int(w.cache.outliers.sum()),
-                                       w.cache.stats["ssr_init"], w.cache.stats["ssr_final"]) for w in wins]
+                    if not device_ba:
+                        decision["ba"] = [(w.stream, w.cache.n_poses, w.cache.n_points, len(w.cache.poses_ids), int(w.cache.outliers.sum()),
+                                           w.cache.stats["ssr_init"], w.cache.stats["ssr_final"]) for w in wins]
             if adaptive:                                                    # the key-frame's own nb_3d_kpts, after the mapper's triangulations
                 last_kf[kf_mask] = i
                 nb_3d = ks.frame_stats(slam.stream_params(S, cam=cam), 0, ex.cell_size, (H, W), ctx=ctx)[:, 1].astype(np.int32)
@@ -254,6 +267,7 @@ def main():
     ap.add_argument("--adaptive-keyframes", action="store_true", help="take key-frames where check_new_kf_required asks for one (any stream), not every 4th frame")
     ap.add_argument("--per-stream-keyframes", action="store_true", help="every stream takes its key-frames where check_new_kf_required asks for one for THAT stream (implies --adaptive-keyframes)")
     ap.add_argument("--local-ba", action="store_true", help="run the estimator's local BA after every key-frame step, on a key-frame map in HBM; the lists take the refined landmarks")
+    ap.add_argument("--device-ba", action="store_true", help="with --local-ba: the estimator step in one call with the windows kept in HBM (KeyframeMap.local_ba), not gather -> solve -> update through the host")
     ap.add_argument("--map-filtering", action="store_true", help="after every local BA drop the redundant key-frames of the map (map_filtering!); requires --local-ba")
     ap.add_argument("--local-map-match", action="store_true", help="describe the key-frames' new keypoints and match each stream's local map against them on the key-frame map (match_local_map!); requires --local-ba")
     ap.add_argument("--merge", action="store_true", help="apply the local-map match's pairs to the map and the lists (merge_matches); requires --local-map-match")
@@ -262,6 +276,8 @@ def main():
     ap.add_argument("--filter-from", type=int, default=20, help="first key-frame id at which the filter acts (the reference's literal 20)")
     ap.add_argument("--replay-dir", default=None, help="write stream s's camera positions to DIR/stream_s as a ReplaySaver dump (src/io/saver.jl)")
     args = ap.parse_args()
+    if args.device_ba and not args.local_ba:
+        ap.error("--device-ba requires --local-ba")
     if args.map_filtering and not args.local_ba:
         ap.error("--map-filtering requires --local-ba")
     if args.local_map_match and not args.local_ba:
@@ -276,7 +292,7 @@ def main():
     lefts, rights, offs = synthetic_scene(args.streams, args.frames, disparity=disparity)
     out, n3 = run(lefts, rights, cam, baseline, verbose=True, adaptive=args.adaptive_keyframes, per_stream=args.per_stream_keyframes, local_ba=args.local_ba,
                   map_filtering=args.map_filtering, filter_from=args.filter_from, local_map_match=args.local_map_match, merge=args.merge,
-                  local_map_history=args.local_map_history, descriptor_rows=args.descriptor_rows)
+                  local_map_history=args.local_map_history, descriptor_rows=args.descriptor_rows, device_ba=args.device_ba)
     Z = cam[0] * baseline / disparity
     for s in range(args.streams):
         o = offs[s][-1] - offs[s][0]

@@ -47,7 +47,10 @@ enum slam_status {
     SLAM_ERR_HIP = -2,          /* HIP runtime error (message has hipGetErrorString) */
     SLAM_ERR_LAYERS = -3,       /* "Not enough layers in pyramids." lucas_kanade.jl:15 */
     SLAM_ERR_CAPACITY = -4,     /* output buffer too small */
-    SLAM_ERR_NUMERIC = -5       /* reduced camera system not positive definite */
+    SLAM_ERR_NUMERIC = -5,      /* reduced camera system not positive definite */
+    /* per-window code of slam_local_ba_batch_dev, not an error of the call: the window is none the one-workgroup kernel takes; its arrays are
+     * untouched (solve it through slam_local_ba_batch) */
+    SLAM_BA_DEV_INELIGIBLE = 4
 };
 
 /* ---- context --------------------------------------------------------------- */
@@ -478,6 +481,19 @@ int slam_kfmap_ba_gather(slam_ctx *ctx, slam_kfmap *km, const int32_t *min_cov_s
  * pending window is an argument error and nothing is enqueued for any stream; a window is consumed by its update.  Enqueue-only. */
 int slam_kfmap_ba_update(slam_ctx *ctx, slam_kfmap *km, slam_kpset *ks /* nullable */, int n_windows, const int32_t *win_stream,
                          const double *theta, const uint8_t *outliers);
+/* The estimator step on the map in ONE call, the windows never leaving HBM: for the streams the last slam_kfmap_add_keyframe acted on, what
+ * slam_kfmap_ba_gather -> slam_local_ba_batch -> slam_kfmap_ba_update(ks) do -- the gather's plan kernel and its headers back (the first wait), the
+ * gather's emit kernel into a device block of the map's own (no copy to the host), slam_local_ba_batch_dev on those arrays (camera cams[4 s ..] for
+ * stream s), and the update's kernels (with ks: its list kernel and the compaction) on the same arrays.  Windows that batch does not take
+ * (SLAM_BA_DEV_INELIGIBLE: e.g. one free pose among several, more than five free poses) take the host route INSIDE the call: their arrays come down,
+ * slam_local_ba_batch solves them, theta and the flags go back up, and the one update launch applies them with the others.  status (S): 0 solved and
+ * applied, 1 no window (the gather's rule), 3 not selected, SLAM_ERR_NUMERIC (the map is untouched for that stream, as when a host caller skips the
+ * update; its window stays pending), SLAM_ERR_ARG.  stats (S x 8, nullable): slam_local_ba_batch's rows, zeros where nothing was solved.  A stream
+ * that goes through has no pending window afterwards.  Synchronous up to the update, which is enqueued. */
+int slam_kfmap_local_ba(slam_ctx *ctx, slam_kfmap *km, slam_kpset *ks /* nullable */, const int32_t *min_cov_score /* S */, const double *cams /* S x 4 */,
+                        int iters_fast, int iterations, double repr_eps, int32_t *status /* S */, double *stats /* S x 8, nullable */);
+/* P, M, O of the window every stream had in the last slam_kfmap_local_ba (S x 3 ints; zeros: none).  Host bookkeeping, no device work. */
+int slam_kfmap_last_windows(slam_kfmap *km, int32_t *pmo);
 /* map_filtering! (estimator.jl:358-406) for the streams the last slam_kfmap_add_keyframe acted on: key-frames that share too many well-observed
  * points with the rest of the ring are removed.  Per stream s, with cur = its newest key-frame:
  *   gates        nothing happens when filtering_ratio[s] >= 1 or cur < first_kfid (the reference's literal is 20; a parameter here);
@@ -819,7 +835,28 @@ int slam_local_ba_batch(slam_ctx *ctx, int S, const double *cams, const int32_t 
                         const int64_t *pose_ids, const int64_t *point_ids, uint8_t *outliers,
                         int iters_fast, int iterations, double repr_eps, double *stats, int32_t *status);
 
-/* The same call in two halves (round 6): _begin hands everything -- structure analysis, staging, upload, solve, download, scatter into the
+/* slam_local_ba_batch on windows that are RESIDENT IN HBM: the arguments are slam_local_ba_batch's, except that theta (in / out), theta_const,
+ * pixels_yx, pose_ids, point_ids and outliers (out) are DEVICE pointers, the windows back to back exactly as the host form takes them; cams, Pn, Mn,
+ * On, stats and status stay host arrays.  Nothing of a window crosses the bus: a probe kernel reports a few ints per window (free poses, the largest
+ * per-point observation count, the observations of free poses, the two checks below), a stager kernel writes each window's solver arrays in place in
+ * the batch arena, the solve is slam_local_ba_batch's one-workgroup kernel (two workgroups per window where the device has room, with the same bounded
+ * wait and the same second attempt on one workgroup -- which stages the windows again, the solver having moved the parameters it was given), and a
+ * results kernel writes theta (the caller's pose order) and the outlier flags back; only the LM states come back to the host, for stats and status.
+ * Contract: a window's observations are grouped by map point in ascending point id (what slam_kfmap_ba_gather's emit kernel writes); a window that
+ * breaks the rule, names an id out of range or has a map point observed twice by one free pose gets SLAM_ERR_ARG in status, found on the device.
+ * Scope: the windows the one-workgroup kernel takes under the rule slam_local_ba_batch applies -- 2 .. 5 free poses once the poses are relabelled so
+ * that the free ones are consecutive (constant poses first, then the free ones, each in the caller's order; one free pose among several is not such a
+ * window, nor is a window of one pose), <= 128 poses, 1 .. 40000 observations, <= 168 observations of one point.  Any other window gets
+ * SLAM_BA_DEV_INELIGIBLE.  A window with a code other than 0 keeps its arrays bit for bit (SLAM_ERR_NUMERIC included) and the rest of the batch is
+ * solved.  Results equal slam_local_ba_batch's on the same arrays to rounding (theta <= 1e-6 relative, costs 1e-8: the map points are summed in the
+ * caller's order here, in the planner's there).  With status the call returns SLAM_OK unless the batch itself failed; without it the first window
+ * code is an error of the call.  The device arrays are read and written on the context's stream; the call returns after the results kernel has run. */
+int slam_local_ba_batch_dev(slam_ctx *ctx, int S, const double *cams, const int32_t *Pn, const int32_t *Mn, const int32_t *On,
+                            double *theta, const uint8_t *theta_const, const double *pixels_yx,
+                            const int64_t *pose_ids, const int64_t *point_ids, uint8_t *outliers,
+                            int iters_fast, int iterations, double repr_eps, double *stats, int32_t *status);
+
+/* slam_local_ba_batch (the host-array form) in two halves (round 6): _begin hands everything -- structure analysis, staging, upload, solve, download, scatter into the
  * caller's arrays -- to a thread of the library's own and returns at once; _end waits for it and returns the call's code (message:
  * slam_last_error).  The estimator task (src/estimator.jl:78-99) prepares the next key-frame's windows while this one's are planned and
  * solved, without a host thread of its own.  Between the two calls the context belongs to the job -- no other call on it; one job per

@@ -104,6 +104,8 @@ SIGNATURES = {
     "slam_kfmap_add_keyframe": (cint, [vp, vp, vp, f64p]),
     "slam_kfmap_ba_gather": (cint, [vp, vp, i32p, vp, i32p]),
     "slam_kfmap_ba_update": (cint, [vp, vp, vp, cint, i32p, f64p, u8p]),
+    "slam_kfmap_local_ba": (cint, [vp, vp, vp, i32p, f64p, cint, cint, dbl, i32p, f64p]),
+    "slam_kfmap_last_windows": (cint, [vp, i32p]),
     "slam_kfmap_filter": (cint, [vp, vp, f64p, i32p, cint, u64p]),
     "slam_kfmap_remove_keyframe": (cint, [vp, vp, cint, cint]),
     "slam_kfmap_newest": (cint, [vp, vp, i32p]),
@@ -121,6 +123,7 @@ SIGNATURES = {
     "slam_kpset_compute_pose": (cint, [vp, vp, f64p, dbl, cint, C.c_uint64, cint, cint, dbl, dbl, f64p, i32p, i32p, i32p]),
     "slam_local_ba": (cint, [vp, dbl, dbl, dbl, dbl, cint, cint, cint, f64p, u8p, f64p, i64p, i64p, u8p, cint, cint, dbl, f64p]),
     "slam_local_ba_batch": (cint, [vp, cint, f64p, i32p, i32p, i32p, f64p, u8p, f64p, i64p, i64p, u8p, cint, cint, dbl, f64p, i32p]),
+    "slam_local_ba_batch_dev": (cint, [vp, cint, f64p, i32p, i32p, i32p, vp, vp, vp, vp, vp, vp, cint, cint, dbl, f64p, i32p]),
     "slam_local_ba_batch_begin": (cint, [vp, cint, f64p, i32p, i32p, i32p, f64p, u8p, f64p, i64p, i64p, u8p, cint, cint, dbl, f64p, i32p]),
     "slam_local_ba_batch_end": (cint, [vp]),
     "slam_pnp_ba": (cint, [vp, dbl, dbl, dbl, dbl, f64p, f64p, f64p, cint, cint, cint, dbl, dbl, f64p, f64p, f64p, u8p, C.POINTER(cint)]),

@@ -122,6 +122,30 @@ def bundle_adjustment_batch_(caches, cameras, iterations=10, repr_eps=5.0, iters
     return status.copy()
 
 
+SLAM_BA_DEV_INELIGIBLE = 4      # include/slamhip.h: per-window code of slam_local_ba_batch_dev
+
+
+def bundle_adjustment_batch_dev_(cameras, Pn, Mn, On, theta, theta_const, pixels, poses_ids, points_ids, outliers,
+                                 iterations=10, repr_eps=5.0, iters_fast=5, ctx=None):
+    """`slam_local_ba_batch_dev`: S windows that are RESIDENT IN HBM, solved in place.  theta (float64, in / out), theta_const (uint8), pixels (float64,
+    (y, x) pairs), poses_ids / points_ids (int64, 1-based) and outliers (uint8, out) are device pointers (ints, e.g. `tensor.data_ptr()`) to the windows'
+    arrays stored back to back as `BABatch` packs them, every window's observations grouped by ascending point id; cameras ((fx, fy, cx, cy) or S of
+    them), Pn, Mn, On are host values.  The arrays are read and written on the context's stream -- whoever wrote them on another stream has finished.
+    -> (status, stats): per window 0, SLAM_ERR_NUMERIC / SLAM_ERR_ARG (arrays untouched) or SLAM_BA_DEV_INELIGIBLE (not a window of <= 5 free poses the
+    one-workgroup kernel takes: untouched, `bundle_adjustment_batch_` solves it); stats (S, 8) as `slam_local_ba_batch`'s."""
+    ctx = ctx or L.default_context()
+    Pn = np.ascontiguousarray(Pn, dtype=np.int32); Mn = np.ascontiguousarray(Mn, dtype=np.int32); On = np.ascontiguousarray(On, dtype=np.int32)
+    S = len(Pn)
+    one = hasattr(cameras, "intrinsics") or np.ndim(cameras) == 1
+    cams = np.asarray([(c.intrinsics if hasattr(c, "intrinsics") else c) for c in ([cameras] * S if one else cameras)], dtype=np.float64).reshape(S, 4)
+    stats = np.zeros((S, 8)); status = np.zeros(S, dtype=np.int32)
+    dp = lambda p: C.c_void_p(int(p)) if p else None
+    ctx.check(ctx.lib.slam_local_ba_batch_dev(ctx.h, S, L.ptr(cams), L.ptr(Pn, L.i32p), L.ptr(Mn, L.i32p), L.ptr(On, L.i32p), dp(theta), dp(theta_const),
+                                              dp(pixels), dp(poses_ids), dp(points_ids), dp(outliers), int(iters_fast), int(iterations), float(repr_eps),
+                                              L.ptr(stats), L.ptr(status, L.i32p)))
+    return status, stats
+
+
 def ba_plan_order(cache):
     """-> (order, half_bandwidth, reordered): the pose order bundle_adjustment_ solves `cache` in (order[k] = the cache's 0-based pose
     at the solver's position k) and the block half-bandwidth of the reduced camera system in it -- `slam_ba_plan_order`, host work only.

@@ -1,4 +1,4 @@
-// ba_batch.hip -- bundle_adjustment! for S windows in one set of launches (slam_local_ba_batch, _begin / _end): the window-indexed wrappers of the
+// ba_batch.hip -- bundle_adjustment! for S windows in one set of launches (slam_local_ba_batch, _begin / _end; _dev: the windows resident in HBM, with its probe / stager / results kernels): the window-indexed wrappers of the
 // bodies of ba_device.hpp (table of BAWin read through the constant address space: ba_win), among them the matrix-core Schur build, and the host half of the call
 // (worker pool, arena layout, retry of k_ba_window on one workgroup).  reference: src/estimator.jl:78-99, :317-347; src/bundle_adjustment.jl:1-111.
 #include "ba_device.hpp"
@@ -120,6 +120,167 @@ __global__ __launch_bounds__(256) void k_results_b(const BAWin *tab, const BARes
         lm_record_pass(&h, 2);
         *(LMState *)(res + r.off_state) = h;
     }
+}
+
+// ---- slam_local_ba_batch_dev: the windows are arrays in HBM (slam_local_ba_batch's layout, observations grouped by point in ascending point id); three
+// small kernels take the place of the host's structure analysis, staging and result scatter for the windows k_ba_window solves.  One 256-thread
+// workgroup per window each; the decisions they share with the host form are ba_dev_plan.hpp's.
+struct BADevArgs { double *theta; const uint8_t *tc; const double *px; const int64_t *pi, *li; uint8_t *outl; };   // the caller's device arrays
+struct BADevIn { long long th_off, pc_off, ob_off; int P, M, O, pad; };      // where a window's arrays start in them
+struct BADevProbe { int nfree, cmax, nfree_obs, flags; };                    // flags: BAD_UNGROUPED | BAD_TWICE
+#define BAD_UNGROUPED 1      // an id out of range, or the point ids do not ascend
+#define BAD_TWICE 2          // a map point observed twice by one free pose
+// first index of the ascending ids[0 .. n) whose id is not below `id`
+__device__ __forceinline__ int bad_lower(const int64_t *ids, int n, int64_t id)
+{
+    int lo = 0, hi = n;
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (ids[mid] < id) lo = mid + 1; else hi = mid; }
+    return lo;
+}
+// exclusive scan of v over the 256 threads of the workgroup (every thread calls it); *total = the workgroup's sum.  s_w: 4 ints of LDS
+__device__ __forceinline__ int bad_scan256(int v, int *s_w, int *total)
+{
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    int inc = v;
+#pragma unroll
+    for (int dd = 1; dd < 64; dd <<= 1) { const int o = __shfl_up(inc, dd); if (lane >= dd) inc += o; }
+    __syncthreads();                                         // (the sums of the round before are read)
+    if (lane == 63) s_w[wv] = inc;
+    __syncthreads();
+    int base = 0;
+    for (int q = 0; q < wv; q++) base += s_w[q];
+    *total = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+    return base + inc - v;
+}
+// Probe: what the host needs to decide a window's route and lay out its arena -- free poses, the largest per-point observation count, the observations of
+// free poses -- and the two checks of the contract.  A window whose sizes alone rule k_ba_window out is not looked at (nfree = -1).
+__global__ __launch_bounds__(256) void k_ba_dev_probe(const BADevIn *din, BADevArgs a, BADevProbe *out)
+{
+    __shared__ uint8_t s_tc[BAP_PMAX];
+    __shared__ int s_nfree, s_cmax, s_nfo, s_flags, s_twice;      // (s_twice: a word of its own -- s_flags is read for a uniform branch while later waves may already be past it)
+    const BADevIn w = din[blockIdx.x];
+    const int tid = threadIdx.x, P = w.P, M = w.M, O = w.O;
+    if (P > BAP_PMAX || O > BAP_OMAX || O <= 0 || M <= 0) { if (tid == 0) out[blockIdx.x] = BADevProbe{-1, 0, 0, 0}; return; }      // (uniform)
+    if (tid == 0) { s_nfree = 0; s_cmax = 0; s_nfo = 0; s_flags = 0; s_twice = 0; }
+    if (tid < P) s_tc[tid] = a.tc[w.pc_off + tid];
+    __syncthreads();
+    if (tid < P && !s_tc[tid]) atomicAdd(&s_nfree, 1);
+    const int64_t *pi = a.pi + w.ob_off, *li = a.li + w.ob_off;
+    int nfo = 0, bad = 0;
+    for (int i = tid; i < O; i += 256) {
+        const int64_t p = pi[i], j = li[i];
+        if (p < 1 || p > P || j < 1 || j > M || (i > 0 && li[i - 1] > j)) bad = 1;
+        else if (!s_tc[p - 1]) nfo++;
+    }
+    if (bad) atomicOr(&s_flags, BAD_UNGROUPED);
+    if (nfo) atomicAdd(&s_nfo, nfo);
+    __syncthreads();
+    if (s_flags) { if (tid == 0) out[blockIdx.x] = BADevProbe{s_nfree, 0, 0, s_flags}; return; }      // (uniform; below, every id is in range and the ids ascend)
+    int cmax = 0, twice = 0;
+    for (int j = tid; j < M; j += 256) {
+        const int s = bad_lower(li, O, j + 1), e = bad_lower(li, O, j + 2);
+        cmax = max(cmax, e - s);
+        unsigned long long seen[2] = {0, 0};                 // the free poses that observe point j (P <= 128)
+        for (int o = s; o < e; o++) {
+            const int p = (int)pi[o] - 1;
+            if (s_tc[p]) continue;
+            const unsigned long long bit = 1ull << (p & 63);
+            if (seen[p >> 6] & bit) twice = 1;
+            seen[p >> 6] |= bit;
+        }
+    }
+    atomicMax(&s_cmax, cmax);
+    if (twice) atomicOr(&s_twice, BAD_TWICE);
+    __syncthreads();
+    if (tid == 0) out[blockIdx.x] = BADevProbe{s_nfree, s_cmax, s_nfo, s_twice};
+}
+// Stager: a window's uploaded region, written in place in exactly the layout ba_stage writes for a `window` plan -- with the caller's point order kept
+// (rank[j] = j, pt_id[k] = k; k_ba_window depends on no particular point order) and the poses relabelled by ba_label_free_last: the constant poses first,
+// then the free ones, each in the caller's order.  The pointers are those of the window's table entry (ba_bind); the cost split goes into that entry.
+__global__ __launch_bounds__(256) void k_ba_dev_stage(BAWin *tab, const BADevIn *din, BADevArgs a)
+{
+    __shared__ uint8_t s_tc[BAP_PMAX];
+    __shared__ int s_lab[BAP_PMAX], s_w[4];
+    const BADevIn w = din[blockIdx.x];
+    const BADev d = tab[blockIdx.x].d;
+    const int tid = threadIdx.x, P = w.P, M = w.M, O = w.O;
+    double *pose = d.pose, *pts = d.pts, *pix = (double *)d.pix;
+    uint8_t *pconst = (uint8_t *)d.pconst;
+    int *opose = (int *)d.opose, *opoint = (int *)d.opoint, *opk = (int *)d.opk, *pt_start = (int *)d.pt_start, *pt_id = (int *)d.pt_id;
+    int *pfs = (int *)d.pfs, *fobs = (int *)d.fobs, *fgrp = (int *)d.fgrp, *blk_start = (int *)d.blk_start;
+    const double *th = a.theta + w.th_off, *px = a.px + 2 * w.ob_off;
+    const int64_t *pi = a.pi + w.ob_off, *li = a.li + w.ob_off;
+    if (tid < P) s_tc[tid] = a.tc[w.pc_off + tid];
+    __syncthreads();
+    if (tid < P) {
+        const int lab = ba_label_free_last(s_tc, P, tid);
+        s_lab[tid] = lab; pconst[lab] = s_tc[tid];
+        for (int c = 0; c < 6; c++) pose[6 * lab + c] = th[6 * tid + c];
+    }
+    for (int t = tid; t <= P; t += 256) fgrp[t] = 0;
+    for (int i = tid; i < 3 * M; i += 256) pts[i] = th[6 * P + i];
+    for (int j = tid; j < M; j += 256) pt_id[j] = j;
+    __syncthreads();
+    for (int i = tid; i < O; i += 256) {
+        const int j = (int)li[i] - 1;
+        opose[i] = s_lab[pi[i] - 1]; opoint[i] = j; opk[i] = j;
+        pix[i] = px[2 * (size_t)i]; pix[(size_t)O + i] = px[2 * (size_t)i + 1];
+    }
+    // the points in chunks of 256: a point's first observation (the ids ascend: a search), the running count of free-pose observations (a scan with carry)
+    int carry = 0;
+    for (int c0 = 0; c0 < M; c0 += 256) {
+        const int j = c0 + tid;
+        int s = 0, e = 0, nf = 0;
+        if (j < M) {
+            s = bad_lower(li, O, j + 1); e = bad_lower(li, O, j + 2);
+            for (int o = s; o < e; o++) nf += s_tc[pi[o] - 1] ? 0 : 1;
+        }
+        int total;
+        const int first = carry + bad_scan256(nf, s_w, &total);
+        if (j < M) {
+            pt_start[j] = s; pfs[j] = first;
+            int r = first;
+            for (int o = s; o < e; o++) if (!s_tc[pi[o] - 1]) fobs[r++] = o;
+        }
+        carry += total;
+    }
+    if (tid == 0) { pt_start[M] = O; pfs[M] = carry; blk_start[0] = 0; }
+    // the cost split: the points before it are those for which ba_ksplit_before holds (each thread reads back what it wrote itself)
+    int before = 0;
+    const long long cost = ba_ksplit_total(O, carry);
+    if (M > 1) for (int j = tid; j < M; j += 256) before += ba_ksplit_before(cost, pt_start[j], pfs[j]) ? 1 : 0;
+    int kk;
+    (void)bad_scan256(before, s_w, &kk);
+    if (tid == 0) tab[blockIdx.x].ksplit = M > 1 ? ba_ksplit_clamp(kk, M) : ba_ksplit_obs(M, O, [&](int k) { return k == 0 ? 0 : O; });
+}
+// Results, behind k_results_b: a window's committed parameters from the solver's pose order to the caller's, its outlier flags (sorted observation order IS
+// the caller's), into the caller's arrays -- where the factorisation held (chol_fail == 0), else the arrays stay as they are.  While the windows run on two
+// workgroups each, one whose halves missed each other (chol_fail == 2) means the whole call is solved again FROM THE CALLER'S ARRAYS: nothing is written.
+__global__ __launch_bounds__(256) void k_ba_dev_results(const BAWin *tab, const BARes *rtab, const char *res, const BADevIn *din, int nb, int two, BADevArgs a)
+{
+    __shared__ uint8_t s_tc[BAP_PMAX];
+    __shared__ int s_missed;
+    const int tid = threadIdx.x;
+    if (tid == 0) s_missed = 0;
+    __syncthreads();
+    if (two) for (int q = tid; q < nb; q += 256) if (((const LMState *)(res + rtab[q].off_state))->chol_fail == 2) s_missed = 1;
+    __syncthreads();
+    if (s_missed) return;
+    const BARes r = rtab[blockIdx.x];
+    if (((const LMState *)(res + r.off_state))->chol_fail) return;
+    const BADevIn w = din[blockIdx.x];
+    const int P = w.P, M = w.M, O = w.O;
+    if (tid < P) s_tc[tid] = a.tc[w.pc_off + tid];
+    __syncthreads();
+    const double *src = (const double *)(res + r.off_theta);
+    double *th = a.theta + w.th_off;
+    if (tid < P) {
+        const int lab = ba_label_free_last(s_tc, P, tid);
+        for (int c = 0; c < 6; c++) th[6 * tid + c] = src[6 * lab + c];
+    }
+    for (int i = tid; i < 3 * M; i += 256) th[6 * P + i] = src[6 * P + i];
+    const uint8_t *ol = (const uint8_t *)(res + r.off_outl);
+    for (int i = tid; i < O; i += 256) a.outl[w.ob_off + i] = ol[i];
 }
 
 
@@ -247,6 +408,17 @@ int batch_arena(BatchCall &c)
     c.res_host = c.stage + c.up_total; c.tab_h = (BAWin *)c.stage; c.rtab_h = (BARes *)(c.stage + c.tab_bytes);
     return SLAM_OK;
 }
+// window k's entry of the window table, once its pointers are bound (ba_bind); ksplit: the plan's, by observation counts
+void win_table(BatchCall &c, int k, char *zero)
+{
+    BAPlan &q = c.plan(k);
+    BAWin &w = c.tab_h[k];
+    slam_ba *b = q.ba; b->device = c.ctx->device; b->owns_arena = false; b->arena = c.A;
+    w.d = b->d;
+    w.B = band_args(b, c.route[c.batch[k]], b->reduce, 0.0); w.B.epoch = 1;
+    w.nb_obs = b->nblocks_obs; w.nb_pts = b->nblocks_pts; w.n_red = (w.d.P * (w.d.whb + 1) * 36 + w.d.P * 12 + 255) / 256;
+    w.ksplit = q.ksplit; w.bwx = q.window ? (double *)(zero + q.o_bwx) : nullptr;
+}
 // stage window k of the batch: its uploaded region, its table entries
 void emit_window(BatchCall &c, int k)
 {
@@ -259,19 +431,12 @@ void emit_window(BatchCall &c, int k)
     // Kept exactly as found: a window whose set-up fails in ba_emit (q.err: a point observed twice by one pose) stays in the table with pad = 2 -- every batch kernel,
     // k_results_b included, returns at once for it, it is in no list of k_ba_window's and its (zeroed) table entry is never read for a launch size
     if (ba_emit(q, c.A + c.up[k], zero, c.A + c.work_base + c.wk[k], c.stage + c.up[k])) { w.pad = 2; return; }
-    slam_ba *b = q.ba; b->device = c.ctx->device; b->owns_arena = false; b->arena = c.A;
-    w.d = b->d;
-    w.B = band_args(b, c.route[c.batch[k]], b->reduce, 0.0); w.B.epoch = 1;
-    w.nb_obs = b->nblocks_obs; w.nb_pts = b->nblocks_pts; w.n_red = (w.d.P * (w.d.whb + 1) * 36 + w.d.P * 12 + 255) / 256;
-    w.ksplit = q.ksplit; w.bwx = q.window ? (double *)(zero + q.o_bwx) : nullptr;
+    win_table(c, k, zero);
     if (q.window && q.M > 1) {
         // the split point of k_ba_window's two workgroups: an observation costs the evaluation phases ~24 cycles, an observation of a FREE
-        // pose ~6.5 times that in the Schur phase (phase clocks, BW_TRACE) -- and those sit at one end of the sorted points: split by cost
+        // pose ~6.5 times that in the Schur phase (phase clocks, BW_TRACE) -- and those sit at one end of the sorted points: split by cost (ba_dev_plan.hpp)
         const int *pfs = (const int *)(c.stage + c.up[k] + q.o_pfs);
-        const long total = 2L * q.O + 13L * pfs[q.M];
-        int kk = 0;
-        while (kk < q.M && 2 * (2L * q.start[kk] + 13L * pfs[kk]) < total) kk++;
-        w.ksplit = std::min(std::max(kk, 1), q.M - 1);
+        w.ksplit = ba_ksplit_cost(q.M, q.O, [&](int kk) { return q.start[kk]; }, [&](int kk) { return pfs[kk]; });
     }
 }
 // a large upload travels in parts: the staged bytes of the first windows go out while the pool stages the next ones (128 x P20: 203 MB = 4 ms of PCIe
@@ -361,6 +526,16 @@ void both_passes(const BatchRoute &r, hipStream_t q, const BAWin *tb, int nb, in
     hipLaunchKernelGGL(k_outlier_count_b, dim3(1, nb), dim3(256), 0, q, tb);
     run_pass(r, q, tb, nb, 1, iterations);
 }
+// k_ba_window over the route's list of windows, on one or two workgroups each (both forms of the batch launch it here); its LDS limit once per device
+int window_attr(BatchCall &c, const BatchRoute &r)
+{
+    static std::atomic<bool> bw_attr[64];
+    return r.NS > 0 ? LDS_ATTR_ONCE(c.ctx, bw_attr, k_ba_window, bw_lds_bytes(BW_PMAX)) : SLAM_OK;
+}
+void launch_window(BatchCall &c, const BatchRoute &r, int iters_fast, int iterations, double repr_eps)
+{
+    if (r.NS > 0) hipLaunchKernelGGL(k_ba_window, dim3(r.two ? r.two_grid : r.NS), dim3(BW_T), r.lds_bw, c.ctx->stream, (const BAWin *)c.A, (const int *)(c.A + c.list_off()), r.NS, r.two, iters_fast, iterations, repr_eps, 1e-6, ba_knobs().xlimit);
+}
 // upload, memset, k_ba_window, the one or two halves, k_results_b, download; a second attempt with one workgroup per window if two halves missed each other
 int batch_enqueue(BatchCall &c, BatchRoute &r, int iters_fast, int iterations, double repr_eps)
 {
@@ -368,7 +543,7 @@ int batch_enqueue(BatchCall &c, BatchRoute &r, int iters_fast, int iterations, d
     const int NB = c.NB;
     char *A = c.A;
     hipStream_t st = ctx->stream;
-    static std::atomic<bool> attr_set[7][64], bw_attr[64];
+    static std::atomic<bool> attr_set[7][64];
     const size_t sg_max = sg_lds_bytes(BS_MAXHB, SOLVE_MAX_N / 6);
     int rc = LDS_ATTR_ONCE(ctx, attr_set[0], k_schur_groups_b<SG_T>, sg_max);
     if (!rc) rc = LDS_ATTR_ONCE(ctx, attr_set[1], k_schur_groups_b<256>, sg_max);
@@ -380,7 +555,7 @@ int batch_enqueue(BatchCall &c, BatchRoute &r, int iters_fast, int iterations, d
     if (rc) return rc;
     const BAWin *tab = (const BAWin *)A; const BARes *rtab = (const BARes *)(A + c.tab_bytes);
     hipStream_t st2 = r.two_streams ? ctx_aux_stream(ctx) : nullptr;
-    if (r.NS > 0 && (rc = LDS_ATTR_ONCE(ctx, bw_attr, k_ba_window, bw_lds_bytes(BW_PMAX))) != SLAM_OK) return rc;
+    if ((rc = window_attr(c, r)) != SLAM_OK) return rc;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     hipError_t e = hipEventCreate(&e0);
     if (e == hipSuccess) e = hipEventCreate(&e1);
@@ -392,7 +567,7 @@ int batch_enqueue(BatchCall &c, BatchRoute &r, int iters_fast, int iterations, d
         if (e == hipSuccess) e = hipMemsetAsync(A + c.zero_base, 0, c.ze[NB], st);
         if (e != hipSuccess) break;
         (void)hipEventRecord(e0, st);
-        if (r.NS > 0) hipLaunchKernelGGL(k_ba_window, dim3(r.two ? r.two_grid : r.NS), dim3(BW_T), r.lds_bw, st, tab, (const int *)(A + c.list_off()), r.NS, r.two, iters_fast, iterations, repr_eps, 1e-6, ba_knobs().xlimit);
+        launch_window(c, r, iters_fast, iterations, repr_eps);
         if (!r.all_small && st2) {
             const int nA = NB / 2;
             (void)hipEventRecord(ctx->fork_ev, st); (void)hipStreamWaitEvent(st2, ctx->fork_ev, 0);
@@ -434,6 +609,167 @@ void batch_scatter(BatchCall &c, BAPool &pool, double *theta, uint8_t *outliers,
         ba_unpermute(q.ba, th, dst, (const uint8_t *)(c.res_host + (r.off_outl - c.res_base)), outliers + c.in.ob_off[z]);
         memcpy(dst + 6 * q.P, th + 6 * q.P, (size_t)3 * q.M * 8);
     });
+}
+
+// ---- slam_local_ba_batch_dev in steps over the same state: dev_probe -> dev_select -> dev_arena -> dev_tables -> dev_enqueue
+struct DevCall {
+    BatchCall c;
+    BADevArgs a;
+    std::vector<BADevIn> din;                     // [S] where window z's arrays start in the caller's device arrays
+    std::vector<BADevProbe> pr;                   // [S] what the probe kernel found
+    size_t din_off = 0;                           // the batch's windows' BADevIn records: behind the tables, in the same upload
+    size_t probe_bytes = 0, state_bytes = 0;      // the call's two device -> host copies
+    const BADevIn *din_dev() const { return (const BADevIn *)(c.A + din_off); }
+};
+// the probe kernel over all S windows and its one small copy back
+int dev_probe(DevCall &dc, const int32_t *Pn, const int32_t *Mn, const int32_t *On)
+{
+    slam_ctx *ctx = dc.c.ctx; const int S = dc.c.S;
+    dc.din.resize(S); dc.pr.resize(S);
+    long long th = 0, pc = 0, ob = 0;
+    for (int z = 0; z < S; z++) { dc.din[z] = {th, pc, ob, Pn[z], Mn[z], On[z], 0}; th += 6ll * Pn[z] + 3ll * Mn[z]; pc += Pn[z]; ob += On[z]; }
+    const size_t in_b = al((size_t)S * sizeof(BADevIn)), out_b = (size_t)S * sizeof(BADevProbe);
+    char *scr, *h;
+    int rc = slam_scratch2(ctx, in_b + out_b, (void **)&scr);
+    if (!rc) rc = slam_pinned(ctx, in_b + out_b, (void **)&h);
+    if (rc) return rc;
+    memcpy(h, dc.din.data(), (size_t)S * sizeof(BADevIn));
+    HIP_TRY(ctx, hipMemcpyAsync(scr, h, in_b, hipMemcpyHostToDevice, ctx->stream));
+    { ProfScope span(ctx, "ba_dev_probe");
+      hipLaunchKernelGGL(k_ba_dev_probe, dim3(S), dim3(256), 0, ctx->stream, (const BADevIn *)scr, dc.a, (BADevProbe *)(scr + in_b)); }
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(h + in_b, scr + in_b, out_b, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, slam_stream_wait(ctx->stream));
+    memcpy(dc.pr.data(), h + in_b, out_b);
+    dc.probe_bytes = out_b;
+    return SLAM_OK;
+}
+// Which windows k_ba_window takes -- ba_plan's own rule (ba_window_eligible) on what the probe found, with the poses relabelled so that the free ones are
+// last -- and their plans, from sizes alone.  The others get their code: SLAM_ERR_ARG (the contract's two checks) or SLAM_BA_DEV_INELIGIBLE.
+void dev_select(DevCall &dc, const double *cams)
+{
+    BatchCall &c = dc.c;
+    const BAKnobs &kn = ba_knobs();
+    c.in.pl = std::vector<BAPlan>(c.S); c.st_code.assign(c.S, SLAM_OK); c.route.resize(c.S);
+    for (int z = 0; z < c.S; z++) {
+        const BADevIn &w = dc.din[z]; const BADevProbe &p = dc.pr[z];
+        BAPlan &q = c.in.pl[z];
+        q.fx = cams[4 * z]; q.fy = cams[4 * z + 1]; q.cx = cams[4 * z + 2]; q.cy = cams[4 * z + 3]; q.P = w.P; q.M = w.M; q.O = w.O; q.small_groups = true;
+        if (p.nfree < 0) { c.st_code[z] = SLAM_BA_DEV_INELIGIBLE; continue; }          // sizes alone: no observations, P > 128, O > 40000
+        if (p.flags) { q.fail(SLAM_ERR_ARG, (p.flags & BAD_UNGROUPED) ? "slam_local_ba_batch_dev: an id out of range, or observations not grouped by ascending point id" : "slam_local_ba_batch_dev: a map point is observed twice by one free pose"); c.st_code[z] = SLAM_ERR_ARG; continue; }
+        int p0, pspan;
+        ba_free_span_relabelled(w.P, p.nfree, &p0, &pspan);
+        // (free poses that are consecutive have half-bandwidth <= nfree - 1: the bound stands in for the value, which k_ba_window never reads)
+        const int hb = std::max(p.nfree - 1, 0);
+        const bool grouped = !kn.no_groups && hb <= BS_MAXHB && sg_fold_fits(hb);
+        if (!ba_window_eligible(!kn.no_bw, grouped, p.nfree, pspan, w.P, w.O, p.cmax)) { c.st_code[z] = SLAM_BA_DEV_INELIGIBLE; continue; }
+        slam_ba *ba = q.ba = new slam_ba();
+        ba->hb = q.hb = hb; ba->p0 = p0; ba->pspan = pspan; ba->grouped = true;
+        q.window = true; q.nfree_obs = p.nfree_obs; q.sg_ob = std::max(p.cmax, 1);
+        ba_layout(q);
+        c.route[z] = solve_route(ba, w.P, c.ctx, true);
+        if (!batch_takes(ba, c.route[z])) { c.st_code[z] = SLAM_BA_DEV_INELIGIBLE; continue; }      // (one pose in all: the host form solves it outside the batch)
+        c.batch.push_back(z);
+    }
+    c.NB = (int)c.batch.size();
+}
+// the arena of the host form with two differences: the windows' BADevIn records travel behind the tables, and the LM states of all windows stand together at
+// the head of the result region -- they are all that comes back
+int dev_arena(DevCall &dc)
+{
+    BatchCall &c = dc.c;
+    const int NB = c.NB;
+    c.up.resize(NB + 1); c.ze.resize(NB + 1); c.wk.resize(NB + 1); c.rs.resize(NB + 1);
+    c.tab_bytes = al((size_t)NB * sizeof(BAWin)); c.rtab_bytes = al((size_t)NB * sizeof(BARes)) + al((size_t)NB * 4);
+    dc.din_off = c.tab_bytes + c.rtab_bytes;
+    c.up[0] = dc.din_off + al((size_t)NB * sizeof(BADevIn)); c.ze[0] = 0; c.wk[0] = 0;
+    dc.state_bytes = (size_t)NB * al(sizeof(LMState)); c.rs[0] = dc.state_bytes;
+    for (int k = 0; k < NB; k++) {
+        const BAPlan &q = c.plan(k);
+        c.up[k + 1] = c.up[k] + q.up_bytes; c.ze[k + 1] = c.ze[k] + q.zero_bytes; c.wk[k + 1] = c.wk[k] + q.work_bytes;
+        c.rs[k + 1] = c.rs[k] + al((6 * (size_t)q.P + 3 * (size_t)q.M) * 8 + 8) + al((size_t)q.O + 8);
+    }
+    c.up_total = c.up[NB]; c.zero_base = c.up_total; c.work_base = c.zero_base + c.ze[NB]; c.res_base = c.work_base + c.wk[NB]; c.total = c.res_base + c.rs[NB];
+    if (const int rc = slam_scratch(c.ctx, c.total, (void **)&c.A)) return rc;
+    if (const int rc = slam_pinned(c.ctx, c.up[0] + dc.state_bytes, (void **)&c.stage)) return rc;
+    c.res_host = c.stage + c.up[0]; c.tab_h = (BAWin *)c.stage; c.rtab_h = (BARes *)(c.stage + c.tab_bytes);
+    return SLAM_OK;
+}
+// the tables, from sizes alone: pointers bound (ba_bind), nothing staged
+void dev_tables(DevCall &dc)
+{
+    BatchCall &c = dc.c;
+    for (int k = 0; k < c.NB; k++) {
+        BAPlan &q = c.plan(k);
+        BAWin &w = c.tab_h[k];
+        memset(&w, 0, sizeof w);
+        BARes &r = c.rtab_h[k];
+        r.off_state = c.res_base + (size_t)k * al(sizeof(LMState)); r.off_theta = c.res_base + c.rs[k]; r.off_outl = r.off_theta + al((6 * (size_t)q.P + 3 * (size_t)q.M) * 8 + 8);
+        char *zero = c.A + c.zero_base + c.ze[k];
+        ba_bind(q, c.A + c.up[k], zero, c.A + c.work_base + c.wk[k]);
+        win_table(c, k, zero);
+        ((BADevIn *)(c.stage + dc.din_off))[k] = dc.din[c.batch[k]];
+    }
+}
+// tables up, memset, the stager; `solve`: k_ba_window, k_results_b, the results kernel, the states back -- and all of it again, THE STAGER INCLUDED, on one
+// workgroup per window if two halves missed each other: the solver advances d.pose / d.pts inside the region the stager wrote, and the caller's arrays are
+// still the inputs (k_ba_dev_results wrote nothing)
+int dev_enqueue(DevCall &dc, BatchRoute &r, bool solve, int iters_fast, int iterations, double repr_eps)
+{
+    BatchCall &c = dc.c;
+    slam_ctx *ctx = c.ctx;
+    hipStream_t st = ctx->stream;
+    char *A = c.A;
+    const int NB = c.NB;
+    if (const int rc = window_attr(c, r)) return rc;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    hipError_t e = hipEventCreate(&e0);
+    if (e == hipSuccess) e = hipEventCreate(&e1);
+    for (int attempt = 0; e == hipSuccess && attempt < 2; attempt++) {
+        e = hipMemcpyAsync(A, c.stage, c.up[0], hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemsetAsync(A + c.zero_base, 0, c.ze[NB], st);
+        if (e != hipSuccess) break;
+        (void)hipEventRecord(e0, st);
+        { ProfScope span(ctx, "ba_dev_stage");
+          hipLaunchKernelGGL(k_ba_dev_stage, dim3(NB), dim3(256), 0, st, (BAWin *)A, dc.din_dev(), dc.a); }
+        if (!solve) { e = hipGetLastError(); break; }
+        launch_window(c, r, iters_fast, iterations, repr_eps);
+        hipLaunchKernelGGL(k_results_b, dim3(8, NB), dim3(256), 0, st, (const BAWin *)A, (const BARes *)(A + c.tab_bytes), A);
+        { ProfScope span(ctx, "ba_dev_results");
+          hipLaunchKernelGGL(k_ba_dev_results, dim3(NB), dim3(256), 0, st, (const BAWin *)A, (const BARes *)(A + c.tab_bytes), (const char *)A, dc.din_dev(), NB, r.two, dc.a); }
+        e = hipGetLastError();
+        (void)hipEventRecord(e1, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(c.res_host, A + c.res_base, dc.state_bytes, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = slam_stream_wait(st);
+        if (e == hipSuccess) (void)hipEventElapsedTime(&c.dev_ms, e0, e1);
+        if (e != hipSuccess || !r.two) break;
+        bool missed = false;
+        for (int k = 0; k < NB; k++) if (c.state(k).chol_fail == 2) { missed = true; break; }
+        if (!missed) break;
+        r.two = 0; n_xretry.fetch_add(1);
+    }
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    if (e == hipSuccess) return SLAM_OK;
+    return slam_fail(ctx, SLAM_ERR_HIP, "slam_local_ba_batch_dev: %s", hipGetErrorString(e));
+}
+int dev_begin(DevCall &dc, slam_ctx *ctx, int S, const double *cams, const int32_t *Pn, const int32_t *Mn, const int32_t *On,
+              double *theta, const uint8_t *theta_const, const double *pixels_yx, const int64_t *pose_ids, const int64_t *point_ids, uint8_t *outliers)
+{
+    ARG_TRY(ctx, ctx != nullptr && S >= 1 && S <= 65535 && cams != nullptr && Pn != nullptr && Mn != nullptr && On != nullptr);
+    ARG_TRY(ctx, theta != nullptr && theta_const != nullptr && outliers != nullptr);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    long long nO = 0;
+    for (int z = 0; z < S; z++) { ARG_TRY(ctx, Pn[z] > 0 && Mn[z] >= 0 && On[z] >= 0); nO += On[z]; }
+    ARG_TRY(ctx, nO == 0 || (pixels_yx != nullptr && pose_ids != nullptr && point_ids != nullptr));
+    dc.c.ctx = ctx; dc.c.S = S;
+    dc.a = {theta, theta_const, pixels_yx, pose_ids, point_ids, outliers};
+    if (const int rc = dev_probe(dc, Pn, Mn, On)) return rc;
+    dev_select(dc, cams);
+    if (dc.c.NB == 0) return SLAM_OK;
+    if (const int rc = dev_arena(dc)) return rc;
+    dev_tables(dc);
+    return SLAM_OK;
 }
 }  // namespace
 
@@ -501,6 +837,65 @@ int slam_local_ba_batch(slam_ctx *ctx, int S, const double *cams, const int32_t 
     return first;
 }
 
+
+// slam_local_ba_batch on windows that are resident in HBM (include/slamhip.h has the contract): theta (in / out), theta_const, pixels_yx, pose_ids, point_ids
+// and outliers (out) are DEVICE pointers.  k_ba_window's windows only; no host structure analysis, no staging, no scatter: the probe's few ints per window and
+// the LM states are all that crosses the bus.
+int slam_local_ba_batch_dev(slam_ctx *ctx, int S, const double *cams, const int32_t *Pn, const int32_t *Mn, const int32_t *On,
+                            double *theta, const uint8_t *theta_const, const double *pixels_yx,
+                            const int64_t *pose_ids, const int64_t *point_ids, uint8_t *outliers,
+                            int iters_fast, int iterations, double repr_eps, double *stats, int32_t *status)
+{
+    ARG_TRY(ctx, ctx != nullptr && iters_fast >= 0 && iterations >= 0);
+    DevCall dc;
+    int rc = dev_begin(dc, ctx, S, cams, Pn, Mn, On, theta, theta_const, pixels_yx, pose_ids, point_ids, outliers);
+    if (rc) return rc;
+    BatchCall &c = dc.c;
+    if (stats) memset(stats, 0, (size_t)S * 8 * sizeof(double));
+    if (c.NB > 0) {
+        BatchRoute r = batch_route(c);
+        if ((rc = dev_enqueue(dc, r, true, iters_fast, iterations, repr_eps)) != SLAM_OK) return rc;
+        for (int k = 0; k < c.NB; k++) {
+            const int z = c.batch[k];
+            const LMState &h = c.state(k);
+            if (stats) lm_stats(h, c.dev_ms, stats + 8 * (size_t)z);
+            if (h.chol_fail) c.st_code[z] = SLAM_ERR_NUMERIC;
+        }
+        if (ba_knobs().host_times) fprintf(stderr, "slam_local_ba_batch_dev: %d of %d windows, device %.0f us; %zu B of probe results and %zu B of LM states back, %zu B of tables up, %zu B arena\n", c.NB, S, c.dev_ms * 1e3, dc.probe_bytes, dc.state_bytes, c.up[0], c.total);
+    }
+    int first = SLAM_OK;
+    for (int z = 0; z < S; z++) { if (status) status[z] = c.st_code[z]; if (c.st_code[z] && !first) first = c.st_code[z]; }
+    if (status || first == SLAM_OK) return SLAM_OK;            // per-window codes are in status[]
+    for (int z = 0; z < S; z++) if (c.st_code[z] == first) return slam_fail(ctx, first < 0 ? first : SLAM_ERR_ARG, "slam_local_ba_batch_dev: window %d: %s", z, first == SLAM_ERR_NUMERIC ? "the reduced camera system was not positive definite (theta and outliers are left unchanged)" : first == SLAM_BA_DEV_INELIGIBLE ? "not a window k_ba_window takes (pass status to have the others solved)" : c.in.pl[z].msg);
+    return first;
+}
+// test aid (tests/test_gpu_ba_batch_dev.py): probe and stage the windows as slam_local_ba_batch_dev does, solve nothing, and download window z's staged
+// ("uploaded") region into out[0 .. cap).  info (16 int64): the offsets of pose, pts, pconst, pix, opose, opoint, pt_start, pt_id, opk, pfs, fobs, fgrp inside it,
+// then its length, the window's ksplit, p0 and free-pose count.  Returns the window's status code when it is not staged (nothing is written then).
+int slam_debug_ba_dev_staged(slam_ctx *ctx, int S, const double *cams, const int32_t *Pn, const int32_t *Mn, const int32_t *On,
+                             double *theta, const uint8_t *theta_const, const double *pixels_yx, const int64_t *pose_ids, const int64_t *point_ids,
+                             uint8_t *outliers, int z, uint8_t *out, long long cap, long long *info)
+{
+    ARG_TRY(ctx, ctx != nullptr && out != nullptr && info != nullptr && z >= 0 && z < S);
+    DevCall dc;
+    int rc = dev_begin(dc, ctx, S, cams, Pn, Mn, On, theta, theta_const, pixels_yx, pose_ids, point_ids, outliers);
+    if (rc) return rc;
+    BatchCall &c = dc.c;
+    if (c.st_code[z]) return c.st_code[z];
+    const int k = (int)(std::find(c.batch.begin(), c.batch.end(), z) - c.batch.begin());
+    const BAPlan &q = c.plan(k);
+    ARG_TRY(ctx, (long long)q.up_bytes <= cap);
+    BatchRoute r = batch_route(c);
+    if ((rc = dev_enqueue(dc, r, false, 0, 0, 0.0)) != SLAM_OK) return rc;
+    BAWin w;
+    HIP_TRY(ctx, hipMemcpyAsync(out, c.A + c.up[k], q.up_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(&w, c.A + (size_t)k * sizeof(BAWin), sizeof w, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, slam_stream_wait(ctx->stream));
+    const size_t o[12] = {q.o_pose, q.o_pts, q.o_const, q.o_pix, q.o_opose, q.o_opoint, q.o_start, q.o_ptid, q.o_opk, q.o_pfs, q.o_fobs, q.o_fgrp};
+    for (int i = 0; i < 12; i++) info[i] = (long long)o[i];
+    info[12] = (long long)q.up_bytes; info[13] = w.ksplit; info[14] = w.B.p0; info[15] = w.B.nb;
+    return SLAM_OK;
+}
 
 // slam_local_ba_batch in two halves: _begin hands the whole call (structure analysis, staging, upload, solve, download, scatter) to a thread of the
 // library's own and returns; _end waits for it and returns its code.  The estimator task of a host (estimator.jl:78-99) thereby prepares key-frame

@@ -73,9 +73,10 @@ bool ba_pose_order(int P, int M, int O, const uint8_t *theta_const, const int64_
     }
     const int hbq = std::min(std::max(best_bw, 1), F - 1);
     if (best_bw > BS_MAXHB || !sg_fold_fits(best_bw) || band_lds_bytes(6 * P, F, hbq) > 150 * 1024) return false;
-    order.clear();
-    for (int p = 0; p < P; p++) if (theta_const[p]) order.push_back(p);
-    for (int k = 0; k < F; k++) order.push_back(fr[best[k]]);
+    std::vector<int> seq(F);
+    for (int k = 0; k < F; k++) seq[k] = fr[best[k]];
+    order.resize(P);
+    ba_relabel_free_last(theta_const, P, seq.data(), F, order.data());
     return true;
 }
 
@@ -92,6 +93,47 @@ int ba_plan_order(int P, int M, int O, const uint8_t *theta_const, const int64_t
     return pl.new_of.empty() ? 0 : 1;
 }
 
+// The layout of a window's three regions and its launch sizes, from sizes alone: P, M, O, hb, window, small_groups, nfree_obs, the counts of groups / pairs /
+// blocks and ba->grouped.  ba_plan ends in it; slam_local_ba_batch_dev, which has no host structure analysis, calls it with the sizes its probe kernel reports.
+void ba_layout(BAPlan &pl)
+{
+    slam_ba *ba = pl.ba;
+    const int P = pl.P, M = pl.M, O = pl.O, n = 6 * P;
+    const bool grouped = ba->grouped;
+    const size_t npairs = pl.npairs;
+    const int nblk = pl.nblk, ngrp = pl.ngrp, hbw = pl.hb + 1;
+    pl.wstride = grouped ? hbw * (hbw + 1) / 2 * 36 + hbw * 12 : 0;
+    const int nbo = (O + 255) / 256, nbp = (std::max(M, n) + 255) / 256;
+    ba->nblocks_obs = std::max(nbo, 1); ba->nblocks_pts = std::max(nbp, 1);
+    // --- layout: uploaded arrays (one contiguous block: a single copy from the staging buffer), the zero-initialised ones (one memset), the rest
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off += al(bytes); return o; };
+    pl.o_pose = take(n * 8); pl.o_pts = take((size_t)3 * M * 8 + 8); pl.o_const = take(P); pl.o_pix = take((size_t)2 * O * 8 + 8);
+    pl.o_opose = take((size_t)O * 4 + 4); pl.o_opoint = take((size_t)O * 4 + 4); pl.o_start = take((size_t)(M + 1) * 4);
+    pl.o_ptid = take((size_t)M * 4 + 4); pl.o_opk = take((size_t)O * 4 + 4); pl.o_ohp = take(pl.window ? 8 : (size_t)O * 4 + 4); pl.o_pfs = take(pl.small_groups ? (size_t)(M + 1) * 4 : 8); pl.o_fobs = take(pl.small_groups ? (size_t)pl.nfree_obs * 4 + 4 : 8); pl.o_grp = take((size_t)ngrp * 16 + 16); pl.o_fgrp = take((size_t)(P + 1) * 4);      // (pfs / fobs: k_ba_window's lists, batches only)
+    pl.o_pairs = take(npairs * 8 + 8); pl.o_bs = take((size_t)(nblk + 1) * 4); pl.o_bpq = take((size_t)nblk * 8 + 8);
+    pl.up_bytes = off; off = 0;
+    pl.o_st = take(sizeof(LMState)); pl.o_cf = take(64); pl.o_outl = take((size_t)O + 1);
+    pl.o_dp = take(n * 8);                                       // dp of the constant poses outside the solve's span stays zero
+    if (pl.window) pl.o_bwx = take(BWX_DOUBLES * 8);               // k_ba_window on two workgroups: flags + two double-buffered partials of 32 x 25 doubles each (zeroed: the flags count exchanges)
+    pl.o_red = take(((size_t)n * n + 2 * n + 8) * 8);            // the private reduce buffer: only its band is ever rewritten
+    pl.zero_bytes = off; off = 0;
+    pl.o_sc0 = take(n * 8); pl.o_sc1 = take(n * 8);
+    pl.o_pose_t = take(n * 8); pl.o_pts_t = take((size_t)3 * M * 8 + 8); pl.o_hasp = take((size_t)O + 1);
+    pl.o_f = take((size_t)2 * O * 8 + 8); pl.o_ft = take(8);    // (trial residuals are not kept: every build re-evaluates d.f)
+    pl.o_Jp = take((size_t)12 * O * 8 + 8); pl.o_Jl = take((size_t)6 * O * 8 + 8);
+    pl.o_Vinv = take((size_t)6 * M * 8 + 8); pl.o_bl = take((size_t)3 * M * 8 + 8);
+    pl.o_T = take(grouped ? 8 : (size_t)18 * O * 8 + 8); pl.o_W = take(grouped ? 8 : (size_t)18 * O * 8 + 8);   // T / W records: pair-list path only
+    // (the tiled Cholesky's working matrices exist for every window: a window whose band does not fit k_band_solve's LDS takes that path)
+    pl.o_Sw = take((size_t)(n + 1) * n * 8); pl.o_dl = take((size_t)3 * M * 8 + 8);
+    pl.o_li = take((size_t)((n + CT - 1) / CT) * CT * CT * 8); pl.o_lf = take((size_t)(n + 1) * n * 8);
+    pl.o_part = take(((size_t)std::max(ba->nblocks_pts, ngrp) + 2 * (size_t)std::max(ba->nblocks_obs, ngrp) + 8) * 8);
+    pl.o_band = take((size_t)P * ((size_t)(BS_MAXHB + 1) * 36 + 8) * 8);
+    pl.o_wpart = take((size_t)ngrp * pl.wstride * 8 + 8);
+    pl.o_xchg = take(2048 * 8);
+    pl.work_bytes = off;
+}
+
 int ba_plan(BAPlan &pl)
 {
     const int P = pl.P, M = pl.M, O = pl.O;
@@ -101,7 +143,6 @@ int ba_plan(BAPlan &pl)
     pl.theta_const = pl.theta_const_in;
     const uint8_t *&theta_const = pl.theta_const;
     slam_ba *ba = pl.ba = new slam_ba();
-    const int n = 6 * P;
     // --- host-side structure.  Map points sorted by (first free observing pose f, id); observations sorted by point in
     //     that order (stable).  hb = widest span of free observers of one point = block half-bandwidth of S.
     std::vector<int> &cnt = pl.cnt, &pfirst = pl.pfirst, plast(M), pany(M);
@@ -164,9 +205,7 @@ int ba_plan(BAPlan &pl)
     }
     ba->hb = hb; pl.hb = hb;
     if (pl.order_only) return SLAM_OK;
-    {   int f0 = P, f1 = -1;
-        for (int p = 0; p < P; p++) if (!theta_const[p]) { f0 = std::min(f0, p); f1 = std::max(f1, p); }
-        if (f1 - f0 + 1 >= 2) { ba->p0 = f0; ba->pspan = f1 - f0 + 1; } else { ba->p0 = 0; ba->pspan = P; } }
+    ba_free_span(theta_const, P, &ba->p0, &ba->pspan);
     std::vector<int> &pt_id = pl.pt_id, &rank = pl.rank, &start = pl.start;
     pt_id.assign(M, 0); rank.assign(M, 0); start.assign(M + 1, 0);
     { std::vector<int> fb(P + 1, 0);
@@ -184,7 +223,7 @@ int ba_plan(BAPlan &pl)
     {   // a window one workgroup can keep to itself (k_ba_window, batches only): the point groups of the launch-per-phase kernels are not built
         int nfree = 0; for (int p = 0; p < P; p++) nfree += theta_const[p] ? 0 : 1;
         int cmax = 0; for (int j = 0; j < M; j++) cmax = std::max(cmax, cnt[j]);
-        pl.window = pl.small_groups && !kn.no_bw && grouped && nfree >= 1 && nfree <= 5 && nfree == ba->pspan && P <= 128 && O <= 40000 && cmax <= 168;
+        pl.window = ba_window_eligible(pl.small_groups && !kn.no_bw, grouped, nfree, ba->pspan, P, O, cmax);
         if (pl.window) pl.sg_ob = std::max(cmax, 1);               // k_ba_window's tiles are sized from it (no point groups are built for such a window)
         if (pl.window && M > 1 && !kn.window_sorted) {
             // k_ba_window splits a window over two workgroups by map points: the points that see a free pose at all (the Schur phase's records --
@@ -280,47 +319,16 @@ int ba_plan(BAPlan &pl)
     }
     blk_start.push_back((int)npairs);
     pl.npairs = npairs;
-    const int nblk = pl.nblk = (int)blk_pq.size();
-    const int ngrp = pl.ngrp = (int)grp.size(), hbw = hb + 1;
-    pl.wstride = grouped ? hbw * (hbw + 1) / 2 * 36 + hbw * 12 : 0;
-    const int nbo = (O + 255) / 256, nbp = (std::max(M, n) + 255) / 256;
-    ba->nblocks_obs = std::max(nbo, 1); ba->nblocks_pts = std::max(nbp, 1);
-    // --- layout: uploaded arrays (one contiguous block: a single copy from the staging buffer), the zero-initialised ones (one memset), the rest
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += al(bytes); return o; };
-    pl.o_pose = take(n * 8); pl.o_pts = take((size_t)3 * M * 8 + 8); pl.o_const = take(P); pl.o_pix = take((size_t)2 * O * 8 + 8);
-    pl.o_opose = take((size_t)O * 4 + 4); pl.o_opoint = take((size_t)O * 4 + 4); pl.o_start = take((size_t)(M + 1) * 4);
-    pl.o_ptid = take((size_t)M * 4 + 4); pl.o_opk = take((size_t)O * 4 + 4); pl.o_ohp = take(pl.window ? 8 : (size_t)O * 4 + 4); pl.o_pfs = take(pl.small_groups ? (size_t)(M + 1) * 4 : 8); pl.o_fobs = take(pl.small_groups ? (size_t)pl.nfree_obs * 4 + 4 : 8); pl.o_grp = take((size_t)ngrp * 16 + 16); pl.o_fgrp = take((size_t)(P + 1) * 4);      // (pfs / fobs: k_ba_window's lists, batches only)
-    pl.o_pairs = take(npairs * 8 + 8); pl.o_bs = take((size_t)(nblk + 1) * 4); pl.o_bpq = take((size_t)nblk * 8 + 8);
-    pl.up_bytes = off; off = 0;
-    pl.o_st = take(sizeof(LMState)); pl.o_cf = take(64); pl.o_outl = take((size_t)O + 1);
-    pl.o_dp = take(n * 8);                                       // dp of the constant poses outside the solve's span stays zero
-    if (pl.window) {                                             // k_ba_window on two workgroups: flags + two double-buffered partials of 32 x 25 doubles each (zeroed: the flags count exchanges)
-        pl.o_bwx = take(BWX_DOUBLES * 8);
-        pl.ksplit = (int)(std::lower_bound(start.begin(), start.end(), (O + 1) / 2) - start.begin());
-        pl.ksplit = std::min(std::max(pl.ksplit, 0), M);
-    }
-    pl.o_red = take(((size_t)n * n + 2 * n + 8) * 8);            // the private reduce buffer: only its band is ever rewritten
-    pl.zero_bytes = off; off = 0;
-    pl.o_sc0 = take(n * 8); pl.o_sc1 = take(n * 8);
-    pl.o_pose_t = take(n * 8); pl.o_pts_t = take((size_t)3 * M * 8 + 8); pl.o_hasp = take((size_t)O + 1);
-    pl.o_f = take((size_t)2 * O * 8 + 8); pl.o_ft = take(8);    // (trial residuals are not kept: every build re-evaluates d.f)
-    pl.o_Jp = take((size_t)12 * O * 8 + 8); pl.o_Jl = take((size_t)6 * O * 8 + 8);
-    pl.o_Vinv = take((size_t)6 * M * 8 + 8); pl.o_bl = take((size_t)3 * M * 8 + 8);
-    pl.o_T = take(grouped ? 8 : (size_t)18 * O * 8 + 8); pl.o_W = take(grouped ? 8 : (size_t)18 * O * 8 + 8);   // T / W records: pair-list path only
-    // (the tiled Cholesky's working matrices exist for every window: a window whose band does not fit k_band_solve's LDS takes that path)
-    pl.o_Sw = take((size_t)(n + 1) * n * 8); pl.o_dl = take((size_t)3 * M * 8 + 8);
-    pl.o_li = take((size_t)((n + CT - 1) / CT) * CT * CT * 8); pl.o_lf = take((size_t)(n + 1) * n * 8);
-    pl.o_part = take(((size_t)std::max(ba->nblocks_pts, ngrp) + 2 * (size_t)std::max(ba->nblocks_obs, ngrp) + 8) * 8);
-    pl.o_band = take((size_t)P * ((size_t)(BS_MAXHB + 1) * 36 + 8) * 8);
-    pl.o_wpart = take((size_t)ngrp * pl.wstride * 8 + 8);
-    pl.o_xchg = take(2048 * 8);
-    pl.work_bytes = off;
+    pl.nblk = (int)blk_pq.size(); pl.ngrp = (int)grp.size();
+    ba_layout(pl);
+    if (pl.window) pl.ksplit = ba_ksplit_obs(M, O, [&](int k) { return start[k]; });
     return SLAM_OK;
 }
 
-// bind the device pointers (region bases Aup / Azero / Awork) and write the uploaded region into `stage` (host memory, up_bytes)
-int ba_emit(BAPlan &pl, char *Aup, char *Azero, char *Awork, char *stage)
+
+// ba_emit in its two halves: ba_bind binds the device pointers (region bases Aup / Azero / Awork), ba_stage writes the uploaded region into `stage` (host
+// memory, up_bytes).  slam_local_ba_batch_dev binds alone: its uploaded region is written on the device (k_ba_dev_stage).
+void ba_bind(BAPlan &pl, char *Aup, char *Azero, char *Awork)
 {
     slam_ba *ba = pl.ba;
     const int P = pl.P, M = pl.M, O = pl.O, n = 6 * P;
@@ -345,6 +353,12 @@ int ba_emit(BAPlan &pl, char *Aup, char *Azero, char *Awork, char *stage)
     d.sg_ob = pl.sg_ob; d.sg_sb = pl.sg_sb; d.ohp = (const int *)(Aup + pl.o_ohp); d.pfs = (const int *)(Aup + pl.o_pfs); d.fobs = (const int *)(Aup + pl.o_fobs);
     ba->nparts = ba->grouped ? pl.ngrp : ba->nblocks_obs;
     ba->xchg = (double *)(Awork + pl.o_xchg);
+    d.sg_hp = pl.sg_hp;
+}
+int ba_stage(BAPlan &pl, char *stage)
+{
+    slam_ba *ba = pl.ba;
+    const int P = pl.P, M = pl.M, O = pl.O, n = 6 * P;
 #define UP(o, src, bytes) do { if ((bytes) > 0) memcpy(stage + (o), (src), (bytes)); } while (0)
     if (!pl.new_of.empty()) { double *dst = (double *)(stage + pl.o_pose); for (int k = 0; k < P; k++) memcpy(dst + 6 * k, pl.theta + 6 * ba->pose_order[k], 48); }
     else UP(pl.o_pose, pl.theta, (size_t)n * 8);
@@ -358,7 +372,12 @@ int ba_emit(BAPlan &pl, char *Aup, char *Azero, char *Awork, char *stage)
     UP(pl.o_pairs, pl.pairs.data(), pl.npairs * 8); UP(pl.o_bs, pl.blk_start.data(), (size_t)(pl.nblk + 1) * 4); UP(pl.o_bpq, pl.blk_pq.data(), (size_t)pl.nblk * 8);
     UP(pl.o_ptid, pl.pt_id.data(), (size_t)M * 4); UP(pl.o_grp, pl.grp.data(), (size_t)pl.ngrp * 16); UP(pl.o_fgrp, pl.fgrp.data(), (size_t)(P + 1) * 4);
 #undef UP
-    d.sg_hp = pl.sg_hp;
+    ba->d.sg_hp = pl.sg_hp;                                    // (fill_obs sized it)
     return SLAM_OK;
+}
+int ba_emit(BAPlan &pl, char *Aup, char *Azero, char *Awork, char *stage)
+{
+    ba_bind(pl, Aup, Azero, Awork);
+    return ba_stage(pl, stage);
 }
 

@@ -3,13 +3,16 @@
 // Also here: BAKnobs (the planner reads switches too) and the small host helpers slam_local_ba and slam_local_ba_batch share (batch_in, lm_stats, ba_unpermute).
 // Definitions: ba_host.hip.  reference: the arrays are those of src/estimator.jl:143-266 (_get_ba_parameters); the planner has no counterpart there.
 #pragma once
+#include "ba_dev_plan.hpp"
 inline size_t al(size_t b) { return (b + 255) & ~(size_t)255; }
 size_t band_lds_bytes(int n, int Ps, int hb);
 bool ba_pose_order(int P, int M, int O, const uint8_t *theta_const, const int64_t *pose_ids, const int64_t *point_ids, std::vector<int> &order);
 // ---- set-up of one window, in two host-only halves so that a batch of windows can be prepared by several threads:
 //   ba_plan   the structure of the problem (map points sorted by first free observer, observation order, point groups or pair lists,
 //             pose order) and the layout of its device memory in three regions -- uploaded arrays, zero-initialised state, work arrays;
-//   ba_emit   binds the device pointers to the three region bases and writes the uploaded region into a host staging block.
+//   ba_emit   binds the device pointers to the three region bases (ba_bind) and writes the uploaded region into a host staging block (ba_stage).
+// slam_local_ba_batch_dev, whose windows lie in HBM, has neither half's analysis: it lays a window out from sizes alone (ba_layout, the tail of ba_plan),
+// binds the pointers (ba_bind) and leaves the uploaded region to a device kernel.  What both forms decide alike is ba_dev_plan.hpp's.
 // slam_ba_create / slam_local_ba give one window its own arena (the three regions back to back); slam_local_ba_batch lays the
 // regions of all windows out region-major (one H2D copy, one memset for the whole batch).  Neither half makes a HIP call.
 // fn(0 .. count-1) on the library's parked worker pool, the caller taking part (ba_batch.hip).  A batch prepares one window per task; ONE large window
@@ -151,7 +154,10 @@ struct BAPlan {
     }
 };
 int ba_plan(BAPlan &pl);
-int ba_emit(BAPlan &pl, char *Aup, char *Azero, char *Awork, char *stage);
+void ba_layout(BAPlan &pl);
+void ba_bind(BAPlan &pl, char *Aup, char *Azero, char *Awork);
+int ba_stage(BAPlan &pl, char *stage);
+int ba_emit(BAPlan &pl, char *Aup, char *Azero, char *Awork, char *stage);      // ba_bind, then ba_stage
 int ba_plan_order(int P, int M, int O, const uint8_t *theta_const, const int64_t *pose_ids, const int64_t *point_ids, int32_t *order_out, int *hb_out);
 // S windows of a batch call: the prefix sums over the caller's concatenated arrays and one BAPlan's inputs per window (slam_local_ba_batch, slam_debug_ba_host_time)
 struct BatchIn { std::vector<size_t> th_off, pc_off, ob_off; std::vector<BAPlan> pl; };

@@ -1,6 +1,7 @@
 // kfmap.hip -- the key-frame map of S lock-stepped streams in HBM (kfmap.hpp has the layout): filled from the keypoint lists (slam_kfmap_add_keyframe),
 // it emits the local-BA windows of the streams' newest key-frames in slam_local_ba_batch's layout (slam_kfmap_ba_gather) and takes the solution back, into
-// the map and optionally into the live lists (slam_kfmap_ba_update).  The semantics are _get_ba_parameters / _update_ba_parameters!
+// the map and optionally into the live lists (slam_kfmap_ba_update).  slam_kfmap_local_ba is the three in one call with the windows kept in HBM (emit into the map's own
+// block, slam_local_ba_batch_dev, the update kernels on the same arrays).  The semantics are _get_ba_parameters / _update_ba_parameters!
 // (src/estimator.jl:143-306) as tests/tracked_ba.py restates them, bounded by the ring and the table (tests/np_kfmap.py is the bounded model).
 // slam_kfmap_filter is map_filtering! (src/estimator.jl:358-406) on the same map, slam_kfmap_remove_keyframe the remove_keyframe! it calls
 // (src/map_manager.jl:184-209); tests/np_kfmap_filter.py is their model.  The descriptor store and slam_kfmap_local_map_match (update_frame_covisibility! +
@@ -552,6 +553,49 @@ static int kfmap_alloc_zeroed(slam_ctx *ctx, const char *who, size_t bytes, char
     return SLAM_OK;
 }
 
+// the count pass of the gather and of slam_kfmap_local_ba: table + thresholds up, k_kfm_plan, the S headers back (a wait)
+static int kfmap_plan_headers(slam_ctx *ctx, slam_kfmap *km, const int32_t *min_cov_score, const int *list, int ns, std::vector<int> &hdr)
+{
+    const KfmapView &V = km->v;
+    const int S = V.S;
+    Layout D;
+    const auto o_sel = D.take<int>(S), o_minc = D.take<int>(S); const size_t in_b = D.size();
+    char *scr, *h;
+    int rc = slam_scratch(ctx, D.size(), (void **)&scr);
+    if (rc) return rc;
+    rc = slam_pinned(ctx, std::max<size_t>(D.size(), (size_t)S * KFM_HDR * 4), (void **)&h);
+    if (rc) return rc;
+    kfmap_put_streams(o_sel, h, list, ns); memcpy(o_minc.at(h), min_cov_score, (size_t)S * 4);
+    HIP_TRY(ctx, hipMemcpyAsync(scr, h, in_b, hipMemcpyHostToDevice, ctx->stream));
+    { ProfScope span(ctx, "kfmap_gather_plan");
+      KFM_LAUNCH_ROWS(km, k_kfm_plan, dim3(ns), (const int *)o_minc.at(scr), (const int *)o_sel.at(scr)); }
+    HIP_TRY(ctx, hipGetLastError());
+    rc = kpset_read_back(ctx, h, {{0, V.whdr, (size_t)S * KFM_HDR * 4, nullptr}});
+    if (rc) return rc;
+    hdr.resize((size_t)S * KFM_HDR);
+    memcpy(hdr.data(), h, hdr.size() * 4);
+    return SLAM_OK;
+}
+
+// the update kernels over the windows of the device table wd, theta / outl in HBM (windows back to back, KfmUpd::theta0 / obs0), then the lists' compaction
+static int kfmap_update_enqueue(slam_ctx *ctx, slam_kfmap *km, slam_kpset *ks, const KfmUpd *wd, int n_windows, int maxM, const double *theta, const uint8_t *outl)
+{
+    const KfmapView &V = km->v;
+    uint8_t *flags = nullptr;
+    if (ks) {
+        const int rc = slam_scratch2(ctx, (size_t)ks->S * ks->v.cap, (void **)&flags);
+        if (rc) return rc;
+        HIP_TRY(ctx, hipMemsetAsync(flags, 0, (size_t)ks->S * ks->v.cap, ctx->stream));
+    }
+    { ProfScope span(ctx, "kfmap_update");
+      KFM_LAUNCH_ROWS(km, k_kfm_upd_obs, dim3((maxM + 255) / 256, n_windows), wd, theta, outl);
+      hipLaunchKernelGGL(k_kfm_upd_points, dim3((V.mcap + 255) / 256, n_windows), dim3(256), 0, ctx->stream, V, wd, theta);
+      if (ks) hipLaunchKernelGGL(k_kfm_upd_list, dim3((ks->v.cap + 255) / 256, n_windows), dim3(256), 0, ctx->stream, V, ks->v, wd, flags); }
+    HIP_TRY(ctx, hipGetLastError());
+    if (ks) return kpset_compact(ctx, ks, 1, flags);             // (a stream without a flag keeps every slot where it is)
+    return SLAM_OK;
+}
+
 extern "C" {
 
 int slam_kfmap_destroy(slam_kfmap *km);
@@ -585,6 +629,7 @@ int slam_kfmap_destroy(slam_kfmap *km)
     if (km->lm_base) (void)hipFree(km->lm_base);
     if (km->mg_base) (void)hipFree(km->mg_base);
     if (km->hs_base) (void)hipFree(km->hs_base);
+    if (km->ba_base) (void)hipFree(km->ba_base);
     if (km->pin_ev) (void)hipEventDestroy(km->pin_ev);
     delete km;
     return SLAM_OK;
@@ -626,23 +671,11 @@ int slam_kfmap_ba_gather(slam_ctx *ctx, slam_kfmap *km, const int32_t *min_cov_s
     for (int k = 0; k < ns; k++) km->pend[list[k]].valid = 0;
     if (ns == 0) return SLAM_OK;
     // count pass: table + thresholds up, the plan, the headers back (the first of the call's two waits)
-    Layout D;
-    const auto o_sel = D.take<int>(S), o_minc = D.take<int>(S); const size_t in_b = D.size();
+    std::vector<int> hdr;
     char *scr, *h;
-    int rc = slam_scratch(ctx, D.size(), (void **)&scr);
-    if (rc) return rc;
-    rc = slam_pinned(ctx, std::max<size_t>(D.size(), (size_t)S * KFM_HDR * 4), (void **)&h);
-    if (rc) return rc;
-    kfmap_put_streams(o_sel, h, list, ns); memcpy(o_minc.at(h), min_cov_score, (size_t)S * 4);
-    HIP_TRY(ctx, hipMemcpyAsync(scr, h, in_b, hipMemcpyHostToDevice, ctx->stream));
-    { ProfScope span(ctx, "kfmap_gather_plan");
-      KFM_LAUNCH_ROWS(km, k_kfm_plan, dim3(ns), (const int *)o_minc.at(scr), (const int *)o_sel.at(scr)); }
-    HIP_TRY(ctx, hipGetLastError());
-    rc = kpset_read_back(ctx, h, {{0, V.whdr, (size_t)S * KFM_HDR * 4, nullptr}});
+    int rc = kfmap_plan_headers(ctx, km, min_cov_score, list, ns, hdr);
     if (rc) return rc;
     // scan over the streams: where each window goes, which ones fit
-    std::vector<int> hdr((size_t)S * KFM_HDR);
-    memcpy(hdr.data(), h, hdr.size() * 4);
     std::vector<KfmWin> wins;
     long long nP = 0, nM = 0, nO = 0, nT = 0;
     for (int k = 0; k < ns; k++) {
@@ -713,20 +746,142 @@ int slam_kfmap_ba_update(slam_ctx *ctx, slam_kfmap *km, slam_kpset *ks, int n_wi
         memcpy(o_win.at(h), wins.data(), o_win.bytes()); memcpy(o_th.at(h), theta, o_th.bytes()); memcpy(o_ol.at(h), outliers, o_ol.bytes());
     });
     if (rc) return rc;
-    const KfmUpd *wd = o_win.at(scr);
-    uint8_t *flags = nullptr;
-    if (ks) {
-        rc = slam_scratch2(ctx, (size_t)ks->S * ks->v.cap, (void **)&flags);
-        if (rc) return rc;
-        HIP_TRY(ctx, hipMemsetAsync(flags, 0, (size_t)ks->S * ks->v.cap, ctx->stream));
-    }
-    { ProfScope span(ctx, "kfmap_update");
-      KFM_LAUNCH_ROWS(km, k_kfm_upd_obs, dim3((maxM + 255) / 256, n_windows), wd, (const double *)o_th.at(scr), (const uint8_t *)o_ol.at(scr));
-      hipLaunchKernelGGL(k_kfm_upd_points, dim3((V.mcap + 255) / 256, n_windows), dim3(256), 0, ctx->stream, V, wd, (const double *)o_th.at(scr));
-      if (ks) hipLaunchKernelGGL(k_kfm_upd_list, dim3((ks->v.cap + 255) / 256, n_windows), dim3(256), 0, ctx->stream, V, ks->v, wd, flags); }
-    HIP_TRY(ctx, hipGetLastError());
+    rc = kfmap_update_enqueue(ctx, km, ks, o_win.at(scr), n_windows, maxM, o_th.at(scr), o_ol.at(scr));
+    if (rc) return rc;
     for (int w = 0; w < n_windows; w++) km->pend[win_stream[w]].valid = 0;
-    if (ks) return kpset_compact(ctx, ks, 1, flags);             // (a stream without a flag keeps every slot where it is)
+    return SLAM_OK;
+}
+
+// The estimator step on the map, the windows never leaving HBM (include/slamhip.h): plan + headers back, emit into the map's own device block, the device-input
+// batch solve on those arrays, the update kernels on the same arrays.  Windows the device batch does not take (SLAM_BA_DEV_INELIGIBLE) take the host route inside
+// the call: their slices come down, slam_local_ba_batch solves them, theta and flags go back up into the block -- and ONE update launch applies all solved windows.
+int slam_kfmap_local_ba(slam_ctx *ctx, slam_kfmap *km, slam_kpset *ks, const int32_t *min_cov_score, const double *cams,
+                        int iters_fast, int iterations, double repr_eps, int32_t *status, double *stats)
+{
+    ARG_TRY(ctx, ctx != nullptr && km != nullptr && min_cov_score != nullptr && cams != nullptr && status != nullptr && iters_fast >= 0 && iterations >= 0 &&
+                     (ks == nullptr || (ks->S == km->v.S && ks->v.cap <= km->v.cap)));
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const KfmapView &V = km->v;
+    const int S = V.S;
+    int list[128];
+    const int ns = kfmap_streams(km, list);
+    for (int s = 0; s < S; s++) { status[s] = 3; km->last_win[s][0] = km->last_win[s][1] = km->last_win[s][2] = 0; }
+    if (stats) memset(stats, 0, (size_t)S * 8 * sizeof(double));
+    for (int k = 0; k < ns; k++) km->pend[list[k]].valid = 0;
+    if (ns == 0) return SLAM_OK;
+    std::vector<int> hdr;
+    int rc = kfmap_plan_headers(ctx, km, min_cov_score, list, ns, hdr);
+    if (rc) return rc;
+    std::vector<KfmWin> wins;
+    std::vector<int32_t> Pn, Mn, On;
+    std::vector<double> cw;
+    long long nP = 0, nM = 0, nO = 0, nT = 0;
+    int maxM = 1;
+    for (int k = 0; k < ns; k++) {
+        const int s = list[k], *hd = hdr.data() + (size_t)KFM_HDR * s, P = hd[2], M = hd[3], O = hd[4];
+        if (hd[0] != 0) { status[s] = 1; continue; }
+        status[s] = 0;
+        wins.push_back({s, (int)nP, (int)nM, (int)nO, nT});
+        Pn.push_back(P); Mn.push_back(M); On.push_back(O); cw.insert(cw.end(), cams + 4 * s, cams + 4 * s + 4);
+        km->pend[s] = {1, hd[1], P, M, O};
+        km->last_win[s][0] = P; km->last_win[s][1] = M; km->last_win[s][2] = O;
+        nP += P; nM += M; nO += O; nT += 6ll * P + 3ll * M; maxM = std::max(maxM, M);
+    }
+    const int nw = (int)wins.size();
+    if (nw == 0) return SLAM_OK;
+    // the windows' arrays, laid out as the gather's block, plus the outlier flags and the update's table: the map's own block in HBM
+    Layout E;
+    const auto e_win = E.take<KfmWin>(nw); const auto e_upd = E.take<KfmUpd>(nw);
+    const auto e_th = E.take<double>((size_t)nT), e_px = E.take<double>(2 * (size_t)nO);
+    const auto e_pi = E.take<int64_t>((size_t)nO), e_li = E.take<int64_t>((size_t)nO), e_ok = E.take<int64_t>((size_t)nO), e_op = E.take<int64_t>((size_t)nO);
+    const auto e_pr = E.take<int64_t>((size_t)nP), e_lr = E.take<int64_t>((size_t)nM);
+    const auto e_tc = E.take<uint8_t>((size_t)nP), e_ic = E.take<uint8_t>((size_t)nO), e_ol = E.take<uint8_t>((size_t)nO + 1);
+    if (km->ba_bytes < E.size()) {
+        HIP_TRY(ctx, slam_stream_wait(ctx->stream));
+        if (km->ba_base) (void)hipFree(km->ba_base);
+        km->ba_base = nullptr; km->ba_bytes = 0;
+        HIP_TRY(ctx, hipMalloc((void **)&km->ba_base, E.size() + E.size() / 4));
+        km->ba_bytes = E.size() + E.size() / 4;
+    }
+    char *blk = km->ba_base, *h;
+    const size_t tab_b = e_th.off;                               // the two tables stand first
+    rc = kfmap_pin(ctx, km, tab_b, &h);
+    if (rc) return rc;
+    memcpy(e_win.at(h), wins.data(), e_win.bytes());
+    HIP_TRY(ctx, hipMemcpyAsync(e_win.at(blk), e_win.at(h), e_win.bytes(), hipMemcpyHostToDevice, ctx->stream));
+    const KfmOut Q = {e_th.at(blk), e_tc.at(blk), e_px.at(blk), e_pi.at(blk), e_li.at(blk), e_pr.at(blk), e_lr.at(blk), e_ok.at(blk), e_op.at(blk), e_ic.at(blk)};
+    { ProfScope span(ctx, "kfmap_gather_emit");
+      hipLaunchKernelGGL(k_kfm_emit, dim3((maxM + 255) / 256, nw), dim3(256), 0, ctx->stream, V, (const KfmWin *)e_win.at(blk), Q); }
+    HIP_TRY(ctx, hipGetLastError());
+    std::vector<int32_t> wst((size_t)nw, 0);
+    std::vector<double> wsv((size_t)nw * 8, 0.0);
+    rc = slam_local_ba_batch_dev(ctx, nw, cw.data(), Pn.data(), Mn.data(), On.data(), e_th.at(blk), e_tc.at(blk), e_px.at(blk), e_pi.at(blk), e_li.at(blk), e_ol.at(blk),
+                                 iters_fast, iterations, repr_eps, wsv.data(), wst.data());
+    if (rc) return rc;
+    // the in-call host route of the windows the device batch does not take
+    std::vector<int> hostw;
+    for (int w = 0; w < nw; w++) if (wst[w] == SLAM_BA_DEV_INELIGIBLE) hostw.push_back(w);
+    if (!hostw.empty()) {
+        const int nh = (int)hostw.size();
+        std::vector<int32_t> hP(nh), hM(nh), hO(nh), hst(nh, 0);
+        std::vector<double> hc, hsv((size_t)nh * 8, 0.0);
+        size_t tT = 0, tP = 0, tO = 0;
+        for (int k = 0; k < nh; k++) { const int w = hostw[k]; hP[k] = Pn[w]; hM[k] = Mn[w]; hO[k] = On[w]; hc.insert(hc.end(), cw.begin() + 4 * w, cw.begin() + 4 * w + 4); tT += 6 * (size_t)Pn[w] + 3 * (size_t)Mn[w]; tP += Pn[w]; tO += On[w]; }
+        std::vector<double> th(tT + 1), px(2 * tO + 2);
+        std::vector<uint8_t> tc(tP + 1), ol(tO + 1, 0);
+        std::vector<int64_t> pi(tO + 1), li(tO + 1);
+        size_t aT = 0, aP = 0, aO = 0;
+        for (int k = 0; k < nh; k++) {
+            const int w = hostw[k]; const size_t n = 6 * (size_t)Pn[w] + 3 * (size_t)Mn[w], O = On[w];
+            HIP_TRY(ctx, hipMemcpyAsync(th.data() + aT, e_th.at(blk) + wins[w].theta0, n * 8, hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(ctx, hipMemcpyAsync(tc.data() + aP, e_tc.at(blk) + wins[w].pose0, (size_t)Pn[w], hipMemcpyDeviceToHost, ctx->stream));
+            if (O) {
+                HIP_TRY(ctx, hipMemcpyAsync(px.data() + 2 * aO, e_px.at(blk) + 2 * (size_t)wins[w].obs0, O * 16, hipMemcpyDeviceToHost, ctx->stream));
+                HIP_TRY(ctx, hipMemcpyAsync(pi.data() + aO, e_pi.at(blk) + wins[w].obs0, O * 8, hipMemcpyDeviceToHost, ctx->stream));
+                HIP_TRY(ctx, hipMemcpyAsync(li.data() + aO, e_li.at(blk) + wins[w].obs0, O * 8, hipMemcpyDeviceToHost, ctx->stream));
+            }
+            aT += n; aP += Pn[w]; aO += O;
+        }
+        HIP_TRY(ctx, slam_stream_wait(ctx->stream));
+        rc = slam_local_ba_batch(ctx, nh, hc.data(), hP.data(), hM.data(), hO.data(), th.data(), tc.data(), px.data(), pi.data(), li.data(), ol.data(),
+                                 iters_fast, iterations, repr_eps, hsv.data(), hst.data());
+        if (rc) return rc;
+        aT = 0; aO = 0;
+        for (int k = 0; k < nh; k++) {
+            const int w = hostw[k]; const size_t n = 6 * (size_t)Pn[w] + 3 * (size_t)Mn[w], O = On[w];
+            wst[w] = hst[k]; memcpy(wsv.data() + 8 * (size_t)w, hsv.data() + 8 * (size_t)k, 64);
+            if (hst[k] == SLAM_OK) {
+                HIP_TRY(ctx, hipMemcpyAsync(e_th.at(blk) + wins[w].theta0, th.data() + aT, n * 8, hipMemcpyHostToDevice, ctx->stream));
+                if (O) HIP_TRY(ctx, hipMemcpyAsync(e_ol.at(blk) + wins[w].obs0, ol.data() + aO, O, hipMemcpyHostToDevice, ctx->stream));
+            }
+            aT += n; aO += O;
+        }
+        HIP_TRY(ctx, slam_stream_wait(ctx->stream));             // (the host vectors end with this scope)
+    }
+    // the update, for the windows that were solved: the existing kernels on the arrays where they lie
+    KfmUpd *uh = (KfmUpd *)e_upd.at(h);                          // (the pinned block: its earlier copy has completed -- the batch waited)
+    int nu = 0, umaxM = 1;
+    for (int w = 0; w < nw; w++) {
+        const int s = wins[w].s;
+        status[s] = wst[w];
+        if (stats) memcpy(stats + 8 * (size_t)s, wsv.data() + 8 * (size_t)w, 64);
+        if (wst[w] != SLAM_OK) continue;
+        uh[nu++] = {s, wins[w].theta0, (long long)wins[w].obs0};
+        umaxM = std::max(umaxM, (int)Mn[w]);
+    }
+    if (nu == 0) return SLAM_OK;
+    HIP_TRY(ctx, hipMemcpyAsync(e_upd.at(blk), uh, (size_t)nu * sizeof(KfmUpd), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(km->pin_ev, ctx->stream));
+    rc = kfmap_update_enqueue(ctx, km, ks, e_upd.at(blk), nu, umaxM, e_th.at(blk), e_ol.at(blk));
+    if (rc) return rc;
+    for (int k = 0; k < nu; k++) km->pend[uh[k].s].valid = 0;
+    return SLAM_OK;
+}
+// P, M, O of the window each stream had in the last slam_kfmap_local_ba (zeros: none), S x 3 ints; host bookkeeping, no device work
+int slam_kfmap_last_windows(slam_kfmap *km, int32_t *pmo)
+{
+    if (!km || !pmo) return SLAM_ERR_ARG;
+    for (int s = 0; s < km->v.S; s++) for (int k = 0; k < 3; k++) pmo[3 * s + k] = km->last_win[s][k];
     return SLAM_OK;
 }
 

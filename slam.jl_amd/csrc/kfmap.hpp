@@ -221,4 +221,6 @@ struct slam_kfmap {
     int lm_np[128] = {};                  // pairs per stream in the result block of the last local-map match, until a merge has consumed them
     char *mg_base = nullptr; size_t mg_bytes = 0; KfmMerge mg = {};       // the merge's scratch
     char *hs_base = nullptr; size_t hs_bytes = 0; KfmHist hs = {};        // the local-map history (nullptr: off)
+    char *ba_base = nullptr; size_t ba_bytes = 0;                         // slam_kfmap_local_ba: the windows' arrays in HBM (grow-only)
+    int last_win[128][3] = {};            // P, M, O of the window each stream had in the last slam_kfmap_local_ba (0s: none)
 };

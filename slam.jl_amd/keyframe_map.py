@@ -116,6 +116,27 @@ class KeyframeMap:
         ol = np.ascontiguousarray(np.concatenate([np.asarray(o).astype(np.uint8).reshape(-1) for o in outliers] + [np.zeros(1, dtype=np.uint8)]))
         c.check(c.lib.slam_kfmap_ba_update(c.h, self.h, ks.h if ks is not None else None, len(streams), L.ptr(streams, L.i32p), L.ptr(th), L.ptr(ol, L.u8p)))
 
+    def local_ba(self, min_cov_score, cams, ks=None, iters_fast=5, iterations=10, repr_eps=5.0, ctx=None):
+        """The estimator step in one call, the windows never leaving HBM (`slam_kfmap_local_ba`): what gather -> bundle_adjustment_batch_ ->
+        update(ks) do for the streams of the last add_keyframe.  cams: one (fx, fy, cx, cy) / Camera or S of them.  -> (status, stats): per stream
+        0 solved and applied, 1 no window, 3 not selected, SLAM_ERR_NUMERIC (-5: the map untouched for that stream); stats (S, 8) as
+        `slam_local_ba_batch`'s.  `last_windows()` has the windows' sizes."""
+        c = ctx or self.ctx
+        S = self.S
+        minc = _per_stream(min_cov_score, np.int32, S)
+        one = hasattr(cams, "intrinsics") or np.ndim(cams) == 1
+        cm = np.ascontiguousarray([(q.intrinsics if hasattr(q, "intrinsics") else q) for q in ([cams] * S if one else cams)], dtype=np.float64).reshape(S, 4)
+        status = np.zeros(S, dtype=np.int32); stats = np.zeros((S, 8))
+        c.check(c.lib.slam_kfmap_local_ba(c.h, self.h, ks.h if ks is not None else None, L.ptr(minc, L.i32p), L.ptr(cm), int(iters_fast), int(iterations),
+                                          float(repr_eps), L.ptr(status, L.i32p), L.ptr(stats)))
+        return status, stats
+
+    def last_windows(self):
+        """(S, 3) P, M, O of the window every stream had in the last local_ba (zeros: none)"""
+        pmo = np.zeros((self.S, 3), dtype=np.int32)
+        self.ctx.check(self.ctx.lib.slam_kfmap_last_windows(self.h, L.ptr(pmo, L.i32p)))
+        return pmo
+
     def filter(self, filtering_ratio, min_cov_score, first_kfid=20, want_removed=True, ctx=None):
         """map_filtering! (src/estimator.jl:358-406) for the streams of the last add_keyframe: a covisible key-frame with fewer than
         min_cov_score // 2 3-D points, or with more than filtering_ratio of them seen by more than four key-frames, is removed.
