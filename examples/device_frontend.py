@@ -15,6 +15,7 @@ lock-stepped stereo streams with every keypoint list resident in HBM -- the call
     --merge: after local_map_match KeyframeMap.merge(ks) applies the match's pairs to the map and the lists, before the gather  (merge_matches)
     --descriptor-rows D: KeyframeMap.enable_descriptor_rows(D); a point keeps one row per key-frame, the match takes the minimum over all pairs of rows  (keyframes_descriptors)
     --local-map-history: KeyframeMap.enable_local_map_history; the match keeps every key-frame's local map and takes in the oldest covisible one's  (frame.local_map_ids)
+    --map-triangulation: with --local-ba KeyframeMap.add_keyframe moves up behind the stereo triangulate and KeyframeMap.triangulate_temporal(ks) replaces KeypointSet.triangulate_temporal  (triangulate_temporal! on the map)
 
 No host keypoint arrays anywhere; per frame the host receives S poses, S status words and S list lengths.  It is an
 array-level driver, not SLAM (no relocalisation; the local-map match of --local-map-match is followed by its merges only with --merge): what it shows is that the seams compose -- on a rigid synthetic
@@ -46,7 +47,12 @@ shared -- so --adaptive-keyframes alone takes a key-frame FOR ALL streams when A
 stream follow its own rule: the key-frame seams run under KeypointSet.selected(required), which restricts them to the streams that asked
 (slam_kpset_select), and the key-frame bookkeeping (last key-frame, its nb_3d_kpts, its pose, the observer ring, the key-frame id) is per stream.
 
-    python examples/device_frontend.py --frames 12 --streams 4 [--adaptive-keyframes | --per-stream-keyframes] [--local-ba [--device-ba] [--map-filtering [--filter-from K]] [--local-map-match [--merge] [--local-map-history] [--descriptor-rows D]]]
+With --map-triangulation (requires --local-ba) the temporal triangulation reads the map instead of a host table of poses: the key-frame is recorded
+right after the stereo triangulation, and every 2-D point of it is triangulated against its first observer as the map knows it NOW -- the smallest
+key-frame id among the point's observers after every removal -- with the pose the last bundle adjustment left in the map, not the pose the key-frame was
+taken with.  The kf_cw ring of the host is then not read; a rejected observation leaves the map while the list keeps the keypoint.
+
+    python examples/device_frontend.py --frames 12 --streams 4 [--adaptive-keyframes | --per-stream-keyframes] [--local-ba [--map-triangulation] [--device-ba] [--map-filtering [--filter-from K]] [--local-map-match [--merge] [--local-map-history] [--descriptor-rows D]]]
 """
 import argparse
 import contextlib
@@ -62,7 +68,7 @@ from slam_jl_amd import synthetic as syn  # noqa: E402
 
 
 def run(lefts, rights, cam, baseline, kf_every=4, max_keypoints=300, seed=0, ctx=None, verbose=False, adaptive=False, probe=None, per_stream=False, local_ba=False,
-        map_filtering=False, filter_from=20, map_probe=None, local_map_match=False, merge=False, local_map_history=False, descriptor_rows=0, device_ba=False):
+        map_filtering=False, filter_from=20, map_probe=None, local_map_match=False, merge=False, local_map_history=False, descriptor_rows=0, device_ba=False, map_triangulation=False):
     """lefts / rights: per stream a list of float images in [0, 1] (H, W).  Returns per frame a dict with the S poses
     (world -> camera, world = the first frame's camera), status words, list lengths and the wall time.
     adaptive: frame 0 is a key-frame; after the pose of every later frame the lists' statistics (KeypointSet.frame_stats, flags = 1) go
@@ -89,7 +95,12 @@ def run(lefts, rights, cam, baseline, kf_every=4, max_keypoints=300, seed=0, ctx
     replace-or-union rule and takes in the oldest covisible key-frame's stored set (mapper.jl:274-286); max_local is then the table's size (sets grow along
     that chain; status 2 cannot occur).  KeyframeMap.local_map_ids(s, kfid) reads a stored set back.
     device_ba (needs local_ba): the estimator step is add_keyframe -> KeyframeMap.local_ba(ks): the windows are emitted, solved (slam_local_ba_batch_dev) and
-    applied where they lie in HBM; `ba` is built from the call's stats and KeyframeMap.last_windows(); map_probe's "solved" stage is not called."""
+    applied where they lie in HBM; `ba` is built from the call's stats and KeyframeMap.last_windows(); map_probe's "solved" stage is not called.
+    map_triangulation (needs local_ba): KeyframeMap.add_keyframe runs right behind the stereo triangulate (map_probe's "lists" and "added" stages with it) and
+    KeyframeMap.triangulate_temporal(cam, ks=ks) stands where KeypointSet.triangulate_temporal stood; those rows carry `tri`: the (S, 4) counts (candidates,
+    triangulated, observations removed, skipped), and map_probe is called with ("triangulated", km, counts).  Every other call is where it was."""
+    if map_triangulation and not local_ba:
+        raise ValueError("map_triangulation needs local_ba: the triangulation reads the local BA's key-frame map")
     if device_ba and not local_ba:
         raise ValueError("device_ba needs local_ba: it is the local BA's estimator step with the windows kept in HBM")
     if map_filtering and not local_ba:
@@ -188,13 +199,22 @@ def run(lefts, rights, cam, baseline, kf_every=4, max_keypoints=300, seed=0, ctx
                 ks.stereo_match(cur, rpyr, params, sp_right, prior=2, ctx=ctx)
                 Twc = np.stack([np.linalg.inv(Tcw[s]) for s in range(S)])
                 ks.triangulate(cam, cam, T21, Twc, max_error=params.max_reprojection_error, ctx=ctx)
-                if (kfid[kf_mask] > 0).any():                               # mapper.jl:86: 2-D keypoints left over, against their first observers
-                    ks.triangulate_temporal(slam.stream_params(S, cam=cam), kf_cw, Twc, kfid, max_error=params.max_reprojection_error, ctx=ctx)
-                if km is not None:                                          # local_bundle_adjustment! (estimator.jl:317-347) of the streams that took the key-frame
-                    notify = map_probe or (lambda *a: None)
+                notify = map_probe or (lambda *a: None)
+                if map_triangulation:                                       # the map's copy of the key-frame first, as the reference's mapper has it
                     notify(i, "lists", ks, kf_mask.copy(), Tcw.copy())
                     km.add_keyframe(ks, slam.stream_params(S, Tcw=Tcw, cam=cam), ctx=ctx)
                     notify(i, "added", km)
+                if (kfid[kf_mask] > 0).any():                               # mapper.jl:86: 2-D keypoints left over, against their first observers
+                    if map_triangulation:                                   # the observers, their pixels and their refined poses are the map's
+                        decision["tri"] = km.triangulate_temporal(cam, ks=ks, max_error=params.max_reprojection_error, ctx=ctx)
+                        notify(i, "triangulated", km, decision["tri"])
+                    else:
+                        ks.triangulate_temporal(slam.stream_params(S, cam=cam), kf_cw, Twc, kfid, max_error=params.max_reprojection_error, ctx=ctx)
+                if km is not None:                                          # local_bundle_adjustment! (estimator.jl:317-347) of the streams that took the key-frame
+                    if not map_triangulation:
+                        notify(i, "lists", ks, kf_mask.copy(), Tcw.copy())
+                        km.add_keyframe(ks, slam.stream_params(S, Tcw=Tcw, cam=cam), ctx=ctx)
+                        notify(i, "added", km)
                     if local_map_match:                                     # update_frame_covisibility! + match_local_map! (mapper.jl:118-133), before add_new_kf!
                         km.add_descriptors(desc.data_ptr(), info.data_ptr(), dcap, ctx=ctx)
                         notify(i, "described", desc, info, dcap)
@@ -236,6 +256,9 @@ def run(lefts, rights, cam, baseline, kf_every=4, max_keypoints=300, seed=0, ctx
                   f"t = {np.round(Tcw[0][:3, 3], 3).tolist()} {row['ms']:.2f} ms")
             for s_, P_, M_, O_, no_, e0_, e1_ in row.get("ba", []):
                 print(f"          local BA stream {s_}: window of {P_} poses, {M_} points, {O_} observations; {no_} outliers, ssr {e0_:.3f} -> {e1_:.3f}")
+            if "tri" in row:
+                print(f"          temporal triangulation on the map: candidates {row['tri'][:, 0].tolist()}, triangulated {row['tri'][:, 1].tolist()}, "
+                      f"observations removed {row['tri'][:, 2].tolist()}, skipped {row['tri'][:, 3].tolist()}")
             if "lmm" in row:
                 print(f"          local-map match: status {row['lmm'][0].tolist()}, pairs per stream {[len(p) for p in row['lmm'][1]]}")
             if "merged" in row:
@@ -273,6 +296,7 @@ def main():
     ap.add_argument("--merge", action="store_true", help="apply the local-map match's pairs to the map and the lists (merge_matches); requires --local-map-match")
     ap.add_argument("--descriptor-rows", type=int, default=0, metavar="D", help="keep one descriptor row per key-frame and point, at most D = 2 .. 8 (keyframes_descriptors): merges hand rows over, removed observations drop theirs, the match reads all of them; requires --local-map-match")
     ap.add_argument("--local-map-history", action="store_true", help="keep every key-frame's local map on the device and let the match take in the oldest covisible key-frame's (frame.local_map_ids, match_local_map!); requires --local-map-match")
+    ap.add_argument("--map-triangulation", action="store_true", help="triangulate the key-frame's 2-D points from the key-frame map (its first observers as they are now, its refined poses) instead of the host's pose table; requires --local-ba")
     ap.add_argument("--filter-from", type=int, default=20, help="first key-frame id at which the filter acts (the reference's literal 20)")
     ap.add_argument("--replay-dir", default=None, help="write stream s's camera positions to DIR/stream_s as a ReplaySaver dump (src/io/saver.jl)")
     args = ap.parse_args()
@@ -280,6 +304,8 @@ def main():
         ap.error("--device-ba requires --local-ba")
     if args.map_filtering and not args.local_ba:
         ap.error("--map-filtering requires --local-ba")
+    if args.map_triangulation and not args.local_ba:
+        ap.error("--map-triangulation requires --local-ba")
     if args.local_map_match and not args.local_ba:
         ap.error("--local-map-match requires --local-ba")
     if args.merge and not args.local_map_match:
@@ -292,7 +318,7 @@ def main():
     lefts, rights, offs = synthetic_scene(args.streams, args.frames, disparity=disparity)
     out, n3 = run(lefts, rights, cam, baseline, verbose=True, adaptive=args.adaptive_keyframes, per_stream=args.per_stream_keyframes, local_ba=args.local_ba,
                   map_filtering=args.map_filtering, filter_from=args.filter_from, local_map_match=args.local_map_match, merge=args.merge,
-                  local_map_history=args.local_map_history, descriptor_rows=args.descriptor_rows, device_ba=args.device_ba)
+                  local_map_history=args.local_map_history, descriptor_rows=args.descriptor_rows, device_ba=args.device_ba, map_triangulation=args.map_triangulation)
     Z = cam[0] * baseline / disparity
     for s in range(args.streams):
         o = offs[s][-1] - offs[s][0]
@@ -302,6 +328,8 @@ def main():
         if args.local_ba:
             n_win = sum(1 for r in out for w in r.get("ba", []) if w[0] == s)
             print(f"stream {s}: {n_win} local-BA windows solved, motion error {np.abs(got - want).max():.4f} m")
+        if args.map_triangulation:
+            print(f"stream {s}: the map triangulated {sum(int(r['tri'][s, 1]) for r in out if 'tri' in r)} points and removed {sum(int(r['tri'][s, 2]) for r in out if 'tri' in r)} observations")
         if args.local_map_match:
             print(f"stream {s}: local-map match found {sum(len(r['lmm'][1][s]) for r in out if 'lmm' in r)} pairs over {sum(1 for r in out if 'lmm' in r)} key-frames")
         if args.merge:

@@ -634,6 +634,28 @@ int slam_kfmap_enable_descriptor_rows(slam_ctx *ctx, slam_kfmap *km, int max_row
  * capacity error (n_points is set); a map without rows: an argument error.  Synchronous. */
 int slam_kfmap_download_descriptor_rows(slam_ctx *ctx, slam_kfmap *km, int s, int64_t *ids, uint8_t *described, int32_t *row_off, int32_t *keys,
                                         uint64_t *rows, int cap_points, int cap_rows, int32_t *n_points, int32_t *dropped);
+/* triangulate_temporal! (mapper.jl:185-262) from the map's own key-frames, for the streams the last slam_kfmap_add_keyframe acted on (call it after
+ * that seam: the reference runs it on the map's copy of the new key-frame).  Every input is in HBM: the slabs' undistorted pixels, the key-frames'
+ * theta AS THE LAST BUNDLE ADJUSTMENT LEFT IT, the observer masks, the table's flags; cams[4 s ..] = fx fy cx cy of stream s.  With k the newest
+ * key-frame of a stream, every live observation of its slab:
+ *   1  is skipped if its point is missing (the entry carries another id), removed, or 3-D already (get_2d_keypoints, :208-211);
+ *   2  is skipped if its point has fewer than two observers (:215) or if the FIRST observer -- the smallest key-frame id among the point's
+ *      observers as they are now, after every removal, ring reuse and outlier tombstone -- is k itself (:217);
+ *   3  is skipped if the first observer's slab does not hold the id alive (:234-235);
+ *   4  else the pair (first observer's stored pixel, k's stored pixel) is triangulated exactly as slam_kpset_triangulate_temporal does it (the DLT,
+ *      both depth gates, both reprojection gates; a failed gate counts only when the rotation-compensated parallax exceeds min_parallax), with
+ *      rel_pose = observer.cw * frame.wc from the two thetas and the closed-form rigid inverse;
+ *   accepted (update_mappoint!): the point's position becomes observer.wc * X and it becomes 3-D (`ba` is not set); ks != NULL: the list slot that
+ *      carries the id now (found by binary search: a merge may have moved it; an id the list no longer holds is no error) takes xyz and is_3d = 1;
+ *   rejected (remove_mappoint_obs!(map, id, k)): k's observation becomes a tombstone, the point loses observer k, with descriptor rows the row keyed
+ *      k goes.  THE LIVE LIST KEEPS THE KEYPOINT, as the reference's current frame does -- unlike slam_kpset_triangulate_temporal, which compacts it away.
+ * Deviations: the list keeps a rejected keypoint; no remove_mappoint_obs! clean-up for a missing point (rule 1), as elsewhere in the map; the first
+ * observer is the smallest id (the reference's observers are an ordered set, of which this is the first).  ks == NULL: the lists are the host's
+ * business (their is_3d and xyz do not follow).  An unselected stream's map and list are untouched.  counts (nullable) [S x 4]: candidates after
+ * rule 1, triangulated, observations removed, skipped by rules 2-3; zeros for a stream the call did not act on.  counts == NULL: enqueue-only; else
+ * one copy of S x 4 ints and one wait.  Legal between a gather and its update: the pending window is untouched. */
+int slam_kfmap_triangulate_temporal(slam_ctx *ctx, slam_kfmap *km, slam_kpset *ks /* nullable */, const double *cams /* S x 4: fx fy cx cy */,
+                                    double max_error, double min_depth, double min_parallax, int32_t *counts /* S x 4, nullable */);
 
 /* ---- one live stream, one call per frame (round 6) -----------------------------------------------------------------------------------
  * What run!() does per frame (src/front_end.jl:58-113: preprocess! :454-470 = copy!(previous_pyramid, current_pyramid) + update!,

@@ -120,6 +120,7 @@ SIGNATURES = {
     "slam_kfmap_download_local_map_ids": (cint, [vp, vp, cint, cint, i64p, cint, i32p]),
     "slam_kfmap_enable_descriptor_rows": (cint, [vp, vp, cint]),
     "slam_kfmap_download_descriptor_rows": (cint, [vp, vp, cint, i64p, u8p, i32p, i32p, u64p, cint, cint, i32p, i32p]),
+    "slam_kfmap_triangulate_temporal": (cint, [vp, vp, vp, f64p, dbl, dbl, dbl, i32p]),
     "slam_kpset_compute_pose": (cint, [vp, vp, f64p, dbl, cint, C.c_uint64, cint, cint, dbl, dbl, f64p, i32p, i32p, i32p]),
     "slam_local_ba": (cint, [vp, dbl, dbl, dbl, dbl, cint, cint, cint, f64p, u8p, f64p, i64p, i64p, u8p, cint, cint, dbl, f64p]),
     "slam_local_ba_batch": (cint, [vp, cint, f64p, i32p, i32p, i32p, f64p, u8p, f64p, i64p, i64p, u8p, cint, cint, dbl, f64p, i32p]),

@@ -110,6 +110,29 @@ __device__ __forceinline__ bool two_view_gates(const double *L, const double *T2
     return ok;
 }
 
+// The per-pair body of triangulate_temporal! (mapper.jl:236-259), the one copy of k_kpset_tri_temporal (kpset.hip) and k_kfm_tri_temporal (kfmap_tri.inc):
+// (y1, x1) = obup, the first observer's undistorted pixel, (y2, x2) = kpup, the frame's; E = the observer's 64 doubles, column-major 4 x 4 each:
+// P2 = K * rel_pose_inv | rel_pose_inv | rel_pose = observer.cw * frame.wc | observer.wc.  A failed gate counts only when the rotation-compensated
+// parallax exceeds min_parallax.  Returns the verdict; accepted: W = observer.wc * X (project_camera_to_world(observer_kf, .)).
+__device__ __forceinline__ bool temporal_pair(const double *cam, const double *E, double y1, double x1, double y2, double x2,
+                                              double max_error, double min_depth, double min_parallax, double *W)
+{
+    const double *P2 = E, *T21 = E + 16, *REL = E + 32, *WOB = E + 48;
+    const double fx = cam[0], fy = cam[1], cx = cam[2], cy = cam[3];
+    double qy, qx;
+    // parallax = |obup - project(camera, R(rel_pose) * kp.position)|, :236-237
+    rotate_project<4>(REL, cam, (x2 - cx) / fx, (y2 - cy) / fy, qy, qx);
+    const double pdy = y1 - qy, pdx = x1 - qx;
+    const bool gated = sqrt(pdy * pdy + pdx * pdx) > min_parallax;
+    // P1 = K * I
+    const double P1[16] = {fx, 0, 0, 0, 0, fy, 0, 0, cx, cy, 1, 0, 0, 0, 0, 1};
+    double L[4];
+    dlt_two_view(x1, y1, x2, y2, P1, P2, L);
+    const bool ok = two_view_gates(L, T21, cam, cam, x1, y1, x2, y2, max_error, min_depth, gated);
+    if (ok) for (int r = 0; r < 3; r++) W[r] = ((WOB[r] * L[0] + WOB[r + 4] * L[1]) + WOB[r + 8] * L[2]) + WOB[r + 12] * L[3];
+    return ok;
+}
+
 // ---- per-problem range of the RANSAC argument blocks: problem z owns [off[z], off[z + 1]), or, in the keypoint-set layout
 // (cnt != nullptr), [z * stride, z * stride + cnt[z]) ----------------------------------------------------------------------------------
 struct ProblemRange { int base, n; };

@@ -7,7 +7,8 @@
 // (src/map_manager.jl:184-209); tests/np_kfmap_filter.py is their model.  The descriptor store and slam_kfmap_local_map_match (update_frame_covisibility! +
 // match_local_map!, staged on the device for localmap.hip's match kernel) are in kfmap_lmm.inc, included at the end: they use the routines below.
 // slam_kfmap_merge (merge_matches -> merge_mappoints -> update_keypoint!: the match's pairs applied in HBM, the touched slabs and lists rebuilt in id
-// order) is in kfmap_merge.inc, included behind it.  The integer logic -- where an id lives, the search in a slab, every serial decision over a ring's slots --
+// order) is in kfmap_merge.inc, included behind it; slam_kfmap_triangulate_temporal (triangulate_temporal! from the map's own observers and refined poses) in
+// kfmap_tri.inc, behind that.  The integer logic -- where an id lives, the search in a slab, every serial decision over a ring's slots --
 // is kfmap_ring.hpp's, host and device (tested on the CPU); the routines every kernel shares (kfm_owned, kfm_slab_point, kfm_each_observer, kfm_live_observers,
 // kfm_tcw) and every host seam shares (kfmap_upload, kfmap_alloc_zeroed, kfmap_put_streams) are below, one copy each.
 //
@@ -528,13 +529,13 @@ static int kfmap_pin(slam_ctx *ctx, slam_kfmap *km, size_t bytes, char **out)
     return SLAM_OK;
 }
 // An enqueue-only call's inputs: `bytes` of the map's pinned block, filled by fill(h), copied to scratch (*scr) on the stream, pin_ev recorded behind the
-// copy.  Nothing waits.
-template <class Fill> static int kfmap_upload(slam_ctx *ctx, slam_kfmap *km, size_t bytes, char **scr, Fill fill)
+// copy.  Nothing waits.  room > bytes: the scratch block is that long (the call's device-only regions lie behind its inputs).
+template <class Fill> static int kfmap_upload(slam_ctx *ctx, slam_kfmap *km, size_t bytes, char **scr, Fill fill, size_t room = 0)
 {
     char *h;
     int rc = kfmap_pin(ctx, km, bytes, &h);
     if (rc) return rc;
-    rc = slam_scratch(ctx, bytes, (void **)scr);
+    rc = slam_scratch(ctx, std::max(bytes, room), (void **)scr);
     if (rc) return rc;
     fill(h);
     HIP_TRY(ctx, hipMemcpyAsync(*scr, h, bytes, hipMemcpyHostToDevice, ctx->stream));
@@ -1037,3 +1038,4 @@ int slam_kfmap_reset(slam_ctx *ctx, slam_kfmap *km, int s)
 
 #include "kfmap_lmm.inc"
 #include "kfmap_merge.inc"
+#include "kfmap_tri.inc"

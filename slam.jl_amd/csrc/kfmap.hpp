@@ -109,6 +109,15 @@
 //                 recorded as a fresh point (the reference always has the current frame at hand)
 //   orphans       pop!(map_points, prev_id) is not remove_mappoint!: where a slab holds both ids (has_new) prev's observation stays, alive, without a point
 //   tombstones    a tombstone whose id equals an arriving new_id is dropped from the slab (a lower bound must not land on it); the slab shrinks by one
+//
+// Temporal triangulation (slam_kfmap_triangulate_temporal, kfmap_tri.inc; no allocation: S R 64 doubles of observer matrices and 4 S counters in the
+// context's scratch): triangulate_temporal! (mapper.jl:185-262) for the newest key-frame's 2-D points, each against its FIRST observer as the mask names it
+// now (kfm_first_observer, kfmap_ring.hpp) and with both poses from ktheta, i.e. as the last bundle adjustment left them.  Accepted: pxyz, KFM_3D (not
+// KFM_BA), and the list slot that carries the id (binary search).  Rejected: a tombstone in the newest slab, observer bit cleared, with rows the row keyed k.
+// Deviations from the reference:
+//   list          the live list KEEPS a rejected keypoint, as the reference's current frame does (slam_kpset_triangulate_temporal compacts it away)
+//   clean-ups     no remove_mappoint_obs! clean-up for a missing point (mapper.jl:209-210), as elsewhere in the map: an orphan is skipped and left as it is
+//   first         the first observer is the smallest key-frame id among the point's valid observer bits (the reference's observers are an ordered set)
 #pragma once
 #include "kpset.hpp"
 #include "kfmap_ring.hpp"

@@ -99,6 +99,17 @@ KFM_HD static inline int kfm_oldest_covisible(unsigned long long covmask, const 
     for (unsigned long long cm = covmask; cm; cm &= cm - 1) { const int b = __builtin_ctzll(cm); if (oldest < 0 || tag[b] < tag[oldest]) oldest = b; }
     return oldest;
 }
+// triangulate_temporal!'s get_observers(mp)[1] (mapper.jl:214-216): among the bits of `mask` that mean something (below R, their slot with a tag) the slot
+// of the smallest key-frame id; -1 where fewer than two bits mean something (`length(observers) < 2 && continue`)
+KFM_HD static inline int kfm_first_observer(unsigned long long mask, const int *tag, int R)
+{
+    int first = -1, n = 0;
+    for (unsigned long long mm = mask; mm; mm &= mm - 1) {
+        const int b = __builtin_ctzll(mm);
+        if (b < R && tag[b]) { n++; if (first < 0 || tag[b] < tag[first]) first = b; }
+    }
+    return n >= 2 ? first : -1;
+}
 // map_manager.jl:350-354 and mapper.jl:274-286 on the sizes nC = |C|, nP = |P|, nU = |P | C|: replace: L = C (len(C) > 0.5 len(P), exact in integers),
 // else L = P | C; chain: the oldest covisible key-frame's set is united in (a covisible key-frame, |L| < max_local, that slot's set its own).
 // Returns |L| before the chain.

@@ -164,22 +164,11 @@ __device__ __forceinline__ void k_kpset_tri_temporal_slot(const KpsetView &K, co
     if (kf == T.kf_cur[s] || kf < T.kf_lo[s]) return;            // :216 the frame itself is the first observer; observer no longer in the table
     const double *par = T.par + KP_PAR * (size_t)s, *cam = par + KP_PAR_CAM, *dist = par + KP_PAR_DIST;
     const double *E = T.tab + ((size_t)s * T.nkf + (kf % T.nkf)) * 64;
-    const double *P2 = E, *T21 = E + 16, *REL = E + 32, *WOB = E + 48;
-    const double fx = cam[0], fy = cam[1], cx = cam[2], cy = cam[3];
-    double y1, x1, y2, x2, qy, qx;
+    double y1, x1, y2, x2, W[3];
     undistort_px(cam, dist, K.fyx[2 * q], K.fyx[2 * q + 1], y1, x1);  // obup
     undistort_px(cam, dist, K.yx[2 * q], K.yx[2 * q + 1], y2, x2);    // kpup
-    // parallax = |obup - project(camera, R(rel_pose) * kp.position)|, :236-237
-    rotate_project<4>(REL, cam, (x2 - cx) / fx, (y2 - cy) / fy, qy, qx);
-    const double pdy = y1 - qy, pdx = x1 - qx;
-    const bool gated = sqrt(pdy * pdy + pdx * pdx) > T.min_parallax;
-    // P1 = K * I
-    const double P1[16] = {fx, 0, 0, 0, 0, fy, 0, 0, cx, cy, 1, 0, 0, 0, 0, 1};
-    double L[4];
-    dlt_two_view(x1, y1, x2, y2, P1, P2, L);
-    const bool ok = two_view_gates(L, T21, cam, cam, x1, y1, x2, y2, T.max_error, T.min_depth, gated);
-    if (ok) {
-        for (int r = 0; r < 3; r++) K.xyz[3 * q + r] = ((WOB[r] * L[0] + WOB[r + 4] * L[1]) + WOB[r + 8] * L[2]) + WOB[r + 12] * L[3];   // project_camera_to_world(observer_kf, .)
+    if (temporal_pair(cam, E, y1, x1, y2, x2, T.max_error, T.min_depth, T.min_parallax, W)) {     // the parallax, the DLT, the gates (geom_device.hpp)
+        for (int r = 0; r < 3; r++) K.xyz[3 * q + r] = W[r];     // project_camera_to_world(observer_kf, .)
         K.is3d[q] = 1;
     } else T.flags[q] = 1;                                        // remove_mappoint_obs!(map_manager, id, frame.kfid)
 }

@@ -488,6 +488,20 @@ function merge!(m::KeyframeMap, k::Union{Nothing, KeypointSet} = nothing; n_pair
         pairs === nothing ? Ptr{Int64}(C_NULL) : pointer(pairs), want_counts ? pointer(merged) : Ptr{Int32}(C_NULL)))
     want_counts ? merged : nothing
 end
+# triangulate_temporal! (mapper.jl:185-262) from the map's own key-frames, for the streams of the last add_keyframe! (call it right after): every 2-D
+# point of the newest key-frame against its first observer as it is now, with the poses the last bundle adjustment left in the map.  cams: 4 x S
+# (fx fy cx cy).  k: the KeypointSet whose lists take xyz and is_3d of the accepted points; a rejected keypoint STAYS in the list (triangulate_temporal!
+# of the KeypointSet drops it).  Returns the 4 x S counts (candidates, triangulated, observations removed, skipped), or nothing with
+# want_counts = false (enqueue-only).
+function triangulate_temporal!(m::KeyframeMap, cams::Matrix{Float64}, k::Union{Nothing, KeypointSet} = nothing; max_error::Real = 3.0,
+                               min_depth::Real = 0.1, min_parallax::Real = 20.0, want_counts::Bool = true)
+    size(cams) == (4, m.S) || throw(ArgumentError("cams: 4 x S"))
+    counts = zeros(Int32, 4, m.S)
+    GC.@preserve cams counts check(ccall((:slam_kfmap_triangulate_temporal, LIB[]), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Cdouble, Cdouble, Cdouble, Ptr{Int32}),
+        ctx(), m.h, k === nothing ? C_NULL : k.h, pointer(cams), max_error, min_depth, min_parallax, want_counts ? pointer(counts) : Ptr{Int32}(C_NULL)))
+    want_counts ? counts : nothing
+end
 
 # ---- one live stream, one call per frame (slam_frontend_*, include/slamhip.h): what run!()'s front-end task does per frame
 # (front_end.jl:58-113, :454-470) and, at a key-frame, create_keyframe! + the mapper's stereo step (map_manager.jl:98-113, mapper.jl:51-66, :142-183),

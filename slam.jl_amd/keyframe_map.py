@@ -157,6 +157,23 @@ class KeyframeMap:
         cur = self.newest(ctx=c)                                 # a bit names a residue: the id is the one in (cur - R, cur) with it
         return [sorted(int(cur[s]) - ((int(cur[s]) - b) % self.R) for b in range(self.R) if int(words[s]) >> b & 1) for s in range(S)]
 
+    def triangulate_temporal(self, cam, ks=None, max_error=3.0, min_depth=0.1, min_parallax=20.0, want_counts=True, ctx=None):
+        """triangulate_temporal! (src/mapper.jl:185-262) from the map's own key-frames, for the streams of the last add_keyframe (call it right
+        after): every 2-D point of the newest key-frame with an earlier observer is triangulated against its FIRST observer as it is now (the
+        smallest key-frame id among the point's observers), with the poses the last bundle adjustment left in the map.  Accepted: the point gets
+        its position and becomes 3-D, and with ks the list slot that carries its id takes xyz and is_3d.  Rejected (a gate fails with a parallax
+        above min_parallax): the newest key-frame's observation leaves the map; THE LIST KEEPS THE KEYPOINT (ks.triangulate_temporal drops it).
+        cam: one (fx, fy, cx, cy) / Camera or S of them.  -> (S, 4) int32: candidates, triangulated, observations removed, skipped (fewer than
+        two observers, or the first observer's pixel is gone) per stream (synchronous), or None with want_counts=False (enqueue-only)."""
+        c = ctx or self.ctx
+        S = self.S
+        one = hasattr(cam, "intrinsics") or np.ndim(cam) == 1
+        cm = np.ascontiguousarray([(q.intrinsics if hasattr(q, "intrinsics") else q) for q in ([cam] * S if one else cam)], dtype=np.float64).reshape(S, 4)
+        counts = np.zeros((S, 4), dtype=np.int32) if want_counts else None
+        c.check(c.lib.slam_kfmap_triangulate_temporal(c.h, self.h, ks.h if ks is not None else None, L.ptr(cm), float(max_error), float(min_depth),
+                                                      float(min_parallax), L.ptr(counts, L.i32p) if want_counts else None))
+        return counts
+
     def newest(self, ctx=None):
         """(S,) the id of every stream's newest key-frame, -1 where there is none yet"""
         c = ctx or self.ctx
