@@ -390,6 +390,26 @@ def essential_poses(E):
     return [Rt[12 * i:12 * i + 12].reshape(4, 3).T.copy() for i in range(k)]
 
 
+def essential_pose_cheirality(E, q1, q2):
+    """[R | t] (3x4) of the essential matrix E (3x3) with most of the five sample points q1, q2 (5, 2) in front of both cameras
+    (orc_essential_pose_cheirality); None if E is degenerate."""
+    E = np.ascontiguousarray(E, dtype=np.float64)
+    a = np.ascontiguousarray(q1, dtype=np.float64).reshape(5, 2); b = np.ascontiguousarray(q2, dtype=np.float64).reshape(5, 2)
+    Rt = np.zeros(12)
+    return Rt.reshape(4, 3).T.copy() if lib().orc_essential_pose_cheirality(_p(E), _p(a), _p(b), _p(Rt)) else None
+
+
+def two_view_inliers(px1_xy, px2_xy, K1, K2, Rt, max_repr_error):
+    """Per-correspondence inlier mask of ONE pose Rt (3x4) under the rule of five_point_ransac (orc_two_view_inliers)."""
+    a = np.ascontiguousarray(px1_xy, dtype=np.float64).reshape(-1, 2); b = np.ascontiguousarray(px2_xy, dtype=np.float64).reshape(-1, 2)
+    k1 = np.asfortranarray(K1, dtype=np.float64); k2 = np.asfortranarray(K2, dtype=np.float64)
+    P = np.asfortranarray(Rt, dtype=np.float64)
+    mask = np.zeros(max(len(a), 1), dtype=np.uint8)
+    cnt = lib().orc_two_view_inliers(_p(a), _p(b), len(a), _p(k1), _p(k2), _p(P), C.c_double(max_repr_error), _p(mask, u8p))
+    assert cnt == int(mask[:len(a)].sum())
+    return mask[:len(a)].astype(bool)
+
+
 def five_point_ransac(px1_xy, px2_xy, pd1_xy, pd2_xy, K1, K2, max_repr_error, samples):
     """five_point_ransac of compute_pose_5pt! (front_end.jl:305-308) over caller-supplied 0-based 5-tuples.
     Returns (n_inliers, E 3x3, P 3x4, inliers bool, error, best_iter)."""

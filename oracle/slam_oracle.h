@@ -190,6 +190,8 @@ int  orc_poly_real_roots(const double *p, int deg, double *roots);
 int  orc_five_point_solve(const double q1[10], const double q2[10], double Es[90]);
 int  orc_essential_poses(const double E[9], double Rt[48]);
 int  orc_essential_pose_cheirality(const double E[9], const double q1[10], const double q2[10], double Rt[12]);
+int  orc_two_view_inliers(const double *px1, const double *px2, int n, const double *K1, const double *K2, const double Rt[12],
+                          double max_repr_error, unsigned char *mask);
 int  orc_five_point_ransac(const double *px1, const double *px2, const double *pd1, const double *pd2, int n,
                            const double *K1, const double *K2, double max_repr_error, const int32_t *samples, int iters,
                            double *E_out, double *P_out, unsigned char *inliers, double *error, int *best_iter);

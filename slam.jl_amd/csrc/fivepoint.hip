@@ -5,9 +5,12 @@
 //   k_5pt_solve   one 16-lane team per caller-supplied 5-tuple (lane 0 owns the sequential phases, the team shares
 //                 the root search, one bracketing interval per lane): Nister's minimal solver (null space of the 5x9 system,
 //                 the ten cubics by polynomial arithmetic, Gauss-Jordan in Nister's monomial order, det B(z) of
-//                 degree 10, real roots bracketed between the derivative's roots), then Horn's closed-form pose of
-//                 each essential matrix with cheirality on the five sample points.  Only + - * / sqrt: the
-//                 hypotheses are bit-identical to the CPU statement.  The 10x20 elimination matrix and the
+//                 degree 10, real roots bracketed between the derivative's roots, back-substitution by lane 0), the polish of every
+//                 root (one root per lane: two Gauss-Newton steps on the ten constraints, then the 1e-9 gate on the unit-norm E; see
+//                 polish_root and the oracle's header for why), then Horn's closed-form pose of
+//                 each essential matrix with cheirality on the five sample points.  Only + - * / sqrt: EVERY
+//                 hypothesis is bit-identical to the CPU statement (tests/test_gpu_5pt_hypotheses.py reads them all out through
+//                 slamhip_test_five_point_hypotheses).  The 10x20 elimination matrix and the
 //                 derivative table live in LDS, one column of doubles per thread.
 //   k_5pt_score   one 256-thread workgroup per (5-tuple, pose): the threads stride over the correspondences -- DLT
 //                 triangulation (the mapper's 4x4 system, eigenvector by inverse iteration), both depths > 0, both reprojection
@@ -272,7 +275,101 @@ __device__ static bool nullspace_5x9(Col A, Col N)
     return true;
 }
 
-// LDS per 5-tuple (doubles): M 200 | N 36 | Ep 36 | W 144 (A 45, then EEt 90 + tr 10, then D 121 + crit 11 + spare 11 + degree 1)
+// The ten constraints of an essential matrix E (row-major): r[0..8] = 2 E E'E - tr(E E')E, r[9] = det E; also G = E E', its trace
+// and the cofactors C.  Same operations as the oracle's essential_constraints.
+__device__ static inline void essential_constraints(const double *E, double *r, double *G, double &tr, double *C)
+{
+#pragma unroll
+    for (int a = 0; a < 3; a++)
+#pragma unroll
+        for (int c = 0; c < 3; c++) G[3 * a + c] = (E[3 * a] * E[3 * c] + E[3 * a + 1] * E[3 * c + 1]) + E[3 * a + 2] * E[3 * c + 2];
+    tr = (G[0] + G[4]) + G[8];
+#pragma unroll
+    for (int a = 0; a < 3; a++)
+#pragma unroll
+        for (int c = 0; c < 3; c++)
+            r[3 * a + c] = 2.0 * ((G[3 * a] * E[c] + G[3 * a + 1] * E[3 + c]) + G[3 * a + 2] * E[6 + c]) - tr * E[3 * a + c];
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        const double *p = E + 3 * ((a + 1) % 3), *q = E + 3 * ((a + 2) % 3);
+        C[3 * a] = p[1] * q[2] - p[2] * q[1]; C[3 * a + 1] = p[2] * q[0] - p[0] * q[2]; C[3 * a + 2] = p[0] * q[1] - p[1] * q[0];
+    }
+    r[9] = (E[0] * C[0] + E[1] * C[1]) + E[2] * C[2];
+}
+
+// derivative of the ten constraints at E along D (the oracle's essential_constraints_d); G = E E', H = E'E, C the cofactors
+__device__ static inline void essential_constraints_d(const double *E, const double *G, double tr, const double *H, const double *C, const double *D, double *j)
+{
+    double F[9], s = 0.0, d = 0.0;
+#pragma unroll
+    for (int a = 0; a < 3; a++)
+#pragma unroll
+        for (int c = 0; c < 3; c++) F[3 * a + c] = (D[a] * E[c] + D[3 + a] * E[3 + c]) + D[6 + a] * E[6 + c];
+#pragma unroll
+    for (int i = 0; i < 9; i++) { s += E[i] * D[i]; d += C[i] * D[i]; }
+#pragma unroll
+    for (int a = 0; a < 3; a++)
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            const double u = (D[3 * a] * H[c] + D[3 * a + 1] * H[3 + c]) + D[3 * a + 2] * H[6 + c];
+            const double v = (E[3 * a] * F[c] + E[3 * a + 1] * F[3 + c]) + E[3 * a + 2] * F[6 + c];
+            const double w = (G[3 * a] * D[c] + G[3 * a + 1] * D[3 + c]) + G[3 * a + 2] * D[6 + c];
+            j[3 * a + c] = (2.0 * ((u + v) + w) - 2.0 * s * E[3 * a + c]) - tr * D[3 * a + c];
+        }
+    j[9] = d;
+}
+
+// Polish of one root (the oracle's polish_root, same operations in the same order): FP_POLISH_STEPS Gauss-Newton steps on the ten
+// constraints in (x, y, z), the 3x3 normal equations by cofactors, then the gate on the constraints of the unit-norm E.  One lane per
+// root: the basis N (4 x 9) comes from LDS, E goes to the lane's own LDS slot Eo.  Returns false when the hypothesis is dropped.
+#define FP_POLISH_STEPS 2
+#define FP_GATE 1e-9
+__device__ static bool polish_root(Col N, double x, double y, double z, Col Eo)
+{
+    double E[9], r[10], G[9], H[9], C[9], tr;
+    for (int it = 0; ; it++) {
+#pragma unroll
+        for (int e = 0; e < 9; e++) E[e] = ((x * N[e] + y * N[9 + e]) + z * N[18 + e]) + N[27 + e];
+        essential_constraints(E, r, G, tr, C);
+        if (it == FP_POLISH_STEPS) break;
+#pragma unroll
+        for (int a = 0; a < 3; a++)
+#pragma unroll
+            for (int c = 0; c < 3; c++) H[3 * a + c] = (E[a] * E[c] + E[3 + a] * E[3 + c]) + E[6 + a] * E[6 + c];
+        double a00 = 0.0, a01 = 0.0, a02 = 0.0, a11 = 0.0, a12 = 0.0, a22 = 0.0, g0 = 0.0, g1 = 0.0, g2 = 0.0;
+        double J0[10], J1[10], J2[10], D[9];
+#pragma unroll
+        for (int e = 0; e < 9; e++) D[e] = N[e];
+        essential_constraints_d(E, G, tr, H, C, D, J0);
+#pragma unroll
+        for (int e = 0; e < 9; e++) D[e] = N[9 + e];
+        essential_constraints_d(E, G, tr, H, C, D, J1);
+#pragma unroll
+        for (int e = 0; e < 9; e++) D[e] = N[18 + e];
+        essential_constraints_d(E, G, tr, H, C, D, J2);
+#pragma unroll
+        for (int i = 0; i < 10; i++) {
+            a00 += J0[i] * J0[i]; a01 += J0[i] * J1[i]; a02 += J0[i] * J2[i];
+            a11 += J1[i] * J1[i]; a12 += J1[i] * J2[i]; a22 += J2[i] * J2[i];
+            g0 += J0[i] * r[i]; g1 += J1[i] * r[i]; g2 += J2[i] * r[i];
+        }
+        const double c00 = a11 * a22 - a12 * a12, c01 = a02 * a12 - a01 * a22, c02 = a01 * a12 - a02 * a11;
+        const double c11 = a00 * a22 - a02 * a02, c12 = a01 * a02 - a00 * a12, c22 = a00 * a11 - a01 * a01;
+        const double det = (a00 * c00 + a01 * c01) + a02 * c02;
+        const double dx = ((c00 * g0 + c01 * g1) + c02 * g2) / det, dy = ((c01 * g0 + c11 * g1) + c12 * g2) / det,
+                     dz = ((c02 * g0 + c12 * g1) + c22 * g2) / det;
+        x -= dx; y -= dy; z -= dz;                        // a singular system gives a non-finite E: dropped below
+    }
+    double nn = 0.0, worst = 0.0;
+#pragma unroll
+    for (int e = 0; e < 9; e++) { nn += E[e] * E[e]; Eo[e] = E[e]; }
+#pragma unroll
+    for (int i = 0; i < 10; i++) { const double v = fabs(r[i]); if (!(v <= worst)) worst = v; }
+    return worst <= FP_GATE * (nn * sqrt(nn));
+}
+
+// LDS per 5-tuple (doubles): M 200 | N 36 | Ep 36 | W 144 (A 45, then EEt 90 + tr 10, then D 121 + crit 11 + spare 11 + degree 1, then -- over D,
+// once the roots are in crit -- (x, y, z) of each root 30 + its live flag 10)
 #define FP_LDS_PER_THREAD (200 + 36 + 36 + 144 + 9 * FP_MAXE)   /* + the essential matrices of the tuple (indexed by a run-time root count: LDS, not scratch) */
 
 // Called by all threads of the workgroup (it synchronises).  Lane l == 0 of each team owns the short sequential
@@ -390,31 +487,40 @@ __device__ static int five_point_solve(const double *q1, const double *q2, Col L
         if (fin) roots_prepare(P, 10, W);
     }
     __syncthreads();
-    const int nr = team_real_roots(W, l, team);
+    const int nr = team_real_roots(W, l, team);           // team-uniform; 0 for a dead tuple
+    // back-substitution by the owner -- (x, y, z) of root i to W[3 i ..], W[30 + i]: the root is live -- then the polish, one root per
+    // lane (the latency chain grows by one root's polish, not by ten), each lane's E in its own slot of Es; the owner compacts in root order
+    if (owner && alive) {
+        const Col zr = W.at(121);
+        for (int i = 0; i < nr; i++) {
+            const double z = zr[i];
+            double R[3][3];
+            for (int r = 0; r < 3; r++) { R[r][0] = peval(Ba[r], 3, z); R[r][1] = peval(Bb[r], 3, z); R[r][2] = peval(Bc[r], 4, z); }
+            double best = 0.0, nx = 0.0, ny = 0.0, nz = 0.0;
+            for (int a = 0; a < 2; a++)
+                for (int b = a + 1; b < 3; b++) {
+                    const double c0 = R[a][1] * R[b][2] - R[a][2] * R[b][1];
+                    const double c1 = R[a][2] * R[b][0] - R[a][0] * R[b][2];
+                    const double c2 = R[a][0] * R[b][1] - R[a][1] * R[b][0];
+                    if (fabs(c2) > best) { best = fabs(c2); nx = c0; ny = c1; nz = c2; }
+                }
+            W[30 + i] = best > 0.0 ? 1.0 : 0.0;
+            if (!(best > 0.0)) continue;
+            W[3 * i] = nx / nz; W[3 * i + 1] = ny / nz; W[3 * i + 2] = z;
+        }
+    }
+    __syncthreads();
+    if (alive && l < nr && W[30 + l] != 0.0) {
+        const bool keep = polish_root(N, W[3 * l], W[3 * l + 1], W[3 * l + 2], Es.at(9 * l));
+        W[30 + l] = keep ? 1.0 : 0.0;
+    }
+    __syncthreads();
     if (!owner || !alive) return 0;
-    const Col zr = W.at(121);
     int ne = 0;
     for (int i = 0; i < nr; i++) {
-        const double z = zr[i];
-        double R[3][3];
-        for (int r = 0; r < 3; r++) { R[r][0] = peval(Ba[r], 3, z); R[r][1] = peval(Bb[r], 3, z); R[r][2] = peval(Bc[r], 4, z); }
-        double best = 0.0, nx = 0.0, ny = 0.0, nz = 0.0;
-        for (int a = 0; a < 2; a++)
-            for (int b = a + 1; b < 3; b++) {
-                const double c0 = R[a][1] * R[b][2] - R[a][2] * R[b][1];
-                const double c1 = R[a][2] * R[b][0] - R[a][0] * R[b][2];
-                const double c2 = R[a][0] * R[b][1] - R[a][1] * R[b][0];
-                if (fabs(c2) > best) { best = fabs(c2); nx = c0; ny = c1; nz = c2; }
-            }
-        if (!(best > 0.0)) continue;
-        const double x = nx / nz, y = ny / nz;
-        bool fin = true;
-        for (int e = 0; e < 9; e++) {
-            const double ev = ((x * N[e] + y * N[9 + e]) + z * N[18 + e]) + N[27 + e];
-            Es[9 * ne + e] = ev;
-            fin = fin && isfinite(ev);
-        }
-        if (fin) ne++;
+        if (W[30 + i] == 0.0) continue;
+        if (ne != i) for (int e = 0; e < 9; e++) Es[9 * ne + e] = Es[9 * i + e];
+        ne++;
     }
     return ne;
 }
@@ -513,7 +619,8 @@ __device__ static inline void ray_depths(const double *Rt, const double *q1, con
 }
 
 // (three waves per SIMD: left to itself the allocator takes 244 registers -- one or two waves per SIMD for a kernel that is a latency chain of eliminations and
-//  root brackets; capped at 168 it spills 191 registers to scratch and is still 21 % faster: 1.02 -> 0.80 ms per 128-stream call; four waves per SIMD, 128 registers: 0.97)
+//  root brackets; capped at 168 it spilt 191 registers to scratch and was still 21 % faster: 1.02 -> 0.80 ms per 128-stream call; four waves per SIMD, 128 registers: 0.97.
+//  With the polish: 168 registers, 301 spilt, 596 bytes of scratch per lane, still three waves per SIMD)
 __global__ __launch_bounds__(FP_TPB * FP_TEAM) __attribute__((amdgpu_waves_per_eu(3))) void k_5pt_solve(FPArgs T)
 {
     extern __shared__ double s_fp[];
@@ -663,6 +770,8 @@ struct FPScratch {
           counts(L.take<int>((size_t)S * iters * FP_MAXE + (size_t)S)), errs(L.take<double>(npts)) {}
     void bind(FPArgs &T, char *scr) const { T.ne = ne.at(scr); T.Es = Es.at(scr); T.poses = poses.at(scr); T.counts = counts.at(scr); T.errs = errs.at(scr); }
 };
+// Test-only read-out of every hypothesis (slamhip_test_five_point_hypotheses): host arrays shaped like the regions above; the S incumbents go to `best`
+struct FPReadout { int *ne; double *Es, *poses; int *counts, *best; };
 // the only launch site of the three kernels (grid.y / grid.y / grid.x = problem)
 static int fp_enqueue(slam_ctx *ctx, int S, const FPArgs &T)
 {
@@ -685,7 +794,7 @@ static void fp_copy_out(const FPOut &o, int z, double *E, double *P, int *n_inli
 // S problems in one round trip through the context's mapped pinned block
 static int fp_run(slam_ctx *ctx, int S, const int32_t *off, const double *px1_xy, const double *px2_xy, const double *pd1_xy,
                   const double *pd2_xy, const double *K1, const double *K2, double max_repr_error, const int32_t *samples, int iters,
-                  double *E, double *P, uint8_t *inliers, int *n_inliers, double *error, int *best_iter)
+                  double *E, double *P, uint8_t *inliers, int *n_inliers, double *error, int *best_iter, const FPReadout *ro = nullptr)
 {
     const int ntot = off[S];
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -716,6 +825,8 @@ static int fp_run(slam_ctx *ctx, int S, const int32_t *off, const double *px1_xy
     T.px1 = o_px1.at(d); T.px2 = o_px2.at(d); T.pd1 = o_pd1.at(d); T.pd2 = o_pd2.at(d); T.samples = o_smp.at(d); T.off = o_off.at(d); T.ks = o_k.at(d);
     T.iters = iters; T.thr = max_repr_error; T.cnt = nullptr; T.stride = 0;
     ds.bind(T, scr); T.out = o_out.at(d); T.inliers = o_inl.at(d);
+    if (ro)                                                       // every byte the kernels leave alone reads 0xFF afterwards
+        HIP_TRY(ctx, hipMemsetAsync(scr + ds.ne.off, 0xFF, ds.counts.off + ds.counts.bytes() - ds.ne.off, ctx->stream));
     { ProfScope span(ctx, "five_point_ransac");
       rc = fp_enqueue(ctx, S, T);
       if (rc) return rc; }
@@ -723,6 +834,14 @@ static int fp_run(slam_ctx *ctx, int S, const int32_t *off, const double *px1_xy
     HIP_TRY(ctx, slam_stream_wait(ctx->stream));
     for (int z = 0; z < S; z++) fp_copy_out(o_out.at(h)[z], z, E, P, n_inliers, error, best_iter);
     memcpy(inliers, o_inl.at(h), o_inl.bytes());
+    if (ro) {
+        const size_t nh = (size_t)S * iters * FP_MAXE;
+        HIP_TRY(ctx, hipMemcpy(ro->ne, T.ne, (size_t)S * iters * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(ro->Es, T.Es, nh * 9 * 8, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(ro->poses, T.poses, nh * 12 * 8, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(ro->counts, T.counts, nh * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(ro->best, T.counts + nh, (size_t)S * 4, hipMemcpyDeviceToHost));
+    }
     return SLAM_OK;
 }
 
@@ -763,6 +882,24 @@ extern "C" int slam_five_point_ransac_batch(slam_ctx *ctx, int S, const int32_t 
     ARG_TRY(ctx, iters == 0 || samples);
     if (ntot == 0 || iters == 0) return fp_empty(S, ntot, E, P, inliers, n_inliers, error, best_iter);
     return fp_run(ctx, S, offsets, px1_xy, px2_xy, pd1_xy, pd2_xy, K1, K2, max_repr_error, samples, iters, E, P, inliers, n_inliers, error, best_iter);
+}
+
+// Test-only (not part of include/slamhip.h): slam_five_point_ransac_batch with the device scratch filled with 0xFF bytes beforehand and every
+// hypothesis copied out afterwards -- ne S x iters, Es S x iters x 10 x 9 (row-major), poses S x iters x 10 x 12, counts S x iters x 10 (k_5pt_score's,
+// partial for a pose it dropped early), best S (the incumbents).  Same staging, same launches (fp_run, fp_enqueue).  Every stream needs n >= 1 and iters >= 1.
+extern "C" int slamhip_test_five_point_hypotheses(slam_ctx *ctx, int S, const int32_t *offsets, const double *px1_xy, const double *px2_xy,
+                                                  const double *pd1_xy, const double *pd2_xy, const double *K1, const double *K2,
+                                                  double max_repr_error, const int32_t *samples, int iters, double *E, double *P,
+                                                  uint8_t *inliers, int *n_inliers, double *error, int *best_iter,
+                                                  int *ne_out, double *Es_out, double *poses_out, int *counts_out, int *best_out)
+{
+    ARG_TRY(ctx, ctx != nullptr && S >= 1 && iters >= 1);
+    ARG_TRY(ctx, offsets && K1 && K2 && E && P && n_inliers && error && best_iter && offsets[0] == 0);
+    for (int z = 0; z < S; z++) ARG_TRY(ctx, offsets[z + 1] > offsets[z]);
+    ARG_TRY(ctx, px1_xy && px2_xy && pd1_xy && pd2_xy && inliers && samples);
+    ARG_TRY(ctx, ne_out && Es_out && poses_out && counts_out && best_out);
+    const FPReadout ro{ne_out, Es_out, poses_out, counts_out, best_out};
+    return fp_run(ctx, S, offsets, px1_xy, px2_xy, pd1_xy, pd2_xy, K1, K2, max_repr_error, samples, iters, E, P, inliers, n_inliers, error, best_iter, &ro);
 }
 
 

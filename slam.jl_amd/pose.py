@@ -137,10 +137,8 @@ def p3p_ransac_batch(points, pixels_xy, pdn_positions, K, threshold=1.0, samples
     return out
 
 
-def five_point_ransac_batch(previous_points_xy, current_points_xy, previous_pd, current_pd, K1, K2, max_repr_error=1.0,
-                            samples=None, iterations=128, seed=0, ctx=None):
-    """S problems at once; returns a list of `(n_inliers, (E, P, inliers, error, best_iter))`."""
-    ctx = ctx or L.default_context()
+def _five_point_batch_stage(previous_points_xy, current_points_xy, previous_pd, current_pd, K1, K2, samples, iterations, seed):
+    """the concatenated inputs of S five-point problems and their result arrays, in the order of slam_five_point_ransac_batch's arguments"""
     S = len(previous_points_xy)
     a, off = _concat(previous_points_xy, 2); b, o2 = _concat(current_points_xy, 2)
     c, o3 = _concat(previous_pd, 2); d, o4 = _concat(current_pd, 2)
@@ -158,8 +156,46 @@ def five_point_ransac_batch(previous_points_xy, current_points_xy, previous_pd, 
     iters = sm.shape[1] if S else 0
     E = np.zeros((S, 9)); P = np.zeros((S, 12)); inl = np.zeros(max(int(off[-1]), 1), dtype=np.uint8)
     cnt = np.zeros(S, dtype=np.int32); bi = np.zeros(S, dtype=np.int32); err = np.zeros(S)
+    return S, off, (a, b, c, d, k1, k2), sm, iters, (E, P, inl, cnt, err, bi)
+
+
+def _five_point_batch_results(S, off, res):
+    E, P, inl, cnt, err, bi = res
+    return [(int(cnt[z]), (E[z].reshape(3, 3).T.copy(), P[z].reshape(4, 3).T.copy(), inl[off[z]:off[z + 1]].view(np.bool_).copy(),
+                           float(err[z]), int(bi[z]))) for z in range(S)]
+
+
+def five_point_ransac_batch(previous_points_xy, current_points_xy, previous_pd, current_pd, K1, K2, max_repr_error=1.0,
+                            samples=None, iterations=128, seed=0, ctx=None):
+    """S problems at once; returns a list of `(n_inliers, (E, P, inliers, error, best_iter))`."""
+    ctx = ctx or L.default_context()
+    S, off, (a, b, c, d, k1, k2), sm, iters, res = _five_point_batch_stage(previous_points_xy, current_points_xy, previous_pd, current_pd,
+                                                                           K1, K2, samples, iterations, seed)
+    E, P, inl, cnt, err, bi = res
     ctx.check(ctx.lib.slam_five_point_ransac_batch(ctx.h, S, L.ptr(off, L.i32p), L.ptr(a), L.ptr(b), L.ptr(c), L.ptr(d), L.ptr(k1), L.ptr(k2),
                                                    float(max_repr_error), L.ptr(sm, L.i32p), iters, L.ptr(E), L.ptr(P), L.ptr(inl, L.u8p),
                                                    L.ptr(cnt, L.i32p), L.ptr(err), L.ptr(bi, L.i32p)))
-    return [(int(cnt[z]), (E[z].reshape(3, 3).T.copy(), P[z].reshape(4, 3).T.copy(), inl[off[z]:off[z + 1]].view(np.bool_).copy(),
-                           float(err[z]), int(bi[z]))) for z in range(S)]
+    return _five_point_batch_results(S, off, res)
+
+
+def five_point_hypotheses(previous_points_xy, current_points_xy, previous_pd, current_pd, K1, K2, max_repr_error, samples, ctx=None):
+    """Test seam (slamhip_test_five_point_hypotheses, exported for the tests only: not in slamhip.h, not in the binding table):
+    five_point_ransac_batch that also reads out every hypothesis.  Every stream needs at least one point and one sample.  Returns
+    `(results, hyp)`: results as five_point_ransac_batch, hyp a dict of the raw device arrays -- ne (S, iters), Es (S, iters, 10, 3, 3)
+    row-major E, poses (S, iters, 10, 12) column-major [R | t], counts (S, iters, 10) as k_5pt_score left them (partial for a pose it
+    dropped early), best (S,) the incumbents.  The device regions are filled with 0xFF bytes before the launches, so a slot no kernel
+    wrote still holds them (-1 as an int, a NaN as a double)."""
+    ctx = ctx or L.default_context()
+    S, off, (a, b, c, d, k1, k2), sm, iters, res = _five_point_batch_stage(previous_points_xy, current_points_xy, previous_pd, current_pd,
+                                                                           K1, K2, samples, 0, 0)
+    E, P, inl, cnt, err, bi = res
+    fn = ctx.lib.slamhip_test_five_point_hypotheses
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p, C.c_int, L.i32p] + [L.f64p] * 6 + [C.c_double, L.i32p, C.c_int, L.f64p, L.f64p, L.u8p, L.i32p, L.f64p, L.i32p,
+                                                                 L.i32p, L.f64p, L.f64p, L.i32p, L.i32p]
+    ne = np.zeros((S, iters), np.int32); Es = np.zeros((S, iters, 10, 3, 3)); poses = np.zeros((S, iters, 10, 12))
+    counts = np.zeros((S, iters, 10), np.int32); best = np.zeros(S, np.int32)
+    ctx.check(fn(ctx.h, S, L.ptr(off, L.i32p), L.ptr(a), L.ptr(b), L.ptr(c), L.ptr(d), L.ptr(k1), L.ptr(k2), float(max_repr_error),
+                 L.ptr(sm, L.i32p), iters, L.ptr(E), L.ptr(P), L.ptr(inl, L.u8p), L.ptr(cnt, L.i32p), L.ptr(err), L.ptr(bi, L.i32p),
+                 L.ptr(ne, L.i32p), L.ptr(Es), L.ptr(poses), L.ptr(counts, L.i32p), L.ptr(best, L.i32p)))
+    return _five_point_batch_results(S, off, res), dict(ne=ne, Es=Es, poses=poses, counts=counts, best=best)

@@ -60,15 +60,15 @@ def test_minimal_solver_satisfies_constraints_and_contains_truth(orc, syn):
         h1 = np.c_[q1, np.ones(5)]; h2 = np.c_[q2, np.ones(5)]
         for E in Es:
             En = E / np.linalg.norm(E)
-            assert np.abs(np.einsum("ij,jk,ik->i", h2, En, h1)).max() < 1e-9           # the five epipolar constraints
+            assert np.abs(np.einsum("ij,jk,ik->i", h2, En, h1)).max() < 1e-9           # the five epipolar constraints (by construction: E is in the null space)
+            assert abs(np.linalg.det(En)) < 1e-9                                       # EVERY returned E is an essential matrix: the solver's gate
+            assert np.abs(2 * En @ En.T @ En - np.trace(En @ En.T) * En).max() < 1e-9
         d = [min(np.abs(E / np.linalg.norm(E) - s * Egt).max() for s in (1, -1)) for E in Es]
-        k = int(np.argmin(d))
-        found += d[k] < 1e-6
-        if d[k] < 1e-10:                                                             # a true essential matrix
-            En = Es[k] / np.linalg.norm(Es[k])
-            assert abs(np.linalg.det(En)) < 1e-9
-            assert np.abs(2 * En @ En.T @ En - np.trace(En @ En.T) * En).max() < 1e-8
-    assert found >= 0.95 * 300                                                       # the rest: ill-conditioned 5-tuples
+        found += min(d) < 1e-6
+    # measured: 299 of 300.  The 5-tuples are NOT ill-conditioned (tests/test_5pt_model_host.py: an independent solver finds the truth on every one of
+    # them to 1e-7 or better); before the solver polished its roots it missed 2.5 % of them through its own rounding.  The one miss left is a
+    # hypothesis the residual gate dropped.
+    assert found >= 299
 
 
 def test_minimal_solver_degenerate(orc):
