@@ -341,11 +341,19 @@ int slam_kpset_detect_describe(slam_ctx *ctx, slam_kpset *ks, const slam_pyr *py
                                uint64_t *desc_dev, int64_t *info_dev, int dcap);
 /* triangulate_stereo! (mapper.jl:142-183) for every 2-D keypoint with a stereo match: success -> map point Twc[s] X and
  * is_3d = 1, failure -> the stereo observation is dropped.  P1, P2, T21, cam1, cam2 as slam_triangulate; Twc: S x 16.
- * The left and right pixels are used as stored: the set's stereo path is for RECTIFIED, zero-distortion pairs (KITTI, the reference's
- * stereo example), where kp.undistorted_pixel == kp.pixel (mapper.jl:162-163); for cameras with lens distortion undistort on the
- * host and use slam_triangulate, or leave the stereo seams on the host lists. */
+ * The left and right pixels are used as stored: this form is for RECTIFIED, zero-distortion pairs (KITTI, the reference's
+ * stereo example), where kp.undistorted_pixel == kp.pixel (mapper.jl:162-163); for cameras with lens distortion use
+ * slam_kpset_triangulate_lens below. */
 int slam_kpset_triangulate(slam_ctx *ctx, slam_kpset *ks, const double *P1, const double *P2, const double *T21,
                            const double *cam1, const double *cam2, const double *Twc, double max_error, double min_depth, int n_bound);
+/* The same for a rig with lenses (dist1, dist2: k1 k2 p1 p2 of camera 1 / camera 2): the left pixel goes through
+ * undistort_point(cam1, dist1, .), the stored stereo pixel through undistort_point(cam2, dist2, .), and the DLT and both reprojection
+ * gates work on the undistorted pair (kp.undistorted_pixel / kp.right_undistorted_pixel, mapper.jl:162-177, frame.jl:272-281).  The
+ * lists keep the raw pixels.  Selection, enqueue-only contract and every other argument as slam_kpset_triangulate; a camera whose four
+ * coefficients are zero has its pixel used as stored, so with both zero the lists come out byte for byte as from that call. */
+int slam_kpset_triangulate_lens(slam_ctx *ctx, slam_kpset *ks, const double *P1, const double *P2, const double *T21,
+                                const double *cam1, const double *cam2, const double *dist1 /* 4 */, const double *dist2 /* 4 */,
+                                const double *Twc, double max_error, double min_depth, int n_bound);
 
 /* compute_pose! (front_end.jl:132-219) for every stream, on the set: the is_3d keypoints in list order (:139-160; undistorted
  * pixel and normalised bearing from params[s][16..23] = fx fy cx cy k1 k2 p1 p2) -> P3P RANSAC (threshold = max_reprojection_error,
@@ -380,6 +388,9 @@ int slam_kpset_download_first(slam_ctx *ctx, slam_kpset *ks, int s, double *firs
 /* the key-frame observations of stream s's list, host <-> device (restoring state, tests): kyx n x 2 (y, x), has_kf n flags */
 int slam_kpset_upload_keyframe(slam_ctx *ctx, slam_kpset *ks, int s, const double *kyx, const uint8_t *has_kf, int n);
 int slam_kpset_download_keyframe(slam_ctx *ctx, slam_kpset *ks, int s, double *kyx, uint8_t *has_kf, int cap_out, int *n_out);
+/* the stereo observations of stream s's list, host -> device (restoring state, tests; slam_kpset_download reads them back):
+ * stereo_yx n x 2 (y, x) in the right image, has_stereo n flags */
+int slam_kpset_upload_stereo(slam_ctx *ctx, slam_kpset *ks, int s, const double *stereo_yx, const uint8_t *has_stereo, int n);
 /* compute_pose_5pt! (front_end.jl:242-332, run every frame at :105) for every stream, on the set: the keypoints the previous
  * key-frame also observes -> undistorted pixels and normalised coordinates of both views (:263-272), the rotation-compensated
  * average parallax (:277-281; params[s][0..8] = R_compensation, column-major; [16..23] camera and distortion) -> five-point
@@ -554,8 +565,9 @@ int slam_kfmap_add_descriptors(slam_ctx *ctx, slam_kfmap *km, const uint64_t *de
  * that stream, the others are unaffected.  Result: the reference's prev_new_map (mapper.jl:370-382) as pairs (keypoint id, local-map point id),
  * ascending by keypoint id, the streams back to back in stream order (n_pairs[s] each), with the winning descriptor distance; more than
  * cap_pairs pairs in all is a capacity error.  The call changes NOTHING in the map: slam_kfmap_merge applies the pairs.
- * Deviations: the slabs hold undistorted pixels while find_best_match uses kp.pixel, so non-zero k1, k2, p1, p2 of any stream is an argument
- * error (as is a map without descriptors), nothing is launched; frame.local_map_ids is kept between key-frames only after
+ * Deviations: the slabs hold undistorted pixels while find_best_match uses kp.pixel, so without the raw-pixel store
+ * (slam_kfmap_enable_pixels, below) non-zero k1, k2, p1, p2 of any stream is an argument error (as is a map without descriptors), nothing is
+ * launched; with the store the match reads the raw pixels and takes any lens; frame.local_map_ids is kept between key-frames only after
  * slam_kfmap_enable_local_map_history (below); no remove_mappoint_obs! clean-ups; a
  * keypoint outside the cell grid is in no cell.  Memory: a staging allocation with fixed per-stream strides, about cap (100 + 20 R) +
  * max_local (100 + 4 R) + 4 mcap bytes per stream, made by the first call.  Synchronous. */
@@ -563,6 +575,17 @@ int slam_kfmap_local_map_match(slam_ctx *ctx, slam_kfmap *km, const double *cam 
                                const double *max_projection_distance, const double *max_descriptor_distance, int max_local,
                                int32_t *status /* S */, int32_t *n_pairs /* S */, int64_t *pairs /* cap_pairs x 2: keypoint id, local-map id */,
                                double *dist, int cap_pairs);
+/* Raw pixels in the map, opt-in (a map that never makes this call launches the same kernels and gets the results it always got): kp.pixel (y, x) of every observation
+ * beside the undistorted pixel, 16 R cap bytes per stream in an allocation of their own; a second call is a no-op.  Call it before the first
+ * slam_kfmap_add_keyframe: an observation recorded earlier gets its undistorted pixel as its raw one.  From then on slam_kfmap_add_keyframe files
+ * the list's pixel as it is beside undistort_point of it, slam_kfmap_merge moves it with the renamed observation, and
+ * slam_kfmap_local_map_match stages keypoint and observer pixels -- hence the cell grid (add_keypoint_to_grid!, frame.jl:576-599) -- from the raw
+ * pixels, as find_best_match does (mapper.jl:405-442), and accepts non-zero k1, k2, p1, p2.  The gather, the update, the filter and
+ * slam_kfmap_triangulate_temporal keep reading the undistorted pixels. */
+int slam_kfmap_enable_pixels(slam_ctx *ctx, slam_kfmap *km);
+/* The raw pixels of key-frame kfid of stream s, in the order of slam_kfmap_download_keyframe's ids: *n_out = -1 when the key-frame is not in the
+ * ring; more than cap_out: a capacity error.  An argument error without the store.  Synchronous. */
+int slam_kfmap_download_pixels(slam_ctx *ctx, slam_kfmap *km, int s, int kfid, double *px_yx, int cap_out, int *n_out);
 /* The local-map history: frame.local_map_ids of every key-frame of the ring, kept in HBM between key-frames.  Opt-in, ONE allocation of about
  * R mcap / 8 + 8 mcap bytes per stream (a bitset over the table's entries per ring slot, the key-frame each set belongs to, a copy of the table's
  * tags as of the stream's last match); a second call is a no-op.  From then on slam_kfmap_local_map_match, for the newest key-frame K of every

@@ -18,9 +18,13 @@ is not run (it models the match without history).  --max-local sets the bound of
 --rows D: a SECOND map with slam_kfmap_enable_descriptor_rows(D) takes the same key-frames and descriptors; per repeat add_keyframe, add_descriptors and
 the match of both maps are timed (rows off first).  With random descriptors no pair occurs: the figures are upkeep and staging, not merges.
 
+--pixels: a SECOND map with slam_kfmap_enable_pixels takes the same key-frames and descriptors (a pinhole camera on both: what the store itself costs);
+per repeat add_keyframe, add_descriptors and the match of both maps are timed, the plain map first, the two alternating through the session.
+
     python scripts/probes/prof_kfmap_local_map.py [--streams 128] [--repeats 25] [--host-repeats 25] [--out profiles/kfmap_local_map_s128.json]
     python scripts/probes/prof_kfmap_local_map.py --history [--max-local 16384] [--out profiles/kfmap_local_map_history_s128.json]
     python scripts/probes/prof_kfmap_local_map.py --rows 4 [--out profiles/kfmap_rows_s128.json]
+    python scripts/probes/prof_kfmap_local_map.py --pixels [--out profiles/kfmap_lens_s128.json]
 """
 import argparse
 import json
@@ -81,11 +85,12 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--history", action="store_true", help="time a second map with the local-map history beside the first, on the same steps (no host route)")
     ap.add_argument("--rows", type=int, default=0, metavar="D", help="time a second map with D descriptor rows per point beside the first, on the same steps (no host route)")
+    ap.add_argument("--pixels", action="store_true", help="time a second map with the raw-pixel store beside the first, on the same steps (no host route)")
     ap.add_argument("--max-local", type=int, default=MAX_LOCAL)
     args = ap.parse_args()
-    if args.history and args.rows:
-        ap.error("--history and --rows each time ONE second map")
-    if args.history or args.rows:
+    if bool(args.history) + bool(args.rows) + bool(args.pixels) > 1:
+        ap.error("--history, --rows and --pixels each time ONE second map")
+    if args.history or args.rows or args.pixels:
         args.host_repeats = 0
     import torch
     import slam_jl_amd as slam
@@ -107,10 +112,13 @@ def main():
     if args.rows:
         kmh = slam.KeyframeMap(S, CAP, R=RING, mcap=MCAP)
         kmh.enable_descriptors(); kmh.enable_descriptor_rows(args.rows)
+    if args.pixels:
+        kmh = slam.KeyframeMap(S, CAP, R=RING, mcap=MCAP)
+        kmh.enable_descriptors(); kmh.enable_pixels()
     rows = [dict() for _ in range(S)]
     m = {k: [] for k in ("desc", "call", "stage", "kernel", "wall", "h_down", "h_asm", "h_call", "h_total", "M", "N", "pairs",
                          "hist_call", "hist_stage", "hist_kernel", "hist_wall", "hist_M", "hist_pairs", "hist_status2", "status2", "add", "hist_add", "hist_desc")}
-    agree = []
+    agree, pairs_equal = [], []
     ctx.prof_enable(True)
     for k in range(WARM + R):
         Tcw = np.tile(np.eye(4), (S, 1, 1))
@@ -166,6 +174,8 @@ def main():
                 dbg = [kmh.debug_local_map(s) for s in range(0, S, max(S // 8, 1))]
                 m["hist_M"].append(float(np.mean([len(d["lm_ids"]) for d in dbg])))
                 m["hist_pairs"].append(int(sum(len(p) for p in hpairs))); m["hist_status2"].append(int((hstatus == 2).sum()))
+                if args.pixels:
+                    pairs_equal.append(bool(np.array_equal(status, hstatus) and all(np.array_equal(a_, b_) for a_, b_ in zip(pairs, hpairs))))
         if k >= WARM and k - WARM < args.host_repeats:
             cur = km.newest()
             t0 = time.perf_counter()
@@ -195,7 +205,7 @@ def main():
         if args.history:
             newest = int(kmh.newest()[0])
             stored = [len(kmh.local_map_ids(s, newest)) for s in range(0, S, max(S // 8, 1))]
-        else:                                                    # the rows the second map holds: per sampled stream the rows per live point, and what the bound dropped
+        elif args.rows:                                          # the rows the second map holds: per sampled stream the rows per live point, and what the bound dropped
             got = [kmh.descriptor_rows(s) for s in range(0, S, max(S // 8, 1))]
             rows_per_point = [float(np.mean([len(k_) for k_ in g["keys"]])) if len(g["keys"]) else 0.0 for g in got]
             rows_dropped = [g["dropped"] for g in got]
@@ -225,6 +235,15 @@ def main():
                     "rows_match_kernel_ms": stat(m["hist_kernel"]), "rows_local_map_match_sync_wall_ms": stat(m["hist_wall"]),
                     "note": "both maps take the same key-frames in one session; random descriptors pair nothing, so the figures are upkeep (add_keyframe's forgetting and "
                             "recording, add_descriptors) and staging, not merges; slam_kfmap_merge and slam_kfmap_filter are not timed here"})
+    if args.pixels:                                              # the same answers from both maps: the store changes where the match reads, not what
+        rec = {k: v for k, v in rec.items() if not k.startswith("c_")}
+        rec.update({"pixels_store_bytes_per_stream": 16 * RING * CAP, "pixels_pairs_equal_plain": pairs_equal,
+                    "pixels_pairs_all_streams": stat(m["hist_pairs"]), "pixels_streams_with_status_2": stat(m["hist_status2"]),
+                    "pixels_add_keyframe_device_ms": stat(m["hist_add"]), "pixels_add_descriptors_device_ms": stat(m["hist_desc"]),
+                    "pixels_local_map_match_device_ms": stat(m["hist_call"]), "pixels_stage_kernel_ms": stat(m["hist_stage"]),
+                    "pixels_match_kernel_ms": stat(m["hist_kernel"]), "pixels_local_map_match_sync_wall_ms": stat(m["hist_wall"]),
+                    "note": "both maps take the same key-frames in one session, the plain map first in every repeat; a pinhole camera on both, so the figures are "
+                            "what the store costs (16 more bytes written per recorded observation, the stager reading kpx for kupx); slam_kfmap_merge is not timed here"})
     print(json.dumps(rec))
     if args.out:
         with open(args.out, "w") as f_:

@@ -90,12 +90,14 @@ SIGNATURES = {
     "slam_kpset_detect": (cint, [vp, vp, vp, cint, cint, cint, cint, cint, dbl, dbl]),
     "slam_kpset_detect_describe": (cint, [vp, vp, vp, cint, cint, cint, cint, cint, dbl, dbl, i32p, cint, dbl, cint, vp, vp, cint]),
     "slam_kpset_triangulate": (cint, [vp, vp, f64p, f64p, f64p, f64p, f64p, f64p, dbl, dbl, cint]),
+    "slam_kpset_triangulate_lens": (cint, [vp, vp, f64p, f64p, f64p, f64p, f64p, f64p, f64p, f64p, dbl, dbl, cint]),
     "slam_kpset_keyframe": (cint, [vp, vp]),
     "slam_kpset_triangulate_temporal": (cint, [vp, vp, f64p, f64p, cint, i32p, i32p, dbl, dbl, dbl, cint]),
     "slam_kpset_upload_first": (cint, [vp, vp, cint, f64p, i32p, cint, cint]),
     "slam_kpset_download_first": (cint, [vp, vp, cint, f64p, i32p, cint, C.POINTER(cint), C.POINTER(cint)]),
     "slam_kpset_upload_keyframe": (cint, [vp, vp, cint, f64p, u8p, cint]),
     "slam_kpset_download_keyframe": (cint, [vp, vp, cint, f64p, u8p, cint, C.POINTER(cint)]),
+    "slam_kpset_upload_stereo": (cint, [vp, vp, cint, f64p, u8p, cint]),
     "slam_kpset_compute_pose_5pt": (cint, [vp, vp, f64p, dbl, dbl, cint, C.c_uint64, f64p, i32p, i32p, f64p, i32p]),
     "slam_kpset_frame_stats": (cint, [vp, vp, f64p, cint, cint, cint, cint, vp, f64p]),
     "slam_keyframe_required": (cint, [cint, f64p, i32p, i32p, u8p, cint, dbl, cint, u8p, u8p]),
@@ -120,6 +122,8 @@ SIGNATURES = {
     "slam_kfmap_download_local_map_ids": (cint, [vp, vp, cint, cint, i64p, cint, i32p]),
     "slam_kfmap_enable_descriptor_rows": (cint, [vp, vp, cint]),
     "slam_kfmap_download_descriptor_rows": (cint, [vp, vp, cint, i64p, u8p, i32p, i32p, u64p, cint, cint, i32p, i32p]),
+    "slam_kfmap_enable_pixels": (cint, [vp, vp]),
+    "slam_kfmap_download_pixels": (cint, [vp, vp, cint, cint, f64p, cint, C.POINTER(cint)]),
     "slam_kfmap_triangulate_temporal": (cint, [vp, vp, vp, f64p, dbl, dbl, dbl, i32p]),
     "slam_kpset_compute_pose": (cint, [vp, vp, f64p, dbl, cint, C.c_uint64, cint, cint, dbl, dbl, f64p, i32p, i32p, i32p]),
     "slam_local_ba": (cint, [vp, dbl, dbl, dbl, dbl, cint, cint, cint, f64p, u8p, f64p, i64p, i64p, u8p, cint, cint, dbl, f64p]),

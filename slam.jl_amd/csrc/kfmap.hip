@@ -113,7 +113,8 @@ __global__ __launch_bounds__(256) void k_kfm_claim(KfmapView V, KpsetView K, con
     V.kfresh[(size_t)s * V.cap + i] = fresh;
 }
 // tracked_ba.add_keyframe: the slab of the new key-frame, and every listed point's entry (one thread per entry: its owner's)
-template <bool ROWS> __global__ __launch_bounds__(256) void k_kfm_record(KfmView<ROWS> V, KpsetView K, const double *par, const int *sel)
+// kpx: the raw-pixel store (nullptr: off) -- the list's pixel as it is goes beside the undistorted one
+template <bool ROWS> __global__ __launch_bounds__(256) void k_kfm_record(KfmView<ROWS> V, KpsetView K, const double *par, const int *sel, double *kpx)
 {
     const int s = KFM_STREAM(blockIdx.y), i = blockIdx.x * 256 + threadIdx.x, kfid = K.kfcount[s] - 1;
     if (kfid < 0) return;
@@ -130,6 +131,7 @@ template <bool ROWS> __global__ __launch_bounds__(256) void k_kfm_record(KfmView
     const int64_t id = K.id[ql];
     double cam[4], dist[4], y = K.yx[2 * ql], x = K.yx[2 * ql + 1];
     load_cam(P, cam, dist);
+    if (kpx) { kpx[2 * q] = y; kpx[2 * q + 1] = x; }
     if (dist[0] != 0.0 || dist[1] != 0.0 || dist[2] != 0.0 || dist[3] != 0.0) undistort_px(cam, dist, y, x, y, x);     // (all zero: the pixel as it is, a copy)
     const uint8_t fresh = V.kfresh[(size_t)s * V.cap + i];
     V.kid[q] = id; V.kupx[2 * q] = y; V.kupx[2 * q + 1] = x; V.klive[q] = fresh != 2;
@@ -627,6 +629,7 @@ int slam_kfmap_destroy(slam_kfmap *km)
     if (km->pin) (void)hipHostFree(km->pin);
     if (km->dbase) (void)hipFree(km->dbase);
     if (km->rbase) (void)hipFree(km->rbase);
+    if (km->kpx) (void)hipFree(km->kpx);
     if (km->lm_base) (void)hipFree(km->lm_base);
     if (km->mg_base) (void)hipFree(km->mg_base);
     if (km->hs_base) (void)hipFree(km->hs_base);
@@ -652,7 +655,7 @@ int slam_kfmap_add_keyframe(slam_ctx *ctx, slam_kfmap *km, slam_kpset *ks, const
       KFM_LAUNCH_ROWS(km, k_kfm_forget, gs, (const int *)ks->v.kfcount, sel);
       hipLaunchKernelGGL(k_kfm_clear_observed, gm, dim3(256), 0, ctx->stream, V, (const int *)ks->v.kfcount, sel);
       hipLaunchKernelGGL(k_kfm_claim, gl, dim3(256), 0, ctx->stream, V, ks->v, sel);
-      KFM_LAUNCH_ROWS(km, k_kfm_record, gl, ks->v, par, sel); }
+      KFM_LAUNCH_ROWS(km, k_kfm_record, gl, ks->v, par, sel, km->kpx); }
     HIP_TRY(ctx, hipGetLastError());
     return SLAM_OK;
 }
@@ -964,6 +967,49 @@ int slam_kfmap_download_keyframe(slam_ctx *ctx, slam_kfmap *km, int s, int kfid,
     if (n > 0 && upx_yx) HIP_TRY(ctx, hipMemcpyAsync(upx_yx, V.kupx + 2 * sr * V.cap, (size_t)n * 16, hipMemcpyDeviceToHost, ctx->stream));
     if (n > 0 && live) HIP_TRY(ctx, hipMemcpyAsync(live, V.klive + sr * V.cap, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, slam_stream_wait(ctx->stream));
+    return SLAM_OK;
+}
+
+// the raw-pixel store: as large as kupx, and a copy of it for whatever was recorded before the call (the raw pixel of a pinhole observation)
+int slam_kfmap_enable_pixels(slam_ctx *ctx, slam_kfmap *km)
+{
+    ARG_TRY(ctx, ctx != nullptr && km != nullptr);
+    if (km->kpx) return SLAM_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const KfmapView &V = km->v;
+    const size_t bytes = (size_t)V.S * V.R * V.cap * 16;
+    if (km->mg_base) {                                           // the merge scratch was laid out without the raw pixels' slab: the next merge makes it anew.
+        HIP_TRY(ctx, hipDeviceSynchronize());                    // First, while the store is still off: a failure here leaves the map as it was
+        (void)hipFree(km->mg_base); km->mg_base = nullptr; km->mg = KfmMerge{};
+    }
+    double *px = nullptr;
+    hipError_t e = hipMalloc((void **)&px, bytes);
+    if (e == hipSuccess) e = hipMemcpyAsync(px, V.kupx, bytes, hipMemcpyDeviceToDevice, ctx->stream);
+    if (e == hipSuccess) e = slam_stream_wait(ctx->stream);
+    if (e != hipSuccess) { if (px) (void)hipFree(px); return slam_fail(ctx, SLAM_ERR_HIP, "slam_kfmap_enable_pixels: %s", hipGetErrorString(e)); }
+    km->kpx = px;                                                // published last: every later layout and launch sees the store whole
+    return SLAM_OK;
+}
+
+int slam_kfmap_download_pixels(slam_ctx *ctx, slam_kfmap *km, int s, int kfid, double *px_yx, int cap_out, int *n_out)
+{
+    ARG_TRY(ctx, ctx != nullptr && km != nullptr && s >= 0 && s < km->v.S && kfid >= 0 && n_out != nullptr);
+    if (!km->kpx) return slam_fail(ctx, SLAM_ERR_ARG, "slam_kfmap_download_pixels: raw pixels are not enabled (slam_kfmap_enable_pixels)");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const KfmapView &V = km->v;
+    const size_t sr = (size_t)s * V.R + kfid % V.R;
+    int tn[2] = {0, 0};
+    HIP_TRY(ctx, hipMemcpyAsync(&tn[0], V.tag + sr, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(&tn[1], V.kn + sr, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, slam_stream_wait(ctx->stream));
+    if (tn[0] != kfid + 1) { *n_out = -1; return SLAM_OK; }      // not in the ring (never added, or forgotten)
+    const int n = tn[1];
+    *n_out = n;
+    if (n > cap_out) return slam_fail(ctx, SLAM_ERR_CAPACITY, "slam_kfmap_download_pixels: %d observations but cap = %d", n, cap_out);
+    if (n > 0 && px_yx) {
+        HIP_TRY(ctx, hipMemcpyAsync(px_yx, km->kpx + 2 * sr * V.cap, (size_t)n * 16, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, slam_stream_wait(ctx->stream));
+    }
     return SLAM_OK;
 }
 

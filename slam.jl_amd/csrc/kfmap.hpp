@@ -54,6 +54,17 @@
 // is added to the stream's counter; the reference's most representative `descriptor` (map_point.jl:98-120, :132-144) is read by nothing but the emptiness test
 // and is not modelled; a reused ring slot counts as remove_keyframe!.
 //
+// Raw pixels (slam_kfmap_enable_pixels; an allocation of its own, made by that call): kpx [S R cap][2], kp.pixel (y, x) of every observation beside
+// kupx, 16 S R cap bytes (cap 1 400, R 32: 0.7 MB per stream; S = 128: 92 MB).  It is not part of the view: KfmapView / KfmapRows, hence the
+// argument block of every kernel that does not deal with pixels, are what they were.  The three kernels that keep or read the store take the pointer by
+// value, nullptr while the store is off; a map without it launches the same kernels on the same views, but THEIR argument blocks have grown -- k_kfm_record
+// (both ROWS forms) by a trailing parameter, the merge kernels by two trailing members of KfmMerge, the stagers by a trailing member of KfmLm -- and
+// k_kfm_record / k_kfm_merge_slabs test the pointer (uniform) where they had no branch.  Their results for such a map are unchanged:
+//   k_kfm_record        files the list's pixel as it is beside undistort_px of it
+//   k_kfm_merge_slabs   moves it with the observation (KfmMerge::kpx / t_px; the merge scratch grows by 16 S R cap bytes)
+//   k_kfm_lm_stage(_hist)   read kp_yx and kp_oyx -- hence the cell grid, add_keypoint_to_grid! -- through KfmLm::px_src: kpx with the store, else kupx
+// The gather, the update, the filter and slam_kfmap_triangulate_temporal read kupx.  A tombstone keeps its raw pixel as it keeps its undistorted one.
+//
 // Local-map staging (slam_kfmap_local_map_match, kfmap_lmm.inc; a third allocation, made by the first call and re-made when max_local or the grid grows):
 // the packed buffer of k_lmm_match (lmm_host.hpp) with FIXED per-stream strides -- no count pass, no scan over the streams, hence no host round trip between
 // staging and match.  With N1 = cap + 1, M1 = max_local + 1, C1 = the call's largest cell count + 1, per stream, each region rounded up to 256 over S:
@@ -67,8 +78,9 @@
 // staging would save, at the price of a second pass over the table and a scan launch.
 //
 // Deviations of slam_kfmap_local_map_match from update_frame_covisibility! + match_local_map! (map_manager.jl:302-355, mapper.jl:265-462):
-//   distortion    the slabs hold UNDISTORTED pixels, find_best_match uses kp.pixel and project_world_to_image_distort; the two coincide only without
-//                 lens distortion, so a stream with non-zero k1, k2, p1, p2 is an argument error (the restriction of the set's stereo seams)
+//   distortion    find_best_match and the frame grid use kp.pixel with project_world_to_image_distort.  With the raw-pixel store (above) so does the
+//                 match, for any lens.  Without it the slabs hold UNDISTORTED pixels only; the two coincide only without lens distortion, so a
+//                 stream with non-zero k1, k2, p1, p2 is then an argument error
 //   persistence   without slam_kfmap_enable_local_map_history frame.local_map_ids is not kept between key-frames (the local map is what this key-frame's
 //                 covisibility pass yields).  With it (below) the replace-or-union rule (map_manager.jl:350-354) and the union with the oldest covisible
 //                 key-frame's local map (mapper.jl:274-286) hold, with three differences: a stored set holds the ids that passed the match's gates
@@ -98,10 +110,11 @@
 // and live list is sorted by id, so the touched slabs and lists are rebuilt in order through scratch.  With Z = S (R + 1) (a stream's R slabs, then its
 // list), n = S R cap, l = S cap, each region rounded up to 256:
 //   renames   count 4 Z | position 4 Z cap | new id 8 Z cap | new ids ascending 8 Z cap | rank by position 4 Z cap | kept before 4 Z (cap + 1)
-//   slabs     ids 8 n | upx 16 n | live n
+//   slabs     ids 8 n | upx 16 n | live n | raw px 16 n (with the raw-pixel store)
 //   pairs     applied l | counts 16 S
 //   lists     yx, stereo yx, key-frame yx, first yx 16 l each | xyz 24 l | id 8 l | is3d, stereo, haskf l each | first key-frame 4 l
-// i.e. about (53 R + 132) cap bytes per stream (cap 1 400, R 32: 2.6 MB; S = 128: 330 MB).  The main allocation's layout is untouched.
+// i.e. about (53 R + 132) cap bytes per stream (cap 1 400, R 32: 2.6 MB; S = 128: 330 MB; with raw pixels 69 R + 132: 3.3 MB; 420 MB).  The main
+// allocation's layout is untouched.
 // slam_kfmap_merge against the reference (the first three are deviations, the last two the reference's own rules as they show in slabs):
 //   covisibility  add_covisibility! has no counterpart: covisibility is derived from the observer masks (as for the filter's remove_covisible_kf!)
 //   descriptors   without the row store one row per point: new keeps its own, prev's goes with prev; with it new takes prev's rows by key (above)
@@ -184,6 +197,7 @@ struct KfmLm {
     int32_t *mark;                        // [S mcap] 1: the entry's point is in the local map
     int32_t *cnt;                         // [S][2] N, M of the last staging (0, 0 unless status 0)
     int32_t *status, *rn; int64_t *rpairs; double *rdist;        // results, one block: [S] | [S] | [S cap][2] | [S cap]
+    const double *px_src;                 // [S R cap][2] where kp_yx / kp_oyx come from: the slabs' raw pixels (slam_kfmap_enable_pixels), else kupx
 };
 
 // the match kernel's argument block over the staged regions
@@ -213,6 +227,8 @@ struct KfmMerge {
     int32_t *stat;                        // [S][4] pairs applied, pairs skipped, observations renamed, status (1: the pairs are not one-to-one)
     // the scratch record array of the lists [S cap]: every field k_kpset_compact carries
     double *q_yx, *q_syx, *q_xyz, *q_kyx, *q_fyx; int64_t *q_id; uint8_t *q_is3d, *q_stereo, *q_haskf; int *q_fkf;
+    // last, so that every member above lies where it did: the raw pixels' scratch slab and the store itself, [S R cap][2] (nullptr both: the store is off)
+    double *t_px, *kpx;
 };
 
 struct slam_kfmap {
@@ -226,6 +242,7 @@ struct slam_kfmap {
     char *pin = nullptr; size_t pin_bytes = 0; hipEvent_t pin_ev = nullptr;
     char *dbase = nullptr;                // the descriptor store
     char *rbase = nullptr;                // the row store (nullptr: off)
+    double *kpx = nullptr;                // the raw-pixel store [S R cap][2] (nullptr: off)
     char *lm_base = nullptr; size_t lm_bytes = 0, lm_res_off = 0, lm_res_bytes = 0; KfmLm lm = {};        // the local-map staging (lm.max_local, lm.C1: what it was laid out for)
     int lm_np[128] = {};                  // pairs per stream in the result block of the last local-map match, until a merge has consumed them
     char *mg_base = nullptr; size_t mg_bytes = 0; KfmMerge mg = {};       // the merge's scratch

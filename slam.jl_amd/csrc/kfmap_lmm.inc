@@ -105,7 +105,8 @@ __device__ __forceinline__ void kfm_lm_history(const KfmapView &V, const KfmLm &
 //   points         per local-map point its position, descriptor and observers (mask bits whose tag matches, ascending by key-frame id); the observer
 //                  offsets are a scan of the counts (kfm_scan)
 //   keypoints      ordered compaction of the newest slab's live observations whose point has a descriptor; per observer the pixel by binary search in that
-//                  slab (kfm_find_live), a missing or dead observation skipped (mapper.jl:429-434 without the clean-up)
+//                  slab (kfm_find_live), a missing or dead observation skipped (mapper.jl:429-434 without the clean-up).  Pixels come from Q.px_src: the
+//                  raw pixels where the map keeps them (slam_kfmap_enable_pixels), else the undistorted ones
 //   key-frames     row = rank of the slot by key-frame id; Tcw from theta by angles_to_pose
 //   cells          lmm_emit's stable counting sort: counts by global atomics of this workgroup alone, offsets by kfm_scan, then the keypoints in chunks of
 //                  256 in list order -- a keypoint's place is its cell's cursor plus the chunk's earlier keypoints of the same cell
@@ -235,7 +236,7 @@ __device__ __forceinline__ void kfm_lm_stage_body(const KfmView<ROWS> &V, const 
             if constexpr (ROWS) doff = kfm_scan(acc ? kfm_rows_count(V.rkey + pe * V.D, V.D) : 0, s_w, &s_dbase);
             if (acc) {
                 const size_t g = (size_t)kp0 + pos;
-                Q.kp_id[g] = id; Q.kp_yx[2 * g] = V.kupx[2 * (sl + i)]; Q.kp_yx[2 * g + 1] = V.kupx[2 * (sl + i) + 1];
+                Q.kp_id[g] = id; Q.kp_yx[2 * g] = Q.px_src[2 * (sl + i)]; Q.kp_yx[2 * g + 1] = Q.px_src[2 * (sl + i) + 1];
                 if constexpr (ROWS) { Q.kp_doff[g] = kp0 * Q.DR + doff; (void)rows_out(pe, Q.kp_desc + 4 * ((size_t)kp0 * Q.DR + doff)); }
                 else { for (int k = 0; k < 4; k++) Q.kp_desc[4 * g + k] = V.ddesc[4 * pe + k]; Q.kp_doff[g] = (int32_t)g; }
                 Q.kp_ooff[g] = kobs0 + off;
@@ -244,7 +245,7 @@ __device__ __forceinline__ void kfm_lm_stage_body(const KfmView<ROWS> &V, const 
                     const int b = s_asc[k];
                     if (!(wm >> b & 1)) continue;
                     const size_t qo = ((size_t)s * R + b) * cap + max(kfm_find_live(V, s, b, id), 0);      // (found: validated above)
-                    Q.kp_okf[o] = k; Q.kp_oyx[2 * o] = V.kupx[2 * qo]; Q.kp_oyx[2 * o + 1] = V.kupx[2 * qo + 1];
+                    Q.kp_okf[o] = k; Q.kp_oyx[2 * o] = Q.px_src[2 * qo]; Q.kp_oyx[2 * o + 1] = Q.px_src[2 * qo + 1];
                     o++;
                 }
             }
@@ -539,7 +540,7 @@ int slam_kfmap_local_map_match(slam_ctx *ctx, slam_kfmap *km, const double *cam,
     for (int s = 0; s < S; s++) {                                // every check, for every stream, before anything is enqueued
         const double *c = cam + 10 * (size_t)s;
         KfmLmArg &A = args[s];
-        if (c[4] != 0.0 || c[5] != 0.0 || c[6] != 0.0 || c[7] != 0.0)
+        if (!km->kpx && (c[4] != 0.0 || c[5] != 0.0 || c[6] != 0.0 || c[7] != 0.0))          // (with the raw-pixel store the match reads kp.pixel: any lens)
             return slam_fail(ctx, SLAM_ERR_ARG, "slam_kfmap_local_map_match: stream %d has lens distortion (%g %g %g %g); the map's pixels are undistorted", s, c[4], c[5], c[6], c[7]);
         const double H = c[8], W = c[9];
         const int cell = cell_size[s];
@@ -571,6 +572,7 @@ int slam_kfmap_local_map_match(slam_ctx *ctx, slam_kfmap *km, const double *cam,
     }
     KfmLm Q = km->lm;
     Q.max_local = max_local;                                                       // the call's bound; the strides stay the allocation's
+    Q.px_src = km->kpx ? km->kpx : V.kupx;                                         // find_best_match's kp.pixel where the map keeps it
     Layout D;
     const auto o_sel = D.take<int>(S); const auto o_arg = D.take<KfmLmArg>(S); const size_t in_b = D.size();
     const size_t o_res = D.take(km->lm_res_bytes);

@@ -152,10 +152,12 @@ __global__ __launch_bounds__(256) void k_kfm_merge_slabs(KfmapView V, KfmMerge G
         const int d = kfm_rename_dest(ids, n, k, Z, i, id);
         if (d < 0 || d >= cap) continue;
         G.t_id[sl + d] = id; G.t_upx[2 * (sl + d)] = V.kupx[2 * (sl + i)]; G.t_upx[2 * (sl + d) + 1] = V.kupx[2 * (sl + i) + 1]; G.t_live[sl + d] = V.klive[sl + i];
+        if (G.kpx) { G.t_px[2 * (sl + d)] = G.kpx[2 * (sl + i)]; G.t_px[2 * (sl + d) + 1] = G.kpx[2 * (sl + i) + 1]; }        // (uniform) the raw pixel travels with the observation
     }
     __syncthreads();                                             // every read of the slab lies behind this barrier
     for (int i = tid; i < n2; i += 256) {
         V.kid[sl + i] = G.t_id[sl + i]; V.kupx[2 * (sl + i)] = G.t_upx[2 * (sl + i)]; V.kupx[2 * (sl + i) + 1] = G.t_upx[2 * (sl + i) + 1]; V.klive[sl + i] = G.t_live[sl + i];
+        if (G.kpx) { G.kpx[2 * (sl + i)] = G.t_px[2 * (sl + i)]; G.kpx[2 * (sl + i) + 1] = G.t_px[2 * (sl + i) + 1]; }
     }
     if (tid == 0) V.kn[s * R + b] = n2;
 }
@@ -217,6 +219,8 @@ static size_t kfmap_merge_regions(slam_kfmap *km, char *base)
     Lo.bind(g.applied, l, base); Lo.bind(g.stat, S * 16, base);
     Lo.bind(g.q_yx, l * 16, base); Lo.bind(g.q_syx, l * 16, base); Lo.bind(g.q_xyz, l * 24, base); Lo.bind(g.q_kyx, l * 16, base); Lo.bind(g.q_fyx, l * 16, base); Lo.bind(g.q_id, l * 8, base);
     Lo.bind(g.q_is3d, l, base); Lo.bind(g.q_stereo, l, base); Lo.bind(g.q_haskf, l, base); Lo.bind(g.q_fkf, l * 4, base);
+    if (km->kpx) Lo.bind(g.t_px, n * 16, base); else g.t_px = nullptr;           // last: every other region lies where it did without the store
+    g.kpx = km->kpx;
     return Lo.size();
 }
 

@@ -118,12 +118,21 @@ struct KTriArgs {
     const double *Twc;                 // [S][16] column-major camera-1 -> world, device
     double max_error, min_depth;
 };
-__device__ __forceinline__ void k_kpset_triangulate_slot(const KpsetView &K, const KTriArgs &T, const int *work, int i)
+// the two lenses of slam_kpset_triangulate_lens: k1 k2 p1 p2 of camera 1 and of camera 2 (the intrinsics are M.cam1 / M.cam2)
+struct KTriLens { double dist1[4], dist2[4]; };
+// LENS: the left pixel and the stored stereo pixel are undistorted first, each through its own camera (kp.undistorted_pixel /
+// kp.right_undistorted_pixel, mapper.jl:162-177); the DLT and the gates then see the undistorted pair.  <false> never touches Z.
+template <bool LENS>
+__device__ __forceinline__ void k_kpset_triangulate_slot(const KpsetView &K, const KTriArgs &T, const KTriLens *Z, const int *work, int i)
 {
     const size_t q = (size_t)work[i];
     if (!K.stereo[q] || K.is3d[q]) return;
     const int s = (int)(q / K.cap);
-    const double x1 = K.yx[2 * q + 1], y1 = K.yx[2 * q], x2 = K.syx[2 * q + 1], y2 = K.syx[2 * q];
+    double x1 = K.yx[2 * q + 1], y1 = K.yx[2 * q], x2 = K.syx[2 * q + 1], y2 = K.syx[2 * q];
+    if constexpr (LENS) {                                        // (a camera whose four coefficients are zero: the pixel as it is, a copy -- k_kfm_record's rule)
+        if (Z->dist1[0] != 0.0 || Z->dist1[1] != 0.0 || Z->dist1[2] != 0.0 || Z->dist1[3] != 0.0) undistort_px(T.M.cam1, Z->dist1, y1, x1, y1, x1);
+        if (Z->dist2[0] != 0.0 || Z->dist2[1] != 0.0 || Z->dist2[2] != 0.0 || Z->dist2[3] != 0.0) undistort_px(T.M.cam2, Z->dist2, y2, x2, y2, x2);
+    }
     double L[4];
     dlt_two_view(x1, y1, x2, y2, T.M.P1, T.M.P2, L);
     const bool ok = two_view_gates(L, T.M.T21, T.M.cam1, T.M.cam2, x1, y1, x2, y2, T.max_error, T.min_depth, true);
@@ -139,7 +148,13 @@ __device__ __forceinline__ void k_kpset_triangulate_slot(const KpsetView &K, con
 __global__ __launch_bounds__(64) void k_kpset_triangulate(KpsetView K, KTriArgs T, const int *work, const int *ntot)
 {
     const int n = ntot[0];
-    for (int i = blockIdx.x * 64 + threadIdx.x; i < n; i += gridDim.x * 64) k_kpset_triangulate_slot(K, T, work, i);
+    for (int i = blockIdx.x * 64 + threadIdx.x; i < n; i += gridDim.x * 64) k_kpset_triangulate_slot<false>(K, T, nullptr, work, i);
+}
+// the same with a lens on either camera (slam_kpset_triangulate_lens)
+__global__ __launch_bounds__(64) void k_kpset_triangulate_lens(KpsetView K, KTriArgs T, KTriLens Z, const int *work, const int *ntot)
+{
+    const int n = ntot[0];
+    for (int i = blockIdx.x * 64 + threadIdx.x; i < n; i += gridDim.x * 64) k_kpset_triangulate_slot<true>(K, T, &Z, work, i);
 }
 
 // Array-level body of triangulate_temporal! (src/mapper.jl:185-262) on the set: every 2-D keypoint whose first observer (the
@@ -579,6 +594,13 @@ int slam_kpset_upload_keyframe(slam_ctx *ctx, slam_kpset *ks, int s, const doubl
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     return kpset_copy(ctx, ks, s, n, hipMemcpyHostToDevice, true, {{ks->v.kyx, 16, kyx}, {ks->v.haskf, 1, has_kf}});
 }
+// the stereo observations of stream s's list, host -> device (restoring state, tests): stereo_yx n x 2 (y, x), has_stereo n flags
+int slam_kpset_upload_stereo(slam_ctx *ctx, slam_kpset *ks, int s, const double *stereo_yx, const uint8_t *has_stereo, int n)
+{
+    ARG_TRY(ctx, ctx != nullptr && ks != nullptr && s >= 0 && s < ks->S && n >= 0 && n <= ks->v.cap && (n == 0 || (stereo_yx != nullptr && has_stereo != nullptr)));
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return kpset_copy(ctx, ks, s, n, hipMemcpyHostToDevice, true, {{ks->v.syx, 16, stereo_yx}, {ks->v.stereo, 1, has_stereo}});
+}
 int slam_kpset_download_keyframe(slam_ctx *ctx, slam_kpset *ks, int s, double *kyx, uint8_t *has_kf, int cap_out, int *n_out)
 {
     ARG_TRY(ctx, ctx != nullptr && ks != nullptr && s >= 0 && s < ks->S && n_out != nullptr);
@@ -607,10 +629,10 @@ int slam_kpset_remove(slam_ctx *ctx, slam_kpset *ks, const uint8_t *flags_dev)
     return kpset_compact(ctx, ks, 1, flags_dev);
 }
 
-int slam_kpset_triangulate(slam_ctx *ctx, slam_kpset *ks, const double *P1, const double *P2, const double *T21,
-                           const double *cam1, const double *cam2, const double *Twc, double max_error, double min_depth, int n_bound)
+// the one body of slam_kpset_triangulate and slam_kpset_triangulate_lens: lens == nullptr launches k_kpset_triangulate, else k_kpset_triangulate_lens
+static int kpset_triangulate(slam_ctx *ctx, slam_kpset *ks, const double *P1, const double *P2, const double *T21, const double *cam1, const double *cam2,
+                             const KTriLens *lens, const double *Twc, double max_error, double min_depth, int n_bound)
 {
-    ARG_TRY(ctx, ctx != nullptr && ks != nullptr && P1 && P2 && T21 && cam1 && cam2 && Twc);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     KTriArgs T;
     T.M.fill(P1, P2, T21, cam1, cam2);
@@ -621,9 +643,27 @@ int slam_kpset_triangulate(slam_ctx *ctx, slam_kpset *ks, const double *P1, cons
     rc = kpset_build_worklist(ctx, ks, 0, 0, true);
     if (rc) return rc;
     const int nb = kpset_sel_grid_bound(ks, n_bound);
-    hipLaunchKernelGGL(k_kpset_triangulate, dim3((nb + 63) / 64), dim3(64), 0, ctx->stream, ks->v, T, (const int *)ks->work, (const int *)ks->ntot);
+    if (lens) hipLaunchKernelGGL(k_kpset_triangulate_lens, dim3((nb + 63) / 64), dim3(64), 0, ctx->stream, ks->v, T, *lens, (const int *)ks->work, (const int *)ks->ntot);
+    else hipLaunchKernelGGL(k_kpset_triangulate, dim3((nb + 63) / 64), dim3(64), 0, ctx->stream, ks->v, T, (const int *)ks->work, (const int *)ks->ntot);
     HIP_TRY(ctx, hipGetLastError());
     return SLAM_OK;
+}
+int slam_kpset_triangulate(slam_ctx *ctx, slam_kpset *ks, const double *P1, const double *P2, const double *T21,
+                           const double *cam1, const double *cam2, const double *Twc, double max_error, double min_depth, int n_bound)
+{
+    ARG_TRY(ctx, ctx != nullptr && ks != nullptr && P1 && P2 && T21 && cam1 && cam2 && Twc);
+    return kpset_triangulate(ctx, ks, P1, P2, T21, cam1, cam2, nullptr, Twc, max_error, min_depth, n_bound);
+}
+// triangulate_stereo! for a rig with lenses: the left pixel through undistort_px(cam1, dist1, .), the stored stereo pixel through
+// undistort_px(cam2, dist2, .), then the DLT and both reprojection gates on the undistorted pair (mapper.jl:162-177)
+int slam_kpset_triangulate_lens(slam_ctx *ctx, slam_kpset *ks, const double *P1, const double *P2, const double *T21,
+                                const double *cam1, const double *cam2, const double *dist1, const double *dist2, const double *Twc,
+                                double max_error, double min_depth, int n_bound)
+{
+    ARG_TRY(ctx, ctx != nullptr && ks != nullptr && P1 && P2 && T21 && cam1 && cam2 && dist1 && dist2 && Twc);
+    KTriLens Z;
+    memcpy(Z.dist1, dist1, sizeof Z.dist1); memcpy(Z.dist2, dist2, sizeof Z.dist2);
+    return kpset_triangulate(ctx, ks, P1, P2, T21, cam1, cam2, &Z, Twc, max_error, min_depth, n_bound);
 }
 
 int slam_kpset_triangulate_temporal(slam_ctx *ctx, slam_kpset *ks, const double *params, const double *tab, int nkf,

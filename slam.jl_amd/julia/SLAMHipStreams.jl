@@ -26,8 +26,8 @@ module SLAMHipStreams
 import ..SLAMHip: LIB, ctx, check
 
 export PyramidBatch, FrameRing, KeypointSet, upload!, update!, flow_match!, stereo_match!, remove!, detect!, detect_describe!, describe_batch, keyframe!, select!, selection,
-       triangulate!, triangulate_temporal!, compute_pose_5pt!, compute_pose!, frame_stats, keyframe_required, counts, download, stream_params,
-       KeyframeMap, add_keyframe!, gather, download_keyframe, download_points, reset!, filter_map!, remove_keyframe!, newest
+       triangulate!, triangulate_lens!, upload_stereo!, triangulate_temporal!, compute_pose_5pt!, compute_pose!, frame_stats, keyframe_required, counts, download, stream_params,
+       KeyframeMap, add_keyframe!, gather, download_keyframe, download_points, reset!, filter_map!, remove_keyframe!, newest, enable_pixels!, keyframe_pixels
 
 const HIP = "libamdhip64"
 hipcheck(e::Cint, what) = e == 0 || error("$what: HIP error $e")
@@ -222,6 +222,26 @@ function triangulate!(k::KeypointSet, P1::Matrix{Float64}, P2::Matrix{Float64}, 
     GC.@preserve P1 P2 T21 c1 c2 Twc check(ccall((:slam_kpset_triangulate, LIB[]), Cint,
         (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cdouble, Cdouble, Cint),
         ctx(), k.h, P1, P2, T21, c1, c2, Twc, max_error, min_depth, n_bound))
+    k
+end
+
+# The same for a rig with lenses: dist1 / dist2 = (k1, k2, p1, p2) of the left / right camera; both pixels are undistorted, each through its own
+# camera, before the DLT and the gates (slam_kpset_triangulate_lens).  The lists keep the raw pixels.
+function triangulate_lens!(k::KeypointSet, P1::Matrix{Float64}, P2::Matrix{Float64}, T21::Matrix{Float64}, cam1, cam2, dist1, dist2, Twc::Matrix{Float64};
+                           max_error = 3.0, min_depth = 0.1, n_bound = 0)
+    c1 = collect(Float64, cam1); c2 = collect(Float64, cam2); d1 = collect(Float64, dist1); d2 = collect(Float64, dist2)
+    GC.@preserve P1 P2 T21 c1 c2 d1 d2 Twc check(ccall((:slam_kpset_triangulate_lens, LIB[]), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cdouble, Cdouble, Cint),
+        ctx(), k.h, P1, P2, T21, c1, c2, d1, d2, Twc, max_error, min_depth, n_bound))
+    k
+end
+# the stereo observations of stream s's list (1-based s, as upload! and download; restoring state): stereo_yx 2 x n (y, x) in the right image,
+# has_stereo n flags
+function upload_stereo!(k::KeypointSet, s, stereo_yx::Matrix{Float64}, has_stereo::Vector{UInt8})
+    n = length(has_stereo)
+    size(stereo_yx) == (2, n) || error("upload_stereo!: stereo_yx is $(size(stereo_yx)), has_stereo has $n flags")
+    GC.@preserve stereo_yx has_stereo check(ccall((:slam_kpset_upload_stereo, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Float64}, Ptr{UInt8}, Cint),
+        ctx(), k.h, s - 1, stereo_yx, has_stereo, n))
     k
 end
 
@@ -436,7 +456,7 @@ function newest(m::KeyframeMap)
 end
 # update_frame_covisibility! + match_local_map! (map_manager.jl:302-355, mapper.jl:265-383) on the map: enable_descriptors! once; per key-frame, after
 # add_keyframe!, add_descriptors! with the device arrays slam_kpset_detect_describe filled (desc_dev: S x dcap x 4 UInt64, info_dev: S x 2 Int64), then
-# local_map_match -> (status, n_pairs, pairs 2 x n (keypoint id, local-map id), dist), the streams back to back.  cam: 10 x S, no lens distortion.
+# local_map_match -> (status, n_pairs, pairs 2 x n (keypoint id, local-map id), dist), the streams back to back.  cam: 10 x S; lens distortion only after enable_pixels!.
 enable_descriptors!(m::KeyframeMap, n_bits::Integer = 256) =
     (check(ccall((:slam_kfmap_enable_descriptors, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint), ctx(), m.h, n_bits)); m)
 add_descriptors!(m::KeyframeMap, desc_dev::Ptr{UInt64}, info_dev::Ptr{Int64}, dcap::Integer) =
@@ -450,6 +470,18 @@ function local_map_match(m::KeyframeMap, cam::Matrix{Float64}, cell_size::Vector
                 ctx(), m.h, cam, cell_size, max_projection_distance, max_descriptor_distance, max_local, status, n_pairs, pairs, dist, cap_pairs))
     n = sum(n_pairs)
     (status = status, n_pairs = n_pairs, pairs = pairs[:, 1:n], dist = dist[1:n])
+end
+# Raw pixels in the map (slam_kfmap_enable_pixels, before the first add_keyframe!): kp.pixel of every observation beside the undistorted one -- from
+# then on local_map_match works on raw pixels, as find_best_match does, and takes cameras with lens distortion; merge! moves them with the
+# observations.  keyframe_pixels: 2 x n raw pixels (y, x) of key-frame kfid of stream s (0-based s and kfid, as download_keyframe and every KeyframeMap
+# wrapper) in download_keyframe's order, nothing when it is not in the ring.
+enable_pixels!(m::KeyframeMap) =
+    (check(ccall((:slam_kfmap_enable_pixels, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), ctx(), m.h)); m)
+function keyframe_pixels(m::KeyframeMap, s::Integer, kfid::Integer)
+    px = zeros(2, m.cap); n = Ref{Cint}(0)
+    check(ccall((:slam_kfmap_download_pixels, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cint, Ptr{Float64}, Cint, Ref{Cint}),
+                ctx(), m.h, s, kfid, px, m.cap, n))
+    n[] < 0 ? nothing : px[:, 1:n[]]
 end
 # The local-map history (slam_kfmap_enable_local_map_history): frame.local_map_ids kept between key-frames -- from then on local_map_match follows the
 # replace-or-union rule (map_manager.jl:350-354) and takes in the oldest covisible key-frame's set (mapper.jl:274-286).  local_map_ids: the set stored

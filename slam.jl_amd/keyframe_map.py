@@ -224,7 +224,7 @@ class KeyframeMap:
 
     def local_map_match(self, cam, cell_size, max_projection_distance, max_descriptor_distance, max_local=None, cap_pairs=None, ctx=None):
         """update_frame_covisibility! + match_local_map! for the newest key-frames of the streams of the last add_keyframe, staged and matched in
-        HBM.  cam: (10,) or (S, 10) = fx fy cx cy k1 k2 p1 p2 height width (no lens distortion); cell_size and the two distances: one value or S.
+        HBM.  cam: (10,) or (S, 10) = fx fy cx cy k1 k2 p1 p2 height width (lens distortion only after enable_pixels()); cell_size and the two distances: one value or S.
         max_local: the bound of a stream's local map (default 10 cap, the reference's 10 max_nb_keypoints).
         -> (status (S,), pairs: per stream an (n, 2) int64 array of (keypoint id, local-map point id) ascending by keypoint id, dist: per stream
         the (n,) winning descriptor distances).  status 0 matched, 1 nothing to match, 2 local map larger than max_local.  Synchronous."""
@@ -242,6 +242,21 @@ class KeyframeMap:
                                                  L.ptr(n, L.i32p), L.ptr(pairs, L.i64p), L.ptr(dist), cap_pairs))
         at = np.concatenate([[0], np.cumsum(n)])
         return status, [pairs[at[s]:at[s + 1]].copy() for s in range(S)], [dist[at[s]:at[s + 1]].copy() for s in range(S)]
+
+    def enable_pixels(self, ctx=None):
+        """Keep the raw pixel (kp.pixel) of every observation beside the undistorted one (slam_kfmap_enable_pixels, 16 R cap bytes per stream): from
+        then on local_map_match works on raw pixels, as find_best_match and the frame grid do, and takes cameras with lens distortion; merge moves
+        the raw pixels with the observations.  Call it before the first add_keyframe.  Opt-in; a second call is a no-op."""
+        c = ctx or self.ctx
+        c.check(c.lib.slam_kfmap_enable_pixels(c.h, self.h))
+
+    def keyframe_pixels(self, s, kfid, ctx=None):
+        """(n, 2) the raw pixels (y, x) of key-frame kfid of stream s in the order of download_keyframe's ids, or None when the ring does not hold it.
+        SlamHipError without enable_pixels().  Synchronous."""
+        c = ctx or self.ctx
+        px = np.zeros((self.cap, 2)); n = C.c_int(0)
+        c.check(c.lib.slam_kfmap_download_pixels(c.h, self.h, int(s), int(kfid), L.ptr(px), self.cap, C.byref(n)))
+        return None if n.value < 0 else px[:n.value].copy()
 
     def enable_local_map_history(self, ctx=None):
         """Keep frame.local_map_ids of every key-frame of the ring in HBM (slam_kfmap_enable_local_map_history): from then on local_map_match applies

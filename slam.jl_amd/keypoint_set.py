@@ -165,7 +165,10 @@ class KeypointSet:
                                                  e.cell_size, float(sigma_mask), float(min_response), L.ptr(pat, L.i32p), len(pat), float(sigma),
                                                  int(window), C.c_void_p(desc_ptr), C.c_void_p(info_ptr), int(dcap)))
 
-    def triangulate(self, cam1, cam2, T21, Twc, max_error, min_depth=0.1, n_bound=0, ctx=None):
+    def triangulate(self, cam1, cam2, T21, Twc, max_error, min_depth=0.1, n_bound=0, ctx=None, dist1=None, dist2=None):
+        """triangulate_stereo! on the lists.  dist1 / dist2: k1 k2 p1 p2 of the left / right lens (None: none) -- with either given the pixels
+        of both views are undistorted, each through its own camera, before the DLT and the gates (slam_kpset_triangulate_lens); with both
+        None the pixels are used as stored (slam_kpset_triangulate)."""
         from .triangulation import projection_matrices
         c = ctx or self.ctx
         P1, P2 = projection_matrices(cam1, cam2, T21)
@@ -173,8 +176,14 @@ class KeypointSet:
         c1 = np.ascontiguousarray(cam1, dtype=np.float64); c2 = np.ascontiguousarray(cam2, dtype=np.float64)
         W = np.asarray(Twc, dtype=np.float64).reshape(-1, 4, 4)
         W = np.ascontiguousarray(np.broadcast_to(W, (self.S, 4, 4)).transpose(0, 2, 1).reshape(self.S, 16))
-        c.check(c.lib.slam_kpset_triangulate(c.h, self.h, L.ptr(P1), L.ptr(P2), L.ptr(T), L.ptr(c1), L.ptr(c2), L.ptr(W),
-                                             float(max_error), float(min_depth), int(n_bound)))
+        if dist1 is None and dist2 is None:
+            c.check(c.lib.slam_kpset_triangulate(c.h, self.h, L.ptr(P1), L.ptr(P2), L.ptr(T), L.ptr(c1), L.ptr(c2), L.ptr(W),
+                                                 float(max_error), float(min_depth), int(n_bound)))
+            return
+        d1 = np.ascontiguousarray(np.zeros(4) if dist1 is None else dist1, dtype=np.float64).reshape(4)
+        d2 = np.ascontiguousarray(np.zeros(4) if dist2 is None else dist2, dtype=np.float64).reshape(4)
+        c.check(c.lib.slam_kpset_triangulate_lens(c.h, self.h, L.ptr(P1), L.ptr(P2), L.ptr(T), L.ptr(c1), L.ptr(c2), L.ptr(d1), L.ptr(d2), L.ptr(W),
+                                                  float(max_error), float(min_depth), int(n_bound)))
 
     def keyframe(self, ctx=None):
         """create_keyframe! for the lists: the current positions become the previous key-frame's observations (slam_kpset_keyframe)"""
@@ -186,6 +195,15 @@ class KeypointSet:
         k = np.ascontiguousarray(kyx, dtype=np.float64).reshape(-1, 2)
         f = np.ascontiguousarray(np.asarray(has_kf).astype(np.uint8))
         c.check(c.lib.slam_kpset_upload_keyframe(c.h, self.h, s, L.ptr(k), L.ptr(f, L.u8p), len(k)))
+
+    def upload_stereo(self, s, stereo_yx, has_stereo, ctx=None):
+        """the stereo observations of stream s's list (download() reads them back): stereo_yx (n, 2) in the right image, has_stereo (n,) flags"""
+        c = ctx or self.ctx
+        k = np.ascontiguousarray(stereo_yx, dtype=np.float64).reshape(-1, 2)
+        f = np.ascontiguousarray(np.asarray(has_stereo).astype(np.uint8)).reshape(-1)
+        if len(f) != len(k):
+            raise ValueError(f"upload_stereo: {len(k)} stereo pixels for {len(f)} flags")
+        c.check(c.lib.slam_kpset_upload_stereo(c.h, self.h, s, L.ptr(k), L.ptr(f, L.u8p), len(k)))
 
     def download_keyframe(self, s, ctx=None):
         c = ctx or self.ctx
