@@ -2,9 +2,10 @@
 (tests/np_kfmap_local_map.py) on the scripted scenes of tests/kfmap_lmm_scripts.py: S = 3 (stream 1 not selected at the last key-frame), cap 64 with
 about 40 keypoints per list, R = 4 (slots are reused, covisible slabs forgotten mid-sequence), mcap = 128 (ids wrap, an entry changes owner with its
 descriptor), a 70 x 105 image with cell 35 (a 2 x 3 grid), 8 key-frames; tests/test_kfmap_local_map_host.py shows that the scenes reach these edges,
-have margin >= 1e-9 and produce pairs.  Bars: ids, orders, pairs and distances are array_equal; proj_yx within 1e-9 px (the device forms Tcw from
-theta by angles_to_pose, the model by the same formula in numpy: the sines and cosines may differ in the last place; decisions are protected by the
-margin rule).  Every test fails without the slam_kfmap_* entry points."""
+have margin >= 1e-9 and produce pairs.  Bars: ids, orders, pairs, distances and proj_yx are array_equal (a key-frame's angles are computed on the
+device; add() -- tests/kfmap_device.py, the driver this file shares with the other map tests -- holds them to 1e-12 once and hands the device's
+bits to the model, so both sides form Tcw from the same theta; decisions are protected by the margin rule besides).  Every test fails without the
+slam_kfmap_* entry points."""
 import copy
 import os
 import sys
@@ -13,85 +14,24 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import kfmap_device as kd  # noqa: E402
 import kfmap_lmm_scripts as ls  # noqa: E402
-import kfmap_scripts as scr  # noqa: E402
 import np_kfmap_filter as npf  # noqa: E402
-import np_kfmap_local_map as nl  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 S = ls.S
-PX_TOL = 1e-9
-DCAP = 64
+DCAP = kd.DCAP
 
 
-class Pair(ls.ModelRun):
+class Pair(kd.DeviceSide, ls.ModelRun):
     """the device map with its keypoint set beside the models, driven by the same scripted key-frames and descriptors"""
+    match = ls.ModelRun.match                                      # the model's alone: these tests call device_match() and compare themselves
 
     def __init__(self, slam):
-        import torch
-        self.torch, self.slam = torch, slam
-        frames, descs = ls.scenes()
-        super().__init__(frames, descs)
-        self.ks = slam.KeypointSet(S, ls.CAP)
-        self.km = slam.KeyframeMap(S, ls.CAP, R=ls.R, mcap=ls.MCAP)
-        self.km.enable_descriptors()
-        self.Tcw = np.tile(np.eye(4), (S, 1, 1))
-        self.rows = [dict() for _ in range(S)]                     # id -> row, as the script handed them out (the cross-check's descriptors)
-
-    def close(self):
-        self.km.close(); self.ks.close()
-
-    def add(self, mask=None):
-        took = super().add(mask)
-        desc = np.full((S, DCAP, 4), 0x5555555555555555, dtype=np.uint64)       # an unselected stream offers rows too: they must not be taken
-        info = np.zeros((S, 2), dtype=np.int64)
-        for s in range(S):
-            info[s] = (10 ** 6, 3)
-        for s, (f, d) in took.items():
-            self.ks.upload(s, f["yx"], f["is_3d"], f["xyz"], f["ids"])
-            self.Tcw[s] = f["Tcw"]
-            info[s] = (d[0], len(d[1])); desc[s, :len(d[1])] = d[1]
-            self.rows[s].update({int(d[0]) + j: r for j, r in enumerate(d[1])})
-        sp = self.slam.stream_params(S, Tcw=self.Tcw, cam=ls.CAM10[:4], dist=np.zeros((S, 4)))
-        desc_dev = self.torch.from_numpy(desc.view(np.int64)).cuda(); info_dev = self.torch.from_numpy(info).cuda()
-        with self.ks.selected(mask):
-            self.ks.keyframe()
-            self.km.add_keyframe(self.ks, sp)
-            self.km.add_descriptors(desc_dev.data_ptr(), info_dev.data_ptr(), DCAP)
-        self.km.ctx.synchronize()                                  # (the device arrays above live until the copies have run)
-        return took
-
-    def device_match(self, **kw):
-        return self.km.local_map_match(ls.CAM10, ls.CELL, ls.PARAMS.max_projection_distance, ls.PARAMS.max_descriptor_distance, **kw)
-
-    def ba(self):
-        wins, status = self.km.gather(np.full(S, self.m[0].min_cov_score, dtype=np.int32))
-        sol = super().ba()
-        assert [w.stream for w in wins] == sorted(sol)
-        self.km.update(wins, [sol[w.stream][1] for w in wins], [sol[w.stream][2] for w in wins])
-        return sol
-
-    def check(self, got, want, staged=True):
-        status, pairs, dist = got
-        assert list(status) == [w["status"] for w in want]
-        for s in range(S):
-            assert pairs[s].dtype == np.int64 and np.array_equal(pairs[s], want[s]["pairs"]), s
-            assert np.array_equal(dist[s], want[s]["dist"]), s
-            if not staged or not self.sel[s]:
-                continue
-            d, w = self.km.debug_local_map(s), want[s]
-            assert np.array_equal(d["lm_ids"], w["lm_ids"]) and np.array_equal(d["kp_ids"], w["kp_ids"]), s
-            assert np.array_equal(d["best_kp"], w["best_kp"]) and np.array_equal(d["best_dist"], w["best_dist"]), s
-            assert np.array_equal(np.isnan(d["proj_yx"]), np.isnan(w["proj_yx"])), s
-            ok = ~np.isnan(w["proj_yx"])
-            assert np.all(np.abs(d["proj_yx"][ok] - w["proj_yx"][ok]) <= PX_TOL), s
+        super().__init__(slam, *ls.scenes())
 
     def snapshot(self):
-        out = []
-        for s in range(S):
-            d = [self.km.download_points(s)] + [self.km.download_keyframe(s, k) for k in range(self.nkf[s] + 1)]
-            out.append(repr([(sorted((k, np.asarray(v).tobytes() if not isinstance(v, list) else repr(v)) for k, v in x.items()) if x is not None else None) for x in d]))
-        return out
+        return self.device_bytes(range(S), staged=False)
 
     def run_to(self, n_kf, last_mask=None):
         """the shared sequence up to (and including) key-frame n_kf - 1, without its match"""
@@ -101,16 +41,7 @@ class Pair(ls.ModelRun):
                 self.ba()
 
 
-@pytest.fixture()
-def pair(slam):
-    made = []
-
-    def make():
-        made.append(Pair(slam))
-        return made[-1]
-    yield make
-    for p in made:
-        p.close()
+pair = kd.device_fixture(Pair, "pair")
 
 
 def test_device_equals_model_stage_by_stage(pair):
@@ -122,7 +53,7 @@ def test_device_equals_model_stage_by_stage(pair):
         p.add(ls.LAST_MASK if last else None)
         got, want = p.device_match(), p.match()
         assert all(w["margin"] >= 1e-9 for w in want)
-        p.check(got, want)
+        p.check_match(got, want)
         for s in range(S):
             n_pairs[s] += len(got[1][s])
         if last:                                                   # the unselected stream: status 1, and what the call before staged for it is untouched
@@ -134,42 +65,13 @@ def test_device_equals_model_stage_by_stage(pair):
     assert min(n_pairs) >= 5
 
 
-def _assemble(p, s):
-    """the arrays of the host-array path from DOWNLOADS of stream s's map (download_keyframe, download_points) and the script's descriptor rows, stated on
-    dicts and sets -> (frame, keypoints, keyframes, local_map, params), the local-map ids, the keypoint ids; None where there is nothing to match"""
-    cur = int(p.km.newest()[s])
-    kfs = {k: d for k in range(max(cur - ls.R + 1, 0), cur + 1) for d in [p.km.download_keyframe(s, k)] if d is not None}
-    pts = p.km.download_points(s)
-    point = {int(i): j for j, i in enumerate(pts["ids"])}
-    rows = p.rows[s]
-    live = {k: {int(i): tuple(px) for i, px, lv in zip(d["ids"], d["upx"], d["live"]) if lv} for k, d in kfs.items()}
-    if cur not in kfs:
-        return None
-    cov = set()
-    for i in live[cur]:
-        if i in point:
-            cov |= {o for o in pts["observers"][point[i]] if o != cur and o in kfs}
-    lm = sorted({i for o in cov for i in live[o] if i in point and pts["is_3d"][point[i]] and i in rows and cur not in pts["observers"][point[i]]})
-    order = sorted(kfs)
-    row = {k: j for j, k in enumerate(order)}
-    kp_ids = [i for i in live[cur] if i in point and i in rows]
-    if not cov or not lm or not kp_ids:
-        return None
-    keypoints = [{"pixel": live[cur][i], "descriptors": rows[i].reshape(1, 4),
-                  "observers": [(row[o], live[o][i]) for o in pts["observers"][point[i]] if o in kfs and i in live[o]]} for i in kp_ids]
-    local_map = [{"position": pts["xyz"][point[i]], "descriptors": rows[i].reshape(1, 4), "observers": [row[o] for o in pts["observers"][point[i]] if o in kfs]} for i in lm]
-    nb3 = sum(1 for i in live[cur] if i in point and pts["is_3d"][point[i]])
-    frame = {"Tcw": nl.tcw_of(kfs[cur]["theta"]), "cam": ls.CAM10, "cell_size": ls.CELL, "nb_3d_kpts": nb3}
-    return (frame, keypoints, np.array([nl.tcw_of(kfs[k]["theta"]) for k in order]), local_map, ls.PARAMS), lm, kp_ids
-
-
 def test_host_array_path_on_downloads_agrees(pair):
     """the parent's only route -- downloads, assembly on the host, slam_local_map_match_batch -- gives the device-staged call's answers"""
     p = pair()
     p.run_to(6)
     status, pairs, dist = p.device_match()
     staged = [p.km.debug_local_map(s) for s in range(S)]
-    made = [_assemble(p, s) for s in range(S)]
+    made = [kd.assemble(p, s) for s in range(S)]
     assert [m is not None for m in made] == [st == 0 for st in status] and sum(m is not None for m in made) >= 2
     res = p.slam.local_map_matching_batch([m[0] for m in made if m is not None])
     for s, r in zip([s for s in range(S) if made[s] is not None], res):
@@ -193,7 +95,7 @@ def test_after_a_filter_and_after_an_update_the_removed_take_no_part(pair):
     logs = [npf.filter_map(p.m[s], 0.999999, minc[s], first_kfid=0) for s in range(S)]
     assert [sorted(k for k, ex, _, _ in log if ex in ("few", "ratio")) for log in logs] == removed and sum(len(r) for r in removed) >= 2
     got, want = p.device_match(), p.match()
-    p.check(got, want)
+    p.check_match(got, want)
     for s in range(S):
         cur, d = p.nkf[s] - 1, p.km.debug_local_map(s)
         assert all(p.km.download_keyframe(s, k) is None for k in removed[s])
@@ -207,7 +109,7 @@ def test_after_a_filter_and_after_an_update_the_removed_take_no_part(pair):
     sol = p.ba()
     assert len(sol) >= 2
     got, want = p.device_match(), p.match()
-    p.check(got, want)
+    p.check_match(got, want)
     n_removed = 0
     for s in range(S):
         now = set(int(i) for i in p.km.download_points(s)["ids"])
@@ -222,20 +124,20 @@ def test_a_local_map_that_does_not_fit_is_status_2_and_leaves_the_others_alone(p
     p = pair()
     p.run_to(6)
     full, want = p.device_match(), p.match()
-    p.check(full, want)
+    p.check_match(full, want)
     sizes = [len(w["lm_ids"]) for w in want]
     big = int(np.argmax(sizes))
     assert sizes[big] > max(sizes[s] for s in range(S) if s != big) >= 1
     got = p.device_match(max_local=sizes[big] - 1)
     want2 = p.match(max_local=sizes[big] - 1)
     assert [w["status"] for w in want2] == [2 if s == big else want[s]["status"] for s in range(S)]
-    p.check(got, want2, staged=False)
+    p.check_match(got, want2, staged=False)
     assert len(got[1][big]) == 0 and len(p.km.debug_local_map(big)["lm_ids"]) == 0
     for s in range(S):
         if s != big:
             assert np.array_equal(got[1][s], full[1][s]) and np.array_equal(got[2][s], full[2][s])
     exact = p.device_match(max_local=sizes[big])                    # exactly as large as the bound: fits
-    p.check(exact, want)
+    p.check_match(exact, want)
 
 
 def test_the_call_has_no_side_effects(pair):

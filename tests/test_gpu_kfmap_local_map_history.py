@@ -4,10 +4,9 @@ match's pairs merged where they lie on the device, a local-BA update behind key-
 shows that the scene has, on every stream, pairs that only the chain of stored local maps brings, purged ids, re-used slots and margins >= 1e-9.
 
 After EVERY step the status, pairs, distances, the staged lists, the stored set of every key-frame of the ring (local_map_ids), every key-frame
-(download_keyframe) and the points (download_points) are array_equal to the model; proj_yx within 1e-9 px as in tests/test_gpu_kfmap_local_map.py (the
-device forms Tcw from theta by angles_to_pose, the model by the same formula in numpy).  A key-frame's angles are computed on the device; add() holds them
-to 1e-12 once and hands the device's bits to the model, as tests/test_gpu_kfmap_merge.py does.  Every test that enables the history fails without
-slam_kfmap_enable_local_map_history."""
+(download_keyframe) and the points (download_points) are array_equal to the model, proj_yx included.  A key-frame's angles are computed on the device;
+add() holds them to 1e-12 once and hands the device's bits to the model.  The device side of every step and every comparison are
+tests/kfmap_device.py's.  Every test that enables the history fails without slam_kfmap_enable_local_map_history."""
 import copy
 import os
 import sys
@@ -16,6 +15,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import kfmap_device as kd  # noqa: E402
 import kfmap_history_scripts as hs  # noqa: E402
 import kfmap_lmm_scripts as ls  # noqa: E402
 import np_kfmap_filter as npf  # noqa: E402
@@ -23,113 +23,19 @@ import np_kfmap_local_map_history as nh  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 S = hs.S
-DCAP = 64
-PX_TOL = 1e-9
-ANGLE_TOL = 1e-12
 FILTER_AT = 9
 
 
-class Pair(hs.HistoryRun):
+class Pair(kd.DeviceSide, hs.HistoryRun):
     """the device map with its keypoint set beside the models, driven by the same scripted key-frames and descriptors"""
+    device_pairs = True                                          # merge(): the model's of `pairs`, the device's of the pairs its last match left in HBM
 
     def __init__(self, slam, history=True, mcap=hs.MCAP, **kw):
-        import torch
-        self.torch, self.slam = torch, slam
-        super().__init__(history=history, mcap=mcap, **kw)
-        self.mcap = mcap
-        self.ks = slam.KeypointSet(S, hs.CAP)
-        self.km = slam.KeyframeMap(S, hs.CAP, R=hs.R, mcap=mcap)
-        self.km.enable_descriptors()
-        if history:
-            self.km.enable_local_map_history()
-        self.Tcw = np.tile(np.eye(4), (S, 1, 1))
-
-    def close(self):
-        self.km.close(); self.ks.close()
-
-    def add(self, mask=None):
-        took = super().add(mask)
-        desc = np.full((S, DCAP, 4), 0x5555555555555555, dtype=np.uint64)
-        info = np.tile(np.array([10 ** 6, 3], dtype=np.int64), (S, 1))
-        for s, (f, d) in took.items():
-            self.ks.upload(s, f["yx"], f["is_3d"], f["xyz"], f["ids"])
-            self.Tcw[s] = f["Tcw"]
-            info[s] = (d[0], len(d[1])); desc[s, :len(d[1])] = d[1]
-        sp = self.slam.stream_params(S, Tcw=self.Tcw, cam=ls.CAM10[:4], dist=np.zeros((S, 4)))
-        desc_dev = self.torch.from_numpy(desc.view(np.int64)).cuda(); info_dev = self.torch.from_numpy(info).cuda()
-        with self.ks.selected(mask):
-            self.ks.keyframe()
-            self.km.add_keyframe(self.ks, sp)
-            self.km.add_descriptors(desc_dev.data_ptr(), info_dev.data_ptr(), DCAP)
-        self.km.ctx.synchronize()
-        for s in took:                                           # the device's angles, checked to their bar, become the model's
-            k = self.nkf[s] - 1
-            th, ref = self.km.download_keyframe(s, k)["theta"], self.m[s].theta[k % hs.R]
-            assert np.array_equal(th[3:], ref[3:]) and np.all(np.abs(th[:3] - ref[:3]) <= ANGLE_TOL), (s, k)
-            self.m[s].theta[k % hs.R] = th
-        return took
-
-    def device_match(self, **kw):
-        return self.km.local_map_match(ls.CAM10, ls.CELL, ls.PARAMS.max_projection_distance, ls.PARAMS.max_descriptor_distance, **kw)
-
-    def match(self, max_local=None, **kw):
-        """the model's match, the device's checked against it: results, staged lists, stored sets"""
-        want = super().match(max_local=max_local, **kw)
-        got = self.device_match(**({} if max_local is None else dict(max_local=max_local)))
-        self.check_match(got, want)
-        return want
-
-    def check_match(self, got, want):
-        status, pairs, dist = got
-        assert list(status) == [w["status"] for w in want]
-        for s in range(S):
-            assert all(w["margin"] >= 1e-9 for w in want)
-            assert pairs[s].dtype == np.int64 and np.array_equal(pairs[s], want[s]["pairs"]), s
-            assert np.array_equal(dist[s], want[s]["dist"]), s
-            if not self.sel[s]:
-                continue
-            d, w = self.km.debug_local_map(s), want[s]
-            assert np.array_equal(d["lm_ids"], w["lm_ids"]) and np.array_equal(d["kp_ids"], w["kp_ids"]), s
-            assert np.array_equal(d["best_kp"], w["best_kp"]) and np.array_equal(d["best_dist"], w["best_dist"]), s
-            assert np.array_equal(np.isnan(d["proj_yx"]), np.isnan(w["proj_yx"])), s
-            ok = ~np.isnan(w["proj_yx"])
-            assert np.all(np.abs(d["proj_yx"][ok] - w["proj_yx"][ok]) <= PX_TOL), s
-        self.check_sets()
+        super().__init__(slam, history=history, mcap=mcap, lm_history=history, **kw)
 
     def device_sets(self, s):
         """{kfid: stored set, or the error's text} of every key-frame id the ring can hold"""
-        out = {}
-        for k in range(max(self.nkf[s] - hs.R, 0), self.nkf[s]):
-            try:
-                out[k] = self.km.local_map_ids(s, k)
-            except self.slam.SlamHipError as e:
-                out[k] = str(e)
-        return out
-
-    def check_sets(self):
-        if not self.history:
-            return
-        for s in range(S):
-            for k, got in self.device_sets(s).items():
-                want = self.H[s].ids(self.m[s], k)
-                if want is None:
-                    assert isinstance(got, str) and ("not in the ring" in got or "no local map was stored" in got), (s, k, got)
-                else:
-                    assert not isinstance(got, str) and got.dtype == np.int64 and np.array_equal(got, want), (s, k)
-
-    def merge(self, pairs):
-        """the model's merge of `pairs`, the device's of the pairs its last match left in HBM"""
-        want = super().merge(pairs).copy()
-        got = self.km.merge(None, None)
-        assert np.array_equal(got, want), (got, want)
-        return want
-
-    def ba(self):
-        wins, status = self.km.gather(np.full(S, self.m[0].min_cov_score, dtype=np.int32))
-        sol = super().ba()
-        assert [w.stream for w in wins] == sorted(sol)
-        self.km.update(wins, [sol[w.stream][1] for w in wins], [sol[w.stream][2] for w in wins])
-        return sol
+        return {k: kd.stored_set(self.km, s, k) for k in range(max(self.nkf[s] - hs.R, 0), self.nkf[s])}
 
     def remove_keyframe(self, s, kfid):
         super().remove_keyframe(s, kfid)
@@ -139,37 +45,8 @@ class Pair(hs.HistoryRun):
         super().reset(s)
         self.km.reset(s)
 
-    def check(self):
-        """every key-frame of the ring, the points and the stored sets of every stream against the models"""
-        for s, m in enumerate(self.m):
-            for k in range(max(self.nkf[s] - hs.R, 0), self.nkf[s]):
-                d, w = self.km.download_keyframe(s, k), m.keyframe(k)
-                assert (d is None) == (w is None), (s, k)
-                if w is not None:
-                    assert all(np.array_equal(d[key], w[key]) for key in ("theta", "ids", "upx", "live")), (s, k)
-            d, w = self.km.download_points(s), m.points()
-            assert all(np.array_equal(d[key], w[key]) for key in ("ids", "xyz", "is_3d", "observed", "ba", "gone")) and d["observers"] == w["observers"], s
-        self.check_sets()
 
-    def device_bytes(self, streams, staged=True):
-        out = []
-        for s in streams:
-            d = [self.km.download_points(s)] + [self.km.download_keyframe(s, k) for k in range(self.nkf[s] + 1)] + ([self.km.debug_local_map(s)] if staged else [])
-            sets = sorted((k, v if isinstance(v, str) else v.tobytes()) for k, v in self.device_sets(s).items()) if self.history else []
-            out.append(repr([(sorted((k, np.asarray(v).tobytes() if not isinstance(v, list) else repr(v)) for k, v in x.items()) if x is not None else None) for x in d]) + repr(sets))
-        return out
-
-
-@pytest.fixture()
-def pair(slam):
-    made = []
-
-    def make(**kw):
-        made.append(Pair(slam, **kw))
-        return made[-1]
-    yield make
-    for p in made:
-        p.close()
+pair = kd.device_fixture(Pair, "pair")
 
 
 def _filter(p):

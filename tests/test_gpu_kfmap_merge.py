@@ -8,7 +8,8 @@ After EVERY step -- add_keyframe + add_descriptors, local_map_match, merge, the 
 (download_keyframe), download_points and KeypointSet.download are array_equal to the model; the invariant (sorted, unique ids) is thereby tested
 through use: the add_keyframe, gather / update(ks), filter and local_map_match that follow a merge search the rebuilt slabs and lists.  No tolerance
 anywhere: the merge moves values, it computes none.  (A key-frame's angles are computed on the device in its own arithmetic; add() holds them to
-1e-12 once, as tests/test_gpu_kfmap_filter.py does, and hands the device's bits to the model.)  Every test fails without slam_kfmap_merge."""
+1e-12 once, as tests/test_gpu_kfmap_filter.py does, and hands the device's bits to the model.)  The device side of every step and every comparison
+are tests/kfmap_device.py's.  Every test fails without slam_kfmap_merge."""
 import copy
 import os
 import sys
@@ -17,127 +18,25 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import kfmap_device as kd  # noqa: E402
 import kfmap_lmm_scripts as ls  # noqa: E402
 import kfmap_merge_scripts as ms  # noqa: E402
 import kfmap_scripts as scr  # noqa: E402
 import np_kfmap as npk  # noqa: E402
 import np_kfmap_filter as npf  # noqa: E402
 import np_kfmap_merge as nm  # noqa: E402
+from kfmap_device import check_map, device_bytes  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 S = ls.S
-DCAP = 64
-ANGLE_TOL = 1e-12
 EMPTY = np.zeros((0, 2), dtype=np.int64)
 
 
-def check_map(km, ks, models, lists, R):
-    """every key-frame of the ring, the points and the live lists of every stream against the models"""
-    for s, m in enumerate(models):
-        for k in range(max(m.cur - R + 1, 0), m.cur + 1):
-            d, w = km.download_keyframe(s, k), m.keyframe(k)
-            assert (d is None) == (w is None), (s, k)
-            if w is not None:
-                assert all(np.array_equal(d[key], w[key]) for key in ("theta", "ids", "upx", "live")), (s, k)
-        d, w = km.download_points(s), m.points()
-        assert all(np.array_equal(d[key], w[key]) for key in ("ids", "xyz", "is_3d", "observed", "ba", "gone")) and d["observers"] == w["observers"], s
-        if lists[s] is not None:
-            d = ks.download(s)
-            assert all(np.array_equal(d[key], lists[s][key]) for key in ("ids", "yx", "is_3d", "xyz")), s
-
-
-def device_bytes(km, ks, streams, nkf, staged=True):
-    """what can be read back of the streams' share of the allocations, as bytes"""
-    out = []
-    for s in streams:
-        d = [km.download_points(s), ks.download(s)] + [km.download_keyframe(s, k) for k in range(nkf[s] + 1)] + ([km.debug_local_map(s)] if staged else [])
-        out.append(repr([(sorted((k, np.asarray(v).tobytes() if not isinstance(v, list) else repr(v)) for k, v in x.items()) if x is not None else None) for x in d]))
-    return out
-
-
-class Pair(ms.MergeRun):
+class Pair(kd.DeviceSide, ms.MergeRun):
     """the device map with its keypoint set beside the models, driven by the same scripted key-frames and descriptors"""
 
-    def __init__(self, slam, mode):
-        import torch
-        self.torch, self.slam = torch, slam
-        super().__init__(mode)
-        self.ks = slam.KeypointSet(S, ls.CAP)
-        self.km = slam.KeyframeMap(S, ls.CAP, R=ls.R, mcap=ls.MCAP)
-        self.km.enable_descriptors()
-        self.Tcw = np.tile(np.eye(4), (S, 1, 1))
-        self.dev_counts = None
 
-    def close(self):
-        self.km.close(); self.ks.close()
-
-    @property
-    def kset(self):
-        return self.ks if self.mode == "follow" else None
-
-    def add(self, mask=None):
-        took = super().add(mask)
-        desc = np.full((S, DCAP, 4), 0x5555555555555555, dtype=np.uint64)
-        info = np.tile(np.array([10 ** 6, 3], dtype=np.int64), (S, 1))
-        for s, (f, d) in took.items():
-            self.ks.upload(s, f["yx"], f["is_3d"], f["xyz"], f["ids"])
-            self.Tcw[s] = f["Tcw"]
-            info[s] = (d[0], len(d[1])); desc[s, :len(d[1])] = d[1]
-        sp = self.slam.stream_params(S, Tcw=self.Tcw, cam=ls.CAM10[:4], dist=np.zeros((S, 4)))
-        desc_dev = self.torch.from_numpy(desc.view(np.int64)).cuda(); info_dev = self.torch.from_numpy(info).cuda()
-        with self.ks.selected(mask):
-            self.ks.keyframe()
-            self.km.add_keyframe(self.ks, sp)
-            self.km.add_descriptors(desc_dev.data_ptr(), info_dev.data_ptr(), DCAP)
-        self.km.ctx.synchronize()
-        for s in took:                                           # the device's angles, checked to their bar, become the model's
-            k = self.nkf[s] - 1
-            th, ref = self.km.download_keyframe(s, k)["theta"], self.m[s].theta[k % ls.R]
-            assert np.array_equal(th[3:], ref[3:]) and np.all(np.abs(th[:3] - ref[:3]) <= ANGLE_TOL), (s, k)
-            self.m[s].theta[k % ls.R] = th
-        return took
-
-    def match(self, **kw):
-        """the model's match, the device's checked against it"""
-        want = super().match(**kw)
-        status, pairs, dist = self.km.local_map_match(ls.CAM10, ls.CELL, ls.PARAMS.max_projection_distance, ls.PARAMS.max_descriptor_distance)
-        assert list(status) == [w["status"] for w in want]
-        for s in range(S):
-            assert np.array_equal(pairs[s], want[s]["pairs"]) and np.array_equal(dist[s], want[s]["dist"]), s
-        return want
-
-    def merge(self, pairs, device_pairs=False):
-        want = super().merge(pairs).copy()
-        self.dev_counts = self.km.merge(self.kset, None if device_pairs else [np.asarray(p, dtype=np.int64).reshape(-1, 2) for p in pairs])
-        assert np.array_equal(self.dev_counts, want), (self.dev_counts, want)
-        return want
-
-    def ba(self):
-        wins, status = self.km.gather(np.full(S, self.m[0].min_cov_score, dtype=np.int32))
-        sol = super().ba()
-        assert [w.stream for w in wins] == sorted(sol)
-        for w in wins:                                           # the gather searched the rebuilt slabs: the window is the model's
-            ref = sol[w.stream][0]
-            P = len(ref["poses_remap"])
-            assert np.array_equal(w.cache.theta[6 * P:], ref["theta"][6 * P:]) and np.array_equal(w.cache.pixels, ref["pixels"])
-            assert np.array_equal(w.obs_kf, ref["obs_kf"]) and np.array_equal(w.obs_kp, ref["obs_kp"]) and np.array_equal(w.points_remap, ref["points_remap"])
-        self.km.update(wins, [sol[w.stream][1] for w in wins], [sol[w.stream][2] for w in wins], ks=self.kset)
-        return sol
-
-    def check(self):
-        check_map(self.km, self.ks, self.m, self.lists, ls.R)
-
-
-@pytest.fixture()
-def pair(slam):
-    made = []
-
-    def make(mode):
-        made.append(Pair(slam, mode))
-        return made[-1]
-    yield make
-    for p in made:
-        p.close()
+pair = kd.device_fixture(Pair, "pair")
 
 
 @pytest.mark.parametrize("mode", ms.MODES)
@@ -160,11 +59,11 @@ def test_device_equals_model_after_every_step(pair, mode):
         on_step("match", k, res)
         pairs = [r["pairs"] if r["status"] == 0 else EMPTY for r in res]
         idle = [s for s in range(S) if len(pairs[s]) == 0]
-        before = device_bytes(p.km, p.ks, idle, p.nkf, staged=False)
+        before = p.device_bytes(idle, staged=False)
         p.merge(pairs, device_pairs=True)
         on_step("merge", k, pairs)
         if idle and len(idle) < S:                               # a stream without pairs beside streams with pairs: its bytes are what they were
-            assert device_bytes(p.km, p.ks, idle, p.nkf, staged=False) == before
+            assert p.device_bytes(idle, staged=False) == before
             seen["idle"] += 1
         if k == ms.HAND_AT:
             hp, kinds = p.hand()
@@ -198,14 +97,14 @@ def test_device_pairs_equal_host_pairs(pair):
         a.merge(pairs, device_pairs=True)
         b.merge(pairs, device_pairs=False)
         assert np.array_equal(a.dev_counts, b.dev_counts)
-        assert device_bytes(a.km, a.ks, range(S), a.nkf) == device_bytes(b.km, b.ks, range(S), b.nkf)
+        assert a.device_bytes(range(S)) == b.device_bytes(range(S))
         n += int(a.dev_counts[:, 0].sum())
         if k in ls.BA_AT:
             a.ba(); b.ba()
     assert n >= 5
     # a match's pairs are consumed once: a second merge without a new match has no pairs and changes nothing
-    before = device_bytes(a.km, a.ks, range(S), a.nkf)
-    assert not a.km.merge(a.ks).any() and device_bytes(a.km, a.ks, range(S), a.nkf) == before
+    before = a.device_bytes(range(S))
+    assert not a.km.merge(a.ks).any() and a.device_bytes(range(S)) == before
 
 
 def test_a_call_without_pairs_changes_nothing(pair):
@@ -215,11 +114,11 @@ def test_a_call_without_pairs_changes_nothing(pair):
         p.match()
         if k in ls.BA_AT:
             p.ba()
-    before = device_bytes(p.km, p.ks, range(S), p.nkf)
+    before = p.device_bytes(range(S))
     assert not p.km.merge(p.ks, [EMPTY] * S).any()
     assert p.km.merge(None, [EMPTY] * S, want_counts=False) is None
     p.km.ctx.synchronize()
-    assert device_bytes(p.km, p.ks, range(S), p.nkf) == before
+    assert p.device_bytes(range(S)) == before
     status, pairs, dist = p.km.local_map_match(ls.CAM10, ls.CELL, ls.PARAMS.max_projection_distance, ls.PARAMS.max_descriptor_distance)
     want = ms.MergeRun.match(p)
     assert all(np.array_equal(pairs[s], want[s]["pairs"]) for s in range(S)) and sum(len(x) for x in pairs) >= 1      # the descriptors are where they were
@@ -236,7 +135,7 @@ def test_argument_errors_enqueue_nothing(pair, slam):
     assert sum(len(x) for x in pairs) >= 2
     # a pending window (the reference merges under optimization_lock): device pairs and host pairs alike
     wins, status = p.km.gather(np.full(S, p.m[0].min_cov_score, dtype=np.int32))
-    before = device_bytes(p.km, p.ks, range(S), p.nkf)          # (behind the gather: it demotes is_bad points itself)
+    before = p.device_bytes(range(S))          # (behind the gather: it demotes is_bad points itself)
     busy = [w.stream for w in wins if len(pairs[w.stream])]
     assert busy
     with pytest.raises(slam.SlamHipError, match="pending"):
@@ -254,7 +153,7 @@ def test_argument_errors_enqueue_nothing(pair, slam):
     with pytest.raises(slam.SlamHipError, match="pairs"):
         p.km.merge(None, [np.stack([np.arange(ls.CAP + 1), 10 ** 6 + np.arange(ls.CAP + 1)], axis=1)] + [EMPTY] * (S - 1))
     p.km.ctx.synchronize()
-    assert device_bytes(p.km, p.ks, range(S), p.nkf) == before
+    assert p.device_bytes(range(S)) == before
     # the device-pairs path on a map without descriptors (there is no match whose pairs to take)
     plain = slam.KeyframeMap(S, ls.CAP, R=ls.R, mcap=ls.MCAP)
     try:
@@ -292,9 +191,7 @@ def test_the_hand_built_case_across_a_chunk_edge(slam):
         ks.keyframe()
         km.add_keyframe(ks, slam.stream_params(S, Tcw=Tcw, cam=ls.CAM10[:4], dist=np.zeros((S, 4))))
         for s in range(S):
-            th, ref = km.download_keyframe(s, k)["theta"], models[s].theta[k % ms.HR]
-            assert np.array_equal(th[3:], ref[3:]) and np.all(np.abs(th[:3] - ref[:3]) <= ANGLE_TOL), (s, k)
-            models[s].theta[k % ms.HR] = th
+            kd.hand_over_theta(km, models[s], s, k)
     try:
         for k in range(ms.HKF):
             record(k)
@@ -305,7 +202,7 @@ def test_the_hand_built_case_across_a_chunk_edge(slam):
             ks.upload_keyframe(s, extra["kyx"], extra["has_kf"])
             ks.upload_first(s, extra["first_yx"], extra["first_kf"], ms.HKF)
             lists.append(dict(ids=f["ids"].copy(), yx=f["yx"].copy(), is_3d=f["is_3d"].copy(), xyz=f["xyz"].copy(), **extra))
-        check_map(km, ks, models, lists, ms.HR)
+        check_map(km, ks, models, lists)
         nkf = [ms.HKF - 1] * S
         idle = device_bytes(km, ks, [0], nkf, staged=False)
         pairs = [EMPTY] + [np.array(ms.HAND_PAIRS, dtype=np.int64)] * (S - 1)
@@ -316,7 +213,7 @@ def test_the_hand_built_case_across_a_chunk_edge(slam):
             want[s] = (r["applied"], r["skipped"], r["renamed"], r["status"])
         got = km.merge(ks, pairs)
         assert np.array_equal(got, want) and tuple(got[1]) == (23, 3, got[1][2], 0) and got[1][2] >= 60
-        check_map(km, ks, models, lists, ms.HR)
+        check_map(km, ks, models, lists)
         assert device_bytes(km, ks, [0], nkf, staged=False) == idle
         for s in range(S):                                       # the fields the plain download does not show
             kyx, has_kf = ks.download_keyframe(s)
@@ -332,7 +229,7 @@ def test_the_hand_built_case_across_a_chunk_edge(slam):
         # through use: the next key-frame is recorded from the lists as the merge left them in HBM
         lists = [{key: l[key] for key in ("ids", "yx", "is_3d", "xyz")} for l in lists]
         record(ms.HKF, lists)
-        check_map(km, ks, models, lists, ms.HR)
+        check_map(km, ks, models, lists)
         wins, status = km.gather(np.full(S, 8, dtype=np.int32))
         assert [w.stream for w in wins] == list(range(S))
         sol = {}
@@ -343,10 +240,10 @@ def test_the_hand_built_case_across_a_chunk_edge(slam):
             lists[s] = npk.update(models[s], win, theta, outl, lists[s])
             sol[s] = (theta, outl)
         km.update(wins, [sol[s][0] for s in range(S)], [sol[s][1] for s in range(S)], ks=ks)
-        check_map(km, ks, models, lists, ms.HR)
+        check_map(km, ks, models, lists)
         removed = km.filter(0.5, 8, first_kfid=0)
         logs = [npf.filter_map(models[s], 0.5, 8, first_kfid=0) for s in range(S)]
         assert [sorted(k for k, ex, _, _ in log if ex in ("few", "ratio")) for log in logs] == removed
-        check_map(km, ks, models, lists, ms.HR)
+        check_map(km, ks, models, lists)
     finally:
         km.close(); ks.close()

@@ -6,7 +6,7 @@ add_descriptors -> local_map_match with the history -> merge of the match's pair
 filter.  After EVERY call the device equals the numpy models (np_kfmap, np_kfmap_filter, np_kfmap_local_map_history, np_kfmap_merge): statuses, pairs,
 distances, staged lists, merge counts, gathered windows, removed key-frames, every key-frame of the ring (download_keyframe), the points
 (download_points) and every stored local map (local_map_ids) array_equal; a key-frame's angles to 1e-12 (computed on the device, then handed to the
-model) and proj_yx to 1e-9 px, as in tests/test_gpu_kfmap.py and tests/test_gpu_kfmap_local_map_history.py.
+model, as in tests/test_gpu_kfmap.py) and proj_yx to 1e-9 px.  The device side of every step and every comparison are tests/kfmap_device.py's.
 
 test_the_models_alone_reach_the_edges runs the same sequence on the models alone, without a GPU, and shows what it reaches."""
 import copy
@@ -17,13 +17,12 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import kfmap_device as kd  # noqa: E402
 import kfmap_history_scripts as hs  # noqa: E402
-import kfmap_lmm_scripts as ls  # noqa: E402
 import np_kfmap_filter as npf  # noqa: E402
 
 S, CAP, MCAP, DCAP, MINC = 2, 65, 130, 65, 4
 N_KF = {2: 6, 64: 70}
-PX_TOL, ANGLE_TOL = 1e-9, 1e-12
 
 
 def sizes(n_kf):
@@ -114,83 +113,14 @@ def test_the_models_alone_reach_the_edges(R):
         assert sum(seen["pairs"]) >= 1 and sum(seen["wins"]) >= 1, seen
 
 
-class Pair(Run):
+class Pair(kd.DeviceSide, Run):
     """the device map with its keypoint set beside the models"""
+    dcap = DCAP
+    device_pairs = True                                          # merge(): the pairs the last match left in HBM
+    proj_tol = kd.PX_TOL                                         # staged proj_yx: the device's sines and cosines of a late key-frame's angles differ in the last place
 
     def __init__(self, slam, R):
-        import torch
-        self.torch, self.slam = torch, slam
-        super().__init__(R)
-        self.ks = slam.KeypointSet(S, CAP)
-        self.km = slam.KeyframeMap(S, CAP, R=R, mcap=MCAP)
-        self.km.enable_descriptors()
-        self.km.enable_local_map_history()
-        self.Tcw = np.tile(np.eye(4), (S, 1, 1))
-
-    def close(self):
-        self.km.close(); self.ks.close()
-
-    def add(self, mask=None):
-        took = super().add(mask)
-        desc = np.full((S, DCAP, 4), 0x5555555555555555, dtype=np.uint64)
-        info = np.tile(np.array([10 ** 6, 3], dtype=np.int64), (S, 1))
-        for s, (f, d) in took.items():
-            self.ks.upload(s, f["yx"], f["is_3d"], f["xyz"], f["ids"])
-            self.Tcw[s] = f["Tcw"]
-            info[s] = (d[0], len(d[1])); desc[s, :len(d[1])] = d[1]
-        sp = self.slam.stream_params(S, Tcw=self.Tcw, cam=ls.CAM10[:4], dist=np.zeros((S, 4)))
-        desc_dev = self.torch.from_numpy(desc.view(np.int64)).cuda(); info_dev = self.torch.from_numpy(info).cuda()
-        with self.ks.selected(mask):
-            self.ks.keyframe()
-            self.km.add_keyframe(self.ks, sp)
-            self.km.add_descriptors(desc_dev.data_ptr(), info_dev.data_ptr(), DCAP)
-        self.km.ctx.synchronize()
-        for s in took:                                           # the device's angles, checked to their bar, become the model's
-            k = self.nkf[s] - 1
-            th, ref = self.km.download_keyframe(s, k)["theta"], self.m[s].theta[k % self.R]
-            assert np.array_equal(th[3:], ref[3:]) and np.all(np.abs(th[:3] - ref[:3]) <= ANGLE_TOL), (s, k)
-            self.m[s].theta[k % self.R] = th
-        return took
-
-    def match(self, max_local=None, **kw):
-        want = super().match(max_local=max_local, **kw)
-        status, pairs, dist = self.km.local_map_match(ls.CAM10, ls.CELL, ls.PARAMS.max_projection_distance, ls.PARAMS.max_descriptor_distance, max_local=max_local)
-        assert list(status) == [w["status"] for w in want]
-        for s in range(S):
-            w = want[s]
-            assert w["margin"] >= 1e-9
-            assert pairs[s].dtype == np.int64 and np.array_equal(pairs[s], w["pairs"]) and np.array_equal(dist[s], w["dist"]), s
-            if not self.sel[s]:
-                continue
-            d = self.km.debug_local_map(s)
-            assert np.array_equal(d["lm_ids"], w["lm_ids"]) and np.array_equal(d["kp_ids"], w["kp_ids"]), s
-            assert np.array_equal(d["best_kp"], w["best_kp"]) and np.array_equal(d["best_dist"], w["best_dist"]), s
-            assert np.array_equal(np.isnan(d["proj_yx"]), np.isnan(w["proj_yx"])), s
-            ok = ~np.isnan(w["proj_yx"])
-            assert np.all(np.abs(d["proj_yx"][ok] - w["proj_yx"][ok]) <= PX_TOL), s
-        return want
-
-    def merge(self, pairs):
-        want = super().merge(pairs).copy()
-        got = self.km.merge(None, None)
-        assert np.array_equal(got, want), (got, want)
-        return want
-
-    def ba(self):
-        wins, status = self.km.gather(np.full(S, MINC, dtype=np.int32))
-        sol = super().ba()
-        assert list(status) == [3 if not self.sel[s] else (0 if s in sol else 1) for s in range(S)]
-        assert [w.stream for w in wins] == sorted(sol)
-        for w in wins:
-            ref, c = sol[w.stream][0], w.cache
-            P = len(ref["poses_remap"])
-            for a, b in ((c.theta_const, ref["theta_const"]), (c.poses_ids, ref["poses_ids"]), (c.points_ids, ref["points_ids"]), (w.poses_remap, ref["poses_remap"]),
-                         (w.points_remap, ref["points_remap"]), (w.obs_kf, ref["obs_kf"]), (w.obs_kp, ref["obs_kp"]), (w.obs_in_covmap, ref["obs_in_covmap"]),
-                         (c.pixels, ref["pixels"]), (c.theta, ref["theta"])):
-                assert a.dtype == b.dtype and np.array_equal(a, b), w.stream      # (the poses' angles are the device's own bits: add() gave them to the model)
-            assert P >= 1 and c.poses_ids.min() >= 1 and c.points_ids.min() >= 1
-        self.km.update(wins, [sol[w.stream][1] for w in wins], [sol[w.stream][2] for w in wins])
-        return sol
+        super().__init__(slam, R, lm_history=True)
 
     def filter(self):
         ratio, minc = self.filter_args()
@@ -198,26 +128,6 @@ class Pair(Run):
         want, logs = super().filter()
         assert got == want, (got, want)
         return want, logs
-
-    def check(self):
-        """every key-frame the ring can hold, the points and the stored sets of every stream against the models"""
-        for s, m in enumerate(self.m):
-            for k in range(max(self.nkf[s] - self.R, 0), self.nkf[s] + 1):
-                d, w = self.km.download_keyframe(s, k), m.keyframe(k)
-                assert (d is None) == (w is None), (s, k)
-                if w is not None:
-                    assert all(np.array_equal(d[key], w[key]) for key in ("theta", "ids", "upx", "live")), (s, k)
-                try:
-                    got = self.km.local_map_ids(s, k)
-                except self.slam.SlamHipError as e:
-                    got = str(e)
-                want = self.H[s].ids(m, k)
-                if want is None:
-                    assert isinstance(got, str) and ("not in the ring" in got or "no local map was stored" in got), (s, k, got)
-                else:
-                    assert not isinstance(got, str) and got.dtype == np.int64 and np.array_equal(got, want), (s, k)
-            d, w = self.km.download_points(s), m.points()
-            assert all(np.array_equal(d[key], w[key]) for key in ("ids", "xyz", "is_3d", "observed", "ba", "gone")) and d["observers"] == w["observers"], s
 
 
 @pytest.mark.gpu

@@ -6,7 +6,7 @@ removed key-frames is decided between concurrent slabs) and once more match and 
 
 After EVERY step descriptor_rows of every stream, every key-frame of the ring, download_points and the live lists are array_equal to the model; after
 every match the status, pairs, distances and the staged lists (debug_local_map) are.  Hamming distances are integers: no tolerance anywhere.  (A
-key-frame's angles are computed on the device in its own arithmetic; add() holds them to 1e-12 once, as tests/test_gpu_kfmap_merge.py does, and hands
+key-frame's angles are computed on the device in its own arithmetic; add() -- tests/kfmap_device.py's -- holds them to 1e-12 once and hands
 the device's bits to the model.)  tests/test_kfmap_rows_host.py holds the model to the reference and shows what the scenes hold.
 
 A hand-built stream at cap 300 (R = 4, mcap = 1024, D = 3) puts more than 256 points into the local map and more than 256 described keypoints into
@@ -19,117 +19,26 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import kfmap_device as kd  # noqa: E402
 import kfmap_lmm_scripts as ls  # noqa: E402
 import kfmap_merge_scripts as ms  # noqa: E402
 import kfmap_rows_scripts as rs  # noqa: E402
 import kfmap_scripts as scr  # noqa: E402
 import np_kfmap as npk  # noqa: E402
 import np_kfmap_rows as nr  # noqa: E402
+from kfmap_device import check_map, check_staged, upload_descriptors  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 S = ls.S
-DCAP = 64
-ANGLE_TOL = 1e-12
 EMPTY = np.zeros((0, 2), dtype=np.int64)
 
 
-def upload_descriptors(torch, km, S_, dcap, per_stream):
-    """km.add_descriptors of {stream: (first id, rows)}; the other streams announce three rows of an id the map never held"""
-    desc = np.full((S_, dcap, 4), 0x5555555555555555, dtype=np.uint64)
-    info = np.tile(np.array([10 ** 6, 3], dtype=np.int64), (S_, 1))
-    for s, (first, rows) in per_stream.items():
-        info[s] = (first, len(rows)); desc[s, :len(rows)] = rows
-    desc_dev = torch.from_numpy(desc.view(np.int64)).cuda(); info_dev = torch.from_numpy(info).cuda()
-    km.add_descriptors(desc_dev.data_ptr(), info_dev.data_ptr(), dcap)
-    km.ctx.synchronize()                                         # (the tensors live until the kernel has read them)
-
-
-def check_map(km, ks, models, lists, R):
-    for s, m in enumerate(models):
-        for k in range(max(m.cur - R + 1, 0), m.cur + 1):
-            d, w = km.download_keyframe(s, k), m.keyframe(k)
-            assert (d is None) == (w is None), (s, k)
-            if w is not None:
-                assert all(np.array_equal(d[key], w[key]) for key in ("theta", "ids", "upx", "live")), (s, k)
-        d, w = km.download_points(s), m.points()
-        assert all(np.array_equal(d[key], w[key]) for key in ("ids", "xyz", "is_3d", "observed", "ba", "gone")) and d["observers"] == w["observers"], s
-        if ks is not None and lists[s] is not None:
-            d = ks.download(s)
-            assert all(np.array_equal(d[key], lists[s][key]) for key in ("ids", "yx", "is_3d", "xyz")), s
-
-
-def check_staged(km, want, streams):
-    for s in streams:
-        got, w = km.debug_local_map(s), want[s]
-        assert np.array_equal(got["lm_ids"], w["lm_ids"]) and np.array_equal(got["kp_ids"], w["kp_ids"]), s
-        assert np.array_equal(got["best_kp"], w["best_kp"]) and np.array_equal(got["best_dist"], w["best_dist"]), s
-        assert np.array_equal(got["proj_yx"], w["proj_yx"], equal_nan=True), s
-
-
-class Dev(rs.RowsRun):
+class Dev(kd.DeviceSide, rs.RowsRun):
     """the device map with its keypoint set beside the models, driven by the same scripted key-frames and descriptors; max_rows = None: a map that
     never enables the rows, beside the one-row models"""
 
     def __init__(self, slam, mode, max_rows, **kw):
-        import torch
-        self.torch, self.slam = torch, slam
-        super().__init__(mode, max_rows, **kw)
-        self.ks = slam.KeypointSet(S, ls.CAP)
-        self.km = slam.KeyframeMap(S, ls.CAP, R=ls.R, mcap=ls.MCAP)
-        self.km.enable_descriptors()
-        if max_rows is not None:
-            self.km.enable_descriptor_rows(max_rows)
-        self.Tcw = np.tile(np.eye(4), (S, 1, 1))
-        self.dev_counts = None
-
-    def close(self):
-        self.km.close(); self.ks.close()
-
-    @property
-    def kset(self):
-        return self.ks if self.mode == "follow" else None
-
-    def add(self, mask=None):
-        took = super().add(mask)
-        for s, (f, d) in took.items():
-            self.ks.upload(s, f["yx"], f["is_3d"], f["xyz"], f["ids"])
-            self.Tcw[s] = f["Tcw"]
-        sp = self.slam.stream_params(S, Tcw=self.Tcw, cam=ls.CAM10[:4], dist=np.zeros((S, 4)))
-        with self.ks.selected(mask):
-            self.ks.keyframe()
-            self.km.add_keyframe(self.ks, sp)
-            upload_descriptors(self.torch, self.km, S, DCAP, {s: d for s, (f, d) in took.items()})
-        for s in took:
-            k = self.nkf[s] - 1
-            th, ref = self.km.download_keyframe(s, k)["theta"], self.m[s].theta[k % ls.R]
-            assert np.array_equal(th[3:], ref[3:]) and np.all(np.abs(th[:3] - ref[:3]) <= ANGLE_TOL), (s, k)
-            self.m[s].theta[k % ls.R] = th
-        return took
-
-    def match(self, max_local=None):
-        want = super().match(max_local=max_local)
-        status, pairs, dist = self.km.local_map_match(ls.CAM10, ls.CELL, ls.PARAMS.max_projection_distance, ls.PARAMS.max_descriptor_distance, max_local=max_local)
-        assert list(status) == [w["status"] for w in want]
-        for s in range(S):
-            assert np.array_equal(pairs[s], want[s]["pairs"]) and np.array_equal(dist[s], want[s]["dist"]), s
-        check_staged(self.km, want, [s for s in range(S) if self.sel[s]])
-        return want
-
-    def merge(self, pairs, device_pairs=False, mutant=None):
-        want = super().merge(pairs).copy()
-        self.dev_counts = self.km.merge(self.kset, None if device_pairs else [np.asarray(p, dtype=np.int64).reshape(-1, 2) for p in pairs])
-        assert np.array_equal(self.dev_counts, want), (self.dev_counts, want)
-        return want
-
-    def ba(self):
-        wins, status = self.km.gather(np.full(S, self.m[0].min_cov_score, dtype=np.int32))
-        sol = super().ba()
-        assert [w.stream for w in wins] == sorted(sol)
-        for w in wins:
-            ref = sol[w.stream][0]
-            assert np.array_equal(w.obs_kf, ref["obs_kf"]) and np.array_equal(w.obs_kp, ref["obs_kp"]) and np.array_equal(w.points_remap, ref["points_remap"])
-        self.km.update(wins, [sol[w.stream][1] for w in wins], [sol[w.stream][2] for w in wins], ks=self.kset)
-        return sol
+        super().__init__(slam, mode, max_rows, descriptor_rows=max_rows, **kw)
 
     def filter(self, ratio, minc, first_kfid=0):
         logs = super().filter(ratio, minc, first_kfid)
@@ -137,23 +46,8 @@ class Dev(rs.RowsRun):
         assert [sorted(k for k, ex, _, _ in log if ex in ("few", "ratio")) for log in logs] == removed
         return logs
 
-    def check(self):
-        check_map(self.km, self.ks, self.m, self.lists, ls.R)
-        if self.max_rows is not None:
-            for s in range(S):
-                assert nr.same_rows(self.km.descriptor_rows(s), self.rows(s)), s
 
-
-@pytest.fixture()
-def dev(slam):
-    made = []
-
-    def make(mode, max_rows, **kw):
-        made.append(Dev(slam, mode, max_rows, **kw))
-        return made[-1]
-    yield make
-    for p in made:
-        p.close()
+dev = kd.device_fixture(Dev, "dev")
 
 
 def _sequence(p):
@@ -296,9 +190,7 @@ def test_row_offsets_cross_a_chunk_edge(slam):
                 rows = np.array([ls.random_row(seed, i) for i in range(first, first + n)], dtype=np.uint64)
                 nr.add_descriptors(m, D, first, rows)
                 upload_descriptors(torch, km, 1, HDCAP, {0: (first, rows)})
-            th = km.download_keyframe(0, k)["theta"]
-            assert np.all(np.abs(th - m.theta[k % HR]) <= ANGLE_TOL)
-            m.theta[k % HR] = th
+            kd.hand_over_theta(km, m, 0, k)
         for pairs in H_MERGES:                                   # the rows come from host-pair merges (a new id once per call: two calls)
             want = nr.merge(m, D, np.array(pairs, dtype=np.int64), None, with_list=False)
             got = km.merge(None, [np.array(pairs, dtype=np.int64)])
@@ -311,6 +203,6 @@ def test_row_offsets_cross_a_chunk_edge(slam):
         status, pairs, dist = km.local_map_match(ls.CAM10, ls.CELL, ls.PARAMS.max_projection_distance, ls.PARAMS.max_descriptor_distance, max_local=HMCAP)
         assert status[0] == 0 and np.array_equal(pairs[0], want["pairs"]) and np.array_equal(dist[0], want["dist"])
         check_staged(km, [want], [0])
-        check_map(km, None, [m], [None], HR)
+        check_map(km, None, [m])
     finally:
         km.close(); ks.close()

@@ -18,72 +18,38 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import kfmap_device as kd  # noqa: E402
 import kfmap_tri_scripts as ts  # noqa: E402
-import np_kfmap_rows as nr  # noqa: E402
 import np_kfmap_tri as nt  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-ANGLE_TOL = 1e-12
 DCAP = 320
 
 
-def device_bytes(km, ks, s, nkf):
-    """what can be read back of stream s's share of the allocations, as bytes"""
-    d = [km.download_points(s), ks.download(s)] + [km.download_keyframe(s, k) for k in range(nkf)]
-    return repr([(sorted((k, np.asarray(v).tobytes() if not isinstance(v, list) else repr(v)) for k, v in x.items()) if x is not None else None) for x in d])
-
-
-class Dev(ts.TriRun):
+class Dev(kd.DeviceSide, ts.TriRun):
     """the device map with its keypoint set beside the models, driven through the same steps"""
+    dcap = DCAP
 
     def __init__(self, slam, want_counts=True, **kw):
-        import torch
-        self.torch, self.slam, self.want_counts = torch, slam, want_counts
-        super().__init__(**kw)
-        self.ks = slam.KeypointSet(self.S, self.cap)
-        self.km = slam.KeyframeMap(self.S, self.cap, R=self.R, mcap=self.mcap)
-        if self.rows:
-            self.km.enable_descriptors()
-            self.km.enable_descriptor_rows(self.rows)
-        self.Tcw = np.tile(np.eye(4), (self.S, 1, 1))
-        self.dev_wins = None
-        self.n_pos = 0
-
-    def close(self):
-        self.km.close(); self.ks.close()
+        rows = kw.get("rows", 0)
+        super().__init__(slam, descriptors=bool(rows), descriptor_rows=rows or None, **kw)
+        self.want_counts, self.n_pos = want_counts, 0
 
     @property
     def kset(self):
         return self.ks if self.with_list else None
 
-    def add(self, mask=None):
-        took = super().add(mask)
-        S = self.S
+    def took_parts(self, took):
+        """the lists as they are; the rows of the ids born at this key-frame (consecutive: one block per stream)"""
+        if not self.rows:
+            return took, None
+        desc = {}
         for s, f in took.items():
-            self.ks.upload(s, f["yx"], f["is_3d"], f["xyz"], f["ids"])
-            self.Tcw[s] = f["Tcw"]
-        sp = self.slam.stream_params(S, Tcw=self.Tcw, cam=ts.CAM, dist=np.zeros((S, 4)))
-        with self.ks.selected(mask):
-            self.ks.keyframe()
-            self.km.add_keyframe(self.ks, sp)
-            if self.rows:
-                desc = np.full((S, DCAP, 4), 0x5555555555555555, dtype=np.uint64)
-                info = np.tile(np.array([10 ** 6, 3], dtype=np.int64), (S, 1))
-                for s, f in took.items():
-                    born = self.tracks[s][self.nkf[s] - 1][1]
-                    new = [int(i) for i in f["ids"] if int(i) >= born]
-                    if new:
-                        rows = self.desc_rows(s, new)
-                        info[s] = (new[0], len(rows)); desc[s, :len(rows)] = rows
-                desc_dev = self.torch.from_numpy(desc.view(np.int64)).cuda(); info_dev = self.torch.from_numpy(info).cuda()
-                self.km.add_descriptors(desc_dev.data_ptr(), info_dev.data_ptr(), DCAP)
-                self.km.ctx.synchronize()                        # (the tensors live until the kernel has read them)
-        for s in took:                                           # the device's angles, checked to their bar, become the model's
-            k = self.nkf[s] - 1
-            th, ref = self.km.download_keyframe(s, k)["theta"], self.m[s].theta[k % self.R]
-            assert np.array_equal(th[3:], ref[3:]) and np.all(np.abs(th[:3] - ref[:3]) <= ANGLE_TOL), (s, k)
-            self.m[s].theta[k % self.R] = th
-        return took
+            born = self.tracks[s][self.nkf[s] - 1][1]
+            new = [int(i) for i in f["ids"] if int(i) >= born]
+            if new:
+                desc[s] = (new[0], self.desc_rows(s, new))
+        return took, desc
 
     def tri(self, mutant=None, with_list=None):
         want = super().tri(mutant, with_list)
@@ -125,52 +91,15 @@ class Dev(ts.TriRun):
 
     def gather(self):
         want = super().gather()
-        wins, status = self.km.gather(np.full(self.S, self.minc, dtype=np.int32))
-        assert [w.stream for w in wins] == sorted(want)
-        for w in wins:                                           # the gather searched the slabs the triangulation wrote: the window is the model's
-            ref = want[w.stream]
-            assert np.array_equal(w.cache.theta, ref["theta"]) and np.array_equal(w.cache.pixels, ref["pixels"])
-            assert np.array_equal(w.obs_kf, ref["obs_kf"]) and np.array_equal(w.obs_kp, ref["obs_kp"]) and np.array_equal(w.points_remap, ref["points_remap"])
-        self.dev_wins = wins
+        self.device_gather(want)                                 # the gather searched the slabs the triangulation wrote: the window is the model's
         return want
 
     def update(self, wins, sols):
         super().update(wins, sols)
-        self.km.update(self.dev_wins, [sols[w.stream][0] for w in self.dev_wins], [sols[w.stream][1] for w in self.dev_wins], ks=self.kset)
-
-    def merge(self, pairs):
-        want = super().merge(pairs)
-        got = self.km.merge(self.kset, [np.asarray(p, dtype=np.int64).reshape(-1, 2) for p in pairs])
-        assert np.array_equal(got, want), (got, want)
-        return want
-
-    def check(self):
-        for s, m in enumerate(self.m):
-            for k in range(max(m.cur - self.R + 1, 0), m.cur + 1):
-                d, w = self.km.download_keyframe(s, k), m.keyframe(k)
-                assert (d is None) == (w is None), (s, k)
-                if w is not None:
-                    assert all(np.array_equal(d[key], w[key]) for key in ("theta", "ids", "upx", "live")), (s, k)
-            d, w = self.km.download_points(s), m.points()
-            assert all(np.array_equal(d[key], w[key]) for key in ("ids", "xyz", "is_3d", "observed", "ba", "gone")) and d["observers"] == w["observers"], s
-            if self.lists[s] is not None:
-                d = self.ks.download(s)
-                assert len(d["ids"]) == len(self.lists[s]["ids"]) and all(np.array_equal(d[key], self.lists[s][key]) for key in ("ids", "yx", "is_3d", "xyz")), s
-            if self.rows:
-                assert nr.same_rows(self.km.descriptor_rows(s), nr.descriptor_rows(m, self.D[s])), s
+        self.device_update(sols)
 
 
-@pytest.fixture()
-def dev(slam):
-    made = []
-
-    def make(name, **kw):
-        run, fn = ts.make(name, cls=lambda **a: Dev(slam, **a), **kw)
-        made.append(run)
-        return run, fn
-    yield make
-    for p in made:
-        p.close()
+dev = kd.device_fixture(Dev, "dev", through=ts.make)
 
 
 @pytest.mark.parametrize("name", sorted(ts.SEQUENCES))
@@ -182,9 +111,9 @@ def test_device_equals_model_after_every_step(dev, slam, name):
         run.check()
         seen["steps"] += 1
         if name == "selection" and step == "add2":                # 7: the unselected stream's bytes, before the call
-            seen["before"] = device_bytes(run.km, run.ks, 1, run.nkf[1])
+            seen["before"] = run.device_bytes([1], staged=False)
         if name == "selection" and step == "tri2":
-            assert device_bytes(run.km, run.ks, 1, run.nkf[1]) == seen["before"] and run.last[1] is None
+            assert run.device_bytes([1], staged=False) == seen["before"] and run.last[1] is None
     run.on_step = on_step
     if name == "no_rows":                                        # 9: a map that never enables rows launches <false>: the route, the way the rows tests assert it
         with pytest.raises(slam.SlamHipError, match="descriptor rows are not enabled"):
