@@ -46,13 +46,17 @@ Key-frames are taken every `kf_every`-th frame, or, with --adaptive-keyframes, w
 shared -- so --adaptive-keyframes alone takes a key-frame FOR ALL streams when ANY stream requires one.  --per-stream-keyframes lets every
 stream follow its own rule: the key-frame seams run under KeypointSet.selected(required), which restricts them to the streams that asked
 (slam_kpset_select), and the key-frame bookkeeping (last key-frame, its nb_3d_kpts, its pose, the observer ring, the key-frame id) is per stream.
+The right frames of such a key-frame are uploaded, built and matched for the streams that asked only: a COMPACT build into the first members of the
+right batch (PyramidBatch.update_selected_) and a compact stereo match (stereo_match(..., compact=True)); --right-members K sizes that batch.
 
 With --map-triangulation (requires --local-ba) the temporal triangulation reads the map instead of a host table of poses: the key-frame is recorded
 right after the stereo triangulation, and every 2-D point of it is triangulated against its first observer as the map knows it NOW -- the smallest
 key-frame id among the point's observers after every removal -- with the pose the last bundle adjustment left in the map, not the pose the key-frame was
 taken with.  The kf_cw ring of the host is then not read; a rejected observation leaves the map while the list keeps the keypoint.
 
-    python examples/device_frontend.py --frames 12 --streams 4 [--adaptive-keyframes | --per-stream-keyframes] [--local-ba [--map-triangulation] [--device-ba] [--map-filtering [--filter-from K]] [--local-map-match [--merge] [--local-map-history] [--descriptor-rows D]]]
+    python examples/device_frontend.py --frames 12 --streams 4 [--adaptive-keyframes | --per-stream-keyframes [--right-members K]]
+        [--local-ba [--map-triangulation] [--device-ba] [--map-filtering [--filter-from K]]
+         [--local-map-match [--merge] [--local-map-history] [--descriptor-rows D]]]
 """
 import argparse
 import contextlib
@@ -68,7 +72,8 @@ from slam_jl_amd import synthetic as syn  # noqa: E402
 
 
 def run(lefts, rights, cam, baseline, kf_every=4, max_keypoints=300, seed=0, ctx=None, verbose=False, adaptive=False, probe=None, per_stream=False, local_ba=False,
-        map_filtering=False, filter_from=20, map_probe=None, local_map_match=False, merge=False, local_map_history=False, descriptor_rows=0, device_ba=False, map_triangulation=False):
+        map_filtering=False, filter_from=20, map_probe=None, local_map_match=False, merge=False, local_map_history=False, descriptor_rows=0, device_ba=False,
+        map_triangulation=False, right_members=None, whole_right_build=False):
     """lefts / rights: per stream a list of float images in [0, 1] (H, W).  Returns per frame a dict with the S poses
     (world -> camera, world = the first frame's camera), status words, list lengths and the wall time.
     adaptive: frame 0 is a key-frame; after the pose of every later frame the lists' statistics (KeypointSet.frame_stats, flags = 1) go
@@ -76,8 +81,12 @@ def run(lefts, rights, cam, baseline, kf_every=4, max_keypoints=300, seed=0, ctx
     also carry kf_stats (S, 8), kf_required, kf_rule, frames_delta and prev_kf_nb_3d (the key-frame's nb_3d_kpts, from the statistics
     taken when it was created).  probe(frame, keypoint set, R_compensation (S, 3, 3)) is called right after the statistics are taken.
     per_stream (implies adaptive): frame 0 is a key-frame for all streams; afterwards stream s takes a key-frame exactly where keyframe_required
-    says so for s -- the key-frame seams run on the selected streams only -- and `keyframe` of a row is an (S,) bool array.  (The right-pyramid
-    batch is still built for all S streams at such a frame: a batch build takes the whole batch.)
+    says so for s -- the key-frame seams run on the selected streams only -- and `keyframe` of a row is an (S,) bool array.  Only the selected
+    streams' right frames are uploaded; they are built compact into the first members of the right batch and matched compact.
+    right_members (per_stream only; default S): the number of members of the right batch, K x 7 planes instead of S x 7.  When more streams ask for
+    a key-frame than it holds (frame 0 with K < S, for one), that frame falls back to an ordinary whole-batch right build and match, in a full S-member
+    batch made at the first such frame.  whole_right_build (per_stream only): every key-frame takes that whole-batch path -- the behaviour before
+    the compact builds existed, kept for comparison.  Rows carry `right_build`: "compact" / "whole" at a key-frame of a per_stream run.
     local_ba: a KeyframeMap follows the key-frames; after the key-frame seams (same selection) the key-frame is added, the windows are gathered,
     solved by bundle_adjustment_batch_ and written back into the map and the lists.  Rows of key-frame steps carry `ba`: per solved window
     (stream, P, M, O, outliers, ssr before, ssr after).
@@ -113,6 +122,8 @@ def run(lefts, rights, cam, baseline, kf_every=4, max_keypoints=300, seed=0, ctx
         raise ValueError("local_map_history needs local_map_match: it is the match that keeps and reads the stored local maps")
     if descriptor_rows and not local_map_match:
         raise ValueError("descriptor_rows needs local_map_match: the rows are what the match is decided on")
+    if right_members is not None and not (per_stream and 1 <= right_members <= len(lefts)):
+        raise ValueError("right_members sizes the compact right batch of per_stream: 1 .. S members")
     adaptive = adaptive or per_stream
     import torch
     ctx = ctx or slam.default_context(0)
@@ -137,7 +148,8 @@ def run(lefts, rights, cam, baseline, kf_every=4, max_keypoints=300, seed=0, ctx
         torch.cuda.synchronize()
     prev = slam.PyramidBatch((H, W), levels=params.pyramid_levels, S=S, ctx=ctx)
     cur = slam.PyramidBatch((H, W), levels=params.pyramid_levels, S=S, ctx=ctx)
-    rpyr = slam.PyramidBatch((H, W), levels=params.pyramid_levels, S=S, ctx=ctx)
+    rpyr = slam.PyramidBatch((H, W), levels=params.pyramid_levels, S=right_members if per_stream and right_members else S, ctx=ctx)
+    rfull = rpyr if rpyr.S == S else None                                           # the whole-batch fallback's batch: made when first needed
     dev = lambda im: torch.from_numpy(np.ascontiguousarray(im.T)).cuda()          # Julia layout: column-major H x W
     T21 = np.eye(4); T21[0, 3] = -baseline                                          # left camera -> right camera
     Tcw = np.tile(np.eye(4), (S, 1, 1)); Tkf = Tcw.copy()
@@ -193,10 +205,23 @@ def run(lefts, rights, cam, baseline, kf_every=4, max_keypoints=300, seed=0, ctx
                 for s in np.flatnonzero(kf_mask):
                     kf_cw[s, kfid[s] % NKF] = Tcw[s]
                 n_kf[kf_mask] += 1
-                rframes = [dev(rights[s][i]) for s in range(S)]
-                torch.cuda.synchronize()
-                rpyr.update_([f.data_ptr() for f in rframes], sigma=params.pyramid_sigma, ctx=ctx, target_only=True)   # only matched INTO
-                ks.stereo_match(cur, rpyr, params, sp_right, prior=2, ctx=ctx)
+                if per_stream and not whole_right_build and int(kf_mask.sum()) <= rpyr.S:
+                    # the right frames of the streams that asked, built into members 0 .. n_sel-1, matched through each stream's rank
+                    rframes = {s: dev(rights[s][i]) for s in np.flatnonzero(kf_mask)}
+                    torch.cuda.synchronize()
+                    rptrs = [rframes[s].data_ptr() if s in rframes else 0 for s in range(S)]
+                    rpyr.update_selected_(rptrs, kf_mask, sigma=params.pyramid_sigma, ctx=ctx, target_only=True)
+                    ks.stereo_match(cur, rpyr, params, sp_right, prior=2, ctx=ctx, compact=True)
+                    decision["right_build"] = "compact"
+                else:
+                    if rfull is None:                                       # more streams asked than the compact batch holds
+                        rfull = slam.PyramidBatch((H, W), levels=params.pyramid_levels, S=S, ctx=ctx)
+                    rframes = [dev(rights[s][i]) for s in range(S)]
+                    torch.cuda.synchronize()
+                    rfull.update_([f.data_ptr() for f in rframes], sigma=params.pyramid_sigma, ctx=ctx, target_only=True)   # only matched INTO
+                    ks.stereo_match(cur, rfull, params, sp_right, prior=2, ctx=ctx)
+                    if per_stream:
+                        decision["right_build"] = "whole"
                 Twc = np.stack([np.linalg.inv(Tcw[s]) for s in range(S)])
                 ks.triangulate(cam, cam, T21, Twc, max_error=params.max_reprojection_error, ctx=ctx)
                 notify = map_probe or (lambda *a: None)
@@ -289,6 +314,9 @@ def main():
     ap.add_argument("--streams", type=int, default=2)
     ap.add_argument("--adaptive-keyframes", action="store_true", help="take key-frames where check_new_kf_required asks for one (any stream), not every 4th frame")
     ap.add_argument("--per-stream-keyframes", action="store_true", help="every stream takes its key-frames where check_new_kf_required asks for one for THAT stream (implies --adaptive-keyframes)")
+    ap.add_argument("--right-members", type=int, default=None, metavar="K",
+                    help="with --per-stream-keyframes: members of the right pyramid batch (default: one per stream); a frame at which more streams take "
+                         "a key-frame falls back to a whole-batch right build")
     ap.add_argument("--local-ba", action="store_true", help="run the estimator's local BA after every key-frame step, on a key-frame map in HBM; the lists take the refined landmarks")
     ap.add_argument("--device-ba", action="store_true", help="with --local-ba: the estimator step in one call with the windows kept in HBM (KeyframeMap.local_ba), not gather -> solve -> update through the host")
     ap.add_argument("--map-filtering", action="store_true", help="after every local BA drop the redundant key-frames of the map (map_filtering!); requires --local-ba")
@@ -300,6 +328,8 @@ def main():
     ap.add_argument("--filter-from", type=int, default=20, help="first key-frame id at which the filter acts (the reference's literal 20)")
     ap.add_argument("--replay-dir", default=None, help="write stream s's camera positions to DIR/stream_s as a ReplaySaver dump (src/io/saver.jl)")
     args = ap.parse_args()
+    if args.right_members is not None and not args.per_stream_keyframes:
+        ap.error("--right-members requires --per-stream-keyframes")
     if args.device_ba and not args.local_ba:
         ap.error("--device-ba requires --local-ba")
     if args.map_filtering and not args.local_ba:
@@ -318,7 +348,8 @@ def main():
     lefts, rights, offs = synthetic_scene(args.streams, args.frames, disparity=disparity)
     out, n3 = run(lefts, rights, cam, baseline, verbose=True, adaptive=args.adaptive_keyframes, per_stream=args.per_stream_keyframes, local_ba=args.local_ba,
                   map_filtering=args.map_filtering, filter_from=args.filter_from, local_map_match=args.local_map_match, merge=args.merge,
-                  local_map_history=args.local_map_history, descriptor_rows=args.descriptor_rows, device_ba=args.device_ba, map_triangulation=args.map_triangulation)
+                  local_map_history=args.local_map_history, descriptor_rows=args.descriptor_rows, device_ba=args.device_ba,
+                  map_triangulation=args.map_triangulation, right_members=args.right_members)
     Z = cam[0] * baseline / disparity
     for s in range(args.streams):
         o = offs[s][-1] - offs[s][0]

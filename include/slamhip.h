@@ -251,6 +251,26 @@ int slam_pyr_update_batch_dev(slam_ctx *ctx, slam_pyr *const *pyrs, const double
  * `Gray{Float64}.(frame)`, example/kitty/main.jl:39-41): raw / 255 on the device. */
 int slam_pyr_update_batch_u8_dev(slam_ctx *ctx, slam_pyr *const *pyrs, const uint8_t *const *images_u8_dev, int S,
                                  int mode, double sigma, int sync);
+/* COMPACT batch builds: a key-frame is a per-stream event (slam_kpset_select), and a member's planes depend on that member's image alone, so
+ * the right frames of the streams that take a key-frame are built into the FIRST n_sel members of the right batch and nothing else is.
+ *   pyrs       the n_members members of ONE slam_pyr_create_batch call, in order.  n_members may be smaller than S: a right batch of K
+ *              members holds K x 7 planes, not S x 7.
+ *   images     S device pointers indexed by STREAM (Float64 images, or 8-bit frames for _u8).  The pointers of unselected streams are never
+ *              read and may be NULL; a selected stream's pointer must not be.
+ *   selected   S bytes on the host, non-zero = selected (required[] of slam_keyframe_required passes as it is), or NULL = every stream.
+ *   *n_built   receives n_sel, the number of selected streams.
+ * MEMBER ORDER: member r receives the build of the r-th selected stream, ascending by stream index -- bit for bit (mode 1) what member s of
+ * an ordinary S-member build of the same frames holds, by the kernels, routes, chunking and graph of an n_sel-member build.  Members at
+ * index n_sel or above KEEP THEIR BYTES (planes, target_only / tolerance marks); n_sel == 0 enqueues nothing.  n_sel > n_members:
+ * SLAM_ERR_ARG, nothing enqueued, nothing changed.  mode, sigma, sync as for slam_pyr_update_batch_dev.
+ * STALE-BUILD RULE: the batch remembers, on the host, the mask it was last built for; these two calls set that record, an ordinary
+ * slam_pyr_update_batch_* clears it.  slam_kpset_stereo_match_compact (below) refuses a batch whose record is not the set's current
+ * selection -- the one guard against matching into another key-frame's pyramids.  A build of a member count not seen before constructs its
+ * launch graph on first use (one executable per distinct count and mode, kept for the batch's lifetime). */
+int slam_pyr_update_batch_sel_dev(slam_ctx *ctx, slam_pyr *const *pyrs, int n_members, const double *const *images_dev, int S,
+                                  const uint8_t *selected, int mode, double sigma, int sync, int *n_built);
+int slam_pyr_update_batch_sel_u8_dev(slam_ctx *ctx, slam_pyr *const *pyrs, int n_members, const uint8_t *const *images_u8_dev, int S,
+                                     const uint8_t *selected, int mode, double sigma, int sync, int *n_built);
 int slam_flow_match_batch(slam_ctx *ctx, const slam_pyr *from0, const slam_pyr *to0, int S, const int32_t *img_index,
                           const double *pts_yx, const uint8_t *is_3d, const double *proj_yx, int n,
                           int pyramid_levels, int pyramid_levels_3d, int window, int iterations,
@@ -320,6 +340,16 @@ int slam_kpset_flow_match(slam_ctx *ctx, slam_kpset *ks, const slam_pyr *from0, 
 int slam_kpset_stereo_match(slam_ctx *ctx, slam_kpset *ks, const slam_pyr *left0, const slam_pyr *right0, const double *params, int prior,
                             int pyramid_levels, int pyramid_levels_3d, int window, int iterations, double eig_thr, double eps,
                             double max_distance, double epipolar_error, int n_bound);
+/* The same into a COMPACT right batch (slam_pyr_update_batch_sel_*): right0 is member 0 of a batch whose member r holds the build of the
+ * r-th selected stream, and stream s's target is read at member rank(s).  left0's batch still needs >= S members (a stream's source is
+ * member s), right0's >= n_sel.  STALE-BUILD RULE: the mask the right batch was last built for must equal the set's current selection,
+ * stream for stream; a batch built for another selection, or by an ordinary slam_pyr_update_batch_* since, gives SLAM_ERR_ARG (the message
+ * names the stale build) and the lists are not touched.  Per selected stream the result is byte for byte that of slam_kpset_stereo_match
+ * into a whole-batch build of the same frames; unselected streams come out as they went in.  With no selection set the call IS
+ * slam_kpset_stereo_match (same kernels, same arguments; right0's batch then needs >= S members and no compact build of fewer streams). */
+int slam_kpset_stereo_match_compact(slam_ctx *ctx, slam_kpset *ks, const slam_pyr *left0, const slam_pyr *right0, const double *params,
+                                    int prior, int pyramid_levels, int pyramid_levels_3d, int window, int iterations, double eig_thr, double eps,
+                                    double max_distance, double epipolar_error, int n_bound);
 /* remove the keypoints whose flag is set (flags_dev: S x cap bytes in HBM, slot order): map culling, outliers of the pose
  * estimators (estimator.jl:283-292, front_end.jl:174-219) */
 int slam_kpset_remove(slam_ctx *ctx, slam_kpset *ks, const uint8_t *flags_dev);

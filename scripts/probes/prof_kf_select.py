@@ -10,7 +10,15 @@ last one (the seams only enqueue), after warm-up; median of `--repeats` with min
 --no-select runs the no-selection leg alone and never touches the selection calls: that leg uses only seams that existed before them, so the
 same script times the parent commit (run it there, alternating with this tree, in one session on one machine).
 
+--right-build times the other half of such a key-frame instead: the right-pyramid build (8-bit frames, target-only) + the stereo match, at 128, 64, 16
+and 1 streams selected -- "whole": slam_pyr_update_batch_u8_dev of all S members + slam_kpset_stereo_match under the selection (what a per-stream
+key-frame cost before the compact builds), "compact": slam_pyr_update_batch_sel_u8_dev of the selected streams + slam_kpset_stereo_match_compact.
+Same clock (first enqueue to the return of the synchronise), same statistics; the lists are detected once and matched again every repeat.  Per count
+the first compact build (its launch graph is made then) is timed on its own, beside the steady build.  --whole-only runs the whole-batch legs alone
+and calls nothing newer than the selection: the same script times the parent commit.
+
     python scripts/probes/prof_kf_select.py [--streams 128] [--repeats 25] [--no-select] [--tag NAME] [--out profiles/kf_select_s128.json]
+    python scripts/probes/prof_kf_select.py --right-build [--whole-only] [--tag NAME] [--out profiles/kf_select_right_s128.json]
 """
 import argparse
 import json
@@ -35,6 +43,8 @@ def main():
     ap.add_argument("--streams", type=int, default=128)
     ap.add_argument("--repeats", type=int, default=25)
     ap.add_argument("--no-select", action="store_true")
+    ap.add_argument("--right-build", action="store_true")
+    ap.add_argument("--whole-only", action="store_true")
     ap.add_argument("--tag", default="this tree")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
@@ -91,6 +101,54 @@ def main():
         ks.close()
         return rec
 
+    def right_legs():
+        r8 = [torch.from_numpy(np.ascontiguousarray((np.clip(im, 0, 1) * 255).round().astype(np.uint8).T)).cuda() for im in right]
+        torch.cuda.synchronize()
+        ptrs = [r8[s % 2].data_ptr() for s in range(S)]
+        legs = []
+        for k in (S, S // 2, S // 8, 1):
+            mask = np.zeros(S, np.uint8)
+            mask[np.linspace(0, S - 1, k).round().astype(int)] = 1
+            for compact in ([False] if args.whole_only else [False, True]):
+                ks = slam.KeypointSet(S, CAP)
+                ks.detect(ex, lp); ks.keyframe()                  # about 1000 2-D keypoints per stream; a stereo match leaves the lists as they are
+                ks.select(mask)
+                n_kp = float(ks.counts()[mask != 0].mean())
+
+                def build():
+                    if compact:
+                        rp.update_selected_(ptrs, mask, u8=True, target_only=True, sync=False)
+                    else:
+                        rp.update_(ptrs, u8=True, target_only=True, sync=False)
+
+                t0 = time.perf_counter(); build(); ctx.synchronize()
+                first_ms = (time.perf_counter() - t0) * 1e3       # a member count not built before: the launch graph is made here
+                both, alone = [], []
+                for it in range(5 + R):
+                    t0 = time.perf_counter()
+                    build()
+                    ks.stereo_match(lp, rp, params, sps, prior=2, **({"compact": True} if compact else {}))
+                    ctx.synchronize()
+                    t1 = time.perf_counter()
+                    build(); ctx.synchronize()
+                    t2 = time.perf_counter()
+                    if it >= 5:
+                        both.append((t1 - t0) * 1e3); alone.append((t2 - t1) * 1e3)
+                matched = float(np.mean([ks.download(int(s))["has_stereo"].mean() for s in np.flatnonzero(mask)[:4]]))
+                legs.append({"leg": f"{k} of {S} selected, {'compact' if compact else 'whole'} right build", "selected": k, "compact": compact,
+                             "build_and_match_ms": stat(both), "build_alone_ms": stat(alone), "first_build_ms": round(first_ms, 4),
+                             "keypoints_mean": n_kp, "stereo_matched_fraction": round(matched, 4)})
+                ks.close()
+        return legs
+
+    if args.right_build:
+        rec = {"lib": os.path.basename(slam.LIB_PATH), "tag": args.tag, "S": S, "cap": CAP, "max_nb_keypoints": MAXKP, "shape": [H, W], "repeats": R,
+               "sequence": "right build (8-bit frames, target-only) -> stereo_match", "legs": right_legs()}
+        print(json.dumps(rec))
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(json.dumps(rec, indent=1) + "\n")
+        return
     rec = {"lib": os.path.basename(slam.LIB_PATH), "tag": args.tag, "S": S, "cap": CAP, "max_nb_keypoints": MAXKP, "shape": [H, W], "repeats": R,
            "sequence": "detect -> keyframe -> stereo_match -> triangulate", "legs": [leg("no selection", None)]}
     if not args.no_select:

@@ -73,6 +73,8 @@ SIGNATURES = {
     "slam_pyr_create_batch": (cint, [vp, cint, cint, cint, cint, C.POINTER(vp)]),
     "slam_pyr_update_batch_dev": (cint, [vp, C.POINTER(vp), C.POINTER(vp), cint, cint, dbl, cint]),
     "slam_pyr_update_batch_u8_dev": (cint, [vp, C.POINTER(vp), C.POINTER(vp), cint, cint, dbl, cint]),
+    "slam_pyr_update_batch_sel_dev": (cint, [vp, C.POINTER(vp), cint, C.POINTER(vp), cint, u8p, cint, dbl, cint, C.POINTER(cint)]),
+    "slam_pyr_update_batch_sel_u8_dev": (cint, [vp, C.POINTER(vp), cint, C.POINTER(vp), cint, u8p, cint, dbl, cint, C.POINTER(cint)]),
     "slam_flow_match_batch": (cint, [vp, vp, vp, cint, i32p, f64p, u8p, f64p, cint, cint, cint, cint, cint, dbl, dbl, dbl, f64p, u8p]),
     "slam_flow_match_batch_kept": (cint, [vp, vp, vp, cint, i32p, f64p, u8p, f64p, cint, cint, cint, cint, cint, dbl, dbl, dbl, f64p, u8p, i32p, i32p, C.POINTER(cint), u8p]),
     "slam_kpset_create": (cint, [vp, cint, cint, C.POINTER(vp)]),
@@ -86,6 +88,7 @@ SIGNATURES = {
     "slam_kpset_counts": (cint, [vp, vp, i32p]),
     "slam_kpset_flow_match": (cint, [vp, vp, vp, vp, f64p, cint, cint, cint, cint, cint, dbl, dbl, dbl, cint]),
     "slam_kpset_stereo_match": (cint, [vp, vp, vp, vp, f64p, cint, cint, cint, cint, cint, dbl, dbl, dbl, dbl, cint]),
+    "slam_kpset_stereo_match_compact": (cint, [vp, vp, vp, vp, f64p, cint, cint, cint, cint, cint, dbl, dbl, dbl, dbl, cint]),
     "slam_kpset_remove": (cint, [vp, vp, vp]),
     "slam_kpset_detect": (cint, [vp, vp, vp, cint, cint, cint, cint, cint, dbl, dbl]),
     "slam_kpset_detect_describe": (cint, [vp, vp, vp, cint, cint, cint, cint, cint, dbl, dbl, i32p, cint, dbl, cint, vp, vp, cint]),

@@ -72,7 +72,16 @@ struct slam_pyr {
     int H[SLAM_MAX_LEVELS], W[SLAM_MAX_LEVELS];
     int P[SLAM_MAX_LEVELS];               // column pitch in doubles (H rounded up to 16)
     int64_t off[SLAM_MAX_LEVELS + 1];     // plane offsets in doubles (sum of P_l * W_l)
-    struct Alloc { double *base = nullptr; double *ck = nullptr; double *tot = nullptr; const void **srctab = nullptr; double *xc = nullptr; int *xf = nullptr; int xseg = 0; double *rck = nullptr; int refs = 0; std::mutex graph_mu; };   // xc / xf / xseg: carry rows and flags of k_cum_fused's row segments (frames taller than 512 rows); rck: k_rows_cum's checkpoints   // shared by the members of a batch; srctab: 64 source-image pointers (fused ingest)
+    // shared by the members of a batch; srctab: 64 source-image pointers (fused ingest); xc / xf / xseg: carry rows and flags of k_cum_fused's row
+    // segments (frames taller than 512 rows); rck: k_rows_cum's checkpoints
+    struct Alloc {
+        double *base = nullptr; double *ck = nullptr; double *tot = nullptr; const void **srctab = nullptr; double *xc = nullptr; int *xf = nullptr;
+        int xseg = 0; double *rck = nullptr; int refs = 0; std::mutex graph_mu;
+        // the COMPACT build the batch last received (slam_pyr_update_batch_sel_*): the sel_S mask bytes (0 / 1) it was built for -- member r holds
+        // the r-th selected stream.  sel_S == 0: none (never built, or an ordinary slam_pyr_update_batch_* since).  Host state, read by
+        // slam_kpset_stereo_match_compact.
+        uint8_t sel_mask[128] = {}; int sel_S = 0;
+    };
     Alloc *alloc = nullptr;
     size_t zstride = 0;                   // doubles between consecutive images of a batch (7 * off[levels])
     int batch_index = 0, batch_size = 1;

@@ -26,8 +26,8 @@ static int work_band() { static const int band = [] { const char *v = getenv("SL
 struct WorkOrder { int H, W, band, pad; };       // band 0: slot order; pad: power of two >= cap whose words fit KPSET_SORT_LDS_BYTES
 // SLAMHIP_NO_MATCH_REC=1, read once per process: the matches build no work records and run their record-less prologue (the A/B of round 22)
 bool kpset_match_records() { static const bool on = [] { const char *v = getenv("SLAMHIP_NO_MATCH_REC"); return !(v && atoi(v) != 0); }(); return on; }
-// the work record of entry idx (work_order.hpp: work_rec_slot) of a list of ceil(ntot / 8) = per entries per XCD: slot q of stream s
-__device__ __forceinline__ void kp_write_rec(const KpWorkRecs &R, const double *yx, int H, int W, int idx, int per, int q, int s)
+// the work record of entry idx (work_order.hpp: work_rec_slot) of a list of ceil(ntot / 8) = per entries per XCD: slot q of stream s, target member zt
+__device__ __forceinline__ void kp_write_rec(const KpWorkRecs &R, const double *yx, int H, int W, int idx, int per, int q, int s, int zt)
 {
     const int at = work_rec_slot(idx, per, R.stride);
     if (at >= WORK_XCDS * R.stride) return;                      // (cannot happen while count <= cap: ntot <= S cap, so per <= stride; it guards the region)
@@ -39,7 +39,7 @@ __device__ __forceinline__ void kp_write_rec(const KpWorkRecs &R, const double *
     double pry, prx;
     kp_match_prior(R.prior, R.xyz + 3 * (size_t)q, R.par + KP_PAR * (size_t)s, r.py, r.px, pry, prx);
     r.pry = is3 ? pry : r.py; r.prx = is3 ? prx : r.px;
-    r.q = q; r.s = s; r.flags = (is3 ? KPREC_3D : 0) | (kp_in_image(r.pry, r.prx, H, W) ? KPREC_INSIDE : 0); r.pad = 0;
+    r.q = q; r.s = s; r.flags = (is3 ? KPREC_3D : 0) | (kp_in_image(r.pry, r.prx, H, W) ? KPREC_INSIDE : 0); r.zt = zt;
     R.rec[at] = r;
 }
 // k_kpset_worklist, k_kpset_compact and k_kpset_keyframe, plain and selected (slam_kpset_select): kpset_kernels.inc, included once per form
@@ -75,8 +75,8 @@ int kpset_build_worklist(slam_ctx *ctx, slam_kpset *ks, int H, int W, bool selec
     WorkOrder O;
     O.H = H; O.W = W; O.pad = ks->sort_pad; O.band = H > 0 && W > 0 && ks->sort_pad > 0 ? work_band() : 0;
     const size_t lds = O.band > 0 ? (size_t)ks->sort_pad * 8 : 0;
-    KpWorkRecs R = {nullptr, 0, 0, nullptr, nullptr, nullptr};
-    if (match && kpset_match_records()) R = {ks->rec, ks->rec_stride, match->prior, match->par, ks->v.xyz, ks->v.is3d};
+    KpWorkRecs R = {nullptr, 0, 0, nullptr, nullptr, nullptr, 0};
+    if (match && kpset_match_records()) R = {ks->rec, ks->rec_stride, match->prior, match->par, ks->v.xyz, ks->v.is3d, match->compact ? 1 : 0};
     if (selected && ks->n_sel != KPSEL_ALL)
         hipLaunchKernelGGL(k_kpset_worklist_sel, dim3(ks->n_sel), dim3(256), lds, ctx->stream, (const int *)ks->v.count, ks->S, ks->v.cap, ks->work, ks->ntot, (const double *)ks->v.yx, O, R,
                            (const int *)ks->sel_idx);
@@ -379,8 +379,8 @@ static size_t kpset_regions(slam_kpset *ks, char *base)
     Lo.bind(v.is3d, n, base); Lo.bind(v.stereo, n, base); Lo.bind(v.st, n, base); Lo.bind(v.count, S * 4, base); Lo.bind(ks->work, n * 4, base); Lo.bind(ks->ntot, 64, base);
     Lo.bind(ks->next_id, S * 8, base); Lo.bind(ks->par, 8 * S * KP_PAR * 8, base); Lo.bind(v.kyx, n * 16, base); Lo.bind(v.haskf, n, base); Lo.bind(v.fyx, n * 16, base);
     Lo.bind(v.fkf, n * 4, base); Lo.bind(v.kfcount, S * 4, base);
-    Lo.bind(ks->sel_idx, S * 4 + S, base);                               // the selection as one block (one staged copy): S indices, then the S mask bytes
-    if (base) ks->sel_mask = (uint8_t *)(ks->sel_idx + S);
+    Lo.bind(ks->sel_idx, S * 8 + S, base);                               // the selection as one block (one staged copy): S indices, S ranks, the S mask bytes
+    if (base) { ks->sel_rank = ks->sel_idx + S; ks->sel_mask = (uint8_t *)(ks->sel_idx + 2 * S); }
     ks->rec_stride = work_rec_stride((long long)n);
     Lo.bind(ks->rec, (size_t)WORK_XCDS * ks->rec_stride * sizeof(KpWorkRec), base);      // the work records of a match (regions start 256-byte aligned)
     return Lo.size();
@@ -486,11 +486,12 @@ int slam_kpset_select(slam_ctx *ctx, slam_kpset *ks, const uint8_t *selected)
 {
     ARG_TRY(ctx, ctx != nullptr && ks != nullptr);
     const int S = ks->S;
-    int32_t idx[128]; uint8_t norm[128];
+    int32_t idx[128], rank[128]; uint8_t norm[128];
     const int n_sel = kpset_select_plan(S, selected, idx, norm);
+    kpset_select_rank(S, idx, n_sel, rank);
     if (n_sel != KPSEL_ALL) {                                    // (no selection needs no table: the unselected kernel forms read none)
         HIP_TRY(ctx, hipSetDevice(ctx->device));
-        const size_t bytes = (size_t)S * 5;
+        const size_t bytes = (size_t)S * 9;
         if (!ks->sel_pin) {
             HIP_TRY(ctx, hipHostMalloc((void **)&ks->sel_pin, 8 * bytes));
             for (int i = 0; i < 8; i++) if (!ks->sel_ev[i]) HIP_TRY(ctx, hipEventCreateWithFlags(&ks->sel_ev[i], hipEventDisableTiming));
@@ -498,7 +499,7 @@ int slam_kpset_select(slam_ctx *ctx, slam_kpset *ks, const uint8_t *selected)
         const int sl = ks->sel_slot; ks->sel_slot = (sl + 1) & 7;
         HIP_TRY(ctx, hipEventSynchronize(ks->sel_ev[sl]));       // (an event never recorded is complete)
         char *h = ks->sel_pin + (size_t)sl * bytes;
-        memcpy(h, idx, (size_t)S * 4); memcpy(h + (size_t)S * 4, norm, (size_t)S);
+        memcpy(h, idx, (size_t)S * 4); memcpy(h + (size_t)S * 4, rank, (size_t)S * 4); memcpy(h + (size_t)S * 8, norm, (size_t)S);
         HIP_TRY(ctx, hipMemcpyAsync(ks->sel_idx, h, bytes, hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(ctx, hipEventRecord(ks->sel_ev[sl], ctx->stream));
     }

@@ -59,7 +59,7 @@ struct alignas(16) KpWorkRec {
     double pry, prx;             // its prior (kp_match_prior; the pixel itself for a 2-D keypoint)
     int q, s;                    // slot in the set's arrays, stream
     int flags;                   // KPREC_3D: is3d[q] != 0, KPREC_INSIDE: the prior lies in the image
-    int pad;
+    int zt;                      // the member of the TARGET batch the match reads: s, or the stream's rank among the selected ones (a compact stereo match)
 };
 constexpr int KPREC_3D = 1, KPREC_INSIDE = 2;
 static_assert(sizeof(KpWorkRec) == 48 && alignof(KpWorkRec) == 16, "the fetch of k_kpset_match (lk.hip) restates the layout");
@@ -67,6 +67,7 @@ static_assert(sizeof(KpWorkRec) == 48 && alignof(KpWorkRec) == 16, "the fetch of
 struct KpWorkRecs {
     KpWorkRec *rec; int stride;  // 8 x stride records (work_rec_stride)
     int prior; const double *par, *xyz; const uint8_t *is3d;
+    int compact;                 // the caller is a compact stereo match: a record's zt is its workgroup's index in the selected launch, else the stream
 };
 
 // The set: the lists (v) and what is not per-keypoint state of them; all arrays but the kf_* ones live in one allocation.
@@ -94,8 +95,10 @@ struct slam_kpset {
     // without one.  Otherwise sel_idx[0 .. n_sel) are the selected streams ascending and sel_mask[s] is 0 / 1 (both device, one block of
     // the set's allocation; sel_host is the host's copy of the mask), staged through a pinned ring of 8 slots with an event each (made by
     // the first call that sets a selection), like `par`.  Not members of KpsetView: that struct is a kernel-argument block.
+    // sel_rank[s]: the rank of stream s among the selected ones (-1: unselected; kpset_select_rank) -- the member of a compact right batch that holds its
+    // build, read by the record-less prologue of a compact stereo match; the same block, between the table and the mask.
     int n_sel = KPSEL_ALL;
-    int *sel_idx = nullptr; uint8_t *sel_mask = nullptr;
+    int *sel_idx = nullptr, *sel_rank = nullptr; uint8_t *sel_mask = nullptr;
     uint8_t sel_host[128] = {};
     char *sel_pin = nullptr;
     hipEvent_t sel_ev[8] = {};
@@ -107,7 +110,8 @@ struct slam_kpset {
 int kpset_stage_params(slam_ctx *ctx, slam_kpset *ks, const double *host, size_t n, const double **dev_out);
 // `selected` (both): the caller is a key-frame seam and honours the set's selection -- only the selected streams' segments / lists; the caller has returned
 // before when no stream is selected (kpset_none_selected)
-struct KpMatchPrior { int prior; const double *par; };           // what a match hands the work list for the records: its prior mode and its staged parameters (device)
+// what a match hands the work list for the records: its prior mode, its staged parameters (device), whether its target batch is compact
+struct KpMatchPrior { int prior; const double *par; bool compact; };
 bool kpset_match_records();                                      // false under SLAMHIP_NO_MATCH_REC=1 (read once per process)
 int kpset_build_worklist(slam_ctx *ctx, slam_kpset *ks, int H, int W, bool selected = false, const KpMatchPrior *match = nullptr);   // H <= 0: slot order (no image, or an order would not pay)
 int kpset_compact(slam_ctx *ctx, slam_kpset *ks, int mode, const uint8_t *flags_dev, bool selected = false);

@@ -19,6 +19,8 @@
 // Selected form: only the selected streams' segments are laid back to back and ntot is their sum, so whatever walks the list (k_kpset_match,
 // both triangulation kernels) never sees a slot of an unselected stream.
 // R.rec != nullptr (the caller is a match): entry off + j also gets its work record (KpWorkRec, kpset.hpp; placed by work_rec_slot, work_order.hpp).
+// The record's target member zt is the stream -- or, for a compact stereo match (R.compact), SEL_SELF(s): the workgroup's index in the selected launch,
+// which is the stream's rank.
 __global__ __launch_bounds__(256) void SEL_NAME(k_kpset_worklist)(const int *count, int S, int cap, int *work, int *ntot, const double *yx, WorkOrder O, KpWorkRecs R SEL_ARG)
 {
     extern __shared__ unsigned long long s_word[];
@@ -28,9 +30,9 @@ __global__ __launch_bounds__(256) void SEL_NAME(k_kpset_worklist)(const int *cou
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) { off += __shfl_xor(off, m); t += __shfl_xor(t, m); }
     if (SEL_SELF(s) == 0 && tid == 0) ntot[0] = t;
-    const int n = count[s], per = work_rec_per(t);
+    const int n = count[s], per = work_rec_per(t), zt = R.compact ? SEL_SELF(s) : s;
     if (O.band <= 0 || n > O.pad) {                              // (n > pad cannot happen: n <= cap <= pad; it guards the LDS array)
-        for (int j = tid; j < n; j += 256) { work[off + j] = s * cap + j; if (R.rec) kp_write_rec(R, yx, O.H, O.W, off + j, per, s * cap + j, s); }
+        for (int j = tid; j < n; j += 256) { work[off + j] = s * cap + j; if (R.rec) kp_write_rec(R, yx, O.H, O.W, off + j, per, s * cap + j, s, zt); }
         return;
     }
     int P = 1;
@@ -51,7 +53,7 @@ __global__ __launch_bounds__(256) void SEL_NAME(k_kpset_worklist)(const int *cou
     for (int j = tid; j < n; j += 256) {
         const int q = s * cap + (int)(unsigned)s_word[j];
         work[off + j] = q;
-        if (R.rec) kp_write_rec(R, yx, O.H, O.W, off + j, per, q, s);        // a match follows: everything its prologue looks up, where its wave will read it
+        if (R.rec) kp_write_rec(R, yx, O.H, O.W, off + j, per, q, s, zt);   // a match follows: everything its prologue looks up, where its wave will read it
     }
 }
 

@@ -561,6 +561,7 @@ struct KpMatchArgs {
     const double *par;
     int H, W, stereo_mode; double epipolar;
     const KpWorkRec *rec; int rec_stride, use_rec;      // the work list's records (the set's region, always); use_rec 0 under SLAMHIP_NO_MATCH_REC: none were written, the record-less prologue
+    const int *rank;           // the record-less prologue's target member of stream s: rank[s] (a compact stereo match: the set's sel_rank), nullptr: s
 };
 // a wave-uniform record through the scalar data cache (constant address space: the records are written by the kernel before this one, never by
 // it): three 16-byte scalar loads into SGPRs, no VGPR and no vector-memory slot spent on values every lane shares
@@ -572,7 +573,7 @@ __device__ __forceinline__ KpWorkRec load_rec_uniform(const KpWorkRec *p)
     KpWorkRec r;
     r.py = __hiloint2double(a.y, a.x); r.px = __hiloint2double(a.w, a.z);
     r.pry = __hiloint2double(b.y, b.x); r.prx = __hiloint2double(b.w, b.z);
-    r.q = d.x; r.s = d.y; r.flags = d.z; r.pad = 0;
+    r.q = d.x; r.s = d.y; r.flags = d.z; r.zt = d.w;
     return r;
 }
 // The first record of a wave AND ntot in one round trip: the three scalar loads are issued back to back and waited for once.  Spelled as one
@@ -588,7 +589,7 @@ __device__ __forceinline__ KpWorkRec load_rec_and_ntot(const KpWorkRec *p, const
     KpWorkRec r;
     r.py = __hiloint2double(a[1], a[0]); r.px = __hiloint2double(a[3], a[2]);
     r.pry = __hiloint2double(a[5], a[4]); r.prx = __hiloint2double(a[7], a[6]);
-    r.q = d[0]; r.s = d[1]; r.flags = d[2]; r.pad = 0;
+    r.q = d[0]; r.s = d[1]; r.flags = d[2]; r.zt = d[3];
     return r;
 }
 template <int LK_MAXE, bool TOL>
@@ -608,19 +609,20 @@ __global__ __launch_bounds__(64) LK_OCC void k_kpset_match(KpMatchArgs M)
     for (int slotx = slot0; slotx < per; slotx += (int)(gridDim.x / LK_XCDS)) {
     const int idx = xcd * per + slotx;
     if (idx >= ntot) break;
-    size_t q; int s; double py, px, pry, prx; bool is3, inside;
+    size_t q; int s, zt; double py, px, pry, prx; bool is3, inside;
     // 2^-levels3d from its exponent (as lk_level's iscale): 1.0 / (1 << levels3d) bit for bit, which k_flow_match still spells as the quotient.
     // (For both prologues: the compiler hoists a quotient in the record-less branch in front of the loop, where every wave would pay for it.)
     const double scale3 = __hiloint2double((1023 - M.tune.levels3d) << 20, 0);
     if (M.use_rec) {
         // everything from the record: no work[], yx, is3d, xyz or par load, no division
         if (slotx != slot0) rc = load_rec_uniform(M.rec + ((size_t)xcd * M.rec_stride + slotx));   // later rounds (slotx < per <= rec_stride)
-        q = (size_t)rc.q; s = rc.s; py = rc.py; px = rc.px; pry = rc.pry; prx = rc.prx;
+        q = (size_t)rc.q; s = rc.s; zt = rc.zt; py = rc.py; px = rc.px; pry = rc.pry; prx = rc.prx;
         is3 = (rc.flags & KPREC_3D) != 0; inside = (rc.flags & KPREC_INSIDE) != 0;
     } else {
         // the record-less prologue (SLAMHIP_NO_MATCH_REC=1): ntot -> work[idx] -> yx, is3d, par -> xyz
         q = (size_t)M.work[idx];
         s = (int)(q / M.cap);
+        zt = M.rank ? M.rank[s] : s;
         py = M.yx[2 * q]; px = M.yx[2 * q + 1];
         is3 = M.is3d[q] != 0;
         pry = py; prx = px;
@@ -634,7 +636,7 @@ __global__ __launch_bounds__(64) LK_OCC void k_kpset_match(KpMatchArgs M)
         continue;
     }
     LKT(6);                                                      // the prologue: wave start (or the previous keypoint's end) to the keypoint's position, prior and decision in registers
-    const size_t offF = (size_t)s * M.zs_from, offT = (size_t)s * M.zs_to;
+    const size_t offF = (size_t)s * M.zs_from, offT = (size_t)zt * M.zs_to;       // the target's member: the stream, or its rank in a compact right batch
     double ny = nan(""), nx = nan("");
     bool ok = false;
     for (int att = is3 ? 0 : 1; att < 2 && !ok; att++) {                                             // mirrors k_flow_match's two attempts
@@ -683,10 +685,26 @@ static int match_check(slam_ctx *ctx, const slam_pyr *from, const slam_pyr *to, 
 }
 
 static int kpset_match(slam_ctx *ctx, slam_kpset *ks, const slam_pyr *from0, const slam_pyr *to0, const double *params,
-                       int prior, const LKTune &t, int stereo_mode, double epipolar, int n_bound)
+                       int prior, const LKTune &t, int stereo_mode, double epipolar, int n_bound, bool compact = false)
 {
     ARG_TRY(ctx, ctx != nullptr && ks != nullptr && from0 != nullptr && to0 != nullptr);
-    ARG_TRY(ctx, from0->batch_index == 0 && to0->batch_index == 0 && from0->batch_size >= ks->S && to0->batch_size >= ks->S);
+    // compact (slam_kpset_stereo_match_compact): to0 is member 0 of a COMPACT batch -- member r holds the build of the r-th selected stream.  The one
+    // guard against matching into another key-frame's pyramids: the mask the batch was last built for must be the set's selection now.  With no
+    // selection set the call IS the ordinary call (member s = stream s); a batch that still holds a compact build of some of the streams is refused too.
+    if (compact) {
+        const slam_pyr::Alloc *al = to0->alloc;
+        const bool all = ks->n_sel == KPSEL_ALL;
+        if (al->sel_S != 0 || !all) {
+            uint8_t cur[128];
+            for (int s = 0; s < ks->S; s++) cur[s] = all ? 1 : ks->sel_host[s];
+            if (!kpset_select_same(al->sel_S, al->sel_mask, ks->S, cur))
+                return slam_fail(ctx, SLAM_ERR_ARG,
+                                 "slam_kpset_stereo_match_compact: stale build -- the right batch %s, not for the set's current selection of %d streams",
+                                 al->sel_S ? "was last built compact for another selection" : "holds an ordinary (whole-batch) build", kpset_sel_streams(ks));
+        }
+        compact = !all;
+    }
+    ARG_TRY(ctx, from0->batch_index == 0 && to0->batch_index == 0 && from0->batch_size >= ks->S && to0->batch_size >= (compact ? ks->n_sel : ks->S));
     ARG_TRY(ctx, t.nonneg() && prior >= 0 && prior <= 2 && (prior == 0 || params != nullptr));
     int rc = match_check(ctx, from0, to0, t);
     if (rc) return rc;
@@ -704,10 +722,10 @@ static int kpset_match(slam_ctx *ctx, slam_kpset *ks, const slam_pyr *from0, con
     if (!params) { zero.assign((size_t)ks->S * KP_PAR, 0.0); for (int s = 0; s < ks->S; s++) { zero[KP_PAR * s + KP_PAR_CAM] = zero[KP_PAR * s + KP_PAR_CAM + 1] = 1.0; } params = zero.data(); }
     rc = kpset_stage_params(ctx, ks, params, (size_t)ks->S * KP_PAR, &M.par);
     if (rc) return rc;
-    const KpMatchPrior mp = {prior, M.par};
+    const KpMatchPrior mp = {prior, M.par, compact};
     rc = kpset_build_worklist(ctx, ks, M.H, M.W, selected, &mp);  // with every entry's work record, the match's whole prologue
     if (rc) return rc;
-    M.rec = ks->rec; M.rec_stride = ks->rec_stride; M.use_rec = kpset_match_records() ? 1 : 0;
+    M.rec = ks->rec; M.rec_stride = ks->rec_stride; M.use_rec = kpset_match_records() ? 1 : 0; M.rank = compact ? ks->sel_rank : nullptr;
     int nb = selected ? kpset_sel_grid_bound(ks, n_bound) : kpset_grid_bound(ks, n_bound);
     // (measurement knob) cap the launch: every wave then walks several keypoints (the kernel loops) instead of one wave being dispatched per keypoint
     static const int grid_cap = [] { const char *v = getenv("SLAMHIP_LK_GRID"); return v ? atoi(v) : 0; }();
@@ -738,6 +756,14 @@ extern "C" int slam_kpset_stereo_match(slam_ctx *ctx, slam_kpset *ks, const slam
                                        double max_distance, double epipolar_error, int n_bound)
 {
     return kpset_match(ctx, ks, left0, right0, params, prior, {pyramid_levels, pyramid_levels_3d, window, iterations, eig_thr, eps, max_distance}, 1, epipolar_error, n_bound);
+}
+// the same into a COMPACT right batch (slam_pyr_update_batch_sel_*): stream s's target is member rank(s) of right0's batch
+extern "C" int slam_kpset_stereo_match_compact(slam_ctx *ctx, slam_kpset *ks, const slam_pyr *left0, const slam_pyr *right0, const double *params, int prior,
+                                               int pyramid_levels, int pyramid_levels_3d, int window, int iterations, double eig_thr, double eps,
+                                               double max_distance, double epipolar_error, int n_bound)
+{
+    const LKTune t = {pyramid_levels, pyramid_levels_3d, window, iterations, eig_thr, eps, max_distance};
+    return kpset_match(ctx, ks, left0, right0, params, prior, t, 1, epipolar_error, n_bound, true);
 }
 
 #define LK_STAGE_MIN_POINTS 4096

@@ -22,6 +22,7 @@
 // checkpointed row filter, the segments' running sum and mv3 -- is in pyr_iir.hpp, one copy each; the kernels here move the samples.
 #include "common.hpp"
 #include "pyr_iir.hpp"
+#include "kpset_select.hpp"
 #include <cmath>
 #include <cstdlib>
 #include <mutex>
@@ -2685,12 +2686,48 @@ int slam_pyr_create_batch(slam_ctx *ctx, int H, int W, int pyramid_levels, int S
 }
 
 // pyrs[0..S) must be the members of one slam_pyr_create_batch call, in order; images: S device pointers to Float64 or (u8) 8-bit frames
+// the build of images[0 .. S) into members 0 .. S-1 of pyrs[0]'s batch (arguments checked by the callers).  S may be SMALLER than the batch: the build
+// kernels run on member ranges, and every scratch region of pyr_create_n is addressed per launch -- ck and rck by the launch's own grid (nlines,
+// lineid), tot through level_io from the build's S (3 S W_l doubles per level, back to back), xc / xf by 3 z0 (xseg - 1) slots, srctab by member --
+// so a build of a prefix of any length stays inside what the batch's own member count sized.  Routes, chunking and the graph key are those of an
+// S-member build.
+static int build_members(slam_ctx *ctx, slam_pyr *const *pyrs, const void *const *images, bool u8, int S, int mode, double sigma, int sync);
 static int update_batch(slam_ctx *ctx, slam_pyr *const *pyrs, const void *const *images, bool u8, int S, int mode, double sigma, int sync)
 {
     ARG_TRY(ctx, ctx != nullptr && pyrs != nullptr && images != nullptr && S >= 1 && S <= BATCH_MAX && pyr_mode_ok(mode, false) && sigma > 0);
     slam_pyr *p0 = pyrs[0];
     ARG_TRY(ctx, p0 != nullptr && p0->batch_index == 0 && p0->batch_size == S);
     for (int s = 0; s < S; s++) ARG_TRY(ctx, pyrs[s] != nullptr && pyrs[s]->alloc == p0->alloc && pyrs[s]->batch_index == s && images[s] != nullptr);
+    p0->alloc->sel_S = 0;                                        // member s is stream s again: no compact build in the batch
+    return build_members(ctx, pyrs, images, u8, S, mode, sigma, sync);
+}
+// Compact build: member r receives the build of the r-th selected stream (ascending); images is indexed by STREAM (S entries), the pointers of
+// unselected streams are never read.  The batch remembers the mask (Alloc::sel_mask), which slam_kpset_stereo_match_compact holds against the set's
+// selection.
+static int update_batch_sel(slam_ctx *ctx, slam_pyr *const *pyrs, int n_members, const void *const *images, bool u8, int S, const uint8_t *selected,
+                            int mode, double sigma, int sync, int *n_built)
+{
+    ARG_TRY(ctx, ctx != nullptr && pyrs != nullptr && images != nullptr && n_built != nullptr);
+    ARG_TRY(ctx, S >= 1 && S <= BATCH_MAX && n_members >= 1 && pyr_mode_ok(mode, false) && sigma > 0);
+    *n_built = 0;
+    slam_pyr *p0 = pyrs[0];
+    ARG_TRY(ctx, p0 != nullptr && p0->batch_index == 0 && p0->batch_size == n_members);
+    for (int r = 0; r < n_members; r++) ARG_TRY(ctx, pyrs[r] != nullptr && pyrs[r]->alloc == p0->alloc && pyrs[r]->batch_index == r);
+    int32_t idx[BATCH_MAX]; uint8_t norm[BATCH_MAX];
+    const int n_sel = kpset_select_streams(S, kpset_select_plan(S, selected, idx, norm));
+    if (n_sel > n_members)
+        return slam_fail(ctx, SLAM_ERR_ARG, "slam_pyr_update_batch_sel: %d streams selected but the batch has %d members (nothing was enqueued)",
+                         n_sel, n_members);
+    const void *compact[BATCH_MAX];
+    for (int r = 0; r < n_sel; r++) { compact[r] = images[idx[r]]; ARG_TRY(ctx, compact[r] != nullptr); }
+    memcpy(p0->alloc->sel_mask, norm, (size_t)S); p0->alloc->sel_S = S;
+    *n_built = n_sel;
+    if (n_sel == 0) return SLAM_OK;
+    return build_members(ctx, pyrs, compact, u8, n_sel, mode, sigma, sync);
+}
+static int build_members(slam_ctx *ctx, slam_pyr *const *pyrs, const void *const *images, bool u8, int S, int mode, double sigma, int sync)
+{
+    slam_pyr *p0 = pyrs[0];
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     ImgPtrs ip; ImgPtrsU8 ip8;
     for (int s = 0; s < BATCH_MAX; s++) { ip.p[s] = s < S ? (const double *)images[s] : nullptr; ip8.p[s] = (const unsigned char *)ip.p[s]; }
@@ -2708,6 +2745,17 @@ static int update_batch(slam_ctx *ctx, slam_pyr *const *pyrs, const void *const 
 int slam_pyr_update_batch_dev(slam_ctx *ctx, slam_pyr *const *pyrs, const double *const *images_dev, int S, int mode, double sigma, int sync) { return update_batch(ctx, pyrs, (const void *const *)images_dev, false, S, mode, sigma, sync); }
 // 8-bit frames already in HBM (column-major H x W bytes, as the KITTI reader decodes them): converted on the device
 int slam_pyr_update_batch_u8_dev(slam_ctx *ctx, slam_pyr *const *pyrs, const uint8_t *const *images_u8_dev, int S, int mode, double sigma, int sync) { return update_batch(ctx, pyrs, (const void *const *)images_u8_dev, true, S, mode, sigma, sync); }
+// the compact builds (slamhip.h): pyrs = the n_members members of one batch, images indexed by stream, member r <- the r-th selected stream
+int slam_pyr_update_batch_sel_dev(slam_ctx *ctx, slam_pyr *const *pyrs, int n_members, const double *const *images_dev, int S, const uint8_t *selected,
+                                  int mode, double sigma, int sync, int *n_built)
+{
+    return update_batch_sel(ctx, pyrs, n_members, (const void *const *)images_dev, false, S, selected, mode, sigma, sync, n_built);
+}
+int slam_pyr_update_batch_sel_u8_dev(slam_ctx *ctx, slam_pyr *const *pyrs, int n_members, const uint8_t *const *images_u8_dev, int S,
+                                     const uint8_t *selected, int mode, double sigma, int sync, int *n_built)
+{
+    return update_batch_sel(ctx, pyrs, n_members, (const void *const *)images_u8_dev, true, S, selected, mode, sigma, sync, n_built);
+}
 
 int slam_pyr_destroy(slam_pyr *p)
 {

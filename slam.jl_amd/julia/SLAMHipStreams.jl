@@ -25,6 +25,7 @@ module SLAMHipStreams
 
 import ..SLAMHip: LIB, ctx, check
 
+export update_selected!
 export PyramidBatch, FrameRing, KeypointSet, upload!, update!, flow_match!, stereo_match!, remove!, detect!, detect_describe!, describe_batch, keyframe!, select!, selection,
        triangulate!, triangulate_lens!, upload_stereo!, triangulate_temporal!, compute_pose_5pt!, compute_pose!, frame_stats, keyframe_required, counts, download, stream_params,
        KeyframeMap, add_keyframe!, gather, download_keyframe, download_points, reset!, filter_map!, remove_keyframe!, newest, enable_pixels!, keyframe_pixels
@@ -85,6 +86,22 @@ function update!(b::PyramidBatch, f::FrameRing; σ = 1.0, target_only::Bool = fa
         (Ptr{Cvoid}, Ptr{Ptr{Cvoid}}, Ptr{Ptr{UInt8}}, Cint, Cint, Cdouble, Cint),
         ctx(), hs, ps, length(hs), mode, Float64(σ), sync ? 1 : 0))
     b
+end
+
+"The COMPACT build (slamhip.h: slam_pyr_update_batch_sel_u8_dev): member r of `b` receives the build of the r-th selected stream of the ring,
+ascending; members at index n_sel or above keep their bytes.  selected: one entry per stream of the ring (Bool or UInt8; the `required` of
+keyframe_required as it is) or nothing = every stream.  `b` may have fewer members than the ring has streams; more selected streams than members is
+an error.  The batch remembers the mask: stereo_match!(...; compact = true) refuses it under any other selection.  Returns n_sel."
+function update_selected!(b::PyramidBatch, f::FrameRing, selected; σ = 1.0, target_only::Bool = false, tolerance::Bool = false, sync::Bool = false)
+    hs = b.handles; ps = f.ptrs
+    mode = (tolerance ? 3 : 1) | (target_only ? 16 : 0)
+    m = selected ≡ nothing ? nothing : UInt8[x != 0 ? 0x01 : 0x00 for x in selected]
+    m ≡ nothing || length(m) == f.S || error("expected $(f.S) mask entries")
+    n = Ref{Cint}(0)
+    GC.@preserve hs ps m check(ccall((:slam_pyr_update_batch_sel_u8_dev, LIB[]), Cint,
+        (Ptr{Cvoid}, Ptr{Ptr{Cvoid}}, Cint, Ptr{Ptr{UInt8}}, Cint, Ptr{UInt8}, Cint, Cdouble, Cint, Ref{Cint}),
+        ctx(), hs, length(hs), ps, f.S, m ≡ nothing ? C_NULL : pointer(m), mode, Float64(σ), sync ? 1 : 0, n))
+    Int(n[])
 end
 
 # ---- per-stream call parameters (slamhip.h: S x 32 doubles) ---------------------------------------------------------------------
@@ -149,7 +166,15 @@ end
 # optical_flow_matching!(..., true) + maybe_stereo_update! (map_manager.jl:579-590); params: the RIGHT camera
 function stereo_match!(k::KeypointSet, left::PyramidBatch, right::PyramidBatch, params::Matrix{Float64}; prior = 2, pyramid_levels = 3,
                        pyramid_levels_3d = 1, window = 9, iterations = 30, eig_thr = 1e-4, eps = 0.01, max_distance = 1.0,
-                       epipolar_error = 2.0, n_bound = 0)
+                       epipolar_error = 2.0, n_bound = 0, compact::Bool = false)
+    # compact: `right` is a compact batch (update_selected! under the set's current selection): stream s's target is its member rank(s)
+    if compact
+        GC.@preserve params check(ccall((:slam_kpset_stereo_match_compact, LIB[]), Cint,
+            (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Cint, Cint, Cint, Cint, Cint, Cdouble, Cdouble, Cdouble, Cdouble, Cint),
+            ctx(), k.h, left.handles[1], right.handles[1], params, prior, pyramid_levels, pyramid_levels_3d, window, iterations,
+            eig_thr, eps, max_distance, epipolar_error, n_bound))
+        return k
+    end
     GC.@preserve params check(ccall((:slam_kpset_stereo_match, LIB[]), Cint,
         (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Cint, Cint, Cint, Cint, Cint, Cdouble, Cdouble, Cdouble, Cdouble, Cint),
         ctx(), k.h, left.handles[1], right.handles[1], params, prior, pyramid_levels, pyramid_levels_3d, window, iterations,

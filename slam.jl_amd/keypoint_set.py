@@ -135,11 +135,15 @@ class KeypointSet:
         _check_match(c, rc)
 
     def stereo_match(self, left_batch, right_batch, params, stream_params_=None, prior=0, pyramid_levels_3d=1, iterations=30,
-                     epipolar_error=2.0, n_bound=0, ctx=None):
+                     epipolar_error=2.0, n_bound=0, ctx=None, compact=False):
+        """compact: right_batch is a COMPACT batch (PyramidBatch.update_selected_ under the set's current selection; it may have fewer members
+        than the set has streams): stream s's target is its member rank(s) (slam_kpset_stereo_match_compact).  A batch built for another
+        selection, or by an ordinary update_ since, raises."""
         c = ctx or self.ctx
         sp, sp_ptr = _sp_ptr(stream_params_)
-        rc = c.lib.slam_kpset_stereo_match(c.h, self.h, left_batch.pyramids[0].h, right_batch.pyramids[0].h, sp_ptr,
-                                           prior, *_tune(params, pyramid_levels_3d, iterations), float(epipolar_error), int(n_bound))
+        fn = c.lib.slam_kpset_stereo_match_compact if compact else c.lib.slam_kpset_stereo_match
+        rc = fn(c.h, self.h, left_batch.pyramids[0].h, right_batch.pyramids[0].h, sp_ptr,
+                prior, *_tune(params, pyramid_levels_3d, iterations), float(epipolar_error), int(n_bound))
         _check_match(c, rc)
 
     def remove(self, flags_dev_ptr, ctx=None):

@@ -260,6 +260,26 @@ class PyramidBatch:
         c.check(fn(c.h, self._handles, imgs, self.S, (3 if fast else 1) | (16 if target_only else 0), float(sigma), 1 if sync else 0))
         return self
 
+    def update_selected_(self, device_ptrs, selected, sigma=1.0, sync=True, fast=False, ctx=None, u8=False, target_only=False):
+        """The COMPACT build (slam_pyr_update_batch_sel_*): device_ptrs is indexed by STREAM (any length >= 1; entries of unselected streams are
+        never read and may be 0 / None), selected = one entry per stream, non-zero / True = selected, or None = every stream.  Member r of this
+        batch receives the build of the r-th selected stream, ascending; members at index n_sel or above keep their bytes.  The batch may have
+        fewer members than there are streams (PyramidBatch(..., S=k)); more selected streams than members raises.  The batch remembers the mask:
+        KeypointSet.stereo_match(..., compact=True) refuses it under any other selection.  Returns n_sel."""
+        c = ctx or self.ctx
+        n = len(device_ptrs)
+        imgs = (C.c_void_p * n)(*[C.c_void_p(int(p) if p else None) for p in device_ptrs])
+        m = None
+        if selected is not None:
+            m = np.ascontiguousarray(np.asarray(selected).reshape(-1) != 0, dtype=np.uint8)
+            if m.shape != (n,):
+                raise ValueError(f"update_selected_: {m.size} mask entries for {n} streams")
+        fn = c.lib.slam_pyr_update_batch_sel_u8_dev if u8 else c.lib.slam_pyr_update_batch_sel_dev
+        n_built = C.c_int(0)
+        c.check(fn(c.h, self._handles, self.S, imgs, n, L.ptr(m, L.u8p) if m is not None else None, (3 if fast else 1) | (16 if target_only else 0),
+                   float(sigma), 1 if sync else 0, C.byref(n_built)))
+        return n_built.value
+
 
 ROUTE_FIELDS = ("family", "cols", "rows", "resize", "cum", "rt_sl", "rt_ns", "dec", "slc32", "slc", "slr", "fuse_sq")
 ROUTE_ENUMS = {"family": ("FAM_NONE", "FAM_TARGET", "FAM_SEG", "FAM_TOLB", "FAM_EXACT"),
